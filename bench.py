@@ -15,6 +15,9 @@ so nothing is served from L2/MALL by repetition (1.66 GB of tables >> 256 MB).
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (HBM-bound
 gather: algorithmic 136 B/lookup = 8 id + 64 row read + 64 output write) and
 `cpu_baseline` (the oracle's C pipeline timed on the host cores, rank 0, N = 1).
+`ms_per_step` is the wall time of one of the `--steps` timed steps.  The inputs depend on the
+arguments only, so `--dump-outputs DIR` (what the last timed step computed, see dump_outputs) can
+be compared between two builds.
 
 Launching.  `python bench.py --gpus N` is enough: without WORLD_SIZE in the environment and
 N > 1 the script starts N ranks of itself on a free port (one process per GPU, RANK /
@@ -137,7 +140,14 @@ def parse_args():
   p.add_argument('--link-probe-mb', type=float, default=16.0,
                  help='N > 1: MB per peer of the equal-split alltoallv that measures the links '
                       'before the timed steps (0 disables it)')
-  return p.parse_args()
+  p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                 help='after the timed steps, write what their last step handed rank 0 (one fp32 '
+                      'array per column) as DIR/output_<column>.npy, at most 64 MB in all: see '
+                      'dump_outputs')
+  args = p.parse_args()
+  if args.steps < 1 or args.warmup < 0:
+    p.error('--steps must be at least 1 and --warmup at least 0')
+  return args
 
 
 def _free_port():
@@ -419,6 +429,26 @@ def backward_secondary(args, hb, tables, batches, device, timed_steps, steps=20,
   out['bytes_formula'] = ('n*8 + S*4D + [emit] u*(4D+8) + [step] u*2*4D (+ (S+1)*4 per ragged '
                           'column); SURVEY 8(d) bytes_bwd, u = n_unique of the call')
   return out
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(directory, outs):
+  """The per-column outputs of the last timed step as DIR/output_<c>.npy (float32, [rows, dim]),
+  so that two builds can be compared output for output.  When all of them would exceed
+  DUMP_LIMIT_BYTES, every column keeps the same rows: the sorted first draw of
+  RandomState(0).choice(batch, k, replace=False), k the most that fit."""
+  batch, dim = outs[0].shape
+  k = min(batch, (DUMP_LIMIT_BYTES - 1024 * len(outs)) // (len(outs) * dim * 4))  # (npy headers)
+  rows = None
+  if k < batch:
+    rows = torch.from_numpy(np.sort(np.random.RandomState(0).choice(batch, k, replace=False)))
+    rows = rows.to(outs[0].device)
+  os.makedirs(directory, exist_ok=True)
+  for c, o in enumerate(outs):
+    arr = (o if rows is None else o.index_select(0, rows)).float().cpu().numpy()
+    np.save(os.path.join(directory, f'output_{c:02d}.npy'), arr)
 
 
 def load_traffic(config_key):
@@ -732,6 +762,9 @@ def main():
   if world > 1 or args.sharded:
     set_form('inline')
   elapsed, gpu_ms = timed_steps(step, args.steps, args.warmup)
+  # (before anything behind the headline reuses the output buffers or steps the tables)
+  if args.dump_outputs and rank == 0:
+    dump_outputs(args.dump_outputs, outs if world == 1 and not args.sharded else sh_outs)
   probe, groups_probe = None, None
   best_form = 'inline' if (world > 1 or args.sharded) else None
 
@@ -853,6 +886,8 @@ def main():
         el2, ms2 = timed_steps(step, args.steps, args.warmup)
         if el2 < elapsed:
           best_form = fastest
+          if args.dump_outputs and rank == 0:     # (the timed steps `value` now comes from)
+            dump_outputs(args.dump_outputs, sh_outs)
           if rank == 0:
             v2, ms_step2, launch2, achieved2 = headline_fields(el2, ms2)
             result['value'], result['ms_per_step'] = v2, ms_step2

@@ -10,7 +10,9 @@ Sources (data only, no reference source text is stored):
     
   * murmur3 vectors produced by compiling the reference's own header
       hybridbackend/common/murmur3.cu.h:32-77 (oracle/_ref, `make -C oracle ref`);
-    when /root/reference is mounted this script re-generates them from that build.
+    when /root/reference is mounted this script re-generates them from that build, together with
+    murmur3_sample.json (2000 random keys), so that the check against that build needs no
+    reference tree.
   * a small values+row_splits parquet stand-in for config 1 (generated here).
   * tf115_semantics.json: TensorFlow 1.15 is the third-party dependency the fp32 rows R1, R7-R10
     of the path live in (pin: reference README.md:44-48, Makefile:19); its sources are absent from
@@ -58,6 +60,13 @@ def main():
     hashes = [int(h) for h in oracle.murmur3_hash32(keys)]
     src = 'oracle restatement (reference tree not mounted)'
   dump('murmur3.json', {'source': src, 'seed': 0, 'keys': keys, 'hash32': hashes})
+  # 2000 random keys (RandomState(1), the first 2000 of 20000 int64) answered by the same build:
+  # only written from that build, never from the oracle it pins
+  if ref is not None:
+    sample = np.random.RandomState(1).randint(-2**63, 2**63 - 1, size=20000, dtype=np.int64)[:2000]
+    dump('murmur3_sample.json', {'source': src, 'seed': 1,
+                                 'keys': [int(k) for k in sample],
+                                 'hash32': [int(ref.ref_murmur3_hash32_i64(int(k))) for k in sample]})
 
   # --- partition KATs derived from the CPU functor ---
   dump('partition.json', {

@@ -95,3 +95,31 @@ def test_not_enough_gpus_is_a_fast_json_error():
   assert r.returncode != 0
   line = _last_json(r.stdout)
   assert line['value'] is None and 'only' in line['error'] and line['n_gpus'] == 8
+
+
+def test_dump_outputs_is_a_fixed_sample_within_64_mb(tmp_path):
+  """--dump-outputs: one fp32 file per column; outputs larger than 64 MB in all are cut to the
+  same seeded rows of every column, the same rows in every run."""
+  sys.path.insert(0, ROOT)
+  import numpy as np
+  import torch
+  import bench
+  g = torch.Generator()
+  g.manual_seed(0)
+  outs = [torch.rand(65536, 16, generator=g) for _ in range(26)]   # the headline's 109 MB
+  for d in ('a', 'b'):
+    bench.dump_outputs(str(tmp_path / d), outs)
+  names = sorted(os.listdir(tmp_path / 'a'))
+  assert names == [f'output_{c:02d}.npy' for c in range(26)]
+  assert sum(os.path.getsize(tmp_path / 'a' / n) for n in names) <= 64e6
+  first = np.load(tmp_path / 'a' / names[0])
+  assert first.dtype == np.float32 and first.shape[1] == 16 and first.shape[0] > 32768
+  rows = np.sort(np.random.RandomState(0).choice(65536, first.shape[0], replace=False))
+  for c, n in enumerate(names):
+    got = np.load(tmp_path / 'a' / n)
+    np.testing.assert_equal(got, outs[c].numpy()[rows])
+    np.testing.assert_equal(np.load(tmp_path / 'b' / n), got)
+  small = [torch.rand(100, 16, generator=g) for _ in range(3)]        # fits: written whole
+  bench.dump_outputs(str(tmp_path / 'c'), small)
+  for c in range(3):
+    np.testing.assert_equal(np.load(tmp_path / 'c' / f'output_{c:02d}.npy'), small[c].numpy())
