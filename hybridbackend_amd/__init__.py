@@ -10,4 +10,4 @@ from hybridbackend_amd import training
 from hybridbackend_amd._lib import HbkError
 from hybridbackend_amd._lib import InvalidArgumentError
 
-__version__ = '0.1.0'
+__version__ = '0.2.0'

@@ -42,7 +42,8 @@ class LookupColumn(C.Structure):
               ('combiner', C.c_int32), ('out', C.c_void_p),
               ('run_start', C.c_void_p), ('run_base', C.c_void_p),
               ('n_runs', C.c_int32), ('out_stride', C.c_int32),
-              ('hot_rows', C.c_int32), ('half_io', C.c_int32), ('out_slots', C.c_void_p)]
+              ('hot_rows', C.c_int32), ('half_io', C.c_int32), ('out_slots', C.c_void_p),
+              ('id_weights', C.c_void_p)]   # (ctypes zero-fills: NULL = unweighted)
 
 
 class LookupGradColumn(C.Structure):
@@ -55,7 +56,8 @@ class LookupGradColumn(C.Structure):
               ('unique_rows', C.c_void_p), ('grad_rows', C.c_void_p),
               ('n_unique', C.c_void_p), ('run_start', C.c_void_p), ('run_ids', C.c_void_p),
               ('run_grads', C.c_void_p), ('n_runs', C.c_int32), ('grad_stride', C.c_int32),
-              ('accum', C.c_void_p), ('table_pitch', C.c_int32), ('flags', C.c_int32)]
+              ('accum', C.c_void_p), ('table_pitch', C.c_int32), ('flags', C.c_int32),
+              ('id_weights', C.c_void_p)]
 
 
 class ShardedColumn(C.Structure):
@@ -71,7 +73,7 @@ class StitchGradColumn(C.Structure):
               ('index', C.c_void_p), ('row_splits', C.c_void_p), ('n_segments', C.c_int64),
               ('grad_out', C.c_void_p), ('grad_rows', C.c_void_p),
               ('run_start', C.c_void_p), ('run_base', C.c_void_p), ('n_runs', C.c_int32),
-              ('grad_stride', C.c_int32)]
+              ('grad_stride', C.c_int32), ('id_weights', C.c_void_p)]
 
 
 _lib = None
@@ -140,6 +142,7 @@ def _declare(l):
     'hbk_sharded_destroy': (C.c_int, [vp]),
     'hbk_sharded_set_hot_rows': (C.c_int, [vp, vp]),
     'hbk_sharded_lookup_fwd': (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
+    'hbk_sharded_lookup_fwd_weighted': (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     'hbk_sharded_prefetch_on': (C.c_int, [vp, vp, vp, vp]),
     'hbk_sharded_lookup_fwd_begin': (C.c_int, [vp, vp, vp, vp, vp, vp]),
     'hbk_sharded_lookup_fwd_end': (C.c_int, [vp, vp, vp, vp]),

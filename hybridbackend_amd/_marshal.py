@@ -141,3 +141,28 @@ def vector_pass(tensors, dtypes):
   return ptrs, lens, dt
 
 
+
+
+def weight_ptrs(sp_weights, ids):
+  """Per column the address of the per-id weights (``sp_weights``: None, or one fp32 device vector
+  of ``ids[c].numel()`` weights or None per column; 0 = unweighted), checked."""
+  n = len(ids)
+  if sp_weights is None:
+    return [0] * n
+  from hybridbackend_amd import _lib   # pylint: disable=import-outside-toplevel
+  if len(sp_weights) != n:
+    raise _lib.InvalidArgumentError(
+      _lib.INVALID_ARGUMENT, f'expected {n} sp_weights entries (None for an unweighted column), '
+      f'got {len(sp_weights)}')
+  ptrs = []
+  for c, w in enumerate(sp_weights):
+    if w is None:
+      ptrs.append(0)
+      continue
+    _lib.require_device_tensor(w, 'sp_weights')
+    if w.dtype is not torch.float32 or w.dim() != 1 or w.shape[0] != ids[c].shape[0]:
+      raise _lib.InvalidArgumentError(
+        _lib.INVALID_ARGUMENT, f'sp_weights {c} must be an fp32 vector of {ids[c].shape[0]} weights '
+        '(one per id)')
+    ptrs.append(w.data_ptr())
+  return ptrs

@@ -3035,8 +3035,10 @@ struct SArgs {
 static_assert(sizeof(SArgs) <= 20480, "kernarg budget");
 static_assert(kMaxStitchCols <= 2 * kWave, "two lanes-worth of columns in the stitch search");
 
-template <typename V>
-__device__ inline void stitch_segments(const SCol& c, int64_t seg0) {
+// WGT (weighted columns, hbk_stitch_grad_column_t.id_weights): grad_rows[index[j]] = t_j -- the
+// segment's gradient row divided by W_s (mean) or sqrtf(Q_s) (sqrtn), zero for a zero divisor, times w_j
+template <typename V, bool WGT = false>
+__device__ inline void stitch_segments(const SCol& c, int64_t seg0, const float* weights = nullptr) {
   constexpr int VE = sizeof(V) / 4;
   const int lane = lane_id();
   const int rpi = kWave >> c.lpr_log2;
@@ -3058,7 +3060,17 @@ __device__ inline void stitch_segments(const SCol& c, int64_t seg0) {
     V g = __builtin_nontemporal_load(
         reinterpret_cast<const V*>(c.grad_out + s * (int64_t)c.grad_stride + (int64_t)sub * VE));
     const int32_t n = end - beg;
-    if (c.combiner == HBK_COMBINER_MEAN) {
+    if (WGT) {
+      if (c.combiner != HBK_COMBINER_SUM) {
+        float wsum = 0.f;
+        for (int32_t j = beg; j < end; ++j) {
+          const float w = weights[j];
+          wsum = wsum + (c.combiner == HBK_COMBINER_SQRTN ? w * w : w);
+        }
+        const float div = c.combiner == HBK_COMBINER_MEAN ? wsum : sqrtf(wsum);
+        g = div != 0.f ? g / div : zero_v<V>();
+      }
+    } else if (c.combiner == HBK_COMBINER_MEAN) {
       g = g / (float)n;
     } else if (c.combiner == HBK_COMBINER_SQRTN) {
       g = g / sqrtf((float)n);
@@ -3071,7 +3083,9 @@ __device__ inline void stitch_segments(const SCol& c, int64_t seg0) {
         while (k + 1 < c.n_runs && c.run_start[k + 1] <= r) ++k;
         off = c.run_base[k] + (r - c.run_start[k]) * c.dim;
       }
-      *reinterpret_cast<V*>(c.grad_rows + off + (int64_t)sub * VE) = g;
+      V t = g;
+      if (WGT) t = g * weights[j];
+      *reinterpret_cast<V*>(c.grad_rows + off + (int64_t)sub * VE) = t;
     }
   }
 }
@@ -3096,6 +3110,228 @@ __global__ __launch_bounds__(kBlock) void stitch_bwd_kernel(const SArgs a) {
   } else {
     stitch_segments<float>(c, seg0);
   }
+}
+
+// the weighted columns of a stitch call: the same search and tiles, the weights beside SArgs
+struct SWeights {
+  const float* w[kMaxStitchCols];
+};
+
+__global__ __launch_bounds__(kBlock) void stitch_bwd_weighted_kernel(const SArgs a, const SWeights w) {
+  int ci;
+  {
+    const int l = (int)threadIdx.x & (kWave - 1);
+    const int t0 = l < a.n_cols ? a.tile0[l] : 0x7fffffff;
+    const int t1 = l + kWave < a.n_cols ? a.tile0[l + kWave] : 0x7fffffff;
+    ci = (int)__builtin_popcountll(__ballot(t0 <= (int)blockIdx.x)) +
+         (int)__builtin_popcountll(__ballot(t1 <= (int)blockIdx.x)) - 1;
+    ci = __builtin_amdgcn_readfirstlane(ci);
+  }
+  const SCol& c = a.col[ci];
+  const int64_t tile = (int)blockIdx.x - c.tile0;
+  const int rpi = kWave >> c.lpr_log2;
+  const int64_t seg0 = (tile * kWavesPerBlock + (threadIdx.x >> 6)) * (int64_t)(kIters * rpi);
+  if (seg0 >= c.n_seg) return;
+  if (c.vec4) {
+    stitch_segments<f32x4, true>(c, seg0, w.w[ci]);
+  } else {
+    stitch_segments<float, true>(c, seg0, w.w[ci]);
+  }
+}
+
+// ---- weighted columns of the backward (hbk_lookup_grad_column_t.id_weights) -------------------------
+// The scale stage at id granularity: t_j = (grad_out[s] / W_s) * w_j (mean), (grad_out[s] / sqrtf(Q_s))
+// * w_j (sqrtn), grad_out[s] * w_j (sum) for every id into an [n_ids, dim] buffer of the workspace
+// (zero for the ids of a zero-divisor segment; W_s / Q_s sum the weights of the segment's VALID ids in
+// id order, as the forward does).  Behind it the column is one of one id per segment, SUM combiner,
+// grad_out = that buffer: every reduce, split, row-sorted, dense and deterministic job and the fused
+// optimizer steps take it as they are.
+constexpr int kMaxTermCols = 64;
+constexpr int kTermIters = 4;   // segments per lane group and wave
+
+struct TCol {
+  const float* grad_out;
+  const void* ids;
+  const int32_t* splits;   // NULL: one id per segment
+  const float* weights;
+  float* terms;            // [n_ids, dim]
+  IdMap map;
+  int64_t n_seg;
+  int32_t grad_stride;
+  int32_t dim;
+  int32_t chunks;
+  uint8_t lpr_log2, ids64, combiner, vec4;
+};
+
+struct TArgs {
+  int32_t n_cols;
+  int32_t tile0[kMaxTermCols];
+  TCol col[kMaxTermCols];
+};
+static_assert(kMaxTermCols <= kWave, "one lane's worth of columns in the term search");
+
+// One lane group per segment.  The segment's ids and weights are read cooperatively (lane `sub` of the
+// group owns id j0 + sub: one coalesced load each, as in the forward) and handed to the group's lanes
+// by shuffles, so W_s / Q_s is still summed in id order -- bit-equal to the forward's -- without every
+// lane repeating every load.  Every lane of a group runs the same loops (the shuffles read whole groups).
+template <typename V>
+__device__ inline void weight_terms(const TCol& c, int64_t seg0) {
+  constexpr int VE = sizeof(V) / 4;
+  const int lane = lane_id();
+  const int lpr = 1 << c.lpr_log2;
+  const int rpi = kWave >> c.lpr_log2;
+  const int sub = lane & (lpr - 1);
+  const int grp = lane >> c.lpr_log2;
+  const int grp_lane0 = grp << c.lpr_log2;
+  const bool live = sub < c.chunks;
+  for (int it = 0; it < kTermIters; ++it) {
+    const int64_t s = seg0 + (int64_t)it * rpi + grp;
+    int32_t beg = 0, end = 0;
+    if (s < c.n_seg) {
+      beg = (int32_t)s;
+      end = (int32_t)s + 1;
+      if (c.splits != nullptr) {
+        beg = c.splits[s];
+        end = c.splits[s + 1];
+      }
+    }
+    V g = zero_v<V>();
+    if (live && end > beg) {
+      g = __builtin_nontemporal_load(
+          reinterpret_cast<const V*>(c.grad_out + s * (int64_t)c.grad_stride + (int64_t)sub * VE));
+    }
+    if (c.combiner != HBK_COMBINER_SUM) {
+      float wsum = 0.f;
+      for (int32_t j0 = beg; __any(j0 < end); j0 += lpr) {
+        float mine = 0.f;
+        int ok = 0;
+        if (j0 + sub < end) {
+          ok = id_to_row(c.map, load_id(c.ids, c.ids64, j0 + sub)) != kNoRow;
+          const float w = c.weights[j0 + sub];
+          mine = c.combiner == HBK_COMBINER_SQRTN ? w * w : w;
+        }
+        for (int t = 0; t < lpr; ++t) {
+          const float v = __shfl(mine, grp_lane0 + t, kWave);
+          const int okt = __shfl(ok, grp_lane0 + t, kWave);
+          if (j0 + t < end && okt) wsum = wsum + v;   // (in id order; invalid rows add no weight)
+        }
+      }
+      const float div = c.combiner == HBK_COMBINER_MEAN ? wsum : sqrtf(wsum);
+      g = div != 0.f ? g / div : zero_v<V>();
+    }
+    for (int32_t j0 = beg; __any(j0 < end); j0 += lpr) {
+      const float mine = j0 + sub < end ? c.weights[j0 + sub] : 0.f;
+      for (int t = 0; t < lpr; ++t) {
+        const float w = __shfl(mine, grp_lane0 + t, kWave);
+        if (live && j0 + t < end) {
+          *reinterpret_cast<V*>(c.terms + (int64_t)(j0 + t) * c.dim + (int64_t)sub * VE) = g * w;
+        }
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void bwd_weight_terms_kernel(const TArgs a) {
+  const int l = lane_id();
+  const int t0 = l < a.n_cols ? a.tile0[l] : 0x7fffffff;
+  int ci = (int)__builtin_popcountll(__ballot(t0 <= (int)blockIdx.x)) - 1;
+  ci = __builtin_amdgcn_readfirstlane(ci);
+  const TCol& c = a.col[ci];
+  const int64_t tile = (int)blockIdx.x - a.tile0[ci];
+  const int rpi = kWave >> c.lpr_log2;
+  const int64_t seg0 = (tile * kWavesPerBlock + (threadIdx.x >> 6)) * (int64_t)(kTermIters * rpi);
+  if (seg0 >= c.n_seg) return;
+  if (c.vec4) {
+    weight_terms<f32x4>(c, seg0);
+  } else {
+    weight_terms<float>(c, seg0);
+  }
+}
+
+inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+bool any_weighted(int32_t n_cols, const hbk_lookup_grad_column_t* cols) {
+  for (int32_t c = 0; c < n_cols; ++c) {
+    if (cols[c].id_weights != nullptr) return true;
+  }
+  return false;
+}
+
+// workspace bytes of the term buffers: 16-byte aligned each, + 16 to align the first one
+size_t weight_terms_bytes(int32_t n_cols, const hbk_lookup_grad_column_t* cols) {
+  size_t b = 0;
+  for (int32_t c = 0; c < n_cols; ++c) {
+    const hbk_lookup_grad_column_t& h = cols[c];
+    if (h.id_weights != nullptr && h.n_ids > 0) b += align16((size_t)h.n_ids * h.dim * 4);
+  }
+  return b == 0 ? 0 : b + 16;
+}
+
+// the columns as the stages behind the term pass see them (terms == NULL: the workspace query)
+void weighted_as_sum(int32_t n_cols, const hbk_lookup_grad_column_t* cols, char* terms,
+                     std::vector<hbk_lookup_grad_column_t>* out) {
+  out->assign(cols, cols + n_cols);
+  size_t off = 0;
+  for (hbk_lookup_grad_column_t& h : *out) {
+    if (h.id_weights == nullptr) continue;
+    if (h.n_segments == 0) h.n_ids = 0;   // ids in no segment: nothing to reduce
+    h.row_splits = nullptr;
+    h.n_segments = h.n_ids;
+    h.combiner = HBK_COMBINER_SUM;
+    h.grad_out = nullptr;
+    h.grad_stride = 0;
+    h.id_weights = nullptr;
+    if (h.n_ids > 0) {
+      if (terms != nullptr) h.grad_out = reinterpret_cast<const float*>(terms + off);
+      off += align16((size_t)h.n_ids * h.dim * 4);
+    }
+  }
+}
+
+int launch_weight_terms(int32_t n_cols, const hbk_lookup_grad_column_t* cols,
+                        const std::vector<hbk_lookup_grad_column_t>& as_sum, hipStream_t stream) {
+  int32_t c0 = 0;
+  while (c0 < n_cols) {
+    TArgs args;
+    int32_t k = 0;
+    int64_t tiles = 0;
+    while (c0 < n_cols && k < kMaxTermCols) {
+      const int32_t ci = c0++;
+      const hbk_lookup_grad_column_t& h = cols[ci];
+      if (h.id_weights == nullptr || h.n_ids == 0 || h.n_segments == 0) continue;
+      TCol& d = args.col[k];
+      d.grad_out = h.grad_out;
+      d.ids = h.ids;
+      d.splits = h.row_splits;
+      d.weights = h.id_weights;
+      d.terms = const_cast<float*>(as_sum[ci].grad_out);
+      d.map = make_idmap(h.bucket, h.divisor, h.rows);
+      d.n_seg = h.n_segments;
+      d.grad_stride = h.grad_stride > 0 ? h.grad_stride : h.dim;
+      d.dim = h.dim;
+      RowShape shape;
+      HBK_REQUIRE(make_rowshape(h.dim,
+                                (uintptr_t)h.grad_out | (uintptr_t)d.terms |
+                                    ((uintptr_t)(uint32_t)d.grad_stride * 4),
+                                &shape),
+                  "group_lookup_bwd: dim %d needs more than 64 lanes per row", h.dim);
+      d.chunks = shape.chunks;
+      d.lpr_log2 = shape.lpr_log2;
+      d.vec4 = shape.vec4;
+      d.ids64 = h.ids_dtype == HBK_INT64;
+      d.combiner = (uint8_t)h.combiner;
+      const int64_t per_block = kWavesPerBlock * kTermIters * (int64_t)(kWave >> d.lpr_log2);
+      args.tile0[k] = (int32_t)tiles;
+      tiles += (h.n_segments + per_block - 1) / per_block;
+      HBK_REQUIRE(tiles < (1ll << 31), "group_lookup_bwd: grid too large");
+      ++k;
+    }
+    if (k == 0) continue;
+    args.n_cols = k;
+    hipLaunchKernelGGL(bwd_weight_terms_kernel, dim3((unsigned)tiles), dim3(kBlock), 0, stream, args);
+    HBK_HIP_OK(hipGetLastError());
+  }
+  return HBK_OK;
 }
 
 // ---- host-side planning ------------------------------------------------------------------------
@@ -3476,6 +3712,12 @@ extern "C" int hbk_debug_bwd_trace(unsigned long long* out, int reset) {
 extern "C" size_t hbk_group_lookup_bwd_workspace_bytes(int32_t n_cols,
                                                        const hbk_lookup_grad_column_t* cols) {
   if (n_cols <= 0 || cols == nullptr) return 0;
+  if (hbk::any_weighted(n_cols, cols)) {   // the term buffers, then the columns behind them
+    std::vector<hbk_lookup_grad_column_t> as_sum;
+    hbk::weighted_as_sum(n_cols, cols, nullptr, &as_sum);
+    return hbk::weight_terms_bytes(n_cols, cols) +
+           hbk_group_lookup_bwd_workspace_bytes(n_cols, as_sum.data());
+  }
   if (hbk::any_deterministic(n_cols, cols)) {
     std::vector<hbk_lookup_grad_column_t> fast, slow, plain;
     hbk::det_split(n_cols, cols, &fast, &slow, &plain);
@@ -3612,6 +3854,9 @@ extern "C" int hbk_group_lookup_bwd_apply(int32_t n_cols, const hbk_lookup_grad_
                                   h.run_grads),
                 "group_lookup_bwd: column %d: segmented inputs need run tables and no "
                 "row_splits", c);
+    HBK_REQUIRE(h.id_weights == nullptr || h.n_runs == 0,
+                "group_lookup_bwd: column %d: id_weights cannot be combined with segmented inputs "
+                "(run_*: the owner-side reduce is never weighted)", c);
   }
   const size_t need = hbk_group_lookup_bwd_workspace_bytes(n_cols, cols);
   HBK_REQUIRE(need == 0 || (workspace != nullptr && workspace_bytes >= need),
@@ -3622,6 +3867,19 @@ extern "C" int hbk_group_lookup_bwd_apply(int32_t n_cols, const hbk_lookup_grad_
   {
     const int rc = sync_check("group_lookup_bwd", stream);
     if (rc != HBK_OK) return rc;
+  }
+  // weighted columns: their gradient terms per id into the head of the workspace, then the call
+  // over the columns as SUM columns of one id per segment
+  if (any_weighted(n_cols, cols)) {
+    const size_t tb = weight_terms_bytes(n_cols, cols);
+    char* terms = reinterpret_cast<char*>(align16(reinterpret_cast<uintptr_t>(workspace)));
+    std::vector<hbk_lookup_grad_column_t> as_sum;
+    weighted_as_sum(n_cols, cols, tb == 0 ? nullptr : terms, &as_sum);
+    const int rc = launch_weight_terms(n_cols, cols, as_sum, stream);
+    if (rc != HBK_OK) return rc;
+    return hbk_group_lookup_bwd_apply(n_cols, as_sum.data(), apply, apply_lr,
+                                      tb == 0 ? workspace : reinterpret_cast<char*>(workspace) + tb,
+                                      workspace_bytes - tb, stream_);
   }
   // option bwd_deterministic: the in-order forms -- row-sorted jobs where they fit (1), the sort + walk
   // of lookup_bwd_det.h for the other columns (and for all of them under 2)
@@ -4190,64 +4448,75 @@ extern "C" int hbk_group_stitch_bwd(int32_t n_cols, const hbk_stitch_grad_column
   HBK_REQUIRE(n_cols >= 0, "group_stitch_bwd: n_cols must be >= 0, got %d", n_cols);
   if (n_cols == 0) return HBK_OK;
   HBK_REQUIRE(cols != nullptr, "group_stitch_bwd: cols is NULL");
-  int32_t c0 = 0;
-  while (c0 < n_cols) {
-    SArgs args;
-    int32_t k = 0;
-    int64_t t_seg = 0;
-    while (c0 < n_cols && k < kMaxStitchCols) {
-      const int32_t ci = c0++;
-      const hbk_stitch_grad_column_t& h = cols[ci];
-      HBK_REQUIRE(h.dim >= 1, "group_stitch_bwd: column %d: dim must be >= 1", ci);
-      HBK_REQUIRE(h.n_ids >= 0 && h.n_segments >= 0 && h.n_ids < (1ll << 31),
-                  "group_stitch_bwd: column %d: bad size", ci);
-      HBK_REQUIRE(h.combiner >= HBK_COMBINER_SUM && h.combiner <= HBK_COMBINER_SQRTN,
-                  "group_stitch_bwd: column %d: unknown combiner %d", ci, h.combiner);
-      HBK_REQUIRE(h.row_splits != nullptr || h.n_segments == h.n_ids,
-                  "group_stitch_bwd: column %d: n_segments must equal n_ids when row_splits "
-                  "is NULL", ci);
-      if (h.n_ids == 0 || h.n_segments == 0) continue;
-      HBK_REQUIRE(h.index && h.grad_out && h.grad_rows,
-                  "group_stitch_bwd: column %d: NULL buffer", ci);
-      SCol& d = args.col[k];
-      d.grad_out = h.grad_out;
-      d.splits = h.row_splits;
-      d.index = h.index;
-      d.grad_rows = h.grad_rows;
-      HBK_REQUIRE(h.n_runs >= 0 && (h.n_runs == 0 || (h.run_start && h.run_base)),
-                  "group_stitch_bwd: column %d: bad run tables", ci);
-      d.run_start = h.run_start;
-      d.run_base = h.run_base;
-      d.n_runs = h.n_runs;
-      HBK_REQUIRE(h.grad_stride == 0 || h.grad_stride >= h.dim,
-                  "group_stitch_bwd: column %d: bad grad_stride %d", ci, h.grad_stride);
-      d.grad_stride = h.grad_stride > 0 ? h.grad_stride : h.dim;
-      d.n_seg = h.n_segments;
-      d.dim = h.dim;
-      RowShape shape;
-      HBK_REQUIRE(make_rowshape(h.dim,
-                                (uintptr_t)h.grad_out | (uintptr_t)h.grad_rows |
-                                    ((uintptr_t)(uint32_t)h.grad_stride * 4),
-                                &shape),
-                  "group_stitch_bwd: dim %d needs more than 64 lanes per row", h.dim);
-      d.chunks = shape.chunks;
-      d.lpr_log2 = shape.lpr_log2;
-      d.vec4 = shape.vec4;
-      d.combiner = (uint8_t)h.combiner;
-      d.pad_ = 0;
-      const int64_t rpi = kWave >> d.lpr_log2;
-      const int64_t per_block = kWavesPerBlock * kIters * rpi;
-      d.tile0 = (int32_t)t_seg;
-      args.tile0[k] = (int32_t)t_seg;
-      t_seg += (h.n_segments + per_block - 1) / per_block;
-      HBK_REQUIRE(t_seg < (1ll << 31), "group_stitch_bwd: grid too large");
-      ++k;
+  // pass 0 the unweighted columns, pass 1 the weighted ones (their own kernel)
+  for (int pass = 0; pass < 2; ++pass) {
+    int32_t c0 = 0;
+    while (c0 < n_cols) {
+      SArgs args;
+      SWeights wts;
+      int32_t k = 0;
+      int64_t t_seg = 0;
+      while (c0 < n_cols && k < kMaxStitchCols) {
+        const int32_t ci = c0++;
+        const hbk_stitch_grad_column_t& h = cols[ci];
+        if ((h.id_weights != nullptr) != (pass == 1)) continue;
+        HBK_REQUIRE(h.dim >= 1, "group_stitch_bwd: column %d: dim must be >= 1", ci);
+        HBK_REQUIRE(h.n_ids >= 0 && h.n_segments >= 0 && h.n_ids < (1ll << 31),
+                    "group_stitch_bwd: column %d: bad size", ci);
+        HBK_REQUIRE(h.combiner >= HBK_COMBINER_SUM && h.combiner <= HBK_COMBINER_SQRTN,
+                    "group_stitch_bwd: column %d: unknown combiner %d", ci, h.combiner);
+        HBK_REQUIRE(h.row_splits != nullptr || h.n_segments == h.n_ids,
+                    "group_stitch_bwd: column %d: n_segments must equal n_ids when row_splits "
+                    "is NULL", ci);
+        if (h.n_ids == 0 || h.n_segments == 0) continue;
+        HBK_REQUIRE(h.index && h.grad_out && h.grad_rows,
+                    "group_stitch_bwd: column %d: NULL buffer", ci);
+        SCol& d = args.col[k];
+        d.grad_out = h.grad_out;
+        d.splits = h.row_splits;
+        d.index = h.index;
+        d.grad_rows = h.grad_rows;
+        HBK_REQUIRE(h.n_runs >= 0 && (h.n_runs == 0 || (h.run_start && h.run_base)),
+                    "group_stitch_bwd: column %d: bad run tables", ci);
+        d.run_start = h.run_start;
+        d.run_base = h.run_base;
+        d.n_runs = h.n_runs;
+        HBK_REQUIRE(h.grad_stride == 0 || h.grad_stride >= h.dim,
+                    "group_stitch_bwd: column %d: bad grad_stride %d", ci, h.grad_stride);
+        d.grad_stride = h.grad_stride > 0 ? h.grad_stride : h.dim;
+        d.n_seg = h.n_segments;
+        d.dim = h.dim;
+        RowShape shape;
+        HBK_REQUIRE(make_rowshape(h.dim,
+                                  (uintptr_t)h.grad_out | (uintptr_t)h.grad_rows |
+                                      ((uintptr_t)(uint32_t)h.grad_stride * 4),
+                                  &shape),
+                    "group_stitch_bwd: dim %d needs more than 64 lanes per row", h.dim);
+        d.chunks = shape.chunks;
+        d.lpr_log2 = shape.lpr_log2;
+        d.vec4 = shape.vec4;
+        d.combiner = (uint8_t)h.combiner;
+        d.pad_ = 0;
+        wts.w[k] = h.id_weights;
+        const int64_t rpi = kWave >> d.lpr_log2;
+        const int64_t per_block = kWavesPerBlock * kIters * rpi;
+        d.tile0 = (int32_t)t_seg;
+        args.tile0[k] = (int32_t)t_seg;
+        t_seg += (h.n_segments + per_block - 1) / per_block;
+        HBK_REQUIRE(t_seg < (1ll << 31), "group_stitch_bwd: grid too large");
+        ++k;
+      }
+      if (k == 0) continue;
+      args.n_cols = k;
+      args.pad_ = 0;
+      if (pass == 0) {
+        hipLaunchKernelGGL(stitch_bwd_kernel, dim3((unsigned)t_seg), dim3(kBlock), 0, stream, args);
+      } else {
+        hipLaunchKernelGGL(stitch_bwd_weighted_kernel, dim3((unsigned)t_seg), dim3(kBlock), 0, stream, args,
+                           wts);
+      }
+      HBK_HIP_OK(hipGetLastError());
     }
-    if (k == 0) continue;
-    args.n_cols = k;
-    args.pad_ = 0;
-    hipLaunchKernelGGL(stitch_bwd_kernel, dim3((unsigned)t_seg), dim3(kBlock), 0, stream, args);
-    HBK_HIP_OK(hipGetLastError());
   }
   return HBK_OK;
 }

@@ -49,8 +49,11 @@ struct ColArg {
   int32_t out_stride;  // floats between output rows (>= dim)
   const int64_t* run_start;
   const int64_t* run_base;
-  const int32_t* out_slots;   // != NULL: segment s is written to row out_slots[s] of `out` (a permutation
-                              // scatter: the owner gather of the sharded step's p2p form)
+  union {   // (never both: the host refuses weights with output slots; the layout stays 0.1.0's)
+    const int32_t* out_slots;   // != NULL: segment s is written to row out_slots[s] of `out` (a permutation
+                                // scatter: the owner gather of the sharded step's p2p form)
+    const float* weights;       // the weighted kernels: one fp32 weight per id
+  };
 };
 
 // float offset of logical row r inside the table
@@ -112,7 +115,10 @@ static_assert(sizeof(LookupArgs) <= 24576, "kernarg budget");
 
 // ---------------------------------------------------------------------------------
 // one id per segment (Criteo scalar columns): out[s,:] = table[row(ids[s]),:]
-template <typename V, int U, bool RUNS, int HALF, bool SLOT = false, bool D16 = false>
+// WGT (weighted instantiations): out[s,:] = w_s e  (sum), (w_s e) / w_s  (mean), (w_s e) / sqrtf(w_s w_s)
+// (sqrtn); a zero divisor or an invalid row gives a zero row.  The weight is read beside the id (one
+// coalesced 4-byte load per segment) and handed to the row's lanes with the same shuffle.
+template <typename V, int U, bool RUNS, int HALF, bool SLOT = false, bool D16 = false, bool WGT = false>
 __device__ inline void gather_rows(const ColArg& c, int64_t wave_row0) {
   constexpr int VE = sizeof(V) / 4;
   const int lane = lane_id();
@@ -125,16 +131,19 @@ __device__ inline void gather_rows(const ColArg& c, int64_t wave_row0) {
   // ids: slot q (0 <= q < U*rpi) lives in register q>>6 of lane q&63
   uint64_t rowreg[U];
   int32_t slotreg[U];   // SLOT: where the segment's row goes (read with the id, handed over like it)
+  float wreg[U];        // WGT: the segment's weight (likewise)
   const int n_slots = U * rpi;
 #pragma unroll
   for (int k = 0; k < U; ++k) {
     rowreg[k] = kNoRow;
     slotreg[k] = 0;
+    wreg[k] = 0.f;
     const int q = k * kWave + lane;
     const int64_t s = wave_row0 + q;
     if (q < n_slots && s < n_seg) {
       rowreg[k] = id_to_row(c.map, load_id(c.ids, D16 ? 1 : c.ids64, s));
       if (SLOT) slotreg[k] = __builtin_nontemporal_load(c.out_slots + s);
+      if (WGT) wreg[k] = __builtin_nontemporal_load(c.weights + s);
     }
   }
 
@@ -151,6 +160,21 @@ __device__ inline void gather_rows(const ColArg& c, int64_t wave_row0) {
     v[u] = zero_v<V>();
     if (live && r != kNoRow) {
       v[u] = load_row_chunk<V, HALF>(c.table, row_offset<RUNS>(c, r) + (uint64_t)sub * VE);
+    }
+    if (WGT) {
+      float w = wreg[0];
+#pragma unroll
+      for (int kk = 1; kk < U; ++kk) w = (k == kk) ? wreg[kk] : w;
+      w = __shfl(w, (q0 & (kWave - 1)) + grp, kWave);
+      const float div = c.combiner == HBK_COMBINER_MEAN    ? w
+                        : c.combiner == HBK_COMBINER_SQRTN ? sqrtf(w * w)
+                                                           : 1.f;
+      if (r != kNoRow && div != 0.f) {
+        v[u] = v[u] * w;
+        if (c.combiner != HBK_COMBINER_SUM) v[u] = v[u] / div;
+      } else {
+        v[u] = zero_v<V>();
+      }
     }
   }
 #pragma unroll
@@ -173,7 +197,11 @@ __device__ inline void gather_rows(const ColArg& c, int64_t wave_row0) {
 
 // ---------------------------------------------------------------------------------
 // ragged segments (row_splits): out[s,:] = combine_j table[row(ids[j]),:], in order of j
-template <typename V, bool RUNS, int HALF>
+// WGT: every row times its id's weight, the divisor W_s = sum w_j (mean) or Q_s = sum w_j w_j (sqrtn)
+// accumulated in the same loop over the ids of valid rows; a zero divisor gives a zero row.  The
+// weights are read beside the ids (lane `sub` of the group owns weight j0 + sub) and handed to the
+// row's lanes with the same shuffle as the row.
+template <typename V, bool RUNS, int HALF, bool WGT = false>
 __device__ inline void combine_segments(const ColArg& c, int64_t wave_seg0) {
   constexpr int VE = sizeof(V) / 4;
   const int lane = lane_id();
@@ -194,24 +222,38 @@ __device__ inline void combine_segments(const ColArg& c, int64_t wave_seg0) {
       end = c.splits[s + 1];
     }
     V acc = zero_v<V>();
+    float wsum = 0.f;   // WGT: W_s or Q_s
     // group-cooperative id fetch: lane `sub` of the group owns id j0 + sub
     int32_t j0 = beg;
     uint64_t myrow = kNoRow;
-    if (j0 + sub < end) myrow = id_to_row(c.map, load_id(c.ids, c.ids64, j0 + sub));
+    float myw = 0.f;
+    if (j0 + sub < end) {
+      myrow = id_to_row(c.map, load_id(c.ids, c.ids64, j0 + sub));
+      if (WGT) myw = __builtin_nontemporal_load(c.weights + j0 + sub);
+    }
     while (__any(j0 < end)) {
       // prefetch the next chunk of ids while this chunk's rows are in flight
       uint64_t nextrow = kNoRow;
+      float nextw = 0.f;
       const int32_t j1 = j0 + lpr;
-      if (j1 + sub < end) nextrow = id_to_row(c.map, load_id(c.ids, c.ids64, j1 + sub));
+      if (j1 + sub < end) {
+        nextrow = id_to_row(c.map, load_id(c.ids, c.ids64, j1 + sub));
+        if (WGT) nextw = __builtin_nontemporal_load(c.weights + j1 + sub);
+      }
       const int32_t cnt = end - j0;  // ids of this group still to add (may be <= 0)
       for (int t0 = 0; t0 < lpr; t0 += 4) {
         V v[4];
         bool p[4];
+        float w[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
           const int tt = t0 + t;
           const uint64_t r = shfl_u64(myrow, grp_lane0 + (tt & (lpr - 1)));
           p[t] = tt < lpr && tt < cnt;
+          if (WGT) {
+            w[t] = __shfl(myw, grp_lane0 + (tt & (lpr - 1)), kWave);
+            p[t] = p[t] && r != kNoRow;   // an invalid row adds neither term nor weight
+          }
           v[t] = zero_v<V>();
           if (p[t] && live && r != kNoRow) {
             v[t] = load_row_chunk<V, HALF>(c.table, row_offset<RUNS>(c, r) + (uint64_t)sub * VE);
@@ -219,14 +261,27 @@ __device__ inline void combine_segments(const ColArg& c, int64_t wave_seg0) {
         }
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-          if (p[t]) acc = acc + v[t];
+          if (WGT) {
+            if (p[t]) {
+              acc = acc + v[t] * w[t];
+              wsum = wsum + (c.combiner == HBK_COMBINER_SQRTN ? w[t] * w[t] : w[t]);
+            }
+          } else {
+            if (p[t]) acc = acc + v[t];
+          }
         }
       }
       myrow = nextrow;
+      if (WGT) myw = nextw;
       j0 = j1;
     }
     const int32_t n = end - beg;
-    if (n > 0 && c.combiner == HBK_COMBINER_MEAN) {
+    if (WGT) {
+      if (c.combiner != HBK_COMBINER_SUM) {
+        const float div = c.combiner == HBK_COMBINER_MEAN ? wsum : sqrtf(wsum);
+        acc = div != 0.f ? acc / div : zero_v<V>();
+      }
+    } else if (n > 0 && c.combiner == HBK_COMBINER_MEAN) {
       acc = acc / (float)n;
     } else if (n > 0 && c.combiner == HBK_COMBINER_SQRTN) {
       acc = acc / sqrtf((float)n);
@@ -273,6 +328,40 @@ __global__ __launch_bounds__(kBlock) void group_lookup_fwd_kernel(const LookupAr
     const int64_t seg0 = (tile * kWavesPerBlock + wave) * (int64_t)(kSegIters * rpi);
     if (seg0 >= c.n_seg) return;
     combine_segments<V, RUNS, HALF>(c, seg0);
+  }
+}
+
+// The weighted columns (hbk_lookup_column_t.id_weights): the same tiles and column search as
+// group_lookup_fwd_kernel, rows times their ids' weights (gather_rows / combine_segments, WGT).
+template <bool CSR, typename V, bool RUNS, int HALF>
+__global__ __launch_bounds__(kBlock) void group_lookup_fwd_weighted_kernel(const LookupArgs a) {
+  const int b = xcd_contiguous((int)blockIdx.x, (int)gridDim.x, a.xcd);
+  int ci;
+  int64_t tile;
+  if (a.interleave) {
+    ci = b % a.n_cols;
+    tile = b / a.n_cols;
+  } else {
+    const int lane = (int)threadIdx.x & (kWave - 1);
+    const int n = a.n_cols;
+    const int t0 = lane < n ? a.tile_start[lane] : 0x7fffffff;
+    const int t1 = lane + kWave < n ? a.tile_start[lane + kWave] : 0x7fffffff;
+    ci = (int)__builtin_popcountll(__ballot(t0 <= b)) +
+         (int)__builtin_popcountll(__ballot(t1 <= b)) - 1;
+    ci = __builtin_amdgcn_readfirstlane(ci);
+    tile = b - a.tile_start[ci];
+  }
+  const ColArg& c = a.col[ci];
+  const int wave = (int)(threadIdx.x >> 6);
+  const int rpi = kWave >> c.lpr_log2;
+  if (!CSR) {
+    const int64_t row0 = (tile * kWavesPerBlock + wave) * (int64_t)(kU * rpi);
+    if (row0 >= c.n_seg) return;
+    gather_rows<V, kU, RUNS, HALF, false, false, true>(c, row0);
+  } else {
+    const int64_t seg0 = (tile * kWavesPerBlock + wave) * (int64_t)(kSegIters * rpi);
+    if (seg0 >= c.n_seg) return;
+    combine_segments<V, RUNS, HALF, true>(c, seg0);
   }
 }
 
@@ -439,7 +528,31 @@ void launch_kind(const LookupArgs& args, unsigned tiles, hipStream_t stream) {
                      stream, args);
 }
 
+template <bool CSR, typename V, bool RUNS, int HALF = 0>
+void launch_weighted(const LookupArgs& args, unsigned tiles, hipStream_t stream) {
+  hipLaunchKernelGGL((group_lookup_fwd_weighted_kernel<CSR, V, RUNS, HALF>), dim3(tiles), dim3(kBlock), 0,
+                     stream, args);
+}
+
+constexpr int kWeightedKind = 40;   // + the column's kind (bits 0, 1, 2 and 4): weighted columns
+
 void launch_by_kind(int kind, const LookupArgs& args, unsigned tiles, hipStream_t stream) {
+  if (kind >= kWeightedKind) {
+    switch (kind - kWeightedKind) {
+      case 0: launch_weighted<false, f32x4, false>(args, tiles, stream); return;
+      case 1: launch_weighted<true, f32x4, false>(args, tiles, stream); return;
+      case 2: launch_weighted<false, float, false>(args, tiles, stream); return;
+      case 3: launch_weighted<true, float, false>(args, tiles, stream); return;
+      case 4: launch_weighted<false, f32x4, true>(args, tiles, stream); return;
+      case 5: launch_weighted<true, f32x4, true>(args, tiles, stream); return;
+      case 6: launch_weighted<false, float, true>(args, tiles, stream); return;
+      case 7: launch_weighted<true, float, true>(args, tiles, stream); return;
+      case 20: launch_weighted<false, f32x4, true, 2>(args, tiles, stream); return;   // half table
+      case 21: launch_weighted<true, f32x4, true, 2>(args, tiles, stream); return;
+      case 22: launch_weighted<false, float, true, 2>(args, tiles, stream); return;
+      default: launch_weighted<true, float, true, 2>(args, tiles, stream); return;
+    }
+  }
   if (kind == 39) {  // kind 0 with every column 16 floats wide and int64 ids (the headline's shape): constants
     hipLaunchKernelGGL((group_lookup_fwd_kernel<false, f32x4, false, 0, false, true>), dim3(tiles), dim3(kBlock), 0,
                        stream, args);
@@ -513,6 +626,9 @@ extern "C" int hbk_group_lookup_fwd(int32_t n_cols, const hbk_lookup_column_t* c
                     (h.row_splits == nullptr && h.n_runs == 0 && h.half_io == 0),
                 "group_lookup_fwd: column %d: out_slots needs one id per segment, a plain table and "
                 "fp32 rows", c);
+    HBK_REQUIRE(h.id_weights == nullptr || (h.out_slots == nullptr && h.half_io != HBK_LOOKUP_OUT_HALF),
+                "group_lookup_fwd: column %d: id_weights cannot be combined with out_slots or "
+                "HBK_LOOKUP_OUT_HALF (the owner gather is never weighted)", c);
   }
 
   const int hot_mode = options().fwd_hot_rows;
@@ -554,10 +670,12 @@ extern "C" int hbk_group_lookup_fwd(int32_t n_cols, const hbk_lookup_column_t* c
         shape.chunks == 4) {
       col_kind = 39;
     }
+    // weighted columns: their own instantiations, never the hot-row or D16 kernels
+    if (h.id_weights != nullptr) col_kind = kWeightedKind + (col_kind == 8 || col_kind == 39 ? 0 : col_kind);
     cls[c].kind = col_kind;
     kinds_present |= 1ull << col_kind;
   }
-  for (int kind = 0; kind < 40; ++kind) {
+  for (int kind = 0; kind < 64; ++kind) {
     if (((kinds_present >> kind) & 1ull) == 0ull) continue;
     int32_t c0 = 0;
     while (c0 < n_cols) {
@@ -594,7 +712,11 @@ extern "C" int hbk_group_lookup_fwd(int32_t n_cols, const hbk_lookup_column_t* c
         d.out_stride = h.out_stride > 0 ? h.out_stride : h.dim;
         d.run_start = h.run_start;
         d.run_base = h.run_base;
-        d.out_slots = h.out_slots;
+        if (kind >= kWeightedKind) {
+          d.weights = h.id_weights;
+        } else {
+          d.out_slots = h.out_slots;
+        }
         const int64_t rpi = kWave >> d.lpr_log2;
         const int64_t per_block =
             col_kind == 8 ? kHotTile : kWavesPerBlock * rpi * (h.row_splits ? kSegIters : kU);

@@ -118,7 +118,7 @@ extern "C" int hbk_sync_check_stream(hbk_stream_t stream) {
   return hbk::sync_check("sync_check_stream", reinterpret_cast<hipStream_t>(stream));
 }
 
-extern "C" const char* hbk_version(void) { return "hbk 0.1.0 gfx950"; }
+extern "C" const char* hbk_version(void) { return "hbk 0.2.0 gfx950"; }
 
 // One slab for N tables, each at a 2 MB-aligned offset: the allocation policy that was fastest in
 // every run of tools/placement_probe (profiles/r05_placement.txt: -2 % on config 4's forward, 2.1 x

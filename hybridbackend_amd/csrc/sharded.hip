@@ -536,6 +536,8 @@ struct hbk_sharded {
   std::vector<int64_t> n_sent;       // ids of column c this rank put on the wire (= n_ids, or its
                                      // distinct ids when the column is deduplicated)
   std::vector<const int32_t*> row_splits;
+  std::vector<const float*> id_weights;   // [N] per-id weights of the last forward (NULL: unweighted):
+                                          // the stitch applies them, the backward's stitch too
   std::vector<int32_t> send_sizes;   // S [N][W] rows this rank requests from owner q, column c
   std::vector<int32_t> recv_sizes;   // R [W][N] rows requester q asked this rank for, column c
   std::vector<hbk::Group> groups;        // column groups of the last forward (reused backward)
@@ -1153,6 +1155,7 @@ extern "C" int hbk_sharded_lookup_fwd_begin(hbk_sharded_t p, const int64_t* cons
   p->n_ids.assign(n_ids, n_ids + N);
   p->n_seg.resize(N);
   p->row_splits.resize(N);
+  p->id_weights.assign((size_t)N, nullptr);   // (hbk_sharded_lookup_fwd_weighted sets them after this)
   for (int c = 0; c < N; ++c) {
     HBK_REQUIRE(n_ids[c] >= 0 && n_ids[c] < (1ll << 31), "sharded_lookup_fwd: bad n_ids[%d]", c);
     p->row_splits[c] = row_splits ? row_splits[c] : nullptr;
@@ -1620,6 +1623,7 @@ extern "C" int hbk_sharded_lookup_fwd_end(hbk_sharded_t p, float* const* outs,
       h.run_start = d_start + (size_t)cc * W;
       h.run_base = d_base + (size_t)cc * W;
       h.n_runs = W;
+      h.id_weights = p->id_weights[cc];   // the weights are applied here, on the requester
     }
     rc = hbk_group_lookup_fwd(ng, v.data(), stream_);
     if (rc != HBK_OK) return rc;
@@ -1642,6 +1646,37 @@ extern "C" int hbk_sharded_lookup_fwd(hbk_sharded_t p, const int64_t* const* ids
   HBK_REQUIRE(outs != nullptr, "sharded_lookup_fwd: NULL argument array");
   const int rc = hbk_sharded_lookup_fwd_begin(p, ids, n_ids, row_splits, n_segments, stream_);
   if (rc != HBK_OK) return rc;
+  return hbk_sharded_lookup_fwd_end(p, outs, out_strides, stream_);
+}
+
+// Weights never cross the wire: the owners gather unweighted rows, the requester's stitch (an
+// hbk_group_lookup_fwd over the received rows) multiplies, and the backward's stitch keeps them.
+extern "C" int hbk_sharded_lookup_fwd_weighted(hbk_sharded_t p, const int64_t* const* ids,
+                                               const int64_t* n_ids,
+                                               const int32_t* const* row_splits,
+                                               const int64_t* n_segments,
+                                               const float* const* id_weights, float* const* outs,
+                                               const int32_t* out_strides, hbk_stream_t stream_) {
+  using namespace hbk;
+  HBK_REQUIRE(p != nullptr && outs != nullptr, "sharded_lookup_fwd: NULL argument");
+  bool weighted = false;
+  for (int c = 0; id_weights != nullptr && c < p->N; ++c) weighted = weighted || id_weights[c] != nullptr;
+  // A column's stitch sees the received rows only, not whether its owner found an id inside its
+  // shard: with a bucket every id is (ids are taken modulo it, the shards cover it); without one an
+  // out-of-range id would still add its weight to W_s / Q_s.  Such columns are refused.
+  for (int c = 0; weighted && c < p->N; ++c) {
+    HBK_REQUIRE(id_weights[c] == nullptr || p->cols[c].bucket > 0,
+                "sharded_lookup_fwd_weighted: column %d: id_weights need a bucket (hbk_sharded_column_t."
+                "bucket > 0) so that every id names a row of its owner's shard", c);
+  }
+  // (the same on every rank: the bind is collective; refused before any exchange)
+  if (weighted && p->p2p_bound) {
+    return fail(HBK_UNIMPLEMENTED, "sharded_lookup_fwd_weighted: the p2p form (hbk_sharded_p2p_bind) has "
+                "no stitch to apply id_weights in");
+  }
+  int rc = hbk_sharded_lookup_fwd_begin(p, ids, n_ids, row_splits, n_segments, stream_);
+  if (rc != HBK_OK) return rc;
+  for (int c = 0; weighted && c < p->N; ++c) p->id_weights[c] = id_weights[c];
   return hbk_sharded_lookup_fwd_end(p, outs, out_strides, stream_);
 }
 
@@ -1788,6 +1823,7 @@ extern "C" int hbk_sharded_lookup_bwd_apply(hbk_sharded_t p, const float* const*
         h.unique_rows = reinterpret_cast<int64_t*>(tmp + t_rows[cc]);
         h.grad_rows = reinterpret_cast<float*>(tmp + t_vals[cc]);
         h.n_unique = tmp_nu + cc;
+        h.id_weights = p->id_weights[cc];   // duplicate positions sum their WEIGHTED terms
         dv.push_back(h);
         int32_t* idx32 = reinterpret_cast<int32_t*>(tmp + t_rows[cc] + (size_t)u * 8);
         narrow.push_back(make_seg(h.unique_rows, idx32, u * 8, 1));
@@ -1834,6 +1870,7 @@ extern "C" int hbk_sharded_lookup_bwd_apply(hbk_sharded_t p, const float* const*
       h.run_start = d_start + (size_t)cc * W;
       h.run_base = d_base + (size_t)cc * W;
       h.n_runs = W;
+      h.id_weights = p->id_weights[cc];
     }
     rc = hbk_group_stitch_bwd(ng, v.data(), stream_);
     if (rc != HBK_OK) return rc;

@@ -8,6 +8,10 @@ at once, what the reference builds per column out of stock TF ops:
 
 Ragged id lists use the values + row_splits layout HybridBackend's own data path
 produces (hybridbackend/tensorflow/data/dataframe.py:366-376).
+
+``sp_weights`` (per column None or an fp32 device vector with one weight per id) gives
+``embedding_lookup_sparse``'s weighted form: sum ``w e``, mean ``sum w e / sum w``, sqrtn
+``sum w e / sqrt(sum w^2)``; a segment whose divisor is 0 gives a zero row (include/hbk.h).
 """
 import ctypes as C
 
@@ -91,10 +95,11 @@ class GroupLookup:
   def __len__(self):
     return len(self.tables)
 
-  def bind(self, ids, row_splits=None, outs=None, lazy=False):
+  def bind(self, ids, row_splits=None, outs=None, lazy=False, sp_weights=None):
     """Point the column descriptors at this step's inputs/outputs; returns outs -- a LIST of the
     per-column ``[segments, dim]`` tensors (``lazy=True`` with ``outs=None``: a lazy sequence whose
-    views are made when indexed, for callers that hand the result on untouched)."""
+    views are made when indexed, for callers that hand the result on untouched).  ``sp_weights``:
+    None, or per column None or the fp32 ``[n_ids]`` weights of its ids."""
     # the descriptors change: what __call__ remembers of its last tensors no longer describes them
     # (__call__ sets its key again after a bind of its own)
     self._call_key = None
@@ -102,6 +107,7 @@ class GroupLookup:
     if len(ids) != n:
       raise _lib.InvalidArgumentError(
         _lib.INVALID_ARGUMENT, f'expected {n} id tensors, got {len(ids)}')
+    self._bind_weights(ids, sp_weights)
     fast = self._bind_fresh(ids, row_splits, outs, lazy=lazy) if n else None
     if fast is not None:
       return fast
@@ -146,7 +152,14 @@ class GroupLookup:
     self._keep = (list(ids), list(row_splits), outs)
     return outs
 
-  def bind_block(self, ids, row_splits, block, offsets):
+  def _bind_weights(self, ids, sp_weights):
+    """Every bind writes the weight field of every column (0 = unweighted): a descriptor never keeps
+    the weights of an earlier step."""
+    if len(ids):
+      self._cols_np['id_weights'] = _marshal.weight_ptrs(sp_weights, ids)
+    self._keep_weights = list(sp_weights) if sp_weights is not None else None
+
+  def bind_block(self, ids, row_splits, block, offsets, sp_weights=None):
     """bind() with every column's output a column block of ONE ``[segments, pitch]`` fp32 tensor
     (``block``; column c starts at float ``offsets[c]`` of every row): what DenseFeatures writes.
     No per-column views are made -- the addresses are arithmetic.  Returns False when the inputs
@@ -159,6 +172,7 @@ class GroupLookup:
     if (n == 0 or block.dtype is not torch.float32 or not block.is_cuda or block.dim() != 2 or
         block.stride(1) != 1 or block.stride(0) % 4 != 0):
       return False
+    self._bind_weights(ids, sp_weights)
     n_rows, pitch = block.shape[0], block.stride(0)
     if len(offsets) != n or any(offsets[c] < 0 or offsets[c] + self._dims[c] > block.shape[1]
                                 for c in range(n)):
@@ -268,24 +282,27 @@ class GroupLookup:
       s = C.c_void_p(stream.cuda_stream)
     _lib.check(self._lib.hbk_group_lookup_fwd(len(self.tables), self._cols, s))
 
-  def __call__(self, ids, row_splits=None, outs=None, lazy=False):
+  def __call__(self, ids, row_splits=None, outs=None, lazy=False, sp_weights=None):
     # handed the SAME tensors as the call before (resident buffers refilled in place, caller-owned
     # outputs): the descriptors are still right, the call is one foreign call
     if outs is not None:
-      tensors = list(ids) + [x for x in (row_splits or []) if x is not None] + list(outs)
-      # the key keeps WHICH column a row_splits tensor belongs to (None positions included)
+      tensors = list(ids) + [x for x in (row_splits or []) if x is not None] + list(outs) + \
+          [x for x in (sp_weights or []) if x is not None]
+      # the key keeps WHICH column a row_splits / weights tensor belongs to (None positions included)
       key = (tuple(id(t) for t in ids),
              tuple(None if x is None else id(x) for x in (row_splits or ())),
-             tuple(id(t) for t in outs))
+             tuple(id(t) for t in outs),
+             tuple(None if x is None else id(x) for x in (sp_weights or ())))
       cached = getattr(self, '_call_key', None)
       if cached is not None and cached[0] == key and all(
           t.data_ptr() == q and t.numel() == m for t, (q, m) in zip(tensors, cached[1])):
         self.launch()
         return cached[2]
-      outs = self.bind(ids, row_splits, outs)
+      outs = self.bind(ids, row_splits, outs, sp_weights=sp_weights)
       self._call_key = (key, [(t.data_ptr(), t.numel()) for t in tensors], outs)
     else:
-      outs = self.bind(ids, row_splits, outs, lazy=lazy)   # (bind clears the remembered call)
+      # (bind clears the remembered call)
+      outs = self.bind(ids, row_splits, outs, lazy=lazy, sp_weights=sp_weights)
     self.launch()
     return outs
 
@@ -314,9 +331,10 @@ class _LazyOutputs(_marshal.collections.abc.Sequence):
 
 
 def group_lookup(tables, ids, row_splits=None, buckets=None, combiners='sum', divisor=1,
-                 outs=None):
+                 outs=None, sp_weights=None):
   """Functional form: one fused launch over N columns; returns the list of outputs."""
-  return GroupLookup(tables, buckets, combiners, divisor)(ids, row_splits, outs)
+  return GroupLookup(tables, buckets, combiners, divisor)(ids, row_splits, outs,
+                                                          sp_weights=sp_weights)
 
 
 class GroupLookupGrad:
@@ -454,13 +472,14 @@ class GroupLookupGrad:
     return True
 
   def __call__(self, ids, grads, row_splits=None, apply_lr=0.0, optimizer='sgd', emit=True,
-               grad_block=None):
+               grad_block=None, sp_weights=None):
     """Returns per column ``(unique_rows int64[n_ids], grad_rows f32[n_ids, dim],
     n_unique int32[1])``; only the first ``n_unique`` rows are meaningful, in unspecified
     order (device-side count: no host sync here).  The result buffers belong to this object
     and are reused by the next call with the same id counts.  ``emit=False`` (with ``apply_lr``):
     step only -- the rows are stepped, no IndexedSlices are written; only ``n_unique`` of each
-    returned triple is meaningful."""
+    returned triple is meaningful.  ``sp_weights``: the forward's per-id weights (per column None
+    or fp32 ``[n_ids]``); no gradient is produced for them."""
     if not emit and apply_lr == 0.0:
       raise _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT, 'emit=False needs apply_lr != 0')
     n = len(self.lookup)
@@ -551,11 +570,15 @@ class GroupLookupGrad:
       self._bound_key = (key, [(t.data_ptr(), t.numel()) for t in tensors])
     if grad_block is not None:
       grads = grad_block[0]
+    # written on every call (whatever path bound the rest): a descriptor never keeps the weights of
+    # an earlier step; the workspace query below counts their gradient-term buffers
+    if n:
+      self._cols_np['id_weights'] = _marshal.weight_ptrs(sp_weights, ids)
     need = self._lib.hbk_group_lookup_bwd_workspace_bytes(n, self._cols)   # (depends on options too)
     if self._ws is None or self._ws.numel() < need:
       self._ws = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
     self._ws_bound = self._ws       # (launch(): the workspace this binding was sized for)
-    self._keep = (ids, grads, row_splits)
+    self._keep = (ids, grads, row_splits, sp_weights)
     if optimizer not in ('sgd', 'adagrad'):
       raise _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT, "optimizer must be 'sgd' or 'adagrad'")
     if optimizer == 'adagrad' and apply_lr != 0.0 and self.accums is None:

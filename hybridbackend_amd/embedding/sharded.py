@@ -52,7 +52,10 @@ _PLAN_LOCK = threading.RLock()
 
 class _BoundStep:
   """One step's tensors marshalled for hbk_sharded_lookup_fwd (ShardedGroupLookup.bind)."""
-  __slots__ = ('keep', 'outs', 'args', 'shapes')
+  __slots__ = ('keep', 'outs', 'args', 'shapes', 'weights')
+
+  def __init__(self):
+    self.weights = None   # (ptr array, tensors) of a weighted step (hbk_sharded_lookup_fwd_weighted)
 
 
 class ShardedGroupLookup:
@@ -219,10 +222,19 @@ class ShardedGroupLookup:
       self._lib.hbk_sharded_destroy(self._plan_handle)
       self._plan_handle = None
 
-  def bind(self, ids, row_splits=None, outs=None):
+  def bind(self, ids, row_splits=None, outs=None, sp_weights=None):
     """Validate one step's tensors and marshal them into the C-ABI argument arrays once; the
     returned object can be launched any number of times (``launch``) at the cost of a single
-    foreign call -- what a training loop with resident input batches does (bench.py)."""
+    foreign call -- what a training loop with resident input batches does (bench.py).
+    ``sp_weights``: per column None or the fp32 ``[n_ids]`` weights of its ids (applied by the
+    requester's stitch; ``backward`` uses them too).  Only ``launch`` takes a weighted step."""
+    bound = self._bind(ids, row_splits, outs)
+    if sp_weights is not None and any(w is not None for w in sp_weights):
+      from hybridbackend_amd import _marshal
+      bound.weights = (_lib.ptr_array(_marshal.weight_ptrs(sp_weights, ids)), list(sp_weights))
+    return bound
+
+  def _bind(self, ids, row_splits, outs):
     n = len(self.shards)
     fast = self._bind_fresh(ids, row_splits, outs)
     if fast is not None:
@@ -319,8 +331,15 @@ class ShardedGroupLookup:
         self.hot_rows[c] = st[2][c] > 0 and 2 * counts[c] < st[2][c]
       _lib.check(self._lib.hbk_sharded_set_hot_rows(
         self._plan(), (C.c_int32 * len(self.hot_rows))(*[int(h) for h in self.hot_rows])))
-    _lib.check(self._lib.hbk_sharded_lookup_fwd(
-      self._plan(), *bound.args, _lib.current_stream(self.device)))
+    if bound.weights is None:
+      _lib.check(self._lib.hbk_sharded_lookup_fwd(
+        self._plan(), *bound.args, _lib.current_stream(self.device)))
+    else:
+      self._keep_weights = bound.weights[1]   # (the backward reads them: alive until the next step)
+      a = bound.args
+      _lib.check(self._lib.hbk_sharded_lookup_fwd_weighted(
+        self._plan(), a[0], a[1], a[2], a[3], bound.weights[0], a[4], a[5],
+        _lib.current_stream(self.device)))
     return bound.outs
 
   def prefetch_on_current_stream(self, bound):
@@ -336,6 +355,7 @@ class ShardedGroupLookup:
   def launch_begin(self, bound):
     """First half of a bound step (``hbk_sharded_lookup_fwd_begin``): partition (or its prefetched
     result), the one host wait, id exchange, owner-side gather.  ``launch_end`` finishes it."""
+    _refuse_weights(bound, 'launch_begin / launch_end')
     self._keep = bound.keep
     self._last_shapes = bound.shapes
     a = bound.args
@@ -377,12 +397,18 @@ class ShardedGroupLookup:
     _lib.check(self._lib.hbk_sharded_prefetch(self._plan(), id_ptrs, n_ids, ev))
     self._keep_prefetch = keep
 
-  def __call__(self, ids, row_splits=None, outs=None):
+  def __call__(self, ids, row_splits=None, outs=None, sp_weights=None):
     """One forward step through the communicator.  ``ids[c]``: int64 device vector;
     ``row_splits[c]``: int32 device vector or None.  Returns the per-column outputs.
+    ``sp_weights``: per column None or the fp32 ``[n_ids]`` weights of its ids (``backward``
+    differentiates the weighted step; keep them unchanged until then).  Not on a p2p-bound object.
     Handed the SAME tensors as the step before (resident buffers refilled in place, caller-owned
     ``outs``) the marshalled arguments of that step are reused: validating and marshalling 26
     columns costs ~130 us of Python, the reuse check ~15."""
+    weighted = sp_weights is not None and any(w is not None for w in sp_weights)
+    if weighted and getattr(self, '_p2p_keep', None) is not None:
+      raise _lib.HbkError(_lib.UNIMPLEMENTED, 'sp_weights: the p2p form of the forward (p2p_bind) has no '
+                          'stitch to apply them in; p2p_unbind first')
     cached = getattr(self, '_call_cache', None)
     # (a step with OTHER tensors is told apart by its first id tensor: the full comparison -- 3 N
     # tensors against the addresses / counts the bound step was marshalled with -- is only paid
@@ -395,12 +421,23 @@ class ShardedGroupLookup:
           ids[c] is p_ids[c] and sp[c] is p_splits[c] and outs[c] is p_outs[c] and
           ids[c].data_ptr() == a[0][c] and ids[c].numel() == a[1][c] and
           (sp[c] is None or sp[c].data_ptr() == a[2][c]) and outs[c].data_ptr() == a[4][c]
-          for c in range(len(ids))):
+          for c in range(len(ids))) and self._same_weights(bound, sp_weights if weighted else None):
         return self.launch(bound)
-    bound = self.bind(ids, row_splits, outs)
+    bound = self.bind(ids, row_splits, outs, sp_weights=sp_weights if weighted else None)
     if outs is not None and len(ids):
       self._call_cache = (bound.keep, bound)
     return self.launch(bound)
+
+  @staticmethod
+  def _same_weights(bound, sp_weights):
+    """The bound step was marshalled with exactly these weight tensors (None: unweighted both)."""
+    if sp_weights is None or bound.weights is None:
+      return sp_weights is None and bound.weights is None
+    ptrs, kept = bound.weights
+    n_ids = bound.args[1]
+    return len(sp_weights) == len(kept) and all(
+      w is k and (w is None or (w.data_ptr() == ptrs[c] and w.numel() == n_ids[c]))
+      for c, (w, k) in enumerate(zip(sp_weights, kept)))
 
   # ---- backward (SURVEY 3.4) -----------------------------------------------------------------
   # phase B1: d(stitch + combiner): per-id gradient rows in the order of the partitioned ids
@@ -513,6 +550,13 @@ class ShardedGroupLookup:
     return res
 
 
+def _refuse_weights(bound, what):
+  if bound is None or bound.weights is not None:
+    raise _lib.InvalidArgumentError(
+      _lib.INVALID_ARGUMENT, f'sp_weights are not supported by {what} (the split forward takes no '
+      'weights): use ShardedGroupLookup.__call__ / launch')
+
+
 class PipelinedLookup:
   """Exchanges overlapped with the local gather ACROSS STEPS (round 5; north_star's "overlapped with
   local gather on a second HIP stream", the reference's mechanism is hbtf/common/stream.cc:83-142).
@@ -561,7 +605,9 @@ class PipelinedLookup:
     self._next = 0
     self._done = [torch.cuda.Event() for _ in self.plans]
 
-  def bind(self, k, ids, row_splits=None, outs=None):
+  def bind(self, k, ids, row_splits=None, outs=None, sp_weights=None):
+    if sp_weights is not None and any(w is not None for w in sp_weights):
+      _refuse_weights(None, 'PipelinedLookup')
     return self.plans[k].bind(ids, row_splits, outs)
 
   def next_plan(self):

@@ -26,9 +26,16 @@ class EmbeddingColumn:
   256-sample tile once and serves the repeats from LDS (GroupLookup(hot_rows=)).  The default
   ``'auto'`` lets the layer decide per column from what the last backward saw (distinct rows <
   half the ids: on); True / False pin it.  ``dedup``: a sharded column sends every distinct id of
-  a batch once (ShardedGroupLookup(dedup=); the tutorials' tf.unique in front of the lookup)."""
+  a batch once (ShardedGroupLookup(dedup=); the tutorials' tf.unique in front of the lookup).
+  ``weight_feature_key``: ``tf.feature_column.weighted_categorical_column``'s -- the features hold
+  one fp32 weight per id under this key (the ``sp_weights`` of embedding_lookup_sparse: sum of
+  ``w e``, mean divides by the sum of the weights, sqrtn by the root of the sum of their squares; a
+  sample whose divisor is 0 gives a zero row).  Nothing is pruned: unlike TF's
+  ``safe_embedding_lookup_sparse``, ids with weight <= 0 stay in the sums, so callers pass positive
+  weights for that behaviour."""
 
-  def __init__(self, key, num_buckets, dimension, combiner='mean', hot_rows='auto', dedup=False):
+  def __init__(self, key, num_buckets, dimension, combiner='mean', hot_rows='auto', dedup=False,
+               weight_feature_key=None):
     if num_buckets < 1 or dimension < 1:
       raise _lib.InvalidArgumentError(
         _lib.INVALID_ARGUMENT, 'num_buckets and dimension must be >= 1')
@@ -36,6 +43,7 @@ class EmbeddingColumn:
     self.combiner = combiner
     self.hot_rows = 'auto' if hot_rows == 'auto' else bool(hot_rows)
     self.dedup = bool(dedup)
+    self.weight_feature_key = weight_feature_key
 
 
 class DenseFeatures:
@@ -98,6 +106,12 @@ class DenseFeatures:
                                          accums=(pick(self._shd, self.accums)
                                                  if self.accums is not None else None))
 
+  def _weights(self, features):
+    """Per column its fp32 per-id weights (weight_feature_key) or None; None when no column has any."""
+    ws = [features[col.weight_feature_key] if col.weight_feature_key is not None else None
+          for col in self.columns]
+    return ws if any(w is not None for w in ws) else None
+
   def _split(self, features):
     ids, splits, batch = [], [], None
     for col in self.columns:
@@ -117,11 +131,13 @@ class DenseFeatures:
     (the values + row_splits layout of hybridbackend/tensorflow/data/dataframe.py:366-376).
     Returns the dense block; ``cols_to_output_tensors`` (a dict) receives each column's view."""
     ids, splits, batch = self._split(features)
+    ws = self._weights(features)
     # rows start on 16-byte boundaries (row stride padded to 4 floats) so that columns whose
     # offset is a multiple of 4 floats keep 16-byte accesses
     pitch = (self.width + 3) // 4 * 4
     out = torch.empty((batch or 0, pitch), dtype=torch.float32, device=self.device)[:, :self.width]
     pick = lambda idx, xs: [xs[c] for c in idx]   # noqa: E731
+    pick_w = lambda idx: None if ws is None else pick(idx, ws)   # noqa: E731
     views = None
 
     def col_views():
@@ -131,15 +147,17 @@ class DenseFeatures:
       # the blocks' addresses are arithmetic: no per-column views unless somebody asks for them
       # (26 views + their validation were ~100 us of Python per step)
       if batch and self._lookup.bind_block(pick(self._rep, ids), pick(self._rep, splits), out,
-                                           pick(self._rep, self.offsets)):
+                                           pick(self._rep, self.offsets), sp_weights=pick_w(self._rep)):
         self._lookup.launch()
       else:
         views = col_views()
-        self._lookup(pick(self._rep, ids), pick(self._rep, splits), pick(self._rep, views))
+        self._lookup(pick(self._rep, ids), pick(self._rep, splits), pick(self._rep, views),
+                     sp_weights=pick_w(self._rep))
     if self._shd:
       views = views or col_views()
-      self._sharded(pick(self._shd, ids), pick(self._shd, splits), pick(self._shd, views))
-    self._last = (ids, splits)
+      self._sharded(pick(self._shd, ids), pick(self._shd, splits), pick(self._shd, views),
+                    sp_weights=pick_w(self._shd))
+    self._last = (ids, splits, ws)
     if cols_to_output_tensors is not None:
       views = views or col_views()
       for c, col in enumerate(self.columns):
@@ -166,7 +184,7 @@ class DenseFeatures:
     this method never applies the step at W > 1: it returns their IndexedSlices and the caller
     applies the aggregated gradient.  ``emit=False`` (with ``apply_lr``): the stepped tables
     write no IndexedSlices (step only; their entries are ``(None, None, n_unique)``)."""
-    ids, splits = self._last
+    ids, splits, ws = self._last
     if grad.dim() != 2 or grad.shape[1] != self.width or grad.dtype != torch.float32:
       raise _lib.InvalidArgumentError(
         _lib.INVALID_ARGUMENT, f'grad must be fp32 [batch, {self.width}]')
@@ -184,7 +202,8 @@ class DenseFeatures:
       # the gradient's column blocks are addressed by arithmetic (no per-column views)
       r = self._grad(pick(self._rep, ids), None, pick(self._rep, splits),
                      apply_lr=rep_lr, optimizer=optimizer, emit=emit or rep_lr == 0.0,
-                     grad_block=(grad, pick(self._rep, self.offsets)))
+                     grad_block=(grad, pick(self._rep, self.offsets)),
+                     sp_weights=None if ws is None else pick(self._rep, ws))
       for k, c in enumerate(self._rep):
         res[c] = r[k]
     if self._shd:

@@ -66,7 +66,7 @@ typedef void* hbk_stream_t;
 #define HBK_TOPOLOGY_INTER_NODE 2
 
 const char* hbk_last_error(void);
-/* "hbk <version> gfx950" */
+/* "hbk <version> gfx950"; "hbk 0.2.0 gfx950" since the lookup column structs end in id_weights */
 const char* hbk_version(void);
 
 /* Table memory (optional; tables stay caller-owned): one slab for N tables, each at a 2 MB-aligned
@@ -267,6 +267,19 @@ typedef struct {
    * The owner gather of the sharded step's p2p form stores every row straight into its place in
    * the requester's output this way.  NULL: rows in segment order. */
   const int32_t* out_slots;
+  /* optional per-id weights (tf.nn.embedding_lookup_sparse's sp_weights; version 0.2.0): device
+   * fp32 [n_ids], one weight per id.  NULL: unweighted (the code path and results of 0.1.0).  With
+   * weights w_j and rows e_j of the segment's ids, in id order, plain fp32 adds of separately
+   * rounded products:
+   *   sum:   out[s] = sum_j w_j e_j
+   *   mean:  out[s] = (sum_j w_j e_j) / W_s,         W_s = sum_j w_j
+   *   sqrtn: out[s] = (sum_j w_j e_j) / sqrtf(Q_s),  Q_s = sum_j w_j * w_j
+   * (one id per segment included: mean gives (w e) / w).  Ids whose row falls outside [0, rows)
+   * contribute neither term nor weight.  A segment whose divisor W_s / Q_s is 0 (empty, or weights
+   * that cancel) gives a ZERO row where TensorFlow divides and gives non-finite values.  Negative
+   * weights are legal and nothing is pruned.  Refused with out_slots and HBK_LOOKUP_OUT_HALF (the
+   * owner gather of the sharded step is never weighted); hot_rows is ignored. */
+  const float* id_weights;
 } hbk_lookup_column_t;
 #define HBK_LOOKUP_OUT_HALF 1
 #define HBK_LOOKUP_TABLE_HALF 2
@@ -333,6 +346,14 @@ typedef struct {
    * bwd_deterministic = 1 does for every column of every call (and the option, when set, still does):
    * the reproducible mode chosen per call instead of per process.  Other bits: 0. */
   int32_t flags;
+  /* per-id weights of the forward (hbk_lookup_column_t.id_weights; NULL: unweighted).  The
+   * gradient term of id j is  t_j = (grad_out[s] / W_s) * w_j  (mean),  (grad_out[s] / sqrtf(Q_s))
+   * * w_j  (sqrtn),  grad_out[s] * w_j  (sum), each a separately rounded fp32 op in that order;
+   * the ids of a zero-divisor segment get t_j = 0.  grad_rows[u] sums the t_j of row u (in id
+   * order under HBK_GRAD_DETERMINISTIC).  No gradient for the weights themselves.  The call writes
+   * every t_j to an [n_ids, dim] fp32 buffer inside the workspace and reduces that as a column of
+   * one id per segment with the SUM combiner.  Refused with segmented inputs (n_runs > 0). */
+  const float* id_weights;
 } hbk_lookup_grad_column_t;
 #define HBK_GRAD_DETERMINISTIC 1
 
@@ -376,6 +397,9 @@ typedef struct {
   const int64_t* run_base;
   int32_t n_runs;
   int32_t grad_stride;        /* row stride of grad_out in floats; 0 = dim */
+  /* per-id weights of the forward's stitch (device fp32 [n_ids], NULL: unweighted):
+   * grad_rows[index[j], :] = t_j as in hbk_lookup_grad_column_t.id_weights */
+  const float* id_weights;
 } hbk_stitch_grad_column_t;
 
 int hbk_group_stitch_bwd(int32_t n_cols, const hbk_stitch_grad_column_t* cols,
@@ -575,6 +599,23 @@ int hbk_sharded_destroy(hbk_sharded_t plan);
 int hbk_sharded_lookup_fwd(hbk_sharded_t plan, const int64_t* const* ids, const int64_t* n_ids,
                            const int32_t* const* row_splits, const int64_t* n_segments,
                            float* const* outs, const int32_t* out_strides, hbk_stream_t stream);
+/* The weighted forward (tf.nn.embedding_lookup_sparse's sp_weights; hbk_lookup_column_t.id_weights):
+ * id_weights[c] is column c's device fp32 [n_ids[c]] (one weight per id) or NULL (unweighted); a NULL
+ * array = hbk_sharded_lookup_fwd.  Weights never cross the wire: the owners gather plain rows and the
+ * requester's stitch applies them.  The plan keeps the pointers for hbk_sharded_lookup_bwd[_apply]
+ * (its stitch backward writes the weighted per-id terms; under dedup the duplicate positions sum
+ * those), so the caller keeps them valid and unchanged until that backward, as with the ids; a plain
+ * hbk_sharded_lookup_fwd (or _begin) clears them.  The stitch sees the received rows, not the owners'
+ * range checks, so a weighted column needs a bucket (hbk_sharded_column_t.bucket > 0: every id then
+ * names a row of its owner's shard, and the results equal hbk_group_lookup_fwd's over the logical
+ * table); a weighted column without one is refused with HBK_INVALID_ARGUMENT before any exchange.
+ * A p2p-bound plan (hbk_sharded_p2p_bind) has no stitch: HBK_UNIMPLEMENTED on every rank, before any
+ * exchange, when some weight pointer is non-NULL.  _begin / _end take no weights. */
+int hbk_sharded_lookup_fwd_weighted(hbk_sharded_t plan, const int64_t* const* ids,
+                                    const int64_t* n_ids, const int32_t* const* row_splits,
+                                    const int64_t* n_segments, const float* const* id_weights,
+                                    float* const* outs, const int32_t* out_strides,
+                                    hbk_stream_t stream);
 /* The forward in two halves (round 5).  _begin: everything up to and including the owner-side
  * gather (the partition or its prefetched result, the step's one host wait, the id exchange, the
  * gather into the reply buffer -- in the p2p form into the requesters' outputs).  _end: rows

@@ -808,7 +808,37 @@ REGISTER_OP("HbGroupLookup")
     // tiles that stage repeated rows in LDS (hbk_lookup_column_t.hot_rows); empty = none
     .Attr("hot_rows: list(bool) = []");
 
-template <typename Tids>
+// HbGroupLookupWeighted: the same with tf.nn.embedding_lookup_sparse's sp_weights -- one fp32 weight
+// per id (hbk_lookup_column_t.id_weights: sum of w e, mean / sqrtn divide by sum w / sqrt(sum w^2), a
+// zero divisor gives a zero row).  `weights` stays the tables, as in every op here.
+REGISTER_OP("HbGroupLookupWeighted")
+    .Output("outputs: N * float")
+    .Input("weights: N * float").Input("ids: N * Tids").Input("row_splits: N * int32")
+    .Input("sp_weights: N * float")
+    .Attr("N: int >= 1").Attr("Tids: {int32, int64}")
+    .Attr("buckets: list(int)").Attr("combiners: list(int)").Attr("ragged: list(bool)")
+    .Attr("divisor: int = 1")
+    .Attr("hot_rows: list(bool) = []");
+
+// the per-id weights of column i of a weighted op (one fp32 per id), or NULL for an unweighted op
+static Status SpWeights(OpKernelContext* ctx, bool weighted, int n, const OpInputList& ids,
+                        std::vector<const float*>* out) {
+  out->assign(n, nullptr);
+  if (!weighted) return Status::OK();
+  OpInputList sw;
+  TF_RETURN_IF_ERROR(ctx->input_list("sp_weights", &sw));
+  if (sw.size() != n) return errors::InvalidArgument("sp_weights: N tensors expected");
+  for (int i = 0; i < n; ++i) {
+    if (sw[i].NumElements() != ids[i].NumElements()) {
+      return errors::InvalidArgument("sp_weights ", i, ": one weight per id (", ids[i].NumElements(),
+                                     "), got ", sw[i].NumElements());
+    }
+    (*out)[i] = sw[i].flat<float>().data();
+  }
+  return Status::OK();
+}
+
+template <typename Tids, bool kWeighted = false>
 class GroupLookupOp : public OpKernel {
  public:
   explicit GroupLookupOp(OpKernelConstruction* ctx) : OpKernel(ctx) {
@@ -824,6 +854,8 @@ class GroupLookupOp : public OpKernel {
     OP_REQUIRES_OK(ctx, ctx->input_list("ids", &ids));
     OP_REQUIRES_OK(ctx, ctx->input_list("row_splits", &splits));
     const int n = w.size();
+    std::vector<const float*> sp_weights;
+    OP_REQUIRES_OK(ctx, SpWeights(ctx, kWeighted, n, ids, &sp_weights));
     std::vector<hbk_lookup_column_t> cols(n);
     for (int i = 0; i < n; ++i) {
       const int64 n_seg = ragged_[i] ? splits[i].NumElements() - 1 : ids[i].NumElements();
@@ -844,6 +876,7 @@ class GroupLookupOp : public OpKernel {
       c.combiner = combiners_[i];
       c.hot_rows = i < static_cast<int>(hot_rows_.size()) && hot_rows_[i] ? 1 : 0;
       c.out = o->flat<float>().data();
+      c.id_weights = sp_weights[i];
     }
     OP_REQUIRES_OK(ctx, HbkStatus(hbk_group_lookup_fwd(n, cols.data(), StreamOf(ctx))));
   }
@@ -859,6 +892,10 @@ REGISTER_KERNEL_BUILDER(Name("HbGroupLookup").Device(DEVICE_GPU).TypeConstraint<
                         GroupLookupOp<int32>);
 REGISTER_KERNEL_BUILDER(Name("HbGroupLookup").Device(DEVICE_GPU).TypeConstraint<int64>("Tids"),
                         GroupLookupOp<int64>);
+REGISTER_KERNEL_BUILDER(Name("HbGroupLookupWeighted").Device(DEVICE_GPU).TypeConstraint<int32>("Tids"),
+                        GroupLookupOp<int32, true>);
+REGISTER_KERNEL_BUILDER(Name("HbGroupLookupWeighted").Device(DEVICE_GPU).TypeConstraint<int64>("Tids"),
+                        GroupLookupOp<int64, true>);
 
 // --------------------------------------------------------------------------------------------
 // HbGroupLookupGrad: the gradient of HbGroupLookup with respect to `weights` as IndexedSlices
@@ -897,6 +934,35 @@ REGISTER_OP("HbGroupLookupGradApply")
     .Input("weights: Ref(N * float)").Input("accums: Ref(M * float)")
     .Input("ids: N * Tids").Input("row_splits: N * int32").Input("grads: N * float")
     .Input("lr: float")
+    .Attr("N: int >= 1").Attr("M: int >= 0 = 0").Attr("Tids: {int32, int64}")
+    .Attr("buckets: list(int)").Attr("combiners: list(int)").Attr("ragged: list(bool)")
+    .Attr("divisor: int = 1").Attr("optimizer: {'sgd', 'adagrad'} = 'sgd'")
+    .Attr("deterministic: bool = false")
+    .SetIsStateful()
+    .SetShapeFn([](InferenceContext* c) {
+      int64 n;
+      TF_RETURN_IF_ERROR(c->GetAttr("N", &n));
+      for (int64 i = 0; i < n; ++i) c->set_output(i, c->Vector(1));
+      return Status::OK();
+    });
+
+// the gradients of HbGroupLookupWeighted (hbk_lookup_grad_column_t.id_weights: the term of id j is
+// the combiner's share of its segment's gradient times w_j; no gradient for the weights themselves)
+REGISTER_OP("HbGroupLookupWeightedGrad")
+    .Output("unique_rows: N * int64").Output("grad_rows: N * float").Output("n_unique: N * int32")
+    .Input("weights: N * float").Input("ids: N * Tids").Input("row_splits: N * int32")
+    .Input("sp_weights: N * float").Input("grads: N * float")
+    .Attr("N: int >= 1").Attr("Tids: {int32, int64}")
+    .Attr("buckets: list(int)").Attr("combiners: list(int)").Attr("ragged: list(bool)")
+    .Attr("divisor: int = 1")
+    .Attr("deterministic: bool = false")
+    .SetShapeFn(GroupLookupGradShape);
+
+REGISTER_OP("HbGroupLookupWeightedGradApply")
+    .Output("n_unique: N * int32")
+    .Input("weights: Ref(N * float)").Input("accums: Ref(M * float)")
+    .Input("ids: N * Tids").Input("row_splits: N * int32").Input("sp_weights: N * float")
+    .Input("grads: N * float").Input("lr: float")
     .Attr("N: int >= 1").Attr("M: int >= 0 = 0").Attr("Tids: {int32, int64}")
     .Attr("buckets: list(int)").Attr("combiners: list(int)").Attr("ragged: list(bool)")
     .Attr("divisor: int = 1").Attr("optimizer: {'sgd', 'adagrad'} = 'sgd'")
@@ -957,7 +1023,7 @@ struct GroupLookupAttrs {
   }
 };
 
-template <typename Tids>
+template <typename Tids, bool kWeighted = false>
 class GroupLookupGradOp : public OpKernel {
  public:
   explicit GroupLookupGradOp(OpKernelConstruction* ctx) : OpKernel(ctx) {
@@ -971,9 +1037,12 @@ class GroupLookupGradOp : public OpKernel {
     OP_REQUIRES_OK(ctx, ctx->input_list("grads", &grads));
     const int n = w.size();
     OP_REQUIRES_OK(ctx, attrs_.Check(n));
+    std::vector<const float*> sp_weights;
+    OP_REQUIRES_OK(ctx, SpWeights(ctx, kWeighted, n, ids, &sp_weights));
     std::vector<hbk_lookup_grad_column_t> cols(n);
     for (int i = 0; i < n; ++i) {
       OP_REQUIRES_OK(ctx, attrs_.Fill<Tids>(i, w[i], ids[i], splits[i], grads[i], &cols[i]));
+      cols[i].id_weights = sp_weights[i];
       Tensor *u, *g, *k;
       const int64 cap = ids[i].NumElements();
       OP_REQUIRES_OK(ctx, ctx->allocate_output(i, TensorShape({cap}), &u));
@@ -997,6 +1066,10 @@ REGISTER_KERNEL_BUILDER(Name("HbGroupLookupGrad").Device(DEVICE_GPU).TypeConstra
                         GroupLookupGradOp<int32>);
 REGISTER_KERNEL_BUILDER(Name("HbGroupLookupGrad").Device(DEVICE_GPU).TypeConstraint<int64>("Tids"),
                         GroupLookupGradOp<int64>);
+REGISTER_KERNEL_BUILDER(Name("HbGroupLookupWeightedGrad").Device(DEVICE_GPU).TypeConstraint<int32>("Tids"),
+                        GroupLookupGradOp<int32, true>);
+REGISTER_KERNEL_BUILDER(Name("HbGroupLookupWeightedGrad").Device(DEVICE_GPU).TypeConstraint<int64>("Tids"),
+                        GroupLookupGradOp<int64, true>);
 
 static Status OptimizerCode(const string& name, int32_t* apply) {
   if (name == "sgd") { *apply = HBK_APPLY_SGD; return Status::OK(); }
@@ -1004,7 +1077,7 @@ static Status OptimizerCode(const string& name, int32_t* apply) {
   return errors::InvalidArgument("optimizer must be 'sgd' or 'adagrad', got ", name);
 }
 
-template <typename Tids>
+template <typename Tids, bool kWeighted = false>
 class GroupLookupGradApplyOp : public OpKernel {
  public:
   explicit GroupLookupGradApplyOp(OpKernelConstruction* ctx) : OpKernel(ctx) {
@@ -1027,10 +1100,13 @@ class GroupLookupGradApplyOp : public OpKernel {
     OP_REQUIRES_OK(ctx, attrs_.Check(n));
     OP_REQUIRES(ctx, accums.size() == (apply_ == HBK_APPLY_ADAGRAD ? n : 0),
                 errors::InvalidArgument("accums: N accumulators for adagrad, none for sgd"));
+    std::vector<const float*> sp_weights;
+    OP_REQUIRES_OK(ctx, SpWeights(ctx, kWeighted, n, ids, &sp_weights));
     std::vector<hbk_lookup_grad_column_t> cols(n);
     for (int i = 0; i < n; ++i) {
       Tensor weight = w.at(i, /*lock_held=*/false);
       OP_REQUIRES_OK(ctx, attrs_.Fill<Tids>(i, weight, ids[i], splits[i], grads[i], &cols[i]));
+      cols[i].id_weights = sp_weights[i];
       if (apply_ == HBK_APPLY_ADAGRAD) {
         Tensor accum = accums.at(i, /*lock_held=*/false);
         OP_REQUIRES(ctx, accum.NumElements() == weight.NumElements(),
@@ -1059,6 +1135,12 @@ REGISTER_KERNEL_BUILDER(Name("HbGroupLookupGradApply").Device(DEVICE_GPU).HostMe
 REGISTER_KERNEL_BUILDER(Name("HbGroupLookupGradApply").Device(DEVICE_GPU).HostMemory("lr")
                             .TypeConstraint<int64>("Tids"),
                         GroupLookupGradApplyOp<int64>);
+REGISTER_KERNEL_BUILDER(Name("HbGroupLookupWeightedGradApply").Device(DEVICE_GPU).HostMemory("lr")
+                            .TypeConstraint<int32>("Tids"),
+                        GroupLookupGradApplyOp<int32, true>);
+REGISTER_KERNEL_BUILDER(Name("HbGroupLookupWeightedGradApply").Device(DEVICE_GPU).HostMemory("lr")
+                            .TypeConstraint<int64>("Tids"),
+                        GroupLookupGradApplyOp<int64, true>);
 
 // ============================================================================================
 // HbUniqueN / HbCastN (new, additive N-ary ops): the owner-side `array_ops.unique` of
@@ -1194,6 +1276,25 @@ class HbShardedPlan : public ResourceBase {
   std::vector<hbk_sharded_column_t> cols_;
 };
 
+static Status ShardedGroupLookupShape(InferenceContext* c) {
+  int64 n, m;
+  TF_RETURN_IF_ERROR(c->GetAttr("N", &n));
+  TF_RETURN_IF_ERROR(c->GetAttr("M", &m));
+  std::vector<bool> ragged;
+  TF_RETURN_IF_ERROR(c->GetAttr("ragged", &ragged));
+  for (int64 i = 0; i < n; ++i) {   // inputs: handle, shards [1, 1+n), accums, ids, row_splits
+    shape_inference::ShapeHandle ids = c->input(1 + n + m + i);
+    shape_inference::ShapeHandle splits = c->input(1 + 2 * n + m + i);
+    shape_inference::DimensionHandle segs = c->Dim(ids, 0);
+    if (i < static_cast<int64>(ragged.size()) && ragged[i]) {
+      TF_RETURN_IF_ERROR(c->Subtract(c->Dim(splits, 0), 1, &segs));
+    }
+    c->set_output(i, c->Matrix(segs, c->Dim(c->input(1 + i), 1)));
+  }
+  c->set_output(n, c->Scalar());
+  return Status::OK();
+}
+
 REGISTER_OP("HbShardedGroupLookup")
     .Output("outputs: N * float").Output("plan: resource")
     .Input("handle: resource").Input("shards: N * float").Input("accums: M * float")
@@ -1204,25 +1305,25 @@ REGISTER_OP("HbShardedGroupLookup")
     .Attr("wire_dtype: " HB_WIRE_DTYPES " = DT_FLOAT")
     .Attr("container: string = ''").Attr("shared_name: string")
     .SetIsStateful()
-    .SetShapeFn([](InferenceContext* c) {
-      int64 n, m;
-      TF_RETURN_IF_ERROR(c->GetAttr("N", &n));
-      TF_RETURN_IF_ERROR(c->GetAttr("M", &m));
-      std::vector<bool> ragged;
-      TF_RETURN_IF_ERROR(c->GetAttr("ragged", &ragged));
-      for (int64 i = 0; i < n; ++i) {   // inputs: handle, shards [1, 1+n), accums, ids, row_splits
-        shape_inference::ShapeHandle ids = c->input(1 + n + m + i);
-        shape_inference::ShapeHandle splits = c->input(1 + 2 * n + m + i);
-        shape_inference::DimensionHandle segs = c->Dim(ids, 0);
-        if (i < static_cast<int64>(ragged.size()) && ragged[i]) {
-          TF_RETURN_IF_ERROR(c->Subtract(c->Dim(splits, 0), 1, &segs));
-        }
-        c->set_output(i, c->Matrix(segs, c->Dim(c->input(1 + i), 1)));
-      }
-      c->set_output(n, c->Scalar());
-      return Status::OK();
-    });
+    .SetShapeFn(ShardedGroupLookupShape);
 
+// HbShardedGroupLookupWeighted: the same forward with sp_weights (hbk_sharded_lookup_fwd_weighted:
+// the requester's stitch applies them, nothing extra crosses the wire).  The plan keeps the weights
+// for HbShardedGroupLookupGrad[Apply], which differentiate its last forward unchanged; a weighted
+// column needs a bucket (hbk.h).
+REGISTER_OP("HbShardedGroupLookupWeighted")
+    .Output("outputs: N * float").Output("plan: resource")
+    .Input("handle: resource").Input("shards: N * float").Input("accums: M * float")
+    .Input("ids: N * int64").Input("row_splits: N * int32").Input("sp_weights: N * float")
+    .Attr("N: int >= 1").Attr("M: int >= 0 = 0")
+    .Attr("buckets: list(int)").Attr("combiners: list(int)").Attr("ragged: list(bool)")
+    .Attr("dedup: list(bool) = []").Attr("hot_rows: list(bool) = []")
+    .Attr("wire_dtype: " HB_WIRE_DTYPES " = DT_FLOAT")
+    .Attr("container: string = ''").Attr("shared_name: string")
+    .SetIsStateful()
+    .SetShapeFn(ShardedGroupLookupShape);
+
+template <bool kWeighted = false>
 class ShardedGroupLookupOp : public CollectiveAsyncOp {
  public:
   explicit ShardedGroupLookupOp(OpKernelConstruction* ctx) : CollectiveAsyncOp(ctx) {
@@ -1287,6 +1388,14 @@ class ShardedGroupLookupOp : public CollectiveAsyncOp {
     Tensor* plan_out;
     OP_REQUIRES_OK(ctx, ctx->allocate_output(n, TensorShape({}), &plan_out));
     plan_out->scalar<ResourceHandle>()() = handle;
+    if (kWeighted) {
+      std::vector<const float*> sp_weights;
+      OP_REQUIRES_OK(ctx, SpWeights(ctx, true, n, ids, &sp_weights));
+      OP_REQUIRES_OK(ctx, HbkStatus(hbk_sharded_lookup_fwd_weighted(
+                              plan->plan(), id_ptrs.data(), n_ids.data(), split_ptrs.data(), n_seg.data(),
+                              sp_weights.data(), outs.data(), nullptr, StreamOf(ctx))));
+      return;
+    }
     OP_REQUIRES_OK(ctx, HbkStatus(hbk_sharded_lookup_fwd(plan->plan(), id_ptrs.data(), n_ids.data(),
                                                          split_ptrs.data(), n_seg.data(), outs.data(),
                                                          nullptr, StreamOf(ctx))));
@@ -1300,7 +1409,9 @@ class ShardedGroupLookupOp : public CollectiveAsyncOp {
   int32_t wire_dtype_;
 };
 REGISTER_KERNEL_BUILDER(Name("HbShardedGroupLookup").Device(DEVICE_GPU).HostMemory("plan"),
-                        ShardedGroupLookupOp);
+                        ShardedGroupLookupOp<>);
+REGISTER_KERNEL_BUILDER(Name("HbShardedGroupLookupWeighted").Device(DEVICE_GPU).HostMemory("plan"),
+                        ShardedGroupLookupOp<true>);
 
 // The backward differentiates the plan's LAST forward (hbk.h): unique_rows / grad_rows have the
 // capacity hbk_sharded_owned_ids(plan, c) -- the ids this rank's shard was asked for -- known on
