@@ -60,6 +60,12 @@ class LookupGradColumn(C.Structure):
               ('id_weights', C.c_void_p)]
 
 
+class AdamParams(C.Structure):
+  """hbk_adam_t"""
+  _fields_ = [('beta1', C.c_float), ('beta2', C.c_float), ('epsilon', C.c_float),
+              ('beta_powers', C.c_void_p), ('finish', C.c_int32)]
+
+
 class ShardedColumn(C.Structure):
   """hbk_sharded_column_t"""
   _fields_ = [('shard', C.c_void_p), ('rows_local', C.c_int64), ('dim', C.c_int32),
@@ -115,6 +121,8 @@ def _declare(l):
     'hbk_group_lookup_bwd_workspace_bytes': (sz, [i32, vp]),
     'hbk_group_lookup_bwd': (C.c_int, [i32, vp, C.c_float, vp, sz, vp]),
     'hbk_group_lookup_bwd_apply': (C.c_int, [i32, vp, i32, C.c_float, vp, sz, vp]),
+    'hbk_group_lookup_bwd_adam_workspace_bytes': (sz, [i32, vp]),
+    'hbk_group_lookup_bwd_adam': (C.c_int, [i32, vp, vp, vp, vp, C.c_float, vp, sz, vp]),
     'hbk_group_stitch_bwd': (C.c_int, [i32, vp, vp]),
     'hbk_cache_probe': (C.c_int, [vp, i64, i32, vp, i64, vp, vp, vp]),
     'hbk_cache_lookup_workspace_bytes': (sz, [i64]),
@@ -151,6 +159,8 @@ def _declare(l):
     'hbk_sharded_last_host_us': (C.c_int, [vp, vp]),
     'hbk_sharded_lookup_bwd': (C.c_int, [vp, vp, vp, C.c_float, vp, vp, vp, vp]),
     'hbk_sharded_lookup_bwd_apply': (C.c_int, [vp, vp, vp, i32, C.c_float, vp, vp, vp, vp]),
+    'hbk_sharded_set_adam_slots': (C.c_int, [vp, vp, vp]),
+    'hbk_sharded_lookup_bwd_adam': (C.c_int, [vp, vp, vp, vp, C.c_float, vp, vp, vp, vp]),
   }
   for name, (res, args) in protos.items():
     fn = getattr(l, name)   # AttributeError here = header and library out of sync
@@ -279,3 +289,32 @@ def require_device_tensor(t, what, row_strided=False):
   if row_strided and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]:
     return
   raise InvalidArgumentError(INVALID_ARGUMENT, f'{what} must be contiguous')
+
+
+def set_adam_slots(plan, moments):
+  """hbk_sharded_set_adam_slots: every column's (m, v) moment shards of a sharded plan."""
+  check(lib().hbk_sharded_set_adam_slots(plan, ptr_array([m.data_ptr() for m, _ in moments]),
+                                         ptr_array([v.data_ptr() for _, v in moments])))
+
+
+def require_moments(moments, tables, what):
+  """(m, v) per table: fp32 device tensors of the table's shape, contiguous, all distinct."""
+  import torch  # pylint: disable=import-outside-toplevel
+  moments = [tuple(p) for p in moments]
+  if len(moments) != len(tables):
+    raise InvalidArgumentError(INVALID_ARGUMENT, f'{what}: {len(moments)} (m, v) pairs for '
+                               f'{len(tables)} tables')
+  for c, (pair, t) in enumerate(zip(moments, tables)):
+    if len(pair) != 2:
+      raise InvalidArgumentError(INVALID_ARGUMENT, f'{what}: moments[{c}] must be an (m, v) pair')
+    for name, x in zip(('m', 'v'), pair):
+      require_device_tensor(x, f'{what}: moments[{c}].{name}')
+      if x.dtype != torch.float32 or tuple(x.shape) != tuple(t.shape):
+        raise InvalidArgumentError(INVALID_ARGUMENT,
+                                   f'{what}: moments[{c}].{name} must be fp32 {tuple(t.shape)}')
+  # Adam is not additive: a buffer stepped as two slots (or as a slot and a table) would race
+  ptrs = [x.data_ptr() for pair in moments for x in pair] + [t.data_ptr() for t in tables]
+  if len(set(ptrs)) != len(ptrs):
+    raise InvalidArgumentError(INVALID_ARGUMENT, f'{what}: the m / v tensors and the tables must '
+                               'all be distinct buffers')
+  return moments

@@ -262,6 +262,9 @@ class SyncChain {
 int sync_check(const char* who, hipStream_t stream);
 int sync_check_any(const char* who);
 
+// host checks of a Lazy Adam call's hyperparameters (sparse_apply.hip): HBK_OK or HBK_INVALID_ARGUMENT
+int adam_check(const hbk_adam_t* adam, float lr, const char* who);
+
 constexpr int kWave = 64;  // gfx950 wavefront
 
 // a wait of an earlier kernel of this call ran out: what it should have written is not there

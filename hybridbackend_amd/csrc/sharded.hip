@@ -24,6 +24,7 @@
 #include <string.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <chrono>
 #include <random>
 #include <utility>
@@ -536,6 +537,7 @@ struct hbk_sharded {
   std::vector<int64_t> n_sent;       // ids of column c this rank put on the wire (= n_ids, or its
                                      // distinct ids when the column is deduplicated)
   std::vector<const int32_t*> row_splits;
+  std::vector<float*> adam_m, adam_v;     // [N] Lazy Adam moment shards (hbk_sharded_set_adam_slots), or empty
   std::vector<const float*> id_weights;   // [N] per-id weights of the last forward (NULL: unweighted):
                                           // the stitch applies them, the backward's stitch too
   std::vector<int32_t> send_sizes;   // S [N][W] rows this rank requests from owner q, column c
@@ -1740,11 +1742,11 @@ extern "C" int hbk_sharded_lookup_bwd(hbk_sharded_t p, const float* const* grads
                                       unique_rows, grad_rows, n_unique, stream_);
 }
 
-extern "C" int hbk_sharded_lookup_bwd_apply(hbk_sharded_t p, const float* const* grads,
-                                            const int32_t* grad_strides, int32_t apply,
-                                            float apply_lr, int64_t* const* unique_rows,
-                                      float* const* grad_rows, int32_t* const* n_unique,
-                                      hbk_stream_t stream_) {
+// the backward of hbk_sharded_lookup_bwd_apply, or -- adam != NULL -- of hbk_sharded_lookup_bwd_adam
+static int sharded_bwd(hbk_sharded_t p, const float* const* grads, const int32_t* grad_strides,
+                       int32_t apply, float apply_lr, const hbk_adam_t* adam,
+                       int64_t* const* unique_rows, float* const* grad_rows, int32_t* const* n_unique,
+                       hbk_stream_t stream_) {
   using namespace hbk;
   HBK_REQUIRE(p != nullptr, "sharded_lookup_bwd: plan is NULL");
   HBK_REQUIRE(p->have_step, "sharded_lookup_bwd: no forward step to differentiate");
@@ -1893,7 +1895,7 @@ extern "C" int hbk_sharded_lookup_bwd_apply(hbk_sharded_t p, const float* const*
     hbk_lookup_grad_column_t& h = v[c];
     memset(&h, 0, sizeof(h));
     h.table = const_cast<float*>(p->cols[c].shard);
-    h.accum = p->cols[c].accum;
+    h.accum = adam != nullptr ? nullptr : p->cols[c].accum;
     h.rows = p->cols[c].rows_local;
     h.dim = p->cols[c].dim;
     h.ids_dtype = p->id32 ? HBK_INT32 : HBK_INT64;
@@ -1914,18 +1916,88 @@ extern "C" int hbk_sharded_lookup_bwd_apply(hbk_sharded_t p, const float* const*
   size_t ws = 0;
   for (int g = 0; g < G; ++g) {
     const Group& gr = p->groups[g];
-    const size_t w = hbk_group_lookup_bwd_workspace_bytes(gr.c1 - gr.c0, v.data() + gr.c0);
+    const size_t w = adam != nullptr
+                         ? hbk_group_lookup_bwd_adam_workspace_bytes(gr.c1 - gr.c0, v.data() + gr.c0)
+                         : hbk_group_lookup_bwd_workspace_bytes(gr.c1 - gr.c0, v.data() + gr.c0);
     ws = w > ws ? w : ws;
   }
   if ((rc = p->bwd_ws.ensure(ws + 8)) != HBK_OK) return rc;
   for (int g = 0; g < G; ++g) {
     const Group& gr = p->groups[g];
     if (hop) HBK_HIP_OK(hipStreamWaitEvent(stream, p->ev[1][g], 0));
-    rc = hbk_group_lookup_bwd_apply(gr.c1 - gr.c0, v.data() + gr.c0, apply, apply_lr,
-                                    p->bwd_ws.ptr, p->bwd_ws.bytes, stream_);
+    if (adam != nullptr) {   // Lazy Adam: the emit-form reduce + the apply; the last group finishes
+      hbk_adam_t a = *adam;
+      a.finish = g == G - 1 ? adam->finish : 0;
+      rc = hbk_group_lookup_bwd_adam(gr.c1 - gr.c0, v.data() + gr.c0, p->adam_m.data() + gr.c0,
+                                     p->adam_v.data() + gr.c0, &a, apply_lr, p->bwd_ws.ptr,
+                                     p->bwd_ws.bytes, stream_);
+    } else {
+      rc = hbk_group_lookup_bwd_apply(gr.c1 - gr.c0, v.data() + gr.c0, apply, apply_lr,
+                                      p->bwd_ws.ptr, p->bwd_ws.bytes, stream_);
+    }
     if (rc != HBK_OK) return rc;
   }
   return HBK_OK;
+}
+
+extern "C" int hbk_sharded_lookup_bwd_apply(hbk_sharded_t p, const float* const* grads,
+                                            const int32_t* grad_strides, int32_t apply,
+                                            float apply_lr, int64_t* const* unique_rows,
+                                            float* const* grad_rows, int32_t* const* n_unique,
+                                            hbk_stream_t stream_) {
+  return sharded_bwd(p, grads, grad_strides, apply, apply_lr, nullptr, unique_rows, grad_rows,
+                     n_unique, stream_);
+}
+
+extern "C" int hbk_sharded_set_adam_slots(hbk_sharded_t p, float* const* m, float* const* v) {
+  using namespace hbk;
+  HBK_REQUIRE(p != nullptr, "sharded_set_adam_slots: plan is NULL");
+  HBK_REQUIRE(m != nullptr && v != nullptr, "sharded_set_adam_slots: the m / v arrays are NULL");
+  for (int c = 0; c < p->N; ++c) {
+    HBK_REQUIRE(m[c] != nullptr, "sharded_set_adam_slots: column %d: m is NULL", c);
+    HBK_REQUIRE(v[c] != nullptr, "sharded_set_adam_slots: column %d: v is NULL", c);
+    HBK_REQUIRE(m[c] != v[c], "sharded_set_adam_slots: column %d: m and v are the same buffer", c);
+    HBK_REQUIRE(m[c] != p->cols[c].shard && v[c] != p->cols[c].shard,
+                "sharded_set_adam_slots: column %d: m or v is the shard (table)", c);
+  }
+  // no slot twice, and no slot that is some column's shard: checked here, before any backward
+  // exchanges (the per-group apply would only see the columns of its own launch group)
+  std::vector<uintptr_t> seen;
+  for (int c = 0; c < p->N; ++c) {
+    seen.push_back((uintptr_t)m[c]);
+    seen.push_back((uintptr_t)v[c]);
+  }
+  std::sort(seen.begin(), seen.end());
+  HBK_REQUIRE(std::adjacent_find(seen.begin(), seen.end()) == seen.end(),
+              "sharded_set_adam_slots: two columns share an m or v buffer");
+  for (int c = 0; c < p->N; ++c) {
+    HBK_REQUIRE(!std::binary_search(seen.begin(), seen.end(), (uintptr_t)p->cols[c].shard),
+                "sharded_set_adam_slots: column %d's shard (table) is also an m or v slot", c);
+  }
+  p->adam_m.assign(m, m + p->N);
+  p->adam_v.assign(v, v + p->N);
+  return HBK_OK;
+}
+
+extern "C" int hbk_sharded_lookup_bwd_adam(hbk_sharded_t p, const float* const* grads,
+                                           const int32_t* grad_strides, const hbk_adam_t* adam,
+                                           float lr, int64_t* const* unique_rows,
+                                           float* const* grad_rows, int32_t* const* n_unique,
+                                           hbk_stream_t stream_) {
+  using namespace hbk;
+  HBK_REQUIRE(p != nullptr, "sharded_lookup_bwd_adam: plan is NULL");
+  {
+    const int rc = adam_check(adam, lr, "sharded_lookup_bwd_adam");
+    if (rc != HBK_OK) return rc;
+  }
+  HBK_REQUIRE((int)p->adam_m.size() == p->N,
+              "sharded_lookup_bwd_adam: no m / v slots (hbk_sharded_set_adam_slots)");
+  for (int c = 0; c < p->N; ++c) {
+    HBK_REQUIRE(p->cols[c].accum == nullptr,
+                "sharded_lookup_bwd_adam: column %d: accum must be NULL (Adam's slots are m and v)", c);
+  }
+  return sharded_bwd(p, grads, grad_strides, HBK_APPLY_SGD, lr, adam, unique_rows, grad_rows,
+                     n_unique, stream_);
 }
 
 // the per-column hot_rows hints of a live plan (hbk_sharded_column_t.hot_rows): the host side turns

@@ -346,7 +346,8 @@ class GroupLookupGrad:
   hybridbackend/tensorflow/training/gradient.py:193-217).
   """
 
-  def __init__(self, lookup, accums=None, interleaved=None, workspace_of=None, deterministic=False):
+  def __init__(self, lookup, accums=None, interleaved=None, workspace_of=None, deterministic=False,
+               moments=None, adam=None):
     """deterministic: every row's gradient terms are summed in id order (``HBK_GRAD_DETERMINISTIC`` on
     every column): IndexedSlices and stepped tables have the same bits on every run, equal to the
     sequential fp32 sum -- TF's CPU ``UnsortedSegmentSum`` -- and the rows leave ascending.  What the
@@ -365,10 +366,24 @@ class GroupLookupGrad:
 
     workspace_of: another GroupLookupGrad whose scratch memory this one uses too (objects bound to
     different resident batches that run one after the other on one stream need one workspace, not
-    one each)."""
+    one each).
+
+    moments: per column the Lazy Adam slots ``(m, v)`` (fp32, same shape as the weights, zeros to
+    start), needed for ``optimizer='adam'``; adam: the :class:`LazyAdam` whose beta powers the steps
+    use and advance (one object per optimizer, shared with everything it steps; a new one with TF's
+    defaults when omitted)."""
     self._lib = _lib.lib()
     self.lookup = lookup
     n = len(lookup)
+    self.moments = None
+    self.adam = adam
+    if moments is not None:
+      self.moments = _lib.require_moments(moments, lookup.tables, 'GroupLookupGrad')
+      self._m_ptrs = _lib.ptr_array([m.data_ptr() for m, _ in self.moments])
+      self._v_ptrs = _lib.ptr_array([v.data_ptr() for _, v in self.moments])
+      if self.adam is None:
+        from hybridbackend_amd.embedding.optimizer import LazyAdam  # pylint: disable=import-outside-toplevel
+        self.adam = LazyAdam(device=lookup.tables[0].device if n else None)
     self.accums = list(accums) if accums is not None else None
     self.interleaved = list(interleaved) if interleaved is not None else None
     if self.interleaved is not None and self.accums is None:
@@ -472,14 +487,22 @@ class GroupLookupGrad:
     return True
 
   def __call__(self, ids, grads, row_splits=None, apply_lr=0.0, optimizer='sgd', emit=True,
-               grad_block=None, sp_weights=None):
+               grad_block=None, sp_weights=None, finish=True):
     """Returns per column ``(unique_rows int64[n_ids], grad_rows f32[n_ids, dim],
     n_unique int32[1])``; only the first ``n_unique`` rows are meaningful, in unspecified
     order (device-side count: no host sync here).  The result buffers belong to this object
     and are reused by the next call with the same id counts.  ``emit=False`` (with ``apply_lr``):
     step only -- the rows are stepped, no IndexedSlices are written; only ``n_unique`` of each
     returned triple is meaningful.  ``sp_weights``: the forward's per-id weights (per column None
-    or fp32 ``[n_ids]``); no gradient is produced for them."""
+    or fp32 ``[n_ids]``); no gradient is produced for them.  ``optimizer='adam'`` (with ``apply_lr``
+    and ``moments``): the Lazy Adam step (:class:`LazyAdam`); ``finish=False`` leaves the beta powers
+    for a later call of the same optimizer step to advance."""
+    if optimizer not in ('sgd', 'adagrad', 'adam'):
+      raise _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT,
+                                      "optimizer must be 'sgd', 'adagrad' or 'adam'")
+    if optimizer == 'adam' and self.moments is None:
+      raise _lib.InvalidArgumentError(
+        _lib.INVALID_ARGUMENT, "optimizer='adam' needs GroupLookupGrad(lookup, moments=[(m, v), ...])")
     if not emit and apply_lr == 0.0:
       raise _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT, 'emit=False needs apply_lr != 0')
     n = len(self.lookup)
@@ -575,25 +598,46 @@ class GroupLookupGrad:
     if n:
       self._cols_np['id_weights'] = _marshal.weight_ptrs(sp_weights, ids)
     need = self._lib.hbk_group_lookup_bwd_workspace_bytes(n, self._cols)   # (depends on options too)
+    self._adam_cd = None
+    if self.moments is not None:   # (sized for the Adam form too: launch() may take either)
+      self._adam_cd = self._adam_form()
+      need = max(need, self._lib.hbk_group_lookup_bwd_adam_workspace_bytes(n, self._adam_cd))
     if self._ws is None or self._ws.numel() < need:
       self._ws = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
     self._ws_bound = self._ws       # (launch(): the workspace this binding was sized for)
     self._keep = (ids, grads, row_splits, sp_weights)
-    if optimizer not in ('sgd', 'adagrad'):
-      raise _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT, "optimizer must be 'sgd' or 'adagrad'")
     if optimizer == 'adagrad' and apply_lr != 0.0 and self.accums is None:
       raise _lib.InvalidArgumentError(
         _lib.INVALID_ARGUMENT, "optimizer='adagrad' needs GroupLookupGrad(lookup, accums=...)")
-    _lib.check(self._lib.hbk_group_lookup_bwd_apply(
-      n, self._cols, _lib.APPLY_ADAGRAD if optimizer == 'adagrad' else _lib.APPLY_SGD,
-      C.c_float(apply_lr), C.c_void_p(self._ws.data_ptr()),
-      C.c_size_t(self._ws.numel()), _lib.current_stream(dev)))
+    self._step(n, optimizer, apply_lr, finish, self._ws, dev)
     if self.lookup._auto_hot:
       self.lookup.note_backward(self._nu, [int(i.numel()) for i in ids])
     self._bound_call = (emit, [int(i.numel()) for i in ids])
     return list(self._views)
 
-  def launch(self, apply_lr=0.0, optimizer='sgd'):
+  def _adam_form(self):
+    """The descriptors of the Adam form: the bound ones without Adagrad accumulators (a copy, made
+    once per binding call, only when the object keeps accumulators too)."""
+    if self.accums is None:
+      return self._cols
+    cols = type(self._cols).from_buffer_copy(self._cols)
+    for c in range(len(self.lookup)):
+      cols[c].accum = None
+    return cols
+
+  def _step(self, n, optimizer, apply_lr, finish, ws, dev):
+    if optimizer == 'adam' and apply_lr != 0.0:
+      _lib.check(self._lib.hbk_group_lookup_bwd_adam(
+        n, self._adam_cd, self._m_ptrs, self._v_ptrs, C.byref(self.adam.params(finish)),
+        C.c_float(apply_lr), C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()),
+        _lib.current_stream(dev)))
+      return
+    _lib.check(self._lib.hbk_group_lookup_bwd_apply(
+      n, self._cols, _lib.APPLY_ADAGRAD if optimizer == 'adagrad' else _lib.APPLY_SGD,
+      C.c_float(apply_lr), C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()),
+      _lib.current_stream(dev)))
+
+  def launch(self, apply_lr=0.0, optimizer='sgd', finish=True):
     """The backward of the LAST call again, on the same tensors (a training loop over resident
     buffers that are refilled in place; bench.py): the descriptors and the workspace of that call are
     still right, so this is ONE foreign call -- no validation, no marshalling (the counterpart of
@@ -607,11 +651,11 @@ class GroupLookupGrad:
     if optimizer == 'adagrad' and apply_lr != 0.0 and self.accums is None:
       raise _lib.InvalidArgumentError(
         _lib.INVALID_ARGUMENT, "optimizer='adagrad' needs GroupLookupGrad(lookup, accums=...)")
+    if optimizer == 'adam' and self.moments is None:
+      raise _lib.InvalidArgumentError(
+        _lib.INVALID_ARGUMENT, "optimizer='adam' needs GroupLookupGrad(lookup, moments=[(m, v), ...])")
     dev = self.lookup.tables[0].device if len(self.lookup) else None
-    _lib.check(self._lib.hbk_group_lookup_bwd_apply(
-      len(self.lookup), self._cols, _lib.APPLY_ADAGRAD if optimizer == 'adagrad' else _lib.APPLY_SGD,
-      C.c_float(apply_lr), C.c_void_p(self._ws_bound.data_ptr()),
-      C.c_size_t(self._ws_bound.numel()), _lib.current_stream(dev)))
+    self._step(len(self.lookup), optimizer, apply_lr, finish, self._ws_bound, dev)
     if self.lookup._auto_hot:
       self.lookup.note_backward(self._nu, n_ids)
     return list(self._views)

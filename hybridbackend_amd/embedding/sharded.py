@@ -81,10 +81,19 @@ class ShardedGroupLookup:
   """
 
   def __init__(self, shards, coll, buckets=None, combiners='sum', wire_dtype=None,
-               world_size=None, accums=None, hot_rows=False, dedup=False):
+               world_size=None, accums=None, hot_rows=False, dedup=False, moments=None, adam=None):
     self.shards = list(shards)
     # Adagrad accumulators of the shards (same shapes), for backward(optimizer='adagrad')
     self.accums = list(accums) if accums is not None else None
+    # Lazy Adam slots of the shards ((m, v) per column, same shapes) and the optimizer whose beta
+    # powers they step with, for backward(optimizer='adam')
+    self.moments = None
+    self.adam = adam
+    if moments is not None:
+      self.moments = _lib.require_moments(moments, self.shards, 'ShardedGroupLookup')
+      if self.adam is None:
+        from hybridbackend_amd.embedding.optimizer import LazyAdam  # pylint: disable=import-outside-toplevel
+        self.adam = LazyAdam(device=self.shards[0].device)
     self.coll = coll
     self.world_size = int(world_size if world_size is not None else coll.world_size)
     n = len(self.shards)
@@ -176,6 +185,8 @@ class ShardedGroupLookup:
     wire = _lib.HALF if self.wire_dtype == torch.float16 else _lib.FLOAT
     _lib.check(self._lib.hbk_sharded_create(
       C.byref(self._plan_handle), self.coll._handle, n, cols, wire))
+    if self.moments is not None:
+      _lib.set_adam_slots(self._plan_handle, self.moments)
 
   def last_host_us(self):
     """Host time of the last forward step in microseconds: (enqueueing the partition and the
@@ -476,20 +487,26 @@ class ShardedGroupLookup:
   def owner_bwd(self, st, recv_grads, apply_lr=0.0):
     return self._owner_grad(st.recv_ids, recv_grads, None, apply_lr=apply_lr)
 
-  def backward(self, grads, apply_lr=0.0, outs=None, optimizer='sgd', emit=True):
+  def backward(self, grads, apply_lr=0.0, outs=None, optimizer='sgd', emit=True, finish=True):
     """Backward of the LAST forward step (hbk_sharded_lookup_bwd).  grads[c]: gradient of
     column c's output [segments, dim].  Returns per column the IndexedSlices of the LOCAL
     shard ``(unique_rows, grad_rows, n_unique)``; with ``apply_lr`` the SGD update is applied
     to the shard in the same pass (sharded variables are not aggregated across ranks,
     training/gradient.py:193-217).  The exchange reuses the forward's sizes reversed
     (collective.py:334-347): no new size exchange, no host sync.  ``emit=False`` (with
-    ``apply_lr``): step only, no IndexedSlices are written (only the ``n_unique`` counts)."""
+    ``apply_lr``): step only, no IndexedSlices are written (only the ``n_unique`` counts).
+    ``optimizer='adam'`` (with ``apply_lr`` and ``moments``): the Lazy Adam step on the shards
+    (hbk_sharded_lookup_bwd_adam); ``finish=False`` leaves the beta powers to a later call."""
     if not emit and apply_lr == 0.0:
       raise _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT, 'emit=False needs apply_lr != 0')
     n = len(self.shards)
     plan = self._plan()
-    if optimizer not in ('sgd', 'adagrad'):
-      raise _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT, "optimizer must be 'sgd' or 'adagrad'")
+    if optimizer not in ('sgd', 'adagrad', 'adam'):
+      raise _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT,
+                                      "optimizer must be 'sgd', 'adagrad' or 'adam'")
+    if optimizer == 'adam' and self.moments is None:
+      raise _lib.InvalidArgumentError(
+        _lib.INVALID_ARGUMENT, "optimizer='adam' needs ShardedGroupLookup(..., moments=[(m, v), ...])")
     res = []
     shapes = getattr(self, '_last_shapes', None)
     auto = bool(self._auto_hot) and outs is None
@@ -533,12 +550,20 @@ class ShardedGroupLookup:
     if optimizer == 'adagrad' and apply_lr != 0.0 and self.accums is None:
       raise _lib.InvalidArgumentError(
         _lib.INVALID_ARGUMENT, "optimizer='adagrad' needs ShardedGroupLookup(..., accums=...)")
-    _lib.check(self._lib.hbk_sharded_lookup_bwd_apply(
-      plan, _lib.ptr_array([g.data_ptr() for g in grads]), strides,
-      _lib.APPLY_ADAGRAD if optimizer == 'adagrad' else _lib.APPLY_SGD, C.c_float(apply_lr),
-      _lib.ptr_array([r[0].data_ptr() for r in res]) if emit else None,
-      _lib.ptr_array([r[1].data_ptr() for r in res]) if emit else None,
-      _lib.ptr_array([r[2].data_ptr() for r in res]), _lib.current_stream(self.device)))
+    if optimizer == 'adam' and apply_lr != 0.0:
+      _lib.check(self._lib.hbk_sharded_lookup_bwd_adam(
+        plan, _lib.ptr_array([g.data_ptr() for g in grads]), strides,
+        C.byref(self.adam.params(finish)), C.c_float(apply_lr),
+        _lib.ptr_array([r[0].data_ptr() for r in res]) if emit else None,
+        _lib.ptr_array([r[1].data_ptr() for r in res]) if emit else None,
+        _lib.ptr_array([r[2].data_ptr() for r in res]), _lib.current_stream(self.device)))
+    else:
+      _lib.check(self._lib.hbk_sharded_lookup_bwd_apply(
+        plan, _lib.ptr_array([g.data_ptr() for g in grads]), strides,
+        _lib.APPLY_ADAGRAD if optimizer == 'adagrad' else _lib.APPLY_SGD, C.c_float(apply_lr),
+        _lib.ptr_array([r[0].data_ptr() for r in res]) if emit else None,
+        _lib.ptr_array([r[1].data_ptr() for r in res]) if emit else None,
+        _lib.ptr_array([r[2].data_ptr() for r in res]), _lib.current_stream(self.device)))
     if auto:
       st = self._auto_state
       if st is None:

@@ -14,6 +14,7 @@ import torch
 from hybridbackend_amd import _lib
 from hybridbackend_amd.embedding.lookup import GroupLookup
 from hybridbackend_amd.embedding.lookup import GroupLookupGrad
+from hybridbackend_amd.embedding.optimizer import LazyAdam
 from hybridbackend_amd.embedding.sharded import ShardedGroupLookup
 from hybridbackend_amd.embedding.variables import sharded_bucket_size
 
@@ -59,10 +60,14 @@ class DenseFeatures:
     init: ``init(column, rows, device) -> fp32 [rows, dim]`` for this rank's rows (rows
       ``rank, rank + W, ..`` of the logical table when sharded); default uniform(-1e-3, 1e-3)
       (docs/tutorial/ranking/criteo/train.py:84,91).
+    initial_accumulator_value: keep Adagrad accumulators (``optimizer='adagrad'``).
+    optimizer: ``'adam'`` keeps Lazy Adam slots -- zero ``m`` and ``v`` for every table -- for
+      ``backward(optimizer='adam')``; ``adam`` is the :class:`LazyAdam` they step with (TF's
+      defaults when omitted), whose beta powers advance once per stepped backward.
   """
 
   def __init__(self, columns, device, coll=None, batch_size=0, init=None,
-               initial_accumulator_value=None):
+               initial_accumulator_value=None, optimizer=None, adam=None):
     self.columns = list(columns)
     self.device = torch.device(device)
     self.coll = coll
@@ -81,6 +86,14 @@ class DenseFeatures:
     self.accums = None
     if initial_accumulator_value is not None:
       self.accums = [torch.full_like(w, float(initial_accumulator_value)) for w in self.weights]
+    if optimizer not in (None, 'sgd', 'adagrad', 'adam'):
+      raise _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT,
+                                      "optimizer must be 'sgd', 'adagrad' or 'adam'")
+    # Lazy Adam slots (tf.contrib.opt.LazyAdamOptimizer: m and v start at zero)
+    self.moments = self.adam = None
+    if optimizer == 'adam' or adam is not None:
+      self.adam = adam if adam is not None else LazyAdam(device=self.device)
+      self.moments = [(torch.zeros_like(w), torch.zeros_like(w)) for w in self.weights]
     self.offsets, off = [], 0
     for col in self.columns:
       self.offsets.append(off)
@@ -96,7 +109,8 @@ class DenseFeatures:
                                  [self.columns[c].combiner for c in self._rep],
                                  hot_rows=[self.columns[c].hot_rows for c in self._rep])
       self._grad = GroupLookupGrad(
-        self._lookup, pick(self._rep, self.accums) if self.accums is not None else None)
+        self._lookup, pick(self._rep, self.accums) if self.accums is not None else None,
+        moments=pick(self._rep, self.moments) if self.moments is not None else None, adam=self.adam)
     if self._shd:
       self._sharded = ShardedGroupLookup(pick(self._shd, self.weights), coll,
                                          buckets=[self.columns[c].num_buckets for c in self._shd],
@@ -104,7 +118,10 @@ class DenseFeatures:
                                          hot_rows=[self.columns[c].hot_rows for c in self._shd],
                                          dedup=[self.columns[c].dedup for c in self._shd],
                                          accums=(pick(self._shd, self.accums)
-                                                 if self.accums is not None else None))
+                                                 if self.accums is not None else None),
+                                         moments=(pick(self._shd, self.moments)
+                                                  if self.moments is not None else None),
+                                         adam=self.adam)
 
   def _weights(self, features):
     """Per column its fp32 per-id weights (weight_feature_key) or None; None when no column has any."""
@@ -183,7 +200,12 @@ class DenseFeatures:
     hybridbackend/tensorflow/training/gradient.py:119-177) or the replicas diverge, so for them
     this method never applies the step at W > 1: it returns their IndexedSlices and the caller
     applies the aggregated gradient.  ``emit=False`` (with ``apply_lr``): the stepped tables
-    write no IndexedSlices (step only; their entries are ``(None, None, n_unique)``)."""
+    write no IndexedSlices (step only; their entries are ``(None, None, n_unique)``).
+    ``optimizer='adam'`` (layer built with ``optimizer='adam'``): the Lazy Adam step; the beta powers
+    advance once per backward that steps any table."""
+    if optimizer == 'adam' and self.moments is None:
+      raise _lib.InvalidArgumentError(
+        _lib.INVALID_ARGUMENT, "optimizer='adam' needs DenseFeatures(..., optimizer='adam')")
     ids, splits, ws = self._last
     if grad.dim() != 2 or grad.shape[1] != self.width or grad.dtype != torch.float32:
       raise _lib.InvalidArgumentError(
@@ -200,10 +222,12 @@ class DenseFeatures:
     if self._rep:
       rep_lr = apply_lr if (self.coll.world_size if self.coll is not None else 1) <= 1 else 0.0
       # the gradient's column blocks are addressed by arithmetic (no per-column views)
+      # one optimizer step: the powers advance with the last call that steps (the sharded one)
       r = self._grad(pick(self._rep, ids), None, pick(self._rep, splits),
                      apply_lr=rep_lr, optimizer=optimizer, emit=emit or rep_lr == 0.0,
                      grad_block=(grad, pick(self._rep, self.offsets)),
-                     sp_weights=None if ws is None else pick(self._rep, ws))
+                     sp_weights=None if ws is None else pick(self._rep, ws),
+                     finish=not (self._shd and apply_lr != 0.0))
       for k, c in enumerate(self._rep):
         res[c] = r[k]
     if self._shd:
@@ -219,19 +243,27 @@ class DenseFeatures:
   def variables(self):
     """``{name: tensor | ShardedSlice}`` of this rank: the embedding weights (TF naming:
     ``<key>_embedding/embedding_weights``; a sharded table is the slice ``part_<rank>`` of it,
-    variables.py:112-141) and, when the layer keeps them, the Adagrad slots (``.../Adagrad``)."""
+    variables.py:112-141) and, when the layer keeps them, the Adagrad slots (``.../Adagrad``) or the
+    Lazy Adam slots (``.../Adam`` = m, ``.../Adam_1`` = v, sharded as the weights) with the 0-d
+    scalars ``beta1_power`` and ``beta2_power``."""
     from hybridbackend_amd.training.saver import ShardedSlice
     world = self.coll.world_size if self.coll is not None else 1
     rank = self.coll.rank if self.coll is not None else 0
     out = {}
     for c, col in enumerate(self.columns):
       name = f'{col.key}_embedding/embedding_weights'
-      for suffix, tensors in (('', self.weights), ('/Adagrad', self.accums)):
+      moms = self.moments
+      for suffix, tensors in (('', self.weights), ('/Adagrad', self.accums),
+                              ('/Adam', None if moms is None else [m for m, _ in moms]),
+                              ('/Adam_1', None if moms is None else [v for _, v in moms])):
         if tensors is None:
           continue
         t = tensors[c]
         out[name + suffix] = (ShardedSlice(t, col.num_buckets, world, rank)
                               if self.sharded[c] else t)
+    if self.adam is not None:   # (0-d views of the device pair: a restore writes into it)
+      out['beta1_power'] = self.adam.beta_powers[0]
+      out['beta2_power'] = self.adam.beta_powers[1]
     return out
 
   def _saver(self, barrier):

@@ -75,9 +75,10 @@ def _to_numpy(t):
     host.copy_(t, non_blocking=False)
     t = host
   t = t.cpu().contiguous()
+  # (np.ascontiguousarray returns at least one dimension: a 0-d tensor keeps its shape ())
   if t.dtype == torch.bfloat16:
-    return np.ascontiguousarray(t.view(torch.int16).numpy()), 'bfloat16'
-  arr = np.ascontiguousarray(t.numpy())
+    return np.ascontiguousarray(t.view(torch.int16).numpy()).reshape(tuple(t.shape)), 'bfloat16'
+  arr = np.ascontiguousarray(t.numpy()).reshape(tuple(t.shape))
   if str(arr.dtype) not in _DTYPES:
     raise ValueError(f'unsupported dtype {arr.dtype} in a checkpoint')
   return arr, str(arr.dtype)
@@ -202,6 +203,14 @@ class Saver:
         else:
           arr = _concatenated(prefix, meta)[v.var_offset:v.var_offset + v.tensor.shape[0]]
         target = v.tensor
+      elif len(meta['slices']) > 1 or meta['slices'][0].get('stride', 1) != 1:
+        # a variable saved as shards, restored whole (a table replicated at this world size)
+        if layout == 'logical':
+          arr = _gather_logical_rows(prefix, meta,
+                                     np.arange(meta['full_shape'][0], dtype=np.int64))
+        else:
+          arr = _concatenated(prefix, meta)
+        target = v
       else:
         arr = _load_slice(prefix, meta, meta['slices'][0])
         target = v
@@ -242,7 +251,7 @@ class Saver:
         table = table[v.rank::v.world_size]
       if tuple(table.shape) != tuple(target.shape):
         raise ValueError(f'{name}: checkpoint shape {tuple(table.shape)} != {tuple(target.shape)}')
-      host = torch.from_numpy(np.ascontiguousarray(table))
+      host = torch.from_numpy(np.ascontiguousarray(table).reshape(table.shape))   # (0-d stays 0-d)
       if reader.is_bfloat16(ck):
         host = host.view(torch.int16).view(torch.bfloat16)
       target.copy_(host.to(target.dtype))
@@ -282,8 +291,9 @@ def _load_slice(prefix, meta, s):
   path = os.path.join(os.path.dirname(prefix) or '.', s['file'])
   if s['nbytes'] == 0:      # a rank without rows (bucket_size < world_size): nothing to map
     return np.empty(tuple(s['var_shape']), _DTYPES[meta['dtype']])
+  # (a 0-d variable -- Adam's beta1_power / beta2_power -- maps as one element: back to shape ())
   return np.memmap(path, dtype=_DTYPES[meta['dtype']], mode='r', offset=s['offset'],
-                   shape=tuple(s['var_shape']))
+                   shape=tuple(s['var_shape']) or (1,)).reshape(tuple(s['var_shape']))
 
 
 def _gather_logical_rows(prefix, meta, rows):

@@ -374,6 +374,37 @@ int hbk_group_lookup_bwd_apply(int32_t n_cols, const hbk_lookup_grad_column_t* c
                                int32_t apply, float apply_lr, void* workspace,
                                size_t workspace_bytes, hbk_stream_t stream);
 
+/* Lazy Adam: tf.contrib.opt.LazyAdamOptimizer's sparse apply (TF 1.15) on the deduplicated gradient
+ * g of every distinct row r of the call, each a separately rounded fp32 op in this order:
+ *     lr_t = (lr * sqrtf(1 - beta_powers[1])) / (1 - beta_powers[0])
+ *     m[r] = beta1 * m[r] + (1 - beta1) * g
+ *     v[r] = beta2 * v[r] + (1 - beta2) * (g * g)
+ *     w[r] = w[r] - (lr_t * m[r]) / (sqrtf(v[r]) + epsilon)
+ * Rows that do not occur are not touched (tf.train.AdamOptimizer's own sparse path decays and moves
+ * every row: a full-table pass, not provided).  Two phases: the backward in its emit form
+ * (hbk_group_lookup_bwd, apply_lr = 0: every distinct row exactly once, deterministic modes and
+ * weights as there), then one apply launch that reads each column's n_unique on the device (no host
+ * sync; capturable).  cols[c].table is the weights, m[c] / v[c] the first / second moments, all three
+ * with the row pitch cols[c].table_pitch (so [w | m | v | pad] may be interleaved per row);
+ * cols[c].accum must be NULL.  unique_rows / grad_rows may both be NULL (step only: they then live in
+ * the workspace, which the query sizes from the same pointers).  beta_powers is a device fp32 [2]
+ * (beta1^t, beta2^t; start at beta1, beta2), read by the apply; finish != 0 multiplies it by
+ * (beta1, beta2) in fp32 after this call's step, in stream order (TF's _finish).  Adam is not
+ * additive: no table, m or v may appear twice in one call.  Dims: those the backward takes -- at most
+ * 256 when table, m, v, grad_rows and the pitch are 16-byte aligned and dim % 4 == 0 (f32x4 chunks),
+ * at most 64 otherwise (scalar chunks); larger dims are refused before any device work.  Detected by
+ * the presence of the symbol. */
+typedef struct {
+  float beta1, beta2, epsilon;
+  float* beta_powers;   /* device [2]: beta1^t, beta2^t */
+  int32_t finish;       /* != 0: advance beta_powers after this call's step */
+} hbk_adam_t;
+size_t hbk_group_lookup_bwd_adam_workspace_bytes(int32_t n_cols,
+                                                 const hbk_lookup_grad_column_t* cols);
+int hbk_group_lookup_bwd_adam(int32_t n_cols, const hbk_lookup_grad_column_t* cols,
+                              float* const* m, float* const* v, const hbk_adam_t* adam, float lr,
+                              void* workspace, size_t workspace_bytes, hbk_stream_t stream);
+
 /* R10 (sharded form)  d(stitch + combiner): the transpose of the requester-side
  *   `gather(embeddings, shard_index)` + combiner (hbtf/embedding/sharding.py:200; TF emits
  *   SparseSegment*Grad followed by an UnsortedSegmentSum over a permutation):
@@ -681,6 +712,16 @@ int hbk_sharded_lookup_bwd_apply(hbk_sharded_t plan, const float* const* grads,
                                  const int32_t* grad_strides, int32_t apply, float apply_lr,
                                  int64_t* const* unique_rows, float* const* grad_rows,
                                  int32_t* const* n_unique, hbk_stream_t stream);
+/* Lazy Adam on the shards (hbk_group_lookup_bwd_adam): hbk_sharded_set_adam_slots registers every
+ * column's first / second moment shard ([rows_local, dim], as the column's shard; the columns' accum
+ * must be NULL), then hbk_sharded_lookup_bwd_adam runs the owner-side reduce in its emit form and the
+ * apply, launch group by launch group; only the last group finishes the powers.  unique_rows and
+ * grad_rows may both be NULL (step only). */
+int hbk_sharded_set_adam_slots(hbk_sharded_t plan, float* const* m, float* const* v);
+int hbk_sharded_lookup_bwd_adam(hbk_sharded_t plan, const float* const* grads,
+                                const int32_t* grad_strides, const hbk_adam_t* adam, float lr,
+                                int64_t* const* unique_rows, float* const* grad_rows,
+                                int32_t* const* n_unique, hbk_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -936,7 +936,8 @@ REGISTER_OP("HbGroupLookupGradApply")
     .Input("lr: float")
     .Attr("N: int >= 1").Attr("M: int >= 0 = 0").Attr("Tids: {int32, int64}")
     .Attr("buckets: list(int)").Attr("combiners: list(int)").Attr("ragged: list(bool)")
-    .Attr("divisor: int = 1").Attr("optimizer: {'sgd', 'adagrad'} = 'sgd'")
+    .Attr("divisor: int = 1").Attr("optimizer: {'sgd', 'adagrad', 'adam'} = 'sgd'")
+    .Attr("beta1: float = 0.9").Attr("beta2: float = 0.999").Attr("epsilon: float = 1e-8")
     .Attr("deterministic: bool = false")
     .SetIsStateful()
     .SetShapeFn([](InferenceContext* c) {
@@ -965,7 +966,8 @@ REGISTER_OP("HbGroupLookupWeightedGradApply")
     .Input("grads: N * float").Input("lr: float")
     .Attr("N: int >= 1").Attr("M: int >= 0 = 0").Attr("Tids: {int32, int64}")
     .Attr("buckets: list(int)").Attr("combiners: list(int)").Attr("ragged: list(bool)")
-    .Attr("divisor: int = 1").Attr("optimizer: {'sgd', 'adagrad'} = 'sgd'")
+    .Attr("divisor: int = 1").Attr("optimizer: {'sgd', 'adagrad', 'adam'} = 'sgd'")
+    .Attr("beta1: float = 0.9").Attr("beta2: float = 0.999").Attr("epsilon: float = 1e-8")
     .Attr("deterministic: bool = false")
     .SetIsStateful()
     .SetShapeFn([](InferenceContext* c) {
@@ -1071,10 +1073,48 @@ REGISTER_KERNEL_BUILDER(Name("HbGroupLookupWeightedGrad").Device(DEVICE_GPU).Typ
 REGISTER_KERNEL_BUILDER(Name("HbGroupLookupWeightedGrad").Device(DEVICE_GPU).TypeConstraint<int64>("Tids"),
                         GroupLookupGradOp<int64, true>);
 
+// optimizer='adam': tf.contrib.opt.LazyAdamOptimizer's sparse apply (hbk_group_lookup_bwd_adam /
+// hbk_sharded_lookup_bwd_adam); `accums` then holds m x N, v x N and the [2] beta powers (M = 2N + 1),
+// and the op advances the powers after its step (TF's _finish)
+constexpr int32_t kApplyLazyAdam = -1;   // (the shim's own code: the C ABI has a separate entry)
 static Status OptimizerCode(const string& name, int32_t* apply) {
   if (name == "sgd") { *apply = HBK_APPLY_SGD; return Status::OK(); }
   if (name == "adagrad") { *apply = HBK_APPLY_ADAGRAD; return Status::OK(); }
-  return errors::InvalidArgument("optimizer must be 'sgd' or 'adagrad', got ", name);
+  if (name == "adam") { *apply = kApplyLazyAdam; return Status::OK(); }
+  return errors::InvalidArgument("optimizer must be 'sgd', 'adagrad' or 'adam', got ", name);
+}
+
+struct AdamAttrs {
+  float beta1 = 0.9f, beta2 = 0.999f, epsilon = 1e-8f;
+  Status Read(OpKernelConstruction* ctx) {
+    TF_RETURN_IF_ERROR(ctx->GetAttr("beta1", &beta1));
+    TF_RETURN_IF_ERROR(ctx->GetAttr("beta2", &beta2));
+    return ctx->GetAttr("epsilon", &epsilon);
+  }
+};
+
+// the slots of an Adam call out of `accums` (m x N, v x N, beta powers [2])
+static Status AdamSlots(OpMutableInputList& accums, int n, const std::vector<int64>& sizes,
+                        std::vector<float*>* m, std::vector<float*>* v, float** powers) {
+  if (accums.size() != 2 * n + 1) {
+    return errors::InvalidArgument("accums: adam takes m x N, v x N and the [2] beta powers (M = ",
+                                   2 * n + 1, "), got ", accums.size());
+  }
+  m->resize(n);
+  v->resize(n);
+  for (int i = 0; i < n; ++i) {
+    Tensor mt = accums.at(i, /*lock_held=*/false);
+    Tensor vt = accums.at(n + i, /*lock_held=*/false);
+    if (mt.NumElements() != sizes[i] || vt.NumElements() != sizes[i]) {
+      return errors::InvalidArgument("m / v ", i, " must have its variable's shape");
+    }
+    (*m)[i] = mt.flat<float>().data();
+    (*v)[i] = vt.flat<float>().data();
+  }
+  Tensor p = accums.at(2 * n, /*lock_held=*/false);
+  if (p.NumElements() != 2) return errors::InvalidArgument("beta powers must be a float [2]");
+  *powers = p.flat<float>().data();
+  return Status::OK();
 }
 
 template <typename Tids, bool kWeighted = false>
@@ -1085,6 +1125,7 @@ class GroupLookupGradApplyOp : public OpKernel {
     string optimizer;
     OP_REQUIRES_OK(ctx, ctx->GetAttr("optimizer", &optimizer));
     OP_REQUIRES_OK(ctx, OptimizerCode(optimizer, &apply_));
+    if (apply_ == kApplyLazyAdam) OP_REQUIRES_OK(ctx, adam_.Read(ctx));
   }
   void Compute(OpKernelContext* ctx) override {
     OpMutableInputList w, accums;
@@ -1098,7 +1139,7 @@ class GroupLookupGradApplyOp : public OpKernel {
     OP_REQUIRES_OK(ctx, ctx->input("lr", &lr));
     const int n = w.size();
     OP_REQUIRES_OK(ctx, attrs_.Check(n));
-    OP_REQUIRES(ctx, accums.size() == (apply_ == HBK_APPLY_ADAGRAD ? n : 0),
+    OP_REQUIRES(ctx, apply_ == kApplyLazyAdam || accums.size() == (apply_ == HBK_APPLY_ADAGRAD ? n : 0),
                 errors::InvalidArgument("accums: N accumulators for adagrad, none for sgd"));
     std::vector<const float*> sp_weights;
     OP_REQUIRES_OK(ctx, SpWeights(ctx, kWeighted, n, ids, &sp_weights));
@@ -1117,6 +1158,25 @@ class GroupLookupGradApplyOp : public OpKernel {
       OP_REQUIRES_OK(ctx, ctx->allocate_output(i, TensorShape({1}), &k));
       cols[i].n_unique = k->flat<int32>().data();      // unique_rows = grad_rows = NULL: step only
     }
+    if (apply_ == kApplyLazyAdam) {
+      std::vector<int64> sizes(n);
+      for (int i = 0; i < n; ++i) sizes[i] = w.at(i, /*lock_held=*/false).NumElements();
+      std::vector<float*> m, v;
+      hbk_adam_t adam;
+      std::memset(&adam, 0, sizeof(adam));
+      OP_REQUIRES_OK(ctx, AdamSlots(accums, n, sizes, &m, &v, &adam.beta_powers));
+      adam.beta1 = adam_.beta1;
+      adam.beta2 = adam_.beta2;
+      adam.epsilon = adam_.epsilon;
+      adam.finish = 1;
+      const size_t ws_bytes = hbk_group_lookup_bwd_adam_workspace_bytes(n, cols.data());
+      Tensor ws;
+      OP_REQUIRES_OK(ctx, AllocScratch(ctx, ws_bytes, &ws));
+      OP_REQUIRES_OK(ctx, HbkStatus(hbk_group_lookup_bwd_adam(
+                              n, cols.data(), m.data(), v.data(), &adam, lr->scalar<float>()(),
+                              ws.flat<int8>().data(), ws_bytes + 16, StreamOf(ctx))));
+      return;
+    }
     const size_t ws_bytes = hbk_group_lookup_bwd_workspace_bytes(n, cols.data());
     Tensor ws;
     OP_REQUIRES_OK(ctx, AllocScratch(ctx, ws_bytes, &ws));
@@ -1127,6 +1187,7 @@ class GroupLookupGradApplyOp : public OpKernel {
 
  private:
   GroupLookupAttrs attrs_;
+  AdamAttrs adam_;
   int32_t apply_;
 };
 REGISTER_KERNEL_BUILDER(Name("HbGroupLookupGradApply").Device(DEVICE_GPU).HostMemory("lr")
@@ -1433,7 +1494,11 @@ REGISTER_OP("HbShardedGroupLookupGrad")
 REGISTER_OP("HbShardedGroupLookupGradApply")
     .Output("n_unique: N * int32")
     .Input("handle: resource").Input("plan: resource").Input("grads: N * float").Input("lr: float")
-    .Attr("N: int >= 1").Attr("optimizer: {'sgd', 'adagrad'} = 'sgd'").SetIsStateful()
+    .Input("accums: Ref(M * float)")   // adam: m x N, v x N, beta powers [2]; empty otherwise
+    .Attr("N: int >= 1").Attr("M: int >= 0 = 0")
+    .Attr("optimizer: {'sgd', 'adagrad', 'adam'} = 'sgd'")
+    .Attr("beta1: float = 0.9").Attr("beta2: float = 0.999").Attr("epsilon: float = 1e-8")
+    .SetIsStateful()
     .SetShapeFn([](InferenceContext* c) {
       int64 n;
       TF_RETURN_IF_ERROR(c->GetAttr("N", &n));
@@ -1450,6 +1515,7 @@ class ShardedGroupLookupGradOp : public CollectiveAsyncOp {
       string optimizer;
       OP_REQUIRES_OK(ctx, ctx->GetAttr("optimizer", &optimizer));
       OP_REQUIRES_OK(ctx, OptimizerCode(optimizer, &apply_));
+      if (apply_ == kApplyLazyAdam) OP_REQUIRES_OK(ctx, adam_.Read(ctx));
     }
   }
   void Run(OpKernelContext* ctx, HbNcclCollective* coll) override {
@@ -1489,7 +1555,24 @@ class ShardedGroupLookupGradOp : public CollectiveAsyncOp {
       OP_REQUIRES_OK(ctx, ctx->input("lr", &t));
       lr = t->scalar<float>()();
     }
-    if (APPLY) {   // step only: no IndexedSlices are written
+    if (APPLY && apply_ == kApplyLazyAdam) {   // the shards' m / v: registered with the plan per call
+      OpMutableInputList accums;
+      OP_REQUIRES_OK(ctx, ctx->mutable_input_list("accums", &accums));
+      std::vector<int64> sizes(n);
+      for (int i = 0; i < n; ++i) sizes[i] = plan->cols()[i].rows_local * plan->cols()[i].dim;
+      std::vector<float*> m, v;
+      hbk_adam_t adam;
+      std::memset(&adam, 0, sizeof(adam));
+      OP_REQUIRES_OK(ctx, AdamSlots(accums, n, sizes, &m, &v, &adam.beta_powers));
+      adam.beta1 = adam_.beta1;
+      adam.beta2 = adam_.beta2;
+      adam.epsilon = adam_.epsilon;
+      adam.finish = 1;
+      OP_REQUIRES_OK(ctx, HbkStatus(hbk_sharded_set_adam_slots(plan->plan(), m.data(), v.data())));
+      OP_REQUIRES_OK(ctx, HbkStatus(hbk_sharded_lookup_bwd_adam(plan->plan(), g.data(), nullptr, &adam,
+                                                              lr, nullptr, nullptr, counts.data(),
+                                                              StreamOf(ctx))));
+    } else if (APPLY) {   // step only: no IndexedSlices are written
       OP_REQUIRES_OK(ctx, HbkStatus(hbk_sharded_lookup_bwd_apply(plan->plan(), g.data(), nullptr, apply_,
                                                                lr, nullptr, nullptr, counts.data(),
                                                                StreamOf(ctx))));
@@ -1501,6 +1584,7 @@ class ShardedGroupLookupGradOp : public CollectiveAsyncOp {
   }
 
  private:
+  AdamAttrs adam_;
   int32_t apply_;
 };
 REGISTER_KERNEL_BUILDER(
