@@ -3567,9 +3567,68 @@ DetLayout det_layout(int32_t n_cols, const hbk_lookup_grad_column_t* cols) {
   return l;
 }
 
-int det_backward(int32_t n_cols, const hbk_lookup_grad_column_t* cols, int32_t apply, float lr,
-                 void* workspace, hipStream_t stream) {
-  const DetLayout l = det_layout(n_cols, cols);
+// workspace of a deterministic call: the sort path's arrays (`slow`, laid out by `l`), then the
+// row-sorted jobs, then the default forms
+size_t det_workspace_bytes(const DetLayout& l, const std::vector<hbk_lookup_grad_column_t>& fast,
+                           const std::vector<hbk_lookup_grad_column_t>& plain) {
+  size_t total = l.total == 0 ? 0 : l.total + 256;
+  size_t planned = 0;
+  for (const hbk_lookup_grad_column_t& h : fast) planned += col_workspace(h, true);
+  total += planned == 0 ? 0 : planned + 256;
+  planned = 0;
+  for (const hbk_lookup_grad_column_t& h : plain) planned += col_workspace(h);
+  return total + (planned == 0 ? 0 : planned + 256);
+}
+
+// Every per-column check of the forms behind the common loop (bwd_planned, det_backward, the weight
+// term pass), made before the call's first launch: a refusal from a later form would leave the
+// columns of the forms that already ran stepped, and a retry would step them twice.
+int check_layouts(int32_t n_cols, const hbk_lookup_grad_column_t* cols, float apply_lr) {
+  int64_t group_ids = 0;   // ids and live columns of det_backward's current launch group
+  int group_cols = 0;
+  for (int32_t c = 0; c < n_cols; ++c) {
+    const hbk_lookup_grad_column_t& h = cols[c];
+    if (h.n_ids <= 0) continue;
+    HBK_REQUIRE(h.grad_stride == 0 || h.grad_stride >= h.dim,
+                "group_lookup_bwd: column %d: grad_stride %d is smaller than dim %d", c,
+                h.grad_stride, h.dim);
+    const uintptr_t stride_bits = (uintptr_t)(uint32_t)h.grad_stride * 4;
+    RowShape shape;
+    if (h.id_weights != nullptr) {
+      // the term pass reads grad_out; the stages behind it see 16-byte aligned terms (and check them
+      // themselves before they step anything)
+      HBK_REQUIRE(h.n_segments == 0 || make_rowshape(h.dim, (uintptr_t)h.grad_out | stride_bits, &shape),
+                  "group_lookup_bwd: column %d: dim %d needs more than 64 lanes per row (at most 256 "
+                  "with 16-byte aligned grad_out / grad_stride, 64 otherwise)", c, h.dim);
+      continue;
+    }
+    if (det_mode(h) != 0 && !det_rowsort(h)) {   // the sort path (det_backward)
+      HBK_REQUIRE(h.dim <= kDetLanes * kDetMaxE, "group_lookup_bwd: column %d: dim %d > %d on the "
+                  "deterministic sort path", c, h.dim, kDetLanes * kDetMaxE);
+      HBK_REQUIRE(h.rows < (1ll << 40), "group_lookup_bwd: column %d: more than 2^40 rows on the "
+                  "deterministic sort path", c);
+      if (group_cols == kMaxCols) group_cols = 0, group_ids = 0;
+      ++group_cols;
+      group_ids += h.n_ids;
+      HBK_REQUIRE(group_ids < (1ll << 31), "group_lookup_bwd: column %d: more than 2^31-1 ids in one "
+                  "launch group of the deterministic sort path", c);
+      continue;
+    }
+    HBK_REQUIRE(h.grad_stride == 0 || h.n_runs == 0,
+                "group_lookup_bwd: column %d: grad_stride %d with segmented inputs", c, h.grad_stride);
+    HBK_REQUIRE(make_rowshape(h.dim,
+                              (uintptr_t)h.grad_out | (uintptr_t)h.grad_rows | stride_bits |
+                                  (apply_lr != 0.0f ? (uintptr_t)h.table | (uintptr_t)h.accum |
+                                                          ((uintptr_t)(uint32_t)h.table_pitch * 4) : 0),
+                              &shape),
+                "group_lookup_bwd: column %d: dim %d needs more than 64 lanes per row (at most 256 "
+                "with 16-byte aligned buffers and strides, 64 otherwise)", c, h.dim);
+  }
+  return HBK_OK;
+}
+
+int det_backward(int32_t n_cols, const hbk_lookup_grad_column_t* cols, const DetLayout& l,
+                 int32_t apply, float lr, void* workspace, hipStream_t stream) {
   for (int32_t c = 0; c < n_cols; ++c) {
     if (cols[c].n_ids == 0) HBK_HIP_OK(hipMemsetAsync(cols[c].n_unique, 0, sizeof(int32_t), stream));
   }
@@ -3721,14 +3780,7 @@ extern "C" size_t hbk_group_lookup_bwd_workspace_bytes(int32_t n_cols,
   if (hbk::any_deterministic(n_cols, cols)) {
     std::vector<hbk_lookup_grad_column_t> fast, slow, plain;
     hbk::det_split(n_cols, cols, &fast, &slow, &plain);
-    size_t total = hbk::det_layout((int32_t)slow.size(), slow.data()).total;
-    if (total != 0) total += 256;
-    size_t planned = 0;
-    for (const hbk_lookup_grad_column_t& h : fast) planned += hbk::col_workspace(h, true);
-    total += planned == 0 ? 0 : planned + 256;
-    planned = 0;
-    for (const hbk_lookup_grad_column_t& h : plain) planned += hbk::col_workspace(h);
-    return total + (planned == 0 ? 0 : planned + 256);
+    return hbk::det_workspace_bytes(hbk::det_layout((int32_t)slow.size(), slow.data()), fast, plain);
   }
   size_t total = 0;
   for (int32_t c = 0; c < n_cols; ++c) total += hbk::col_workspace(cols[c]);
@@ -3858,7 +3910,24 @@ extern "C" int hbk_group_lookup_bwd_apply(int32_t n_cols, const hbk_lookup_grad_
                 "group_lookup_bwd: column %d: id_weights cannot be combined with segmented inputs "
                 "(run_*: the owner-side reduce is never weighted)", c);
   }
-  const size_t need = hbk_group_lookup_bwd_workspace_bytes(n_cols, cols);
+  {
+    const int rc = check_layouts(n_cols, cols, apply_lr);
+    if (rc != HBK_OK) return rc;
+  }
+  // a deterministic call's split and the sort path's layout (two size queries of the sort / scan
+  // primitives), made once and handed down
+  const bool weighted = any_weighted(n_cols, cols);
+  const bool det = !weighted && any_deterministic(n_cols, cols);
+  std::vector<hbk_lookup_grad_column_t> fast, slow, plain;
+  DetLayout dl = {};
+  if (det) {
+    det_split(n_cols, cols, &fast, &slow, &plain);
+    dl = det_layout((int32_t)slow.size(), slow.data());
+    HBK_REQUIRE(dl.total == 0 || dl.temp_bytes > 256, "deterministic backward: the sort / scan "
+                "primitives cannot be sized on this device");
+  }
+  const size_t need = det ? det_workspace_bytes(dl, fast, plain)
+                          : hbk_group_lookup_bwd_workspace_bytes(n_cols, cols);
   HBK_REQUIRE(need == 0 || (workspace != nullptr && workspace_bytes >= need),
               "group_lookup_bwd: workspace too small: need %zu bytes, got %zu", need,
               workspace_bytes);
@@ -3870,7 +3939,7 @@ extern "C" int hbk_group_lookup_bwd_apply(int32_t n_cols, const hbk_lookup_grad_
   }
   // weighted columns: their gradient terms per id into the head of the workspace, then the call
   // over the columns as SUM columns of one id per segment
-  if (any_weighted(n_cols, cols)) {
+  if (weighted) {
     const size_t tb = weight_terms_bytes(n_cols, cols);
     char* terms = reinterpret_cast<char*>(align16(reinterpret_cast<uintptr_t>(workspace)));
     std::vector<hbk_lookup_grad_column_t> as_sum;
@@ -3883,15 +3952,12 @@ extern "C" int hbk_group_lookup_bwd_apply(int32_t n_cols, const hbk_lookup_grad_
   }
   // option bwd_deterministic: the in-order forms -- row-sorted jobs where they fit (1), the sort + walk
   // of lookup_bwd_det.h for the other columns (and for all of them under 2)
-  if (any_deterministic(n_cols, cols)) {
-    std::vector<hbk_lookup_grad_column_t> fast, slow, plain;
-    det_split(n_cols, cols, &fast, &slow, &plain);
+  if (det) {
     char* at = reinterpret_cast<char*>(workspace);
     if (!slow.empty()) {
-      const int rc = det_backward((int32_t)slow.size(), slow.data(), apply, apply_lr, at, stream);
+      const int rc = det_backward((int32_t)slow.size(), slow.data(), dl, apply, apply_lr, at, stream);
       if (rc != HBK_OK) return rc;
-      const size_t slow_bytes = det_layout((int32_t)slow.size(), slow.data()).total;
-      at += slow_bytes == 0 ? 0 : slow_bytes + 256;
+      at += dl.total == 0 ? 0 : dl.total + 256;
     }
     if (!fast.empty()) {
       const int rc = bwd_planned((int32_t)fast.size(), fast.data(), apply, apply_lr, at, stream, true);

@@ -99,6 +99,12 @@ class DenseFeatures:
       self.offsets.append(off)
       off += col.dimension
     self.width = off
+    # columns whose block the kernels cannot address: a row of more than 64 floats needs 16-byte
+    # chunks, so it must start on a 16-byte boundary of the row.  Such a column is looked up into a
+    # tensor of its own and copied into the block, and its gradient is handed over as a contiguous
+    # copy of its block; every other column keeps the block's addresses.
+    self._staged = {c for c, col in enumerate(self.columns)
+                    if col.dimension > 64 and self.offsets[c] % 4 != 0}
     self._rep = [c for c in range(len(self.columns)) if not self.sharded[c]]
     self._shd = [c for c in range(len(self.columns)) if self.sharded[c]]
     pick = lambda idx, xs: [xs[c] for c in idx]   # noqa: E731
@@ -160,20 +166,30 @@ class DenseFeatures:
     def col_views():
       return [out[:, self.offsets[c]:self.offsets[c] + self.columns[c].dimension]
               for c in range(len(self.columns))]
+    # the kernels' outputs: the block's views, a tensor of its own for a staged column
+    dests = None
+    if self._staged:
+      views = col_views()
+      dests = [torch.empty((batch or 0, self.columns[c].dimension), dtype=torch.float32,
+                           device=self.device) if c in self._staged else views[c]
+               for c in range(len(self.columns))]
     if self._rep:
       # the blocks' addresses are arithmetic: no per-column views unless somebody asks for them
       # (26 views + their validation were ~100 us of Python per step)
-      if batch and self._lookup.bind_block(pick(self._rep, ids), pick(self._rep, splits), out,
-                                           pick(self._rep, self.offsets), sp_weights=pick_w(self._rep)):
+      if (batch and dests is None and
+          self._lookup.bind_block(pick(self._rep, ids), pick(self._rep, splits), out,
+                                  pick(self._rep, self.offsets), sp_weights=pick_w(self._rep))):
         self._lookup.launch()
       else:
-        views = col_views()
-        self._lookup(pick(self._rep, ids), pick(self._rep, splits), pick(self._rep, views),
+        views = views or col_views()
+        self._lookup(pick(self._rep, ids), pick(self._rep, splits), pick(self._rep, dests or views),
                      sp_weights=pick_w(self._rep))
     if self._shd:
       views = views or col_views()
-      self._sharded(pick(self._shd, ids), pick(self._shd, splits), pick(self._shd, views),
+      self._sharded(pick(self._shd, ids), pick(self._shd, splits), pick(self._shd, dests or views),
                     sp_weights=pick_w(self._shd))
+    for c in self._staged:
+      views[c].copy_(dests[c])
     self._last = (ids, splits, ws)
     if cols_to_output_tensors is not None:
       views = views or col_views()
@@ -219,13 +235,21 @@ class DenseFeatures:
       grad = padded
     pick = lambda idx, xs: [xs[c] for c in idx]   # noqa: E731
     res = [None] * len(self.columns)
+    def col_grads():
+      return [grad[:, self.offsets[c]:self.offsets[c] + self.columns[c].dimension]
+              for c in range(len(self.columns))]
     if self._rep:
       rep_lr = apply_lr if (self.coll.world_size if self.coll is not None else 1) <= 1 else 0.0
       # the gradient's column blocks are addressed by arithmetic (no per-column views)
       # one optimizer step: the powers advance with the last call that steps (the sharded one)
-      r = self._grad(pick(self._rep, ids), None, pick(self._rep, splits),
+      grads, grad_block = None, (grad, pick(self._rep, self.offsets))
+      if any(c in self._staged for c in self._rep):
+        views = col_grads()
+        grads = [views[c].contiguous() for c in self._rep]
+        grad_block = None
+      r = self._grad(pick(self._rep, ids), grads, pick(self._rep, splits),
                      apply_lr=rep_lr, optimizer=optimizer, emit=emit or rep_lr == 0.0,
-                     grad_block=(grad, pick(self._rep, self.offsets)),
+                     grad_block=grad_block,
                      sp_weights=None if ws is None else pick(self._rep, ws),
                      finish=not (self._shd and apply_lr != 0.0))
       for k, c in enumerate(self._rep):
@@ -233,6 +257,7 @@ class DenseFeatures:
     if self._shd:
       views = [grad[:, self.offsets[c]:self.offsets[c] + self.columns[c].dimension]
                for c in self._shd]
+      views = [v.contiguous() if c in self._staged else v for c, v in zip(self._shd, views)]
       r = self._sharded.backward(views, apply_lr=apply_lr, optimizer=optimizer,
                                  emit=emit)
       for k, c in enumerate(self._shd):

@@ -248,7 +248,11 @@ typedef struct {
   const int64_t* run_base;
   int32_t n_runs;
   /* row stride of `out` in floats; 0 = dim.  Lets N columns write their blocks of one
-   * concatenated [segments, sum of dims] tensor (hb.feature_column.DenseFeatures) in place. */
+   * concatenated [segments, sum of dims] tensor (hb.feature_column.DenseFeatures) in place.
+   * Rows move in 16-byte chunks when dim % 4 == 0 and table, out and the stride are 16-byte aligned
+   * (8 bytes for fp16 rows), else in 4-byte chunks of one lane each, which hold at most 64 floats:
+   * a column of dim > 64 whose block is not 16-byte aligned is refused (INVALID_ARGUMENT).
+   * DenseFeatures looks such a column up into a tensor of its own and copies it into the block. */
   int32_t out_stride;
   /* 1: skewed ids expected (Zipf heads): wide one-id-per-segment columns (dim >= 64, 16-byte
    * chunks, plain table of < 2^32 rows) go through 256-segment tiles that fetch every row
@@ -334,7 +338,11 @@ typedef struct {
   const int64_t* run_ids;
   const int64_t* run_grads;
   int32_t n_runs;
-  int32_t grad_stride;       /* row stride of grad_out in floats; 0 = dim (see out_stride) */
+  /* row stride of grad_out in floats; 0 = dim, else >= dim.  The 16-byte / 4-byte chunk rule of
+   * out_stride holds over grad_out, grad_rows and the stride (and table, accum and table_pitch with a
+   * step); the deterministic sort path walks up to 256 floats as 4-byte chunks.  Every column is
+   * checked before the call's first launch: a refused call steps and writes nothing. */
+  int32_t grad_stride;
   float* accum;              /* Adagrad accumulator [rows, dim] (HBK_APPLY_ADAGRAD), else NULL */
   /* floats between consecutive rows of `table` AND of `accum` (round 6); 0 = dim.  Lets a caller
    * keep weights and accumulator interleaved row by row (table = buf, accum = buf + dim,

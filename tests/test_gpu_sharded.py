@@ -438,9 +438,9 @@ def test_cxx_driver_p2p_form_in_process_world(hbk_option, world, inline, id64, p
   if id64:
     hbk_option('sharded_id64', 1)
   rng = np.random.RandomState(900 + world)
-  # (a dim-6 column -- 4-byte chunks -- only with separate outputs: inside one wide tensor it would
-  # take the rows of the wide columns off the 16-byte boundaries their chunks need)
-  dims = [16, 128, 4, 32, 8 if block else 6]
+  # (a dim-6 column -- 4-byte chunks -- in the wide tensor too: its rows are padded to 16 bytes, so
+  # the wide columns before it keep the 16-byte boundaries their chunks need)
+  dims = [16, 128, 4, 32, 6]
   rows = [50021, 3000, 64, 100003, 211]
   n = len(dims)
   batch = 1500
@@ -459,7 +459,7 @@ def test_cxx_driver_p2p_form_in_process_world(hbk_option, world, inline, id64, p
       with torch.cuda.stream(torch.cuda.Stream()):
         drv = ShardedGroupLookup(shards[r], comms[r], buckets=rows)
         if block:
-          wide = torch.full((batch, sum(dims)), float('nan'), device=DEV)
+          wide = torch.full((batch, (sum(dims) + 3) // 4 * 4), float('nan'), device=DEV)
           outs, at = [], 0
           for d in dims:
             outs.append(wide[:, at:at + d])
