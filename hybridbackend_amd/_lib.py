@@ -66,6 +66,12 @@ class AdamParams(C.Structure):
               ('beta_powers', C.c_void_p), ('finish', C.c_int32)]
 
 
+class FtrlParams(C.Structure):
+  """hbk_ftrl_t"""
+  _fields_ = [('l1', C.c_float), ('l2', C.c_float), ('l2_shrinkage', C.c_float),
+              ('lr_power', C.c_float)]
+
+
 class ShardedColumn(C.Structure):
   """hbk_sharded_column_t"""
   _fields_ = [('shard', C.c_void_p), ('rows_local', C.c_int64), ('dim', C.c_int32),
@@ -123,6 +129,8 @@ def _declare(l):
     'hbk_group_lookup_bwd_apply': (C.c_int, [i32, vp, i32, C.c_float, vp, sz, vp]),
     'hbk_group_lookup_bwd_adam_workspace_bytes': (sz, [i32, vp]),
     'hbk_group_lookup_bwd_adam': (C.c_int, [i32, vp, vp, vp, vp, C.c_float, vp, sz, vp]),
+    'hbk_group_lookup_bwd_ftrl_workspace_bytes': (sz, [i32, vp]),
+    'hbk_group_lookup_bwd_ftrl': (C.c_int, [i32, vp, vp, vp, vp, C.c_float, vp, sz, vp]),
     'hbk_group_stitch_bwd': (C.c_int, [i32, vp, vp]),
     'hbk_cache_probe': (C.c_int, [vp, i64, i32, vp, i64, vp, vp, vp]),
     'hbk_cache_lookup_workspace_bytes': (sz, [i64]),
@@ -161,6 +169,8 @@ def _declare(l):
     'hbk_sharded_lookup_bwd_apply': (C.c_int, [vp, vp, vp, i32, C.c_float, vp, vp, vp, vp]),
     'hbk_sharded_set_adam_slots': (C.c_int, [vp, vp, vp]),
     'hbk_sharded_lookup_bwd_adam': (C.c_int, [vp, vp, vp, vp, C.c_float, vp, vp, vp, vp]),
+    'hbk_sharded_set_ftrl_slots': (C.c_int, [vp, vp, vp]),
+    'hbk_sharded_lookup_bwd_ftrl': (C.c_int, [vp, vp, vp, vp, C.c_float, vp, vp, vp, vp]),
   }
   for name, (res, args) in protos.items():
     fn = getattr(l, name)   # AttributeError here = header and library out of sync
@@ -297,24 +307,42 @@ def set_adam_slots(plan, moments):
                                          ptr_array([v.data_ptr() for _, v in moments])))
 
 
-def require_moments(moments, tables, what):
-  """(m, v) per table: fp32 device tensors of the table's shape, contiguous, all distinct."""
+def set_ftrl_slots(plan, slots):
+  """hbk_sharded_set_ftrl_slots: every column's (accum, linear) slot shards of a sharded plan."""
+  check(lib().hbk_sharded_set_ftrl_slots(plan, ptr_array([a.data_ptr() for a, _ in slots]),
+                                         ptr_array([z.data_ptr() for _, z in slots])))
+
+
+def require_slot_pairs(pairs, tables, what, kw='moments', names=('m', 'v')):
+  """Two slots per table (Adam's (m, v), FTRL's (accum, linear)): fp32 device tensors of the table's
+  shape, contiguous, all distinct."""
   import torch  # pylint: disable=import-outside-toplevel
-  moments = [tuple(p) for p in moments]
-  if len(moments) != len(tables):
-    raise InvalidArgumentError(INVALID_ARGUMENT, f'{what}: {len(moments)} (m, v) pairs for '
+  pairs = [tuple(p) for p in pairs]
+  pair = f'({names[0]}, {names[1]})'
+  if len(pairs) != len(tables):
+    raise InvalidArgumentError(INVALID_ARGUMENT, f'{what}: {len(pairs)} {pair} pairs for '
                                f'{len(tables)} tables')
-  for c, (pair, t) in enumerate(zip(moments, tables)):
-    if len(pair) != 2:
-      raise InvalidArgumentError(INVALID_ARGUMENT, f'{what}: moments[{c}] must be an (m, v) pair')
-    for name, x in zip(('m', 'v'), pair):
-      require_device_tensor(x, f'{what}: moments[{c}].{name}')
+  for c, (two, t) in enumerate(zip(pairs, tables)):
+    if len(two) != 2:
+      raise InvalidArgumentError(INVALID_ARGUMENT, f'{what}: {kw}[{c}] must be an {pair} pair')
+    for name, x in zip(names, two):
+      require_device_tensor(x, f'{what}: {kw}[{c}].{name}')
       if x.dtype != torch.float32 or tuple(x.shape) != tuple(t.shape):
         raise InvalidArgumentError(INVALID_ARGUMENT,
-                                   f'{what}: moments[{c}].{name} must be fp32 {tuple(t.shape)}')
-  # Adam is not additive: a buffer stepped as two slots (or as a slot and a table) would race
-  ptrs = [x.data_ptr() for pair in moments for x in pair] + [t.data_ptr() for t in tables]
+                                   f'{what}: {kw}[{c}].{name} must be fp32 {tuple(t.shape)}')
+  # neither step is additive: a buffer stepped as two slots (or as a slot and a table) would race
+  ptrs = [x.data_ptr() for two in pairs for x in two] + [t.data_ptr() for t in tables]
   if len(set(ptrs)) != len(ptrs):
-    raise InvalidArgumentError(INVALID_ARGUMENT, f'{what}: the m / v tensors and the tables must '
-                               'all be distinct buffers')
-  return moments
+    raise InvalidArgumentError(INVALID_ARGUMENT, f'{what}: the {names[0]} / {names[1]} tensors and '
+                               'the tables must all be distinct buffers')
+  return pairs
+
+
+def require_moments(moments, tables, what):
+  """(m, v) per table: fp32 device tensors of the table's shape, contiguous, all distinct."""
+  return require_slot_pairs(moments, tables, what)
+
+
+def require_ftrl_slots(slots, tables, what):
+  """(accum, linear) per table: fp32 device tensors of the table's shape, contiguous, all distinct."""
+  return require_slot_pairs(slots, tables, what, 'ftrl_slots', ('accum', 'linear'))

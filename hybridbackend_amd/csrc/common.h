@@ -264,6 +264,8 @@ int sync_check_any(const char* who);
 
 // host checks of a Lazy Adam call's hyperparameters (sparse_apply.hip): HBK_OK or HBK_INVALID_ARGUMENT
 int adam_check(const hbk_adam_t* adam, float lr, const char* who);
+// host checks of an FTRL call's hyperparameters (sparse_apply.hip): HBK_OK or HBK_INVALID_ARGUMENT
+int ftrl_check(const hbk_ftrl_t* ftrl, float lr, const char* who);
 
 constexpr int kWave = 64;  // gfx950 wavefront
 

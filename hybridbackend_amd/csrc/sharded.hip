@@ -538,6 +538,7 @@ struct hbk_sharded {
                                      // distinct ids when the column is deduplicated)
   std::vector<const int32_t*> row_splits;
   std::vector<float*> adam_m, adam_v;     // [N] Lazy Adam moment shards (hbk_sharded_set_adam_slots), or empty
+  std::vector<float*> ftrl_accum, ftrl_linear;   // [N] FTRL slot shards (hbk_sharded_set_ftrl_slots), or empty
   std::vector<const float*> id_weights;   // [N] per-id weights of the last forward (NULL: unweighted):
                                           // the stitch applies them, the backward's stitch too
   std::vector<int32_t> send_sizes;   // S [N][W] rows this rank requests from owner q, column c
@@ -1742,12 +1743,23 @@ extern "C" int hbk_sharded_lookup_bwd(hbk_sharded_t p, const float* const* grads
                                       unique_rows, grad_rows, n_unique, stream_);
 }
 
-// the backward of hbk_sharded_lookup_bwd_apply, or -- adam != NULL -- of hbk_sharded_lookup_bwd_adam
+namespace {
+// the optimizer step of a sharded backward: the reduce's own SGD / Adagrad (apply), or -- adam or ftrl
+// set -- a two-slot step after the owner-side reduce in its emit form
+struct ShardedStep {
+  int32_t apply;
+  const hbk_adam_t* adam;
+  const hbk_ftrl_t* ftrl;
+};
+}  // namespace
+
+// the backward of hbk_sharded_lookup_bwd_apply, hbk_sharded_lookup_bwd_adam and _ftrl
 static int sharded_bwd(hbk_sharded_t p, const float* const* grads, const int32_t* grad_strides,
-                       int32_t apply, float apply_lr, const hbk_adam_t* adam,
-                       int64_t* const* unique_rows, float* const* grad_rows, int32_t* const* n_unique,
-                       hbk_stream_t stream_) {
+                       const ShardedStep& step, float apply_lr, int64_t* const* unique_rows,
+                       float* const* grad_rows, int32_t* const* n_unique, hbk_stream_t stream_) {
   using namespace hbk;
+  const hbk_adam_t* const adam = step.adam;
+  const hbk_ftrl_t* const ftrl = step.ftrl;
   HBK_REQUIRE(p != nullptr, "sharded_lookup_bwd: plan is NULL");
   HBK_REQUIRE(p->have_step, "sharded_lookup_bwd: no forward step to differentiate");
   HBK_REQUIRE(grads && n_unique, "sharded_lookup_bwd: NULL argument array");
@@ -1895,7 +1907,7 @@ static int sharded_bwd(hbk_sharded_t p, const float* const* grads, const int32_t
     hbk_lookup_grad_column_t& h = v[c];
     memset(&h, 0, sizeof(h));
     h.table = const_cast<float*>(p->cols[c].shard);
-    h.accum = adam != nullptr ? nullptr : p->cols[c].accum;
+    h.accum = adam != nullptr || ftrl != nullptr ? nullptr : p->cols[c].accum;
     h.rows = p->cols[c].rows_local;
     h.dim = p->cols[c].dim;
     h.ids_dtype = p->id32 ? HBK_INT32 : HBK_INT64;
@@ -1916,9 +1928,10 @@ static int sharded_bwd(hbk_sharded_t p, const float* const* grads, const int32_t
   size_t ws = 0;
   for (int g = 0; g < G; ++g) {
     const Group& gr = p->groups[g];
-    const size_t w = adam != nullptr
-                         ? hbk_group_lookup_bwd_adam_workspace_bytes(gr.c1 - gr.c0, v.data() + gr.c0)
-                         : hbk_group_lookup_bwd_workspace_bytes(gr.c1 - gr.c0, v.data() + gr.c0);
+    const size_t w =
+        adam != nullptr ? hbk_group_lookup_bwd_adam_workspace_bytes(gr.c1 - gr.c0, v.data() + gr.c0)
+        : ftrl != nullptr ? hbk_group_lookup_bwd_ftrl_workspace_bytes(gr.c1 - gr.c0, v.data() + gr.c0)
+                          : hbk_group_lookup_bwd_workspace_bytes(gr.c1 - gr.c0, v.data() + gr.c0);
     ws = w > ws ? w : ws;
   }
   if ((rc = p->bwd_ws.ensure(ws + 8)) != HBK_OK) return rc;
@@ -1931,8 +1944,12 @@ static int sharded_bwd(hbk_sharded_t p, const float* const* grads, const int32_t
       rc = hbk_group_lookup_bwd_adam(gr.c1 - gr.c0, v.data() + gr.c0, p->adam_m.data() + gr.c0,
                                      p->adam_v.data() + gr.c0, &a, apply_lr, p->bwd_ws.ptr,
                                      p->bwd_ws.bytes, stream_);
+    } else if (ftrl != nullptr) {   // FTRL: the emit-form reduce + the apply
+      rc = hbk_group_lookup_bwd_ftrl(gr.c1 - gr.c0, v.data() + gr.c0, p->ftrl_accum.data() + gr.c0,
+                                     p->ftrl_linear.data() + gr.c0, ftrl, apply_lr, p->bwd_ws.ptr,
+                                     p->bwd_ws.bytes, stream_);
     } else {
-      rc = hbk_group_lookup_bwd_apply(gr.c1 - gr.c0, v.data() + gr.c0, apply, apply_lr,
+      rc = hbk_group_lookup_bwd_apply(gr.c1 - gr.c0, v.data() + gr.c0, step.apply, apply_lr,
                                       p->bwd_ws.ptr, p->bwd_ws.bytes, stream_);
     }
     if (rc != HBK_OK) return rc;
@@ -1945,8 +1962,8 @@ extern "C" int hbk_sharded_lookup_bwd_apply(hbk_sharded_t p, const float* const*
                                             float apply_lr, int64_t* const* unique_rows,
                                             float* const* grad_rows, int32_t* const* n_unique,
                                             hbk_stream_t stream_) {
-  return sharded_bwd(p, grads, grad_strides, apply, apply_lr, nullptr, unique_rows, grad_rows,
-                     n_unique, stream_);
+  return sharded_bwd(p, grads, grad_strides, ShardedStep{apply, nullptr, nullptr}, apply_lr,
+                     unique_rows, grad_rows, n_unique, stream_);
 }
 
 extern "C" int hbk_sharded_set_adam_slots(hbk_sharded_t p, float* const* m, float* const* v) {
@@ -1996,8 +2013,62 @@ extern "C" int hbk_sharded_lookup_bwd_adam(hbk_sharded_t p, const float* const* 
     HBK_REQUIRE(p->cols[c].accum == nullptr,
                 "sharded_lookup_bwd_adam: column %d: accum must be NULL (Adam's slots are m and v)", c);
   }
-  return sharded_bwd(p, grads, grad_strides, HBK_APPLY_SGD, lr, adam, unique_rows, grad_rows,
-                     n_unique, stream_);
+  return sharded_bwd(p, grads, grad_strides, ShardedStep{HBK_APPLY_SGD, adam, nullptr}, lr,
+                     unique_rows, grad_rows, n_unique, stream_);
+}
+
+extern "C" int hbk_sharded_set_ftrl_slots(hbk_sharded_t p, float* const* accum, float* const* linear) {
+  using namespace hbk;
+  HBK_REQUIRE(p != nullptr, "sharded_set_ftrl_slots: plan is NULL");
+  HBK_REQUIRE(accum != nullptr && linear != nullptr,
+              "sharded_set_ftrl_slots: the accum / linear arrays are NULL");
+  for (int c = 0; c < p->N; ++c) {
+    HBK_REQUIRE(accum[c] != nullptr, "sharded_set_ftrl_slots: column %d: accum is NULL", c);
+    HBK_REQUIRE(linear[c] != nullptr, "sharded_set_ftrl_slots: column %d: linear is NULL", c);
+    HBK_REQUIRE(accum[c] != linear[c],
+                "sharded_set_ftrl_slots: column %d: accum and linear are the same buffer", c);
+    HBK_REQUIRE(accum[c] != p->cols[c].shard && linear[c] != p->cols[c].shard,
+                "sharded_set_ftrl_slots: column %d: accum or linear is the shard (table)", c);
+  }
+  // no slot twice, and no slot that is some column's shard: checked here, before any backward
+  // exchanges (the per-group apply would only see the columns of its own launch group)
+  std::vector<uintptr_t> seen;
+  for (int c = 0; c < p->N; ++c) {
+    seen.push_back((uintptr_t)accum[c]);
+    seen.push_back((uintptr_t)linear[c]);
+  }
+  std::sort(seen.begin(), seen.end());
+  HBK_REQUIRE(std::adjacent_find(seen.begin(), seen.end()) == seen.end(),
+              "sharded_set_ftrl_slots: two columns share an accum or linear buffer");
+  for (int c = 0; c < p->N; ++c) {
+    HBK_REQUIRE(!std::binary_search(seen.begin(), seen.end(), (uintptr_t)p->cols[c].shard),
+                "sharded_set_ftrl_slots: column %d's shard (table) is also an accum or linear slot", c);
+  }
+  p->ftrl_accum.assign(accum, accum + p->N);
+  p->ftrl_linear.assign(linear, linear + p->N);
+  return HBK_OK;
+}
+
+extern "C" int hbk_sharded_lookup_bwd_ftrl(hbk_sharded_t p, const float* const* grads,
+                                           const int32_t* grad_strides, const hbk_ftrl_t* ftrl,
+                                           float lr, int64_t* const* unique_rows,
+                                           float* const* grad_rows, int32_t* const* n_unique,
+                                           hbk_stream_t stream_) {
+  using namespace hbk;
+  HBK_REQUIRE(p != nullptr, "sharded_lookup_bwd_ftrl: plan is NULL");
+  {
+    const int rc = ftrl_check(ftrl, lr, "sharded_lookup_bwd_ftrl");
+    if (rc != HBK_OK) return rc;
+  }
+  HBK_REQUIRE((int)p->ftrl_accum.size() == p->N,
+              "sharded_lookup_bwd_ftrl: no accum / linear slots (hbk_sharded_set_ftrl_slots)");
+  for (int c = 0; c < p->N; ++c) {
+    HBK_REQUIRE(p->cols[c].accum == nullptr,
+                "sharded_lookup_bwd_ftrl: column %d: the column's accum must be NULL (FTRL's slots "
+                "come from hbk_sharded_set_ftrl_slots)", c);
+  }
+  return sharded_bwd(p, grads, grad_strides, ShardedStep{HBK_APPLY_SGD, nullptr, ftrl}, lr,
+                     unique_rows, grad_rows, n_unique, stream_);
 }
 
 // the per-column hot_rows hints of a live plan (hbk_sharded_column_t.hot_rows): the host side turns

@@ -347,7 +347,7 @@ class GroupLookupGrad:
   """
 
   def __init__(self, lookup, accums=None, interleaved=None, workspace_of=None, deterministic=False,
-               moments=None, adam=None):
+               moments=None, adam=None, ftrl_slots=None, ftrl=None):
     """deterministic: every row's gradient terms are summed in id order (``HBK_GRAD_DETERMINISTIC`` on
     every column): IndexedSlices and stepped tables have the same bits on every run, equal to the
     sequential fp32 sum -- TF's CPU ``UnsortedSegmentSum`` -- and the rows leave ascending.  What the
@@ -371,7 +371,11 @@ class GroupLookupGrad:
     moments: per column the Lazy Adam slots ``(m, v)`` (fp32, same shape as the weights, zeros to
     start), needed for ``optimizer='adam'``; adam: the :class:`LazyAdam` whose beta powers the steps
     use and advance (one object per optimizer, shared with everything it steps; a new one with TF's
-    defaults when omitted)."""
+    defaults when omitted).
+
+    ftrl_slots: per column the FTRL slots ``(accum, linear)`` (fp32, same shape as the weights; accum
+    filled with ``initial_accumulator_value``, linear zeros: :meth:`Ftrl.slots_like`), needed for
+    ``optimizer='ftrl'``; ftrl: the :class:`Ftrl` hyperparameters (TF's defaults when omitted)."""
     self._lib = _lib.lib()
     self.lookup = lookup
     n = len(lookup)
@@ -384,6 +388,15 @@ class GroupLookupGrad:
       if self.adam is None:
         from hybridbackend_amd.embedding.optimizer import LazyAdam  # pylint: disable=import-outside-toplevel
         self.adam = LazyAdam(device=lookup.tables[0].device if n else None)
+    self.ftrl_slots = None
+    self.ftrl = ftrl
+    if ftrl_slots is not None:
+      self.ftrl_slots = _lib.require_ftrl_slots(ftrl_slots, lookup.tables, 'GroupLookupGrad')
+      self._acc_ptrs = _lib.ptr_array([a.data_ptr() for a, _ in self.ftrl_slots])
+      self._lin_ptrs = _lib.ptr_array([z.data_ptr() for _, z in self.ftrl_slots])
+      if self.ftrl is None:
+        from hybridbackend_amd.embedding.optimizer import Ftrl  # pylint: disable=import-outside-toplevel
+        self.ftrl = Ftrl()
     self.accums = list(accums) if accums is not None else None
     self.interleaved = list(interleaved) if interleaved is not None else None
     if self.interleaved is not None and self.accums is None:
@@ -496,13 +509,18 @@ class GroupLookupGrad:
     returned triple is meaningful.  ``sp_weights``: the forward's per-id weights (per column None
     or fp32 ``[n_ids]``); no gradient is produced for them.  ``optimizer='adam'`` (with ``apply_lr``
     and ``moments``): the Lazy Adam step (:class:`LazyAdam`); ``finish=False`` leaves the beta powers
-    for a later call of the same optimizer step to advance."""
-    if optimizer not in ('sgd', 'adagrad', 'adam'):
+    for a later call of the same optimizer step to advance.  ``optimizer='ftrl'`` (with ``apply_lr``
+    and ``ftrl_slots``): the FTRL-Proximal step (:class:`Ftrl`)."""
+    if optimizer not in ('sgd', 'adagrad', 'adam', 'ftrl'):
       raise _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT,
-                                      "optimizer must be 'sgd', 'adagrad' or 'adam'")
+                                      "optimizer must be 'sgd', 'adagrad', 'adam' or 'ftrl'")
     if optimizer == 'adam' and self.moments is None:
       raise _lib.InvalidArgumentError(
         _lib.INVALID_ARGUMENT, "optimizer='adam' needs GroupLookupGrad(lookup, moments=[(m, v), ...])")
+    if optimizer == 'ftrl' and self.ftrl_slots is None:
+      raise _lib.InvalidArgumentError(
+        _lib.INVALID_ARGUMENT,
+        "optimizer='ftrl' needs GroupLookupGrad(lookup, ftrl_slots=[(accum, linear), ...])")
     if not emit and apply_lr == 0.0:
       raise _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT, 'emit=False needs apply_lr != 0')
     n = len(self.lookup)
@@ -598,10 +616,12 @@ class GroupLookupGrad:
     if n:
       self._cols_np['id_weights'] = _marshal.weight_ptrs(sp_weights, ids)
     need = self._lib.hbk_group_lookup_bwd_workspace_bytes(n, self._cols)   # (depends on options too)
-    self._adam_cd = None
-    if self.moments is not None:   # (sized for the Adam form too: launch() may take either)
-      self._adam_cd = self._adam_form()
-      need = max(need, self._lib.hbk_group_lookup_bwd_adam_workspace_bytes(n, self._adam_cd))
+    self._slot_cd = None
+    if self.moments is not None or self.ftrl_slots is not None:
+      # (sized for the two-slot forms too: launch() may take any of them)
+      self._slot_cd = self._slot_form()
+      need = max(need, self._lib.hbk_group_lookup_bwd_adam_workspace_bytes(n, self._slot_cd),
+                 self._lib.hbk_group_lookup_bwd_ftrl_workspace_bytes(n, self._slot_cd))
     if self._ws is None or self._ws.numel() < need:
       self._ws = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
     self._ws_bound = self._ws       # (launch(): the workspace this binding was sized for)
@@ -615,9 +635,9 @@ class GroupLookupGrad:
     self._bound_call = (emit, [int(i.numel()) for i in ids])
     return list(self._views)
 
-  def _adam_form(self):
-    """The descriptors of the Adam form: the bound ones without Adagrad accumulators (a copy, made
-    once per binding call, only when the object keeps accumulators too)."""
+  def _slot_form(self):
+    """The descriptors of the Adam and FTRL forms: the bound ones without Adagrad accumulators (a
+    copy, made once per binding call, only when the object keeps accumulators too)."""
     if self.accums is None:
       return self._cols
     cols = type(self._cols).from_buffer_copy(self._cols)
@@ -628,7 +648,13 @@ class GroupLookupGrad:
   def _step(self, n, optimizer, apply_lr, finish, ws, dev):
     if optimizer == 'adam' and apply_lr != 0.0:
       _lib.check(self._lib.hbk_group_lookup_bwd_adam(
-        n, self._adam_cd, self._m_ptrs, self._v_ptrs, C.byref(self.adam.params(finish)),
+        n, self._slot_cd, self._m_ptrs, self._v_ptrs, C.byref(self.adam.params(finish)),
+        C.c_float(apply_lr), C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()),
+        _lib.current_stream(dev)))
+      return
+    if optimizer == 'ftrl' and apply_lr != 0.0:
+      _lib.check(self._lib.hbk_group_lookup_bwd_ftrl(
+        n, self._slot_cd, self._acc_ptrs, self._lin_ptrs, C.byref(self.ftrl.params()),
         C.c_float(apply_lr), C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()),
         _lib.current_stream(dev)))
       return
@@ -654,6 +680,10 @@ class GroupLookupGrad:
     if optimizer == 'adam' and self.moments is None:
       raise _lib.InvalidArgumentError(
         _lib.INVALID_ARGUMENT, "optimizer='adam' needs GroupLookupGrad(lookup, moments=[(m, v), ...])")
+    if optimizer == 'ftrl' and self.ftrl_slots is None:
+      raise _lib.InvalidArgumentError(
+        _lib.INVALID_ARGUMENT,
+        "optimizer='ftrl' needs GroupLookupGrad(lookup, ftrl_slots=[(accum, linear), ...])")
     dev = self.lookup.tables[0].device if len(self.lookup) else None
     self._step(len(self.lookup), optimizer, apply_lr, finish, self._ws_bound, dev)
     if self.lookup._auto_hot:

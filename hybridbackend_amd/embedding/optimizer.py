@@ -1,5 +1,7 @@
-"""Lazy Adam (``tf.contrib.opt.LazyAdamOptimizer``, TF 1.15): the state every step of one optimizer
-shares -- the hyperparameters and the device-side beta powers."""
+"""The two-slot sparse optimizers' shared state: Lazy Adam (``tf.contrib.opt.LazyAdamOptimizer``,
+TF 1.15) -- the hyperparameters and the device-side beta powers -- and FTRL-Proximal
+(``tf.train.FtrlOptimizer``, TF 1.15) -- the hyperparameters only."""
+import math
 import ctypes as C
 
 import torch
@@ -50,3 +52,46 @@ class LazyAdam:
                           self.beta_powers.data_ptr(), 1 if finish else 0)
       self._params[key] = p
     return p
+
+
+class Ftrl:
+  """The sparse FTRL-Proximal step of ``GroupLookupGrad`` / ``ShardedGroupLookup`` / ``DenseFeatures``
+  with ``optimizer='ftrl'`` (TF 1.15 ``SparseApplyFtrl`` / ``SparseApplyFtrlV2``, the sparse apply of
+  ``tf.train.FtrlOptimizer``): for every distinct row r of a step, with its deduplicated gradient g,
+  in fp32, a = accum[r], z = linear[r], w = weights[r]::
+
+      gs = g if l2_shrinkage == 0 else g + (2 * l2_shrinkage) * w
+      na = a + g * g
+      p(x) = sqrt(x) if lr_power == -0.5 else x ** -lr_power
+      z  = z + (gs - ((p(na) - p(a)) / lr) * w)
+      w  = (clip(z, -l1, l1) - z) / (p(na) / lr + 2 * l2)
+      a  = na
+
+  Rows that do not occur in the step are not touched, as in TF's sparse apply.  The slots are the
+  accumulator (filled with ``initial_accumulator_value``) and the linear term (zeros).  There is no
+  device state: one object may serve any number of calls."""
+
+  def __init__(self, l1=0.0, l2=0.0, l2_shrinkage=0.0, lr_power=-0.5, initial_accumulator_value=0.1):
+    # tf.train.FtrlOptimizer.__init__ and the SparseApplyFtrl kernel refuse the same
+    for name, x in (('l1', l1), ('l2', l2), ('l2_shrinkage', l2_shrinkage)):
+      if not (math.isfinite(float(x)) and float(x) >= 0.0):
+        raise _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT, f'{name} must be finite and >= 0, got {x}')
+    if not (math.isfinite(float(lr_power)) and float(lr_power) <= 0.0):
+      raise _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT,
+                                      f'lr_power must be finite and <= 0, got {lr_power}')
+    if not float(initial_accumulator_value) >= 0.0:
+      raise _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT, 'initial_accumulator_value must be >= 0, '
+                                      f'got {initial_accumulator_value}')
+    self.l1, self.l2, self.l2_shrinkage = float(l1), float(l2), float(l2_shrinkage)
+    self.lr_power = float(lr_power)
+    self.initial_accumulator_value = float(initial_accumulator_value)
+    self._params = _lib.FtrlParams(C.c_float(self.l1), C.c_float(self.l2),
+                                   C.c_float(self.l2_shrinkage), C.c_float(self.lr_power))
+
+  def params(self):
+    """The ``hbk_ftrl_t`` of a call (kept alive by this object)."""
+    return self._params
+
+  def slots_like(self, table):
+    """A new ``(accum, linear)`` pair for ``table``: TF's initial values."""
+    return (torch.full_like(table, self.initial_accumulator_value), torch.zeros_like(table))

@@ -81,7 +81,8 @@ class ShardedGroupLookup:
   """
 
   def __init__(self, shards, coll, buckets=None, combiners='sum', wire_dtype=None,
-               world_size=None, accums=None, hot_rows=False, dedup=False, moments=None, adam=None):
+               world_size=None, accums=None, hot_rows=False, dedup=False, moments=None, adam=None,
+               ftrl_slots=None, ftrl=None):
     self.shards = list(shards)
     # Adagrad accumulators of the shards (same shapes), for backward(optimizer='adagrad')
     self.accums = list(accums) if accums is not None else None
@@ -94,6 +95,15 @@ class ShardedGroupLookup:
       if self.adam is None:
         from hybridbackend_amd.embedding.optimizer import LazyAdam  # pylint: disable=import-outside-toplevel
         self.adam = LazyAdam(device=self.shards[0].device)
+    # FTRL slots of the shards ((accum, linear) per column, same shapes) and their hyperparameters,
+    # for backward(optimizer='ftrl')
+    self.ftrl_slots = None
+    self.ftrl = ftrl
+    if ftrl_slots is not None:
+      self.ftrl_slots = _lib.require_ftrl_slots(ftrl_slots, self.shards, 'ShardedGroupLookup')
+      if self.ftrl is None:
+        from hybridbackend_amd.embedding.optimizer import Ftrl  # pylint: disable=import-outside-toplevel
+        self.ftrl = Ftrl()
     self.coll = coll
     self.world_size = int(world_size if world_size is not None else coll.world_size)
     n = len(self.shards)
@@ -187,6 +197,8 @@ class ShardedGroupLookup:
       C.byref(self._plan_handle), self.coll._handle, n, cols, wire))
     if self.moments is not None:
       _lib.set_adam_slots(self._plan_handle, self.moments)
+    if self.ftrl_slots is not None:
+      _lib.set_ftrl_slots(self._plan_handle, self.ftrl_slots)
 
   def last_host_us(self):
     """Host time of the last forward step in microseconds: (enqueueing the partition and the
@@ -496,17 +508,23 @@ class ShardedGroupLookup:
     (collective.py:334-347): no new size exchange, no host sync.  ``emit=False`` (with
     ``apply_lr``): step only, no IndexedSlices are written (only the ``n_unique`` counts).
     ``optimizer='adam'`` (with ``apply_lr`` and ``moments``): the Lazy Adam step on the shards
-    (hbk_sharded_lookup_bwd_adam); ``finish=False`` leaves the beta powers to a later call."""
+    (hbk_sharded_lookup_bwd_adam); ``finish=False`` leaves the beta powers to a later call.
+    ``optimizer='ftrl'`` (with ``apply_lr`` and ``ftrl_slots``): the FTRL-Proximal step on the shards
+    (hbk_sharded_lookup_bwd_ftrl)."""
     if not emit and apply_lr == 0.0:
       raise _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT, 'emit=False needs apply_lr != 0')
     n = len(self.shards)
     plan = self._plan()
-    if optimizer not in ('sgd', 'adagrad', 'adam'):
+    if optimizer not in ('sgd', 'adagrad', 'adam', 'ftrl'):
       raise _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT,
-                                      "optimizer must be 'sgd', 'adagrad' or 'adam'")
+                                      "optimizer must be 'sgd', 'adagrad', 'adam' or 'ftrl'")
     if optimizer == 'adam' and self.moments is None:
       raise _lib.InvalidArgumentError(
         _lib.INVALID_ARGUMENT, "optimizer='adam' needs ShardedGroupLookup(..., moments=[(m, v), ...])")
+    if optimizer == 'ftrl' and self.ftrl_slots is None:
+      raise _lib.InvalidArgumentError(
+        _lib.INVALID_ARGUMENT,
+        "optimizer='ftrl' needs ShardedGroupLookup(..., ftrl_slots=[(accum, linear), ...])")
     res = []
     shapes = getattr(self, '_last_shapes', None)
     auto = bool(self._auto_hot) and outs is None
@@ -554,6 +572,13 @@ class ShardedGroupLookup:
       _lib.check(self._lib.hbk_sharded_lookup_bwd_adam(
         plan, _lib.ptr_array([g.data_ptr() for g in grads]), strides,
         C.byref(self.adam.params(finish)), C.c_float(apply_lr),
+        _lib.ptr_array([r[0].data_ptr() for r in res]) if emit else None,
+        _lib.ptr_array([r[1].data_ptr() for r in res]) if emit else None,
+        _lib.ptr_array([r[2].data_ptr() for r in res]), _lib.current_stream(self.device)))
+    elif optimizer == 'ftrl' and apply_lr != 0.0:
+      _lib.check(self._lib.hbk_sharded_lookup_bwd_ftrl(
+        plan, _lib.ptr_array([g.data_ptr() for g in grads]), strides,
+        C.byref(self.ftrl.params()), C.c_float(apply_lr),
         _lib.ptr_array([r[0].data_ptr() for r in res]) if emit else None,
         _lib.ptr_array([r[1].data_ptr() for r in res]) if emit else None,
         _lib.ptr_array([r[2].data_ptr() for r in res]), _lib.current_stream(self.device)))

@@ -413,6 +413,31 @@ int hbk_group_lookup_bwd_adam(int32_t n_cols, const hbk_lookup_grad_column_t* co
                               float* const* m, float* const* v, const hbk_adam_t* adam, float lr,
                               void* workspace, size_t workspace_bytes, hbk_stream_t stream);
 
+/* FTRL-Proximal: TF 1.15 SparseApplyFtrl / SparseApplyFtrlV2 on the deduplicated gradient g of every
+ * distinct row r of the call, each a separately rounded fp32 op in this order (a = accum[r],
+ * z = linear[r], w = weights[r], the old values):
+ *     gs = l2_shrinkage == 0 ? g : g + (2 * l2_shrinkage) * w
+ *     na = a + g * g
+ *     p(x) = lr_power == -0.5 ? sqrtf(x) : powf(x, -lr_power)
+ *     z  = z + (gs - ((p(na) - p(a)) / lr) * w)
+ *     y  = p(na) / lr + (2 * l2)
+ *     w  = (clamp(z, -l1, l1) - z) / y;   a = na
+ * Rows that do not occur are not touched.  The phases, the pitch (cols[c].table_pitch for weights,
+ * accum[c] and linear[c]: [w | accum | linear | pad] may be interleaved), step only, the dim limits and
+ * the refusal of a table or slot named twice are hbk_group_lookup_bwd_adam's; cols[c].accum must be
+ * NULL.  Refused before any device work: lr <= 0 or not finite; l1, l2 or l2_shrinkage < 0 or not
+ * finite; lr_power > 0 or not finite.  lr_power = -0.5 (TF's default) runs an instantiation without
+ * powf; powf is not correctly rounded, so other powers may differ from a host powf in the last bit.
+ * Detected by the presence of the symbol. */
+typedef struct {
+  float l1, l2, l2_shrinkage, lr_power;
+} hbk_ftrl_t;
+size_t hbk_group_lookup_bwd_ftrl_workspace_bytes(int32_t n_cols,
+                                                 const hbk_lookup_grad_column_t* cols);
+int hbk_group_lookup_bwd_ftrl(int32_t n_cols, const hbk_lookup_grad_column_t* cols,
+                              float* const* accum, float* const* linear, const hbk_ftrl_t* ftrl,
+                              float lr, void* workspace, size_t workspace_bytes, hbk_stream_t stream);
+
 /* R10 (sharded form)  d(stitch + combiner): the transpose of the requester-side
  *   `gather(embeddings, shard_index)` + combiner (hbtf/embedding/sharding.py:200; TF emits
  *   SparseSegment*Grad followed by an UnsortedSegmentSum over a permutation):
@@ -728,6 +753,16 @@ int hbk_sharded_lookup_bwd_apply(hbk_sharded_t plan, const float* const* grads,
 int hbk_sharded_set_adam_slots(hbk_sharded_t plan, float* const* m, float* const* v);
 int hbk_sharded_lookup_bwd_adam(hbk_sharded_t plan, const float* const* grads,
                                 const int32_t* grad_strides, const hbk_adam_t* adam, float lr,
+                                int64_t* const* unique_rows, float* const* grad_rows,
+                                int32_t* const* n_unique, hbk_stream_t stream);
+/* FTRL on the shards (hbk_group_lookup_bwd_ftrl), as the Lazy Adam pair: hbk_sharded_set_ftrl_slots
+ * registers every column's accum / linear shard ([rows_local, dim], as the column's shard; the
+ * columns' accum must be NULL), then hbk_sharded_lookup_bwd_ftrl runs the owner-side reduce in its emit
+ * form and the apply, launch group by launch group.  unique_rows and grad_rows may both be NULL (step
+ * only). */
+int hbk_sharded_set_ftrl_slots(hbk_sharded_t plan, float* const* accum, float* const* linear);
+int hbk_sharded_lookup_bwd_ftrl(hbk_sharded_t plan, const float* const* grads,
+                                const int32_t* grad_strides, const hbk_ftrl_t* ftrl, float lr,
                                 int64_t* const* unique_rows, float* const* grad_rows,
                                 int32_t* const* n_unique, hbk_stream_t stream);
 

@@ -936,8 +936,10 @@ REGISTER_OP("HbGroupLookupGradApply")
     .Input("lr: float")
     .Attr("N: int >= 1").Attr("M: int >= 0 = 0").Attr("Tids: {int32, int64}")
     .Attr("buckets: list(int)").Attr("combiners: list(int)").Attr("ragged: list(bool)")
-    .Attr("divisor: int = 1").Attr("optimizer: {'sgd', 'adagrad', 'adam'} = 'sgd'")
+    .Attr("divisor: int = 1").Attr("optimizer: {'sgd', 'adagrad', 'adam', 'ftrl'} = 'sgd'")
     .Attr("beta1: float = 0.9").Attr("beta2: float = 0.999").Attr("epsilon: float = 1e-8")
+    .Attr("l1: float = 0").Attr("l2: float = 0").Attr("l2_shrinkage: float = 0")
+    .Attr("lr_power: float = -0.5")
     .Attr("deterministic: bool = false")
     .SetIsStateful()
     .SetShapeFn([](InferenceContext* c) {
@@ -966,8 +968,10 @@ REGISTER_OP("HbGroupLookupWeightedGradApply")
     .Input("grads: N * float").Input("lr: float")
     .Attr("N: int >= 1").Attr("M: int >= 0 = 0").Attr("Tids: {int32, int64}")
     .Attr("buckets: list(int)").Attr("combiners: list(int)").Attr("ragged: list(bool)")
-    .Attr("divisor: int = 1").Attr("optimizer: {'sgd', 'adagrad', 'adam'} = 'sgd'")
+    .Attr("divisor: int = 1").Attr("optimizer: {'sgd', 'adagrad', 'adam', 'ftrl'} = 'sgd'")
     .Attr("beta1: float = 0.9").Attr("beta2: float = 0.999").Attr("epsilon: float = 1e-8")
+    .Attr("l1: float = 0").Attr("l2: float = 0").Attr("l2_shrinkage: float = 0")
+    .Attr("lr_power: float = -0.5")
     .Attr("deterministic: bool = false")
     .SetIsStateful()
     .SetShapeFn([](InferenceContext* c) {
@@ -1076,12 +1080,47 @@ REGISTER_KERNEL_BUILDER(Name("HbGroupLookupWeightedGrad").Device(DEVICE_GPU).Typ
 // optimizer='adam': tf.contrib.opt.LazyAdamOptimizer's sparse apply (hbk_group_lookup_bwd_adam /
 // hbk_sharded_lookup_bwd_adam); `accums` then holds m x N, v x N and the [2] beta powers (M = 2N + 1),
 // and the op advances the powers after its step (TF's _finish)
-constexpr int32_t kApplyLazyAdam = -1;   // (the shim's own code: the C ABI has a separate entry)
+// optimizer='ftrl': TF's SparseApplyFtrl[V2] (hbk_group_lookup_bwd_ftrl / hbk_sharded_lookup_bwd_ftrl);
+// `accums` then holds accum x N, then linear x N (M = 2N)
+constexpr int32_t kApplyLazyAdam = -1;   // (the shim's own codes: the C ABI has separate entries)
+constexpr int32_t kApplyFtrl = -2;
 static Status OptimizerCode(const string& name, int32_t* apply) {
   if (name == "sgd") { *apply = HBK_APPLY_SGD; return Status::OK(); }
   if (name == "adagrad") { *apply = HBK_APPLY_ADAGRAD; return Status::OK(); }
   if (name == "adam") { *apply = kApplyLazyAdam; return Status::OK(); }
-  return errors::InvalidArgument("optimizer must be 'sgd', 'adagrad' or 'adam', got ", name);
+  if (name == "ftrl") { *apply = kApplyFtrl; return Status::OK(); }
+  return errors::InvalidArgument("optimizer must be 'sgd', 'adagrad', 'adam' or 'ftrl', got ", name);
+}
+
+struct FtrlAttrs {
+  hbk_ftrl_t ftrl = {0.0f, 0.0f, 0.0f, -0.5f};
+  Status Read(OpKernelConstruction* ctx) {
+    TF_RETURN_IF_ERROR(ctx->GetAttr("l1", &ftrl.l1));
+    TF_RETURN_IF_ERROR(ctx->GetAttr("l2", &ftrl.l2));
+    TF_RETURN_IF_ERROR(ctx->GetAttr("l2_shrinkage", &ftrl.l2_shrinkage));
+    return ctx->GetAttr("lr_power", &ftrl.lr_power);
+  }
+};
+
+// the slots of an FTRL call out of `accums` (accum x N, linear x N)
+static Status FtrlSlots(OpMutableInputList& accums, int n, const std::vector<int64>& sizes,
+                        std::vector<float*>* accum, std::vector<float*>* linear) {
+  if (accums.size() != 2 * n) {
+    return errors::InvalidArgument("accums: ftrl takes accum x N, then linear x N (M = ", 2 * n,
+                                   "), got ", accums.size());
+  }
+  accum->resize(n);
+  linear->resize(n);
+  for (int i = 0; i < n; ++i) {
+    Tensor at = accums.at(i, /*lock_held=*/false);
+    Tensor lt = accums.at(n + i, /*lock_held=*/false);
+    if (at.NumElements() != sizes[i] || lt.NumElements() != sizes[i]) {
+      return errors::InvalidArgument("accum / linear ", i, " must have its variable's shape");
+    }
+    (*accum)[i] = at.flat<float>().data();
+    (*linear)[i] = lt.flat<float>().data();
+  }
+  return Status::OK();
 }
 
 struct AdamAttrs {
@@ -1126,6 +1165,7 @@ class GroupLookupGradApplyOp : public OpKernel {
     OP_REQUIRES_OK(ctx, ctx->GetAttr("optimizer", &optimizer));
     OP_REQUIRES_OK(ctx, OptimizerCode(optimizer, &apply_));
     if (apply_ == kApplyLazyAdam) OP_REQUIRES_OK(ctx, adam_.Read(ctx));
+    if (apply_ == kApplyFtrl) OP_REQUIRES_OK(ctx, ftrl_.Read(ctx));
   }
   void Compute(OpKernelContext* ctx) override {
     OpMutableInputList w, accums;
@@ -1139,7 +1179,8 @@ class GroupLookupGradApplyOp : public OpKernel {
     OP_REQUIRES_OK(ctx, ctx->input("lr", &lr));
     const int n = w.size();
     OP_REQUIRES_OK(ctx, attrs_.Check(n));
-    OP_REQUIRES(ctx, apply_ == kApplyLazyAdam || accums.size() == (apply_ == HBK_APPLY_ADAGRAD ? n : 0),
+    OP_REQUIRES(ctx, apply_ == kApplyLazyAdam || apply_ == kApplyFtrl ||
+                         accums.size() == (apply_ == HBK_APPLY_ADAGRAD ? n : 0),
                 errors::InvalidArgument("accums: N accumulators for adagrad, none for sgd"));
     std::vector<const float*> sp_weights;
     OP_REQUIRES_OK(ctx, SpWeights(ctx, kWeighted, n, ids, &sp_weights));
@@ -1177,6 +1218,20 @@ class GroupLookupGradApplyOp : public OpKernel {
                               ws.flat<int8>().data(), ws_bytes + 16, StreamOf(ctx))));
       return;
     }
+    if (apply_ == kApplyFtrl) {
+      std::vector<int64> sizes(n);
+      for (int i = 0; i < n; ++i) sizes[i] = w.at(i, /*lock_held=*/false).NumElements();
+      std::vector<float*> accum, linear;
+      OP_REQUIRES_OK(ctx, FtrlSlots(accums, n, sizes, &accum, &linear));
+      const size_t ws_bytes = hbk_group_lookup_bwd_ftrl_workspace_bytes(n, cols.data());
+      Tensor ws;
+      OP_REQUIRES_OK(ctx, AllocScratch(ctx, ws_bytes, &ws));
+      OP_REQUIRES_OK(ctx, HbkStatus(hbk_group_lookup_bwd_ftrl(
+                              n, cols.data(), accum.data(), linear.data(), &ftrl_.ftrl,
+                              lr->scalar<float>()(), ws.flat<int8>().data(), ws_bytes + 16,
+                              StreamOf(ctx))));
+      return;
+    }
     const size_t ws_bytes = hbk_group_lookup_bwd_workspace_bytes(n, cols.data());
     Tensor ws;
     OP_REQUIRES_OK(ctx, AllocScratch(ctx, ws_bytes, &ws));
@@ -1188,6 +1243,7 @@ class GroupLookupGradApplyOp : public OpKernel {
  private:
   GroupLookupAttrs attrs_;
   AdamAttrs adam_;
+  FtrlAttrs ftrl_;
   int32_t apply_;
 };
 REGISTER_KERNEL_BUILDER(Name("HbGroupLookupGradApply").Device(DEVICE_GPU).HostMemory("lr")
@@ -1494,10 +1550,12 @@ REGISTER_OP("HbShardedGroupLookupGrad")
 REGISTER_OP("HbShardedGroupLookupGradApply")
     .Output("n_unique: N * int32")
     .Input("handle: resource").Input("plan: resource").Input("grads: N * float").Input("lr: float")
-    .Input("accums: Ref(M * float)")   // adam: m x N, v x N, beta powers [2]; empty otherwise
+    .Input("accums: Ref(M * float)")   // adam: m x N, v x N, beta powers [2]; ftrl: accum x N, linear x N; empty otherwise
     .Attr("N: int >= 1").Attr("M: int >= 0 = 0")
-    .Attr("optimizer: {'sgd', 'adagrad', 'adam'} = 'sgd'")
+    .Attr("optimizer: {'sgd', 'adagrad', 'adam', 'ftrl'} = 'sgd'")
     .Attr("beta1: float = 0.9").Attr("beta2: float = 0.999").Attr("epsilon: float = 1e-8")
+    .Attr("l1: float = 0").Attr("l2: float = 0").Attr("l2_shrinkage: float = 0")
+    .Attr("lr_power: float = -0.5")
     .SetIsStateful()
     .SetShapeFn([](InferenceContext* c) {
       int64 n;
@@ -1516,6 +1574,7 @@ class ShardedGroupLookupGradOp : public CollectiveAsyncOp {
       OP_REQUIRES_OK(ctx, ctx->GetAttr("optimizer", &optimizer));
       OP_REQUIRES_OK(ctx, OptimizerCode(optimizer, &apply_));
       if (apply_ == kApplyLazyAdam) OP_REQUIRES_OK(ctx, adam_.Read(ctx));
+      if (apply_ == kApplyFtrl) OP_REQUIRES_OK(ctx, ftrl_.Read(ctx));
     }
   }
   void Run(OpKernelContext* ctx, HbNcclCollective* coll) override {
@@ -1572,6 +1631,18 @@ class ShardedGroupLookupGradOp : public CollectiveAsyncOp {
       OP_REQUIRES_OK(ctx, HbkStatus(hbk_sharded_lookup_bwd_adam(plan->plan(), g.data(), nullptr, &adam,
                                                               lr, nullptr, nullptr, counts.data(),
                                                               StreamOf(ctx))));
+    } else if (APPLY && apply_ == kApplyFtrl) {   // the shards' accum / linear, registered per call
+      OpMutableInputList accums;
+      OP_REQUIRES_OK(ctx, ctx->mutable_input_list("accums", &accums));
+      std::vector<int64> sizes(n);
+      for (int i = 0; i < n; ++i) sizes[i] = plan->cols()[i].rows_local * plan->cols()[i].dim;
+      std::vector<float*> accum, linear;
+      OP_REQUIRES_OK(ctx, FtrlSlots(accums, n, sizes, &accum, &linear));
+      OP_REQUIRES_OK(ctx, HbkStatus(hbk_sharded_set_ftrl_slots(plan->plan(), accum.data(),
+                                                             linear.data())));
+      OP_REQUIRES_OK(ctx, HbkStatus(hbk_sharded_lookup_bwd_ftrl(plan->plan(), g.data(), nullptr,
+                                                              &ftrl_.ftrl, lr, nullptr, nullptr,
+                                                              counts.data(), StreamOf(ctx))));
     } else if (APPLY) {   // step only: no IndexedSlices are written
       OP_REQUIRES_OK(ctx, HbkStatus(hbk_sharded_lookup_bwd_apply(plan->plan(), g.data(), nullptr, apply_,
                                                                lr, nullptr, nullptr, counts.data(),
@@ -1585,6 +1656,7 @@ class ShardedGroupLookupGradOp : public CollectiveAsyncOp {
 
  private:
   AdamAttrs adam_;
+  FtrlAttrs ftrl_;
   int32_t apply_;
 };
 REGISTER_KERNEL_BUILDER(
