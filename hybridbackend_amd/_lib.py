@@ -301,18 +301,6 @@ def require_device_tensor(t, what, row_strided=False):
   raise InvalidArgumentError(INVALID_ARGUMENT, f'{what} must be contiguous')
 
 
-def set_adam_slots(plan, moments):
-  """hbk_sharded_set_adam_slots: every column's (m, v) moment shards of a sharded plan."""
-  check(lib().hbk_sharded_set_adam_slots(plan, ptr_array([m.data_ptr() for m, _ in moments]),
-                                         ptr_array([v.data_ptr() for _, v in moments])))
-
-
-def set_ftrl_slots(plan, slots):
-  """hbk_sharded_set_ftrl_slots: every column's (accum, linear) slot shards of a sharded plan."""
-  check(lib().hbk_sharded_set_ftrl_slots(plan, ptr_array([a.data_ptr() for a, _ in slots]),
-                                         ptr_array([z.data_ptr() for _, z in slots])))
-
-
 def require_slot_pairs(pairs, tables, what, kw='moments', names=('m', 'v')):
   """Two slots per table (Adam's (m, v), FTRL's (accum, linear)): fp32 device tensors of the table's
   shape, contiguous, all distinct."""
@@ -337,12 +325,3 @@ def require_slot_pairs(pairs, tables, what, kw='moments', names=('m', 'v')):
                                'the tables must all be distinct buffers')
   return pairs
 
-
-def require_moments(moments, tables, what):
-  """(m, v) per table: fp32 device tensors of the table's shape, contiguous, all distinct."""
-  return require_slot_pairs(moments, tables, what)
-
-
-def require_ftrl_slots(slots, tables, what):
-  """(accum, linear) per table: fp32 device tensors of the table's shape, contiguous, all distinct."""
-  return require_slot_pairs(slots, tables, what, 'ftrl_slots', ('accum', 'linear'))

@@ -262,10 +262,20 @@ class SyncChain {
 int sync_check(const char* who, hipStream_t stream);
 int sync_check_any(const char* who);
 
+// the names a two-slot optimizer call's refusals use (sparse_apply.hip, sharded.hip)
+struct SlotNames {
+  const char* who;   // "group_lookup_bwd_adam"
+  const char* opt;   // "Adam"
+  const char* s0;    // "m"
+  const char* s1;    // "v"
+};
 // host checks of a Lazy Adam call's hyperparameters (sparse_apply.hip): HBK_OK or HBK_INVALID_ARGUMENT
 int adam_check(const hbk_adam_t* adam, float lr, const char* who);
 // host checks of an FTRL call's hyperparameters (sparse_apply.hip): HBK_OK or HBK_INVALID_ARGUMENT
 int ftrl_check(const hbk_ftrl_t* ftrl, float lr, const char* who);
+
+// compute units of the current device (cached; lookup_bwd.hip)
+int device_cus();
 
 constexpr int kWave = 64;  // gfx950 wavefront
 

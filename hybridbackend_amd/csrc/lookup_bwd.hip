@@ -3795,17 +3795,7 @@ extern "C" int hbk_group_lookup_bwd(int32_t n_cols, const hbk_lookup_grad_column
 }
 
 namespace hbk {
-namespace {
-// Four streams and their fork / join events per device, kept for the life of the process.  The
-// mutex is held while a call enqueues on them (host side only: microseconds).
-constexpr int kHelperStreams = 4;
-struct BwdHelpers {
-  hipStream_t s[kHelperStreams];
-  hipEvent_t fork, join[kHelperStreams];
-  std::mutex mu;
-};
-
-// compute units of the current device (cached)
+// compute units of the current device (cached; common.h)
 int device_cus() {
   static std::mutex mu;
   static std::map<int, int> cus;
@@ -3821,6 +3811,16 @@ int device_cus() {
   cus[dev] = n;
   return n;
 }
+
+namespace {
+// Four streams and their fork / join events per device, kept for the life of the process.  The
+// mutex is held while a call enqueues on them (host side only: microseconds).
+constexpr int kHelperStreams = 4;
+struct BwdHelpers {
+  hipStream_t s[kHelperStreams];
+  hipEvent_t fork, join[kHelperStreams];
+  std::mutex mu;
+};
 
 BwdHelpers* bwd_helpers(hipStream_t caller) {
   static std::mutex table_mu;

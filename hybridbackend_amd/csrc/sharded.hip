@@ -26,6 +26,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <functional>
 #include <random>
 #include <utility>
 #include <vector>
@@ -512,6 +513,11 @@ struct Layout {
   }
 };
 
+// a two-slot optimizer's slot shards, one per column (hbk_sharded_set_*_slots), or empty
+struct SlotPair {
+  std::vector<float*> s0, s1;
+};
+
 // One column group of the pipelined step: its own peer-major regions in the exchange buffers.
 struct Group {
   int c0, c1;
@@ -537,8 +543,8 @@ struct hbk_sharded {
   std::vector<int64_t> n_sent;       // ids of column c this rank put on the wire (= n_ids, or its
                                      // distinct ids when the column is deduplicated)
   std::vector<const int32_t*> row_splits;
-  std::vector<float*> adam_m, adam_v;     // [N] Lazy Adam moment shards (hbk_sharded_set_adam_slots), or empty
-  std::vector<float*> ftrl_accum, ftrl_linear;   // [N] FTRL slot shards (hbk_sharded_set_ftrl_slots), or empty
+  hbk::SlotPair adam;   // Lazy Adam's m / v shards (hbk_sharded_set_adam_slots)
+  hbk::SlotPair ftrl;   // FTRL's accum / linear shards (hbk_sharded_set_ftrl_slots)
   std::vector<const float*> id_weights;   // [N] per-id weights of the last forward (NULL: unweighted):
                                           // the stitch applies them, the backward's stitch too
   std::vector<int32_t> send_sizes;   // S [N][W] rows this rank requests from owner q, column c
@@ -1744,12 +1750,15 @@ extern "C" int hbk_sharded_lookup_bwd(hbk_sharded_t p, const float* const* grads
 }
 
 namespace {
-// the optimizer step of a sharded backward: the reduce's own SGD / Adagrad (apply), or -- adam or ftrl
-// set -- a two-slot step after the owner-side reduce in its emit form
+// the optimizer step of a sharded backward: the reduce's own SGD / Adagrad (apply), or -- with
+// workspace_bytes set -- a two-slot step after the owner-side reduce in its emit form: its workspace
+// query and its call on one launch group (columns c0 .., the last group or not)
 struct ShardedStep {
   int32_t apply;
-  const hbk_adam_t* adam;
-  const hbk_ftrl_t* ftrl;
+  size_t (*workspace_bytes)(int32_t n_cols, const hbk_lookup_grad_column_t* cols);
+  std::function<int(int32_t c0, int32_t n_cols, const hbk_lookup_grad_column_t* cols, bool last,
+                    void* workspace, size_t workspace_bytes, hbk_stream_t stream)>
+      run;
 };
 }  // namespace
 
@@ -1758,8 +1767,7 @@ static int sharded_bwd(hbk_sharded_t p, const float* const* grads, const int32_t
                        const ShardedStep& step, float apply_lr, int64_t* const* unique_rows,
                        float* const* grad_rows, int32_t* const* n_unique, hbk_stream_t stream_) {
   using namespace hbk;
-  const hbk_adam_t* const adam = step.adam;
-  const hbk_ftrl_t* const ftrl = step.ftrl;
+  const bool two_slot = step.workspace_bytes != nullptr;
   HBK_REQUIRE(p != nullptr, "sharded_lookup_bwd: plan is NULL");
   HBK_REQUIRE(p->have_step, "sharded_lookup_bwd: no forward step to differentiate");
   HBK_REQUIRE(grads && n_unique, "sharded_lookup_bwd: NULL argument array");
@@ -1907,7 +1915,7 @@ static int sharded_bwd(hbk_sharded_t p, const float* const* grads, const int32_t
     hbk_lookup_grad_column_t& h = v[c];
     memset(&h, 0, sizeof(h));
     h.table = const_cast<float*>(p->cols[c].shard);
-    h.accum = adam != nullptr || ftrl != nullptr ? nullptr : p->cols[c].accum;
+    h.accum = two_slot ? nullptr : p->cols[c].accum;
     h.rows = p->cols[c].rows_local;
     h.dim = p->cols[c].dim;
     h.ids_dtype = p->id32 ? HBK_INT32 : HBK_INT64;
@@ -1928,30 +1936,18 @@ static int sharded_bwd(hbk_sharded_t p, const float* const* grads, const int32_t
   size_t ws = 0;
   for (int g = 0; g < G; ++g) {
     const Group& gr = p->groups[g];
-    const size_t w =
-        adam != nullptr ? hbk_group_lookup_bwd_adam_workspace_bytes(gr.c1 - gr.c0, v.data() + gr.c0)
-        : ftrl != nullptr ? hbk_group_lookup_bwd_ftrl_workspace_bytes(gr.c1 - gr.c0, v.data() + gr.c0)
-                          : hbk_group_lookup_bwd_workspace_bytes(gr.c1 - gr.c0, v.data() + gr.c0);
+    const size_t w = (two_slot ? step.workspace_bytes : hbk_group_lookup_bwd_workspace_bytes)(
+        gr.c1 - gr.c0, v.data() + gr.c0);
     ws = w > ws ? w : ws;
   }
   if ((rc = p->bwd_ws.ensure(ws + 8)) != HBK_OK) return rc;
   for (int g = 0; g < G; ++g) {
     const Group& gr = p->groups[g];
     if (hop) HBK_HIP_OK(hipStreamWaitEvent(stream, p->ev[1][g], 0));
-    if (adam != nullptr) {   // Lazy Adam: the emit-form reduce + the apply; the last group finishes
-      hbk_adam_t a = *adam;
-      a.finish = g == G - 1 ? adam->finish : 0;
-      rc = hbk_group_lookup_bwd_adam(gr.c1 - gr.c0, v.data() + gr.c0, p->adam_m.data() + gr.c0,
-                                     p->adam_v.data() + gr.c0, &a, apply_lr, p->bwd_ws.ptr,
-                                     p->bwd_ws.bytes, stream_);
-    } else if (ftrl != nullptr) {   // FTRL: the emit-form reduce + the apply
-      rc = hbk_group_lookup_bwd_ftrl(gr.c1 - gr.c0, v.data() + gr.c0, p->ftrl_accum.data() + gr.c0,
-                                     p->ftrl_linear.data() + gr.c0, ftrl, apply_lr, p->bwd_ws.ptr,
-                                     p->bwd_ws.bytes, stream_);
-    } else {
-      rc = hbk_group_lookup_bwd_apply(gr.c1 - gr.c0, v.data() + gr.c0, step.apply, apply_lr,
-                                      p->bwd_ws.ptr, p->bwd_ws.bytes, stream_);
-    }
+    rc = two_slot ? step.run(gr.c0, gr.c1 - gr.c0, v.data() + gr.c0, g == G - 1, p->bwd_ws.ptr,
+                             p->bwd_ws.bytes, stream_)
+                  : hbk_group_lookup_bwd_apply(gr.c1 - gr.c0, v.data() + gr.c0, step.apply, apply_lr,
+                                               p->bwd_ws.ptr, p->bwd_ws.bytes, stream_);
     if (rc != HBK_OK) return rc;
   }
   return HBK_OK;
@@ -1966,34 +1962,62 @@ extern "C" int hbk_sharded_lookup_bwd_apply(hbk_sharded_t p, const float* const*
                      unique_rows, grad_rows, n_unique, stream_);
 }
 
-extern "C" int hbk_sharded_set_adam_slots(hbk_sharded_t p, float* const* m, float* const* v) {
+namespace {
+// a two-slot optimizer's slot shards, checked and registered with the plan
+int set_slot_pair(hbk_sharded_t p, const hbk::SlotNames& nm, float* const* s0, float* const* s1,
+                  hbk::SlotPair hbk_sharded::*pair) {
   using namespace hbk;
-  HBK_REQUIRE(p != nullptr, "sharded_set_adam_slots: plan is NULL");
-  HBK_REQUIRE(m != nullptr && v != nullptr, "sharded_set_adam_slots: the m / v arrays are NULL");
+  const char* who = nm.who;
+  HBK_REQUIRE(p != nullptr, "%s: plan is NULL", who);
+  HBK_REQUIRE(s0 != nullptr && s1 != nullptr, "%s: the %s / %s arrays are NULL", who, nm.s0, nm.s1);
   for (int c = 0; c < p->N; ++c) {
-    HBK_REQUIRE(m[c] != nullptr, "sharded_set_adam_slots: column %d: m is NULL", c);
-    HBK_REQUIRE(v[c] != nullptr, "sharded_set_adam_slots: column %d: v is NULL", c);
-    HBK_REQUIRE(m[c] != v[c], "sharded_set_adam_slots: column %d: m and v are the same buffer", c);
-    HBK_REQUIRE(m[c] != p->cols[c].shard && v[c] != p->cols[c].shard,
-                "sharded_set_adam_slots: column %d: m or v is the shard (table)", c);
+    HBK_REQUIRE(s0[c] != nullptr, "%s: column %d: %s is NULL", who, c, nm.s0);
+    HBK_REQUIRE(s1[c] != nullptr, "%s: column %d: %s is NULL", who, c, nm.s1);
+    HBK_REQUIRE(s0[c] != s1[c], "%s: column %d: %s and %s are the same buffer", who, c, nm.s0, nm.s1);
+    HBK_REQUIRE(s0[c] != p->cols[c].shard && s1[c] != p->cols[c].shard,
+                "%s: column %d: %s or %s is the shard (table)", who, c, nm.s0, nm.s1);
   }
   // no slot twice, and no slot that is some column's shard: checked here, before any backward
   // exchanges (the per-group apply would only see the columns of its own launch group)
   std::vector<uintptr_t> seen;
   for (int c = 0; c < p->N; ++c) {
-    seen.push_back((uintptr_t)m[c]);
-    seen.push_back((uintptr_t)v[c]);
+    seen.push_back((uintptr_t)s0[c]);
+    seen.push_back((uintptr_t)s1[c]);
   }
   std::sort(seen.begin(), seen.end());
   HBK_REQUIRE(std::adjacent_find(seen.begin(), seen.end()) == seen.end(),
-              "sharded_set_adam_slots: two columns share an m or v buffer");
+              "%s: two columns share an %s or %s buffer", who, nm.s0, nm.s1);
   for (int c = 0; c < p->N; ++c) {
     HBK_REQUIRE(!std::binary_search(seen.begin(), seen.end(), (uintptr_t)p->cols[c].shard),
-                "sharded_set_adam_slots: column %d's shard (table) is also an m or v slot", c);
+                "%s: column %d's shard (table) is also an %s or %s slot", who, c, nm.s0, nm.s1);
   }
-  p->adam_m.assign(m, m + p->N);
-  p->adam_v.assign(v, v + p->N);
+  (p->*pair).s0.assign(s0, s0 + p->N);
+  (p->*pair).s1.assign(s1, s1 + p->N);
   return HBK_OK;
+}
+
+// the host checks of a sharded two-slot backward before any exchange: the plan, the hyperparameters
+// (check()), slots registered by `setter`, no column with an Adagrad accumulator
+template <typename Check>
+int two_slot_prologue(hbk_sharded_t p, const hbk::SlotNames& nm, Check check, const char* setter,
+                      hbk::SlotPair hbk_sharded::*pair) {
+  using namespace hbk;
+  HBK_REQUIRE(p != nullptr, "%s: plan is NULL", nm.who);
+  const int rc = check();
+  if (rc != HBK_OK) return rc;
+  HBK_REQUIRE((int)(p->*pair).s0.size() == p->N, "%s: no %s / %s slots (%s)", nm.who, nm.s0, nm.s1,
+              setter);
+  for (int c = 0; c < p->N; ++c) {
+    HBK_REQUIRE(p->cols[c].accum == nullptr,
+                "%s: column %d: the column's accum must be NULL (%s's slots are %s and %s, from %s)",
+                nm.who, c, nm.opt, nm.s0, nm.s1, setter);
+  }
+  return HBK_OK;
+}
+}  // namespace
+
+extern "C" int hbk_sharded_set_adam_slots(hbk_sharded_t p, float* const* m, float* const* v) {
+  return set_slot_pair(p, {"sharded_set_adam_slots", "Adam", "m", "v"}, m, v, &hbk_sharded::adam);
 }
 
 extern "C" int hbk_sharded_lookup_bwd_adam(hbk_sharded_t p, const float* const* grads,
@@ -2002,51 +2026,25 @@ extern "C" int hbk_sharded_lookup_bwd_adam(hbk_sharded_t p, const float* const* 
                                            float* const* grad_rows, int32_t* const* n_unique,
                                            hbk_stream_t stream_) {
   using namespace hbk;
-  HBK_REQUIRE(p != nullptr, "sharded_lookup_bwd_adam: plan is NULL");
-  {
-    const int rc = adam_check(adam, lr, "sharded_lookup_bwd_adam");
-    if (rc != HBK_OK) return rc;
-  }
-  HBK_REQUIRE((int)p->adam_m.size() == p->N,
-              "sharded_lookup_bwd_adam: no m / v slots (hbk_sharded_set_adam_slots)");
-  for (int c = 0; c < p->N; ++c) {
-    HBK_REQUIRE(p->cols[c].accum == nullptr,
-                "sharded_lookup_bwd_adam: column %d: accum must be NULL (Adam's slots are m and v)", c);
-  }
-  return sharded_bwd(p, grads, grad_strides, ShardedStep{HBK_APPLY_SGD, adam, nullptr}, lr,
-                     unique_rows, grad_rows, n_unique, stream_);
+  static const SlotNames kNames = {"sharded_lookup_bwd_adam", "Adam", "m", "v"};
+  const int rc = two_slot_prologue(p, kNames, [&] { return adam_check(adam, lr, kNames.who); },
+                                   "hbk_sharded_set_adam_slots", &hbk_sharded::adam);
+  if (rc != HBK_OK) return rc;
+  const ShardedStep step{HBK_APPLY_SGD, hbk_group_lookup_bwd_adam_workspace_bytes,
+                         [&](int32_t c0, int32_t n, const hbk_lookup_grad_column_t* cols, bool last,
+                             void* ws, size_t ws_bytes, hbk_stream_t s) {
+                           hbk_adam_t a = *adam;
+                           a.finish = last ? adam->finish : 0;   // the last launch group finishes
+                           return hbk_group_lookup_bwd_adam(n, cols, p->adam.s0.data() + c0,
+                                                            p->adam.s1.data() + c0, &a, lr, ws,
+                                                            ws_bytes, s);
+                         }};
+  return sharded_bwd(p, grads, grad_strides, step, lr, unique_rows, grad_rows, n_unique, stream_);
 }
 
 extern "C" int hbk_sharded_set_ftrl_slots(hbk_sharded_t p, float* const* accum, float* const* linear) {
-  using namespace hbk;
-  HBK_REQUIRE(p != nullptr, "sharded_set_ftrl_slots: plan is NULL");
-  HBK_REQUIRE(accum != nullptr && linear != nullptr,
-              "sharded_set_ftrl_slots: the accum / linear arrays are NULL");
-  for (int c = 0; c < p->N; ++c) {
-    HBK_REQUIRE(accum[c] != nullptr, "sharded_set_ftrl_slots: column %d: accum is NULL", c);
-    HBK_REQUIRE(linear[c] != nullptr, "sharded_set_ftrl_slots: column %d: linear is NULL", c);
-    HBK_REQUIRE(accum[c] != linear[c],
-                "sharded_set_ftrl_slots: column %d: accum and linear are the same buffer", c);
-    HBK_REQUIRE(accum[c] != p->cols[c].shard && linear[c] != p->cols[c].shard,
-                "sharded_set_ftrl_slots: column %d: accum or linear is the shard (table)", c);
-  }
-  // no slot twice, and no slot that is some column's shard: checked here, before any backward
-  // exchanges (the per-group apply would only see the columns of its own launch group)
-  std::vector<uintptr_t> seen;
-  for (int c = 0; c < p->N; ++c) {
-    seen.push_back((uintptr_t)accum[c]);
-    seen.push_back((uintptr_t)linear[c]);
-  }
-  std::sort(seen.begin(), seen.end());
-  HBK_REQUIRE(std::adjacent_find(seen.begin(), seen.end()) == seen.end(),
-              "sharded_set_ftrl_slots: two columns share an accum or linear buffer");
-  for (int c = 0; c < p->N; ++c) {
-    HBK_REQUIRE(!std::binary_search(seen.begin(), seen.end(), (uintptr_t)p->cols[c].shard),
-                "sharded_set_ftrl_slots: column %d's shard (table) is also an accum or linear slot", c);
-  }
-  p->ftrl_accum.assign(accum, accum + p->N);
-  p->ftrl_linear.assign(linear, linear + p->N);
-  return HBK_OK;
+  return set_slot_pair(p, {"sharded_set_ftrl_slots", "FTRL", "accum", "linear"}, accum, linear,
+                       &hbk_sharded::ftrl);
 }
 
 extern "C" int hbk_sharded_lookup_bwd_ftrl(hbk_sharded_t p, const float* const* grads,
@@ -2055,20 +2053,18 @@ extern "C" int hbk_sharded_lookup_bwd_ftrl(hbk_sharded_t p, const float* const* 
                                            float* const* grad_rows, int32_t* const* n_unique,
                                            hbk_stream_t stream_) {
   using namespace hbk;
-  HBK_REQUIRE(p != nullptr, "sharded_lookup_bwd_ftrl: plan is NULL");
-  {
-    const int rc = ftrl_check(ftrl, lr, "sharded_lookup_bwd_ftrl");
-    if (rc != HBK_OK) return rc;
-  }
-  HBK_REQUIRE((int)p->ftrl_accum.size() == p->N,
-              "sharded_lookup_bwd_ftrl: no accum / linear slots (hbk_sharded_set_ftrl_slots)");
-  for (int c = 0; c < p->N; ++c) {
-    HBK_REQUIRE(p->cols[c].accum == nullptr,
-                "sharded_lookup_bwd_ftrl: column %d: the column's accum must be NULL (FTRL's slots "
-                "come from hbk_sharded_set_ftrl_slots)", c);
-  }
-  return sharded_bwd(p, grads, grad_strides, ShardedStep{HBK_APPLY_SGD, nullptr, ftrl}, lr,
-                     unique_rows, grad_rows, n_unique, stream_);
+  static const SlotNames kNames = {"sharded_lookup_bwd_ftrl", "FTRL", "accum", "linear"};
+  const int rc = two_slot_prologue(p, kNames, [&] { return ftrl_check(ftrl, lr, kNames.who); },
+                                   "hbk_sharded_set_ftrl_slots", &hbk_sharded::ftrl);
+  if (rc != HBK_OK) return rc;
+  const ShardedStep step{HBK_APPLY_SGD, hbk_group_lookup_bwd_ftrl_workspace_bytes,
+                         [&](int32_t c0, int32_t n, const hbk_lookup_grad_column_t* cols, bool,
+                             void* ws, size_t ws_bytes, hbk_stream_t s) {
+                           return hbk_group_lookup_bwd_ftrl(n, cols, p->ftrl.s0.data() + c0,
+                                                            p->ftrl.s1.data() + c0, ftrl, lr, ws,
+                                                            ws_bytes, s);
+                         }};
+  return sharded_bwd(p, grads, grad_strides, step, lr, unique_rows, grad_rows, n_unique, stream_);
 }
 
 // the per-column hot_rows hints of a live plan (hbk_sharded_column_t.hot_rows): the host side turns

@@ -7,26 +7,26 @@
 // only, into buffers carved from this call's workspace.  Every reduce plan, the deterministic modes,
 // weighted columns and segmented inputs come from there unchanged, and so does the guarantee that each
 // distinct row appears exactly once (Adam is not additive: a row stepped twice would decay its moments
-// twice; FTRL would add g^2 to its accumulator twice).  (2) ONE apply launch for up to kAdamMaxCols
+// twice; FTRL would add g^2 to its accumulator twice).  (2) ONE apply launch for up to kSlotMaxCols
 // columns: sparse_adam_apply_kernel or sparse_ftrl_apply_kernel.
 //
-// The apply kernels share their scheduling (scan_tasks, walk_tasks).  Work is counted in wave tasks:
-// a task is kAdamItems rows per lane group of one column, a lane group holds one row (f32x4 chunks
-// when dim % 4 == 0 and every address is 16-byte aligned, scalar chunks otherwise -- the reduce's
-// rule, make_rowshape).  Wave 0 of every workgroup
-// reads the columns' n_unique from the device and scans their task counts into LDS; the grid is sized
-// from the host-known capacities only and walks the tasks grid-stride, so the call needs no host sync
-// and can be captured in a graph.  A lane issues the w / slot / slot / g loads of all its kAdamItems rows
+// Both optimizers share everything but their arithmetic: one kernel body (slot_apply_body), one row
+// walk (slot_task) and one host driver (slot_apply); a rule (AdamRule, FtrlRule) holds what differs.
+// Work is counted in wave tasks: a task is kSlotItems rows per lane group of one column, a lane group
+// holds one row (f32x4 chunks when dim % 4 == 0 and every address is 16-byte aligned, scalar chunks
+// otherwise -- the reduce's rule, make_rowshape).  Wave 0 of every workgroup reads the columns'
+// n_unique from the device and scans their task counts into LDS; the grid is sized from the
+// host-known capacities only and walks the tasks grid-stride, so the call needs no host sync and can
+// be captured in a graph.  A lane issues the w / slot / slot / g loads of all its kSlotItems rows
 // before any arithmetic: random rows are bound by the request rate (~49 G requests/s), so
 // what matters is how many are in flight.  grad_rows and unique_rows are read once (non-temporal).
-// The bias-corrected rate lr_t is computed once per workgroup from the device beta powers; the
+// Adam's bias-corrected rate lr_t is computed once per workgroup from the device beta powers; the
 // powers advance after the apply, in stream order (adam_finish_kernel), when the call asks for it.
 // FTRL has no device state besides its slots; its lr_power != -0.5 form (powf) is a separate
 // instantiation, so the default form carries no powf code.
 #include <string.h>
 
 #include <algorithm>
-#include <mutex>
 #include <vector>
 
 #include "common.h"
@@ -35,12 +35,12 @@
 namespace hbk {
 namespace {
 
-constexpr int kAdamMaxCols = 64;    // columns per apply launch (kernarg: 64 descriptors)
-constexpr int kAdamBlock = 256;
-constexpr int kAdamWaves = kAdamBlock / kWave;
-constexpr int kAdamItems = 4;       // rows per lane group in flight
-constexpr int kAdamBlocksPerCU = 8;
-static_assert(kAdamMaxCols <= kWave, "one lane per column in the task scan");
+constexpr int kSlotMaxCols = 64;    // columns per apply launch (kernarg: 64 descriptors)
+constexpr int kSlotBlock = 256;
+constexpr int kSlotWaves = kSlotBlock / kWave;
+constexpr int kSlotItems = 4;       // rows per lane group in flight
+constexpr int kSlotBlocksPerCU = 8;
+static_assert(kSlotMaxCols <= kWave, "one lane per column in the task scan");
 
 // one column of a two-slot apply: Adam's (m, v) or FTRL's (accum, linear) in s0 / s1
 struct SlotCol {
@@ -59,58 +59,145 @@ struct SlotCol {
   int32_t pad;
 };
 
-struct AdamArgs {
-  SlotCol c[kAdamMaxCols];
-  const float* powers;
-  float lr, beta1, beta2, eps;
+// the kernel arguments of one apply launch: the columns and the rule's parameters P
+template <typename P>
+struct SlotArgs {
+  SlotCol c[kSlotMaxCols];
+  P p;
   int32_t n_cols;
 };
-static_assert(sizeof(AdamArgs) <= 8192, "kernarg budget");
 
 __device__ inline float sqrt_v(float a) { return sqrtf(a); }
 __device__ inline f32x4 sqrt_v(f32x4 a) { return f32x4{sqrtf(a.x), sqrtf(a.y), sqrtf(a.z), sqrtf(a.w)}; }
 
-// one task: rows base + k * groups + grp (k < kAdamItems) of column c; W floats per lane chunk
-template <typename V, int W>
-__device__ inline void adam_task(const SlotCol& c, int64_t base, int64_t n, float lr_t, float beta1,
-                                 float beta2, float eps) {
+// one stepped chunk of a row: the new weights and slots
+template <typename V>
+struct Stepped {
+  V w, s0, s1;
+};
+
+// A rule is the arithmetic of one optimizer.  Rule::setup(p) runs on wave 0 lane 0 of every
+// workgroup before the barrier, Rule::state() on every thread after it; every task builds its
+// Rule(p, state), and rule(w, s0, s1, g) steps one chunk of a row in place.
+
+// Lazy Adam (s0 = m, s1 = v): the bias-corrected rate lr_t, computed once per workgroup from the
+// device beta powers, is its state (one LDS word)
+struct AdamParams {
+  const float* powers;
+  float lr, beta1, beta2, eps;
+};
+struct AdamRule {
+  using Params = AdamParams;
+  using State = float;
+  float lr_t, beta1, beta2, eps;
+
+  __device__ static float& lds_lr_t() {
+    __shared__ float s_lr_t;
+    return s_lr_t;
+  }
+  __device__ static void setup(const AdamParams& p) {
+    const float b1p = p.powers[0], b2p = p.powers[1];
+    lds_lr_t() = (p.lr * sqrtf(1.0f - b2p)) / (1.0f - b1p);
+  }
+  __device__ static float state() { return lds_lr_t(); }
+  __device__ AdamRule(const AdamParams& p, float lr_t_)
+      : lr_t(lr_t_), beta1(p.beta1), beta2(p.beta2), eps(p.eps) {}
+  template <typename V>
+  __device__ Stepped<V> operator()(V& w, V& m, V& v, V g) const {
+    const float one_m_b1 = 1.0f - beta1, one_m_b2 = 1.0f - beta2;
+    const V mk = beta1 * m + one_m_b1 * g;
+    const V vk = beta2 * v + one_m_b2 * (g * g);
+    return Stepped<V>{w - (lr_t * mk) / (sqrt_v(vk) + eps), mk, vk};
+  }
+};
+
+// TF's _finish: beta1^t, beta2^t -> beta1^(t+1), beta2^(t+1), one fp32 product each
+__global__ void adam_finish_kernel(float* powers, float beta1, float beta2) {
+  if (threadIdx.x == 0) {
+    powers[0] = powers[0] * beta1;
+    powers[1] = powers[1] * beta2;
+  }
+}
+
+// FTRL-Proximal (s0 = accum, s1 = linear): TF 1.15 SparseApplyFtrl[V2] on every element, each op a
+// separately rounded fp32 op in TF's order; kPow: lr_power != -0.5 (powf), else sqrtf
+struct FtrlParams {
+  float lr, l1, two_l2, two_shrinkage, neg_lr_power;   // (2 * l2, 2 * l2_shrinkage, -lr_power: exact)
+};
+template <bool kPow>
+struct FtrlRule {
+  using Params = FtrlParams;
+  struct State {};
+  const FtrlParams& a;
+
+  __device__ static void setup(const FtrlParams&) {}
+  __device__ static State state() { return State{}; }
+  __device__ FtrlRule(const FtrlParams& p, State) : a(p) {}
+  __device__ void elem(float& w, float& acc, float& z, float g) const {
+    const float gs = a.two_shrinkage == 0.0f ? g : g + a.two_shrinkage * w;
+    const float na = acc + g * g;
+    const float pn = kPow ? powf(na, a.neg_lr_power) : sqrtf(na);
+    const float po = kPow ? powf(acc, a.neg_lr_power) : sqrtf(acc);
+    const float zn = z + (gs - ((pn - po) / a.lr) * w);
+    const float y = pn / a.lr + a.two_l2;
+    w = (fmaxf(fminf(zn, a.l1), -a.l1) - zn) / y;
+    acc = na;
+    z = zn;
+  }
+  __device__ Stepped<float> operator()(float& w, float& acc, float& z, float g) const {
+    elem(w, acc, z, g);
+    return Stepped<float>{w, acc, z};
+  }
+  __device__ Stepped<f32x4> operator()(f32x4& w, f32x4& acc, f32x4& z, f32x4 g) const {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      float wi = w[i], ai = acc[i], zi = z[i];
+      elem(wi, ai, zi, g[i]);
+      w[i] = wi;
+      acc[i] = ai;
+      z[i] = zi;
+    }
+    return Stepped<f32x4>{w, acc, z};
+  }
+};
+
+// one task: rows base + k * groups + grp (k < kSlotItems) of column c; W floats per lane chunk
+template <typename V, int W, typename Rule>
+__device__ inline void slot_task(const SlotCol& c, int64_t base, int64_t n, const Rule& rule) {
   const int lane = lane_id();
   const int lpr = c.lpr_log2;
   const int grp = lane >> lpr;
   const int sub = lane & ((1 << lpr) - 1);
   const int groups = kWave >> lpr;
   const bool lane_on = sub * W < c.dim;
-  int64_t r[kAdamItems];
-  bool on[kAdamItems];
+  int64_t r[kSlotItems];
+  bool on[kSlotItems];
 #pragma unroll
-  for (int k = 0; k < kAdamItems; ++k) {
+  for (int k = 0; k < kSlotItems; ++k) {
     const int64_t u = base + (int64_t)k * groups + grp;
     on[k] = lane_on && u < n;
     r[k] = on[k] ? __builtin_nontemporal_load(c.urows + u) : 0;
     on[k] = on[k] && (uint64_t)r[k] < (uint64_t)c.rows;   // (the reduce only emits rows of the table)
   }
-  V w[kAdamItems], m[kAdamItems], v[kAdamItems], g[kAdamItems];
+  V w[kSlotItems], s0[kSlotItems], s1[kSlotItems], g[kSlotItems];
 #pragma unroll
-  for (int k = 0; k < kAdamItems; ++k) {
+  for (int k = 0; k < kSlotItems; ++k) {
     if (!on[k]) continue;
     const int64_t u = base + (int64_t)k * groups + grp;
     const int64_t off = r[k] * c.pitch + sub * W;
     w[k] = *reinterpret_cast<const V*>(c.w + off);
-    m[k] = *reinterpret_cast<const V*>(c.s0 + off);
-    v[k] = *reinterpret_cast<const V*>(c.s1 + off);
+    s0[k] = *reinterpret_cast<const V*>(c.s0 + off);
+    s1[k] = *reinterpret_cast<const V*>(c.s1 + off);
     g[k] = __builtin_nontemporal_load(reinterpret_cast<const V*>(c.grows + u * c.dim + sub * W));
   }
-  const float one_m_b1 = 1.0f - beta1, one_m_b2 = 1.0f - beta2;
 #pragma unroll
-  for (int k = 0; k < kAdamItems; ++k) {
+  for (int k = 0; k < kSlotItems; ++k) {
     if (!on[k]) continue;
     const int64_t off = r[k] * c.pitch + sub * W;
-    const V mk = beta1 * m[k] + one_m_b1 * g[k];
-    const V vk = beta2 * v[k] + one_m_b2 * (g[k] * g[k]);
-    const V wk = w[k] - (lr_t * mk) / (sqrt_v(vk) + eps);
-    *reinterpret_cast<V*>(c.s0 + off) = mk;
-    *reinterpret_cast<V*>(c.s1 + off) = vk;
-    *reinterpret_cast<V*>(c.w + off) = wk;
+    const Stepped<V> o = rule(w[k], s0[k], s1[k], g[k]);
+    *reinterpret_cast<V*>(c.s0 + off) = o.s0;
+    *reinterpret_cast<V*>(c.s1 + off) = o.s1;
+    *reinterpret_cast<V*>(c.w + off) = o.w;
   }
 }
 
@@ -122,7 +209,7 @@ __device__ inline void scan_tasks(const SlotCol* cols, int n_cols, int lane, int
   if (lane < n_cols) {
     const SlotCol& c = cols[lane];
     const int64_t n = min(max(__builtin_nontemporal_load(c.nu), 0), c.cap);
-    const int64_t rpt = (int64_t)(kWave >> c.lpr_log2) * kAdamItems;
+    const int64_t rpt = (int64_t)(kWave >> c.lpr_log2) * kSlotItems;
     tasks = (n + rpt - 1) / rpt;
     s_n[lane] = n;
   }
@@ -140,156 +227,44 @@ __device__ inline void walk_tasks(const SlotCol* cols, int n_cols, const int64_t
                                   const int64_t* s_n, Task task) {
   const int64_t total = s_end[n_cols - 1];
   int c = 0;
-  for (int64_t t = (int64_t)blockIdx.x * kAdamWaves + threadIdx.x / kWave; t < total;
-       t += (int64_t)gridDim.x * kAdamWaves) {
+  for (int64_t t = (int64_t)blockIdx.x * kSlotWaves + threadIdx.x / kWave; t < total;
+       t += (int64_t)gridDim.x * kSlotWaves) {
     while (s_end[c] <= t) ++c;   // (t only grows: the column only moves forward)
     const SlotCol& col = cols[c];
     const int64_t t0 = c == 0 ? 0 : s_end[c - 1];
-    const int64_t base = (t - t0) * ((int64_t)(kWave >> col.lpr_log2) * kAdamItems);
+    const int64_t base = (t - t0) * ((int64_t)(kWave >> col.lpr_log2) * kSlotItems);
     task(col, base, s_n[c]);
   }
 }
 
-__global__ __launch_bounds__(kAdamBlock) void sparse_adam_apply_kernel(AdamArgs a) {
-  __shared__ int64_t s_end[kAdamMaxCols];   // inclusive prefix of the columns' task counts
-  __shared__ int64_t s_n[kAdamMaxCols];     // their n_unique (clamped to the capacity)
-  __shared__ float s_lr_t;
+// the body of every apply kernel: the scan, the rule's setup, the barrier, the walk
+template <typename Rule>
+__device__ inline void slot_apply_body(const SlotArgs<typename Rule::Params>& a) {
+  __shared__ int64_t s_end[kSlotMaxCols];   // inclusive prefix of the columns' task counts
+  __shared__ int64_t s_n[kSlotMaxCols];     // their n_unique (clamped to the capacity)
   if (threadIdx.x < kWave) {
     const int lane = (int)threadIdx.x;
     scan_tasks(a.c, a.n_cols, lane, s_end, s_n);
-    if (lane == 0) {
-      const float b1p = a.powers[0], b2p = a.powers[1];
-      s_lr_t = (a.lr * sqrtf(1.0f - b2p)) / (1.0f - b1p);
-    }
+    if (lane == 0) Rule::setup(a.p);
   }
   __syncthreads();
-  const float lr_t = s_lr_t;
+  const typename Rule::State st = Rule::state();
   walk_tasks(a.c, a.n_cols, s_end, s_n, [&](const SlotCol& col, int64_t base, int64_t n) {
     if (col.vec4) {
-      adam_task<f32x4, 4>(col, base, n, lr_t, a.beta1, a.beta2, a.eps);
+      slot_task<f32x4, 4>(col, base, n, Rule(a.p, st));
     } else {
-      adam_task<float, 1>(col, base, n, lr_t, a.beta1, a.beta2, a.eps);
+      slot_task<float, 1>(col, base, n, Rule(a.p, st));
     }
   });
 }
 
-// TF's _finish: beta1^t, beta2^t -> beta1^(t+1), beta2^(t+1), one fp32 product each
-__global__ void adam_finish_kernel(float* powers, float beta1, float beta2) {
-  if (threadIdx.x == 0) {
-    powers[0] = powers[0] * beta1;
-    powers[1] = powers[1] * beta2;
-  }
-}
-
-struct FtrlArgs {
-  SlotCol c[kAdamMaxCols];   // s0 = accum, s1 = linear
-  float lr, l1, two_l2, two_shrinkage, neg_lr_power;   // (2 * l2, 2 * l2_shrinkage, -lr_power: exact)
-  int32_t n_cols;
-};
-static_assert(sizeof(FtrlArgs) <= 8192, "kernarg budget");
-
-struct FtrlOut {
-  float w, acc, z;
-};
-
-// TF 1.15 SparseApplyFtrl[V2] on one element, every op a separately rounded fp32 op in TF's order;
-// kPow: lr_power != -0.5 (powf), else sqrtf
-template <bool kPow>
-__device__ inline FtrlOut ftrl_elem(float w, float acc, float z, float g, const FtrlArgs& a) {
-  const float gs = a.two_shrinkage == 0.0f ? g : g + a.two_shrinkage * w;
-  const float na = acc + g * g;
-  const float pn = kPow ? powf(na, a.neg_lr_power) : sqrtf(na);
-  const float po = kPow ? powf(acc, a.neg_lr_power) : sqrtf(acc);
-  const float zn = z + (gs - ((pn - po) / a.lr) * w);
-  const float y = pn / a.lr + a.two_l2;
-  return FtrlOut{(fmaxf(fminf(zn, a.l1), -a.l1) - zn) / y, na, zn};
+__global__ __launch_bounds__(kSlotBlock) void sparse_adam_apply_kernel(SlotArgs<AdamParams> a) {
+  slot_apply_body<AdamRule>(a);
 }
 
 template <bool kPow>
-__device__ inline void ftrl_v(float& w, float& acc, float& z, float g, const FtrlArgs& a) {
-  const FtrlOut o = ftrl_elem<kPow>(w, acc, z, g, a);
-  w = o.w;
-  acc = o.acc;
-  z = o.z;
-}
-template <bool kPow>
-__device__ inline void ftrl_v(f32x4& w, f32x4& acc, f32x4& z, f32x4 g, const FtrlArgs& a) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const FtrlOut o = ftrl_elem<kPow>(w[i], acc[i], z[i], g[i], a);
-    w[i] = o.w;
-    acc[i] = o.acc;
-    z[i] = o.z;
-  }
-}
-
-// one task of FTRL: adam_task's rows and loads, accum / linear in place of m / v
-template <typename V, int W, bool kPow>
-__device__ inline void ftrl_task(const SlotCol& c, int64_t base, int64_t n, const FtrlArgs& a) {
-  const int lane = lane_id();
-  const int lpr = c.lpr_log2;
-  const int grp = lane >> lpr;
-  const int sub = lane & ((1 << lpr) - 1);
-  const int groups = kWave >> lpr;
-  const bool lane_on = sub * W < c.dim;
-  int64_t r[kAdamItems];
-  bool on[kAdamItems];
-#pragma unroll
-  for (int k = 0; k < kAdamItems; ++k) {
-    const int64_t u = base + (int64_t)k * groups + grp;
-    on[k] = lane_on && u < n;
-    r[k] = on[k] ? __builtin_nontemporal_load(c.urows + u) : 0;
-    on[k] = on[k] && (uint64_t)r[k] < (uint64_t)c.rows;   // (the reduce only emits rows of the table)
-  }
-  V w[kAdamItems], acc[kAdamItems], z[kAdamItems], g[kAdamItems];
-#pragma unroll
-  for (int k = 0; k < kAdamItems; ++k) {
-    if (!on[k]) continue;
-    const int64_t u = base + (int64_t)k * groups + grp;
-    const int64_t off = r[k] * c.pitch + sub * W;
-    w[k] = *reinterpret_cast<const V*>(c.w + off);
-    acc[k] = *reinterpret_cast<const V*>(c.s0 + off);
-    z[k] = *reinterpret_cast<const V*>(c.s1 + off);
-    g[k] = __builtin_nontemporal_load(reinterpret_cast<const V*>(c.grows + u * c.dim + sub * W));
-  }
-#pragma unroll
-  for (int k = 0; k < kAdamItems; ++k) {
-    if (!on[k]) continue;
-    const int64_t off = r[k] * c.pitch + sub * W;
-    ftrl_v<kPow>(w[k], acc[k], z[k], g[k], a);
-    *reinterpret_cast<V*>(c.s0 + off) = acc[k];
-    *reinterpret_cast<V*>(c.s1 + off) = z[k];
-    *reinterpret_cast<V*>(c.w + off) = w[k];
-  }
-}
-
-template <bool kPow>
-__global__ __launch_bounds__(kAdamBlock) void sparse_ftrl_apply_kernel(FtrlArgs a) {
-  __shared__ int64_t s_end[kAdamMaxCols];
-  __shared__ int64_t s_n[kAdamMaxCols];
-  if (threadIdx.x < kWave) scan_tasks(a.c, a.n_cols, (int)threadIdx.x, s_end, s_n);
-  __syncthreads();
-  walk_tasks(a.c, a.n_cols, s_end, s_n, [&](const SlotCol& col, int64_t base, int64_t n) {
-    if (col.vec4) {
-      ftrl_task<f32x4, 4, kPow>(col, base, n, a);
-    } else {
-      ftrl_task<float, 1, kPow>(col, base, n, a);
-    }
-  });
-}
-
-int adam_cus() {
-  static std::mutex mu;
-  static int cache[64] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  std::lock_guard<std::mutex> lock(mu);
-  if (cache[dev] == 0) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cache[dev] = n;
-  }
-  return cache[dev];
+__global__ __launch_bounds__(kSlotBlock) void sparse_ftrl_apply_kernel(SlotArgs<FtrlParams> a) {
+  slot_apply_body<FtrlRule<kPow>>(a);
 }
 
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -313,15 +288,6 @@ std::vector<hbk_lookup_grad_column_t> emit_form(int32_t n_cols, const hbk_lookup
   }
   return e;
 }
-
-
-// the names a two-slot call's refusals use
-struct SlotNames {
-  const char* who;   // "group_lookup_bwd_adam"
-  const char* opt;   // "Adam"
-  const char* s0;    // "m"
-  const char* s1;    // "v"
-};
 
 // every host check of a two-slot call's columns, before any device work; the apply's row shapes
 int check_slot_columns(const SlotNames& nm, int32_t n_cols, const hbk_lookup_grad_column_t* cols,
@@ -432,13 +398,44 @@ int fill_slot_cols(const std::vector<hbk_lookup_grad_column_t>& e, const std::ve
     const RowShape& shape = shapes[(size_t)c];   // (validated before the reduce)
     d.lpr_log2 = shape.lpr_log2;
     d.vec4 = shape.vec4;
-    const int64_t rpt = (int64_t)(kWave >> shape.lpr_log2) * kAdamItems;
+    const int64_t rpt = (int64_t)(kWave >> shape.lpr_log2) * kSlotItems;
     tasks += (std::min<int64_t>(h.n_ids, h.rows) + rpt - 1) / rpt;
     ++k;
   }
-  const int64_t want = (tasks + kAdamWaves - 1) / kAdamWaves;
-  *blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)adam_cus() * kAdamBlocksPerCU));
+  const int64_t want = (tasks + kSlotWaves - 1) / kSlotWaves;
+  *blocks = (unsigned)std::max<int64_t>(
+      1, std::min<int64_t>(want, (int64_t)device_cus() * kSlotBlocksPerCU));
   return k;
+}
+
+// one two-slot call: every host check (n_cols, check() for the hyperparameters, the columns), the
+// emit-form reduce, then one apply launch per kSlotMaxCols columns -- launch(args, blocks, stream)
+// sets args.p and launches the rule's kernel.  run_empty: go on with n_cols = 0 (what follows the
+// apply still has to run)
+template <typename P, typename Check, typename Launch>
+int slot_apply(const SlotNames& nm, Check check, bool run_empty, int32_t n_cols,
+               const hbk_lookup_grad_column_t* cols, float* const* s0, float* const* s1, Launch launch,
+               void* workspace, size_t workspace_bytes, hbk_stream_t stream_) {
+  HBK_REQUIRE(n_cols >= 0, "%s: n_cols must be >= 0, got %d", nm.who, n_cols);
+  int rc = check();
+  if (rc != HBK_OK) return rc;
+  std::vector<RowShape> shapes;
+  if ((rc = check_slot_columns(nm, n_cols, cols, s0, s1, &shapes)) != HBK_OK) return rc;
+  if (n_cols == 0 && !run_empty) return HBK_OK;
+  std::vector<hbk_lookup_grad_column_t> e;
+  rc = run_emit_form(nm.who, n_cols, cols, workspace, workspace_bytes, stream_, &e);
+  if (rc != HBK_OK) return rc;
+  hipStream_t stream = as_stream(stream_);
+  for (int32_t c0 = 0; c0 < n_cols; c0 += kSlotMaxCols) {
+    SlotArgs<P> a;
+    memset(&a, 0, sizeof(a));
+    unsigned blocks = 0;
+    a.n_cols = fill_slot_cols(e, shapes, s0, s1, c0, std::min(n_cols, c0 + kSlotMaxCols), a.c, &blocks);
+    if (a.n_cols == 0) continue;
+    launch(a, blocks, stream);
+    HBK_HIP_OK(hipGetLastError());
+  }
+  return HBK_OK;
 }
 
 }  // namespace
@@ -491,37 +488,18 @@ extern "C" int hbk_group_lookup_bwd_adam(int32_t n_cols, const hbk_lookup_grad_c
                                          hbk_stream_t stream_) {
   using namespace hbk;
   static const SlotNames kNames = {"group_lookup_bwd_adam", "Adam", "m", "v"};
-  HBK_REQUIRE(n_cols >= 0, "group_lookup_bwd_adam: n_cols must be >= 0, got %d", n_cols);
-  int rc = adam_check(adam, lr, kNames.who);
-  if (rc != HBK_OK) return rc;
-  std::vector<RowShape> shapes;
-  if ((rc = check_slot_columns(kNames, n_cols, cols, m, v, &shapes)) != HBK_OK) return rc;
-  if (n_cols == 0 && !adam->finish) return HBK_OK;
-  std::vector<hbk_lookup_grad_column_t> e;
-  rc = run_emit_form(kNames.who, n_cols, cols, workspace, workspace_bytes, stream_, &e);
-  if (rc != HBK_OK) return rc;
-  hipStream_t stream = as_stream(stream_);
-
-  // phase 2: the apply, kAdamMaxCols columns per launch
-  for (int32_t c0 = 0; c0 < n_cols; c0 += kAdamMaxCols) {
-    AdamArgs a;
-    memset(&a, 0, sizeof(a));
-    unsigned blocks = 0;
-    a.n_cols = fill_slot_cols(e, shapes, m, v, c0, std::min(n_cols, c0 + kAdamMaxCols), a.c, &blocks);
-    if (a.n_cols == 0) continue;
-    a.powers = adam->beta_powers;
-    a.lr = lr;
-    a.beta1 = adam->beta1;
-    a.beta2 = adam->beta2;
-    a.eps = adam->epsilon;
-    hipLaunchKernelGGL(sparse_adam_apply_kernel, dim3(blocks), dim3(kAdamBlock), 0, stream, a);
-    HBK_HIP_OK(hipGetLastError());
-  }
-  if (adam->finish) {
-    hipLaunchKernelGGL(adam_finish_kernel, dim3(1), dim3(kWave), 0, stream, adam->beta_powers,
-                       adam->beta1, adam->beta2);
-    HBK_HIP_OK(hipGetLastError());
-  }
+  const int rc = slot_apply<AdamParams>(
+      kNames, [&] { return adam_check(adam, lr, kNames.who); }, adam != nullptr && adam->finish,
+      n_cols, cols, m, v,
+      [&](SlotArgs<AdamParams>& a, unsigned blocks, hipStream_t stream) {
+        a.p = AdamParams{adam->beta_powers, lr, adam->beta1, adam->beta2, adam->epsilon};
+        hipLaunchKernelGGL(sparse_adam_apply_kernel, dim3(blocks), dim3(kSlotBlock), 0, stream, a);
+      },
+      workspace, workspace_bytes, stream_);
+  if (rc != HBK_OK || !adam->finish) return rc;
+  hipLaunchKernelGGL(adam_finish_kernel, dim3(1), dim3(kWave), 0, as_stream(stream_), adam->beta_powers,
+                     adam->beta1, adam->beta2);
+  HBK_HIP_OK(hipGetLastError());
   return HBK_OK;
 }
 
@@ -536,38 +514,18 @@ extern "C" int hbk_group_lookup_bwd_ftrl(int32_t n_cols, const hbk_lookup_grad_c
                                          size_t workspace_bytes, hbk_stream_t stream_) {
   using namespace hbk;
   static const SlotNames kNames = {"group_lookup_bwd_ftrl", "FTRL", "accum", "linear"};
-  HBK_REQUIRE(n_cols >= 0, "group_lookup_bwd_ftrl: n_cols must be >= 0, got %d", n_cols);
-  int rc = ftrl_check(ftrl, lr, kNames.who);
-  if (rc != HBK_OK) return rc;
-  std::vector<RowShape> shapes;
-  if ((rc = check_slot_columns(kNames, n_cols, cols, accum, linear, &shapes)) != HBK_OK) return rc;
-  if (n_cols == 0) return HBK_OK;
-  std::vector<hbk_lookup_grad_column_t> e;
-  rc = run_emit_form(kNames.who, n_cols, cols, workspace, workspace_bytes, stream_, &e);
-  if (rc != HBK_OK) return rc;
-  hipStream_t stream = as_stream(stream_);
-
-  // phase 2: the apply, kAdamMaxCols columns per launch; lr_power = -0.5 (TF's default) takes the
-  // sqrtf instantiation, any other the powf one
-  const bool use_pow = ftrl->lr_power != -0.5f;
-  for (int32_t c0 = 0; c0 < n_cols; c0 += kAdamMaxCols) {
-    FtrlArgs a;
-    memset(&a, 0, sizeof(a));
-    unsigned blocks = 0;
-    a.n_cols = fill_slot_cols(e, shapes, accum, linear, c0, std::min(n_cols, c0 + kAdamMaxCols), a.c,
-                              &blocks);
-    if (a.n_cols == 0) continue;
-    a.lr = lr;
-    a.l1 = ftrl->l1;
-    a.two_l2 = 2.0f * ftrl->l2;
-    a.two_shrinkage = 2.0f * ftrl->l2_shrinkage;
-    a.neg_lr_power = -ftrl->lr_power;
-    if (use_pow) {
-      hipLaunchKernelGGL(sparse_ftrl_apply_kernel<true>, dim3(blocks), dim3(kAdamBlock), 0, stream, a);
-    } else {
-      hipLaunchKernelGGL(sparse_ftrl_apply_kernel<false>, dim3(blocks), dim3(kAdamBlock), 0, stream, a);
-    }
-    HBK_HIP_OK(hipGetLastError());
-  }
-  return HBK_OK;
+  return slot_apply<FtrlParams>(
+      kNames, [&] { return ftrl_check(ftrl, lr, kNames.who); }, false, n_cols, cols, accum, linear,
+      [&](SlotArgs<FtrlParams>& a, unsigned blocks, hipStream_t stream) {
+        a.p = FtrlParams{lr, ftrl->l1, 2.0f * ftrl->l2, 2.0f * ftrl->l2_shrinkage, -ftrl->lr_power};
+        // lr_power = -0.5 (TF's default) takes the sqrtf instantiation, any other the powf one
+        if (ftrl->lr_power != -0.5f) {
+          hipLaunchKernelGGL(sparse_ftrl_apply_kernel<true>, dim3(blocks), dim3(kSlotBlock), 0, stream,
+                             a);
+        } else {
+          hipLaunchKernelGGL(sparse_ftrl_apply_kernel<false>, dim3(blocks), dim3(kSlotBlock), 0, stream,
+                             a);
+        }
+      },
+      workspace, workspace_bytes, stream_);
 }

@@ -20,6 +20,7 @@ import torch
 
 from hybridbackend_amd import _lib
 from hybridbackend_amd import _marshal
+from hybridbackend_amd.embedding import optimizer as _opt
 
 _COMBINERS = {None: _lib.COMBINER_MEAN,  # embedding_lookup_sparse default
               'sum': _lib.COMBINER_SUM, 'mean': _lib.COMBINER_MEAN,
@@ -379,24 +380,16 @@ class GroupLookupGrad:
     self._lib = _lib.lib()
     self.lookup = lookup
     n = len(lookup)
-    self.moments = None
-    self.adam = adam
-    if moments is not None:
-      self.moments = _lib.require_moments(moments, lookup.tables, 'GroupLookupGrad')
-      self._m_ptrs = _lib.ptr_array([m.data_ptr() for m, _ in self.moments])
-      self._v_ptrs = _lib.ptr_array([v.data_ptr() for _, v in self.moments])
-      if self.adam is None:
-        from hybridbackend_amd.embedding.optimizer import LazyAdam  # pylint: disable=import-outside-toplevel
-        self.adam = LazyAdam(device=lookup.tables[0].device if n else None)
-    self.ftrl_slots = None
-    self.ftrl = ftrl
-    if ftrl_slots is not None:
-      self.ftrl_slots = _lib.require_ftrl_slots(ftrl_slots, lookup.tables, 'GroupLookupGrad')
-      self._acc_ptrs = _lib.ptr_array([a.data_ptr() for a, _ in self.ftrl_slots])
-      self._lin_ptrs = _lib.ptr_array([z.data_ptr() for _, z in self.ftrl_slots])
-      if self.ftrl is None:
-        from hybridbackend_amd.embedding.optimizer import Ftrl  # pylint: disable=import-outside-toplevel
-        self.ftrl = Ftrl()
+    self.moments, self.adam = _opt.bind_slots(_opt.LazyAdam, moments, adam, lookup.tables,
+                                              'GroupLookupGrad')
+    self.ftrl_slots, self.ftrl = _opt.bind_slots(_opt.Ftrl, ftrl_slots, ftrl, lookup.tables,
+                                                 'GroupLookupGrad')
+    # the pointer arrays of the slot pairs, by optimizer name
+    self._slot_ptrs = {}
+    for opt, pairs in ((self.adam, self.moments), (self.ftrl, self.ftrl_slots)):
+      if pairs is not None:
+        self._slot_ptrs[opt.name] = (_lib.ptr_array([a.data_ptr() for a, _ in pairs]),
+                                     _lib.ptr_array([b.data_ptr() for _, b in pairs]))
     self.accums = list(accums) if accums is not None else None
     self.interleaved = list(interleaved) if interleaved is not None else None
     if self.interleaved is not None and self.accums is None:
@@ -511,16 +504,7 @@ class GroupLookupGrad:
     and ``moments``): the Lazy Adam step (:class:`LazyAdam`); ``finish=False`` leaves the beta powers
     for a later call of the same optimizer step to advance.  ``optimizer='ftrl'`` (with ``apply_lr``
     and ``ftrl_slots``): the FTRL-Proximal step (:class:`Ftrl`)."""
-    if optimizer not in ('sgd', 'adagrad', 'adam', 'ftrl'):
-      raise _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT,
-                                      "optimizer must be 'sgd', 'adagrad', 'adam' or 'ftrl'")
-    if optimizer == 'adam' and self.moments is None:
-      raise _lib.InvalidArgumentError(
-        _lib.INVALID_ARGUMENT, "optimizer='adam' needs GroupLookupGrad(lookup, moments=[(m, v), ...])")
-    if optimizer == 'ftrl' and self.ftrl_slots is None:
-      raise _lib.InvalidArgumentError(
-        _lib.INVALID_ARGUMENT,
-        "optimizer='ftrl' needs GroupLookupGrad(lookup, ftrl_slots=[(accum, linear), ...])")
+    two_slot = _opt.two_slot_class(optimizer, self, self._NEEDS)
     if not emit and apply_lr == 0.0:
       raise _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT, 'emit=False needs apply_lr != 0')
     n = len(self.lookup)
@@ -617,11 +601,10 @@ class GroupLookupGrad:
       self._cols_np['id_weights'] = _marshal.weight_ptrs(sp_weights, ids)
     need = self._lib.hbk_group_lookup_bwd_workspace_bytes(n, self._cols)   # (depends on options too)
     self._slot_cd = None
-    if self.moments is not None or self.ftrl_slots is not None:
-      # (sized for the two-slot forms too: launch() may take any of them)
+    if self._slot_ptrs:
+      # (sized for the two-slot forms too: launch() may take any of them; they share one query)
       self._slot_cd = self._slot_form()
-      need = max(need, self._lib.hbk_group_lookup_bwd_adam_workspace_bytes(n, self._slot_cd),
-                 self._lib.hbk_group_lookup_bwd_ftrl_workspace_bytes(n, self._slot_cd))
+      need = max(need, _opt.TWO_SLOT[next(iter(self._slot_ptrs))].workspace_bytes(n, self._slot_cd))
     if self._ws is None or self._ws.numel() < need:
       self._ws = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
     self._ws_bound = self._ws       # (launch(): the workspace this binding was sized for)
@@ -629,14 +612,14 @@ class GroupLookupGrad:
     if optimizer == 'adagrad' and apply_lr != 0.0 and self.accums is None:
       raise _lib.InvalidArgumentError(
         _lib.INVALID_ARGUMENT, "optimizer='adagrad' needs GroupLookupGrad(lookup, accums=...)")
-    self._step(n, optimizer, apply_lr, finish, self._ws, dev)
+    self._step(n, optimizer, two_slot, apply_lr, finish, self._ws, dev)
     if self.lookup._auto_hot:
       self.lookup.note_backward(self._nu, [int(i.numel()) for i in ids])
     self._bound_call = (emit, [int(i.numel()) for i in ids])
     return list(self._views)
 
   def _slot_form(self):
-    """The descriptors of the Adam and FTRL forms: the bound ones without Adagrad accumulators (a
+    """The descriptors of the two-slot forms: the bound ones without Adagrad accumulators (a
     copy, made once per binding call, only when the object keeps accumulators too)."""
     if self.accums is None:
       return self._cols
@@ -645,18 +628,13 @@ class GroupLookupGrad:
       cols[c].accum = None
     return cols
 
-  def _step(self, n, optimizer, apply_lr, finish, ws, dev):
-    if optimizer == 'adam' and apply_lr != 0.0:
-      _lib.check(self._lib.hbk_group_lookup_bwd_adam(
-        n, self._slot_cd, self._m_ptrs, self._v_ptrs, C.byref(self.adam.params(finish)),
-        C.c_float(apply_lr), C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()),
-        _lib.current_stream(dev)))
-      return
-    if optimizer == 'ftrl' and apply_lr != 0.0:
-      _lib.check(self._lib.hbk_group_lookup_bwd_ftrl(
-        n, self._slot_cd, self._acc_ptrs, self._lin_ptrs, C.byref(self.ftrl.params()),
-        C.c_float(apply_lr), C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()),
-        _lib.current_stream(dev)))
+  _NEEDS = 'GroupLookupGrad(lookup, {kw}=[({s0}, {s1}), ...])'
+
+  def _step(self, n, optimizer, two_slot, apply_lr, finish, ws, dev):
+    if two_slot is not None and apply_lr != 0.0:
+      s0, s1 = self._slot_ptrs[two_slot.name]
+      getattr(self, two_slot.name).group_step(n, self._slot_cd, s0, s1, apply_lr, ws,
+                                              _lib.current_stream(dev), finish)
       return
     _lib.check(self._lib.hbk_group_lookup_bwd_apply(
       n, self._cols, _lib.APPLY_ADAGRAD if optimizer == 'adagrad' else _lib.APPLY_SGD,
@@ -677,15 +655,9 @@ class GroupLookupGrad:
     if optimizer == 'adagrad' and apply_lr != 0.0 and self.accums is None:
       raise _lib.InvalidArgumentError(
         _lib.INVALID_ARGUMENT, "optimizer='adagrad' needs GroupLookupGrad(lookup, accums=...)")
-    if optimizer == 'adam' and self.moments is None:
-      raise _lib.InvalidArgumentError(
-        _lib.INVALID_ARGUMENT, "optimizer='adam' needs GroupLookupGrad(lookup, moments=[(m, v), ...])")
-    if optimizer == 'ftrl' and self.ftrl_slots is None:
-      raise _lib.InvalidArgumentError(
-        _lib.INVALID_ARGUMENT,
-        "optimizer='ftrl' needs GroupLookupGrad(lookup, ftrl_slots=[(accum, linear), ...])")
+    two_slot = _opt.two_slot_class(optimizer, self, self._NEEDS)
     dev = self.lookup.tables[0].device if len(self.lookup) else None
-    self._step(len(self.lookup), optimizer, apply_lr, finish, self._ws_bound, dev)
+    self._step(len(self.lookup), optimizer, two_slot, apply_lr, finish, self._ws_bound, dev)
     if self.lookup._auto_hot:
       self.lookup.note_backward(self._nu, n_ids)
     return list(self._views)

@@ -1,6 +1,9 @@
-"""The two-slot sparse optimizers' shared state: Lazy Adam (``tf.contrib.opt.LazyAdamOptimizer``,
-TF 1.15) -- the hyperparameters and the device-side beta powers -- and FTRL-Proximal
-(``tf.train.FtrlOptimizer``, TF 1.15) -- the hyperparameters only."""
+"""The two-slot sparse optimizers: Lazy Adam (``tf.contrib.opt.LazyAdamOptimizer``, TF 1.15) -- the
+hyperparameters and the device-side beta powers -- and FTRL-Proximal (``tf.train.FtrlOptimizer``,
+TF 1.15) -- the hyperparameters only.  Each class also carries what ``GroupLookupGrad``,
+``ShardedGroupLookup`` and ``DenseFeatures`` need to know of it: its ``optimizer=`` name, the keyword
+of its slot pairs, fresh slots, its TF checkpoint names and its C entry points.  ``TWO_SLOT`` lists
+them; adding one here is all those drivers need."""
 import math
 import ctypes as C
 
@@ -9,7 +12,41 @@ import torch
 from hybridbackend_amd import _lib
 
 
-class LazyAdam:
+class _TwoSlot:
+  """What the drivers use of a two-slot optimizer.  A subclass sets ``name`` (``optimizer=``, and the
+  drivers' attribute holding the object), ``slot_kw`` (the drivers' keyword and attribute of the slot
+  pairs), ``slot_names``, ``tf_suffixes`` (checkpoint names of the two slots), and implements
+  ``params(finish)`` (the C parameter struct), ``slots_like(table)`` and ``_c(lib)`` (its C entry
+  points: group step, workspace query, sharded slot registration, sharded step)."""
+
+  def tf_variables(self):
+    """Checkpoint variables besides the slots: ``{name: tensor}``."""
+    return {}
+
+  @classmethod
+  def workspace_bytes(cls, n, cols):
+    return cls._c(_lib.lib())[1](n, cols)
+
+  def group_step(self, n, cols, s0_ptrs, s1_ptrs, lr, ws, stream, finish=True):
+    """The step of ``GroupLookupGrad``: the emit-form reduce and the apply on ``n`` descriptors."""
+    _lib.check(self._c(_lib.lib())[0](
+      n, cols, s0_ptrs, s1_ptrs, C.byref(self.params(finish)), C.c_float(lr),
+      C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()), stream))
+
+  def set_sharded_slots(self, plan, pairs):
+    """Every column's slot shards, registered with a sharded plan."""
+    _lib.check(self._c(_lib.lib())[2](plan, _lib.ptr_array([a.data_ptr() for a, _ in pairs]),
+                                      _lib.ptr_array([b.data_ptr() for _, b in pairs])))
+
+  def sharded_step(self, plan, grads, strides, lr, unique_rows, grad_rows, n_unique, stream,
+                   finish=True):
+    """The step of ``ShardedGroupLookup.backward`` (pointer arrays; unique_rows / grad_rows None: step
+    only)."""
+    _lib.check(self._c(_lib.lib())[3](plan, grads, strides, C.byref(self.params(finish)),
+                                      C.c_float(lr), unique_rows, grad_rows, n_unique, stream))
+
+
+class LazyAdam(_TwoSlot):
   """The sparse Adam step of ``GroupLookupGrad`` / ``ShardedGroupLookup`` / ``DenseFeatures`` with
   ``optimizer='adam'``: for every distinct row r of a step, with its deduplicated gradient g, in fp32::
 
@@ -25,6 +62,8 @@ class LazyAdam:
   graph replayed K times makes K correct steps.  Share ONE object between everything one optimizer
   steps, as TF does; when one optimizer step spans several calls, pass ``finish=False`` to all but the
   last."""
+  name, slot_kw, slot_names = 'adam', 'moments', ('m', 'v')
+  tf_suffixes = ('/Adam', '/Adam_1')
 
   def __init__(self, beta1=0.9, beta2=0.999, epsilon=1e-8, device=None):
     for name, b in (('beta1', beta1), ('beta2', beta2)):
@@ -53,8 +92,25 @@ class LazyAdam:
       self._params[key] = p
     return p
 
+  @classmethod
+  def default(cls, device):
+    return cls(device=device)
 
-class Ftrl:
+  def slots_like(self, table):
+    """A new ``(m, v)`` pair for ``table``: zeros."""
+    return (torch.zeros_like(table), torch.zeros_like(table))
+
+  def tf_variables(self):
+    # (0-d views of the device pair: a restore writes into it)
+    return {'beta1_power': self.beta_powers[0], 'beta2_power': self.beta_powers[1]}
+
+  @staticmethod
+  def _c(lib):
+    return (lib.hbk_group_lookup_bwd_adam, lib.hbk_group_lookup_bwd_adam_workspace_bytes,
+            lib.hbk_sharded_set_adam_slots, lib.hbk_sharded_lookup_bwd_adam)
+
+
+class Ftrl(_TwoSlot):
   """The sparse FTRL-Proximal step of ``GroupLookupGrad`` / ``ShardedGroupLookup`` / ``DenseFeatures``
   with ``optimizer='ftrl'`` (TF 1.15 ``SparseApplyFtrl`` / ``SparseApplyFtrlV2``, the sparse apply of
   ``tf.train.FtrlOptimizer``): for every distinct row r of a step, with its deduplicated gradient g,
@@ -70,6 +126,8 @@ class Ftrl:
   Rows that do not occur in the step are not touched, as in TF's sparse apply.  The slots are the
   accumulator (filled with ``initial_accumulator_value``) and the linear term (zeros).  There is no
   device state: one object may serve any number of calls."""
+  name, slot_kw, slot_names = 'ftrl', 'ftrl_slots', ('accum', 'linear')
+  tf_suffixes = ('/Ftrl', '/Ftrl_1')
 
   def __init__(self, l1=0.0, l2=0.0, l2_shrinkage=0.0, lr_power=-0.5, initial_accumulator_value=0.1):
     # tf.train.FtrlOptimizer.__init__ and the SparseApplyFtrl kernel refuse the same
@@ -88,10 +146,53 @@ class Ftrl:
     self._params = _lib.FtrlParams(C.c_float(self.l1), C.c_float(self.l2),
                                    C.c_float(self.l2_shrinkage), C.c_float(self.lr_power))
 
-  def params(self):
-    """The ``hbk_ftrl_t`` of a call (kept alive by this object)."""
+  def params(self, finish=True):   # pylint: disable=unused-argument
+    """The ``hbk_ftrl_t`` of a call (kept alive by this object; ``finish`` is Adam's)."""
     return self._params
+
+  @classmethod
+  def default(cls, device):   # pylint: disable=unused-argument
+    return cls()
 
   def slots_like(self, table):
     """A new ``(accum, linear)`` pair for ``table``: TF's initial values."""
     return (torch.full_like(table, self.initial_accumulator_value), torch.zeros_like(table))
+
+  @staticmethod
+  def _c(lib):
+    return (lib.hbk_group_lookup_bwd_ftrl, lib.hbk_group_lookup_bwd_ftrl_workspace_bytes,
+            lib.hbk_sharded_set_ftrl_slots, lib.hbk_sharded_lookup_bwd_ftrl)
+
+
+# the two-slot optimizers by their optimizer= name; 'sgd' and 'adagrad' are fused into the reduce
+TWO_SLOT = {c.name: c for c in (LazyAdam, Ftrl)}
+_NAMES = ['sgd', 'adagrad'] + list(TWO_SLOT)
+
+
+def two_slot_class(optimizer, owner=None, needs=''):
+  """The two-slot class ``optimizer`` names, or None for a fused step ('sgd', 'adagrad').  Refuses
+  other names and -- with an ``owner`` -- a two-slot optimizer whose slot pairs the owner does not
+  hold; ``needs``: how to build one that does (formatted with the class's ``name``, ``kw``, ``s0``
+  and ``s1``)."""
+  if optimizer in ('sgd', 'adagrad'):
+    return None
+  cls = TWO_SLOT.get(optimizer)
+  if cls is None:
+    raise _lib.InvalidArgumentError(
+      _lib.INVALID_ARGUMENT,
+      'optimizer must be ' + ', '.join(repr(n) for n in _NAMES[:-1]) + f' or {_NAMES[-1]!r}')
+  if owner is not None and getattr(owner, cls.slot_kw, None) is None:
+    raise _lib.InvalidArgumentError(
+      _lib.INVALID_ARGUMENT, f"optimizer='{cls.name}' needs " + needs.format(
+        name=cls.name, kw=cls.slot_kw, s0=cls.slot_names[0], s1=cls.slot_names[1]))
+  return cls
+
+
+def bind_slots(cls, pairs, opt, tables, what):
+  """A driver's ``(slot pairs, optimizer)`` of one two-slot class from its keyword arguments: the
+  pairs checked against ``tables`` (None when not given) and, with pairs, an optimizer with TF's
+  defaults when ``opt`` is None."""
+  if pairs is None:
+    return None, opt
+  pairs = _lib.require_slot_pairs(pairs, tables, what, cls.slot_kw, cls.slot_names)
+  return pairs, opt if opt is not None else cls.default(tables[0].device if tables else None)

@@ -32,6 +32,7 @@ from hybridbackend_amd import _lib
 from hybridbackend_amd.distribute import partition as _partition
 from hybridbackend_amd.embedding.lookup import GroupLookup
 from hybridbackend_amd.embedding.lookup import GroupLookupGrad
+from hybridbackend_amd.embedding import optimizer as _opt
 
 
 class _Step:
@@ -86,24 +87,12 @@ class ShardedGroupLookup:
     self.shards = list(shards)
     # Adagrad accumulators of the shards (same shapes), for backward(optimizer='adagrad')
     self.accums = list(accums) if accums is not None else None
-    # Lazy Adam slots of the shards ((m, v) per column, same shapes) and the optimizer whose beta
-    # powers they step with, for backward(optimizer='adam')
-    self.moments = None
-    self.adam = adam
-    if moments is not None:
-      self.moments = _lib.require_moments(moments, self.shards, 'ShardedGroupLookup')
-      if self.adam is None:
-        from hybridbackend_amd.embedding.optimizer import LazyAdam  # pylint: disable=import-outside-toplevel
-        self.adam = LazyAdam(device=self.shards[0].device)
-    # FTRL slots of the shards ((accum, linear) per column, same shapes) and their hyperparameters,
-    # for backward(optimizer='ftrl')
-    self.ftrl_slots = None
-    self.ftrl = ftrl
-    if ftrl_slots is not None:
-      self.ftrl_slots = _lib.require_ftrl_slots(ftrl_slots, self.shards, 'ShardedGroupLookup')
-      if self.ftrl is None:
-        from hybridbackend_amd.embedding.optimizer import Ftrl  # pylint: disable=import-outside-toplevel
-        self.ftrl = Ftrl()
+    # the two-slot optimizers' slots of the shards (per column a pair of the shard's shape) and the
+    # optimizers they step with, for backward(optimizer='adam') / backward(optimizer='ftrl')
+    self.moments, self.adam = _opt.bind_slots(_opt.LazyAdam, moments, adam, self.shards,
+                                              'ShardedGroupLookup')
+    self.ftrl_slots, self.ftrl = _opt.bind_slots(_opt.Ftrl, ftrl_slots, ftrl, self.shards,
+                                                 'ShardedGroupLookup')
     self.coll = coll
     self.world_size = int(world_size if world_size is not None else coll.world_size)
     n = len(self.shards)
@@ -195,10 +184,9 @@ class ShardedGroupLookup:
     wire = _lib.HALF if self.wire_dtype == torch.float16 else _lib.FLOAT
     _lib.check(self._lib.hbk_sharded_create(
       C.byref(self._plan_handle), self.coll._handle, n, cols, wire))
-    if self.moments is not None:
-      _lib.set_adam_slots(self._plan_handle, self.moments)
-    if self.ftrl_slots is not None:
-      _lib.set_ftrl_slots(self._plan_handle, self.ftrl_slots)
+    for opt, pairs in ((self.adam, self.moments), (self.ftrl, self.ftrl_slots)):
+      if pairs is not None:
+        opt.set_sharded_slots(self._plan_handle, pairs)
 
   def last_host_us(self):
     """Host time of the last forward step in microseconds: (enqueueing the partition and the
@@ -515,16 +503,8 @@ class ShardedGroupLookup:
       raise _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT, 'emit=False needs apply_lr != 0')
     n = len(self.shards)
     plan = self._plan()
-    if optimizer not in ('sgd', 'adagrad', 'adam', 'ftrl'):
-      raise _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT,
-                                      "optimizer must be 'sgd', 'adagrad', 'adam' or 'ftrl'")
-    if optimizer == 'adam' and self.moments is None:
-      raise _lib.InvalidArgumentError(
-        _lib.INVALID_ARGUMENT, "optimizer='adam' needs ShardedGroupLookup(..., moments=[(m, v), ...])")
-    if optimizer == 'ftrl' and self.ftrl_slots is None:
-      raise _lib.InvalidArgumentError(
-        _lib.INVALID_ARGUMENT,
-        "optimizer='ftrl' needs ShardedGroupLookup(..., ftrl_slots=[(accum, linear), ...])")
+    two_slot = _opt.two_slot_class(optimizer, self,
+                                   'ShardedGroupLookup(..., {kw}=[({s0}, {s1}), ...])')
     res = []
     shapes = getattr(self, '_last_shapes', None)
     auto = bool(self._auto_hot) and outs is None
@@ -568,20 +548,12 @@ class ShardedGroupLookup:
     if optimizer == 'adagrad' and apply_lr != 0.0 and self.accums is None:
       raise _lib.InvalidArgumentError(
         _lib.INVALID_ARGUMENT, "optimizer='adagrad' needs ShardedGroupLookup(..., accums=...)")
-    if optimizer == 'adam' and apply_lr != 0.0:
-      _lib.check(self._lib.hbk_sharded_lookup_bwd_adam(
-        plan, _lib.ptr_array([g.data_ptr() for g in grads]), strides,
-        C.byref(self.adam.params(finish)), C.c_float(apply_lr),
+    if two_slot is not None and apply_lr != 0.0:
+      getattr(self, two_slot.name).sharded_step(
+        plan, _lib.ptr_array([g.data_ptr() for g in grads]), strides, apply_lr,
         _lib.ptr_array([r[0].data_ptr() for r in res]) if emit else None,
         _lib.ptr_array([r[1].data_ptr() for r in res]) if emit else None,
-        _lib.ptr_array([r[2].data_ptr() for r in res]), _lib.current_stream(self.device)))
-    elif optimizer == 'ftrl' and apply_lr != 0.0:
-      _lib.check(self._lib.hbk_sharded_lookup_bwd_ftrl(
-        plan, _lib.ptr_array([g.data_ptr() for g in grads]), strides,
-        C.byref(self.ftrl.params()), C.c_float(apply_lr),
-        _lib.ptr_array([r[0].data_ptr() for r in res]) if emit else None,
-        _lib.ptr_array([r[1].data_ptr() for r in res]) if emit else None,
-        _lib.ptr_array([r[2].data_ptr() for r in res]), _lib.current_stream(self.device)))
+        _lib.ptr_array([r[2].data_ptr() for r in res]), _lib.current_stream(self.device), finish)
     else:
       _lib.check(self._lib.hbk_sharded_lookup_bwd_apply(
         plan, _lib.ptr_array([g.data_ptr() for g in grads]), strides,

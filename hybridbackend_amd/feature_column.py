@@ -14,8 +14,7 @@ import torch
 from hybridbackend_amd import _lib
 from hybridbackend_amd.embedding.lookup import GroupLookup
 from hybridbackend_amd.embedding.lookup import GroupLookupGrad
-from hybridbackend_amd.embedding.optimizer import Ftrl
-from hybridbackend_amd.embedding.optimizer import LazyAdam
+from hybridbackend_amd.embedding import optimizer as _opt
 from hybridbackend_amd.embedding.sharded import ShardedGroupLookup
 from hybridbackend_amd.embedding.variables import sharded_bucket_size
 
@@ -90,19 +89,16 @@ class DenseFeatures:
     self.accums = None
     if initial_accumulator_value is not None:
       self.accums = [torch.full_like(w, float(initial_accumulator_value)) for w in self.weights]
-    if optimizer not in (None, 'sgd', 'adagrad', 'adam', 'ftrl'):
-      raise _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT,
-                                      "optimizer must be 'sgd', 'adagrad', 'adam' or 'ftrl'")
-    # Lazy Adam slots (tf.contrib.opt.LazyAdamOptimizer: m and v start at zero)
-    self.moments = self.adam = None
-    if optimizer == 'adam' or adam is not None:
-      self.adam = adam if adam is not None else LazyAdam(device=self.device)
-      self.moments = [(torch.zeros_like(w), torch.zeros_like(w)) for w in self.weights]
-    # FTRL slots (tf.train.FtrlOptimizer: accum = initial_accumulator_value, linear = 0)
-    self.ftrl_slots = self.ftrl = None
-    if optimizer == 'ftrl' or ftrl is not None:
-      self.ftrl = ftrl if ftrl is not None else Ftrl()
-      self.ftrl_slots = [self.ftrl.slots_like(w) for w in self.weights]
+    if optimizer is not None:
+      _opt.two_slot_class(optimizer)   # (refuses unknown names)
+    # two-slot optimizers: the optimizer named (TF's defaults) or passed, fresh slots for every table
+    # (Lazy Adam: m = v = 0; FTRL: accum = initial_accumulator_value, linear = 0)
+    self.moments = self.adam = self.ftrl_slots = self.ftrl = None
+    for cls, opt in ((_opt.LazyAdam, adam), (_opt.Ftrl, ftrl)):
+      if optimizer == cls.name or opt is not None:
+        opt = opt if opt is not None else cls.default(self.device)
+        setattr(self, cls.name, opt)
+        setattr(self, cls.slot_kw, [opt.slots_like(w) for w in self.weights])
     self.offsets, off = [], 0
     for col in self.columns:
       self.offsets.append(off)
@@ -117,6 +113,14 @@ class DenseFeatures:
     self._rep = [c for c in range(len(self.columns)) if not self.sharded[c]]
     self._shd = [c for c in range(len(self.columns)) if self.sharded[c]]
     pick = lambda idx, xs: [xs[c] for c in idx]   # noqa: E731
+
+    def two_slot_kw(idx):   # the drivers' keyword arguments of the two-slot optimizers, tables idx
+      kw = {}
+      for cls in _opt.TWO_SLOT.values():
+        pairs = getattr(self, cls.slot_kw)
+        kw[cls.slot_kw] = None if pairs is None else pick(idx, pairs)
+        kw[cls.name] = getattr(self, cls.name)
+      return kw
     self._lookup = self._grad = self._sharded = None
     if self._rep:
       self._lookup = GroupLookup(pick(self._rep, self.weights),
@@ -125,9 +129,7 @@ class DenseFeatures:
                                  hot_rows=[self.columns[c].hot_rows for c in self._rep])
       self._grad = GroupLookupGrad(
         self._lookup, pick(self._rep, self.accums) if self.accums is not None else None,
-        moments=pick(self._rep, self.moments) if self.moments is not None else None, adam=self.adam,
-        ftrl_slots=pick(self._rep, self.ftrl_slots) if self.ftrl_slots is not None else None,
-        ftrl=self.ftrl)
+        **two_slot_kw(self._rep))
     if self._shd:
       self._sharded = ShardedGroupLookup(pick(self._shd, self.weights), coll,
                                          buckets=[self.columns[c].num_buckets for c in self._shd],
@@ -136,12 +138,7 @@ class DenseFeatures:
                                          dedup=[self.columns[c].dedup for c in self._shd],
                                          accums=(pick(self._shd, self.accums)
                                                  if self.accums is not None else None),
-                                         moments=(pick(self._shd, self.moments)
-                                                  if self.moments is not None else None),
-                                         adam=self.adam,
-                                         ftrl_slots=(pick(self._shd, self.ftrl_slots)
-                                                     if self.ftrl_slots is not None else None),
-                                         ftrl=self.ftrl)
+                                         **two_slot_kw(self._shd))
 
   def _weights(self, features):
     """Per column its fp32 per-id weights (weight_feature_key) or None; None when no column has any."""
@@ -234,12 +231,7 @@ class DenseFeatures:
     ``optimizer='adam'`` (layer built with ``optimizer='adam'``): the Lazy Adam step; the beta powers
     advance once per backward that steps any table.  ``optimizer='ftrl'`` (layer built with
     ``optimizer='ftrl'``): the FTRL-Proximal step."""
-    if optimizer == 'adam' and self.moments is None:
-      raise _lib.InvalidArgumentError(
-        _lib.INVALID_ARGUMENT, "optimizer='adam' needs DenseFeatures(..., optimizer='adam')")
-    if optimizer == 'ftrl' and self.ftrl_slots is None:
-      raise _lib.InvalidArgumentError(
-        _lib.INVALID_ARGUMENT, "optimizer='ftrl' needs DenseFeatures(..., optimizer='ftrl')")
+    _opt.two_slot_class(optimizer, self, "DenseFeatures(..., optimizer='{name}')")
     ids, splits, ws = self._last
     if grad.dim() != 2 or grad.shape[1] != self.width or grad.dtype != torch.float32:
       raise _lib.InvalidArgumentError(
@@ -293,23 +285,24 @@ class DenseFeatures:
     from hybridbackend_amd.training.saver import ShardedSlice
     world = self.coll.world_size if self.coll is not None else 1
     rank = self.coll.rank if self.coll is not None else 0
+    per_table = [('', self.weights), ('/Adagrad', self.accums)]
+    extra = {}
+    for cls in _opt.TWO_SLOT.values():
+      pairs = getattr(self, cls.slot_kw)
+      if pairs is not None:
+        per_table += [(cls.tf_suffixes[0], [a for a, _ in pairs]),
+                      (cls.tf_suffixes[1], [b for _, b in pairs])]
+        extra.update(getattr(self, cls.name).tf_variables())
     out = {}
     for c, col in enumerate(self.columns):
       name = f'{col.key}_embedding/embedding_weights'
-      moms, fs = self.moments, self.ftrl_slots
-      for suffix, tensors in (('', self.weights), ('/Adagrad', self.accums),
-                              ('/Adam', None if moms is None else [m for m, _ in moms]),
-                              ('/Adam_1', None if moms is None else [v for _, v in moms]),
-                              ('/Ftrl', None if fs is None else [a for a, _ in fs]),
-                              ('/Ftrl_1', None if fs is None else [z for _, z in fs])):
+      for suffix, tensors in per_table:
         if tensors is None:
           continue
         t = tensors[c]
         out[name + suffix] = (ShardedSlice(t, col.num_buckets, world, rank)
                               if self.sharded[c] else t)
-    if self.adam is not None:   # (0-d views of the device pair: a restore writes into it)
-      out['beta1_power'] = self.adam.beta_powers[0]
-      out['beta2_power'] = self.adam.beta_powers[1]
+    out.update(extra)
     return out
 
   def _saver(self, barrier):

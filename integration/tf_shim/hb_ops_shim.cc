@@ -1102,27 +1102,6 @@ struct FtrlAttrs {
   }
 };
 
-// the slots of an FTRL call out of `accums` (accum x N, linear x N)
-static Status FtrlSlots(OpMutableInputList& accums, int n, const std::vector<int64>& sizes,
-                        std::vector<float*>* accum, std::vector<float*>* linear) {
-  if (accums.size() != 2 * n) {
-    return errors::InvalidArgument("accums: ftrl takes accum x N, then linear x N (M = ", 2 * n,
-                                   "), got ", accums.size());
-  }
-  accum->resize(n);
-  linear->resize(n);
-  for (int i = 0; i < n; ++i) {
-    Tensor at = accums.at(i, /*lock_held=*/false);
-    Tensor lt = accums.at(n + i, /*lock_held=*/false);
-    if (at.NumElements() != sizes[i] || lt.NumElements() != sizes[i]) {
-      return errors::InvalidArgument("accum / linear ", i, " must have its variable's shape");
-    }
-    (*accum)[i] = at.flat<float>().data();
-    (*linear)[i] = lt.flat<float>().data();
-  }
-  return Status::OK();
-}
-
 struct AdamAttrs {
   float beta1 = 0.9f, beta2 = 0.999f, epsilon = 1e-8f;
   Status Read(OpKernelConstruction* ctx) {
@@ -1130,29 +1109,49 @@ struct AdamAttrs {
     TF_RETURN_IF_ERROR(ctx->GetAttr("beta2", &beta2));
     return ctx->GetAttr("epsilon", &epsilon);
   }
+  // the hbk_adam_t of one op call (beta_powers: from `accums`); the op advances the powers
+  hbk_adam_t Params() const {
+    hbk_adam_t a;
+    std::memset(&a, 0, sizeof(a));
+    a.beta1 = beta1;
+    a.beta2 = beta2;
+    a.epsilon = epsilon;
+    a.finish = 1;
+    return a;
+  }
 };
 
-// the slots of an Adam call out of `accums` (m x N, v x N, beta powers [2])
-static Status AdamSlots(OpMutableInputList& accums, int n, const std::vector<int64>& sizes,
-                        std::vector<float*>* m, std::vector<float*>* v, float** powers) {
-  if (accums.size() != 2 * n + 1) {
-    return errors::InvalidArgument("accums: adam takes m x N, v x N and the [2] beta powers (M = ",
-                                   2 * n + 1, "), got ", accums.size());
-  }
-  m->resize(n);
-  v->resize(n);
-  for (int i = 0; i < n; ++i) {
-    Tensor mt = accums.at(i, /*lock_held=*/false);
-    Tensor vt = accums.at(n + i, /*lock_held=*/false);
-    if (mt.NumElements() != sizes[i] || vt.NumElements() != sizes[i]) {
-      return errors::InvalidArgument("m / v ", i, " must have its variable's shape");
+// the slots of a two-slot call out of `accums`: s0 x N, then s1 x N (adam: m / v, ftrl: accum /
+// linear), then -- adam, powers != NULL -- the [2] beta powers
+static Status TwoSlots(OpMutableInputList& accums, int n, const std::vector<int64>& sizes,
+                       std::vector<float*>* s0, std::vector<float*>* s1, float** powers) {
+  const bool adam = powers != nullptr;
+  const int m = 2 * n + (adam ? 1 : 0);
+  if (accums.size() != m) {
+    if (adam) {
+      return errors::InvalidArgument("accums: adam takes m x N, v x N and the [2] beta powers (M = ", m,
+                                     "), got ", accums.size());
     }
-    (*m)[i] = mt.flat<float>().data();
-    (*v)[i] = vt.flat<float>().data();
+    return errors::InvalidArgument("accums: ftrl takes accum x N, then linear x N (M = ", m, "), got ",
+                                   accums.size());
   }
-  Tensor p = accums.at(2 * n, /*lock_held=*/false);
-  if (p.NumElements() != 2) return errors::InvalidArgument("beta powers must be a float [2]");
-  *powers = p.flat<float>().data();
+  s0->resize(n);
+  s1->resize(n);
+  for (int i = 0; i < n; ++i) {
+    Tensor t0 = accums.at(i, /*lock_held=*/false);
+    Tensor t1 = accums.at(n + i, /*lock_held=*/false);
+    if (t0.NumElements() != sizes[i] || t1.NumElements() != sizes[i]) {
+      return errors::InvalidArgument(adam ? "m / v " : "accum / linear ", i,
+                                     " must have its variable's shape");
+    }
+    (*s0)[i] = t0.flat<float>().data();
+    (*s1)[i] = t1.flat<float>().data();
+  }
+  if (adam) {
+    Tensor p = accums.at(2 * n, /*lock_held=*/false);
+    if (p.NumElements() != 2) return errors::InvalidArgument("beta powers must be a float [2]");
+    *powers = p.flat<float>().data();
+  }
   return Status::OK();
 }
 
@@ -1199,37 +1198,24 @@ class GroupLookupGradApplyOp : public OpKernel {
       OP_REQUIRES_OK(ctx, ctx->allocate_output(i, TensorShape({1}), &k));
       cols[i].n_unique = k->flat<int32>().data();      // unique_rows = grad_rows = NULL: step only
     }
-    if (apply_ == kApplyLazyAdam) {
+    if (apply_ == kApplyLazyAdam || apply_ == kApplyFtrl) {
+      const bool adam = apply_ == kApplyLazyAdam;
       std::vector<int64> sizes(n);
       for (int i = 0; i < n; ++i) sizes[i] = w.at(i, /*lock_held=*/false).NumElements();
-      std::vector<float*> m, v;
-      hbk_adam_t adam;
-      std::memset(&adam, 0, sizeof(adam));
-      OP_REQUIRES_OK(ctx, AdamSlots(accums, n, sizes, &m, &v, &adam.beta_powers));
-      adam.beta1 = adam_.beta1;
-      adam.beta2 = adam_.beta2;
-      adam.epsilon = adam_.epsilon;
-      adam.finish = 1;
-      const size_t ws_bytes = hbk_group_lookup_bwd_adam_workspace_bytes(n, cols.data());
+      std::vector<float*> s0, s1;
+      hbk_adam_t a = adam_.Params();
+      OP_REQUIRES_OK(ctx, TwoSlots(accums, n, sizes, &s0, &s1, adam ? &a.beta_powers : nullptr));
+      const size_t ws_bytes = adam ? hbk_group_lookup_bwd_adam_workspace_bytes(n, cols.data())
+                                   : hbk_group_lookup_bwd_ftrl_workspace_bytes(n, cols.data());
       Tensor ws;
       OP_REQUIRES_OK(ctx, AllocScratch(ctx, ws_bytes, &ws));
-      OP_REQUIRES_OK(ctx, HbkStatus(hbk_group_lookup_bwd_adam(
-                              n, cols.data(), m.data(), v.data(), &adam, lr->scalar<float>()(),
-                              ws.flat<int8>().data(), ws_bytes + 16, StreamOf(ctx))));
-      return;
-    }
-    if (apply_ == kApplyFtrl) {
-      std::vector<int64> sizes(n);
-      for (int i = 0; i < n; ++i) sizes[i] = w.at(i, /*lock_held=*/false).NumElements();
-      std::vector<float*> accum, linear;
-      OP_REQUIRES_OK(ctx, FtrlSlots(accums, n, sizes, &accum, &linear));
-      const size_t ws_bytes = hbk_group_lookup_bwd_ftrl_workspace_bytes(n, cols.data());
-      Tensor ws;
-      OP_REQUIRES_OK(ctx, AllocScratch(ctx, ws_bytes, &ws));
-      OP_REQUIRES_OK(ctx, HbkStatus(hbk_group_lookup_bwd_ftrl(
-                              n, cols.data(), accum.data(), linear.data(), &ftrl_.ftrl,
-                              lr->scalar<float>()(), ws.flat<int8>().data(), ws_bytes + 16,
-                              StreamOf(ctx))));
+      const float rate = lr->scalar<float>()();
+      void* const wp = ws.flat<int8>().data();
+      OP_REQUIRES_OK(ctx, HbkStatus(
+          adam ? hbk_group_lookup_bwd_adam(n, cols.data(), s0.data(), s1.data(), &a, rate, wp,
+                                           ws_bytes + 16, StreamOf(ctx))
+               : hbk_group_lookup_bwd_ftrl(n, cols.data(), s0.data(), s1.data(), &ftrl_.ftrl, rate, wp,
+                                           ws_bytes + 16, StreamOf(ctx))));
       return;
     }
     const size_t ws_bytes = hbk_group_lookup_bwd_workspace_bytes(n, cols.data());
@@ -1614,35 +1600,27 @@ class ShardedGroupLookupGradOp : public CollectiveAsyncOp {
       OP_REQUIRES_OK(ctx, ctx->input("lr", &t));
       lr = t->scalar<float>()();
     }
-    if (APPLY && apply_ == kApplyLazyAdam) {   // the shards' m / v: registered with the plan per call
+    if (APPLY && (apply_ == kApplyLazyAdam || apply_ == kApplyFtrl)) {
+      // the shards' two slots: registered with the plan per call
+      const bool adam = apply_ == kApplyLazyAdam;
       OpMutableInputList accums;
       OP_REQUIRES_OK(ctx, ctx->mutable_input_list("accums", &accums));
       std::vector<int64> sizes(n);
       for (int i = 0; i < n; ++i) sizes[i] = plan->cols()[i].rows_local * plan->cols()[i].dim;
-      std::vector<float*> m, v;
-      hbk_adam_t adam;
-      std::memset(&adam, 0, sizeof(adam));
-      OP_REQUIRES_OK(ctx, AdamSlots(accums, n, sizes, &m, &v, &adam.beta_powers));
-      adam.beta1 = adam_.beta1;
-      adam.beta2 = adam_.beta2;
-      adam.epsilon = adam_.epsilon;
-      adam.finish = 1;
-      OP_REQUIRES_OK(ctx, HbkStatus(hbk_sharded_set_adam_slots(plan->plan(), m.data(), v.data())));
-      OP_REQUIRES_OK(ctx, HbkStatus(hbk_sharded_lookup_bwd_adam(plan->plan(), g.data(), nullptr, &adam,
-                                                              lr, nullptr, nullptr, counts.data(),
-                                                              StreamOf(ctx))));
-    } else if (APPLY && apply_ == kApplyFtrl) {   // the shards' accum / linear, registered per call
-      OpMutableInputList accums;
-      OP_REQUIRES_OK(ctx, ctx->mutable_input_list("accums", &accums));
-      std::vector<int64> sizes(n);
-      for (int i = 0; i < n; ++i) sizes[i] = plan->cols()[i].rows_local * plan->cols()[i].dim;
-      std::vector<float*> accum, linear;
-      OP_REQUIRES_OK(ctx, FtrlSlots(accums, n, sizes, &accum, &linear));
-      OP_REQUIRES_OK(ctx, HbkStatus(hbk_sharded_set_ftrl_slots(plan->plan(), accum.data(),
-                                                             linear.data())));
-      OP_REQUIRES_OK(ctx, HbkStatus(hbk_sharded_lookup_bwd_ftrl(plan->plan(), g.data(), nullptr,
-                                                              &ftrl_.ftrl, lr, nullptr, nullptr,
-                                                              counts.data(), StreamOf(ctx))));
+      std::vector<float*> s0, s1;
+      hbk_adam_t a = adam_.Params();
+      OP_REQUIRES_OK(ctx, TwoSlots(accums, n, sizes, &s0, &s1, adam ? &a.beta_powers : nullptr));
+      if (adam) {
+        OP_REQUIRES_OK(ctx, HbkStatus(hbk_sharded_set_adam_slots(plan->plan(), s0.data(), s1.data())));
+        OP_REQUIRES_OK(ctx, HbkStatus(hbk_sharded_lookup_bwd_adam(plan->plan(), g.data(), nullptr, &a,
+                                                                lr, nullptr, nullptr, counts.data(),
+                                                                StreamOf(ctx))));
+      } else {
+        OP_REQUIRES_OK(ctx, HbkStatus(hbk_sharded_set_ftrl_slots(plan->plan(), s0.data(), s1.data())));
+        OP_REQUIRES_OK(ctx, HbkStatus(hbk_sharded_lookup_bwd_ftrl(plan->plan(), g.data(), nullptr,
+                                                                &ftrl_.ftrl, lr, nullptr, nullptr,
+                                                                counts.data(), StreamOf(ctx))));
+      }
     } else if (APPLY) {   // step only: no IndexedSlices are written
       OP_REQUIRES_OK(ctx, HbkStatus(hbk_sharded_lookup_bwd_apply(plan->plan(), g.data(), nullptr, apply_,
                                                                lr, nullptr, nullptr, counts.data(),
