@@ -131,6 +131,13 @@ def _declare(l):
     'hbk_group_lookup_bwd_adam': (C.c_int, [i32, vp, vp, vp, vp, C.c_float, vp, sz, vp]),
     'hbk_group_lookup_bwd_ftrl_workspace_bytes': (sz, [i32, vp]),
     'hbk_group_lookup_bwd_ftrl': (C.c_int, [i32, vp, vp, vp, vp, C.c_float, vp, sz, vp]),
+    'hbk_group_lookup_fwd_clipped': (C.c_int, [i32, vp, vp, vp]),
+    'hbk_group_lookup_bwd_apply_clipped_workspace_bytes': (sz, [i32, vp, vp]),
+    'hbk_group_lookup_bwd_apply_clipped': (C.c_int, [i32, vp, vp, i32, C.c_float, vp, sz, vp]),
+    'hbk_group_lookup_bwd_adam_clipped_workspace_bytes': (sz, [i32, vp, vp]),
+    'hbk_group_lookup_bwd_adam_clipped': (C.c_int, [i32, vp, vp, vp, vp, vp, C.c_float, vp, sz, vp]),
+    'hbk_group_lookup_bwd_ftrl_clipped_workspace_bytes': (sz, [i32, vp, vp]),
+    'hbk_group_lookup_bwd_ftrl_clipped': (C.c_int, [i32, vp, vp, vp, vp, vp, C.c_float, vp, sz, vp]),
     'hbk_group_stitch_bwd': (C.c_int, [i32, vp, vp]),
     'hbk_cache_probe': (C.c_int, [vp, i64, i32, vp, i64, vp, vp, vp]),
     'hbk_cache_lookup_workspace_bytes': (sz, [i64]),
@@ -157,6 +164,7 @@ def _declare(l):
     'hbk_sharded_create': (C.c_int, [vp, vp, i32, vp, i32]),
     'hbk_sharded_destroy': (C.c_int, [vp]),
     'hbk_sharded_set_hot_rows': (C.c_int, [vp, vp]),
+    'hbk_sharded_set_max_norms': (C.c_int, [vp, vp]),
     'hbk_sharded_lookup_fwd': (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
     'hbk_sharded_lookup_fwd_weighted': (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     'hbk_sharded_prefetch_on': (C.c_int, [vp, vp, vp, vp]),

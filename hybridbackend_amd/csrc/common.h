@@ -274,6 +274,10 @@ int adam_check(const hbk_adam_t* adam, float lr, const char* who);
 // host checks of an FTRL call's hyperparameters (sparse_apply.hip): HBK_OK or HBK_INVALID_ARGUMENT
 int ftrl_check(const hbk_ftrl_t* ftrl, float lr, const char* who);
 
+// every host check hbk_group_lookup_bwd_apply makes of its columns, without launching anything
+// (lookup_bwd.hip): HBK_OK or HBK_INVALID_ARGUMENT
+int bwd_check(int32_t n_cols, const hbk_lookup_grad_column_t* cols, int32_t apply, float apply_lr);
+
 // compute units of the current device (cached; lookup_bwd.hip)
 int device_cus();
 

@@ -3859,13 +3859,11 @@ BwdHelpers* bwd_helpers(hipStream_t caller) {
 static int bwd_planned(int32_t n_cols, const hbk_lookup_grad_column_t* cols, int32_t apply,
                        float apply_lr, void* workspace, hipStream_t stream, bool det);
 
-extern "C" int hbk_group_lookup_bwd_apply(int32_t n_cols, const hbk_lookup_grad_column_t* cols,
-                                          int32_t apply, float apply_lr, void* workspace,
-                                          size_t workspace_bytes, hbk_stream_t stream_) {
-  using namespace hbk;
+namespace hbk {
+// every host check of hbk_group_lookup_bwd_apply's arguments but the workspace (common.h)
+int bwd_check(int32_t n_cols, const hbk_lookup_grad_column_t* cols, int32_t apply, float apply_lr) {
   HBK_REQUIRE(apply == HBK_APPLY_SGD || apply == HBK_APPLY_ADAGRAD,
               "group_lookup_bwd: apply must be HBK_APPLY_SGD or HBK_APPLY_ADAGRAD, got %d", apply);
-  hipStream_t stream = as_stream(stream_);
   HBK_REQUIRE(n_cols >= 0, "group_lookup_bwd: n_cols must be >= 0, got %d", n_cols);
   if (n_cols == 0) return HBK_OK;
   HBK_REQUIRE(cols != nullptr, "group_lookup_bwd: cols is NULL");
@@ -3910,10 +3908,20 @@ extern "C" int hbk_group_lookup_bwd_apply(int32_t n_cols, const hbk_lookup_grad_
                 "group_lookup_bwd: column %d: id_weights cannot be combined with segmented inputs "
                 "(run_*: the owner-side reduce is never weighted)", c);
   }
+  return check_layouts(n_cols, cols, apply_lr);
+}
+}  // namespace hbk
+
+extern "C" int hbk_group_lookup_bwd_apply(int32_t n_cols, const hbk_lookup_grad_column_t* cols,
+                                          int32_t apply, float apply_lr, void* workspace,
+                                          size_t workspace_bytes, hbk_stream_t stream_) {
+  using namespace hbk;
+  hipStream_t stream = as_stream(stream_);
   {
-    const int rc = check_layouts(n_cols, cols, apply_lr);
+    const int rc = bwd_check(n_cols, cols, apply, apply_lr);
     if (rc != HBK_OK) return rc;
   }
+  if (n_cols == 0) return HBK_OK;
   // a deterministic call's split and the sort path's layout (two size queries of the sort / scan
   // primitives), made once and handed down
   const bool weighted = any_weighted(n_cols, cols);

@@ -16,6 +16,7 @@
 //   * ids and outputs are streamed with non-temporal accesses so the L2/MALL capacity is
 //     left to the table rows.
 #include <stdlib.h>
+#include <string.h>
 
 #include <vector>
 
@@ -113,13 +114,30 @@ struct LookupArgs {
 };
 static_assert(sizeof(LookupArgs) <= 24576, "kernarg budget");
 
+// max_norm (the clipped instantiations, hbk_group_lookup_fwd_clipped): y = (x * c) / max(|x|, c) of a
+// row x held by the LPR lanes of its group.  |x|^2 is summed per lane over its chunk in element order,
+// then by a butterfly over the group's lanes (xor 1, 2, 4, ..; both lanes of a pair add the same two
+// values, so every lane ends with the same bits).  Lanes without a row chunk hold zeros.
+__device__ inline float chunk_sq(float a) { return a * a; }
+__device__ inline float chunk_sq(f32x4 a) { return ((a.x * a.x + a.y * a.y) + a.z * a.z) + a.w * a.w; }
+
+template <typename V>
+__device__ inline V clip_row(V x, float c, int lpr_log2) {
+  float s = chunk_sq(x);
+  for (int o = 1; o < (1 << lpr_log2); o <<= 1) s = s + __shfl_xor(s, o, kWave);
+  const float n = s > 0.0f ? sqrtf(s) : 0.0f;
+  return (x * c) / fmaxf(n, c);
+}
+
 // ---------------------------------------------------------------------------------
 // one id per segment (Criteo scalar columns): out[s,:] = table[row(ids[s]),:]
 // WGT (weighted instantiations): out[s,:] = w_s e  (sum), (w_s e) / w_s  (mean), (w_s e) / sqrtf(w_s w_s)
 // (sqrtn); a zero divisor or an invalid row gives a zero row.  The weight is read beside the id (one
 // coalesced 4-byte load per segment) and handed to the row's lanes with the same shuffle.
-template <typename V, int U, bool RUNS, int HALF, bool SLOT = false, bool D16 = false, bool WGT = false>
-__device__ inline void gather_rows(const ColArg& c, int64_t wave_row0) {
+// CLIP: every row clipped to max_norm (clip_row) before its weight
+template <typename V, int U, bool RUNS, int HALF, bool SLOT = false, bool D16 = false, bool WGT = false,
+          bool CLIP = false>
+__device__ inline void gather_rows(const ColArg& c, int64_t wave_row0, float max_norm = 0.0f) {
   constexpr int VE = sizeof(V) / 4;
   const int lane = lane_id();
   const int lpr_log2 = D16 ? 2 : c.lpr_log2;   // (D16: the host has looked -- rows of 16 floats, int64 ids)
@@ -161,6 +179,7 @@ __device__ inline void gather_rows(const ColArg& c, int64_t wave_row0) {
     if (live && r != kNoRow) {
       v[u] = load_row_chunk<V, HALF>(c.table, row_offset<RUNS>(c, r) + (uint64_t)sub * VE);
     }
+    if (CLIP) v[u] = clip_row<V>(v[u], max_norm, lpr_log2);
     if (WGT) {
       float w = wreg[0];
 #pragma unroll
@@ -201,8 +220,8 @@ __device__ inline void gather_rows(const ColArg& c, int64_t wave_row0) {
 // accumulated in the same loop over the ids of valid rows; a zero divisor gives a zero row.  The
 // weights are read beside the ids (lane `sub` of the group owns weight j0 + sub) and handed to the
 // row's lanes with the same shuffle as the row.
-template <typename V, bool RUNS, int HALF, bool WGT = false>
-__device__ inline void combine_segments(const ColArg& c, int64_t wave_seg0) {
+template <typename V, bool RUNS, int HALF, bool WGT = false, bool CLIP = false>
+__device__ inline void combine_segments(const ColArg& c, int64_t wave_seg0, float max_norm = 0.0f) {
   constexpr int VE = sizeof(V) / 4;
   const int lane = lane_id();
   const int lpr_log2 = c.lpr_log2;
@@ -258,6 +277,7 @@ __device__ inline void combine_segments(const ColArg& c, int64_t wave_seg0) {
           if (p[t] && live && r != kNoRow) {
             v[t] = load_row_chunk<V, HALF>(c.table, row_offset<RUNS>(c, r) + (uint64_t)sub * VE);
           }
+          if (CLIP) v[t] = clip_row<V>(v[t], max_norm, lpr_log2);
         }
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
@@ -362,6 +382,49 @@ __global__ __launch_bounds__(kBlock) void group_lookup_fwd_weighted_kernel(const
     const int64_t seg0 = (tile * kWavesPerBlock + wave) * (int64_t)(kSegIters * rpi);
     if (seg0 >= c.n_seg) return;
     combine_segments<V, RUNS, HALF, true>(c, seg0);
+  }
+}
+
+// The clipped columns (hbk_group_lookup_fwd_clipped): the launch's columns and their max_norm
+struct ClipLookupArgs {
+  LookupArgs a;
+  float max_norm[kMaxColsPerLaunch];
+};
+static_assert(sizeof(ClipLookupArgs) <= 24576, "kernarg budget");
+
+// the same tiles and column search as group_lookup_fwd_kernel, every row clipped before its weight and
+// the combine (gather_rows / combine_segments, CLIP)
+template <bool CSR, typename V, bool RUNS, int HALF, bool WGT>
+__global__ __launch_bounds__(kBlock) void group_lookup_fwd_clip_kernel(const ClipLookupArgs ca) {
+  const LookupArgs& a = ca.a;
+  const int b = xcd_contiguous((int)blockIdx.x, (int)gridDim.x, a.xcd);
+  int ci;
+  int64_t tile;
+  if (a.interleave) {
+    ci = b % a.n_cols;
+    tile = b / a.n_cols;
+  } else {
+    const int lane = (int)threadIdx.x & (kWave - 1);
+    const int n = a.n_cols;
+    const int t0 = lane < n ? a.tile_start[lane] : 0x7fffffff;
+    const int t1 = lane + kWave < n ? a.tile_start[lane + kWave] : 0x7fffffff;
+    ci = (int)__builtin_popcountll(__ballot(t0 <= b)) +
+         (int)__builtin_popcountll(__ballot(t1 <= b)) - 1;
+    ci = __builtin_amdgcn_readfirstlane(ci);
+    tile = b - a.tile_start[ci];
+  }
+  const ColArg& c = a.col[ci];
+  const float max_norm = ca.max_norm[ci];
+  const int wave = (int)(threadIdx.x >> 6);
+  const int rpi = kWave >> c.lpr_log2;
+  if (!CSR) {
+    const int64_t row0 = (tile * kWavesPerBlock + wave) * (int64_t)(kU * rpi);
+    if (row0 >= c.n_seg) return;
+    gather_rows<V, kU, RUNS, HALF, false, false, WGT, true>(c, row0, max_norm);
+  } else {
+    const int64_t seg0 = (tile * kWavesPerBlock + wave) * (int64_t)(kSegIters * rpi);
+    if (seg0 >= c.n_seg) return;
+    combine_segments<V, RUNS, HALF, WGT, true>(c, seg0, max_norm);
   }
 }
 
@@ -535,6 +598,37 @@ void launch_weighted(const LookupArgs& args, unsigned tiles, hipStream_t stream)
 }
 
 constexpr int kWeightedKind = 40;   // + the column's kind (bits 0, 1, 2 and 4): weighted columns
+constexpr int kClipKind = 64;       // + the column's kind (bits 0, 1, 2 and 4) + 32 when weighted: clipped
+constexpr int kKinds = 128;
+
+template <bool CSR, typename V, bool RUNS, int HALF = 0, bool WGT = false>
+void launch_clip(const ClipLookupArgs& args, unsigned tiles, hipStream_t stream) {
+  hipLaunchKernelGGL((group_lookup_fwd_clip_kernel<CSR, V, RUNS, HALF, WGT>), dim3(tiles), dim3(kBlock), 0,
+                     stream, args);
+}
+
+void launch_clip_kind(int kind, const ClipLookupArgs& args, unsigned tiles, hipStream_t stream) {
+  switch (kind - kClipKind) {
+    case 0: launch_clip<false, f32x4, false>(args, tiles, stream); return;
+    case 1: launch_clip<true, f32x4, false>(args, tiles, stream); return;
+    case 2: launch_clip<false, float, false>(args, tiles, stream); return;
+    case 3: launch_clip<true, float, false>(args, tiles, stream); return;
+    case 4: launch_clip<false, f32x4, true>(args, tiles, stream); return;
+    case 5: launch_clip<true, f32x4, true>(args, tiles, stream); return;
+    case 6: launch_clip<false, float, true>(args, tiles, stream); return;
+    case 7: launch_clip<true, float, true>(args, tiles, stream); return;
+    case 16: launch_clip<false, f32x4, false, 1>(args, tiles, stream); return;   // half output (owner gather)
+    case 18: launch_clip<false, float, false, 1>(args, tiles, stream); return;
+    case 32: launch_clip<false, f32x4, false, 0, true>(args, tiles, stream); return;   // weighted
+    case 33: launch_clip<true, f32x4, false, 0, true>(args, tiles, stream); return;
+    case 34: launch_clip<false, float, false, 0, true>(args, tiles, stream); return;
+    case 35: launch_clip<true, float, false, 0, true>(args, tiles, stream); return;
+    case 36: launch_clip<false, f32x4, true, 0, true>(args, tiles, stream); return;
+    case 37: launch_clip<true, f32x4, true, 0, true>(args, tiles, stream); return;
+    case 38: launch_clip<false, float, true, 0, true>(args, tiles, stream); return;
+    default: launch_clip<true, float, true, 0, true>(args, tiles, stream); return;
+  }
+}
 
 void launch_by_kind(int kind, const LookupArgs& args, unsigned tiles, hipStream_t stream) {
   if (kind >= kWeightedKind) {
@@ -588,9 +682,11 @@ void launch_by_kind(int kind, const LookupArgs& args, unsigned tiles, hipStream_
 }  // namespace
 }  // namespace hbk
 
-extern "C" int hbk_group_lookup_fwd(int32_t n_cols, const hbk_lookup_column_t* cols,
-                                    hbk_stream_t stream) {
-  using namespace hbk;
+namespace hbk {
+namespace {
+// hbk_group_lookup_fwd, and with max_norms != NULL hbk_group_lookup_fwd_clipped (validated by the caller)
+int group_lookup_fwd(int32_t n_cols, const hbk_lookup_column_t* cols, const float* max_norms,
+                     hbk_stream_t stream) {
   HBK_REQUIRE(n_cols >= 0, "group_lookup_fwd: n_cols must be >= 0, got %d", n_cols);
   HBK_REQUIRE(n_cols == 0 || cols != nullptr, "group_lookup_fwd: cols is NULL");
   for (int32_t c = 0; c < n_cols; ++c) {
@@ -629,6 +725,10 @@ extern "C" int hbk_group_lookup_fwd(int32_t n_cols, const hbk_lookup_column_t* c
     HBK_REQUIRE(h.id_weights == nullptr || (h.out_slots == nullptr && h.half_io != HBK_LOOKUP_OUT_HALF),
                 "group_lookup_fwd: column %d: id_weights cannot be combined with out_slots or "
                 "HBK_LOOKUP_OUT_HALF (the owner gather is never weighted)", c);
+    HBK_REQUIRE(max_norms == nullptr || max_norms[c] == 0.0f ||
+                    (h.half_io != HBK_LOOKUP_TABLE_HALF && h.out_slots == nullptr),
+                "group_lookup_fwd_clipped: column %d: a clipped column cannot read fp16 table rows "
+                "(HBK_LOOKUP_TABLE_HALF) or write through out_slots", c);
   }
 
   const int hot_mode = options().fwd_hot_rows;
@@ -640,7 +740,7 @@ extern "C" int hbk_group_lookup_fwd(int32_t n_cols, const hbk_lookup_column_t* c
     int kind;   // -1: nothing to do (no segments)
   };
   std::vector<Classified> cls((size_t)(n_cols > 0 ? n_cols : 1));
-  uint64_t kinds_present = 0;
+  bool kinds_present[kKinds] = {};
   for (int32_t c = 0; c < n_cols; ++c) {
     const hbk_lookup_column_t& h = cols[c];
     cls[c].kind = -1;
@@ -671,12 +771,17 @@ extern "C" int hbk_group_lookup_fwd(int32_t n_cols, const hbk_lookup_column_t* c
       col_kind = 39;
     }
     // weighted columns: their own instantiations, never the hot-row or D16 kernels
-    if (h.id_weights != nullptr) col_kind = kWeightedKind + (col_kind == 8 || col_kind == 39 ? 0 : col_kind);
+    if (max_norms != nullptr && max_norms[c] != 0.0f) {
+      // clipped columns: their own instantiations (weighted or not), never the hot-row or D16 kernels
+      col_kind = kClipKind + (col_kind == 8 || col_kind == 39 ? 0 : col_kind) + (h.id_weights != nullptr ? 32 : 0);
+    } else if (h.id_weights != nullptr) {
+      col_kind = kWeightedKind + (col_kind == 8 || col_kind == 39 ? 0 : col_kind);
+    }
     cls[c].kind = col_kind;
-    kinds_present |= 1ull << col_kind;
+    kinds_present[col_kind] = true;
   }
-  for (int kind = 0; kind < 64; ++kind) {
-    if (((kinds_present >> kind) & 1ull) == 0ull) continue;
+  for (int kind = 0; kind < kKinds; ++kind) {
+    if (!kinds_present[kind]) continue;
     int32_t c0 = 0;
     while (c0 < n_cols) {
       LookupArgs args;
@@ -688,6 +793,7 @@ extern "C" int hbk_group_lookup_fwd(int32_t n_cols, const hbk_lookup_column_t* c
       bool same_tiles = true, one_block = true;   // (see args.interleave below)
       uintptr_t block_lo = 0, block_hi = 0;   // lowest / highest output address of the launch
       int64_t small_lookups = 0, all_lookups = 0;   // (tables of <= 2 MB: see args.xcd below)
+      float clip[kMaxColsPerLaunch];   // (clipped kinds)
       args.tile_start[0] = 0;
       while (c0 < n_cols && k < kMaxColsPerLaunch) {
         const int32_t ci = c0++;
@@ -717,6 +823,7 @@ extern "C" int hbk_group_lookup_fwd(int32_t n_cols, const hbk_lookup_column_t* c
         } else {
           d.out_slots = h.out_slots;
         }
+        clip[k] = kind >= kClipKind ? max_norms[ci] : 0.0f;
         const int64_t rpi = kWave >> d.lpr_log2;
         const int64_t per_block =
             col_kind == 8 ? kHotTile : kWavesPerBlock * rpi * (h.row_splits ? kSegIters : kU);
@@ -764,9 +871,38 @@ extern "C" int hbk_group_lookup_fwd(int32_t n_cols, const hbk_lookup_column_t* c
           (il == 3 || (one_block && (kind != 8 || il == 2)))) {
         args.interleave = 1;
       }
-      launch_by_kind(kind, args, (unsigned)tiles, as_stream(stream));
+      if (kind >= kClipKind) {
+        ClipLookupArgs ca;
+        ca.a = args;
+        memcpy(ca.max_norm, clip, sizeof(float) * (size_t)k);
+        launch_clip_kind(kind, ca, (unsigned)tiles, as_stream(stream));
+      } else {
+        launch_by_kind(kind, args, (unsigned)tiles, as_stream(stream));
+      }
       HBK_HIP_OK(hipGetLastError());
     }
   }
   return HBK_OK;
+}
+}  // namespace
+}  // namespace hbk
+
+extern "C" int hbk_group_lookup_fwd(int32_t n_cols, const hbk_lookup_column_t* cols,
+                                    hbk_stream_t stream) {
+  return hbk::group_lookup_fwd(n_cols, cols, nullptr, stream);
+}
+
+extern "C" int hbk_group_lookup_fwd_clipped(int32_t n_cols, const hbk_lookup_column_t* cols,
+                                            const float* max_norms, hbk_stream_t stream) {
+  using namespace hbk;
+  HBK_REQUIRE(n_cols <= 0 || max_norms != nullptr, "group_lookup_fwd_clipped: max_norms is NULL");
+  bool any = false;
+  for (int32_t c = 0; c < n_cols; ++c) {
+    const float x = max_norms[c];
+    HBK_REQUIRE(x >= 0.0f && x <= 3.402823466e38f,
+                "group_lookup_fwd_clipped: column %d: max_norm must be 0 (no clip) or finite and > 0, "
+                "got %g", c, (double)x);
+    any = any || x > 0.0f;
+  }
+  return group_lookup_fwd(n_cols, cols, any ? max_norms : nullptr, stream);
 }

@@ -545,6 +545,7 @@ struct hbk_sharded {
   std::vector<const int32_t*> row_splits;
   hbk::SlotPair adam;   // Lazy Adam's m / v shards (hbk_sharded_set_adam_slots)
   hbk::SlotPair ftrl;   // FTRL's accum / linear shards (hbk_sharded_set_ftrl_slots)
+  std::vector<float> max_norms;   // [N] the columns' max_norm (hbk_sharded_set_max_norms; 0: not clipped)
   std::vector<const float*> id_weights;   // [N] per-id weights of the last forward (NULL: unweighted):
                                           // the stitch applies them, the backward's stitch too
   std::vector<int32_t> send_sizes;   // S [N][W] rows this rank requests from owner q, column c
@@ -647,6 +648,7 @@ extern "C" int hbk_sharded_create(hbk_sharded_t* plan, hbk_comm_t comm, int32_t 
   p->N = n_cols;
   p->wire_dtype = wire_dtype;
   p->cols.assign(cols, cols + n_cols);
+  p->max_norms.assign((size_t)n_cols, 0.0f);
   // After the bucketize ids are < bucket, so when every bucket fits int32 the id exchange moves
   // half the bytes (the reference always sends the tensor's own dtype, nccl_collective.cc:257-259;
   // SURVEY 8e).  Option sharded_id64 keeps int64 on the wire.  (All options are read here, at
@@ -1172,6 +1174,12 @@ extern "C" int hbk_sharded_lookup_fwd_begin(hbk_sharded_t p, const int64_t* cons
                 "sharded_lookup_fwd: n_segments is NULL");
     p->n_seg[c] = p->row_splits[c] ? n_segments[c] : n_ids[c];
   }
+  for (int c = 0; c < N && p->p2p_bound; ++c) {
+    if (p->max_norms[(size_t)c] != 0.0f) {
+      return fail(HBK_UNIMPLEMENTED, "sharded_lookup_fwd: column %d is clipped (hbk_sharded_set_max_norms): the "
+                  "p2p form (hbk_sharded_p2p_bind) has no clipped owner gather", c);
+    }
+  }
   int rc;
   // option sharded_trace: host-side time of the step's phases on stderr (us)
   const bool trace = p->trace;
@@ -1473,11 +1481,13 @@ extern "C" int hbk_sharded_lookup_fwd_begin(hbk_sharded_t p, const int64_t* cons
     if (hop) HBK_HIP_OK(hipStreamWaitEvent(stream, p->ev[1][g], 0));
     if (hop && p2p) HBK_HIP_OK(hipStreamWaitEvent(stream, p->ev[3][0], 0));
     std::vector<hbk_lookup_column_t> v;
+    std::vector<float> clip;   // the owner clips: every virtual column carries its column's max_norm
     v.reserve((size_t)ng * W);
     for (int q = 0; q < W; ++q) {
       for (int c = 0; c < ng; ++c) {
         const int64_t n = gr.R[(size_t)q * ng + c];
         if (n == 0) continue;
+        clip.push_back(p->max_norms[(size_t)(gr.c0 + c)]);
         const hbk_sharded_column_t& col = p->cols[gr.c0 + c];
         hbk_lookup_column_t h;
         memset(&h, 0, sizeof(h));
@@ -1516,7 +1526,8 @@ extern "C" int hbk_sharded_lookup_fwd_begin(hbk_sharded_t p, const int64_t* cons
         v.push_back(h);
       }
     }
-    rc = hbk_group_lookup_fwd((int32_t)v.size(), v.data(), stream_);
+    // (no column clipped: hbk_group_lookup_fwd_clipped is hbk_group_lookup_fwd)
+    rc = hbk_group_lookup_fwd_clipped((int32_t)v.size(), v.data(), clip.data(), stream_);
     if (rc != HBK_OK) return rc;
     if (!wire) continue;
     if (hop) HBK_HIP_OK(hipEventRecord(p->ev[2][g], stream));
@@ -1753,11 +1764,12 @@ namespace {
 // the optimizer step of a sharded backward: the reduce's own SGD / Adagrad (apply), or -- with
 // workspace_bytes set -- a two-slot step after the owner-side reduce in its emit form: its workspace
 // query and its call on one launch group (columns c0 .., the last group or not)
+// (the clipped entries: with every max_norm 0 they are the unclipped ones)
 struct ShardedStep {
   int32_t apply;
-  size_t (*workspace_bytes)(int32_t n_cols, const hbk_lookup_grad_column_t* cols);
-  std::function<int(int32_t c0, int32_t n_cols, const hbk_lookup_grad_column_t* cols, bool last,
-                    void* workspace, size_t workspace_bytes, hbk_stream_t stream)>
+  size_t (*workspace_bytes)(int32_t n_cols, const hbk_lookup_grad_column_t* cols, const float* max_norms);
+  std::function<int(int32_t c0, int32_t n_cols, const hbk_lookup_grad_column_t* cols, const float* max_norms,
+                    bool last, void* workspace, size_t workspace_bytes, hbk_stream_t stream)>
       run;
 };
 }  // namespace
@@ -1936,18 +1948,20 @@ static int sharded_bwd(hbk_sharded_t p, const float* const* grads, const int32_t
   size_t ws = 0;
   for (int g = 0; g < G; ++g) {
     const Group& gr = p->groups[g];
-    const size_t w = (two_slot ? step.workspace_bytes : hbk_group_lookup_bwd_workspace_bytes)(
-        gr.c1 - gr.c0, v.data() + gr.c0);
+    const size_t w = (two_slot ? step.workspace_bytes : hbk_group_lookup_bwd_apply_clipped_workspace_bytes)(
+        gr.c1 - gr.c0, v.data() + gr.c0, p->max_norms.data() + gr.c0);
     ws = w > ws ? w : ws;
   }
   if ((rc = p->bwd_ws.ensure(ws + 8)) != HBK_OK) return rc;
   for (int g = 0; g < G; ++g) {
     const Group& gr = p->groups[g];
     if (hop) HBK_HIP_OK(hipStreamWaitEvent(stream, p->ev[1][g], 0));
-    rc = two_slot ? step.run(gr.c0, gr.c1 - gr.c0, v.data() + gr.c0, g == G - 1, p->bwd_ws.ptr,
+    // the owner clips: the reduce in its emit form, then the clip pass on the shard rows
+    const float* clip = p->max_norms.data() + gr.c0;
+    rc = two_slot ? step.run(gr.c0, gr.c1 - gr.c0, v.data() + gr.c0, clip, g == G - 1, p->bwd_ws.ptr,
                              p->bwd_ws.bytes, stream_)
-                  : hbk_group_lookup_bwd_apply(gr.c1 - gr.c0, v.data() + gr.c0, step.apply, apply_lr,
-                                               p->bwd_ws.ptr, p->bwd_ws.bytes, stream_);
+                  : hbk_group_lookup_bwd_apply_clipped(gr.c1 - gr.c0, v.data() + gr.c0, clip, step.apply,
+                                                       apply_lr, p->bwd_ws.ptr, p->bwd_ws.bytes, stream_);
     if (rc != HBK_OK) return rc;
   }
   return HBK_OK;
@@ -2030,14 +2044,14 @@ extern "C" int hbk_sharded_lookup_bwd_adam(hbk_sharded_t p, const float* const* 
   const int rc = two_slot_prologue(p, kNames, [&] { return adam_check(adam, lr, kNames.who); },
                                    "hbk_sharded_set_adam_slots", &hbk_sharded::adam);
   if (rc != HBK_OK) return rc;
-  const ShardedStep step{HBK_APPLY_SGD, hbk_group_lookup_bwd_adam_workspace_bytes,
-                         [&](int32_t c0, int32_t n, const hbk_lookup_grad_column_t* cols, bool last,
-                             void* ws, size_t ws_bytes, hbk_stream_t s) {
+  const ShardedStep step{HBK_APPLY_SGD, hbk_group_lookup_bwd_adam_clipped_workspace_bytes,
+                         [&](int32_t c0, int32_t n, const hbk_lookup_grad_column_t* cols, const float* clip,
+                             bool last, void* ws, size_t ws_bytes, hbk_stream_t s) {
                            hbk_adam_t a = *adam;
                            a.finish = last ? adam->finish : 0;   // the last launch group finishes
-                           return hbk_group_lookup_bwd_adam(n, cols, p->adam.s0.data() + c0,
-                                                            p->adam.s1.data() + c0, &a, lr, ws,
-                                                            ws_bytes, s);
+                           return hbk_group_lookup_bwd_adam_clipped(n, cols, clip, p->adam.s0.data() + c0,
+                                                                    p->adam.s1.data() + c0, &a, lr, ws,
+                                                                    ws_bytes, s);
                          }};
   return sharded_bwd(p, grads, grad_strides, step, lr, unique_rows, grad_rows, n_unique, stream_);
 }
@@ -2057,14 +2071,28 @@ extern "C" int hbk_sharded_lookup_bwd_ftrl(hbk_sharded_t p, const float* const* 
   const int rc = two_slot_prologue(p, kNames, [&] { return ftrl_check(ftrl, lr, kNames.who); },
                                    "hbk_sharded_set_ftrl_slots", &hbk_sharded::ftrl);
   if (rc != HBK_OK) return rc;
-  const ShardedStep step{HBK_APPLY_SGD, hbk_group_lookup_bwd_ftrl_workspace_bytes,
-                         [&](int32_t c0, int32_t n, const hbk_lookup_grad_column_t* cols, bool,
-                             void* ws, size_t ws_bytes, hbk_stream_t s) {
-                           return hbk_group_lookup_bwd_ftrl(n, cols, p->ftrl.s0.data() + c0,
-                                                            p->ftrl.s1.data() + c0, ftrl, lr, ws,
-                                                            ws_bytes, s);
+  const ShardedStep step{HBK_APPLY_SGD, hbk_group_lookup_bwd_ftrl_clipped_workspace_bytes,
+                         [&](int32_t c0, int32_t n, const hbk_lookup_grad_column_t* cols, const float* clip,
+                             bool, void* ws, size_t ws_bytes, hbk_stream_t s) {
+                           return hbk_group_lookup_bwd_ftrl_clipped(n, cols, clip, p->ftrl.s0.data() + c0,
+                                                                    p->ftrl.s1.data() + c0, ftrl, lr, ws,
+                                                                    ws_bytes, s);
                          }};
   return sharded_bwd(p, grads, grad_strides, step, lr, unique_rows, grad_rows, n_unique, stream_);
+}
+
+// max_norm of the plan's columns (hbk_group_lookup_fwd_clipped): the owner gather clips the rows before the
+// wire, the owner-side backward runs the clip pass on the shard rows; NULL = no column clipped
+extern "C" int hbk_sharded_set_max_norms(hbk_sharded_t p, const float* max_norms) {
+  using namespace hbk;
+  HBK_REQUIRE(p != nullptr, "sharded_set_max_norms: plan is NULL");
+  for (int c = 0; max_norms != nullptr && c < p->N; ++c) {
+    HBK_REQUIRE(max_norms[c] >= 0.0f && max_norms[c] <= 3.402823466e38f,
+                "sharded_set_max_norms: column %d: max_norm must be 0 (no clip) or finite and > 0, got %g", c,
+                (double)max_norms[c]);
+  }
+  for (int c = 0; c < p->N; ++c) p->max_norms[(size_t)c] = max_norms != nullptr ? max_norms[c] : 0.0f;
+  return HBK_OK;
 }
 
 // the per-column hot_rows hints of a live plan (hbk_sharded_column_t.hot_rows): the host side turns

@@ -56,7 +56,7 @@ struct SlotCol {
   int32_t pitch;            // floats between rows of w, s0 and s1
   int32_t lpr_log2;
   int32_t vec4;
-  int32_t pad;
+  float max_norm;           // > 0: the clip pass's c (clip kernels only; 0: the column is not clipped)
 };
 
 // the kernel arguments of one apply launch: the columns and the rule's parameters P
@@ -89,6 +89,8 @@ struct AdamParams {
 struct AdamRule {
   using Params = AdamParams;
   using State = float;
+  static constexpr int kSlots = 2;
+  static constexpr bool kStep = true;
   float lr_t, beta1, beta2, eps;
 
   __device__ static float& lds_lr_t() {
@@ -128,6 +130,8 @@ template <bool kPow>
 struct FtrlRule {
   using Params = FtrlParams;
   struct State {};
+  static constexpr int kSlots = 2;
+  static constexpr bool kStep = true;
   const FtrlParams& a;
 
   __device__ static void setup(const FtrlParams&) {}
@@ -161,8 +165,93 @@ struct FtrlRule {
   }
 };
 
-// one task: rows base + k * groups + grp (k < kSlotItems) of column c; W floats per lane chunk
-template <typename V, int W, typename Rule>
+// The rules of the clip pass (hbk_group_lookup_bwd_apply_clipped): SGD and Adagrad with the arithmetic
+// of the fused reduce's step (step_row, lookup_bwd.hip), so that a row with g' == g gets the same bits,
+// and the emit rule, which steps nothing and writes g' back over the gradient row.
+struct LrParams {
+  float lr;
+};
+struct SgdRule {
+  using Params = LrParams;
+  struct State {};
+  static constexpr int kSlots = 0;
+  static constexpr bool kStep = true;
+  float lr;
+
+  __device__ static void setup(const LrParams&) {}
+  __device__ static State state() { return State{}; }
+  __device__ SgdRule(const LrParams& p, State) : lr(p.lr) {}
+  template <typename V>
+  __device__ Stepped<V> operator()(V& w, V& s0, V& s1, V g) const {
+    return Stepped<V>{w - lr * g, s0, s1};
+  }
+};
+
+__device__ inline float rsqrt_v(float a) { return 1.0f / sqrtf(a); }
+__device__ inline f32x4 rsqrt_v(f32x4 a) {
+  return f32x4{1.0f / sqrtf(a.x), 1.0f / sqrtf(a.y), 1.0f / sqrtf(a.z), 1.0f / sqrtf(a.w)};
+}
+
+// s0 = the accumulator
+struct AdagradRule {
+  using Params = LrParams;
+  struct State {};
+  static constexpr int kSlots = 1;
+  static constexpr bool kStep = true;
+  float lr;
+
+  __device__ static void setup(const LrParams&) {}
+  __device__ static State state() { return State{}; }
+  __device__ AdagradRule(const LrParams& p, State) : lr(p.lr) {}
+  template <typename V>
+  __device__ Stepped<V> operator()(V& w, V& s0, V& s1, V g) const {
+    const V acc = s0 + g * g;
+    return Stepped<V>{w - (lr * g) * rsqrt_v(acc), acc, s1};
+  }
+};
+
+struct EmitRule {
+  using Params = LrParams;
+  struct State {};
+  static constexpr int kSlots = 0;
+  static constexpr bool kStep = false;
+
+  __device__ static void setup(const LrParams&) {}
+  __device__ static State state() { return State{}; }
+  __device__ EmitRule(const LrParams&, State) {}
+};
+
+// The clip prologue (include/hbk.h, hbk_group_lookup_fwd_clipped): the sums of a row over its lane
+// group, each lane's chunk in element order, then a butterfly over the group's lanes (xor 1, 2, 4, ..):
+// both lanes of a pair add the same two values, so every lane of the group ends with the same bits.
+__device__ inline float chunk_sum(float a) { return a; }
+__device__ inline float chunk_sum(f32x4 a) { return ((a.x + a.y) + a.z) + a.w; }
+__device__ inline float group_sum(float s, int lpr_log2) {
+  for (int o = 1; o < (1 << lpr_log2); o <<= 1) s = s + __shfl_xor(s, o, kWave);
+  return s;
+}
+
+// g' of one lane chunk from the pre-step row chunk x and the summed gradient chunk g (TF's clip_by_norm
+// differentiated once per distinct row).  Every lane of the group takes part (lanes without a row
+// pass zeros).
+template <typename V>
+__device__ inline V clip_grad(V x, V g, float c, int lpr_log2) {
+  const float s = group_sum(chunk_sum(x * x), lpr_log2);
+  const float n = s > 0.0f ? sqrtf(s) : 0.0f;
+  const float m = fmaxf(n, c);
+  // d = sum_k G_k * ((x_k * c) / m) / m: every term rounded on its own, then summed as s is
+  const float d = group_sum(chunk_sum((g * ((x * c) / m)) / m), lpr_log2);
+  const V tangent = (g / m) * c;
+  if (!(s > 0.0f && n >= c)) return tangent;
+  const float ds = (-d * 0.5f) / n;
+  return tangent + (2.0f * ds) * x;
+}
+
+// one task: rows base + k * groups + grp (k < kSlotItems) of column c; W floats per lane chunk.
+// Rule::kSlots slots are read and written; Rule::kStep false: nothing is stepped.  CLIP: the rows of a
+// column with max_norm > 0 step with clip_grad's g', which is written back over the gradient row in
+// every form (the IndexedSlices of a clipped column are the gradient its rows were stepped with).
+template <typename V, int W, typename Rule, bool CLIP = false>
 __device__ inline void slot_task(const SlotCol& c, int64_t base, int64_t n, const Rule& rule) {
   const int lane = lane_id();
   const int lpr = c.lpr_log2;
@@ -180,24 +269,42 @@ __device__ inline void slot_task(const SlotCol& c, int64_t base, int64_t n, cons
     on[k] = on[k] && (uint64_t)r[k] < (uint64_t)c.rows;   // (the reduce only emits rows of the table)
   }
   V w[kSlotItems], s0[kSlotItems], s1[kSlotItems], g[kSlotItems];
+  if constexpr (CLIP || Rule::kSlots < 2) {
+#pragma unroll
+    for (int k = 0; k < kSlotItems; ++k) w[k] = s0[k] = s1[k] = g[k] = zero_v<V>();
+  }
 #pragma unroll
   for (int k = 0; k < kSlotItems; ++k) {
     if (!on[k]) continue;
     const int64_t u = base + (int64_t)k * groups + grp;
     const int64_t off = r[k] * c.pitch + sub * W;
-    w[k] = *reinterpret_cast<const V*>(c.w + off);
-    s0[k] = *reinterpret_cast<const V*>(c.s0 + off);
-    s1[k] = *reinterpret_cast<const V*>(c.s1 + off);
+    if constexpr (Rule::kStep || CLIP) w[k] = *reinterpret_cast<const V*>(c.w + off);
+    if constexpr (Rule::kSlots >= 1) s0[k] = *reinterpret_cast<const V*>(c.s0 + off);
+    if constexpr (Rule::kSlots >= 2) s1[k] = *reinterpret_cast<const V*>(c.s1 + off);
     g[k] = __builtin_nontemporal_load(reinterpret_cast<const V*>(c.grows + u * c.dim + sub * W));
+  }
+  if constexpr (CLIP) {
+    if (c.max_norm != 0.0f) {   // (uniform: one column per task)
+#pragma unroll
+      for (int k = 0; k < kSlotItems; ++k) g[k] = clip_grad<V>(w[k], g[k], c.max_norm, lpr);
+    }
   }
 #pragma unroll
   for (int k = 0; k < kSlotItems; ++k) {
     if (!on[k]) continue;
-    const int64_t off = r[k] * c.pitch + sub * W;
-    const Stepped<V> o = rule(w[k], s0[k], s1[k], g[k]);
-    *reinterpret_cast<V*>(c.s0 + off) = o.s0;
-    *reinterpret_cast<V*>(c.s1 + off) = o.s1;
-    *reinterpret_cast<V*>(c.w + off) = o.w;
+    if constexpr (CLIP) {
+      if (c.max_norm != 0.0f) {
+        const int64_t u = base + (int64_t)k * groups + grp;
+        *reinterpret_cast<V*>(const_cast<float*>(c.grows) + u * c.dim + sub * W) = g[k];
+      }
+    }
+    if constexpr (Rule::kStep) {
+      const int64_t off = r[k] * c.pitch + sub * W;
+      const Stepped<V> o = rule(w[k], s0[k], s1[k], g[k]);
+      if constexpr (Rule::kSlots >= 1) *reinterpret_cast<V*>(c.s0 + off) = o.s0;
+      if constexpr (Rule::kSlots >= 2) *reinterpret_cast<V*>(c.s1 + off) = o.s1;
+      *reinterpret_cast<V*>(c.w + off) = o.w;
+    }
   }
 }
 
@@ -238,7 +345,7 @@ __device__ inline void walk_tasks(const SlotCol* cols, int n_cols, const int64_t
 }
 
 // the body of every apply kernel: the scan, the rule's setup, the barrier, the walk
-template <typename Rule>
+template <typename Rule, bool CLIP = false>
 __device__ inline void slot_apply_body(const SlotArgs<typename Rule::Params>& a) {
   __shared__ int64_t s_end[kSlotMaxCols];   // inclusive prefix of the columns' task counts
   __shared__ int64_t s_n[kSlotMaxCols];     // their n_unique (clamped to the capacity)
@@ -251,9 +358,9 @@ __device__ inline void slot_apply_body(const SlotArgs<typename Rule::Params>& a)
   const typename Rule::State st = Rule::state();
   walk_tasks(a.c, a.n_cols, s_end, s_n, [&](const SlotCol& col, int64_t base, int64_t n) {
     if (col.vec4) {
-      slot_task<f32x4, 4>(col, base, n, Rule(a.p, st));
+      slot_task<f32x4, 4, Rule, CLIP>(col, base, n, Rule(a.p, st));
     } else {
-      slot_task<float, 1>(col, base, n, Rule(a.p, st));
+      slot_task<float, 1, Rule, CLIP>(col, base, n, Rule(a.p, st));
     }
   });
 }
@@ -265,6 +372,28 @@ __global__ __launch_bounds__(kSlotBlock) void sparse_adam_apply_kernel(SlotArgs<
 template <bool kPow>
 __global__ __launch_bounds__(kSlotBlock) void sparse_ftrl_apply_kernel(SlotArgs<FtrlParams> a) {
   slot_apply_body<FtrlRule<kPow>>(a);
+}
+
+// the clip pass: the walk of the two-slot kernels with the clip prologue in front of the rule
+__global__ __launch_bounds__(kSlotBlock) void sparse_adam_clip_kernel(SlotArgs<AdamParams> a) {
+  slot_apply_body<AdamRule, true>(a);
+}
+
+template <bool kPow>
+__global__ __launch_bounds__(kSlotBlock) void sparse_ftrl_clip_kernel(SlotArgs<FtrlParams> a) {
+  slot_apply_body<FtrlRule<kPow>, true>(a);
+}
+
+__global__ __launch_bounds__(kSlotBlock) void sparse_sgd_clip_kernel(SlotArgs<LrParams> a) {
+  slot_apply_body<SgdRule, true>(a);
+}
+
+__global__ __launch_bounds__(kSlotBlock) void sparse_adagrad_clip_kernel(SlotArgs<LrParams> a) {
+  slot_apply_body<AdagradRule, true>(a);
+}
+
+__global__ __launch_bounds__(kSlotBlock) void sparse_emit_clip_kernel(SlotArgs<LrParams> a) {
+  slot_apply_body<EmitRule, true>(a);
 }
 
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -378,7 +507,7 @@ int run_emit_form(const char* who, int32_t n_cols, const hbk_lookup_grad_column_
 // and the grid the launch needs
 int fill_slot_cols(const std::vector<hbk_lookup_grad_column_t>& e, const std::vector<RowShape>& shapes,
                    float* const* s0, float* const* s1, int32_t c0, int32_t c1, SlotCol* out,
-                   unsigned* blocks) {
+                   unsigned* blocks, const float* max_norms = nullptr) {
   int64_t tasks = 0;
   int k = 0;
   for (int32_t c = c0; c < c1; ++c) {
@@ -398,6 +527,7 @@ int fill_slot_cols(const std::vector<hbk_lookup_grad_column_t>& e, const std::ve
     const RowShape& shape = shapes[(size_t)c];   // (validated before the reduce)
     d.lpr_log2 = shape.lpr_log2;
     d.vec4 = shape.vec4;
+    d.max_norm = max_norms != nullptr ? max_norms[c] : 0.0f;
     const int64_t rpt = (int64_t)(kWave >> shape.lpr_log2) * kSlotItems;
     tasks += (std::min<int64_t>(h.n_ids, h.rows) + rpt - 1) / rpt;
     ++k;
@@ -412,10 +542,12 @@ int fill_slot_cols(const std::vector<hbk_lookup_grad_column_t>& e, const std::ve
 // emit-form reduce, then one apply launch per kSlotMaxCols columns -- launch(args, blocks, stream)
 // sets args.p and launches the rule's kernel.  run_empty: go on with n_cols = 0 (what follows the
 // apply still has to run)
+// max_norms: NULL, or the clip of every column (the apply is then a clip kernel)
 template <typename P, typename Check, typename Launch>
 int slot_apply(const SlotNames& nm, Check check, bool run_empty, int32_t n_cols,
                const hbk_lookup_grad_column_t* cols, float* const* s0, float* const* s1, Launch launch,
-               void* workspace, size_t workspace_bytes, hbk_stream_t stream_) {
+               void* workspace, size_t workspace_bytes, hbk_stream_t stream_,
+               const float* max_norms = nullptr) {
   HBK_REQUIRE(n_cols >= 0, "%s: n_cols must be >= 0, got %d", nm.who, n_cols);
   int rc = check();
   if (rc != HBK_OK) return rc;
@@ -430,7 +562,8 @@ int slot_apply(const SlotNames& nm, Check check, bool run_empty, int32_t n_cols,
     SlotArgs<P> a;
     memset(&a, 0, sizeof(a));
     unsigned blocks = 0;
-    a.n_cols = fill_slot_cols(e, shapes, s0, s1, c0, std::min(n_cols, c0 + kSlotMaxCols), a.c, &blocks);
+    a.n_cols = fill_slot_cols(e, shapes, s0, s1, c0, std::min(n_cols, c0 + kSlotMaxCols), a.c, &blocks,
+                              max_norms);
     if (a.n_cols == 0) continue;
     launch(a, blocks, stream);
     HBK_HIP_OK(hipGetLastError());
@@ -477,6 +610,242 @@ int ftrl_check(const hbk_ftrl_t* ftrl, float lr, const char* who) {
 }
 }  // namespace hbk
 
+namespace hbk {
+namespace {
+// The clip of a call (max_norms[c] of hbk_group_lookup_bwd_*_clipped): 0 or a finite c > 0 per column,
+// refused otherwise.  *any: some column is clipped.
+int check_max_norms(const char* who, int32_t n_cols, const float* max_norms, bool* any) {
+  *any = false;
+  HBK_REQUIRE(n_cols <= 0 || max_norms != nullptr, "%s: max_norms is NULL", who);
+  for (int32_t c = 0; c < n_cols; ++c) {
+    const float x = max_norms[c];
+    HBK_REQUIRE(x >= 0.0f && x <= 3.402823466e38f,
+                "%s: column %d: max_norm must be 0 (no clip) or finite and > 0, got %g", who, c, (double)x);
+    *any = *any || x > 0.0f;
+  }
+  return HBK_OK;
+}
+
+int adam_call(int32_t n_cols, const hbk_lookup_grad_column_t* cols, const float* clip, float* const* m,
+              float* const* v, const hbk_adam_t* adam, float lr, void* workspace, size_t workspace_bytes,
+              hbk_stream_t stream_) {
+  static const SlotNames kNames = {"group_lookup_bwd_adam", "Adam", "m", "v"};
+  const int rc = slot_apply<AdamParams>(
+      kNames, [&] { return adam_check(adam, lr, kNames.who); }, adam != nullptr && adam->finish,
+      n_cols, cols, m, v,
+      [&](SlotArgs<AdamParams>& a, unsigned blocks, hipStream_t stream) {
+        a.p = AdamParams{adam->beta_powers, lr, adam->beta1, adam->beta2, adam->epsilon};
+        if (clip != nullptr) {
+          hipLaunchKernelGGL(sparse_adam_clip_kernel, dim3(blocks), dim3(kSlotBlock), 0, stream, a);
+        } else {
+          hipLaunchKernelGGL(sparse_adam_apply_kernel, dim3(blocks), dim3(kSlotBlock), 0, stream, a);
+        }
+      },
+      workspace, workspace_bytes, stream_, clip);
+  if (rc != HBK_OK || !adam->finish) return rc;
+  hipLaunchKernelGGL(adam_finish_kernel, dim3(1), dim3(kWave), 0, as_stream(stream_), adam->beta_powers,
+                     adam->beta1, adam->beta2);
+  HBK_HIP_OK(hipGetLastError());
+  return HBK_OK;
+}
+
+int ftrl_call(int32_t n_cols, const hbk_lookup_grad_column_t* cols, const float* clip, float* const* accum,
+              float* const* linear, const hbk_ftrl_t* ftrl, float lr, void* workspace,
+              size_t workspace_bytes, hbk_stream_t stream_) {
+  static const SlotNames kNames = {"group_lookup_bwd_ftrl", "FTRL", "accum", "linear"};
+  return slot_apply<FtrlParams>(
+      kNames, [&] { return ftrl_check(ftrl, lr, kNames.who); }, false, n_cols, cols, accum, linear,
+      [&](SlotArgs<FtrlParams>& a, unsigned blocks, hipStream_t stream) {
+        a.p = FtrlParams{lr, ftrl->l1, 2.0f * ftrl->l2, 2.0f * ftrl->l2_shrinkage, -ftrl->lr_power};
+        // lr_power = -0.5 (TF's default) takes the sqrtf instantiation, any other the powf one
+        if (clip != nullptr) {
+          if (ftrl->lr_power != -0.5f) {
+            hipLaunchKernelGGL(sparse_ftrl_clip_kernel<true>, dim3(blocks), dim3(kSlotBlock), 0, stream, a);
+          } else {
+            hipLaunchKernelGGL(sparse_ftrl_clip_kernel<false>, dim3(blocks), dim3(kSlotBlock), 0, stream, a);
+          }
+        } else if (ftrl->lr_power != -0.5f) {
+          hipLaunchKernelGGL(sparse_ftrl_apply_kernel<true>, dim3(blocks), dim3(kSlotBlock), 0, stream,
+                             a);
+        } else {
+          hipLaunchKernelGGL(sparse_ftrl_apply_kernel<false>, dim3(blocks), dim3(kSlotBlock), 0, stream,
+                             a);
+        }
+      },
+      workspace, workspace_bytes, stream_, clip);
+}
+
+// The columns of a clipped SGD / Adagrad / emit call, split: `plain` keeps the route of
+// hbk_group_lookup_bwd_apply (the fused step), `clipped` runs the emit form and the clip pass.
+struct ClipSplit {
+  std::vector<hbk_lookup_grad_column_t> plain, clipped;
+  std::vector<float> c;   // the clipped columns' max_norm
+};
+ClipSplit clip_split(int32_t n_cols, const hbk_lookup_grad_column_t* cols, const float* max_norms) {
+  ClipSplit s;
+  for (int32_t c = 0; c < n_cols; ++c) {
+    if (max_norms[c] > 0.0f) {
+      s.clipped.push_back(cols[c]);
+      s.c.push_back(max_norms[c]);
+    } else {
+      s.plain.push_back(cols[c]);
+    }
+  }
+  return s;
+}
+
+// the workspace of a split call: the plain columns' reduce, then the clipped columns' emit form and
+// step-only slices
+size_t clip_workspace_bytes(const ClipSplit& s) {
+  const size_t plain = hbk_group_lookup_bwd_workspace_bytes((int32_t)s.plain.size(), s.plain.data());
+  const size_t clipped = slot_workspace_bytes((int32_t)s.clipped.size(), s.clipped.data());
+  return align256(plain) + clipped;
+}
+}  // namespace
+}  // namespace hbk
+
+extern "C" size_t hbk_group_lookup_bwd_apply_clipped_workspace_bytes(int32_t n_cols,
+                                                                    const hbk_lookup_grad_column_t* cols,
+                                                                    const float* max_norms) {
+  using namespace hbk;
+  bool any = false;
+  if (n_cols <= 0 || cols == nullptr || check_max_norms("", n_cols, max_norms, &any) != HBK_OK || !any) {
+    return hbk_group_lookup_bwd_workspace_bytes(n_cols, cols);
+  }
+  return clip_workspace_bytes(clip_split(n_cols, cols, max_norms));
+}
+
+extern "C" int hbk_group_lookup_bwd_apply_clipped(int32_t n_cols, const hbk_lookup_grad_column_t* cols,
+                                                  const float* max_norms, int32_t apply, float apply_lr,
+                                                  void* workspace, size_t workspace_bytes,
+                                                  hbk_stream_t stream_) {
+  using namespace hbk;
+  static const char* kWho = "group_lookup_bwd_apply_clipped";
+  HBK_REQUIRE(n_cols >= 0, "%s: n_cols must be >= 0, got %d", kWho, n_cols);
+  HBK_REQUIRE(n_cols == 0 || cols != nullptr, "%s: cols is NULL", kWho);
+  bool any = false;
+  int rc = check_max_norms(kWho, n_cols, max_norms, &any);
+  if (rc != HBK_OK) return rc;
+  if (!any) {
+    return hbk_group_lookup_bwd_apply(n_cols, cols, apply, apply_lr, workspace, workspace_bytes, stream_);
+  }
+  // every check of both halves before the first launch: a refused call steps and writes nothing
+  if ((rc = bwd_check(n_cols, cols, apply, apply_lr)) != HBK_OK) return rc;
+  const ClipSplit s = clip_split(n_cols, cols, max_norms);
+  const int32_t nc = (int32_t)s.clipped.size();
+  {
+    const std::vector<hbk_lookup_grad_column_t> q = emit_form(nc, s.clipped.data());
+    if ((rc = bwd_check(nc, q.data(), HBK_APPLY_SGD, 0.0f)) != HBK_OK) return rc;
+  }
+  const bool stepping = apply_lr != 0.0f;
+  const bool adagrad = stepping && apply == HBK_APPLY_ADAGRAD;
+  std::vector<RowShape> shapes((size_t)nc);
+  std::vector<float*> s0((size_t)nc, nullptr), s1((size_t)nc, nullptr);
+  for (int32_t k = 0; k < nc; ++k) {
+    const hbk_lookup_grad_column_t& h = s.clipped[(size_t)k];
+    if (h.n_ids <= 0) continue;
+    HBK_REQUIRE(h.table != nullptr, "%s: clipped column %d: table is NULL (the clip reads the rows)", kWho,
+                k);
+    const int32_t pitch = h.table_pitch > 0 ? h.table_pitch : h.dim;
+    if (adagrad) s0[(size_t)k] = h.accum;
+    HBK_REQUIRE(make_rowshape(h.dim,
+                              (uintptr_t)h.table | (uintptr_t)h.grad_rows | (adagrad ? (uintptr_t)h.accum : 0) |
+                                  ((uintptr_t)(uint32_t)pitch * 4),
+                              &shapes[(size_t)k]),
+                "%s: clipped column %d: dim %d needs more than 64 lanes per row (at most 256 with 16-byte "
+                "aligned table / accum / grad_rows / pitch, 64 otherwise)", kWho, k, h.dim);
+  }
+  if (stepping) {
+    // the clip reads every row as it was before this call's step: a table stepped by a clipped column
+    // may not be named by any other column of the call
+    for (int32_t a = 0; a < n_cols; ++a) {
+      if (max_norms[a] <= 0.0f || cols[a].n_ids <= 0) continue;
+      for (int32_t b = 0; b < n_cols; ++b) {
+        if (b == a || cols[b].n_ids <= 0) continue;
+        HBK_REQUIRE(cols[b].table != cols[a].table && cols[b].accum != cols[a].table &&
+                        (cols[a].accum == nullptr ||
+                         (cols[b].table != cols[a].accum && cols[b].accum != cols[a].accum)),
+                    "%s: columns %d and %d share a table or accumulator; a clipped column's table may "
+                    "not be named twice in a stepping call", kWho, a, b);
+      }
+    }
+  }
+  const size_t plain_ws = hbk_group_lookup_bwd_workspace_bytes((int32_t)s.plain.size(), s.plain.data());
+  const size_t need = clip_workspace_bytes(s);
+  HBK_REQUIRE(need == 0 || (workspace != nullptr && workspace_bytes >= need),
+              "%s: workspace too small: need %zu bytes, got %zu", kWho, need, workspace_bytes);
+  HBK_REQUIRE(((uintptr_t)workspace & 7) == 0, "%s: workspace must be 8-byte aligned", kWho);
+  // (1) the plain columns on their own route
+  if (!s.plain.empty()) {
+    rc = hbk_group_lookup_bwd_apply((int32_t)s.plain.size(), s.plain.data(), apply, apply_lr, workspace,
+                                    workspace_bytes, stream_);
+    if (rc != HBK_OK) return rc;
+  }
+  // (2) the clipped columns' emit form behind them in the workspace, (3) the clip pass
+  char* const ws = reinterpret_cast<char*>(workspace) + align256(plain_ws);
+  std::vector<hbk_lookup_grad_column_t> e;
+  rc = run_emit_form(kWho, nc, s.clipped.data(), ws, workspace_bytes - align256(plain_ws), stream_, &e);
+  if (rc != HBK_OK) return rc;
+  hipStream_t stream = as_stream(stream_);
+  for (int32_t c0 = 0; c0 < nc; c0 += kSlotMaxCols) {
+    SlotArgs<LrParams> a;
+    memset(&a, 0, sizeof(a));
+    unsigned blocks = 0;
+    a.n_cols = fill_slot_cols(e, shapes, s0.data(), s1.data(), c0, std::min(nc, c0 + kSlotMaxCols), a.c,
+                              &blocks, s.c.data());
+    if (a.n_cols == 0) continue;
+    a.p = LrParams{apply_lr};
+    if (!stepping) {
+      hipLaunchKernelGGL(sparse_emit_clip_kernel, dim3(blocks), dim3(kSlotBlock), 0, stream, a);
+    } else if (adagrad) {
+      hipLaunchKernelGGL(sparse_adagrad_clip_kernel, dim3(blocks), dim3(kSlotBlock), 0, stream, a);
+    } else {
+      hipLaunchKernelGGL(sparse_sgd_clip_kernel, dim3(blocks), dim3(kSlotBlock), 0, stream, a);
+    }
+    HBK_HIP_OK(hipGetLastError());
+  }
+  return HBK_OK;
+}
+
+extern "C" size_t hbk_group_lookup_bwd_adam_clipped_workspace_bytes(int32_t n_cols,
+                                                                   const hbk_lookup_grad_column_t* cols,
+                                                                   const float* max_norms) {
+  (void)max_norms;
+  return hbk::slot_workspace_bytes(n_cols, cols);
+}
+
+extern "C" int hbk_group_lookup_bwd_adam_clipped(int32_t n_cols, const hbk_lookup_grad_column_t* cols,
+                                                 const float* max_norms, float* const* m, float* const* v,
+                                                 const hbk_adam_t* adam, float lr, void* workspace,
+                                                 size_t workspace_bytes, hbk_stream_t stream_) {
+  using namespace hbk;
+  bool any = false;
+  const int rc = check_max_norms("group_lookup_bwd_adam_clipped", n_cols, max_norms, &any);
+  if (rc != HBK_OK) return rc;
+  return adam_call(n_cols, cols, any ? max_norms : nullptr, m, v, adam, lr, workspace, workspace_bytes,
+                   stream_);
+}
+
+extern "C" size_t hbk_group_lookup_bwd_ftrl_clipped_workspace_bytes(int32_t n_cols,
+                                                                   const hbk_lookup_grad_column_t* cols,
+                                                                   const float* max_norms) {
+  (void)max_norms;
+  return hbk::slot_workspace_bytes(n_cols, cols);
+}
+
+extern "C" int hbk_group_lookup_bwd_ftrl_clipped(int32_t n_cols, const hbk_lookup_grad_column_t* cols,
+                                                 const float* max_norms, float* const* accum,
+                                                 float* const* linear, const hbk_ftrl_t* ftrl, float lr,
+                                                 void* workspace, size_t workspace_bytes,
+                                                 hbk_stream_t stream_) {
+  using namespace hbk;
+  bool any = false;
+  const int rc = check_max_norms("group_lookup_bwd_ftrl_clipped", n_cols, max_norms, &any);
+  if (rc != HBK_OK) return rc;
+  return ftrl_call(n_cols, cols, any ? max_norms : nullptr, accum, linear, ftrl, lr, workspace,
+                   workspace_bytes, stream_);
+}
+
 extern "C" size_t hbk_group_lookup_bwd_adam_workspace_bytes(int32_t n_cols,
                                                             const hbk_lookup_grad_column_t* cols) {
   return hbk::slot_workspace_bytes(n_cols, cols);
@@ -486,21 +855,7 @@ extern "C" int hbk_group_lookup_bwd_adam(int32_t n_cols, const hbk_lookup_grad_c
                                          float* const* m, float* const* v, const hbk_adam_t* adam,
                                          float lr, void* workspace, size_t workspace_bytes,
                                          hbk_stream_t stream_) {
-  using namespace hbk;
-  static const SlotNames kNames = {"group_lookup_bwd_adam", "Adam", "m", "v"};
-  const int rc = slot_apply<AdamParams>(
-      kNames, [&] { return adam_check(adam, lr, kNames.who); }, adam != nullptr && adam->finish,
-      n_cols, cols, m, v,
-      [&](SlotArgs<AdamParams>& a, unsigned blocks, hipStream_t stream) {
-        a.p = AdamParams{adam->beta_powers, lr, adam->beta1, adam->beta2, adam->epsilon};
-        hipLaunchKernelGGL(sparse_adam_apply_kernel, dim3(blocks), dim3(kSlotBlock), 0, stream, a);
-      },
-      workspace, workspace_bytes, stream_);
-  if (rc != HBK_OK || !adam->finish) return rc;
-  hipLaunchKernelGGL(adam_finish_kernel, dim3(1), dim3(kWave), 0, as_stream(stream_), adam->beta_powers,
-                     adam->beta1, adam->beta2);
-  HBK_HIP_OK(hipGetLastError());
-  return HBK_OK;
+  return hbk::adam_call(n_cols, cols, nullptr, m, v, adam, lr, workspace, workspace_bytes, stream_);
 }
 
 extern "C" size_t hbk_group_lookup_bwd_ftrl_workspace_bytes(int32_t n_cols,
@@ -512,20 +867,6 @@ extern "C" int hbk_group_lookup_bwd_ftrl(int32_t n_cols, const hbk_lookup_grad_c
                                          float* const* accum, float* const* linear,
                                          const hbk_ftrl_t* ftrl, float lr, void* workspace,
                                          size_t workspace_bytes, hbk_stream_t stream_) {
-  using namespace hbk;
-  static const SlotNames kNames = {"group_lookup_bwd_ftrl", "FTRL", "accum", "linear"};
-  return slot_apply<FtrlParams>(
-      kNames, [&] { return ftrl_check(ftrl, lr, kNames.who); }, false, n_cols, cols, accum, linear,
-      [&](SlotArgs<FtrlParams>& a, unsigned blocks, hipStream_t stream) {
-        a.p = FtrlParams{lr, ftrl->l1, 2.0f * ftrl->l2, 2.0f * ftrl->l2_shrinkage, -ftrl->lr_power};
-        // lr_power = -0.5 (TF's default) takes the sqrtf instantiation, any other the powf one
-        if (ftrl->lr_power != -0.5f) {
-          hipLaunchKernelGGL(sparse_ftrl_apply_kernel<true>, dim3(blocks), dim3(kSlotBlock), 0, stream,
-                             a);
-        } else {
-          hipLaunchKernelGGL(sparse_ftrl_apply_kernel<false>, dim3(blocks), dim3(kSlotBlock), 0, stream,
-                             a);
-        }
-      },
-      workspace, workspace_bytes, stream_);
+  return hbk::ftrl_call(n_cols, cols, nullptr, accum, linear, ftrl, lr, workspace, workspace_bytes,
+                        stream_);
 }

@@ -12,8 +12,14 @@ produces (hybridbackend/tensorflow/data/dataframe.py:366-376).
 ``sp_weights`` (per column None or an fp32 device vector with one weight per id) gives
 ``embedding_lookup_sparse``'s weighted form: sum ``w e``, mean ``sum w e / sum w``, sqrtn
 ``sum w e / sqrt(sum w^2)``; a segment whose divisor is 0 gives a zero row (include/hbk.h).
+
+``max_norms`` gives ``max_norm=`` of ``embedding_lookup[_sparse]`` / ``embedding_column``: every
+gathered row is clipped to an L2 norm of at most ``c`` (``x * c / max(|x|, c)``) before its weight and
+the combine, and ``GroupLookupGrad`` differentiates through the clip (include/hbk.h).
 """
 import ctypes as C
+import math
+import numbers
 
 import numpy as np
 import torch
@@ -25,6 +31,34 @@ from hybridbackend_amd.embedding import optimizer as _opt
 _COMBINERS = {None: _lib.COMBINER_MEAN,  # embedding_lookup_sparse default
               'sum': _lib.COMBINER_SUM, 'mean': _lib.COMBINER_MEAN,
               'sqrtn': _lib.COMBINER_SQRTN}
+
+
+def max_norm_list(max_norms, n):
+  """``max_norms`` (None, one number for all columns, or one per column, None = not clipped) as a list
+  of n floats, 0.0 for a column without a clip; an explicit value must be finite and > 0."""
+  if max_norms is None or isinstance(max_norms, numbers.Real):
+    max_norms = [max_norms] * n
+  try:
+    max_norms = list(max_norms)
+  except TypeError:
+    raise _lib.InvalidArgumentError(
+      _lib.INVALID_ARGUMENT, f'max_norms must be None, a number or one per column, got {max_norms!r}') from None
+  if len(max_norms) != n:
+    raise _lib.InvalidArgumentError(
+      _lib.INVALID_ARGUMENT, f'expected {n} max_norms, got {len(max_norms)}')
+  out = []
+  for c, x in enumerate(max_norms):
+    if x is None:
+      out.append(0.0)
+      continue
+    if isinstance(x, (bool, np.bool_)) or not isinstance(x, numbers.Real) or not math.isfinite(x) or x <= 0:
+      raise _lib.InvalidArgumentError(
+        _lib.INVALID_ARGUMENT, f'max_norm of column {c} must be None or finite and > 0, got {x!r}')
+    if float(C.c_float(x).value) <= 0.0 or not math.isfinite(C.c_float(x).value):
+      raise _lib.InvalidArgumentError(
+        _lib.INVALID_ARGUMENT, f'max_norm of column {c} is not a finite positive fp32 value: {x!r}')
+    out.append(float(x))
+  return out
 
 
 def _combiner_code(c):
@@ -55,9 +89,12 @@ class GroupLookup:
       forward that finds the copy landed turns the staging on for the columns whose last batch
       named fewer than half as many distinct rows as ids, off for the others (the reference's
       cache in front of the table is switched by the user, service.py:87; here the engine looks).
+    max_norms: TF's ``max_norm``: None (no clip), one number for all columns or one per column (None:
+      that column is not clipped).  A clipped row is ``x * c / max(|x|, c)``; ``hot_rows`` is ignored
+      for clipped columns.  Values must be finite and > 0.
   """
 
-  def __init__(self, tables, buckets=None, combiners='sum', divisor=1, hot_rows=False):
+  def __init__(self, tables, buckets=None, combiners='sum', divisor=1, hot_rows=False, max_norms=None):
     self._lib = _lib.lib()
     self.tables = list(tables)
     n = len(self.tables)
@@ -73,6 +110,9 @@ class GroupLookup:
     self.buckets = [int(b or 0) for b in buckets]
     self.combiners = [_combiner_code(c) for c in combiners]
     self.divisor = int(divisor)
+    self.max_norms = max_norm_list(max_norms, n)
+    # the host float[n] of the clipped C entries; None: no column is clipped (the plain entries)
+    self.max_norms_c = (C.c_float * n)(*self.max_norms) if any(self.max_norms) else None
     if isinstance(hot_rows, (bool, int, str)):
       hot_rows = [hot_rows] * n
     self._auto_hot = [c for c in range(n) if hot_rows[c] == 'auto']
@@ -281,7 +321,10 @@ class GroupLookup:
       s = _lib.current_stream(self.tables[0].device if self.tables else None)
     else:
       s = C.c_void_p(stream.cuda_stream)
-    _lib.check(self._lib.hbk_group_lookup_fwd(len(self.tables), self._cols, s))
+    if self.max_norms_c is not None:
+      _lib.check(self._lib.hbk_group_lookup_fwd_clipped(len(self.tables), self._cols, self.max_norms_c, s))
+    else:
+      _lib.check(self._lib.hbk_group_lookup_fwd(len(self.tables), self._cols, s))
 
   def __call__(self, ids, row_splits=None, outs=None, lazy=False, sp_weights=None):
     # handed the SAME tensors as the call before (resident buffers refilled in place, caller-owned
@@ -332,10 +375,10 @@ class _LazyOutputs(_marshal.collections.abc.Sequence):
 
 
 def group_lookup(tables, ids, row_splits=None, buckets=None, combiners='sum', divisor=1,
-                 outs=None, sp_weights=None):
+                 outs=None, sp_weights=None, max_norms=None):
   """Functional form: one fused launch over N columns; returns the list of outputs."""
-  return GroupLookup(tables, buckets, combiners, divisor)(ids, row_splits, outs,
-                                                          sp_weights=sp_weights)
+  return GroupLookup(tables, buckets, combiners, divisor, max_norms=max_norms)(
+    ids, row_splits, outs, sp_weights=sp_weights)
 
 
 class GroupLookupGrad:
@@ -376,7 +419,12 @@ class GroupLookupGrad:
 
     ftrl_slots: per column the FTRL slots ``(accum, linear)`` (fp32, same shape as the weights; accum
     filled with ``initial_accumulator_value``, linear zeros: :meth:`Ftrl.slots_like`), needed for
-    ``optimizer='ftrl'``; ftrl: the :class:`Ftrl` hyperparameters (TF's defaults when omitted)."""
+    ``optimizer='ftrl'``; ftrl: the :class:`Ftrl` hyperparameters (TF's defaults when omitted).
+
+    A lookup with ``max_norms`` is differentiated through its clip: every optimizer steps with the
+    clipped gradient g' of each distinct row, taken at the row as it was before the step, and the
+    returned gradient rows of a clipped column are g' in every form (with or without a step).  A
+    stepping call refuses a clipped column whose table another column also names."""
     self._lib = _lib.lib()
     self.lookup = lookup
     n = len(lookup)
@@ -599,12 +647,16 @@ class GroupLookupGrad:
     # an earlier step; the workspace query below counts their gradient-term buffers
     if n:
       self._cols_np['id_weights'] = _marshal.weight_ptrs(sp_weights, ids)
-    need = self._lib.hbk_group_lookup_bwd_workspace_bytes(n, self._cols)   # (depends on options too)
+    clip = self.lookup.max_norms_c
+    if clip is None:
+      need = self._lib.hbk_group_lookup_bwd_workspace_bytes(n, self._cols)   # (depends on options too)
+    else:
+      need = self._lib.hbk_group_lookup_bwd_apply_clipped_workspace_bytes(n, self._cols, clip)
     self._slot_cd = None
     if self._slot_ptrs:
       # (sized for the two-slot forms too: launch() may take any of them; they share one query)
       self._slot_cd = self._slot_form()
-      need = max(need, _opt.TWO_SLOT[next(iter(self._slot_ptrs))].workspace_bytes(n, self._slot_cd))
+      need = max(need, _opt.TWO_SLOT[next(iter(self._slot_ptrs))].workspace_bytes(n, self._slot_cd, clip))
     if self._ws is None or self._ws.numel() < need:
       self._ws = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
     self._ws_bound = self._ws       # (launch(): the workspace this binding was sized for)
@@ -631,15 +683,19 @@ class GroupLookupGrad:
   _NEEDS = 'GroupLookupGrad(lookup, {kw}=[({s0}, {s1}), ...])'
 
   def _step(self, n, optimizer, two_slot, apply_lr, finish, ws, dev):
+    clip = self.lookup.max_norms_c
     if two_slot is not None and apply_lr != 0.0:
       s0, s1 = self._slot_ptrs[two_slot.name]
       getattr(self, two_slot.name).group_step(n, self._slot_cd, s0, s1, apply_lr, ws,
-                                              _lib.current_stream(dev), finish)
+                                              _lib.current_stream(dev), finish, max_norms=clip)
       return
-    _lib.check(self._lib.hbk_group_lookup_bwd_apply(
-      n, self._cols, _lib.APPLY_ADAGRAD if optimizer == 'adagrad' else _lib.APPLY_SGD,
-      C.c_float(apply_lr), C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()),
-      _lib.current_stream(dev)))
+    apply = _lib.APPLY_ADAGRAD if optimizer == 'adagrad' else _lib.APPLY_SGD
+    tail = (apply, C.c_float(apply_lr), C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()),
+            _lib.current_stream(dev))
+    if clip is not None:
+      _lib.check(self._lib.hbk_group_lookup_bwd_apply_clipped(n, self._cols, clip, *tail))
+    else:
+      _lib.check(self._lib.hbk_group_lookup_bwd_apply(n, self._cols, *tail))
 
   def launch(self, apply_lr=0.0, optimizer='sgd', finish=True):
     """The backward of the LAST call again, on the same tensors (a training loop over resident

@@ -16,22 +16,28 @@ class _TwoSlot:
   """What the drivers use of a two-slot optimizer.  A subclass sets ``name`` (``optimizer=``, and the
   drivers' attribute holding the object), ``slot_kw`` (the drivers' keyword and attribute of the slot
   pairs), ``slot_names``, ``tf_suffixes`` (checkpoint names of the two slots), and implements
-  ``params(finish)`` (the C parameter struct), ``slots_like(table)`` and ``_c(lib)`` (its C entry
-  points: group step, workspace query, sharded slot registration, sharded step)."""
+  ``params(finish)`` (the C parameter struct), ``slots_like(table)``, ``_c(lib)`` (its C entry
+  points: group step, workspace query, sharded slot registration, sharded step) and ``_c_clipped(lib)``
+  (the max_norm forms of the group step and its workspace query)."""
 
   def tf_variables(self):
     """Checkpoint variables besides the slots: ``{name: tensor}``."""
     return {}
 
   @classmethod
-  def workspace_bytes(cls, n, cols):
+  def workspace_bytes(cls, n, cols, max_norms=None):
+    if max_norms is not None:
+      return cls._c_clipped(_lib.lib())[1](n, cols, max_norms)
     return cls._c(_lib.lib())[1](n, cols)
 
-  def group_step(self, n, cols, s0_ptrs, s1_ptrs, lr, ws, stream, finish=True):
-    """The step of ``GroupLookupGrad``: the emit-form reduce and the apply on ``n`` descriptors."""
-    _lib.check(self._c(_lib.lib())[0](
-      n, cols, s0_ptrs, s1_ptrs, C.byref(self.params(finish)), C.c_float(lr),
-      C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()), stream))
+  def group_step(self, n, cols, s0_ptrs, s1_ptrs, lr, ws, stream, finish=True, max_norms=None):
+    """The step of ``GroupLookupGrad``: the emit-form reduce and the apply on ``n`` descriptors;
+    ``max_norms`` (a ctypes float array, or None): the clipped form."""
+    lib = _lib.lib()
+    head = (n, cols) if max_norms is None else (n, cols, max_norms)
+    fn = self._c(lib)[0] if max_norms is None else self._c_clipped(lib)[0]
+    _lib.check(fn(*head, s0_ptrs, s1_ptrs, C.byref(self.params(finish)), C.c_float(lr),
+                  C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()), stream))
 
   def set_sharded_slots(self, plan, pairs):
     """Every column's slot shards, registered with a sharded plan."""
@@ -109,6 +115,10 @@ class LazyAdam(_TwoSlot):
     return (lib.hbk_group_lookup_bwd_adam, lib.hbk_group_lookup_bwd_adam_workspace_bytes,
             lib.hbk_sharded_set_adam_slots, lib.hbk_sharded_lookup_bwd_adam)
 
+  @staticmethod
+  def _c_clipped(lib):
+    return (lib.hbk_group_lookup_bwd_adam_clipped, lib.hbk_group_lookup_bwd_adam_clipped_workspace_bytes)
+
 
 class Ftrl(_TwoSlot):
   """The sparse FTRL-Proximal step of ``GroupLookupGrad`` / ``ShardedGroupLookup`` / ``DenseFeatures``
@@ -162,6 +172,10 @@ class Ftrl(_TwoSlot):
   def _c(lib):
     return (lib.hbk_group_lookup_bwd_ftrl, lib.hbk_group_lookup_bwd_ftrl_workspace_bytes,
             lib.hbk_sharded_set_ftrl_slots, lib.hbk_sharded_lookup_bwd_ftrl)
+
+  @staticmethod
+  def _c_clipped(lib):
+    return (lib.hbk_group_lookup_bwd_ftrl_clipped, lib.hbk_group_lookup_bwd_ftrl_clipped_workspace_bytes)
 
 
 # the two-slot optimizers by their optimizer= name; 'sgd' and 'adagrad' are fused into the reduce

@@ -79,12 +79,19 @@ class ShardedGroupLookup:
       patched lookup (docs/tutorial/ranking/data.py:180-182: ``tf.unique`` -> lookup ->
       ``tf.gather``).  Same results; fewer ids out, fewer rows back and fewer gradient rows in the
       backward when ids repeat inside a batch (Zipf), at the price of a unique over the batch.
+    max_norms: TF's ``max_norm``, as for ``GroupLookup``: the owner clips every row it gathers (in
+      fp32, before the fp16 wire) and steps its shard rows with the gradient through the clip; the
+      p2p form (``p2p_bind``) refuses a clipped forward.
   """
 
   def __init__(self, shards, coll, buckets=None, combiners='sum', wire_dtype=None,
                world_size=None, accums=None, hot_rows=False, dedup=False, moments=None, adam=None,
-               ftrl_slots=None, ftrl=None):
+               ftrl_slots=None, ftrl=None, max_norms=None):
+    from hybridbackend_amd.embedding.lookup import max_norm_list
     self.shards = list(shards)
+    # TF's max_norm per column (GroupLookup(max_norms=)): the owner clips its rows before the wire and
+    # differentiates through the clip on its shard rows (hbk_sharded_set_max_norms)
+    self.max_norms = max_norm_list(max_norms, len(self.shards))
     # Adagrad accumulators of the shards (same shapes), for backward(optimizer='adagrad')
     self.accums = list(accums) if accums is not None else None
     # the two-slot optimizers' slots of the shards (per column a pair of the shard's shape) and the
@@ -115,7 +122,7 @@ class ShardedGroupLookup:
     self._lib = _lib.lib()
     # owner-side gather: ids arrive bucketized, row = id // W (sharding.py:188-189)
     self._owner = GroupLookup(self.shards, None, 'sum', divisor=self.world_size,
-                              hot_rows=self.hot_rows)
+                              hot_rows=self.hot_rows, max_norms=[m or None for m in self.max_norms])
     self._owner_grad = GroupLookupGrad(self._owner)
 
   # ---- phase 1: bucketize + stable partition -------------------------------------
@@ -184,6 +191,8 @@ class ShardedGroupLookup:
     wire = _lib.HALF if self.wire_dtype == torch.float16 else _lib.FLOAT
     _lib.check(self._lib.hbk_sharded_create(
       C.byref(self._plan_handle), self.coll._handle, n, cols, wire))
+    if any(self.max_norms):   # (plan state: set again on every plan this object creates)
+      _lib.check(self._lib.hbk_sharded_set_max_norms(self._plan_handle, (C.c_float * n)(*self.max_norms)))
     for opt, pairs in ((self.adam, self.moments), (self.ftrl, self.ftrl_slots)):
       if pairs is not None:
         opt.set_sharded_slots(self._plan_handle, pairs)

@@ -33,10 +33,12 @@ class EmbeddingColumn:
   ``w e``, mean divides by the sum of the weights, sqrtn by the root of the sum of their squares; a
   sample whose divisor is 0 gives a zero row).  Nothing is pruned: unlike TF's
   ``safe_embedding_lookup_sparse``, ids with weight <= 0 stay in the sums, so callers pass positive
-  weights for that behaviour."""
+  weights for that behaviour.  ``max_norm``: ``embedding_column(max_norm=)`` -- every looked-up row is
+  clipped to an L2 norm of at most ``max_norm`` before its weight and the combine, and the gradient
+  goes through the clip (GroupLookup(max_norms=), ShardedGroupLookup(max_norms=)); None: no clip."""
 
   def __init__(self, key, num_buckets, dimension, combiner='mean', hot_rows='auto', dedup=False,
-               weight_feature_key=None):
+               weight_feature_key=None, max_norm=None):
     if num_buckets < 1 or dimension < 1:
       raise _lib.InvalidArgumentError(
         _lib.INVALID_ARGUMENT, 'num_buckets and dimension must be >= 1')
@@ -45,6 +47,8 @@ class EmbeddingColumn:
     self.hot_rows = 'auto' if hot_rows == 'auto' else bool(hot_rows)
     self.dedup = bool(dedup)
     self.weight_feature_key = weight_feature_key
+    from hybridbackend_amd.embedding.lookup import max_norm_list
+    self.max_norm = None if max_norm is None else max_norm_list([max_norm], 1)[0]
 
 
 class DenseFeatures:
@@ -126,7 +130,8 @@ class DenseFeatures:
       self._lookup = GroupLookup(pick(self._rep, self.weights),
                                  [self.columns[c].num_buckets for c in self._rep],
                                  [self.columns[c].combiner for c in self._rep],
-                                 hot_rows=[self.columns[c].hot_rows for c in self._rep])
+                                 hot_rows=[self.columns[c].hot_rows for c in self._rep],
+                                 max_norms=[self.columns[c].max_norm for c in self._rep])
       self._grad = GroupLookupGrad(
         self._lookup, pick(self._rep, self.accums) if self.accums is not None else None,
         **two_slot_kw(self._rep))
@@ -136,6 +141,7 @@ class DenseFeatures:
                                          combiners=[self.columns[c].combiner for c in self._shd],
                                          hot_rows=[self.columns[c].hot_rows for c in self._shd],
                                          dedup=[self.columns[c].dedup for c in self._shd],
+                                         max_norms=[self.columns[c].max_norm for c in self._shd],
                                          accums=(pick(self._shd, self.accums)
                                                  if self.accums is not None else None),
                                          **two_slot_kw(self._shd))

@@ -438,6 +438,73 @@ int hbk_group_lookup_bwd_ftrl(int32_t n_cols, const hbk_lookup_grad_column_t* co
                               float* const* accum, float* const* linear, const hbk_ftrl_t* ftrl,
                               float lr, void* workspace, size_t workspace_bytes, hbk_stream_t stream);
 
+/* max_norm: TF 1.15's embedding_lookup[_sparse](..., max_norm=) / embedding_column(max_norm=) -- every
+ * gathered row clipped to an L2 norm of at most c before its weight and the combine, and the gradient
+ * taken through the clip.  max_norms is a HOST float[n_cols]: 0 = the column is not clipped, c > 0
+ * finite = clipped; negative, NaN or infinite values are refused (HBK_INVALID_ARGUMENT) before any
+ * launch.  With every value 0 each entry is its unclipped twin, bit for bit.  Detected by the presence
+ * of the symbols; the column structs and the version are those of 0.2.0.
+ *
+ * Forward.  For each gathered fp32 row x of `dim` elements, each a separately rounded fp32 op:
+ *     s   = sum_k x_k * x_k
+ *     n   = s > 0 ? sqrtf(s) : 0
+ *     m   = fmaxf(n, c)
+ *     y_k = (x_k * c) / m            (every row, rows inside the ball included)
+ * y then replaces x in the weighted / unweighted sum, mean and sqrtn formulas above.  The order of s:
+ * the row is split over its lanes as the gather splits it (chunks of 4 floats when dim % 4 == 0 and the
+ * buffers are 16-byte aligned, else of 1 float; lanes per row L = the power of two >= chunks); every
+ * lane sums its chunk in element order (((x0 x0 + x1 x1) + x2 x2) + x3 x3), lanes without a chunk give
+ * 0, then the L partial sums meet in a butterfly: for o = 1, 2, 4, .. < L, p[i] = p[i] + p[i ^ o].
+ * The order depends on the row shape only, never on a reduce plan: results are bit-reproducible.
+ * Refused for a clipped column: HBK_LOOKUP_TABLE_HALF rows, out_slots.  HBK_LOOKUP_OUT_HALF clips in
+ * fp32, then rounds.  hot_rows is ignored for clipped columns.
+ * Consequence: with c a power of two and every row norm < c (zero rows included), y == x bit for bit. */
+int hbk_group_lookup_fwd_clipped(int32_t n_cols, const hbk_lookup_column_t* cols,
+                                 const float* max_norms, hbk_stream_t stream);
+/* Backward through the clip.  TF clips every DISTINCT row once, so the Jacobian applies to the row's
+ * summed gradient G (grad_rows of the unclipped backward: weights, combiner scale and the
+ * deterministic modes included), with x = the table row BEFORE this call's step:
+ *     if s > 0 and n >= c:    (the tie n == c included: TF's Maximum gradient uses >=)
+ *         d    = sum_k G_k * ((x_k * c) / m) / m
+ *         ds   = (-d * 0.5f) / n
+ *         g'_k = (G_k / m) * c + (2 * ds) * x_k
+ *     else:
+ *         g'_k = (G_k / m) * c
+ * Every term of d, G_k * ((x_k * c) / m) / m, is rounded on its own; the terms are then summed in the
+ * order of the forward's s (per lane in element order, then the butterfly), over the row shape of the
+ * step (the table, the accumulator or slots, grad_rows and the pitch decide 4-float chunks).  Every
+ * optimizer steps with g'.
+ * Two phases: the clipped columns' backward in its emit form (into grad_rows, or for step-only columns
+ * into workspace slices), then one clip pass per 64 columns that reads x, forms g' and steps the row
+ * (SGD / Adagrad with the fused step's arithmetic, Lazy Adam, FTRL).  In every form grad_rows of a
+ * clipped column end as g', the gradient its rows were stepped with (G for unclipped columns).
+ * Unclipped columns of hbk_group_lookup_bwd_apply_clipped keep the fused route of
+ * hbk_group_lookup_bwd_apply (their bits are that call's); in the Adam / FTRL entries every column
+ * runs the two phases as in the unclipped entries.  Refused before any launch: a clipped column whose
+ * table is named by another column (table or accum) of a stepping call (the clip must see the pre-step
+ * row; the emit form may repeat tables); a clipped column without a table.  Workspace: the matching
+ * query, made with the same pointers and max_norms. */
+size_t hbk_group_lookup_bwd_apply_clipped_workspace_bytes(int32_t n_cols,
+                                                          const hbk_lookup_grad_column_t* cols,
+                                                          const float* max_norms);
+int hbk_group_lookup_bwd_apply_clipped(int32_t n_cols, const hbk_lookup_grad_column_t* cols,
+                                       const float* max_norms, int32_t apply, float apply_lr,
+                                       void* workspace, size_t workspace_bytes, hbk_stream_t stream);
+size_t hbk_group_lookup_bwd_adam_clipped_workspace_bytes(int32_t n_cols,
+                                                         const hbk_lookup_grad_column_t* cols,
+                                                         const float* max_norms);
+int hbk_group_lookup_bwd_adam_clipped(int32_t n_cols, const hbk_lookup_grad_column_t* cols,
+                                      const float* max_norms, float* const* m, float* const* v,
+                                      const hbk_adam_t* adam, float lr, void* workspace,
+                                      size_t workspace_bytes, hbk_stream_t stream);
+size_t hbk_group_lookup_bwd_ftrl_clipped_workspace_bytes(int32_t n_cols,
+                                                         const hbk_lookup_grad_column_t* cols,
+                                                         const float* max_norms);
+int hbk_group_lookup_bwd_ftrl_clipped(int32_t n_cols, const hbk_lookup_grad_column_t* cols,
+                                      const float* max_norms, float* const* accum,
+                                      float* const* linear, const hbk_ftrl_t* ftrl, float lr,
+                                      void* workspace, size_t workspace_bytes, hbk_stream_t stream);
+
 /* R10 (sharded form)  d(stitch + combiner): the transpose of the requester-side
  *   `gather(embeddings, shard_index)` + combiner (hbtf/embedding/sharding.py:200; TF emits
  *   SparseSegment*Grad followed by an UnsortedSegmentSum over a permutation):
@@ -657,6 +724,14 @@ int hbk_sharded_create(hbk_sharded_t* plan, hbk_comm_t comm, int32_t n_cols,
  * the next forward reads them.  (The host side derives them from the distinct rows / ids of the
  * last backward: hybridbackend_amd/embedding/sharded.py.) */
 int hbk_sharded_set_hot_rows(hbk_sharded_t plan, const int32_t* hot_rows);
+/* max_norm of the plan's columns (host float[n_cols], the values of hbk_group_lookup_fwd_clipped; NULL: no
+ * column clipped); kept by the plan until set again.  As in the reference, the OWNER clips: its gather
+ * clips every row in fp32 before the wire (and the fp16 cast), the requester's stitch applies the
+ * weights; the owner-side backward runs the reduce in its emit form and the clip pass on its shard
+ * rows (every optimizer; unique_rows / grad_rows as in hbk_group_lookup_bwd_apply_clipped).  A
+ * p2p-bound plan (hbk_sharded_p2p_bind) refuses a forward with a clipped column: HBK_UNIMPLEMENTED
+ * before any exchange.  Values are refused as in the clipped entries. */
+int hbk_sharded_set_max_norms(hbk_sharded_t plan, const float* max_norms);
 int hbk_sharded_destroy(hbk_sharded_t plan);
 /* out_strides / grad_strides: NULL, or per column the row stride in floats of outs[c] /
  * grads[c] (0 = dim): the columns' blocks of one concatenated [segments, sum of dims] tensor. */
