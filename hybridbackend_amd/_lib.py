@@ -138,6 +138,7 @@ def _declare(l):
     'hbk_group_lookup_bwd_adam_clipped': (C.c_int, [i32, vp, vp, vp, vp, vp, C.c_float, vp, sz, vp]),
     'hbk_group_lookup_bwd_ftrl_clipped_workspace_bytes': (sz, [i32, vp, vp]),
     'hbk_group_lookup_bwd_ftrl_clipped': (C.c_int, [i32, vp, vp, vp, vp, vp, C.c_float, vp, sz, vp]),
+    'hbk_group_lookup_bwd_weights': (C.c_int, [i32, vp, vp, vp, vp]),
     'hbk_group_stitch_bwd': (C.c_int, [i32, vp, vp]),
     'hbk_cache_probe': (C.c_int, [vp, i64, i32, vp, i64, vp, vp, vp]),
     'hbk_cache_lookup_workspace_bytes': (sz, [i64]),
@@ -179,6 +180,7 @@ def _declare(l):
     'hbk_sharded_lookup_bwd_adam': (C.c_int, [vp, vp, vp, vp, C.c_float, vp, vp, vp, vp]),
     'hbk_sharded_set_ftrl_slots': (C.c_int, [vp, vp, vp]),
     'hbk_sharded_lookup_bwd_ftrl': (C.c_int, [vp, vp, vp, vp, C.c_float, vp, vp, vp, vp]),
+    'hbk_sharded_lookup_bwd_weights': (C.c_int, [vp, vp, vp, vp, vp]),
   }
   for name, (res, args) in protos.items():
     fn = getattr(l, name)   # AttributeError here = header and library out of sync

@@ -166,3 +166,73 @@ def weight_ptrs(sp_weights, ids):
         '(one per id)')
     ptrs.append(w.data_ptr())
   return ptrs
+
+
+def weight_grad_request(weight_grads, sp_weights, n):
+  """What a backward's ``weight_grads`` asks for, checked against ``sp_weights`` before anything touches
+  the device: None when nothing is wanted (None / False), else a list of n entries -- True (allocate
+  the column's gradient), a preallocated fp32 ``[n_ids]`` tensor, or None (unweighted column, or not
+  wanted).  ``weight_grads=True`` asks for every weighted column; a list names the columns itself
+  (None / False: not wanted, True: allocate, a tensor: write there).  Asking for the gradient of a
+  column without weights is refused."""
+  from hybridbackend_amd import _lib   # pylint: disable=import-outside-toplevel
+  if weight_grads is None or weight_grads is False:
+    return None
+  weighted = [w is not None for w in sp_weights] if sp_weights is not None else []
+  if sp_weights is not None and len(weighted) != n:
+    raise _lib.InvalidArgumentError(
+      _lib.INVALID_ARGUMENT, f'expected {n} sp_weights entries (None for an unweighted column), '
+      f'got {len(weighted)}')
+  if weight_grads is True:
+    if not any(weighted):
+      raise _lib.InvalidArgumentError(
+        _lib.INVALID_ARGUMENT, 'weight_grads=True needs sp_weights: no column of this call is weighted')
+    return [True if w else None for w in weighted]
+  try:
+    want = list(weight_grads)
+  except TypeError:
+    raise _lib.InvalidArgumentError(
+      _lib.INVALID_ARGUMENT, 'weight_grads must be True, False or one entry per column (None, True or '
+      f'an fp32 [n_ids] tensor), got {weight_grads!r}') from None
+  if len(want) != n:
+    raise _lib.InvalidArgumentError(
+      _lib.INVALID_ARGUMENT, f'expected {n} weight_grads entries, got {len(want)}')
+  out = []
+  for c, x in enumerate(want):
+    if x is None or x is False:
+      out.append(None)
+      continue
+    if not (weighted and weighted[c]):
+      raise _lib.InvalidArgumentError(
+        _lib.INVALID_ARGUMENT, f'weight_grads: column {c} has no sp_weights, so it has no weight gradient')
+    if x is not True and not isinstance(x, torch.Tensor):
+      raise _lib.InvalidArgumentError(
+        _lib.INVALID_ARGUMENT, f'weight_grads[{c}] must be None, True or an fp32 [n_ids] tensor, got {x!r}')
+    out.append(x)
+  if not any(x is not None for x in out):
+    return None
+  return out
+
+
+def weight_grad_outputs(request, ids, device):
+  """The fp32 ``[n_ids]`` output tensors of a checked request (weight_grad_request): allocated where the
+  request says True -- one allocation for all of them -- and checked where it names a tensor."""
+  from hybridbackend_amd import _lib   # pylint: disable=import-outside-toplevel
+  sizes = [int(ids[c].shape[0]) if x is True else 0 for c, x in enumerate(request)]
+  pad = [(k + 3) // 4 * 4 for k in sizes]
+  flat = torch.empty(sum(pad), dtype=torch.float32, device=device) if sum(pad) else None
+  outs, at = [], 0
+  for c, x in enumerate(request):
+    if x is None:
+      outs.append(None)
+    elif x is True:
+      outs.append(flat[at:at + sizes[c]])
+      at += pad[c]
+    else:
+      _lib.require_device_tensor(x, 'weight_grads')
+      if x.dtype is not torch.float32 or x.dim() != 1 or x.shape[0] != ids[c].shape[0]:
+        raise _lib.InvalidArgumentError(
+          _lib.INVALID_ARGUMENT, f'weight_grads[{c}] must be an fp32 vector of {ids[c].shape[0]} elements '
+          '(one per id)')
+      outs.append(x)
+  return outs

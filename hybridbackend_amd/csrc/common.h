@@ -160,6 +160,7 @@ struct Options {
   int bwd_trace = 0;           // HBK_BWD_TRACE: the composition of every launch group of a backward call on stderr
   int bwd_large_first = 0;     // HBK_BWD_LARGE_FIRST: the launch groups of the large columns (histogram / scan / scatter chain) are enqueued before the one-launch groups
   int bwd_rowsort_ratio = 8;   // HBK_BWD_ROWSORT_RATIO: row-sorted buckets for columns of rows <= ratio x ids (four times that for dim <= 32; 0: never)
+  int bwd_weights_lds = 1;     // HBK_BWD_WEIGHTS_LDS: the weight gradient parks d_j of segments of up to 8 x LPR ids in LDS (0: every segment longer than LPR ids takes the second sweep over its ids in memory; A/B)
   int fwd_d16 = 1;             // HBK_FWD_D16: one-id-per-segment columns of 16 floats with int64 ids take the gather's instantiation with those as constants (0: the general one; A/B)
   int fwd_interleave = 2;      // HBK_FWD_INTERLEAVE: lookup tiles of one dense output block ordered row tile first (lookup_fwd.hip)
   int fwd_hot_rows = 0;        // HBK_FWD_HOT: forward of wide one-id-per-sample columns: 1 = 256-segment tiles with
@@ -277,6 +278,36 @@ int ftrl_check(const hbk_ftrl_t* ftrl, float lr, const char* who);
 // every host check hbk_group_lookup_bwd_apply makes of its columns, without launching anything
 // (lookup_bwd.hip): HBK_OK or HBK_INVALID_ARGUMENT
 int bwd_check(int32_t n_cols, const hbk_lookup_grad_column_t* cols, int32_t apply, float apply_lr);
+
+// One column of the weight gradient (lookup_bwd_weights.hip): what hbk_group_lookup_bwd_weights reads of
+// an hbk_lookup_grad_column_t, plus the table forms only the sharded step's requester needs -- the
+// received rows as a segmented table (run_start / run_base as in hbk_lookup_column_t) of fp32 or fp16
+// rows.  grad_weights == NULL: the column is skipped.
+struct WeightGradColumn {
+  const float* table;
+  int64_t rows;
+  int32_t dim;
+  int32_t table_pitch;   // floats between rows; 0 = dim
+  int32_t ids_dtype;
+  const void* ids;
+  int64_t n_ids;
+  const int32_t* row_splits;
+  int64_t n_segments;
+  int64_t bucket;
+  int32_t divisor;
+  int32_t combiner;
+  const float* grad_out;
+  int32_t grad_stride;
+  const float* id_weights;
+  float max_norm;        // 0: not clipped
+  float* grad_weights;   // device [n_ids]
+  const int64_t* run_start;
+  const int64_t* run_base;
+  int32_t n_runs;
+  int32_t table_half;    // != 0: the table's rows are fp16 (needs n_runs > 0)
+};
+// checks every column (HBK_INVALID_ARGUMENT before any launch), then one launch per kind of column
+int group_lookup_bwd_weights(int32_t n_cols, const WeightGradColumn* cols, hipStream_t stream);
 
 // compute units of the current device (cached; lookup_bwd.hip)
 int device_cus();

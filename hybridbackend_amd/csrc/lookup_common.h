@@ -89,6 +89,41 @@ inline bool make_rowshape(int32_t dim, uintptr_t align_bits, RowShape* s) {
   return true;
 }
 
+// fp16 rows on one side of a gather (the wire format of the sharded step's embedding exchange,
+// hbtf/distribute/nccl/nccl_alltoallv.cc:56-88 + hbtf/common/cast.cu.cc:84-285, fused into the
+// kernels on either side of it): HALF = 1 the OUTPUT rows are half (owner gather -> reply
+// buffer, fp32 -> fp16 round to nearest even as the reference's cast), HALF = 2 the TABLE rows
+// are half (stitch over the received buffer; sums stay fp32).  Offsets and strides count elements.
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+
+template <typename V, int HALF>
+__device__ inline V load_row_chunk(const float* table, uint64_t off) {
+  if (HALF != 2) return *reinterpret_cast<const V*>(table + off);
+  const _Float16* t = reinterpret_cast<const _Float16*>(table) + off;
+  if (sizeof(V) == 16) {
+    const f16x4 h = *reinterpret_cast<const f16x4*>(t);
+    f32x4 v = {(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
+    return *reinterpret_cast<V*>(&v);
+  }
+  float f = (float)*t;
+  return *reinterpret_cast<V*>(&f);
+}
+
+// max_norm (the clipped instantiations, hbk_group_lookup_fwd_clipped): y = (x * c) / max(|x|, c) of a
+// row x held by the LPR lanes of its group.  |x|^2 is summed per lane over its chunk in element order,
+// then by a butterfly over the group's lanes (xor 1, 2, 4, ..; both lanes of a pair add the same two
+// values, so every lane ends with the same bits).  Lanes without a row chunk hold zeros.
+__device__ inline float chunk_sq(float a) { return a * a; }
+__device__ inline float chunk_sq(f32x4 a) { return ((a.x * a.x + a.y * a.y) + a.z * a.z) + a.w * a.w; }
+
+template <typename V>
+__device__ inline V clip_row(V x, float c, int lpr_log2) {
+  float s = chunk_sq(x);
+  for (int o = 1; o < (1 << lpr_log2); o <<= 1) s = s + __shfl_xor(s, o, kWave);
+  const float n = s > 0.0f ? sqrtf(s) : 0.0f;
+  return (x * c) / fmaxf(n, c);
+}
+
 }  // namespace hbk
 
 #endif  // HBK_CSRC_LOOKUP_COMMON_H_

@@ -554,6 +554,8 @@ struct hbk_sharded {
   std::vector<int64_t> fwd_own_id_off;   // [W][N] where run (q, c) of the forward sits in recv_ids
   hipEvent_t ev[4][4];                   // [stage][group]: packed, ids in, gathered, rows in
   bool have_step;
+  bool rows_live = false;   // the forward's received rows are still in recv_rows_p (hbk_sharded_lookup_bwd_weights):
+                            // from the end of a stitched forward until the next _begin or row backward
   float host_us[3];     // host time of the last forward: enqueue 1-2, wait for the sizes, enqueue the rest
   // device buffers owned by the plan
   // ids_buf = ids coming in (the ids going out live in the step's PartSet), rows_buf = [rows
@@ -1161,6 +1163,7 @@ extern "C" int hbk_sharded_lookup_fwd_begin(hbk_sharded_t p, const int64_t* cons
   HBK_REQUIRE(p != nullptr, "sharded_lookup_fwd: plan is NULL");
   HBK_REQUIRE(ids && n_ids, "sharded_lookup_fwd: NULL argument array");
   p->fwd_open = false;
+  p->rows_live = false;   // (the exchange buffers are about to be laid out again)
   hipStream_t stream = as_stream(stream_);
   const int N = p->N, W = p->W;
   p->n_ids.assign(n_ids, n_ids + N);
@@ -1649,6 +1652,7 @@ extern "C" int hbk_sharded_lookup_fwd_end(hbk_sharded_t p, float* const* outs,
     if (rc != HBK_OK) return rc;
   }
   p->have_step = true;
+  p->rows_live = !p2p;
   const double total = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() -
                                                                 p->fin_t0).count();
   p->host_us[0] = p->fin_us[0];
@@ -1752,6 +1756,75 @@ extern "C" int hbk_sharded_prefetch(hbk_sharded_t p, const int64_t* const* ids,
   return HBK_OK;
 }
 
+// The gradient of the per-id weights, on the requester (the weights never cross the wire): e_j is the
+// RECEIVED row the forward's stitch multiplied -- clipped by its owner, rounded by an fp16 wire -- found
+// through the stitch's composed index (duplicate positions of a deduplicated column share one received
+// row).  The received rows stay in the plan's exchange buffer from the forward's stitch until the next
+// hbk_sharded_lookup_fwd_begin lays the buffers out again or the row backward writes the gradient rows
+// over them (a prefetch only partitions ids: it does not touch them), so the call is legal exactly in
+// between -- before the row backward of the same step -- and refused otherwise; nothing is copied and a
+// plan that never asks pays nothing.  Local work only: no exchange.
+extern "C" int hbk_sharded_lookup_bwd_weights(hbk_sharded_t p, const float* const* grads,
+                                              const int32_t* grad_strides, float* const* grad_weights,
+                                              hbk_stream_t stream_) {
+  using namespace hbk;
+  HBK_REQUIRE(p != nullptr, "sharded_lookup_bwd_weights: plan is NULL");
+  // (the same on every rank: the bind is collective)
+  if (p->p2p_bound) {
+    return fail(HBK_UNIMPLEMENTED, "sharded_lookup_bwd_weights: the p2p form (hbk_sharded_p2p_bind) has no "
+                "stitch and keeps no received rows");
+  }
+  HBK_REQUIRE(grads != nullptr && grad_weights != nullptr, "sharded_lookup_bwd_weights: NULL argument array");
+  const int N = p->N, W = p->W;
+  bool any = false;
+  for (int c = 0; c < N; ++c) any = any || grad_weights[c] != nullptr;
+  if (!any) return HBK_OK;
+  HBK_REQUIRE(p->have_step, "sharded_lookup_bwd_weights: no forward step to differentiate");
+  for (int c = 0; c < N; ++c) {
+    HBK_REQUIRE(grad_weights[c] == nullptr || (c < (int)p->id_weights.size() && p->id_weights[c] != nullptr),
+                "sharded_lookup_bwd_weights: column %d: a weight gradient is wanted but the last forward "
+                "(hbk_sharded_lookup_fwd_weighted) gave the column no id_weights", c);
+  }
+  HBK_REQUIRE(p->rows_live, "sharded_lookup_bwd_weights: the forward's received rows are gone: call this "
+              "after the forward and BEFORE the row backward (hbk_sharded_lookup_bwd*) of the same step");
+  const bool half = p->fused_half;
+  const int64_t* d_start = reinterpret_cast<const int64_t*>(p->runs_dev.ptr);
+  const int64_t* d_base = d_start + (size_t)N * W;
+  std::vector<int64_t> ioff(N + 1, 0);
+  for (int c = 0; c < N; ++c) ioff[c + 1] = ioff[c] + p->n_ids[c];
+  std::vector<WeightGradColumn> v;
+  for (const Group& gr : p->groups) {
+    for (int cc = gr.c0; cc < gr.c1; ++cc) {
+      if (grad_weights[cc] == nullptr) continue;
+      WeightGradColumn h;
+      memset(&h, 0, sizeof(h));
+      // the column as the forward's stitch saw it (stage D of hbk_sharded_lookup_fwd_end)
+      h.table = half ? reinterpret_cast<const float*>(reinterpret_cast<const uint16_t*>(p->recv_rows_p) +
+                                                      gr.row_recv)
+                     : p->recv_rows_p + gr.row_recv;
+      h.table_half = half ? 1 : 0;
+      h.rows = p->n_sent[cc];
+      h.dim = p->cols[cc].dim;
+      h.ids_dtype = HBK_INT32;
+      h.ids = reinterpret_cast<const int32_t*>(p->ps[p->cur].shard_index.ptr) + ioff[cc];
+      h.n_ids = p->n_ids[cc];
+      h.row_splits = p->row_splits[cc];
+      h.n_segments = p->n_seg[cc];
+      h.divisor = 1;
+      h.combiner = p->cols[cc].combiner;
+      h.grad_out = grads[cc];
+      h.grad_stride = grad_strides ? grad_strides[cc] : 0;
+      h.id_weights = p->id_weights[cc];
+      h.grad_weights = grad_weights[cc];
+      h.run_start = d_start + (size_t)cc * W;
+      h.run_base = d_base + (size_t)cc * W;
+      h.n_runs = W;
+      v.push_back(h);
+    }
+  }
+  return group_lookup_bwd_weights((int32_t)v.size(), v.data(), as_stream(stream_));
+}
+
 extern "C" int hbk_sharded_lookup_bwd(hbk_sharded_t p, const float* const* grads,
                                       const int32_t* grad_strides, float apply_lr,
                                       int64_t* const* unique_rows, float* const* grad_rows,
@@ -1826,6 +1899,7 @@ static int sharded_bwd(hbk_sharded_t p, const float* const* grads, const int32_t
   char* const tmp = reinterpret_cast<char*>(p->dedup_tmp.ptr);
   int32_t* const tmp_nu = p->any_dedup ? reinterpret_cast<int32_t*>(tmp + tmp_bytes - (size_t)N * 4 - 8)
                                        : nullptr;
+  p->rows_live = false;   // from here on B1 writes the gradient rows over the forward's received rows
   for (int g = 0; g < G; ++g) {
     const Group& gr = p->groups[g];
     const int ng = gr.c1 - gr.c0;

@@ -541,14 +541,19 @@ class GroupLookupGrad:
     return True
 
   def __call__(self, ids, grads, row_splits=None, apply_lr=0.0, optimizer='sgd', emit=True,
-               grad_block=None, sp_weights=None, finish=True):
+               grad_block=None, sp_weights=None, finish=True, weight_grads=False):
     """Returns per column ``(unique_rows int64[n_ids], grad_rows f32[n_ids, dim],
     n_unique int32[1])``; only the first ``n_unique`` rows are meaningful, in unspecified
     order (device-side count: no host sync here).  The result buffers belong to this object
     and are reused by the next call with the same id counts.  ``emit=False`` (with ``apply_lr``):
     step only -- the rows are stepped, no IndexedSlices are written; only ``n_unique`` of each
     returned triple is meaningful.  ``sp_weights``: the forward's per-id weights (per column None
-    or fp32 ``[n_ids]``); no gradient is produced for them.  ``optimizer='adam'`` (with ``apply_lr``
+    or fp32 ``[n_ids]``).  ``weight_grads``: True, or per column None / True / a preallocated fp32
+    ``[n_ids]`` tensor -- the call then returns ``(triples, weight_gradients)``, the second a list with
+    one fp32 ``[n_ids]`` tensor per asked (weighted) column and None for the others: dL/dw of every id
+    (include/hbk.h, hbk_group_lookup_bwd_weights), computed before the optimizer step of the same call,
+    so from the rows as the forward read them.  Absent or False: the return value and the work are
+    exactly those without it.  ``optimizer='adam'`` (with ``apply_lr``
     and ``moments``): the Lazy Adam step (:class:`LazyAdam`); ``finish=False`` leaves the beta powers
     for a later call of the same optimizer step to advance.  ``optimizer='ftrl'`` (with ``apply_lr``
     and ``ftrl_slots``): the FTRL-Proximal step (:class:`Ftrl`)."""
@@ -556,6 +561,7 @@ class GroupLookupGrad:
     if not emit and apply_lr == 0.0:
       raise _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT, 'emit=False needs apply_lr != 0')
     n = len(self.lookup)
+    wg_request = _marshal.weight_grad_request(weight_grads, sp_weights, n)
     if row_splits is None:
       row_splits = [None] * n
     dev = self.lookup.tables[0].device if n else None
@@ -664,10 +670,17 @@ class GroupLookupGrad:
     if optimizer == 'adagrad' and apply_lr != 0.0 and self.accums is None:
       raise _lib.InvalidArgumentError(
         _lib.INVALID_ARGUMENT, "optimizer='adagrad' needs GroupLookupGrad(lookup, accums=...)")
+    self._wg = None
+    if wg_request is not None:
+      outs = _marshal.weight_grad_outputs(wg_request, ids, dev)
+      self._wg = (outs, _lib.ptr_array([0 if o is None else o.data_ptr() for o in outs]))
+      self._weight_grads(n, dev)     # before the step: the rows as the forward read them
     self._step(n, optimizer, two_slot, apply_lr, finish, self._ws, dev)
     if self.lookup._auto_hot:
       self.lookup.note_backward(self._nu, [int(i.numel()) for i in ids])
     self._bound_call = (emit, [int(i.numel()) for i in ids])
+    if self._wg is not None:
+      return list(self._views), list(self._wg[0])
     return list(self._views)
 
   def _slot_form(self):
@@ -681,6 +694,11 @@ class GroupLookupGrad:
     return cols
 
   _NEEDS = 'GroupLookupGrad(lookup, {kw}=[({s0}, {s1}), ...])'
+
+  def _weight_grads(self, n, dev):
+    """The weight gradients of the bound step into the bound outputs (self._wg): one foreign call."""
+    _lib.check(self._lib.hbk_group_lookup_bwd_weights(n, self._cols, self.lookup.max_norms_c, self._wg[1],
+                                                      _lib.current_stream(dev)))
 
   def _step(self, n, optimizer, two_slot, apply_lr, finish, ws, dev):
     clip = self.lookup.max_norms_c
@@ -701,7 +719,9 @@ class GroupLookupGrad:
     """The backward of the LAST call again, on the same tensors (a training loop over resident
     buffers that are refilled in place; bench.py): the descriptors and the workspace of that call are
     still right, so this is ONE foreign call -- no validation, no marshalling (the counterpart of
-    ``GroupLookup.launch``).  Same emit mode as that call; returns the same result views."""
+    ``GroupLookup.launch``).  Same emit mode as that call; returns the same result views.  A last call
+    with ``weight_grads`` is repeated with them (one more foreign call, before the step, into the same
+    output tensors) and returns ``(triples, weight_gradients)`` as it did."""
     bound = getattr(self, '_bound_call', None)
     if bound is None:
       raise _lib.HbkError(_lib.INTERNAL, 'launch() needs a call that bound the tensors first')
@@ -713,7 +733,12 @@ class GroupLookupGrad:
         _lib.INVALID_ARGUMENT, "optimizer='adagrad' needs GroupLookupGrad(lookup, accums=...)")
     two_slot = _opt.two_slot_class(optimizer, self, self._NEEDS)
     dev = self.lookup.tables[0].device if len(self.lookup) else None
+    wg = getattr(self, '_wg', None)
+    if wg is not None:
+      self._weight_grads(len(self.lookup), dev)
     self._step(len(self.lookup), optimizer, two_slot, apply_lr, finish, self._ws_bound, dev)
     if self.lookup._auto_hot:
       self.lookup.note_backward(self._nu, n_ids)
+    if wg is not None:
+      return list(self._views), list(wg[0])
     return list(self._views)

@@ -29,6 +29,7 @@ import threading
 import torch
 
 from hybridbackend_amd import _lib
+from hybridbackend_amd import _marshal
 from hybridbackend_amd.distribute import partition as _partition
 from hybridbackend_amd.embedding.lookup import GroupLookup
 from hybridbackend_amd.embedding.lookup import GroupLookupGrad
@@ -86,9 +87,12 @@ class ShardedGroupLookup:
 
   def __init__(self, shards, coll, buckets=None, combiners='sum', wire_dtype=None,
                world_size=None, accums=None, hot_rows=False, dedup=False, moments=None, adam=None,
-               ftrl_slots=None, ftrl=None, max_norms=None):
+               ftrl_slots=None, ftrl=None, max_norms=None, weight_grads=False):
     from hybridbackend_amd.embedding.lookup import max_norm_list
     self.shards = list(shards)
+    # backward() also returns the gradient of the last forward's sp_weights (its own weight_grads
+    # argument overrides this default)
+    self.weight_grads = weight_grads
     # TF's max_norm per column (GroupLookup(max_norms=)): the owner clips its rows before the wire and
     # differentiates through the clip on its shard rows (hbk_sharded_set_max_norms)
     self.max_norms = max_norm_list(max_norms, len(self.shards))
@@ -352,6 +356,7 @@ class ShardedGroupLookup:
       _lib.check(self._lib.hbk_sharded_set_hot_rows(
         self._plan(), (C.c_int32 * len(self.hot_rows))(*[int(h) for h in self.hot_rows])))
     if bound.weights is None:
+      self._keep_weights = None
       _lib.check(self._lib.hbk_sharded_lookup_fwd(
         self._plan(), *bound.args, _lib.current_stream(self.device)))
     else:
@@ -376,6 +381,7 @@ class ShardedGroupLookup:
     """First half of a bound step (``hbk_sharded_lookup_fwd_begin``): partition (or its prefetched
     result), the one host wait, id exchange, owner-side gather.  ``launch_end`` finishes it."""
     _refuse_weights(bound, 'launch_begin / launch_end')
+    self._keep_weights = None     # (an unweighted step: nothing of an earlier step's weights is kept)
     self._keep = bound.keep
     self._last_shapes = bound.shapes
     a = bound.args
@@ -496,7 +502,8 @@ class ShardedGroupLookup:
   def owner_bwd(self, st, recv_grads, apply_lr=0.0):
     return self._owner_grad(st.recv_ids, recv_grads, None, apply_lr=apply_lr)
 
-  def backward(self, grads, apply_lr=0.0, outs=None, optimizer='sgd', emit=True, finish=True):
+  def backward(self, grads, apply_lr=0.0, outs=None, optimizer='sgd', emit=True, finish=True,
+               weight_grads=None):
     """Backward of the LAST forward step (hbk_sharded_lookup_bwd).  grads[c]: gradient of
     column c's output [segments, dim].  Returns per column the IndexedSlices of the LOCAL
     shard ``(unique_rows, grad_rows, n_unique)``; with ``apply_lr`` the SGD update is applied
@@ -507,10 +514,19 @@ class ShardedGroupLookup:
     ``optimizer='adam'`` (with ``apply_lr`` and ``moments``): the Lazy Adam step on the shards
     (hbk_sharded_lookup_bwd_adam); ``finish=False`` leaves the beta powers to a later call.
     ``optimizer='ftrl'`` (with ``apply_lr`` and ``ftrl_slots``): the FTRL-Proximal step on the shards
-    (hbk_sharded_lookup_bwd_ftrl)."""
+    (hbk_sharded_lookup_bwd_ftrl).
+    ``weight_grads`` (default: the constructor's): True, or per column None / True / a preallocated fp32
+    ``[n_ids]`` tensor -- the call returns ``(slices, weight_gradients)``, the second a list with dL/dw of
+    every id of the asked columns (those the last forward weighted) and None for the others.  Computed
+    on this rank from the rows it received (clipped by their owners, rounded by an fp16 wire: what the
+    forward multiplied), before the row backward overwrites them (hbk_sharded_lookup_bwd_weights)."""
     if not emit and apply_lr == 0.0:
       raise _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT, 'emit=False needs apply_lr != 0')
     n = len(self.shards)
+    if weight_grads is None:
+      weight_grads = self.weight_grads
+    kept_w = getattr(self, '_keep_weights', None)
+    wg_request = _marshal.weight_grad_request(weight_grads, kept_w, n)
     plan = self._plan()
     two_slot = _opt.two_slot_class(optimizer, self,
                                    'ShardedGroupLookup(..., {kw}=[({s0}, {s1}), ...])')
@@ -557,6 +573,15 @@ class ShardedGroupLookup:
     if optimizer == 'adagrad' and apply_lr != 0.0 and self.accums is None:
       raise _lib.InvalidArgumentError(
         _lib.INVALID_ARGUMENT, "optimizer='adagrad' needs ShardedGroupLookup(..., accums=...)")
+    wg_outs = None
+    if wg_request is not None:
+      # (sized by the weights: one per id of the last forward)
+      wg_outs = _marshal.weight_grad_outputs(wg_request, kept_w, self.device)
+      self._keep_wg = wg_outs
+      _lib.check(self._lib.hbk_sharded_lookup_bwd_weights(
+        plan, _lib.ptr_array([g.data_ptr() for g in grads]), strides,
+        _lib.ptr_array([0 if o is None else o.data_ptr() for o in wg_outs]),
+        _lib.current_stream(self.device)))
     if two_slot is not None and apply_lr != 0.0:
       getattr(self, two_slot.name).sharded_step(
         plan, _lib.ptr_array([g.data_ptr() for g in grads]), strides, apply_lr,
@@ -578,6 +603,8 @@ class ShardedGroupLookup:
       st[0].copy_(nu_call if nu_call is not None else self._nu_step, non_blocking=True)
       st[1].record()
       st[2], st[3] = owned, True
+    if wg_outs is not None:
+      return res, wg_outs
     return res
 
 

@@ -223,7 +223,7 @@ class DenseFeatures:
       ids, _, _ = self._split(features)
       self._sharded.prefetch([ids[c] for c in self._shd], ids_ready)
 
-  def backward(self, grad, apply_lr=0.0, optimizer='sgd', emit=True):
+  def backward(self, grad, apply_lr=0.0, optimizer='sgd', emit=True, weight_grads=False):
     """grad: ``[batch, sum of dims]`` gradient of the last forward's output.  Returns per column
     the ``IndexedSlices`` ``(unique_rows, grad_rows, n_unique)`` of this rank's rows (local row
     numbers for sharded tables); with ``apply_lr`` the sparse optimizer step (``'sgd'``, or
@@ -236,7 +236,10 @@ class DenseFeatures:
     write no IndexedSlices (step only; their entries are ``(None, None, n_unique)``).
     ``optimizer='adam'`` (layer built with ``optimizer='adam'``): the Lazy Adam step; the beta powers
     advance once per backward that steps any table.  ``optimizer='ftrl'`` (layer built with
-    ``optimizer='ftrl'``): the FTRL-Proximal step."""
+    ``optimizer='ftrl'``): the FTRL-Proximal step.
+    ``weight_grads=True``: returns ``(slices, {weight_feature_key: tensor})`` -- the gradient of every
+    weighted column's per-id weights (fp32 ``[n_ids]``; replicated and sharded tables alike, taken at the
+    rows as the forward read them), an empty dict for a layer without weighted columns."""
     _opt.two_slot_class(optimizer, self, "DenseFeatures(..., optimizer='{name}')")
     ids, splits, ws = self._last
     if grad.dim() != 2 or grad.shape[1] != self.width or grad.dtype != torch.float32:
@@ -251,6 +254,24 @@ class DenseFeatures:
       grad = padded
     pick = lambda idx, xs: [xs[c] for c in idx]   # noqa: E731
     res = [None] * len(self.columns)
+    wgrads = {}
+
+    def want(idx):
+      # the weighted columns among `idx` (False: none, and the callee is called as without the flag)
+      if not weight_grads or ws is None:
+        return False
+      w = [True if ws[c] is not None else None for c in idx]
+      return w if any(w) else False
+
+    def take(idx, r):
+      # a callee that was asked returns (slices, weight gradients)
+      if not isinstance(r, tuple):
+        return r
+      for c, g in zip(idx, r[1]):
+        if g is not None:
+          wgrads[self.columns[c].weight_feature_key] = g
+      return r[0]
+
     def col_grads():
       return [grad[:, self.offsets[c]:self.offsets[c] + self.columns[c].dimension]
               for c in range(len(self.columns))]
@@ -267,7 +288,8 @@ class DenseFeatures:
                      apply_lr=rep_lr, optimizer=optimizer, emit=emit or rep_lr == 0.0,
                      grad_block=grad_block,
                      sp_weights=None if ws is None else pick(self._rep, ws),
-                     finish=not (self._shd and apply_lr != 0.0))
+                     finish=not (self._shd and apply_lr != 0.0), weight_grads=want(self._rep))
+      r = take(self._rep, r)
       for k, c in enumerate(self._rep):
         res[c] = r[k]
     if self._shd:
@@ -275,9 +297,12 @@ class DenseFeatures:
                for c in self._shd]
       views = [v.contiguous() if c in self._staged else v for c, v in zip(self._shd, views)]
       r = self._sharded.backward(views, apply_lr=apply_lr, optimizer=optimizer,
-                                 emit=emit)
+                                 emit=emit, weight_grads=want(self._shd))
+      r = take(self._shd, r)
       for k, c in enumerate(self._shd):
         res[c] = r[k]
+    if weight_grads:
+      return res, wgrads
     return res
 
   # ---- checkpoints (hybridbackend/tensorflow/training/saver.py:97-185) ----------------------------

@@ -88,7 +88,7 @@ int hbk_tables_free(void* slab);
  * 1: columns whose row range fits the row-sorted jobs take those jobs' in-order form -- a row's pairs ordered by gradient row inside the
  * job, output ranges in bucket order, no bucket split over workgroups -- and the other columns the sort of 2; 2: a stable sort of the
  * batch's (row, gradient row) pairs and a sequential walk for every column; the reproducibility mode, TF_DETERMINISTIC_OPS' analogue),
- * bwd_pairs_packed, bwd_seg_inline, bwd_scale_fused, bwd_simple (0: the general instantiation of the grouping kernels for every launch group), fwd_d16 (0: the general gather for columns of 16 floats too), bwd_scatter_staged, bwd_rowsort_pos, bwd_rowsort_ratio (round 5: x 4 for dim <= 32),
+ * bwd_pairs_packed, bwd_seg_inline, bwd_scale_fused, bwd_simple (0: the general instantiation of the grouping kernels for every launch group), fwd_d16 (0: the general gather for columns of 16 floats too), bwd_weights_lds (0: the weight gradient's segments of more than LPR ids all take the second sweep in memory), bwd_scatter_staged, bwd_rowsort_pos, bwd_rowsort_ratio (round 5: x 4 for dim <= 32),
  * bwd_streams (launch groups of > 64 columns rotate over this many library streams; 0: the caller's), bwd_large_first,
  * bwd_trace (the launch groups of every backward call on stderr), bwd_lds_pad (a probe), sharded_p2p,
  * sharded_p2p_test_refuse (test hook: the rank whose hbk_sharded_p2p_bind behaves as if a peer's memory could not be mapped),
@@ -358,7 +358,8 @@ typedef struct {
    * gradient term of id j is  t_j = (grad_out[s] / W_s) * w_j  (mean),  (grad_out[s] / sqrtf(Q_s))
    * * w_j  (sqrtn),  grad_out[s] * w_j  (sum), each a separately rounded fp32 op in that order;
    * the ids of a zero-divisor segment get t_j = 0.  grad_rows[u] sums the t_j of row u (in id
-   * order under HBK_GRAD_DETERMINISTIC).  No gradient for the weights themselves.  The call writes
+   * order under HBK_GRAD_DETERMINISTIC).  The gradient of the weights themselves is a call of its own,
+   * hbk_group_lookup_bwd_weights (below), made before a stepping call.  The call writes
    * every t_j to an [n_ids, dim] fp32 buffer inside the workspace and reduces that as a column of
    * one id per segment with the SUM combiner.  Refused with segmented inputs (n_runs > 0). */
   const float* id_weights;
@@ -437,6 +438,40 @@ size_t hbk_group_lookup_bwd_ftrl_workspace_bytes(int32_t n_cols,
 int hbk_group_lookup_bwd_ftrl(int32_t n_cols, const hbk_lookup_grad_column_t* cols,
                               float* const* accum, float* const* linear, const hbk_ftrl_t* ftrl,
                               float lr, void* workspace, size_t workspace_bytes, hbk_stream_t stream);
+
+/* The gradient of the per-id weights (tf.nn.embedding_lookup_sparse is differentiable in
+ * sp_weights.values).  grad_weights[c] is a device fp32 [n_ids of column c], or NULL = not wanted;
+ * max_norms is NULL or a HOST float[n_cols] as in the clipped entries (0 = not clipped).  Reads
+ * cols[c].{table, rows, dim, table_pitch, ids, ids_dtype, n_ids, row_splits, n_segments, bucket, divisor,
+ * combiner, grad_out, grad_stride, id_weights} as hbk_group_lookup_bwd does and writes grad_weights only: no
+ * workspace, no atomics, one launch per kind of column (ragged or not, 16-byte or 4-byte chunks).  Per id
+ * j of segment s, with e_j = table[row(j)] after the column's clip (hbk_group_lookup_fwd_clipped's y), w_j
+ * its weight and G_s = grad_out[s]:
+ *     d_j = sum_k G_sk * e_jk      A_s = sum_i w_i * d_i      W_s = sum_i w_i      Q_s = sum_i w_i * w_i
+ *     sum:    dw_j = d_j
+ *     mean:   dw_j = (d_j - A_s / W_s) / W_s
+ *     sqrtn:  r = sqrtf(Q_s);  dw_j = d_j / r - (w_j * A_s) / (Q_s * r)
+ * each a separately rounded fp32 op in that order.  A_s, W_s and Q_s run over the segment's ids that map
+ * inside [0, rows), in id order (A = A + w_i * d_i, ...), as the forward sums its divisor.  The order of
+ * d_j: the row is split over its lanes as the clip's s is (chunks of 4 floats when dim % 4 == 0 and table,
+ * grad_out, the pitch and the stride are 16-byte aligned, else of 1 float; L = the power of two >= chunks);
+ * a lane sums its chunk in element order (((G0 e0 + G1 e1) + G2 e2) + G3 e3), lanes without a chunk give 0,
+ * and the L partial sums meet in the butterfly p[i] = p[i] + p[i ^ o], o = 1, 2, 4, .. < L.  Nothing
+ * depends on scheduling: two runs give the same bits.  dw_j = 0 for an id that maps outside [0, rows), for
+ * the ids of a segment whose divisor (W_s, sqrtf(Q_s)) is 0 and for ids in no segment; every position
+ * [0, n_ids) is written.  row_splits = NULL (one id per segment) is legal: A = w d, W = w, Q = w w.  A
+ * lane group owns a segment whatever its length (no chunked path: a segment of 10^5 ids is walked by one
+ * group); a segment of more than L and at most 8 L ids parks d_j, w_j and the validity in LDS until A_s is
+ * known, a longer one writes d_j to grad_weights first and fixes it up in a second sweep over its own ids
+ * (the same arithmetic and bits either way; option bwd_weights_lds = 0: the second sweep for both).
+ * The rows are read as they are when the call runs: call it BEFORE a stepping backward of the same step,
+ * as the clip's gradient reads the rows before the step.  Refused (HBK_INVALID_ARGUMENT) before any
+ * launch: segmented inputs (n_runs > 0), a wanted gradient on a column without id_weights, a max_norm
+ * that is negative, NaN or infinite, a row the gather cannot take (dim > 256, or > 64 as 4-byte chunks).
+ * Detected by the presence of the symbol; the structs and the version are those of 0.2.0. */
+int hbk_group_lookup_bwd_weights(int32_t n_cols, const hbk_lookup_grad_column_t* cols,
+                                 const float* max_norms, float* const* grad_weights,
+                                 hbk_stream_t stream);
 
 /* max_norm: TF 1.15's embedding_lookup[_sparse](..., max_norm=) / embedding_column(max_norm=) -- every
  * gathered row clipped to an L2 norm of at most c before its weight and the combine, and the gradient
@@ -809,6 +844,21 @@ int hbk_sharded_p2p_unbind(hbk_sharded_t plan);
  * partition and the size exchange, [1] waiting for the sizes (the device, not host work),
  * [2] enqueueing everything else */
 int hbk_sharded_last_host_us(hbk_sharded_t plan, float* out3);
+/* The gradient of the per-id weights of the last hbk_sharded_lookup_fwd_weighted, computed on the requester
+ * (the weights never cross the wire) by hbk_group_lookup_bwd_weights' kernel over the rows this rank
+ * RECEIVED: e_j is exactly what the forward's stitch multiplied -- clipped by its owner, rounded to fp16 on
+ * an fp16 wire -- found through the stitch's index, so duplicate positions of a deduplicated column share
+ * one received row.  grad_weights[c]: device fp32 [n_ids of column c] or NULL = not wanted; grads /
+ * grad_strides as in hbk_sharded_lookup_bwd.  The received rows live in the plan's exchange buffer until
+ * the next forward (_begin) lays it out again or the row backward writes the gradient rows over them; a
+ * prefetch does not touch them.  So the call is made after the forward and BEFORE the row backward of the
+ * same step; anywhere else it is refused (HBK_INVALID_ARGUMENT), nothing is copied and nothing is kept
+ * for a plan that never asks (no opt-in switch is needed).  Local work: no exchange, ranks need not agree on
+ * which columns they ask for.  Refused before any launch: a p2p-bound plan (HBK_UNIMPLEMENTED on every
+ * rank: no stitch), a wanted column the last forward gave no weights, no forward before it. */
+int hbk_sharded_lookup_bwd_weights(hbk_sharded_t plan, const float* const* grads,
+                                   const int32_t* grad_strides, float* const* grad_weights,
+                                   hbk_stream_t stream);
 int hbk_sharded_lookup_bwd(hbk_sharded_t plan, const float* const* grads,
                            const int32_t* grad_strides, float apply_lr,
                            int64_t* const* unique_rows, float* const* grad_rows,
