@@ -68,6 +68,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <map>
 #include <type_traits>
 #include <mutex>
@@ -3251,30 +3252,22 @@ __global__ __launch_bounds__(kBlock) void bwd_weight_terms_kernel(const TArgs a)
 inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 bool any_weighted(int32_t n_cols, const hbk_lookup_grad_column_t* cols) {
-  for (int32_t c = 0; c < n_cols; ++c) {
-    if (cols[c].id_weights != nullptr) return true;
-  }
-  return false;
+  return std::any_of(cols, cols + n_cols,
+                     [](const hbk_lookup_grad_column_t& h) { return h.id_weights != nullptr; });
 }
 
-// workspace bytes of the term buffers: 16-byte aligned each, + 16 to align the first one
-size_t weight_terms_bytes(int32_t n_cols, const hbk_lookup_grad_column_t* cols) {
-  size_t b = 0;
-  for (int32_t c = 0; c < n_cols; ++c) {
-    const hbk_lookup_grad_column_t& h = cols[c];
-    if (h.id_weights != nullptr && h.n_ids > 0) b += align16((size_t)h.n_ids * h.dim * 4);
-  }
-  return b == 0 ? 0 : b + 16;
-}
-
-// the columns as the stages behind the term pass see them (terms == NULL: the workspace query)
-void weighted_as_sum(int32_t n_cols, const hbk_lookup_grad_column_t* cols, char* terms,
-                     std::vector<hbk_lookup_grad_column_t>* out) {
+// the columns as the stages behind the term pass see them (terms == NULL: the workspace query).
+// Returns the workspace bytes of the term buffers: one per weighted column with ids, 16-byte aligned
+// each, + 16 to align the first one
+size_t weighted_as_sum(int32_t n_cols, const hbk_lookup_grad_column_t* cols, char* terms,
+                       std::vector<hbk_lookup_grad_column_t>* out) {
   out->assign(cols, cols + n_cols);
-  size_t off = 0;
+  size_t off = 0, bytes = 0;
   for (hbk_lookup_grad_column_t& h : *out) {
     if (h.id_weights == nullptr) continue;
-    if (h.n_segments == 0) h.n_ids = 0;   // ids in no segment: nothing to reduce
+    const size_t term_bytes = h.n_ids > 0 ? align16((size_t)h.n_ids * h.dim * 4) : 0;
+    bytes += term_bytes;
+    if (h.n_segments == 0) h.n_ids = 0;   // ids in no segment: nothing to reduce (the buffer stays unused)
     h.row_splits = nullptr;
     h.n_segments = h.n_ids;
     h.combiner = HBK_COMBINER_SUM;
@@ -3283,55 +3276,10 @@ void weighted_as_sum(int32_t n_cols, const hbk_lookup_grad_column_t* cols, char*
     h.id_weights = nullptr;
     if (h.n_ids > 0) {
       if (terms != nullptr) h.grad_out = reinterpret_cast<const float*>(terms + off);
-      off += align16((size_t)h.n_ids * h.dim * 4);
+      off += term_bytes;
     }
   }
-}
-
-int launch_weight_terms(int32_t n_cols, const hbk_lookup_grad_column_t* cols,
-                        const std::vector<hbk_lookup_grad_column_t>& as_sum, hipStream_t stream) {
-  int32_t c0 = 0;
-  while (c0 < n_cols) {
-    TArgs args;
-    int32_t k = 0;
-    int64_t tiles = 0;
-    while (c0 < n_cols && k < kMaxTermCols) {
-      const int32_t ci = c0++;
-      const hbk_lookup_grad_column_t& h = cols[ci];
-      if (h.id_weights == nullptr || h.n_ids == 0 || h.n_segments == 0) continue;
-      TCol& d = args.col[k];
-      d.grad_out = h.grad_out;
-      d.ids = h.ids;
-      d.splits = h.row_splits;
-      d.weights = h.id_weights;
-      d.terms = const_cast<float*>(as_sum[ci].grad_out);
-      d.map = make_idmap(h.bucket, h.divisor, h.rows);
-      d.n_seg = h.n_segments;
-      d.grad_stride = h.grad_stride > 0 ? h.grad_stride : h.dim;
-      d.dim = h.dim;
-      RowShape shape;
-      HBK_REQUIRE(make_rowshape(h.dim,
-                                (uintptr_t)h.grad_out | (uintptr_t)d.terms |
-                                    ((uintptr_t)(uint32_t)d.grad_stride * 4),
-                                &shape),
-                  "group_lookup_bwd: dim %d needs more than 64 lanes per row", h.dim);
-      d.chunks = shape.chunks;
-      d.lpr_log2 = shape.lpr_log2;
-      d.vec4 = shape.vec4;
-      d.ids64 = h.ids_dtype == HBK_INT64;
-      d.combiner = (uint8_t)h.combiner;
-      const int64_t per_block = kWavesPerBlock * kTermIters * (int64_t)(kWave >> d.lpr_log2);
-      args.tile0[k] = (int32_t)tiles;
-      tiles += (h.n_segments + per_block - 1) / per_block;
-      HBK_REQUIRE(tiles < (1ll << 31), "group_lookup_bwd: grid too large");
-      ++k;
-    }
-    if (k == 0) continue;
-    args.n_cols = k;
-    hipLaunchKernelGGL(bwd_weight_terms_kernel, dim3((unsigned)tiles), dim3(kBlock), 0, stream, args);
-    HBK_HIP_OK(hipGetLastError());
-  }
-  return HBK_OK;
+  return bytes == 0 ? 0 : bytes + 16;
 }
 
 // ---- host-side planning ------------------------------------------------------------------------
@@ -3464,33 +3412,71 @@ ColPlan plan_of(int64_t n_ids, int32_t dim, int64_t rows, bool ragged, bool det 
   return p;
 }
 
-// row-sorted columns keep a pair as ONE word (GCol.packed)
-inline bool pairs_packed(const ColPlan& p) { return p.rowsort && options().bwd_pairs_packed != 0; }
+// Bucket kinds x row widths.  kind = 2 * bucket kind + (16-byte chunks ? 0 : 1): the columns of a
+// launch group are sorted by it, so every kernel instantiation runs on ONE range of job slots
+enum BucketKind {
+  kDenseLean = 0,     // row-range buckets, few repeated rows (4b)
+  kDenseSorted = 1,   // row-range buckets with the sorted walk
+  kHashed = 2,
+  kHashedWide = 3,    // hashed with the wide sorted walk (an optimizer step, >= 16 lanes per row, one
+                      // id per sample: bucket_reduce)
+  kRowSorted = 4,     // row-range buckets reduced by the row-sorted jobs (4c)
+  kBucketKinds = 5
+};
+constexpr int kKinds = 2 * kBucketKinds;
+static_assert(kKinds == sizeof(GArgs::xcd_start) / sizeof(GArgs::xcd_start[0]), "one xcd_start row per kind");
+inline int kind_of(int bucket_kind, bool vec4) { return 2 * bucket_kind + (vec4 ? 0 : 1); }
+inline int bucket_kind_of(int kind) { return kind >> 1; }
+// job slots per workgroup of a kind's reduce launch
+inline int64_t slots_per_block(int kind) {
+  return bucket_kind_of(kind) == kHashed || bucket_kind_of(kind) == kHashedWide ? kTeams : 1;
+}
 
-size_t col_workspace(const hbk_lookup_grad_column_t& h, bool det = false) {
-  if (h.n_ids <= 0) return 0;
-  const ColPlan p = plan_of(h.n_ids, h.dim, h.rows, h.row_splits != nullptr, det);
-  size_t b = align8(((size_t)p.tiles * p.n_buckets) * 4);   // hist
-  b += align8(((size_t)p.n_buckets + 1) * 4);          // bstart
-  b += (size_t)h.n_ids * 8;                                // pair_row
-  if (!pairs_packed(p)) b += align8((size_t)h.n_ids * 4);  // pair_seg
-  if (h.row_splits != nullptr && options().bwd_seg_inline == 0) {
-    b += align8((size_t)h.n_ids * 4);                      // seg_of
-  }
-  if (h.row_splits != nullptr && h.combiner != HBK_COMBINER_SUM) {
-    b += align8((size_t)h.n_segments * h.dim * 4) + 16;   // the segments' scaled gradient rows
-  }
-  b += ((size_t)p.n_buckets + p.e_max) * sizeof(int4);     // desc (carved from the call's head)
-  b += 256;                                                // the claim counter's own line
-  b += align8((size_t)p.e_max * 8) + 8;                    // work, n_extra
-  b += align8(((size_t)p.n_buckets) * 4);                 // pcount
-  b += (size_t)h.n_ids * 8;                                // part_rows
-  b += align8((size_t)h.n_ids * h.dim * 4) + 16;           // part_vals (16-byte aligned)
-  if (h.grad_rows == nullptr) {                            // step only: scratch for the rows of the
-    b += (size_t)h.n_ids * 8;                              // few jobs that must emit (several
-    b += align8((size_t)h.n_ids * h.dim * 4) + 16;         // chunks, split buckets)
-  }
-  return b;
+// Where a column's buffers lie: offsets from the start of the column's slice of the call's buffer
+// region (kNoBuf: the column has no such buffer), the bytes of that slice, of the column's job
+// descriptors (carved from the call's head) and of everything the column adds to the workspace.
+// The float buffers (scaled, part_vals, step_vals) are aligned to 16 bytes where they are carved:
+// their sizes carry the 16 bytes of slack.
+constexpr size_t kNoBuf = ~(size_t)0;
+struct ColLayout {
+  size_t hist, bstart, pair_row, pair_seg, seg_of, scaled, work, n_extra, pcount, part_rows, part_vals;
+  size_t step_rows, step_vals;   // step only: scratch for the rows of the few jobs that must emit
+                                 // (several chunks, split buckets)
+  size_t bytes, desc_bytes, total;
+};
+
+ColLayout col_layout(const hbk_lookup_grad_column_t& h, const ColPlan& p) {
+  ColLayout l = {};
+  size_t at = 0;
+  auto take = [&](bool present, size_t bytes) {
+    const size_t here = present ? at : kNoBuf;
+    if (present) at += bytes;
+    return here;
+  };
+  const bool ragged = h.row_splits != nullptr;
+  const size_t n = (size_t)h.n_ids;
+  const size_t row_bytes = align8(n * h.dim * 4) + 16;
+  l.hist = take(true, align8(((size_t)p.tiles * p.n_buckets) * 4));
+  l.bstart = take(true, align8(((size_t)p.n_buckets + 1) * 4));
+  l.pair_row = take(true, n * 8);
+  // row-sorted columns keep a pair as ONE word (GCol.packed)
+  l.pair_seg = take(!(p.rowsort && options().bwd_pairs_packed != 0), align8(n * 4));
+  // ragged columns: the grouping kernels find the segment of an id themselves (0a); option
+  // bwd_seg_inline = 0 keeps the seg-of array and the launch that writes it
+  l.seg_of = take(ragged && options().bwd_seg_inline == 0, align8(n * 4));
+  // the segments' scaled gradient rows
+  l.scaled = take(ragged && h.combiner != HBK_COMBINER_SUM, align8((size_t)h.n_segments * h.dim * 4) + 16);
+  l.work = take(true, align8((size_t)p.e_max * 8));
+  l.n_extra = take(true, 8);
+  l.pcount = take(true, align8(((size_t)p.n_buckets) * 4));
+  l.part_rows = take(true, n * 8);
+  l.part_vals = take(true, row_bytes);
+  l.step_rows = take(h.grad_rows == nullptr, n * 8);
+  l.step_vals = take(h.grad_rows == nullptr, row_bytes);
+  l.bytes = at;
+  l.desc_bytes = ((size_t)p.n_buckets + p.e_max) * sizeof(int4);
+  l.total = l.bytes + l.desc_bytes + 256;   // (the claim counter's own line)
+  return l;
 }
 
 // deterministic mode, option value 1: the columns whose buckets fit the row-sorted jobs take their
@@ -3502,27 +3488,39 @@ inline int det_mode(const hbk_lookup_grad_column_t& h) {
   if (opt != 0) return opt;
   return (h.flags & HBK_GRAD_DETERMINISTIC) != 0 ? 1 : 0;
 }
-inline bool det_rowsort(const hbk_lookup_grad_column_t& h) {
-  if (det_mode(h) != 1 || h.n_ids <= 0) return false;
-  return plan_of(h.n_ids, h.dim, h.rows, h.row_splits != nullptr, true).rowsort;
-}
-// the columns of a call by the form they take: `fast` the in-order row-sorted jobs, `slow` the sort,
-// `plain` the default forms (empty columns of a deterministic call ride with the sort, which clears
-// their counts)
-inline void det_split(int32_t n_cols, const hbk_lookup_grad_column_t* cols,
-                      std::vector<hbk_lookup_grad_column_t>* fast,
-                      std::vector<hbk_lookup_grad_column_t>* slow,
-                      std::vector<hbk_lookup_grad_column_t>* plain) {
-  for (int32_t c = 0; c < n_cols; ++c) {
-    (det_mode(cols[c]) == 0 ? plain : det_rowsort(cols[c]) ? fast : slow)->push_back(cols[c]);
+
+// The form a column takes: kFormTerms the weight term pass (the call then runs again over the terms),
+// kFormSort the sort of lookup_bwd_det.h, kFormInOrder the in-order row-sorted jobs, kFormPlain the
+// default forms (empty columns of a deterministic call ride with the sort, which clears their counts)
+enum ColForm { kFormTerms, kFormSort, kFormInOrder, kFormPlain };
+
+// One column of a call, made once: the only caller of plan_of() and col_layout()
+struct ColInfo {
+  int form;
+  ColPlan p;        // kFormInOrder, kFormPlain (with ids)
+  ColLayout lay;
+  bool onepass;     // small enough for the one-launch grouping (bwd_group_kernel)
+  RowShape shape;   // check_layouts(): of the planned forms, or of the term pass
+  int kind;         // check_layouts(): kind_of() of the planned forms
+};
+
+// form, plan and layout: all that the size queries know of a column
+ColInfo col_info(const hbk_lookup_grad_column_t& h) {
+  ColInfo ci = {};
+  const int mode = det_mode(h);
+  ci.form = h.id_weights != nullptr ? kFormTerms : mode != 0 ? kFormSort : kFormPlain;
+  if (h.n_ids <= 0 || ci.form == kFormTerms || (mode != 0 && mode != 1)) return ci;
+  ci.p = plan_of(h.n_ids, h.dim, h.rows, h.row_splits != nullptr, mode == 1);
+  if (mode == 1) {
+    if (!ci.p.rowsort) return ci;
+    ci.form = kFormInOrder;
   }
+  ci.lay = col_layout(h, ci.p);
+  ci.onepass = options().bwd_onepass != 0 && ci.p.n_buckets <= kGroupMaxBuckets && ci.p.tiles <= 64;
+  return ci;
 }
-inline bool any_deterministic(int32_t n_cols, const hbk_lookup_grad_column_t* cols) {
-  if (options().bwd_deterministic != 0) return true;
-  for (int32_t c = 0; c < n_cols; ++c) {
-    if ((cols[c].flags & HBK_GRAD_DETERMINISTIC) != 0) return true;
-  }
-  return false;
+inline bool has_form(const std::vector<ColInfo>& info, int form) {
+  return std::any_of(info.begin(), info.end(), [form](const ColInfo& ci) { return ci.form == form; });
 }
 
 // ---- host side of the deterministic backward (lookup_bwd_det.h) -----------------------------------
@@ -3567,42 +3565,56 @@ DetLayout det_layout(int32_t n_cols, const hbk_lookup_grad_column_t* cols) {
   return l;
 }
 
-// workspace of a deterministic call: the sort path's arrays (`slow`, laid out by `l`), then the
-// row-sorted jobs, then the default forms
-size_t det_workspace_bytes(const DetLayout& l, const std::vector<hbk_lookup_grad_column_t>& fast,
-                           const std::vector<hbk_lookup_grad_column_t>& plain) {
-  size_t total = l.total == 0 ? 0 : l.total + 256;
-  size_t planned = 0;
-  for (const hbk_lookup_grad_column_t& h : fast) planned += col_workspace(h, true);
-  total += planned == 0 ? 0 : planned + 256;
-  planned = 0;
-  for (const hbk_lookup_grad_column_t& h : plain) planned += col_workspace(h);
-  return total + (planned == 0 ? 0 : planned + 256);
+// workspace of a call without weighted columns: the sort path's arrays (the `sorted` columns, laid
+// out by `dl`), then the slice of the in-order row-sorted jobs, then that of the default forms.  Each
+// slice has 256 bytes of slack: its head (counters, descriptors) is aligned inside.
+struct CallLayout {
+  std::vector<hbk_lookup_grad_column_t> sorted;
+  DetLayout dl;
+  size_t in_order, plain, total;   // where the planned forms' slices begin, and the call's bytes
+};
+CallLayout call_layout(int32_t n_cols, const hbk_lookup_grad_column_t* cols, const std::vector<ColInfo>& info) {
+  CallLayout l;
+  size_t in_order = 0, plain = 0;
+  for (int32_t c = 0; c < n_cols; ++c) {
+    const ColInfo& ci = info[(size_t)c];
+    if (ci.form == kFormSort) l.sorted.push_back(cols[c]);
+    (ci.form == kFormInOrder ? in_order : plain) += ci.lay.total;
+  }
+  l.dl = det_layout((int32_t)l.sorted.size(), l.sorted.data());
+  l.in_order = l.dl.total == 0 ? 0 : l.dl.total + 256;
+  l.plain = l.in_order + (in_order == 0 ? 0 : in_order + 256);
+  l.total = l.plain + (plain == 0 ? 0 : plain + 256);
+  return l;
 }
 
 // Every per-column check of the forms behind the common loop (bwd_planned, det_backward, the weight
 // term pass), made before the call's first launch: a refusal from a later form would leave the
-// columns of the forms that already ran stepped, and a retry would step them twice.
-int check_layouts(int32_t n_cols, const hbk_lookup_grad_column_t* cols, float apply_lr) {
+// columns of the forms that already ran stepped, and a retry would step them twice.  *info: the
+// columns' records, which those forms then read.
+int check_layouts(int32_t n_cols, const hbk_lookup_grad_column_t* cols, float apply_lr,
+                  std::vector<ColInfo>* info) {
+  info->assign((size_t)n_cols, ColInfo{});
   int64_t group_ids = 0;   // ids and live columns of det_backward's current launch group
   int group_cols = 0;
   for (int32_t c = 0; c < n_cols; ++c) {
     const hbk_lookup_grad_column_t& h = cols[c];
+    ColInfo& ci = (*info)[(size_t)c];
+    ci = col_info(h);
     if (h.n_ids <= 0) continue;
     HBK_REQUIRE(h.grad_stride == 0 || h.grad_stride >= h.dim,
                 "group_lookup_bwd: column %d: grad_stride %d is smaller than dim %d", c,
                 h.grad_stride, h.dim);
     const uintptr_t stride_bits = (uintptr_t)(uint32_t)h.grad_stride * 4;
-    RowShape shape;
-    if (h.id_weights != nullptr) {
-      // the term pass reads grad_out; the stages behind it see 16-byte aligned terms (and check them
-      // themselves before they step anything)
-      HBK_REQUIRE(h.n_segments == 0 || make_rowshape(h.dim, (uintptr_t)h.grad_out | stride_bits, &shape),
+    if (ci.form == kFormTerms) {
+      // the term pass reads grad_out and writes 16-byte aligned terms; the stages behind it see those
+      // terms (and check them themselves before they step anything)
+      HBK_REQUIRE(h.n_segments == 0 || make_rowshape(h.dim, (uintptr_t)h.grad_out | stride_bits, &ci.shape),
                   "group_lookup_bwd: column %d: dim %d needs more than 64 lanes per row (at most 256 "
                   "with 16-byte aligned grad_out / grad_stride, 64 otherwise)", c, h.dim);
       continue;
     }
-    if (det_mode(h) != 0 && !det_rowsort(h)) {   // the sort path (det_backward)
+    if (ci.form == kFormSort) {   // (det_backward)
       HBK_REQUIRE(h.dim <= kDetLanes * kDetMaxE, "group_lookup_bwd: column %d: dim %d > %d on the "
                   "deterministic sort path", c, h.dim, kDetLanes * kDetMaxE);
       HBK_REQUIRE(h.rows < (1ll << 40), "group_lookup_bwd: column %d: more than 2^40 rows on the "
@@ -3620,9 +3632,57 @@ int check_layouts(int32_t n_cols, const hbk_lookup_grad_column_t* cols, float ap
                               (uintptr_t)h.grad_out | (uintptr_t)h.grad_rows | stride_bits |
                                   (apply_lr != 0.0f ? (uintptr_t)h.table | (uintptr_t)h.accum |
                                                           ((uintptr_t)(uint32_t)h.table_pitch * 4) : 0),
-                              &shape),
+                              &ci.shape),
                 "group_lookup_bwd: column %d: dim %d needs more than 64 lanes per row (at most 256 "
                 "with 16-byte aligned buffers and strides, 64 otherwise)", c, h.dim);
+    const bool wide = apply_lr != 0.0f && ci.shape.lpr_log2 >= 4 &&
+                      (options().bwd_wide == 2 || (options().bwd_wide == 1 && h.row_splits == nullptr));
+    ci.kind = kind_of(ci.p.rowsort ? kRowSorted
+                      : ci.p.dense_mul != 0 ? (ci.p.dense_sort ? kDenseSorted : kDenseLean)
+                      : wide ? kHashedWide : kHashed,
+                      ci.shape.vec4 != 0);
+  }
+  return HBK_OK;
+}
+
+// the weighted columns' gradient terms per id (`as_sum`: where they go); shapes from check_layouts()
+int launch_weight_terms(int32_t n_cols, const hbk_lookup_grad_column_t* cols, const std::vector<ColInfo>& info,
+                        const std::vector<hbk_lookup_grad_column_t>& as_sum, hipStream_t stream) {
+  int32_t c0 = 0;
+  while (c0 < n_cols) {
+    TArgs args;
+    int32_t k = 0;
+    int64_t tiles = 0;
+    while (c0 < n_cols && k < kMaxTermCols) {
+      const int32_t ci = c0++;
+      const hbk_lookup_grad_column_t& h = cols[ci];
+      if (h.id_weights == nullptr || h.n_ids == 0 || h.n_segments == 0) continue;
+      const RowShape& shape = info[(size_t)ci].shape;
+      TCol& d = args.col[k];
+      d.grad_out = h.grad_out;
+      d.ids = h.ids;
+      d.splits = h.row_splits;
+      d.weights = h.id_weights;
+      d.terms = const_cast<float*>(as_sum[ci].grad_out);
+      d.map = make_idmap(h.bucket, h.divisor, h.rows);
+      d.n_seg = h.n_segments;
+      d.grad_stride = h.grad_stride > 0 ? h.grad_stride : h.dim;
+      d.dim = h.dim;
+      d.chunks = shape.chunks;
+      d.lpr_log2 = shape.lpr_log2;
+      d.vec4 = shape.vec4;
+      d.ids64 = h.ids_dtype == HBK_INT64;
+      d.combiner = (uint8_t)h.combiner;
+      const int64_t per_block = kWavesPerBlock * kTermIters * (int64_t)(kWave >> d.lpr_log2);
+      args.tile0[k] = (int32_t)tiles;
+      tiles += (h.n_segments + per_block - 1) / per_block;
+      HBK_REQUIRE(tiles < (1ll << 31), "group_lookup_bwd: grid too large");
+      ++k;
+    }
+    if (k == 0) continue;
+    args.n_cols = k;
+    hipLaunchKernelGGL(bwd_weight_terms_kernel, dim3((unsigned)tiles), dim3(kBlock), 0, stream, args);
+    HBK_HIP_OK(hipGetLastError());
   }
   return HBK_OK;
 }
@@ -3654,9 +3714,6 @@ int det_backward(int32_t n_cols, const hbk_lookup_grad_column_t* cols, const Det
     while (c0 < n_cols && k < kMaxCols) {
       const hbk_lookup_grad_column_t& h = cols[c0++];
       if (h.n_ids <= 0) continue;
-      HBK_REQUIRE(h.dim <= kDetLanes * kDetMaxE, "deterministic backward: dim %d > %d", h.dim,
-                  kDetLanes * kDetMaxE);
-      HBK_REQUIRE(h.rows < (1ll << 40), "deterministic backward: more than 2^40 rows");
       DCol& d = a.col[k];
       d.ids = h.ids;
       d.grad = h.grad_out;
@@ -3691,7 +3748,6 @@ int det_backward(int32_t n_cols, const hbk_lookup_grad_column_t* cols, const Det
       ++k;
     }
     if (k == 0) continue;
-    HBK_REQUIRE(total < (1ll << 31), "deterministic backward: more than 2^31-1 ids in one launch group");
     for (int q = k; q <= kMaxCols; ++q) a.base[q] = (int32_t)total;
     a.n_cols = k;
     a.row_bits = bits_for(max_rows);        // the all-ones row field (> every row) marks "no row"
@@ -3773,18 +3829,12 @@ extern "C" size_t hbk_group_lookup_bwd_workspace_bytes(int32_t n_cols,
   if (n_cols <= 0 || cols == nullptr) return 0;
   if (hbk::any_weighted(n_cols, cols)) {   // the term buffers, then the columns behind them
     std::vector<hbk_lookup_grad_column_t> as_sum;
-    hbk::weighted_as_sum(n_cols, cols, nullptr, &as_sum);
-    return hbk::weight_terms_bytes(n_cols, cols) +
-           hbk_group_lookup_bwd_workspace_bytes(n_cols, as_sum.data());
+    const size_t tb = hbk::weighted_as_sum(n_cols, cols, nullptr, &as_sum);
+    return tb + hbk_group_lookup_bwd_workspace_bytes(n_cols, as_sum.data());
   }
-  if (hbk::any_deterministic(n_cols, cols)) {
-    std::vector<hbk_lookup_grad_column_t> fast, slow, plain;
-    hbk::det_split(n_cols, cols, &fast, &slow, &plain);
-    return hbk::det_workspace_bytes(hbk::det_layout((int32_t)slow.size(), slow.data()), fast, plain);
-  }
-  size_t total = 0;
-  for (int32_t c = 0; c < n_cols; ++c) total += hbk::col_workspace(cols[c]);
-  return total == 0 ? 0 : total + 256;  // the head (counters, descriptors) is aligned inside
+  std::vector<hbk::ColInfo> info;
+  for (int32_t c = 0; c < n_cols; ++c) info.push_back(hbk::col_info(cols[c]));
+  return hbk::call_layout(n_cols, cols, info).total;
 }
 
 extern "C" int hbk_group_lookup_bwd(int32_t n_cols, const hbk_lookup_grad_column_t* cols,
@@ -3853,15 +3903,11 @@ BwdHelpers* bwd_helpers(hipStream_t caller) {
   }
   return h;
 }
-}  // namespace
-}  // namespace hbk
 
-static int bwd_planned(int32_t n_cols, const hbk_lookup_grad_column_t* cols, int32_t apply,
-                       float apply_lr, void* workspace, hipStream_t stream, bool det);
-
-namespace hbk {
-// every host check of hbk_group_lookup_bwd_apply's arguments but the workspace (common.h)
-int bwd_check(int32_t n_cols, const hbk_lookup_grad_column_t* cols, int32_t apply, float apply_lr) {
+// every host check of hbk_group_lookup_bwd_apply's arguments but the workspace; *info: the columns'
+// records (check_layouts)
+int check_columns(int32_t n_cols, const hbk_lookup_grad_column_t* cols, int32_t apply, float apply_lr,
+                  std::vector<ColInfo>* info) {
   HBK_REQUIRE(apply == HBK_APPLY_SGD || apply == HBK_APPLY_ADAGRAD,
               "group_lookup_bwd: apply must be HBK_APPLY_SGD or HBK_APPLY_ADAGRAD, got %d", apply);
   HBK_REQUIRE(n_cols >= 0, "group_lookup_bwd: n_cols must be >= 0, got %d", n_cols);
@@ -3908,139 +3954,431 @@ int bwd_check(int32_t n_cols, const hbk_lookup_grad_column_t* cols, int32_t appl
                 "group_lookup_bwd: column %d: id_weights cannot be combined with segmented inputs "
                 "(run_*: the owner-side reduce is never weighted)", c);
   }
-  return check_layouts(n_cols, cols, apply_lr);
-}
-}  // namespace hbk
-
-extern "C" int hbk_group_lookup_bwd_apply(int32_t n_cols, const hbk_lookup_grad_column_t* cols,
-                                          int32_t apply, float apply_lr, void* workspace,
-                                          size_t workspace_bytes, hbk_stream_t stream_) {
-  using namespace hbk;
-  hipStream_t stream = as_stream(stream_);
-  {
-    const int rc = bwd_check(n_cols, cols, apply, apply_lr);
-    if (rc != HBK_OK) return rc;
-  }
-  if (n_cols == 0) return HBK_OK;
-  // a deterministic call's split and the sort path's layout (two size queries of the sort / scan
-  // primitives), made once and handed down
-  const bool weighted = any_weighted(n_cols, cols);
-  const bool det = !weighted && any_deterministic(n_cols, cols);
-  std::vector<hbk_lookup_grad_column_t> fast, slow, plain;
-  DetLayout dl = {};
-  if (det) {
-    det_split(n_cols, cols, &fast, &slow, &plain);
-    dl = det_layout((int32_t)slow.size(), slow.data());
-    HBK_REQUIRE(dl.total == 0 || dl.temp_bytes > 256, "deterministic backward: the sort / scan "
-                "primitives cannot be sized on this device");
-  }
-  const size_t need = det ? det_workspace_bytes(dl, fast, plain)
-                          : hbk_group_lookup_bwd_workspace_bytes(n_cols, cols);
-  HBK_REQUIRE(need == 0 || (workspace != nullptr && workspace_bytes >= need),
-              "group_lookup_bwd: workspace too small: need %zu bytes, got %zu", need,
-              workspace_bytes);
-  HBK_REQUIRE(((uintptr_t)workspace & 7) == 0,
-              "group_lookup_bwd: workspace must be 8-byte aligned");
-  {
-    const int rc = sync_check("group_lookup_bwd", stream);
-    if (rc != HBK_OK) return rc;
-  }
-  // weighted columns: their gradient terms per id into the head of the workspace, then the call
-  // over the columns as SUM columns of one id per segment
-  if (weighted) {
-    const size_t tb = weight_terms_bytes(n_cols, cols);
-    char* terms = reinterpret_cast<char*>(align16(reinterpret_cast<uintptr_t>(workspace)));
-    std::vector<hbk_lookup_grad_column_t> as_sum;
-    weighted_as_sum(n_cols, cols, tb == 0 ? nullptr : terms, &as_sum);
-    const int rc = launch_weight_terms(n_cols, cols, as_sum, stream);
-    if (rc != HBK_OK) return rc;
-    return hbk_group_lookup_bwd_apply(n_cols, as_sum.data(), apply, apply_lr,
-                                      tb == 0 ? workspace : reinterpret_cast<char*>(workspace) + tb,
-                                      workspace_bytes - tb, stream_);
-  }
-  // option bwd_deterministic: the in-order forms -- row-sorted jobs where they fit (1), the sort + walk
-  // of lookup_bwd_det.h for the other columns (and for all of them under 2)
-  if (det) {
-    char* at = reinterpret_cast<char*>(workspace);
-    if (!slow.empty()) {
-      const int rc = det_backward((int32_t)slow.size(), slow.data(), dl, apply, apply_lr, at, stream);
-      if (rc != HBK_OK) return rc;
-      at += dl.total == 0 ? 0 : dl.total + 256;
-    }
-    if (!fast.empty()) {
-      const int rc = bwd_planned((int32_t)fast.size(), fast.data(), apply, apply_lr, at, stream, true);
-      if (rc != HBK_OK) return rc;
-      size_t planned = 0;
-      for (const hbk_lookup_grad_column_t& h : fast) planned += col_workspace(h, true);
-      at += planned == 0 ? 0 : planned + 256;
-    }
-    if (plain.empty()) return HBK_OK;
-    return bwd_planned((int32_t)plain.size(), plain.data(), apply, apply_lr, at, stream, false);
-  }
-  return bwd_planned(n_cols, cols, apply, apply_lr, workspace, stream, false);
+  return check_layouts(n_cols, cols, apply_lr, info);
 }
 
-// the bucket plans: grouping, reduce, merge (everything but the sort path of the deterministic mode)
-static int bwd_planned(int32_t n_cols, const hbk_lookup_grad_column_t* cols, int32_t apply,
-                       float apply_lr, void* workspace, hipStream_t stream, bool det) {
-  using namespace hbk;
-  // head of the workspace: the job descriptors of all columns (16-byte aligned), then the
-  // per-column buffers
-  char* cp = reinterpret_cast<char*>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-  char* dp = cp;
-  for (int32_t c = 0; c < n_cols; ++c) {
-    if (cols[c].n_ids > 0) dp += 256;       // one claim counter per column, one per line
-  }
-  char* wp = dp;
-  for (int32_t c = 0; c < n_cols; ++c) {
-    if (cols[c].n_ids <= 0) continue;
-    const ColPlan p = plan_of(cols[c].n_ids, cols[c].dim, cols[c].rows, cols[c].row_splits != nullptr, det);
-    wp += ((size_t)p.n_buckets + p.e_max) * sizeof(int4);
-  }
-
-  // Per column: plan, row shape, kind.  Everything that can fail is checked here, before any
-  // helper stream is forked.
-  struct ColInfo {
-    ColPlan p;
-    RowShape shape;
-    int kind;       // 2 * (0 dense lean | 1 dense with the sorted walk | 2 hashed) + (16-byte chunks ?
-                    // 0 : 1): columns of a launch group are sorted by it, so every kernel
-                    // instantiation runs on ONE range of job slots
-    bool onepass;   // small enough for the one-launch grouping (bwd_group_kernel)
-  };
-  std::vector<ColInfo> info((size_t)n_cols);
-  std::vector<int32_t> order;   // live columns: the one-launch ones first, then the large ones
+// ---- the bucket plans: grouping, reduce, merge (everything but the sort path of the deterministic mode)
+// the columns of `form` with ids: the one-launch ones first, then the large ones
+std::vector<int32_t> order_columns(int32_t n_cols, const hbk_lookup_grad_column_t* cols,
+                                   const std::vector<ColInfo>& info, int form) {
+  std::vector<int32_t> order;
   for (int pass = 0; pass < 2; ++pass) {
     for (int32_t c = 0; c < n_cols; ++c) {
-      const hbk_lookup_grad_column_t& h = cols[c];
-      if (h.n_ids <= 0) continue;
-      ColInfo& ci = info[(size_t)c];
-      if (pass == 0) {
-        ci.p = plan_of(h.n_ids, h.dim, h.rows, h.row_splits != nullptr, det);
-        HBK_REQUIRE(h.grad_stride == 0 || (h.grad_stride >= h.dim && h.n_runs == 0),
-                    "group_lookup_bwd: column %d: bad grad_stride %d", c, h.grad_stride);
-        HBK_REQUIRE(make_rowshape(h.dim,
-                                  (uintptr_t)h.grad_out | (uintptr_t)h.grad_rows |
-                                      ((uintptr_t)(uint32_t)h.grad_stride * 4) |
-                                      (apply_lr != 0.0f ? (uintptr_t)h.table | (uintptr_t)h.accum |
-                                                              ((uintptr_t)(uint32_t)h.table_pitch * 4) : 0),
-                                  &ci.shape),
-                    "group_lookup_bwd: dim %d needs more than 64 lanes per row", h.dim);
-        // bucket kind: 0 dense, 1 dense with sorted duplicates, 2 hashed, 3 hashed with the wide
-        // sorted walk (an optimizer step, >= 16 lanes per row, one id per sample: bucket_reduce)
-        const bool wide = apply_lr != 0.0f && ci.shape.lpr_log2 >= 4 &&
-                          (options().bwd_wide == 2 ||
-                           (options().bwd_wide == 1 && h.row_splits == nullptr));
-        const int bkind = ci.p.rowsort ? 4 : ci.p.dense_mul != 0 ? (ci.p.dense_sort ? 1 : 0) : wide ? 3 : 2;
-        ci.kind = 2 * bkind + (ci.shape.vec4 ? 0 : 1);
-        ci.onepass = options().bwd_onepass != 0 && ci.p.n_buckets <= kGroupMaxBuckets &&
-                     ci.p.tiles <= 64;
-      }
+      const ColInfo& ci = info[(size_t)c];
+      if (cols[c].n_ids <= 0 || ci.form != form) continue;
       if ((pass == 0) == (ci.onepass != (options().bwd_large_first != 0))) order.push_back(c);
     }
   }
+  return order;
+}
+
+// the next launch group's columns: up to group_cols of one grouping form from order[*q0 ..], sorted by
+// kind (stable)
+int32_t next_group(const std::vector<ColInfo>& info, const std::vector<int32_t>& order, int32_t* q0,
+                   int group_cols, int32_t* members) {
+  const bool group_onepass = info[(size_t)order[(size_t)*q0]].onepass;
+  int32_t k_n = 0;
+  while (*q0 < (int32_t)order.size() && k_n < group_cols &&
+         info[(size_t)order[(size_t)*q0]].onepass == group_onepass) {
+    members[k_n++] = order[(size_t)(*q0)++];
+  }
+  std::stable_sort(members, members + k_n,
+                   [&](int32_t a, int32_t b) { return info[(size_t)a].kind < info[(size_t)b].kind; });
+  return k_n;
+}
+
+// where the next column's claim counter, job descriptors and buffers go (head of the workspace: one
+// counter per column, each on its own line, then the descriptors of all columns, 16-byte aligned,
+// then the per-column buffers)
+struct Carve {
+  char* counter;
+  char* desc;
+  char* buf;
+};
+template <typename T>
+inline T* buf_at(char* base, size_t off) {
+  return off == kNoBuf ? nullptr : reinterpret_cast<T*>(base + off);
+}
+inline float* rows_at(char* base, size_t off) {   // 16-byte aligned inside the buffer's slack
+  return off == kNoBuf ? nullptr : reinterpret_cast<float*>(((uintptr_t)(base + off) + 15) & ~(uintptr_t)15);
+}
+
+// One launch group: its columns as the kernels see them and the grids of every launch
+struct KindCol { int32_t n_buckets, e_max, weight; };   // slots of a column: buckets, then extras
+struct Group {
+  GArgs args, seg_args;
+  bool onepass;         // one-launch columns, or large ones
+  int32_t k = 0, ks = 0;   // columns of args, of seg_args
+  int64_t tiles = 0, buckets = 0, segtiles = 0, merges = 0, scans = 0, sync_words = 0;
+  size_t lds_hist = 0;
+  bool small_scan = true;
+  int64_t slot_lo[kKinds] = {0}, slot_hi[kKinds] = {0};     // job slots of every kind
+  int64_t merge_lo[kKinds] = {0}, merge_hi[kKinds] = {0};   // merge blocks of every kind
+  bool have_kind[kKinds] = {false};
+  std::vector<KindCol> kind_cols[kKinds];
+  int64_t xcd_grid[kKinds] = {0};   // place_xcds(): > 0: the reduce grid of a kind with ranges of equal work
+};
+
+// column h as the group's next GCol (and as seg_args' next where it needs the seg-of launch)
+int add_column(Group& g, const hbk_lookup_grad_column_t& h, const ColInfo& ci, bool det, Carve* at) {
+  const ColPlan& p = ci.p;
+  const ColLayout& l = ci.lay;
+  const int32_t k = g.k;
+  GCol& d = g.args.col[k];
+  memset(&d, 0, sizeof(d));
+  d.ids = h.ids;
+  d.grad_out = h.grad_out;
+  d.splits = h.row_splits;
+  d.unique_rows = h.unique_rows;
+  d.grad_rows = h.grad_rows;
+  d.n_unique = h.n_unique;
+  d.counter = reinterpret_cast<int32_t*>(at->counter);
+  at->counter += 256;
+  d.desc = reinterpret_cast<int4*>(at->desc);
+  at->desc += l.desc_bytes;
+  char* const base = at->buf;
+  at->buf += l.bytes;
+  d.table = h.table;
+  d.accum = h.accum;
+  d.hist = buf_at<int32_t>(base, l.hist);
+  d.bstart = buf_at<int32_t>(base, l.bstart);
+  d.pair_row[0] = buf_at<int64_t>(base, l.pair_row);
+  d.pair_seg[0] = buf_at<int32_t>(base, l.pair_seg);
+  d.packed = l.pair_seg == kNoBuf ? 1 : 0;
+  d.seg_of = buf_at<int32_t>(base, l.seg_of);
+  float* const scaled = rows_at(base, l.scaled);
+  d.work = buf_at<int32_t>(base, l.work);
+  d.n_extra = buf_at<int32_t>(base, l.n_extra);
+  d.pcount = buf_at<int32_t>(base, l.pcount);
+  d.part_rows = buf_at<int64_t>(base, l.part_rows);
+  d.part_vals = rows_at(base, l.part_vals);
+  if (h.grad_rows == nullptr) {
+    d.no_emit = 1;
+    d.unique_rows = buf_at<int64_t>(base, l.step_rows);
+    d.grad_rows = rows_at(base, l.step_vals);
+  }
+  d.split_t = p.split_t;
+  d.e_max = p.e_max;
+  d.dense_mul = p.dense_mul;
+  d.rowsort = p.rowsort ? 1 : 0;
+  d.det = det ? 1 : 0;
+  d.merge0 = (int32_t)g.merges;
+  const int64_t merge_blocks = p.e_max < kMergeBlocks ? p.e_max : kMergeBlocks;
+  d.scan0 = (int32_t)g.scans;
+  g.scans += ((int64_t)p.n_buckets + kBlock - 1) / kBlock;
+  g.small_scan = g.small_scan && p.n_buckets <= 4 * kBlock && p.tiles <= 64;
+  d.sync0 = (int32_t)g.sync_words;
+  g.sync_words += (int64_t)p.tiles * p.n_buckets;
+  d.run_start = h.run_start;
+  d.run_ids = h.run_ids;
+  d.run_grads = h.run_grads;
+  d.n_runs = h.n_runs;
+  d.grad_stride = h.grad_stride > 0 ? h.grad_stride : h.dim;
+  d.map = make_idmap(h.bucket, h.divisor, h.rows);
+  d.n_ids = h.n_ids;
+  d.n_seg = h.n_segments;
+  d.dim = h.dim;
+  d.tpitch = h.table_pitch > 0 ? h.table_pitch : h.dim;
+  d.chunks = ci.shape.chunks;
+  d.lpr_log2 = ci.shape.lpr_log2;
+  d.vec4 = ci.shape.vec4;
+  d.ids64 = h.ids_dtype == HBK_INT64;
+  d.combiner = (uint8_t)h.combiner;
+  d.n_buckets = p.n_buckets;
+  d.tile0 = (int32_t)g.tiles;
+  d.bucket0 = (int32_t)g.buckets;
+  if (!g.have_kind[ci.kind]) {
+    g.have_kind[ci.kind] = true;
+    g.slot_lo[ci.kind] = g.buckets;
+    g.merge_lo[ci.kind] = g.merges;
+  }
+  g.kind_cols[ci.kind].push_back({p.n_buckets, p.e_max, 24 + h.dim});
+  g.tiles += p.tiles;
+  g.buckets += (int64_t)p.n_buckets + p.e_max;
+  g.merges += merge_blocks;
+  g.slot_hi[ci.kind] = g.buckets;
+  g.merge_hi[ci.kind] = g.merges;
+  if (g.tiles >= (1ll << 31) || g.buckets >= (1ll << 31)) {
+    return fail(HBK_INVALID_ARGUMENT, "group_lookup_bwd: grid too large");
+  }
+  if ((size_t)4 * p.n_buckets > g.lds_hist) g.lds_hist = (size_t)4 * p.n_buckets;
+  g.args.tile0[k] = d.tile0;
+  g.args.bucket0[k] = d.bucket0;
+  g.args.merge0[k] = d.merge0;
+  g.args.scan0[k] = d.scan0;
+  g.args.segtile0[k] = 0;
+  // large ragged mean / sqrtn columns without a seg-of array: the histogram launch scales the
+  // segments' rows (it knows the caller's gradient through raw_*)
+  const bool scale_in_hist = scaled != nullptr && d.seg_of == nullptr && !g.onepass &&
+                             options().bwd_scale_fused != 0 && h.n_segments > 0;
+  if (scale_in_hist) {
+    d.scaled = scaled;
+    d.raw_grad = h.grad_out;
+    d.raw_stride = h.grad_stride > 0 ? h.grad_stride : h.dim;
+    d.raw_combiner = h.combiner;
+  }
+  // the seg-of launch: columns with a seg-of array, or with rows to scale (mean / sqrtn)
+  if (!scale_in_hist && h.row_splits != nullptr && h.n_segments > 0 &&
+      (d.seg_of != nullptr || scaled != nullptr)) {
+    GCol& sdesc = g.seg_args.col[g.ks];
+    sdesc = d;
+    sdesc.scaled = scaled;
+    sdesc.segtile0 = (int32_t)g.segtiles;
+    g.seg_args.segtile0[g.ks] = (int32_t)g.segtiles;
+    g.segtiles += (h.n_segments + kBlock - 1) / kBlock;
+    ++g.ks;
+  }
+  if (scaled != nullptr && h.n_segments > 0) {
+    // one of the two launches scales the segments' gradient rows once; everything behind it reads
+    // the scaled rows as the gradient of a SUM column
+    d.grad_out = scaled;
+    d.grad_stride = h.dim;
+    d.combiner = HBK_COMBINER_SUM;
+  }
+  ++g.k;
+  return HBK_OK;
+}
+
+// HBK_BWD_TRACE: the composition of a launch group on stderr
+void trace_group(const Group& g, const hbk_lookup_grad_column_t* cols, const std::vector<ColInfo>& info,
+                 const int32_t* members, int group_no, int stream_no) {
+  int64_t g_ids = 0, g_bytes = 0;
+  int by_kind[kKinds] = {0};
+  for (int32_t i = 0; i < g.k; ++i) {
+    g_ids += cols[members[i]].n_ids;
+    g_bytes += (int64_t)cols[members[i]].n_ids * cols[members[i]].dim * 4;
+    ++by_kind[info[(size_t)members[i]].kind];
+  }
+  fprintf(stderr, "[hbk bwd] group %d on stream %d: %d columns (%s), %lld ids, %.1f MB of gradient rows, "
+          "%lld tiles, %lld job slots; columns by kind", group_no, stream_no, g.k,
+          g.onepass ? "one-launch" : "large", (long long)g_ids, (double)g_bytes / 1e6, (long long)g.tiles,
+          (long long)g.buckets);
+  for (int q = 0; q < kKinds; ++q) {
+    if (by_kind[q] != 0) fprintf(stderr, " %d:%d", q, by_kind[q]);
+  }
+  fprintf(stderr, "\n");
+}
+
+// Reduce jobs to XCDs (xcd_contiguous): whole columns per XCD -- when that leaves the XCDs
+// evenly loaded.  The eight ranges hold equal numbers of job slots, not equal work: a job of
+// a dim-128 column costs several jobs of a dim-4 one, and a launch of mixed columns then waits
+// for its heaviest XCD (config-5 shape: + 3 %, where equal columns gain 4 %).  The host knows
+// the columns: it adds up each range's work (jobs x (24 + dim); the extra slots of a column
+// are mostly unused) and keeps the round-robin placement when the heaviest range is > 8 %
+// above the mean.  Option bwd_xcd: 0 never, 1 this rule, 2 always.
+// Host arithmetic on the group's kind_cols: sets args.xcd, args.xcd_w, args.xcd_start and xcd_grid.
+void place_xcds(Group& g) {
+  GArgs& args = g.args;
+  args.xcd = 0;
+  for (int kind = 0; kind < kKinds; ++kind) {
+    if (!g.have_kind[kind] || options().bwd_xcd == 0) continue;
+    bool even = options().bwd_xcd == 2;
+    if (!even) {
+      const int64_t per = slots_per_block(kind);
+      const int64_t n = (g.slot_hi[kind] - g.slot_lo[kind] + per - 1) / per;   // the launch's blocks
+      const int64_t q = n / 8, r = n % 8;
+      double work[8] = {0}, total = 0;
+      int64_t slot = 0;      // walked once: ranges and columns both ascend
+      int x = 0;
+      int64_t x_end = (r > 0 ? q + 1 : q) * per;
+      for (const KindCol& kc : g.kind_cols[kind]) {
+        for (int part = 0; part < 2; ++part) {
+          int64_t len = part == 0 ? kc.n_buckets : kc.e_max;
+          const double w = part == 0 ? (double)kc.weight : 0.0;
+          while (len > 0) {
+            while (x < 7 && slot >= x_end) {
+              ++x;
+              x_end += (x < r ? q + 1 : q) * per;
+            }
+            const int64_t take = x < 7 && x_end - slot < len ? x_end - slot : len;
+            work[x] += w * (double)take;
+            total += w * (double)take;
+            slot += take;
+            len -= take;
+          }
+        }
+      }
+      double heaviest = 0;
+      for (double w : work) heaviest = w > heaviest ? w : heaviest;
+      even = total > 0 && heaviest <= 1.08 * total / 8;
+    }
+    if (even) args.xcd |= 1 << kind;
+  }
+  // The launches that pass get ranges of equal WORK rather than of equal slot counts (the extra
+  // slots at every column's end are mostly empty): config 2 99.9 -> 98.9 us, + SGD 181 -> 176,
+  // step only 144 -> 140.3, toggled in-process.  (bwd_xcd = 4, a probe: such ranges for every
+  // launch -- the config-5 shape loses 5 % with them, so its loss above is not the imbalance
+  // alone.)
+  args.xcd_w = 0;
+  if ((options().bwd_xcd == 4 || options().bwd_xcd == 1 || options().bwd_xcd == 3) && kTeams == 1) {
+    for (int kind = 0; kind < kKinds; ++kind) {
+      if (!g.have_kind[kind]) continue;
+      if (options().bwd_xcd != 4 && !((args.xcd >> kind) & 1)) continue;
+      double total = 0;
+      for (const KindCol& kc : g.kind_cols[kind]) total += (double)kc.weight * kc.n_buckets;
+      if (total <= 0) continue;
+      int32_t* st = args.xcd_start[kind];
+      st[0] = 0;
+      int x = 1;
+      double acc = 0;
+      int64_t slot = 0;
+      for (const KindCol& kc : g.kind_cols[kind]) {
+        // the live slots of the column, one by one in blocks: boundary x sits where the work
+        // before it first reaches x / 8 of the total
+        for (int64_t b = 0; b < kc.n_buckets; ++b) {
+          while (x < 8 && acc >= total * x / 8) st[x++] = (int32_t)(slot + b);
+          acc += kc.weight;
+        }
+        slot += (int64_t)kc.n_buckets + kc.e_max;
+      }
+      while (x <= 8) st[x++] = (int32_t)slot;
+      st[8] = (int32_t)(g.slot_hi[kind] - g.slot_lo[kind]);
+      int64_t longest = 0;
+      for (int q = 0; q < 8; ++q) longest = st[q + 1] - st[q] > longest ? st[q + 1] - st[q] : longest;
+      g.xcd_grid[kind] = 8 * longest;
+      args.xcd_w |= 1 << kind;
+    }
+  }
+  // (equal tiles: always even; bwd_xcd = 3: the rule above without this -- probes)
+  if (options().bwd_xcd == 1 || options().bwd_xcd == 2) args.xcd |= 1 << kXcdScatterBit;
+}
+
+// The grouping launches on `ls`: the seg-of launch where columns need it, then hist, scan and scatter
+// -- as one launch (the one-launch columns, when sync words can be had: *sync, returns true) or as
+// three.  `caller`: the call's stream (sync_take reports to it).
+bool launch_grouping(Group& g, hipStream_t ls, hipStream_t caller, GSync* sync) {
+  GArgs& args = g.args;
+  const int32_t k = g.k;
+  const dim3 tiles((unsigned)g.tiles), block(kBlock);
+  if (g.ks > 0) {
+    g.seg_args.n_cols = g.ks;
+    g.seg_args.lr = 0.f;
+    hipLaunchKernelGGL(bwd_segof_kernel, dim3((unsigned)g.segtiles), block, 0, ls, g.seg_args);
+  }
+  // SIMPLE: every column of the group: no segmented inputs, no seg-of array, packed pairs, int64 ids,
+  // row-range buckets
+  bool simple_group = options().bwd_simple != 0;
+  bool unpacked = false;
+  for (int32_t i = 0; i < k; ++i) {
+    const GCol& c = args.col[i];
+    simple_group = simple_group && c.n_runs == 0 && c.seg_of == nullptr && c.packed != 0 && c.ids64 != 0 &&
+                   c.dense_mul != 0;
+    unpacked = unpacked || c.packed == 0;
+  }
+  // LDS behind the kernels' own: a tile's segments where some column keeps them apart from the rows
+  const size_t lds_tail = (unpacked ? (size_t)kTile * 4 : 0) + (size_t)options().bwd_lds_pad * 1024;
+  memset(sync, 0, sizeof(*sync));
+  const auto group_kernel = simple_group ? &bwd_group_kernel<true> : &bwd_group_kernel<false>;
+  bool onepass = g.onepass && g.sync_words < (1ll << 30);
+  if (onepass) {
+    SyncTake take;
+    onepass = sync_take(ls, (size_t)g.sync_words, &take, reinterpret_cast<const void*>(group_kernel), kBlock,
+                        64, caller);
+    if (onepass) {
+      sync->hist = take.words;
+      sync->zero = take.zero;
+      sync->zero_words = take.zero_words;
+      sync->wait = sync_wait_of(take);
+    }
+  }
+  if (onepass) {
+    // (hist, scan and scatter are this one launch)
+    SyncChain chain(ls);   // never beside another kernel whose tiles wait for later tiles
+    hipLaunchKernelGGL(group_kernel, tiles, block, lds_tail, ls, args, *sync);
+    return true;
+  }
+  hipLaunchKernelGGL(simple_group ? &bwd_hist_kernel<true> : &bwd_hist_kernel<false>, tiles, block, g.lds_hist,
+                     ls, args);
+  if (g.small_scan) {
+    hipLaunchKernelGGL(bwd_scan_fused_kernel, dim3((unsigned)k), block, 0, ls, args);
+  } else {
+    hipLaunchKernelGGL(bwd_scan_tiles_kernel, dim3((unsigned)g.scans), block, 0, ls, args);
+    hipLaunchKernelGGL(bwd_scan_kernel, dim3((unsigned)k), block, 0, ls, args);
+  }
+  if (g.lds_hist <= (size_t)4 * kStageMaxBuckets && options().bwd_scatter_staged != 0) {
+    args.stage_p = (int32_t)(g.lds_hist / 4);
+    hipLaunchKernelGGL(simple_group ? &bwd_scatter_staged_kernel<true> : &bwd_scatter_staged_kernel<false>,
+                       tiles, block, 2 * g.lds_hist + lds_tail, ls, args);
+  } else {
+    hipLaunchKernelGGL(bwd_scatter_pairs_kernel, tiles, block, g.lds_hist, ls, args);
+  }
+  return false;
+}
+
+// The reduce and merge launches of a group: one instantiation per kind and optimizer (none / SGD /
+// Adagrad), each on its own job slots.  desc: the group's first job descriptor; poison: of a
+// one-launch grouping (else NULL)
+int launch_reduce_merge(const Group& g, bool det, int32_t apply, float apply_lr, const int4* desc,
+                        const int32_t* poison, hipStream_t ls) {
+  const GArgs& args = g.args;
+  const int step = apply_lr == 0.0f ? 0 : apply == HBK_APPLY_ADAGRAD ? 2 : 1;
+  typedef void (*reduce_fn)(const GArgs, const int4*, int, int, const int32_t*);
+  typedef void (*merge_fn)(const GArgs, int, const int32_t*);
+  // one row per kind, one entry per step
+#define HBK_BY_STEP(K, V, ...) {&K<V, 0, ##__VA_ARGS__>, &K<V, 1, ##__VA_ARGS__>, &K<V, 2, ##__VA_ARGS__>}
+  static const reduce_fn kReduce[kKinds][3] = {
+      HBK_BY_STEP(bwd_dense_kernel, f32x4, false), HBK_BY_STEP(bwd_dense_kernel, float, false),
+      HBK_BY_STEP(bwd_dense_kernel, f32x4, true), HBK_BY_STEP(bwd_dense_kernel, float, true),
+      HBK_BY_STEP(bwd_reduce_kernel, f32x4, false), HBK_BY_STEP(bwd_reduce_kernel, float, false),
+      {nullptr, &bwd_reduce_kernel<f32x4, 1, true>, &bwd_reduce_kernel<f32x4, 2, true>},
+      {nullptr, &bwd_reduce_kernel<float, 1, true>, &bwd_reduce_kernel<float, 2, true>},
+      HBK_BY_STEP(bwd_rowsort_kernel, f32x4), HBK_BY_STEP(bwd_rowsort_kernel, float)};
+  static const merge_fn kMerge[kKinds][3] = {
+      HBK_BY_STEP(bwd_dense_merge_kernel, f32x4), HBK_BY_STEP(bwd_dense_merge_kernel, float),
+      HBK_BY_STEP(bwd_dense_merge_kernel, f32x4), HBK_BY_STEP(bwd_dense_merge_kernel, float),
+      HBK_BY_STEP(bwd_merge_kernel, f32x4, false), HBK_BY_STEP(bwd_merge_kernel, float, false),
+      {nullptr, &bwd_merge_kernel<f32x4, 1, true>, &bwd_merge_kernel<f32x4, 2, true>},
+      {nullptr, &bwd_merge_kernel<float, 1, true>, &bwd_merge_kernel<float, 2, true>},
+      HBK_BY_STEP(bwd_rowsort_merge_kernel, f32x4), HBK_BY_STEP(bwd_rowsort_merge_kernel, float)};
+  // (the in-order form of the row-sorted jobs: 16-byte chunks, 4-byte chunks)
+  static const reduce_fn kReduceDet[2][3] = {HBK_BY_STEP(bwd_rowsort_kernel, f32x4, true),
+                                             HBK_BY_STEP(bwd_rowsort_kernel, float, true)};
+#undef HBK_BY_STEP
+  int status = HBK_OK;
+  if (det) {   // where every bucket's rows begin in its column's output (lookup_bwd_rowsort.h)
+    hipLaunchKernelGGL(bwd_rowsort_count_kernel, dim3((unsigned)g.buckets), dim3(kBlock), 0, ls, args, desc,
+                       (int)g.buckets, poison);
+  }
+  for (int kind = 0; kind < kKinds; ++kind) {
+    if (!g.have_kind[kind]) continue;
+    const int64_t n_slots = g.slot_hi[kind] - g.slot_lo[kind];
+    const int64_t per = slots_per_block(kind);
+    const int64_t grid = g.xcd_grid[kind] > 0 ? g.xcd_grid[kind] : (n_slots + per - 1) / per;
+    if (det && bucket_kind_of(kind) != kRowSorted) {
+      status = fail(HBK_INTERNAL, "group_lookup_bwd: a deterministic column without row-sorted buckets");
+      break;
+    }
+    hipLaunchKernelGGL(det ? kReduceDet[kind & 1][step] : kReduce[kind][step],
+                       dim3((unsigned)grid), dim3(kBlock), 0, ls, args, desc, (int)g.slot_lo[kind],
+                       (int)g.slot_hi[kind], poison);
+  }
+  for (int kind = 0; kind < kKinds; ++kind) {
+    if (!g.have_kind[kind]) continue;
+    hipLaunchKernelGGL(kMerge[kind][step], dim3((unsigned)(g.merge_hi[kind] - g.merge_lo[kind])),
+                       dim3(kBlock), 0, ls, args, (int)g.merge_lo[kind], poison);
+  }
+  const hipError_t launch_err = hipGetLastError();
+  if (launch_err != hipSuccess) {
+    status = fail(HBK_INTERNAL, "group_lookup_bwd: launch failed: %s", hipGetErrorString(launch_err));
+  }
+  return status;
+}
+
+// the columns of `form` (kFormInOrder, kFormPlain) through the bucket plans; workspace: their slice
+int bwd_planned(int32_t n_cols, const hbk_lookup_grad_column_t* cols, const std::vector<ColInfo>& info,
+                int form, int32_t apply, float apply_lr, void* workspace, hipStream_t stream) {
+  const bool det = form == kFormInOrder;
+  const std::vector<int32_t> order = order_columns(n_cols, cols, info, form);
+  const int32_t live_cols = (int32_t)order.size();
+  Carve at;
+  at.counter = reinterpret_cast<char*>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  at.desc = at.counter + (size_t)256 * order.size();
+  at.buf = at.desc;
+  for (int32_t c : order) at.buf += info[(size_t)c].lay.desc_bytes;
   for (int32_t c = 0; c < n_cols; ++c) {
-    if (cols[c].n_ids == 0) HBK_HIP_OK(hipMemsetAsync(cols[c].n_unique, 0, sizeof(int32_t), stream));
+    if (cols[c].n_ids == 0 && info[(size_t)c].form == form) {
+      HBK_HIP_OK(hipMemsetAsync(cols[c].n_unique, 0, sizeof(int32_t), stream));
+    }
   }
 
   // More than kMaxCols columns make several launch groups (config 5: 200 columns = 4).  They are
@@ -4049,7 +4387,6 @@ static int bwd_planned(int32_t n_cols, const hbk_lookup_grad_column_t* cols, int
   // beside the next group's grouping launches instead of in front of them.  A group holds either
   // one-launch columns or large ones (a single large column would otherwise put its whole group
   // on the three grouping launches).
-  const int32_t live_cols = (int32_t)order.size();
   int group_cols = options().bwd_group_cols;   // columns per launch group (tuning; 0: kMaxCols)
   if (group_cols <= 0 || group_cols > kMaxCols) group_cols = kMaxCols;
   bool mixed = false;
@@ -4073,430 +4410,27 @@ static int bwd_planned(int32_t n_cols, const hbk_lookup_grad_column_t* cols, int
   int group_no = 0;
   int32_t q0 = 0;
   while (q0 < live_cols && status == HBK_OK) {
-    hipStream_t ls = helpers != nullptr ? helpers->s[group_no++ % n_streams] : stream;
-    GArgs args, seg_args;
-    int4* const desc_group = reinterpret_cast<int4*>(dp);
-    // the group's columns: up to group_cols of one grouping form, sorted by kind (stable)
-    const bool group_onepass = info[(size_t)order[q0]].onepass;
+    const int stream_no = helpers != nullptr ? group_no % n_streams : -1;
+    hipStream_t ls = helpers != nullptr ? helpers->s[stream_no] : stream;
+    Group g;
+    const int4* const desc_group = reinterpret_cast<const int4*>(at.desc);
     int32_t members[kMaxCols];
-    int32_t k_n = 0;
-    while (q0 < live_cols && k_n < group_cols && info[(size_t)order[q0]].onepass == group_onepass) {
-      members[k_n++] = order[q0++];
-    }
-    for (int32_t i = 1; i < k_n; ++i) {   // insertion sort: <= 64 entries
-      const int32_t m = members[i];
-      int32_t j = i;
-      while (j > 0 && info[(size_t)members[j - 1]].kind > info[(size_t)m].kind) {
-        members[j] = members[j - 1];
-        --j;
-      }
-      members[j] = m;
-    }
-    int32_t k = 0, ks = 0;
-    int64_t tiles = 0, buckets = 0, segtiles = 0, merges = 0, scans = 0, sync_words = 0;
-    size_t lds_hist = 0;
-    bool small_scan = true;
-    constexpr int kKinds = 10;
-    int64_t slot_lo[kKinds] = {0}, slot_hi[kKinds] = {0};     // job slots of every kind
-    int64_t merge_lo[kKinds] = {0}, merge_hi[kKinds] = {0};   // merge blocks of every kind
-    bool have_kind[kKinds] = {false};
-    struct KindCol { int32_t n_buckets, e_max, weight; };   // slots of a column: buckets, then extras
-    std::vector<KindCol> kind_cols[kKinds];
-    for (; k < k_n; ++k) {
-      const int32_t col_index = members[k];
-      const hbk_lookup_grad_column_t& h = cols[col_index];
-      const ColInfo& ci = info[(size_t)col_index];
-      const ColPlan& p = ci.p;
-      GCol& d = args.col[k];
-      memset(&d, 0, sizeof(d));
-      d.ids = h.ids;
-      d.grad_out = h.grad_out;
-      d.splits = h.row_splits;
-      d.unique_rows = h.unique_rows;
-      d.grad_rows = h.grad_rows;
-      d.n_unique = h.n_unique;
-      d.counter = reinterpret_cast<int32_t*>(cp);
-      cp += 256;
-      d.table = h.table;
-      d.accum = h.accum;
-      d.hist = reinterpret_cast<int32_t*>(wp);
-      wp += align8(((size_t)p.tiles * p.n_buckets) * 4);
-      d.bstart = reinterpret_cast<int32_t*>(wp);
-      wp += align8(((size_t)p.n_buckets + 1) * 4);
-      d.pair_row[0] = reinterpret_cast<int64_t*>(wp);
-      wp += (size_t)h.n_ids * 8;
-      d.packed = pairs_packed(p) ? 1 : 0;
-      d.pair_seg[0] = nullptr;
-      if (!d.packed) {
-        d.pair_seg[0] = reinterpret_cast<int32_t*>(wp);
-        wp += align8((size_t)h.n_ids * 4);
-      }
-      // ragged columns: the grouping kernels find the segment of an id themselves (0a); option
-      // bwd_seg_inline = 0 keeps the seg-of array and the launch that writes it
-      d.seg_of = nullptr;
-      if (h.row_splits != nullptr && options().bwd_seg_inline == 0) {
-        d.seg_of = reinterpret_cast<int32_t*>(wp);
-        wp += align8((size_t)h.n_ids * 4);
-      }
-      float* scaled = nullptr;
-      if (h.row_splits != nullptr && h.combiner != HBK_COMBINER_SUM) {
-        scaled = reinterpret_cast<float*>(((uintptr_t)wp + 15) & ~(uintptr_t)15);
-        wp += align8((size_t)h.n_segments * h.dim * 4) + 16;
-      }
-      d.desc = reinterpret_cast<int4*>(dp);
-      dp += ((size_t)p.n_buckets + p.e_max) * sizeof(int4);
-      d.work = reinterpret_cast<int32_t*>(wp);
-      wp += align8((size_t)p.e_max * 8);
-      d.n_extra = reinterpret_cast<int32_t*>(wp);
-      wp += 8;
-      d.pcount = reinterpret_cast<int32_t*>(wp);
-      wp += align8(((size_t)p.n_buckets) * 4);
-      d.part_rows = reinterpret_cast<int64_t*>(wp);
-      wp += (size_t)h.n_ids * 8;
-      d.part_vals = reinterpret_cast<float*>(((uintptr_t)wp + 15) & ~(uintptr_t)15);
-      wp += align8((size_t)h.n_ids * h.dim * 4) + 16;
-      d.no_emit = 0;
-      if (h.grad_rows == nullptr) {
-        d.no_emit = 1;
-        d.unique_rows = reinterpret_cast<int64_t*>(wp);
-        wp += (size_t)h.n_ids * 8;
-        d.grad_rows = reinterpret_cast<float*>(((uintptr_t)wp + 15) & ~(uintptr_t)15);
-        wp += align8((size_t)h.n_ids * h.dim * 4) + 16;
-      }
-      d.split_t = p.split_t;
-      d.e_max = p.e_max;
-      d.dense_mul = p.dense_mul;
-      d.rowsort = p.rowsort ? 1 : 0;
-      d.det = det ? 1 : 0;
-      d.merge0 = (int32_t)merges;
-      const int64_t merge_blocks = p.e_max < kMergeBlocks ? p.e_max : kMergeBlocks;
-      d.scan0 = (int32_t)scans;
-      scans += ((int64_t)p.n_buckets + kBlock - 1) / kBlock;
-      small_scan = small_scan && p.n_buckets <= 4 * kBlock && p.tiles <= 64;
-      d.sync0 = (int32_t)sync_words;
-      sync_words += (int64_t)p.tiles * p.n_buckets;
-      d.run_start = h.run_start;
-      d.run_ids = h.run_ids;
-      d.run_grads = h.run_grads;
-      d.n_runs = h.n_runs;
-      d.grad_stride = h.grad_stride > 0 ? h.grad_stride : h.dim;
-      d.map = make_idmap(h.bucket, h.divisor, h.rows);
-      d.n_ids = h.n_ids;
-      d.n_seg = h.n_segments;
-      d.dim = h.dim;
-      d.tpitch = h.table_pitch > 0 ? h.table_pitch : h.dim;
-      d.chunks = ci.shape.chunks;
-      d.lpr_log2 = ci.shape.lpr_log2;
-      d.vec4 = ci.shape.vec4;
-      d.ids64 = h.ids_dtype == HBK_INT64;
-      d.combiner = (uint8_t)h.combiner;
-      d.n_buckets = p.n_buckets;
-      d.tile0 = (int32_t)tiles;
-      d.bucket0 = (int32_t)buckets;
-      d.segtile0 = 0;
-      if (!have_kind[ci.kind]) {
-        have_kind[ci.kind] = true;
-        slot_lo[ci.kind] = buckets;
-        merge_lo[ci.kind] = merges;
-      }
-      kind_cols[ci.kind].push_back({p.n_buckets, p.e_max, 24 + h.dim});
-      tiles += p.tiles;
-      buckets += (int64_t)p.n_buckets + p.e_max;
-      merges += merge_blocks;
-      slot_hi[ci.kind] = buckets;
-      merge_hi[ci.kind] = merges;
-      if (tiles >= (1ll << 31) || buckets >= (1ll << 31)) {
-        status = fail(HBK_INVALID_ARGUMENT, "group_lookup_bwd: grid too large");
-        break;
-      }
-      if ((size_t)4 * p.n_buckets > lds_hist) lds_hist = (size_t)4 * p.n_buckets;
-      args.tile0[k] = d.tile0;
-      args.bucket0[k] = d.bucket0;
-      args.merge0[k] = d.merge0;
-      args.scan0[k] = d.scan0;
-      args.segtile0[k] = 0;
-      // large ragged mean / sqrtn columns without a seg-of array: the histogram launch scales the
-      // segments' rows (it knows the caller's gradient through raw_*)
-      const bool scale_in_hist = scaled != nullptr && d.seg_of == nullptr && !group_onepass &&
-                                 options().bwd_scale_fused != 0 && h.n_segments > 0;
-      if (scale_in_hist) {
-        d.scaled = scaled;
-        d.raw_grad = h.grad_out;
-        d.raw_stride = h.grad_stride > 0 ? h.grad_stride : h.dim;
-        d.raw_combiner = h.combiner;
-        d.grad_out = scaled;
-        d.grad_stride = h.dim;
-        d.combiner = HBK_COMBINER_SUM;
-      }
-      // the seg-of launch: columns with a seg-of array, or with rows to scale (mean / sqrtn)
-      if (!scale_in_hist && h.row_splits != nullptr && h.n_segments > 0 &&
-          (d.seg_of != nullptr || scaled != nullptr)) {
-        GCol& sdesc = seg_args.col[ks];
-        sdesc = d;
-        sdesc.scaled = scaled;
-        if (scaled != nullptr) {
-          // the seg-of launch scales the segments' gradient rows once; everything behind it reads
-          // the scaled rows as the gradient of a SUM column
-          d.grad_out = scaled;
-          d.grad_stride = h.dim;
-          d.combiner = HBK_COMBINER_SUM;
-        }
-        sdesc.segtile0 = (int32_t)segtiles;
-        seg_args.segtile0[ks] = (int32_t)segtiles;
-        segtiles += (h.n_segments + kBlock - 1) / kBlock;
-        ++ks;
-      }
+    const int32_t k_n = next_group(info, order, &q0, group_cols, members);
+    g.onepass = info[(size_t)members[0]].onepass;
+    for (int32_t i = 0; i < k_n && status == HBK_OK; ++i) {
+      status = add_column(g, cols[members[i]], info[(size_t)members[i]], det, &at);
     }
     if (status != HBK_OK) break;
-    if (k == 0) continue;
-    if (options().bwd_trace != 0) {   // HBK_BWD_TRACE: the composition of every launch group on stderr
-      int64_t g_ids = 0, g_bytes = 0;
-      int by_kind[kKinds] = {0};
-      for (int32_t i = 0; i < k; ++i) {
-        g_ids += cols[members[i]].n_ids;
-        g_bytes += (int64_t)cols[members[i]].n_ids * cols[members[i]].dim * 4;
-        ++by_kind[info[(size_t)members[i]].kind];
-      }
-      fprintf(stderr, "[hbk bwd] group %d on stream %d: %d columns (%s), %lld ids, %.1f MB of gradient rows, "
-              "%lld tiles, %lld job slots; columns by kind", group_no - (helpers != nullptr ? 1 : 0),
-              helpers != nullptr ? (group_no - 1) % n_streams : -1, k, group_onepass ? "one-launch" : "large",
-              (long long)g_ids, (double)g_bytes / 1e6, (long long)tiles, (long long)buckets);
-      for (int q = 0; q < kKinds; ++q) {
-        if (by_kind[q] != 0) fprintf(stderr, " %d:%d", q, by_kind[q]);
-      }
-      fprintf(stderr, "\n");
-    }
-    args.n_cols = k;
-    args.lr = apply_lr;
-    args.apply = apply;
-    // Reduce jobs to XCDs (xcd_contiguous): whole columns per XCD -- when that leaves the XCDs
-    // evenly loaded.  The eight ranges hold equal numbers of job slots, not equal work: a job of
-    // a dim-128 column costs several jobs of a dim-4 one, and a launch of mixed columns then waits
-    // for its heaviest XCD (config-5 shape: + 3 %, where equal columns gain 4 %).  The host knows
-    // the columns: it adds up each range's work (jobs x (24 + dim); the extra slots of a column
-    // are mostly unused) and keeps the round-robin placement when the heaviest range is > 8 %
-    // above the mean.  Option bwd_xcd: 0 never, 1 this rule, 2 always.
-    args.xcd = 0;
-    for (int kind = 0; kind < kKinds; ++kind) {
-      if (!have_kind[kind] || options().bwd_xcd == 0) continue;
-      bool even = options().bwd_xcd == 2;
-      if (!even) {
-        const int64_t per = kind >= 4 && kind < 8 ? kTeams : 1;
-        const int64_t n = (slot_hi[kind] - slot_lo[kind] + per - 1) / per;   // the launch's blocks
-        const int64_t q = n / 8, r = n % 8;
-        double work[8] = {0}, total = 0;
-        int64_t slot = 0;      // walked once: ranges and columns both ascend
-        int x = 0;
-        int64_t x_end = (r > 0 ? q + 1 : q) * per;
-        for (const KindCol& kc : kind_cols[kind]) {
-          for (int part = 0; part < 2; ++part) {
-            int64_t len = part == 0 ? kc.n_buckets : kc.e_max;
-            const double w = part == 0 ? (double)kc.weight : 0.0;
-            while (len > 0) {
-              while (x < 7 && slot >= x_end) {
-                ++x;
-                x_end += (x < r ? q + 1 : q) * per;
-              }
-              const int64_t take = x < 7 && x_end - slot < len ? x_end - slot : len;
-              work[x] += w * (double)take;
-              total += w * (double)take;
-              slot += take;
-              len -= take;
-            }
-          }
-        }
-        double heaviest = 0;
-        for (double w : work) heaviest = w > heaviest ? w : heaviest;
-        even = total > 0 && heaviest <= 1.08 * total / 8;
-      }
-      if (even) args.xcd |= 1 << kind;
-    }
-    // The launches that pass get ranges of equal WORK rather than of equal slot counts (the extra
-    // slots at every column's end are mostly empty): config 2 99.9 -> 98.9 us, + SGD 181 -> 176,
-    // step only 144 -> 140.3, toggled in-process.  (bwd_xcd = 4, a probe: such ranges for every
-    // launch -- the config-5 shape loses 5 % with them, so its loss above is not the imbalance
-    // alone.)
-    args.xcd_w = 0;
-    args.stage_p = 0;
-    int64_t xcd_grid[kKinds] = {0};
-    if ((options().bwd_xcd == 4 || options().bwd_xcd == 1 || options().bwd_xcd == 3) && kTeams == 1) {
-      for (int kind = 0; kind < kKinds; ++kind) {
-        if (!have_kind[kind]) continue;
-        if (options().bwd_xcd != 4 && !((args.xcd >> kind) & 1)) continue;
-        double total = 0;
-        for (const KindCol& kc : kind_cols[kind]) total += (double)kc.weight * kc.n_buckets;
-        if (total <= 0) continue;
-        int32_t* st = args.xcd_start[kind];
-        st[0] = 0;
-        int x = 1;
-        double acc = 0;
-        int64_t slot = 0;
-        for (const KindCol& kc : kind_cols[kind]) {
-          // the live slots of the column, one by one in blocks: boundary x sits where the work
-          // before it first reaches x / 8 of the total
-          for (int64_t b = 0; b < kc.n_buckets; ++b) {
-            while (x < 8 && acc >= total * x / 8) st[x++] = (int32_t)(slot + b);
-            acc += kc.weight;
-          }
-          slot += (int64_t)kc.n_buckets + kc.e_max;
-        }
-        while (x <= 8) st[x++] = (int32_t)slot;
-        st[8] = (int32_t)(slot_hi[kind] - slot_lo[kind]);
-        int64_t longest = 0;
-        for (int q = 0; q < 8; ++q) longest = st[q + 1] - st[q] > longest ? st[q + 1] - st[q] : longest;
-        xcd_grid[kind] = 8 * longest;
-        args.xcd_w |= 1 << kind;
-      }
-    }
-    // (equal tiles: always even; bwd_xcd = 3: the rule above without this -- probes)
-    if (options().bwd_xcd == 1 || options().bwd_xcd == 2) args.xcd |= 1 << kXcdScatterBit;
-    if (ks > 0) {
-      seg_args.n_cols = ks;
-      seg_args.lr = 0.f;
-      hipLaunchKernelGGL(bwd_segof_kernel, dim3((unsigned)segtiles), dim3(kBlock), 0, ls,
-                         seg_args);
-    }
-    // every column of the group: no segmented inputs, no seg-of array, packed pairs, int64 ids, row-range buckets
-    bool simple_group = options().bwd_simple != 0;
-    for (int32_t i = 0; i < k; ++i) {
-      const GCol& g = args.col[i];
-      simple_group = simple_group && g.n_runs == 0 && g.seg_of == nullptr && g.packed != 0 && g.ids64 != 0 &&
-                     g.dense_mul != 0;
-    }
+    if (options().bwd_trace != 0) trace_group(g, cols, info, members, group_no, stream_no);
+    if (helpers != nullptr) ++group_no;   // (the trace numbers the groups of a forked call only)
+    g.args.n_cols = g.k;
+    g.args.lr = apply_lr;
+    g.args.apply = apply;
+    g.args.stage_p = 0;
+    place_xcds(g);
     GSync sync;
-    memset(&sync, 0, sizeof(sync));
-    bool onepass = group_onepass && sync_words < (1ll << 30);
-    if (onepass) {
-      SyncTake take;
-      onepass = sync_take(ls, (size_t)sync_words, &take,
-                          reinterpret_cast<const void*>(simple_group ? &bwd_group_kernel<true> : &bwd_group_kernel<false>),
-                          kBlock, 64, stream);
-      if (onepass) {
-        sync.hist = take.words;
-        sync.zero = take.zero;
-        sync.zero_words = take.zero_words;
-        sync.wait = sync_wait_of(take);
-      }
-    }
-    if (onepass) {
-      // (hist, scan and scatter are this one launch)
-      SyncChain chain(ls);   // never beside another kernel whose tiles wait for later tiles
-      bool unpacked = false;
-      for (int32_t i = 0; i < k; ++i) unpacked = unpacked || args.col[i].packed == 0;
-      if (simple_group) {
-        hipLaunchKernelGGL(bwd_group_kernel<true>, dim3((unsigned)tiles), dim3(kBlock),
-                           (size_t)options().bwd_lds_pad * 1024, ls, args, sync);
-      } else {
-        hipLaunchKernelGGL(bwd_group_kernel<false>, dim3((unsigned)tiles), dim3(kBlock),
-                           (unpacked ? (size_t)kTile * 4 : 0) + (size_t)options().bwd_lds_pad * 1024, ls,
-                           args, sync);
-      }
-    } else {
-      if (simple_group) {
-        hipLaunchKernelGGL(bwd_hist_kernel<true>, dim3((unsigned)tiles), dim3(kBlock), lds_hist, ls, args);
-      } else {
-        hipLaunchKernelGGL(bwd_hist_kernel<false>, dim3((unsigned)tiles), dim3(kBlock), lds_hist, ls, args);
-      }
-      if (small_scan) {
-        hipLaunchKernelGGL(bwd_scan_fused_kernel, dim3((unsigned)k), dim3(kBlock), 0, ls, args);
-      } else {
-        hipLaunchKernelGGL(bwd_scan_tiles_kernel, dim3((unsigned)scans), dim3(kBlock), 0, ls,
-                           args);
-        hipLaunchKernelGGL(bwd_scan_kernel, dim3((unsigned)k), dim3(kBlock), 0, ls, args);
-      }
-      if (lds_hist <= (size_t)4 * kStageMaxBuckets && options().bwd_scatter_staged != 0) {
-        bool unpacked = false;
-        for (int32_t i = 0; i < k; ++i) unpacked = unpacked || args.col[i].packed == 0;
-        args.stage_p = (int32_t)(lds_hist / 4);
-        if (simple_group) {
-          hipLaunchKernelGGL(bwd_scatter_staged_kernel<true>, dim3((unsigned)tiles), dim3(kBlock),
-                             2 * lds_hist + (size_t)options().bwd_lds_pad * 1024, ls, args);
-        } else {
-          hipLaunchKernelGGL(bwd_scatter_staged_kernel<false>, dim3((unsigned)tiles), dim3(kBlock),
-                             2 * lds_hist + (unpacked ? (size_t)kTile * 4 : 0) +
-                                 (size_t)options().bwd_lds_pad * 1024, ls, args);
-        }
-      } else {
-        hipLaunchKernelGGL(bwd_scatter_pairs_kernel, dim3((unsigned)tiles), dim3(kBlock), lds_hist,
-                           ls, args);
-      }
-    }
-    // one instantiation per kind and optimizer (none / SGD / Adagrad), each on its own job slots
-    const int step = apply_lr == 0.0f ? 0 : apply == HBK_APPLY_ADAGRAD ? 2 : 1;
-    typedef void (*reduce_fn)(const GArgs, const int4*, int, int, const int32_t*);
-    typedef void (*merge_fn)(const GArgs, int, const int32_t*);
-    const int32_t* poison = onepass ? sync.wait.poison : nullptr;
-    static const reduce_fn kReduce[kKinds][3] = {
-        {&bwd_dense_kernel<f32x4, 0, false>, &bwd_dense_kernel<f32x4, 1, false>,
-         &bwd_dense_kernel<f32x4, 2, false>},
-        {&bwd_dense_kernel<float, 0, false>, &bwd_dense_kernel<float, 1, false>,
-         &bwd_dense_kernel<float, 2, false>},
-        {&bwd_dense_kernel<f32x4, 0, true>, &bwd_dense_kernel<f32x4, 1, true>,
-         &bwd_dense_kernel<f32x4, 2, true>},
-        {&bwd_dense_kernel<float, 0, true>, &bwd_dense_kernel<float, 1, true>,
-         &bwd_dense_kernel<float, 2, true>},
-        {&bwd_reduce_kernel<f32x4, 0, false>, &bwd_reduce_kernel<f32x4, 1, false>,
-         &bwd_reduce_kernel<f32x4, 2, false>},
-        {&bwd_reduce_kernel<float, 0, false>, &bwd_reduce_kernel<float, 1, false>,
-         &bwd_reduce_kernel<float, 2, false>},
-        {nullptr, &bwd_reduce_kernel<f32x4, 1, true>, &bwd_reduce_kernel<f32x4, 2, true>},
-        {nullptr, &bwd_reduce_kernel<float, 1, true>, &bwd_reduce_kernel<float, 2, true>},
-        {&bwd_rowsort_kernel<f32x4, 0>, &bwd_rowsort_kernel<f32x4, 1>, &bwd_rowsort_kernel<f32x4, 2>},
-        {&bwd_rowsort_kernel<float, 0>, &bwd_rowsort_kernel<float, 1>, &bwd_rowsort_kernel<float, 2>}};
-    static const merge_fn kMerge[kKinds][3] = {
-        {&bwd_dense_merge_kernel<f32x4, 0>, &bwd_dense_merge_kernel<f32x4, 1>,
-         &bwd_dense_merge_kernel<f32x4, 2>},
-        {&bwd_dense_merge_kernel<float, 0>, &bwd_dense_merge_kernel<float, 1>,
-         &bwd_dense_merge_kernel<float, 2>},
-        {&bwd_dense_merge_kernel<f32x4, 0>, &bwd_dense_merge_kernel<f32x4, 1>,
-         &bwd_dense_merge_kernel<f32x4, 2>},
-        {&bwd_dense_merge_kernel<float, 0>, &bwd_dense_merge_kernel<float, 1>,
-         &bwd_dense_merge_kernel<float, 2>},
-        {&bwd_merge_kernel<f32x4, 0, false>, &bwd_merge_kernel<f32x4, 1, false>,
-         &bwd_merge_kernel<f32x4, 2, false>},
-        {&bwd_merge_kernel<float, 0, false>, &bwd_merge_kernel<float, 1, false>,
-         &bwd_merge_kernel<float, 2, false>},
-        {nullptr, &bwd_merge_kernel<f32x4, 1, true>, &bwd_merge_kernel<f32x4, 2, true>},
-        {nullptr, &bwd_merge_kernel<float, 1, true>, &bwd_merge_kernel<float, 2, true>},
-        {&bwd_rowsort_merge_kernel<f32x4, 0>, &bwd_rowsort_merge_kernel<f32x4, 1>,
-         &bwd_rowsort_merge_kernel<f32x4, 2>},
-        {&bwd_rowsort_merge_kernel<float, 0>, &bwd_rowsort_merge_kernel<float, 1>,
-         &bwd_rowsort_merge_kernel<float, 2>}};
-    static const reduce_fn kReduceDet[2][3] = {
-        {&bwd_rowsort_kernel<f32x4, 0, true>, &bwd_rowsort_kernel<f32x4, 1, true>, &bwd_rowsort_kernel<f32x4, 2, true>},
-        {&bwd_rowsort_kernel<float, 0, true>, &bwd_rowsort_kernel<float, 1, true>, &bwd_rowsort_kernel<float, 2, true>}};
-    if (det) {   // where every bucket's rows begin in its column's output (lookup_bwd_rowsort.h)
-      hipLaunchKernelGGL(bwd_rowsort_count_kernel, dim3((unsigned)buckets), dim3(kBlock), 0, ls, args, desc_group,
-                         (int)buckets, poison);
-    }
-    for (int kind = 0; kind < kKinds; ++kind) {
-      if (!have_kind[kind]) continue;
-      const int64_t n_slots = slot_hi[kind] - slot_lo[kind];
-      const int64_t per = kind >= 4 && kind < 8 ? kTeams : 1;   // job slots per workgroup
-      const int64_t grid = xcd_grid[kind] > 0 ? xcd_grid[kind] : (n_slots + per - 1) / per;
-      if (det) {
-        if (kind < 8) {
-          status = fail(HBK_INTERNAL, "group_lookup_bwd: a deterministic column without row-sorted buckets");
-          break;
-        }
-        hipLaunchKernelGGL(kReduceDet[kind - 8][step], dim3((unsigned)grid), dim3(kBlock), 0, ls, args,
-                           desc_group, (int)slot_lo[kind], (int)slot_hi[kind], poison);
-        continue;
-      }
-      hipLaunchKernelGGL(kReduce[kind][step], dim3((unsigned)grid),
-                         dim3(kBlock), 0, ls, args, desc_group, (int)slot_lo[kind],
-                         (int)slot_hi[kind], poison);
-    }
-    for (int kind = 0; kind < kKinds; ++kind) {
-      if (!have_kind[kind]) continue;
-      hipLaunchKernelGGL(kMerge[kind][step], dim3((unsigned)(merge_hi[kind] - merge_lo[kind])),
-                         dim3(kBlock), 0, ls, args, (int)merge_lo[kind], poison);
-    }
-    const hipError_t launch_err = hipGetLastError();
-    if (launch_err != hipSuccess) {
-      status = fail(HBK_INTERNAL, "group_lookup_bwd: launch failed: %s",
-                    hipGetErrorString(launch_err));
-    }
+    const bool onepass = launch_grouping(g, ls, stream, &sync);
+    status = launch_reduce_merge(g, det, apply, apply_lr, desc_group, onepass ? sync.wait.poison : nullptr, ls);
   }
   if (helpers != nullptr) {
     for (int i = 0; i < kHelperStreams; ++i) {
@@ -4509,6 +4443,66 @@ static int bwd_planned(int32_t n_cols, const hbk_lookup_grad_column_t* cols, int
     }
   }
   return status;
+}
+}  // namespace
+
+// (common.h)
+int bwd_check(int32_t n_cols, const hbk_lookup_grad_column_t* cols, int32_t apply, float apply_lr) {
+  std::vector<ColInfo> info;
+  return check_columns(n_cols, cols, apply, apply_lr, &info);
+}
+}  // namespace hbk
+
+extern "C" int hbk_group_lookup_bwd_apply(int32_t n_cols, const hbk_lookup_grad_column_t* cols,
+                                          int32_t apply, float apply_lr, void* workspace,
+                                          size_t workspace_bytes, hbk_stream_t stream_) {
+  using namespace hbk;
+  hipStream_t stream = as_stream(stream_);
+  std::vector<ColInfo> info;
+  int rc = check_columns(n_cols, cols, apply, apply_lr, &info);
+  if (rc != HBK_OK) return rc;
+  if (n_cols == 0) return HBK_OK;
+  // the forms' slices of the workspace and the sort path's layout (two size queries of the sort /
+  // scan primitives), made once from the records: what the size query adds up
+  const bool weighted = any_weighted(n_cols, cols);
+  CallLayout cl = {};
+  if (!weighted) {
+    cl = call_layout(n_cols, cols, info);
+    HBK_REQUIRE(cl.dl.total == 0 || cl.dl.temp_bytes > 256, "deterministic backward: the sort / scan "
+                "primitives cannot be sized on this device");
+  }
+  const size_t need = weighted ? hbk_group_lookup_bwd_workspace_bytes(n_cols, cols) : cl.total;
+  HBK_REQUIRE(need == 0 || (workspace != nullptr && workspace_bytes >= need),
+              "group_lookup_bwd: workspace too small: need %zu bytes, got %zu", need,
+              workspace_bytes);
+  HBK_REQUIRE(((uintptr_t)workspace & 7) == 0,
+              "group_lookup_bwd: workspace must be 8-byte aligned");
+  if ((rc = sync_check("group_lookup_bwd", stream)) != HBK_OK) return rc;
+  // weighted columns: their gradient terms per id into the head of the workspace, then the call
+  // over the columns as SUM columns of one id per segment
+  if (weighted) {
+    char* terms = reinterpret_cast<char*>(align16(reinterpret_cast<uintptr_t>(workspace)));
+    std::vector<hbk_lookup_grad_column_t> as_sum;
+    const size_t tb = weighted_as_sum(n_cols, cols, terms, &as_sum);   // (tb == 0: no term is placed)
+    if ((rc = launch_weight_terms(n_cols, cols, info, as_sum, stream)) != HBK_OK) return rc;
+    return hbk_group_lookup_bwd_apply(n_cols, as_sum.data(), apply, apply_lr,
+                                      tb == 0 ? workspace : reinterpret_cast<char*>(workspace) + tb,
+                                      workspace_bytes - tb, stream_);
+  }
+  // option bwd_deterministic: the in-order forms -- the sort + walk of lookup_bwd_det.h for the
+  // columns without row-sorted buckets (and for all of them under 2), row-sorted jobs where they
+  // fit (1); then the default forms
+  char* const ws = reinterpret_cast<char*>(workspace);
+  if (!cl.sorted.empty()) {
+    rc = det_backward((int32_t)cl.sorted.size(), cl.sorted.data(), cl.dl, apply, apply_lr, ws, stream);
+  }
+  if (rc == HBK_OK && has_form(info, kFormInOrder)) {
+    rc = bwd_planned(n_cols, cols, info, kFormInOrder, apply, apply_lr, ws + cl.in_order, stream);
+  }
+  if (rc == HBK_OK && has_form(info, kFormPlain)) {
+    rc = bwd_planned(n_cols, cols, info, kFormPlain, apply, apply_lr, ws + cl.plain, stream);
+  }
+  return rc;
 }
 
 // d(stitch + combiner) of the sharded pipeline (sharding.py:200 in reverse):

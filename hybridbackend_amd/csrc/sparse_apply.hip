@@ -465,12 +465,23 @@ int check_slot_columns(const SlotNames& nm, int32_t n_cols, const hbk_lookup_gra
   return HBK_OK;
 }
 
-size_t slot_workspace_bytes(int32_t n_cols, const hbk_lookup_grad_column_t* cols) {
-  if (n_cols <= 0 || cols == nullptr) return 0;
+// workspace of a two-slot call: the emit form's reduce, then the step-only slices (256-byte aligned
+// each).  The backward's size query runs once per call: `slots` is where the slices begin.
+struct SlotLayout {
+  size_t slots, total;
+};
+SlotLayout slot_layout(int32_t n_cols, const hbk_lookup_grad_column_t* cols) {
+  SlotLayout l = {0, 0};
+  if (n_cols <= 0 || cols == nullptr) return l;
   const std::vector<hbk_lookup_grad_column_t> e = emit_form(n_cols, cols);
-  size_t total = align256(hbk_group_lookup_bwd_workspace_bytes(n_cols, e.data()));
-  for (int32_t c = 0; c < n_cols; ++c) total += slot_bytes(cols[c]);
-  return total == 0 ? 0 : total + 256;
+  l.slots = align256(hbk_group_lookup_bwd_workspace_bytes(n_cols, e.data()));
+  l.total = l.slots;
+  for (int32_t c = 0; c < n_cols; ++c) l.total += slot_bytes(cols[c]);
+  if (l.total != 0) l.total += 256;
+  return l;
+}
+size_t slot_workspace_bytes(int32_t n_cols, const hbk_lookup_grad_column_t* cols) {
+  return slot_layout(n_cols, cols).total;
 }
 
 // phase 1: the reduce in its emit form (validates the rest of the columns); *e: the columns as the
@@ -478,24 +489,22 @@ size_t slot_workspace_bytes(int32_t n_cols, const hbk_lookup_grad_column_t* cols
 int run_emit_form(const char* who, int32_t n_cols, const hbk_lookup_grad_column_t* cols,
                   void* workspace, size_t workspace_bytes, hbk_stream_t stream_,
                   std::vector<hbk_lookup_grad_column_t>* e) {
-  const size_t need = slot_workspace_bytes(n_cols, cols);
+  const SlotLayout l = slot_layout(n_cols, cols);
+  const size_t need = l.total;
   HBK_REQUIRE(need == 0 || (workspace != nullptr && workspace_bytes >= need),
               "%s: workspace too small: need %zu bytes, got %zu", who, need, workspace_bytes);
   HBK_REQUIRE(((uintptr_t)workspace & 7) == 0, "%s: workspace must be 8-byte aligned", who);
   e->assign(cols, cols + n_cols);
   char* const base = reinterpret_cast<char*>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-  {
-    const std::vector<hbk_lookup_grad_column_t> q = emit_form(n_cols, cols);
-    char* slot = base + align256(hbk_group_lookup_bwd_workspace_bytes(n_cols, q.data()));
-    for (int32_t c = 0; c < n_cols; ++c) {
-      hbk_lookup_grad_column_t& h = (*e)[(size_t)c];
-      h.accum = nullptr;
-      if (h.grad_rows == nullptr && h.n_ids > 0) {
-        h.unique_rows = reinterpret_cast<int64_t*>(slot);
-        slot += align256((size_t)h.n_ids * 8);
-        h.grad_rows = reinterpret_cast<float*>(slot);
-        slot += align256((size_t)h.n_ids * h.dim * 4);
-      }
+  char* slot = base + l.slots;
+  for (int32_t c = 0; c < n_cols; ++c) {
+    hbk_lookup_grad_column_t& h = (*e)[(size_t)c];
+    h.accum = nullptr;
+    if (h.grad_rows == nullptr && h.n_ids > 0) {
+      h.unique_rows = reinterpret_cast<int64_t*>(slot);
+      slot += align256((size_t)h.n_ids * 8);
+      h.grad_rows = reinterpret_cast<float*>(slot);
+      slot += align256((size_t)h.n_ids * h.dim * 4);
     }
   }
   if (n_cols == 0) return HBK_OK;
