@@ -72,6 +72,12 @@ class FtrlParams(C.Structure):
               ('lr_power', C.c_float)]
 
 
+class Sequence(C.Structure):
+  """hbk_sequence_t"""
+  _fields_ = [('max_len', C.c_int32), ('has_pad', C.c_int32), ('pad_id', C.c_int64),
+              ('lengths', C.c_void_p), ('row_grid', C.c_void_p)]
+
+
 class ShardedColumn(C.Structure):
   """hbk_sharded_column_t"""
   _fields_ = [('shard', C.c_void_p), ('rows_local', C.c_int64), ('dim', C.c_int32),
@@ -139,6 +145,8 @@ def _declare(l):
     'hbk_group_lookup_bwd_ftrl_clipped_workspace_bytes': (sz, [i32, vp, vp]),
     'hbk_group_lookup_bwd_ftrl_clipped': (C.c_int, [i32, vp, vp, vp, vp, vp, C.c_float, vp, sz, vp]),
     'hbk_group_lookup_bwd_weights': (C.c_int, [i32, vp, vp, vp, vp]),
+    'hbk_group_lookup_fwd_sequence': (C.c_int, [i32, vp, vp, vp, vp]),
+    'hbk_sequence_row_grid_n': (C.c_int, [i32, vp, vp, vp]),
     'hbk_group_stitch_bwd': (C.c_int, [i32, vp, vp]),
     'hbk_cache_probe': (C.c_int, [vp, i64, i32, vp, i64, vp, vp, vp]),
     'hbk_cache_lookup_workspace_bytes': (sz, [i64]),

@@ -51,30 +51,12 @@ class EmbeddingColumn:
     self.max_norm = None if max_norm is None else max_norm_list([max_norm], 1)[0]
 
 
-class DenseFeatures:
-  """N embedding columns -> ``[batch, sum of dims]``.
+class _TableLayer:
+  """What DenseFeatures and SequenceFeatures share: one table per column, replicated or sharded by the
+  reference's rule, the optimizer slots, and the checkpoints."""
 
-  Args:
-    columns: list of :class:`EmbeddingColumn`.
-    device: the GPU.
-    coll: a ``hybridbackend_amd.distribute.Collective`` for sharded tables, or None.
-    batch_size: local batch size used by the replicate-or-shard rule
-      (``bucket_size <= num_shards or bucket_size <= batch_size`` keeps a table replicated,
-      variables.py:93-104).
-    init: ``init(column, rows, device) -> fp32 [rows, dim]`` for this rank's rows (rows
-      ``rank, rank + W, ..`` of the logical table when sharded); default uniform(-1e-3, 1e-3)
-      (docs/tutorial/ranking/criteo/train.py:84,91).
-    initial_accumulator_value: keep Adagrad accumulators (``optimizer='adagrad'``).
-    optimizer: ``'adam'`` keeps Lazy Adam slots -- zero ``m`` and ``v`` for every table -- for
-      ``backward(optimizer='adam')``; ``adam`` is the :class:`LazyAdam` they step with (TF's
-      defaults when omitted), whose beta powers advance once per stepped backward.  ``'ftrl'`` keeps
-      FTRL slots -- accum filled with ``ftrl.initial_accumulator_value``, zero linear -- for
-      ``backward(optimizer='ftrl')``; ``ftrl`` is the :class:`Ftrl` they step with (TF's defaults
-      when omitted).
-  """
-
-  def __init__(self, columns, device, coll=None, batch_size=0, init=None,
-               initial_accumulator_value=None, optimizer=None, adam=None, ftrl=None):
+  def _init_tables(self, columns, device, coll, batch_size, init, initial_accumulator_value, optimizer,
+                   adam, ftrl):
     self.columns = list(columns)
     self.device = torch.device(device)
     self.coll = coll
@@ -103,6 +85,111 @@ class DenseFeatures:
         opt = opt if opt is not None else cls.default(self.device)
         setattr(self, cls.name, opt)
         setattr(self, cls.slot_kw, [opt.slots_like(w) for w in self.weights])
+    self._rep = [c for c in range(len(self.columns)) if not self.sharded[c]]
+    self._shd = [c for c in range(len(self.columns)) if self.sharded[c]]
+
+  def _two_slot_kw(self, idx):
+    """The drivers' keyword arguments of the two-slot optimizers, tables idx."""
+    kw = {}
+    for cls in _opt.TWO_SLOT.values():
+      pairs = getattr(self, cls.slot_kw)
+      kw[cls.slot_kw] = None if pairs is None else [pairs[c] for c in idx]
+      kw[cls.name] = getattr(self, cls.name)
+    return kw
+
+  # ---- checkpoints (hybridbackend/tensorflow/training/saver.py:97-185) ----------------------------
+  def variables(self):
+    """``{name: tensor | ShardedSlice}`` of this rank: the embedding weights (TF naming:
+    ``<key>_embedding/embedding_weights``; a sharded table is the slice ``part_<rank>`` of it,
+    variables.py:112-141) and, when the layer keeps them, the Adagrad slots (``.../Adagrad``) or the
+    Lazy Adam slots (``.../Adam`` = m, ``.../Adam_1`` = v, sharded as the weights) with the 0-d
+    scalars ``beta1_power`` and ``beta2_power``, or the FTRL slots (``.../Ftrl`` = accum,
+    ``.../Ftrl_1`` = linear, sharded as the weights)."""
+    from hybridbackend_amd.training.saver import ShardedSlice
+    world = self.coll.world_size if self.coll is not None else 1
+    rank = self.coll.rank if self.coll is not None else 0
+    per_table = [('', self.weights), ('/Adagrad', self.accums)]
+    extra = {}
+    for cls in _opt.TWO_SLOT.values():
+      pairs = getattr(self, cls.slot_kw)
+      if pairs is not None:
+        per_table += [(cls.tf_suffixes[0], [a for a, _ in pairs]),
+                      (cls.tf_suffixes[1], [b for _, b in pairs])]
+        extra.update(getattr(self, cls.name).tf_variables())
+    out = {}
+    for c, col in enumerate(self.columns):
+      name = f'{col.key}_embedding/embedding_weights'
+      for suffix, tensors in per_table:
+        if tensors is None:
+          continue
+        t = tensors[c]
+        out[name + suffix] = (ShardedSlice(t, col.num_buckets, world, rank)
+                              if self.sharded[c] else t)
+    out.update(extra)
+    return out
+
+  def _saver(self, barrier):
+    from hybridbackend_amd.training.saver import Saver
+    world = self.coll.world_size if self.coll is not None else 1
+    rank = self.coll.rank if self.coll is not None else 0
+    if barrier is None and world > 1:
+      import torch.distributed as dist   # pylint: disable=import-outside-toplevel
+      if not dist.is_initialized():
+        raise _lib.HbkError(_lib.INTERNAL, 'save/restore at W > 1 needs a barrier '
+                                           '(torch.distributed is not initialized)')
+      barrier = dist.barrier
+    return Saver(rank, world, barrier)
+
+  def save(self, prefix, barrier=None):
+    """Every rank writes its shards, rank 0 also the replicated tables and the index; all ranks
+    call this together.  The device work of the current stream is waited for first."""
+    if self.device.type == 'cuda':
+      torch.cuda.current_stream(self.device).synchronize()
+    return self._saver(barrier).save(prefix, self.variables())
+
+  def restore(self, prefix, barrier=None, layout='logical'):
+    """Loads this rank's rows from a checkpoint written at ANY world size (``layout='reference'``:
+    the reference's contiguous slicing instead, see training/saver.py)."""
+    self._saver(barrier).restore(prefix, self.variables(), layout=layout)
+
+  def restore_reference(self, prefix, names=None, barrier=None, layout='logical'):
+    """Loads this rank's rows from a checkpoint the REFERENCE saved (TensorFlow tensor bundle,
+    training/tf_bundle.py), written at any world size.  ``names``: ``{name here: tensor name in
+    the checkpoint}`` for variables the model named differently (default: the TF names of
+    ``variables()``).  layout: see ``Saver.restore_reference``."""
+    self._saver(barrier).restore_reference(prefix, self.variables(), names=names, layout=layout)
+
+  def close(self):
+    if self._sharded is not None:
+      self._sharded.close()
+
+
+class DenseFeatures(_TableLayer):
+  """N embedding columns -> ``[batch, sum of dims]``.
+
+  Args:
+    columns: list of :class:`EmbeddingColumn`.
+    device: the GPU.
+    coll: a ``hybridbackend_amd.distribute.Collective`` for sharded tables, or None.
+    batch_size: local batch size used by the replicate-or-shard rule
+      (``bucket_size <= num_shards or bucket_size <= batch_size`` keeps a table replicated,
+      variables.py:93-104).
+    init: ``init(column, rows, device) -> fp32 [rows, dim]`` for this rank's rows (rows
+      ``rank, rank + W, ..`` of the logical table when sharded); default uniform(-1e-3, 1e-3)
+      (docs/tutorial/ranking/criteo/train.py:84,91).
+    initial_accumulator_value: keep Adagrad accumulators (``optimizer='adagrad'``).
+    optimizer: ``'adam'`` keeps Lazy Adam slots -- zero ``m`` and ``v`` for every table -- for
+      ``backward(optimizer='adam')``; ``adam`` is the :class:`LazyAdam` they step with (TF's
+      defaults when omitted), whose beta powers advance once per stepped backward.  ``'ftrl'`` keeps
+      FTRL slots -- accum filled with ``ftrl.initial_accumulator_value``, zero linear -- for
+      ``backward(optimizer='ftrl')``; ``ftrl`` is the :class:`Ftrl` they step with (TF's defaults
+      when omitted).
+  """
+
+  def __init__(self, columns, device, coll=None, batch_size=0, init=None,
+               initial_accumulator_value=None, optimizer=None, adam=None, ftrl=None):
+    self._init_tables(columns, device, coll, batch_size, init, initial_accumulator_value, optimizer,
+                      adam, ftrl)
     self.offsets, off = [], 0
     for col in self.columns:
       self.offsets.append(off)
@@ -114,17 +201,8 @@ class DenseFeatures:
     # copy of its block; every other column keeps the block's addresses.
     self._staged = {c for c, col in enumerate(self.columns)
                     if col.dimension > 64 and self.offsets[c] % 4 != 0}
-    self._rep = [c for c in range(len(self.columns)) if not self.sharded[c]]
-    self._shd = [c for c in range(len(self.columns)) if self.sharded[c]]
     pick = lambda idx, xs: [xs[c] for c in idx]   # noqa: E731
-
-    def two_slot_kw(idx):   # the drivers' keyword arguments of the two-slot optimizers, tables idx
-      kw = {}
-      for cls in _opt.TWO_SLOT.values():
-        pairs = getattr(self, cls.slot_kw)
-        kw[cls.slot_kw] = None if pairs is None else pick(idx, pairs)
-        kw[cls.name] = getattr(self, cls.name)
-      return kw
+    two_slot_kw = self._two_slot_kw
     self._lookup = self._grad = self._sharded = None
     if self._rep:
       self._lookup = GroupLookup(pick(self._rep, self.weights),
@@ -305,75 +383,134 @@ class DenseFeatures:
       return res, wgrads
     return res
 
-  # ---- checkpoints (hybridbackend/tensorflow/training/saver.py:97-185) ----------------------------
-  def variables(self):
-    """``{name: tensor | ShardedSlice}`` of this rank: the embedding weights (TF naming:
-    ``<key>_embedding/embedding_weights``; a sharded table is the slice ``part_<rank>`` of it,
-    variables.py:112-141) and, when the layer keeps them, the Adagrad slots (``.../Adagrad``) or the
-    Lazy Adam slots (``.../Adam`` = m, ``.../Adam_1`` = v, sharded as the weights) with the 0-d
-    scalars ``beta1_power`` and ``beta2_power``, or the FTRL slots (``.../Ftrl`` = accum,
-    ``.../Ftrl_1`` = linear, sharded as the weights)."""
-    from hybridbackend_amd.training.saver import ShardedSlice
-    world = self.coll.world_size if self.coll is not None else 1
-    rank = self.coll.rank if self.coll is not None else 0
-    per_table = [('', self.weights), ('/Adagrad', self.accums)]
-    extra = {}
-    for cls in _opt.TWO_SLOT.values():
-      pairs = getattr(self, cls.slot_kw)
-      if pairs is not None:
-        per_table += [(cls.tf_suffixes[0], [a for a, _ in pairs]),
-                      (cls.tf_suffixes[1], [b for _, b in pairs])]
-        extra.update(getattr(self, cls.name).tf_variables())
-    out = {}
-    for c, col in enumerate(self.columns):
-      name = f'{col.key}_embedding/embedding_weights'
-      for suffix, tensors in per_table:
-        if tensors is None:
-          continue
-        t = tensors[c]
-        out[name + suffix] = (ShardedSlice(t, col.num_buckets, world, rank)
-                              if self.sharded[c] else t)
-    out.update(extra)
-    return out
-
-  def _saver(self, barrier):
-    from hybridbackend_amd.training.saver import Saver
-    world = self.coll.world_size if self.coll is not None else 1
-    rank = self.coll.rank if self.coll is not None else 0
-    if barrier is None and world > 1:
-      import torch.distributed as dist   # pylint: disable=import-outside-toplevel
-      if not dist.is_initialized():
-        raise _lib.HbkError(_lib.INTERNAL, 'save/restore at W > 1 needs a barrier '
-                                           '(torch.distributed is not initialized)')
-      barrier = dist.barrier
-    return Saver(rank, world, barrier)
-
-  def save(self, prefix, barrier=None):
-    """Every rank writes its shards, rank 0 also the replicated tables and the index; all ranks
-    call this together.  The device work of the current stream is waited for first."""
-    if self.device.type == 'cuda':
-      torch.cuda.current_stream(self.device).synchronize()
-    return self._saver(barrier).save(prefix, self.variables())
-
-  def restore(self, prefix, barrier=None, layout='logical'):
-    """Loads this rank's rows from a checkpoint written at ANY world size (``layout='reference'``:
-    the reference's contiguous slicing instead, see training/saver.py)."""
-    self._saver(barrier).restore(prefix, self.variables(), layout=layout)
-
-  def restore_reference(self, prefix, names=None, barrier=None, layout='logical'):
-    """Loads this rank's rows from a checkpoint the REFERENCE saved (TensorFlow tensor bundle,
-    training/tf_bundle.py), written at any world size.  ``names``: ``{name here: tensor name in
-    the checkpoint}`` for variables the model named differently (default: the TF names of
-    ``variables()``).  layout: see ``Saver.restore_reference``."""
-    self._saver(barrier).restore_reference(prefix, self.variables(), names=names, layout=layout)
-
-  def close(self):
-    if self._sharded is not None:
-      self._sharded.close()
-
 
 def dense_features(features, layer):
   """``hb.keras.layers.dense_features``: the per-column tensors, in column order."""
   m = {}
   layer(features, cols_to_output_tensors=m)
   return [m[c] for c in layer.columns]
+
+
+class SequenceEmbeddingColumn:
+  """``embedding_column(sequence_categorical_column_with_identity/hash_bucket(key, num_buckets),
+  dimension)`` -- or the DIN tutorial's ``transform_categorical_non_pooling``
+  (docs/tutorial/ranking/data.py:195-224): a ragged id list looked up WITHOUT a combiner into
+  ``[batch, max_len, dimension]``.  A sample's first ``max_len`` ids are looked up (``tf.sparse.slice``);
+  ``pad_id`` None: the positions past a sample's length are zero rows that take part in nothing (TF's
+  ``SequenceFeatures``); ``pad_id`` set (``0 <= pad_id < num_buckets``): they look that id up
+  (``tf.sparse.to_dense(default_value=)``) and its row collects their gradient.  ``max_norm`` and
+  ``dedup`` are EmbeddingColumn's.  A column whose table is sharded needs a ``pad_id``."""
+
+  def __init__(self, key, num_buckets, dimension, max_len, pad_id=None, max_norm=None, dedup=False):
+    from hybridbackend_amd.embedding.lookup import max_norm_list
+    from hybridbackend_amd.embedding.sequence import check_sequence_args
+    if num_buckets < 1 or dimension < 1:
+      raise _lib.InvalidArgumentError(
+        _lib.INVALID_ARGUMENT, 'num_buckets and dimension must be >= 1')
+    self.key, self.num_buckets, self.dimension = key, int(num_buckets), int(dimension)
+    _, (self.max_len,), (self.pad_id,) = check_sequence_args(1, [self.num_buckets], max_len, pad_id)
+    self.max_norm = None if max_norm is None else max_norm_list([max_norm], 1)[0]
+    self.dedup = bool(dedup)
+
+
+class SequenceFeatures(_TableLayer):
+  """N sequence columns -> per column ``[batch, max_len, dimension]`` rows and the int32 ``[batch]``
+  lengths (``tf.keras.experimental.SequenceFeatures``; the columns may differ in ``max_len``, so there is
+  no concatenated block).  Arguments, tables, optimizer slots, the replicate-or-shard rule and the
+  checkpoint names are :class:`DenseFeatures`'.
+
+  Replicated tables go through ``SequenceLookup`` / ``SequenceLookupGrad``.  A sharded table (W > 1) is
+  looked up through ``ShardedGroupLookup`` as ``batch * max_len`` ids of one sample each, over the grid
+  ``sequence_row_grid`` builds.  The sharded step bucketizes its ids again, which would carry the ``-1`` of
+  a zero-padded position to row ``num_buckets - 1``: a sharded sequence column therefore requires a
+  ``pad_id`` (zero-padded sequences on sharded tables are not provided)."""
+
+  def __init__(self, columns, device, coll=None, batch_size=0, init=None,
+               initial_accumulator_value=None, optimizer=None, adam=None, ftrl=None):
+    from hybridbackend_amd.embedding.sequence import SequenceLookup, SequenceLookupGrad
+    self._init_tables(columns, device, coll, batch_size, init, initial_accumulator_value, optimizer,
+                      adam, ftrl)
+    for c in self._shd:
+      col = self.columns[c]
+      if col.pad_id is None:
+        raise _lib.InvalidArgumentError(
+          _lib.INVALID_ARGUMENT,
+          f'sequence column {col.key!r}: its table is sharded over {coll.world_size} ranks, and a sharded '
+          'sequence column requires a pad_id (the sharded step bucketizes the id grid again, which would '
+          'turn the -1 of a zero-padded position into a row; zero padding is for replicated tables)')
+    pick = lambda idx, xs: [xs[c] for c in idx]   # noqa: E731
+    attr = lambda idx, name: [getattr(self.columns[c], name) for c in idx]   # noqa: E731
+    self._lookup = self._grad = self._sharded = None
+    if self._rep:
+      self._lookup = SequenceLookup(pick(self._rep, self.weights), attr(self._rep, 'num_buckets'),
+                                    max_lens=attr(self._rep, 'max_len'), pad_ids=attr(self._rep, 'pad_id'),
+                                    max_norms=attr(self._rep, 'max_norm'))
+      self._grad = SequenceLookupGrad(
+        self._lookup, pick(self._rep, self.accums) if self.accums is not None else None,
+        **self._two_slot_kw(self._rep))
+    if self._shd:
+      self._sharded = ShardedGroupLookup(pick(self._shd, self.weights), coll,
+                                         buckets=attr(self._shd, 'num_buckets'), combiners='sum',
+                                         dedup=attr(self._shd, 'dedup'),
+                                         max_norms=attr(self._shd, 'max_norm'),
+                                         accums=(pick(self._shd, self.accums)
+                                                 if self.accums is not None else None),
+                                         **self._two_slot_kw(self._shd))
+
+  def __call__(self, features):
+    """features[key] = ``(values, row_splits)`` (int32/int64 ids, int32 ``[batch + 1]``), or an id vector
+    (one id per sample).  Returns ``(outputs, lengths)``, two lists in column order."""
+    from hybridbackend_amd.embedding.sequence import sequence_row_grid
+    ids, splits, batch = [], [], None
+    for col in self.columns:
+      f = features[col.key]
+      i, s = f if isinstance(f, (tuple, list)) else (f, None)
+      n = i.numel() if s is None else s.numel() - 1
+      if batch is not None and n != batch:
+        raise _lib.InvalidArgumentError(
+          _lib.INVALID_ARGUMENT, f'feature {col.key}: {n} samples, expected {batch}')
+      batch = n
+      ids.append(i)
+      splits.append(s)
+    pick = lambda idx, xs: [xs[c] for c in idx]   # noqa: E731
+    outs, lengths = [None] * len(self.columns), [None] * len(self.columns)
+    if self._rep:
+      o, ln = self._lookup(pick(self._rep, ids), pick(self._rep, splits))
+      for k, c in enumerate(self._rep):
+        outs[c], lengths[c] = o[k], ln[k]
+    if self._shd:
+      cols = pick(self._shd, self.columns)
+      grids, ln = sequence_row_grid(pick(self._shd, ids), pick(self._shd, splits),
+                                    [col.num_buckets for col in cols], [col.max_len for col in cols],
+                                    [col.pad_id for col in cols])
+      o = self._sharded(grids)
+      for k, c in enumerate(self._shd):
+        outs[c] = o[k].view(batch or 0, cols[k].max_len, cols[k].dimension)
+        lengths[c] = ln[k]
+    return outs, lengths
+
+  def backward(self, grads, apply_lr=0.0, optimizer='sgd', emit=True):
+    """grads[c]: the gradient of the last forward's ``outputs[c]``.  Returns per column the
+    ``IndexedSlices`` ``(unique_rows, grad_rows, n_unique)`` of this rank's rows, as
+    ``DenseFeatures.backward`` does and with its rule for the step: the sharded tables are stepped in the
+    same pass, replicated tables are stepped only at W = 1 (at W > 1 their gradients must be aggregated
+    across ranks first; their IndexedSlices are returned)."""
+    _opt.two_slot_class(optimizer, self, "SequenceFeatures(..., optimizer='{name}')")
+    if len(grads) != len(self.columns):
+      raise _lib.InvalidArgumentError(
+        _lib.INVALID_ARGUMENT, f'expected {len(self.columns)} gradients, got {len(grads)}')
+    res = [None] * len(self.columns)
+    if self._rep:
+      rep_lr = apply_lr if (self.coll.world_size if self.coll is not None else 1) <= 1 else 0.0
+      # one optimizer step: the powers advance with the last call that steps (the sharded one)
+      r = self._grad([grads[c] for c in self._rep], apply_lr=rep_lr, optimizer=optimizer,
+                     emit=emit or rep_lr == 0.0, finish=not (self._shd and apply_lr != 0.0))
+      for k, c in enumerate(self._rep):
+        res[c] = r[k]
+    if self._shd:
+      flat = [grads[c].contiguous().view(grads[c].shape[0] * self.columns[c].max_len, self.columns[c].dimension)
+              for c in self._shd]
+      r = self._sharded.backward(flat, apply_lr=apply_lr, optimizer=optimizer, emit=emit)
+      for k, c in enumerate(self._shd):
+        res[c] = r[k]
+    return res

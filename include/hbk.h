@@ -540,6 +540,60 @@ int hbk_group_lookup_bwd_ftrl_clipped(int32_t n_cols, const hbk_lookup_grad_colu
                                       float* const* linear, const hbk_ftrl_t* ftrl, float lr,
                                       void* workspace, size_t workspace_bytes, hbk_stream_t stream);
 
+/* Sequence lookups: a ragged id list WITHOUT a combiner -- the padded [batch, max_len, dim] rows an
+ * attention layer reads (DIN / DIEN / BST): docs/tutorial/ranking/data.py:195-224
+ * (transform_categorical_non_pooling: tf.sparse.slice to max_varlength ids, tf.sparse.to_dense(default_value=),
+ * then the lookup of the [batch, max_varlength] grid), or TF's sequence_categorical_column_* + embedding_column
+ * + SequenceFeatures (zero rows past a sample's length, and a sequence_length vector).
+ * seq is an array of n_cols entries, one per column.  Per column, with B = n_segments, T = seq[c].max_len,
+ * len_b = row_splits[b + 1] - row_splits[b] (1 when row_splits == NULL) and L_b = min(len_b, T), for every
+ * position p = b * T + t of the flattened [B * T] grid:
+ *     t <  L_b            id(p) = ids[row_splits[b] + t]     (the sample's FIRST T ids; later ones are never read)
+ *     t >= L_b, has_pad   id(p) = pad_id
+ *     t >= L_b, no pad    nothing is looked up: out[b, t, :] = 0, row_grid[p] = -1
+ *     g(p)        = floormod(id(p), bucket)   (bucket > 0)
+ *                 = id(p)                     (bucket == 0; id(p) < 0: nothing is looked up, zero row, -1)
+ *     row_grid[p] = g(p)
+ *     out[b, t, :] = table[g(p) / divisor, :]                (rows outside [0, rows) read as zeros)
+ *     lengths[b]  = L_b
+ * cols[c].out is [B, T, dim] fp32; cols[c].out_stride counts the floats between SAMPLES (0 = T * dim, else
+ * >= T * dim); a sample's T rows are contiguous.  The 16-byte / 4-byte chunk rule of out_stride holds over
+ * table, out and that stride.  max_norms (NULL, or a HOST float[n_cols], 0 = not clipped) clips every
+ * looked-up row, pad rows included, as hbk_group_lookup_fwd_clipped does (same formulas and order of s).
+ * lengths and row_grid may be NULL (not wanted: the inference form writes neither).  cols[c].combiner and
+ * hot_rows are ignored.  Refused (HBK_INVALID_ARGUMENT) before any device work: seq == NULL, max_len < 1,
+ * id_weights, out_slots, half_io, n_runs > 0, B * T >= 2^31, a bad max_norm, a row the gather cannot take.
+ * No workspace, no host synchronisation, no device-to-host copy: capturable.  One launch per kind of column
+ * (16-byte or 4-byte chunks, clipped or not).
+ *
+ * The backward needs no entry of its own.  row_grid is bucketized already, so a column of ONE id per
+ * segment with
+ *     ids = row_grid (HBK_INT64), n_ids = n_segments = B * T, row_splits = NULL, bucket = 0,
+ *     the same divisor / rows / table, grad_out = the [B, T, dim] gradient in place, grad_stride = dim
+ * (a gradient with a sample stride other than T * dim: one contiguous copy first) handed to
+ * hbk_group_lookup_bwd* IS the backward of the sequence lookup: a negative id with bucket == 0 maps to no
+ * row, so padding without pad_id and truncated ids (which are not in the grid at all) reach no reduce, no
+ * unique_rows and no optimizer slot, while pad_id's row collects the gradient of every padding position.
+ * The emit form, apply_lr, Adagrad, Lazy Adam, FTRL, the _clipped entries (with the forward's max_norms),
+ * HBK_GRAD_DETERMINISTIC (the order is position order, b-major) and table_pitch apply unchanged.
+ * Detected by the presence of the symbols; the structs above and the version are those of 0.2.0. */
+typedef struct {
+  int32_t max_len;     /* T >= 1 */
+  int32_t has_pad;     /* 0: padding positions are zero rows, -1 in the grid */
+  int64_t pad_id;      /* has_pad != 0: mapped like any id of the column */
+  int32_t* lengths;    /* device [n_segments] or NULL */
+  int64_t* row_grid;   /* device [n_segments * max_len] or NULL (inference) */
+} hbk_sequence_t;
+int hbk_group_lookup_fwd_sequence(int32_t n_cols, const hbk_lookup_column_t* cols,
+                                  const hbk_sequence_t* seq, const float* max_norms,
+                                  hbk_stream_t stream);
+/* row_grid and lengths alone, by the same arithmetic: one thread per position, reads ids and row_splits
+ * only (cols[c].table and cols[c].out may be NULL; dim and out_stride are not looked at).  With
+ * hbk_group_lookup_fwd over the grid (the column of the recipe above, out viewed [B * T, dim]) this is the
+ * two-launch form of the sequence lookup: the same bits as the fused entry. */
+int hbk_sequence_row_grid_n(int32_t n_cols, const hbk_lookup_column_t* cols,
+                            const hbk_sequence_t* seq, hbk_stream_t stream);
+
 /* R10 (sharded form)  d(stitch + combiner): the transpose of the requester-side
  *   `gather(embeddings, shard_index)` + combiner (hbtf/embedding/sharding.py:200; TF emits
  *   SparseSegment*Grad followed by an UnsortedSegmentSum over a permutation):
