@@ -78,6 +78,14 @@ class Sequence(C.Structure):
               ('lengths', C.c_void_p), ('row_grid', C.c_void_p)]
 
 
+class HashColumn(C.Structure):
+  """hbk_hash_column_t"""
+  _fields_ = [('keys_cache', C.c_void_p), ('slab_count', C.c_int64), ('slab_size', C.c_int32),
+              ('keys', C.c_void_p), ('n_keys', C.c_int64), ('slots', C.c_void_p),
+              ('counts', C.c_void_p), ('table', C.c_void_p), ('dim', C.c_int32),
+              ('table_pitch', C.c_int32), ('init_scale', C.c_float), ('seed', C.c_int64)]
+
+
 class ShardedColumn(C.Structure):
   """hbk_sharded_column_t"""
   _fields_ = [('shard', C.c_void_p), ('rows_local', C.c_int64), ('dim', C.c_int32),
@@ -152,6 +160,7 @@ def _declare(l):
     'hbk_cache_lookup_workspace_bytes': (sz, [i64]),
     'hbk_cache_lookup': (C.c_int, [vp, i64, i32, vp, i64, vp, vp, vp, vp, vp, vp, sz, vp]),
     'hbk_murmur3_hash32': (C.c_int, [vp, i64, vp, vp]),
+    'hbk_hash_insert_n': (C.c_int, [i32, vp, i32, vp]),
     'hbk_comm_get_id': (C.c_int, [vp]),
     'hbk_comm_rccl_versions': (C.c_int, [vp, vp]),
     'hbk_comm_create': (C.c_int, [vp, vp, i32, i32, i32]),

@@ -1,0 +1,304 @@
+// Hash-keyed tables (hbk_hash_insert_n): the WRITER of the slab key cache that probe.hip reads.  Raw
+// int64 ids -> row numbers of a fixed-capacity table by find-or-insert, N columns per launch:
+//   slab = murmur3_hash32(key) % slab_count
+//   the key is in the slab                  -> its slot
+//   else the slab has EMPTY slots           -> the FIRST of them is claimed by a 64-bit agent-scope CAS
+//   else (the slab is full)                 -> the next slab, wrapping; slab_count full slabs: -1
+// so a key never sits behind a slab that still has an EMPTY slot, which is all cache_probe_kernel needs
+// to find it.  The reference places missed keys at where(cache_keys == EMPTY)[:n_miss]
+// (hbtf/embedding/service.py:212-218): not where its own probe looks.
+//
+// Lane mapping as cache_probe_kernel: a group of G = pow2(slab_size) adjacent lanes owns one key and
+// reads one slab per step; kKeys keys per group with all first reads in flight at once.
+//
+// Memory rules (per-XCD L2s are not coherent with each other and a CU's L1 is never refreshed by
+// another CU's stores): inside the inserting kernel EVERY read of the key array is a relaxed agent-scope
+// 8-byte atomic load and EVERY write the CAS; no fences, no plain stores to the key array.  A plain load
+// could be served from a stale L1 line and make the retry see the same EMPTY slot again.
+//
+// Bounded loops: slots only ever go EMPTY -> key, so a lost CAS means a slot of the slab was filled by
+// somebody else: at most slab_size lost CASes per slab, at most slab_count slabs per key.  Both bounds
+// are written out (`tries`, `probed`); nothing spins on another workgroup's progress.
+//
+// The group whose CAS returned EMPTY is the key's ONE inserter and writes the new row's initial values
+// itself: a function of (key, seed, j) alone (include/hbk.h), never of the slot the key happened to get.
+#include <math.h>
+
+#include "common.h"
+
+namespace hbk {
+namespace {
+
+__host__ __device__ inline uint32_t rotl32_(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
+
+// murmur3_hash32<int64, seed 0> as probe.hip (hybridbackend/common/murmur3.cu.h:32-77): the placement
+// must be the probe's, bit for bit (tests compare with hbk_cache_probe and the C oracle)
+__host__ __device__ inline uint32_t murmur3_i64(int64_t key) {
+  const uint32_t c1 = 0xcc9e2d51u, c2 = 0x1b873593u;
+  uint32_t h1 = 0;
+  const uint32_t blocks[2] = {(uint32_t)((uint64_t)key & 0xffffffffu), (uint32_t)((uint64_t)key >> 32)};
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    uint32_t k1 = blocks[i];
+    k1 *= c1;
+    k1 = rotl32_(k1, 15);
+    k1 *= c2;
+    h1 ^= k1;
+    h1 = rotl32_(h1, 13);
+    h1 = h1 * 5 + 0xe6546b64u;
+  }
+  h1 ^= 8u;
+  h1 ^= h1 >> 16;
+  h1 *= 0x85ebca6bu;
+  h1 ^= h1 >> 13;
+  h1 *= 0xc2b2ae35u;
+  h1 ^= h1 >> 16;
+  return h1;
+}
+
+constexpr int kBlock = 256;
+constexpr int kWavesPerBlock = kBlock / kWave;
+constexpr int kMaxColsPerLaunch = 64;   // one ballot finds the column; HashArgs travels by value
+constexpr int kKeys = 8;                // keys per lane group, first reads all in flight (probe.hip)
+constexpr long long kEmptyKey = (long long)0x8000000000000000ull;
+
+struct HashCol {
+  long long* cache;
+  const int64_t* keys;
+  int64_t* slots;
+  int32_t* counts;      // {n_inserted, n_failed} or NULL
+  float* table;         // NULL: no row is written
+  int64_t n_keys;
+  FastDiv slab_div;     // .d = slab_count
+  int64_t pitch;        // floats between rows
+  uint64_t seed;
+  float init_scale;
+  int32_t slab_size;
+  int32_t dim;
+  int32_t group_log2;
+};
+
+struct HashArgs {
+  int32_t n_cols;
+  int32_t tile_start[kMaxColsPerLaunch + 1];
+  HashCol col[kMaxColsPerLaunch];
+};
+static_assert(sizeof(HashArgs) <= 24576, "kernarg budget");
+
+// last column whose first tile is <= b: one entry per lane, one ballot (lookup_fwd.hip)
+__device__ inline int find_column(const HashArgs& a, int b) {
+  const int lane = (int)threadIdx.x & (kWave - 1);
+  const int t0 = lane < a.n_cols ? a.tile_start[lane] : 0x7fffffff;
+  const int ci = (int)__builtin_popcountll(__ballot(t0 <= b)) - 1;
+  return __builtin_amdgcn_readfirstlane(ci);
+}
+
+// float j of the initial row of `key` (include/hbk.h): exact in fp32 up to the final multiply
+__host__ __device__ inline float init_value(int64_t key, uint64_t seed, int j, float scale) {
+  const uint64_t mix = (seed + (uint64_t)j + 1ull) * 0x9E3779B97F4A7C15ull;
+  const uint32_t r = murmur3_i64(key ^ (int64_t)mix);
+  const float unit = (float)(r >> 8) * 1.1920928955078125e-07f - 1.0f;   // 2^-23: [-1, 1)
+  return unit * scale;
+}
+
+template <bool INSERT>
+__device__ inline long long read_slot(const long long* p) {
+  if (INSERT) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return *p;
+}
+
+template <bool INSERT>
+__global__ __launch_bounds__(kBlock) void hash_insert_kernel(const HashArgs a) {
+  const int b = (int)blockIdx.x;
+  const int ci = find_column(a, b);
+  const HashCol& c = a.col[ci];
+  const int lane = lane_id();
+  const int wave = (int)(threadIdx.x >> 6);
+  const int group_log2 = c.group_log2;
+  const int gsize = 1 << group_log2;
+  const int sub = lane & (gsize - 1);
+  const int grp = lane >> group_log2;
+  const int gbase = grp << group_log2;
+  const int groups_per_wave = kWave >> group_log2;
+  const int64_t wave_in_col = (int64_t)(b - a.tile_start[ci]) * kWavesPerBlock + wave;
+  const int64_t first_key = wave_in_col * groups_per_wave * kKeys;
+  const int64_t n_keys = c.n_keys;
+  if (first_key >= n_keys) return;   // (wave-uniform)
+  const int64_t i0 = first_key + grp;   // + u * groups_per_wave
+  const unsigned long long group_mask = (gsize == 64 ? ~0ull : ((1ull << gsize) - 1ull)) << gbase;
+  const int32_t slab_size = c.slab_size;
+  const int64_t slab_count = (int64_t)c.slab_div.d;
+  const bool in_slab = sub < slab_size;
+  long long* const cache = c.cache;
+
+  long long key[kKeys], read_key[kKeys];
+  int64_t slab[kKeys];
+#pragma unroll
+  for (int u = 0; u < kKeys; ++u) {
+    const int64_t i = i0 + (int64_t)u * groups_per_wave;
+    key[u] = i < n_keys ? (long long)c.keys[i] : kEmptyKey;
+  }
+#pragma unroll
+  for (int u = 0; u < kKeys; ++u) {
+    slab[u] = (int64_t)fastmod((uint64_t)murmur3_i64(key[u]), c.slab_div);
+    read_key[u] = 0;
+    // (EMPTY is never looked for: the lanes past n_keys hold it too)
+    if (key[u] != kEmptyKey && in_slab) read_key[u] = read_slot<INSERT>(cache + slab[u] * slab_size + sub);
+  }
+  int32_t n_inserted = 0, n_failed = 0;
+#pragma unroll
+  for (int u = 0; u < kKeys; ++u) {
+    const int64_t i = i0 + (int64_t)u * groups_per_wave;
+    bool active = key[u] != kEmptyKey;
+    bool won = false;
+    int64_t result = -1;
+    int64_t probed = 0;     // slabs found full: < slab_count
+    int32_t tries = 0;      // CASes lost in this slab: <= slab_size (each one a slot somebody else filled)
+    long long rk = read_key[u];
+    for (;;) {
+      const bool live = active && in_slab;
+      const unsigned long long match = __ballot(live && rk == key[u]) & group_mask;
+      const unsigned long long empty = __ballot(live && rk == kEmptyKey) & group_mask;
+      bool advance = false, cas = false;
+      int first = 0;
+      if (active) {
+        if (match != 0ull) {
+          result = slab[u] * slab_size + (__builtin_ctzll(match) - gbase);
+          active = false;
+        } else if (empty != 0ull) {
+          first = __builtin_ctzll(empty) - gbase;
+          if (INSERT) cas = true; else active = false;
+        } else {
+          advance = true;
+        }
+      }
+      if (INSERT) {
+        // (every lane of the wave takes the shuffle; the CAS is the first EMPTY slot's lane alone)
+        long long old = 0;
+        if (cas && sub == first) {
+          long long expected = kEmptyKey;
+          __hip_atomic_compare_exchange_strong(cache + slab[u] * slab_size + first, &expected, key[u],
+                                               __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          old = expected;   // what the slot held: EMPTY when the exchange was made
+        }
+        old = __shfl(old, gbase + first, kWave);
+        if (cas) {
+          if (old == kEmptyKey || old == key[u]) {
+            // inserted, or a concurrent duplicate of the key won this slot: a hit on it
+            won = old == kEmptyKey;
+            result = slab[u] * slab_size + first;
+            active = false;
+          } else if (++tries > slab_size) {
+            advance = true;   // (unreachable while slots only go EMPTY -> key: the bound, written out)
+          }
+          // else: re-read the SAME slab -- a match first, then its first EMPTY slot
+        }
+      }
+      if (advance) {
+        ++probed;
+        tries = 0;
+        slab[u] = slab[u] + 1 == slab_count ? 0 : slab[u] + 1;
+        if (probed >= slab_count) active = false;
+      }
+      if (!__any(active)) break;
+      rk = 0;
+      if (active && in_slab) rk = read_slot<INSERT>(cache + slab[u] * slab_size + sub);
+    }
+    if (INSERT && won && c.table != nullptr) {
+      float* row = c.table + result * c.pitch;
+      for (int j = sub; j < c.dim; j += gsize) {
+        row[j] = c.init_scale == 0.0f ? 0.0f : init_value(key[u], c.seed, j, c.init_scale);
+      }
+    }
+    if (i < n_keys && sub == 0) {
+      c.slots[i] = result;
+      n_inserted += won ? 1 : 0;
+      n_failed += result < 0 ? 1 : 0;
+    }
+  }
+  if (c.counts != nullptr) {
+    // one atomic per wave and counter: the lanes' counts summed across the wave
+#pragma unroll
+    for (int off = 1; off < kWave; off <<= 1) {
+      n_inserted += __shfl_xor(n_inserted, off, kWave);
+      n_failed += __shfl_xor(n_failed, off, kWave);
+    }
+    if (lane == 0 && n_inserted != 0) atomicAdd(c.counts, n_inserted);
+    if (lane == 0 && n_failed != 0) atomicAdd(c.counts + 1, n_failed);
+  }
+}
+
+}  // namespace
+}  // namespace hbk
+
+extern "C" int hbk_hash_insert_n(int32_t n_cols, const hbk_hash_column_t* cols, int32_t insert,
+                                 hbk_stream_t stream) {
+  using namespace hbk;
+  const char* who = "hash_insert_n";
+  HBK_REQUIRE(n_cols >= 0, "%s: n_cols must be >= 0, got %d", who, n_cols);
+  HBK_REQUIRE(n_cols == 0 || cols != nullptr, "%s: cols is NULL", who);
+  for (int32_t c = 0; c < n_cols; ++c) {
+    const hbk_hash_column_t& h = cols[c];
+    HBK_REQUIRE(h.slab_size >= 1 && h.slab_size <= kWave, "%s: column %d: slab_size must be in [1, 64], got %d",
+                who, c, h.slab_size);
+    HBK_REQUIRE(h.slab_count >= 1, "%s: column %d: slab_count must be >= 1, got %lld", who, c,
+                (long long)h.slab_count);
+    HBK_REQUIRE(h.slab_count <= ((1ll << 62) / kWave), "%s: column %d: slab_count %lld is out of range", who, c,
+                (long long)h.slab_count);
+    HBK_REQUIRE(h.n_keys >= 0 && h.n_keys < (1ll << 31), "%s: column %d: n_keys must be in [0, 2^31), got %lld",
+                who, c, (long long)h.n_keys);
+    HBK_REQUIRE(h.n_keys == 0 || (h.keys_cache != nullptr && h.keys != nullptr && h.slots != nullptr),
+                "%s: column %d: NULL buffer (keys_cache, keys and slots are needed with n_keys > 0)", who, c);
+    HBK_REQUIRE(((uintptr_t)h.keys_cache & 7) == 0, "%s: column %d: keys_cache must be 8-byte aligned", who, c);
+    if (h.table != nullptr) {
+      HBK_REQUIRE(h.dim >= 1, "%s: column %d: dim must be >= 1 with a table, got %d", who, c, h.dim);
+      HBK_REQUIRE(h.table_pitch == 0 || h.table_pitch >= h.dim,
+                  "%s: column %d: table_pitch %d is smaller than dim %d", who, c, h.table_pitch, h.dim);
+    }
+    HBK_REQUIRE(h.init_scale >= 0.0f && h.init_scale <= 3.402823466e38f,
+                "%s: column %d: init_scale must be finite and >= 0, got %g", who, c, (double)h.init_scale);
+  }
+  int32_t c0 = 0;
+  while (c0 < n_cols) {
+    HashArgs args;
+    int32_t k = 0;
+    int64_t tiles = 0;
+    args.tile_start[0] = 0;
+    while (c0 < n_cols && k < kMaxColsPerLaunch) {
+      const hbk_hash_column_t& h = cols[c0++];
+      if (h.n_keys == 0) continue;
+      HashCol& d = args.col[k];
+      d.cache = reinterpret_cast<long long*>(h.keys_cache);
+      d.keys = h.keys;
+      d.slots = h.slots;
+      d.counts = h.counts;
+      d.table = insert != 0 ? h.table : nullptr;
+      d.n_keys = h.n_keys;
+      d.slab_div = make_fastdiv((uint64_t)h.slab_count);
+      d.slab_div.d = (uint64_t)h.slab_count;
+      d.pitch = h.table_pitch > 0 ? h.table_pitch : h.dim;
+      d.seed = (uint64_t)h.seed;
+      d.init_scale = h.init_scale;
+      d.slab_size = h.slab_size;
+      d.dim = h.dim;
+      d.group_log2 = 0;
+      while ((1 << d.group_log2) < h.slab_size) ++d.group_log2;
+      const int64_t keys_per_block = (int64_t)(kBlock >> d.group_log2) * kKeys;
+      tiles += (h.n_keys + keys_per_block - 1) / keys_per_block;
+      HBK_REQUIRE(tiles < (1ll << 31), "%s: grid too large", who);
+      ++k;
+      args.tile_start[k] = (int32_t)tiles;
+    }
+    if (k == 0) continue;
+    args.n_cols = k;
+    if (insert != 0) {
+      hipLaunchKernelGGL(hash_insert_kernel<true>, dim3((unsigned)tiles), dim3(kBlock), 0, as_stream(stream),
+                         args);
+    } else {
+      hipLaunchKernelGGL(hash_insert_kernel<false>, dim3((unsigned)tiles), dim3(kBlock), 0, as_stream(stream),
+                         args);
+    }
+    HBK_HIP_OK(hipGetLastError());
+  }
+  return HBK_OK;
+}

@@ -655,6 +655,67 @@ int hbk_cache_lookup(const int64_t* keys_cache, int64_t slab_count, int32_t slab
 int hbk_murmur3_hash32(const int64_t* keys, int64_t n_keys, uint32_t* out,
                        hbk_stream_t stream);
 
+/* Hash-keyed tables: device find-or-insert, the WRITER of the slab key cache hbk_cache_probe reads.  Raw
+ * int64 ids become row numbers of a fixed-capacity table (capacity = slab_count * slab_size rows), so two
+ * ids never share a row as they do under floormod(id, num_buckets) (DeepRec's EmbeddingVariable; the
+ * reference's EmbeddingService in miniature, whose own placement -- where(cache_keys == EMPTY)[:n_miss],
+ * hbtf/embedding/service.py:212-218 -- is not where its probe looks).  One launch serves all
+ * columns (64 per launch).
+ *
+ * Placement rule, per key (EMPTY = INT64_MIN; keys_cache starts all EMPTY):
+ *     slab = murmur3_hash32(key) % slab_count
+ *     the slab holds the key                 -> slots[i] = slab * slab_size + its slot
+ *     else the slab has EMPTY slots          -> the FIRST of them is claimed (64-bit agent-scope
+ *                                               compare-and-swap EMPTY -> key); a claim lost to the same key
+ *                                               is a hit on that slot, a claim lost to another key reads the
+ *                                               same slab again (match first, then its first EMPTY slot)
+ *     else (the slab is full)                -> the next slab, wrapping; after slab_count slabs slots[i] = -1
+ * Slots only ever go EMPTY -> key, so a key never sits behind a slab that still has an EMPTY slot: every key
+ * this entry placed is found by hbk_cache_probe / hbk_cache_lookup on the same array, and by insert = 0.
+ * key == EMPTY is never stored and gives -1.  Retries are bounded by slab_size per slab and slab_count slabs
+ * per key; no workgroup waits for another.
+ *
+ * Row initialisation.  The call that inserts a key writes its row, table[slot * pitch + j] for j < dim:
+ *     r      = murmur3_hash32(key ^ (int64)((uint64)(seed + j + 1) * 0x9E3779B97F4A7C15))
+ *     row[j] = ((float)(r >> 8) * 2^-23 - 1.0f) * init_scale          (uniform in [-init_scale, init_scale))
+ * exact in fp32 up to the final multiply; init_scale == 0 stores +0.0f; table == NULL writes nothing; rows of
+ * keys already present are not touched.  A row's start depends on its key, never on the slot it got.
+ *
+ * Counters.  counts (device int32[2] or NULL; the CALLER zeroes it, calls add to it): {n_inserted, n_failed}.
+ * n_inserted counts keys stored by this call (a key repeated in the call counts once); n_failed counts key
+ * OCCURRENCES whose slot is -1.  One atomic per wave and counter.
+ *
+ * Reproducible between runs: every key's row contents; which keys are stored when no key fails; the SET of
+ * keys of every slab when no slab overflows into its neighbour.  NOT reproducible: slot numbers (the order
+ * inside a slab, and which keys spill once a slab is full, depend on which workgroup claims first), hence
+ * not which keys fail in a table that fills up.
+ *
+ * insert == 0: a pure find -- no compare-and-swap, no row is written, plain loads; n_failed counts the
+ * misses.  The results are hbk_cache_probe's (except key == EMPTY: -1 here), for N columns in one launch.
+ *
+ * Refused (HBK_INVALID_ARGUMENT) before any device work: slab_size outside [1, 64], slab_count < 1, NULL
+ * keys_cache / keys / slots with n_keys > 0, n_keys outside [0, 2^31), dim < 1 with a table, table_pitch
+ * non-zero and < dim, init_scale negative, NaN or infinite.  No workspace, no host synchronisation:
+ * capturable.  The row numbers feed hbk_group_lookup_fwd* / hbk_group_lookup_bwd* as int64 ids with
+ * bucket = 0 (a -1 looks nothing up and reaches no gradient row).  Detected by the presence of the symbol;
+ * the structs above and the version are those of 0.2.0. */
+typedef struct {
+  int64_t* keys_cache;    /* device [slab_count * slab_size], 8-byte aligned */
+  int64_t slab_count;
+  int32_t slab_size;      /* 1..64 */
+  const int64_t* keys;    /* device [n_keys] */
+  int64_t n_keys;
+  int64_t* slots;         /* device [n_keys]: row number or -1 */
+  int32_t* counts;        /* device int32[2] {n_inserted, n_failed}, added to; or NULL */
+  float* table;           /* device, slab_count * slab_size rows; NULL: new rows are not initialised */
+  int32_t dim;
+  int32_t table_pitch;    /* floats between rows; 0 = dim */
+  float init_scale;       /* finite, >= 0 */
+  int64_t seed;
+} hbk_hash_column_t;
+int hbk_hash_insert_n(int32_t n_cols, const hbk_hash_column_t* cols, int32_t insert,
+                      hbk_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * Communicator lifecycle: HbGetNcclId / HbCreateNcclCollective /
  * HbIsNcclCollectiveInitialized / async-error polling.
