@@ -86,6 +86,26 @@ class HashColumn(C.Structure):
               ('table_pitch', C.c_int32), ('init_scale', C.c_float), ('seed', C.c_int64)]
 
 
+class HashExpiry(C.Structure):
+  """hbk_hash_expiry_t"""
+  _fields_ = [('last_seen', C.c_void_p), ('freq', C.c_void_p), ('step', C.c_void_p), ('stats', C.c_void_p)]
+
+
+HASH_MAX_FILLS = 4
+
+
+class HashFill(C.Structure):
+  """hbk_hash_fill_t"""
+  _fields_ = [('base', C.c_void_p), ('pitch', C.c_int32), ('dim', C.c_int32), ('value', C.c_float)]
+
+
+class HashEvictColumn(C.Structure):
+  """hbk_hash_evict_column_t"""
+  _fields_ = [('keys_cache', C.c_void_p), ('slab_count', C.c_int64), ('slab_size', C.c_int32),
+              ('exp', HashExpiry), ('steps_to_live', C.c_int64), ('keep_freq', C.c_int32),
+              ('n_fills', C.c_int32), ('fills', HashFill * HASH_MAX_FILLS)]
+
+
 class ShardedColumn(C.Structure):
   """hbk_sharded_column_t"""
   _fields_ = [('shard', C.c_void_p), ('rows_local', C.c_int64), ('dim', C.c_int32),
@@ -161,6 +181,8 @@ def _declare(l):
     'hbk_cache_lookup': (C.c_int, [vp, i64, i32, vp, i64, vp, vp, vp, vp, vp, vp, sz, vp]),
     'hbk_murmur3_hash32': (C.c_int, [vp, i64, vp, vp]),
     'hbk_hash_insert_n': (C.c_int, [i32, vp, i32, vp]),
+    'hbk_hash_insert_expiring_n': (C.c_int, [i32, vp, vp, i32, vp]),
+    'hbk_hash_evict_n': (C.c_int, [i32, vp, vp]),
     'hbk_comm_get_id': (C.c_int, [vp]),
     'hbk_comm_rccl_versions': (C.c_int, [vp, vp]),
     'hbk_comm_create': (C.c_int, [vp, vp, i32, i32, i32]),

@@ -1,0 +1,196 @@
+// Expiring hash tables (hbk_hash_evict_n): the eviction sweep.  One streaming pass over the slots of N
+// tables per launch.  A slot whose key is neither EMPTY nor TOMBSTONE is evicted iff
+//     steps_to_live > 0  and  (int64)*step - last_seen[slot] >= steps_to_live      (idle long enough)
+//     and (keep_freq == 0  or  freq[slot] < keep_freq)                             (not seen often enough to stay)
+// An evicted slot's key becomes TOMBSTONE (never EMPTY: hash_insert.hip, the probe's invariant), its freq and
+// last_seen become 0 and its row of every companion array named in the call (the optimizer slots) is filled
+// with that array's value; the padding between dim and pitch is not written.  The embedding row is left: the
+// next key to take the slot writes it.
+//
+// The sweep is a kernel of its own, stream-ordered against the translate launches and never beside one, so
+// the key array is read and written with plain vector loads and stores: nobody else touches it meanwhile, and
+// a kernel boundary makes the stores visible to the next launch.
+//
+// A wave decides 64 consecutive slots with coalesced loads (16 bytes per slot), ballots the evicted ones,
+// gathers their lane numbers into the low lanes with one permute, and fills their companion rows with all
+// lanes: 64 / pow2(dim) rows per pass.  n_evicted: one atomic per wave.
+#include <math.h>
+
+#include "common.h"
+
+namespace hbk {
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kWavesPerBlock = kBlock / kWave;
+constexpr int kChunks = 4;                              // 64-slot chunks per wave
+constexpr int kSlotsPerBlock = kBlock * kChunks;
+constexpr int kMaxColsPerLaunch = 32;                   // EvictArgs travels by value
+constexpr long long kEmptyKey = (long long)0x8000000000000000ull;
+constexpr long long kTombstoneKey = kEmptyKey + 1;
+
+struct Fill {
+  float* base;
+  int64_t pitch;        // floats between rows
+  int32_t dim;
+  int32_t lanes_log2;   // lanes per row of a pass: pow2(dim), at most 64
+  float value;
+  int32_t pad_;
+};
+
+struct EvictCol {
+  long long* keys;
+  int32_t* last_seen;
+  int32_t* freq;
+  const int32_t* step;
+  int32_t* stats;         // {n_evicted, n_reused} or NULL
+  int64_t capacity;
+  int64_t steps_to_live;
+  int32_t keep_freq;
+  int32_t n_fills;
+  Fill fill[HBK_HASH_MAX_FILLS];
+};
+
+struct EvictArgs {
+  int32_t n_cols;
+  int32_t tile_start[kMaxColsPerLaunch + 1];
+  EvictCol col[kMaxColsPerLaunch];
+};
+static_assert(sizeof(EvictArgs) <= 24576, "kernarg budget");
+
+__global__ __launch_bounds__(kBlock) void hash_evict_kernel(const EvictArgs a) {
+  const int b = (int)blockIdx.x;
+  const int lane = lane_id();
+  const int wave = (int)(threadIdx.x >> 6);
+  // last column whose first tile is <= b: one entry per lane, one ballot (hash_insert.hip)
+  const int t0 = lane < a.n_cols ? a.tile_start[lane] : 0x7fffffff;
+  const int ci = __builtin_amdgcn_readfirstlane((int)__builtin_popcountll(__ballot(t0 <= b)) - 1);
+  const EvictCol& c = a.col[ci];
+  const int64_t capacity = c.capacity;
+  const int64_t ttl = c.steps_to_live;
+  const int32_t keep_freq = c.keep_freq;
+  const int64_t block_first = (int64_t)(b - a.tile_start[ci]) * kSlotsPerBlock;
+  if (ttl <= 0) return;   // nothing expires (the host launches nothing for such a column; the rule, written out)
+  const int64_t now = (int64_t)*c.step;
+  int32_t n_evicted = 0;
+#pragma unroll
+  for (int u = 0; u < kChunks; ++u) {
+    const int64_t first = block_first + (int64_t)(u * kWavesPerBlock + wave) * kWave;
+    if (first >= capacity) break;   // (wave-uniform)
+    const int64_t slot = first + lane;
+    bool evict = false;
+    if (slot < capacity) {
+      const long long key = c.keys[slot];
+      const int32_t seen = c.last_seen[slot];
+      const int32_t freq = c.freq[slot];
+      evict = key != kEmptyKey && key != kTombstoneKey && now - (int64_t)seen >= ttl &&
+              (keep_freq == 0 || freq < keep_freq);
+    }
+    const unsigned long long mask = __ballot(evict);
+    if (mask == 0ull) continue;   // (wave-uniform)
+    const int n = (int)__builtin_popcountll(mask);
+    n_evicted += n;
+    if (evict) {
+      c.keys[slot] = kTombstoneKey;
+      c.last_seen[slot] = 0;
+      c.freq[slot] = 0;
+    }
+    if (c.n_fills == 0) continue;
+    // lane r < n receives the lane number of the r-th evicted slot; the other lanes take what is left,
+    // so the permute is a bijection of the wave
+    const int below = rank_below(mask);
+    const int dest = evict ? below : n + lane - below;
+    const int evicted_lane = __builtin_amdgcn_ds_permute(dest << 2, lane);
+    for (int f = 0; f < c.n_fills; ++f) {
+      const Fill& fl = c.fill[f];
+      const int rows_log2 = 6 - fl.lanes_log2;                 // rows per pass
+      const int j0 = lane & ((1 << fl.lanes_log2) - 1);
+      for (int r0 = 0; r0 < n; r0 += 1 << rows_log2) {
+        const int r = r0 + (lane >> fl.lanes_log2);
+        const int src = __shfl(evicted_lane, r & (kWave - 1), kWave);   // (every lane takes the shuffle)
+        if (r < n) {
+          float* row = fl.base + (first + src) * fl.pitch;
+          for (int j = j0; j < fl.dim; j += 1 << fl.lanes_log2) row[j] = fl.value;
+        }
+      }
+    }
+  }
+  if (c.stats != nullptr && lane == 0 && n_evicted != 0) atomicAdd(c.stats, n_evicted);
+}
+
+}  // namespace
+}  // namespace hbk
+
+extern "C" int hbk_hash_evict_n(int32_t n_cols, const hbk_hash_evict_column_t* cols, hbk_stream_t stream) {
+  using namespace hbk;
+  const char* who = "hash_evict_n";
+  HBK_REQUIRE(n_cols >= 0, "%s: n_cols must be >= 0, got %d", who, n_cols);
+  HBK_REQUIRE(n_cols == 0 || cols != nullptr, "%s: cols is NULL", who);
+  for (int32_t c = 0; c < n_cols; ++c) {
+    const hbk_hash_evict_column_t& h = cols[c];
+    HBK_REQUIRE(h.slab_size >= 1 && h.slab_size <= kWave, "%s: column %d: slab_size must be in [1, 64], got %d",
+                who, c, h.slab_size);
+    HBK_REQUIRE(h.slab_count >= 1, "%s: column %d: slab_count must be >= 1, got %lld", who, c,
+                (long long)h.slab_count);
+    HBK_REQUIRE(h.slab_count <= ((1ll << 62) / kWave), "%s: column %d: slab_count %lld is out of range", who, c,
+                (long long)h.slab_count);
+    HBK_REQUIRE(h.keys_cache != nullptr, "%s: column %d: keys_cache is NULL", who, c);
+    HBK_REQUIRE(((uintptr_t)h.keys_cache & 7) == 0, "%s: column %d: keys_cache must be 8-byte aligned", who, c);
+    HBK_REQUIRE(h.exp.last_seen != nullptr && h.exp.freq != nullptr && h.exp.step != nullptr,
+                "%s: column %d: NULL expiry buffer (last_seen, freq and step are needed)", who, c);
+    HBK_REQUIRE(h.steps_to_live >= 0, "%s: column %d: steps_to_live must be >= 0, got %lld", who, c,
+                (long long)h.steps_to_live);
+    HBK_REQUIRE(h.keep_freq >= 0, "%s: column %d: keep_freq must be >= 0, got %d", who, c, h.keep_freq);
+    HBK_REQUIRE(h.n_fills >= 0 && h.n_fills <= HBK_HASH_MAX_FILLS, "%s: column %d: n_fills must be in [0, %d], got %d",
+                who, c, HBK_HASH_MAX_FILLS, h.n_fills);
+    for (int32_t f = 0; f < h.n_fills; ++f) {
+      const hbk_hash_fill_t& fl = h.fills[f];
+      HBK_REQUIRE(fl.base != nullptr, "%s: column %d: fill %d: base is NULL", who, c, f);
+      HBK_REQUIRE(fl.dim >= 1, "%s: column %d: fill %d: dim must be >= 1, got %d", who, c, f, fl.dim);
+      HBK_REQUIRE(fl.pitch == 0 || fl.pitch >= fl.dim, "%s: column %d: fill %d: pitch %d is smaller than dim %d",
+                  who, c, f, fl.pitch, fl.dim);
+      HBK_REQUIRE(isfinite(fl.value), "%s: column %d: fill %d: value must be finite, got %g", who, c, f,
+                  (double)fl.value);
+    }
+  }
+  int32_t c0 = 0;
+  while (c0 < n_cols) {
+    EvictArgs args;
+    int32_t k = 0;
+    int64_t tiles = 0;
+    args.tile_start[0] = 0;
+    while (c0 < n_cols && k < kMaxColsPerLaunch) {
+      const hbk_hash_evict_column_t& h = cols[c0++];
+      if (h.steps_to_live == 0) continue;   // nothing expires
+      EvictCol& d = args.col[k];
+      d.keys = reinterpret_cast<long long*>(h.keys_cache);
+      d.last_seen = h.exp.last_seen;
+      d.freq = h.exp.freq;
+      d.step = h.exp.step;
+      d.stats = h.exp.stats;
+      d.capacity = h.slab_count * h.slab_size;
+      d.steps_to_live = h.steps_to_live;
+      d.keep_freq = h.keep_freq;
+      d.n_fills = h.n_fills;
+      for (int32_t f = 0; f < h.n_fills; ++f) {
+        Fill& fl = d.fill[f];
+        fl.base = h.fills[f].base;
+        fl.pitch = h.fills[f].pitch > 0 ? h.fills[f].pitch : h.fills[f].dim;
+        fl.dim = h.fills[f].dim;
+        fl.lanes_log2 = 0;
+        while (fl.lanes_log2 < 6 && (1 << fl.lanes_log2) < fl.dim) ++fl.lanes_log2;
+        fl.value = h.fills[f].value;
+        fl.pad_ = 0;
+      }
+      tiles += (d.capacity + kSlotsPerBlock - 1) / kSlotsPerBlock;
+      HBK_REQUIRE(tiles < (1ll << 31), "%s: grid too large", who);
+      ++k;
+      args.tile_start[k] = (int32_t)tiles;
+    }
+    if (k == 0) continue;
+    args.n_cols = k;
+    hipLaunchKernelGGL(hash_evict_kernel, dim3((unsigned)tiles), dim3(kBlock), 0, as_stream(stream), args);
+    HBK_HIP_OK(hipGetLastError());
+  }
+  return HBK_OK;
+}

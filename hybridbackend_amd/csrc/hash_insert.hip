@@ -22,6 +22,39 @@
 //
 // The group whose CAS returned EMPTY is the key's ONE inserter and writes the new row's initial values
 // itself: a function of (key, seed, j) alone (include/hbk.h), never of the slot the key happened to get.
+//
+// Expiring tables (hbk_hash_insert_expiring_n, hash_insert_expiring_kernel below; the kernel above is not
+// touched by them).  A second sentinel, TOMBSTONE = INT64_MIN + 1, marks a slot the eviction sweep
+// (hash_evict.hip) took back: key -> TOMBSTONE, never -> EMPTY, so a slab without an EMPTY slot stays without
+// one and every live key is still found by the probe's walk.  The insert reuses such slots:
+//   walk the slabs from the home slab, wrapping, at most slab_count of them:
+//       the slab holds the key            -> hit
+//       remember the FIRST TOMBSTONE slot of the walk (slab order, then slot order)
+//       the slab has an EMPTY slot        -> stop walking
+//   claim the remembered TOMBSTONE (CAS TOMBSTONE -> key) if there is one, else the stopping slab's first
+//   EMPTY slot (CAS EMPTY -> key), else -1; a claim lost to the same key is a hit on that slot, a claim lost
+//   to another key starts the walk again at the home slab.
+// The walk goes on PAST a tombstone to the stopping slab before anything is claimed: a key that spilled into
+// slab h+1 while h was full is still there after a slot of h was evicted, and claiming the tombstone in h at
+// first sight would store that key twice.
+//
+// One key, concurrent inserters, one slot.  Inside this kernel slots only go free -> key (free = EMPTY or
+// TOMBSTONE; the sweep is a kernel of its own, stream-ordered against every translate launch, never beside
+// one) and every read is an agent-scope atomic load.  A CAS that succeeds on slot s therefore takes the first
+// free slot of the key's walk at that moment: every slot before s was read as filled and stays filled.  A
+// second inserter of the same key whose walk covers s reads s either as free -- then s is its own first free
+// slot or behind it; its CAS on s loses to the same key, a hit; a CAS on an earlier free slot cannot succeed,
+// the first inserter read that slot as filled by another key -- or as the key, a hit.  It cannot read s as
+// foreign.
+//
+// Bounded loops, expiring form: a walk reads at most slab_count slabs (`probed`); a walk is started again
+// only after a lost CAS, and each lost CAS is a free slot somebody else filled, of which the table has at most
+// slab_count * slab_size (`restarts`, written out).  Nothing waits on another workgroup.
+//
+// Metadata (insert != 0 only; an occurrence answered -1 touches nothing): every occurrence that resolved to a
+// slot stores last_seen[slot] = *step -- all writers of a launch store the same value, plain stores -- and
+// adds 1 to freq[slot] with a relaxed agent-scope atomic unless the value it read is already >= 2^30; with
+// n_keys < 2^30 per column the counter cannot wrap.
 #include <math.h>
 
 #include "common.h"
@@ -228,6 +261,239 @@ __global__ __launch_bounds__(kBlock) void hash_insert_kernel(const HashArgs a) {
   }
 }
 
+constexpr long long kTombstoneKey = kEmptyKey + 1;   // expiring tables only
+constexpr int32_t kFreqCeiling = 1 << 30;
+
+struct ExpiryCol {
+  int32_t* last_seen;
+  int32_t* freq;
+  const int32_t* step;
+  int32_t* stats;       // {n_evicted, n_reused} or NULL
+};
+
+struct ExpiringArgs {
+  HashArgs h;
+  ExpiryCol e[kMaxColsPerLaunch];
+};
+static_assert(sizeof(ExpiringArgs) <= 24576, "kernarg budget");
+
+// The sibling of hash_insert_kernel for expiring tables: same lane mapping and first reads, the placement
+// rule with tombstones of the header comment.
+template <bool INSERT>
+__global__ __launch_bounds__(kBlock) void hash_insert_expiring_kernel(const ExpiringArgs x) {
+  const HashArgs& a = x.h;
+  const int b = (int)blockIdx.x;
+  const int ci = find_column(a, b);
+  const HashCol& c = a.col[ci];
+  const ExpiryCol& e = x.e[ci];
+  const int lane = lane_id();
+  const int wave = (int)(threadIdx.x >> 6);
+  const int group_log2 = c.group_log2;
+  const int gsize = 1 << group_log2;
+  const int sub = lane & (gsize - 1);
+  const int grp = lane >> group_log2;
+  const int gbase = grp << group_log2;
+  const int groups_per_wave = kWave >> group_log2;
+  const int64_t wave_in_col = (int64_t)(b - a.tile_start[ci]) * kWavesPerBlock + wave;
+  const int64_t first_key = wave_in_col * groups_per_wave * kKeys;
+  const int64_t n_keys = c.n_keys;
+  if (first_key >= n_keys) return;   // (wave-uniform)
+  const int64_t i0 = first_key + grp;   // + u * groups_per_wave
+  const unsigned long long group_mask = (gsize == 64 ? ~0ull : ((1ull << gsize) - 1ull)) << gbase;
+  const int32_t slab_size = c.slab_size;
+  const int64_t slab_count = (int64_t)c.slab_div.d;
+  const int64_t capacity = slab_count * slab_size;
+  const bool in_slab = sub < slab_size;
+  long long* const cache = c.cache;
+  const int32_t step = INSERT ? *e.step : 0;
+
+  long long key[kKeys], read_key[kKeys];
+  int64_t home[kKeys];
+#pragma unroll
+  for (int u = 0; u < kKeys; ++u) {
+    const int64_t i = i0 + (int64_t)u * groups_per_wave;
+    key[u] = i < n_keys ? (long long)c.keys[i] : kEmptyKey;
+    if (key[u] == kTombstoneKey) key[u] = kEmptyKey;   // neither sentinel is ever stored: -1, counted as failed
+  }
+#pragma unroll
+  for (int u = 0; u < kKeys; ++u) {
+    home[u] = (int64_t)fastmod((uint64_t)murmur3_i64(key[u]), c.slab_div);
+    read_key[u] = 0;
+    if (key[u] != kEmptyKey && in_slab) read_key[u] = read_slot<INSERT>(cache + home[u] * slab_size + sub);
+  }
+  int32_t n_inserted = 0, n_failed = 0, n_reused = 0;
+  int64_t seen_slot[kKeys];   // the slot of every occurrence this lane answers for, or -1
+#pragma unroll
+  for (int u = 0; u < kKeys; ++u) {
+    const int64_t i = i0 + (int64_t)u * groups_per_wave;
+    bool active = key[u] != kEmptyKey;
+    bool won = false, reused = false;
+    int64_t result = -1;
+    int64_t slab = home[u];
+    int64_t probed = 0;      // slabs of this walk read without an EMPTY slot: <= slab_count
+    int64_t tomb = -1;       // the first TOMBSTONE slot of this walk
+    int64_t restarts = 0;    // CASes lost to another key: <= capacity (each one a free slot somebody else filled)
+    long long rk = read_key[u];
+    for (;;) {
+      const bool live = active && in_slab;
+      const unsigned long long match = __ballot(live && rk == key[u]) & group_mask;
+      const unsigned long long empty = __ballot(live && rk == kEmptyKey) & group_mask;
+      const unsigned long long dead = __ballot(live && rk == kTombstoneKey) & group_mask;
+      bool claim = false;
+      int64_t target = -1;
+      if (active) {
+        if (match != 0ull) {
+          result = slab * slab_size + (__builtin_ctzll(match) - gbase);
+          active = false;
+        } else {
+          if (tomb < 0 && dead != 0ull) tomb = slab * slab_size + (__builtin_ctzll(dead) - gbase);
+          if (empty != 0ull) {
+            claim = true;   // the stopping slab: the key is nowhere behind it
+            target = tomb >= 0 ? tomb : slab * slab_size + (__builtin_ctzll(empty) - gbase);
+          } else {
+            slab = slab + 1 == slab_count ? 0 : slab + 1;
+            if (++probed >= slab_count) {
+              claim = true;   // every slab read, none with an EMPTY slot
+              target = tomb;
+            }
+          }
+        }
+      }
+      if (INSERT) {
+        // (every lane of the wave takes the shuffle; the CAS is the group's first lane alone)
+        const bool cas = claim && target >= 0;
+        const long long free_key = target == tomb ? kTombstoneKey : kEmptyKey;
+        long long old = 0;
+        if (cas && sub == 0) {
+          long long expected = free_key;
+          __hip_atomic_compare_exchange_strong(cache + target, &expected, key[u], __ATOMIC_RELAXED,
+                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          old = expected;   // what the slot held: free_key when the exchange was made
+        }
+        old = __shfl(old, gbase, kWave);
+        if (claim) {
+          if (!cas) {
+            active = false;   // no free slot on the whole walk: -1
+          } else if (old == free_key || old == key[u]) {
+            // stored, or a concurrent duplicate of the key won this slot: a hit on it
+            won = old == free_key;
+            reused = won && free_key == kTombstoneKey;
+            result = target;
+            active = false;
+          } else {
+            // lost to another key: the walk again from the home slab
+            slab = home[u];
+            probed = 0;
+            tomb = -1;
+            if (++restarts > capacity) active = false;   // (unreachable: the bound, written out)
+          }
+        }
+      } else if (claim) {
+        active = false;   // a find stops where an insert would claim: not stored
+      }
+      if (!__any(active)) break;
+      rk = 0;
+      if (active && in_slab) rk = read_slot<INSERT>(cache + slab * slab_size + sub);
+    }
+    if (INSERT && won && c.table != nullptr) {
+      float* row = c.table + result * c.pitch;
+      for (int j = sub; j < c.dim; j += gsize) {
+        row[j] = c.init_scale == 0.0f ? 0.0f : init_value(key[u], c.seed, j, c.init_scale);
+      }
+    }
+    if (i < n_keys && sub == 0) {
+      c.slots[i] = result;
+      n_inserted += won ? 1 : 0;
+      n_reused += reused ? 1 : 0;
+      n_failed += result < 0 ? 1 : 0;
+    }
+    seen_slot[u] = i < n_keys && sub == 0 ? result : -1;
+  }
+  if (INSERT) {
+    // the metadata of the wave's keys together, reads first: 8 independent loads, then 8 independent adds.
+    // The read is a plain load (it only decides whether the counter is at its ceiling; a value as old as the
+    // launch's start keeps the bound: below 2^30 then, plus fewer than 2^30 occurrences).
+    int32_t seen_freq[kKeys];
+#pragma unroll
+    for (int u = 0; u < kKeys; ++u) {
+      seen_freq[u] = kFreqCeiling;
+      if (seen_slot[u] >= 0) {
+        e.last_seen[seen_slot[u]] = step;
+        seen_freq[u] = e.freq[seen_slot[u]];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kKeys; ++u) {
+      if (seen_freq[u] < kFreqCeiling) {
+        __hip_atomic_fetch_add(e.freq + seen_slot[u], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  }
+  // one atomic per wave and counter: the lanes' counts summed across the wave
+#pragma unroll
+  for (int off = 1; off < kWave; off <<= 1) {
+    n_inserted += __shfl_xor(n_inserted, off, kWave);
+    n_failed += __shfl_xor(n_failed, off, kWave);
+    n_reused += __shfl_xor(n_reused, off, kWave);
+  }
+  if (c.counts != nullptr) {
+    if (lane == 0 && n_inserted != 0) atomicAdd(c.counts, n_inserted);
+    if (lane == 0 && n_failed != 0) atomicAdd(c.counts + 1, n_failed);
+  }
+  if (e.stats != nullptr && lane == 0 && n_reused != 0) atomicAdd(e.stats + 1, n_reused);
+}
+
+}  // namespace
+}  // namespace hbk
+
+namespace hbk {
+namespace {
+
+// the host checks both entries make of one column: HBK_OK or HBK_INVALID_ARGUMENT
+int check_column(const char* who, int32_t c, const hbk_hash_column_t& h) {
+  HBK_REQUIRE(h.slab_size >= 1 && h.slab_size <= kWave, "%s: column %d: slab_size must be in [1, 64], got %d",
+              who, c, h.slab_size);
+  HBK_REQUIRE(h.slab_count >= 1, "%s: column %d: slab_count must be >= 1, got %lld", who, c,
+              (long long)h.slab_count);
+  HBK_REQUIRE(h.slab_count <= ((1ll << 62) / kWave), "%s: column %d: slab_count %lld is out of range", who, c,
+              (long long)h.slab_count);
+  HBK_REQUIRE(h.n_keys >= 0 && h.n_keys < (1ll << 31), "%s: column %d: n_keys must be in [0, 2^31), got %lld",
+              who, c, (long long)h.n_keys);
+  HBK_REQUIRE(h.n_keys == 0 || (h.keys_cache != nullptr && h.keys != nullptr && h.slots != nullptr),
+              "%s: column %d: NULL buffer (keys_cache, keys and slots are needed with n_keys > 0)", who, c);
+  HBK_REQUIRE(((uintptr_t)h.keys_cache & 7) == 0, "%s: column %d: keys_cache must be 8-byte aligned", who, c);
+  if (h.table != nullptr) {
+    HBK_REQUIRE(h.dim >= 1, "%s: column %d: dim must be >= 1 with a table, got %d", who, c, h.dim);
+    HBK_REQUIRE(h.table_pitch == 0 || h.table_pitch >= h.dim,
+                "%s: column %d: table_pitch %d is smaller than dim %d", who, c, h.table_pitch, h.dim);
+  }
+  HBK_REQUIRE(h.init_scale >= 0.0f && h.init_scale <= 3.402823466e38f,
+              "%s: column %d: init_scale must be finite and >= 0, got %g", who, c, (double)h.init_scale);
+  return HBK_OK;
+}
+
+// the kernel's view of one column; returns its tiles
+int64_t describe_column(const hbk_hash_column_t& h, int32_t insert, HashCol* out) {
+  HashCol& d = *out;
+  d.cache = reinterpret_cast<long long*>(h.keys_cache);
+  d.keys = h.keys;
+  d.slots = h.slots;
+  d.counts = h.counts;
+  d.table = insert != 0 ? h.table : nullptr;
+  d.n_keys = h.n_keys;
+  d.slab_div = make_fastdiv((uint64_t)h.slab_count);
+  d.slab_div.d = (uint64_t)h.slab_count;
+  d.pitch = h.table_pitch > 0 ? h.table_pitch : h.dim;
+  d.seed = (uint64_t)h.seed;
+  d.init_scale = h.init_scale;
+  d.slab_size = h.slab_size;
+  d.dim = h.dim;
+  d.group_log2 = 0;
+  while ((1 << d.group_log2) < h.slab_size) ++d.group_log2;
+  const int64_t keys_per_block = (int64_t)(kBlock >> d.group_log2) * kKeys;
+  return (h.n_keys + keys_per_block - 1) / keys_per_block;
+}
+
 }  // namespace
 }  // namespace hbk
 
@@ -238,25 +504,7 @@ extern "C" int hbk_hash_insert_n(int32_t n_cols, const hbk_hash_column_t* cols, 
   HBK_REQUIRE(n_cols >= 0, "%s: n_cols must be >= 0, got %d", who, n_cols);
   HBK_REQUIRE(n_cols == 0 || cols != nullptr, "%s: cols is NULL", who);
   for (int32_t c = 0; c < n_cols; ++c) {
-    const hbk_hash_column_t& h = cols[c];
-    HBK_REQUIRE(h.slab_size >= 1 && h.slab_size <= kWave, "%s: column %d: slab_size must be in [1, 64], got %d",
-                who, c, h.slab_size);
-    HBK_REQUIRE(h.slab_count >= 1, "%s: column %d: slab_count must be >= 1, got %lld", who, c,
-                (long long)h.slab_count);
-    HBK_REQUIRE(h.slab_count <= ((1ll << 62) / kWave), "%s: column %d: slab_count %lld is out of range", who, c,
-                (long long)h.slab_count);
-    HBK_REQUIRE(h.n_keys >= 0 && h.n_keys < (1ll << 31), "%s: column %d: n_keys must be in [0, 2^31), got %lld",
-                who, c, (long long)h.n_keys);
-    HBK_REQUIRE(h.n_keys == 0 || (h.keys_cache != nullptr && h.keys != nullptr && h.slots != nullptr),
-                "%s: column %d: NULL buffer (keys_cache, keys and slots are needed with n_keys > 0)", who, c);
-    HBK_REQUIRE(((uintptr_t)h.keys_cache & 7) == 0, "%s: column %d: keys_cache must be 8-byte aligned", who, c);
-    if (h.table != nullptr) {
-      HBK_REQUIRE(h.dim >= 1, "%s: column %d: dim must be >= 1 with a table, got %d", who, c, h.dim);
-      HBK_REQUIRE(h.table_pitch == 0 || h.table_pitch >= h.dim,
-                  "%s: column %d: table_pitch %d is smaller than dim %d", who, c, h.table_pitch, h.dim);
-    }
-    HBK_REQUIRE(h.init_scale >= 0.0f && h.init_scale <= 3.402823466e38f,
-                "%s: column %d: init_scale must be finite and >= 0, got %g", who, c, (double)h.init_scale);
+    if (int rc = check_column(who, c, cols[c])) return rc;
   }
   int32_t c0 = 0;
   while (c0 < n_cols) {
@@ -267,24 +515,7 @@ extern "C" int hbk_hash_insert_n(int32_t n_cols, const hbk_hash_column_t* cols, 
     while (c0 < n_cols && k < kMaxColsPerLaunch) {
       const hbk_hash_column_t& h = cols[c0++];
       if (h.n_keys == 0) continue;
-      HashCol& d = args.col[k];
-      d.cache = reinterpret_cast<long long*>(h.keys_cache);
-      d.keys = h.keys;
-      d.slots = h.slots;
-      d.counts = h.counts;
-      d.table = insert != 0 ? h.table : nullptr;
-      d.n_keys = h.n_keys;
-      d.slab_div = make_fastdiv((uint64_t)h.slab_count);
-      d.slab_div.d = (uint64_t)h.slab_count;
-      d.pitch = h.table_pitch > 0 ? h.table_pitch : h.dim;
-      d.seed = (uint64_t)h.seed;
-      d.init_scale = h.init_scale;
-      d.slab_size = h.slab_size;
-      d.dim = h.dim;
-      d.group_log2 = 0;
-      while ((1 << d.group_log2) < h.slab_size) ++d.group_log2;
-      const int64_t keys_per_block = (int64_t)(kBlock >> d.group_log2) * kKeys;
-      tiles += (h.n_keys + keys_per_block - 1) / keys_per_block;
+      tiles += describe_column(h, insert, &args.col[k]);
       HBK_REQUIRE(tiles < (1ll << 31), "%s: grid too large", who);
       ++k;
       args.tile_start[k] = (int32_t)tiles;
@@ -297,6 +528,54 @@ extern "C" int hbk_hash_insert_n(int32_t n_cols, const hbk_hash_column_t* cols, 
     } else {
       hipLaunchKernelGGL(hash_insert_kernel<false>, dim3((unsigned)tiles), dim3(kBlock), 0, as_stream(stream),
                          args);
+    }
+    HBK_HIP_OK(hipGetLastError());
+  }
+  return HBK_OK;
+}
+
+extern "C" int hbk_hash_insert_expiring_n(int32_t n_cols, const hbk_hash_column_t* cols,
+                                          const hbk_hash_expiry_t* exp, int32_t insert, hbk_stream_t stream) {
+  using namespace hbk;
+  const char* who = "hash_insert_expiring_n";
+  HBK_REQUIRE(n_cols >= 0, "%s: n_cols must be >= 0, got %d", who, n_cols);
+  HBK_REQUIRE(n_cols == 0 || cols != nullptr, "%s: cols is NULL", who);
+  HBK_REQUIRE(n_cols == 0 || exp != nullptr, "%s: exp is NULL", who);
+  for (int32_t c = 0; c < n_cols; ++c) {
+    if (int rc = check_column(who, c, cols[c])) return rc;
+    HBK_REQUIRE(cols[c].n_keys < (1ll << 30), "%s: column %d: n_keys must be below 2^30 (freq must not wrap), got %lld",
+                who, c, (long long)cols[c].n_keys);
+    HBK_REQUIRE(cols[c].n_keys == 0 ||
+                    (exp[c].last_seen != nullptr && exp[c].freq != nullptr && exp[c].step != nullptr),
+                "%s: column %d: NULL expiry buffer (last_seen, freq and step are needed with n_keys > 0)", who, c);
+  }
+  int32_t c0 = 0;
+  while (c0 < n_cols) {
+    ExpiringArgs args;
+    int32_t k = 0;
+    int64_t tiles = 0;
+    args.h.tile_start[0] = 0;
+    while (c0 < n_cols && k < kMaxColsPerLaunch) {
+      const hbk_hash_column_t& h = cols[c0];
+      const hbk_hash_expiry_t& x = exp[c0++];
+      if (h.n_keys == 0) continue;
+      tiles += describe_column(h, insert, &args.h.col[k]);
+      HBK_REQUIRE(tiles < (1ll << 31), "%s: grid too large", who);
+      args.e[k].last_seen = x.last_seen;
+      args.e[k].freq = x.freq;
+      args.e[k].step = x.step;
+      args.e[k].stats = x.stats;
+      ++k;
+      args.h.tile_start[k] = (int32_t)tiles;
+    }
+    if (k == 0) continue;
+    args.h.n_cols = k;
+    if (insert != 0) {
+      hipLaunchKernelGGL(hash_insert_expiring_kernel<true>, dim3((unsigned)tiles), dim3(kBlock), 0,
+                         as_stream(stream), args);
+    } else {
+      hipLaunchKernelGGL(hash_insert_expiring_kernel<false>, dim3((unsigned)tiles), dim3(kBlock), 0,
+                         as_stream(stream), args);
     }
     HBK_HIP_OK(hipGetLastError());
   }

@@ -716,6 +716,96 @@ typedef struct {
 int hbk_hash_insert_n(int32_t n_cols, const hbk_hash_column_t* cols, int32_t insert,
                       hbk_stream_t stream);
 
+/* Expiring hash tables: last-seen steps, an eviction sweep and slot reuse (DeepRec's steps_to_live).  A table
+ * that cannot forget has a fixed lifetime: new ids arrive for ever.  An expiring table is an hbk_hash_column_t
+ * table plus per-slot metadata, translated by hbk_hash_insert_expiring_n and swept by hbk_hash_evict_n;
+ * hbk_hash_insert_n above and the tables it serves are unchanged (INT64_MIN + 1 stays an ordinary key there).
+ *
+ * Sentinels.  EMPTY = INT64_MIN as above and TOMBSTONE = INT64_MIN + 1.  Eviction turns key -> TOMBSTONE, never
+ * -> EMPTY: a slab without an EMPTY slot stays without one, so every live key is still found by the walk of
+ * hbk_cache_probe / hbk_cache_lookup (to them a tombstone is a key nobody asks for).  The ids EMPTY and
+ * TOMBSTONE are never stored; they translate to -1 and count in n_failed.  EMPTY slots come back only by
+ * rebuilding the table (HashTable.compact in Python: not an entry of this ABI).
+ *
+ * Placement rule of the expiring insert, per key:
+ *     walk the slabs from murmur3_hash32(key) % slab_count, wrapping, at most slab_count slabs:
+ *         the slab holds the key             -> slots[i] = its slot, done
+ *         remember the FIRST TOMBSTONE slot seen on the walk (slab order, then slot order)
+ *         the slab has an EMPTY slot         -> stop walking here
+ *     claim the remembered TOMBSTONE (compare-and-swap TOMBSTONE -> key) if there is one, else the stopping
+ *     slab's first EMPTY slot (EMPTY -> key), else slots[i] = -1
+ *     a claim lost to the same key is a hit on that slot; a claim lost to another key walks again from the
+ *     home slab
+ * The walk goes past a tombstone to the stopping slab before it claims: a key that spilled into the next slab
+ * while its home slab was full is still there after a slot of the home slab was evicted, and must be found,
+ * not stored a second time.  Concurrent inserters of one key end in one slot (the argument is in
+ * csrc/hash_insert.hip).  Retries are bounded: a walk reads at most slab_count slabs, and each new walk is a
+ * free slot that somebody else filled; no workgroup waits for another.  With no tombstone in the table the
+ * results are those of hbk_hash_insert_n: the same slab sets, the same counters.  The winner writes the row as
+ * above, a function of (key, seed, j).
+ *
+ * Metadata, written by the translate launch itself.  last_seen, freq: device int32 [slab_count * slab_size];
+ * step: a device int32 scalar the caller keeps current (on the device so that replayed launches and captured
+ * graphs see it).  With insert != 0 every id OCCURRENCE that resolves to a slot >= 0 stores last_seen[slot] =
+ * *step and adds 1 to freq[slot] (relaxed agent-scope atomic); the add is skipped once the value read is
+ * >= 2^30, and n_keys >= 2^30 per column is refused, so the counter never wraps: it saturates somewhere in
+ * [2^30, 2^31).  A find (insert == 0) and an occurrence answered -1 touch neither array.
+ *
+ * Counters.  counts as above ({n_inserted, n_failed}; a key stored into a reused slot counts in n_inserted).
+ * stats (device int32[2] or NULL, zeroed by the caller, added to): {n_evicted, n_reused}.  n_reused counts the
+ * keys stored into a TOMBSTONE slot, n_evicted is the sweep's.  Live keys = n_inserted - n_evicted.
+ *
+ * hbk_hash_evict_n: one streaming pass over the slots of N tables.  A slot whose key is neither EMPTY nor
+ * TOMBSTONE is evicted iff
+ *     steps_to_live > 0  and  (int64)*step - last_seen[slot] >= steps_to_live
+ *     and (keep_freq == 0  or  freq[slot] < keep_freq)
+ * (idle ids expire unless they were seen often enough to be kept for good; steps_to_live == 0 evicts
+ * nothing).  For an evicted slot: key = TOMBSTONE, freq = last_seen = 0, and for each of the n_fills companion
+ * arrays (the optimizer slots, which the next id to get the row must not inherit: Adagrad's accumulator ->
+ * initial_accumulator_value, Adam's m / v -> 0, FTRL's accum / linear -> theirs) base[slot * pitch + j] =
+ * value for j < dim; the padding up to pitch is not written.  The embedding row is left as it is: the next
+ * inserter writes it.  The sweep must be stream-ordered against the translate launches of its tables, never
+ * concurrent with one (its accesses to the key array are plain).  It reads 16 bytes per slot.
+ *
+ * Reproducible between runs: the evicted SET (a function of the arrays alone), n_evicted, every row's
+ * contents, freq and last_seen per key.  NOT reproducible: which of several free slots a key gets under
+ * concurrency beyond what is stated for hbk_hash_insert_n, hence n_reused once keys of different home slabs
+ * compete for the same tombstones (exact for one slab, or one key at a time).
+ *
+ * Refused (HBK_INVALID_ARGUMENT) before any device work: everything hbk_hash_insert_n refuses; NULL last_seen,
+ * freq or step where there is work (n_keys > 0; always for the sweep, which also needs keys_cache); n_keys
+ * >= 2^30; steps_to_live < 0 or keep_freq < 0; n_fills outside [0, 4]; a fill with NULL base, dim < 1, a
+ * non-zero pitch < dim or a non-finite value.  No workspace, no host synchronisation: both are capturable.
+ * Detected by the presence of the symbols; the version stays that of 0.2.0. */
+typedef struct {
+  int32_t* last_seen;     /* device int32 [slab_count * slab_size] */
+  int32_t* freq;          /* device int32 [slab_count * slab_size] */
+  const int32_t* step;    /* device int32 scalar: the current step */
+  int32_t* stats;         /* device int32[2] {n_evicted, n_reused}, added to; or NULL */
+} hbk_hash_expiry_t;
+/* exp[c] belongs to cols[c] */
+int hbk_hash_insert_expiring_n(int32_t n_cols, const hbk_hash_column_t* cols, const hbk_hash_expiry_t* exp,
+                               int32_t insert, hbk_stream_t stream);
+
+#define HBK_HASH_MAX_FILLS 4
+typedef struct {
+  float* base;            /* device, slab_count * slab_size rows */
+  int32_t pitch;          /* floats between rows; 0 = dim */
+  int32_t dim;
+  float value;            /* finite */
+} hbk_hash_fill_t;
+typedef struct {
+  int64_t* keys_cache;    /* device [slab_count * slab_size], 8-byte aligned */
+  int64_t slab_count;
+  int32_t slab_size;      /* 1..64 */
+  hbk_hash_expiry_t exp;
+  int64_t steps_to_live;  /* >= 0; 0: nothing expires */
+  int32_t keep_freq;      /* >= 0; 0: frequency keeps nothing */
+  int32_t n_fills;        /* 0..HBK_HASH_MAX_FILLS */
+  hbk_hash_fill_t fills[HBK_HASH_MAX_FILLS];
+} hbk_hash_evict_column_t;
+int hbk_hash_evict_n(int32_t n_cols, const hbk_hash_evict_column_t* cols, hbk_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * Communicator lifecycle: HbGetNcclId / HbCreateNcclCollective /
  * HbIsNcclCollectiveInitialized / async-error polling.

@@ -110,7 +110,7 @@ def main():
 
     def translate(obj, insert):
       def step(i):   # pylint: disable=unused-argument
-        _lib.check(lib.hbk_hash_insert_n(cols, obj._cols, insert, stream))
+        _lib.check(lib.hbk_hash_insert_n(cols, obj._plan.plain, insert, stream))
       return step
     steps = {'hit': translate(hit, 1), 'zipf': translate(zf, 1), 'find': translate(find, 0),
              'hit_lookup': lambda i: hit.launch(), 'bucketed': lambda i: bucketed.launch()}
