@@ -92,6 +92,13 @@ class HashExpiry(C.Structure):
 
 
 HASH_MAX_FILLS = 4
+HASH_MAX_SKETCH_DEPTH = 8
+
+
+class HashAdmission(C.Structure):
+  """hbk_hash_admission_t"""
+  _fields_ = [('sketch', C.c_void_p), ('width', C.c_int64), ('depth', C.c_int32), ('min_freq', C.c_int32),
+              ('seed', C.c_int64), ('filtered', C.c_void_p)]
 
 
 class HashFill(C.Structure):
@@ -183,6 +190,8 @@ def _declare(l):
     'hbk_hash_insert_n': (C.c_int, [i32, vp, i32, vp]),
     'hbk_hash_insert_expiring_n': (C.c_int, [i32, vp, vp, i32, vp]),
     'hbk_hash_evict_n': (C.c_int, [i32, vp, vp]),
+    'hbk_hash_insert_admit_n': (C.c_int, [i32, vp, vp, i32, vp]),
+    'hbk_hash_insert_expiring_admit_n': (C.c_int, [i32, vp, vp, vp, i32, vp]),
     'hbk_comm_get_id': (C.c_int, [vp]),
     'hbk_comm_rccl_versions': (C.c_int, [vp, vp]),
     'hbk_comm_create': (C.c_int, [vp, vp, i32, i32, i32]),

@@ -55,6 +55,15 @@
 // slot stores last_seen[slot] = *step -- all writers of a launch store the same value, plain stores -- and
 // adds 1 to freq[slot] with a relaxed agent-scope atomic unless the value it read is already >= 2^30; with
 // n_keys < 2^30 per column the counter cannot wrap.
+//
+// Admission filter (hbk_hash_insert_admit_n, hbk_hash_insert_expiring_admit_n): count, then admit -- the two
+// kernels above again, with PHASE 1 and 2.  Phase 1 writes no key, so its walk uses plain loads; its only
+// writes besides slots (and an expiring table's metadata of the hits) are relaxed agent-scope adds to the
+// sketch, skipped from 2^30 on.  Phase 2 reads slots and the sketch with plain loads -- phase 1 ended at a
+// kernel boundary -- and reads the key array as the inserting kernel does, atomically.  A wave of phase 2 whose
+// keys were all resolved returns after one coalesced read of slots.  The loops are the ones above, with their
+// bounds; the sketch loops run `depth` <= 8 times.  The provisional -2 in slots is overwritten by phase 2 for
+// every occurrence that carries it.
 #include <math.h>
 
 #include "common.h"
@@ -134,14 +143,69 @@ __host__ __device__ inline float init_value(int64_t key, uint64_t seed, int j, f
   return unit * scale;
 }
 
+constexpr int32_t kFreqCeiling = 1 << 30;   // of freq and of the sketch's counters
+constexpr int64_t kPending = -2;            // slots[i] between the two phases of an admitting call: not resolved yet
+
+// The admission filter of one column (hbk_hash_admission_t): a count-min sketch, row r at sketch + r * width.
+struct AdmitCol {
+  int32_t* sketch;
+  int32_t* filtered;    // or NULL
+  FastDiv width_div;    // .d = width
+  uint64_t seed;
+  int32_t depth;
+  int32_t min_freq;
+};
+
+struct AdmitArgs {
+  HashArgs h;
+  AdmitCol f[kMaxColsPerLaunch];
+};
+static_assert(sizeof(AdmitArgs) <= 24576, "kernarg budget");
+
+__device__ inline const HashArgs& hash_args(const HashArgs& a) { return a; }
+__device__ inline const HashArgs& hash_args(const AdmitArgs& a) { return a.h; }
+
+// the cell of `key` in row r of the sketch: the mix of init_value
+__device__ inline int32_t* sketch_cell(const AdmitCol& f, long long key, int r) {
+  const uint64_t mix = (f.seed + (uint64_t)r + 1ull) * 0x9E3779B97F4A7C15ull;
+  const uint64_t cell = fastmod((uint64_t)murmur3_i64((int64_t)key ^ (int64_t)mix), f.width_div);
+  return f.sketch + (uint64_t)r * f.width_div.d + cell;
+}
+
+// Phase 1 of an admitting call, for a key its walk did not find: 1 to each of its cells, the lanes of the
+// group taking the rows in turn; skipped at the ceiling (the rule of freq).
+__device__ inline void sketch_count(const AdmitCol& f, long long key, int sub, int gsize) {
+  for (int r = sub; r < f.depth; r += gsize) {
+    int32_t* cell = sketch_cell(f, key, r);
+    if (*cell < kFreqCeiling) __hip_atomic_fetch_add(cell, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// Phase 2: min over the key's cells, plain loads (phase 1 ended at a kernel boundary).  Every lane of the wave
+// takes the shuffles; the lanes of a group whose key is not `wanted` read nothing.
+__device__ inline int32_t sketch_estimate(const AdmitCol& f, long long key, bool wanted, int sub, int gsize) {
+  int32_t est = 0x7fffffff;
+  if (wanted) {
+    for (int r = sub; r < f.depth; r += gsize) est = min(est, *sketch_cell(f, key, r));
+  }
+  for (int off = 1; off < gsize; off <<= 1) est = min(est, __shfl_xor(est, off, kWave));
+  return est;
+}
+
 template <bool INSERT>
 __device__ inline long long read_slot(const long long* p) {
   if (INSERT) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   return *p;
 }
 
-template <bool INSERT>
-__global__ __launch_bounds__(kBlock) void hash_insert_kernel(const HashArgs a) {
+// PHASE 0: the entries without a filter (Args = HashArgs).  PHASE 1 / 2 (Args = AdmitArgs): the two launches of
+// an admitting call -- 1 = the find walk, the sketch adds of its misses, kPending into their slots; 2 = the
+// find-or-insert of the pending occurrences whose estimate reaches min_freq, -1 for the others.  Everything the
+// phases add is behind `if constexpr`: the PHASE 0 instantiations are the kernels they were.
+template <bool INSERT, int PHASE = 0, class Args = HashArgs>
+__global__ __launch_bounds__(kBlock) void hash_insert_kernel(const Args args) {
+  static_assert(PHASE == 0 || INSERT == (PHASE == 2), "phase 1 finds, phase 2 inserts");
+  const HashArgs& a = hash_args(args);
   const int b = (int)blockIdx.x;
   const int ci = find_column(a, b);
   const HashCol& c = a.col[ci];
@@ -166,10 +230,33 @@ __global__ __launch_bounds__(kBlock) void hash_insert_kernel(const HashArgs a) {
 
   long long key[kKeys], read_key[kKeys];
   int64_t slab[kKeys];
+  [[maybe_unused]] bool pending[kKeys], admitted[kKeys];   // (PHASE 2)
+  if constexpr (PHASE == 2) {
+    // one coalesced read of the answers of phase 1: a wave with nothing pending leaves here
+    bool any = false;
+#pragma unroll
+    for (int u = 0; u < kKeys; ++u) {
+      const int64_t i = i0 + (int64_t)u * groups_per_wave;
+      pending[u] = i < n_keys && c.slots[i] == kPending;
+      any |= pending[u];
+    }
+    if (!__any(any)) return;
+  }
 #pragma unroll
   for (int u = 0; u < kKeys; ++u) {
     const int64_t i = i0 + (int64_t)u * groups_per_wave;
-    key[u] = i < n_keys ? (long long)c.keys[i] : kEmptyKey;
+    if constexpr (PHASE == 2) {
+      key[u] = pending[u] ? (long long)c.keys[i] : kEmptyKey;
+    } else {
+      key[u] = i < n_keys ? (long long)c.keys[i] : kEmptyKey;
+    }
+  }
+  if constexpr (PHASE == 2) {
+#pragma unroll
+    for (int u = 0; u < kKeys; ++u) {
+      admitted[u] = sketch_estimate(args.f[ci], key[u], pending[u], sub, gsize) >= args.f[ci].min_freq && pending[u];
+      if (!admitted[u]) key[u] = kEmptyKey;   // not walked: -1, counted in `filtered`
+    }
   }
 #pragma unroll
   for (int u = 0; u < kKeys; ++u) {
@@ -178,7 +265,7 @@ __global__ __launch_bounds__(kBlock) void hash_insert_kernel(const HashArgs a) {
     // (EMPTY is never looked for: the lanes past n_keys hold it too)
     if (key[u] != kEmptyKey && in_slab) read_key[u] = read_slot<INSERT>(cache + slab[u] * slab_size + sub);
   }
-  int32_t n_inserted = 0, n_failed = 0;
+  int32_t n_inserted = 0, n_failed = 0, n_filtered = 0;
 #pragma unroll
   for (int u = 0; u < kKeys; ++u) {
     const int64_t i = i0 + (int64_t)u * groups_per_wave;
@@ -243,10 +330,24 @@ __global__ __launch_bounds__(kBlock) void hash_insert_kernel(const HashArgs a) {
         row[j] = c.init_scale == 0.0f ? 0.0f : init_value(key[u], c.seed, j, c.init_scale);
       }
     }
-    if (i < n_keys && sub == 0) {
+    if constexpr (PHASE == 1) {
+      // not found and not the sentinel (which stays -1, counted as failed): counted, decided in phase 2
+      if (result < 0 && key[u] != kEmptyKey) {
+        sketch_count(args.f[ci], key[u], sub, gsize);
+        result = kPending;
+      }
+    }
+    if constexpr (PHASE == 2) {
+      if (pending[u] && sub == 0) {
+        c.slots[i] = result;
+        n_inserted += won ? 1 : 0;
+        n_failed += admitted[u] && result < 0 ? 1 : 0;
+        n_filtered += admitted[u] ? 0 : 1;
+      }
+    } else if (i < n_keys && sub == 0) {
       c.slots[i] = result;
       n_inserted += won ? 1 : 0;
-      n_failed += result < 0 ? 1 : 0;
+      n_failed += (PHASE == 1 ? result == -1 : result < 0) ? 1 : 0;
     }
   }
   if (c.counts != nullptr) {
@@ -259,10 +360,16 @@ __global__ __launch_bounds__(kBlock) void hash_insert_kernel(const HashArgs a) {
     if (lane == 0 && n_inserted != 0) atomicAdd(c.counts, n_inserted);
     if (lane == 0 && n_failed != 0) atomicAdd(c.counts + 1, n_failed);
   }
+  if constexpr (PHASE == 2) {
+    if (args.f[ci].filtered != nullptr) {
+#pragma unroll
+      for (int off = 1; off < kWave; off <<= 1) n_filtered += __shfl_xor(n_filtered, off, kWave);
+      if (lane == 0 && n_filtered != 0) atomicAdd(args.f[ci].filtered, n_filtered);
+    }
+  }
 }
 
 constexpr long long kTombstoneKey = kEmptyKey + 1;   // expiring tables only
-constexpr int32_t kFreqCeiling = 1 << 30;
 
 struct ExpiryCol {
   int32_t* last_seen;
@@ -277,10 +384,23 @@ struct ExpiringArgs {
 };
 static_assert(sizeof(ExpiringArgs) <= 24576, "kernarg budget");
 
+struct ExpiringAdmitArgs {
+  ExpiringArgs x;
+  AdmitCol f[kMaxColsPerLaunch];
+};
+static_assert(sizeof(ExpiringAdmitArgs) <= 24576, "kernarg budget");
+
+__device__ inline const ExpiringArgs& expiring_args(const ExpiringArgs& x) { return x; }
+__device__ inline const ExpiringArgs& expiring_args(const ExpiringAdmitArgs& x) { return x.x; }
+
 // The sibling of hash_insert_kernel for expiring tables: same lane mapping and first reads, the placement
-// rule with tombstones of the header comment.
-template <bool INSERT>
-__global__ __launch_bounds__(kBlock) void hash_insert_expiring_kernel(const ExpiringArgs x) {
+// rule with tombstones of the header comment.  PHASE as in hash_insert_kernel (Args = ExpiringAdmitArgs for 1 and
+// 2); the metadata of an occurrence is written by the phase that resolved it to a slot.
+template <bool INSERT, int PHASE = 0, class Args = ExpiringArgs>
+__global__ __launch_bounds__(kBlock) void hash_insert_expiring_kernel(const Args args) {
+  static_assert(PHASE == 0 || INSERT == (PHASE == 2), "phase 1 finds, phase 2 inserts");
+  constexpr bool kMetadata = INSERT || PHASE == 1;
+  const ExpiringArgs& x = expiring_args(args);
   const HashArgs& a = x.h;
   const int b = (int)blockIdx.x;
   const int ci = find_column(a, b);
@@ -305,15 +425,37 @@ __global__ __launch_bounds__(kBlock) void hash_insert_expiring_kernel(const Expi
   const int64_t capacity = slab_count * slab_size;
   const bool in_slab = sub < slab_size;
   long long* const cache = c.cache;
-  const int32_t step = INSERT ? *e.step : 0;
-
   long long key[kKeys], read_key[kKeys];
   int64_t home[kKeys];
+  [[maybe_unused]] bool pending[kKeys], admitted[kKeys];   // (PHASE 2)
+  if constexpr (PHASE == 2) {
+    // one coalesced read of the answers of phase 1: a wave with nothing pending leaves here
+    bool any = false;
+#pragma unroll
+    for (int u = 0; u < kKeys; ++u) {
+      const int64_t i = i0 + (int64_t)u * groups_per_wave;
+      pending[u] = i < n_keys && c.slots[i] == kPending;
+      any |= pending[u];
+    }
+    if (!__any(any)) return;
+  }
+  const int32_t step = kMetadata ? *e.step : 0;
 #pragma unroll
   for (int u = 0; u < kKeys; ++u) {
     const int64_t i = i0 + (int64_t)u * groups_per_wave;
-    key[u] = i < n_keys ? (long long)c.keys[i] : kEmptyKey;
+    if constexpr (PHASE == 2) {
+      key[u] = pending[u] ? (long long)c.keys[i] : kEmptyKey;
+    } else {
+      key[u] = i < n_keys ? (long long)c.keys[i] : kEmptyKey;
+    }
     if (key[u] == kTombstoneKey) key[u] = kEmptyKey;   // neither sentinel is ever stored: -1, counted as failed
+  }
+  if constexpr (PHASE == 2) {
+#pragma unroll
+    for (int u = 0; u < kKeys; ++u) {
+      admitted[u] = sketch_estimate(args.f[ci], key[u], pending[u], sub, gsize) >= args.f[ci].min_freq && pending[u];
+      if (!admitted[u]) key[u] = kEmptyKey;   // not walked: -1, counted in `filtered`
+    }
   }
 #pragma unroll
   for (int u = 0; u < kKeys; ++u) {
@@ -321,7 +463,7 @@ __global__ __launch_bounds__(kBlock) void hash_insert_expiring_kernel(const Expi
     read_key[u] = 0;
     if (key[u] != kEmptyKey && in_slab) read_key[u] = read_slot<INSERT>(cache + home[u] * slab_size + sub);
   }
-  int32_t n_inserted = 0, n_failed = 0, n_reused = 0;
+  int32_t n_inserted = 0, n_failed = 0, n_reused = 0, n_filtered = 0;
   int64_t seen_slot[kKeys];   // the slot of every occurrence this lane answers for, or -1
 #pragma unroll
   for (int u = 0; u < kKeys; ++u) {
@@ -401,15 +543,33 @@ __global__ __launch_bounds__(kBlock) void hash_insert_expiring_kernel(const Expi
         row[j] = c.init_scale == 0.0f ? 0.0f : init_value(key[u], c.seed, j, c.init_scale);
       }
     }
-    if (i < n_keys && sub == 0) {
-      c.slots[i] = result;
-      n_inserted += won ? 1 : 0;
-      n_reused += reused ? 1 : 0;
-      n_failed += result < 0 ? 1 : 0;
+    if constexpr (PHASE == 1) {
+      // not found and not a sentinel (which stays -1, counted as failed): counted, decided in phase 2
+      if (result < 0 && key[u] != kEmptyKey) {
+        sketch_count(args.f[ci], key[u], sub, gsize);
+        result = kPending;
+      }
     }
-    seen_slot[u] = i < n_keys && sub == 0 ? result : -1;
+    if constexpr (PHASE == 2) {
+      if (pending[u] && sub == 0) {
+        c.slots[i] = result;
+        n_inserted += won ? 1 : 0;
+        n_reused += reused ? 1 : 0;
+        n_failed += admitted[u] && result < 0 ? 1 : 0;
+        n_filtered += admitted[u] ? 0 : 1;
+      }
+      seen_slot[u] = pending[u] && sub == 0 ? result : -1;
+    } else {
+      if (i < n_keys && sub == 0) {
+        c.slots[i] = result;
+        n_inserted += won ? 1 : 0;
+        n_reused += reused ? 1 : 0;
+        n_failed += (PHASE == 1 ? result == -1 : result < 0) ? 1 : 0;
+      }
+      seen_slot[u] = i < n_keys && sub == 0 ? result : -1;   // (kPending is no slot either)
+    }
   }
-  if (INSERT) {
+  if (kMetadata) {
     // the metadata of the wave's keys together, reads first: 8 independent loads, then 8 independent adds.
     // The read is a plain load (it only decides whether the counter is at its ceiling; a value as old as the
     // launch's start keeps the bound: below 2^30 then, plus fewer than 2^30 occurrences).
@@ -441,6 +601,13 @@ __global__ __launch_bounds__(kBlock) void hash_insert_expiring_kernel(const Expi
     if (lane == 0 && n_failed != 0) atomicAdd(c.counts + 1, n_failed);
   }
   if (e.stats != nullptr && lane == 0 && n_reused != 0) atomicAdd(e.stats + 1, n_reused);
+  if constexpr (PHASE == 2) {
+    if (args.f[ci].filtered != nullptr) {
+#pragma unroll
+      for (int off = 1; off < kWave; off <<= 1) n_filtered += __shfl_xor(n_filtered, off, kWave);
+      if (lane == 0 && n_filtered != 0) atomicAdd(args.f[ci].filtered, n_filtered);
+    }
+  }
 }
 
 }  // namespace
@@ -492,6 +659,40 @@ int64_t describe_column(const hbk_hash_column_t& h, int32_t insert, HashCol* out
   while ((1 << d.group_log2) < h.slab_size) ++d.group_log2;
   const int64_t keys_per_block = (int64_t)(kBlock >> d.group_log2) * kKeys;
   return (h.n_keys + keys_per_block - 1) / keys_per_block;
+}
+
+// the checks both admitting entries make of one column's filter
+int check_admission(const char* who, int32_t c, const hbk_hash_column_t& h, const hbk_hash_admission_t& f) {
+  HBK_REQUIRE(h.n_keys < (1ll << 30), "%s: column %d: n_keys must be below 2^30 (a counter must not wrap), got %lld",
+              who, c, (long long)h.n_keys);
+  HBK_REQUIRE(f.width >= 1 && f.width < (1ll << 31), "%s: column %d: sketch width must be in [1, 2^31), got %lld",
+              who, c, (long long)f.width);
+  HBK_REQUIRE(f.depth >= 1 && f.depth <= HBK_HASH_MAX_SKETCH_DEPTH,
+              "%s: column %d: sketch depth must be in [1, %d], got %d", who, c, HBK_HASH_MAX_SKETCH_DEPTH, f.depth);
+  HBK_REQUIRE(f.min_freq >= 1 && f.min_freq <= kFreqCeiling,
+              "%s: column %d: min_freq must be in [1, 2^30], got %d", who, c, f.min_freq);
+  HBK_REQUIRE(h.n_keys == 0 || f.sketch != nullptr,
+              "%s: column %d: NULL sketch (needed with n_keys > 0)", who, c);
+  HBK_REQUIRE(((uintptr_t)f.sketch & 3) == 0, "%s: column %d: sketch must be 4-byte aligned", who, c);
+  return HBK_OK;
+}
+
+void describe_admission(const hbk_hash_admission_t& f, AdmitCol* out) {
+  AdmitCol& d = *out;
+  d.sketch = f.sketch;
+  d.filtered = f.filtered;
+  d.width_div = make_fastdiv((uint64_t)f.width);
+  d.width_div.d = (uint64_t)f.width;
+  d.seed = (uint64_t)f.seed;
+  d.depth = f.depth;
+  d.min_freq = f.min_freq;
+}
+
+void describe_expiry(const hbk_hash_expiry_t& x, ExpiryCol* out) {
+  out->last_seen = x.last_seen;
+  out->freq = x.freq;
+  out->step = x.step;
+  out->stats = x.stats;
 }
 
 }  // namespace
@@ -561,10 +762,7 @@ extern "C" int hbk_hash_insert_expiring_n(int32_t n_cols, const hbk_hash_column_
       if (h.n_keys == 0) continue;
       tiles += describe_column(h, insert, &args.h.col[k]);
       HBK_REQUIRE(tiles < (1ll << 31), "%s: grid too large", who);
-      args.e[k].last_seen = x.last_seen;
-      args.e[k].freq = x.freq;
-      args.e[k].step = x.step;
-      args.e[k].stats = x.stats;
+      describe_expiry(x, &args.e[k]);
       ++k;
       args.h.tile_start[k] = (int32_t)tiles;
     }
@@ -578,6 +776,102 @@ extern "C" int hbk_hash_insert_expiring_n(int32_t n_cols, const hbk_hash_column_
                          as_stream(stream), args);
     }
     HBK_HIP_OK(hipGetLastError());
+  }
+  return HBK_OK;
+}
+
+// Count, then admit: every counting launch of the call before any admitting one, on one stream.
+extern "C" int hbk_hash_insert_admit_n(int32_t n_cols, const hbk_hash_column_t* cols,
+                                       const hbk_hash_admission_t* adm, int32_t insert, hbk_stream_t stream) {
+  using namespace hbk;
+  const char* who = "hash_insert_admit_n";
+  HBK_REQUIRE(n_cols >= 0, "%s: n_cols must be >= 0, got %d", who, n_cols);
+  HBK_REQUIRE(n_cols == 0 || cols != nullptr, "%s: cols is NULL", who);
+  HBK_REQUIRE(n_cols == 0 || adm != nullptr, "%s: adm is NULL", who);
+  for (int32_t c = 0; c < n_cols; ++c) {
+    if (int rc = check_column(who, c, cols[c])) return rc;
+    if (int rc = check_admission(who, c, cols[c], adm[c])) return rc;
+  }
+  if (insert == 0) return hbk_hash_insert_n(n_cols, cols, 0, stream);   // a find: the sketch is not touched
+  for (int phase = 1; phase <= 2; ++phase) {
+    int32_t c0 = 0;
+    while (c0 < n_cols) {
+      AdmitArgs args;
+      int32_t k = 0;
+      int64_t tiles = 0;
+      args.h.tile_start[0] = 0;
+      while (c0 < n_cols && k < kMaxColsPerLaunch) {
+        const hbk_hash_column_t& h = cols[c0];
+        const hbk_hash_admission_t& f = adm[c0++];
+        if (h.n_keys == 0) continue;
+        tiles += describe_column(h, insert, &args.h.col[k]);
+        HBK_REQUIRE(tiles < (1ll << 31), "%s: grid too large", who);
+        describe_admission(f, &args.f[k]);
+        ++k;
+        args.h.tile_start[k] = (int32_t)tiles;
+      }
+      if (k == 0) continue;
+      args.h.n_cols = k;
+      if (phase == 1) {
+        hipLaunchKernelGGL((hash_insert_kernel<false, 1, AdmitArgs>), dim3((unsigned)tiles), dim3(kBlock), 0,
+                           as_stream(stream), args);
+      } else {
+        hipLaunchKernelGGL((hash_insert_kernel<true, 2, AdmitArgs>), dim3((unsigned)tiles), dim3(kBlock), 0,
+                           as_stream(stream), args);
+      }
+      HBK_HIP_OK(hipGetLastError());
+    }
+  }
+  return HBK_OK;
+}
+
+extern "C" int hbk_hash_insert_expiring_admit_n(int32_t n_cols, const hbk_hash_column_t* cols,
+                                                const hbk_hash_expiry_t* exp, const hbk_hash_admission_t* adm,
+                                                int32_t insert, hbk_stream_t stream) {
+  using namespace hbk;
+  const char* who = "hash_insert_expiring_admit_n";
+  HBK_REQUIRE(n_cols >= 0, "%s: n_cols must be >= 0, got %d", who, n_cols);
+  HBK_REQUIRE(n_cols == 0 || cols != nullptr, "%s: cols is NULL", who);
+  HBK_REQUIRE(n_cols == 0 || exp != nullptr, "%s: exp is NULL", who);
+  HBK_REQUIRE(n_cols == 0 || adm != nullptr, "%s: adm is NULL", who);
+  for (int32_t c = 0; c < n_cols; ++c) {
+    if (int rc = check_column(who, c, cols[c])) return rc;
+    if (int rc = check_admission(who, c, cols[c], adm[c])) return rc;
+    HBK_REQUIRE(cols[c].n_keys == 0 ||
+                    (exp[c].last_seen != nullptr && exp[c].freq != nullptr && exp[c].step != nullptr),
+                "%s: column %d: NULL expiry buffer (last_seen, freq and step are needed with n_keys > 0)", who, c);
+  }
+  if (insert == 0) return hbk_hash_insert_expiring_n(n_cols, cols, exp, 0, stream);   // a find
+  for (int phase = 1; phase <= 2; ++phase) {
+    int32_t c0 = 0;
+    while (c0 < n_cols) {
+      ExpiringAdmitArgs args;
+      int32_t k = 0;
+      int64_t tiles = 0;
+      args.x.h.tile_start[0] = 0;
+      while (c0 < n_cols && k < kMaxColsPerLaunch) {
+        const hbk_hash_column_t& h = cols[c0];
+        const hbk_hash_expiry_t& x = exp[c0];
+        const hbk_hash_admission_t& f = adm[c0++];
+        if (h.n_keys == 0) continue;
+        tiles += describe_column(h, insert, &args.x.h.col[k]);
+        HBK_REQUIRE(tiles < (1ll << 31), "%s: grid too large", who);
+        describe_expiry(x, &args.x.e[k]);
+        describe_admission(f, &args.f[k]);
+        ++k;
+        args.x.h.tile_start[k] = (int32_t)tiles;
+      }
+      if (k == 0) continue;
+      args.x.h.n_cols = k;
+      if (phase == 1) {
+        hipLaunchKernelGGL((hash_insert_expiring_kernel<false, 1, ExpiringAdmitArgs>), dim3((unsigned)tiles),
+                           dim3(kBlock), 0, as_stream(stream), args);
+      } else {
+        hipLaunchKernelGGL((hash_insert_expiring_kernel<true, 2, ExpiringAdmitArgs>), dim3((unsigned)tiles),
+                           dim3(kBlock), 0, as_stream(stream), args);
+      }
+      HBK_HIP_OK(hipGetLastError());
+    }
   }
   return HBK_OK;
 }

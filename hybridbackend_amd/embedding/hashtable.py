@@ -14,8 +14,13 @@ every slot carries the step it was last seen at and how often it was seen, both 
 launch; :meth:`HashTable.evict` turns idle slots into TOMBSTONEs (``INT64_MIN + 1``) and resets their
 optimizer slots, later inserts reuse them, :meth:`HashTable.compact` turns tombstones back into EMPTY slots.
 
-Not provided: admission filters / automatic growth (a full table answers -1; ``items()`` / ``load()`` into a
-larger table is the way to grow), sharded hash tables, feature-column integration, the TF shim op.
+Admission filter (``HashTable(..., min_freq=F)``; ``hbk_hash_insert_admit_n`` /
+``hbk_hash_insert_expiring_admit_n``; DeepRec's CounterFilter / CBFFilter): an id gets a row once a count-min
+sketch of the table has seen it ``F`` times; until then it translates to -1 -- a zero row, no gradient, no
+optimizer slot (DeepRec reads its default-value row there).
+
+Not provided: automatic growth (a full table answers -1; ``items()`` / ``load()`` into a larger table is the
+way to grow), sharded hash tables, feature-column integration, the TF shim op.
 """
 import ctypes as C
 import math
@@ -49,6 +54,16 @@ class HashTable:
     expiring: False -- nothing below is allocated and nothing changes.  True -- the table can forget: see
       :meth:`set_step`, :meth:`evict` and :meth:`compact`.  The ids ``INT64_MIN`` and ``INT64_MIN + 1``
       (TOMBSTONE) are then never stored.
+    min_freq: 0 -- no filter: nothing below is allocated and nothing changes.  F >= 1 -- an id is stored by the
+      translate call (``insert=True``) after whose counting phase its estimate reaches F; before that it
+      translates to -1, counted in :meth:`filtered`.  Ids the table holds are not counted.
+    sketch_depth / sketch_width / sketch_seed: the count-min sketch, ``depth`` rows (1..8) of ``width`` int32
+      counters (None: ``capacity``); an id's cell in row r is ``sketch_cells``'s.  Collisions only add: an id
+      may be admitted early, never late.
+
+  Attributes of a filtered table: ``sketch`` int32 ``[depth, width]``, ``filter_counts`` int32 ``[1]`` = id
+  occurrences the filter answered -1.  The sketch is never decremented, so an id evicted from an expiring table
+  is admitted again at once unless :meth:`clear_filter` or :meth:`age_filter` ran.
 
   Attributes of an expiring table: ``last_seen`` / ``freq`` int32 ``[capacity]`` (the step of a slot's last
   translate with ``insert=True`` and its occurrences so far, saturating at 2^30), ``step`` int32 ``[1]`` on
@@ -58,7 +73,8 @@ class HashTable:
   ``[capacity, dim]``, ``counts`` int32 ``[2]`` = keys inserted / id occurrences refused (table full) so far.
   """
 
-  def __init__(self, capacity, dim, device, slab_size=8, init_scale=1e-3, seed=0, expiring=False):
+  def __init__(self, capacity, dim, device, slab_size=8, init_scale=1e-3, seed=0, expiring=False, min_freq=0,
+               sketch_depth=4, sketch_width=None, sketch_seed=0):
     slab_size, capacity, dim = int(slab_size), int(capacity), int(dim)
     if not 1 <= slab_size <= 64:
       raise _bad(f'slab_size must be in [1, 64], got {slab_size}')
@@ -85,6 +101,21 @@ class HashTable:
       self.freq = torch.zeros(self.capacity, dtype=torch.int32, device=self.device)
       self.step = torch.zeros(1, dtype=torch.int32, device=self.device)
       self.stats = torch.zeros(2, dtype=torch.int32, device=self.device)
+    self.min_freq = int(min_freq)
+    if not 0 <= self.min_freq <= 2 ** 30:
+      raise _bad(f'min_freq must be in [0, 2^30], got {min_freq}')
+    if self.min_freq:
+      depth = int(sketch_depth)
+      width = self.capacity if sketch_width is None else int(sketch_width)
+      if not 1 <= depth <= _lib.HASH_MAX_SKETCH_DEPTH:
+        raise _bad(f'sketch_depth must be in [1, {_lib.HASH_MAX_SKETCH_DEPTH}], got {sketch_depth}')
+      if not 1 <= width < 2 ** 31:
+        raise _bad(f'sketch_width must be in [1, 2^31), got {sketch_width}')
+      if not -2 ** 63 <= int(sketch_seed) < 2 ** 63:
+        raise _bad(f'sketch_seed must be an int64, got {sketch_seed}')
+      self.sketch_seed = int(sketch_seed)
+      self.sketch = torch.zeros((depth, width), dtype=torch.int32, device=self.device)
+      self.filter_counts = torch.zeros(1, dtype=torch.int32, device=self.device)
 
   def _describe(self, col, init=True, count=True):
     """The table side of a descriptor."""
@@ -103,6 +134,17 @@ class HashTable:
     exp.freq = self.freq.data_ptr()
     exp.step = self.step.data_ptr()
     exp.stats = self.stats.data_ptr()
+
+  def _describe_admission(self, adm):
+    adm.sketch = self.sketch.data_ptr()
+    adm.depth, adm.width = self.sketch.shape
+    adm.min_freq = self.min_freq
+    adm.seed = self.sketch_seed
+    adm.filtered = self.filter_counts.data_ptr()
+
+  def _need_filter(self, what):
+    if not self.min_freq:
+      raise _bad(f'{what} needs a table built with min_freq >= 1')
 
   def _need_expiring(self, what):
     if not self.expiring:
@@ -139,6 +181,8 @@ class HashTable:
     self.counts[1] = 0
     if self.expiring:
       self.stats.zero_()
+    if self.min_freq:
+      self.filter_counts.zero_()
 
   def items(self):
     """``(keys, rows)`` of the occupied slots, sorted by key: the geometry-free form of the table."""
@@ -149,12 +193,13 @@ class HashTable:
 
   def load(self, keys, rows):
     """Insert ``keys`` (without initialising) and store ``rows`` as their rows: ``load(*other.items())``
-    moves a table into one of any capacity or slab size.  Refuses when a key does not fit."""
+    moves a table into one of any capacity or slab size.  Refuses when a key does not fit.  The admission
+    filter is bypassed and the sketch left alone: these are keys a table already admitted."""
     check_ids([keys], [self])
     if rows.dtype != torch.float32 or tuple(rows.shape) != (keys.numel(), self.dim) or \
         rows.device != self.table.device:
       raise _bad(f'rows must be fp32 [{keys.numel()}, {self.dim}] on {self.table.device}')
-    slots = _translate([self], [keys], True, None, init=False)[0]
+    slots = _translate([self], [keys], True, None, init=False, plan=_Plan([self], admit=False))[0]
     ok = slots >= 0
     if not bool(ok.all().item()):
       raise _bad(f'load: {int((~ok).sum().item())} of {keys.numel()} keys do not fit: the table is full')
@@ -168,7 +213,34 @@ class HashTable:
     if self.expiring:
       out[name + '/last_seen'] = self.last_seen
       out[name + '/freq'] = self.freq
+    if self.min_freq:
+      out[name + '/admission_sketch'] = self.sketch
     return out
+
+  # ---- admission filter -------------------------------------------------------------------------------------
+  def filtered(self):
+    """Id occurrences the filter answered -1 so far (syncs the host)."""
+    self._need_filter('filtered')
+    return int(self.filter_counts[0].item())
+
+  def estimate(self, ids):
+    """The sketch's count of every id, int32 ``[n]``: the min over its cells, restated in torch ops (a test
+    and debugging aid, not the hot path).  At least the times the id was counted; ids the table holds are not
+    counted."""
+    self._need_filter('estimate')
+    depth, width = self.sketch.shape
+    cells = sketch_cells(ids.to(self.sketch.device), depth, width, self.sketch_seed)
+    return torch.gather(self.sketch, 1, cells).min(dim=0).values
+
+  def clear_filter(self):
+    """Zero the sketch in place: every id not in the table needs ``min_freq`` sightings again."""
+    self._need_filter('clear_filter')
+    self.sketch.zero_()
+
+  def age_filter(self):
+    """Halve every counter in place (``>>= 1``): old sightings fade."""
+    self._need_filter('age_filter')
+    self.sketch.bitwise_right_shift_(1)
 
   # ---- expiry -------------------------------------------------------------------------------------------
   def set_step(self, n):
@@ -300,28 +372,44 @@ def check_ids(ids_list, tables):
 
 class _Plan:
   """The descriptors of N tables, split by entry: the plain tables' columns for ``hbk_hash_insert_n``, the
-  expiring ones' (with their expiry records) for ``hbk_hash_insert_expiring_n``.  ``cols[c]`` is table c's."""
+  expiring ones' (with their expiry records) for ``hbk_hash_insert_expiring_n``, and the filtered tables of
+  either kind (with their admission records) for ``hbk_hash_insert_admit_n`` /
+  ``hbk_hash_insert_expiring_admit_n``.  ``cols[c]`` is table c's.  ``admit=False``: no table is taken as
+  filtered (:meth:`HashTable.load`)."""
 
-  def __init__(self, tables):
-    plain = [c for c, t in enumerate(tables) if not t.expiring]
-    expiring = [c for c, t in enumerate(tables) if t.expiring]
-    self.plain = (_lib.HashColumn * len(plain))()
-    self.expiring = (_lib.HashColumn * len(expiring))()
-    self.expiry = (_lib.HashExpiry * len(expiring))()
+  def __init__(self, tables, admit=True):
+    groups = {}
+    for c, t in enumerate(tables):
+      groups.setdefault((t.expiring, bool(admit and t.min_freq)), []).append(c)
     self.cols = [None] * len(tables)
-    for k, c in enumerate(plain):
-      self.cols[c] = self.plain[k]
-    for k, c in enumerate(expiring):
-      self.cols[c] = self.expiring[k]
-      tables[c]._describe_expiry(self.expiry[k])
+    self.groups = []   # (expiring, filtered, columns, expiry records, admission records)
+    for (expiring, filtered), members in sorted(groups.items()):
+      cols = (_lib.HashColumn * len(members))()
+      expiry = (_lib.HashExpiry * len(members))() if expiring else None
+      adm = (_lib.HashAdmission * len(members))() if filtered else None
+      for k, c in enumerate(members):
+        self.cols[c] = cols[k]
+        if expiring:
+          tables[c]._describe_expiry(expiry[k])
+        if filtered:
+          tables[c]._describe_admission(adm[k])
+      self.groups.append((expiring, filtered, cols, expiry, adm))
 
   def launch(self, insert, stream):
     insert = 1 if insert else 0
-    if len(self.plain) or not len(self.expiring):
-      _lib.check(_lib.lib().hbk_hash_insert_n(len(self.plain), self.plain, insert, stream))
-    if len(self.expiring):
-      _lib.check(_lib.lib().hbk_hash_insert_expiring_n(len(self.expiring), self.expiring, self.expiry, insert,
-                                                       stream))
+    lib = _lib.lib()
+    if not self.groups:
+      _lib.check(lib.hbk_hash_insert_n(0, None, insert, stream))
+    for expiring, filtered, cols, expiry, adm in self.groups:
+      n = len(cols)
+      if expiring and filtered:
+        _lib.check(lib.hbk_hash_insert_expiring_admit_n(n, cols, expiry, adm, insert, stream))
+      elif expiring:
+        _lib.check(lib.hbk_hash_insert_expiring_n(n, cols, expiry, insert, stream))
+      elif filtered:
+        _lib.check(lib.hbk_hash_insert_admit_n(n, cols, adm, insert, stream))
+      else:
+        _lib.check(lib.hbk_hash_insert_n(n, cols, insert, stream))
 
 
 def _translate(tables, ids_list, insert, outs, init=True, plan=None):
@@ -351,13 +439,39 @@ def _translate(tables, ids_list, insert, outs, init=True, plan=None):
 
 
 def hash_translate(tables, ids_list, insert=True, outs=None):
-  """ids -> row numbers for N columns in ONE launch (``hbk_hash_insert_n``; plain and expiring tables may be
-  mixed: the expiring ones go through ``hbk_hash_insert_expiring_n`` in a second launch).  ``insert=False``:
-  a pure find (-1 for ids never seen).  ``outs``: preallocated int64 ``[n_ids]`` tensors.  Returns the list
-  of slots."""
+  """ids -> row numbers for N columns in ONE launch (``hbk_hash_insert_n``; plain, expiring and filtered tables
+  may be mixed: each kind goes through its own entry, the filtered ones in two launches, count then admit).
+  ``insert=False``: a pure find (-1 for ids never seen; no sketch is touched).  ``outs``: preallocated int64
+  ``[n_ids]`` tensors.  Returns the list of slots."""
   tables = list(tables)
   same_device(tables)
   return _translate(tables, list(ids_list), insert, outs)
+
+
+def sketch_cells(ids, depth, width, seed=0):
+  """int64 ``[depth, n]``: the cell of every id in every row of a ``[depth, width]`` admission sketch,
+  ``murmur3_hash32(id ^ (int64)((uint64)(seed + r + 1) * 0x9E3779B97F4A7C15)) % width`` (include/hbk.h), in
+  torch ops on the ids' device."""
+  m = 0xffffffff
+
+  def rotl(x, r):
+    return ((x << r) | (x >> (32 - r))) & m
+  rows = []
+  for r in range(int(depth)):
+    mix = ((int(seed) + r + 1) * 0x9E3779B97F4A7C15) & 0xffffffffffffffff
+    x = ids ^ (mix - (1 << 64) if mix >> 63 else mix)
+    h = torch.zeros_like(x)
+    for k in (x & m, (x >> 32) & m):
+      k = (k * 0xcc9e2d51) & m
+      k = (rotl(k, 15) * 0x1b873593) & m
+      h = rotl(h ^ k, 13)
+      h = (h * 5 + 0xe6546b64) & m
+    h = h ^ 8
+    h = ((h ^ (h >> 16)) * 0x85ebca6b) & m
+    h = ((h ^ (h >> 13)) * 0xc2b2ae35) & m
+    h = h ^ (h >> 16)
+    rows.append(h % int(width))
+  return torch.stack(rows) if rows else ids.new_zeros((0, ids.numel()))
 
 
 def same_device(tables):

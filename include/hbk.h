@@ -806,6 +806,66 @@ typedef struct {
 } hbk_hash_evict_column_t;
 int hbk_hash_evict_n(int32_t n_cols, const hbk_hash_evict_column_t* cols, hbk_stream_t stream);
 
+/* Admission filter: a count-min sketch gates new ids (DeepRec's CounterFilter / CBFFilter beside
+ * steps_to_live).  Most distinct ids of a click log occur once or twice; unfiltered, each of them claims a row,
+ * its optimizer slots and a key slot at first sight.  A filtered table stores an id once it was seen min_freq
+ * times; until then it translates to -1: a zero row that reaches no gradient and no optimizer slot (DeepRec reads
+ * its default-value row there).  The counters are a sketch per table, not per-id counters in the key array: an
+ * exact counter would spend a key slot on every rare id.  hbk_hash_insert_n and hbk_hash_insert_expiring_n are
+ * unchanged.
+ *
+ * sketch: device int32 [depth * width], zero at start, row r at sketch + r * width.  The cell of key k in row r:
+ *     cell(k, r) = murmur3_hash32(k ^ (int64)((uint64)(seed + r + 1) * 0x9E3779B97F4A7C15)) % width
+ * (the mix of the row initialisation above).
+ *
+ * A call with insert != 0 is COUNT, THEN ADMIT: two kernels on the call's stream.
+ *   1. count.  Every occurrence is looked for by its table's own walk (the plain rule, or the rule with
+ *      tombstones).  Found: that slot is the answer (an expiring table's last_seen / freq are written as above)
+ *      and the sketch is not touched -- a batch of resident ids issues no atomic.  Not found and not a sentinel
+ *      of that table kind (those are -1, counted in n_failed): 1 is added to each of its depth cells, a relaxed
+ *      agent-scope atomic add skipped when the value read is already >= 2^30 (the ceiling rule of freq; n_keys
+ *      >= 2^30 per column is refused, so a counter cannot wrap).
+ *   2. admit.  For an occurrence not found in 1: estimate = min over r of sketch[r][cell(k, r)], read after
+ *      ALL of 1.  estimate >= min_freq: the find-or-insert of that table kind -- the same compare-and-swap rules,
+ *      the row written by the one winner, the same counts / stats, last_seen / freq for every occurrence that
+ *      resolved to a slot.  Otherwise slots[i] = -1, *filtered grows by one per occurrence and nothing else is
+ *      written: not the key array, not counts, not last_seen / freq.
+ * Between the two kernels slots[] holds a provisional value (-2) for the unresolved occurrences; none survives
+ * the call.  When the columns need several launches (more than 64 columns) or two columns name one table, every
+ * counting launch of the call runs before any admitting launch.
+ *
+ * What follows.  The decision depends on the sketch after phase 1 alone, so every occurrence of an id in one
+ * call gets the same answer, and an id seen min_freq times inside one batch is admitted by that batch.  Which
+ * ids are admitted, the sketch, filtered, n_inserted and n_failed are the same on every run and equal to a
+ * sequential restatement (phase 1 over all keys, then phase 2 in key order); slot numbers stay run-dependent as
+ * above.  Collisions only add: estimate >= the true count, an id is admitted early, never late.  An admitted id
+ * that finds the table full is -1 counted in n_failed, not in filtered.  insert == 0 is the find of the entry
+ * without a filter and never touches the sketch.
+ *
+ * The sketch is never decremented.  An id evicted from an expiring table is therefore admitted again at once
+ * unless the caller cleared the sketch or aged it (halved every counter): both are plain array operations, not
+ * entries of this ABI (HashTable.clear_filter / age_filter in Python).
+ *
+ * Refused (HBK_INVALID_ARGUMENT) before any device work: everything the entry without a filter refuses; NULL
+ * adm; NULL sketch with n_keys > 0; width outside [1, 2^31), depth outside [1, 8], min_freq outside [1, 2^30];
+ * n_keys >= 2^30; a sketch that is not 4-byte aligned.  No workspace, no host synchronisation: capturable.
+ * Detected by the presence of the symbols; the structs above and the version are those of 0.2.0. */
+#define HBK_HASH_MAX_SKETCH_DEPTH 8
+typedef struct {
+  int32_t* sketch;        /* device int32 [depth * width] */
+  int64_t width;          /* 1 .. 2^31 - 1 */
+  int32_t depth;          /* 1 .. HBK_HASH_MAX_SKETCH_DEPTH */
+  int32_t min_freq;       /* 1 .. 2^30 */
+  int64_t seed;
+  int32_t* filtered;      /* device int32: occurrences the filter answered -1, added to; or NULL */
+} hbk_hash_admission_t;
+/* adm[c] (and exp[c]) belongs to cols[c] */
+int hbk_hash_insert_admit_n(int32_t n_cols, const hbk_hash_column_t* cols, const hbk_hash_admission_t* adm,
+                            int32_t insert, hbk_stream_t stream);
+int hbk_hash_insert_expiring_admit_n(int32_t n_cols, const hbk_hash_column_t* cols,
+                                     const hbk_hash_expiry_t* exp, const hbk_hash_admission_t* adm,
+                                     int32_t insert, hbk_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * Communicator lifecycle: HbGetNcclId / HbCreateNcclCollective /
  * HbIsNcclCollectiveInitialized / async-error polling.

@@ -110,7 +110,7 @@ def main():
 
     def translate(obj, insert):
       def step(i):   # pylint: disable=unused-argument
-        _lib.check(lib.hbk_hash_insert_n(cols, obj._plan.plain, insert, stream))
+        obj._plan.launch(insert, stream)   # plain tables alone: one hbk_hash_insert_n
       return step
     steps = {'hit': translate(hit, 1), 'zipf': translate(zf, 1), 'find': translate(find, 0),
              'hit_lookup': lambda i: hit.launch(), 'bucketed': lambda i: bucketed.launch()}
