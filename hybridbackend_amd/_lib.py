@@ -113,6 +113,23 @@ class HashEvictColumn(C.Structure):
               ('n_fills', C.c_int32), ('fills', HashFill * HASH_MAX_FILLS)]
 
 
+HASH_MAX_MOVES = 8
+
+
+class HashMove(C.Structure):
+  """hbk_hash_move_t"""
+  _fields_ = [('src', C.c_void_p), ('dst', C.c_void_p), ('words', C.c_int32), ('src_pitch', C.c_int32),
+              ('dst_pitch', C.c_int32)]
+
+
+class HashRehashColumn(C.Structure):
+  """hbk_hash_rehash_column_t"""
+  _fields_ = [('src_keys', C.c_void_p), ('src_slab_count', C.c_int64), ('src_slab_size', C.c_int32),
+              ('dst_keys', C.c_void_p), ('dst_slab_count', C.c_int64), ('dst_slab_size', C.c_int32),
+              ('expiring', C.c_int32), ('n_moves', C.c_int32), ('moves', HashMove * HASH_MAX_MOVES),
+              ('new_slots', C.c_void_p), ('counts', C.c_void_p)]
+
+
 class ShardedColumn(C.Structure):
   """hbk_sharded_column_t"""
   _fields_ = [('shard', C.c_void_p), ('rows_local', C.c_int64), ('dim', C.c_int32),
@@ -192,6 +209,7 @@ def _declare(l):
     'hbk_hash_evict_n': (C.c_int, [i32, vp, vp]),
     'hbk_hash_insert_admit_n': (C.c_int, [i32, vp, vp, i32, vp]),
     'hbk_hash_insert_expiring_admit_n': (C.c_int, [i32, vp, vp, vp, i32, vp]),
+    'hbk_hash_rehash_n': (C.c_int, [i32, vp, vp]),
     'hbk_comm_get_id': (C.c_int, [vp]),
     'hbk_comm_rccl_versions': (C.c_int, [vp, vp]),
     'hbk_comm_create': (C.c_int, [vp, vp, i32, i32, i32]),

@@ -19,8 +19,16 @@ Admission filter (``HashTable(..., min_freq=F)``; ``hbk_hash_insert_admit_n`` /
 sketch of the table has seen it ``F`` times; until then it translates to -1 -- a zero row, no gradient, no
 optimizer slot (DeepRec reads its default-value row there).
 
-Not provided: automatic growth (a full table answers -1; ``items()`` / ``load()`` into a larger table is the
-way to grow), sharded hash tables, feature-column integration, the TF shim op.
+Growth and compaction (``hbk_hash_rehash_n``): :meth:`HashTable.rehash` / :func:`hash_rehash` move every live
+key of N tables into fresh arrays of any geometry in ONE launch -- rows, ``last_seen``, ``freq`` and the optimizer
+slots moving along, no host round trip when the table does not shrink; ``t.rehash()`` is a device-side
+``compact()``.  :meth:`HashTable.maybe_grow` / :meth:`HashGroupLookup.maybe_grow` decide from the counters (one
+host read) whether a table must grow or shed its tombstones.  A rehash changes slot numbers and tensor
+addresses: :meth:`HashGroupLookup.rebind`, a new ``GroupLookupGrad`` over the new slot tensors, a new capture
+of any captured graph.
+
+Not provided: growth from inside a translate launch (a full table answers -1 until ``maybe_grow`` ran), a
+compaction that keeps the tensors' addresses, sharded hash tables, feature-column integration, the TF shim op.
 """
 import ctypes as C
 import math
@@ -170,6 +178,13 @@ class HashTable:
     n = int(self.counts[0].item())
     return n - int(self.stats[0].item()) if self.expiring else n
 
+  def _live_count(self):
+    """:meth:`size` in ONE host read."""
+    if not self.expiring:
+      return int(self.counts[0].item())
+    inserted, _, evicted, _ = torch.cat([self.counts, self.stats]).tolist()
+    return inserted - evicted
+
   def failed(self):
     """Id occurrences refused so far because the table was full (syncs the host)."""
     return int(self.counts[1].item())
@@ -299,6 +314,36 @@ class HashTable:
       t[new] = m
     self.counts[1] = failed
 
+  # ---- growth and device-side compaction -------------------------------------------------------------------
+  def rehash(self, capacity=None, slab_size=None, slots=()):
+    """Move the table into fresh arrays of ``capacity`` rows in slabs of ``slab_size`` (None: as now) in one
+    launch (``hbk_hash_rehash_n``): see :func:`hash_rehash`.  ``t.rehash()`` is :meth:`compact` on the device.
+    ``slots``: up to 4 ``(tensor, fill_value)`` companions as in :meth:`evict`.  Returns the new companion
+    tensors in order.  Slot numbers and tensor addresses change."""
+    return hash_rehash([self], [capacity], [slab_size], [slots])[0]
+
+  def maybe_grow(self, max_load=0.75, factor=2.0, slots=()):
+    """Rehash when more than ``max_load`` of the slots are occupied (keys and tombstones: inserted - reused),
+    decided from ONE host read of ``counts`` and ``stats``: to the same capacity when the live keys (inserted -
+    evicted) are at most ``max_load * capacity / 2`` -- tombstones were the load -- else to ``ceil(capacity *
+    factor)``.  Returns None when nothing was done, else the new companion tensors of ``slots`` (see
+    :meth:`rehash` for what a rehash invalidates)."""
+    max_load, factor = float(max_load), float(factor)
+    if not 0.0 < max_load <= 1.0:
+      raise _bad(f'max_load must be in (0, 1], got {max_load!r}')
+    if not (math.isfinite(factor) and factor > 1.0):
+      raise _bad(f'factor must be finite and > 1, got {factor!r}')
+    if self.expiring:
+      inserted, _, evicted, reused = torch.cat([self.counts, self.stats]).tolist()
+    else:
+      (inserted, _), evicted, reused = self.counts.tolist(), 0, 0
+    occupied, live = inserted - reused, inserted - evicted
+    if occupied <= max_load * self.capacity:
+      return None
+    if live <= max_load * self.capacity / 2:
+      return self.rehash(slots=slots)
+    return self.rehash(capacity=int(math.ceil(self.capacity * factor)), slots=slots)
+
 
 def _companions(table, slots):
   """Checked ``(tensor, fill_value)`` pairs of one table."""
@@ -319,6 +364,104 @@ def _companions(table, slots):
       raise _bad(f'slots[{n}]: fill_value must be finite, got {p[1]!r}')
     out.append((t, value))
   return out
+
+
+def hash_rehash(tables, capacities=None, slab_sizes=None, slots=None):
+  """Growth and compaction of N tables (plain, expiring and filtered ones may be mixed) in ONE launch
+  (``hbk_hash_rehash_n``): every live key is placed into a fresh all-EMPTY key array by the plain placement rule
+  and its rows move with it -- ``table``, an expiring table's ``last_seen`` and ``freq``, and the companions.
+
+  ``capacities[c]`` / ``slab_sizes[c]``: the new geometry of table c (None: as now; the capacity is rounded down
+  to whole slabs); ``slots[c]``: its ``(tensor, fill_value)`` companions as in :meth:`HashTable.evict`.  The call
+  allocates the new arrays (``keys`` all EMPTY, ``table`` zeros, ``last_seen`` / ``freq`` zeros, one ``[capacity,
+  d]`` tensor per companion filled with its ``fill_value``), launches, and replaces the tables' attributes;
+  ``capacity``, ``slab_count`` and ``slab_size`` follow.  Returns, per table, the list of its new companion
+  tensors in order.
+
+  Counters (new tensors too, swapped in with the arrays, so a refused call leaves the table and its counters as
+  they were): ``counts[0]`` becomes the keys moved, ``counts[1]`` (failed) is kept; an expiring table's ``stats``
+  is zeroed (``tombstones()``, ``evicted()`` and ``reused()`` read 0, ``size()`` is unchanged), ``step`` is kept;
+  a filtered table's sketch, ``filter_counts``, ``min_freq`` and seeds are untouched.
+
+  No host synchronisation when no table shrinks (every live key then fits: the walk covers all slabs).  A
+  smaller capacity reads ``size()`` -- one sync -- and is refused before anything changes when the keys do not
+  fit.
+
+  Slot numbers and tensor addresses change: slots handed out before are void, a :class:`HashGroupLookup` over
+  the tables needs :meth:`HashGroupLookup.rebind`, a ``GroupLookupGrad`` built on the old ``hgl.lookup`` must be
+  rebuilt with the new slot tensors, and a captured graph must be captured again.  Must not run beside a
+  translate or a sweep of the same tables on another stream."""
+  tables = list(tables)
+  same_device(tables)
+  n = len(tables)
+  capacities = [None] * n if capacities is None else list(capacities)
+  slab_sizes = [None] * n if slab_sizes is None else list(slab_sizes)
+  slots = [()] * n if slots is None else list(slots)
+  if not len(capacities) == len(slab_sizes) == len(slots) == n:
+    raise _bad(f'expected {n} capacities, slab sizes and lists of companion tensors, got {len(capacities)}, '
+               f'{len(slab_sizes)} and {len(slots)}')
+  if len(set(id(t) for t in tables)) != n:
+    raise _bad('a table is named twice')
+  if n == 0:
+    _lib.check(_lib.lib().hbk_hash_rehash_n(0, None, None))
+    return []
+  geometry, checked = [], []
+  for c, t in enumerate(tables):
+    slab_size = t.slab_size if slab_sizes[c] is None else int(slab_sizes[c])
+    capacity = t.capacity if capacities[c] is None else int(capacities[c])
+    if not 1 <= slab_size <= 64:
+      raise _bad(f'table {c}: slab_size must be in [1, 64], got {slab_size}')
+    if capacity < slab_size:
+      raise _bad(f'table {c}: capacity {capacity} is below one slab of {slab_size} slots')
+    geometry.append((capacity // slab_size, slab_size))
+    checked.append(_companions(t, slots[c]))
+  for c, t in enumerate(tables):
+    _lib.require_device_tensor(t.keys, 'keys')
+    capacity = geometry[c][0] * geometry[c][1]
+    if capacity < t.capacity:
+      live = t._live_count()   # (the one sync of a shrink)
+      if live > capacity:
+        raise _bad(f'table {c}: {live} keys do not fit into {capacity} slots')
+  cols = (_lib.HashRehashColumn * n)()
+  fresh = []
+  for c, t in enumerate(tables):
+    slab_count, slab_size = geometry[c]
+    capacity, dev = slab_count * slab_size, t.keys.device
+    new = {'keys': torch.full((capacity,), EMPTY_KEY, dtype=torch.int64, device=dev),
+           'table': torch.zeros((capacity, t.dim), dtype=torch.float32, device=dev)}
+    moves = [(t.table, new['table'])]
+    if t.expiring:
+      for name in ('last_seen', 'freq'):
+        new[name] = torch.zeros(capacity, dtype=torch.int32, device=dev)
+        moves.append((getattr(t, name), new[name]))
+    companions = [torch.full((capacity, x.shape[1]), value, dtype=torch.float32, device=dev) for x, value in checked[c]]
+    moves += [(x, y) for (x, _), y in zip(checked[c], companions)]
+    col = cols[c]
+    col.src_keys, col.src_slab_count, col.src_slab_size = t.keys.data_ptr(), t.slab_count, t.slab_size
+    col.dst_keys, col.dst_slab_count, col.dst_slab_size = new['keys'].data_ptr(), slab_count, slab_size
+    col.expiring = 1 if t.expiring else 0
+    col.n_moves = len(moves)
+    for m, (src, dst) in enumerate(moves):
+      mv = col.moves[m]
+      mv.src, mv.dst = src.data_ptr(), dst.data_ptr()
+      mv.words = 1 if src.dim() == 1 else src.shape[1]
+      mv.src_pitch = 1 if src.dim() == 1 else src.stride(0)
+      mv.dst_pitch = 0
+    col.new_slots = None
+    # a fresh counter pair: {0, the failures so far}; the kernel adds the keys it moved.  It is swapped in with
+    # the other new arrays, so a refused launch leaves the table and its counters as they were
+    new['counts'] = t.counts.clone()
+    new['counts'][:1].zero_()
+    col.counts = new['counts'].data_ptr()
+    if t.expiring:
+      new['stats'] = torch.zeros(2, dtype=torch.int32, device=dev)
+    fresh.append((new, companions))
+  _lib.check(_lib.lib().hbk_hash_rehash_n(n, cols, _lib.current_stream(tables[0].keys.device)))
+  for t, (slab_count, slab_size), (new, _) in zip(tables, geometry, fresh):
+    for name, x in new.items():
+      setattr(t, name, x)
+    t.slab_count, t.slab_size, t.capacity = slab_count, slab_size, slab_count * slab_size
+  return [companions for _, companions in fresh]
 
 
 def hash_evict(tables, steps_to_live, keep_freq=0, slots=None):
@@ -501,11 +644,38 @@ class HashGroupLookup:
     self.tables = list(tables)
     same_device(self.tables)
     self.train = bool(train)
-    self.lookup = GroupLookup([t.table for t in self.tables], buckets=None, combiners=combiners,
-                              max_norms=max_norms)
+    self._combiners, self._max_norms = combiners, max_norms
+    self.rebind()
+
+  def rebind(self):
+    """After a rehash of a table (:func:`hash_rehash`, :meth:`HashTable.maybe_grow`): ``self.lookup`` is built
+    again over the tables' current ``table`` tensors with the same combiners and max_norms, and the bound state
+    is dropped -- :meth:`launch` refuses until the next call, as on a fresh object.  Slot numbers and tensor
+    addresses changed: a ``GroupLookupGrad`` built on the old ``hgl.lookup`` must be rebuilt with the new slot
+    tensors (the companions the rehash returned), and a captured graph must be captured again."""
+    self.lookup = GroupLookup([t.table for t in self.tables], buckets=None, combiners=self._combiners,
+                              max_norms=self._max_norms)
     self._plan = _Plan(self.tables)
+    self._rows = [t.table for t in self.tables]
     self.slots = None
+    self._keep = None
     self._bound = False
+
+  def maybe_grow(self, max_load=0.75, factor=2.0, slots=None):
+    """:meth:`HashTable.maybe_grow` on every table (``slots[c]``: the companions of table c), then
+    :meth:`rebind` if any table was rehashed.  Returns the per-table results: None, or the new companion
+    tensors.  See :meth:`rebind` for what must be rebuilt afterwards."""
+    slots = [()] * len(self.tables) if slots is None else list(slots)
+    if len(slots) != len(self.tables):
+      raise _bad(f'expected {len(self.tables)} lists of companion tensors, got {len(slots)}')
+    out = [t.maybe_grow(max_load, factor, slots[c]) for c, t in enumerate(self.tables)]
+    if any(o is not None for o in out):
+      self.rebind()
+    return out
+
+  def _current(self):
+    if any(t.table is not r for t, r in zip(self.tables, self._rows)):
+      raise _bad('a table was rehashed: rebind() first')
 
   def __len__(self):
     return len(self.tables)
@@ -513,6 +683,7 @@ class HashGroupLookup:
   def __call__(self, ids, row_splits=None, outs=None, sp_weights=None):
     """ids[c]: int64 raw ids, row_splits[c]: int32 ``[segments + 1]`` or None.  Returns GroupLookup's outputs."""
     ids = list(ids)
+    self._current()
     # the slot buffers of the call before serve again while the id counts stay (a resident loop; a
     # captured launch() needs them to stay where they are)
     keep = self.slots
@@ -529,6 +700,7 @@ class HashGroupLookup:
     two foreign calls, no allocation."""
     if not self._bound:
       raise _lib.HbkError(_lib.INTERNAL, 'launch() needs a call that bound the tensors first')
+    self._current()
     dev = self.tables[0].keys.device if self.tables else None
     s = _lib.current_stream(dev) if stream is None else C.c_void_p(stream.cuda_stream)
     self._plan.launch(self.train, s)

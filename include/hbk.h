@@ -725,7 +725,7 @@ int hbk_hash_insert_n(int32_t n_cols, const hbk_hash_column_t* cols, int32_t ins
  * -> EMPTY: a slab without an EMPTY slot stays without one, so every live key is still found by the walk of
  * hbk_cache_probe / hbk_cache_lookup (to them a tombstone is a key nobody asks for).  The ids EMPTY and
  * TOMBSTONE are never stored; they translate to -1 and count in n_failed.  EMPTY slots come back only by
- * rebuilding the table (HashTable.compact in Python: not an entry of this ABI).
+ * rebuilding the table (hbk_hash_rehash_n below; HashTable.compact in Python is the same in torch ops).
  *
  * Placement rule of the expiring insert, per key:
  *     walk the slabs from murmur3_hash32(key) % slab_count, wrapping, at most slab_count slabs:
@@ -865,6 +865,74 @@ int hbk_hash_insert_admit_n(int32_t n_cols, const hbk_hash_column_t* cols, const
 int hbk_hash_insert_expiring_admit_n(int32_t n_cols, const hbk_hash_column_t* cols,
                                      const hbk_hash_expiry_t* exp, const hbk_hash_admission_t* adm,
                                      int32_t insert, hbk_stream_t stream);
+
+/* Rehash: growth and tombstone compaction on the device.  A full table answers -1 for ever, and an expiring
+ * table's probes get longer with every tombstone; both are cured by moving every live key into a fresh key
+ * array -- of a larger geometry, or of the same one -- with its rows.  hbk_hash_rehash_n does that for N tables
+ * per launch (32 per launch) without a host round trip: one streaming pass over the source key array and one
+ * insert into the destination per live key, the rows moving along.
+ *
+ * Source.  src_keys [src_slab_count * src_slab_size] is read with plain loads, 64 consecutive slots per wave;
+ * nobody may write it during the call.  A slot holds a key unless it is EMPTY, or TOMBSTONE with expiring != 0
+ * (expiring == 0: INT64_MIN + 1 is an ordinary key, as for hbk_hash_insert_n).  The keys of the source are
+ * taken to be distinct, as the keys of a table are.
+ *
+ * Placement, per live key (dst_keys must be all EMPTY on entry: the caller's contract, not checked):
+ *     slab = murmur3_hash32(key) % dst_slab_count
+ *     the slab has EMPTY slots  -> the FIRST of them is claimed (64-bit agent-scope compare-and-swap EMPTY -> key);
+ *                                  a claim lost (to another key: the source keys are distinct) reads the same
+ *                                  slab again
+ *     else (the slab is full)   -> the next slab, wrapping; after dst_slab_count slabs the key did not fit
+ * the rule of hbk_hash_insert_n bit for bit, so hbk_cache_probe and every translate entry find each key where
+ * this entry put it.  The destination holds no tombstone: the one rule serves plain and expiring tables.
+ * Inside the kernel every read of dst_keys is a relaxed agent-scope 8-byte atomic load and every write the
+ * compare-and-swap; no fences.  Retries are bounded by dst_slab_size per slab and dst_slab_count slabs per key;
+ * no workgroup waits for another.  With dst capacity >= the live keys every key fits: the walk covers all slabs.
+ *
+ * Moves.  Each of the n_moves per-slot arrays (the embedding rows, optimizer slots, last_seen, freq) is an
+ * array of rows of `words` 4-byte words, copied bit for bit: for a key that went from source slot s to
+ * destination slot d, dst[d * dst_pitch + j] = src[s * src_pitch + j] for j < words, plain stores by the lane
+ * group that won the slot; the padding between words and the pitch is not written, and neither are the rows of
+ * destination slots no key took (the caller pre-fills them).  Rows whose bases, pitches and width are all
+ * multiples of 16 bytes travel in 16-byte accesses.
+ *
+ * Results.  new_slots (device int64 [src capacity] or NULL): new_slots[s] = the destination slot of the key of
+ * source slot s; -1 where s holds no key and where the key did not fit.  counts (device int32[2] or NULL, added
+ * to): {n_moved, n_failed}, one atomic per wave and counter.  Reproducible between runs: the SET of keys of
+ * every destination slab when no slab overflows, every row's contents per key, the counters.  NOT reproducible:
+ * slot numbers.
+ *
+ * What a rehash invalidates: every slot number handed out before it, and -- the arrays being new -- every
+ * address derived from the old ones (descriptors, captured graphs).
+ *
+ * Refused (HBK_INVALID_ARGUMENT) before any device work: n_cols < 0; NULL cols with n_cols > 0; a slab size
+ * outside [1, 64] or a slab count < 1 or > 2^62 / 64 on either side; NULL or not 8-byte aligned src_keys /
+ * dst_keys; src_keys == dst_keys; n_moves outside [0, 8]; a move with words < 1, a non-zero pitch < words, a NULL
+ * or not 4-byte aligned src / dst, or src == dst.  n_cols == 0 returns HBK_OK without touching a device.  No
+ * workspace, no host synchronisation: capturable.  Detected by the presence of the symbol; the version stays
+ * that of 0.2.0. */
+#define HBK_HASH_MAX_MOVES 8
+typedef struct {            /* one per-slot array that travels with its key, in 4-byte words */
+  const void* src;
+  void* dst;
+  int32_t words;            /* >= 1: words per row (fp32 rows, int32 metadata: copied bit for bit) */
+  int32_t src_pitch;        /* words between rows; 0 = words */
+  int32_t dst_pitch;
+} hbk_hash_move_t;
+typedef struct {
+  const int64_t* src_keys;  /* device [src_slab_count * src_slab_size], 8-byte aligned */
+  int64_t src_slab_count;
+  int32_t src_slab_size;    /* 1..64 */
+  int64_t* dst_keys;        /* device [dst_slab_count * dst_slab_size], 8-byte aligned, all EMPTY on entry */
+  int64_t dst_slab_count;
+  int32_t dst_slab_size;    /* 1..64 */
+  int32_t expiring;         /* != 0: a TOMBSTONE in src is skipped; 0: INT64_MIN + 1 is an ordinary key */
+  int32_t n_moves;          /* 0..HBK_HASH_MAX_MOVES */
+  hbk_hash_move_t moves[HBK_HASH_MAX_MOVES];
+  int64_t* new_slots;       /* device int64 [src capacity] or NULL */
+  int32_t* counts;          /* device int32[2] {n_moved, n_failed}, added to; or NULL */
+} hbk_hash_rehash_column_t;
+int hbk_hash_rehash_n(int32_t n_cols, const hbk_hash_rehash_column_t* cols, hbk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Communicator lifecycle: HbGetNcclId / HbCreateNcclCollective /
