@@ -101,6 +101,21 @@ class HashAdmission(C.Structure):
               ('seed', C.c_int64), ('filtered', C.c_void_p)]
 
 
+HASH_MAX_RUNS_PER_LAUNCH = 256
+
+
+class HashRun(C.Structure):
+  """hbk_hash_run_t"""
+  _fields_ = [('keys', C.c_void_p), ('slots', C.c_void_p), ('n_keys', C.c_int64)]
+
+
+class ShardedHash(C.Structure):
+  """hbk_sharded_hash_t"""
+  _fields_ = [('keys_cache', C.c_void_p), ('slab_count', C.c_int64), ('slab_size', C.c_int32),
+              ('counts', C.c_void_p), ('init_scale', C.c_float), ('seed', C.c_int64), ('exp', HashExpiry),
+              ('adm', HashAdmission), ('insert', C.c_int32)]
+
+
 class HashFill(C.Structure):
   """hbk_hash_fill_t"""
   _fields_ = [('base', C.c_void_p), ('pitch', C.c_int32), ('dim', C.c_int32), ('value', C.c_float)]
@@ -210,6 +225,7 @@ def _declare(l):
     'hbk_hash_insert_admit_n': (C.c_int, [i32, vp, vp, i32, vp]),
     'hbk_hash_insert_expiring_admit_n': (C.c_int, [i32, vp, vp, vp, i32, vp]),
     'hbk_hash_rehash_n': (C.c_int, [i32, vp, vp]),
+    'hbk_hash_translate_runs_n': (C.c_int, [i32, vp, vp, vp, vp, vp, i32, vp]),
     'hbk_comm_get_id': (C.c_int, [vp]),
     'hbk_comm_rccl_versions': (C.c_int, [vp, vp]),
     'hbk_comm_create': (C.c_int, [vp, vp, i32, i32, i32]),
@@ -232,6 +248,7 @@ def _declare(l):
     'hbk_sharded_destroy': (C.c_int, [vp]),
     'hbk_sharded_set_hot_rows': (C.c_int, [vp, vp]),
     'hbk_sharded_set_max_norms': (C.c_int, [vp, vp]),
+    'hbk_sharded_set_hash_tables': (C.c_int, [vp, vp]),
     'hbk_sharded_lookup_fwd': (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
     'hbk_sharded_lookup_fwd_weighted': (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     'hbk_sharded_prefetch_on': (C.c_int, [vp, vp, vp, vp]),

@@ -64,6 +64,12 @@
 // keys were all resolved returns after one coalesced read of slots.  The loops are the ones above, with their
 // bounds; the sketch loops run `depth` <= 8 times.  The provisional -2 in slots is overwritten by phase 2 for
 // every occurrence that carries it.
+//
+// Runs (hbk_hash_translate_runs_n): the same kernels with Args = RunsArgs<the entry's Args>.  Only how a tile finds
+// its work differs -- its run, by up to four ballots, and through the run its column; everything after that is
+// the body above, so the memory rules, the bounds and the one-inserter argument hold unchanged: occurrences of a
+// key in different runs of a column are occurrences of that key in one launch.  The instantiations without runs
+// are the kernels they were, instruction for instruction.
 #include <math.h>
 
 #include "common.h"
@@ -134,6 +140,70 @@ __device__ inline int find_column(const HashArgs& a, int b) {
   const int ci = (int)__builtin_popcountll(__ballot(t0 <= b)) - 1;
   return __builtin_amdgcn_readfirstlane(ci);
 }
+
+// Keys that arrive as runs (hbk_hash_translate_runs_n): a column's keys are several arrays, each with its own
+// slots.  The launch is tiled over the RUNS; a run names its column, whose HashCol.keys / slots / n_keys and
+// the tile_start of the base arguments are not read.
+constexpr int kMaxRunsPerLaunch = HBK_HASH_MAX_RUNS_PER_LAUNCH;
+static_assert(kMaxRunsPerLaunch % kWave == 0, "one ballot per 64 runs");
+
+struct Run {
+  const int64_t* keys;
+  int64_t* slots;
+  int64_t n_keys;
+  int32_t col;          // of the launch
+  int32_t pad_;
+};
+
+template <class Base>
+struct RunsArgs : Base {
+  int32_t n_runs;
+  int32_t run_tile_start[kMaxRunsPerLaunch + 1];
+  Run run[kMaxRunsPerLaunch];
+};
+
+// What a tile works on -- its run (0 without runs), its column, its place in the column's or run's keys, and
+// those keys and their slots -- by the kind of arguments: the column's own for the entries without runs, read
+// where the kernels always read them.
+template <class Args>
+__device__ inline int find_run(const Args&, int) { return 0; }
+template <class Args>
+__device__ inline int work_column(const Args&, const HashArgs& a, int, int b) { return find_column(a, b); }
+template <class Args>
+__device__ inline int work_tile(const Args&, const HashArgs& a, int, int ci, int b) { return b - a.tile_start[ci]; }
+template <class Args>
+__device__ inline const int64_t* work_keys(const Args&, const HashCol& c, int) { return c.keys; }
+template <class Args>
+__device__ inline int64_t* work_slots(const Args&, const HashCol& c, int) { return c.slots; }
+template <class Args>
+__device__ inline int64_t work_n_keys(const Args&, const HashCol& c, int) { return c.n_keys; }
+
+// last run whose first tile is <= b: find_column over up to four 64-wide ballots
+template <class Base>
+__device__ inline int find_run(const RunsArgs<Base>& r, int b) {
+  const int lane = (int)threadIdx.x & (kWave - 1);
+  int below = 0;
+#pragma unroll
+  for (int k = 0; k < kMaxRunsPerLaunch / kWave; ++k) {
+    if (k * kWave >= r.n_runs) break;   // (uniform)
+    const int i = k * kWave + lane;
+    const int t0 = i < r.n_runs ? r.run_tile_start[i] : 0x7fffffff;
+    below += (int)__builtin_popcountll(__ballot(t0 <= b));
+  }
+  return __builtin_amdgcn_readfirstlane(below - 1);
+}
+template <class Base>
+__device__ inline int work_column(const RunsArgs<Base>& r, const HashArgs&, int ri, int) { return r.run[ri].col; }
+template <class Base>
+__device__ inline int work_tile(const RunsArgs<Base>& r, const HashArgs&, int ri, int, int b) {
+  return b - r.run_tile_start[ri];
+}
+template <class Base>
+__device__ inline const int64_t* work_keys(const RunsArgs<Base>& r, const HashCol&, int ri) { return r.run[ri].keys; }
+template <class Base>
+__device__ inline int64_t* work_slots(const RunsArgs<Base>& r, const HashCol&, int ri) { return r.run[ri].slots; }
+template <class Base>
+__device__ inline int64_t work_n_keys(const RunsArgs<Base>& r, const HashCol&, int ri) { return r.run[ri].n_keys; }
 
 // float j of the initial row of `key` (include/hbk.h): exact in fp32 up to the final multiply
 __host__ __device__ inline float init_value(int64_t key, uint64_t seed, int j, float scale) {
@@ -207,7 +277,8 @@ __global__ __launch_bounds__(kBlock) void hash_insert_kernel(const Args args) {
   static_assert(PHASE == 0 || INSERT == (PHASE == 2), "phase 1 finds, phase 2 inserts");
   const HashArgs& a = hash_args(args);
   const int b = (int)blockIdx.x;
-  const int ci = find_column(a, b);
+  const int ri = find_run(args, b);
+  const int ci = work_column(args, a, ri, b);
   const HashCol& c = a.col[ci];
   const int lane = lane_id();
   const int wave = (int)(threadIdx.x >> 6);
@@ -217,9 +288,9 @@ __global__ __launch_bounds__(kBlock) void hash_insert_kernel(const Args args) {
   const int grp = lane >> group_log2;
   const int gbase = grp << group_log2;
   const int groups_per_wave = kWave >> group_log2;
-  const int64_t wave_in_col = (int64_t)(b - a.tile_start[ci]) * kWavesPerBlock + wave;
+  const int64_t wave_in_col = (int64_t)work_tile(args, a, ri, ci, b) * kWavesPerBlock + wave;
   const int64_t first_key = wave_in_col * groups_per_wave * kKeys;
-  const int64_t n_keys = c.n_keys;
+  const int64_t n_keys = work_n_keys(args, c, ri);
   if (first_key >= n_keys) return;   // (wave-uniform)
   const int64_t i0 = first_key + grp;   // + u * groups_per_wave
   const unsigned long long group_mask = (gsize == 64 ? ~0ull : ((1ull << gsize) - 1ull)) << gbase;
@@ -237,7 +308,7 @@ __global__ __launch_bounds__(kBlock) void hash_insert_kernel(const Args args) {
 #pragma unroll
     for (int u = 0; u < kKeys; ++u) {
       const int64_t i = i0 + (int64_t)u * groups_per_wave;
-      pending[u] = i < n_keys && c.slots[i] == kPending;
+      pending[u] = i < n_keys && work_slots(args, c, ri)[i] == kPending;
       any |= pending[u];
     }
     if (!__any(any)) return;
@@ -246,9 +317,9 @@ __global__ __launch_bounds__(kBlock) void hash_insert_kernel(const Args args) {
   for (int u = 0; u < kKeys; ++u) {
     const int64_t i = i0 + (int64_t)u * groups_per_wave;
     if constexpr (PHASE == 2) {
-      key[u] = pending[u] ? (long long)c.keys[i] : kEmptyKey;
+      key[u] = pending[u] ? (long long)work_keys(args, c, ri)[i] : kEmptyKey;
     } else {
-      key[u] = i < n_keys ? (long long)c.keys[i] : kEmptyKey;
+      key[u] = i < n_keys ? (long long)work_keys(args, c, ri)[i] : kEmptyKey;
     }
   }
   if constexpr (PHASE == 2) {
@@ -339,13 +410,13 @@ __global__ __launch_bounds__(kBlock) void hash_insert_kernel(const Args args) {
     }
     if constexpr (PHASE == 2) {
       if (pending[u] && sub == 0) {
-        c.slots[i] = result;
+        work_slots(args, c, ri)[i] = result;
         n_inserted += won ? 1 : 0;
         n_failed += admitted[u] && result < 0 ? 1 : 0;
         n_filtered += admitted[u] ? 0 : 1;
       }
     } else if (i < n_keys && sub == 0) {
-      c.slots[i] = result;
+      work_slots(args, c, ri)[i] = result;
       n_inserted += won ? 1 : 0;
       n_failed += (PHASE == 1 ? result == -1 : result < 0) ? 1 : 0;
     }
@@ -403,7 +474,8 @@ __global__ __launch_bounds__(kBlock) void hash_insert_expiring_kernel(const Args
   const ExpiringArgs& x = expiring_args(args);
   const HashArgs& a = x.h;
   const int b = (int)blockIdx.x;
-  const int ci = find_column(a, b);
+  const int ri = find_run(args, b);
+  const int ci = work_column(args, a, ri, b);
   const HashCol& c = a.col[ci];
   const ExpiryCol& e = x.e[ci];
   const int lane = lane_id();
@@ -414,9 +486,9 @@ __global__ __launch_bounds__(kBlock) void hash_insert_expiring_kernel(const Args
   const int grp = lane >> group_log2;
   const int gbase = grp << group_log2;
   const int groups_per_wave = kWave >> group_log2;
-  const int64_t wave_in_col = (int64_t)(b - a.tile_start[ci]) * kWavesPerBlock + wave;
+  const int64_t wave_in_col = (int64_t)work_tile(args, a, ri, ci, b) * kWavesPerBlock + wave;
   const int64_t first_key = wave_in_col * groups_per_wave * kKeys;
-  const int64_t n_keys = c.n_keys;
+  const int64_t n_keys = work_n_keys(args, c, ri);
   if (first_key >= n_keys) return;   // (wave-uniform)
   const int64_t i0 = first_key + grp;   // + u * groups_per_wave
   const unsigned long long group_mask = (gsize == 64 ? ~0ull : ((1ull << gsize) - 1ull)) << gbase;
@@ -434,7 +506,7 @@ __global__ __launch_bounds__(kBlock) void hash_insert_expiring_kernel(const Args
 #pragma unroll
     for (int u = 0; u < kKeys; ++u) {
       const int64_t i = i0 + (int64_t)u * groups_per_wave;
-      pending[u] = i < n_keys && c.slots[i] == kPending;
+      pending[u] = i < n_keys && work_slots(args, c, ri)[i] == kPending;
       any |= pending[u];
     }
     if (!__any(any)) return;
@@ -444,9 +516,9 @@ __global__ __launch_bounds__(kBlock) void hash_insert_expiring_kernel(const Args
   for (int u = 0; u < kKeys; ++u) {
     const int64_t i = i0 + (int64_t)u * groups_per_wave;
     if constexpr (PHASE == 2) {
-      key[u] = pending[u] ? (long long)c.keys[i] : kEmptyKey;
+      key[u] = pending[u] ? (long long)work_keys(args, c, ri)[i] : kEmptyKey;
     } else {
-      key[u] = i < n_keys ? (long long)c.keys[i] : kEmptyKey;
+      key[u] = i < n_keys ? (long long)work_keys(args, c, ri)[i] : kEmptyKey;
     }
     if (key[u] == kTombstoneKey) key[u] = kEmptyKey;   // neither sentinel is ever stored: -1, counted as failed
   }
@@ -552,7 +624,7 @@ __global__ __launch_bounds__(kBlock) void hash_insert_expiring_kernel(const Args
     }
     if constexpr (PHASE == 2) {
       if (pending[u] && sub == 0) {
-        c.slots[i] = result;
+        work_slots(args, c, ri)[i] = result;
         n_inserted += won ? 1 : 0;
         n_reused += reused ? 1 : 0;
         n_failed += admitted[u] && result < 0 ? 1 : 0;
@@ -561,7 +633,7 @@ __global__ __launch_bounds__(kBlock) void hash_insert_expiring_kernel(const Args
       seen_slot[u] = pending[u] && sub == 0 ? result : -1;
     } else {
       if (i < n_keys && sub == 0) {
-        c.slots[i] = result;
+        work_slots(args, c, ri)[i] = result;
         n_inserted += won ? 1 : 0;
         n_reused += reused ? 1 : 0;
         n_failed += (PHASE == 1 ? result == -1 : result < 0) ? 1 : 0;
@@ -874,4 +946,162 @@ extern "C" int hbk_hash_insert_expiring_admit_n(int32_t n_cols, const hbk_hash_c
     }
   }
   return HBK_OK;
+}
+
+// ---- keys that arrive as runs ---------------------------------------------------------------------------
+namespace hbk {
+namespace {
+
+static_assert(sizeof(RunsArgs<HashArgs>) <= 24576, "kernarg budget");
+static_assert(sizeof(RunsArgs<ExpiringAdmitArgs>) <= 24576, "kernarg budget");
+
+// the parts of the base arguments a column is described into (nullptr: the table kind has none)
+inline HashArgs& hash_part(HashArgs& a) { return a; }
+inline HashArgs& hash_part(AdmitArgs& a) { return a.h; }
+inline HashArgs& hash_part(ExpiringArgs& a) { return a.h; }
+inline HashArgs& hash_part(ExpiringAdmitArgs& a) { return a.x.h; }
+inline ExpiryCol* expiry_part(HashArgs&) { return nullptr; }
+inline ExpiryCol* expiry_part(AdmitArgs&) { return nullptr; }
+inline ExpiryCol* expiry_part(ExpiringArgs& a) { return a.e; }
+inline ExpiryCol* expiry_part(ExpiringAdmitArgs& a) { return a.x.e; }
+inline AdmitCol* admit_part(HashArgs&) { return nullptr; }
+inline AdmitCol* admit_part(AdmitArgs& a) { return a.f; }
+inline AdmitCol* admit_part(ExpiringArgs&) { return nullptr; }
+inline AdmitCol* admit_part(ExpiringAdmitArgs& a) { return a.f; }
+
+// One pass over all runs of all columns with `kernel`: a launch takes up to kMaxRunsPerLaunch non-empty runs of
+// up to kMaxColsPerLaunch columns (a column whose runs straddle two launches is described in both).
+template <class Base>
+int launch_runs(const char* who, int32_t n_cols, const hbk_hash_column_t* cols, const hbk_hash_expiry_t* exp,
+                const hbk_hash_admission_t* adm, const int32_t* n_runs, const hbk_hash_run_t* const* runs,
+                int32_t insert, void (*kernel)(const RunsArgs<Base>), hipStream_t stream) {
+  int32_t c = 0, r = 0;   // the next run to place
+  while (c < n_cols) {
+    RunsArgs<Base> args;
+    HashArgs& h = hash_part(static_cast<Base&>(args));
+    int32_t k = 0, nr = 0, described = -1;
+    int64_t tiles = 0;
+    h.tile_start[0] = 0;
+    args.run_tile_start[0] = 0;
+    while (c < n_cols && nr < kMaxRunsPerLaunch) {
+      if (r >= n_runs[c]) {
+        ++c;
+        r = 0;
+        continue;
+      }
+      const hbk_hash_run_t& run = runs[c][r];
+      if (run.n_keys == 0) {
+        ++r;
+        continue;
+      }
+      if (described != c) {
+        if (k == kMaxColsPerLaunch) break;
+        hbk_hash_column_t col = cols[c];   // (its keys / slots / n_keys are the runs')
+        col.keys = nullptr;
+        col.slots = nullptr;
+        col.n_keys = 0;
+        (void)describe_column(col, insert, &h.col[k]);
+        if (ExpiryCol* e = expiry_part(static_cast<Base&>(args))) describe_expiry(exp[c], e + k);
+        if (AdmitCol* f = admit_part(static_cast<Base&>(args))) describe_admission(adm[c], f + k);
+        described = c;
+        ++k;
+      }
+      const int64_t keys_per_block = (int64_t)(kBlock >> h.col[k - 1].group_log2) * kKeys;
+      tiles += (run.n_keys + keys_per_block - 1) / keys_per_block;
+      HBK_REQUIRE(tiles < (1ll << 31), "%s: grid too large", who);
+      args.run[nr].keys = run.keys;
+      args.run[nr].slots = run.slots;
+      args.run[nr].n_keys = run.n_keys;
+      args.run[nr].col = k - 1;
+      args.run[nr].pad_ = 0;
+      ++nr;
+      args.run_tile_start[nr] = (int32_t)tiles;
+      ++r;
+    }
+    if (nr == 0) continue;   // (only when every column is through)
+    h.n_cols = k;
+    args.n_runs = nr;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)tiles), dim3(kBlock), 0, stream, args);
+    HBK_HIP_OK(hipGetLastError());
+  }
+  return HBK_OK;
+}
+
+}  // namespace
+}  // namespace hbk
+
+// The four translate entries over keys that arrive as runs: one launch (two for filtered tables: every counting
+// launch of the call before any admitting one) while the non-empty runs stay within
+// HBK_HASH_MAX_RUNS_PER_LAUNCH and the columns within 64.
+extern "C" int hbk_hash_translate_runs_n(int32_t n_cols, const hbk_hash_column_t* cols,
+                                         const hbk_hash_expiry_t* exp, const hbk_hash_admission_t* adm,
+                                         const int32_t* n_runs, const hbk_hash_run_t* const* runs,
+                                         int32_t insert, hbk_stream_t stream_) {
+  using namespace hbk;
+  const char* who = "hash_translate_runs_n";
+  HBK_REQUIRE(n_cols >= 0, "%s: n_cols must be >= 0, got %d", who, n_cols);
+  HBK_REQUIRE(n_cols == 0 || cols != nullptr, "%s: cols is NULL", who);
+  HBK_REQUIRE(n_cols == 0 || (n_runs != nullptr && runs != nullptr), "%s: n_runs or runs is NULL", who);
+  const int64_t key_limit = exp != nullptr || adm != nullptr ? (1ll << 30) : (1ll << 31);
+  for (int32_t c = 0; c < n_cols; ++c) {
+    HBK_REQUIRE(n_runs[c] >= 0, "%s: column %d: n_runs must be >= 0, got %d", who, c, n_runs[c]);
+    HBK_REQUIRE(n_runs[c] == 0 || runs[c] != nullptr, "%s: column %d: runs is NULL with n_runs = %d", who, c,
+                n_runs[c]);
+    int64_t total = 0;
+    const hbk_hash_run_t* first = nullptr;
+    for (int32_t r = 0; r < n_runs[c]; ++r) {
+      const hbk_hash_run_t& run = runs[c][r];
+      HBK_REQUIRE(run.n_keys >= 0 && run.n_keys < (1ll << 31),
+                  "%s: column %d: run %d: n_keys must be in [0, 2^31), got %lld", who, c, r, (long long)run.n_keys);
+      HBK_REQUIRE(run.n_keys == 0 || (run.keys != nullptr && run.slots != nullptr),
+                  "%s: column %d: run %d: NULL buffer (keys and slots are needed with n_keys > 0)", who, c, r);
+      if (run.n_keys > 0 && first == nullptr) first = &run;
+      total += run.n_keys;
+      HBK_REQUIRE(total < key_limit, "%s: column %d: the runs sum to %lld keys or more: must stay below 2^%d%s", who,
+                  c, (long long)total, key_limit == (1ll << 30) ? 30 : 31,
+                  key_limit == (1ll << 30) ? " (a counter must not wrap)" : "");
+    }
+    // the column as the matching entry would see it: the concatenation of its runs
+    hbk_hash_column_t whole = cols[c];
+    whole.n_keys = total;
+    whole.keys = first != nullptr ? first->keys : nullptr;
+    whole.slots = first != nullptr ? first->slots : nullptr;
+    if (int rc = check_column(who, c, whole)) return rc;
+    if (adm != nullptr) {
+      if (int rc = check_admission(who, c, whole, adm[c])) return rc;
+    }
+    HBK_REQUIRE(exp == nullptr || total == 0 ||
+                    (exp[c].last_seen != nullptr && exp[c].freq != nullptr && exp[c].step != nullptr),
+                "%s: column %d: NULL expiry buffer (last_seen, freq and step are needed with keys)", who, c);
+  }
+  hipStream_t stream = as_stream(stream_);
+  if (adm != nullptr && insert != 0) {   // count, then admit
+    if (exp != nullptr) {
+      if (int rc = launch_runs<ExpiringAdmitArgs>(
+              who, n_cols, cols, exp, adm, n_runs, runs, insert,
+              hash_insert_expiring_kernel<false, 1, RunsArgs<ExpiringAdmitArgs>>, stream)) {
+        return rc;
+      }
+      return launch_runs<ExpiringAdmitArgs>(who, n_cols, cols, exp, adm, n_runs, runs, insert,
+                                            hash_insert_expiring_kernel<true, 2, RunsArgs<ExpiringAdmitArgs>>,
+                                            stream);
+    }
+    if (int rc = launch_runs<AdmitArgs>(who, n_cols, cols, exp, adm, n_runs, runs, insert,
+                                        hash_insert_kernel<false, 1, RunsArgs<AdmitArgs>>, stream)) {
+      return rc;
+    }
+    return launch_runs<AdmitArgs>(who, n_cols, cols, exp, adm, n_runs, runs, insert,
+                                  hash_insert_kernel<true, 2, RunsArgs<AdmitArgs>>, stream);
+  }
+  // no filter, or a find (which never touches the sketch)
+  if (exp != nullptr) {
+    return launch_runs<ExpiringArgs>(who, n_cols, cols, exp, nullptr, n_runs, runs, insert,
+                                     insert != 0 ? hash_insert_expiring_kernel<true, 0, RunsArgs<ExpiringArgs>>
+                                                 : hash_insert_expiring_kernel<false, 0, RunsArgs<ExpiringArgs>>,
+                                     stream);
+  }
+  return launch_runs<HashArgs>(who, n_cols, cols, nullptr, nullptr, n_runs, runs, insert,
+                               insert != 0 ? hash_insert_kernel<true, 0, RunsArgs<HashArgs>>
+                                           : hash_insert_kernel<false, 0, RunsArgs<HashArgs>>,
+                               stream);
 }

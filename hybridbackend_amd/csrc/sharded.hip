@@ -16,6 +16,11 @@
 //   backward  d(stitch+combiner) -> pack -> reverse alltoallv (forward's sizes, collective.py:334-347)
 //             -> unpack -> duplicate-row reduction (+ fused SGD) (R10: lookup_bwd.hip)
 //
+// Hash columns (hbk_sharded_set_hash_tables): the shard is a hash-keyed table keyed by the raw id.  The owner
+// translates the ids it received into slot numbers (hbk_hash_translate_runs_n over the W runs of the column,
+// where the gather would read its ids) into a plan-owned slot buffer laid out as the received ids; the gather
+// and the backward's owner reduce then read the slots with divisor 1.  A plan without one does none of this.
+//
 // Buffers whose size depends on what the peers send (known only after the size exchange)
 // are owned by the plan and grow on demand (hipMalloc, never shrinks); everything else is
 // caller-owned as usual.
@@ -546,6 +551,11 @@ struct hbk_sharded {
   hbk::SlotPair adam;   // Lazy Adam's m / v shards (hbk_sharded_set_adam_slots)
   hbk::SlotPair ftrl;   // FTRL's accum / linear shards (hbk_sharded_set_ftrl_slots)
   std::vector<float> max_norms;   // [N] the columns' max_norm (hbk_sharded_set_max_norms; 0: not clipped)
+  std::vector<hbk_sharded_hash_t> hash;   // [N] the hash columns' tables (hbk_sharded_set_hash_tables; keys_cache
+                                          // NULL: an ordinary column), or empty
+  bool any_hash = false;
+  hbk::Buffer slots_buf;          // hash columns: the slot of every id this rank owns, laid out as the received
+                                  // ids (the own slice too, wherever its ids stayed); lives until the next forward
   std::vector<const float*> id_weights;   // [N] per-id weights of the last forward (NULL: unweighted):
                                           // the stitch applies them, the backward's stitch too
   std::vector<int32_t> send_sizes;   // S [N][W] rows this rank requests from owner q, column c
@@ -712,7 +722,7 @@ extern "C" int hbk_sharded_destroy(hbk_sharded_t p) {
   if (p->pre_stream) (void)hipStreamSynchronize(p->pre_stream);
   for (hbk::Buffer* b : {&p->part_ws, &p->ids_buf, &p->rows_buf, &p->wire_ws, &p->bwd_ws,
                          &p->runs_dev, &p->dedup_tmp, &p->slot_send, &p->slot_recv, &p->token_buf,
-                         &p->bind_buf}) {
+                         &p->bind_buf, &p->slots_buf}) {
     b->release();
   }
   for (void* m : p->ipc_opened) (void)hipIpcCloseMemHandle(m);
@@ -1005,6 +1015,11 @@ extern "C" int hbk_sharded_p2p_bind(hbk_sharded_t p, float* const* outs, const i
   const int N = p->N, W = p->W, me = p->rank;
   p->p2p_bound = false;
   p->ps[0].pending = p->ps[1].pending = false;   // (a prefetch packed for another group count)
+  // (the same on every rank that set hash tables; before the option, so that the refusal names its reason)
+  if (p->any_hash) {
+    return fail(HBK_UNIMPLEMENTED, "sharded_p2p_bind: the plan has a hash column (hbk_sharded_set_hash_tables): "
+                "the p2p form has no owner-side translate");
+  }
   if (!p->p2p_opt) return fail(HBK_UNIMPLEMENTED, "sharded_p2p_bind: option sharded_p2p is off");
   HBK_REQUIRE(p->wire_dtype == HBK_FLOAT, "sharded_p2p_bind: the p2p form has no fp16 wire");
   HBK_REQUIRE(!p->any_dedup, "sharded_p2p_bind: not with requester-side dedup");
@@ -1144,6 +1159,100 @@ extern "C" int hbk_sharded_p2p_unbind(hbk_sharded_t p) {
   p->ps[0].pending = p->ps[1].pending = false;
   for (void* m : p->ipc_opened) (void)hipIpcCloseMemHandle(m);
   p->ipc_opened.clear();
+  return HBK_OK;
+}
+
+namespace hbk {
+namespace {
+// Stage C of a plan with hash columns: the ids of the group's hash columns -> slots, one
+// hbk_hash_translate_runs_n per table kind and insert flag present.  ids_at(q, c): where run (q, c) of the group
+// lies (int64 ids); its slots go to the run's place in the layout of the received ids.
+template <typename IdsAt>
+int translate_group(hbk_sharded* p, const Group& gr, IdsAt ids_at, int64_t* slots_base, hbk_stream_t stream) {
+  const int W = p->W, ng = gr.c1 - gr.c0;
+  for (int kind = 0; kind < 8; ++kind) {
+    const bool expiring = (kind & 1) != 0, filtered = (kind & 2) != 0, insert = (kind & 4) != 0;
+    std::vector<hbk_hash_column_t> cols;
+    std::vector<hbk_hash_expiry_t> exp;
+    std::vector<hbk_hash_admission_t> adm;
+    std::vector<int> members;
+    for (int c = 0; c < ng; ++c) {
+      const hbk_sharded_hash_t& t = p->hash[(size_t)(gr.c0 + c)];
+      if (t.keys_cache == nullptr || (t.exp.last_seen != nullptr) != expiring ||
+          (t.adm.sketch != nullptr) != filtered || (t.insert != 0) != insert) {
+        continue;
+      }
+      const hbk_sharded_column_t& col = p->cols[gr.c0 + c];
+      hbk_hash_column_t h;
+      memset(&h, 0, sizeof(h));
+      h.keys_cache = t.keys_cache;
+      h.slab_count = t.slab_count;
+      h.slab_size = t.slab_size;
+      h.counts = t.counts;
+      h.table = const_cast<float*>(col.shard);
+      h.dim = col.dim;
+      h.init_scale = t.init_scale;
+      h.seed = t.seed;
+      cols.push_back(h);
+      exp.push_back(t.exp);
+      adm.push_back(t.adm);
+      members.push_back(c);
+    }
+    if (members.empty()) continue;
+    std::vector<hbk_hash_run_t> runs(members.size() * (size_t)W);
+    std::vector<const hbk_hash_run_t*> run_ptrs(members.size());
+    std::vector<int32_t> n_runs(members.size(), W);
+    for (size_t k = 0; k < members.size(); ++k) {
+      const int c = members[k];
+      for (int q = 0; q < W; ++q) {
+        hbk_hash_run_t& r = runs[k * W + q];
+        r.n_keys = gr.R[(size_t)q * ng + c];
+        r.keys = reinterpret_cast<const int64_t*>(ids_at(q, c));
+        r.slots = slots_base + gr.id_recv + gr.lay.own_id_off[(size_t)q * ng + c];
+      }
+      run_ptrs[k] = runs.data() + k * W;
+    }
+    const int rc = hbk_hash_translate_runs_n((int32_t)members.size(), cols.data(), expiring ? exp.data() : nullptr,
+                                             filtered ? adm.data() : nullptr, n_runs.data(), run_ptrs.data(),
+                                             insert ? 1 : 0, stream);
+    if (rc != HBK_OK) return rc;
+  }
+  return HBK_OK;
+}
+}  // namespace
+}  // namespace hbk
+
+// The hash columns of a plan (include/hbk.h): plan state like the max_norms, set by every rank for itself.
+extern "C" int hbk_sharded_set_hash_tables(hbk_sharded_t p, const hbk_sharded_hash_t* tables) {
+  using namespace hbk;
+  const char* who = "sharded_set_hash_tables";
+  HBK_REQUIRE(p != nullptr, "%s: plan is NULL", who);
+  bool any = false;
+  for (int c = 0; tables != nullptr && c < p->N; ++c) {
+    const hbk_sharded_hash_t& t = tables[c];
+    if (t.keys_cache == nullptr) continue;
+    any = true;
+    const hbk_sharded_column_t& col = p->cols[c];
+    HBK_REQUIRE(col.bucket == 0, "%s: column %d: a hash column takes raw ids: its bucket must be 0, got %lld", who,
+                c, (long long)col.bucket);
+    HBK_REQUIRE(t.slab_size >= 1 && t.slab_size <= 64, "%s: column %d: slab_size must be in [1, 64], got %d", who,
+                c, t.slab_size);
+    HBK_REQUIRE(t.slab_count >= 1 && t.slab_count <= ((1ll << 62) / 64),
+                "%s: column %d: slab_count %lld is out of range", who, c, (long long)t.slab_count);
+    HBK_REQUIRE(col.rows_local == t.slab_count * t.slab_size,
+                "%s: column %d: the shard has %lld rows, the table's capacity is %lld (slab_count * slab_size)", who,
+                c, (long long)col.rows_local, (long long)(t.slab_count * t.slab_size));
+    HBK_REQUIRE(t.exp.last_seen == nullptr || (t.exp.freq != nullptr && t.exp.step != nullptr),
+                "%s: column %d: an expiring table needs last_seen, freq and step", who, c);
+  }
+  if (any && p->p2p_bound) {
+    return fail(HBK_UNIMPLEMENTED, "%s: the plan is p2p-bound (hbk_sharded_p2p_bind): the p2p form has no "
+                "owner-side translate", who);
+  }
+  p->hash.clear();
+  if (any) p->hash.assign(tables, tables + p->N);
+  p->any_hash = any;
+  p->have_step = false;   // (a step translated under other tables is not differentiated)
   return HBK_OK;
 }
 
@@ -1332,6 +1441,9 @@ extern "C" int hbk_sharded_lookup_fwd_begin(hbk_sharded_t p, const int64_t* cons
   HBK_REQUIRE((int64_t)(rows_send_bytes / 4) + tot_req_floats < (1ll << 32),
               "sharded_lookup_fwd: more than 2^32 floats (16 GB) of rows per step on one rank");
   if ((rc = p->runs_dev.ensure(sizeof(int64_t) * 7 * (size_t)N * W)) != HBK_OK) return rc;
+  const bool any_hash = p->any_hash;   // (never with p2p: hbk_sharded_set_hash_tables, hbk_sharded_p2p_bind)
+  if (any_hash && (rc = p->slots_buf.ensure((size_t)tot_own_ids * 8 + 16)) != HBK_OK) return rc;
+  int64_t* const slots_base = reinterpret_cast<int64_t*>(p->slots_buf.ptr);
   if (p2p) {
     if ((rc = p->slot_send.ensure((size_t)tot_req_ids * 4 + 16)) != HBK_OK) return rc;
     if ((rc = p->slot_recv.ensure((size_t)tot_own_ids * 4 + 16)) != HBK_OK) return rc;
@@ -1399,8 +1511,20 @@ extern "C" int hbk_sharded_lookup_fwd_begin(hbk_sharded_t p, const int64_t* cons
         }
       }
     }
+    // hash columns, owner side of the backward: where run (q, c) sits in the slot buffer (the layout of the
+    // received ids, the own slice included); shares its place with the p2p tables, which it never meets
+    if (any_hash) {
+      for (const Group& gr : groups) {
+        const int ng = gr.c1 - gr.c0;
+        for (int c = 0; c < ng; ++c) {
+          for (int q = 0; q < W; ++q) {
+            h_soff[(size_t)(gr.c0 + c) * W + q] = gr.id_recv + gr.lay.own_id_off[(size_t)q * ng + c];
+          }
+        }
+      }
+    }
     HBK_HIP_OK(hipMemcpyAsync(p->runs_dev.ptr, p->host_runs,
-                              sizeof(int64_t) * (p2p ? 7 : 5) * (size_t)N * W,
+                              sizeof(int64_t) * (p2p ? 7 : any_hash ? 6 : 5) * (size_t)N * W,
                               hipMemcpyHostToDevice, stream));
   }
   // stage A: the ids of every group peer-major -- run_partition has done it (pack_ids_kernel, while
@@ -1483,6 +1607,13 @@ extern "C" int hbk_sharded_lookup_fwd_begin(hbk_sharded_t p, const int64_t* cons
     const int ng = gr.c1 - gr.c0;
     if (hop) HBK_HIP_OK(hipStreamWaitEvent(stream, p->ev[1][g], 0));
     if (hop && p2p) HBK_HIP_OK(hipStreamWaitEvent(stream, p->ev[3][0], 0));
+    // where run (q, c) of the group's received ids lies: the own slice in the outgoing buffer when it stayed
+    auto run_ids = [&](int q, int c) {
+      return zc && q == me
+                 ? ids_send_base + (gr.id_send + gr.lay.req_id_off[(size_t)q * ng + c]) * id_bytes
+                 : ids_recv_base + (gr.id_recv + gr.lay.own_id_off[(size_t)q * ng + c]) * id_bytes;
+    };
+    if (any_hash && (rc = translate_group(p, gr, run_ids, slots_base, stream_)) != HBK_OK) return rc;
     std::vector<hbk_lookup_column_t> v;
     std::vector<float> clip;   // the owner clips: every virtual column carries its column's max_norm
     v.reserve((size_t)ng * W);
@@ -1498,7 +1629,6 @@ extern "C" int hbk_sharded_lookup_fwd_begin(hbk_sharded_t p, const int64_t* cons
         h.rows = col.rows_local;
         h.dim = col.dim;
         h.ids_dtype = id_dtype;
-        h.ids = ids_recv_base + (gr.id_recv + gr.lay.own_id_off[(size_t)q * ng + c]) * id_bytes;
         h.n_ids = n;
         h.n_segments = n;
         h.divisor = W;
@@ -1506,8 +1636,14 @@ extern "C" int hbk_sharded_lookup_fwd_begin(hbk_sharded_t p, const int64_t* cons
         h.hot_rows = col.hot_rows;
         int64_t out_at = gr.row_send + gr.lay.own_row_off[(size_t)q * ng + c];   // elements
         float* out_base = rows_send_base;
+        h.ids = run_ids(q, c);
+        if (any_hash && p->hash[(size_t)(gr.c0 + c)].keys_cache != nullptr) {
+          // a hash column: the rows are named by the slots just translated (-1: a zero row)
+          h.ids_dtype = HBK_INT64;
+          h.ids = slots_base + gr.id_recv + gr.lay.own_id_off[(size_t)q * ng + c];
+          h.divisor = 1;
+        }
         if (zc && q == me) {
-          h.ids = ids_send_base + (gr.id_send + gr.lay.req_id_off[(size_t)q * ng + c]) * id_bytes;
           out_at = gr.row_recv + gr.lay.req_row_off[(size_t)q * ng + c];
           out_base = rows_recv_base;
         }
@@ -2018,6 +2154,13 @@ static int sharded_bwd(hbk_sharded_t p, const float* const* grads, const int32_t
     h.run_ids = d_oids + (size_t)c * W;
     h.run_grads = d_ograds + (size_t)c * W;
     h.n_runs = W;
+    if (p->any_hash && p->hash[(size_t)c].keys_cache != nullptr) {
+      // a hash column: the rows are the slots the forward translated, in the slot buffer's own layout
+      h.ids_dtype = HBK_INT64;
+      h.ids = p->slots_buf.ptr;
+      h.divisor = 1;
+      h.run_ids = d_start + 5 * (size_t)N * W + (size_t)c * W;
+    }
   }
   size_t ws = 0;
   for (int g = 0; g < G; ++g) {

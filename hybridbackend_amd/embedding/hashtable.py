@@ -27,8 +27,12 @@ host read) whether a table must grow or shed its tombstones.  A rehash changes s
 addresses: :meth:`HashGroupLookup.rebind`, a new ``GroupLookupGrad`` over the new slot tensors, a new capture
 of any captured graph.
 
+Sharded hash tables: :class:`hybridbackend_amd.embedding.ShardedHashGroupLookup` (sharded_hash.py) puts tables of
+W ranks behind the sharded lookup step, owner = :func:`hash_owner`; :meth:`HashTable.load_owned` restores
+``items()`` of W ranks onto W' ranks.
+
 Not provided: growth from inside a translate launch (a full table answers -1 until ``maybe_grow`` ran), a
-compaction that keeps the tensors' addresses, sharded hash tables, feature-column integration, the TF shim op.
+compaction that keeps the tensors' addresses, feature-column integration, the TF shim op.
 """
 import ctypes as C
 import math
@@ -221,6 +225,14 @@ class HashTable:
     self.table[slots] = rows
     return slots
 
+  def load_owned(self, keys, rows, world, rank):
+    """:meth:`load` of the keys rank ``rank`` of ``world`` owns (:func:`hash_owner`) and their rows: handed the
+    concatenated ``items()`` of W ranks on each of W' ranks, the tables are resharded.  Returns the slots of the
+    keys loaded."""
+    check_ids([keys], [self])
+    mine = hash_owner(keys, world) == int(rank)
+    return self.load(keys[mine], rows[mine])
+
   def variables(self, name):
     """The raw arrays for ``training.saver.Saver``: they restore into a table of the SAME geometry
     (capacity, slab_size); then :meth:`recount`.  ``items()`` / ``load()`` is the geometry-free form."""
@@ -364,6 +376,15 @@ def _companions(table, slots):
       raise _bad(f'slots[{n}]: fill_value must be finite, got {p[1]!r}')
     out.append((t, value))
   return out
+
+
+def hash_owner(ids, world):
+  """The rank that owns every id of a sharded hash table: ``floormod(id, world)`` (what the sharded step's
+  partition computes: negative ids have an owner), as a tensor op."""
+  world = int(world)
+  if world < 1:
+    raise _bad(f'world must be >= 1, got {world}')
+  return torch.remainder(ids, world)
 
 
 def hash_rehash(tables, capacities=None, slab_sizes=None, slots=None):

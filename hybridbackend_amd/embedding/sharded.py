@@ -195,11 +195,15 @@ class ShardedGroupLookup:
     wire = _lib.HALF if self.wire_dtype == torch.float16 else _lib.FLOAT
     _lib.check(self._lib.hbk_sharded_create(
       C.byref(self._plan_handle), self.coll._handle, n, cols, wire))
+    self._plan_created()
     if any(self.max_norms):   # (plan state: set again on every plan this object creates)
       _lib.check(self._lib.hbk_sharded_set_max_norms(self._plan_handle, (C.c_float * n)(*self.max_norms)))
     for opt, pairs in ((self.adam, self.moments), (self.ftrl, self.ftrl_slots)):
       if pairs is not None:
         opt.set_sharded_slots(self._plan_handle, pairs)
+
+  def _plan_created(self):
+    """Hook: plan state a subclass sets right after creation (ShardedHashGroupLookup: its tables)."""
 
   def last_host_us(self):
     """Host time of the last forward step in microseconds: (enqueueing the partition and the
@@ -647,6 +651,9 @@ class PipelinedLookup:
     pipeline is then correct but serialises)."""
     if len(plans) < 2:
       raise ValueError('PipelinedLookup needs at least two plans')
+    if any(getattr(p, 'tables', None) is not None for p in plans):
+      raise _lib.HbkError(_lib.UNIMPLEMENTED, 'PipelinedLookup over hash columns (ShardedHashGroupLookup): the '
+                          'translate of a step inserts into tables the step before still reads')
     self.plans = list(plans)
     if stream_exchanges:
       with _PLAN_LOCK:

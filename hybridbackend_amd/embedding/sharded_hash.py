@@ -1,0 +1,141 @@
+"""Sharded hash tables: hash-keyed columns behind the sharded lookup step (``hbk_sharded_set_hash_tables``,
+include/hbk.h; DeepRec partitions its EmbeddingVariable the same way, the reference's ``EmbeddingService`` sits
+behind its sharded lookup).
+
+Every rank holds one :class:`HashTable` per column.  An id belongs to rank ``floormod(id, W)``
+(:func:`hash_owner`); the step brings each owner the raw int64 ids it owns, the owner translates them into row
+numbers of its table (one ``hbk_hash_translate_runs_n`` call per table kind, over the W runs where they lie),
+gathers those rows, and in the backward reduces and steps them -- everything else of the step is
+:class:`ShardedGroupLookup`'s, unchanged.
+"""
+import ctypes as C
+
+from hybridbackend_amd import _lib
+from hybridbackend_amd.embedding import hashtable as _ht
+from hybridbackend_amd.embedding import optimizer as _opt
+from hybridbackend_amd.embedding.sharded import ShardedGroupLookup
+
+
+class ShardedHashGroupLookup(ShardedGroupLookup):
+  """N hash-keyed columns, each sharded over the ranks by ``floormod(id, W)``.
+
+  Args:
+    tables: this rank's :class:`HashTable` per column (plain, expiring and filtered ones may be mixed; ranks
+      may differ in capacity and geometry, not in dim).
+    coll, combiners, wire_dtype, dedup, max_norms, hot_rows, world_size: :class:`ShardedGroupLookup`'s.
+    train: True -- ids the owner never saw are inserted (a filtered table: once admitted); False -- a pure find:
+      they read as zero rows, and neither ``size()`` nor ``counts`` moves.
+    accums / moments, adam / ftrl_slots, ftrl: the optimizer slots of the tables, ``[capacity, dim]`` each, as for
+      :class:`ShardedGroupLookup`.
+    initial_accumulator_value: what :meth:`maybe_grow` fills the rows of a grown Adagrad accumulator with that no
+      key holds (FTRL's comes from ``ftrl``).
+
+  ``__call__``, ``bind``, ``launch``, ``backward``, ``prefetch`` and ``close`` are inherited; in the slices
+  ``backward`` returns, ``unique_rows`` are slot numbers of this rank's tables (``tables[c].keys[unique_rows]``
+  names the ids).  ``sp_weights`` and ``p2p_bind`` are refused by the library; ``PipelinedLookup`` refuses
+  objects of this class.  Eviction, ``set_step`` and filter maintenance are the tables' own methods: they move
+  no tensor, so the plan stays valid.  A rehash of a table does: :meth:`rebind` (or :meth:`maybe_grow`, which
+  does both)."""
+
+  def __init__(self, tables, coll, combiners='sum', wire_dtype=None, dedup=False, max_norms=None, train=True,
+               accums=None, moments=None, adam=None, ftrl_slots=None, ftrl=None, hot_rows=False, world_size=None,
+               initial_accumulator_value=0.1):
+    self.tables = list(tables)
+    _ht.same_device(self.tables)
+    self.train = bool(train)
+    self.initial_accumulator_value = float(initial_accumulator_value)
+    self._rows = [t.table for t in self.tables]
+    super().__init__(self._rows, coll, buckets=None, combiners=combiners, wire_dtype=wire_dtype,
+                     world_size=world_size, accums=accums, hot_rows=hot_rows, dedup=dedup, moments=moments, adam=adam,
+                     ftrl_slots=ftrl_slots, ftrl=ftrl, max_norms=max_norms)
+
+  def _current(self):
+    if any(t.table is not r for t, r in zip(self.tables, self._rows)):
+      raise _ht._bad('a table was rehashed: rebind() first')   # pylint: disable=protected-access
+
+  def _plan(self):
+    self._current()
+    return super()._plan()
+
+  def _plan_created(self):
+    """The tables' descriptors, right after the plan's creation; a refusal leaves no plan behind."""
+    n = len(self.tables)
+    arr = (_lib.ShardedHash * n)()
+    for c, t in enumerate(self.tables):
+      _lib.require_device_tensor(t.keys, 'keys')
+      h = arr[c]
+      h.keys_cache, h.slab_count, h.slab_size = t.keys.data_ptr(), t.slab_count, t.slab_size
+      # a find counts nothing: `counts` is the table's record of what was inserted and refused
+      h.counts = t.counts.data_ptr() if self.train else None
+      h.init_scale, h.seed = t.init_scale, t.seed
+      if t.expiring:
+        t._describe_expiry(h.exp)        # pylint: disable=protected-access
+      if t.min_freq:
+        t._describe_admission(h.adm)     # pylint: disable=protected-access
+      h.insert = 1 if self.train else 0
+    try:
+      _lib.check(self._lib.hbk_sharded_set_hash_tables(self._plan_handle, arr))
+    except _lib.HbkError:
+      self.close()
+      raise
+
+  def p2p_bind(self, outs):
+    """Refused (``hbk_sharded_p2p_bind``: the p2p form has no owner-side translate)."""
+    n = len(self.shards)
+    _lib.check(self._lib.hbk_sharded_p2p_bind(
+      self._plan(), _lib.ptr_array([o.data_ptr() for o in outs]), (C.c_int32 * n)(),
+      _lib.i64_array([int(o.shape[0]) for o in outs]), _lib.current_stream(self.device)))
+    raise _lib.HbkError(_lib.INTERNAL, 'p2p_bind: a plan with hash columns was bound')
+
+  def rebind(self, accums=None, moments=None, ftrl_slots=None):
+    """After a rehash of any table (``hash_rehash``, ``HashTable.maybe_grow``): the plan is closed and the
+    owner-side state built again over the tables' current tensors and the given slot tensors (the companions the
+    rehash returned; None: the ones bound now, which must still have the tables' shapes).  Until then every call
+    on the object is refused.  Local to the rank: no exchange."""
+    self.close()
+    rows = [t.table for t in self.tables]
+    if accums is None:
+      accums = self.accums
+    if accums is not None:
+      accums = list(accums)
+      if len(accums) != len(rows) or any(tuple(a.shape) != tuple(r.shape) for a, r in zip(accums, rows)):
+        raise _ht._bad('rebind: accums must be one fp32 [capacity, dim] tensor per table')   # pylint: disable=protected-access
+    moments = self.moments if moments is None else moments
+    ftrl_slots = self.ftrl_slots if ftrl_slots is None else ftrl_slots
+    what = 'ShardedHashGroupLookup.rebind'
+    new_moments, adam = _opt.bind_slots(_opt.LazyAdam, moments, self.adam, rows, what)
+    new_ftrl, ftrl = _opt.bind_slots(_opt.Ftrl, ftrl_slots, self.ftrl, rows, what)
+    self.shards, self._rows, self.accums = rows, rows, accums
+    self.moments, self.adam, self.ftrl_slots, self.ftrl = new_moments, adam, new_ftrl, ftrl
+    self._call_cache = self._keep = self._auto_state = None
+    self._setup()
+
+  def maybe_grow(self, max_load=0.75, factor=2.0):
+    """:meth:`HashTable.maybe_grow` on every table of this rank, the bound optimizer slots moving along as
+    companions (the rows no key holds afterwards: Adagrad's accumulator ``initial_accumulator_value``, Adam's m /
+    v 0, FTRL's accum its ``initial_accumulator_value`` and linear 0), then :meth:`rebind` with the new tensors
+    if any table was rehashed.  Local to the rank: no exchange, and ranks need not agree.  Returns per table
+    whether it was rehashed."""
+    kinds = []   # (attribute, index in a pair or None, fill value)
+    if self.accums is not None:
+      kinds.append(('accums', None, self.initial_accumulator_value))
+    if self.moments is not None:
+      kinds += [('moments', 0, 0.0), ('moments', 1, 0.0)]
+    if self.ftrl_slots is not None:
+      kinds += [('ftrl_slots', 0, self.ftrl.initial_accumulator_value), ('ftrl_slots', 1, 0.0)]
+    new = {name: [list(x) if k is not None else x for x in getattr(self, name)]
+           for name, k, _ in kinds}
+    grown = []
+    for c, t in enumerate(self.tables):
+      comp = [((getattr(self, name)[c] if k is None else getattr(self, name)[c][k]), fill) for name, k, fill in kinds]
+      out = t.maybe_grow(max_load, factor, comp)
+      grown.append(out is not None)
+      for (name, k, _), x in zip(kinds, out or ()):
+        if k is None:
+          new[name][c] = x
+        else:
+          new[name][c][k] = x
+    if any(grown):
+      pairs = {name: [tuple(p) for p in new[name]] for name in ('moments', 'ftrl_slots') if name in new}
+      self.rebind(accums=new.get('accums'), moments=pairs.get('moments'), ftrl_slots=pairs.get('ftrl_slots'))
+    return grown

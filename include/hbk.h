@@ -866,6 +866,45 @@ int hbk_hash_insert_expiring_admit_n(int32_t n_cols, const hbk_hash_column_t* co
                                      const hbk_hash_expiry_t* exp, const hbk_hash_admission_t* adm,
                                      int32_t insert, hbk_stream_t stream);
 
+/* Keys that arrive as runs.  On the owner of a sharded hash table (hbk_sharded_set_hash_tables below) the ids of
+ * one column are W separate arrays, one per requester, each with its own place for the answers.  Handing them
+ * to the four entries above as W virtual columns costs one 64-column launch per 64 runs (26 columns x 8 peers:
+ * 4 launches, 8 for filtered tables) and grows with W.  hbk_hash_translate_runs_n takes the runs as they lie.
+ *
+ * cols[c] describes table c as above; its keys, slots and n_keys are IGNORED: runs[c][0 .. n_runs[c]) are
+ * column c's keys and slots.  exp and adm are each NULL or hold one record per column, and name the table kind
+ * of ALL columns of the call: (NULL, NULL) = hbk_hash_insert_n, (exp, NULL) = hbk_hash_insert_expiring_n,
+ * (NULL, adm) = hbk_hash_insert_admit_n, (exp, adm) = hbk_hash_insert_expiring_admit_n.
+ *
+ * Semantics: exactly those of the matching entry called ONCE on the concatenation of column c's runs --
+ * placement, row initialisation, counts, stats, last_seen, freq and the sketch.  n_inserted counts a key once
+ * even when it appears in several runs (one compare-and-swap wins).  For filtered tables the counting phase
+ * covers all runs of all columns before any admitting launch starts: an id seen once in each of two runs, with
+ * min_freq = 2, is admitted by the call.  insert == 0 is the find of the entry without a filter.
+ *
+ * Launches: one per call, two for filtered tables (count, admit), while the non-empty runs number at most
+ * HBK_HASH_MAX_RUNS_PER_LAUNCH and the columns at most 64 (26 columns x 8 runs = 208 fit).  The kernels are
+ * those of the four entries with another way to find a tile's work: the tile's RUN is found with up to four
+ * 64-wide ballots over the runs' first tiles, and the run names its column.  Beyond the limits the call is
+ * chunked, every counting launch still before any admitting one.
+ *
+ * Refused (HBK_INVALID_ARGUMENT) before any device work: everything the matching entry refuses of a column;
+ * NULL n_runs or runs with n_cols > 0; n_runs[c] < 0; NULL runs[c] with n_runs[c] > 0; a run with n_keys < 0, or
+ * with n_keys > 0 and NULL keys or slots; a column whose runs sum to >= 2^31 keys (>= 2^30 with exp or adm: a
+ * counter must not wrap).  Zero runs and zero-length runs are fine.  No workspace, no host synchronisation:
+ * capturable.  Detected by the presence of the symbol; the version stays that of 0.2.0. */
+#define HBK_HASH_MAX_RUNS_PER_LAUNCH 256
+typedef struct {
+  const int64_t* keys;    /* device [n_keys] */
+  int64_t* slots;         /* device [n_keys]: row number or -1 */
+  int64_t n_keys;
+} hbk_hash_run_t;
+int hbk_hash_translate_runs_n(int32_t n_cols, const hbk_hash_column_t* cols,
+                              const hbk_hash_expiry_t* exp,      /* NULL, or [n_cols] */
+                              const hbk_hash_admission_t* adm,   /* NULL, or [n_cols] */
+                              const int32_t* n_runs, const hbk_hash_run_t* const* runs,
+                              int32_t insert, hbk_stream_t stream);
+
 /* Rehash: growth and tombstone compaction on the device.  A full table answers -1 for ever, and an expiring
  * table's probes get longer with every tombstone; both are cured by moving every live key into a fresh key
  * array -- of a larger geometry, or of the same one -- with its rows.  hbk_hash_rehash_n does that for N tables
@@ -1100,6 +1139,39 @@ int hbk_sharded_set_hot_rows(hbk_sharded_t plan, const int32_t* hot_rows);
  * p2p-bound plan (hbk_sharded_p2p_bind) refuses a forward with a clipped column: HBK_UNIMPLEMENTED
  * before any exchange.  Values are refused as in the clipped entries. */
 int hbk_sharded_set_max_norms(hbk_sharded_t plan, const float* max_norms);
+/* Sharded hash tables: columns of the plan whose shard is a hash-keyed table (hbk_hash_column_t above) keyed by
+ * the RAW id.  owner = floormod(id, W) as for every column (the partition uses floormod: negative ids have an
+ * owner); what changes is the owner's side: instead of row = id // W in a dense shard, the owner TRANSLATES the
+ * ids it received into row numbers of its table -- hbk_hash_translate_runs_n over the W runs of the column
+ * exactly where the gather would read its ids (the own slice in the outgoing buffer when it stays in place),
+ * one call per table kind (and insert flag) present in a column group -- into a plan-owned int64 slot buffer
+ * laid out as the received ids.  The owner gather then reads ids = slots, divisor = 1, rows = capacity (a -1
+ * reads a zero row), and the owner reduce of the backward (every optimizer) reads the same slots with divisor
+ * = 1: unique_rows are SLOT numbers, keys_cache[unique_rows] names the ids, Adagrad / Adam / FTRL slots are
+ * [capacity, dim].  The slot buffer lives until the next forward, as the received ids do.
+ *
+ * tables: host [n_cols], copied; NULL, or all keys_cache NULL: no hash column (today's step, no extra work).
+ * tables[c].keys_cache == NULL: column c is an ordinary column.  Otherwise column c's shard is the table's
+ * rows ([slab_count * slab_size, dim], dense), and counts, init_scale, seed, exp (exp.last_seen == NULL: not
+ * expiring), adm (adm.sketch == NULL: no filter) and insert (0: a pure find, inference) are what the translate
+ * call is handed.  Plan state like the max_norms: plan creation is local, every rank sets it for itself, and
+ * after a rehash of a table (new arrays) the plan is made again.  Requester-side dedup, the fp16 wire,
+ * max_norms, hot_rows, column groups, inline or hopped exchanges and prefetch work unchanged.
+ *
+ * Refused (HBK_INVALID_ARGUMENT): a hash column with rows_local != slab_count * slab_size, with bucket != 0
+ * (ids must reach the owner raw, as int64), with slab_size outside [1, 64] or slab_count < 1, or with
+ * exp.last_seen set and exp.freq or exp.step NULL.  HBK_UNIMPLEMENTED: a p2p-bound plan; and
+ * hbk_sharded_p2p_bind on a plan with a hash column.  hbk_sharded_lookup_fwd_weighted's rule that a weighted
+ * column needs a bucket stands, so id_weights on a hash column are refused. */
+typedef struct {
+  int64_t* keys_cache;          /* NULL: column c is an ordinary column */
+  int64_t slab_count; int32_t slab_size;
+  int32_t* counts; float init_scale; int64_t seed;
+  hbk_hash_expiry_t exp;        /* exp.last_seen == NULL: not expiring */
+  hbk_hash_admission_t adm;     /* adm.sketch == NULL: no filter */
+  int32_t insert;               /* 0: pure find (inference) */
+} hbk_sharded_hash_t;
+int hbk_sharded_set_hash_tables(hbk_sharded_t plan, const hbk_sharded_hash_t* tables /* [n_cols] or NULL */);
 int hbk_sharded_destroy(hbk_sharded_t plan);
 /* out_strides / grad_strides: NULL, or per column the row stride in floats of outs[c] /
  * grads[c] (0 = dim): the columns' blocks of one concatenated [segments, sum of dims] tensor. */
