@@ -82,7 +82,8 @@ class HashTable:
   the device (:meth:`set_step`), ``stats`` int32 ``[2]`` = keys evicted / keys stored into a reused slot.
 
   Attributes: ``keys`` int64 ``[slab_count * slab_size]`` (EMPTY = INT64_MIN), ``table`` fp32
-  ``[capacity, dim]``, ``counts`` int32 ``[2]`` = keys inserted / id occurrences refused (table full) so far.
+  ``[capacity, dim]``, ``counts`` int32 ``[2]`` = keys inserted (since the last rehash or compact: the keys it
+  moved count as inserted) / id occurrences answered -1 by inserting calls (table full, or a sentinel id) so far.
   """
 
   def __init__(self, capacity, dim, device, slab_size=8, init_scale=1e-3, seed=0, expiring=False, min_freq=0,
@@ -169,7 +170,8 @@ class HashTable:
 
   def lookup_or_insert(self, ids):
     """Row number of every id, int64 ``[n]``; ids never seen are inserted and their rows initialised; -1
-    where the table is full (and for id == INT64_MIN)."""
+    where the table is full, for id == INT64_MIN and, on an expiring table, for id == INT64_MIN + 1 (these count
+    in :meth:`failed` too), and for ids a filter has not admitted yet (counted in :meth:`filtered`)."""
     return hash_translate([self], [ids], insert=True)[0]
 
   def find(self, ids):
@@ -190,7 +192,8 @@ class HashTable:
     return inserted - evicted
 
   def failed(self):
-    """Id occurrences refused so far because the table was full (syncs the host)."""
+    """Id occurrences answered -1 by an inserting call so far because the table was full or the id is a sentinel
+    (INT64_MIN; INT64_MIN + 1 on an expiring table); kept by a rehash and by :meth:`compact` (syncs the host)."""
     return int(self.counts[1].item())
 
   def recount(self):
@@ -213,7 +216,10 @@ class HashTable:
   def load(self, keys, rows):
     """Insert ``keys`` (without initialising) and store ``rows`` as their rows: ``load(*other.items())``
     moves a table into one of any capacity or slab size.  Refuses when a key does not fit.  The admission
-    filter is bypassed and the sketch left alone: these are keys a table already admitted."""
+    filter is bypassed and the sketch left alone: these are keys a table already admitted.  On an expiring table
+    the keys go through the expiring insert, so a loaded key counts as seen now: ``last_seen`` = the current step
+    and ``freq`` + 1, for keys the table already held as well (a key loaded with ``last_seen`` 0 would leave with
+    the next sweep); ``items()`` does not carry the metadata of the table it came from."""
     check_ids([keys], [self])
     if rows.dtype != torch.float32 or tuple(rows.shape) != (keys.numel(), self.dim) or \
         rows.device != self.table.device:

@@ -2,16 +2,14 @@
 the matching existing entry called once on the concatenation of the runs, on twin tables.  Slot numbers are
 run-dependent; everything else -- the key set of every slab (no slab overflows here), counts, stats, freq and
 last_seen per key, the sketch -- must be equal."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
-from hybridbackend_amd import _lib
 from hybridbackend_amd.embedding import HashTable
 from hybridbackend_amd.embedding import hashtable as _ht
 from tests.support import hash_ref as ref
+from tests.support.hash_lifecycle import translate_runs
 from tests.support.sharded_hash_ref import keys_without_overflow
 
 pytestmark = pytest.mark.gpu
@@ -31,36 +29,6 @@ def make_tables(kind, min_freq=2):
   return [HashTable(ss * sc, dim, DEV, slab_size=ss, init_scale=0.05, seed=3 + c, expiring='expiring' in kind,
                     min_freq=min_freq if 'admit' in kind else 0, sketch_width=4096)
           for c, (ss, sc, dim) in enumerate(GEOMETRY)]
-
-
-def translate_runs(tables, runs, insert=True):
-  """The runs entry: runs[c] = list of id tensors; returns the slot tensors in the same shape."""
-  n = len(tables)
-  kinds = {(t.expiring, bool(t.min_freq)) for t in tables}
-  assert len(kinds) <= 1
-  expiring, filtered = kinds.pop() if kinds else (False, False)
-  cols = (_lib.HashColumn * max(n, 1))()
-  exp = (_lib.HashExpiry * max(n, 1))() if expiring else None
-  adm = (_lib.HashAdmission * max(n, 1))() if filtered else None
-  keep, ptrs, slots = [], [], []
-  for c, t in enumerate(tables):
-    t._describe(cols[c], init=insert, count=bool(insert))
-    cols[c].keys, cols[c].slots, cols[c].n_keys = None, None, -3          # ignored
-    if expiring:
-      t._describe_expiry(exp[c])
-    if filtered:
-      t._describe_admission(adm[c])
-    r = (_lib.HashRun * max(len(runs[c]), 1))()
-    out = [torch.full((i.numel(),), -7, dtype=torch.int64, device=DEV) for i in runs[c]]
-    for k, (i, o) in enumerate(zip(runs[c], out)):
-      r[k].keys, r[k].slots, r[k].n_keys = (i.data_ptr(), o.data_ptr(), i.numel()) if i.numel() else (None, None, 0)
-    keep.append(r)
-    ptrs.append(C.cast(r, C.c_void_p).value)
-    slots.append(out)
-  _lib.check(_lib.lib().hbk_hash_translate_runs_n(
-    n, cols, exp, adm, _lib.i32_array([len(r) for r in runs]), _lib.ptr_array(ptrs), 1 if insert else 0,
-    _lib.current_stream(torch.device(DEV))))
-  return slots
 
 
 def draw_runs(rng, pools):
