@@ -145,6 +145,20 @@ class HashRehashColumn(C.Structure):
               ('new_slots', C.c_void_p), ('counts', C.c_void_p)]
 
 
+class HashExportColumn(C.Structure):
+  """hbk_hash_export_column_t"""
+  _fields_ = [('keys', C.c_void_p), ('slab_count', C.c_int64), ('slab_size', C.c_int32), ('expiring', C.c_int32),
+              ('last_seen', C.c_void_p), ('since', C.c_int32), ('n_moves', C.c_int32),
+              ('moves', HashMove * HASH_MAX_MOVES), ('out_keys', C.c_void_p), ('out_slots', C.c_void_p),
+              ('out_capacity', C.c_int64), ('count', C.c_void_p)]
+
+
+class HashStoreColumn(C.Structure):
+  """hbk_hash_store_column_t"""
+  _fields_ = [('slots', C.c_void_p), ('n', C.c_int64), ('dst_rows', C.c_int64), ('n_moves', C.c_int32),
+              ('moves', HashMove * HASH_MAX_MOVES)]
+
+
 class ShardedColumn(C.Structure):
   """hbk_sharded_column_t"""
   _fields_ = [('shard', C.c_void_p), ('rows_local', C.c_int64), ('dim', C.c_int32),
@@ -226,6 +240,9 @@ def _declare(l):
     'hbk_hash_insert_expiring_admit_n': (C.c_int, [i32, vp, vp, vp, i32, vp]),
     'hbk_hash_rehash_n': (C.c_int, [i32, vp, vp]),
     'hbk_hash_translate_runs_n': (C.c_int, [i32, vp, vp, vp, vp, vp, i32, vp]),
+    'hbk_hash_export_workspace_bytes': (C.c_int, [i32, vp, vp]),
+    'hbk_hash_export_n': (C.c_int, [i32, vp, vp, vp]),
+    'hbk_hash_store_rows_n': (C.c_int, [i32, vp, vp]),
     'hbk_comm_get_id': (C.c_int, [vp]),
     'hbk_comm_rccl_versions': (C.c_int, [vp, vp]),
     'hbk_comm_create': (C.c_int, [vp, vp, i32, i32, i32]),

@@ -1,0 +1,421 @@
+// Hash tables leaving and entering the device whole (hbk_hash_export_n, hbk_hash_store_rows_n).
+//
+// Export: a stream compaction of N tables per call.  A slot is exported iff it holds a key (not EMPTY; not
+// TOMBSTONE when `expiring` is set) and, with since > 0, last_seen[slot] >= since.  The exported keys appear in
+// ASCENDING SOURCE-SLOT ORDER, packed from position 0, and every per-slot array named as a move (the embedding
+// row, the optimizer slots, last_seen, freq) is copied bit for bit from the source slot to the key's position.
+// The output is a function of the table's arrays alone: no ticket atomic (its order differs from run to run)
+// and no look-back between tiles (no workgroup waits for another).  Instead, "output ranges from a count
+// launch" as the deterministic backward has them -- three launches on the call's stream:
+//   1. count   a 256-slot tile (one 64-slot chunk per wave) counts its matches into the workspace;
+//   2. scan    one workgroup per column turns the tile counts into exclusive offsets in place and writes the
+//              total to `count`;
+//   3. write   every tile evaluates the SAME predicate again (nobody may write the table during the call) and
+//              places lane's key at  tile offset + matches of the earlier waves of the tile + rank_below(ballot).
+// The live lanes' numbers are gathered into the low lanes with one ds_permute (hash_evict.hip, hash_rehash.hip)
+// and lane groups copy the rows, r-th live slot -> r-th position of the wave's range: a wave's output rows are
+// contiguous.  Nothing is written at positions >= out_capacity; `count` still receives the total.
+//
+// Store (hbk_hash_store_rows_n): the other half of an import.  The keys were placed by the table's own translate
+// entry; this launch is dst[slots[i] * dst_pitch + j] = src[i * src_pitch + j] for every move of every column,
+// one lane group per row, slots[i] outside [0, dst_rows) skipped.
+//
+// Memory rules: plain loads and plain vector stores only; no atomics anywhere in this file.  The tables are
+// quiescent during either call, and the kernel boundaries order the three launches of an export.
+//
+// Rows travel as 4-byte words.  A move whose two bases, two pitches and width are all multiples of 16 bytes is
+// copied with 16-byte accesses (hash_rehash.hip's rule); the lane group of a move is pow2(accesses per row).
+#include "common.h"
+
+namespace hbk {
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kWavesPerBlock = kBlock / kWave;
+constexpr int kSlotsPerTile = kBlock;                   // one 64-slot chunk per wave
+constexpr int kScanPerThread = 8;                       // tile counts a thread of the scan takes per pass
+constexpr int kMaxColsPerLaunch = 32;                   // the argument structs travel by value
+constexpr long long kEmptyKey = (long long)0x8000000000000000ull;
+constexpr long long kTombstoneKey = kEmptyKey + 1;
+
+struct Move {
+  const uint32_t* src;
+  uint32_t* dst;
+  int64_t src_pitch;    // words between rows
+  int64_t dst_pitch;
+  int32_t words;
+  int16_t vec16;        // != 0: bases, pitches and words are multiples of 16 bytes
+  int16_t lanes_log2;   // lanes per row of a pass: pow2(accesses per row), at most 64
+};
+
+struct ExportCol {
+  const long long* keys;
+  const int32_t* last_seen;   // read only when since > 0
+  long long* out_keys;
+  int64_t* out_slots;         // or NULL
+  int64_t* count;
+  int64_t* tiles;             // workspace [n_tiles]: counts after launch 1, exclusive offsets after launch 2
+  int64_t capacity;
+  int64_t out_capacity;
+  int64_t n_tiles;
+  int32_t since;
+  int32_t expiring;
+  int32_t n_moves;
+  int32_t pad_;
+  Move move[HBK_HASH_MAX_MOVES];
+};
+
+struct ExportArgs {
+  int32_t n_cols;
+  int32_t tile_start[kMaxColsPerLaunch + 1];
+  ExportCol col[kMaxColsPerLaunch];
+};
+static_assert(sizeof(ExportArgs) <= 24576, "kernarg budget");
+
+struct StoreCol {
+  const int64_t* slots;
+  int64_t n;
+  int64_t dst_rows;
+  int32_t n_moves;
+  int32_t pad_;
+  Move move[HBK_HASH_MAX_MOVES];
+};
+
+struct StoreArgs {
+  int32_t n_cols;
+  int32_t tile_start[kMaxColsPerLaunch + 1];
+  StoreCol col[kMaxColsPerLaunch];
+};
+static_assert(sizeof(StoreArgs) <= 24576, "kernarg budget");
+
+// last column whose first tile is <= b: one entry per lane, one ballot (hash_insert.hip)
+__device__ inline int column_of(const int32_t* tile_start, int n_cols, int b, int lane) {
+  const int t0 = lane < n_cols ? tile_start[lane] : 0x7fffffff;
+  return __builtin_amdgcn_readfirstlane((int)__builtin_popcountll(__ballot(t0 <= b)) - 1);
+}
+
+// the selection: the one predicate of the count and the write launch
+__device__ inline bool exported(const ExportCol& c, int64_t slot) {
+  if (slot >= c.capacity) return false;
+  const long long key = c.keys[slot];
+  if (key == kEmptyKey || (c.expiring != 0 && key == kTombstoneKey)) return false;
+  return c.since <= 0 || c.last_seen[slot] >= c.since;
+}
+
+// one row: `words` 4-byte words, by the `1 << lanes_log2` lanes of a group (sub = the lane's place in it)
+__device__ inline void copy_row(const Move& mv, const uint32_t* s, uint32_t* d, int sub) {
+  const int step = 1 << mv.lanes_log2;
+  if (mv.vec16 != 0) {
+    const uint4* s4 = reinterpret_cast<const uint4*>(s);
+    uint4* d4 = reinterpret_cast<uint4*>(d);
+    for (int j = sub; j < (mv.words >> 2); j += step) d4[j] = s4[j];
+    return;
+  }
+  for (int j = sub; j < mv.words; j += step) d[j] = s[j];
+}
+
+__global__ __launch_bounds__(kBlock) void hash_export_count_kernel(const ExportArgs a) {
+  __shared__ int32_t wave_n[kWavesPerBlock];
+  const int b = (int)blockIdx.x;
+  const int lane = lane_id();
+  const int wave = (int)(threadIdx.x >> 6);
+  const int ci = column_of(a.tile_start, a.n_cols, b, lane);
+  const ExportCol& c = a.col[ci];
+  const int64_t tile = (int64_t)(b - a.tile_start[ci]);
+  const int64_t slot = tile * kSlotsPerTile + (int64_t)wave * kWave + lane;
+  const unsigned long long mask = __ballot(exported(c, slot));
+  if (lane == 0) wave_n[wave] = (int32_t)__builtin_popcountll(mask);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int32_t n = 0;
+#pragma unroll
+    for (int w = 0; w < kWavesPerBlock; ++w) n += wave_n[w];
+    c.tiles[tile] = (int64_t)n;
+  }
+}
+
+// one workgroup per column: counts -> exclusive offsets in place, the total -> *count
+__global__ __launch_bounds__(kBlock) void hash_export_scan_kernel(const ExportArgs a) {
+  __shared__ int64_t wave_sum[kWavesPerBlock];
+  const ExportCol& c = a.col[blockIdx.x];
+  const int lane = lane_id();
+  const int wave = (int)(threadIdx.x >> 6);
+  int64_t carry = 0;   // matches of the tiles before this pass (block-uniform)
+  for (int64_t t0 = 0; t0 < c.n_tiles; t0 += (int64_t)kBlock * kScanPerThread) {   // (block-uniform bounds)
+    const int64_t first = t0 + (int64_t)threadIdx.x * kScanPerThread;
+    int64_t v[kScanPerThread];
+    int64_t mine = 0;
+#pragma unroll
+    for (int k = 0; k < kScanPerThread; ++k) {
+      v[k] = first + k < c.n_tiles ? c.tiles[first + k] : 0;
+      mine += v[k];
+    }
+    // inclusive scan of `mine` across the wave, then across the four waves through LDS
+    int64_t incl = mine;
+#pragma unroll
+    for (int off = 1; off < kWave; off <<= 1) {
+      const int64_t up = (int64_t)__shfl_up((long long)incl, off, kWave);
+      if (lane >= off) incl += up;
+    }
+    if (lane == kWave - 1) wave_sum[wave] = incl;
+    __syncthreads();
+    int64_t before = carry, total = 0;
+#pragma unroll
+    for (int w = 0; w < kWavesPerBlock; ++w) {
+      if (w < wave) before += wave_sum[w];
+      total += wave_sum[w];
+    }
+    __syncthreads();   // (wave_sum is written again by the next pass)
+    int64_t run = before + incl - mine;
+#pragma unroll
+    for (int k = 0; k < kScanPerThread; ++k) {
+      if (first + k < c.n_tiles) c.tiles[first + k] = run;
+      run += v[k];
+    }
+    carry += total;
+  }
+  if (threadIdx.x == 0) *c.count = carry;
+}
+
+__global__ __launch_bounds__(kBlock) void hash_export_write_kernel(const ExportArgs a) {
+  __shared__ int32_t wave_n[kWavesPerBlock];
+  const int b = (int)blockIdx.x;
+  const int lane = lane_id();
+  const int wave = (int)(threadIdx.x >> 6);
+  const int ci = column_of(a.tile_start, a.n_cols, b, lane);
+  const ExportCol& c = a.col[ci];
+  const int64_t tile = (int64_t)(b - a.tile_start[ci]);
+  const int64_t first = tile * kSlotsPerTile + (int64_t)wave * kWave;
+  const int64_t slot = first + lane;
+  const bool take = exported(c, slot);
+  const unsigned long long mask = __ballot(take);
+  const int n = (int)__builtin_popcountll(mask);
+  if (lane == 0) wave_n[wave] = n;
+  __syncthreads();   // (every wave of the tile is here: nothing above returns)
+  if (mask == 0ull) return;   // (wave-uniform)
+  int64_t base = c.tiles[tile];
+  for (int w = 0; w < wave; ++w) base += wave_n[w];
+  const int64_t out_capacity = c.out_capacity;
+  if (base >= out_capacity) return;   // (wave-uniform) the whole range lies behind the output
+  const int below = rank_below(mask);
+  if (take && base + below < out_capacity) {
+    c.out_keys[base + below] = c.keys[slot];
+    if (c.out_slots != nullptr) c.out_slots[base + below] = slot;
+  }
+  if (c.n_moves == 0) return;
+  // lane r < n receives the lane number of the r-th live slot; the other lanes take what is left, so the
+  // permute is a bijection of the wave (hash_evict.hip)
+  const int dest = take ? below : n + lane - below;
+  const int live_lane = __builtin_amdgcn_ds_permute(dest << 2, lane);
+  for (int m = 0; m < c.n_moves; ++m) {
+    const Move& mv = c.move[m];
+    const int lanes_log2 = mv.lanes_log2;
+    const int sub = lane & ((1 << lanes_log2) - 1);
+    for (int r0 = 0; r0 < n; r0 += kWave >> lanes_log2) {   // (wave-uniform bounds)
+      const int r = r0 + (lane >> lanes_log2);
+      const int from = __shfl(live_lane, r & (kWave - 1), kWave);   // (every lane takes the shuffle)
+      if (r < n && base + r < out_capacity) {
+        copy_row(mv, mv.src + (first + from) * mv.src_pitch, mv.dst + (base + r) * mv.dst_pitch, sub);
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void hash_store_rows_kernel(const StoreArgs a) {
+  const int b = (int)blockIdx.x;
+  const int lane = lane_id();
+  const int wave = (int)(threadIdx.x >> 6);
+  const int ci = column_of(a.tile_start, a.n_cols, b, lane);
+  const StoreCol& c = a.col[ci];
+  const int64_t first = (int64_t)(b - a.tile_start[ci]) * kSlotsPerTile + (int64_t)wave * kWave;
+  if (first >= c.n) return;   // (wave-uniform)
+  int64_t my_slot = -1;
+  if (first + lane < c.n) my_slot = c.slots[first + lane];
+  if (my_slot >= c.dst_rows) my_slot = -1;   // (a slot outside the destination is skipped, never written)
+  if (__ballot(my_slot >= 0) == 0ull) return;   // (wave-uniform)
+  for (int m = 0; m < c.n_moves; ++m) {
+    const Move& mv = c.move[m];
+    const int lanes_log2 = mv.lanes_log2;
+    const int sub = lane & ((1 << lanes_log2) - 1);
+    for (int r0 = 0; r0 < kWave; r0 += kWave >> lanes_log2) {
+      const int r = r0 + (lane >> lanes_log2);
+      const int64_t to = (int64_t)__shfl((long long)my_slot, r & (kWave - 1), kWave);   // (every lane takes the shuffle)
+      if (to >= 0) copy_row(mv, mv.src + (first + r) * mv.src_pitch, mv.dst + to * mv.dst_pitch, sub);
+    }
+  }
+}
+
+// the checks of a table's geometry (hash_rehash.hip: check_geometry)
+int check_geometry(const char* who, int32_t c, const void* keys, int64_t slab_count, int32_t slab_size) {
+  HBK_REQUIRE(slab_size >= 1 && slab_size <= kWave, "%s: column %d: slab_size must be in [1, 64], got %d", who, c,
+              slab_size);
+  HBK_REQUIRE(slab_count >= 1, "%s: column %d: slab_count must be >= 1, got %lld", who, c, (long long)slab_count);
+  HBK_REQUIRE(slab_count <= ((1ll << 62) / kWave), "%s: column %d: slab_count %lld is out of range", who, c,
+              (long long)slab_count);
+  HBK_REQUIRE(keys != nullptr, "%s: column %d: keys is NULL", who, c);
+  HBK_REQUIRE(((uintptr_t)keys & 7) == 0, "%s: column %d: keys must be 8-byte aligned", who, c);
+  return HBK_OK;
+}
+
+// the checks of a column's moves (hash_rehash.hip's)
+int check_moves(const char* who, int32_t c, int32_t n_moves, const hbk_hash_move_t* moves) {
+  HBK_REQUIRE(n_moves >= 0 && n_moves <= HBK_HASH_MAX_MOVES, "%s: column %d: n_moves must be in [0, %d], got %d", who,
+              c, HBK_HASH_MAX_MOVES, n_moves);
+  for (int32_t m = 0; m < n_moves; ++m) {
+    const hbk_hash_move_t& mv = moves[m];
+    HBK_REQUIRE(mv.words >= 1, "%s: column %d: move %d: words must be >= 1, got %d", who, c, m, mv.words);
+    HBK_REQUIRE(mv.src_pitch == 0 || mv.src_pitch >= mv.words,
+                "%s: column %d: move %d: src_pitch %d is smaller than words %d", who, c, m, mv.src_pitch, mv.words);
+    HBK_REQUIRE(mv.dst_pitch == 0 || mv.dst_pitch >= mv.words,
+                "%s: column %d: move %d: dst_pitch %d is smaller than words %d", who, c, m, mv.dst_pitch, mv.words);
+    HBK_REQUIRE(mv.src != nullptr && mv.dst != nullptr, "%s: column %d: move %d: NULL src or dst", who, c, m);
+    HBK_REQUIRE((((uintptr_t)mv.src | (uintptr_t)mv.dst) & 3) == 0,
+                "%s: column %d: move %d: src and dst must be 4-byte aligned", who, c, m);
+    HBK_REQUIRE(mv.src != mv.dst, "%s: column %d: move %d: src and dst are the same array", who, c, m);
+  }
+  return HBK_OK;
+}
+
+void describe_moves(int32_t n_moves, const hbk_hash_move_t* moves, Move* out) {
+  for (int32_t m = 0; m < n_moves; ++m) {
+    const hbk_hash_move_t& mv = moves[m];
+    Move& o = out[m];
+    o.src = static_cast<const uint32_t*>(mv.src);
+    o.dst = static_cast<uint32_t*>(mv.dst);
+    o.src_pitch = mv.src_pitch > 0 ? mv.src_pitch : mv.words;
+    o.dst_pitch = mv.dst_pitch > 0 ? mv.dst_pitch : mv.words;
+    o.words = mv.words;
+    o.vec16 = (((uintptr_t)mv.src | (uintptr_t)mv.dst) & 15) == 0 &&
+              ((o.src_pitch | o.dst_pitch | (int64_t)mv.words) & 3) == 0;
+    const int32_t accesses = o.vec16 != 0 ? mv.words >> 2 : mv.words;
+    o.lanes_log2 = 0;
+    while (o.lanes_log2 < 6 && (1 << o.lanes_log2) < accesses) ++o.lanes_log2;
+  }
+}
+
+inline int64_t tiles_of(int64_t n) { return (n + kSlotsPerTile - 1) / kSlotsPerTile; }
+
+int check_export(const char* who, int32_t n_cols, const hbk_hash_export_column_t* cols, bool outputs) {
+  HBK_REQUIRE(n_cols >= 0, "%s: n_cols must be >= 0, got %d", who, n_cols);
+  HBK_REQUIRE(n_cols == 0 || cols != nullptr, "%s: cols is NULL", who);
+  for (int32_t c = 0; c < n_cols; ++c) {
+    const hbk_hash_export_column_t& h = cols[c];
+    if (int rc = check_geometry(who, c, h.keys, h.slab_count, h.slab_size)) return rc;
+    if (!outputs) continue;
+    HBK_REQUIRE(h.since <= 0 || h.last_seen != nullptr, "%s: column %d: since = %d needs last_seen, which is NULL",
+                who, c, h.since);
+    if (int rc = check_moves(who, c, h.n_moves, h.moves)) return rc;
+    HBK_REQUIRE(h.count != nullptr, "%s: column %d: count is NULL", who, c);
+    HBK_REQUIRE(h.out_capacity >= 0, "%s: column %d: out_capacity must be >= 0, got %lld", who, c,
+                (long long)h.out_capacity);
+    HBK_REQUIRE(h.out_capacity == 0 || h.out_keys != nullptr, "%s: column %d: out_keys is NULL with out_capacity %lld",
+                who, c, (long long)h.out_capacity);
+  }
+  return HBK_OK;
+}
+
+}  // namespace
+}  // namespace hbk
+
+extern "C" int hbk_hash_export_workspace_bytes(int32_t n_cols, const hbk_hash_export_column_t* cols, size_t* bytes) {
+  using namespace hbk;
+  const char* who = "hash_export_workspace_bytes";
+  HBK_REQUIRE(bytes != nullptr, "%s: bytes is NULL", who);
+  *bytes = 0;
+  if (int rc = check_export(who, n_cols, cols, false)) return rc;
+  int64_t tiles = 0;
+  for (int32_t c = 0; c < n_cols; ++c) tiles += tiles_of(cols[c].slab_count * cols[c].slab_size);
+  *bytes = (size_t)tiles * sizeof(int64_t);
+  return HBK_OK;
+}
+
+extern "C" int hbk_hash_export_n(int32_t n_cols, const hbk_hash_export_column_t* cols, void* workspace,
+                                 hbk_stream_t stream) {
+  using namespace hbk;
+  const char* who = "hash_export_n";
+  if (int rc = check_export(who, n_cols, cols, true)) return rc;
+  if (n_cols == 0) return HBK_OK;
+  HBK_REQUIRE(workspace != nullptr, "%s: workspace is NULL (hbk_hash_export_workspace_bytes says how large)", who);
+  HBK_REQUIRE(((uintptr_t)workspace & 7) == 0, "%s: workspace must be 8-byte aligned", who);
+  int64_t* ws = static_cast<int64_t*>(workspace);
+  int32_t c0 = 0;
+  while (c0 < n_cols) {
+    ExportArgs args;
+    int32_t k = 0;
+    int64_t tiles = 0;
+    args.tile_start[0] = 0;
+    while (c0 < n_cols && k < kMaxColsPerLaunch) {
+      const hbk_hash_export_column_t& h = cols[c0++];
+      ExportCol& d = args.col[k];
+      d.keys = reinterpret_cast<const long long*>(h.keys);
+      d.last_seen = h.last_seen;
+      d.out_keys = reinterpret_cast<long long*>(h.out_keys);
+      d.out_slots = h.out_slots;
+      d.count = h.count;
+      d.tiles = ws;
+      d.capacity = h.slab_count * h.slab_size;
+      d.out_capacity = h.out_capacity;
+      d.n_tiles = tiles_of(d.capacity);
+      d.since = h.since;
+      d.expiring = h.expiring;
+      d.n_moves = h.n_moves;
+      d.pad_ = 0;
+      describe_moves(h.n_moves, h.moves, d.move);
+      ws += d.n_tiles;
+      tiles += d.n_tiles;
+      HBK_REQUIRE(tiles < (1ll << 31), "%s: grid too large", who);
+      ++k;
+      args.tile_start[k] = (int32_t)tiles;
+    }
+    args.n_cols = k;
+    hipLaunchKernelGGL(hash_export_count_kernel, dim3((unsigned)tiles), dim3(kBlock), 0, as_stream(stream), args);
+    HBK_HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(hash_export_scan_kernel, dim3((unsigned)k), dim3(kBlock), 0, as_stream(stream), args);
+    HBK_HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(hash_export_write_kernel, dim3((unsigned)tiles), dim3(kBlock), 0, as_stream(stream), args);
+    HBK_HIP_OK(hipGetLastError());
+  }
+  return HBK_OK;
+}
+
+extern "C" int hbk_hash_store_rows_n(int32_t n_cols, const hbk_hash_store_column_t* cols, hbk_stream_t stream) {
+  using namespace hbk;
+  const char* who = "hash_store_rows_n";
+  HBK_REQUIRE(n_cols >= 0, "%s: n_cols must be >= 0, got %d", who, n_cols);
+  HBK_REQUIRE(n_cols == 0 || cols != nullptr, "%s: cols is NULL", who);
+  for (int32_t c = 0; c < n_cols; ++c) {
+    const hbk_hash_store_column_t& h = cols[c];
+    HBK_REQUIRE(h.n >= 0, "%s: column %d: n must be >= 0, got %lld", who, c, (long long)h.n);
+    HBK_REQUIRE(h.n == 0 || h.slots != nullptr, "%s: column %d: slots is NULL with n = %lld", who, c, (long long)h.n);
+    HBK_REQUIRE(((uintptr_t)h.slots & 7) == 0, "%s: column %d: slots must be 8-byte aligned", who, c);
+    HBK_REQUIRE(h.dst_rows >= 0, "%s: column %d: dst_rows must be >= 0, got %lld", who, c, (long long)h.dst_rows);
+    if (int rc = check_moves(who, c, h.n_moves, h.moves)) return rc;
+  }
+  int32_t c0 = 0;
+  while (c0 < n_cols) {
+    StoreArgs args;
+    int32_t k = 0;
+    int64_t tiles = 0;
+    args.tile_start[0] = 0;
+    while (c0 < n_cols && k < kMaxColsPerLaunch) {
+      const hbk_hash_store_column_t& h = cols[c0++];
+      if (h.n == 0 || h.n_moves == 0 || h.dst_rows == 0) continue;   // nothing to store
+      StoreCol& d = args.col[k];
+      d.slots = h.slots;
+      d.n = h.n;
+      d.dst_rows = h.dst_rows;
+      d.n_moves = h.n_moves;
+      d.pad_ = 0;
+      describe_moves(h.n_moves, h.moves, d.move);
+      tiles += tiles_of(h.n);
+      HBK_REQUIRE(tiles < (1ll << 31), "%s: grid too large", who);
+      ++k;
+      args.tile_start[k] = (int32_t)tiles;
+    }
+    if (k == 0) continue;
+    args.n_cols = k;
+    hipLaunchKernelGGL(hash_store_rows_kernel, dim3((unsigned)tiles), dim3(kBlock), 0, as_stream(stream), args);
+    HBK_HIP_OK(hipGetLastError());
+  }
+  return HBK_OK;
+}

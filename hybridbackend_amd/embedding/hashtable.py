@@ -31,6 +31,12 @@ Sharded hash tables: :class:`hybridbackend_amd.embedding.ShardedHashGroupLookup`
 W ranks behind the sharded lookup step, owner = :func:`hash_owner`; :meth:`HashTable.load_owned` restores
 ``items()`` of W ranks onto W' ranks.
 
+Export and import (``hbk_hash_export_n`` / ``hbk_hash_store_rows_n``): :meth:`HashTable.export_items` /
+:func:`hash_export` pack the keys of N tables -- all, or those seen since a step: an incremental checkpoint --
+with rows, ``last_seen``, ``freq`` and the optimizer slots into a :class:`HashExport`, in ascending slot order;
+:meth:`HashTable.import_items` upserts one into a table of any geometry or, with ``world`` / ``rank``, onto any
+number of ranks.  ``items()`` / ``load()`` / ``load_owned()`` / ``variables()`` are what they were.
+
 Not provided: growth from inside a translate launch (a full table answers -1 until ``maybe_grow`` ran), a
 compaction that keeps the tensors' addresses, feature-column integration, the TF shim op.
 """
@@ -362,6 +368,80 @@ class HashTable:
       return self.rehash(slots=slots)
     return self.rehash(capacity=int(math.ceil(self.capacity * factor)), slots=slots)
 
+  # ---- export and import ----------------------------------------------------------------------------------
+  def export_items(self, since=None, slots=()):
+    """The table in its geometry-free form WITH its state (``hbk_hash_export_n``): a :class:`HashExport` of the
+    keys, their rows, an expiring table's ``last_seen`` and ``freq``, and the rows of the companion tensors
+    ``slots`` (fp32 ``[capacity, d]`` tensors: the optimizer slots), in ascending slot order.  ``since`` (expiring
+    tables only): the keys with ``last_seen >= since`` -- a delta.  See :func:`hash_export`."""
+    return hash_export([self], [since], [slots])[0]
+
+  def import_items(self, exp, slots=(), world=None, rank=None, assume_distinct=False):
+    """Upsert a :class:`HashExport`: a key the table holds keeps its slot and takes the imported payload, a new
+    key is inserted by the table's own rule (the filter bypassed and the sketch left alone, tombstones of an
+    expiring table reused, as :meth:`load`), then rows, metadata and companions are stored in ONE launch
+    (``hbk_hash_store_rows_n``).  Returns the slots of the keys imported.
+
+    ``slots``: the destination companions, fp32 ``[capacity, d]``, matching ``exp.slots`` in number and width.
+    ``world`` / ``rank``: only the keys rank ``rank`` of ``world`` owns are imported (:func:`hash_owner`).
+    An export with metadata restores ``last_seen`` and ``freq`` on an expiring table (the key keeps its age and
+    count); one without leaves :meth:`load`'s "seen now" stamp; a plain table drops the metadata.  The keys must
+    be distinct: checked by a sort and a neighbour compare (one host read) unless ``assume_distinct``.  When some
+    keys do not fit, the keys that did are stored completely and then the call raises, naming the count."""
+    if not isinstance(exp, HashExport):
+      raise _bad('import_items needs a HashExport')
+    dev = self.keys.device
+    dst_slots = _plain_companions(self, slots)
+    if len(dst_slots) != len(exp.slots):
+      raise _bad(f'import_items: the export carries {len(exp.slots)} companion tensors, slots names {len(dst_slots)}')
+    n = exp.keys.numel()
+    if exp.keys.dtype != torch.int64 or exp.keys.dim() != 1:
+      raise _bad('import_items: exp.keys must be an int64 vector')
+    if exp.rows.dtype != torch.float32 or tuple(exp.rows.shape) != (n, self.dim):
+      raise _bad(f'import_items: exp.rows must be fp32 [{n}, {self.dim}], got {tuple(exp.rows.shape)}')
+    for k, (x, y) in enumerate(zip(exp.slots, dst_slots)):
+      if x.dtype != torch.float32 or x.dim() != 2 or tuple(x.shape) != (n, y.shape[1]):
+        raise _bad(f'import_items: exp.slots[{k}] must be fp32 [{n}, {y.shape[1]}], got {tuple(x.shape)}')
+    meta = self.expiring and exp.last_seen is not None and exp.freq is not None
+    if meta:
+      for name in ('last_seen', 'freq'):
+        x = getattr(exp, name)
+        if x.dtype != torch.int32 or tuple(x.shape) != (n,):
+          raise _bad(f'import_items: exp.{name} must be int32 [{n}]')
+    if (world is None) != (rank is None):
+      raise _bad('import_items: world and rank come together')
+    src = [exp.rows] + ([exp.last_seen, exp.freq] if meta else []) + list(exp.slots)
+    dst = [self.table] + ([self.last_seen, self.freq] if meta else []) + dst_slots
+    keys = exp.keys.to(dev)
+    src = [x.to(dev) for x in src]
+    if world is not None:
+      mine = (hash_owner(keys, world) == int(rank)).nonzero().flatten()
+      keys = keys[mine]
+      src = [x[mine] for x in src]
+    keys = keys.contiguous()
+    if keys.numel() == 0:
+      return keys.new_empty(0)
+    if not assume_distinct:
+      ordered = torch.sort(keys).values
+      if bool((ordered[1:] == ordered[:-1]).any().item()):
+        raise _bad('import_items: the keys are not distinct')
+    check_ids([keys], [self])
+    for x in src:
+      if x.stride(-1) != 1:
+        raise _bad('import_items: the export\'s rows must be contiguous')
+    got = _translate([self], [keys], True, None, init=False, plan=_Plan([self], admit=False))[0]
+    col = (_lib.HashStoreColumn * 1)()
+    col[0].slots, col[0].n, col[0].dst_rows = got.data_ptr(), keys.numel(), self.capacity
+    col[0].n_moves = len(src)
+    for m, (x, y) in enumerate(zip(src, dst)):
+      _describe_move(col[0].moves[m], per_slot=y, packed=x, to_packed=False)
+    _lib.check(_lib.lib().hbk_hash_store_rows_n(1, col, _lib.current_stream(dev)))
+    missing = int((got < 0).sum().item())
+    if missing:
+      raise _bad(f'import_items: {missing} of {keys.numel()} keys do not fit: the table is full (the others are '
+                 'stored)')
+    return got
+
 
 def _companions(table, slots):
   """Checked ``(tensor, fill_value)`` pairs of one table."""
@@ -382,6 +462,175 @@ def _companions(table, slots):
       raise _bad(f'slots[{n}]: fill_value must be finite, got {p[1]!r}')
     out.append((t, value))
   return out
+
+
+def _plain_companions(table, slots):
+  """Checked companion tensors of one table, without fill values (an export and an import fill nothing)."""
+  return [t for t, _ in _companions(table, [(x, 0.0) for x in slots])]
+
+
+def _describe_move(mv, per_slot, packed, to_packed):
+  """One hbk_hash_move_t between a per-slot array of a table and a packed array of an export."""
+  src, dst = (per_slot, packed) if to_packed else (packed, per_slot)
+  mv.src, mv.dst = src.data_ptr(), dst.data_ptr()
+  mv.words = 1 if per_slot.dim() == 1 else per_slot.shape[1]
+  mv.src_pitch = 1 if src.dim() == 1 else src.stride(0)
+  mv.dst_pitch = 1 if dst.dim() == 1 else dst.stride(0)
+
+
+class HashExport:
+  """What :meth:`HashTable.export_items` returns and :meth:`HashTable.import_items` takes: the keys of a table
+  (all of them, or a delta) with everything that belongs to them, independent of the table's geometry.
+
+  Attributes: ``keys`` int64 ``[n]``; ``rows`` fp32 ``[n, dim]``; ``last_seen`` / ``freq`` int32 ``[n]`` (None
+  for a table that is not expiring); ``slots``: a list of fp32 ``[n, d]`` tensors, one per companion; ``src_slots``
+  int64 ``[n]``: the slot every key had in the table it came from (ascending: the order of the export); ``since``:
+  the ``since`` of the export, 0 for a full one."""
+
+  def __init__(self, keys, rows, last_seen=None, freq=None, slots=(), src_slots=None, since=0):
+    self.keys, self.rows, self.last_seen, self.freq = keys, rows, last_seen, freq
+    self.slots = list(slots)
+    self.src_slots = src_slots
+    self.since = int(since)
+
+  def __len__(self):
+    return self.keys.numel()
+
+  def variables(self, name):
+    """The flat ``{name + '/items/...': tensor}`` dict ``training.saver.Saver.save`` takes (``since`` as an int64
+    ``[1]`` tensor)."""
+    base = name + '/items/'
+    out = {base + 'keys': self.keys, base + 'rows': self.rows,
+           base + 'since': torch.tensor([self.since], dtype=torch.int64)}
+    if self.last_seen is not None and self.freq is not None:
+      out[base + 'last_seen'] = self.last_seen
+      out[base + 'freq'] = self.freq
+    if self.src_slots is not None:
+      out[base + 'src_slots'] = self.src_slots
+    for k, x in enumerate(self.slots):
+      out[base + f'slot{k}'] = x
+    return out
+
+  @classmethod
+  def from_variables(cls, name, d):
+    """The export a :meth:`variables` dict describes (the tensors themselves, not copies: restore into them with
+    ``Saver.restore`` first, or hand over the dict that was saved)."""
+    base = name + '/items/'
+    if base + 'keys' not in d or base + 'rows' not in d:
+      raise _bad(f'from_variables: {base}keys and {base}rows are needed')
+    slots = []
+    while base + f'slot{len(slots)}' in d:
+      slots.append(d[base + f'slot{len(slots)}'])
+    since = d.get(base + 'since')
+    return cls(d[base + 'keys'], d[base + 'rows'], d.get(base + 'last_seen'), d.get(base + 'freq'), slots,
+               d.get(base + 'src_slots'), 0 if since is None else int(since.reshape(-1)[0].item()))
+
+  @classmethod
+  def empty(cls, n, dim, expiring=False, slot_dims=(), device='cpu'):
+    """An export of ``n`` zero keys: the tensors a ``Saver.restore`` of a saved export is read into."""
+    n = int(n)
+    meta = [torch.zeros(n, dtype=torch.int32, device=device) for _ in range(2)] if expiring else [None, None]
+    return cls(torch.zeros(n, dtype=torch.int64, device=device), torch.zeros((n, int(dim)), device=device),
+               meta[0], meta[1], [torch.zeros((n, int(d)), device=device) for d in slot_dims],
+               torch.zeros(n, dtype=torch.int64, device=device), 0)
+
+  @classmethod
+  def cat(cls, exports):
+    """The exports of several ranks (or a table's parts) as one: concatenated in order.  The metadata stays only
+    when every part has it; ``since`` is the smallest of the parts'."""
+    exports = list(exports)
+    if not exports:
+      raise _bad('cat: no exports')
+    if len(set(len(e.slots) for e in exports)) != 1:
+      raise _bad('cat: the exports differ in their number of companion tensors')
+    meta = all(e.last_seen is not None and e.freq is not None for e in exports)
+    src = all(e.src_slots is not None for e in exports)
+    return cls(torch.cat([e.keys for e in exports]), torch.cat([e.rows for e in exports]),
+               torch.cat([e.last_seen for e in exports]) if meta else None,
+               torch.cat([e.freq for e in exports]) if meta else None,
+               [torch.cat([e.slots[k] for e in exports]) for k in range(len(exports[0].slots))],
+               torch.cat([e.src_slots for e in exports]) if src else None, min(e.since for e in exports))
+
+
+def hash_export(tables, sinces=None, slots=None):
+  """:meth:`HashTable.export_items` for N tables of any kinds in ONE C call (``hbk_hash_export_n``: a count, a
+  scan and a write launch per 32 tables, no atomics, the keys in ascending slot order -- the result is a function
+  of the tables' arrays alone).
+
+  ``sinces[c]``: None for every key of table c, else an int: the keys with ``last_seen >= since`` (refused on a
+  table that is not expiring).  ``slots[c]``: its companion tensors, fp32 ``[capacity, d]`` (the optimizer slots;
+  no fill value is needed here).  Returns one :class:`HashExport` per table.
+
+  The outputs are allocated from ONE host read of the counters (the live keys: an upper bound for a delta), the
+  launches run, ONE host read of the counts follows and the outputs are narrowed to views.  More matches than the
+  counters promised is refused: the counters are stale after a restore of the raw arrays -- :meth:`recount`.
+  Must not run beside a translate, a sweep or a backward of the same tables on another stream."""
+  tables = list(tables)
+  same_device(tables)
+  n = len(tables)
+  sinces = [None] * n if sinces is None else list(sinces)
+  slots = [()] * n if slots is None else list(slots)
+  if not len(sinces) == len(slots) == n:
+    raise _bad(f'expected {n} since values and lists of companion tensors, got {len(sinces)} and {len(slots)}')
+  if n == 0:
+    _lib.check(_lib.lib().hbk_hash_export_n(0, None, None, None))
+    return []
+  checked = []
+  for c, t in enumerate(tables):
+    if sinces[c] is not None:
+      if not t.expiring:
+        raise _bad(f'table {c}: since needs a table built with expiring=True (last_seen is the dirty mark)')
+      if not -2 ** 31 <= int(sinces[c]) < 2 ** 31:
+        raise _bad(f'table {c}: since must be an int32, got {sinces[c]}')
+    checked.append(_plain_companions(t, slots[c]))
+  for t in tables:
+    _lib.require_device_tensor(t.keys, 'keys')
+  dev = tables[0].keys.device
+  # the live keys of every table in one host read
+  counters = torch.cat([torch.cat([t.counts, t.stats]) if t.expiring else
+                        torch.cat([t.counts, t.counts.new_zeros(2)]) for t in tables]).tolist()
+  cols = (_lib.HashExportColumn * n)()
+  counts = torch.zeros(n, dtype=torch.int64, device=dev)
+  outs = []
+  for c, t in enumerate(tables):
+    live = counters[4 * c] - counters[4 * c + 2]
+    cap = min(max(live, 0), t.capacity)
+    rows = max(cap, 1)   # (never an empty allocation: a move needs an address)
+    out = {'keys': torch.empty(rows, dtype=torch.int64, device=dev),
+           'src_slots': torch.empty(rows, dtype=torch.int64, device=dev),
+           'rows': torch.empty((rows, t.dim), dtype=torch.float32, device=dev)}
+    moves = [(t.table, out['rows'])]
+    if t.expiring:
+      for name in ('last_seen', 'freq'):
+        out[name] = torch.empty(rows, dtype=torch.int32, device=dev)
+        moves.append((getattr(t, name), out[name]))
+    out['slots'] = [torch.empty((rows, x.shape[1]), dtype=torch.float32, device=dev) for x in checked[c]]
+    moves += list(zip(checked[c], out['slots']))
+    col = cols[c]
+    col.keys, col.slab_count, col.slab_size = t.keys.data_ptr(), t.slab_count, t.slab_size
+    col.expiring = 1 if t.expiring else 0
+    col.last_seen = t.last_seen.data_ptr() if t.expiring else None
+    col.since = 0 if sinces[c] is None else max(int(sinces[c]), 0)
+    col.n_moves = len(moves)
+    for m, (x, y) in enumerate(moves):
+      _describe_move(col.moves[m], per_slot=x, packed=y, to_packed=True)
+    col.out_keys, col.out_slots, col.out_capacity = out['keys'].data_ptr(), out['src_slots'].data_ptr(), cap
+    col.count = counts.data_ptr() + 8 * c
+    outs.append((out, cap))
+  lib = _lib.lib()
+  nbytes = C.c_size_t()
+  _lib.check(lib.hbk_hash_export_workspace_bytes(n, cols, C.byref(nbytes)))
+  workspace = torch.empty(max(nbytes.value // 8, 1), dtype=torch.int64, device=dev)
+  _lib.check(lib.hbk_hash_export_n(n, cols, workspace.data_ptr(), _lib.current_stream(dev)))
+  result = []
+  for c, (k, (out, cap)) in enumerate(zip(counts.tolist(), outs)):
+    if k > cap:
+      raise _bad(f'table {c}: {k} keys match but the counters promise {cap}: they are stale (a restore of the raw '
+                 'arrays?) -- call recount() first')
+    result.append(HashExport(out['keys'][:k], out['rows'][:k], out['last_seen'][:k] if tables[c].expiring else None,
+                             out['freq'][:k] if tables[c].expiring else None, [x[:k] for x in out['slots']],
+                             out['src_slots'][:k], 0 if sinces[c] is None else max(int(sinces[c]), 0)))
+  return result
 
 
 def hash_owner(ids, world):

@@ -110,19 +110,50 @@ class ShardedHashGroupLookup(ShardedGroupLookup):
     self._call_cache = self._keep = self._auto_state = None
     self._setup()
 
-  def maybe_grow(self, max_load=0.75, factor=2.0):
-    """:meth:`HashTable.maybe_grow` on every table of this rank, the bound optimizer slots moving along as
-    companions (the rows no key holds afterwards: Adagrad's accumulator ``initial_accumulator_value``, Adam's m /
-    v 0, FTRL's accum its ``initial_accumulator_value`` and linear 0), then :meth:`rebind` with the new tensors
-    if any table was rehashed.  Local to the rank: no exchange, and ranks need not agree.  Returns per table
-    whether it was rehashed."""
-    kinds = []   # (attribute, index in a pair or None, fill value)
+  def _slot_kinds(self):
+    """The bound optimizer slots as (attribute, index in a pair or None, fill value), in the order every method
+    that moves them uses: ``accums``; ``moments`` m, v; ``ftrl_slots`` accum, linear."""
+    kinds = []
     if self.accums is not None:
       kinds.append(('accums', None, self.initial_accumulator_value))
     if self.moments is not None:
       kinds += [('moments', 0, 0.0), ('moments', 1, 0.0)]
     if self.ftrl_slots is not None:
       kinds += [('ftrl_slots', 0, self.ftrl.initial_accumulator_value), ('ftrl_slots', 1, 0.0)]
+    return kinds
+
+  def _slot_tensors(self, c):
+    return [getattr(self, name)[c] if k is None else getattr(self, name)[c][k] for name, k, _ in self._slot_kinds()]
+
+  def export_items(self, since=None):
+    """:func:`hash_export` of this rank's tables in one call, the bound optimizer slots travelling as companions
+    in the order Adagrad's ``accums``; Lazy Adam's ``moments`` m, v; FTRL's ``ftrl_slots`` accum, linear (those
+    that are bound).  ``since``: None, or the step of a delta -- every table must then be expiring.  Returns one
+    :class:`HashExport` per table.  Local to the rank: no exchange, and ranks need not agree."""
+    self._current()
+    n = len(self.tables)
+    return _ht.hash_export(self.tables, [since] * n, [self._slot_tensors(c) for c in range(n)])
+
+  def import_items(self, exports):
+    """``exports[c]``: a :class:`HashExport` of column c -- typically ``HashExport.cat`` of what every rank of the
+    saving job exported, at whatever world size that was.  Each table upserts the keys THIS rank owns
+    (``hash_owner(keys, world_size) == rank``) with rows, metadata and the bound optimizer slots (the order of
+    :meth:`export_items`); the tensors stay where they are, so the plan stays valid.  Returns the slots per
+    table.  Local to the rank: no exchange, and ranks need not agree."""
+    self._current()
+    exports = list(exports)
+    if len(exports) != len(self.tables):
+      raise _ht._bad(f'expected {len(self.tables)} exports, got {len(exports)}')   # pylint: disable=protected-access
+    return [t.import_items(e, self._slot_tensors(c), world=self.world_size, rank=self.coll.rank)
+            for c, (t, e) in enumerate(zip(self.tables, exports))]
+
+  def maybe_grow(self, max_load=0.75, factor=2.0):
+    """:meth:`HashTable.maybe_grow` on every table of this rank, the bound optimizer slots moving along as
+    companions (the rows no key holds afterwards: Adagrad's accumulator ``initial_accumulator_value``, Adam's m /
+    v 0, FTRL's accum its ``initial_accumulator_value`` and linear 0), then :meth:`rebind` with the new tensors
+    if any table was rehashed.  Local to the rank: no exchange, and ranks need not agree.  Returns per table
+    whether it was rehashed."""
+    kinds = self._slot_kinds()
     new = {name: [list(x) if k is not None else x for x in getattr(self, name)]
            for name, k, _ in kinds}
     grown = []

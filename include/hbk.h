@@ -973,6 +973,93 @@ typedef struct {
 } hbk_hash_rehash_column_t;
 int hbk_hash_rehash_n(int32_t n_cols, const hbk_hash_rehash_column_t* cols, hbk_stream_t stream);
 
+/* Export and import: a table leaves the device whole and comes back whole.  A table's keys with their rows are
+ * not the table: the optimizer slots of every key, and an expiring table's last_seen and freq, are state too.
+ * hbk_hash_export_n packs the keys a table holds -- all of them, or those touched since a step -- with every
+ * per-slot array named in the call into dense arrays of a geometry-free form; hbk_hash_store_rows_n is the
+ * second half of the way back (the first half, placing the keys, is the table's own translate entry).
+ *
+ * hbk_hash_export_n, N tables per call (32 per launch), three launches per 32 tables on the call's stream.
+ *
+ * Selection.  Source slot s of column c is exported iff it holds a key -- keys[s] is not EMPTY, and not
+ * TOMBSTONE when expiring != 0 (expiring == 0: INT64_MIN + 1 is an ordinary key, as for hbk_hash_rehash_n) --
+ * and, in addition, since <= 0 or last_seen[s] >= since.  last_seen[s] is the step of the slot's last training
+ * translate, and that step's backward is the only thing that writes the slot's row and optimizer slots: with
+ * since = s0 + 1 the export holds exactly the keys whose payload may have changed after step s0 (a delta).
+ * last_seen is read only when since > 0.
+ *
+ * Order.  The exported keys appear in ASCENDING SOURCE-SLOT ORDER, packed from position 0: the p-th exported
+ * slot goes to position p.  No ticket atomic and no look-back between tiles -- no workgroup waits for another:
+ *   1. count: every 256-slot tile writes its number of matches into the workspace;
+ *   2. scan:  one workgroup per column turns the tile counts into exclusive offsets and writes the total to count;
+ *   3. write: every tile evaluates the same predicate again and places its matches behind its offset.
+ * The table's arrays must not be written during the call (launch 3 must see what launch 1 saw).
+ *
+ * Moves.  As for hbk_hash_rehash_n, each of the n_moves arrays is rows of `words` 4-byte words copied bit for
+ * bit: for the key of source slot s at position p, dst[p * dst_pitch + j] = src[s * src_pitch + j] for j <
+ * words; the padding between words and the pitch is not written.  Rows whose bases, pitches and width are all
+ * multiples of 16 bytes travel in 16-byte accesses.  The embedding rows, last_seen, freq and the optimizer slots
+ * are all just moves.
+ *
+ * Results.  out_keys[p] = the key, out_slots[p] (if not NULL) = its source slot, for p < min(count,
+ * out_capacity).  *count ALWAYS receives the total number of matches; nothing is written at positions >=
+ * out_capacity -- keys, slots and rows alike -- and the caller compares the two.  Positions in [count,
+ * out_capacity) are not written.
+ *
+ * Memory rules.  Plain loads and plain vector stores only; no atomics.  Reproducible between runs: everything
+ * -- the output is a function of the table's arrays alone.  What is NOT reproducible is inherited from the
+ * table: which slot a key got when it was inserted, hence the order of the keys of two tables that hold the
+ * same set.
+ *
+ * Workspace: hbk_hash_export_workspace_bytes(n_cols, cols, &bytes) reads the geometry of the columns only (8
+ * bytes per 256 slots); one device pointer, 8-byte aligned, not kept after the call.  No host synchronisation:
+ * capturable.
+ *
+ * Refused (HBK_INVALID_ARGUMENT) before any device work: everything hbk_hash_rehash_n refuses of a source
+ * geometry and of a move; NULL count; NULL out_keys with out_capacity > 0; out_capacity < 0; since > 0 with NULL
+ * last_seen; a NULL (or not 8-byte aligned) workspace with n_cols > 0.  n_cols == 0 returns HBK_OK without
+ * touching a device.
+ *
+ * hbk_hash_store_rows_n, N columns per launch (32 per launch).  For every i < n with 0 <= slots[i] < dst_rows
+ * and every move: dst[slots[i] * dst_pitch + j] = src[i * src_pitch + j] for j < words, one lane group per row,
+ * the 16-byte rule as above; entries with slots[i] < 0 (a key that did not fit) or >= dst_rows are skipped.
+ * Here src is the packed array (an export's) and dst the per-slot array of the table.  An import is an upsert:
+ * the caller translates the imported keys with its table's own entry (insert != 0, table == NULL: rows not
+ * initialised; an expiring table reuses tombstones by its own walk) and hands the slots to this entry.
+ * last_seen and freq travel as moves and overwrite what the expiring insert just stamped, so an imported key
+ * keeps its age and count.  Distinct keys have distinct slots, so no two rows race; duplicate slots[] entries
+ * are the caller's contract (which of the duplicates' rows stays is then run-dependent, word by word).  Plain
+ * loads and stores, no atomics, no workspace, no host synchronisation: capturable.  Refused: n_cols < 0; NULL
+ * cols with n_cols > 0; n < 0; NULL slots with n > 0; slots not 8-byte aligned; dst_rows < 0; everything
+ * hbk_hash_rehash_n refuses of a move.  n_cols == 0 returns HBK_OK without touching a device.
+ *
+ * Both entries are detected by the presence of the symbol; the version stays that of 0.2.0. */
+typedef struct {
+  const int64_t* keys;      /* device [slab_count * slab_size], 8-byte aligned */
+  int64_t slab_count;
+  int32_t slab_size;        /* 1..64 */
+  int32_t expiring;         /* != 0: a TOMBSTONE is skipped; 0: INT64_MIN + 1 is an ordinary key */
+  const int32_t* last_seen; /* device int32 [slab_count * slab_size]; may be NULL when since <= 0 */
+  int32_t since;            /* <= 0: every key; > 0: the keys with last_seen >= since */
+  int32_t n_moves;          /* 0..HBK_HASH_MAX_MOVES */
+  hbk_hash_move_t moves[HBK_HASH_MAX_MOVES];   /* src: the per-slot array; dst: the packed array */
+  int64_t* out_keys;        /* device int64 [out_capacity] */
+  int64_t* out_slots;       /* device int64 [out_capacity] or NULL */
+  int64_t out_capacity;     /* >= 0: rows of out_keys, out_slots and every move's dst */
+  int64_t* count;           /* device int64[1]: the total number of matches */
+} hbk_hash_export_column_t;
+int hbk_hash_export_workspace_bytes(int32_t n_cols, const hbk_hash_export_column_t* cols, size_t* bytes);
+int hbk_hash_export_n(int32_t n_cols, const hbk_hash_export_column_t* cols, void* workspace, hbk_stream_t stream);
+
+typedef struct {
+  const int64_t* slots;     /* device int64 [n]: destination row of packed row i; outside [0, dst_rows): skipped */
+  int64_t n;
+  int64_t dst_rows;         /* rows of every move's dst */
+  int32_t n_moves;          /* 0..HBK_HASH_MAX_MOVES */
+  hbk_hash_move_t moves[HBK_HASH_MAX_MOVES];   /* src: the packed array; dst: the per-slot array */
+} hbk_hash_store_column_t;
+int hbk_hash_store_rows_n(int32_t n_cols, const hbk_hash_store_column_t* cols, hbk_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * Communicator lifecycle: HbGetNcclId / HbCreateNcclCollective /
  * HbIsNcclCollectiveInitialized / async-error polling.
