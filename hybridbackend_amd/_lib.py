@@ -109,6 +109,12 @@ class HashRun(C.Structure):
   _fields_ = [('keys', C.c_void_p), ('slots', C.c_void_p), ('n_keys', C.c_int64)]
 
 
+class HashSequence(C.Structure):
+  """hbk_hash_sequence_t"""
+  _fields_ = [('row_splits', C.c_void_p), ('n_segments', C.c_int64), ('max_len', C.c_int32),
+              ('has_pad', C.c_int32), ('pad_id', C.c_int64), ('lengths', C.c_void_p)]
+
+
 class ShardedHash(C.Structure):
   """hbk_sharded_hash_t"""
   _fields_ = [('keys_cache', C.c_void_p), ('slab_count', C.c_int64), ('slab_size', C.c_int32),
@@ -240,6 +246,7 @@ def _declare(l):
     'hbk_hash_insert_expiring_admit_n': (C.c_int, [i32, vp, vp, vp, i32, vp]),
     'hbk_hash_rehash_n': (C.c_int, [i32, vp, vp]),
     'hbk_hash_translate_runs_n': (C.c_int, [i32, vp, vp, vp, vp, vp, i32, vp]),
+    'hbk_hash_translate_sequence_n': (C.c_int, [i32, vp, vp, vp, vp, i32, vp]),
     'hbk_hash_export_workspace_bytes': (C.c_int, [i32, vp, vp]),
     'hbk_hash_export_n': (C.c_int, [i32, vp, vp, vp]),
     'hbk_hash_store_rows_n': (C.c_int, [i32, vp, vp]),

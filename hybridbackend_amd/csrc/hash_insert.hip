@@ -70,6 +70,15 @@
 // the body above, so the memory rules, the bounds and the one-inserter argument hold unchanged: occurrences of a
 // key in different runs of a column are occurrences of that key in one launch.  The instantiations without runs
 // are the kernels they were, instruction for instruction.
+//
+// Sequences (hbk_hash_translate_sequence_n): the same kernels with Args = SeqArgs<the entry's Args>, a third source
+// of work, indexed by POSITION of the [B * T] slot grid.  A tile covers positions of one column (found as a
+// column's keys are: the column's n_keys is B * T, its slots the grid); a position finds its sample by a FastDiv
+// by T, reads the two row_splits entries and takes its key, the pad id or NOTHING.  Nothing is a state of its own
+// (`there`), not the EMPTY sentinel by value: a position with nothing is not walked, exactly as a lane past n_keys,
+// its slot is written -1 and it counts nowhere, while an id INT64_MIN in the data is -1 counted as failed, as
+// everywhere.  The walk is the body above, every lane of the wave in every ballot and shuffle as before.
+// Everything new is behind `if constexpr (kSeq)`.
 #include <math.h>
 
 #include "common.h"
@@ -205,6 +214,49 @@ __device__ inline int64_t* work_slots(const RunsArgs<Base>& r, const HashCol&, i
 template <class Base>
 __device__ inline int64_t work_n_keys(const RunsArgs<Base>& r, const HashCol&, int ri) { return r.run[ri].n_keys; }
 
+// Keys that arrive as ragged sequences (hbk_hash_translate_sequence_n): HashCol.n_keys is the POSITIONS of the
+// column, B * T, HashCol.slots its slot grid and tile_start tiles the positions; HashCol.keys are the flat ids.
+struct SeqCol {
+  const int32_t* row_splits;   // [B + 1], or NULL: one id per sample
+  int32_t* lengths;            // [B] or NULL
+  int64_t pad_id;
+  int64_t n_ids;
+  FastDiv len_div;             // .d = T
+  int32_t has_pad;
+  int32_t pad_;
+};
+
+template <class Base>
+struct SeqArgs : Base {
+  SeqCol s[kMaxColsPerLaunch];
+};
+
+template <class Args>
+struct IsSeq { static constexpr bool value = false; };
+template <class Base>
+struct IsSeq<SeqArgs<Base>> { static constexpr bool value = true; };
+
+// The id of position p = b * T + t: the sample's t-th id when t < min(len_b, T), else the pad id, else nothing
+// (*there = false; the value returned is then not looked at as a key).  Ids at t >= T are never read; row_splits
+// that point outside the ids name no id.  The lane that is told to also stores lengths[b] (the one of t == 0).
+__device__ inline long long seq_key(const SeqCol& s, const int64_t* ids, int64_t p, bool write_length, bool* there) {
+  const int64_t T = (int64_t)s.len_div.d;
+  const int64_t b = (int64_t)fastdiv((uint64_t)p, s.len_div);
+  const int64_t t = p - b * T;
+  int64_t start = b, len = 1;
+  if (s.row_splits != nullptr) {
+    start = s.row_splits[b];
+    len = (int64_t)s.row_splits[b + 1] - start;
+  }
+  const int64_t L = len < 0 ? 0 : (len < T ? len : T);
+  if (write_length && t == 0 && s.lengths != nullptr) s.lengths[b] = (int32_t)L;
+  *there = true;
+  if (t < L && (uint64_t)(start + t) < (uint64_t)s.n_ids) return (long long)ids[start + t];
+  if (s.has_pad != 0) return (long long)s.pad_id;
+  *there = false;
+  return kEmptyKey;
+}
+
 // float j of the initial row of `key` (include/hbk.h): exact in fp32 up to the final multiply
 __host__ __device__ inline float init_value(int64_t key, uint64_t seed, int j, float scale) {
   const uint64_t mix = (seed + (uint64_t)j + 1ull) * 0x9E3779B97F4A7C15ull;
@@ -275,6 +327,7 @@ __device__ inline long long read_slot(const long long* p) {
 template <bool INSERT, int PHASE = 0, class Args = HashArgs>
 __global__ __launch_bounds__(kBlock) void hash_insert_kernel(const Args args) {
   static_assert(PHASE == 0 || INSERT == (PHASE == 2), "phase 1 finds, phase 2 inserts");
+  constexpr bool kSeq = IsSeq<Args>::value;
   const HashArgs& a = hash_args(args);
   const int b = (int)blockIdx.x;
   const int ri = find_run(args, b);
@@ -302,6 +355,7 @@ __global__ __launch_bounds__(kBlock) void hash_insert_kernel(const Args args) {
   long long key[kKeys], read_key[kKeys];
   int64_t slab[kKeys];
   [[maybe_unused]] bool pending[kKeys], admitted[kKeys];   // (PHASE 2)
+  [[maybe_unused]] bool there[kKeys];                      // (sequences) the position holds an id: a key or the pad id
   if constexpr (PHASE == 2) {
     // one coalesced read of the answers of phase 1: a wave with nothing pending leaves here
     bool any = false;
@@ -316,7 +370,13 @@ __global__ __launch_bounds__(kBlock) void hash_insert_kernel(const Args args) {
 #pragma unroll
   for (int u = 0; u < kKeys; ++u) {
     const int64_t i = i0 + (int64_t)u * groups_per_wave;
-    if constexpr (PHASE == 2) {
+    if constexpr (kSeq) {
+      // (phase 2 reads what phase 1 read; the lengths were written by phase 1)
+      const bool wanted = PHASE == 2 ? pending[u] : i < n_keys;
+      there[u] = false;
+      key[u] = kEmptyKey;
+      if (wanted) key[u] = seq_key(args.s[ci], c.keys, i, PHASE != 2 && sub == 0, &there[u]);
+    } else if constexpr (PHASE == 2) {
       key[u] = pending[u] ? (long long)work_keys(args, c, ri)[i] : kEmptyKey;
     } else {
       key[u] = i < n_keys ? (long long)work_keys(args, c, ri)[i] : kEmptyKey;
@@ -418,7 +478,11 @@ __global__ __launch_bounds__(kBlock) void hash_insert_kernel(const Args args) {
     } else if (i < n_keys && sub == 0) {
       work_slots(args, c, ri)[i] = result;
       n_inserted += won ? 1 : 0;
-      n_failed += (PHASE == 1 ? result == -1 : result < 0) ? 1 : 0;
+      if constexpr (kSeq) {
+        n_failed += there[u] && (PHASE == 1 ? result == -1 : result < 0) ? 1 : 0;   // nothing here: not a failure
+      } else {
+        n_failed += (PHASE == 1 ? result == -1 : result < 0) ? 1 : 0;
+      }
     }
   }
   if (c.counts != nullptr) {
@@ -471,6 +535,7 @@ template <bool INSERT, int PHASE = 0, class Args = ExpiringArgs>
 __global__ __launch_bounds__(kBlock) void hash_insert_expiring_kernel(const Args args) {
   static_assert(PHASE == 0 || INSERT == (PHASE == 2), "phase 1 finds, phase 2 inserts");
   constexpr bool kMetadata = INSERT || PHASE == 1;
+  constexpr bool kSeq = IsSeq<Args>::value;
   const ExpiringArgs& x = expiring_args(args);
   const HashArgs& a = x.h;
   const int b = (int)blockIdx.x;
@@ -500,6 +565,7 @@ __global__ __launch_bounds__(kBlock) void hash_insert_expiring_kernel(const Args
   long long key[kKeys], read_key[kKeys];
   int64_t home[kKeys];
   [[maybe_unused]] bool pending[kKeys], admitted[kKeys];   // (PHASE 2)
+  [[maybe_unused]] bool there[kKeys];                      // (sequences) the position holds an id: a key or the pad id
   if constexpr (PHASE == 2) {
     // one coalesced read of the answers of phase 1: a wave with nothing pending leaves here
     bool any = false;
@@ -515,7 +581,13 @@ __global__ __launch_bounds__(kBlock) void hash_insert_expiring_kernel(const Args
 #pragma unroll
   for (int u = 0; u < kKeys; ++u) {
     const int64_t i = i0 + (int64_t)u * groups_per_wave;
-    if constexpr (PHASE == 2) {
+    if constexpr (kSeq) {
+      // (phase 2 reads what phase 1 read; the lengths were written by phase 1)
+      const bool wanted = PHASE == 2 ? pending[u] : i < n_keys;
+      there[u] = false;
+      key[u] = kEmptyKey;
+      if (wanted) key[u] = seq_key(args.s[ci], c.keys, i, PHASE != 2 && sub == 0, &there[u]);
+    } else if constexpr (PHASE == 2) {
       key[u] = pending[u] ? (long long)work_keys(args, c, ri)[i] : kEmptyKey;
     } else {
       key[u] = i < n_keys ? (long long)work_keys(args, c, ri)[i] : kEmptyKey;
@@ -636,7 +708,11 @@ __global__ __launch_bounds__(kBlock) void hash_insert_expiring_kernel(const Args
         work_slots(args, c, ri)[i] = result;
         n_inserted += won ? 1 : 0;
         n_reused += reused ? 1 : 0;
-        n_failed += (PHASE == 1 ? result == -1 : result < 0) ? 1 : 0;
+        if constexpr (kSeq) {
+          n_failed += there[u] && (PHASE == 1 ? result == -1 : result < 0) ? 1 : 0;   // nothing here: not a failure
+        } else {
+          n_failed += (PHASE == 1 ? result == -1 : result < 0) ? 1 : 0;
+        }
       }
       seen_slot[u] = i < n_keys && sub == 0 ? result : -1;   // (kPending is no slot either)
     }
@@ -1104,4 +1180,140 @@ extern "C" int hbk_hash_translate_runs_n(int32_t n_cols, const hbk_hash_column_t
                                insert != 0 ? hash_insert_kernel<true, 0, RunsArgs<HashArgs>>
                                            : hash_insert_kernel<false, 0, RunsArgs<HashArgs>>,
                                stream);
+}
+
+// ---- keys that arrive as ragged sequences ---------------------------------------------------------------
+namespace hbk {
+namespace {
+
+static_assert(sizeof(SeqArgs<HashArgs>) <= 24576, "kernarg budget");
+static_assert(sizeof(SeqArgs<ExpiringAdmitArgs>) <= 24576, "kernarg budget");   // (64 columns fit: no smaller chunk)
+
+// One pass over the positions of all columns with `kernel`: up to kMaxColsPerLaunch columns with positions per
+// launch.
+template <class Base>
+int launch_sequences(const char* who, int32_t n_cols, const hbk_hash_column_t* cols, const hbk_hash_expiry_t* exp,
+                     const hbk_hash_admission_t* adm, const hbk_hash_sequence_t* seq, int32_t insert,
+                     void (*kernel)(const SeqArgs<Base>), hipStream_t stream) {
+  int32_t c0 = 0;
+  while (c0 < n_cols) {
+    SeqArgs<Base> args;
+    HashArgs& h = hash_part(static_cast<Base&>(args));
+    int32_t k = 0;
+    int64_t tiles = 0;
+    h.tile_start[0] = 0;
+    while (c0 < n_cols && k < kMaxColsPerLaunch) {
+      const int32_t c = c0++;
+      const hbk_hash_sequence_t& q = seq[c];
+      const int64_t positions = q.n_segments * (int64_t)q.max_len;
+      if (positions == 0) continue;
+      hbk_hash_column_t col = cols[c];   // (the kernel's n_keys: the positions; its keys: the flat ids)
+      col.n_keys = positions;
+      tiles += describe_column(col, insert, &h.col[k]);
+      HBK_REQUIRE(tiles < (1ll << 31), "%s: grid too large", who);
+      if (ExpiryCol* e = expiry_part(static_cast<Base&>(args))) describe_expiry(exp[c], e + k);
+      if (AdmitCol* f = admit_part(static_cast<Base&>(args))) describe_admission(adm[c], f + k);
+      SeqCol& s = args.s[k];
+      s.row_splits = q.row_splits;
+      s.lengths = q.lengths;
+      s.pad_id = q.pad_id;
+      s.n_ids = cols[c].n_keys;
+      s.len_div = make_fastdiv((uint64_t)q.max_len);
+      s.len_div.d = (uint64_t)q.max_len;
+      s.has_pad = q.has_pad != 0 ? 1 : 0;
+      s.pad_ = 0;
+      ++k;
+      h.tile_start[k] = (int32_t)tiles;
+    }
+    if (k == 0) continue;
+    h.n_cols = k;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)tiles), dim3(kBlock), 0, stream, args);
+    HBK_HIP_OK(hipGetLastError());
+  }
+  return HBK_OK;
+}
+
+}  // namespace
+}  // namespace hbk
+
+// The four translate entries over the first T ids of every sample, answers into a [B * T] slot grid: one launch
+// (two for filtered tables: every counting launch of the call before any admitting one) per 64 columns.
+extern "C" int hbk_hash_translate_sequence_n(int32_t n_cols, const hbk_hash_column_t* cols,
+                                             const hbk_hash_expiry_t* exp, const hbk_hash_admission_t* adm,
+                                             const hbk_hash_sequence_t* seq, int32_t insert,
+                                             hbk_stream_t stream_) {
+  using namespace hbk;
+  const char* who = "hash_translate_sequence_n";
+  HBK_REQUIRE(n_cols >= 0, "%s: n_cols must be >= 0, got %d", who, n_cols);
+  HBK_REQUIRE(n_cols == 0 || cols != nullptr, "%s: cols is NULL", who);
+  HBK_REQUIRE(n_cols == 0 || seq != nullptr, "%s: seq is NULL", who);
+  const int64_t limit = exp != nullptr || adm != nullptr ? (1ll << 30) : (1ll << 31);
+  for (int32_t c = 0; c < n_cols; ++c) {
+    const hbk_hash_column_t& h = cols[c];
+    const hbk_hash_sequence_t& q = seq[c];
+    HBK_REQUIRE(q.max_len >= 1, "%s: column %d: max_len must be >= 1, got %d", who, c, q.max_len);
+    HBK_REQUIRE(q.n_segments >= 0, "%s: column %d: n_segments must be >= 0, got %lld", who, c,
+                (long long)q.n_segments);
+    HBK_REQUIRE(q.n_segments < limit && q.n_segments * (int64_t)q.max_len < limit,
+                "%s: column %d: %lld samples x max_len %d positions: must stay below 2^%d%s", who, c,
+                (long long)q.n_segments, q.max_len, limit == (1ll << 30) ? 30 : 31,
+                limit == (1ll << 30) ? " (a counter must not wrap)" : "");
+    const int64_t positions = q.n_segments * (int64_t)q.max_len;
+    HBK_REQUIRE(positions == 0 || h.slots != nullptr, "%s: column %d: NULL slots (the grid is needed with B * T > 0)",
+                who, c);
+    HBK_REQUIRE(h.n_keys >= 0 && h.n_keys < (1ll << 31), "%s: column %d: n_keys must be in [0, 2^31), got %lld", who,
+                c, (long long)h.n_keys);
+    HBK_REQUIRE(h.n_keys == 0 || h.keys != nullptr, "%s: column %d: NULL keys with n_keys = %lld", who, c,
+                (long long)h.n_keys);
+    HBK_REQUIRE(q.row_splits != nullptr || h.n_keys == q.n_segments,
+                "%s: column %d: row_splits is NULL (one id per sample) but n_keys %lld != n_segments %lld", who, c,
+                (long long)h.n_keys, (long long)q.n_segments);
+    if (q.has_pad != 0) {
+      HBK_REQUIRE(q.pad_id != (int64_t)kEmptyKey, "%s: column %d: pad_id INT64_MIN (EMPTY) is never stored", who, c);
+      HBK_REQUIRE(exp == nullptr || q.pad_id != (int64_t)kTombstoneKey,
+                  "%s: column %d: pad_id INT64_MIN + 1 (TOMBSTONE) is never stored in an expiring table", who, c);
+    }
+    // the column as the matching entry would see it: one key per position (a column without ids has no keys to
+    // show: the grid stands in, the check only asks for an address)
+    hbk_hash_column_t whole = h;
+    whole.n_keys = positions;
+    if (whole.keys == nullptr) whole.keys = h.slots;
+    if (int rc = check_column(who, c, whole)) return rc;
+    if (adm != nullptr) {
+      if (int rc = check_admission(who, c, whole, adm[c])) return rc;
+    }
+    HBK_REQUIRE(exp == nullptr || positions == 0 ||
+                    (exp[c].last_seen != nullptr && exp[c].freq != nullptr && exp[c].step != nullptr),
+                "%s: column %d: NULL expiry buffer (last_seen, freq and step are needed with B * T > 0)", who, c);
+  }
+  hipStream_t stream = as_stream(stream_);
+  if (adm != nullptr && insert != 0) {   // count, then admit
+    if (exp != nullptr) {
+      if (int rc = launch_sequences<ExpiringAdmitArgs>(
+              who, n_cols, cols, exp, adm, seq, insert,
+              hash_insert_expiring_kernel<false, 1, SeqArgs<ExpiringAdmitArgs>>, stream)) {
+        return rc;
+      }
+      return launch_sequences<ExpiringAdmitArgs>(who, n_cols, cols, exp, adm, seq, insert,
+                                                 hash_insert_expiring_kernel<true, 2, SeqArgs<ExpiringAdmitArgs>>,
+                                                 stream);
+    }
+    if (int rc = launch_sequences<AdmitArgs>(who, n_cols, cols, exp, adm, seq, insert,
+                                             hash_insert_kernel<false, 1, SeqArgs<AdmitArgs>>, stream)) {
+      return rc;
+    }
+    return launch_sequences<AdmitArgs>(who, n_cols, cols, exp, adm, seq, insert,
+                                       hash_insert_kernel<true, 2, SeqArgs<AdmitArgs>>, stream);
+  }
+  // no filter, or a find (which never touches the sketch)
+  if (exp != nullptr) {
+    return launch_sequences<ExpiringArgs>(who, n_cols, cols, exp, nullptr, seq, insert,
+                                          insert != 0 ? hash_insert_expiring_kernel<true, 0, SeqArgs<ExpiringArgs>>
+                                                      : hash_insert_expiring_kernel<false, 0, SeqArgs<ExpiringArgs>>,
+                                          stream);
+  }
+  return launch_sequences<HashArgs>(who, n_cols, cols, nullptr, nullptr, seq, insert,
+                                    insert != 0 ? hash_insert_kernel<true, 0, SeqArgs<HashArgs>>
+                                                : hash_insert_kernel<false, 0, SeqArgs<HashArgs>>,
+                                    stream);
 }

@@ -905,6 +905,71 @@ int hbk_hash_translate_runs_n(int32_t n_cols, const hbk_hash_column_t* cols,
                               const int32_t* n_runs, const hbk_hash_run_t* const* runs,
                               int32_t insert, hbk_stream_t stream);
 
+/* Hash-keyed sequence lookups: the first T ids of every sample translated into a slot grid.  The behaviour
+ * histories of DIN / DIEN / BST (item and shop ids: an open vocabulary) are the columns that most need a raw-id
+ * table, and hbk_group_lookup_fwd_sequence above reads ids only through floormod(id, bucket).  The existing calls
+ * do not compose: hbk_sequence_row_grid_n with bucket == 0 maps every negative id to -1 and writes -1 at padding
+ * positions, and -1 is an ordinary key of a hash table (translated, it would be inserted once per padding position,
+ * bump its freq and count in the sketch); translating the whole ragged list inserts the ids past T, which the
+ * sequence lookup promises are never read -- they would claim a key slot, a row and its optimizer slots for ever
+ * and stay fresh in an expiring table without ever being trained; padding with INT64_MIN gives -1 but counts
+ * every padding position in n_failed.  hbk_hash_translate_sequence_n reads ids the way the sequence lookup does.
+ *
+ * exp and adm name the table kind of ALL columns as for hbk_hash_translate_runs_n.  cols[c] describes table c;
+ * cols[c].keys / n_keys are the flat int64 ids of the column and cols[c].slots is the SLOT GRID, int64 [B * T]
+ * with B = seq[c].n_segments and T = seq[c].max_len.  len_b = row_splits[b + 1] - row_splits[b] (1 when
+ * row_splits == NULL) and L_b = min(len_b, T).  The EFFECTIVE ID LIST E_c of a column is, sample after sample,
+ * the sample's first L_b ids, followed by T - L_b copies of pad_id when has_pad.
+ *   - The call does to the table, its counters, stats, last_seen, freq and the sketch exactly what the matching
+ *     existing entry does when called ONCE on E_c.
+ *   - The answer for position p = b * T + t is written to slots[p].
+ *   - A padding position (t >= L_b) without has_pad gets slots[p] = -1 and touches nothing else: no walk, no
+ *     n_failed, no filtered, no sketch cell, no freq.
+ *   - lengths[b] = L_b (lengths may be NULL: not wanted).
+ *   - Ids at positions >= T of a sample are never read.
+ *   - An id equal to INT64_MIN in the data behaves as it does everywhere: -1, counted in n_failed; in an expiring
+ *     table INT64_MIN + 1 behaves the same way.  "Nothing here" is a state of its own in the kernel, not the
+ *     EMPTY sentinel by value.
+ *   - insert == 0 is a pure find (of the entry without a filter: no sketch is touched).
+ *   - For filtered tables every counting launch of the call runs before any admitting launch.
+ * A row_splits entry that points outside [0, n_keys) names no id: such a position is padding.
+ *
+ * Kernel: those of the four entries with a third way to find a tile's work, by POSITION.  A tile covers
+ * positions of one column; a position finds its sample by a fast division by T, reads the two row_splits
+ * entries and takes its key, the pad id or nothing; the walk runs unchanged.  One launch per call (two for
+ * filtered tables) up to 64 columns, chunked beyond.
+ *
+ * Recipe.  The slot grid is what hbk_group_lookup_fwd_sequence's row_grid is to a bucketed column:
+ *     forward   hbk_group_lookup_fwd[_clipped] over a column of ONE id per segment with ids = the slot grid
+ *               (HBK_INT64), n_ids = n_segments = B * T, row_splits = NULL, bucket = 0, table = the hash table's
+ *               rows, out = the [B, T, dim] output viewed [B * T, dim]: a -1 reads a zero row
+ *     backward  the same column handed to hbk_group_lookup_bwd* (the recipe of hbk_group_lookup_fwd_sequence)
+ * The translate and the gather are two launches on purpose: a concurrent duplicate of a new id can hit the freshly
+ * claimed slot before the winner has written its row, so the row write and the gather need a kernel boundary
+ * between them.
+ *
+ * Refused (HBK_INVALID_ARGUMENT) before any device work: everything the matching entry refuses of a column (with
+ * B * T in the place of n_keys), of expiry and of admission; seq == NULL with n_cols > 0; max_len < 1;
+ * n_segments < 0; B * T >= 2^31 (>= 2^30 with exp or adm: a counter must not wrap); NULL slots with B * T > 0;
+ * n_keys outside [0, 2^31); NULL keys with n_keys > 0; row_splits == NULL with n_keys != n_segments; has_pad with
+ * pad_id == INT64_MIN, and in an expiring table also pad_id == INT64_MIN + 1.  n_cols == 0, B == 0 and a column
+ * of only empty samples are fine.  No workspace, no host synchronisation: capturable.  Detected by the presence of
+ * the symbol; the structs above and the version are those of 0.2.0. */
+typedef struct {
+  const int32_t* row_splits;   /* device int32 [n_segments + 1], or NULL: one id per sample */
+  int64_t n_segments;          /* B >= 0 */
+  int32_t max_len;             /* T >= 1 */
+  int32_t has_pad;             /* 0: padding positions are -1 in the grid and touch nothing */
+  int64_t pad_id;              /* has_pad != 0: a RAW id, any value the table can store */
+  int32_t* lengths;            /* device int32 [n_segments], or NULL */
+} hbk_hash_sequence_t;
+/* seq[c] (and exp[c], adm[c]) belongs to cols[c] */
+int hbk_hash_translate_sequence_n(int32_t n_cols, const hbk_hash_column_t* cols,
+                                  const hbk_hash_expiry_t* exp,      /* NULL, or [n_cols] */
+                                  const hbk_hash_admission_t* adm,   /* NULL, or [n_cols] */
+                                  const hbk_hash_sequence_t* seq,    /* [n_cols] */
+                                  int32_t insert, hbk_stream_t stream);
+
 /* Rehash: growth and tombstone compaction on the device.  A full table answers -1 for ever, and an expiring
  * table's probes get longer with every tombstone; both are cured by moving every live key into a fresh key
  * array -- of a larger geometry, or of the same one -- with its rows.  hbk_hash_rehash_n does that for N tables
