@@ -335,6 +335,13 @@ __device__ inline int rank_below(unsigned long long mask) {
       (unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
 }
 
+// A launch of up to 64 columns, tile_start[i] = the first tile of column i: the last column whose first tile
+// is <= b.  One entry per lane, one ballot; every lane of the wave calls.
+__device__ inline int column_of(const int32_t* tile_start, int n_cols, int b, int lane) {
+  const int t0 = lane < n_cols ? tile_start[lane] : 0x7fffffff;
+  return __builtin_amdgcn_readfirstlane((int)__builtin_popcountll(__ballot(t0 <= b)) - 1);
+}
+
 }  // namespace hbk
 
 #endif  // HBK_CSRC_COMMON_H_

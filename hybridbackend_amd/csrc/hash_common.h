@@ -1,0 +1,147 @@
+// The hash tables' contract, once: what probe.hip, hash_insert.hip, hash_evict.hip, hash_rehash.hip and
+// hash_export.hip must agree on to read each other's tables -- the sentinels, the placement hash, which slots
+// hold a key, the host checks of a table's geometry -- and the pieces their sweeps share: the wave compaction
+// and the per-slot row moves.  Plain constants, structs and inline functions; internal to libhbk_core.so.
+#ifndef HBK_CSRC_HASH_COMMON_H_
+#define HBK_CSRC_HASH_COMMON_H_
+
+#include "common.h"
+
+namespace hbk {
+
+constexpr long long kEmptyKey = (long long)0x8000000000000000ull;   // INT64_MIN: the slot was never taken
+constexpr long long kTombstoneKey = kEmptyKey + 1;                   // expiring tables only: the sweep took the slot back
+
+__host__ __device__ inline uint32_t rotl32(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
+
+// murmur3_hash32<int64, seed 0> (hybridbackend/common/murmur3.cu.h:32-77): two 4-byte blocks, no tail, len = 8.
+// THE placement hash: home slab = murmur3_i64(key) % slab_count for the probe, both translate kernels and the
+// rehash, and the mix behind the initial rows and the sketch cells.  hbk_murmur3_hash32 returns this function,
+// so the tests that pin that entry to the reference's header pin every placement.
+__host__ __device__ inline uint32_t murmur3_i64(int64_t key) {
+  const uint32_t c1 = 0xcc9e2d51u, c2 = 0x1b873593u;
+  uint32_t h1 = 0;
+  const uint32_t blocks[2] = {(uint32_t)((uint64_t)key & 0xffffffffu), (uint32_t)((uint64_t)key >> 32)};
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    uint32_t k1 = blocks[i];
+    k1 *= c1;
+    k1 = rotl32(k1, 15);
+    k1 *= c2;
+    h1 ^= k1;
+    h1 = rotl32(h1, 13);
+    h1 = h1 * 5 + 0xe6546b64u;
+  }
+  h1 ^= 8u;
+  h1 ^= h1 >> 16;
+  h1 *= 0x85ebca6bu;
+  h1 ^= h1 >> 13;
+  h1 *= 0xc2b2ae35u;
+  h1 ^= h1 >> 16;
+  return h1;
+}
+
+// the slot holds a key: not EMPTY, and not TOMBSTONE in a table that has tombstones
+__host__ __device__ inline bool holds_key(long long key, bool expiring) {
+  return key != kEmptyKey && !(expiring && key == kTombstoneKey);
+}
+
+// smallest x with 2^x >= n, at most `cap`: the lanes of the group that owns a slab (slab_size <= 64 was checked)
+// or moves a row (cap 6: a wave at the most)
+inline int32_t pow2_log2(int32_t n, int32_t cap = 30) {
+  int32_t x = 0;
+  while (x < cap && (1 << x) < n) ++x;
+  return x;
+}
+
+// Wave compaction: lane r < popcount(mask) receives the lane number of the r-th flagged lane; the other lanes
+// take what is left, so the permute is a bijection of the wave.  mask = __ballot(flagged); every lane calls.
+__device__ inline int compact_lanes(unsigned long long mask, bool flagged, int lane) {
+  const int below = rank_below(mask);
+  const int dest = flagged ? below : (int)__builtin_popcountll(mask) + lane - below;
+  return __builtin_amdgcn_ds_permute(dest << 2, lane);
+}
+
+// One per-slot array that travels with the keys (hbk_hash_move_t as the kernels take it).  Rows travel as 4-byte
+// words, bit for bit; a move whose two bases, two pitches and width are all multiples of 16 bytes is copied with
+// 16-byte accesses.
+struct Move {
+  const uint32_t* src;
+  uint32_t* dst;
+  int64_t src_pitch;    // words between rows
+  int64_t dst_pitch;
+  int32_t words;
+  int16_t vec16;        // != 0: bases, pitches and words are multiples of 16 bytes
+  int16_t lanes_log2;   // lanes per row of a pass: pow2(accesses per row), at most 64
+};
+
+// one row: `words` 4-byte words by the `step` lanes of a group (sub = the lane's place in it); the padding up
+// to the pitch is not written
+__device__ inline void copy_row(const Move& mv, const uint32_t* s, uint32_t* d, int sub, int step) {
+  if (mv.vec16 != 0) {
+    const uint4* s4 = reinterpret_cast<const uint4*>(s);
+    uint4* d4 = reinterpret_cast<uint4*>(d);
+    for (int j = sub; j < (mv.words >> 2); j += step) d4[j] = s4[j];
+    return;
+  }
+  for (int j = sub; j < mv.words; j += step) d[j] = s[j];
+}
+
+// the checks of a column's moves: HBK_OK or HBK_INVALID_ARGUMENT
+inline int check_moves(const char* who, int32_t c, int32_t n_moves, const hbk_hash_move_t* moves) {
+  HBK_REQUIRE(n_moves >= 0 && n_moves <= HBK_HASH_MAX_MOVES, "%s: column %d: n_moves must be in [0, %d], got %d", who,
+              c, HBK_HASH_MAX_MOVES, n_moves);
+  for (int32_t m = 0; m < n_moves; ++m) {
+    const hbk_hash_move_t& mv = moves[m];
+    HBK_REQUIRE(mv.words >= 1, "%s: column %d: move %d: words must be >= 1, got %d", who, c, m, mv.words);
+    HBK_REQUIRE(mv.src_pitch == 0 || mv.src_pitch >= mv.words,
+                "%s: column %d: move %d: src_pitch %d is smaller than words %d", who, c, m, mv.src_pitch, mv.words);
+    HBK_REQUIRE(mv.dst_pitch == 0 || mv.dst_pitch >= mv.words,
+                "%s: column %d: move %d: dst_pitch %d is smaller than words %d", who, c, m, mv.dst_pitch, mv.words);
+    HBK_REQUIRE(mv.src != nullptr && mv.dst != nullptr, "%s: column %d: move %d: NULL src or dst", who, c, m);
+    HBK_REQUIRE((((uintptr_t)mv.src | (uintptr_t)mv.dst) & 3) == 0,
+                "%s: column %d: move %d: src and dst must be 4-byte aligned", who, c, m);
+    HBK_REQUIRE(mv.src != mv.dst, "%s: column %d: move %d: src and dst are the same array", who, c, m);
+  }
+  return HBK_OK;
+}
+
+// checked moves as the kernels take them
+inline void describe_moves(int32_t n_moves, const hbk_hash_move_t* moves, Move* out) {
+  for (int32_t m = 0; m < n_moves; ++m) {
+    const hbk_hash_move_t& mv = moves[m];
+    Move& o = out[m];
+    o.src = static_cast<const uint32_t*>(mv.src);
+    o.dst = static_cast<uint32_t*>(mv.dst);
+    o.src_pitch = mv.src_pitch > 0 ? mv.src_pitch : mv.words;
+    o.dst_pitch = mv.dst_pitch > 0 ? mv.dst_pitch : mv.words;
+    o.words = mv.words;
+    o.vec16 = (((uintptr_t)mv.src | (uintptr_t)mv.dst) & 15) == 0 &&
+              ((o.src_pitch | o.dst_pitch | (int64_t)mv.words) & 3) == 0;
+    o.lanes_log2 = (int16_t)pow2_log2(o.vec16 != 0 ? mv.words >> 2 : mv.words, 6);
+  }
+}
+
+// The checks of a table's geometry.  `prefix` goes before the field names in the messages ("", "src_", "dst_").
+// check_slabs: slab size and slab count alone, for the entries with a rule of their own for the key array.
+inline int check_slabs(const char* who, int32_t c, const char* prefix, int64_t slab_count, int32_t slab_size) {
+  HBK_REQUIRE(slab_size >= 1 && slab_size <= kWave, "%s: column %d: %sslab_size must be in [1, 64], got %d", who, c,
+              prefix, slab_size);
+  HBK_REQUIRE(slab_count >= 1, "%s: column %d: %sslab_count must be >= 1, got %lld", who, c, prefix,
+              (long long)slab_count);
+  HBK_REQUIRE(slab_count <= ((1ll << 62) / kWave), "%s: column %d: %sslab_count %lld is out of range", who, c, prefix,
+              (long long)slab_count);
+  return HBK_OK;
+}
+// ... and the key array, under the name the entry's struct gives it ("keys", "keys_cache")
+inline int check_geometry(const char* who, int32_t c, const char* prefix, const char* keys_name, const void* keys,
+                          int64_t slab_count, int32_t slab_size) {
+  if (int rc = check_slabs(who, c, prefix, slab_count, slab_size)) return rc;
+  HBK_REQUIRE(keys != nullptr, "%s: column %d: %s%s is NULL", who, c, prefix, keys_name);
+  HBK_REQUIRE(((uintptr_t)keys & 7) == 0, "%s: column %d: %s%s must be 8-byte aligned", who, c, prefix, keys_name);
+  return HBK_OK;
+}
+
+}  // namespace hbk
+
+#endif  // HBK_CSRC_HASH_COMMON_H_

@@ -12,11 +12,11 @@
 // a kernel boundary makes the stores visible to the next launch.
 //
 // A wave decides 64 consecutive slots with coalesced loads (16 bytes per slot), ballots the evicted ones,
-// gathers their lane numbers into the low lanes with one permute, and fills their companion rows with all
+// gathers their lane numbers into the low lanes with one permute (hash_common.h: compact_lanes), and fills their companion rows with all
 // lanes: 64 / pow2(dim) rows per pass.  n_evicted: one atomic per wave.
 #include <math.h>
 
-#include "common.h"
+#include "hash_common.h"
 
 namespace hbk {
 namespace {
@@ -26,8 +26,6 @@ constexpr int kWavesPerBlock = kBlock / kWave;
 constexpr int kChunks = 4;                              // 64-slot chunks per wave
 constexpr int kSlotsPerBlock = kBlock * kChunks;
 constexpr int kMaxColsPerLaunch = 32;                   // EvictArgs travels by value
-constexpr long long kEmptyKey = (long long)0x8000000000000000ull;
-constexpr long long kTombstoneKey = kEmptyKey + 1;
 
 struct Fill {
   float* base;
@@ -62,9 +60,7 @@ __global__ __launch_bounds__(kBlock) void hash_evict_kernel(const EvictArgs a) {
   const int b = (int)blockIdx.x;
   const int lane = lane_id();
   const int wave = (int)(threadIdx.x >> 6);
-  // last column whose first tile is <= b: one entry per lane, one ballot (hash_insert.hip)
-  const int t0 = lane < a.n_cols ? a.tile_start[lane] : 0x7fffffff;
-  const int ci = __builtin_amdgcn_readfirstlane((int)__builtin_popcountll(__ballot(t0 <= b)) - 1);
+  const int ci = column_of(a.tile_start, a.n_cols, b, lane);
   const EvictCol& c = a.col[ci];
   const int64_t capacity = c.capacity;
   const int64_t ttl = c.steps_to_live;
@@ -83,7 +79,7 @@ __global__ __launch_bounds__(kBlock) void hash_evict_kernel(const EvictArgs a) {
       const long long key = c.keys[slot];
       const int32_t seen = c.last_seen[slot];
       const int32_t freq = c.freq[slot];
-      evict = key != kEmptyKey && key != kTombstoneKey && now - (int64_t)seen >= ttl &&
+      evict = holds_key(key, true) && now - (int64_t)seen >= ttl &&
               (keep_freq == 0 || freq < keep_freq);
     }
     const unsigned long long mask = __ballot(evict);
@@ -96,11 +92,7 @@ __global__ __launch_bounds__(kBlock) void hash_evict_kernel(const EvictArgs a) {
       c.freq[slot] = 0;
     }
     if (c.n_fills == 0) continue;
-    // lane r < n receives the lane number of the r-th evicted slot; the other lanes take what is left,
-    // so the permute is a bijection of the wave
-    const int below = rank_below(mask);
-    const int dest = evict ? below : n + lane - below;
-    const int evicted_lane = __builtin_amdgcn_ds_permute(dest << 2, lane);
+    const int evicted_lane = compact_lanes(mask, evict, lane);   // lane r < n: the lane of the r-th evicted slot
     for (int f = 0; f < c.n_fills; ++f) {
       const Fill& fl = c.fill[f];
       const int rows_log2 = 6 - fl.lanes_log2;                 // rows per pass
@@ -128,14 +120,7 @@ extern "C" int hbk_hash_evict_n(int32_t n_cols, const hbk_hash_evict_column_t* c
   HBK_REQUIRE(n_cols == 0 || cols != nullptr, "%s: cols is NULL", who);
   for (int32_t c = 0; c < n_cols; ++c) {
     const hbk_hash_evict_column_t& h = cols[c];
-    HBK_REQUIRE(h.slab_size >= 1 && h.slab_size <= kWave, "%s: column %d: slab_size must be in [1, 64], got %d",
-                who, c, h.slab_size);
-    HBK_REQUIRE(h.slab_count >= 1, "%s: column %d: slab_count must be >= 1, got %lld", who, c,
-                (long long)h.slab_count);
-    HBK_REQUIRE(h.slab_count <= ((1ll << 62) / kWave), "%s: column %d: slab_count %lld is out of range", who, c,
-                (long long)h.slab_count);
-    HBK_REQUIRE(h.keys_cache != nullptr, "%s: column %d: keys_cache is NULL", who, c);
-    HBK_REQUIRE(((uintptr_t)h.keys_cache & 7) == 0, "%s: column %d: keys_cache must be 8-byte aligned", who, c);
+    if (int rc = check_geometry(who, c, "", "keys_cache", h.keys_cache, h.slab_count, h.slab_size)) return rc;
     HBK_REQUIRE(h.exp.last_seen != nullptr && h.exp.freq != nullptr && h.exp.step != nullptr,
                 "%s: column %d: NULL expiry buffer (last_seen, freq and step are needed)", who, c);
     HBK_REQUIRE(h.steps_to_live >= 0, "%s: column %d: steps_to_live must be >= 0, got %lld", who, c,
@@ -177,8 +162,7 @@ extern "C" int hbk_hash_evict_n(int32_t n_cols, const hbk_hash_evict_column_t* c
         fl.base = h.fills[f].base;
         fl.pitch = h.fills[f].pitch > 0 ? h.fills[f].pitch : h.fills[f].dim;
         fl.dim = h.fills[f].dim;
-        fl.lanes_log2 = 0;
-        while (fl.lanes_log2 < 6 && (1 << fl.lanes_log2) < fl.dim) ++fl.lanes_log2;
+        fl.lanes_log2 = pow2_log2(fl.dim, 6);
         fl.value = h.fills[f].value;
         fl.pad_ = 0;
       }

@@ -12,7 +12,7 @@
 //              total to `count`;
 //   3. write   every tile evaluates the SAME predicate again (nobody may write the table during the call) and
 //              places lane's key at  tile offset + matches of the earlier waves of the tile + rank_below(ballot).
-// The live lanes' numbers are gathered into the low lanes with one ds_permute (hash_evict.hip, hash_rehash.hip)
+// The live lanes' numbers are gathered into the low lanes with one ds_permute (hash_common.h: compact_lanes)
 // and lane groups copy the rows, r-th live slot -> r-th position of the wave's range: a wave's output rows are
 // contiguous.  Nothing is written at positions >= out_capacity; `count` still receives the total.
 //
@@ -24,8 +24,8 @@
 // quiescent during either call, and the kernel boundaries order the three launches of an export.
 //
 // Rows travel as 4-byte words.  A move whose two bases, two pitches and width are all multiples of 16 bytes is
-// copied with 16-byte accesses (hash_rehash.hip's rule); the lane group of a move is pow2(accesses per row).
-#include "common.h"
+// copied with 16-byte accesses (hash_common.h: Move); the lane group of a move is pow2(accesses per row).
+#include "hash_common.h"
 
 namespace hbk {
 namespace {
@@ -35,18 +35,6 @@ constexpr int kWavesPerBlock = kBlock / kWave;
 constexpr int kSlotsPerTile = kBlock;                   // one 64-slot chunk per wave
 constexpr int kScanPerThread = 8;                       // tile counts a thread of the scan takes per pass
 constexpr int kMaxColsPerLaunch = 32;                   // the argument structs travel by value
-constexpr long long kEmptyKey = (long long)0x8000000000000000ull;
-constexpr long long kTombstoneKey = kEmptyKey + 1;
-
-struct Move {
-  const uint32_t* src;
-  uint32_t* dst;
-  int64_t src_pitch;    // words between rows
-  int64_t dst_pitch;
-  int32_t words;
-  int16_t vec16;        // != 0: bases, pitches and words are multiples of 16 bytes
-  int16_t lanes_log2;   // lanes per row of a pass: pow2(accesses per row), at most 64
-};
 
 struct ExportCol {
   const long long* keys;
@@ -88,30 +76,12 @@ struct StoreArgs {
 };
 static_assert(sizeof(StoreArgs) <= 24576, "kernarg budget");
 
-// last column whose first tile is <= b: one entry per lane, one ballot (hash_insert.hip)
-__device__ inline int column_of(const int32_t* tile_start, int n_cols, int b, int lane) {
-  const int t0 = lane < n_cols ? tile_start[lane] : 0x7fffffff;
-  return __builtin_amdgcn_readfirstlane((int)__builtin_popcountll(__ballot(t0 <= b)) - 1);
-}
-
 // the selection: the one predicate of the count and the write launch
 __device__ inline bool exported(const ExportCol& c, int64_t slot) {
   if (slot >= c.capacity) return false;
   const long long key = c.keys[slot];
-  if (key == kEmptyKey || (c.expiring != 0 && key == kTombstoneKey)) return false;
+  if (!holds_key(key, c.expiring != 0)) return false;
   return c.since <= 0 || c.last_seen[slot] >= c.since;
-}
-
-// one row: `words` 4-byte words, by the `1 << lanes_log2` lanes of a group (sub = the lane's place in it)
-__device__ inline void copy_row(const Move& mv, const uint32_t* s, uint32_t* d, int sub) {
-  const int step = 1 << mv.lanes_log2;
-  if (mv.vec16 != 0) {
-    const uint4* s4 = reinterpret_cast<const uint4*>(s);
-    uint4* d4 = reinterpret_cast<uint4*>(d);
-    for (int j = sub; j < (mv.words >> 2); j += step) d4[j] = s4[j];
-    return;
-  }
-  for (int j = sub; j < mv.words; j += step) d[j] = s[j];
 }
 
 __global__ __launch_bounds__(kBlock) void hash_export_count_kernel(const ExportArgs a) {
@@ -203,10 +173,7 @@ __global__ __launch_bounds__(kBlock) void hash_export_write_kernel(const ExportA
     if (c.out_slots != nullptr) c.out_slots[base + below] = slot;
   }
   if (c.n_moves == 0) return;
-  // lane r < n receives the lane number of the r-th live slot; the other lanes take what is left, so the
-  // permute is a bijection of the wave (hash_evict.hip)
-  const int dest = take ? below : n + lane - below;
-  const int live_lane = __builtin_amdgcn_ds_permute(dest << 2, lane);
+  const int live_lane = compact_lanes(mask, take, lane);   // lane r < n: the lane of the r-th live slot
   for (int m = 0; m < c.n_moves; ++m) {
     const Move& mv = c.move[m];
     const int lanes_log2 = mv.lanes_log2;
@@ -215,7 +182,8 @@ __global__ __launch_bounds__(kBlock) void hash_export_write_kernel(const ExportA
       const int r = r0 + (lane >> lanes_log2);
       const int from = __shfl(live_lane, r & (kWave - 1), kWave);   // (every lane takes the shuffle)
       if (r < n && base + r < out_capacity) {
-        copy_row(mv, mv.src + (first + from) * mv.src_pitch, mv.dst + (base + r) * mv.dst_pitch, sub);
+        copy_row(mv, mv.src + (first + from) * mv.src_pitch, mv.dst + (base + r) * mv.dst_pitch, sub,
+                 1 << mv.lanes_log2);
       }
     }
   }
@@ -240,56 +208,8 @@ __global__ __launch_bounds__(kBlock) void hash_store_rows_kernel(const StoreArgs
     for (int r0 = 0; r0 < kWave; r0 += kWave >> lanes_log2) {
       const int r = r0 + (lane >> lanes_log2);
       const int64_t to = (int64_t)__shfl((long long)my_slot, r & (kWave - 1), kWave);   // (every lane takes the shuffle)
-      if (to >= 0) copy_row(mv, mv.src + (first + r) * mv.src_pitch, mv.dst + to * mv.dst_pitch, sub);
+      if (to >= 0) copy_row(mv, mv.src + (first + r) * mv.src_pitch, mv.dst + to * mv.dst_pitch, sub, 1 << mv.lanes_log2);
     }
-  }
-}
-
-// the checks of a table's geometry (hash_rehash.hip: check_geometry)
-int check_geometry(const char* who, int32_t c, const void* keys, int64_t slab_count, int32_t slab_size) {
-  HBK_REQUIRE(slab_size >= 1 && slab_size <= kWave, "%s: column %d: slab_size must be in [1, 64], got %d", who, c,
-              slab_size);
-  HBK_REQUIRE(slab_count >= 1, "%s: column %d: slab_count must be >= 1, got %lld", who, c, (long long)slab_count);
-  HBK_REQUIRE(slab_count <= ((1ll << 62) / kWave), "%s: column %d: slab_count %lld is out of range", who, c,
-              (long long)slab_count);
-  HBK_REQUIRE(keys != nullptr, "%s: column %d: keys is NULL", who, c);
-  HBK_REQUIRE(((uintptr_t)keys & 7) == 0, "%s: column %d: keys must be 8-byte aligned", who, c);
-  return HBK_OK;
-}
-
-// the checks of a column's moves (hash_rehash.hip's)
-int check_moves(const char* who, int32_t c, int32_t n_moves, const hbk_hash_move_t* moves) {
-  HBK_REQUIRE(n_moves >= 0 && n_moves <= HBK_HASH_MAX_MOVES, "%s: column %d: n_moves must be in [0, %d], got %d", who,
-              c, HBK_HASH_MAX_MOVES, n_moves);
-  for (int32_t m = 0; m < n_moves; ++m) {
-    const hbk_hash_move_t& mv = moves[m];
-    HBK_REQUIRE(mv.words >= 1, "%s: column %d: move %d: words must be >= 1, got %d", who, c, m, mv.words);
-    HBK_REQUIRE(mv.src_pitch == 0 || mv.src_pitch >= mv.words,
-                "%s: column %d: move %d: src_pitch %d is smaller than words %d", who, c, m, mv.src_pitch, mv.words);
-    HBK_REQUIRE(mv.dst_pitch == 0 || mv.dst_pitch >= mv.words,
-                "%s: column %d: move %d: dst_pitch %d is smaller than words %d", who, c, m, mv.dst_pitch, mv.words);
-    HBK_REQUIRE(mv.src != nullptr && mv.dst != nullptr, "%s: column %d: move %d: NULL src or dst", who, c, m);
-    HBK_REQUIRE((((uintptr_t)mv.src | (uintptr_t)mv.dst) & 3) == 0,
-                "%s: column %d: move %d: src and dst must be 4-byte aligned", who, c, m);
-    HBK_REQUIRE(mv.src != mv.dst, "%s: column %d: move %d: src and dst are the same array", who, c, m);
-  }
-  return HBK_OK;
-}
-
-void describe_moves(int32_t n_moves, const hbk_hash_move_t* moves, Move* out) {
-  for (int32_t m = 0; m < n_moves; ++m) {
-    const hbk_hash_move_t& mv = moves[m];
-    Move& o = out[m];
-    o.src = static_cast<const uint32_t*>(mv.src);
-    o.dst = static_cast<uint32_t*>(mv.dst);
-    o.src_pitch = mv.src_pitch > 0 ? mv.src_pitch : mv.words;
-    o.dst_pitch = mv.dst_pitch > 0 ? mv.dst_pitch : mv.words;
-    o.words = mv.words;
-    o.vec16 = (((uintptr_t)mv.src | (uintptr_t)mv.dst) & 15) == 0 &&
-              ((o.src_pitch | o.dst_pitch | (int64_t)mv.words) & 3) == 0;
-    const int32_t accesses = o.vec16 != 0 ? mv.words >> 2 : mv.words;
-    o.lanes_log2 = 0;
-    while (o.lanes_log2 < 6 && (1 << o.lanes_log2) < accesses) ++o.lanes_log2;
   }
 }
 
@@ -300,7 +220,7 @@ int check_export(const char* who, int32_t n_cols, const hbk_hash_export_column_t
   HBK_REQUIRE(n_cols == 0 || cols != nullptr, "%s: cols is NULL", who);
   for (int32_t c = 0; c < n_cols; ++c) {
     const hbk_hash_export_column_t& h = cols[c];
-    if (int rc = check_geometry(who, c, h.keys, h.slab_count, h.slab_size)) return rc;
+    if (int rc = check_geometry(who, c, "", "keys", h.keys, h.slab_count, h.slab_size)) return rc;
     if (!outputs) continue;
     HBK_REQUIRE(h.since <= 0 || h.last_seen != nullptr, "%s: column %d: since = %d needs last_seen, which is NULL",
                 who, c, h.since);

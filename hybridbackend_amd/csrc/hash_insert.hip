@@ -81,43 +81,15 @@
 // Everything new is behind `if constexpr (kSeq)`.
 #include <math.h>
 
-#include "common.h"
+#include "hash_common.h"
 
 namespace hbk {
 namespace {
-
-__host__ __device__ inline uint32_t rotl32_(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
-
-// murmur3_hash32<int64, seed 0> as probe.hip (hybridbackend/common/murmur3.cu.h:32-77): the placement
-// must be the probe's, bit for bit (tests compare with hbk_cache_probe and the C oracle)
-__host__ __device__ inline uint32_t murmur3_i64(int64_t key) {
-  const uint32_t c1 = 0xcc9e2d51u, c2 = 0x1b873593u;
-  uint32_t h1 = 0;
-  const uint32_t blocks[2] = {(uint32_t)((uint64_t)key & 0xffffffffu), (uint32_t)((uint64_t)key >> 32)};
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    uint32_t k1 = blocks[i];
-    k1 *= c1;
-    k1 = rotl32_(k1, 15);
-    k1 *= c2;
-    h1 ^= k1;
-    h1 = rotl32_(h1, 13);
-    h1 = h1 * 5 + 0xe6546b64u;
-  }
-  h1 ^= 8u;
-  h1 ^= h1 >> 16;
-  h1 *= 0x85ebca6bu;
-  h1 ^= h1 >> 13;
-  h1 *= 0xc2b2ae35u;
-  h1 ^= h1 >> 16;
-  return h1;
-}
 
 constexpr int kBlock = 256;
 constexpr int kWavesPerBlock = kBlock / kWave;
 constexpr int kMaxColsPerLaunch = 64;   // one ballot finds the column; HashArgs travels by value
 constexpr int kKeys = 8;                // keys per lane group, first reads all in flight (probe.hip)
-constexpr long long kEmptyKey = (long long)0x8000000000000000ull;
 
 struct HashCol {
   long long* cache;
@@ -141,14 +113,6 @@ struct HashArgs {
   HashCol col[kMaxColsPerLaunch];
 };
 static_assert(sizeof(HashArgs) <= 24576, "kernarg budget");
-
-// last column whose first tile is <= b: one entry per lane, one ballot (lookup_fwd.hip)
-__device__ inline int find_column(const HashArgs& a, int b) {
-  const int lane = (int)threadIdx.x & (kWave - 1);
-  const int t0 = lane < a.n_cols ? a.tile_start[lane] : 0x7fffffff;
-  const int ci = (int)__builtin_popcountll(__ballot(t0 <= b)) - 1;
-  return __builtin_amdgcn_readfirstlane(ci);
-}
 
 // Keys that arrive as runs (hbk_hash_translate_runs_n): a column's keys are several arrays, each with its own
 // slots.  The launch is tiled over the RUNS; a run names its column, whose HashCol.keys / slots / n_keys and
@@ -177,7 +141,9 @@ struct RunsArgs : Base {
 template <class Args>
 __device__ inline int find_run(const Args&, int) { return 0; }
 template <class Args>
-__device__ inline int work_column(const Args&, const HashArgs& a, int, int b) { return find_column(a, b); }
+__device__ inline int work_column(const Args&, const HashArgs& a, int, int b) {
+  return column_of(a.tile_start, a.n_cols, b, lane_id());
+}
 template <class Args>
 __device__ inline int work_tile(const Args&, const HashArgs& a, int, int ci, int b) { return b - a.tile_start[ci]; }
 template <class Args>
@@ -187,7 +153,7 @@ __device__ inline int64_t* work_slots(const Args&, const HashCol& c, int) { retu
 template <class Args>
 __device__ inline int64_t work_n_keys(const Args&, const HashCol& c, int) { return c.n_keys; }
 
-// last run whose first tile is <= b: find_column over up to four 64-wide ballots
+// last run whose first tile is <= b: column_of (common.h) over up to four 64-wide ballots
 template <class Base>
 __device__ inline int find_run(const RunsArgs<Base>& r, int b) {
   const int lane = (int)threadIdx.x & (kWave - 1);
@@ -504,8 +470,6 @@ __global__ __launch_bounds__(kBlock) void hash_insert_kernel(const Args args) {
   }
 }
 
-constexpr long long kTombstoneKey = kEmptyKey + 1;   // expiring tables only
-
 struct ExpiryCol {
   int32_t* last_seen;
   int32_t* freq;
@@ -766,12 +730,7 @@ namespace {
 
 // the host checks both entries make of one column: HBK_OK or HBK_INVALID_ARGUMENT
 int check_column(const char* who, int32_t c, const hbk_hash_column_t& h) {
-  HBK_REQUIRE(h.slab_size >= 1 && h.slab_size <= kWave, "%s: column %d: slab_size must be in [1, 64], got %d",
-              who, c, h.slab_size);
-  HBK_REQUIRE(h.slab_count >= 1, "%s: column %d: slab_count must be >= 1, got %lld", who, c,
-              (long long)h.slab_count);
-  HBK_REQUIRE(h.slab_count <= ((1ll << 62) / kWave), "%s: column %d: slab_count %lld is out of range", who, c,
-              (long long)h.slab_count);
+  if (int rc = check_slabs(who, c, "", h.slab_count, h.slab_size)) return rc;
   HBK_REQUIRE(h.n_keys >= 0 && h.n_keys < (1ll << 31), "%s: column %d: n_keys must be in [0, 2^31), got %lld",
               who, c, (long long)h.n_keys);
   HBK_REQUIRE(h.n_keys == 0 || (h.keys_cache != nullptr && h.keys != nullptr && h.slots != nullptr),
@@ -803,8 +762,7 @@ int64_t describe_column(const hbk_hash_column_t& h, int32_t insert, HashCol* out
   d.init_scale = h.init_scale;
   d.slab_size = h.slab_size;
   d.dim = h.dim;
-  d.group_log2 = 0;
-  while ((1 << d.group_log2) < h.slab_size) ++d.group_log2;
+  d.group_log2 = pow2_log2(h.slab_size);
   const int64_t keys_per_block = (int64_t)(kBlock >> d.group_log2) * kKeys;
   return (h.n_keys + keys_per_block - 1) / keys_per_block;
 }

@@ -5,10 +5,10 @@
 //
 // Source sweep (hash_evict.hip's): a wave reads 64 consecutive source slots with coalesced plain loads --
 // nobody writes the source during the call -- ballots the slots that hold a key (not EMPTY; not TOMBSTONE when
-// `expiring` is set), gathers their lane numbers into the low lanes with rank_below and one ds_permute, and
+// `expiring` is set), gathers their lane numbers into the low lanes (hash_common.h: compact_lanes), and
 // lane groups of G = pow2(dst_slab_size) lanes take the live keys in turn, 64 / G per pass.
 //
-// Placement (hash_insert.hip's plain rule, bit for bit): home slab = murmur3_hash32(key) % dst_slab_count, the
+// Placement (hash_insert.hip's plain rule; the hash is hash_common.h's): home slab = murmur3_i64(key) % dst_slab_count, the
 // key takes the slab's FIRST EMPTY slot by a 64-bit agent-scope CAS, a full slab sends it to the next slab,
 // wrapping.  The destination never holds a tombstone, so one rule serves both table kinds, and every key is
 // found afterwards by hbk_cache_probe and by both translate kernels.  Source keys are distinct, so there is no
@@ -22,64 +22,20 @@
 // Bounded loops: slots only go EMPTY -> key, so at most dst_slab_size lost CASes per slab (`tries`) and at most
 // dst_slab_count slabs per key (`probed`), both written out; nothing spins on another workgroup.
 //
-// Rows travel as 4-byte words, bit for bit.  A move whose two bases, two pitches and width are all multiples
-// of 16 bytes is copied with 16-byte accesses.  HBK_REHASH_VEC16=0 builds the 4-byte form alone, for the A/B of
-// tools/bench_hash_rehash.py --ab-lib: 494 against 676 us for growth, 517 against 728 us for compaction on 26
-// tables x 131 072 slots with five moves (profiles/hash_rehash.txt, "rehash_kernel" against
-// "rehash_kernel_ab_lib"), hence 1.
+// Rows travel as 4-byte words, bit for bit (hash_common.h: Move, copy_row).  A move whose two bases, two pitches
+// and width are all multiples of 16 bytes is copied with 16-byte accesses.
 //
 // One 64-slot chunk per wave, 64 / G keys per pass, one dependent load -> CAS -> copy chain per key: the launch
 // reaches 1.7 TB/s of its byte model, a fifth of the HBM rate (same profile).  It is latency, hidden only by
 // occupancy; several keys in flight per lane group, as hash_insert.hip's kKeys, is the open improvement.
-#include "common.h"
-
-#ifndef HBK_REHASH_VEC16
-#define HBK_REHASH_VEC16 1
-#endif
+#include "hash_common.h"
 
 namespace hbk {
 namespace {
 
-__host__ __device__ inline uint32_t rotl32_(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
-
-// murmur3_hash32<int64, seed 0> as probe.hip and hash_insert.hip: the placement must be theirs, bit for bit
-__host__ __device__ inline uint32_t murmur3_i64(int64_t key) {
-  const uint32_t c1 = 0xcc9e2d51u, c2 = 0x1b873593u;
-  uint32_t h1 = 0;
-  const uint32_t blocks[2] = {(uint32_t)((uint64_t)key & 0xffffffffu), (uint32_t)((uint64_t)key >> 32)};
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    uint32_t k1 = blocks[i];
-    k1 *= c1;
-    k1 = rotl32_(k1, 15);
-    k1 *= c2;
-    h1 ^= k1;
-    h1 = rotl32_(h1, 13);
-    h1 = h1 * 5 + 0xe6546b64u;
-  }
-  h1 ^= 8u;
-  h1 ^= h1 >> 16;
-  h1 *= 0x85ebca6bu;
-  h1 ^= h1 >> 13;
-  h1 *= 0xc2b2ae35u;
-  h1 ^= h1 >> 16;
-  return h1;
-}
-
 constexpr int kBlock = 256;
 constexpr int kSlotsPerBlock = kBlock;                  // one 64-slot chunk per wave: the placement is the work
 constexpr int kMaxColsPerLaunch = 32;                   // RehashArgs travels by value
-constexpr long long kEmptyKey = (long long)0x8000000000000000ull;
-constexpr long long kTombstoneKey = kEmptyKey + 1;
-
-struct Move {
-  const uint32_t* src;
-  uint32_t* dst;
-  int64_t src_pitch;    // words between rows
-  int64_t dst_pitch;
-  int32_t words;
-  int32_t vec16;        // != 0: bases, pitches and words are multiples of 16 bytes
-};
 
 struct RehashCol {
   const long long* src_keys;
@@ -106,9 +62,7 @@ __global__ __launch_bounds__(kBlock) void hash_rehash_kernel(const RehashArgs a)
   const int b = (int)blockIdx.x;
   const int lane = lane_id();
   const int wave = (int)(threadIdx.x >> 6);
-  // last column whose first tile is <= b: one entry per lane, one ballot (hash_insert.hip)
-  const int t0 = lane < a.n_cols ? a.tile_start[lane] : 0x7fffffff;
-  const int ci = __builtin_amdgcn_readfirstlane((int)__builtin_popcountll(__ballot(t0 <= b)) - 1);
+  const int ci = column_of(a.tile_start, a.n_cols, b, lane);
   const RehashCol& c = a.col[ci];
   const int64_t src_capacity = c.src_capacity;
   const int64_t first = (int64_t)(b - a.tile_start[ci]) * kSlotsPerBlock + (int64_t)wave * kWave;
@@ -117,16 +71,12 @@ __global__ __launch_bounds__(kBlock) void hash_rehash_kernel(const RehashArgs a)
   const bool in_table = slot < src_capacity;
   long long my_key = kEmptyKey;
   if (in_table) my_key = c.src_keys[slot];
-  const bool holds = my_key != kEmptyKey && !(c.expiring != 0 && my_key == kTombstoneKey);
+  const bool holds = holds_key(my_key, c.expiring != 0);
   if (c.new_slots != nullptr && in_table && !holds) c.new_slots[slot] = -1;   // no key there
   const unsigned long long mask = __ballot(holds);
   if (mask == 0ull) return;   // (wave-uniform)
   const int n = (int)__builtin_popcountll(mask);
-  // lane r < n receives the lane number of the r-th live slot; the other lanes take what is left, so the
-  // permute is a bijection of the wave (hash_evict.hip)
-  const int below = rank_below(mask);
-  const int dest = holds ? below : n + lane - below;
-  const int live_lane = __builtin_amdgcn_ds_permute(dest << 2, lane);
+  const int live_lane = compact_lanes(mask, holds, lane);   // lane r < n: the lane of the r-th live slot
 
   const int group_log2 = c.group_log2;
   const int gsize = 1 << group_log2;
@@ -203,17 +153,7 @@ __global__ __launch_bounds__(kBlock) void hash_rehash_kernel(const RehashArgs a)
         // the group that won the slot moves the key's rows; the padding up to the pitch is not written
         for (int m = 0; m < c.n_moves; ++m) {
           const Move& mv = c.move[m];
-          const uint32_t* s = mv.src + src_slot * mv.src_pitch;
-          uint32_t* d = mv.dst + result * mv.dst_pitch;
-#if HBK_REHASH_VEC16
-          if (mv.vec16 != 0) {
-            const uint4* s4 = reinterpret_cast<const uint4*>(s);
-            uint4* d4 = reinterpret_cast<uint4*>(d);
-            for (int j = sub; j < (mv.words >> 2); j += gsize) d4[j] = s4[j];
-            continue;
-          }
-#endif
-          for (int j = sub; j < mv.words; j += gsize) d[j] = s[j];
+          copy_row(mv, mv.src + src_slot * mv.src_pitch, mv.dst + result * mv.dst_pitch, sub, gsize);
         }
       }
       if (sub == 0) {
@@ -235,20 +175,6 @@ __global__ __launch_bounds__(kBlock) void hash_rehash_kernel(const RehashArgs a)
   }
 }
 
-// the checks of one side's geometry (hash_insert.hip: check_column)
-int check_geometry(const char* who, int32_t c, const char* side, const void* keys, int64_t slab_count,
-                   int32_t slab_size) {
-  HBK_REQUIRE(slab_size >= 1 && slab_size <= kWave, "%s: column %d: %s_slab_size must be in [1, 64], got %d", who, c,
-              side, slab_size);
-  HBK_REQUIRE(slab_count >= 1, "%s: column %d: %s_slab_count must be >= 1, got %lld", who, c, side,
-              (long long)slab_count);
-  HBK_REQUIRE(slab_count <= ((1ll << 62) / kWave), "%s: column %d: %s_slab_count %lld is out of range", who, c, side,
-              (long long)slab_count);
-  HBK_REQUIRE(keys != nullptr, "%s: column %d: %s_keys is NULL", who, c, side);
-  HBK_REQUIRE(((uintptr_t)keys & 7) == 0, "%s: column %d: %s_keys must be 8-byte aligned", who, c, side);
-  return HBK_OK;
-}
-
 }  // namespace
 }  // namespace hbk
 
@@ -259,24 +185,11 @@ extern "C" int hbk_hash_rehash_n(int32_t n_cols, const hbk_hash_rehash_column_t*
   HBK_REQUIRE(n_cols == 0 || cols != nullptr, "%s: cols is NULL", who);
   for (int32_t c = 0; c < n_cols; ++c) {
     const hbk_hash_rehash_column_t& h = cols[c];
-    if (int rc = check_geometry(who, c, "src", h.src_keys, h.src_slab_count, h.src_slab_size)) return rc;
-    if (int rc = check_geometry(who, c, "dst", h.dst_keys, h.dst_slab_count, h.dst_slab_size)) return rc;
+    if (int rc = check_geometry(who, c, "src_", "keys", h.src_keys, h.src_slab_count, h.src_slab_size)) return rc;
+    if (int rc = check_geometry(who, c, "dst_", "keys", h.dst_keys, h.dst_slab_count, h.dst_slab_size)) return rc;
     HBK_REQUIRE(h.src_keys != h.dst_keys, "%s: column %d: src_keys and dst_keys are the same array (a rehash is "
                 "never in place)", who, c);
-    HBK_REQUIRE(h.n_moves >= 0 && h.n_moves <= HBK_HASH_MAX_MOVES, "%s: column %d: n_moves must be in [0, %d], got %d",
-                who, c, HBK_HASH_MAX_MOVES, h.n_moves);
-    for (int32_t m = 0; m < h.n_moves; ++m) {
-      const hbk_hash_move_t& mv = h.moves[m];
-      HBK_REQUIRE(mv.words >= 1, "%s: column %d: move %d: words must be >= 1, got %d", who, c, m, mv.words);
-      HBK_REQUIRE(mv.src_pitch == 0 || mv.src_pitch >= mv.words,
-                  "%s: column %d: move %d: src_pitch %d is smaller than words %d", who, c, m, mv.src_pitch, mv.words);
-      HBK_REQUIRE(mv.dst_pitch == 0 || mv.dst_pitch >= mv.words,
-                  "%s: column %d: move %d: dst_pitch %d is smaller than words %d", who, c, m, mv.dst_pitch, mv.words);
-      HBK_REQUIRE(mv.src != nullptr && mv.dst != nullptr, "%s: column %d: move %d: NULL src or dst", who, c, m);
-      HBK_REQUIRE((((uintptr_t)mv.src | (uintptr_t)mv.dst) & 3) == 0,
-                  "%s: column %d: move %d: src and dst must be 4-byte aligned", who, c, m);
-      HBK_REQUIRE(mv.src != mv.dst, "%s: column %d: move %d: src and dst are the same array", who, c, m);
-    }
+    if (int rc = check_moves(who, c, h.n_moves, h.moves)) return rc;
   }
   int32_t c0 = 0;
   while (c0 < n_cols) {
@@ -295,21 +208,10 @@ extern "C" int hbk_hash_rehash_n(int32_t n_cols, const hbk_hash_rehash_column_t*
       d.dst_div = make_fastdiv((uint64_t)h.dst_slab_count);
       d.dst_div.d = (uint64_t)h.dst_slab_count;
       d.dst_slab_size = h.dst_slab_size;
-      d.group_log2 = 0;
-      while ((1 << d.group_log2) < h.dst_slab_size) ++d.group_log2;
+      d.group_log2 = pow2_log2(h.dst_slab_size);
       d.expiring = h.expiring;
       d.n_moves = h.n_moves;
-      for (int32_t m = 0; m < h.n_moves; ++m) {
-        const hbk_hash_move_t& mv = h.moves[m];
-        Move& o = d.move[m];
-        o.src = static_cast<const uint32_t*>(mv.src);
-        o.dst = static_cast<uint32_t*>(mv.dst);
-        o.src_pitch = mv.src_pitch > 0 ? mv.src_pitch : mv.words;
-        o.dst_pitch = mv.dst_pitch > 0 ? mv.dst_pitch : mv.words;
-        o.words = mv.words;
-        o.vec16 = (((uintptr_t)mv.src | (uintptr_t)mv.dst) & 15) == 0 &&
-                  ((o.src_pitch | o.dst_pitch | (int64_t)mv.words) & 3) == 0;
-      }
+      describe_moves(h.n_moves, h.moves, d.move);
       tiles += (d.src_capacity + kSlotsPerBlock - 1) / kSlotsPerBlock;
       HBK_REQUIRE(tiles < (1ll << 31), "%s: grid too large", who);
       ++k;

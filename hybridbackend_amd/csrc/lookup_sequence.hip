@@ -114,20 +114,12 @@ __device__ inline uint64_t seq_position(const SeqCol& c, int64_t p, bool valid) 
   return row;
 }
 
-// last column whose first tile is <= b: one entry per lane, one ballot (lookup_fwd.hip)
-__device__ inline int find_column(const SeqArgs& a, int b) {
-  const int lane = (int)threadIdx.x & (kWave - 1);
-  const int t0 = lane < a.n_cols ? a.tile_start[lane] : 0x7fffffff;
-  const int ci = (int)__builtin_popcountll(__ballot(t0 <= b)) - 1;
-  return __builtin_amdgcn_readfirstlane(ci);
-}
-
 // kU * rpi consecutive positions per wave: slot q lives in register q >> 6 of lane q & 63
 template <typename V, bool CLIP>
 __global__ __launch_bounds__(kBlock) void sequence_lookup_fwd_kernel(const SeqArgs a) {
   constexpr int VE = sizeof(V) / 4;
   const int b = (int)blockIdx.x;
-  const int ci = find_column(a, b);
+  const int ci = column_of(a.tile_start, a.n_cols, b, lane_id());
   const SeqCol& c = a.col[ci];
   const int lane = lane_id();
   const int wave = (int)(threadIdx.x >> 6);
@@ -178,7 +170,7 @@ __global__ __launch_bounds__(kBlock) void sequence_lookup_fwd_kernel(const SeqAr
 // the grid and the lengths alone: one thread per position
 __global__ __launch_bounds__(kBlock) void sequence_row_grid_kernel(const SeqArgs a) {
   const int b = (int)blockIdx.x;
-  const int ci = find_column(a, b);
+  const int ci = column_of(a.tile_start, a.n_cols, b, lane_id());
   const SeqCol& c = a.col[ci];
   const int64_t p = (int64_t)(b - a.tile_start[ci]) * kBlock + (int64_t)threadIdx.x;
   seq_position(c, p, p < c.n_pos);

@@ -9,48 +9,18 @@
 // slab per step (slot = lane in group, coalesced 8*slab_size bytes); match / empty are found
 // with one 64-bit ballot masked to the group, so a wave64 probes 64/G keys concurrently
 // instead of one (the reference serialises its 32 keys through one slab read at a time).
-#include "common.h"
+#include "hash_common.h"
 
 namespace hbk {
-
-__host__ __device__ inline uint32_t rotl32(uint32_t x, int r) {
-  return (x << r) | (x >> (32 - r));
-}
-
-// murmur3_hash32<int64, seed 0>: two 4-byte blocks, no tail, len = 8.
-__host__ __device__ inline uint32_t murmur3_hash32_i64(int64_t key) {
-  const uint32_t c1 = 0xcc9e2d51u, c2 = 0x1b873593u;
-  uint32_t h1 = 0;
-  uint32_t blocks[2] = {(uint32_t)((uint64_t)key & 0xffffffffu),
-                        (uint32_t)((uint64_t)key >> 32)};
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    uint32_t k1 = blocks[i];
-    k1 *= c1;
-    k1 = rotl32(k1, 15);
-    k1 *= c2;
-    h1 ^= k1;
-    h1 = rotl32(h1, 13);
-    h1 = h1 * 5 + 0xe6546b64u;
-  }
-  h1 ^= 8u;
-  h1 ^= h1 >> 16;
-  h1 *= 0x85ebca6bu;
-  h1 ^= h1 >> 13;
-  h1 *= 0xc2b2ae35u;
-  h1 ^= h1 >> 16;
-  return h1;
-}
 
 namespace {
 
 constexpr int kBlock = 256;
-constexpr long long kEmptyKey = (long long)0x8000000000000000ull;
 
 __global__ __launch_bounds__(kBlock) void murmur3_kernel(const int64_t* keys, int64_t n,
                                                          uint32_t* out) {
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (i < n) out[i] = murmur3_hash32_i64(keys[i]);
+  if (i < n) out[i] = murmur3_i64(keys[i]);
 }
 
 // A group of pow2(slab_size) lanes owns a key and reads one slab per probe; a wave takes kProbeKeys
@@ -85,7 +55,7 @@ __global__ __launch_bounds__(kBlock) void cache_probe_kernel(
 #pragma unroll
   for (int u = 0; u < kProbeKeys; ++u) {
     const int64_t i = i0 + (int64_t)u * groups_per_wave;
-    slab[u] = (int64_t)fastmod((uint64_t)murmur3_hash32_i64(key[u]), slab_div);
+    slab[u] = (int64_t)fastmod((uint64_t)murmur3_i64(key[u]), slab_div);
     read_key[u] = 0;
     if (i < n_keys && in_slab) read_key[u] = keys_cache[slab[u] * slab_size + sub];
   }
@@ -294,8 +264,7 @@ extern "C" int hbk_cache_probe(const int64_t* keys_cache, int64_t slab_count,
   }
   if (n_keys == 0) return HBK_OK;
   HBK_REQUIRE(keys_cache && keys && hit_slot, "cache_probe: NULL buffer");
-  int group_log2 = 0;
-  while ((1 << group_log2) < slab_size) ++group_log2;
+  const int group_log2 = pow2_log2(slab_size);
   const int64_t keys_per_block = (int64_t)(kBlock >> group_log2) * kProbeKeys;
   const int64_t blocks = (n_keys + keys_per_block - 1) / keys_per_block;
   FastDiv sd = make_fastdiv((uint64_t)slab_count);

@@ -25,7 +25,10 @@ from hybridbackend_amd import _lib
 from hybridbackend_amd.embedding.cache import EMPTY_KEY
 from hybridbackend_amd.embedding.hashtable import TOMBSTONE_KEY
 from hybridbackend_amd.embedding.hashtable import _Plan
+from hybridbackend_amd.embedding.hashtable import check_bound
+from hybridbackend_amd.embedding.hashtable import check_current
 from hybridbackend_amd.embedding.hashtable import check_ids
+from hybridbackend_amd.embedding.hashtable import grow_tables
 from hybridbackend_amd.embedding.hashtable import same_device
 from hybridbackend_amd.embedding.lookup import GroupLookup
 from hybridbackend_amd.embedding.lookup import max_norm_list
@@ -203,17 +206,7 @@ class HashSequenceLookup:
     """:meth:`HashTable.maybe_grow` on every table (``slots[c]``: the companions of table c), then
     :meth:`rebind` if any table was rehashed.  Returns the per-table results: None, or the new companion
     tensors."""
-    slots = [()] * len(self.hash_tables) if slots is None else list(slots)
-    if len(slots) != len(self.hash_tables):
-      raise _bad(f'expected {len(self.hash_tables)} lists of companion tensors, got {len(slots)}')
-    out = [t.maybe_grow(max_load, factor, slots[c]) for c, t in enumerate(self.hash_tables)]
-    if any(o is not None for o in out):
-      self.rebind()
-    return out
-
-  def _current(self):
-    if any(t.table is not r for t, r in zip(self.hash_tables, self.tables)):
-      raise _bad('a table was rehashed: rebind() first')
+    return grow_tables(self, self.hash_tables, max_load, factor, slots)
 
   def __len__(self):
     return len(self.hash_tables)
@@ -228,7 +221,7 @@ class HashSequenceLookup:
     ``(outs, lengths)``: per column fp32 ``[B, T_c, dim_c]`` (or the caller's contiguous ``outs[c]`` of that
     shape) and int32 ``[B]`` ``min(len, T_c)``."""
     ids = list(ids)
-    self._current()
+    check_current(self.hash_tables, self.tables)
     n = len(self.hash_tables)
     # the grids of the call before serve again while the shapes stay (a resident loop; a captured launch()
     # needs them to stay where they are)
@@ -272,7 +265,5 @@ class HashSequenceLookup:
   def launch(self, stream=None):
     """Both launches of the LAST call again on its tensors (ids and row_splits refilled in place; captured
     graphs): two foreign calls (three with filtered tables of both kinds), no allocation."""
-    if not self._bound:
-      raise _lib.HbkError(_lib.INTERNAL, 'launch() needs a call that bound the tensors first')
-    self._current()
+    check_bound(self, self.hash_tables, self.tables)
     self._launch(stream)

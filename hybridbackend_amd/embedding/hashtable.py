@@ -56,6 +56,33 @@ def _bad(msg):
   return _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT, msg)
 
 
+def _per_table(n, *named):
+  """Per-table argument lists: ``(name, value, default)`` each -- None becomes ``n`` defaults, anything else a list;
+  all of them must then hold exactly ``n`` entries.  Returns the lists in order."""
+  lists = [[default] * n if value is None else list(value) for _, value, default in named]
+  if any(len(x) != n for x in lists):
+    def listed(words):
+      words = [str(w) for w in words]
+      return words[0] if len(words) == 1 else ', '.join(words[:-1]) + ' and ' + words[-1]
+    raise _bad(f'expected {n} {listed(name for name, _, _ in named)}, got {listed(len(x) for x in lists)}')
+  return lists
+
+
+def _check_geometry(capacity, slab_size, where=''):
+  if not 1 <= slab_size <= 64:
+    raise _bad(f'{where}slab_size must be in [1, 64], got {slab_size}')
+  if capacity < slab_size:
+    raise _bad(f'{where}capacity {capacity} is below one slab of {slab_size} slots')
+
+
+def _read_counters(tables):
+  """``(inserted, failed, evicted, reused)`` of every table -- 0 evicted and reused for one that is not expiring --
+  from ONE host read for all of them."""
+  parts = [x for t in tables for x in ((t.counts, t.stats) if t.expiring else (t.counts,))]
+  words = iter((parts[0] if len(parts) == 1 else torch.cat(parts)).tolist())
+  return [(next(words), next(words)) + ((next(words), next(words)) if t.expiring else (0, 0)) for t in tables]
+
+
 class HashTable:
   """A fixed-capacity table keyed by raw int64 ids.
 
@@ -95,10 +122,7 @@ class HashTable:
   def __init__(self, capacity, dim, device, slab_size=8, init_scale=1e-3, seed=0, expiring=False, min_freq=0,
                sketch_depth=4, sketch_width=None, sketch_seed=0):
     slab_size, capacity, dim = int(slab_size), int(capacity), int(dim)
-    if not 1 <= slab_size <= 64:
-      raise _bad(f'slab_size must be in [1, 64], got {slab_size}')
-    if capacity < slab_size:
-      raise _bad(f'capacity {capacity} is below one slab of {slab_size} slots')
+    _check_geometry(capacity, slab_size)
     if dim < 1:
       raise _bad(f'dim must be >= 1, got {dim}')
     init_scale = float(init_scale)
@@ -190,11 +214,13 @@ class HashTable:
     n = int(self.counts[0].item())
     return n - int(self.stats[0].item()) if self.expiring else n
 
+  def _counters(self):
+    """``(inserted, failed, evicted, reused)`` in ONE host read."""
+    return _read_counters([self])[0]
+
   def _live_count(self):
     """:meth:`size` in ONE host read."""
-    if not self.expiring:
-      return int(self.counts[0].item())
-    inserted, _, evicted, _ = torch.cat([self.counts, self.stats]).tolist()
+    inserted, _, evicted, _ = self._counters()
     return inserted - evicted
 
   def failed(self):
@@ -357,10 +383,7 @@ class HashTable:
       raise _bad(f'max_load must be in (0, 1], got {max_load!r}')
     if not (math.isfinite(factor) and factor > 1.0):
       raise _bad(f'factor must be finite and > 1, got {factor!r}')
-    if self.expiring:
-      inserted, _, evicted, reused = torch.cat([self.counts, self.stats]).tolist()
-    else:
-      (inserted, _), evicted, reused = self.counts.tolist(), 0, 0
+    inserted, _, evicted, reused = self._counters()
     occupied, live = inserted - reused, inserted - evicted
     if occupied <= max_load * self.capacity:
       return None
@@ -568,10 +591,7 @@ def hash_export(tables, sinces=None, slots=None):
   tables = list(tables)
   same_device(tables)
   n = len(tables)
-  sinces = [None] * n if sinces is None else list(sinces)
-  slots = [()] * n if slots is None else list(slots)
-  if not len(sinces) == len(slots) == n:
-    raise _bad(f'expected {n} since values and lists of companion tensors, got {len(sinces)} and {len(slots)}')
+  sinces, slots = _per_table(n, ('since values', sinces, None), ('lists of companion tensors', slots, ()))
   if n == 0:
     _lib.check(_lib.lib().hbk_hash_export_n(0, None, None, None))
     return []
@@ -587,13 +607,13 @@ def hash_export(tables, sinces=None, slots=None):
     _lib.require_device_tensor(t.keys, 'keys')
   dev = tables[0].keys.device
   # the live keys of every table in one host read
-  counters = torch.cat([torch.cat([t.counts, t.stats]) if t.expiring else
-                        torch.cat([t.counts, t.counts.new_zeros(2)]) for t in tables]).tolist()
+  counters = _read_counters(tables)
   cols = (_lib.HashExportColumn * n)()
   counts = torch.zeros(n, dtype=torch.int64, device=dev)
   outs = []
   for c, t in enumerate(tables):
-    live = counters[4 * c] - counters[4 * c + 2]
+    inserted, _, evicted, _ = counters[c]
+    live = inserted - evicted
     cap = min(max(live, 0), t.capacity)
     rows = max(cap, 1)   # (never an empty allocation: a move needs an address)
     out = {'keys': torch.empty(rows, dtype=torch.int64, device=dev),
@@ -670,12 +690,8 @@ def hash_rehash(tables, capacities=None, slab_sizes=None, slots=None):
   tables = list(tables)
   same_device(tables)
   n = len(tables)
-  capacities = [None] * n if capacities is None else list(capacities)
-  slab_sizes = [None] * n if slab_sizes is None else list(slab_sizes)
-  slots = [()] * n if slots is None else list(slots)
-  if not len(capacities) == len(slab_sizes) == len(slots) == n:
-    raise _bad(f'expected {n} capacities, slab sizes and lists of companion tensors, got {len(capacities)}, '
-               f'{len(slab_sizes)} and {len(slots)}')
+  capacities, slab_sizes, slots = _per_table(n, ('capacities', capacities, None), ('slab sizes', slab_sizes, None),
+                                             ('lists of companion tensors', slots, ()))
   if len(set(id(t) for t in tables)) != n:
     raise _bad('a table is named twice')
   if n == 0:
@@ -685,10 +701,7 @@ def hash_rehash(tables, capacities=None, slab_sizes=None, slots=None):
   for c, t in enumerate(tables):
     slab_size = t.slab_size if slab_sizes[c] is None else int(slab_sizes[c])
     capacity = t.capacity if capacities[c] is None else int(capacities[c])
-    if not 1 <= slab_size <= 64:
-      raise _bad(f'table {c}: slab_size must be in [1, 64], got {slab_size}')
-    if capacity < slab_size:
-      raise _bad(f'table {c}: capacity {capacity} is below one slab of {slab_size} slots')
+    _check_geometry(capacity, slab_size, f'table {c}: ')
     geometry.append((capacity // slab_size, slab_size))
     checked.append(_companions(t, slots[c]))
   for c, t in enumerate(tables):
@@ -718,11 +731,7 @@ def hash_rehash(tables, capacities=None, slab_sizes=None, slots=None):
     col.expiring = 1 if t.expiring else 0
     col.n_moves = len(moves)
     for m, (src, dst) in enumerate(moves):
-      mv = col.moves[m]
-      mv.src, mv.dst = src.data_ptr(), dst.data_ptr()
-      mv.words = 1 if src.dim() == 1 else src.shape[1]
-      mv.src_pitch = 1 if src.dim() == 1 else src.stride(0)
-      mv.dst_pitch = 0
+      _describe_move(col.moves[m], per_slot=src, packed=dst, to_packed=True)
     col.new_slots = None
     # a fresh counter pair: {0, the failures so far}; the kernel adds the keys it moved.  It is swapped in with
     # the other new arrays, so a refused launch leaves the table and its counters as they were
@@ -755,9 +764,7 @@ def _evict_columns(tables, steps_to_live, keep_freq, slots):
   steps_to_live, keep_freq = int(steps_to_live), int(keep_freq)
   if steps_to_live < 0 or keep_freq < 0:
     raise _bad(f'steps_to_live and keep_freq must be >= 0, got {steps_to_live} and {keep_freq}')
-  slots = [()] * len(tables) if slots is None else list(slots)
-  if len(slots) != len(tables):
-    raise _bad(f'expected {len(tables)} lists of companion tensors, got {len(slots)}')
+  slots, = _per_table(len(tables), ('lists of companion tensors', slots, ()))
   for t in tables:
     t._need_expiring('evict')
   checked = [_companions(t, slots[c]) for c, t in enumerate(tables)]
@@ -902,6 +909,28 @@ def same_device(tables):
                  f'{tables[0].keys.device}')
 
 
+def check_current(tables, rows):
+  """Refuses when ``rows``, the ``table`` tensors an object was built over, are no longer the tables' own."""
+  if any(t.table is not r for t, r in zip(tables, rows)):
+    raise _bad('a table was rehashed: rebind() first')
+
+
+def check_bound(lookup, tables, rows):
+  """The guard of a ``launch()``: a call bound the tensors, and no table was rehashed since."""
+  if not lookup._bound:   # pylint: disable=protected-access
+    raise _lib.HbkError(_lib.INTERNAL, 'launch() needs a call that bound the tensors first')
+  check_current(tables, rows)
+
+
+def grow_tables(lookup, tables, max_load, factor, slots):
+  """:meth:`HashTable.maybe_grow` on every table, then ``lookup.rebind()`` if any was rehashed."""
+  slots, = _per_table(len(tables), ('lists of companion tensors', slots, ()))
+  out = [t.maybe_grow(max_load, factor, slots[c]) for c, t in enumerate(tables)]
+  if any(o is not None for o in out):
+    lookup.rebind()
+  return out
+
+
 class HashGroupLookup:
   """N hash-keyed columns: one translate launch, then a :class:`GroupLookup` over ``[t.table ...]`` with
   buckets 0 on the row numbers.
@@ -941,17 +970,7 @@ class HashGroupLookup:
     """:meth:`HashTable.maybe_grow` on every table (``slots[c]``: the companions of table c), then
     :meth:`rebind` if any table was rehashed.  Returns the per-table results: None, or the new companion
     tensors.  See :meth:`rebind` for what must be rebuilt afterwards."""
-    slots = [()] * len(self.tables) if slots is None else list(slots)
-    if len(slots) != len(self.tables):
-      raise _bad(f'expected {len(self.tables)} lists of companion tensors, got {len(slots)}')
-    out = [t.maybe_grow(max_load, factor, slots[c]) for c, t in enumerate(self.tables)]
-    if any(o is not None for o in out):
-      self.rebind()
-    return out
-
-  def _current(self):
-    if any(t.table is not r for t, r in zip(self.tables, self._rows)):
-      raise _bad('a table was rehashed: rebind() first')
+    return grow_tables(self, self.tables, max_load, factor, slots)
 
   def __len__(self):
     return len(self.tables)
@@ -959,7 +978,7 @@ class HashGroupLookup:
   def __call__(self, ids, row_splits=None, outs=None, sp_weights=None):
     """ids[c]: int64 raw ids, row_splits[c]: int32 ``[segments + 1]`` or None.  Returns GroupLookup's outputs."""
     ids = list(ids)
-    self._current()
+    check_current(self.tables, self._rows)
     # the slot buffers of the call before serve again while the id counts stay (a resident loop; a
     # captured launch() needs them to stay where they are)
     keep = self.slots
@@ -974,9 +993,7 @@ class HashGroupLookup:
   def launch(self, stream=None):
     """Both launches of the LAST call again on its tensors (id buffers refilled in place; captured graphs):
     two foreign calls, no allocation."""
-    if not self._bound:
-      raise _lib.HbkError(_lib.INTERNAL, 'launch() needs a call that bound the tensors first')
-    self._current()
+    check_bound(self, self.tables, self._rows)
     dev = self.tables[0].keys.device if self.tables else None
     s = _lib.current_stream(dev) if stream is None else C.c_void_p(stream.cuda_stream)
     self._plan.launch(self.train, s)

@@ -50,8 +50,7 @@ class ShardedHashGroupLookup(ShardedGroupLookup):
                      ftrl_slots=ftrl_slots, ftrl=ftrl, max_norms=max_norms)
 
   def _current(self):
-    if any(t.table is not r for t, r in zip(self.tables, self._rows)):
-      raise _ht._bad('a table was rehashed: rebind() first')   # pylint: disable=protected-access
+    _ht.check_current(self.tables, self._rows)
 
   def _plan(self):
     self._current()

@@ -11,8 +11,8 @@ of tools/bench_hash_expiry.py: 26 expiring tables x 131 072 slots, dim 16, slab_
                 ones and evicted after them): rehash_call / rehash_kernel against compact(slots=...) per table
   translate     the resident translate (every key of the batch resident) of tables that never held a tombstone,
                 of the tombstoned tables, and of those after the device-side rehash
-  --ab-lib      a second build of the library (make OUT=... OBJDIR=... EXTRA=-DHBK_REHASH_VEC16=0): the entry alone,
-                the two builds taking turns on the same descriptors
+  --ab-lib      a second build of the library (make OUT=... OBJDIR=..., of another commit or with other flags): the
+                entry alone, the two builds taking turns on the same descriptors
 
 Every timed region is one operation between its own HIP events, the tables restored before it; `--rounds`
 rounds with the forms taking turns; medians with min / max.  Bytes per launch: 8 B per source slot, per live key
