@@ -134,6 +134,13 @@ class HashEvictColumn(C.Structure):
               ('n_fills', C.c_int32), ('fills', HashFill * HASH_MAX_FILLS)]
 
 
+class HashEvictToColumn(C.Structure):
+  """hbk_hash_evict_to_column_t"""
+  _fields_ = [('keys_cache', C.c_void_p), ('slab_count', C.c_int64), ('slab_size', C.c_int32),
+              ('exp', HashExpiry), ('max_size', C.c_int64), ('keep_freq', C.c_int32),
+              ('n_fills', C.c_int32), ('fills', HashFill * HASH_MAX_FILLS), ('report', C.c_void_p)]
+
+
 HASH_MAX_MOVES = 8
 
 
@@ -242,6 +249,8 @@ def _declare(l):
     'hbk_hash_insert_n': (C.c_int, [i32, vp, i32, vp]),
     'hbk_hash_insert_expiring_n': (C.c_int, [i32, vp, vp, i32, vp]),
     'hbk_hash_evict_n': (C.c_int, [i32, vp, vp]),
+    'hbk_hash_evict_to_workspace_bytes': (sz, [i32]),
+    'hbk_hash_evict_to_n': (C.c_int, [i32, vp, vp, sz, vp]),
     'hbk_hash_insert_admit_n': (C.c_int, [i32, vp, vp, i32, vp]),
     'hbk_hash_insert_expiring_admit_n': (C.c_int, [i32, vp, vp, vp, i32, vp]),
     'hbk_hash_rehash_n': (C.c_int, [i32, vp, vp]),

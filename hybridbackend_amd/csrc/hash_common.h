@@ -1,9 +1,11 @@
 // The hash tables' contract, once: what probe.hip, hash_insert.hip, hash_evict.hip, hash_rehash.hip and
 // hash_export.hip must agree on to read each other's tables -- the sentinels, the placement hash, which slots
-// hold a key, the host checks of a table's geometry -- and the pieces their sweeps share: the wave compaction
-// and the per-slot row moves.  Plain constants, structs and inline functions; internal to libhbk_core.so.
+// hold a key, the host checks of a table's geometry -- and the pieces their sweeps share: the wave compaction,
+// the eviction sweep's body and fills, and the per-slot row moves.  Plain constants, structs and inline functions; internal to libhbk_core.so.
 #ifndef HBK_CSRC_HASH_COMMON_H_
 #define HBK_CSRC_HASH_COMMON_H_
+
+#include <math.h>
 
 #include "common.h"
 
@@ -60,6 +62,88 @@ __device__ inline int compact_lanes(unsigned long long mask, bool flagged, int l
   const int below = rank_below(mask);
   const int dest = flagged ? below : (int)__builtin_popcountll(mask) + lane - below;
   return __builtin_amdgcn_ds_permute(dest << 2, lane);
+}
+
+// One companion array of a sweep (hbk_hash_fill_t as the kernels take it): the rows of the evicted slots are
+// filled with `value`; the padding between dim and pitch is not written.
+struct Fill {
+  float* base;
+  int64_t pitch;        // floats between rows
+  int32_t dim;
+  int32_t lanes_log2;   // lanes per row of a pass: pow2(dim), at most 64
+  float value;
+  int32_t pad_;
+};
+
+// The sweeps' body (hash_evict.hip, hash_evict_to.hip): a wave decides the 64 consecutive slots from `first`
+// (wave-uniform, < capacity) with coalesced loads, 16 bytes per slot -- doomed(key, last_seen, freq) is the
+// sweep's predicate -- ballots the evicted ones, writes key = TOMBSTONE, last_seen = freq = 0, gathers their lane
+// numbers into the low lanes with one permute and fills their companion rows with all lanes: 64 / pow2(dim)
+// rows per pass.  Returns the slots evicted (wave-uniform); every lane of the wave calls.
+template <class Doomed>
+__device__ inline int sweep_wave(long long* keys, int32_t* last_seen, int32_t* freqs, int64_t capacity, int64_t first,
+                                 int lane, int n_fills, const Fill* fills, Doomed doomed) {
+  const int64_t slot = first + lane;
+  bool evict = false;
+  if (slot < capacity) {
+    const long long key = keys[slot];
+    const int32_t seen = last_seen[slot];
+    const int32_t freq = freqs[slot];
+    evict = doomed(key, seen, freq);
+  }
+  const unsigned long long mask = __ballot(evict);
+  if (mask == 0ull) return 0;   // (wave-uniform)
+  const int n = (int)__builtin_popcountll(mask);
+  if (evict) {
+    keys[slot] = kTombstoneKey;
+    last_seen[slot] = 0;
+    freqs[slot] = 0;
+  }
+  if (n_fills == 0) return n;
+  const int evicted_lane = compact_lanes(mask, evict, lane);   // lane r < n: the lane of the r-th evicted slot
+  for (int f = 0; f < n_fills; ++f) {
+    const Fill& fl = fills[f];
+    const int rows_log2 = 6 - fl.lanes_log2;                 // rows per pass
+    const int j0 = lane & ((1 << fl.lanes_log2) - 1);
+    for (int r0 = 0; r0 < n; r0 += 1 << rows_log2) {
+      const int r = r0 + (lane >> fl.lanes_log2);
+      const int src = __shfl(evicted_lane, r & (kWave - 1), kWave);   // (every lane takes the shuffle)
+      if (r < n) {
+        float* row = fl.base + (first + src) * fl.pitch;
+        for (int j = j0; j < fl.dim; j += 1 << fl.lanes_log2) row[j] = fl.value;
+      }
+    }
+  }
+  return n;
+}
+
+// the checks of a column's fills: HBK_OK or HBK_INVALID_ARGUMENT
+inline int check_fills(const char* who, int32_t c, int32_t n_fills, const hbk_hash_fill_t* fills) {
+  HBK_REQUIRE(n_fills >= 0 && n_fills <= HBK_HASH_MAX_FILLS, "%s: column %d: n_fills must be in [0, %d], got %d", who,
+              c, HBK_HASH_MAX_FILLS, n_fills);
+  for (int32_t f = 0; f < n_fills; ++f) {
+    const hbk_hash_fill_t& fl = fills[f];
+    HBK_REQUIRE(fl.base != nullptr, "%s: column %d: fill %d: base is NULL", who, c, f);
+    HBK_REQUIRE(fl.dim >= 1, "%s: column %d: fill %d: dim must be >= 1, got %d", who, c, f, fl.dim);
+    HBK_REQUIRE(fl.pitch == 0 || fl.pitch >= fl.dim, "%s: column %d: fill %d: pitch %d is smaller than dim %d", who,
+                c, f, fl.pitch, fl.dim);
+    HBK_REQUIRE(isfinite(fl.value), "%s: column %d: fill %d: value must be finite, got %g", who, c, f,
+                (double)fl.value);
+  }
+  return HBK_OK;
+}
+
+// checked fills as the kernels take them
+inline void describe_fills(int32_t n_fills, const hbk_hash_fill_t* fills, Fill* out) {
+  for (int32_t f = 0; f < n_fills; ++f) {
+    Fill& fl = out[f];
+    fl.base = fills[f].base;
+    fl.pitch = fills[f].pitch > 0 ? fills[f].pitch : fills[f].dim;
+    fl.dim = fills[f].dim;
+    fl.lanes_log2 = pow2_log2(fl.dim, 6);
+    fl.value = fills[f].value;
+    fl.pad_ = 0;
+  }
 }
 
 // One per-slot array that travels with the keys (hbk_hash_move_t as the kernels take it).  Rows travel as 4-byte

@@ -12,10 +12,9 @@
 // a kernel boundary makes the stores visible to the next launch.
 //
 // A wave decides 64 consecutive slots with coalesced loads (16 bytes per slot), ballots the evicted ones,
-// gathers their lane numbers into the low lanes with one permute (hash_common.h: compact_lanes), and fills their companion rows with all
-// lanes: 64 / pow2(dim) rows per pass.  n_evicted: one atomic per wave.
-#include <math.h>
-
+// gathers their lane numbers into the low lanes with one permute, and fills their companion rows with all
+// lanes: 64 / pow2(dim) rows per pass (hash_common.h: sweep_wave, the body hash_evict_to.hip's sweep shares).
+// n_evicted: one atomic per wave.
 #include "hash_common.h"
 
 namespace hbk {
@@ -26,15 +25,6 @@ constexpr int kWavesPerBlock = kBlock / kWave;
 constexpr int kChunks = 4;                              // 64-slot chunks per wave
 constexpr int kSlotsPerBlock = kBlock * kChunks;
 constexpr int kMaxColsPerLaunch = 32;                   // EvictArgs travels by value
-
-struct Fill {
-  float* base;
-  int64_t pitch;        // floats between rows
-  int32_t dim;
-  int32_t lanes_log2;   // lanes per row of a pass: pow2(dim), at most 64
-  float value;
-  int32_t pad_;
-};
 
 struct EvictCol {
   long long* keys;
@@ -73,39 +63,11 @@ __global__ __launch_bounds__(kBlock) void hash_evict_kernel(const EvictArgs a) {
   for (int u = 0; u < kChunks; ++u) {
     const int64_t first = block_first + (int64_t)(u * kWavesPerBlock + wave) * kWave;
     if (first >= capacity) break;   // (wave-uniform)
-    const int64_t slot = first + lane;
-    bool evict = false;
-    if (slot < capacity) {
-      const long long key = c.keys[slot];
-      const int32_t seen = c.last_seen[slot];
-      const int32_t freq = c.freq[slot];
-      evict = holds_key(key, true) && now - (int64_t)seen >= ttl &&
-              (keep_freq == 0 || freq < keep_freq);
-    }
-    const unsigned long long mask = __ballot(evict);
-    if (mask == 0ull) continue;   // (wave-uniform)
-    const int n = (int)__builtin_popcountll(mask);
-    n_evicted += n;
-    if (evict) {
-      c.keys[slot] = kTombstoneKey;
-      c.last_seen[slot] = 0;
-      c.freq[slot] = 0;
-    }
-    if (c.n_fills == 0) continue;
-    const int evicted_lane = compact_lanes(mask, evict, lane);   // lane r < n: the lane of the r-th evicted slot
-    for (int f = 0; f < c.n_fills; ++f) {
-      const Fill& fl = c.fill[f];
-      const int rows_log2 = 6 - fl.lanes_log2;                 // rows per pass
-      const int j0 = lane & ((1 << fl.lanes_log2) - 1);
-      for (int r0 = 0; r0 < n; r0 += 1 << rows_log2) {
-        const int r = r0 + (lane >> fl.lanes_log2);
-        const int src = __shfl(evicted_lane, r & (kWave - 1), kWave);   // (every lane takes the shuffle)
-        if (r < n) {
-          float* row = fl.base + (first + src) * fl.pitch;
-          for (int j = j0; j < fl.dim; j += 1 << fl.lanes_log2) row[j] = fl.value;
-        }
-      }
-    }
+    n_evicted += sweep_wave(c.keys, c.last_seen, c.freq, capacity, first, lane, c.n_fills, c.fill,
+                            [&](long long key, int32_t seen, int32_t freq) {
+                              return holds_key(key, true) && now - (int64_t)seen >= ttl &&
+                                     (keep_freq == 0 || freq < keep_freq);
+                            });
   }
   if (c.stats != nullptr && lane == 0 && n_evicted != 0) atomicAdd(c.stats, n_evicted);
 }
@@ -126,17 +88,7 @@ extern "C" int hbk_hash_evict_n(int32_t n_cols, const hbk_hash_evict_column_t* c
     HBK_REQUIRE(h.steps_to_live >= 0, "%s: column %d: steps_to_live must be >= 0, got %lld", who, c,
                 (long long)h.steps_to_live);
     HBK_REQUIRE(h.keep_freq >= 0, "%s: column %d: keep_freq must be >= 0, got %d", who, c, h.keep_freq);
-    HBK_REQUIRE(h.n_fills >= 0 && h.n_fills <= HBK_HASH_MAX_FILLS, "%s: column %d: n_fills must be in [0, %d], got %d",
-                who, c, HBK_HASH_MAX_FILLS, h.n_fills);
-    for (int32_t f = 0; f < h.n_fills; ++f) {
-      const hbk_hash_fill_t& fl = h.fills[f];
-      HBK_REQUIRE(fl.base != nullptr, "%s: column %d: fill %d: base is NULL", who, c, f);
-      HBK_REQUIRE(fl.dim >= 1, "%s: column %d: fill %d: dim must be >= 1, got %d", who, c, f, fl.dim);
-      HBK_REQUIRE(fl.pitch == 0 || fl.pitch >= fl.dim, "%s: column %d: fill %d: pitch %d is smaller than dim %d",
-                  who, c, f, fl.pitch, fl.dim);
-      HBK_REQUIRE(isfinite(fl.value), "%s: column %d: fill %d: value must be finite, got %g", who, c, f,
-                  (double)fl.value);
-    }
+    if (int rc = check_fills(who, c, h.n_fills, h.fills)) return rc;
   }
   int32_t c0 = 0;
   while (c0 < n_cols) {
@@ -157,15 +109,7 @@ extern "C" int hbk_hash_evict_n(int32_t n_cols, const hbk_hash_evict_column_t* c
       d.steps_to_live = h.steps_to_live;
       d.keep_freq = h.keep_freq;
       d.n_fills = h.n_fills;
-      for (int32_t f = 0; f < h.n_fills; ++f) {
-        Fill& fl = d.fill[f];
-        fl.base = h.fills[f].base;
-        fl.pitch = h.fills[f].pitch > 0 ? h.fills[f].pitch : h.fills[f].dim;
-        fl.dim = h.fills[f].dim;
-        fl.lanes_log2 = pow2_log2(fl.dim, 6);
-        fl.value = h.fills[f].value;
-        fl.pad_ = 0;
-      }
+      describe_fills(h.n_fills, h.fills, d.fill);
       tiles += (d.capacity + kSlotsPerBlock - 1) / kSlotsPerBlock;
       HBK_REQUIRE(tiles < (1ll << 31), "%s: grid too large", who);
       ++k;

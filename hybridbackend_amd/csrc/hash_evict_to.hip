@@ -1,0 +1,326 @@
+// Bounded hash tables (hbk_hash_evict_to_n): evict the oldest keys of N expiring tables down to a size bound,
+// the threshold found on the device.  include/hbk.h has the semantics: need = live - max_size, cut = the smallest
+// last_seen value (signed) at or below which at least `need` evictable slots lie, and every evictable slot with
+// last_seen <= cut leaves -- whole steps together, no tie-break.
+//
+// The selection is a radix select over u = last_seen ^ 0x80000000 (signed order as unsigned), most significant
+// digit first, 11 / 11 / 10 bits.  Per digit two kernels, for up to 32 tables per launch:
+//   hist  a streaming pass tiled over the slots of all tables as the sweep tiles them: a wave reads 64 consecutive
+//         slots with coalesced loads (16 bytes per slot) and counts, in a per-workgroup LDS histogram of 2048 bins,
+//         the evictable slots whose higher digits equal the prefix chosen so far (read from the table's state).
+//         Real last_seen values are small and close together: in the high digits every lane of every wave hits
+//         ONE bin.  So the wave's lanes that share the leading lane's bin are found with one ballot and added
+//         once, as their popcount; only the lanes left over add one by one.  The non-zero bins are then added to
+//         the table's histogram with integer atomics: an order-independent sum.  The first pass also counts the
+//         live slots.
+//   pick  one workgroup per table scans the 2048 bins, finds the bin the remaining need falls into, extends the
+//         prefix, writes the need that remains inside that bin, and zeroes the bins for the next pass.
+// Then the sweep (hash_common.h: sweep_wave, hash_evict.hip's body) with the predicate "evictable and u <= cut",
+// need and cut read from the state.  Every pass after the first leaves at once for a table with need <= 0 or
+// whose evictable slots all go.
+//
+// State per table in the workspace, int32 words: kState words, then the 2048 bins.  The entry clears it on the
+// stream, so a captured call replays.  No host read anywhere.
+#include "hash_common.h"
+
+namespace hbk {
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kWavesPerBlock = kBlock / kWave;
+constexpr int kChunks = 4;                              // 64-slot chunks per wave
+constexpr int kSlotsPerBlock = kBlock * kChunks;
+constexpr int kMaxColsPerLaunch = 32;                   // the argument structs travel by value
+constexpr int kBins = 2048;                             // 11 bits: 8 KB of LDS
+constexpr int kBinsPerThread = kBins / kBlock;
+
+// the state words of a table
+constexpr int kLive = 0;      // live slots (hist pass 0)
+constexpr int kNeed = 1;      // live - max_size (pick 0); <= 0: the table is left alone
+constexpr int kRemain = 2;    // the need that falls into the chosen bin
+constexpr int kPrefix = 3;    // the digits chosen so far, right-aligned
+constexpr int kAll = 4;       // != 0: fewer evictable slots than need, all of them go (cut = INT32_MAX)
+constexpr int kCut = 5;       // the cut as u = last_seen ^ 0x80000000 (pick 2, or pick 0 with kAll)
+constexpr int kState = 8;
+constexpr int kWordsPerTable = kState + kBins;
+
+__host__ __device__ constexpr int digit_shift(int digit) { return digit == 0 ? 21 : digit == 1 ? 10 : 0; }
+__host__ __device__ constexpr int digit_bits(int digit) { return digit == 2 ? 10 : 11; }
+
+__device__ inline uint32_t order_key(int32_t seen) { return (uint32_t)seen ^ 0x80000000u; }
+
+struct ToCol {
+  long long* keys;
+  int32_t* last_seen;
+  int32_t* freq;
+  int32_t* stats;         // {n_evicted, n_reused} or NULL
+  int32_t* report;        // {live_before, need, cut, n_evicted} or NULL
+  int32_t* state;         // kWordsPerTable words of the workspace
+  int64_t capacity;
+  int64_t max_size;
+  int32_t keep_freq;
+  int32_t n_fills;
+};
+
+struct HistArgs {
+  int32_t n_cols;
+  int32_t tile_start[kMaxColsPerLaunch + 1];
+  ToCol col[kMaxColsPerLaunch];
+};
+
+struct SweepArgs {
+  int32_t n_cols;
+  int32_t tile_start[kMaxColsPerLaunch + 1];
+  ToCol col[kMaxColsPerLaunch];
+  Fill fill[kMaxColsPerLaunch][HBK_HASH_MAX_FILLS];
+};
+static_assert(sizeof(SweepArgs) <= 24576, "kernarg budget");
+
+// the table's state says there is nothing (more) to select
+__device__ inline bool settled(const int32_t* state) { return state[kNeed] <= 0 || state[kAll] != 0; }
+
+template <int DIGIT>
+__global__ __launch_bounds__(kBlock) void hash_evict_to_hist_kernel(const HistArgs a) {
+  __shared__ int32_t bins[kBins];
+  const int b = (int)blockIdx.x;
+  const int lane = lane_id();
+  const int wave = (int)(threadIdx.x >> 6);
+  const int ci = column_of(a.tile_start, a.n_cols, b, lane);
+  const ToCol& c = a.col[ci];
+  uint32_t prefix = 0;
+  if (DIGIT > 0) {
+    if (settled(c.state)) return;   // (workgroup-uniform)
+    prefix = (uint32_t)c.state[kPrefix];
+  }
+  for (int i = (int)threadIdx.x; i < kBins; i += kBlock) bins[i] = 0;
+  __syncthreads();
+  const int64_t capacity = c.capacity;
+  const int32_t keep_freq = c.keep_freq;
+  const int64_t block_first = (int64_t)(b - a.tile_start[ci]) * kSlotsPerBlock;
+  int32_t n_live = 0;
+#pragma unroll
+  for (int u = 0; u < kChunks; ++u) {
+    const int64_t first = block_first + (int64_t)(u * kWavesPerBlock + wave) * kWave;
+    if (first >= capacity) break;   // (wave-uniform)
+    const int64_t slot = first + lane;
+    bool live = false, counted = false;
+    int bin = 0;
+    if (slot < capacity) {
+      const long long key = c.keys[slot];
+      const int32_t seen = c.last_seen[slot];
+      const int32_t freq = c.freq[slot];
+      live = holds_key(key, true);
+      const uint32_t k = order_key(seen);
+      counted = live && (keep_freq == 0 || freq < keep_freq);
+      if (DIGIT > 0) counted = counted && (k >> (digit_shift(DIGIT) + digit_bits(DIGIT))) == prefix;
+      bin = (int)((k >> digit_shift(DIGIT)) & ((1u << digit_bits(DIGIT)) - 1u));
+    }
+    if (DIGIT == 0) n_live += (int)__builtin_popcountll(__ballot(live));
+    const unsigned long long mask = __ballot(counted);
+    if (mask == 0ull) continue;   // (wave-uniform)
+    // the lanes that share the leading lane's bin: one add of their number
+    const int leader = (int)__builtin_ctzll(mask);
+    const int lead_bin = __shfl(bin, leader, kWave);
+    const unsigned long long same = __ballot(counted && bin == lead_bin);
+    if (lane == leader) atomicAdd(&bins[lead_bin], (int32_t)__builtin_popcountll(same));
+    if (counted && bin != lead_bin) atomicAdd(&bins[bin], 1);
+  }
+  if (DIGIT == 0 && lane == 0 && n_live != 0) atomicAdd(&c.state[kLive], n_live);
+  __syncthreads();
+  int32_t* hist = c.state + kState;
+  for (int i = (int)threadIdx.x; i < kBins; i += kBlock) {
+    const int32_t v = bins[i];
+    if (v != 0) atomicAdd(&hist[i], v);
+  }
+}
+
+struct PickArgs {
+  ToCol col[kMaxColsPerLaunch];
+};
+
+// One workgroup per table.  Thread t owns the bins [8 t, 8 t + 8); a scan over the threads' sums finds the one
+// thread whose bins the remaining need falls into.
+template <int DIGIT>
+__global__ __launch_bounds__(kBlock) void hash_evict_to_pick_kernel(const PickArgs a) {
+  __shared__ int32_t sums[kBlock];
+  const ToCol& c = a.col[blockIdx.x];
+  int32_t* state = c.state;
+  int32_t* hist = state + kState;
+  const int t = (int)threadIdx.x;
+  int32_t need;
+  if (DIGIT == 0) {
+    const int32_t live = state[kLive];
+    const int64_t wanted = (int64_t)live - c.max_size;   // (live < 2^31, max_size >= 0: fits an int32 once clamped)
+    need = wanted < -0x7fffffffll ? -0x7fffffff : (int32_t)wanted;
+    if (t == 0) {
+      state[kNeed] = need;
+      if (c.report != nullptr) {
+        c.report[0] = live;
+        c.report[1] = need;
+        c.report[2] = 0;
+        c.report[3] = 0;
+      }
+    }
+  } else {
+    if (settled(state)) return;   // (workgroup-uniform; the bins were not written by the pass before)
+    need = state[kRemain];
+  }
+  int32_t v[kBinsPerThread];
+  int32_t sum = 0;
+#pragma unroll
+  for (int j = 0; j < kBinsPerThread; ++j) {
+    v[j] = hist[t * kBinsPerThread + j];
+    hist[t * kBinsPerThread + j] = 0;   // for the next digit's pass
+    sum += v[j];
+  }
+  if (DIGIT == 0 && need <= 0) return;   // (workgroup-uniform)
+  sums[t] = sum;
+  __syncthreads();
+  for (int d = 1; d < kBlock; d <<= 1) {   // inclusive scan
+    const int32_t x = t >= d ? sums[t - d] : 0;
+    __syncthreads();
+    sums[t] += x;
+    __syncthreads();
+  }
+  const int32_t upto = sums[t], before = upto - sum;
+  if (DIGIT == 0 && sums[kBlock - 1] < need) {   // (workgroup-uniform) not enough evictable slots: all of them go
+    if (t == 0) {
+      state[kAll] = 1;
+      state[kCut] = (int32_t)0xffffffffu;
+      if (c.report != nullptr) c.report[2] = 0x7fffffff;
+    }
+    return;
+  }
+  // (digits 1 and 2: the chosen bin of the digit before holds at least `need` slots, so one thread matches)
+  if (before < need && need <= upto) {
+    int32_t run = before;
+    int j = 0;
+    while (run + v[j] < need) run += v[j++];
+    const uint32_t prefix = ((DIGIT == 0 ? 0u : (uint32_t)state[kPrefix]) << digit_bits(DIGIT)) |
+                            (uint32_t)(t * kBinsPerThread + j);
+    state[kPrefix] = (int32_t)prefix;
+    state[kRemain] = need - run;
+    if (DIGIT == 2) {
+      state[kCut] = (int32_t)prefix;
+      if (c.report != nullptr) c.report[2] = (int32_t)(prefix ^ 0x80000000u);
+    }
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void hash_evict_to_sweep_kernel(const SweepArgs a) {
+  const int b = (int)blockIdx.x;
+  const int lane = lane_id();
+  const int wave = (int)(threadIdx.x >> 6);
+  const int ci = column_of(a.tile_start, a.n_cols, b, lane);
+  const ToCol& c = a.col[ci];
+  if (c.state[kNeed] <= 0) return;   // inside the bound: nothing is written
+  const uint32_t cut = (uint32_t)c.state[kCut];
+  const int64_t capacity = c.capacity;
+  const int32_t keep_freq = c.keep_freq;
+  const int64_t block_first = (int64_t)(b - a.tile_start[ci]) * kSlotsPerBlock;
+  int32_t n_evicted = 0;
+#pragma unroll
+  for (int u = 0; u < kChunks; ++u) {
+    const int64_t first = block_first + (int64_t)(u * kWavesPerBlock + wave) * kWave;
+    if (first >= capacity) break;   // (wave-uniform)
+    n_evicted += sweep_wave(c.keys, c.last_seen, c.freq, capacity, first, lane, c.n_fills, a.fill[ci],
+                            [&](long long key, int32_t seen, int32_t freq) {
+                              return holds_key(key, true) && (keep_freq == 0 || freq < keep_freq) &&
+                                     order_key(seen) <= cut;
+                            });
+  }
+  if (lane == 0 && n_evicted != 0) {
+    if (c.stats != nullptr) atomicAdd(c.stats, n_evicted);
+    if (c.report != nullptr) atomicAdd(c.report + 3, n_evicted);
+  }
+}
+
+// the call's first launch: every table's state and bins start at zero (a kernel, not a memset: it is captured
+// into a graph as what it is)
+__global__ __launch_bounds__(kBlock) void hash_evict_to_clear_kernel(int32_t* words, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) words[i] = 0;
+}
+
+template <int DIGIT>
+int launch_digit(const HistArgs& hist, const PickArgs& pick, int64_t tiles, hipStream_t stream) {
+  hipLaunchKernelGGL(hash_evict_to_hist_kernel<DIGIT>, dim3((unsigned)tiles), dim3(kBlock), 0, stream, hist);
+  HBK_HIP_OK(hipGetLastError());
+  hipLaunchKernelGGL(hash_evict_to_pick_kernel<DIGIT>, dim3((unsigned)hist.n_cols), dim3(kBlock), 0, stream, pick);
+  HBK_HIP_OK(hipGetLastError());
+  return HBK_OK;
+}
+
+}  // namespace
+}  // namespace hbk
+
+extern "C" size_t hbk_hash_evict_to_workspace_bytes(int32_t n_cols) {
+  return n_cols <= 0 ? 0 : (size_t)n_cols * hbk::kWordsPerTable * sizeof(int32_t);
+}
+
+extern "C" int hbk_hash_evict_to_n(int32_t n_cols, const hbk_hash_evict_to_column_t* cols, void* workspace,
+                                   size_t workspace_bytes, hbk_stream_t stream) {
+  using namespace hbk;
+  const char* who = "hash_evict_to_n";
+  HBK_REQUIRE(n_cols >= 0, "%s: n_cols must be >= 0, got %d", who, n_cols);
+  HBK_REQUIRE(n_cols == 0 || cols != nullptr, "%s: cols is NULL", who);
+  for (int32_t c = 0; c < n_cols; ++c) {
+    const hbk_hash_evict_to_column_t& h = cols[c];
+    if (int rc = check_geometry(who, c, "", "keys_cache", h.keys_cache, h.slab_count, h.slab_size)) return rc;
+    HBK_REQUIRE(h.slab_count * h.slab_size < (1ll << 31),
+                "%s: column %d: slab_count * slab_size = %lld slots, must be below 2^31 (the counters are int32)", who,
+                c, (long long)(h.slab_count * h.slab_size));
+    HBK_REQUIRE(h.exp.last_seen != nullptr, "%s: column %d: last_seen is NULL", who, c);
+    HBK_REQUIRE(h.exp.freq != nullptr, "%s: column %d: freq is NULL", who, c);
+    HBK_REQUIRE(h.max_size >= 0, "%s: column %d: max_size must be >= 0, got %lld", who, c, (long long)h.max_size);
+    HBK_REQUIRE(h.keep_freq >= 0, "%s: column %d: keep_freq must be >= 0, got %d", who, c, h.keep_freq);
+    if (int rc = check_fills(who, c, h.n_fills, h.fills)) return rc;
+  }
+  if (n_cols == 0) return HBK_OK;
+  const size_t needed = hbk_hash_evict_to_workspace_bytes(n_cols);
+  HBK_REQUIRE(workspace != nullptr, "%s: workspace is NULL (%zu bytes are needed)", who, needed);
+  HBK_REQUIRE(((uintptr_t)workspace & 3) == 0, "%s: workspace must be 4-byte aligned", who);
+  HBK_REQUIRE(workspace_bytes >= needed, "%s: workspace of %zu bytes is too small: %zu are needed", who,
+              workspace_bytes, needed);
+  hipStream_t s = as_stream(stream);
+  int32_t* words = static_cast<int32_t*>(workspace);
+  const int64_t n_words = (int64_t)n_cols * kWordsPerTable;
+  const int64_t clear_blocks = (n_words + kBlock - 1) / kBlock;
+  hipLaunchKernelGGL(hash_evict_to_clear_kernel, dim3((unsigned)(clear_blocks < 1024 ? clear_blocks : 1024)),
+                     dim3(kBlock), 0, s, words, n_words);
+  HBK_HIP_OK(hipGetLastError());
+  for (int32_t c0 = 0; c0 < n_cols; c0 += kMaxColsPerLaunch) {
+    SweepArgs sweep;
+    HistArgs hist;
+    PickArgs pick;
+    const int32_t k = n_cols - c0 < kMaxColsPerLaunch ? n_cols - c0 : kMaxColsPerLaunch;
+    int64_t tiles = 0;
+    sweep.tile_start[0] = 0;
+    for (int32_t i = 0; i < k; ++i) {
+      const hbk_hash_evict_to_column_t& h = cols[c0 + i];
+      ToCol& d = sweep.col[i];
+      d.keys = reinterpret_cast<long long*>(h.keys_cache);
+      d.last_seen = h.exp.last_seen;
+      d.freq = h.exp.freq;
+      d.stats = h.exp.stats;
+      d.report = h.report;
+      d.state = words + (int64_t)(c0 + i) * kWordsPerTable;
+      d.capacity = h.slab_count * h.slab_size;
+      d.max_size = h.max_size;
+      d.keep_freq = h.keep_freq;
+      d.n_fills = h.n_fills;
+      describe_fills(h.n_fills, h.fills, sweep.fill[i]);
+      tiles += (d.capacity + kSlotsPerBlock - 1) / kSlotsPerBlock;   // (< 2^21 per table: 32 of them fit a grid)
+      sweep.tile_start[i + 1] = (int32_t)tiles;
+      hist.col[i] = d;
+      pick.col[i] = d;
+    }
+    sweep.n_cols = hist.n_cols = k;
+    for (int32_t i = 0; i <= k; ++i) hist.tile_start[i] = sweep.tile_start[i];
+    if (int rc = launch_digit<0>(hist, pick, tiles, s)) return rc;
+    if (int rc = launch_digit<1>(hist, pick, tiles, s)) return rc;
+    if (int rc = launch_digit<2>(hist, pick, tiles, s)) return rc;
+    hipLaunchKernelGGL(hash_evict_to_sweep_kernel, dim3((unsigned)tiles), dim3(kBlock), 0, s, sweep);
+    HBK_HIP_OK(hipGetLastError());
+  }
+  return HBK_OK;
+}

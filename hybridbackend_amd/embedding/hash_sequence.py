@@ -28,6 +28,7 @@ from hybridbackend_amd.embedding.hashtable import _Plan
 from hybridbackend_amd.embedding.hashtable import check_bound
 from hybridbackend_amd.embedding.hashtable import check_current
 from hybridbackend_amd.embedding.hashtable import check_ids
+from hybridbackend_amd.embedding.hashtable import evict_tables
 from hybridbackend_amd.embedding.hashtable import grow_tables
 from hybridbackend_amd.embedding.hashtable import same_device
 from hybridbackend_amd.embedding.lookup import GroupLookup
@@ -207,6 +208,12 @@ class HashSequenceLookup:
     :meth:`rebind` if any table was rehashed.  Returns the per-table results: None, or the new companion
     tensors."""
     return grow_tables(self, self.hash_tables, max_load, factor, slots)
+
+  def maybe_evict(self, max_load=0.75, target_load=0.5, keep_freq=0, slots=None):
+    """:meth:`HashTable.maybe_evict` on every table (``slots[c]``: the companions of table c), then
+    :meth:`rebind` if any table was rehashed.  Returns the per-table results: None, or the new companion
+    tensors."""
+    return evict_tables(self, self.hash_tables, max_load, target_load, keep_freq, slots)
 
   def __len__(self):
     return len(self.hash_tables)

@@ -27,6 +27,10 @@ host read) whether a table must grow or shed its tombstones.  A rehash changes s
 addresses: :meth:`HashGroupLookup.rebind`, a new ``GroupLookupGrad`` over the new slot tensors, a new capture
 of any captured graph.
 
+Bounded tables (``hbk_hash_evict_to_n``): :meth:`HashTable.evict_to` / :func:`hash_evict_to` evict the oldest keys
+down to a size bound, the cut found on the device (whole steps leave together: no exact size, no tie-break);
+:meth:`HashTable.maybe_evict` / :meth:`HashGroupLookup.maybe_evict` are ``maybe_grow`` for a fixed memory budget.
+
 Sharded hash tables: :class:`hybridbackend_amd.embedding.ShardedHashGroupLookup` (sharded_hash.py) puts tables of
 W ranks behind the sharded lookup step, owner = :func:`hash_owner`; :meth:`HashTable.load_owned` restores
 ``items()`` of W ranks onto W' ranks.
@@ -390,6 +394,38 @@ class HashTable:
     if live <= max_load * self.capacity / 2:
       return self.rehash(slots=slots)
     return self.rehash(capacity=int(math.ceil(self.capacity * factor)), slots=slots)
+
+  # ---- a size bound ---------------------------------------------------------------------------------------
+  def evict_to(self, max_size, keep_freq=0, slots=(), report=None):
+    """The oldest keys leave until at most ``max_size`` stay (``hbk_hash_evict_to_n``): with ``need = size() -
+    max_size > 0``, every key whose ``last_seen`` is at or below the smallest step that covers ``need`` keys is
+    evicted as :meth:`evict` evicts.  Whole steps leave together -- keys last seen at the same step are equally
+    old -- so the size afterwards is ``<= max_size`` and undershoots it by less than the keys of one step; there
+    is no tie-break and no exact size.  ``keep_freq > 0``: keys seen that often stay whatever their age (the
+    table may then stay above the bound).  ``slots``: as in :meth:`evict`.  The step counter is not read.
+    Returns the report, int32 ``[4]`` on the device: ``{live_before, need, cut, n_evicted}`` (``report``: a
+    preallocated one, for a captured call).  No host read, no sync."""
+    return hash_evict_to([self], [max_size], keep_freq, [slots], [report])[0]
+
+  def maybe_evict(self, max_load=0.75, target_load=0.5, keep_freq=0, slots=()):
+    """The bounded-memory twin of :meth:`maybe_grow`: the capacity never changes.  Decided from ONE host read of
+    ``counts`` and ``stats``: nothing (None) while at most ``max_load`` of the slots are occupied (keys and
+    tombstones); else, when the live keys exceed ``target_load * capacity``, :meth:`evict_to`
+    ``floor(target_load * capacity)`` and ALWAYS a :meth:`rehash` to the same capacity -- the eviction has just
+    turned up to ``max_load - target_load`` of the slots into tombstones, and a table full of them translates
+    slowly; else (tombstones were the load) the rehash alone.  Returns the new companion tensors of ``slots``
+    (see :meth:`rehash` for what a rehash invalidates)."""
+    self._need_expiring('maybe_evict')
+    max_load, target_load = _check_loads(max_load, target_load)
+    if int(keep_freq) < 0:
+      raise _bad(f'keep_freq must be >= 0, got {keep_freq}')
+    inserted, _, evicted, reused = self._counters()
+    occupied, live = inserted - reused, inserted - evicted
+    if occupied <= max_load * self.capacity:
+      return None
+    if live > target_load * self.capacity:
+      self.evict_to(int(math.floor(target_load * self.capacity)), keep_freq, slots)
+    return self.rehash(slots=slots)
 
   # ---- export and import ----------------------------------------------------------------------------------
   def export_items(self, since=None, slots=()):
@@ -771,16 +807,78 @@ def _evict_columns(tables, steps_to_live, keep_freq, slots):
   cols = (_lib.HashEvictColumn * len(tables))()
   for c, t in enumerate(tables):
     _lib.require_device_tensor(t.keys, 'keys')
-    col = cols[c]
-    col.keys_cache, col.slab_count, col.slab_size = t.keys.data_ptr(), t.slab_count, t.slab_size
-    t._describe_expiry(col.exp)
-    col.steps_to_live, col.keep_freq = steps_to_live, keep_freq
-    pairs = checked[c]
-    col.n_fills = len(pairs)
-    for f, (x, value) in enumerate(pairs):
-      col.fills[f].base, col.fills[f].pitch, col.fills[f].dim = x.data_ptr(), x.stride(0), x.shape[1]
-      col.fills[f].value = value
+    _describe_sweep(cols[c], t, keep_freq, checked[c])
+    cols[c].steps_to_live = steps_to_live
   return cols, checked
+
+
+def _describe_sweep(col, t, keep_freq, pairs):
+  """What the descriptors of both sweeps share: the table, its expiry record, the guard and the fills."""
+  col.keys_cache, col.slab_count, col.slab_size = t.keys.data_ptr(), t.slab_count, t.slab_size
+  t._describe_expiry(col.exp)
+  col.keep_freq = keep_freq
+  col.n_fills = len(pairs)
+  for f, (x, value) in enumerate(pairs):
+    col.fills[f].base, col.fills[f].pitch, col.fills[f].dim = x.data_ptr(), x.stride(0), x.shape[1]
+    col.fills[f].value = value
+
+
+_EVICT_TO_WORKSPACES = {}   # (device, n_tables) -> int32 scratch: the same address at every call, so a captured call replays
+
+
+def hash_evict_to(tables, max_sizes, keep_freq=0, slots=None, reports=None):
+  """:meth:`HashTable.evict_to` for N expiring tables in ONE C call (``hbk_hash_evict_to_n``): per table the
+  oldest keys leave until at most ``max_sizes[c]`` stay -- the cut is found on the device, three histogram passes
+  over ``last_seen`` and a sweep, no host read.  ``max_sizes``: one int for all tables or one per table.
+  ``slots[c]``: the ``(tensor, fill_value)`` pairs of table ``c`` as in :func:`hash_evict`.  ``reports[c]``: an
+  int32 ``[4]`` device tensor or None (allocated): ``{live_before, need, cut, n_evicted}`` of table c after the
+  call.  Returns the list of reports; does not sync.  The scratch tensor is kept per (device, number of tables),
+  so a captured call replays."""
+  tables = list(tables)
+  same_device(tables)
+  n = len(tables)
+  keep_freq = int(keep_freq)
+  if not isinstance(max_sizes, (list, tuple)):
+    max_sizes = [max_sizes] * n
+  max_sizes, slots, reports = _per_table(n, ('max_sizes', max_sizes, 0), ('lists of companion tensors', slots, ()),
+                                         ('reports', reports, None))
+  max_sizes = [int(m) for m in max_sizes]
+  if any(m < 0 for m in max_sizes) or keep_freq < 0:
+    raise _bad(f'max_size and keep_freq must be >= 0, got {min(max_sizes + [0])} and {keep_freq}')
+  for t in tables:
+    t._need_expiring('evict_to')
+  checked = [_companions(t, slots[c]) for c, t in enumerate(tables)]
+  lib = _lib.lib()
+  if n == 0:
+    _lib.check(lib.hbk_hash_evict_to_n(0, None, None, 0, None))
+    return []
+  dev = tables[0].keys.device
+  cols = (_lib.HashEvictToColumn * n)()
+  for c, r in enumerate(reports):
+    if r is not None and (not isinstance(r, torch.Tensor) or r.dtype != torch.int32 or tuple(r.shape) != (4,) or
+                          r.device != dev or not r.is_contiguous()):
+      raise _bad(f'reports[{c}] must be a contiguous int32 [4] tensor on {dev}')
+  for c, t in enumerate(tables):
+    _lib.require_device_tensor(t.keys, 'keys')
+    if reports[c] is None:
+      reports[c] = torch.zeros(4, dtype=torch.int32, device=dev)
+    _describe_sweep(cols[c], t, keep_freq, checked[c])
+    cols[c].max_size = max_sizes[c]
+    cols[c].report = reports[c].data_ptr()
+  nbytes = lib.hbk_hash_evict_to_workspace_bytes(n)
+  workspace = _EVICT_TO_WORKSPACES.get((dev, n))
+  if workspace is None or workspace.numel() * 4 < nbytes:
+    workspace = _EVICT_TO_WORKSPACES[(dev, n)] = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=dev)
+  _lib.check(lib.hbk_hash_evict_to_n(n, cols, workspace.data_ptr(), workspace.numel() * 4, _lib.current_stream(dev)))
+  return reports
+
+
+def _check_loads(max_load, target_load):
+  max_load, target_load = float(max_load), float(target_load)
+  if not 0.0 < target_load <= max_load <= 1.0:
+    raise _bad(f'0 < target_load <= max_load <= 1 is needed, got target_load {target_load!r} and max_load '
+               f'{max_load!r}')
+  return max_load, target_load
 
 
 def check_ids(ids_list, tables):
@@ -931,6 +1029,16 @@ def grow_tables(lookup, tables, max_load, factor, slots):
   return out
 
 
+def evict_tables(lookup, tables, max_load, target_load, keep_freq, slots):
+  """:meth:`HashTable.maybe_evict` on every table, then ``lookup.rebind()`` if any was rehashed."""
+  slots, = _per_table(len(tables), ('lists of companion tensors', slots, ()))
+  _check_loads(max_load, target_load)
+  out = [t.maybe_evict(max_load, target_load, keep_freq, slots[c]) for c, t in enumerate(tables)]
+  if any(o is not None for o in out):
+    lookup.rebind()
+  return out
+
+
 class HashGroupLookup:
   """N hash-keyed columns: one translate launch, then a :class:`GroupLookup` over ``[t.table ...]`` with
   buckets 0 on the row numbers.
@@ -971,6 +1079,12 @@ class HashGroupLookup:
     :meth:`rebind` if any table was rehashed.  Returns the per-table results: None, or the new companion
     tensors.  See :meth:`rebind` for what must be rebuilt afterwards."""
     return grow_tables(self, self.tables, max_load, factor, slots)
+
+  def maybe_evict(self, max_load=0.75, target_load=0.5, keep_freq=0, slots=None):
+    """:meth:`HashTable.maybe_evict` on every table (``slots[c]``: the companions of table c), then
+    :meth:`rebind` if any table was rehashed.  Returns the per-table results: None, or the new companion
+    tensors.  See :meth:`rebind` for what must be rebuilt afterwards."""
+    return evict_tables(self, self.tables, max_load, target_load, keep_freq, slots)
 
   def __len__(self):
     return len(self.tables)

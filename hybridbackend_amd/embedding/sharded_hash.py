@@ -34,8 +34,8 @@ class ShardedHashGroupLookup(ShardedGroupLookup):
   ``backward`` returns, ``unique_rows`` are slot numbers of this rank's tables (``tables[c].keys[unique_rows]``
   names the ids).  ``sp_weights`` and ``p2p_bind`` are refused by the library; ``PipelinedLookup`` refuses
   objects of this class.  Eviction, ``set_step`` and filter maintenance are the tables' own methods: they move
-  no tensor, so the plan stays valid.  A rehash of a table does: :meth:`rebind` (or :meth:`maybe_grow`, which
-  does both)."""
+  no tensor, so the plan stays valid.  A rehash of a table does: :meth:`rebind` (or :meth:`maybe_grow` and
+  :meth:`maybe_evict`, which do both)."""
 
   def __init__(self, tables, coll, combiners='sum', wire_dtype=None, dedup=False, max_norms=None, train=True,
                accums=None, moments=None, adam=None, ftrl_slots=None, ftrl=None, hot_rows=False, world_size=None,
@@ -152,13 +152,25 @@ class ShardedHashGroupLookup(ShardedGroupLookup):
     v 0, FTRL's accum its ``initial_accumulator_value`` and linear 0), then :meth:`rebind` with the new tensors
     if any table was rehashed.  Local to the rank: no exchange, and ranks need not agree.  Returns per table
     whether it was rehashed."""
+    return self._maybe(lambda t, comp: t.maybe_grow(max_load, factor, comp))
+
+  def maybe_evict(self, max_load=0.75, target_load=0.5, keep_freq=0):
+    """:meth:`HashTable.maybe_evict` on every table of this rank -- the capacity stays, the oldest keys leave --
+    with the bound optimizer slots as companions and the fill values of :meth:`maybe_grow`, then :meth:`rebind`
+    with the new tensors if any table was rehashed.  Local to the rank: no exchange, and ranks need not agree.
+    Returns per table whether it was rehashed."""
+    _ht._check_loads(max_load, target_load)   # pylint: disable=protected-access
+    return self._maybe(lambda t, comp: t.maybe_evict(max_load, target_load, keep_freq, comp))
+
+  def _maybe(self, policy):
+    """``policy(table, companions)`` -> None or the new companions, on every table; the rebind that follows."""
     kinds = self._slot_kinds()
     new = {name: [list(x) if k is not None else x for x in getattr(self, name)]
            for name, k, _ in kinds}
     grown = []
     for c, t in enumerate(self.tables):
       comp = [((getattr(self, name)[c] if k is None else getattr(self, name)[c][k]), fill) for name, k, fill in kinds]
-      out = t.maybe_grow(max_load, factor, comp)
+      out = policy(t, comp)
       grown.append(out is not None)
       for (name, k, _), x in zip(kinds, out or ()):
         if k is None:

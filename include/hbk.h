@@ -806,6 +806,59 @@ typedef struct {
 } hbk_hash_evict_column_t;
 int hbk_hash_evict_n(int32_t n_cols, const hbk_hash_evict_column_t* cols, hbk_stream_t stream);
 
+/* Bounded tables: evict the oldest keys down to a size bound (the reference's EmbeddingService removes the
+ * num_removes entries with the oldest step: hybridbackend/tensorflow/embedding/service.py:180-210).
+ * hbk_hash_evict_n asks for an age threshold in advance; hbk_hash_evict_to_n finds it on the device.  Per table:
+ *     live      = the slots that hold a key (neither EMPTY nor TOMBSTONE), L = |live|
+ *     evictable = the live slots with  keep_freq == 0  or  freq[slot] < keep_freq    (hbk_hash_evict_n's guard)
+ *     need      = L - max_size;  need <= 0: nothing is written to the table's arrays, they stay bit-identical
+ *     cut       = the smallest v with  #{evictable : last_seen <= v} >= need,  last_seen compared as SIGNED int32;
+ *                 fewer than `need` evictable slots: cut = INT32_MAX (every evictable slot goes, and the table
+ *                 stays above the bound)
+ * and every evictable slot with last_seen <= cut is evicted exactly as hbk_hash_evict_n evicts: key = TOMBSTONE,
+ * freq = last_seen = 0, the rows of the n_fills companion arrays = their value, stats[0] += the slots evicted.
+ * *step is not read: the order is last_seen itself.
+ *
+ * WHOLE STEPS LEAVE TOGETHER.  Keys last seen at the same step are equally old, so all of them go: the size
+ * after the call is <= max_size (unless the frequency guard kept it above) and undershoots the bound by less
+ * than the keys of one step -- those with last_seen == cut.  There is no tie-break: the evicted set is a
+ * function of the table's arrays alone, the same on every run and whatever slots the keys sit in (the
+ * reference's top_k picks arbitrarily among ties).  Not an exact size, and not an LFU order: keep_freq is the
+ * only use of freq.
+ *
+ * report (device int32[4] or NULL), written by the call: {live_before, need, cut, n_evicted}; cut is 0 when
+ * need <= 0.
+ *
+ * One call serves N tables of any capacities (more than 32: several launches each).  The selection is a radix
+ * select over last_seen ^ 0x80000000, most significant digit first, 11 / 11 / 10 bits: per digit one streaming
+ * histogram pass over the slots (16 bytes per slot; per-workgroup histogram in LDS, a wave's hits on its leading
+ * lane's bin added once, non-zero bins added to the table's histogram with integer atomics -- an
+ * order-independent sum) and one small kernel per table that picks the bin the remaining need falls into; then
+ * the sweep.  The passes after the first leave at once for a table with need <= 0.  No host read anywhere:
+ * everything is stream-ordered device work, and the call clears its workspace on the stream itself, so it can
+ * be captured into a graph and replayed.  Stream-ordered against the translate launches of its tables, never
+ * beside one, as the sweep.
+ *
+ * workspace: device memory of hbk_hash_evict_to_workspace_bytes(n_cols) bytes, 4-byte aligned; contents are
+ * scratch.  Refused (HBK_INVALID_ARGUMENT) before any device work: what hbk_hash_evict_n refuses of keys_cache,
+ * slab_count, slab_size and the fills; NULL last_seen or freq; max_size < 0; keep_freq < 0; a table of 2^31
+ * slots or more (the counters are int32); a NULL or too small workspace where n_cols > 0.  exp.step may be
+ * NULL. */
+typedef struct {
+  int64_t* keys_cache;    /* device [slab_count * slab_size], 8-byte aligned */
+  int64_t slab_count;
+  int32_t slab_size;      /* 1..64 */
+  hbk_hash_expiry_t exp;  /* step is not read */
+  int64_t max_size;       /* >= 0: the keys that may stay */
+  int32_t keep_freq;      /* >= 0; 0: frequency keeps nothing */
+  int32_t n_fills;        /* 0..HBK_HASH_MAX_FILLS */
+  hbk_hash_fill_t fills[HBK_HASH_MAX_FILLS];
+  int32_t* report;        /* device int32[4] {live_before, need, cut, n_evicted}, or NULL */
+} hbk_hash_evict_to_column_t;
+size_t hbk_hash_evict_to_workspace_bytes(int32_t n_cols);
+int hbk_hash_evict_to_n(int32_t n_cols, const hbk_hash_evict_to_column_t* cols, void* workspace,
+                        size_t workspace_bytes, hbk_stream_t stream);
+
 /* Admission filter: a count-min sketch gates new ids (DeepRec's CounterFilter / CBFFilter beside
  * steps_to_live).  Most distinct ids of a click log occur once or twice; unfiltered, each of them claims a row,
  * its optimizer slots and a key slot at first sight.  A filtered table stores an id once it was seen min_freq
