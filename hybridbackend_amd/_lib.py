@@ -172,6 +172,15 @@ class HashStoreColumn(C.Structure):
               ('moves', HashMove * HASH_MAX_MOVES)]
 
 
+class HashSpillColumn(C.Structure):
+  """hbk_hash_spill_column_t"""
+  _fields_ = [('keys_cache', C.c_void_p), ('slab_count', C.c_int64), ('slab_size', C.c_int32),
+              ('exp', HashExpiry), ('selection', C.c_void_p), ('keep_freq', C.c_int32), ('n_moves', C.c_int32),
+              ('moves', HashMove * HASH_MAX_MOVES), ('n_fills', C.c_int32), ('fills', HashFill * HASH_MAX_FILLS),
+              ('out_keys', C.c_void_p), ('out_slots', C.c_void_p), ('out_capacity', C.c_int64),
+              ('count', C.c_void_p), ('n_evicted', C.c_void_p)]
+
+
 class ShardedColumn(C.Structure):
   """hbk_sharded_column_t"""
   _fields_ = [('shard', C.c_void_p), ('rows_local', C.c_int64), ('dim', C.c_int32),
@@ -251,6 +260,7 @@ def _declare(l):
     'hbk_hash_evict_n': (C.c_int, [i32, vp, vp]),
     'hbk_hash_evict_to_workspace_bytes': (sz, [i32]),
     'hbk_hash_evict_to_n': (C.c_int, [i32, vp, vp, sz, vp]),
+    'hbk_hash_evict_to_select_n': (C.c_int, [i32, vp, vp, sz, vp]),
     'hbk_hash_insert_admit_n': (C.c_int, [i32, vp, vp, i32, vp]),
     'hbk_hash_insert_expiring_admit_n': (C.c_int, [i32, vp, vp, vp, i32, vp]),
     'hbk_hash_rehash_n': (C.c_int, [i32, vp, vp]),
@@ -259,6 +269,8 @@ def _declare(l):
     'hbk_hash_export_workspace_bytes': (C.c_int, [i32, vp, vp]),
     'hbk_hash_export_n': (C.c_int, [i32, vp, vp, vp]),
     'hbk_hash_store_rows_n': (C.c_int, [i32, vp, vp]),
+    'hbk_hash_spill_workspace_bytes': (C.c_int, [i32, vp, vp]),
+    'hbk_hash_spill_n': (C.c_int, [i32, vp, vp, vp]),
     'hbk_comm_get_id': (C.c_int, [vp]),
     'hbk_comm_rccl_versions': (C.c_int, [vp, vp]),
     'hbk_comm_create': (C.c_int, [vp, vp, i32, i32, i32]),

@@ -21,6 +21,11 @@
 //
 // State per table in the workspace, int32 words: kState words, then the 2048 bins.  The entry clears it on the
 // stream, so a captured call replays.  No host read anywhere.
+//
+// hbk_hash_evict_to_select_n is the same call without the sweep: the clear launch and the three digit passes, the
+// pick kernels instantiated with SELECT, which also write the number of slots the sweep would evict to the report's
+// fourth word -- the need consumed before the last chosen bin plus that bin's count, or the scan total when all
+// evictable slots go.  Nothing of the table is written.
 #include "hash_common.h"
 
 namespace hbk {
@@ -140,7 +145,8 @@ struct PickArgs {
 
 // One workgroup per table.  Thread t owns the bins [8 t, 8 t + 8); a scan over the threads' sums finds the one
 // thread whose bins the remaining need falls into.
-template <int DIGIT>
+// SELECT: report[3] = the slots a sweep with this cut evicts (hbk_hash_evict_to_select_n; the report is not NULL)
+template <int DIGIT, bool SELECT>
 __global__ __launch_bounds__(kBlock) void hash_evict_to_pick_kernel(const PickArgs a) {
   __shared__ int32_t sums[kBlock];
   const ToCol& c = a.col[blockIdx.x];
@@ -188,6 +194,7 @@ __global__ __launch_bounds__(kBlock) void hash_evict_to_pick_kernel(const PickAr
       state[kAll] = 1;
       state[kCut] = (int32_t)0xffffffffu;
       if (c.report != nullptr) c.report[2] = 0x7fffffff;
+      if (SELECT) c.report[3] = sums[kBlock - 1];
     }
     return;
   }
@@ -203,6 +210,9 @@ __global__ __launch_bounds__(kBlock) void hash_evict_to_pick_kernel(const PickAr
     if (DIGIT == 2) {
       state[kCut] = (int32_t)prefix;
       if (c.report != nullptr) c.report[2] = (int32_t)(prefix ^ 0x80000000u);
+      // `need - run` of the whole need is still open in front of the chosen bin: the rest was consumed by the
+      // bins below it, over all three digits; the chosen bin leaves whole
+      if (SELECT) c.report[3] = state[kNeed] - (need - run) + v[j];
     }
   }
 }
@@ -241,11 +251,12 @@ __global__ __launch_bounds__(kBlock) void hash_evict_to_clear_kernel(int32_t* wo
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) words[i] = 0;
 }
 
-template <int DIGIT>
+template <int DIGIT, bool SELECT>
 int launch_digit(const HistArgs& hist, const PickArgs& pick, int64_t tiles, hipStream_t stream) {
   hipLaunchKernelGGL(hash_evict_to_hist_kernel<DIGIT>, dim3((unsigned)tiles), dim3(kBlock), 0, stream, hist);
   HBK_HIP_OK(hipGetLastError());
-  hipLaunchKernelGGL(hash_evict_to_pick_kernel<DIGIT>, dim3((unsigned)hist.n_cols), dim3(kBlock), 0, stream, pick);
+  hipLaunchKernelGGL((hash_evict_to_pick_kernel<DIGIT, SELECT>), dim3((unsigned)hist.n_cols), dim3(kBlock), 0, stream,
+                     pick);
   HBK_HIP_OK(hipGetLastError());
   return HBK_OK;
 }
@@ -257,10 +268,13 @@ extern "C" size_t hbk_hash_evict_to_workspace_bytes(int32_t n_cols) {
   return n_cols <= 0 ? 0 : (size_t)n_cols * hbk::kWordsPerTable * sizeof(int32_t);
 }
 
-extern "C" int hbk_hash_evict_to_n(int32_t n_cols, const hbk_hash_evict_to_column_t* cols, void* workspace,
-                                   size_t workspace_bytes, hbk_stream_t stream) {
-  using namespace hbk;
-  const char* who = "hash_evict_to_n";
+namespace hbk {
+namespace {
+
+// both entries: SELECT = the selection alone, no sweep
+template <bool SELECT>
+int evict_to(const char* who, int32_t n_cols, const hbk_hash_evict_to_column_t* cols, void* workspace,
+             size_t workspace_bytes, hbk_stream_t stream) {
   HBK_REQUIRE(n_cols >= 0, "%s: n_cols must be >= 0, got %d", who, n_cols);
   HBK_REQUIRE(n_cols == 0 || cols != nullptr, "%s: cols is NULL", who);
   for (int32_t c = 0; c < n_cols; ++c) {
@@ -274,6 +288,7 @@ extern "C" int hbk_hash_evict_to_n(int32_t n_cols, const hbk_hash_evict_to_colum
     HBK_REQUIRE(h.max_size >= 0, "%s: column %d: max_size must be >= 0, got %lld", who, c, (long long)h.max_size);
     HBK_REQUIRE(h.keep_freq >= 0, "%s: column %d: keep_freq must be >= 0, got %d", who, c, h.keep_freq);
     if (int rc = check_fills(who, c, h.n_fills, h.fills)) return rc;
+    HBK_REQUIRE(!SELECT || h.report != nullptr, "%s: column %d: report is NULL", who, c);
   }
   if (n_cols == 0) return HBK_OK;
   const size_t needed = hbk_hash_evict_to_workspace_bytes(n_cols);
@@ -316,11 +331,25 @@ extern "C" int hbk_hash_evict_to_n(int32_t n_cols, const hbk_hash_evict_to_colum
     }
     sweep.n_cols = hist.n_cols = k;
     for (int32_t i = 0; i <= k; ++i) hist.tile_start[i] = sweep.tile_start[i];
-    if (int rc = launch_digit<0>(hist, pick, tiles, s)) return rc;
-    if (int rc = launch_digit<1>(hist, pick, tiles, s)) return rc;
-    if (int rc = launch_digit<2>(hist, pick, tiles, s)) return rc;
+    if (int rc = launch_digit<0, SELECT>(hist, pick, tiles, s)) return rc;
+    if (int rc = launch_digit<1, SELECT>(hist, pick, tiles, s)) return rc;
+    if (int rc = launch_digit<2, SELECT>(hist, pick, tiles, s)) return rc;
+    if (SELECT) continue;
     hipLaunchKernelGGL(hash_evict_to_sweep_kernel, dim3((unsigned)tiles), dim3(kBlock), 0, s, sweep);
     HBK_HIP_OK(hipGetLastError());
   }
   return HBK_OK;
+}
+
+}  // namespace
+}  // namespace hbk
+
+extern "C" int hbk_hash_evict_to_n(int32_t n_cols, const hbk_hash_evict_to_column_t* cols, void* workspace,
+                                   size_t workspace_bytes, hbk_stream_t stream) {
+  return hbk::evict_to<false>("hash_evict_to_n", n_cols, cols, workspace, workspace_bytes, stream);
+}
+
+extern "C" int hbk_hash_evict_to_select_n(int32_t n_cols, const hbk_hash_evict_to_column_t* cols, void* workspace,
+                                          size_t workspace_bytes, hbk_stream_t stream) {
+  return hbk::evict_to<true>("hash_evict_to_select_n", n_cols, cols, workspace, workspace_bytes, stream);
 }

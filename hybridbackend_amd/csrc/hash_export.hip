@@ -25,16 +25,15 @@
 //
 // Rows travel as 4-byte words.  A move whose two bases, two pitches and width are all multiples of 16 bytes is
 // copied with 16-byte accesses (hash_common.h: Move); the lane group of a move is pow2(accesses per row).
-#include "hash_common.h"
+//
+// The three launches of the export are hash_pack.h's, shared with hbk_hash_spill_n (hash_spill.hip): the kernels are
+// templates over the argument struct, whose columns bring the selection.
+#include "hash_pack.h"
 
 namespace hbk {
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kWavesPerBlock = kBlock / kWave;
-constexpr int kSlotsPerTile = kBlock;                   // one 64-slot chunk per wave
-constexpr int kScanPerThread = 8;                       // tile counts a thread of the scan takes per pass
-constexpr int kMaxColsPerLaunch = 32;                   // the argument structs travel by value
+using namespace pack;   // kBlock, kSlotsPerTile, kMaxColsPerLaunch, tiles_of, the three kernels
 
 struct ExportCol {
   const long long* keys;
@@ -51,6 +50,15 @@ struct ExportCol {
   int32_t n_moves;
   int32_t pad_;
   Move move[HBK_HASH_MAX_MOVES];
+
+  // the selection: the one predicate of the count and the write launch
+  __device__ bool selected(int64_t slot) const {
+    if (slot >= capacity) return false;
+    const long long key = keys[slot];
+    if (!holds_key(key, expiring != 0)) return false;
+    return since <= 0 || last_seen[slot] >= since;
+  }
+  __device__ void scanned() const {}
 };
 
 struct ExportArgs {
@@ -76,119 +84,6 @@ struct StoreArgs {
 };
 static_assert(sizeof(StoreArgs) <= 24576, "kernarg budget");
 
-// the selection: the one predicate of the count and the write launch
-__device__ inline bool exported(const ExportCol& c, int64_t slot) {
-  if (slot >= c.capacity) return false;
-  const long long key = c.keys[slot];
-  if (!holds_key(key, c.expiring != 0)) return false;
-  return c.since <= 0 || c.last_seen[slot] >= c.since;
-}
-
-__global__ __launch_bounds__(kBlock) void hash_export_count_kernel(const ExportArgs a) {
-  __shared__ int32_t wave_n[kWavesPerBlock];
-  const int b = (int)blockIdx.x;
-  const int lane = lane_id();
-  const int wave = (int)(threadIdx.x >> 6);
-  const int ci = column_of(a.tile_start, a.n_cols, b, lane);
-  const ExportCol& c = a.col[ci];
-  const int64_t tile = (int64_t)(b - a.tile_start[ci]);
-  const int64_t slot = tile * kSlotsPerTile + (int64_t)wave * kWave + lane;
-  const unsigned long long mask = __ballot(exported(c, slot));
-  if (lane == 0) wave_n[wave] = (int32_t)__builtin_popcountll(mask);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int32_t n = 0;
-#pragma unroll
-    for (int w = 0; w < kWavesPerBlock; ++w) n += wave_n[w];
-    c.tiles[tile] = (int64_t)n;
-  }
-}
-
-// one workgroup per column: counts -> exclusive offsets in place, the total -> *count
-__global__ __launch_bounds__(kBlock) void hash_export_scan_kernel(const ExportArgs a) {
-  __shared__ int64_t wave_sum[kWavesPerBlock];
-  const ExportCol& c = a.col[blockIdx.x];
-  const int lane = lane_id();
-  const int wave = (int)(threadIdx.x >> 6);
-  int64_t carry = 0;   // matches of the tiles before this pass (block-uniform)
-  for (int64_t t0 = 0; t0 < c.n_tiles; t0 += (int64_t)kBlock * kScanPerThread) {   // (block-uniform bounds)
-    const int64_t first = t0 + (int64_t)threadIdx.x * kScanPerThread;
-    int64_t v[kScanPerThread];
-    int64_t mine = 0;
-#pragma unroll
-    for (int k = 0; k < kScanPerThread; ++k) {
-      v[k] = first + k < c.n_tiles ? c.tiles[first + k] : 0;
-      mine += v[k];
-    }
-    // inclusive scan of `mine` across the wave, then across the four waves through LDS
-    int64_t incl = mine;
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-      const int64_t up = (int64_t)__shfl_up((long long)incl, off, kWave);
-      if (lane >= off) incl += up;
-    }
-    if (lane == kWave - 1) wave_sum[wave] = incl;
-    __syncthreads();
-    int64_t before = carry, total = 0;
-#pragma unroll
-    for (int w = 0; w < kWavesPerBlock; ++w) {
-      if (w < wave) before += wave_sum[w];
-      total += wave_sum[w];
-    }
-    __syncthreads();   // (wave_sum is written again by the next pass)
-    int64_t run = before + incl - mine;
-#pragma unroll
-    for (int k = 0; k < kScanPerThread; ++k) {
-      if (first + k < c.n_tiles) c.tiles[first + k] = run;
-      run += v[k];
-    }
-    carry += total;
-  }
-  if (threadIdx.x == 0) *c.count = carry;
-}
-
-__global__ __launch_bounds__(kBlock) void hash_export_write_kernel(const ExportArgs a) {
-  __shared__ int32_t wave_n[kWavesPerBlock];
-  const int b = (int)blockIdx.x;
-  const int lane = lane_id();
-  const int wave = (int)(threadIdx.x >> 6);
-  const int ci = column_of(a.tile_start, a.n_cols, b, lane);
-  const ExportCol& c = a.col[ci];
-  const int64_t tile = (int64_t)(b - a.tile_start[ci]);
-  const int64_t first = tile * kSlotsPerTile + (int64_t)wave * kWave;
-  const int64_t slot = first + lane;
-  const bool take = exported(c, slot);
-  const unsigned long long mask = __ballot(take);
-  const int n = (int)__builtin_popcountll(mask);
-  if (lane == 0) wave_n[wave] = n;
-  __syncthreads();   // (every wave of the tile is here: nothing above returns)
-  if (mask == 0ull) return;   // (wave-uniform)
-  int64_t base = c.tiles[tile];
-  for (int w = 0; w < wave; ++w) base += wave_n[w];
-  const int64_t out_capacity = c.out_capacity;
-  if (base >= out_capacity) return;   // (wave-uniform) the whole range lies behind the output
-  const int below = rank_below(mask);
-  if (take && base + below < out_capacity) {
-    c.out_keys[base + below] = c.keys[slot];
-    if (c.out_slots != nullptr) c.out_slots[base + below] = slot;
-  }
-  if (c.n_moves == 0) return;
-  const int live_lane = compact_lanes(mask, take, lane);   // lane r < n: the lane of the r-th live slot
-  for (int m = 0; m < c.n_moves; ++m) {
-    const Move& mv = c.move[m];
-    const int lanes_log2 = mv.lanes_log2;
-    const int sub = lane & ((1 << lanes_log2) - 1);
-    for (int r0 = 0; r0 < n; r0 += kWave >> lanes_log2) {   // (wave-uniform bounds)
-      const int r = r0 + (lane >> lanes_log2);
-      const int from = __shfl(live_lane, r & (kWave - 1), kWave);   // (every lane takes the shuffle)
-      if (r < n && base + r < out_capacity) {
-        copy_row(mv, mv.src + (first + from) * mv.src_pitch, mv.dst + (base + r) * mv.dst_pitch, sub,
-                 1 << mv.lanes_log2);
-      }
-    }
-  }
-}
-
 __global__ __launch_bounds__(kBlock) void hash_store_rows_kernel(const StoreArgs a) {
   const int b = (int)blockIdx.x;
   const int lane = lane_id();
@@ -212,8 +107,6 @@ __global__ __launch_bounds__(kBlock) void hash_store_rows_kernel(const StoreArgs
     }
   }
 }
-
-inline int64_t tiles_of(int64_t n) { return (n + kSlotsPerTile - 1) / kSlotsPerTile; }
 
 int check_export(const char* who, int32_t n_cols, const hbk_hash_export_column_t* cols, bool outputs) {
   HBK_REQUIRE(n_cols >= 0, "%s: n_cols must be >= 0, got %d", who, n_cols);
@@ -288,12 +181,7 @@ extern "C" int hbk_hash_export_n(int32_t n_cols, const hbk_hash_export_column_t*
       args.tile_start[k] = (int32_t)tiles;
     }
     args.n_cols = k;
-    hipLaunchKernelGGL(hash_export_count_kernel, dim3((unsigned)tiles), dim3(kBlock), 0, as_stream(stream), args);
-    HBK_HIP_OK(hipGetLastError());
-    hipLaunchKernelGGL(hash_export_scan_kernel, dim3((unsigned)k), dim3(kBlock), 0, as_stream(stream), args);
-    HBK_HIP_OK(hipGetLastError());
-    hipLaunchKernelGGL(hash_export_write_kernel, dim3((unsigned)tiles), dim3(kBlock), 0, as_stream(stream), args);
-    HBK_HIP_OK(hipGetLastError());
+    if (int rc = launch_pack(args, tiles, as_stream(stream))) return rc;
   }
   return HBK_OK;
 }

@@ -31,6 +31,12 @@ Bounded tables (``hbk_hash_evict_to_n``): :meth:`HashTable.evict_to` / :func:`ha
 down to a size bound, the cut found on the device (whole steps leave together: no exact size, no tie-break);
 :meth:`HashTable.maybe_evict` / :meth:`HashGroupLookup.maybe_evict` are ``maybe_grow`` for a fixed memory budget.
 
+Spilling to a host tier (``hbk_hash_evict_to_select_n`` / ``hbk_hash_spill_n``): :meth:`HashTable.spill_to` /
+:func:`hash_spill` export exactly the keys an ``evict_to`` would remove -- rows, ``last_seen``, ``freq`` and the
+optimizer slots -- and then remove them; a :class:`HashSpillStore` keeps them on the host, and
+:meth:`HashTable.fault_in` / :meth:`HashGroupLookup.fault_in` bring a batch's spilled keys back as they left before
+the translate.  ``maybe_evict(..., spill=store)`` spills where it evicted.
+
 Sharded hash tables: :class:`hybridbackend_amd.embedding.ShardedHashGroupLookup` (sharded_hash.py) puts tables of
 W ranks behind the sharded lookup step, owner = :func:`hash_owner`; :meth:`HashTable.load_owned` restores
 ``items()`` of W ranks onto W' ranks.
@@ -407,25 +413,77 @@ class HashTable:
     preallocated one, for a captured call).  No host read, no sync."""
     return hash_evict_to([self], [max_size], keep_freq, [slots], [report])[0]
 
-  def maybe_evict(self, max_load=0.75, target_load=0.5, keep_freq=0, slots=()):
+  def maybe_evict(self, max_load=0.75, target_load=0.5, keep_freq=0, slots=(), spill=None):
     """The bounded-memory twin of :meth:`maybe_grow`: the capacity never changes.  Decided from ONE host read of
     ``counts`` and ``stats``: nothing (None) while at most ``max_load`` of the slots are occupied (keys and
     tombstones); else, when the live keys exceed ``target_load * capacity``, :meth:`evict_to`
     ``floor(target_load * capacity)`` and ALWAYS a :meth:`rehash` to the same capacity -- the eviction has just
     turned up to ``max_load - target_load`` of the slots into tombstones, and a table full of them translates
     slowly; else (tombstones were the load) the rehash alone.  Returns the new companion tensors of ``slots``
-    (see :meth:`rehash` for what a rehash invalidates)."""
+    (see :meth:`rehash` for what a rehash invalidates).  ``spill``: a :class:`HashSpillStore` -- when the call
+    evicts it uses :meth:`spill_to` where it used :meth:`evict_to`: the keys that leave go to the store."""
     self._need_expiring('maybe_evict')
     max_load, target_load = _check_loads(max_load, target_load)
     if int(keep_freq) < 0:
       raise _bad(f'keep_freq must be >= 0, got {keep_freq}')
+    if spill is not None:
+      _check_store(spill, self, slots)
     inserted, _, evicted, reused = self._counters()
     occupied, live = inserted - reused, inserted - evicted
     if occupied <= max_load * self.capacity:
       return None
     if live > target_load * self.capacity:
-      self.evict_to(int(math.floor(target_load * self.capacity)), keep_freq, slots)
+      bound = int(math.floor(target_load * self.capacity))
+      if spill is None:
+        self.evict_to(bound, keep_freq, slots)
+      else:
+        self.spill_to(bound, spill, keep_freq, slots)
     return self.rehash(slots=slots)
+
+  # ---- a host tier behind the bound -----------------------------------------------------------------------
+  def spill_to(self, max_size, store=None, keep_freq=0, slots=()):
+    """:meth:`evict_to` that keeps what it evicts (``hbk_hash_evict_to_select_n`` / ``hbk_hash_spill_n``): the
+    keys an ``evict_to(max_size, keep_freq)`` would remove are exported -- row, ``last_seen``, ``freq`` and the rows
+    of the companions -- and then evicted as :meth:`evict_to` evicts.  ``slots``: ``(tensor, fill_value)`` pairs
+    as in :meth:`evict`: the tensor is exported, then reset to the value.  ``store``: a :class:`HashSpillStore`
+    that takes the export (``store.put``).  Returns the :class:`HashExport`, on the device, in ascending slot
+    order.  Two host reads (the selection's size, the export's count): see :func:`hash_spill`."""
+    self._need_expiring('spill_to')
+    if store is not None:
+      _check_store(store, self, slots)   # (before anything leaves the table)
+    exp = hash_spill([self], [max_size], keep_freq, [slots])[0]
+    if store is not None and len(exp):
+      store.put(exp)
+    return exp
+
+  def fault_in(self, ids, store, slots=()):
+    """Bring the keys of ``ids`` that ``store`` holds back into the table, before the translate of the step: a
+    :meth:`find`, the distinct missed ids (``torch.unique`` on the device), one device-to-host copy of them,
+    ``store.take`` and, if it returned anything, :meth:`import_items` -- rows, ``last_seen``, ``freq`` and the
+    companions ``slots`` (the destination tensors, as for :meth:`import_items`) come back as they left.  Nothing
+    the store does not hold is inserted: ids never seen are left to the translate that follows, and so is the
+    ``last_seen`` stamp (``find`` does not stamp).  The admission filter is bypassed, as by :meth:`import_items`.
+    No key is lost: when the table is too full for some of the taken keys they go back into the store before
+    the error is raised.  Returns the number of keys restored."""
+    self._need_expiring('fault_in')
+    _check_store(store, self, [(x, 0.0) for x in slots])
+    check_ids([ids], [self])
+    found = self.find(ids)
+    missed = torch.unique(ids[found < 0]).cpu()
+    if missed.numel() == 0 or len(store) == 0:
+      return 0
+    exp = store.take(missed)
+    if len(exp) == 0:
+      return 0
+    try:
+      self.import_items(exp, slots, assume_distinct=True)
+    except Exception:
+      # whatever is not in the table now goes back where it came from
+      lost = (self.find(exp.keys.to(self.keys.device)) < 0).cpu().nonzero().flatten()
+      store.put(HashExport(exp.keys[lost], exp.rows[lost], exp.last_seen[lost], exp.freq[lost],
+                           [x[lost] for x in exp.slots]))
+      raise
+    return len(exp)
 
   # ---- export and import ----------------------------------------------------------------------------------
   def export_items(self, since=None, slots=()):
@@ -834,6 +892,19 @@ def hash_evict_to(tables, max_sizes, keep_freq=0, slots=None, reports=None):
   int32 ``[4]`` device tensor or None (allocated): ``{live_before, need, cut, n_evicted}`` of table c after the
   call.  Returns the list of reports; does not sync.  The scratch tensor is kept per (device, number of tables),
   so a captured call replays."""
+  return _evict_to(tables, max_sizes, keep_freq, slots, reports, 'evict_to', 'hbk_hash_evict_to_n')
+
+
+def hash_evict_to_select(tables, max_sizes, keep_freq=0, reports=None):
+  """The selection of :func:`hash_evict_to` without its sweep (``hbk_hash_evict_to_select_n``): nothing of the
+  tables is written.  Returns the reports, int32 ``[4]`` on the device: ``{live_before, need, cut, n_selected}`` --
+  ``n_selected`` is the exact number of keys ``hash_evict_to`` with the same arguments would evict.  ``reports``:
+  preallocated ones.  No host read, no sync."""
+  return _evict_to(tables, max_sizes, keep_freq, None, reports, 'evict_to_select', 'hbk_hash_evict_to_select_n')
+
+
+def _evict_to(tables, max_sizes, keep_freq, slots, reports, what, entry):
+  """Both entries of the select: ``entry`` is the C entry, ``what`` names the call in a refusal."""
   tables = list(tables)
   same_device(tables)
   n = len(tables)
@@ -846,11 +917,12 @@ def hash_evict_to(tables, max_sizes, keep_freq=0, slots=None, reports=None):
   if any(m < 0 for m in max_sizes) or keep_freq < 0:
     raise _bad(f'max_size and keep_freq must be >= 0, got {min(max_sizes + [0])} and {keep_freq}')
   for t in tables:
-    t._need_expiring('evict_to')
+    t._need_expiring(what)
   checked = [_companions(t, slots[c]) for c, t in enumerate(tables)]
   lib = _lib.lib()
+  call = getattr(lib, entry)
   if n == 0:
-    _lib.check(lib.hbk_hash_evict_to_n(0, None, None, 0, None))
+    _lib.check(call(0, None, None, 0, None))
     return []
   dev = tables[0].keys.device
   cols = (_lib.HashEvictToColumn * n)()
@@ -869,8 +941,223 @@ def hash_evict_to(tables, max_sizes, keep_freq=0, slots=None, reports=None):
   workspace = _EVICT_TO_WORKSPACES.get((dev, n))
   if workspace is None or workspace.numel() * 4 < nbytes:
     workspace = _EVICT_TO_WORKSPACES[(dev, n)] = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=dev)
-  _lib.check(lib.hbk_hash_evict_to_n(n, cols, workspace.data_ptr(), workspace.numel() * 4, _lib.current_stream(dev)))
+  _lib.check(call(n, cols, workspace.data_ptr(), workspace.numel() * 4, _lib.current_stream(dev)))
   return reports
+
+
+def hash_spill(tables, max_sizes, keep_freq=0, slots=None):
+  """:meth:`HashTable.spill_to` for N expiring tables: the keys :func:`hash_evict_to` with the same arguments would
+  evict leave the tables WITH their payload.  Returns one :class:`HashExport` per table, on the device, in ascending
+  slot order: keys, rows, ``last_seen``, ``freq`` and the rows of the companions as they were before the call.
+
+  ``slots[c]``: the ``(tensor, fill_value)`` pairs of table c as in :func:`hash_evict`: the tensor is exported,
+  then its evicted rows are reset to the value.
+
+  The steps: the select (:func:`hash_evict_to_select`); ONE host read of all reports; outputs allocated for exactly
+  ``n_selected`` keys per table; ``hbk_hash_spill_n`` -- count, scan and write of the export with the eviction's
+  predicate, then the sweep, which leaves a table alone whose selected keys do not all fit the output; ONE host
+  read of the counts, and a count that differs from its ``n_selected`` is refused (somebody wrote the table between
+  the two calls; a table with more keys than promised was not touched).  Must not run beside a translate, a sweep
+  or a backward of the same tables on another stream."""
+  tables = list(tables)
+  same_device(tables)
+  n = len(tables)
+  keep_freq = int(keep_freq)
+  slots, = _per_table(n, ('lists of companion tensors', slots, ()))
+  for t in tables:
+    t._need_expiring('spill_to')
+  checked = [_companions(t, slots[c]) for c, t in enumerate(tables)]
+  reports = hash_evict_to_select(tables, max_sizes, keep_freq)
+  lib = _lib.lib()
+  if n == 0:
+    _lib.check(lib.hbk_hash_spill_n(0, None, None, None))
+    return []
+  dev = tables[0].keys.device
+  selected = [r[3] for r in torch.stack(reports).tolist()]   # the one host read of the selection
+  cols = (_lib.HashSpillColumn * n)()
+  counts = torch.zeros(n, dtype=torch.int64, device=dev)
+  n_evicted = torch.zeros(n, dtype=torch.int32, device=dev)
+  outs = []
+  for c, t in enumerate(tables):
+    cap = selected[c]
+    rows = max(cap, 1)   # (never an empty allocation: a move needs an address)
+    out = {'keys': torch.empty(rows, dtype=torch.int64, device=dev),
+           'src_slots': torch.empty(rows, dtype=torch.int64, device=dev),
+           'rows': torch.empty((rows, t.dim), dtype=torch.float32, device=dev),
+           'last_seen': torch.empty(rows, dtype=torch.int32, device=dev),
+           'freq': torch.empty(rows, dtype=torch.int32, device=dev),
+           'slots': [torch.empty((rows, x.shape[1]), dtype=torch.float32, device=dev) for x, _ in checked[c]]}
+    moves = [(t.table, out['rows']), (t.last_seen, out['last_seen']), (t.freq, out['freq'])]
+    moves += [(x, y) for (x, _), y in zip(checked[c], out['slots'])]
+    col = cols[c]
+    _describe_sweep(col, t, keep_freq, checked[c])
+    col.selection = reports[c].data_ptr()
+    col.n_moves = len(moves)
+    for m, (x, y) in enumerate(moves):
+      _describe_move(col.moves[m], per_slot=x, packed=y, to_packed=True)
+    col.out_keys, col.out_slots, col.out_capacity = out['keys'].data_ptr(), out['src_slots'].data_ptr(), cap
+    col.count = counts.data_ptr() + 8 * c
+    col.n_evicted = n_evicted.data_ptr() + 4 * c
+    outs.append(out)
+  nbytes = C.c_size_t()
+  _lib.check(lib.hbk_hash_spill_workspace_bytes(n, cols, C.byref(nbytes)))
+  workspace = torch.empty(max(nbytes.value // 8, 1), dtype=torch.int64, device=dev)
+  _lib.check(lib.hbk_hash_spill_n(n, cols, workspace.data_ptr(), _lib.current_stream(dev)))
+  result = []
+  for c, (k, out) in enumerate(zip(counts.tolist(), outs)):
+    if k != selected[c]:
+      raise _bad(f'table {c}: the select promised {selected[c]} keys and the spill counted {k}: the table was '
+                 'written between the two' + (' (it was left untouched)' if k > selected[c] else ''))
+    result.append(HashExport(out['keys'][:k], out['rows'][:k], out['last_seen'][:k], out['freq'][:k],
+                             [x[:k] for x in out['slots']], out['src_slots'][:k], 0))
+  return result
+
+
+def _check_store(store, table, slots):
+  """Refuses a store that cannot take what ``table`` with the companions ``slots`` spills."""
+  if not isinstance(store, HashSpillStore):
+    raise _bad('the store must be a HashSpillStore')
+  widths = tuple(int(p[0].shape[1]) if isinstance(p, (tuple, list)) and len(p) == 2 and
+                 isinstance(p[0], torch.Tensor) and p[0].dim() == 2 else -1 for p in slots)
+  if store.dim != table.dim or store.slot_dims != widths:
+    raise _bad(f'the store holds rows of dim {store.dim} with companions of widths {list(store.slot_dims)}, the '
+               f'table has dim {table.dim} and companions of widths {list(widths)}')
+
+
+class HashSpillStore:
+  """The host tier of ONE bounded table: the keys :meth:`HashTable.spill_to` evicted, with their rows, ``last_seen``,
+  ``freq`` and companion rows, in host memory, sorted by key.  A key lives in the store or in the table, not in
+  both: :meth:`take` removes what it returns.
+
+  Args:
+    dim: floats per row of the table.
+    slot_dims: the widths of the companion tensors, in the order of the ``slots`` of ``spill_to`` / ``fault_in``.
+    pin_memory: keep the arrays in page-locked memory when a GPU is present (copies from and to the device run
+      at the link's speed).
+
+  Everything is vectorised torch (sort, ``searchsorted``, masks): no per-key Python loop; the results are a
+  function of the calls alone."""
+
+  def __init__(self, dim, slot_dims=(), pin_memory=True):
+    self.dim = int(dim)
+    self.slot_dims = tuple(int(d) for d in slot_dims)
+    if self.dim < 1 or any(d < 1 for d in self.slot_dims):
+      raise _bad(f'dim and slot_dims must be >= 1, got {dim} and {list(slot_dims)}')
+    self._pin = bool(pin_memory) and torch.cuda.is_available()
+    self.clear()
+
+  def clear(self):
+    """Forget everything."""
+    self._data = self._arrays(HashExport.empty(0, self.dim, True, self.slot_dims))
+
+  @staticmethod
+  def _arrays(exp):
+    return [exp.keys, exp.rows, exp.last_seen, exp.freq] + list(exp.slots)
+
+  def _export(self, arrays):
+    return HashExport(arrays[0], arrays[1], arrays[2], arrays[3], arrays[4:])
+
+  def _host(self, shape, dtype):
+    return torch.empty(shape, dtype=dtype, pin_memory=self._pin)
+
+  def __len__(self):
+    return self._data[0].numel()
+
+  def keys(self):
+    """The keys the store holds, ascending (a copy)."""
+    return self._data[0].clone()
+
+  def _check(self, exp):
+    if not isinstance(exp, HashExport):
+      raise _bad('put needs a HashExport')
+    n = exp.keys.numel()
+    if exp.keys.dtype != torch.int64 or exp.keys.dim() != 1:
+      raise _bad('put: exp.keys must be an int64 vector')
+    if exp.rows.dtype != torch.float32 or tuple(exp.rows.shape) != (n, self.dim):
+      raise _bad(f'put: exp.rows must be fp32 [{n}, {self.dim}], got {tuple(exp.rows.shape)}')
+    if exp.last_seen is None or exp.freq is None:
+      raise _bad('put: the export carries no last_seen / freq: a store keeps the keys of an expiring table')
+    for name in ('last_seen', 'freq'):
+      x = getattr(exp, name)
+      if x.dtype != torch.int32 or tuple(x.shape) != (n,):
+        raise _bad(f'put: exp.{name} must be int32 [{n}]')
+    if len(exp.slots) != len(self.slot_dims):
+      raise _bad(f'put: the export carries {len(exp.slots)} companion tensors, the store keeps {len(self.slot_dims)}')
+    for k, (x, d) in enumerate(zip(exp.slots, self.slot_dims)):
+      if x.dtype != torch.float32 or tuple(x.shape) != (n, d):
+        raise _bad(f'put: exp.slots[{k}] must be fp32 [{n}, {d}], got {tuple(x.shape)}')
+
+  def put(self, exp):
+    """Copy a :class:`HashExport` (of any device) to the host and upsert it by key: a key the store already holds
+    takes the new payload, as does the later of two equal keys of one export.  Widths or metadata that do not
+    match the store are refused."""
+    self._check(exp)
+    if len(exp) == 0:
+      return
+    new = []
+    for x in self._arrays(exp):
+      if x.device.type == 'cpu':
+        new.append(x)
+      else:
+        y = self._host(tuple(x.shape), x.dtype)
+        y.copy_(x, non_blocking=True)
+        new.append(y)
+    if exp.keys.device.type != 'cpu':
+      torch.cuda.current_stream(exp.keys.device).synchronize()
+    keys = torch.cat([self._data[0], new[0]])
+    order = torch.argsort(keys, stable=True)            # equal keys: the earlier entry first
+    ordered = keys[order]
+    last = torch.ones(ordered.numel(), dtype=torch.bool)
+    last[:-1] = ordered[1:] != ordered[:-1]             # the last of every run of equal keys stays
+    pick = order[last]
+    self._data = [self._gather(torch.cat([a, b]), pick) for a, b in zip(self._data, new)]
+
+  def _gather(self, x, index):
+    out = self._host((index.numel(),) + tuple(x.shape[1:]), x.dtype)
+    return torch.index_select(x, 0, index, out=out)
+
+  def _locate(self, keys):
+    """Positions in the store of the distinct requested keys it holds, ascending."""
+    if not isinstance(keys, torch.Tensor) or keys.dtype != torch.int64 or keys.dim() != 1:
+      raise _bad('keys must be an int64 vector')
+    held = self._data[0]
+    if held.numel() == 0 or keys.numel() == 0:
+      return torch.zeros(0, dtype=torch.int64)
+    wanted = torch.unique(keys.cpu())
+    pos = torch.searchsorted(held, wanted).clamp_(max=held.numel() - 1)
+    return pos[held[pos] == wanted]
+
+  def peek(self, keys):
+    """A CPU :class:`HashExport` of the requested keys the store holds, in ascending key order (duplicates in
+    ``keys`` count once; keys the store does not hold are simply not returned).  The store keeps them."""
+    pos = self._locate(keys)
+    return self._export([self._gather(x, pos) for x in self._data])
+
+  def take(self, keys):
+    """:meth:`peek`, and the returned keys leave the store."""
+    pos = self._locate(keys)
+    out = self._export([self._gather(x, pos) for x in self._data])
+    if pos.numel():
+      keep = torch.ones(len(self), dtype=torch.bool)
+      keep[pos] = False
+      rest = keep.nonzero().flatten()
+      self._data = [self._gather(x, rest) for x in self._data]
+    return out
+
+  def variables(self, name):
+    """The store's content as the flat dict ``training.saver.Saver.save`` takes (:meth:`HashExport.variables`)."""
+    return self._export(self._data).variables(name)
+
+  @classmethod
+  def from_variables(cls, name, d, pin_memory=True):
+    """The store a :meth:`variables` dict describes (:meth:`HashExport.from_variables`): dim and slot widths are
+    read from the tensors."""
+    exp = HashExport.from_variables(name, d)
+    if exp.rows.dim() != 2 or any(x.dim() != 2 for x in exp.slots):
+      raise _bad('from_variables: rows and companions must be matrices')
+    store = cls(exp.rows.shape[1], [x.shape[1] for x in exp.slots], pin_memory)
+    store.put(exp)
+    return store
 
 
 def _check_loads(max_load, target_load):
@@ -1029,11 +1316,14 @@ def grow_tables(lookup, tables, max_load, factor, slots):
   return out
 
 
-def evict_tables(lookup, tables, max_load, target_load, keep_freq, slots):
-  """:meth:`HashTable.maybe_evict` on every table, then ``lookup.rebind()`` if any was rehashed."""
-  slots, = _per_table(len(tables), ('lists of companion tensors', slots, ()))
+def evict_tables(lookup, tables, max_load, target_load, keep_freq, slots, spill=None):
+  """:meth:`HashTable.maybe_evict` on every table, then ``lookup.rebind()`` if any was rehashed.  ``spill``: one
+  :class:`HashSpillStore` per table (a single store for a single table), or None."""
+  if isinstance(spill, HashSpillStore):
+    spill = [spill]
+  slots, spill = _per_table(len(tables), ('lists of companion tensors', slots, ()), ('spill stores', spill, None))
   _check_loads(max_load, target_load)
-  out = [t.maybe_evict(max_load, target_load, keep_freq, slots[c]) for c, t in enumerate(tables)]
+  out = [t.maybe_evict(max_load, target_load, keep_freq, slots[c], spill[c]) for c, t in enumerate(tables)]
   if any(o is not None for o in out):
     lookup.rebind()
   return out
@@ -1080,11 +1370,21 @@ class HashGroupLookup:
     tensors.  See :meth:`rebind` for what must be rebuilt afterwards."""
     return grow_tables(self, self.tables, max_load, factor, slots)
 
-  def maybe_evict(self, max_load=0.75, target_load=0.5, keep_freq=0, slots=None):
-    """:meth:`HashTable.maybe_evict` on every table (``slots[c]``: the companions of table c), then
-    :meth:`rebind` if any table was rehashed.  Returns the per-table results: None, or the new companion
-    tensors.  See :meth:`rebind` for what must be rebuilt afterwards."""
-    return evict_tables(self, self.tables, max_load, target_load, keep_freq, slots)
+  def maybe_evict(self, max_load=0.75, target_load=0.5, keep_freq=0, slots=None, spill=None):
+    """:meth:`HashTable.maybe_evict` on every table (``slots[c]``: the companions of table c; ``spill``: one
+    :class:`HashSpillStore` per table, or None), then :meth:`rebind` if any table was rehashed.  Returns the
+    per-table results: None, or the new companion tensors.  See :meth:`rebind` for what must be rebuilt
+    afterwards."""
+    return evict_tables(self, self.tables, max_load, target_load, keep_freq, slots, spill)
+
+  def fault_in(self, ids, stores, slots=None):
+    """:meth:`HashTable.fault_in` per table, before the call of the step: ``ids[c]`` the raw ids of column c,
+    ``stores[c]`` its :class:`HashSpillStore`, ``slots[c]`` its companion tensors.  The row tensors do not move, so
+    no :meth:`rebind` is needed.  Returns the keys restored per table."""
+    n = len(self.tables)
+    ids, stores, slots = _per_table(n, ('id tensors', ids, None), ('spill stores', stores, None),
+                                    ('lists of companion tensors', slots, ()))
+    return [t.fault_in(ids[c], stores[c], slots[c]) for c, t in enumerate(self.tables)]
 
   def __len__(self):
     return len(self.tables)

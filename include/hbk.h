@@ -859,6 +859,20 @@ size_t hbk_hash_evict_to_workspace_bytes(int32_t n_cols);
 int hbk_hash_evict_to_n(int32_t n_cols, const hbk_hash_evict_to_column_t* cols, void* workspace,
                         size_t workspace_bytes, hbk_stream_t stream);
 
+/* The selection alone: hbk_hash_evict_to_n without its sweep.  Same struct, same argument checks and refusal texts
+ * (under the name hash_evict_to_select_n), same workspace (hbk_hash_evict_to_workspace_bytes), the same clear
+ * launch and three digit passes -- and no sweep: the table's arrays, its stats and its companions are NOT WRITTEN
+ * (the fills are checked and not used).  report is required here (NULL is refused) and receives
+ *     {live_before, need, cut, n_selected}
+ * live_before, need and cut as above (cut = 0 when need <= 0, INT32_MAX when fewer than `need` slots are
+ * evictable); n_selected is the exact number of slots the sweep of hbk_hash_evict_to_n would evict from the table
+ * as it is: 0 when need <= 0, else the evictable slots with last_seen <= cut -- all evictable slots when cut =
+ * INT32_MAX.  It falls out of the select: the need consumed before the last chosen bin plus that bin's count.  No
+ * host read, capturable; the report is what hbk_hash_spill_n (below, behind the export) takes as its selection.
+ * hbk_hash_evict_to_n itself is unchanged: the fourth word of its report stays the sweep's own count. */
+int hbk_hash_evict_to_select_n(int32_t n_cols, const hbk_hash_evict_to_column_t* cols, void* workspace,
+                               size_t workspace_bytes, hbk_stream_t stream);
+
 /* Admission filter: a count-min sketch gates new ids (DeepRec's CounterFilter / CBFFilter beside
  * steps_to_live).  Most distinct ids of a click log occur once or twice; unfiltered, each of them claims a row,
  * its optimizer slots and a key slot at first sight.  A filtered table stores an id once it was seen min_freq
@@ -1177,6 +1191,73 @@ typedef struct {
   hbk_hash_move_t moves[HBK_HASH_MAX_MOVES];   /* src: the packed array; dst: the per-slot array */
 } hbk_hash_store_column_t;
 int hbk_hash_store_rows_n(int32_t n_cols, const hbk_hash_store_column_t* cols, hbk_stream_t stream);
+
+/* Spilling: export exactly the keys an eviction removes, then remove them (the reference's EmbeddingService keeps a
+ * device cache in front of a larger store and pushes out what it evicts: service.py:153-283).  The evicted keys
+ * leave with their rows, their age and count and their optimizer slots, for a host tier to keep; a later import
+ * (the table's translate entry and hbk_hash_store_rows_n) brings them back as they left.
+ *
+ * hbk_hash_spill_n, N expiring tables per call (32 per launch), four launches per 32 tables on the call's stream.
+ *
+ * Selection.  `selection` is a device int32[4] as hbk_hash_evict_to_select_n writes it: {live_before, need, cut,
+ * n_selected}.  It is READ FROM DEVICE MEMORY by the launches: there is no host read anywhere in the call, and it
+ * may be stream-ordered right behind the select.  Slot s is SELECTED iff ALL of
+ *     keys_cache[s] holds a key (neither EMPTY nor TOMBSTONE)
+ *     keep_freq == 0  or  freq[s] < keep_freq
+ *     selection[1] > 0            (the need: with need <= 0 the report's cut is 0 and last_seen may well be <= 0,
+ *                                  so the need is tested and not only the cut)
+ *     last_seen[s] <= selection[2]   as SIGNED int32
+ * -- with the keep_freq of the select, exactly the slots hbk_hash_evict_to_n would evict.  selection[0] and [3] are
+ * not read.
+ *
+ * Launches 1-3 are the count, scan and write of hbk_hash_export_n with this predicate, and the contract is that
+ * entry's: the selected keys in ASCENDING SOURCE-SLOT ORDER packed from position 0, out_slots (if not NULL) their
+ * source slots, every move a bit-for-bit copy (dst[p * dst_pitch + j] = src[s * src_pitch + j], the 16-byte rule
+ * as there), nothing written at positions >= out_capacity, *count = the total number of selected slots whatever
+ * the capacity; plain loads and stores, no atomics.  *n_evicted (if not NULL) is zeroed by the scan launch, so a
+ * captured call replays.
+ *
+ * Launch 4 is the eviction sweep with the same predicate: what hbk_hash_evict_to_n's sweep does -- key =
+ * TOMBSTONE, last_seen = freq = 0, the rows of the n_fills companions = their value, stats[0] (if not NULL) and
+ * *n_evicted (if not NULL) += the slots evicted.  ALL OR NOTHING per table: the sweep is guarded by
+ * *count <= out_capacity.  A table whose selected keys do not all fit its output is left completely untouched and
+ * its n_evicted stays 0: nothing leaves the table that was not exported in full.  The kernel boundary between
+ * launches 3 and 4 orders the copies before the resets; a move's src may therefore be a fill's array (an
+ * optimizer slot is exported, then reset).
+ *
+ * If the table changed between the select and the spill the call is still self-consistent -- it evicts exactly
+ * what it exports -- just a different set than the select counted: *count says how many.  The table's arrays must
+ * not be written by anyone else during the call.
+ *
+ * Workspace: hbk_hash_spill_workspace_bytes(n_cols, cols, &bytes) reads the geometry of the columns only (8 bytes
+ * per 256 slots); one device pointer, 8-byte aligned, not kept after the call.  No host synchronisation:
+ * capturable.
+ *
+ * Refused (HBK_INVALID_ARGUMENT) before any device work: what hbk_hash_evict_to_n refuses of keys_cache,
+ * slab_count, slab_size (a table of 2^31 slots or more included) and the fills; NULL last_seen, freq, selection or
+ * count; keep_freq < 0; everything hbk_hash_rehash_n refuses of a move; out_capacity < 0; NULL out_keys with
+ * out_capacity > 0; a NULL (or not 8-byte aligned) workspace with n_cols > 0.  exp.step is not read, exp.stats may
+ * be NULL.  n_cols == 0 returns HBK_OK without touching a device.  Detected by the presence of the symbols; the
+ * version stays that of 0.2.0. */
+typedef struct {
+  int64_t* keys_cache;      /* device [slab_count * slab_size], 8-byte aligned */
+  int64_t slab_count;
+  int32_t slab_size;        /* 1..64 */
+  hbk_hash_expiry_t exp;    /* last_seen and freq are required; step is not read; stats may be NULL */
+  const int32_t* selection; /* device int32[4] {live_before, need, cut, n_selected} of hbk_hash_evict_to_select_n */
+  int32_t keep_freq;        /* >= 0; 0: frequency keeps nothing.  The select's */
+  int32_t n_moves;          /* 0..HBK_HASH_MAX_MOVES */
+  hbk_hash_move_t moves[HBK_HASH_MAX_MOVES];   /* src: the per-slot array; dst: the packed array */
+  int32_t n_fills;          /* 0..HBK_HASH_MAX_FILLS */
+  hbk_hash_fill_t fills[HBK_HASH_MAX_FILLS];   /* the companions the sweep resets */
+  int64_t* out_keys;        /* device int64 [out_capacity] */
+  int64_t* out_slots;       /* device int64 [out_capacity] or NULL */
+  int64_t out_capacity;     /* >= 0: rows of out_keys, out_slots and every move's dst */
+  int64_t* count;           /* device int64[1]: the total number of selected slots */
+  int32_t* n_evicted;       /* device int32[1]: the slots the sweep evicted (0 when the guard held it back); or NULL */
+} hbk_hash_spill_column_t;
+int hbk_hash_spill_workspace_bytes(int32_t n_cols, const hbk_hash_spill_column_t* cols, size_t* bytes);
+int hbk_hash_spill_n(int32_t n_cols, const hbk_hash_spill_column_t* cols, void* workspace, hbk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Communicator lifecycle: HbGetNcclId / HbCreateNcclCollective /
