@@ -37,6 +37,13 @@ Per-key values are order-free: a new row is a function of (key, seed, column); `
 for every id the call resolved; ``freq`` grows by the id's occurrences (an atomic add per occurrence; the ceiling of
 2^30 is out of reach here).
 
+The size bound, the host tier, export / import and the sequence translate are order-free as well: the selection
+of ``evict_to`` / ``spill_to`` is a function of the per-key ``last_seen`` and ``freq``; an export is a function of the
+table's arrays (its ``src_slots`` are not predicted, only checked against the key array); a ``fault_in`` and an
+import go through the insert without the filter, so the D / F argument above holds for them with D = the distinct
+keys not stored; a sequence translate is a translate of its effective id list.  ``Model.store`` is what the table's
+``HashSpillStore`` holds.
+
 Events (``Events``) are computed from the model and the geometry alone -- pigeonhole bounds where a layout fact is
 wanted: more stored keys homing to one slab than it has slots means one of them overflowed; more new keys than the
 table can still have EMPTY slots means a tombstone was reused.  The one exception is "an id found behind a
@@ -48,9 +55,12 @@ import ctypes as C
 import numpy as np
 
 from tests.support import hash_admission_ref as aref
+from tests.support import hash_evict_to_ref as tref
 from tests.support import hash_expiry_ref as xref
+from tests.support import hash_export_ref as pref
 from tests.support import hash_ref as ref
 from tests.support import hash_rehash_ref as rref
+from tests.support import hash_spill_ref as sref
 
 EMPTY = ref.EMPTY
 TOMBSTONE = EMPTY + 1
@@ -58,10 +68,22 @@ KINDS = ('plain', 'expiring', 'admit', 'expiring_admit')
 SLAB_SIZES = (1, 5, 8, 16, 33, 64)
 SLAB_COUNTS = (1, 3, 20, 257)
 MAX_CAPACITY = 1300
+INT32_MAX = tref.INT32_MAX
 SEEDS = tuple(range(10))   # chosen so that the conditions of tests/test_hash_lifecycle_model.py hold
-EVENTS = ('overflow', 'eviction', 'reused', 'behind_tombstone', 'exact_admission', 'early_admission', 'growth',
-          'rehash_sheds_tombstones', 'fills_last_slot', 'empty_run')
-_EXPIRING_EVENTS = ('eviction', 'reused', 'behind_tombstone', 'rehash_sheds_tombstones')
+TIER_SEEDS = (11, 18, 21, 22, 26, 49, 54)   # the same, for the sequences that also draw the later operations;
+# none of them is one of SEEDS: a seed fixes its fleet, so these put the later operations on seven further fleets
+BASE_EVENTS = ('overflow', 'eviction', 'reused', 'behind_tombstone', 'exact_admission', 'early_admission', 'growth',
+               'rehash_sheds_tombstones', 'fills_last_slot', 'empty_run')
+# the size bound, the host tier, export / import and the sequence translate (drawn only by the TIER_SEEDS)
+TIER_EVENTS = ('cut_inside_a_step', 'keep_freq_holds_the_bound', 'bound_already_met', 'spill', 'fault_in',
+               'fault_in_onto_tombstone', 'respill', 'fresh_over_store', 'delta_is_a_proper_subset',
+               'export_after_rehash', 'import_overwrites_stored', 'import_inserts', 'import_by_owner',
+               'sequence_truncates', 'sequence_pads', 'sequence_on_tombstones')
+EVENTS = BASE_EVENTS + TIER_EVENTS
+_EXPIRING_EVENTS = ('eviction', 'reused', 'behind_tombstone', 'rehash_sheds_tombstones', 'cut_inside_a_step',
+                    'keep_freq_holds_the_bound', 'bound_already_met', 'spill', 'fault_in', 'fault_in_onto_tombstone',
+                    'respill', 'fresh_over_store', 'delta_is_a_proper_subset', 'sequence_on_tombstones',
+                    'import_inserts')   # (no key ever leaves a table that does not expire: its snapshots hold nothing new)
 _FILTER_EVENTS = ('exact_admission', 'early_admission')
 
 
@@ -160,6 +182,10 @@ class Record:
   def __init__(self, row, last_seen, freq, comps):
     self.row, self.last_seen, self.freq, self.comps = row, last_seen, freq, comps
 
+  def copy(self):
+    return Record(np.array(self.row, np.float32), self.last_seen, self.freq,
+                  [np.array(c, np.float32) for c in self.comps])
+
 
 class Model:
   """One table, free of slot numbers (the module docstring says what it may predict)."""
@@ -182,6 +208,12 @@ class Model:
     self.nonempty_lb = 0          # slots that are certainly not EMPTY
     self.tomb_lb = 0              # tombstones the table certainly holds
     self.own = {}                 # id -> its own sightings the sketch carries
+    # the host tier, the snapshots and what their events need
+    self.store = {}               # key -> Record: what a HashSpillStore of this table holds (put is an upsert)
+    self.returned = set()         # keys a fault_in brought back
+    self.snapshots = []           # (version when taken, {key: Record}) per export, in order
+    self.version = 0              # state-changing operations so far (kept by the Runner: `fingerprint`)
+    self.rehashed = False         # a rehash or compact ran since the last export
 
   @property
   def capacity(self):
@@ -298,6 +330,7 @@ class Model:
     mask = xref.evict_mask(keys, seen, freq, self.step, steps_to_live, keep_freq)
     for k in keys[mask].tolist():
       del self.stored[k]       # its metadata and companion rows go with it: the slot's are zeroed / filled
+    self.returned -= set(keys[mask].tolist())
     n = int(mask.sum())
     self.evicted += n
     self.tomb_lb += n
@@ -316,6 +349,7 @@ class Model:
     self.counts[0] = len(self.stored)
     self.evicted = self.reused_seen = 0
     self.nonempty_lb, self.tomb_lb = len(self.stored), 0
+    self.rehashed = True
 
   def compact(self):
     """The host path: the same table in the same geometry, tombstones gone, stats reset, size() and failed() kept."""
@@ -353,6 +387,172 @@ class Model:
       rec = self.stored[k]
       rec.row = np.array(rows[n], np.float32)
       rec.comps = [np.array(c[n], np.float32) for c in comp_rows]
+
+  # ---- the size bound and the host tier ----------------------------------------------------------------------
+  def select(self, max_size, keep_freq):
+    """(report without its last word, the keys that leave) of ``evict_to`` / ``spill_to``: ``need = size() -
+    max_size``; the cut is the need-th smallest last_seen among the keys seen fewer than keep_freq times (all of
+    them with keep_freq 0), INT32_MAX when they are fewer than need; every such key at or below the cut leaves."""
+    assert self.expiring
+    live = len(self.stored)
+    need = live - int(max_size)
+    if need <= 0:
+      return [live, need, 0], []
+    able = [(rec.last_seen, k) for k, rec in self.stored.items() if keep_freq == 0 or rec.freq < keep_freq]
+    cut = sorted(a for a, _ in able)[need - 1] if len(able) >= need else INT32_MAX
+    return [live, need, cut], [k for a, k in able if a <= cut]
+
+  def _bound_events(self, report, max_size):
+    live, need, cut, n = report
+    events = set()
+    if need <= 0:
+      events.add('bound_already_met')
+    else:
+      if live - n < max_size:
+        events.add('cut_inside_a_step')
+      if cut == INT32_MAX or live - n > max_size:
+        events.add('keep_freq_holds_the_bound')
+    return events
+
+  def evict_to(self, max_size, keep_freq):
+    """Returns (report {live_before, need, cut, n_evicted}, events); the bookkeeping is ``evict``'s."""
+    head, leaving = self.select(max_size, keep_freq)
+    for k in leaving:
+      del self.stored[k]
+    self.returned -= set(leaving)
+    self.evicted += len(leaving)
+    self.tomb_lb += len(leaving)
+    report = head + [len(leaving)]
+    return report, self._bound_events(report, max_size)
+
+  def spill(self, max_size, keep_freq):
+    """``evict_to`` whose keys leave with their records into the store.  Returns ({key: Record} of the export,
+    events)."""
+    head, leaving = self.select(max_size, keep_freq)
+    events = self._bound_events(head + [len(leaving)], max_size)
+    out = {}
+    for k in leaving:
+      out[k] = self.stored.pop(k)
+      if k in self.returned:
+        events.add('respill')
+      if k in self.store:           # it came back fresh, by a translate, a load or an import: the store upserts
+        events.add('fresh_over_store')
+      self.store[k] = out[k].copy()
+    self.returned -= set(leaving)
+    self.evicted += len(leaving)
+    self.tomb_lb += len(leaving)
+    if leaving:
+      events.add('spill')
+    return out, events
+
+  def wanted(self, ids):
+    """The keys a ``fault_in(ids)`` asks the store for and gets: distinct, no sentinel, not stored, in the store."""
+    ids = np.asarray(ids, np.int64)
+    uniq = np.unique(ids[~self.sentinel_mask(ids)])
+    return [k for k in uniq.tolist() if k not in self.stored and k in self.store]
+
+  def fault_in(self, ids, now=None):
+    """The wanted keys come back with their whole record and leave the store; nothing is stamped, the filter and
+    the sketch are not touched.  With more of them than free slots the call raises after storing exactly F of
+    them -- which F is the device's choice: `now`, the device's key array afterwards, is then read and the subset
+    adopted; the others stay in the store and each counts as one failed occurrence.  Returns (keys restored,
+    whether the call raises, events)."""
+    want = self.wanted(ids)
+    F = self.free()
+    came = want
+    if len(want) > F:
+      assert now is not None, 'which keys of a fault_in that does not fit came in is the device\'s choice'
+      held = set(np.asarray(now, np.int64).tolist())
+      came = [k for k in want if k in held]
+      assert len(came) == F, f'{len(want)} keys wanted, {F} free slots: {len(came)} came in, not {F}'
+    events = set()
+    for k in came:
+      self.stored[k] = self.store.pop(k)
+    self.returned |= set(came)
+    self.counts[0] += len(came)
+    self.counts[1] += len(want) - len(came)
+    if came:
+      events.add('fault_in')
+      if len(came) > self.capacity - self.nonempty_lb:
+        events.add('fault_in_onto_tombstone')
+    self.nonempty_lb = max(self.nonempty_lb, len(self.stored))
+    self.tomb_lb = max(0, self.tomb_lb - len(came))
+    return len(came), len(want) > F, events
+
+  # ---- export and import ---------------------------------------------------------------------------------
+  def export(self, since=None):
+    """{key: Record} of every key (since None), or of the keys with last_seen >= since (expiring kinds); the
+    table does not change.  The snapshot is kept.  Returns (snapshot, events)."""
+    assert since is None or self.expiring
+    take = {k: r.copy() for k, r in self.stored.items() if since is None or r.last_seen >= since}
+    events = set()
+    if since is not None and 0 < len(take) < len(self.stored):
+      events.add('delta_is_a_proper_subset')
+    if self.rehashed and take:
+      events.add('export_after_rehash')
+    self.rehashed = False
+    self.snapshots.append((self.version, take))
+    return take, events
+
+  def owned(self, keys, world, rank):
+    keys = np.asarray(keys, np.int64)
+    return np.ones(keys.size, bool) if world is None else np.mod(keys, world) == rank   # (numpy's % is a floormod)
+
+  def import_(self, snapshot, world=None, rank=None, with_meta=True):
+    """An upsert of {key: Record}: a stored key takes row and companions; on an expiring table last_seen and freq
+    come from the snapshot with `with_meta`, else the key counts as seen now (last_seen = step; freq + 1, or 1
+    when new).  A plain kind has no metadata.  Returns (the keys imported, events)."""
+    keys = np.array(sorted(snapshot), np.int64)
+    mine = keys[self.owned(keys, world, rank)]
+    events = set()
+    new = 0
+    for k in mine.tolist():
+      src, rec = snapshot[k], self.stored.get(k)
+      if rec is None:
+        rec = self.stored[k] = self._new_record(k, src.row, 1)
+        new += 1
+        events.add('import_inserts')
+      else:
+        events.add('import_overwrites_stored')
+        rec.row = np.array(src.row, np.float32)
+        if self.expiring:
+          rec.last_seen, rec.freq = self.step, rec.freq + 1
+      rec.comps = [np.array(c, np.float32) for c in src.comps]
+      if self.expiring and with_meta:
+        rec.last_seen, rec.freq = src.last_seen, src.freq
+    assert len(self.stored) <= self.capacity
+    if world is not None and 0 < mine.size < keys.size:
+      events.add('import_by_owner')
+    self.counts[0] += new
+    self.nonempty_lb = max(self.nonempty_lb, len(self.stored))
+    self.tomb_lb = max(0, self.tomb_lb - new)
+    return mine, events
+
+  def fingerprint(self):
+    """Everything an export of the table could tell, and its geometry."""
+    out = [np.array([self.slab_size, self.slab_count], np.int64).tobytes()]
+    for k in sorted(self.stored):
+      r = self.stored[k]
+      out.append(np.array([k, r.last_seen, r.freq], np.int64).tobytes() + r.row.tobytes() +
+                 b''.join(c.tobytes() for c in r.comps))
+    return hash(b''.join(out))
+
+
+def effective_ids(ids, row_splits, max_len, pad_id):
+  """What a sequence translate looks up: per sample its first min(len, T) ids, then T - len pad ids when a pad id
+  is given.  Returns (the ids, their positions b * T + t in the grid, lengths = min(len, T))."""
+  ids = np.asarray(ids, np.int64)
+  splits = np.arange(ids.size + 1) if row_splits is None else np.asarray(row_splits, np.int64)
+  lens = np.minimum(np.diff(splits), max_len).astype(np.int64)
+  out, at = [], []
+  for b, (start, n) in enumerate(zip(splits[:-1].tolist(), lens.tolist())):
+    out.append(ids[start:start + n])
+    at.append(b * max_len + np.arange(n))
+    if pad_id is not None and n < max_len:
+      out.append(np.full(max_len - n, pad_id, np.int64))
+      at.append(b * max_len + np.arange(n, max_len))
+  cat = lambda x, t: np.concatenate(x).astype(t) if x else np.zeros(0, t)
+  return cat(out, np.int64), cat(at, np.int64), lens.astype(np.int32)
 
 
 # ---- the numpy device: the sequential restatements behind the attributes of a HashTable -----------------------
@@ -488,6 +688,46 @@ class NumpyTable:
   def clear_filter(self):
     self.sketch[:] = 0
 
+  def evict_to(self, max_size, keep_freq, companions):
+    report, _ = tref.evict_to(self.keys, self.last_seen, self.freq, max_size, keep_freq,
+                              [(a, a.shape[1], v) for a, v in companions])
+    self.stats[0] += int(report[3])
+    return report
+
+  def spill(self, max_size, keep_freq, companions):
+    """The select, then the spill of exactly the selected keys: the export, in ascending slot order."""
+    selection = sref.select(self.keys, self.last_seen, self.freq, max_size, keep_freq)
+    moves = [(self.table, self.dim), (self.last_seen, 1), (self.freq, 1)] + [(a, a.shape[1]) for a, _ in companions]
+    exp, after, n_evicted, count = sref.spill(self.keys, self.last_seen, self.freq, selection, keep_freq, moves,
+                                              [(a, a.shape[1], v) for a, v in companions], int(selection[3]))
+    assert n_evicted == count == int(selection[3])
+    self.keys[:], self.last_seen[:], self.freq[:] = after['cache'], after['last_seen'], after['freq']
+    for (a, _), b in zip(companions, after['companions']):
+      a[:] = b
+    self.stats[0] += n_evicted
+    return {'keys': exp['keys'], 'src_slots': exp['src_slots'], 'rows': exp['moves'][0], 'last_seen': exp['moves'][1],
+            'freq': exp['moves'][2], 'comps': exp['moves'][3:]}
+
+  def export(self, since, companions):
+    arrays = [self.table] + ([self.last_seen, self.freq] if self.expiring else []) + [a for a, _ in companions]
+    _, keys, slots, packed = pref.export(self.keys, self.expiring, arrays, self.last_seen,
+                                         0 if since is None else max(int(since), 0))
+    meta = packed[1:3] if self.expiring else [None, None]
+    return {'keys': keys, 'src_slots': slots, 'rows': packed[0], 'last_seen': meta[0], 'freq': meta[1],
+            'comps': packed[3:] if self.expiring else packed[1:]}
+
+  def store_items(self, exp, companions, meta):
+    """What ``import_items`` does with keys that passed its checks: the insert without the filter and without row
+    initialisation, then the stores at the slots that were found.  Returns the slots."""
+    slots = self._insert(exp['keys'], admit=False, init=False)
+    ok = slots >= 0
+    self.table[slots[ok]] = exp['rows'][ok]
+    if meta and self.expiring:
+      self.last_seen[slots[ok]], self.freq[slots[ok]] = exp['last_seen'][ok], exp['freq'][ok]
+    for (a, _), rows in zip(companions, exp['comps']):
+      a[slots[ok]] = rows[ok]
+    return slots
+
 
 def reachable(keys, slab_size, wanted, slots):
   """For keys `wanted` sitting in `slots` of the key array: whether no slab on the walk from the key's home slab
@@ -545,10 +785,99 @@ def _probe(table, ids):
   return host(cache.probe(table.keys, _like(table, ids), table.slab_size)[0])
 
 
-def check(table, model, companions):
+def same_state(before, after, what):
+  """Two readings of ``_state``: bit for bit the same."""
+  assert before.keys() == after.keys()
+  for name, a in before.items():
+    np.testing.assert_array_equal(bits(a) if a.dtype == np.float32 else a,
+                                  bits(after[name]) if a.dtype == np.float32 else after[name],
+                                  err_msg=f'{what} changed {name}')
+
+
+def export_arrays(exp):
+  """A ``HashExport`` as a dict of numpy arrays."""
+  return {'keys': host(exp.keys), 'src_slots': None if exp.src_slots is None else host(exp.src_slots),
+          'rows': host(exp.rows), 'last_seen': None if exp.last_seen is None else host(exp.last_seen),
+          'freq': None if exp.freq is None else host(exp.freq), 'comps': [host(x) for x in exp.slots]}
+
+
+def as_export(arrays, device='cpu', meta=True, take=None):
+  """The ``HashExport`` of such a dict (its rows `take`; without last_seen / freq when not `meta`)."""
+  import torch
+  from hybridbackend_amd.embedding.hashtable import HashExport
+
+  def t(a):
+    return torch.from_numpy(np.ascontiguousarray(a if take is None else a[take])).to(device)
+  meta = meta and arrays['last_seen'] is not None
+  return HashExport(t(arrays['keys']), t(arrays['rows']), t(arrays['last_seen']) if meta else None,
+                    t(arrays['freq']) if meta else None, [t(c) for c in arrays['comps']])
+
+
+def check_payload(model, got, want, what):
+  """The arrays of an export (or of a store's ``peek``) against {key: Record}: the same key set, and per key the
+  row, last_seen, freq and every companion row bit for bit."""
+  keys = got['keys']
+  assert keys.dtype == np.int64 and keys.ndim == 1
+  assert np.unique(keys).size == keys.size, f'{what}: a key twice'
+  np.testing.assert_array_equal(np.sort(keys), np.array(sorted(want), np.int64), err_msg=f'{what}: the keys')
+  recs = [want[k] for k in keys.tolist()]
+  assert got['rows'].dtype == np.float32 and got['rows'].shape == (keys.size, model.dim)
+  np.testing.assert_array_equal(bits(got['rows']),
+                                bits(np.array([r.row for r in recs], np.float32).reshape(keys.size, model.dim)),
+                                err_msg=f'{what}: rows')
+  if model.expiring:
+    for name in ('last_seen', 'freq'):
+      assert got[name].dtype == np.int32 and got[name].shape == (keys.size,)
+      np.testing.assert_array_equal(got[name], np.array([getattr(r, name) for r in recs], np.int32),
+                                    err_msg=f'{what}: {name}')
+  else:
+    assert got['last_seen'] is None and got['freq'] is None
+  assert len(got['comps']) == len(model.comp_specs)
+  for n, (w, _) in enumerate(model.comp_specs):
+    assert got['comps'][n].dtype == np.float32 and got['comps'][n].shape == (keys.size, w)
+    np.testing.assert_array_equal(bits(got['comps'][n]),
+                                  bits(np.array([r.comps[n] for r in recs], np.float32).reshape(keys.size, w)),
+                                  err_msg=f'{what}: companion {n}')
+
+
+def check_export(model, got, want, keys_before, what):
+  """An export or a spill: ``check_payload``, and src_slots -- not predicted, but strictly ascending, and the key
+  array before the call held exactly these keys at these slots."""
+  check_payload(model, got, want, what)
+  src = got['src_slots']
+  assert src.dtype == np.int64 and src.shape == got['keys'].shape
+  assert (np.diff(src) > 0).all(), f'{what}: src_slots are not strictly ascending'
+  assert src.size == 0 or (0 <= src[0] and src[-1] < keys_before.size)
+  np.testing.assert_array_equal(keys_before[src], got['keys'], err_msg=f'{what}: the keys were not at src_slots')
+
+
+def check_report(got, want, what):
+  """{live_before, need, cut, n_evicted}, exactly."""
+  got = np.asarray(got)
+  assert got.dtype == np.int32 and got.shape == (4,)
+  assert got.tolist() == list(want), f'{what}: the report is {got.tolist()}, not {list(want)}'
+
+
+def check_store(store, model):
+  """A ``HashSpillStore`` against ``Model.store``: the same keys, ascending, the payload bit for bit through
+  ``peek`` -- and the peek changed nothing."""
+  import torch
+  assert model.expiring
+  want = np.array(sorted(model.store), np.int64)
+  before = {k: host(v) for k, v in store.variables('s').items()}
+  assert len(store) == want.size, f'the store holds {len(store)} keys, the model\'s {want.size}'
+  np.testing.assert_array_equal(host(store.keys()), want, err_msg='the store\'s keys')
+  wanted = np.concatenate([want[::-1], want[:3]])   # (any order, duplicates: peek answers ascending, once each)
+  got = export_arrays(store.peek(torch.from_numpy(wanted)))
+  np.testing.assert_array_equal(got['keys'], want, err_msg='peek\'s keys')
+  check_payload(model, got, model.store, 'the store')
+  same_state(before, {k: host(v) for k, v in store.variables('s').items()}, 'a peek')
+
+
+def check(table, model, companions, store=None):
   """The table (a ``HashTable`` or a ``NumpyTable``) and its companion arrays against the model: keys, reachability
-  by every reader, per-key and per-free-slot values bit for bit, the counters and the sketch; and that the finds it
-  makes change nothing."""
+  by every reader, per-key and per-free-slot values bit for bit, the counters and the sketch; that the finds it
+  makes change nothing; and the table's ``HashSpillStore`` against the model's."""
   s = _state(table, companions)
   keys, ss, sc = s['keys'], table.slab_size, table.slab_count
   assert (ss, sc, keys.size) == (model.slab_size, model.slab_count, model.capacity)
@@ -578,8 +907,9 @@ def check(table, model, companions):
   np.testing.assert_array_equal(bits(s['table'][slot_of]), bits(rows), err_msg='rows')
   free = ~live
   if model.expiring:
-    np.testing.assert_array_equal(s['last_seen'][slot_of], np.array([r.last_seen for r in recs], np.int32))
-    np.testing.assert_array_equal(s['freq'][slot_of], np.array([r.freq for r in recs], np.int32))
+    np.testing.assert_array_equal(s['last_seen'][slot_of], np.array([r.last_seen for r in recs], np.int32),
+                                  err_msg='last_seen')
+    np.testing.assert_array_equal(s['freq'][slot_of], np.array([r.freq for r in recs], np.int32), err_msg='freq')
     assert not s['last_seen'][free].any() and not s['freq'][free].any(), 'metadata in a slot without a key'
   for n, (w, value) in enumerate(model.comp_specs):
     c = s[f'companion{n}']
@@ -605,11 +935,9 @@ def check(table, model, companions):
     assert s['filter_counts'].tolist() == [model.filtered]
     assert table.filtered() == model.filtered
   # the finds above changed nothing
-  again = _state(table, companions)
-  for name, a in s.items():
-    np.testing.assert_array_equal(bits(a) if a.dtype == np.float32 else a,
-                                  bits(again[name]) if a.dtype == np.float32 else again[name],
-                                  err_msg=f'a find changed {name}')
+  same_state(s, _state(table, companions), 'a find')
+  if store is not None:
+    check_store(store, model)
   return s
 
 
@@ -626,11 +954,19 @@ def check_slots(ids, slots, stored, keys):
 
 
 # ---- fleets: the two sides behind one set of operations ---------------------------------------------------------
+def make_stores(specs, pin_memory):
+  """One real ``HashSpillStore`` per expiring table, None for the others."""
+  from hybridbackend_amd.embedding.hashtable import HashSpillStore
+  return [HashSpillStore(s.dim, [w for w, _ in s.comps], pin_memory=pin_memory) if s.expiring else None
+          for s in specs]
+
+
 class NumpyFleet:
   def __init__(self, specs, order=None):
     self.tables = [NumpyTable(s, order) for s in specs]
     self.comps = [[np.full((s.capacity, w), v, np.float32) for w, v in s.comps] for s in specs]
     self.fills = [[v for _, v in s.comps] for s in specs]
+    self.stores = make_stores(specs, pin_memory=False)
 
   def pairs(self, i):
     return list(zip(self.comps[i], self.fills[i]))
@@ -673,9 +1009,64 @@ class NumpyFleet:
     for c, r in zip(self.comps[i], comp_rows):
       c[slots] = r
 
+  def evict_to(self, idx, max_sizes, keep_freq):
+    return [self.tables[i].evict_to(m, keep_freq, self.pairs(i)) for i, m in zip(idx, max_sizes)]
+
+  def spill(self, idx, max_sizes, keep_freq):
+    out = []
+    for i, m in zip(idx, max_sizes):
+      exp = self.tables[i].spill(m, keep_freq, self.pairs(i))
+      if exp['keys'].size:
+        self.stores[i].put(as_export(exp))
+      out.append(exp)
+    return out
+
+  def fault_in(self, i, ids):
+    """``HashTable.fault_in`` restated: a find, the distinct misses, ``store.take``, the import; what did not fit
+    goes back into the store.  Returns (keys restored, whether the call raises)."""
+    import torch
+    t, store = self.tables[i], self.stores[i]
+    ids = np.asarray(ids, np.int64)
+    missed = np.unique(ids[t.find(ids) < 0])
+    if missed.size == 0 or len(store) == 0:
+      return 0, False
+    exp = export_arrays(store.take(torch.from_numpy(missed)))
+    if exp['keys'].size == 0:
+      return 0, False
+    slots = t.store_items(exp, self.pairs(i), meta=True)
+    lost = np.nonzero(slots < 0)[0]
+    if lost.size:
+      store.put(as_export(exp, take=lost))
+      return None, True
+    return int(exp['keys'].size), False
+
+  def export(self, idx, sinces):
+    return [self.tables[i].export(since, self.pairs(i)) for i, since in zip(idx, sinces)]
+
+  def import_(self, i, exp, take, world, rank, with_meta):
+    exp = {k: (None if v is None else [c[take] for c in v] if k == 'comps' else v[take]) for k, v in exp.items()}
+    mine = np.ones(exp['keys'].size, bool) if world is None else np.mod(exp['keys'], world) == rank
+    exp = {k: (None if v is None else [c[mine] for c in v] if k == 'comps' else v[mine]) for k, v in exp.items()}
+    slots = self.tables[i].store_items(exp, self.pairs(i), meta=with_meta)
+    assert (slots >= 0).all()
+    return slots
+
+  def translate_sequence(self, idx, ids, row_splits, max_lens, pad_ids, insert):
+    """Through the effective id list: (grids, lengths)."""
+    grids, lengths = [], []
+    for i, x, s, T, pad in zip(idx, ids, row_splits, max_lens, pad_ids):
+      eff, at, lens = effective_ids(x, s, T, pad)
+      grid = np.full(lens.size * T, -1, np.int64)
+      grid[at] = self.tables[i]._insert(eff) if insert else self.tables[i].find(eff)
+      grids.append(grid)
+      lengths.append(lens)
+    return grids, lengths
+
 
 class DeviceFleet:
-  """``HashTable``s on the GPU; fleet-wide calls go through hash_translate / hash_evict / hash_rehash."""
+  """``HashTable``s on the GPU; fleet-wide calls go through hash_translate (or the runs entry) / hash_evict /
+  hash_rehash / hash_evict_to / hash_spill / hash_export / hash_translate_sequence, several tables of mixed kinds
+  per call; fault_in and import_items are per-table entries and are called per table."""
 
   def __init__(self, specs, device='cuda:0'):
     import torch
@@ -687,6 +1078,7 @@ class DeviceFleet:
     self.comps = [[torch.full((s.capacity, w), v, dtype=torch.float32, device=device) for w, v in s.comps]
                   for s in specs]
     self.fills = [[v for _, v in s.comps] for s in specs]
+    self.stores = make_stores(specs, pin_memory=True)
 
   def dev(self, a):
     return self.torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
@@ -749,6 +1141,44 @@ class DeviceFleet:
     self.tables[i].table[at] = self.dev(rows)
     for c, r in zip(self.comps[i], comp_rows):
       c[at] = self.dev(r)
+
+  def evict_to(self, idx, max_sizes, keep_freq):
+    from hybridbackend_amd.embedding import hashtable as ht
+    reports = ht.hash_evict_to([self.tables[i] for i in idx], list(max_sizes), keep_freq, [self.pairs(i) for i in idx])
+    return [host(r) for r in reports]
+
+  def spill(self, idx, max_sizes, keep_freq):
+    from hybridbackend_amd.embedding import hashtable as ht
+    exps = ht.hash_spill([self.tables[i] for i in idx], list(max_sizes), keep_freq, [self.pairs(i) for i in idx])
+    for i, exp in zip(idx, exps):
+      if len(exp):
+        self.stores[i].put(exp)
+    return [export_arrays(e) for e in exps]
+
+  def fault_in(self, i, ids):
+    from hybridbackend_amd import _lib
+    try:
+      return self.tables[i].fault_in(self.dev(ids), self.stores[i], self.comps[i]), False
+    except _lib.InvalidArgumentError as e:
+      if 'do not fit' not in str(e):   # (any other refusal is not the one a full table earns)
+        raise
+      return None, True
+
+  def export(self, idx, sinces):
+    from hybridbackend_amd.embedding import hashtable as ht
+    exps = ht.hash_export([self.tables[i] for i in idx], list(sinces), [self.comps[i] for i in idx])
+    return [export_arrays(e) for e in exps]
+
+  def import_(self, i, exp, take, world, rank, with_meta):
+    got = self.tables[i].import_items(as_export(exp, self.device, with_meta, take), self.comps[i], world, rank)
+    return host(got)
+
+  def translate_sequence(self, idx, ids, row_splits, max_lens, pad_ids, insert):
+    from hybridbackend_amd.embedding import hash_sequence as hs
+    splits = [None if s is None else self.dev(np.asarray(s, np.int32)) for s in row_splits]
+    grids, lengths = hs.hash_translate_sequence([self.tables[i] for i in idx], [self.dev(x) for x in ids], splits,
+                                                list(max_lens), list(pad_ids), insert=insert)
+    return [host(g) for g in grids], [host(n) for n in lengths]
 
 
 # ---- the generator ------------------------------------------------------------------------------------------
@@ -824,8 +1254,9 @@ def make_fleet(rng):
 class Generator:
   """The next operation of a sequence, drawn from `rng` and the models' state (never from a device)."""
 
-  def __init__(self, rng, specs, n_ops=40):
+  def __init__(self, rng, specs, n_ops=40, tier=False):
     self.rng, self.specs, self.n_ops = rng, specs, n_ops
+    self.tier, self.pending = tier, []   # tier: also draw the operations of ``tier_op``
     self.many_runs_at = int(rng.randint(n_ops // 4, n_ops))
     self.expiring = [c for c, s in enumerate(specs) if s.expiring]
     self.filtered = [c for c, s in enumerate(specs) if s.filtered]
@@ -846,20 +1277,26 @@ class Generator:
       return pool[rng.choice(pool.size, size=n, p=p / p.sum())]
     return pool[rng.randint(0, pool.size, size=n)]
 
-  def fit(self, model, ids):
+  def to_drop(self, model, ids):
     """Outside the over-full table no call may offer more new ids than there are free slots (0 < F < D is the
-    device's choice): occurrences of candidates are dropped until D <= F.  And a call that must fail walks every
-    slab per failing occurrence: those are kept to a number the sequential restatement gets through quickly.
-    Decided by the model alone."""
+    device's choice): candidates are named until D <= F.  And a call that must fail walks every slab per failing
+    occurrence: those are kept to a number the sequential restatement gets through quickly.  Decided by the model
+    alone.  None: the ids may stay as they are."""
+    D, F, occurrences = model.preview(ids)
+    absent = [k for k in np.unique(ids).tolist() if k not in model.stored and not model.sentinel_mask([k])[0]]
+    if model.regime != 'over' and 0 < F < D:
+      return absent[:max(1, D - F)]
+    if D > F and occurrences * model.slab_count > 20000:
+      return absent[:len(absent) // 2 + 1]
+    return None
+
+  def fit(self, model, ids):
+    """The ids without the occurrences of what ``to_drop`` names, until it names nothing."""
     while True:
-      D, F, occurrences = model.preview(ids)
-      absent = [k for k in np.unique(ids).tolist() if k not in model.stored and not model.sentinel_mask([k])[0]]
-      if model.regime != 'over' and 0 < F < D:
-        ids = ids[~np.isin(ids, absent[:max(1, D - F)])]
-      elif D > F and occurrences * model.slab_count > 20000:
-        ids = ids[~np.isin(ids, absent[:len(absent) // 2 + 1])]
-      else:
+      drop = self.to_drop(model, ids)
+      if drop is None:
         return ids
+      ids = ids[~np.isin(ids, drop)]
 
   def cuts(self, n):
     """1-4 runs at random places, empty runs among them."""
@@ -877,11 +1314,11 @@ class Generator:
     return {'op': 'translate', 'tables': idx, 'ids': ids, 'insert': insert, 'route': route,
             'cuts': [self.cuts(x.size) for x in ids], 'write': bool(rng.rand() < 0.6)}
 
-  def fill_exactly(self, models):
+  def fill_exactly(self, models, only=None):
     """A call that offers one table exactly as many new ids as it has free slots, each often enough to pass its
     filter, among resident ids."""
     rng = self.rng
-    order = rng.permutation(len(models)).tolist()
+    order = rng.permutation(len(models)).tolist() if only is None else only
     for i in order:
       m = models[i]
       absent = [k for k in m.pool.tolist() if k not in m.stored and not m.sentinel_mask([k])[0]]
@@ -894,7 +1331,7 @@ class Generator:
         if m.preview(ids)[:2] == (F, F):
           return {'op': 'translate', 'tables': [i], 'ids': [ids], 'insert': True,
                   'route': 'runs' if rng.rand() < 0.5 else 'plain', 'cuts': [self.cuts(ids.size)], 'write': True}
-    return self.translate(models, self.subset(range(len(models))))
+    return self.translate(models, self.subset(range(len(models)))) if only is None else None
 
   def many_runs(self, models):
     """More than 64 non-empty runs for one table: 65 runs of 1-3 ids, the second ballot of the run search."""
@@ -941,10 +1378,171 @@ class Generator:
         return {'op': 'rehash', 'tables': [i], 'geometry': [(m.slab_size, sc)], 'refused': True}
     return None
 
+  # ---- the size bound, the host tier, export / import, the sequence translate (tier=True only) ---------------
+  def draw_bound(self, m, keep):
+    """A max_size around the live size: 0, one below it, inside a last_seen group, at a group boundary, above it."""
+    rng, live = self.rng, len(m.stored)
+    ages = [r.last_seen for r in m.stored.values() if keep == 0 or r.freq < keep]
+    mode = int(rng.randint(5))
+    if mode == 0:
+      return 0
+    if mode == 1:
+      return max(live - 1, 0)
+    if mode == 4 or not ages:
+      return live + int(rng.randint(0, 3))
+    _, counts = np.unique(ages, return_counts=True)
+    upto = np.cumsum(counts)
+    wide = np.nonzero(counts > 1)[0]
+    if mode == 2 and wide.size:
+      g = int(wide[rng.randint(wide.size)])
+      return live - (int(upto[g] - counts[g]) + int(rng.randint(1, counts[g])))
+    return live - int(upto[rng.randint(upto.size)])
+
+  def fill_spill_return(self, models):
+    """An expiring table is filled to its last slot, spilled without a rehash, and asked for everything its store
+    holds: the keys come back onto tombstones, in front of and behind what stayed."""
+    order = self.rng.permutation(self.expiring).tolist()
+    op = self.fill_exactly(models, [i for i in order if models[i].regime != 'over'])
+    if op is not None:
+      i = op['tables'][0]
+      self.pending.append(lambda models: self.bound(models, [i], again=False, rehash=False, spill=True))
+      self.pending.append(lambda models: self.fault_in(models, i, everything=True))
+    return op
+
+  def bound(self, models, idx=None, again=True, rehash=None, spill=None):
+    """A spill or an evict_to; about half of the time the same-capacity rehash of ``maybe_evict`` follows, else
+    the tombstones stay for what comes next: often a fault_in, a translate or a sequence translate of one of the
+    tables, and then sometimes a second spill (of keys that came back, or came back fresh over the store)."""
+    rng = self.rng
+    if idx is None:
+      idx = self.subset([i for i in self.expiring if models[i].stored] or self.expiring)
+    keep = (0, 2)[int(rng.randint(2))]
+    op = {'op': 'spill' if (rng.rand() < 0.65 if spill is None else spill) else 'evict_to', 'tables': idx,
+          'keep': keep, 'max_sizes': [self.draw_bound(models[i], keep) for i in idx]}
+    if rng.rand() < 0.5 if rehash is None else rehash:
+      self.pending.append(lambda models: {'op': 'rehash', 'tables': idx,
+                                          'geometry': [(models[i].slab_size, models[i].slab_count) for i in idx]})
+    if again and rng.rand() < 0.7:
+      i = idx[int(rng.randint(len(idx)))]
+      r = rng.rand()
+      if r < 0.4:
+        self.pending.append(lambda models: self.fault_in(models, i))
+      elif r < 0.6:
+        self.pending.append(lambda models: self.translate(models, [i]))
+      elif r < 0.75:
+        self.pending.append(lambda models: self.translate_sequence(models, [i]))
+      else:   # (a snapshot from before the bound brings back what has just left)
+        self.pending.append(lambda models: self.import_(models, i))
+      if rng.rand() < 0.6:
+        self.pending.append(lambda models: self.bound(models, [i], again=False))
+    return op
+
+  def fault_in(self, models, i=None, everything=False):
+    """Ids of one table: some of what its store holds or all of it (some twice), ids of the pool, the sentinels
+    that come with them; stored keys are dropped until the rest fits."""
+    rng = self.rng
+    if i is None:
+      having = [i for i in self.expiring if models[i].store]
+      if not having:
+        return None
+      i = having[int(rng.randint(len(having)))]
+    m = models[i]
+    if not m.store:
+      return None
+    held = np.array(sorted(m.store), np.int64)
+    n = held.size if everything or rng.rand() < 0.5 else int(rng.randint(1, held.size + 1))
+    some = held[rng.permutation(held.size)[:n]]
+    ids = np.concatenate([some, some[:int(rng.randint(0, some.size + 1))], self.draw_ids(m, int(rng.randint(0, 9)))])
+    rng.shuffle(ids)
+    ids = ids[~np.isin(ids, m.wanted(ids)[m.free():])]
+    return {'op': 'fault_in', 'table': i, 'ids': ids}
+
+  def export(self, models):
+    rng = self.rng
+    idx = self.subset(range(len(models)))
+    sinces = [max(models[i].step - int(rng.randint(0, 3)), 0) if models[i].expiring and rng.rand() < 0.6 else None
+              for i in idx]
+    return {'op': 'export', 'tables': idx, 'sinces': sinces}
+
+  def import_(self, models, only=None):
+    """One of a table's last three snapshots that is at least one state-changing operation old, all of it or
+    what one rank of 2 or 3 owns, with or without its metadata; new keys are dropped until the rest fits."""
+    rng = self.rng
+    old = [(i, n) for i, m in enumerate(models) for n, (version, _) in enumerate(m.snapshots)
+           if n >= len(m.snapshots) - 3 and version < m.version and only in (None, i)]
+    if not old:
+      return None
+    i, n = old[int(rng.randint(len(old)))]
+    m = models[i]
+    world = (None, 2, 3)[int(rng.randint(3))]
+    rank = None if world is None else int(rng.randint(world))
+    keys = np.array(sorted(m.snapshots[n][1]), np.int64)
+    new = [k for k in keys[m.owned(keys, world, rank)].tolist() if k not in m.stored]
+    return {'op': 'import', 'table': i, 'snapshot': n, 'world': world, 'rank': rank,
+            'with_meta': bool(rng.rand() < 0.5), 'drop': new[m.free():]}
+
+  def translate_sequence(self, models, idx=None):
+    rng = self.rng
+    idx = self.subset(range(len(models))) if idx is None else idx
+    op = {'op': 'translate_sequence', 'tables': idx, 'ids': [], 'row_splits': [], 'max_lens': [], 'pad_ids': [],
+          'insert': bool(rng.rand() < 0.85), 'write': bool(rng.rand() < 0.6),
+          'by': [int(rng.randint(1, 3)) if models[i].expiring and rng.rand() < 0.5 else 0 for i in idx]}
+    for i in idx:
+      m = models[i]
+      K = keys_per_block(m.slab_size)
+      T = (1, 2, 5)[int(rng.randint(3))]
+      B = (0, 1, 7, K // T, K // T + 1)[int(rng.randint(5))]
+      ragged = rng.rand() < 0.7   # else no row_splits: one id per sample
+      lens = rng.randint(0, 2 * T + 1, size=B) if ragged else np.ones(B, np.int64)
+      flat = self.draw_ids(m, int(lens.sum()))
+      samples = np.split(flat, np.cumsum(lens)[:-1]) if B else []
+      plain = m.pool[~m.sentinel_mask(m.pool)]
+      pad = int(plain[rng.randint(plain.size)]) if rng.rand() < 0.5 else None
+      while op['insert']:   # (Generator.fit, on the effective ids)
+        lens = np.array([x.size for x in samples], np.int64)
+        eff, _, _ = effective_ids(np.concatenate(samples) if samples else flat[:0],
+                                  np.concatenate([[0], np.cumsum(lens)]), T, pad)
+        drop = self.to_drop(m, eff)
+        if drop is None:
+          break
+        if pad in drop:
+          pad = None
+        samples = [x[~np.isin(x, drop)] for x in samples]
+      if not ragged:
+        samples = [x for x in samples if x.size]
+      lens = np.array([x.size for x in samples], np.int64)
+      op['ids'].append(np.concatenate(samples) if samples else flat[:0])
+      op['row_splits'].append(np.concatenate([[0], np.cumsum(lens)]).astype(np.int32) if ragged else None)
+      op['max_lens'].append(T)
+      op['pad_ids'].append(pad)
+    return op
+
+  def tier_op(self, models):
+    r = self.rng.rand()
+    if r < 0.08 and self.expiring:
+      return self.fill_spill_return(models)
+    if r < 0.25 and self.expiring:
+      return self.bound(models)
+    if r < 0.37 and self.expiring:
+      return self.fault_in(models)
+    if r < 0.50:
+      return self.export(models)
+    if r < 0.75:
+      return self.import_(models) or self.export(models)
+    return self.translate_sequence(models)
+
   def next(self, models, index):
     rng = self.rng
+    while self.tier and self.pending:   # (what a bound queued: made from the models as they are now)
+      op = self.pending.pop(0)(models)
+      if op is not None:
+        return op
     if index == self.many_runs_at:
       return self.many_runs(models)
+    if self.tier and rng.rand() < 0.6:
+      op = self.tier_op(models)
+      if op is not None:
+        return op
     everyone = range(len(models))
     r = rng.rand()
     if r < 0.30:
@@ -985,7 +1583,8 @@ class Generator:
 class Events:
   """Event counts per (event, table kind), and the share of translate calls whose subset was adopted."""
 
-  def __init__(self):
+  def __init__(self, names=EVENTS):
+    self.names = tuple(names)     # the events a list of seeds answers for
     self.counts = {}
     self.translates = self.adopted = 0
 
@@ -993,11 +1592,11 @@ class Events:
     self.counts[(event, kind)] = self.counts.get((event, kind), 0) + 1
 
   def missing(self):
-    return [(e, k) for e in EVENTS for k in KINDS if applies(e, k) and not self.counts.get((e, k))]
+    return [(e, k) for e in self.names for k in KINDS if applies(e, k) and not self.counts.get((e, k))]
 
   def report(self):
     lines = [f'{e:24s} ' + ' '.join(f'{k}={self.counts.get((e, k), 0)}' for k in KINDS if applies(e, k))
-             for e in EVENTS]
+             for e in self.names]
     share = self.adopted / max(self.translates, 1)
     return '\n'.join(lines + [f'subset adopted in {self.adopted} of {self.translates} translate calls ({share:.1%})'])
 
@@ -1010,46 +1609,137 @@ class Runner:
     self.models = [Model(s) for s in specs]
     self.events = events if events is not None else Events()
 
+    self.snapshots = [[] for _ in specs]   # the exports of every table, as arrays: beside Model.snapshots
+    self.prints = [m.fingerprint() for m in self.models]
+
   def check_all(self):
-    for t, m, c in zip(self.fleet.tables, self.models, self.fleet.comps):
-      check(t, m, c)
+    for t, m, c, s in zip(self.fleet.tables, self.models, self.fleet.comps, self.fleet.stores):
+      check(t, m, c, s)
+    for n, m in enumerate(self.models):   # (what an import may call an older state)
+      now = m.fingerprint()
+      m.version += int(now != self.prints[n])
+      self.prints[n] = now
+
+  def answered(self, i, ids, slots, before, op, index):
+    """The answers `slots` of table i to the ids of one translate (of a sequence translate: its effective ids),
+    against the model; then the row writes."""
+    m, ev, fleet = self.models[i], self.events, self.fleet
+    if op['insert']:
+      if m.expiring and ids.size:   # resident ids whose walk passes a tombstone: a fact of the layout
+        res = np.unique([k for k in ids.tolist() if k in m.stored])
+        if res.size:
+          order = np.argsort(before, kind='stable')
+          at = order[np.searchsorted(before[order], res)]
+          if passes_tombstone(before, m.slab_size, res, at).any():
+            ev.add('behind_tombstone', m.kind)
+      stored, events, adopted = m.translate(ids, slots)
+      assert not adopted or m.regime == 'over', 'a subset was the device\'s choice outside the over-full table'
+      ev.translates += 1
+      ev.adopted += int(adopted)
+      for e in events:
+        ev.add(e, m.kind)
+    else:
+      stored = m.find(ids)
+    keys = fleet.keys(i)
+    check_slots(ids, slots, stored, keys)
+    if op['write'] and stored.any():
+      k, first = np.unique(ids[stored], return_index=True)
+      at = slots[stored][first]
+      rows = written_rows(k, index, m.dim)
+      comp_rows = [written_rows(k, index, w, salt=c + 1) for c, (w, _) in enumerate(m.comp_specs)]
+      fleet.write(i, at, rows, comp_rows)
+      m.write(k, rows, comp_rows)
+
+  def advance(self, op):
+    for i, by in zip(op['tables'], op.get('by', ())):
+      if by:
+        self.models[i].set_step(self.models[i].step + by)
+        self.fleet.set_step(i, self.models[i].step)
 
   def apply(self, op, index):
     fleet, models, ev = self.fleet, self.models, self.events
     what = op['op']
     if what == 'translate':
       idx, ids = op['tables'], op['ids']
-      before = [fleet.keys(i) for i in idx] if op['insert'] else None
+      before = [fleet.keys(i) for i in idx] if op['insert'] else [None] * len(idx)
       slots = fleet.translate(idx, ids, op['insert'], op['route'], op['cuts'])
       for n, i in enumerate(idx):
+        self.answered(i, ids[n], slots[n], before[n], op, index)
+        if op['insert'] and op['route'] == 'runs' and any(a.size == 0 for a in np.split(ids[n], op['cuts'][n])):
+          ev.add('empty_run', models[i].kind)
+    elif what == 'translate_sequence':
+      idx, ids = op['tables'], op['ids']
+      self.advance(op)
+      before = [fleet.keys(i) for i in idx] if op['insert'] else [None] * len(idx)
+      grids, lengths = fleet.translate_sequence(idx, ids, op['row_splits'], op['max_lens'], op['pad_ids'], op['insert'])
+      for n, i in enumerate(idx):
+        m, T, pad = models[i], op['max_lens'][n], op['pad_ids'][n]
+        eff, at, lens = effective_ids(ids[n], op['row_splits'][n], T, pad)
+        assert lengths[n].dtype == np.int32
+        np.testing.assert_array_equal(lengths[n], lens, err_msg='lengths')
+        assert grids[n].shape == (lens.size * T,)
+        rest = np.ones(grids[n].size, bool)
+        rest[at] = False
+        assert (grids[n][rest] == -1).all(), 'a position past a sample\'s length, without a pad id, is not -1'
+        full = np.diff(np.arange(ids[n].size + 1) if op['row_splits'][n] is None else op['row_splits'][n])
+        if (full > T).any():
+          ev.add('sequence_truncates', m.kind)
+        if pad is not None and (full < T).any():
+          ev.add('sequence_pads', m.kind)
+        if m.expiring and m.tomb_lb > 0 and eff.size:
+          ev.add('sequence_on_tombstones', m.kind)
+        self.answered(i, eff, grids[n][at], before[n], op, index)
+    elif what in ('evict_to', 'spill'):
+      idx, sizes, keep = op['tables'], op['max_sizes'], op['keep']
+      before = [fleet.keys(i) for i in idx]
+      got = (fleet.evict_to if what == 'evict_to' else fleet.spill)(idx, sizes, keep)
+      for n, i in enumerate(idx):
         m = models[i]
-        if op['insert']:
-          if m.expiring and ids[n].size:   # resident ids whose walk passes a tombstone: a fact of the layout
-            res = np.unique([k for k in ids[n].tolist() if k in m.stored])
-            if res.size:
-              order = np.argsort(before[n], kind='stable')
-              at = order[np.searchsorted(before[n][order], res)]
-              if passes_tombstone(before[n], m.slab_size, res, at).any():
-                ev.add('behind_tombstone', m.kind)
-          stored, events, adopted = m.translate(ids[n], slots[n])
-          assert not adopted or m.regime == 'over', 'a subset was the device\'s choice outside the over-full table'
-          ev.translates += 1
-          ev.adopted += int(adopted)
-          for e in events:
-            ev.add(e, m.kind)
-          if op['route'] == 'runs' and any(a.size == 0 for a in np.split(ids[n], op['cuts'][n])):
-            ev.add('empty_run', m.kind)
+        if what == 'evict_to':
+          report, events = m.evict_to(sizes[n], keep)
+          check_report(got[n], report, f'table {i}')
         else:
-          stored = m.find(ids[n])
-        keys = fleet.keys(i)
-        check_slots(ids[n], slots[n], stored, keys)
-        if op['write'] and stored.any():
-          k, first = np.unique(ids[n][stored], return_index=True)
-          at = slots[n][stored][first]
-          rows = written_rows(k, index, m.dim)
-          comp_rows = [written_rows(k, index, w, salt=c + 1) for c, (w, _) in enumerate(m.comp_specs)]
-          fleet.write(i, at, rows, comp_rows)
-          m.write(k, rows, comp_rows)
+          want, events = m.spill(sizes[n], keep)
+          check_export(m, got[n], want, before[n], f'the spill of table {i}')
+        for e in events:
+          ev.add(e, m.kind)
+    elif what == 'fault_in':
+      i, ids = op['table'], op['ids']
+      m = models[i]
+      before = set(m.stored) | set(m.store)
+      n, raised = fleet.fault_in(i, ids)
+      want, raises, events = m.fault_in(ids, fleet.keys(i))
+      assert raised == raises == bool(op.get('raises')), 'a fault_in that fits raised' if raised else \
+          'a fault_in that does not fit did not raise'
+      assert raised or n == want, f'fault_in returned {n}, {want} keys came back'
+      assert set(m.stored) | set(m.store) == before   # (and check_all: no key is lost, none is in both)
+      for e in events:
+        ev.add(e, m.kind)
+    elif what == 'export':
+      idx, sinces = op['tables'], op['sinces']
+      state = [_state(fleet.tables[i], fleet.comps[i]) for i in idx]
+      got = fleet.export(idx, sinces)
+      for n, i in enumerate(idx):
+        m = models[i]
+        want, events = m.export(sinces[n])
+        check_export(m, got[n], want, state[n]['keys'], f'the export of table {i}')
+        same_state(state[n], _state(fleet.tables[i], fleet.comps[i]), 'an export')
+        self.snapshots[i].append(got[n])
+        for e in events:
+          ev.add(e, m.kind)
+    elif what == 'import':
+      i, m = op['table'], models[op['table']]
+      arrays, (_, snapshot) = self.snapshots[i][op['snapshot']], m.snapshots[op['snapshot']]
+      take = np.nonzero(~np.isin(arrays['keys'], np.asarray(op.get('drop', ()), np.int64)))[0]
+      kept = {k: snapshot[k] for k in arrays['keys'][take].tolist()}
+      slots = fleet.import_(i, arrays, take, op.get('world'), op.get('rank'), op['with_meta'])
+      mine, events = m.import_(kept, op.get('world'), op.get('rank'), op['with_meta'])
+      own = m.owned(arrays['keys'][take], op.get('world'), op.get('rank'))
+      assert slots.shape == (int(own.sum()),)
+      np.testing.assert_array_equal(fleet.keys(i)[slots], arrays['keys'][take][own],
+                                    err_msg='the returned slots do not hold the imported keys')
+      for e in events:
+        ev.add(e, m.kind)
     elif what == 'step':
       for i, by in zip(op['tables'], op['by']):
         models[i].set_step(models[i].step + by)
@@ -1099,13 +1789,14 @@ class Runner:
     self.check_all()
 
 
-def run_seed(seed, make, events=None, n_ops=40):
-  """One seeded sequence; `make(specs)` builds the fleet to drive."""
+def run_seed(seed, make, events=None, n_ops=40, tier=False):
+  """One seeded sequence; `make(specs)` builds the fleet to drive.  `tier`: with the operations of
+  ``Generator.tier_op`` (the TIER_SEEDS)."""
   rng = np.random.RandomState(1000 + seed)
   specs = make_fleet(rng)
   runner = Runner(make(specs), specs, events)
   runner.check_all()
-  gen = Generator(rng, specs, n_ops)
+  gen = Generator(rng, specs, n_ops, tier)
   for index in range(n_ops):
     op = gen.next(runner.models, index)
     try:
@@ -1116,14 +1807,17 @@ def run_seed(seed, make, events=None, n_ops=40):
 
 
 def describe(op):
-  out = {k: v for k, v in op.items() if k not in ('ids', 'cuts', 'keys')}
+  out = {k: v for k, v in op.items() if k not in ('ids', 'cuts', 'keys', 'row_splits', 'drop')}
   if 'ids' in op:
-    out['n_ids'] = [int(x.size) for x in op['ids']]
+    out['n_ids'] = [int(x.size) for x in op['ids']] if isinstance(op['ids'], list) else int(op['ids'].size)
+  if 'cuts' in op:
     out['n_runs'] = [len(c) + 1 for c in op['cuts']]
+  if 'drop' in op:
+    out['n_dropped'] = len(op['drop'])
   return str(out)
 
 
-# ---- three sequences written out by hand ------------------------------------------------------------------------
+# ---- sequences written out by hand ------------------------------------------------------------------------
 def _homing(slab_count, slab, n, start=1):
   """The first n positive ids from `start` on whose home slab is `slab`."""
   out, k = [], start
@@ -1184,9 +1878,89 @@ def fixed_two_rehashes_around_a_write():
   return [spec], ops
 
 
+def _step(by=1):
+  return {'op': 'step', 'tables': [0], 'by': [by]}
+
+
+def fixed_spill_chain_and_return():
+  """A 3 x 5 filtered expiring table filled to the last slot by ids that all home into slab 1, with a width-4 and a
+  width-1 companion, rows written, in three age groups of five.  A spill to a bound inside the middle group takes
+  the two older groups: ten tombstones in front of and among the five keys that stay.  ONE fault_in then asks for
+  six spilled ids twice each, the resident ids (behind the tombstones now), ids never seen and both sentinels: the
+  six come back as they left, nothing else appears.  A translate stamps two of them and brings two ids back FRESH
+  while the store still holds them; a second spill takes returned keys again and the two fresh ones (the store
+  upserts); the table is rehashed to 8 x 2 and everything left comes back."""
+  old = _homing(3, 1, 15)
+  never = _homing(3, 1, 4, start=int(old[-1]) + 1)
+  spec = Spec('expiring_admit', 5, 3, 4, [(4, 0.1), (1, -2.5)], 'tight',
+              np.concatenate([old, never, [EMPTY, TOMBSTONE]]), min_freq=2, depth=4, width=64, seed=7, sketch_seed=3)
+  back = old[[0, 2, 4, 5, 7, 9]]
+  asked = np.concatenate([back, old[10:], never, [EMPTY, TOMBSTONE], back[::-1], never[:2]])
+  spill = {'op': 'spill', 'tables': [0], 'keep': 0}
+  ops = [_call(0, np.repeat(old, 2), write=True), _step(), _call(0, old[5:], write=True), _step(),
+         _call(0, old[10:], route='runs', cuts=(2,), write=True),
+         dict(spill, max_sizes=[8]),                                    # need 7, the cut inside the group of step 1
+         {'op': 'fault_in', 'table': 0, 'ids': asked},
+         _call(0, np.concatenate([old[[1, 3]], back[:2], old[10:11]]), write=True),   # 1, 3: fresh over the store
+         _step(), _call(0, np.concatenate([old[11:14], back[2:3]])),
+         dict(spill, max_sizes=[5]),                                    # 13 keys, four of step 3: nine leave
+         {'op': 'rehash', 'tables': [0], 'geometry': [(8, 2)]},
+         {'op': 'fault_in', 'table': 0, 'ids': np.concatenate([old, old])},
+         _call(0, old, insert=False)]
+  return [spec], ops
+
+
+def fixed_fault_in_that_does_not_fit():
+  """A full 3 x 5 expiring table spills ten keys, six new ids take six of the tombstones, and a fault_in asks for
+  all ten: four fit.  The call must raise; afterwards the four are in the table as they left, the six are in the
+  store again, nothing is lost and nothing is in both.  Which four is the device's choice.  After a rehash to
+  24 slots the six follow."""
+  old = _homing(3, 1, 15)
+  new = _homing(3, 2, 6, start=1000)
+  spec = Spec('expiring', 5, 3, 4, [(4, 0.1)], 'tight', np.concatenate([old, new, [EMPTY, TOMBSTONE]]), seed=11)
+  ops = [_call(0, old, write=True), _step(), _call(0, old[10:], write=True),
+         {'op': 'spill', 'tables': [0], 'keep': 0, 'max_sizes': [5]},
+         _call(0, new, write=True),
+         {'op': 'fault_in', 'table': 0, 'ids': np.concatenate([old, old[:10]]), 'raises': True},
+         {'op': 'rehash', 'tables': [0], 'geometry': [(8, 3)]},
+         {'op': 'fault_in', 'table': 0, 'ids': old},
+         _call(0, np.concatenate([old, new]), insert=False)]
+  return [spec], ops
+
+
+def fixed_snapshot_over_a_moved_table():
+  """dim 19 with a width-4 companion, expiring: a full export; then a sweep evicts a third of the keys, rows are
+  written, the table moves to another slab size and takes new keys -- and the old snapshot is imported with its
+  metadata: evicted keys return as they were, written rows are overwritten, the new keys stay.  Then a delta
+  export of that second state; an evict_to takes seven of its nine keys and the table moves again; the delta is
+  imported without metadata: seven keys are new, two are overwritten, all nine count as seen now."""
+  first = np.concatenate([_homing(20, 2, 9), np.arange(-20, 20, dtype=np.int64) * 977])
+  later = np.arange(1, 13, dtype=np.int64) * 7919 + (1 << 32)
+  spec = Spec('expiring', 5, 20, 19, [(4, 0.1)], 'roomy', np.concatenate([first, later, [EMPTY, TOMBSTONE]]), seed=5)
+  ops = [_call(0, first, write=True), _step(), _call(0, first[::3], write=True), _step(), _call(0, first[1::3]),
+         {'op': 'export', 'tables': [0], 'sinces': [None]},
+         _step(), {'op': 'evict', 'tables': [0], 'ttl': 3, 'keep': 0},           # first[2::3], last seen at step 0
+         _call(0, first[::3], insert=False, write=True),
+         {'op': 'rehash', 'tables': [0], 'geometry': [(33, 3)]},
+         _call(0, later, write=True),
+         {'op': 'import', 'table': 0, 'snapshot': 0, 'with_meta': True},
+         _step(), _call(0, np.concatenate([later[:5], first[2::3][:4]]), write=True),
+         {'op': 'export', 'tables': [0], 'sinces': [4]},                         # the nine keys of step 4
+         _step(), _call(0, np.concatenate([first[::3], later[:2]])),
+         {'op': 'evict_to', 'tables': [0], 'keep': 0, 'max_sizes': [20]},        # all of step 4 and before: 42 keys
+         {'op': 'rehash', 'tables': [0], 'geometry': [(8, 12)]},
+         _call(0, later[:2], insert=False, write=True), _step(2),
+         {'op': 'import', 'table': 0, 'snapshot': 1, 'with_meta': False},
+         _call(0, np.concatenate([first, later]), insert=False)]
+  return [spec], ops
+
+
 FIXED = {'refill_of_tombstones': fixed_refill_of_tombstones,
          'sighting_across_evict_and_rehash': fixed_sighting_across_evict_and_rehash,
-         'two_rehashes_around_a_write': fixed_two_rehashes_around_a_write}
+         'two_rehashes_around_a_write': fixed_two_rehashes_around_a_write,
+         'spill_chain_and_return': fixed_spill_chain_and_return,
+         'fault_in_that_does_not_fit': fixed_fault_in_that_does_not_fit,
+         'snapshot_over_a_moved_table': fixed_snapshot_over_a_moved_table}
 
 
 def run_fixed(name, make, events=None):
