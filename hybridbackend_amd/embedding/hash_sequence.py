@@ -30,6 +30,7 @@ from hybridbackend_amd.embedding.hashtable import check_current
 from hybridbackend_amd.embedding.hashtable import check_ids
 from hybridbackend_amd.embedding.hashtable import evict_tables
 from hybridbackend_amd.embedding.hashtable import grow_tables
+from hybridbackend_amd.embedding.hashtable import remove_tables
 from hybridbackend_amd.embedding.hashtable import same_device
 from hybridbackend_amd.embedding.lookup import GroupLookup
 from hybridbackend_amd.embedding.lookup import max_norm_list
@@ -214,6 +215,13 @@ class HashSequenceLookup:
     :meth:`rebind` if any table was rehashed.  Returns the per-table results: None, or the new companion
     tensors."""
     return evict_tables(self, self.hash_tables, max_load, target_load, keep_freq, slots)
+
+  def remove(self, ids_list, slots=None, stores=None):
+    """:meth:`HashGroupLookup.remove`: the ids of ``ids_list[c]`` leave table c (``slots[c]``: its ``(tensor,
+    fill_value)`` companions, ``stores[c]``: its spill store or None).  The row tensors do not move, so no
+    :meth:`rebind` is needed; slots handed out earlier for the removed ids are void.  Returns the old slots per
+    table."""
+    return remove_tables(self.hash_tables, ids_list, slots, stores)
 
   def __len__(self):
     return len(self.hash_tables)

@@ -37,6 +37,12 @@ optimizer slots -- and then remove them; a :class:`HashSpillStore` keeps them on
 :meth:`HashTable.fault_in` / :meth:`HashGroupLookup.fault_in` bring a batch's spilled keys back as they left before
 the translate.  ``maybe_evict(..., spill=store)`` spills where it evicted.
 
+Removal by id (``hbk_hash_remove_n``): :meth:`HashTable.remove` / :func:`hash_remove` take the keys the caller
+names out of N expiring tables -- a find and an erase launch, the old slots returned, the companions reset as a sweep
+resets them.  :meth:`HashTable.track_removals` records every key that leaves (removed, evicted or spilled), and a
+delta export of a tracking table carries them (``HashExport.removed``), so base + deltas restore the table that was
+saved, not a superset of it.
+
 Sharded hash tables: :class:`hybridbackend_amd.embedding.ShardedHashGroupLookup` (sharded_hash.py) puts tables of
 W ranks behind the sharded lookup step, owner = :func:`hash_owner`; :meth:`HashTable.load_owned` restores
 ``items()`` of W ranks onto W' ranks.
@@ -149,6 +155,7 @@ class HashTable:
     self.table = torch.zeros((self.capacity, dim), dtype=torch.float32, device=self.device)
     self.counts = torch.zeros(2, dtype=torch.int32, device=self.device)
     self.expiring = bool(expiring)
+    self._removals = None   # track_removals(): the keys that left, as device tensors
     if self.expiring:
       self.last_seen = torch.zeros(self.capacity, dtype=torch.int32, device=self.device)
       self.freq = torch.zeros(self.capacity, dtype=torch.int32, device=self.device)
@@ -329,7 +336,9 @@ class HashTable:
     becomes a TOMBSTONE that later inserts reuse.  ``slots``: up to 4 ``(tensor, fill_value)`` pairs, the
     optimizer slots (fp32 ``[capacity, d]``), whose rows of the evicted slots are set to ``fill_value``
     (Adagrad: ``initial_accumulator_value``).  Must not run beside a translate of the table on another
-    stream.  Returns nothing and does not sync."""
+    stream.  Returns nothing and does not sync -- unless the table tracks its removals (:meth:`track_removals`):
+    the call then copies the key array, compares after the sweep and synchronises the host once, and is refused
+    inside a stream capture."""
     hash_evict([self], steps_to_live, keep_freq, [slots])
 
   def evicted(self):
@@ -346,6 +355,64 @@ class HashTable:
     """Slots that hold a TOMBSTONE now (syncs the host)."""
     self._need_expiring('tombstones')
     return int((self.keys == TOMBSTONE_KEY).sum().item())
+
+  # ---- removal by id ------------------------------------------------------------------------------------
+  def remove(self, ids, slots=(), store=None):
+    """The keys of ``ids`` leave the table (``hbk_hash_remove_n``: a find and an erase launch) exactly as
+    :meth:`evict` makes a key leave: the slot becomes a TOMBSTONE that later inserts reuse, ``last_seen`` and
+    ``freq`` become 0, the rows of the companions ``slots`` (``(tensor, fill_value)`` pairs as in :meth:`evict`)
+    are set to their fill value, the embedding row is left for the next key.  Returns the slot every id held
+    before the call, int64 ``[n]`` on the device, -1 for ids the table did not hold -- for every occurrence,
+    duplicates included.  ``evicted()`` counts the distinct ids removed and ``size()`` stays right.  Does not
+    sync.  Slots handed out earlier for the removed ids are void.  Needs ``expiring=True``: a removed key leaves
+    a TOMBSTONE behind, and a plain table has none.
+
+    ``store``: a :class:`HashSpillStore` -- the ids it holds leave it too (``store.discard``); this costs one
+    device-to-host copy of the distinct ids, and only in this case.  Must not run beside a translate, a sweep or
+    a backward of the table on another stream."""
+    if store is not None:
+      _check_store(store, self, slots)
+    out = hash_remove([self], [ids], [slots])[0]
+    if store is not None and len(store):
+      store.discard(torch.unique(ids).cpu())
+    return out
+
+  def track_removals(self, on=True):
+    """Start (or, ``on=False``, stop and forget) recording the keys that leave the table: every call that writes
+    TOMBSTONEs -- :meth:`remove`, :meth:`evict`, :meth:`evict_to`, :meth:`spill_to`, :meth:`maybe_evict` and the
+    N-table functions behind them -- then adds the keys it took out to a log of device int64 tensors, which
+    :meth:`removed_keys` reads and a delta export carries (``HashExport.removed``).  The cost: ``remove`` and
+    ``spill_to`` record the keys they already hold; a tracked SWEEP (``evict``, ``evict_to``) copies the key
+    array before the call (8 B/slot) and compares after it, with one host synchronisation.  An untracked table
+    issues exactly the calls it issued before.  ``rehash``, ``compact`` and ``maybe_grow`` do not touch the log.
+    A captured ``remove`` records when it is captured, not when it is replayed; a tracked sweep needs the host and
+    is refused inside a stream capture."""
+    self._need_expiring('track_removals')
+    if not on:
+      self._removals = None
+    elif self._removals is None:
+      self._removals = []
+
+  def removed_keys(self):
+    """The sorted distinct keys recorded since :meth:`track_removals` / :meth:`clear_removals` that :meth:`find`
+    does not see now, int64 on the device: a key that left and came back is not removed.  Syncs the host."""
+    if self._removals is None:
+      raise _bad('removed_keys needs track_removals() first')
+    dev = self.keys.device
+    if not self._removals:
+      return torch.zeros(0, dtype=torch.int64, device=dev)
+    keys = torch.unique(torch.cat(self._removals))
+    keys = keys[(keys != TOMBSTONE_KEY) & (keys != EMPTY_KEY)]
+    self._removals = [keys]   # (the log stays as long as its distinct keys)
+    if keys.numel() == 0:
+      return keys
+    return keys[self.find(keys.contiguous()) < 0]
+
+  def clear_removals(self):
+    """Forget the recorded keys (after the delta that carried them was saved); tracking stays on."""
+    if self._removals is None:
+      raise _bad('clear_removals needs track_removals() first')
+    self._removals = []
 
   def compact(self, slots=()):
     """Rebuild the table in place: every live key is inserted again into an all-EMPTY key array, so every
@@ -410,7 +477,8 @@ class HashTable:
     is no tie-break and no exact size.  ``keep_freq > 0``: keys seen that often stay whatever their age (the
     table may then stay above the bound).  ``slots``: as in :meth:`evict`.  The step counter is not read.
     Returns the report, int32 ``[4]`` on the device: ``{live_before, need, cut, n_evicted}`` (``report``: a
-    preallocated one, for a captured call).  No host read, no sync."""
+    preallocated one, for a captured call).  No host read, no sync -- unless the table tracks its removals
+    (:meth:`track_removals`): one key-array copy and one host synchronisation then, and no capture."""
     return hash_evict_to([self], [max_size], keep_freq, [slots], [report])[0]
 
   def maybe_evict(self, max_load=0.75, target_load=0.5, keep_freq=0, slots=(), spill=None):
@@ -499,7 +567,11 @@ class HashTable:
     expiring table reused, as :meth:`load`), then rows, metadata and companions are stored in ONE launch
     (``hbk_hash_store_rows_n``).  Returns the slots of the keys imported.
 
-    ``slots``: the destination companions, fp32 ``[capacity, d]``, matching ``exp.slots`` in number and width.
+    ``slots``: the destination companions, fp32 ``[capacity, d]``, matching ``exp.slots`` in number and width;
+    each entry a tensor or a ``(tensor, fill_value)`` pair.  An export with a non-empty ``removed`` (a delta of a
+    tracking table) first removes those keys (:meth:`remove`; owner-filtered under ``world`` / ``rank``), then
+    upserts: a removal resets the companion rows of the slots it frees, so such an import needs the pairs and is
+    refused with bare tensors.
     ``world`` / ``rank``: only the keys rank ``rank`` of ``world`` owns are imported (:func:`hash_owner`).
     An export with metadata restores ``last_seen`` and ``freq`` on an expiring table (the key keeps its age and
     count); one without leaves :meth:`load`'s "seen now" stamp; a plain table drops the metadata.  The keys must
@@ -508,7 +580,22 @@ class HashTable:
     if not isinstance(exp, HashExport):
       raise _bad('import_items needs a HashExport')
     dev = self.keys.device
-    dst_slots = _plain_companions(self, slots)
+    removed = getattr(exp, 'removed', None)
+    if removed is not None and (not isinstance(removed, torch.Tensor) or removed.dtype != torch.int64 or
+                                removed.dim() != 1):
+      raise _bad('import_items: exp.removed must be an int64 vector')
+    removing = removed is not None and removed.numel() > 0
+    slots = list(slots)
+    paired = [isinstance(p, (tuple, list)) for p in slots]
+    if removing:
+      if not self.expiring:
+        raise _bad('import_items: the export names removed keys, and removing needs a table built with '
+                   'expiring=True')
+      if not all(paired):
+        raise _bad('import_items: the export names removed keys, and a removal resets the companion rows of the '
+                   'slots it frees: slots must be (tensor, fill_value) pairs, got bare tensors')
+    pairs = _companions(self, [p if is_pair else (p, 0.0) for p, is_pair in zip(slots, paired)])
+    dst_slots = [t for t, _ in pairs]
     if len(dst_slots) != len(exp.slots):
       raise _bad(f'import_items: the export carries {len(exp.slots)} companion tensors, slots names {len(dst_slots)}')
     n = exp.keys.numel()
@@ -536,16 +623,25 @@ class HashTable:
       keys = keys[mine]
       src = [x[mine] for x in src]
     keys = keys.contiguous()
+    if keys.numel():   # (the checks of the upsert, before anything is removed: a refusal leaves the table as it was)
+      if not assume_distinct:
+        ordered = torch.sort(keys).values
+        if bool((ordered[1:] == ordered[:-1]).any().item()):
+          raise _bad('import_items: the keys are not distinct')
+      check_ids([keys], [self])
+      for x in src:
+        if x.stride(-1) != 1:
+          raise _bad('import_items: the export\'s rows must be contiguous')
+    if removing:
+      # every argument is checked: what left the saved table since its base leaves this one first (the owned keys;
+      # the others are not here)
+      gone = removed.to(dev)
+      if world is not None:
+        gone = gone[hash_owner(gone, world) == int(rank)]
+      if gone.numel():
+        hash_remove([self], [gone.contiguous()], [pairs])
     if keys.numel() == 0:
       return keys.new_empty(0)
-    if not assume_distinct:
-      ordered = torch.sort(keys).values
-      if bool((ordered[1:] == ordered[:-1]).any().item()):
-        raise _bad('import_items: the keys are not distinct')
-    check_ids([keys], [self])
-    for x in src:
-      if x.stride(-1) != 1:
-        raise _bad('import_items: the export\'s rows must be contiguous')
     got = _translate([self], [keys], True, None, init=False, plan=_Plan([self], admit=False))[0]
     col = (_lib.HashStoreColumn * 1)()
     col[0].slots, col[0].n, col[0].dst_rows = got.data_ptr(), keys.numel(), self.capacity
@@ -602,13 +698,17 @@ class HashExport:
   Attributes: ``keys`` int64 ``[n]``; ``rows`` fp32 ``[n, dim]``; ``last_seen`` / ``freq`` int32 ``[n]`` (None
   for a table that is not expiring); ``slots``: a list of fp32 ``[n, d]`` tensors, one per companion; ``src_slots``
   int64 ``[n]``: the slot every key had in the table it came from (ascending: the order of the export); ``since``:
-  the ``since`` of the export, 0 for a full one."""
+  the ``since`` of the export, 0 for a full one; ``removed``: int64 ``[m]`` ascending, the keys that left the
+  table since tracking began or was cleared and are not in it now (a table with :meth:`HashTable.track_removals`
+  on: :meth:`HashTable.removed_keys` for a delta, empty for a full export), or None for a table that does not
+  track."""
 
-  def __init__(self, keys, rows, last_seen=None, freq=None, slots=(), src_slots=None, since=0):
+  def __init__(self, keys, rows, last_seen=None, freq=None, slots=(), src_slots=None, since=0, removed=None):
     self.keys, self.rows, self.last_seen, self.freq = keys, rows, last_seen, freq
     self.slots = list(slots)
     self.src_slots = src_slots
     self.since = int(since)
+    self.removed = removed
 
   def __len__(self):
     return self.keys.numel()
@@ -626,6 +726,8 @@ class HashExport:
       out[base + 'src_slots'] = self.src_slots
     for k, x in enumerate(self.slots):
       out[base + f'slot{k}'] = x
+    if self.removed is not None:
+      out[base + 'removed'] = self.removed
     return out
 
   @classmethod
@@ -640,21 +742,25 @@ class HashExport:
       slots.append(d[base + f'slot{len(slots)}'])
     since = d.get(base + 'since')
     return cls(d[base + 'keys'], d[base + 'rows'], d.get(base + 'last_seen'), d.get(base + 'freq'), slots,
-               d.get(base + 'src_slots'), 0 if since is None else int(since.reshape(-1)[0].item()))
+               d.get(base + 'src_slots'), 0 if since is None else int(since.reshape(-1)[0].item()),
+               d.get(base + 'removed'))
 
   @classmethod
-  def empty(cls, n, dim, expiring=False, slot_dims=(), device='cpu'):
-    """An export of ``n`` zero keys: the tensors a ``Saver.restore`` of a saved export is read into."""
+  def empty(cls, n, dim, expiring=False, slot_dims=(), device='cpu', n_removed=None):
+    """An export of ``n`` zero keys: the tensors a ``Saver.restore`` of a saved export is read into.  ``n_removed``:
+    None, or the length of ``removed``."""
     n = int(n)
     meta = [torch.zeros(n, dtype=torch.int32, device=device) for _ in range(2)] if expiring else [None, None]
     return cls(torch.zeros(n, dtype=torch.int64, device=device), torch.zeros((n, int(dim)), device=device),
                meta[0], meta[1], [torch.zeros((n, int(d)), device=device) for d in slot_dims],
-               torch.zeros(n, dtype=torch.int64, device=device), 0)
+               torch.zeros(n, dtype=torch.int64, device=device), 0,
+               None if n_removed is None else torch.zeros(int(n_removed), dtype=torch.int64, device=device))
 
   @classmethod
   def cat(cls, exports):
     """The exports of several ranks (or a table's parts) as one: concatenated in order.  The metadata stays only
-    when every part has it; ``since`` is the smallest of the parts'."""
+    when every part has it, and so does ``removed`` (the parts' keys as one ascending distinct list); ``since`` is
+    the smallest of the parts'."""
     exports = list(exports)
     if not exports:
       raise _bad('cat: no exports')
@@ -662,11 +768,13 @@ class HashExport:
       raise _bad('cat: the exports differ in their number of companion tensors')
     meta = all(e.last_seen is not None and e.freq is not None for e in exports)
     src = all(e.src_slots is not None for e in exports)
+    gone = all(e.removed is not None for e in exports)
     return cls(torch.cat([e.keys for e in exports]), torch.cat([e.rows for e in exports]),
                torch.cat([e.last_seen for e in exports]) if meta else None,
                torch.cat([e.freq for e in exports]) if meta else None,
                [torch.cat([e.slots[k] for e in exports]) for k in range(len(exports[0].slots))],
-               torch.cat([e.src_slots for e in exports]) if src else None, min(e.since for e in exports))
+               torch.cat([e.src_slots for e in exports]) if src else None, min(e.since for e in exports),
+               torch.unique(torch.cat([e.removed for e in exports])) if gone else None)
 
 
 def hash_export(tables, sinces=None, slots=None):
@@ -681,6 +789,8 @@ def hash_export(tables, sinces=None, slots=None):
   The outputs are allocated from ONE host read of the counters (the live keys: an upper bound for a delta), the
   launches run, ONE host read of the counts follows and the outputs are narrowed to views.  More matches than the
   counters promised is refused: the counters are stale after a restore of the raw arrays -- :meth:`recount`.
+  A table that tracks its removals (:meth:`HashTable.track_removals`) also gets ``removed``:
+  :meth:`HashTable.removed_keys` for a delta (a find and one more host read), an empty tensor for a full export.
   Must not run beside a translate, a sweep or a backward of the same tables on another stream."""
   tables = list(tables)
   same_device(tables)
@@ -744,6 +854,9 @@ def hash_export(tables, sinces=None, slots=None):
     result.append(HashExport(out['keys'][:k], out['rows'][:k], out['last_seen'][:k] if tables[c].expiring else None,
                              out['freq'][:k] if tables[c].expiring else None, [x[:k] for x in out['slots']],
                              out['src_slots'][:k], 0 if sinces[c] is None else max(int(sinces[c]), 0)))
+  for c, t in enumerate(tables):
+    if t._removals is not None:
+      result[c].removed = t.removed_keys() if sinces[c] is not None else torch.zeros(0, dtype=torch.int64, device=dev)
   return result
 
 
@@ -845,11 +958,34 @@ def hash_rehash(tables, capacities=None, slab_sizes=None, slots=None):
 
 def hash_evict(tables, steps_to_live, keep_freq=0, slots=None):
   """:meth:`HashTable.evict` for N expiring tables in ONE launch.  ``slots[c]``: the ``(tensor, fill_value)``
-  pairs of table ``c`` (None: no table has any)."""
+  pairs of table ``c`` (None: no table has any).  Does not sync, unless a table tracks its removals
+  (:meth:`HashTable.track_removals`): see :meth:`HashTable.evict`."""
   tables = list(tables)
   cols, _ = _evict_columns(tables, steps_to_live, keep_freq, slots)
   dev = tables[0].keys.device if tables else None
+  before = _keys_before(tables)
   _lib.check(_lib.lib().hbk_hash_evict_n(len(tables), cols, _lib.current_stream(dev)))
+  _record_swept(tables, before)
+
+
+def _keys_before(tables):
+  """The snapshot a tracked sweep needs (:meth:`HashTable.track_removals`): a copy of the key array of every
+  tracking table, None for the others -- and None altogether when no table tracks."""
+  if not any(t._removals is not None for t in tables):
+    return None
+  if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+    raise _bad('a sweep of a table that tracks its removals reads the host (the key array is compared after the '
+               'call): it cannot be captured -- track_removals(False) first, or sweep outside the capture')
+  return [t.keys.clone() if t._removals is not None else None for t in tables]
+
+
+def _record_swept(tables, before):
+  """The keys a sweep turned into TOMBSTONEs, into the log of every tracking table (one host synchronisation)."""
+  if before is None:
+    return
+  for t, b in zip(tables, before):
+    if b is not None:
+      t._removals.append(b[(t.keys == TOMBSTONE_KEY) & (b != TOMBSTONE_KEY)])
 
 
 def _evict_columns(tables, steps_to_live, keep_freq, slots):
@@ -891,7 +1027,9 @@ def hash_evict_to(tables, max_sizes, keep_freq=0, slots=None, reports=None):
   ``slots[c]``: the ``(tensor, fill_value)`` pairs of table ``c`` as in :func:`hash_evict`.  ``reports[c]``: an
   int32 ``[4]`` device tensor or None (allocated): ``{live_before, need, cut, n_evicted}`` of table c after the
   call.  Returns the list of reports; does not sync.  The scratch tensor is kept per (device, number of tables),
-  so a captured call replays."""
+  so a captured call replays.  With a table that tracks its removals (:meth:`HashTable.track_removals`) the call
+  copies that table's key array first, compares after the sweep with one host synchronisation, and is refused inside
+  a stream capture."""
   return _evict_to(tables, max_sizes, keep_freq, slots, reports, 'evict_to', 'hbk_hash_evict_to_n')
 
 
@@ -941,7 +1079,9 @@ def _evict_to(tables, max_sizes, keep_freq, slots, reports, what, entry):
   workspace = _EVICT_TO_WORKSPACES.get((dev, n))
   if workspace is None or workspace.numel() * 4 < nbytes:
     workspace = _EVICT_TO_WORKSPACES[(dev, n)] = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=dev)
+  before = _keys_before(tables) if what == 'evict_to' else None   # (the select writes nothing)
   _lib.check(call(n, cols, workspace.data_ptr(), workspace.numel() * 4, _lib.current_stream(dev)))
+  _record_swept(tables, before)
   return reports
 
 
@@ -1010,7 +1150,73 @@ def hash_spill(tables, max_sizes, keep_freq=0, slots=None):
                  'written between the two' + (' (it was left untouched)' if k > selected[c] else ''))
     result.append(HashExport(out['keys'][:k], out['rows'][:k], out['last_seen'][:k], out['freq'][:k],
                              [x[:k] for x in out['slots']], out['src_slots'][:k], 0))
+  for t, exp in zip(tables, result):
+    if t._removals is not None and len(exp):
+      t._removals.append(exp.keys.clone())   # what left is what was exported
   return result
+
+
+def hash_remove(tables, ids_list, slots=None, outs=None):
+  """:meth:`HashTable.remove` for N expiring tables in ONE C call (``hbk_hash_remove_n``: a find and an erase
+  launch per 32 tables).  ``ids_list[c]``: the int64 ids to take out of table c (duplicates, absent ids and the
+  sentinels are fine); ``slots[c]``: its ``(tensor, fill_value)`` companions as in :func:`hash_evict`; ``outs[c]``:
+  a preallocated int64 ``[n_ids]`` tensor or None.  Returns, per table, the slot every id held before the call or
+  -1.  The tables' arrays, their counters and the answers are functions of the inputs alone.  No workspace, no host
+  read, no sync: capturable -- a captured call removes, at every replay, whatever the id buffers then hold."""
+  tables = list(tables)
+  same_device(tables)
+  n = len(tables)
+  ids_list = list(ids_list)
+  slots, outs = _per_table(n, ('lists of companion tensors', slots, ()), ('outputs', outs, None))
+  for c, t in enumerate(tables):
+    if not t.expiring:
+      raise _bad(f'table {c}: remove needs a table built with expiring=True: a removed key leaves a TOMBSTONE '
+                 'behind, and a plain table has none (INT64_MIN + 1 is an ordinary key there)')
+  checked = [_companions(t, slots[c]) for c, t in enumerate(tables)]
+  check_ids(ids_list, tables)
+  if n == 0:
+    _lib.check(_lib.lib().hbk_hash_remove_n(0, None, None))
+    return []
+  dev = tables[0].keys.device
+  cols = (_lib.HashRemoveColumn * n)()
+  for c, (t, i) in enumerate(zip(tables, ids_list)):
+    _lib.require_device_tensor(t.keys, 'keys')
+    if outs[c] is None:
+      outs[c] = torch.empty(i.numel(), dtype=torch.int64, device=dev)
+    o = outs[c]
+    if not isinstance(o, torch.Tensor) or o.dtype != torch.int64 or tuple(o.shape) != (i.numel(),) or \
+        o.device != i.device or not o.is_contiguous():
+      raise _bad(f'output {c} must be a contiguous int64 [{i.numel()}] tensor on {i.device}')
+    col = cols[c]
+    col.keys_cache, col.slab_count, col.slab_size = t.keys.data_ptr(), t.slab_count, t.slab_size
+    t._describe_expiry(col.exp)
+    col.keys, col.n_keys, col.slots = i.data_ptr(), i.numel(), o.data_ptr()
+    col.n_removed = None
+    col.n_fills = len(checked[c])
+    for f, (x, value) in enumerate(checked[c]):
+      col.fills[f].base, col.fills[f].pitch, col.fills[f].dim = x.data_ptr(), x.stride(0), x.shape[1]
+      col.fills[f].value = value
+  _lib.check(_lib.lib().hbk_hash_remove_n(n, cols, _lib.current_stream(dev)))
+  for t, i, o in zip(tables, ids_list, outs):
+    if t._removals is not None and i.numel():
+      t._removals.append(torch.where(o >= 0, i, TOMBSTONE_KEY))   # (no sync; removed_keys drops the sentinel)
+  return outs
+
+
+def remove_tables(tables, ids_list, slots, stores):
+  """:func:`hash_remove` over the tables of a lookup object, and ``stores[c].discard`` where a store is named."""
+  if isinstance(stores, HashSpillStore):
+    stores = [stores]
+  ids_list = list(ids_list)
+  slots, stores = _per_table(len(tables), ('lists of companion tensors', slots, ()), ('spill stores', stores, None))
+  for c, (t, st) in enumerate(zip(tables, stores)):
+    if st is not None:
+      _check_store(st, t, slots[c])
+  out = hash_remove(tables, ids_list, slots)
+  for i, st in zip(ids_list, stores):
+    if st is not None and len(st):
+      st.discard(torch.unique(i).cpu())
+  return out
 
 
 def _check_store(store, table, slots):
@@ -1137,12 +1343,22 @@ class HashSpillStore:
     """:meth:`peek`, and the returned keys leave the store."""
     pos = self._locate(keys)
     out = self._export([self._gather(x, pos) for x in self._data])
+    self._drop(pos)
+    return out
+
+  def discard(self, keys):
+    """:meth:`take` without building the export: the requested keys the store holds leave it.  Returns their
+    number."""
+    pos = self._locate(keys)
+    self._drop(pos)
+    return int(pos.numel())
+
+  def _drop(self, pos):
     if pos.numel():
       keep = torch.ones(len(self), dtype=torch.bool)
       keep[pos] = False
       rest = keep.nonzero().flatten()
       self._data = [self._gather(x, rest) for x in self._data]
-    return out
 
   def variables(self, name):
     """The store's content as the flat dict ``training.saver.Saver.save`` takes (:meth:`HashExport.variables`)."""
@@ -1385,6 +1601,13 @@ class HashGroupLookup:
     ids, stores, slots = _per_table(n, ('id tensors', ids, None), ('spill stores', stores, None),
                                     ('lists of companion tensors', slots, ()))
     return [t.fault_in(ids[c], stores[c], slots[c]) for c, t in enumerate(self.tables)]
+
+  def remove(self, ids_list, slots=None, stores=None):
+    """:meth:`HashTable.remove` on every table in one call (:func:`hash_remove`): ``ids_list[c]`` the raw ids to take
+    out of column c, ``slots[c]`` its ``(tensor, fill_value)`` companions, ``stores[c]`` its
+    :class:`HashSpillStore` or None.  The row tensors do not move, so no :meth:`rebind` is needed; slots handed out
+    earlier for the removed ids are void.  Returns the old slots per table."""
+    return remove_tables(self.tables, ids_list, slots, stores)
 
   def __len__(self):
     return len(self.tables)

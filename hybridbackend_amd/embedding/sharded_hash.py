@@ -127,7 +127,8 @@ class ShardedHashGroupLookup(ShardedGroupLookup):
   def export_items(self, since=None):
     """:func:`hash_export` of this rank's tables in one call, the bound optimizer slots travelling as companions
     in the order Adagrad's ``accums``; Lazy Adam's ``moments`` m, v; FTRL's ``ftrl_slots`` accum, linear (those
-    that are bound).  ``since``: None, or the step of a delta -- every table must then be expiring.  Returns one
+    that are bound).  ``since``: None, or the step of a delta -- every table must then be expiring; with
+    :meth:`track_removals` on, the delta names the keys that left (``HashExport.removed``).  Returns one
     :class:`HashExport` per table.  Local to the rank: no exchange, and ranks need not agree."""
     self._current()
     n = len(self.tables)
@@ -137,14 +138,35 @@ class ShardedHashGroupLookup(ShardedGroupLookup):
     """``exports[c]``: a :class:`HashExport` of column c -- typically ``HashExport.cat`` of what every rank of the
     saving job exported, at whatever world size that was.  Each table upserts the keys THIS rank owns
     (``hash_owner(keys, world_size) == rank``) with rows, metadata and the bound optimizer slots (the order of
-    :meth:`export_items`); the tensors stay where they are, so the plan stays valid.  Returns the slots per
-    table.  Local to the rank: no exchange, and ranks need not agree."""
+    :meth:`export_items`), after the owned keys of ``removed`` left with the fill values of :meth:`maybe_grow`; the
+    tensors stay where they are, so the plan stays valid.  Returns the slots per table.  Local to the rank: no
+    exchange, and ranks need not agree."""
     self._current()
     exports = list(exports)
     if len(exports) != len(self.tables):
       raise _ht._bad(f'expected {len(self.tables)} exports, got {len(exports)}')   # pylint: disable=protected-access
-    return [t.import_items(e, self._slot_tensors(c), world=self.world_size, rank=self.coll.rank)
+    return [t.import_items(e, self._companions(c), world=self.world_size, rank=self.coll.rank)
             for c, (t, e) in enumerate(zip(self.tables, exports))]
+
+  def _companions(self, c):
+    """The bound optimizer slots of table c as ``(tensor, fill_value)`` pairs, the fill values of
+    :meth:`maybe_grow`."""
+    return list(zip(self._slot_tensors(c), [fill for _, _, fill in self._slot_kinds()]))
+
+  def remove(self, ids_list):
+    """:func:`hash_remove` on this rank's tables: the ids of ``ids_list[c]`` this rank's table c holds leave it,
+    the bound optimizer slots reset as companions with the fill values of :meth:`maybe_grow`.  Local to the rank:
+    ids the rank does not own are simply not found, there is no exchange, and ranks need not agree.  The tensors
+    stay where they are, so the plan stays valid.  Returns the old slots per table."""
+    self._current()
+    return _ht.hash_remove(self.tables, ids_list, [self._companions(c) for c in range(len(self.tables))])
+
+  def track_removals(self, on=True):
+    """:meth:`HashTable.track_removals` on every table of this rank (all must be expiring): what :meth:`remove`,
+    :meth:`maybe_evict` and the tables' own sweeps take out is recorded, and a delta :meth:`export_items` carries
+    it."""
+    for t in self.tables:
+      t.track_removals(on)
 
   def maybe_grow(self, max_load=0.75, factor=2.0):
     """:meth:`HashTable.maybe_grow` on every table of this rank, the bound optimizer slots moving along as
@@ -169,8 +191,7 @@ class ShardedHashGroupLookup(ShardedGroupLookup):
            for name, k, _ in kinds}
     grown = []
     for c, t in enumerate(self.tables):
-      comp = [((getattr(self, name)[c] if k is None else getattr(self, name)[c][k]), fill) for name, k, fill in kinds]
-      out = policy(t, comp)
+      out = policy(t, self._companions(c))
       grown.append(out is not None)
       for (name, k, _), x in zip(kinds, out or ()):
         if k is None:

@@ -873,6 +873,54 @@ int hbk_hash_evict_to_n(int32_t n_cols, const hbk_hash_evict_to_column_t* cols, 
 int hbk_hash_evict_to_select_n(int32_t n_cols, const hbk_hash_evict_to_column_t* cols, void* workspace,
                                size_t workspace_bytes, hbk_stream_t stream);
 
+/* Removal by id: the keys the caller names leave (tf.lookup's mutable tables have remove; the reference's
+ * EmbeddingService removes entries by index: hybridbackend/tensorflow/embedding/service.py:180-210).  The sweeps
+ * above decide by age; hbk_hash_remove_n takes a list.  Expiring tables only: a plain table has no TOMBSTONE, and
+ * INT64_MIN + 1 is an ordinary key there.  Per table:
+ *     slots[i] = the slot keys[i] held BEFORE the call, or -1 -- for every occurrence, duplicates included; the ids
+ *                EMPTY and TOMBSTONE give -1
+ *     every distinct id that was found leaves exactly as hbk_hash_evict_n makes a key leave: key = TOMBSTONE (never
+ *     EMPTY: the probe's invariant holds, keys that spilled past the slot's slab are still found), last_seen =
+ *     freq = 0, and for each of the n_fills companion arrays base[slot * pitch + j] = value for j < dim, the
+ *     padding up to pitch not written.  The embedding row is left as it is: the next inserter writes it.
+ *     stats[0] and *n_removed (device int32 or NULL; the CALLER zeroes it, the call adds to it) grow by the number
+ *     of DISTINCT ids removed: live keys = n_inserted - n_evicted stays right.  counts, an admission sketch and
+ *     stats[1] are not touched.
+ * Every array, both counters and slots are functions of the inputs alone: the same on every run.
+ *
+ * Two launches per 32 columns on the call's stream.  The first is the pure find of the expiring kind
+ * (hbk_hash_insert_expiring_n with insert == 0: plain loads, no counter; a column of 2^30 keys or more goes
+ * through it in parts) and writes slots.  The second is tiled over the occurrences: a lane with slots[i] >= 0
+ * swaps keys[slot]: id -> TOMBSTONE with a 64-bit agent-scope compare-and-swap; of the occurrences of an id
+ * exactly one wins, stores the metadata zeros, and the wave fills its winners' companion rows with lane groups of
+ * pow2(dim) lanes; one atomic per wave and counter.  The kernel boundary between the two is what makes slots
+ * deterministic: in one fused kernel a duplicate that walks after the winner's swap would answer -1.  Which
+ * occurrence wins is not fixed, and nothing written depends on it.
+ *
+ * Stream-ordered against the translates, sweeps and backwards of its tables, never beside one.  No workspace, no
+ * host synchronisation: capturable.  It reads, per occurrence, the 8-byte id, the slabs of its walk and writes an
+ * 8-byte slot; per removed key the 8-byte swap, 8 bytes of metadata and the fills' rows.
+ *
+ * Refused (HBK_INVALID_ARGUMENT) before any device work, naming the column and the field: what hbk_hash_evict_n
+ * refuses of keys_cache, slab_count, slab_size and the fills; a table of 2^31 slots or more (the counters are
+ * int32); NULL last_seen or freq; NULL keys or slots with n_keys > 0; n_keys outside [0, 2^31); 32 consecutive
+ * columns whose find would need a grid of 2^31 tiles (only at slab_size above 32, with nearly 2^31 ids in each).  More
+ * than 32 columns with keys run as groups of 32, a group's find and erase before the next group's.  exp.step is not
+ * read and may be NULL.  Detected by the presence of the symbol; the version stays that of 0.2.0. */
+typedef struct {
+  int64_t* keys_cache;    /* device [slab_count * slab_size], 8-byte aligned */
+  int64_t slab_count;
+  int32_t slab_size;      /* 1..64 */
+  hbk_hash_expiry_t exp;  /* last_seen, freq and stats are used; step is not read */
+  const int64_t* keys;    /* device [n_keys]: the ids to remove */
+  int64_t n_keys;
+  int64_t* slots;         /* device [n_keys], written: the slot every id held before the call, or -1 */
+  int32_t* n_removed;     /* device int32, added to: the distinct ids removed; or NULL */
+  int32_t n_fills;        /* 0..HBK_HASH_MAX_FILLS */
+  hbk_hash_fill_t fills[HBK_HASH_MAX_FILLS];
+} hbk_hash_remove_column_t;
+int hbk_hash_remove_n(int32_t n_cols, const hbk_hash_remove_column_t* cols, hbk_stream_t stream);
+
 /* Admission filter: a count-min sketch gates new ids (DeepRec's CounterFilter / CBFFilter beside
  * steps_to_live).  Most distinct ids of a click log occur once or twice; unfiltered, each of them claims a row,
  * its optimizer slots and a key slot at first sight.  A filtered table stores an id once it was seen min_freq
