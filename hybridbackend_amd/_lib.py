@@ -268,6 +268,9 @@ def _declare(l):
     'hbk_hash_evict_to_workspace_bytes': (sz, [i32]),
     'hbk_hash_evict_to_n': (C.c_int, [i32, vp, vp, sz, vp]),
     'hbk_hash_evict_to_select_n': (C.c_int, [i32, vp, vp, sz, vp]),
+    'hbk_hash_evict_to_lfu_workspace_bytes': (sz, [i32]),
+    'hbk_hash_evict_to_lfu_n': (C.c_int, [i32, vp, vp, sz, vp]),
+    'hbk_hash_evict_to_lfu_select_n': (C.c_int, [i32, vp, vp, sz, vp]),
     'hbk_hash_remove_n': (C.c_int, [i32, vp, vp]),
     'hbk_hash_insert_admit_n': (C.c_int, [i32, vp, vp, i32, vp]),
     'hbk_hash_insert_expiring_admit_n': (C.c_int, [i32, vp, vp, vp, i32, vp]),
@@ -279,6 +282,7 @@ def _declare(l):
     'hbk_hash_store_rows_n': (C.c_int, [i32, vp, vp]),
     'hbk_hash_spill_workspace_bytes': (C.c_int, [i32, vp, vp]),
     'hbk_hash_spill_n': (C.c_int, [i32, vp, vp, vp]),
+    'hbk_hash_spill_lfu_n': (C.c_int, [i32, vp, vp, vp]),
     'hbk_comm_get_id': (C.c_int, [vp]),
     'hbk_comm_rccl_versions': (C.c_int, [vp, vp]),
     'hbk_comm_create': (C.c_int, [vp, vp, i32, i32, i32]),

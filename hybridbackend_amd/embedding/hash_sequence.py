@@ -210,11 +210,12 @@ class HashSequenceLookup:
     tensors."""
     return grow_tables(self, self.hash_tables, max_load, factor, slots)
 
-  def maybe_evict(self, max_load=0.75, target_load=0.5, keep_freq=0, slots=None):
-    """:meth:`HashTable.maybe_evict` on every table (``slots[c]``: the companions of table c), then
+  def maybe_evict(self, max_load=0.75, target_load=0.5, keep_freq=0, slots=None, order='lru'):
+    """:meth:`HashTable.maybe_evict` on every table (``slots[c]``: the companions of table c; ``order``: ``'lru'``
+    or ``'lfu'``), then
     :meth:`rebind` if any table was rehashed.  Returns the per-table results: None, or the new companion
     tensors."""
-    return evict_tables(self, self.hash_tables, max_load, target_load, keep_freq, slots)
+    return evict_tables(self, self.hash_tables, max_load, target_load, keep_freq, slots, order=order)
 
   def remove(self, ids_list, slots=None, stores=None):
     """:meth:`HashGroupLookup.remove`: the ids of ``ids_list[c]`` leave table c (``slots[c]``: its ``(tensor,

@@ -30,6 +30,8 @@ of any captured graph.
 Bounded tables (``hbk_hash_evict_to_n``): :meth:`HashTable.evict_to` / :func:`hash_evict_to` evict the oldest keys
 down to a size bound, the cut found on the device (whole steps leave together: no exact size, no tie-break);
 :meth:`HashTable.maybe_evict` / :meth:`HashGroupLookup.maybe_evict` are ``maybe_grow`` for a fixed memory budget.
+``order='lfu'`` (``hbk_hash_evict_to_lfu_n``) on any of them picks the least frequently used keys instead, the oldest
+first among equally frequent ones; :meth:`HashTable.age_freq` lets old popularity fade.
 
 Spilling to a host tier (``hbk_hash_evict_to_select_n`` / ``hbk_hash_spill_n``): :meth:`HashTable.spill_to` /
 :func:`hash_spill` export exactly the keys an ``evict_to`` would remove -- rows, ``last_seen``, ``freq`` and the
@@ -127,8 +129,9 @@ class HashTable:
   is admitted again at once unless :meth:`clear_filter` or :meth:`age_filter` ran.
 
   Attributes of an expiring table: ``last_seen`` / ``freq`` int32 ``[capacity]`` (the step of a slot's last
-  translate with ``insert=True`` and its occurrences so far, saturating at 2^30), ``step`` int32 ``[1]`` on
-  the device (:meth:`set_step`), ``stats`` int32 ``[2]`` = keys evicted / keys stored into a reused slot.
+  translate with ``insert=True`` and its occurrences so far, saturating at 2^30; :meth:`age_freq` lets them
+  fade), ``step`` int32 ``[1]`` on the device (:meth:`set_step`), ``stats`` int32 ``[2]`` = keys evicted / keys
+  stored into a reused slot.
 
   Attributes: ``keys`` int64 ``[slab_count * slab_size]`` (EMPTY = INT64_MIN), ``table`` fp32
   ``[capacity, dim]``, ``counts`` int32 ``[2]`` = keys inserted (since the last rehash or compact: the keys it
@@ -320,7 +323,8 @@ class HashTable:
     self.sketch.zero_()
 
   def age_filter(self):
-    """Halve every counter in place (``>>= 1``): old sightings fade."""
+    """Halve every counter in place (``>>= 1``): old sightings fade.  (:meth:`age_freq` does the same to the
+    per-slot ``freq`` of an expiring table.)"""
     self._need_filter('age_filter')
     self.sketch.bitwise_right_shift_(1)
 
@@ -329,6 +333,18 @@ class HashTable:
     """The current step, on the device: an in-place fill (capturable; replayed launches see it)."""
     self._need_expiring('set_step')
     self.step.fill_(int(n))
+
+  def age_freq(self, shift=1):
+    """Shift every slot's ``freq`` right in place (``>>= shift``; 1 halves it): old popularity fades, as
+    :meth:`age_filter` lets old sightings fade in the sketch.  The count saturates at 2^30 and otherwise never
+    forgets, so a table bounded with ``order='lfu'`` calls this now and then -- else an id that was hot long ago
+    outlives everything newer.  Stream-ordered, no host read (capturable); keys and ``last_seen`` are not touched.
+    ``shift`` must be in [1, 30]."""
+    self._need_expiring('age_freq')
+    shift = int(shift)
+    if not 1 <= shift <= 30:
+      raise _bad(f'age_freq: shift must be in [1, 30], got {shift}')
+    self.freq.bitwise_right_shift_(shift)
 
   def evict(self, steps_to_live, keep_freq=0, slots=()):
     """One sweep launch (``hbk_hash_evict_n``): a key whose slot was last seen ``steps_to_live`` or more steps
@@ -469,7 +485,7 @@ class HashTable:
     return self.rehash(capacity=int(math.ceil(self.capacity * factor)), slots=slots)
 
   # ---- a size bound ---------------------------------------------------------------------------------------
-  def evict_to(self, max_size, keep_freq=0, slots=(), report=None):
+  def evict_to(self, max_size, keep_freq=0, slots=(), report=None, order='lru'):
     """The oldest keys leave until at most ``max_size`` stay (``hbk_hash_evict_to_n``): with ``need = size() -
     max_size > 0``, every key whose ``last_seen`` is at or below the smallest step that covers ``need`` keys is
     evicted as :meth:`evict` evicts.  Whole steps leave together -- keys last seen at the same step are equally
@@ -478,10 +494,16 @@ class HashTable:
     table may then stay above the bound).  ``slots``: as in :meth:`evict`.  The step counter is not read.
     Returns the report, int32 ``[4]`` on the device: ``{live_before, need, cut, n_evicted}`` (``report``: a
     preallocated one, for a captured call).  No host read, no sync -- unless the table tracks its removals
-    (:meth:`track_removals`): one key-array copy and one host synchronisation then, and no capture."""
-    return hash_evict_to([self], [max_size], keep_freq, [slots], [report])[0]
+    (:meth:`track_removals`): one key-array copy and one host synchronisation then, and no capture.
 
-  def maybe_evict(self, max_load=0.75, target_load=0.5, keep_freq=0, slots=(), spill=None):
+    ``order='lfu'`` (``hbk_hash_evict_to_lfu_n``): the LEAST FREQUENTLY USED keys leave instead -- the order is the
+    pair (``freq``, ``last_seen``), least frequent first, the oldest first among equally frequent keys; keys with
+    equal (``freq``, ``last_seen``) leave together, so the undershoot is less than one such class.  The report is
+    then int32 ``[8]``: ``{live_before, need, cut_freq, cut_last_seen, n_evicted, 0, 0, 0}``.  See
+    :meth:`age_freq`."""
+    return hash_evict_to([self], [max_size], keep_freq, [slots], [report], order=order)[0]
+
+  def maybe_evict(self, max_load=0.75, target_load=0.5, keep_freq=0, slots=(), spill=None, order='lru'):
     """The bounded-memory twin of :meth:`maybe_grow`: the capacity never changes.  Decided from ONE host read of
     ``counts`` and ``stats``: nothing (None) while at most ``max_load`` of the slots are occupied (keys and
     tombstones); else, when the live keys exceed ``target_load * capacity``, :meth:`evict_to`
@@ -489,8 +511,10 @@ class HashTable:
     turned up to ``max_load - target_load`` of the slots into tombstones, and a table full of them translates
     slowly; else (tombstones were the load) the rehash alone.  Returns the new companion tensors of ``slots``
     (see :meth:`rehash` for what a rehash invalidates).  ``spill``: a :class:`HashSpillStore` -- when the call
-    evicts it uses :meth:`spill_to` where it used :meth:`evict_to`: the keys that leave go to the store."""
+    evicts it uses :meth:`spill_to` where it used :meth:`evict_to`: the keys that leave go to the store.
+    ``order``: ``'lru'`` or ``'lfu'``, which keys leave when it evicts or spills (:meth:`evict_to`)."""
     self._need_expiring('maybe_evict')
+    order = _check_order(order)
     max_load, target_load = _check_loads(max_load, target_load)
     if int(keep_freq) < 0:
       raise _bad(f'keep_freq must be >= 0, got {keep_freq}')
@@ -503,23 +527,25 @@ class HashTable:
     if live > target_load * self.capacity:
       bound = int(math.floor(target_load * self.capacity))
       if spill is None:
-        self.evict_to(bound, keep_freq, slots)
+        self.evict_to(bound, keep_freq, slots, order=order)
       else:
-        self.spill_to(bound, spill, keep_freq, slots)
+        self.spill_to(bound, spill, keep_freq, slots, order=order)
     return self.rehash(slots=slots)
 
   # ---- a host tier behind the bound -----------------------------------------------------------------------
-  def spill_to(self, max_size, store=None, keep_freq=0, slots=()):
+  def spill_to(self, max_size, store=None, keep_freq=0, slots=(), order='lru'):
     """:meth:`evict_to` that keeps what it evicts (``hbk_hash_evict_to_select_n`` / ``hbk_hash_spill_n``): the
     keys an ``evict_to(max_size, keep_freq)`` would remove are exported -- row, ``last_seen``, ``freq`` and the rows
     of the companions -- and then evicted as :meth:`evict_to` evicts.  ``slots``: ``(tensor, fill_value)`` pairs
     as in :meth:`evict`: the tensor is exported, then reset to the value.  ``store``: a :class:`HashSpillStore`
     that takes the export (``store.put``).  Returns the :class:`HashExport`, on the device, in ascending slot
-    order.  Two host reads (the selection's size, the export's count): see :func:`hash_spill`."""
+    order.  Two host reads (the selection's size, the export's count): see :func:`hash_spill`.  ``order``:
+    ``'lru'`` or ``'lfu'`` as in :meth:`evict_to` (``hbk_hash_evict_to_lfu_select_n`` / ``hbk_hash_spill_lfu_n``)."""
     self._need_expiring('spill_to')
+    order = _check_order(order)
     if store is not None:
       _check_store(store, self, slots)   # (before anything leaves the table)
-    exp = hash_spill([self], [max_size], keep_freq, [slots])[0]
+    exp = hash_spill([self], [max_size], keep_freq, [slots], order=order)[0]
     if store is not None and len(exp):
       store.put(exp)
     return exp
@@ -1018,9 +1044,25 @@ def _describe_sweep(col, t, keep_freq, pairs):
 
 
 _EVICT_TO_WORKSPACES = {}   # (device, n_tables) -> int32 scratch: the same address at every call, so a captured call replays
+_EVICT_TO_LFU_WORKSPACES = {}   # the same for order='lfu'
+
+# order -> (words of a report, the C entries of the sweep, of the select and of the workspace size, the scratch)
+_EVICT_TO_ORDERS = {
+  'lru': (4, 'hbk_hash_evict_to_n', 'hbk_hash_evict_to_select_n', 'hbk_hash_evict_to_workspace_bytes',
+          _EVICT_TO_WORKSPACES),
+  'lfu': (8, 'hbk_hash_evict_to_lfu_n', 'hbk_hash_evict_to_lfu_select_n', 'hbk_hash_evict_to_lfu_workspace_bytes',
+          _EVICT_TO_LFU_WORKSPACES),
+}
 
 
-def hash_evict_to(tables, max_sizes, keep_freq=0, slots=None, reports=None):
+def _check_order(order):
+  """``'lru'`` or ``'lfu'``; anything else is refused by name."""
+  if not isinstance(order, str) or order not in _EVICT_TO_ORDERS:
+    raise _bad(f"order must be 'lru' or 'lfu', got {order!r}")
+  return order
+
+
+def hash_evict_to(tables, max_sizes, keep_freq=0, slots=None, reports=None, order='lru'):
   """:meth:`HashTable.evict_to` for N expiring tables in ONE C call (``hbk_hash_evict_to_n``): per table the
   oldest keys leave until at most ``max_sizes[c]`` stay -- the cut is found on the device, three histogram passes
   over ``last_seen`` and a sweep, no host read.  ``max_sizes``: one int for all tables or one per table.
@@ -1029,20 +1071,27 @@ def hash_evict_to(tables, max_sizes, keep_freq=0, slots=None, reports=None):
   call.  Returns the list of reports; does not sync.  The scratch tensor is kept per (device, number of tables),
   so a captured call replays.  With a table that tracks its removals (:meth:`HashTable.track_removals`) the call
   copies that table's key array first, compares after the sweep with one host synchronisation, and is refused inside
-  a stream capture."""
-  return _evict_to(tables, max_sizes, keep_freq, slots, reports, 'evict_to', 'hbk_hash_evict_to_n')
+  a stream capture.
+
+  ``order='lfu'`` (``hbk_hash_evict_to_lfu_n``): the least frequently used keys leave, the oldest first among
+  equally frequent ones -- six histogram passes over (``freq``, ``last_seen``) and a sweep.  ``reports[c]`` is then
+  int32 ``[8]``: ``{live_before, need, cut_freq, cut_last_seen, n_evicted, 0, 0, 0}``."""
+  return _evict_to(tables, max_sizes, keep_freq, slots, reports, 'evict_to', _check_order(order))
 
 
-def hash_evict_to_select(tables, max_sizes, keep_freq=0, reports=None):
+def hash_evict_to_select(tables, max_sizes, keep_freq=0, reports=None, order='lru'):
   """The selection of :func:`hash_evict_to` without its sweep (``hbk_hash_evict_to_select_n``): nothing of the
   tables is written.  Returns the reports, int32 ``[4]`` on the device: ``{live_before, need, cut, n_selected}`` --
   ``n_selected`` is the exact number of keys ``hash_evict_to`` with the same arguments would evict.  ``reports``:
-  preallocated ones.  No host read, no sync."""
-  return _evict_to(tables, max_sizes, keep_freq, None, reports, 'evict_to_select', 'hbk_hash_evict_to_select_n')
+  preallocated ones.  No host read, no sync.  ``order='lfu'`` (``hbk_hash_evict_to_lfu_select_n``): int32 ``[8]``,
+  ``{live_before, need, cut_freq, cut_last_seen, n_selected, 0, 0, 0}``."""
+  return _evict_to(tables, max_sizes, keep_freq, None, reports, 'evict_to_select', _check_order(order))
 
 
-def _evict_to(tables, max_sizes, keep_freq, slots, reports, what, entry):
-  """Both entries of the select: ``entry`` is the C entry, ``what`` names the call in a refusal."""
+def _evict_to(tables, max_sizes, keep_freq, slots, reports, what, order):
+  """Both entries of the select, in either order: ``what`` names the call in a refusal and picks the C entry."""
+  words, sweep_entry, select_entry, size_entry, workspaces = _EVICT_TO_ORDERS[order]
+  entry = sweep_entry if what == 'evict_to' else select_entry
   tables = list(tables)
   same_device(tables)
   n = len(tables)
@@ -1065,27 +1114,27 @@ def _evict_to(tables, max_sizes, keep_freq, slots, reports, what, entry):
   dev = tables[0].keys.device
   cols = (_lib.HashEvictToColumn * n)()
   for c, r in enumerate(reports):
-    if r is not None and (not isinstance(r, torch.Tensor) or r.dtype != torch.int32 or tuple(r.shape) != (4,) or
+    if r is not None and (not isinstance(r, torch.Tensor) or r.dtype != torch.int32 or tuple(r.shape) != (words,) or
                           r.device != dev or not r.is_contiguous()):
-      raise _bad(f'reports[{c}] must be a contiguous int32 [4] tensor on {dev}')
+      raise _bad(f'reports[{c}] must be a contiguous int32 [{words}] tensor on {dev}')
   for c, t in enumerate(tables):
     _lib.require_device_tensor(t.keys, 'keys')
     if reports[c] is None:
-      reports[c] = torch.zeros(4, dtype=torch.int32, device=dev)
+      reports[c] = torch.zeros(words, dtype=torch.int32, device=dev)
     _describe_sweep(cols[c], t, keep_freq, checked[c])
     cols[c].max_size = max_sizes[c]
     cols[c].report = reports[c].data_ptr()
-  nbytes = lib.hbk_hash_evict_to_workspace_bytes(n)
-  workspace = _EVICT_TO_WORKSPACES.get((dev, n))
+  nbytes = getattr(lib, size_entry)(n)
+  workspace = workspaces.get((dev, n))
   if workspace is None or workspace.numel() * 4 < nbytes:
-    workspace = _EVICT_TO_WORKSPACES[(dev, n)] = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=dev)
+    workspace = workspaces[(dev, n)] = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=dev)
   before = _keys_before(tables) if what == 'evict_to' else None   # (the select writes nothing)
   _lib.check(call(n, cols, workspace.data_ptr(), workspace.numel() * 4, _lib.current_stream(dev)))
   _record_swept(tables, before)
   return reports
 
 
-def hash_spill(tables, max_sizes, keep_freq=0, slots=None):
+def hash_spill(tables, max_sizes, keep_freq=0, slots=None, order='lru'):
   """:meth:`HashTable.spill_to` for N expiring tables: the keys :func:`hash_evict_to` with the same arguments would
   evict leave the tables WITH their payload.  Returns one :class:`HashExport` per table, on the device, in ascending
   slot order: keys, rows, ``last_seen``, ``freq`` and the rows of the companions as they were before the call.
@@ -1098,7 +1147,12 @@ def hash_spill(tables, max_sizes, keep_freq=0, slots=None):
   predicate, then the sweep, which leaves a table alone whose selected keys do not all fit the output; ONE host
   read of the counts, and a count that differs from its ``n_selected`` is refused (somebody wrote the table between
   the two calls; a table with more keys than promised was not touched).  Must not run beside a translate, a sweep
-  or a backward of the same tables on another stream."""
+  or a backward of the same tables on another stream.
+
+  ``order='lfu'``: the keys ``hash_evict_to(..., order='lfu')`` would evict -- the select and the spill are then
+  ``hbk_hash_evict_to_lfu_select_n`` and ``hbk_hash_spill_lfu_n``; the steps and the host reads are the same."""
+  order = _check_order(order)
+  lfu = order == 'lfu'
   tables = list(tables)
   same_device(tables)
   n = len(tables)
@@ -1107,13 +1161,14 @@ def hash_spill(tables, max_sizes, keep_freq=0, slots=None):
   for t in tables:
     t._need_expiring('spill_to')
   checked = [_companions(t, slots[c]) for c, t in enumerate(tables)]
-  reports = hash_evict_to_select(tables, max_sizes, keep_freq)
+  reports = hash_evict_to_select(tables, max_sizes, keep_freq, order=order)
   lib = _lib.lib()
+  spill = lib.hbk_hash_spill_lfu_n if lfu else lib.hbk_hash_spill_n
   if n == 0:
-    _lib.check(lib.hbk_hash_spill_n(0, None, None, None))
+    _lib.check(spill(0, None, None, None))
     return []
   dev = tables[0].keys.device
-  selected = [r[3] for r in torch.stack(reports).tolist()]   # the one host read of the selection
+  selected = [r[4 if lfu else 3] for r in torch.stack(reports).tolist()]   # the one host read of the selection
   cols = (_lib.HashSpillColumn * n)()
   counts = torch.zeros(n, dtype=torch.int64, device=dev)
   n_evicted = torch.zeros(n, dtype=torch.int32, device=dev)
@@ -1142,7 +1197,7 @@ def hash_spill(tables, max_sizes, keep_freq=0, slots=None):
   nbytes = C.c_size_t()
   _lib.check(lib.hbk_hash_spill_workspace_bytes(n, cols, C.byref(nbytes)))
   workspace = torch.empty(max(nbytes.value // 8, 1), dtype=torch.int64, device=dev)
-  _lib.check(lib.hbk_hash_spill_n(n, cols, workspace.data_ptr(), _lib.current_stream(dev)))
+  _lib.check(spill(n, cols, workspace.data_ptr(), _lib.current_stream(dev)))
   result = []
   for c, (k, out) in enumerate(zip(counts.tolist(), outs)):
     if k != selected[c]:
@@ -1532,14 +1587,16 @@ def grow_tables(lookup, tables, max_load, factor, slots):
   return out
 
 
-def evict_tables(lookup, tables, max_load, target_load, keep_freq, slots, spill=None):
+def evict_tables(lookup, tables, max_load, target_load, keep_freq, slots, spill=None, order='lru'):
   """:meth:`HashTable.maybe_evict` on every table, then ``lookup.rebind()`` if any was rehashed.  ``spill``: one
-  :class:`HashSpillStore` per table (a single store for a single table), or None."""
+  :class:`HashSpillStore` per table (a single store for a single table), or None.  ``order``: ``'lru'`` or ``'lfu'``,
+  for every table."""
+  order = _check_order(order)
   if isinstance(spill, HashSpillStore):
     spill = [spill]
   slots, spill = _per_table(len(tables), ('lists of companion tensors', slots, ()), ('spill stores', spill, None))
   _check_loads(max_load, target_load)
-  out = [t.maybe_evict(max_load, target_load, keep_freq, slots[c], spill[c]) for c, t in enumerate(tables)]
+  out = [t.maybe_evict(max_load, target_load, keep_freq, slots[c], spill[c], order) for c, t in enumerate(tables)]
   if any(o is not None for o in out):
     lookup.rebind()
   return out
@@ -1586,12 +1643,12 @@ class HashGroupLookup:
     tensors.  See :meth:`rebind` for what must be rebuilt afterwards."""
     return grow_tables(self, self.tables, max_load, factor, slots)
 
-  def maybe_evict(self, max_load=0.75, target_load=0.5, keep_freq=0, slots=None, spill=None):
+  def maybe_evict(self, max_load=0.75, target_load=0.5, keep_freq=0, slots=None, spill=None, order='lru'):
     """:meth:`HashTable.maybe_evict` on every table (``slots[c]``: the companions of table c; ``spill``: one
-    :class:`HashSpillStore` per table, or None), then :meth:`rebind` if any table was rehashed.  Returns the
-    per-table results: None, or the new companion tensors.  See :meth:`rebind` for what must be rebuilt
-    afterwards."""
-    return evict_tables(self, self.tables, max_load, target_load, keep_freq, slots, spill)
+    :class:`HashSpillStore` per table, or None; ``order``: ``'lru'`` or ``'lfu'``), then :meth:`rebind` if any table
+    was rehashed.  Returns the per-table results: None, or the new companion tensors.  See :meth:`rebind` for what
+    must be rebuilt afterwards."""
+    return evict_tables(self, self.tables, max_load, target_load, keep_freq, slots, spill, order)
 
   def fault_in(self, ids, stores, slots=None):
     """:meth:`HashTable.fault_in` per table, before the call of the step: ``ids[c]`` the raw ids of column c,

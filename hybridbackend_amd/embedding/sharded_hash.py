@@ -176,13 +176,15 @@ class ShardedHashGroupLookup(ShardedGroupLookup):
     whether it was rehashed."""
     return self._maybe(lambda t, comp: t.maybe_grow(max_load, factor, comp))
 
-  def maybe_evict(self, max_load=0.75, target_load=0.5, keep_freq=0):
-    """:meth:`HashTable.maybe_evict` on every table of this rank -- the capacity stays, the oldest keys leave --
+  def maybe_evict(self, max_load=0.75, target_load=0.5, keep_freq=0, order='lru'):
+    """:meth:`HashTable.maybe_evict` on every table of this rank -- the capacity stays, the oldest keys leave
+    (``order='lfu'``: the least frequently used ones) --
     with the bound optimizer slots as companions and the fill values of :meth:`maybe_grow`, then :meth:`rebind`
     with the new tensors if any table was rehashed.  Local to the rank: no exchange, and ranks need not agree.
     Returns per table whether it was rehashed."""
     _ht._check_loads(max_load, target_load)   # pylint: disable=protected-access
-    return self._maybe(lambda t, comp: t.maybe_evict(max_load, target_load, keep_freq, comp))
+    _ht._check_order(order)   # pylint: disable=protected-access
+    return self._maybe(lambda t, comp: t.maybe_evict(max_load, target_load, keep_freq, comp, order=order))
 
   def _maybe(self, policy):
     """``policy(table, companions)`` -> None or the new companions, on every table; the rebind that follows."""

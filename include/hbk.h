@@ -823,8 +823,8 @@ int hbk_hash_evict_n(int32_t n_cols, const hbk_hash_evict_column_t* cols, hbk_st
  * after the call is <= max_size (unless the frequency guard kept it above) and undershoots the bound by less
  * than the keys of one step -- those with last_seen == cut.  There is no tie-break: the evicted set is a
  * function of the table's arrays alone, the same on every run and whatever slots the keys sit in (the
- * reference's top_k picks arbitrarily among ties).  Not an exact size, and not an LFU order: keep_freq is the
- * only use of freq.
+ * reference's top_k picks arbitrarily among ties).  Not an exact size.  This entry orders by age alone and
+ * keep_freq is its only use of freq; hbk_hash_evict_to_lfu_n (below) orders by (freq, last_seen).
  *
  * report (device int32[4] or NULL), written by the call: {live_before, need, cut, n_evicted}; cut is 0 when
  * need <= 0.
@@ -872,6 +872,56 @@ int hbk_hash_evict_to_n(int32_t n_cols, const hbk_hash_evict_to_column_t* cols, 
  * hbk_hash_evict_to_n itself is unchanged: the fourth word of its report stays the sweep's own count. */
 int hbk_hash_evict_to_select_n(int32_t n_cols, const hbk_hash_evict_to_column_t* cols, void* workspace,
                                size_t workspace_bytes, hbk_stream_t stream);
+
+/* Bounded tables in LFU order: the LEAST FREQUENTLY USED keys leave first (DeepRec's multi-tier EmbeddingVariable
+ * offers LRU and LFU caches).  hbk_hash_evict_to_n orders by last_seen alone; hbk_hash_evict_to_lfu_n orders by the
+ * pair (freq, last_seen): least frequent first, among equally frequent keys the oldest first, both fields compared
+ * as SIGNED int32 (an import may carry any value).  As one 64-bit key
+ *     k(slot) = ((uint64)(freq ^ 0x80000000) << 32) | (uint32)(last_seen ^ 0x80000000)
+ * Per table, live, evictable (the keep_freq guard) and need = L - max_size are hbk_hash_evict_to_n's, and
+ *     cut       = the smallest k with  #{evictable : k(slot) <= cut} >= need;  fewer than `need` evictable slots:
+ *                 every evictable slot goes, the table stays above the bound, and the report says
+ *                 cut_freq = cut_last_seen = INT32_MAX
+ * and every evictable slot with k(slot) <= cut leaves exactly as the other sweeps make a key leave: key = TOMBSTONE,
+ * last_seen = freq = 0, the rows of the n_fills companion arrays = their value (the padding up to the pitch not
+ * written), stats[0] += the slots evicted.  need <= 0: nothing is written to the table's arrays.  *step is not
+ * read.
+ *
+ * WHOLE CLASSES LEAVE TOGETHER.  Keys with equal (freq, last_seen) are equally cold, so all of them go: the size
+ * after the call is <= max_size (unless the frequency guard kept it above) and undershoots the bound by less than
+ * one such class -- the slots with k == cut.  There is no tie-break by slot: the evicted set is a function of the
+ * table's arrays alone, the same on every run.
+ *
+ * report (device int32[8] or NULL -- EIGHT words, not the four of hbk_hash_evict_to_n), written by the call:
+ *     {live_before, need, cut_freq, cut_last_seen, n_evicted, 0, 0, 0}
+ * both cuts are 0 when need <= 0.
+ *
+ * The selection is the radix select of hbk_hash_evict_to_n carried over k: SIX digits, most significant first,
+ * 11 / 11 / 10 bits over freq, then 11 / 11 / 10 over last_seen; per digit one streaming histogram pass (16 bytes
+ * per slot; per-workgroup LDS histogram, a wave's hits on its leading lane's bin added once -- real counts pile up
+ * on 1 and 2 --, integer atomics into the table's histogram: an order-independent sum) and one pick kernel per
+ * table that carries the 64-bit prefix and the need that remains; a slot takes part in a digit only if its higher
+ * digits equal the prefix.  Then the sweep.  The passes after the first leave at once for a table with need <= 0.
+ * 32 tables per launch, more are chunked.  No host read anywhere; the call clears its workspace on the stream, so
+ * it can be captured into a graph and replayed.
+ *
+ * Same struct as hbk_hash_evict_to_n (report -> int32[8]), the same argument checks and refusal texts under the
+ * names hash_evict_to_lfu_n / hash_evict_to_lfu_select_n, refused before any device work; workspace: device memory
+ * of hbk_hash_evict_to_lfu_workspace_bytes(n_cols) bytes, 4-byte aligned, contents scratch.
+ *
+ * hbk_hash_evict_to_lfu_select_n is the selection alone -- the clear launch and the six digit passes, no sweep,
+ * nothing of the table written, report required -- and writes {live_before, need, cut_freq, cut_last_seen,
+ * n_selected, 0, 0, 0}: n_selected is the exact number of slots the sweep would evict, as it falls out of the
+ * select.  Its report is what hbk_hash_spill_lfu_n takes as its selection.
+ *
+ * freq saturates at 2^30 and otherwise never forgets; callers let old popularity fade by shifting freq right in
+ * place between calls (Python: HashTable.age_freq).  Detected by the presence of the symbols; the version stays
+ * that of 0.2.0. */
+size_t hbk_hash_evict_to_lfu_workspace_bytes(int32_t n_cols);
+int hbk_hash_evict_to_lfu_n(int32_t n_cols, const hbk_hash_evict_to_column_t* cols, void* workspace,
+                            size_t workspace_bytes, hbk_stream_t stream);
+int hbk_hash_evict_to_lfu_select_n(int32_t n_cols, const hbk_hash_evict_to_column_t* cols, void* workspace,
+                                   size_t workspace_bytes, hbk_stream_t stream);
 
 /* Removal by id: the keys the caller names leave (tf.lookup's mutable tables have remove; the reference's
  * EmbeddingService removes entries by index: hybridbackend/tensorflow/embedding/service.py:180-210).  The sweeps
@@ -1306,6 +1356,19 @@ typedef struct {
 } hbk_hash_spill_column_t;
 int hbk_hash_spill_workspace_bytes(int32_t n_cols, const hbk_hash_spill_column_t* cols, size_t* bytes);
 int hbk_hash_spill_n(int32_t n_cols, const hbk_hash_spill_column_t* cols, void* workspace, hbk_stream_t stream);
+
+/* Spilling in LFU order: hbk_hash_spill_n with the selection of hbk_hash_evict_to_lfu_select_n.  Same struct;
+ * `selection` points at that entry's device int32[8] {live_before, need, cut_freq, cut_last_seen, n_selected, ...},
+ * read from device memory by every launch.  Slot s is SELECTED iff ALL of
+ *     keys_cache[s] holds a key;   keep_freq == 0  or  freq[s] < keep_freq;   selection[1] > 0;
+ *     (freq[s], last_seen[s]) <= (selection[2], selection[3])   as a pair of SIGNED int32, freq first
+ * -- with the keep_freq of the select, exactly the slots hbk_hash_evict_to_lfu_n would evict.  Everything else is
+ * hbk_hash_spill_n's contract: count, scan and write of the export with this predicate (ascending source-slot
+ * order, packed from 0, nothing behind out_capacity, *count = the total), then the sweep, ALL OR NOTHING per table
+ * (guarded by *count <= out_capacity); *n_evicted zeroed by the scan launch; 32 tables per launch; no host read,
+ * capturable.  Workspace: hbk_hash_spill_workspace_bytes (the geometry alone decides).  The argument checks and
+ * refusal texts are hbk_hash_spill_n's under the name hash_spill_lfu_n, before any device work. */
+int hbk_hash_spill_lfu_n(int32_t n_cols, const hbk_hash_spill_column_t* cols, void* workspace, hbk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Communicator lifecycle: HbGetNcclId / HbCreateNcclCollective /
