@@ -148,6 +148,13 @@ class HashRemoveColumn(C.Structure):
               ('n_removed', C.c_void_p), ('n_fills', C.c_int32), ('fills', HashFill * HASH_MAX_FILLS)]
 
 
+class HashMissingColumn(C.Structure):
+  """hbk_hash_missing_column_t"""
+  _fields_ = [('keys_cache', C.c_void_p), ('slab_count', C.c_int64), ('slab_size', C.c_int32),
+              ('exp', HashExpiry), ('keys', C.c_void_p), ('n_keys', C.c_int64), ('slots', C.c_void_p),
+              ('out_ids', C.c_void_p), ('out_capacity', C.c_int64), ('count', C.c_void_p)]
+
+
 HASH_MAX_MOVES = 8
 
 
@@ -272,6 +279,8 @@ def _declare(l):
     'hbk_hash_evict_to_lfu_n': (C.c_int, [i32, vp, vp, sz, vp]),
     'hbk_hash_evict_to_lfu_select_n': (C.c_int, [i32, vp, vp, sz, vp]),
     'hbk_hash_remove_n': (C.c_int, [i32, vp, vp]),
+    'hbk_hash_missing_workspace_bytes': (sz, [i32, vp, vp]),
+    'hbk_hash_missing_n': (C.c_int, [i32, vp, vp, vp, sz, vp]),
     'hbk_hash_insert_admit_n': (C.c_int, [i32, vp, vp, i32, vp]),
     'hbk_hash_insert_expiring_admit_n': (C.c_int, [i32, vp, vp, vp, i32, vp]),
     'hbk_hash_rehash_n': (C.c_int, [i32, vp, vp]),

@@ -14,6 +14,10 @@ The gather over the slot grid and the whole backward already exist: :class:`Hash
 launch in front of the plain :class:`GroupLookup` (buckets 0) over the grid viewed as one id per position, and
 ``SequenceLookupGrad(hsl, ...)`` is its backward and optimizer step.
 
+Tiered tables: :meth:`HashSequenceLookup.fault_in` brings back, before the call of a step, the spilled keys among
+the ids the call will read -- the first ``T`` ids of every sample and the pad id, never an id past ``T``
+(:func:`hash_missing_sequence`, ``hbk_hash_missing_n``).
+
 Not provided: sharded hash sequence columns, feature-column / ``SequenceFeatures`` integration, per-id weights,
 fp16 outputs, the TF shim op.
 """
@@ -25,6 +29,8 @@ from hybridbackend_amd import _lib
 from hybridbackend_amd.embedding.cache import EMPTY_KEY
 from hybridbackend_amd.embedding.hashtable import TOMBSTONE_KEY
 from hybridbackend_amd.embedding.hashtable import _Plan
+from hybridbackend_amd.embedding.hashtable import _missing
+from hybridbackend_amd.embedding.hashtable import hash_fault_in
 from hybridbackend_amd.embedding.hashtable import check_bound
 from hybridbackend_amd.embedding.hashtable import check_current
 from hybridbackend_amd.embedding.hashtable import check_ids
@@ -157,6 +163,22 @@ def hash_translate_sequence(tables, ids, row_splits=None, max_lens=None, pad_ids
   return grids, lengths
 
 
+def hash_missing_sequence(tables, ids, row_splits=None, max_lens=None, pad_ids=None):
+  """:func:`hybridbackend_amd.embedding.hash_missing` on the EFFECTIVE id lists (``hbk_hash_missing_n`` with a
+  sequence record per column): per expiring table the distinct ids among the first ``T_c`` ids of every sample --
+  and the pad id, where a sample is shorter than ``T_c`` and ``pad_ids[c]`` is given -- that the table does not hold,
+  a device int64 tensor in the order of their first occurrence by position ``b * T_c + t``.  Ids past ``T_c`` are
+  never read.  The arguments are those of :func:`hash_translate_sequence`.  One C call, one host read (all
+  counts); the tables are not written."""
+  tables, ids = list(tables), list(ids)
+  same_device(tables)
+  max_lens, pad_ids = check_hash_sequence_args(tables, max_lens, pad_ids)
+  row_splits = [None] * len(tables) if row_splits is None else list(row_splits)
+  if len(row_splits) != len(tables):
+    raise _bad(f'expected {len(tables)} row_splits, got {len(row_splits)}')
+  return _missing(tables, ids, (row_splits, max_lens, pad_ids))[0]
+
+
 class HashSequenceLookup:
   """N hash-keyed sequence columns: one translate launch (``hbk_hash_translate_sequence_n``), then the plain
   :class:`GroupLookup` with buckets 0 over the slot grid viewed as one id per position, so a ``-1`` reads a zero
@@ -223,6 +245,15 @@ class HashSequenceLookup:
     :meth:`rebind` is needed; slots handed out earlier for the removed ids are void.  Returns the old slots per
     table."""
     return remove_tables(self.hash_tables, ids_list, slots, stores)
+
+  def fault_in(self, ids, row_splits, stores, slots=None):
+    """:meth:`HashGroupLookup.fault_in` for sequence columns, before the call of the step (:func:`hash_fault_in`
+    with this object's ``max_lens`` and ``pad_ids``): of ``ids[c]`` / ``row_splits[c]`` only what the call will
+    read is asked of ``stores[c]`` -- the first ``T_c`` ids of every sample and, where a sample is shorter, the pad
+    id.  An id that occurs only past ``T_c`` stays in the store; a pad id the store holds comes back.  ``slots[c]``:
+    the companion tensors of table c.  The row tensors do not move, so no :meth:`rebind` is needed.  Returns the
+    keys restored per table."""
+    return hash_fault_in(self.hash_tables, ids, stores, slots, row_splits, self.max_lens, self.pad_ids)
 
   def __len__(self):
     return len(self.hash_tables)

@@ -37,7 +37,10 @@ Spilling to a host tier (``hbk_hash_evict_to_select_n`` / ``hbk_hash_spill_n``):
 :func:`hash_spill` export exactly the keys an ``evict_to`` would remove -- rows, ``last_seen``, ``freq`` and the
 optimizer slots -- and then remove them; a :class:`HashSpillStore` keeps them on the host, and
 :meth:`HashTable.fault_in` / :meth:`HashGroupLookup.fault_in` bring a batch's spilled keys back as they left before
-the translate.  ``maybe_evict(..., spill=store)`` spills where it evicted.
+the translate.  ``maybe_evict(..., spill=store)`` spills where it evicted.  :func:`hash_missing`
+(``hbk_hash_missing_n``) reports, for N tables in one C call, the distinct ids the tables do not hold, in
+first-occurrence order and without writing a table; :func:`hash_fault_in` asks the stores of N tables for them after
+one such call, and with ``max_lens`` reads the ids as a sequence lookup does (``HashSequenceLookup.fault_in``).
 
 Removal by id (``hbk_hash_remove_n``): :meth:`HashTable.remove` / :func:`hash_remove` take the keys the caller
 names out of N expiring tables -- a find and an erase launch, the old slots returned, the companions reset as a sweep
@@ -566,18 +569,12 @@ class HashTable:
     missed = torch.unique(ids[found < 0]).cpu()
     if missed.numel() == 0 or len(store) == 0:
       return 0
-    exp = store.take(missed)
-    if len(exp) == 0:
-      return 0
-    try:
-      self.import_items(exp, slots, assume_distinct=True)
-    except Exception:
-      # whatever is not in the table now goes back where it came from
-      lost = (self.find(exp.keys.to(self.keys.device)) < 0).cpu().nonzero().flatten()
-      store.put(HashExport(exp.keys[lost], exp.rows[lost], exp.last_seen[lost], exp.freq[lost],
-                           [x[lost] for x in exp.slots]))
-      raise
-    return len(exp)
+    return _restore(self, store, missed, slots)
+
+  def missing(self, ids):
+    """The distinct ids of ``ids`` the table does not hold, a device int64 tensor in the order of their first
+    occurrence (:func:`hash_missing` for one table).  The table is not written."""
+    return hash_missing([self], [ids])[0]
 
   # ---- export and import ----------------------------------------------------------------------------------
   def export_items(self, since=None, slots=()):
@@ -1431,6 +1428,151 @@ class HashSpillStore:
     return store
 
 
+def _missing(tables, ids_list, seq=None):
+  """``hbk_hash_missing_n`` over checked arguments: ONE C call for all tables, its outputs and workspace allocated
+  once, ONE host read (all counts).  ``seq``: None, or the checked ``(row_splits, max_lens, pad_ids)`` lists of the
+  sequence form.  Returns ``(missed, slots)``: per table the distinct missed ids (views of one buffer, narrowed to
+  their counts) and the find's answers per position."""
+  n = len(tables)
+  for c, t in enumerate(tables):
+    if not isinstance(t, HashTable):
+      raise _bad(f'table {c} must be a HashTable')
+    if not t.expiring:
+      raise _bad(f'table {c}: missing needs a table built with expiring=True, as fault_in does (on a plain table '
+                 'INT64_MIN + 1 is an ordinary key)')
+  check_ids(ids_list, tables)
+  lib = _lib.lib()
+  if n == 0:
+    _lib.check(lib.hbk_hash_missing_n(0, None, None, None, 0, None))
+    return [], []
+  dev = tables[0].keys.device
+  cols = (_lib.HashMissingColumn * n)()
+  seqs = (_lib.HashSequence * n)() if seq is not None else None
+  positions = []
+  for c, i in enumerate(ids_list):
+    if seq is None:
+      positions.append(i.numel())
+      continue
+    s, t_max = seq[0][c], seq[1][c]
+    if s is not None:
+      _lib.require_device_tensor(s, 'row_splits')
+      if s.dtype != torch.int32 or s.dim() != 1 or s.numel() < 1 or s.device != i.device:
+        raise _bad(f'row_splits of column {c} must be an int32 vector [samples+1] on {i.device}')
+    b = i.numel() if s is None else s.numel() - 1
+    if b * t_max >= 2 ** 30:
+      raise _bad(f'column {c}: {b} samples x max_len {t_max} positions, must stay below 2^30')
+    q = seqs[c]
+    q.row_splits = s.data_ptr() if s is not None else None
+    q.n_segments, q.max_len = b, t_max
+    q.has_pad = 0 if seq[2][c] is None else 1
+    q.pad_id = seq[2][c] or 0
+    q.lengths = None
+    positions.append(b * t_max)
+  total = sum(positions)
+  slots = torch.split(torch.empty(total, dtype=torch.int64, device=dev), positions)
+  outs = torch.split(torch.empty(total, dtype=torch.int64, device=dev), positions)
+  counts = torch.empty(n, dtype=torch.int64, device=dev)
+  for c, (t, i) in enumerate(zip(tables, ids_list)):
+    _lib.require_device_tensor(t.keys, 'keys')
+    col = cols[c]
+    col.keys_cache, col.slab_count, col.slab_size = t.keys.data_ptr(), t.slab_count, t.slab_size
+    t._describe_expiry(col.exp)
+    col.keys, col.n_keys = (i.data_ptr() if i.numel() else None), i.numel()
+    col.slots = slots[c].data_ptr() if positions[c] else None
+    col.out_ids, col.out_capacity = (outs[c].data_ptr() if positions[c] else None), positions[c]
+    col.count = counts.data_ptr() + 8 * c
+  nbytes = lib.hbk_hash_missing_workspace_bytes(n, cols, seqs)
+  workspace = torch.empty(max(nbytes // 8, 1), dtype=torch.int64, device=dev)
+  _lib.check(lib.hbk_hash_missing_n(n, cols, seqs, workspace.data_ptr(), nbytes, _lib.current_stream(dev)))
+  return [o[:k] for o, k in zip(outs, counts.tolist())], list(slots)   # the one host read
+
+
+def hash_missing(tables, ids_list):
+  """The distinct ids of ``ids_list[c]`` that expiring table c does not hold, per table a device int64 tensor in the
+  order of the ids' FIRST occurrence (``hbk_hash_missing_n``): what :func:`hash_fault_in` asks the stores for.  ONE C
+  call for all tables -- a find, a claim into a scratch set and a stream compaction per 32 tables -- with outputs
+  and workspace allocated once, and ONE host read (all counts) whatever N.  ``INT64_MIN`` and ``INT64_MIN + 1`` are
+  never reported; an evicted id (a TOMBSTONE) is.  The tables are not written: nothing is inserted, no
+  ``last_seen`` is stamped."""
+  tables = list(tables)
+  same_device(tables)
+  return _missing(tables, list(ids_list))[0]
+
+
+def _restore(table, store, missed, slots):
+  """The host half of a fault-in: ``store.take`` of the missed ids (a CPU int64 vector) and, if it returned anything,
+  ``import_items``; what does not fit goes back into the store before the error is raised.  Returns the keys
+  restored."""
+  exp = store.take(missed)
+  if len(exp) == 0:
+    return 0
+  try:
+    table.import_items(exp, slots, assume_distinct=True)
+  except Exception:
+    # whatever is not in the table now goes back where it came from
+    lost = (table.find(exp.keys.to(table.keys.device)) < 0).cpu().nonzero().flatten()
+    store.put(HashExport(exp.keys[lost], exp.rows[lost], exp.last_seen[lost], exp.freq[lost],
+                         [x[lost] for x in exp.slots]))
+    raise
+  return len(exp)
+
+
+def hash_fault_in(tables, ids_list, stores, slots=None, row_splits=None, max_lens=None, pad_ids=None):
+  """:meth:`HashTable.fault_in` for N expiring tables: the keys of ``ids_list[c]`` that ``stores[c]`` holds come back
+  into table c as they left.  Tables whose store is empty are left out entirely; the others go through ONE
+  :func:`hash_missing` call (one host read of the counts), their distinct missed ids reach the host in ONE copy, and
+  then, per table in order, ``stores[c].take`` and -- if anything came back -- :meth:`HashTable.import_items` with
+  the companions ``slots[c]``.  ``take`` returns ascending key order and counts duplicates once, so tables, stores
+  and the return value are what the per-table loop produces, bit for bit.
+
+  ``max_lens`` (with ``row_splits`` and ``pad_ids``, as for ``hash_translate_sequence``): the ids are read the way
+  :class:`hybridbackend_amd.embedding.HashSequenceLookup` reads them (:func:`hash_missing_sequence`): an id that
+  occurs only past ``T`` stays in its store, a pad id the store holds comes back.
+
+  When a table is too full for some of the taken keys they go back into its store before the error is raised; the
+  tables after it have not been taken from.  Returns the keys restored per table."""
+  tables = list(tables)
+  same_device(tables)
+  n = len(tables)
+  ids_list, stores, slots = _per_table(n, ('id tensors', ids_list, None), ('spill stores', stores, None),
+                                       ('lists of companion tensors', slots, ()))
+  for c, t in enumerate(tables):
+    t._need_expiring('fault_in')
+    _check_store(stores[c], t, [(x, 0.0) for x in slots[c]])
+  seq = None
+  if max_lens is not None:
+    from hybridbackend_amd.embedding.hash_sequence import check_hash_sequence_args   # pylint: disable=import-outside-toplevel
+    max_lens, pad_ids = check_hash_sequence_args(tables, max_lens, pad_ids)
+    row_splits, = _per_table(n, ('row_splits', row_splits, None))
+    seq = (row_splits, max_lens, pad_ids)
+  elif row_splits is not None or pad_ids is not None:
+    raise _bad('row_splits and pad_ids come with max_lens: the sequence form')
+  check_ids(ids_list, tables)
+  restored = [0] * n
+  live = [c for c in range(n) if len(stores[c])]
+  if not live:
+    return restored
+  missed, _ = _missing([tables[c] for c in live], [ids_list[c] for c in live],
+                       None if seq is None else tuple([x[c] for c in live] for x in seq))
+  sizes = [m.numel() for m in missed]
+  if sum(sizes) == 0:
+    return restored
+  # ascending per table before they leave the device (two stable sorts over all tables' ids at once): `take` orders
+  # its keys on the host, where an ordered list is the cheaper one (profiles/hash_fault_in.txt: 29.4 -> 25.7 ms at
+  # 10 % missed)
+  flat = missed[0] if len(missed) == 1 else torch.cat(missed)
+  order = torch.argsort(flat, stable=True)
+  if len(missed) > 1:
+    owner = torch.repeat_interleave(torch.arange(len(missed), device=flat.device),
+                                    torch.tensor(sizes, device=flat.device), output_size=flat.numel())
+    order = order[torch.argsort(owner[order], stable=True)]
+  host = torch.split(flat[order].cpu(), sizes)   # the one copy
+  for c, m in zip(live, host):
+    if m.numel():
+      restored[c] = _restore(tables[c], stores[c], m, slots[c])
+  return restored
+
+
 def _check_loads(max_load, target_load):
   max_load, target_load = float(max_load), float(target_load)
   if not 0.0 < target_load <= max_load <= 1.0:
@@ -1651,13 +1793,11 @@ class HashGroupLookup:
     return evict_tables(self, self.tables, max_load, target_load, keep_freq, slots, spill, order)
 
   def fault_in(self, ids, stores, slots=None):
-    """:meth:`HashTable.fault_in` per table, before the call of the step: ``ids[c]`` the raw ids of column c,
+    """:meth:`HashTable.fault_in` on every table, before the call of the step (:func:`hash_fault_in`: one
+    ``hbk_hash_missing_n`` call for all tables that have anything spilled): ``ids[c]`` the raw ids of column c,
     ``stores[c]`` its :class:`HashSpillStore`, ``slots[c]`` its companion tensors.  The row tensors do not move, so
     no :meth:`rebind` is needed.  Returns the keys restored per table."""
-    n = len(self.tables)
-    ids, stores, slots = _per_table(n, ('id tensors', ids, None), ('spill stores', stores, None),
-                                    ('lists of companion tensors', slots, ()))
-    return [t.fault_in(ids[c], stores[c], slots[c]) for c, t in enumerate(self.tables)]
+    return hash_fault_in(self.tables, ids, stores, slots)
 
   def remove(self, ids_list, slots=None, stores=None):
     """:meth:`HashTable.remove` on every table in one call (:func:`hash_remove`): ``ids_list[c]`` the raw ids to take

@@ -1135,6 +1135,69 @@ int hbk_hash_translate_sequence_n(int32_t n_cols, const hbk_hash_column_t* cols,
                                   const hbk_hash_sequence_t* seq,    /* [n_cols] */
                                   int32_t insert, hbk_stream_t stream);
 
+/* Missing ids: the distinct ids of N id lists that their tables do not hold -- what a fault-in asks the host tier
+ * for (HashTable.fault_in composed it from a find, a boolean index and a sort per table, with two host
+ * synchronisations each).  Expiring tables only, as fault-in.  seq == NULL: the id list E of a column is keys[0 ..
+ * n_keys) and slots is int64 [n_keys].  seq != NULL ([n_cols]): E is the EFFECTIVE ID LIST exactly as
+ * hbk_hash_translate_sequence_n defines it above -- per sample its first min(len, T) ids, then the pad id T - L_b
+ * times when has_pad; padding without a pad id is "nothing here"; ids past T are never read; a row_splits entry
+ * that points outside [0, n_keys) names no id -- and slots is the [B * T] grid.  positions = n_keys or B * T.
+ *   - slots[p] is the pure find's answer for position p (with seq: -1 at a padding position without a pad id;
+ *     seq[c].lengths is written as the translate writes it, or NULL).
+ *   - out_ids[0 .. min(*count, out_capacity)) holds the distinct ids of E that the table does not hold, in the
+ *     order of their FIRST OCCURRENCE in E.  *count is their number even when it exceeds out_capacity; writes stop
+ *     at out_capacity, nothing is written behind it.
+ *   - An id equal to INT64_MIN or INT64_MIN + 1 is never reported: no store can hold it.  A TOMBSTONE slot holds no
+ *     key, so an evicted id is reported.
+ *   - The table is NOT written: keys, rows, last_seen, freq, counts, stats and the sketch are bit for bit what
+ *     they were.  Nothing is inserted, nothing past T is looked at.
+ *   - slots, out_ids[0 .. count) and *count are functions of the inputs alone: the same on every run.
+ *
+ * Launches, on the call's stream: one clear of the workspace per call, then per 32 columns (more columns run as
+ * groups of 32, as hbk_hash_remove_n) the find -- hbk_hash_insert_expiring_n or hbk_hash_translate_sequence_n with
+ * insert == 0, called as it is --, a claim launch tiled over the positions and the count, scan and write of the
+ * export's stream compaction.  The claim: a lane whose position holds an id with slots[p] < 0 and no sentinel puts
+ * the id into a scratch set of the column -- open addressing over S = pow2 >= 2 * positions cells (at least 64),
+ * EMPTY = INT64_MIN, home cell murmur3_hash32(id) & (S - 1), linear probing, cells claimed with a 64-bit agent-scope
+ * compare-and-swap -- and does atomicMin(first[cell], p) on an int32 array pre-set to INT32_MAX; a lane that finds
+ * its id in a cell does only the atomicMin (skipped when the value it reads there is already below p: first[]
+ * only falls).  The probe reads at most S cells and no lane waits for another: there is no spin loop.  A wave whose positions all hit leaves after reading slots: a batch of resident ids issues no
+ * atomic.  The compaction selects position p iff it missed and first[cell(id)] == p, in position order.
+ *
+ * Workspace: hbk_hash_missing_workspace_bytes(n_cols, cols, seq) bytes, 16-byte aligned: 12 bytes per cell and 8
+ * bytes per 256 positions, so about 24 bytes per position.  Only the id counts, n_segments and max_len are read to
+ * size it (a column whose counts are out of range adds nothing; the call refuses it).  The call clears what it
+ * uses on the stream before it reads it: the workspace needs no preparation, there is no host read, and a captured
+ * call replays on whatever the id buffers then hold.  Stream-ordered against the translates, sweeps and backwards
+ * of its tables, never beside one.
+ *
+ * Refused (HBK_INVALID_ARGUMENT) before any device work, naming the column and the field: what hbk_hash_remove_n
+ * refuses of keys_cache, slab_count and slab_size; NULL last_seen or freq; NULL count; out_capacity < 0; NULL
+ * out_ids with out_capacity > 0; n_keys outside [0, 2^31) (positions >= 2^31); NULL keys with n_keys > 0; NULL
+ * slots with positions > 0; with seq everything hbk_hash_translate_sequence_n refuses of an expiring table's
+ * column (max_len < 1, n_segments < 0, B * T >= 2^30, row_splits == NULL with n_keys != n_segments, a sentinel
+ * pad_id); 32 consecutive columns whose find would need a grid of 2^31 tiles; a NULL, misaligned or too small
+ * workspace where one is needed, with the size needed.  n_cols == 0, n_keys == 0, B == 0 and all-empty samples are
+ * fine (*count = 0).  exp.step is not read and may be NULL; exp.stats is not touched.  Detected by the presence of
+ * the symbol; the structs above and the version are those of 0.2.0. */
+typedef struct {
+  const int64_t* keys_cache;   /* device [slab_count * slab_size], 8-byte aligned: read only */
+  int64_t slab_count;
+  int32_t slab_size;           /* 1..64 */
+  hbk_hash_expiry_t exp;       /* last_seen and freq name an expiring table; nothing of it is written */
+  const int64_t* keys;         /* device [n_keys]: the ids */
+  int64_t n_keys;
+  int64_t* slots;              /* device [n_keys], or [B * T] with seq; written: the find's answers */
+  int64_t* out_ids;            /* device [out_capacity]; written: the distinct missed ids, first occurrence first */
+  int64_t out_capacity;
+  int64_t* count;              /* device int64 [1]; written: the distinct missed ids */
+} hbk_hash_missing_column_t;
+int hbk_hash_missing_n(int32_t n_cols, const hbk_hash_missing_column_t* cols,
+                       const hbk_hash_sequence_t* seq,   /* NULL: flat id lists; else [n_cols] */
+                       void* workspace, size_t workspace_bytes, hbk_stream_t stream);
+size_t hbk_hash_missing_workspace_bytes(int32_t n_cols, const hbk_hash_missing_column_t* cols,
+                                        const hbk_hash_sequence_t* seq);
+
 /* Rehash: growth and tombstone compaction on the device.  A full table answers -1 for ever, and an expiring
  * table's probes get longer with every tombstone; both are cured by moving every live key into a fresh key
  * array -- of a larger geometry, or of the same one -- with its rows.  hbk_hash_rehash_n does that for N tables
