@@ -264,6 +264,7 @@ def _declare(l):
     'hbk_group_lookup_bwd_weights': (C.c_int, [i32, vp, vp, vp, vp]),
     'hbk_group_lookup_fwd_sequence': (C.c_int, [i32, vp, vp, vp, vp]),
     'hbk_sequence_row_grid_n': (C.c_int, [i32, vp, vp, vp]),
+    'hbk_sequence_id_grid_n': (C.c_int, [i32, vp, vp, vp]),
     'hbk_group_stitch_bwd': (C.c_int, [i32, vp, vp]),
     'hbk_cache_probe': (C.c_int, [vp, i64, i32, vp, i64, vp, vp, vp]),
     'hbk_cache_lookup_workspace_bytes': (sz, [i64]),

@@ -1,4 +1,4 @@
-// Sequence lookups (hbk_group_lookup_fwd_sequence, hbk_sequence_row_grid_n): a ragged id list WITHOUT a
+// Sequence lookups (hbk_group_lookup_fwd_sequence, hbk_sequence_row_grid_n, hbk_sequence_id_grid_n): a ragged id list WITHOUT a
 // combiner -- the first T ids of every sample gathered into padded [B, T, dim] rows, with the lengths and
 // the bucketized id grid the backward reduces (include/hbk.h; replaces tf.sparse.slice +
 // tf.sparse.to_dense + FloorMod + GatherV2 of docs/tutorial/ranking/data.py:195-224).
@@ -72,11 +72,13 @@ __host__ __device__ inline uint64_t seq_map(const IdMap& m, int64_t id, int64_t*
   return r < m.rows ? r : kNoRow;
 }
 
-// Position p of the column's grid -> its row, and the grid word and the sample's length written.  The
-// lanes of a wave hold CONSECUTIVE positions (lane l: p - l is lane 0's), valid ones first; every lane of
-// the wave calls this.  The first lane of each sample inside the wave (t == 0, or lane 0) reads the
-// sample's two row splits, the sample's other lanes take them by shuffle.
-__device__ inline uint64_t seq_position(const SeqCol& c, int64_t p, bool valid) {
+// The sample side of position p: t = p - b * T, the index of the sample's first id and L_b = min(len_b, T),
+// the sample's length written by its first position.  False for a lane without a position.  The lanes of a
+// wave hold CONSECUTIVE positions (lane l: p - l is lane 0's), valid ones first; every lane of the wave calls
+// this.  The first lane of each sample inside the wave (t == 0, or lane 0) reads the sample's two row splits,
+// the sample's other lanes take them by shuffle.
+__device__ inline bool seq_sample(const SeqCol& c, int64_t p, bool valid, int64_t* t_out, int32_t* beg_out,
+                                  int64_t* len_out) {
   const int lane = lane_id();
   const int64_t T = (int64_t)c.max_len.d;
   int64_t b = 0, t = 0;
@@ -97,10 +99,21 @@ __device__ inline uint64_t seq_position(const SeqCol& c, int64_t p, bool valid) 
   const int src = lane - (int)(t < lane ? t : lane);
   beg = __shfl(beg, src, kWave);
   end = __shfl(end, src, kWave);
-  if (!valid) return kNoRow;
+  if (!valid) return false;
   int64_t len = (int64_t)end - (int64_t)beg;
   len = len < 0 ? 0 : (len > T ? T : len);
   if (t == 0 && c.lengths != nullptr) c.lengths[b] = (int32_t)len;
+  *t_out = t;
+  *beg_out = beg;
+  *len_out = len;
+  return true;
+}
+
+// Position p of the column's grid -> its row, and the grid word written (every lane of the wave calls this)
+__device__ inline uint64_t seq_position(const SeqCol& c, int64_t p, bool valid) {
+  int64_t t, len;
+  int32_t beg;
+  if (!seq_sample(c, p, valid, &t, &beg, &len)) return kNoRow;
   uint64_t row = c.pad_row;
   int64_t g = c.pad_grid;
   if (t < len) {
@@ -174,6 +187,26 @@ __global__ __launch_bounds__(kBlock) void sequence_row_grid_kernel(const SeqArgs
   const SeqCol& c = a.col[ci];
   const int64_t p = (int64_t)(b - a.tile_start[ci]) * kBlock + (int64_t)threadIdx.x;
   seq_position(c, p, p < c.n_pos);
+}
+
+// the RAW-id grid (hbk_sequence_id_grid_n): the same position arithmetic, the effective ids themselves -- never
+// bucketized, negative ones kept, pad_grid (= pad_id) past a sample's length.  One thread per position: a wave
+// stores 64 consecutive words, 512 bytes in whole lines; the ids of a sample are consecutive too.
+__global__ __launch_bounds__(kBlock) void sequence_id_grid_kernel(const SeqArgs a) {
+  const int b = (int)blockIdx.x;
+  const int ci = column_of(a.tile_start, a.n_cols, b, lane_id());
+  const SeqCol& c = a.col[ci];
+  const int64_t p = (int64_t)(b - a.tile_start[ci]) * kBlock + (int64_t)threadIdx.x;
+  int64_t t, len;
+  int32_t beg;
+  if (!seq_sample(c, p, p < c.n_pos, &t, &beg, &len)) return;
+  int64_t g = c.pad_grid;
+  if (t < len) {
+    const int64_t j = (int64_t)beg + t;
+    // (row splits that point outside the ids read nothing: such a position holds the pad id)
+    if ((uint64_t)j < (uint64_t)c.n_ids) g = load_id(c.ids, c.ids64, j);
+  }
+  __builtin_nontemporal_store(g, c.grid + p);
 }
 
 template <typename V, bool CLIP>
@@ -304,8 +337,74 @@ int sequence_fwd(const char* who, bool gather, int32_t n_cols, const hbk_lookup_
   return HBK_OK;
 }
 
+// hbk_sequence_id_grid_n: one launch per kMaxColsPerLaunch columns, tiled as the row-grid kernel tiles
+int sequence_id_grid(int32_t n_cols, const hbk_lookup_column_t* cols, const hbk_sequence_t* seq,
+                     hbk_stream_t stream) {
+  const char* who = "sequence_id_grid_n";
+  HBK_REQUIRE(n_cols >= 0, "%s: n_cols must be >= 0, got %d", who, n_cols);
+  HBK_REQUIRE(n_cols == 0 || cols != nullptr, "%s: cols is NULL", who);
+  HBK_REQUIRE(n_cols == 0 || seq != nullptr, "%s: seq is NULL", who);
+  for (int32_t c = 0; c < n_cols; ++c) {
+    const hbk_lookup_column_t& h = cols[c];
+    const hbk_sequence_t& q = seq[c];
+    HBK_REQUIRE(q.max_len >= 1, "%s: column %d: max_len must be >= 1, got %d", who, c, q.max_len);
+    HBK_REQUIRE(q.has_pad != 0, "%s: column %d: has_pad is 0: every int64 is an id, so a raw-id grid has no value "
+                "for a position that holds nothing -- give a pad_id", who, c);
+    HBK_REQUIRE(q.row_grid != nullptr, "%s: column %d: row_grid is NULL", who, c);
+    HBK_REQUIRE(h.n_ids >= 0 && h.n_segments >= 0, "%s: column %d: negative size", who, c);
+    HBK_REQUIRE(h.ids_dtype == HBK_INT32 || h.ids_dtype == HBK_INT64,
+                "%s: column %d: ids must be int32 or int64", who, c);
+    HBK_REQUIRE(h.row_splits != nullptr || h.n_segments == h.n_ids,
+                "%s: column %d: n_segments (%lld) must equal n_ids (%lld) when row_splits is NULL", who, c,
+                (long long)h.n_segments, (long long)h.n_ids);
+    HBK_REQUIRE(h.n_ids < (1ll << 31), "%s: column %d: more than 2^31-1 ids", who, c);
+    HBK_REQUIRE(h.n_segments < (1ll << 31) && h.n_segments * (int64_t)q.max_len < (1ll << 31),
+                "%s: column %d: B * T = %lld x %d positions, must stay below 2^31", who, c,
+                (long long)h.n_segments, q.max_len);
+    HBK_REQUIRE(h.n_segments == 0 || h.ids != nullptr || h.n_ids == 0, "%s: column %d: NULL buffer", who, c);
+  }
+  int32_t c0 = 0;
+  while (c0 < n_cols) {
+    SeqArgs args;
+    int32_t k = 0;
+    int64_t tiles = 0;
+    args.tile_start[0] = 0;
+    while (c0 < n_cols && k < kMaxColsPerLaunch) {
+      const int32_t ci = c0++;
+      const hbk_lookup_column_t& h = cols[ci];
+      const hbk_sequence_t& q = seq[ci];
+      if (h.n_segments == 0) continue;
+      SeqCol& d = args.col[k];
+      memset(&d, 0, sizeof(d));
+      d.ids = h.ids;
+      d.splits = h.row_splits;
+      d.grid = q.row_grid;
+      d.lengths = q.lengths;
+      d.n_pos = h.n_segments * (int64_t)q.max_len;
+      d.n_ids = h.n_ids;
+      d.max_len = make_fastdiv((uint64_t)q.max_len);
+      d.pad_grid = q.pad_id;
+      d.ids64 = h.ids_dtype == HBK_INT64;
+      tiles += (d.n_pos + kBlock - 1) / kBlock;
+      HBK_REQUIRE(tiles < (1ll << 31), "%s: grid too large", who);
+      ++k;
+      args.tile_start[k] = (int32_t)tiles;
+    }
+    if (k == 0) continue;
+    args.n_cols = k;
+    hipLaunchKernelGGL(sequence_id_grid_kernel, dim3((unsigned)tiles), dim3(kBlock), 0, as_stream(stream), args);
+    HBK_HIP_OK(hipGetLastError());
+  }
+  return HBK_OK;
+}
+
 }  // namespace
 }  // namespace hbk
+
+extern "C" int hbk_sequence_id_grid_n(int32_t n_cols, const hbk_lookup_column_t* cols,
+                                      const hbk_sequence_t* seq, hbk_stream_t stream) {
+  return hbk::sequence_id_grid(n_cols, cols, seq, stream);
+}
 
 extern "C" int hbk_group_lookup_fwd_sequence(int32_t n_cols, const hbk_lookup_column_t* cols,
                                              const hbk_sequence_t* seq, const float* max_norms,

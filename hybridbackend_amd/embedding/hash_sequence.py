@@ -18,8 +18,10 @@ Tiered tables: :meth:`HashSequenceLookup.fault_in` brings back, before the call 
 the ids the call will read -- the first ``T`` ids of every sample and the pad id, never an id past ``T``
 (:func:`hash_missing_sequence`, ``hbk_hash_missing_n``).
 
-Not provided: sharded hash sequence columns, feature-column / ``SequenceFeatures`` integration, per-id weights,
-fp16 outputs, the TF shim op.
+As a column of a layer, and sharded over W ranks: ``feature_column.HashSequenceEmbeddingColumn`` in
+``SequenceFeatures`` (the sharded form goes through ``ShardedHashGroupLookup`` over ``sequence_id_grid``).
+
+Not provided: per-id weights, fp16 outputs, the TF shim op.
 """
 import ctypes as C
 

@@ -59,7 +59,8 @@ with rows, ``last_seen``, ``freq`` and the optimizer slots into a :class:`HashEx
 number of ranks.  ``items()`` / ``load()`` / ``load_owned()`` / ``variables()`` are what they were.
 
 Not provided: growth from inside a translate launch (a full table answers -1 until ``maybe_grow`` ran), a
-compaction that keeps the tensors' addresses, feature-column integration, the TF shim op.
+compaction that keeps the tensors' addresses, the TF shim op.  (As feature columns: ``feature_column.
+HashEmbeddingColumn`` / ``HashSequenceEmbeddingColumn``.)
 """
 import ctypes as C
 import math
@@ -1811,6 +1812,22 @@ class HashGroupLookup:
 
   def __call__(self, ids, row_splits=None, outs=None, sp_weights=None):
     """ids[c]: int64 raw ids, row_splits[c]: int32 ``[segments + 1]`` or None.  Returns GroupLookup's outputs."""
+    self._translate_step(ids)
+    return self.lookup(self.slots, row_splits, outs, sp_weights=sp_weights)
+
+  def call_block(self, ids, row_splits, block, offsets, outs, sp_weights=None):
+    """The call with every column's output a column block of ONE ``[segments, pitch]`` fp32 tensor (column c starts
+    at float ``offsets[c]`` of every row: ``GroupLookup.bind_block``, what ``DenseFeatures`` writes): no per-column
+    views are made.  ``outs``: a callable that gives the per-column views, asked only when the block needs the
+    detailed checks of the ordinary call."""
+    self._translate_step(ids)
+    if self.lookup.bind_block(self.slots, row_splits, block, offsets, sp_weights=sp_weights):
+      self.lookup.launch()
+    else:
+      self.lookup(self.slots, row_splits, outs(), sp_weights=sp_weights)
+
+  def _translate_step(self, ids):
+    """The translate launch of a call: ``self.slots`` holds the row numbers afterwards."""
     ids = list(ids)
     check_current(self.tables, self._rows)
     # the slot buffers of the call before serve again while the id counts stay (a resident loop; a
@@ -1822,7 +1839,6 @@ class HashGroupLookup:
     self.slots = _translate(self.tables, ids, self.train, keep, plan=self._plan)
     self._keep = ids
     self._bound = True
-    return self.lookup(self.slots, row_splits, outs, sp_weights=sp_weights)
 
   def launch(self, stream=None):
     """Both launches of the LAST call again on its tensors (id buffers refilled in place; captured graphs):

@@ -316,3 +316,39 @@ def sequence_row_grid(ids, row_splits=None, buckets=None, max_lens=None, pad_ids
     seqs[c].row_grid = grids[c].data_ptr()
   _lib.check(_lib.lib().hbk_sequence_row_grid_n(n, cols, seqs, _lib.current_stream(dev)))
   return grids, lengths
+
+
+def sequence_id_grid(ids, row_splits=None, max_lens=None, pad_ids=None):
+  """The RAW-id grid (``hbk_sequence_id_grid_n``): per column the int64 ``[B * T]`` effective ids -- the first
+  ``T`` ids of every sample as they are (sign-extended from int32, never bucketized, negative ids kept), then
+  ``pad_id`` -- and the int32 ``[B]`` lengths.  Returns ``(grids, lengths)``.  ``pad_ids`` are RAW ids, any int64,
+  and every column needs one: among raw ids no value means "nothing".  What a sharded hash-keyed sequence column
+  feeds ``ShardedHashGroupLookup`` as ``B * T`` ids of one sample each; ids past ``T`` are never read."""
+  n = len(ids)
+  if max_lens is None:
+    raise _bad('max_lens is required: the padded length of every column')
+  max_lens = per_column(max_lens, n, 'max_lens')
+  pad_ids = per_column(pad_ids, n, 'pad_ids', none_ok=True)
+  for c in range(n):
+    if not 1 <= max_lens[c] < 2 ** 31:
+      raise _bad(f'max_len of column {c} must be in [1, 2^31), got {max_lens[c]}')
+    if pad_ids[c] is None:
+      raise _bad(f'pad_id of column {c} is required: every int64 is an id, so a raw-id grid has no value for a '
+                 'position that holds nothing')
+    if not -2 ** 63 <= pad_ids[c] < 2 ** 63:
+      raise _bad(f'pad_id of column {c} must be an int64, got {pad_ids[c]}')
+  cols = (_lib.LookupColumn * n)()
+  seqs = (_lib.Sequence * n)()
+  batch, _ = _bind_ids(cols, seqs, ids, row_splits, max_lens, pad_ids)
+  for c in range(n):
+    seqs[c].pad_id = pad_ids[c]
+  dev = ids[0].device if n else None
+  lengths, _ = _alloc_side(batch, max_lens, dev, False)
+  # (the entry refuses a NULL grid whatever the batch: a column without samples gets a view of one word)
+  bufs = [torch.empty(max(b * t, 1), dtype=torch.int64, device=dev) for b, t in zip(batch, max_lens)]
+  grids = [x[:b * t] for x, b, t in zip(bufs, batch, max_lens)]
+  for c in range(n):
+    seqs[c].lengths = lengths[c].data_ptr()
+    seqs[c].row_grid = bufs[c].data_ptr()
+  _lib.check(_lib.lib().hbk_sequence_id_grid_n(n, cols, seqs, _lib.current_stream(dev)))
+  return grids, lengths

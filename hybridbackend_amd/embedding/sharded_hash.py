@@ -16,6 +16,27 @@ from hybridbackend_amd.embedding import optimizer as _opt
 from hybridbackend_amd.embedding.sharded import ShardedGroupLookup
 
 
+def slot_kinds(owner, accum_fill):
+  """The optimizer slots ``owner`` holds (``accums``, ``moments``, ``ftrl_slots`` with ``ftrl``) as (attribute, index
+  in a pair or None, fill value), in the ONE order every call that moves them with a hash table uses -- ``accums``;
+  ``moments`` m, v; ``ftrl_slots`` accum, linear -- and with the value a row that no key holds is set to:
+  ``accum_fill`` for Adagrad's accumulator, 0 for Adam's m / v, FTRL's accum its ``initial_accumulator_value`` and
+  linear 0.  The sharded driver and the feature-column layers share it."""
+  kinds = []
+  if owner.accums is not None:
+    kinds.append(('accums', None, float(accum_fill)))
+  if owner.moments is not None:
+    kinds += [('moments', 0, 0.0), ('moments', 1, 0.0)]
+  if owner.ftrl_slots is not None:
+    kinds += [('ftrl_slots', 0, float(owner.ftrl.initial_accumulator_value)), ('ftrl_slots', 1, 0.0)]
+  return kinds
+
+
+def slot_companions(owner, kinds, c):
+  """The slots of table c as ``(tensor, fill_value)`` pairs, in the order of ``kinds``."""
+  return [(getattr(owner, name)[c] if k is None else getattr(owner, name)[c][k], fill) for name, k, fill in kinds]
+
+
 class ShardedHashGroupLookup(ShardedGroupLookup):
   """N hash-keyed columns, each sharded over the ranks by ``floormod(id, W)``.
 
@@ -112,14 +133,7 @@ class ShardedHashGroupLookup(ShardedGroupLookup):
   def _slot_kinds(self):
     """The bound optimizer slots as (attribute, index in a pair or None, fill value), in the order every method
     that moves them uses: ``accums``; ``moments`` m, v; ``ftrl_slots`` accum, linear."""
-    kinds = []
-    if self.accums is not None:
-      kinds.append(('accums', None, self.initial_accumulator_value))
-    if self.moments is not None:
-      kinds += [('moments', 0, 0.0), ('moments', 1, 0.0)]
-    if self.ftrl_slots is not None:
-      kinds += [('ftrl_slots', 0, self.ftrl.initial_accumulator_value), ('ftrl_slots', 1, 0.0)]
-    return kinds
+    return slot_kinds(self, self.initial_accumulator_value)
 
   def _slot_tensors(self, c):
     return [getattr(self, name)[c] if k is None else getattr(self, name)[c][k] for name, k, _ in self._slot_kinds()]
@@ -151,7 +165,7 @@ class ShardedHashGroupLookup(ShardedGroupLookup):
   def _companions(self, c):
     """The bound optimizer slots of table c as ``(tensor, fill_value)`` pairs, the fill values of
     :meth:`maybe_grow`."""
-    return list(zip(self._slot_tensors(c), [fill for _, _, fill in self._slot_kinds()]))
+    return slot_companions(self, self._slot_kinds(), c)
 
   def remove(self, ids_list):
     """:func:`hash_remove` on this rank's tables: the ids of ``ids_list[c]`` this rank's table c holds leave it,

@@ -8,15 +8,33 @@ All columns are looked up by ONE fused launch (``hbk_group_lookup_fwd``) or one 
 (``hbk_sharded_lookup_fwd``), and every column writes its block of the concatenated
 ``[batch, sum of dims]`` tensor in place (``out_stride``): there is no per-column output and no
 concat pass.  The backward reads the blocks of the incoming gradient in place the same way.
+
+Hash-keyed columns (:class:`HashEmbeddingColumn`, :class:`HashSequenceEmbeddingColumn`) are what the
+reference's users get from ``embedding_column`` under DeepRec (``embedding/deeprecev.py`` hooks
+``get_embedding_variable`` into the sharded rewrite): the table is a :class:`HashTable` keyed by the raw ids.
+The layers keep the tables, their optimizer slots and the lookup objects together, so the "void after a
+rehash" rules of the hand composition stay inside ``maybe_grow`` / ``maybe_evict``.
 """
+import re
+
 import torch
 
 from hybridbackend_amd import _lib
+from hybridbackend_amd.embedding.hashtable import HashExport
+from hybridbackend_amd.embedding.hashtable import HashGroupLookup
+from hybridbackend_amd.embedding.hashtable import HashTable
 from hybridbackend_amd.embedding.lookup import GroupLookup
 from hybridbackend_amd.embedding.lookup import GroupLookupGrad
 from hybridbackend_amd.embedding import optimizer as _opt
 from hybridbackend_amd.embedding.sharded import ShardedGroupLookup
+from hybridbackend_amd.embedding.sharded_hash import ShardedHashGroupLookup
+from hybridbackend_amd.embedding.sharded_hash import slot_companions
+from hybridbackend_amd.embedding.sharded_hash import slot_kinds
 from hybridbackend_amd.embedding.variables import sharded_bucket_size
+
+
+def _bad(msg):
+  return _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT, msg)
 
 
 class EmbeddingColumn:
@@ -51,22 +69,101 @@ class EmbeddingColumn:
     self.max_norm = None if max_norm is None else max_norm_list([max_norm], 1)[0]
 
 
+class _HashColumn:
+  """What the hash-keyed columns share: the arguments of the column's :class:`HashTable`, checked when the
+  column is made (a table on the ``meta`` device allocates nothing and refuses what every table refuses)."""
+
+  def _init_table_args(self, key, capacity, dimension, max_norm, dedup, slab_size, init_scale, seed, expiring,
+                       min_freq, sketch_depth, sketch_width, sketch_seed):
+    from hybridbackend_amd.embedding.lookup import max_norm_list
+    self.key, self.capacity, self.dimension = key, int(capacity), int(dimension)
+    self.table_args = dict(slab_size=int(slab_size), init_scale=float(init_scale), seed=int(seed),
+                           expiring=bool(expiring), min_freq=int(min_freq), sketch_depth=sketch_depth,
+                           sketch_width=sketch_width, sketch_seed=sketch_seed)
+    self.expiring = bool(expiring)
+    self._probe = HashTable(self.capacity, self.dimension, 'meta', **self.table_args)
+    self.max_norm = None if max_norm is None else max_norm_list([max_norm], 1)[0]
+    self.dedup = bool(dedup)
+
+  def local_capacity(self, world):
+    """The slots of one rank's table: ``capacity`` at W = 1 (whole slabs: HashTable rounds down), else
+    ``ceil(capacity / W)`` rounded UP to whole slabs."""
+    if world <= 1:
+      return self.capacity
+    slab = self.table_args['slab_size']
+    return (-(-self.capacity // world) + slab - 1) // slab * slab
+
+  def make_table(self, device, world):
+    """This rank's table.  The seed is the column's on every rank: a key's first row does not depend on W."""
+    return HashTable(self.local_capacity(world), self.dimension, device, **self.table_args)
+
+
+class HashEmbeddingColumn(_HashColumn):
+  """``embedding_column`` over a DeepRec EmbeddingVariable (``get_embedding_variable``): the rows are keyed by the
+  RAW int64 ids -- no bucketize, an open vocabulary -- in a :class:`HashTable` of ``capacity`` slots in all
+  (the logical total across ranks).  ``slab_size``, ``init_scale``, ``seed``, ``expiring``, ``min_freq`` and the
+  ``sketch_*`` arguments are the table's, with its refusals.  ``combiner``, ``max_norm``, ``dedup`` and
+  ``weight_feature_key`` are :class:`EmbeddingColumn`'s; per-id weights work on one rank only (the sharded step
+  refuses weights on a column without a bucket, so a weighted hash column is refused when a layer is built over
+  more than one rank)."""
+
+  def __init__(self, key, capacity, dimension, combiner='mean', max_norm=None, dedup=False,
+               weight_feature_key=None, slab_size=8, init_scale=1e-3, seed=0, expiring=False, min_freq=0,
+               sketch_depth=4, sketch_width=None, sketch_seed=0):
+    from hybridbackend_amd.embedding.lookup import _combiner_code
+    self._init_table_args(key, capacity, dimension, max_norm, dedup, slab_size, init_scale, seed, expiring,
+                          min_freq, sketch_depth, sketch_width, sketch_seed)
+    _combiner_code(combiner)   # (refuses unknown names)
+    self.combiner = combiner
+    self.weight_feature_key = weight_feature_key
+
+
+class HashSequenceEmbeddingColumn(_HashColumn):
+  """:class:`SequenceEmbeddingColumn` over a :class:`HashTable`: a sample's first ``max_len`` RAW ids looked up
+  into ``[batch, max_len, dimension]``.  ``pad_id`` is a raw id, any int64 the table can store (not a sentinel
+  of the table); None: the positions past a sample's length are zero rows.  A column on more than one rank
+  needs a ``pad_id``.  The table arguments are :class:`HashEmbeddingColumn`'s."""
+
+  def __init__(self, key, capacity, dimension, max_len, pad_id=None, max_norm=None, dedup=False, slab_size=8,
+               init_scale=1e-3, seed=0, expiring=False, min_freq=0, sketch_depth=4, sketch_width=None,
+               sketch_seed=0):
+    from hybridbackend_amd.embedding.hash_sequence import check_hash_sequence_args
+    self._init_table_args(key, capacity, dimension, max_norm, dedup, slab_size, init_scale, seed, expiring,
+                          min_freq, sketch_depth, sketch_width, sketch_seed)
+    (self.max_len,), (self.pad_id,) = check_hash_sequence_args([self._probe], max_len, pad_id)
+
+
+def _is_hash(col):
+  return isinstance(col, _HashColumn)
+
+
 class _TableLayer:
   """What DenseFeatures and SequenceFeatures share: one table per column, replicated or sharded by the
-  reference's rule, the optimizer slots, and the checkpoints."""
+  reference's rule (a hash-keyed column: one :class:`HashTable`, sharded by ``floormod(id, W)`` whenever
+  W > 1), the optimizer slots, and the checkpoints."""
 
   def _init_tables(self, columns, device, coll, batch_size, init, initial_accumulator_value, optimizer,
-                   adam, ftrl):
+                   adam, ftrl, train=True):
     self.columns = list(columns)
     self.device = torch.device(device)
     self.coll = coll
+    self.train = bool(train)
+    self._initial_accumulator_value = initial_accumulator_value
     world = coll.world_size if coll is not None else 1
     rank = coll.rank if coll is not None else 0
     if init is None:
       def init(col, rows, dev):
         return torch.empty(rows, col.dimension, device=dev).uniform_(-1e-3, 1e-3)
-    self.sharded, self.weights = [], []
+    self.sharded, self.weights, self.hash_tables = [], [], []
     for col in self.columns:
+      if _is_hash(col):
+        # never replicated: slot numbers differ per rank, and replicated tables are not stepped at W > 1
+        table = col.make_table(self.device, world)
+        self.hash_tables.append(table)
+        self.sharded.append(world > 1)
+        self.weights.append(table.table)
+        continue
+      self.hash_tables.append(None)
       is_sharded, rows, _ = sharded_bucket_size(col.num_buckets, world, rank, batch_size)
       is_sharded = is_sharded and world > 1
       self.sharded.append(is_sharded)
@@ -85,8 +182,11 @@ class _TableLayer:
         opt = opt if opt is not None else cls.default(self.device)
         setattr(self, cls.name, opt)
         setattr(self, cls.slot_kw, [opt.slots_like(w) for w in self.weights])
-    self._rep = [c for c in range(len(self.columns)) if not self.sharded[c]]
-    self._shd = [c for c in range(len(self.columns)) if self.sharded[c]]
+    self._hash = [c for c in range(len(self.columns)) if self.hash_tables[c] is not None]
+    self._rep = [c for c in range(len(self.columns)) if not self.sharded[c] and c not in self._hash]
+    self._shd = [c for c in range(len(self.columns)) if self.sharded[c] and c not in self._hash]
+    # the lookup objects of the hash group: one rank (_hash_lookup + _hash_grad) or the sharded step
+    self._hash_lookup = self._hash_grad = self._hash_sharded = None
 
   def _two_slot_kw(self, idx):
     """The drivers' keyword arguments of the two-slot optimizers, tables idx."""
@@ -97,6 +197,94 @@ class _TableLayer:
       kw[cls.name] = getattr(self, cls.name)
     return kw
 
+  # ---- hash-keyed columns: what moves with a table ------------------------------------------------------
+  def _world(self):
+    return self.coll.world_size if self.coll is not None else 1
+
+  def _sharded_hash_lookup(self, combiners):
+    """The sharded step of the hash group (W > 1)."""
+    attr = lambda name: [getattr(self.columns[c], name) for c in self._hash]   # noqa: E731
+    pick = lambda xs: [xs[c] for c in self._hash]   # noqa: E731
+    # (the driver's own fill value: read only with accums, which the layer keeps only with a value of its own)
+    kw = {} if self.accums is None else dict(accums=pick(self.accums),
+                                             initial_accumulator_value=self._initial_accumulator_value)
+    return ShardedHashGroupLookup(pick(self.hash_tables), self.coll, combiners=combiners, dedup=attr('dedup'),
+                                  max_norms=attr('max_norm'), train=self.train, **kw,
+                                  **self._two_slot_kw(self._hash))
+
+  def _hash_slot_kinds(self):
+    """The layer's optimizer slots in the drivers' one order with their fill values (``sharded_hash.slot_kinds``):
+    the fill value is what a row no key holds is set to -- what the slot was made with."""
+    return slot_kinds(self, self._initial_accumulator_value if self.accums is not None else 0.0)
+
+  def _hash_companions(self, c):
+    """The slots of hash column c as ``(tensor, fill_value)`` pairs."""
+    return slot_companions(self, self._hash_slot_kinds(), c)
+
+  def _rebuild_hash_grad(self):
+    """(W = 1) the backward object of the hash group over the lookup's current tables and the layer's slots."""
+    raise NotImplementedError
+
+  def _rehash_each(self, policy):
+    """``policy(table, companions)`` -> None or the new companion tensors, on every hash table; the tensors that
+    moved are stored back and the lookup objects rebuilt over them.  Returns the keys of the columns rehashed."""
+    kinds = self._hash_slot_kinds()
+    moved = []
+    for c in self._hash:
+      out = policy(self.hash_tables[c], self._hash_companions(c))
+      if out is None:
+        continue
+      moved.append(self.columns[c].key)
+      self.weights[c] = self.hash_tables[c].table
+      for (name, k, _), x in zip(kinds, out):
+        slots = getattr(self, name)
+        if k is None:
+          slots[c] = x
+        else:
+          pair = list(slots[c])
+          pair[k] = x
+          slots[c] = tuple(pair)
+    if moved and self._hash_sharded is not None:
+      pick = lambda xs: None if xs is None else [xs[c] for c in self._hash]   # noqa: E731
+      self._hash_sharded.rebind(accums=pick(self.accums), moments=pick(self.moments),
+                                ftrl_slots=pick(self.ftrl_slots))
+    elif moved:
+      self._hash_lookup.rebind()
+      self._rebuild_hash_grad()
+    return moved
+
+  def set_step(self, n):
+    """The step number of every expiring hash table (:meth:`HashTable.set_step`).  The layers do not advance it
+    themselves: a captured graph follows the device scalar."""
+    for t in self.hash_tables:
+      if t is not None and t.expiring:
+        t.set_step(n)
+
+  def maybe_grow(self, max_load=0.75, factor=2.0):
+    """:meth:`HashTable.maybe_grow` on every hash table, the layer's optimizer slots moving along as companions
+    (rows no key holds: Adagrad's ``initial_accumulator_value``, Adam's 0, FTRL's accum its
+    ``initial_accumulator_value`` and linear 0).  The new tensors are stored back into ``weights``, ``accums``,
+    ``moments`` and ``ftrl_slots`` and the lookup objects rebuilt over them: afterwards ``layer.weights[c] is
+    layer.hash_tables[c].table`` and the next forward and backward work as before; tensors taken from the layer
+    earlier (and a captured graph) are void.  Local to the rank: no exchange, and ranks need not agree.  Returns
+    the keys of the columns that were rehashed."""
+    return self._rehash_each(lambda t, comp: t.maybe_grow(max_load, factor, comp))
+
+  def maybe_evict(self, max_load=0.75, target_load=0.5, keep_freq=0, order='lru'):
+    """:meth:`HashTable.maybe_evict` on every hash table -- the capacity stays, the oldest (``order='lfu'``:
+    the least frequently used) keys leave -- with the companions and the bookkeeping of :meth:`maybe_grow`.
+    Every hash column must be ``expiring``.  Returns the keys of the columns that were rehashed."""
+    for c in self._hash:
+      if not self.columns[c].expiring:
+        raise _bad(f'maybe_evict: hash column {self.columns[c].key!r} is not expiring (build the column with '
+                   'expiring=True)')
+    return self._rehash_each(lambda t, comp: t.maybe_evict(max_load, target_load, keep_freq, comp, order=order))
+
+  def _refuse_backward_of_a_find(self, what):
+    if self._hash and not self.train:
+      raise _bad(f'{what}.backward: the layer was built with train=False, its hash columns only find: there is '
+                 'nothing to step')
+
   # ---- checkpoints (hybridbackend/tensorflow/training/saver.py:97-185) ----------------------------
   def variables(self):
     """``{name: tensor | ShardedSlice}`` of this rank: the embedding weights (TF naming:
@@ -104,7 +292,8 @@ class _TableLayer:
     variables.py:112-141) and, when the layer keeps them, the Adagrad slots (``.../Adagrad``) or the
     Lazy Adam slots (``.../Adam`` = m, ``.../Adam_1`` = v, sharded as the weights) with the 0-d
     scalars ``beta1_power`` and ``beta2_power``, or the FTRL slots (``.../Ftrl`` = accum,
-    ``.../Ftrl_1`` = linear, sharded as the weights)."""
+    ``.../Ftrl_1`` = linear, sharded as the weights).  Hash-keyed columns are not in it: they do not fit a
+    mapping of preallocated tensors, ``save`` and ``restore`` handle them beside it."""
     from hybridbackend_amd.training.saver import ShardedSlice
     world = self.coll.world_size if self.coll is not None else 1
     rank = self.coll.rank if self.coll is not None else 0
@@ -118,6 +307,8 @@ class _TableLayer:
         extra.update(getattr(self, cls.name).tf_variables())
     out = {}
     for c, col in enumerate(self.columns):
+      if _is_hash(col):
+        continue   # (the number of keys is the state: save / restore export and import them beside this dict)
       name = f'{col.key}_embedding/embedding_weights'
       for suffix, tensors in per_table:
         if tensors is None:
@@ -145,12 +336,87 @@ class _TableLayer:
     call this together.  The device work of the current stream is waited for first."""
     if self.device.type == 'cuda':
       torch.cuda.current_stream(self.device).synchronize()
-    return self._saver(barrier).save(prefix, self.variables())
+    variables = self.variables()
+    variables.update(self._hash_variables())
+    return self._saver(barrier).save(prefix, variables)
+
+  def _hash_variables(self):
+    """The hash columns' state for a save: per column :meth:`HashTable.export_items` with the layer's slots as
+    companions (the drivers' order: accums; m, v; accum, linear), named ``<key>_embedding/embedding_weights
+    [/part_<rank>_of_<W>]/items/...``.  At W > 1 every rank writes its own part (``PerRank``)."""
+    from hybridbackend_amd.training.saver import PerRank
+    world = self._world()
+    rank = self.coll.rank if self.coll is not None else 0
+    out = {}
+    for c in self._hash:
+      exp = self.hash_tables[c].export_items(slots=[t for t, _ in self._hash_companions(c)])
+      name = f'{self.columns[c].key}_embedding/embedding_weights'
+      if world > 1:
+        name += f'/part_{rank}_of_{world}'
+      for k, v in exp.variables(name).items():
+        out[k] = PerRank(v) if world > 1 else v
+    return out
 
   def restore(self, prefix, barrier=None, layout='logical'):
     """Loads this rank's rows from a checkpoint written at ANY world size (``layout='reference'``:
-    the reference's contiguous slicing instead, see training/saver.py)."""
-    self._saver(barrier).restore(prefix, self.variables(), layout=layout)
+    the reference's contiguous slicing instead, see training/saver.py).  A hash column imports, of the keys
+    every rank of the saving job exported, those this rank owns (:meth:`HashTable.import_items` with ``world``
+    and ``rank``: an upsert, with rows, ``last_seen`` / ``freq`` and the optimizer slots); a table too small
+    for them raises ``import_items``'s error.  A column whose name the checkpoint holds as the other kind of
+    variable (bucketed against hash-keyed) is refused by name."""
+    if layout not in ('logical', 'reference'):
+      raise ValueError("layout must be 'logical' or 'reference'")
+    saver = self._saver(barrier)
+    exports = self._load_hash_exports(prefix)   # (every name, kind and part set is checked before anything moves)
+    for c, exp in exports:
+      self.hash_tables[c].import_items(exp, self._hash_companions(c), world=saver.world_size, rank=saver.rank)
+    saver.restore(prefix, self.variables(), layout=layout)
+
+  def _load_hash_exports(self, prefix):
+    """What a restore imports: ``[(column, HashExport)]`` of the hash columns the checkpoint holds, read to the
+    host.  Everything that can be refused without touching a table is refused here, for ALL columns, before the
+    first import: a name the checkpoint holds as the other kind of variable, parts that are not ``part_0 ..
+    part_<W-1>_of_<W>`` of one W (or the one unsharded entry), an export whose companions are not the layer's
+    slots.  (A table too small for its keys is found by ``import_items`` itself, which stores what fits.)"""
+    import numpy as np   # pylint: disable=import-outside-toplevel
+    from hybridbackend_amd.training.saver import _read_index, load_full
+    names = set(_read_index(prefix)['variables'])
+    found = []
+    for c, col in enumerate(self.columns):
+      name = f'{col.key}_embedding/embedding_weights'
+      part = re.compile(re.escape(name) + r'(?:/part_(\d+)_of_(\d+))?/items/keys$')
+      hits = sorted((m.group(1) is not None, int(m.group(2) or 1), int(m.group(1) or 0), n[:-len('/items/keys')])
+                    for n, m in ((n, part.match(n)) for n in names) if m)
+      if not _is_hash(col):
+        if hits and name not in names:
+          raise _bad(f'restore: {name}: the checkpoint holds the items of a hash-keyed column, the layer a '
+                     'bucketed variable of this name')
+        continue
+      if name in names:
+        raise _bad(f'restore: {name}: the checkpoint holds a bucketed variable, the layer a hash-keyed column of '
+                   'this name')
+      if not hits:
+        continue   # (names missing from the checkpoint are left untouched)
+      world = hits[0][1]
+      if [(h[1], h[2]) for h in hits] != [(world, r) for r in range(world)] or len({h[0] for h in hits}) != 1:
+        raise _bad(f'restore: {name}: the checkpoint does not hold the parts 0 .. W-1 of one world size (found '
+                   f'{", ".join(h[3][len(name):] or "the unsharded entry" for h in hits)})')
+      found.append((c, [h[3] for h in hits]))
+    out = []
+    for c, bases in found:
+      parts = []
+      for base in bases:
+        d = {n: torch.from_numpy(np.array(load_full(prefix, n), copy=True))
+             for n in names if n.startswith(base + '/items/')}
+        parts.append(HashExport.from_variables(base, d))
+      exp = HashExport.cat(parts)
+      slots = self._hash_companions(c)
+      if len(exp.slots) != len(slots) or exp.rows.shape[1:] != self.hash_tables[c].table.shape[1:]:
+        raise _bad(f'restore: {self.columns[c].key}_embedding/embedding_weights: the checkpoint holds rows of '
+                   f'{tuple(exp.rows.shape[1:])} floats with {len(exp.slots)} optimizer slot tensors, the layer '
+                   f'rows of {tuple(self.hash_tables[c].table.shape[1:])} with {len(slots)}')
+      out.append((c, exp))
+    return out
 
   def restore_reference(self, prefix, names=None, barrier=None, layout='logical'):
     """Loads this rank's rows from a checkpoint the REFERENCE saved (TensorFlow tensor bundle,
@@ -162,6 +428,8 @@ class _TableLayer:
   def close(self):
     if self._sharded is not None:
       self._sharded.close()
+    if self._hash_sharded is not None:
+      self._hash_sharded.close()
 
 
 class DenseFeatures(_TableLayer):
@@ -184,12 +452,29 @@ class DenseFeatures(_TableLayer):
       FTRL slots -- accum filled with ``ftrl.initial_accumulator_value``, zero linear -- for
       ``backward(optimizer='ftrl')``; ``ftrl`` is the :class:`Ftrl` they step with (TF's defaults
       when omitted).
+    train: False makes every hash-keyed column a pure find -- unseen ids read zero rows, ``size()`` and
+      ``counts`` do not move, and ``backward`` is refused; bucketed columns ignore it.
+
+  Hash-keyed columns (:class:`HashEmbeddingColumn`) mix freely with bucketed ones; column order decides the
+  block offsets.  ``hash_tables[c]`` is the column's :class:`HashTable` (None for a bucketed column) and
+  ``weights[c]`` its ``table``; ``accums`` / ``moments`` / ``ftrl_slots`` of such a column are ``[capacity_local,
+  dim]``.  On one rank the hash group goes through one :class:`HashGroupLookup` and one ``GroupLookupGrad``; on
+  W > 1 ranks through one :class:`ShardedHashGroupLookup` (owner ``floormod(id, W)``), a step of its own beside
+  the bucketed columns' -- and ``weight_feature_key`` on a hash column is then refused.  See ``set_step``,
+  ``maybe_grow`` and ``maybe_evict``.  Spilling to a host tier, ``track_removals`` and delta exports are not
+  driven by the layer: compose them on ``hash_tables``.
   """
 
   def __init__(self, columns, device, coll=None, batch_size=0, init=None,
-               initial_accumulator_value=None, optimizer=None, adam=None, ftrl=None):
+               initial_accumulator_value=None, optimizer=None, adam=None, ftrl=None, train=True):
     self._init_tables(columns, device, coll, batch_size, init, initial_accumulator_value, optimizer,
-                      adam, ftrl)
+                      adam, ftrl, train)
+    for c in self._hash:
+      col = self.columns[c]
+      if col.weight_feature_key is not None and self._world() > 1:
+        raise _bad(f'hash column {col.key!r}: weight_feature_key {col.weight_feature_key!r} on a layer over '
+                   f'{self._world()} ranks: the sharded step refuses weights on a column without a bucket '
+                   '(weighted hash columns work on one rank)')
     self.offsets, off = [], 0
     for col in self.columns:
       self.offsets.append(off)
@@ -223,6 +508,20 @@ class DenseFeatures(_TableLayer):
                                          accums=(pick(self._shd, self.accums)
                                                  if self.accums is not None else None),
                                          **two_slot_kw(self._shd))
+    if self._hash:
+      combiners = [self.columns[c].combiner for c in self._hash]
+      if self._world() > 1:
+        self._hash_sharded = self._sharded_hash_lookup(combiners)
+      else:
+        self._hash_lookup = HashGroupLookup(pick(self._hash, self.hash_tables), combiners=combiners,
+                                            max_norms=[self.columns[c].max_norm for c in self._hash],
+                                            train=self.train)
+        self._rebuild_hash_grad()
+
+  def _rebuild_hash_grad(self):
+    self._hash_grad = GroupLookupGrad(
+      self._hash_lookup.lookup, [self.accums[c] for c in self._hash] if self.accums is not None else None,
+      **self._two_slot_kw(self._hash))
 
   def _weights(self, features):
     """Per column its fp32 per-id weights (weight_feature_key) or None; None when no column has any."""
@@ -283,6 +582,22 @@ class DenseFeatures(_TableLayer):
       views = views or col_views()
       self._sharded(pick(self._shd, ids), pick(self._shd, splits), pick(self._shd, dests or views),
                     sp_weights=pick_w(self._shd))
+    if self._hash:
+      # the hash columns write their blocks in place too: outs = the block's views (the translate's slot
+      # buffers stay with the lookup object)
+      if self._hash_lookup is not None and batch and dests is None:
+        # (as for the replicated group: the blocks' addresses are arithmetic, views only when the checks need them)
+        def hash_views():
+          nonlocal views
+          views = views or col_views()
+          return pick(self._hash, views)
+        self._hash_lookup.call_block(pick(self._hash, ids), pick(self._hash, splits), out,
+                                     pick(self._hash, self.offsets), hash_views, sp_weights=pick_w(self._hash))
+      else:
+        views = views or col_views()
+        look = self._hash_lookup if self._hash_lookup is not None else self._hash_sharded
+        look(pick(self._hash, ids), pick(self._hash, splits), pick(self._hash, dests or views),
+             sp_weights=pick_w(self._hash))
     for c in self._staged:
       views[c].copy_(dests[c])
     self._last = (ids, splits, ws)
@@ -317,8 +632,12 @@ class DenseFeatures(_TableLayer):
     ``optimizer='ftrl'``): the FTRL-Proximal step.
     ``weight_grads=True``: returns ``(slices, {weight_feature_key: tensor})`` -- the gradient of every
     weighted column's per-id weights (fp32 ``[n_ids]``; replicated and sharded tables alike, taken at the
-    rows as the forward read them), an empty dict for a layer without weighted columns."""
+    rows as the forward read them), an empty dict for a layer without weighted columns.
+    A hash-keyed column is always stepped (it is never replicated), and the ``unique_rows`` of its
+    IndexedSlices are SLOT NUMBERS of this rank's table: ``layer.hash_tables[c].keys[unique_rows]`` names the
+    ids.  Refused after a forward of a layer built with ``train=False``."""
     _opt.two_slot_class(optimizer, self, "DenseFeatures(..., optimizer='{name}')")
+    self._refuse_backward_of_a_find('DenseFeatures')
     ids, splits, ws = self._last
     if grad.dim() != 2 or grad.shape[1] != self.width or grad.dtype != torch.float32:
       raise _lib.InvalidArgumentError(
@@ -366,7 +685,8 @@ class DenseFeatures(_TableLayer):
                      apply_lr=rep_lr, optimizer=optimizer, emit=emit or rep_lr == 0.0,
                      grad_block=grad_block,
                      sp_weights=None if ws is None else pick(self._rep, ws),
-                     finish=not (self._shd and apply_lr != 0.0), weight_grads=want(self._rep))
+                     finish=not ((self._shd or self._hash) and apply_lr != 0.0),
+                     weight_grads=want(self._rep))
       r = take(self._rep, r)
       for k, c in enumerate(self._rep):
         res[c] = r[k]
@@ -375,9 +695,31 @@ class DenseFeatures(_TableLayer):
                for c in self._shd]
       views = [v.contiguous() if c in self._staged else v for c, v in zip(self._shd, views)]
       r = self._sharded.backward(views, apply_lr=apply_lr, optimizer=optimizer,
-                                 emit=emit, weight_grads=want(self._shd))
+                                 emit=emit, finish=not (self._hash and apply_lr != 0.0),
+                                 weight_grads=want(self._shd))
       r = take(self._shd, r)
       for k, c in enumerate(self._shd):
+        res[c] = r[k]
+    if self._hash_sharded is not None:
+      views = [grad[:, self.offsets[c]:self.offsets[c] + self.columns[c].dimension]
+               for c in self._hash]
+      views = [v.contiguous() if c in self._staged else v for c, v in zip(self._hash, views)]
+      r = self._hash_sharded.backward(views, apply_lr=apply_lr, optimizer=optimizer, emit=emit)
+      for k, c in enumerate(self._hash):
+        res[c] = r[k]
+    elif self._hash:
+      # the last forward's slot numbers are the ids of the backward: the tables are stepped at W = 1 only here
+      grads, grad_block = None, (grad, pick(self._hash, self.offsets))
+      if any(c in self._staged for c in self._hash):
+        views = col_grads()
+        grads = [views[c].contiguous() for c in self._hash]
+        grad_block = None
+      r = self._hash_grad(self._hash_lookup.slots, grads, pick(self._hash, splits), apply_lr=apply_lr,
+                          optimizer=optimizer, emit=emit, grad_block=grad_block,
+                          sp_weights=None if ws is None else pick(self._hash, ws),
+                          weight_grads=want(self._hash))
+      r = take(self._hash, r)
+      for k, c in enumerate(self._hash):
         res[c] = r[k]
     if weight_grads:
       return res, wgrads
@@ -423,13 +765,28 @@ class SequenceFeatures(_TableLayer):
   looked up through ``ShardedGroupLookup`` as ``batch * max_len`` ids of one sample each, over the grid
   ``sequence_row_grid`` builds.  The sharded step bucketizes its ids again, which would carry the ``-1`` of
   a zero-padded position to row ``num_buckets - 1``: a sharded sequence column therefore requires a
-  ``pad_id`` (zero-padded sequences on sharded tables are not provided)."""
+  ``pad_id`` (zero-padded sequences on sharded tables are not provided).
+
+  Hash-keyed columns (:class:`HashSequenceEmbeddingColumn`) mix freely with bucketed ones.  On one rank they go
+  through ``HashSequenceLookup`` / ``SequenceLookupGrad``; on W > 1 ranks through ``ShardedHashGroupLookup``
+  with combiner ``'sum'`` over the RAW-id grid ``sequence_id_grid`` builds (``batch * max_len`` ids of one sample
+  each): ids past ``max_len`` are not in the grid, so they are not inserted, counted or kept fresh on any rank,
+  and a pad id is required there too.  ``train``, ``hash_tables``, ``set_step``, ``maybe_grow`` and
+  ``maybe_evict`` are :class:`DenseFeatures`'."""
 
   def __init__(self, columns, device, coll=None, batch_size=0, init=None,
-               initial_accumulator_value=None, optimizer=None, adam=None, ftrl=None):
+               initial_accumulator_value=None, optimizer=None, adam=None, ftrl=None, train=True):
+    from hybridbackend_amd.embedding.hash_sequence import HashSequenceLookup
     from hybridbackend_amd.embedding.sequence import SequenceLookup, SequenceLookupGrad
     self._init_tables(columns, device, coll, batch_size, init, initial_accumulator_value, optimizer,
-                      adam, ftrl)
+                      adam, ftrl, train)
+    for c in self._hash:
+      col = self.columns[c]
+      if col.pad_id is None and self._world() > 1:
+        raise _bad(f'hash sequence column {col.key!r}: its table is sharded over {self._world()} ranks, and a '
+                   'sharded sequence column requires a pad_id (the sharded step takes one raw id per position, '
+                   'and among raw ids no value means "nothing": every int64 is a key; zero padding is for one '
+                   'rank)')
     for c in self._shd:
       col = self.columns[c]
       if col.pad_id is None:
@@ -456,6 +813,19 @@ class SequenceFeatures(_TableLayer):
                                          accums=(pick(self._shd, self.accums)
                                                  if self.accums is not None else None),
                                          **self._two_slot_kw(self._shd))
+    if self._hash and self._world() > 1:
+      self._hash_sharded = self._sharded_hash_lookup('sum')
+    elif self._hash:
+      self._hash_lookup = HashSequenceLookup(pick(self._hash, self.hash_tables), attr(self._hash, 'max_len'),
+                                             pad_ids=attr(self._hash, 'pad_id'),
+                                             max_norms=attr(self._hash, 'max_norm'), train=self.train)
+      self._rebuild_hash_grad()
+
+  def _rebuild_hash_grad(self):
+    from hybridbackend_amd.embedding.sequence import SequenceLookupGrad
+    self._hash_grad = SequenceLookupGrad(
+      self._hash_lookup, [self.accums[c] for c in self._hash] if self.accums is not None else None,
+      **self._two_slot_kw(self._hash))
 
   def __call__(self, features):
     """features[key] = ``(values, row_splits)`` (int32/int64 ids, int32 ``[batch + 1]``), or an id vector
@@ -487,6 +857,21 @@ class SequenceFeatures(_TableLayer):
       for k, c in enumerate(self._shd):
         outs[c] = o[k].view(batch or 0, cols[k].max_len, cols[k].dimension)
         lengths[c] = ln[k]
+    if self._hash_sharded is not None:
+      # the RAW-id grid: B * T ids of one sample each, the pad id past a sample's length; ids past T are not in
+      # it, so they reach no owner
+      from hybridbackend_amd.embedding.sequence import sequence_id_grid
+      cols = pick(self._hash, self.columns)
+      grids, ln = sequence_id_grid(pick(self._hash, ids), pick(self._hash, splits),
+                                   [col.max_len for col in cols], [col.pad_id for col in cols])
+      o = self._hash_sharded(grids)
+      for k, c in enumerate(self._hash):
+        outs[c] = o[k].view(batch or 0, cols[k].max_len, cols[k].dimension)
+        lengths[c] = ln[k]
+    elif self._hash:
+      o, ln = self._hash_lookup(pick(self._hash, ids), pick(self._hash, splits))
+      for k, c in enumerate(self._hash):
+        outs[c], lengths[c] = o[k], ln[k]
     return outs, lengths
 
   def backward(self, grads, apply_lr=0.0, optimizer='sgd', emit=True):
@@ -494,8 +879,11 @@ class SequenceFeatures(_TableLayer):
     ``IndexedSlices`` ``(unique_rows, grad_rows, n_unique)`` of this rank's rows, as
     ``DenseFeatures.backward`` does and with its rule for the step: the sharded tables are stepped in the
     same pass, replicated tables are stepped only at W = 1 (at W > 1 their gradients must be aggregated
-    across ranks first; their IndexedSlices are returned)."""
+    across ranks first; their IndexedSlices are returned).  A hash-keyed column is always stepped, and its
+    ``unique_rows`` are slot numbers of this rank's table (``layer.hash_tables[c].keys[unique_rows]`` names the
+    ids).  Refused after a forward of a layer built with ``train=False``."""
     _opt.two_slot_class(optimizer, self, "SequenceFeatures(..., optimizer='{name}')")
+    self._refuse_backward_of_a_find('SequenceFeatures')
     if len(grads) != len(self.columns):
       raise _lib.InvalidArgumentError(
         _lib.INVALID_ARGUMENT, f'expected {len(self.columns)} gradients, got {len(grads)}')
@@ -504,13 +892,22 @@ class SequenceFeatures(_TableLayer):
       rep_lr = apply_lr if (self.coll.world_size if self.coll is not None else 1) <= 1 else 0.0
       # one optimizer step: the powers advance with the last call that steps (the sharded one)
       r = self._grad([grads[c] for c in self._rep], apply_lr=rep_lr, optimizer=optimizer,
-                     emit=emit or rep_lr == 0.0, finish=not (self._shd and apply_lr != 0.0))
+                     emit=emit or rep_lr == 0.0,
+                     finish=not ((self._shd or self._hash) and apply_lr != 0.0))
       for k, c in enumerate(self._rep):
         res[c] = r[k]
+    flat = lambda c: grads[c].contiguous().view(   # noqa: E731
+      grads[c].shape[0] * self.columns[c].max_len, self.columns[c].dimension)
     if self._shd:
-      flat = [grads[c].contiguous().view(grads[c].shape[0] * self.columns[c].max_len, self.columns[c].dimension)
-              for c in self._shd]
-      r = self._sharded.backward(flat, apply_lr=apply_lr, optimizer=optimizer, emit=emit)
+      r = self._sharded.backward([flat(c) for c in self._shd], apply_lr=apply_lr, optimizer=optimizer, emit=emit,
+                                 finish=not (self._hash and apply_lr != 0.0))
       for k, c in enumerate(self._shd):
         res[c] = r[k]
+    if self._hash_sharded is not None:
+      r = self._hash_sharded.backward([flat(c) for c in self._hash], apply_lr=apply_lr, optimizer=optimizer,
+                                      emit=emit)
+    elif self._hash:
+      r = self._hash_grad([grads[c] for c in self._hash], apply_lr=apply_lr, optimizer=optimizer, emit=emit)
+    for k, c in enumerate(self._hash):
+      res[c] = r[k]
     return res

@@ -67,6 +67,16 @@ class ShardedSlice:
     return q * self.rank + min(self.rank, rem)
 
 
+class PerRank:
+  """A whole tensor that EVERY rank writes (a plain tensor is written by rank 0 only): state that is per rank
+  without being a row slice of one table -- a hash table's exported keys and rows, whose number is the state.  The
+  ranks give their entries different names (``.../part_<rank>_of_<W>/...``); an entry is restored whole, by the
+  name it was saved under."""
+
+  def __init__(self, tensor):
+    self.tensor = tensor
+
+
 def _to_numpy(t):
   """(array, dtype name): bfloat16 tensors are written as their 16-bit patterns."""
   t = t.detach()
@@ -97,8 +107,9 @@ class Saver:
 
   # -- save ------------------------------------------------------------------------------------
   def save(self, prefix, variables):
-    """variables: ``{name: tensor | ShardedSlice}``.  Replicated tensors are written by rank 0
-    only (saver.py:135-141), shards by every rank.  Returns ``prefix`` (saver.py:176-185)."""
+    """variables: ``{name: tensor | ShardedSlice | PerRank}``.  Replicated tensors are written by rank 0
+    only (saver.py:135-141), shards and :class:`PerRank` tensors by every rank.  Returns ``prefix``
+    (saver.py:176-185)."""
     tmp_dir = f'{prefix}_temp'
     part = os.path.join(tmp_dir, f'part-{self.rank:05d}-of-{self.world_size:05d}')
     if self.rank == 0:
@@ -109,9 +120,10 @@ class Saver:
       for name in sorted(variables):
         v = variables[name]
         sharded = isinstance(v, ShardedSlice)
-        if not sharded and self.rank != 0:
+        per_rank = isinstance(v, PerRank)
+        if not sharded and not per_rank and self.rank != 0:
           continue                      # only sharded saveables for non-chief workers
-        arr, dtype_name = _to_numpy(v.tensor if sharded else v)
+        arr, dtype_name = _to_numpy(v.tensor if sharded or per_rank else v)
         e = {'name': name, 'dtype': dtype_name, 'shape': list(arr.shape), 'offset': off,
              'nbytes': int(arr.nbytes)}
         if sharded:
@@ -193,6 +205,8 @@ class Saver:
       if name not in index['variables']:
         continue
       meta = index['variables'][name]
+      if isinstance(v, PerRank):
+        v = v.tensor
       if isinstance(v, ShardedSlice):
         if meta['full_shape'][0] != v.bucket_size:
           raise ValueError(f'{name}: checkpoint holds {meta["full_shape"][0]} rows, '

@@ -593,6 +593,22 @@ int hbk_group_lookup_fwd_sequence(int32_t n_cols, const hbk_lookup_column_t* col
  * two-launch form of the sequence lookup: the same bits as the fused entry. */
 int hbk_sequence_row_grid_n(int32_t n_cols, const hbk_lookup_column_t* cols,
                             const hbk_sequence_t* seq, hbk_stream_t stream);
+/* The RAW-id grid: what a sharded hash-keyed sequence column hands the sharded step as B * T ids of one sample
+ * each.  hbk_sequence_row_grid_n with bucket == 0 writes -1 for every negative id and every padding position,
+ * and -1 is an ordinary key of a hash table (see hbk_hash_translate_sequence_n); here the effective ids
+ * themselves are written.  With B, T, len_b and L_b as above, for every position p = b * T + t:
+ *     row_grid[p] = ids[row_splits[b] + t]   (t <  L_b; sign-extended from int32 ids, NEVER bucketized, negative
+ *                                             ids kept; an index outside [0, n_ids) is not read: pad_id)
+ *                 = pad_id                   (t >= L_b)
+ *     lengths[b]  = L_b                      (lengths may be NULL)
+ * row_splits == NULL: one id per sample.  Only ids and row_splits are read, and never an id past a sample's first
+ * T: cols[c].table, out, bucket, divisor, rows, dim and every other field of the column are ignored.
+ * Refused (HBK_INVALID_ARGUMENT) before any device work: seq == NULL, has_pad == 0 (there is no "nothing" value
+ * among raw ids), row_grid == NULL (also with B == 0), max_len < 1, B * T >= 2^31.  One launch for up to 64 columns, one thread per
+ * position, 8-byte coalesced stores; no workspace, no atomics, no host synchronisation: capturable.
+ * Detected by the presence of the symbol; the structs and the version are those of 0.2.0. */
+int hbk_sequence_id_grid_n(int32_t n_cols, const hbk_lookup_column_t* cols,
+                           const hbk_sequence_t* seq, hbk_stream_t stream);
 
 /* R10 (sharded form)  d(stitch + combiner): the transpose of the requester-side
  *   `gather(embeddings, shard_index)` + combiner (hbtf/embedding/sharding.py:200; TF emits
