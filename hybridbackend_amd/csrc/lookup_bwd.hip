@@ -1347,12 +1347,15 @@ __device__ inline void store_wt(float* p, float v) {
   asm volatile("global_store_dword %0, %1, off sc0 sc1" : : "v"(p), "v"(v) : "memory");
 }
 
-// out row u += (or =) v
+// out row u += (or =) v.  A new row is 0 + v, not v: a row whose ONE pair is stored straight from the
+// registers it arrived in would otherwise keep a term of -0.0 (a zero gradient under a negative weight)
+// where the scatter-add into zeros -- and every plan that sums into a zeroed accumulator -- gives +0.0
 template <typename V>
 __device__ inline void emit_row(const GCol& c, const ReduceJob& job, int32_t u, bool is_new,
                                 int sub, V v) {
   constexpr int VE = sizeof(V) / 4;
   V* o = reinterpret_cast<V*>(job.out_vals + (int64_t)u * c.dim + (int64_t)sub * VE);
+  if (is_new) v = v + 0.0f;
 #ifdef HBK_BWD_ABLATE_STORES   // probe builds: what the kernel costs without its output traffic
   if (u == 0x7fffffff) *o = v;
   (void)is_new;

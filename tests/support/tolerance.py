@@ -15,6 +15,24 @@ everywhere a test compares such sums (VERDICT r05 "next round" 1a).  With sequen
 the actual error is ~0.5 * 2^-24 * sum|terms| ~ 3e-8 * sum|terms|: the bound leaves a factor of
 > 100 and still catches one missing or doubled term of ordinary size (a term is ~1/n of
 sum|terms|; 1e-5 * n < 1 for every n < 100 000).
+
+What the bound cannot see: a missing or doubled term SMALLER than rel * sum|terms|, and on a hot row
+that is a sizeable share of them.  Measured in numpy (tests/test_exact_support.py repeats the second
+line as an assertion) -- fp32 sums in random order with ONE term of the row dropped, 200 trials:
+
+    terms in the row                          term size    bound     dropped terms not noticed
+    6 300   (skew='one' in the fuzz)          N(0,1)       0.050       6 of 200
+    50 000  (Zipf head of a big fuzz column)  N(0,1)       0.40       54 of 200
+    50 000  (mean over 4 ids)                 N(0,1)/4     0.099      57 of 200
+    4 000   (mean over 32 ids)                N(0,1)/32    0.00099     9 of 200
+
+Hot rows are where the reduce plans' special paths live (runs that cross shares, jobs of several chunks,
+split buckets and their merge), and the step-only optimizer modes are compared through this bound on
+every row that occurs more than once.  Those are pinned elsewhere, bit for bit: tests/support/exact.py
+makes inputs whose fp32 sums are exact in any order, and tests/test_gpu_backward_exact.py and
+test_group_lookup_random_plans_exact (tests/test_gpu_fuzz.py) hold every plan, the hot-row paths, the
+step-only modes, the sequence pad row and the sharded owner reduce to the float64 result's bits.  This
+bound stays for what the exact grid cannot express: arbitrary lengths and N(0,1) values.
 """
 import os
 

@@ -1,6 +1,7 @@
 """Randomised parity: hypothesis draws shapes, dims, id distributions, combiners and ragged
 layouts; the fused lookup, its backward and the stable partition must agree with the CPU oracle
-on every draw (bit-exact integers and in-order fp32 sums, 1e-5 against float64 for the backward)."""
+on every draw (bit-exact integers and in-order fp32 sums, 1e-5 against float64 for the backward; bit for
+bit on the exact twin of the plan fuzz, whose inputs sum exactly in any order)."""
 import os
 import sys
 
@@ -11,6 +12,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from tests.support import exact  # noqa: E402
 from tests.support.tolerance import (WIRE16_FLOOR, WIRE16_REL, assert_sums_close,  # noqa: E402
                                      dense_sums, world_grad_sums)
 
@@ -102,6 +104,79 @@ def test_group_lookup_random_plans(cols, opts, seed):
   old = {k: _lib.set_option(k, v) for k, v in opts.items()}
   try:
     _check_group_lookup(cols, seed)
+  finally:
+    for k, v in old.items():
+      _lib.set_option(k, v)
+
+
+@_cfg(20)
+@given(cols=st.lists(st.one_of(big_column, column), min_size=1, max_size=5), opts=plan_options,
+       seed=st.integers(0, 2**31 - 1))
+def test_group_lookup_random_plans_exact(cols, opts, seed):
+  """The exact twin of test_group_lookup_random_plans (tests/support/exact.py): the same columns and plan
+  switches, with ragged lengths moved onto the sets whose combiner factor is a power of two and
+  gradients on a grid sized per column from the drawn ids, so that every fp32 sum is exact in any order.
+  The emitted sums are BIT-EQUAL to the float64 scatter-add -- one lost or doubled pair of any size in
+  the Zipf head of a big column changes bits -- and the fused step (SGD or Adagrad by the seed, step only
+  on every third draw) is bit-equal to the oracle's apply of the EXACT sums, not of the call's own slices."""
+  import oracle
+  import hybridbackend_amd as hb
+  from hybridbackend_amd import _lib
+  rng = np.random.RandomState(seed)
+  tables, ids, splits, buckets, combs, grads, wants = [], [], [], [], [], [], []
+  for k, c in enumerate(cols):
+    if c['dim'] % 4 != 0 and c['dim'] > 64:
+      c = dict(c, dim=64)
+    tables.append(exact.exact_tables(rng, c['rows'], c['dim']))
+    if c['ragged']:
+      lens = exact.snap_lengths(rng.randint(0, c['max_len'] + 1, size=c['n_seg']), c['combiner'])
+      sp, n = exact.splits_of(lens), int(lens.sum())
+    else:
+      lens, sp, n = np.ones(1, np.int64), None, c['n_seg']
+    i = np.asarray(_ids(rng, n, c['rows'], c['skew']), np.int64)
+    rows = i % c['rows']
+    bits = exact.exact_terms_budget(rows, exact.factor_bits(c['combiner'], int(lens.max(initial=0))),
+                                    case=f'column {k} {c}')
+    g = exact.exact_grads(rng, (c['n_seg'], c['dim']), min(bits, 12))
+    wants.append(exact.exact_dense(tables[-1].shape, rows, exact.id_terms(g, sp, c['combiner']),
+                                   case=f'column {k} {c}'))
+    ids.append(i)
+    splits.append(sp)
+    buckets.append(c['rows'])
+    combs.append(c['combiner'])
+    grads.append(g)
+  opt = 'adagrad' if seed % 2 else 'sgd'
+  emit = seed % 3 != 0
+  lr = exact.EXACT_LR
+  old = {k: _lib.set_option(k, v) for k, v in opts.items()}
+  try:
+    d_ids = [dev(i) for i in ids]
+    d_sp = [None if s is None else dev(s) for s in splits]
+    lookup = hb.embedding.GroupLookup([dev(t) for t in tables], buckets, combs)
+    res = hb.embedding.GroupLookupGrad(lookup)(d_ids, [dev(g) for g in grads], d_sp)
+    for k, (u, g, nu) in enumerate(res):
+      n = int(nu.item())
+      got_rows = u.cpu().numpy()[:n]
+      order = np.argsort(got_rows, kind='stable')
+      np.testing.assert_equal(got_rows[order], wants[k].rows, err_msg=f'column {k}: emitted rows')
+      exact.assert_bits_equal(g.cpu().numpy()[:n][order], wants[k].sums(), f'column {k}: gradient sums',
+                              unit=wants[k].unit[wants[k].rows], rows=wants[k].rows)
+    t2 = [dev(t) for t in tables]
+    a2 = [torch.full_like(t, 0.1) for t in t2]
+    res2 = hb.embedding.GroupLookupGrad(hb.embedding.GroupLookup(t2, buckets, combs), accums=a2)(
+      d_ids, [dev(g) for g in grads], d_sp, apply_lr=lr, optimizer=opt, emit=emit)
+    for k in range(len(cols)):
+      assert int(res2[k][2].item()) == wants[k].rows.size
+      want_a = np.full(tables[k].shape, 0.1, np.float32)      # (SGD leaves the accumulator alone)
+      if opt == 'adagrad':
+        want_t = tables[k].copy()
+        oracle.sparse_adagrad_apply(want_t, want_a, wants[k].rows, wants[k].sums(), lr)
+      else:
+        want_t = exact.exact_sgd(tables[k], wants[k], lr, case=f'column {k}')   # (the step is exact too)
+        exact.assert_bits_equal(oracle.sparse_sgd_apply(tables[k].copy(), wants[k].rows, wants[k].sums(), lr),
+                                want_t, f'column {k}: oracle.sparse_sgd_apply of the exact sums')
+      exact.assert_bits_equal(t2[k].cpu().numpy(), want_t, f'column {k}: table after {opt}, emit={emit}')
+      exact.assert_bits_equal(a2[k].cpu().numpy(), want_a, f'column {k}: accumulator after {opt}, emit={emit}')
   finally:
     for k, v in old.items():
       _lib.set_option(k, v)
