@@ -72,6 +72,11 @@ class FtrlParams(C.Structure):
               ('lr_power', C.c_float)]
 
 
+class RowwiseAdagradParams(C.Structure):
+  """hbk_rowwise_adagrad_t"""
+  _fields_ = [('epsilon', C.c_float)]
+
+
 class Sequence(C.Structure):
   """hbk_sequence_t"""
   _fields_ = [('max_len', C.c_int32), ('has_pad', C.c_int32), ('pad_id', C.c_int64),
@@ -261,6 +266,10 @@ def _declare(l):
     'hbk_group_lookup_bwd_adam_clipped': (C.c_int, [i32, vp, vp, vp, vp, vp, C.c_float, vp, sz, vp]),
     'hbk_group_lookup_bwd_ftrl_clipped_workspace_bytes': (sz, [i32, vp, vp]),
     'hbk_group_lookup_bwd_ftrl_clipped': (C.c_int, [i32, vp, vp, vp, vp, vp, C.c_float, vp, sz, vp]),
+    'hbk_group_lookup_bwd_rowwise_adagrad_workspace_bytes': (sz, [i32, vp]),
+    'hbk_group_lookup_bwd_rowwise_adagrad': (C.c_int, [i32, vp, vp, vp, C.c_float, vp, sz, vp]),
+    'hbk_group_lookup_bwd_rowwise_adagrad_clipped_workspace_bytes': (sz, [i32, vp, vp]),
+    'hbk_group_lookup_bwd_rowwise_adagrad_clipped': (C.c_int, [i32, vp, vp, vp, vp, C.c_float, vp, sz, vp]),
     'hbk_group_lookup_bwd_weights': (C.c_int, [i32, vp, vp, vp, vp]),
     'hbk_group_lookup_fwd_sequence': (C.c_int, [i32, vp, vp, vp, vp]),
     'hbk_sequence_row_grid_n': (C.c_int, [i32, vp, vp, vp]),
@@ -330,6 +339,8 @@ def _declare(l):
     'hbk_sharded_lookup_bwd_adam': (C.c_int, [vp, vp, vp, vp, C.c_float, vp, vp, vp, vp]),
     'hbk_sharded_set_ftrl_slots': (C.c_int, [vp, vp, vp]),
     'hbk_sharded_lookup_bwd_ftrl': (C.c_int, [vp, vp, vp, vp, C.c_float, vp, vp, vp, vp]),
+    'hbk_sharded_set_rowwise_adagrad_slots': (C.c_int, [vp, vp]),
+    'hbk_sharded_lookup_bwd_rowwise_adagrad': (C.c_int, [vp, vp, vp, vp, C.c_float, vp, vp, vp, vp]),
     'hbk_sharded_lookup_bwd_weights': (C.c_int, [vp, vp, vp, vp, vp]),
   }
   for name, (res, args) in protos.items():
@@ -461,10 +472,35 @@ def require_device_tensor(t, what, row_strided=False):
   raise InvalidArgumentError(INVALID_ARGUMENT, f'{what} must be contiguous')
 
 
-def require_slot_pairs(pairs, tables, what, kw='moments', names=('m', 'v')):
-  """Two slots per table (Adam's (m, v), FTRL's (accum, linear)): fp32 device tensors of the table's
-  shape, contiguous, all distinct."""
+def _require_single_slots(slots, tables, what, kw, name, shape_of):
+  """One slot per table (row-wise Adagrad's ``[rows, 1]`` accumulator): the entries are the tensors."""
   import torch  # pylint: disable=import-outside-toplevel
+  slots = list(slots)
+  if len(slots) != len(tables):
+    raise InvalidArgumentError(INVALID_ARGUMENT, f'{what}: {len(slots)} {name} tensors for '
+                               f'{len(tables)} tables')
+  for c, (x, t) in enumerate(zip(slots, tables)):
+    if not isinstance(x, torch.Tensor):
+      raise InvalidArgumentError(INVALID_ARGUMENT, f'{what}: {kw}[{c}] must be a tensor')
+    require_device_tensor(x, f'{what}: {kw}[{c}]')
+    if x.dtype != torch.float32 or tuple(x.shape) != tuple(shape_of(t)):
+      raise InvalidArgumentError(INVALID_ARGUMENT, f'{what}: {kw}[{c}] must be fp32 {tuple(shape_of(t))}')
+  ptrs = [x.data_ptr() for x in slots] + [t.data_ptr() for t in tables]
+  if len(set(ptrs)) != len(ptrs):
+    raise InvalidArgumentError(INVALID_ARGUMENT, f'{what}: the {name} tensors and the tables must all be '
+                               'distinct buffers')
+  return slots
+
+
+def require_slot_pairs(pairs, tables, what, kw='moments', names=('m', 'v'), shape_of=None):
+  """The slots of every table, checked: two per table (Adam's (m, v), FTRL's (accum, linear)) as pairs, or
+  -- one name -- one tensor per table (row-wise Adagrad's accumulator).  fp32 device tensors of the shape
+  ``shape_of(table)`` (default: the table's), contiguous, all distinct."""
+  import torch  # pylint: disable=import-outside-toplevel
+  if shape_of is None:
+    shape_of = lambda t: tuple(t.shape)   # noqa: E731
+  if len(names) == 1:
+    return _require_single_slots(pairs, tables, what, kw, names[0], shape_of)
   pairs = [tuple(p) for p in pairs]
   pair = f'({names[0]}, {names[1]})'
   if len(pairs) != len(tables):
@@ -475,9 +511,9 @@ def require_slot_pairs(pairs, tables, what, kw='moments', names=('m', 'v')):
       raise InvalidArgumentError(INVALID_ARGUMENT, f'{what}: {kw}[{c}] must be an {pair} pair')
     for name, x in zip(names, two):
       require_device_tensor(x, f'{what}: {kw}[{c}].{name}')
-      if x.dtype != torch.float32 or tuple(x.shape) != tuple(t.shape):
+      if x.dtype != torch.float32 or tuple(x.shape) != tuple(shape_of(t)):
         raise InvalidArgumentError(INVALID_ARGUMENT,
-                                   f'{what}: {kw}[{c}].{name} must be fp32 {tuple(t.shape)}')
+                                   f'{what}: {kw}[{c}].{name} must be fp32 {tuple(shape_of(t))}')
   # neither step is additive: a buffer stepped as two slots (or as a slot and a table) would race
   ptrs = [x.data_ptr() for two in pairs for x in two] + [t.data_ptr() for t in tables]
   if len(set(ptrs)) != len(ptrs):

@@ -268,12 +268,14 @@ struct SlotNames {
   const char* who;   // "group_lookup_bwd_adam"
   const char* opt;   // "Adam"
   const char* s0;    // "m"
-  const char* s1;    // "v"
+  const char* s1;    // "v"; NULL: the optimizer has one slot
 };
 // host checks of a Lazy Adam call's hyperparameters (sparse_apply.hip): HBK_OK or HBK_INVALID_ARGUMENT
 int adam_check(const hbk_adam_t* adam, float lr, const char* who);
 // host checks of an FTRL call's hyperparameters (sparse_apply.hip): HBK_OK or HBK_INVALID_ARGUMENT
 int ftrl_check(const hbk_ftrl_t* ftrl, float lr, const char* who);
+// host checks of a row-wise Adagrad call's hyperparameters (sparse_apply.hip)
+int rowwise_adagrad_check(const hbk_rowwise_adagrad_t* opt, float lr, const char* who);
 
 // every host check hbk_group_lookup_bwd_apply makes of its columns, without launching anything
 // (lookup_bwd.hip): HBK_OK or HBK_INVALID_ARGUMENT

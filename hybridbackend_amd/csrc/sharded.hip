@@ -518,7 +518,8 @@ struct Layout {
   }
 };
 
-// a two-slot optimizer's slot shards, one per column (hbk_sharded_set_*_slots), or empty
+// a slot optimizer's slot shards, one per column (hbk_sharded_set_*_slots), or empty; an optimizer with
+// one slot (row-wise Adagrad) leaves s1 empty
 struct SlotPair {
   std::vector<float*> s0, s1;
 };
@@ -550,6 +551,7 @@ struct hbk_sharded {
   std::vector<const int32_t*> row_splits;
   hbk::SlotPair adam;   // Lazy Adam's m / v shards (hbk_sharded_set_adam_slots)
   hbk::SlotPair ftrl;   // FTRL's accum / linear shards (hbk_sharded_set_ftrl_slots)
+  hbk::SlotPair rowwise;   // row-wise Adagrad's [rows_local, 1] accumulators (hbk_sharded_set_rowwise_adagrad_slots)
   std::vector<float> max_norms;   // [N] the columns' max_norm (hbk_sharded_set_max_norms; 0: not clipped)
   std::vector<hbk_sharded_hash_t> hash;   // [N] the hash columns' tables (hbk_sharded_set_hash_tables; keys_cache
                                           // NULL: an ordinary column), or empty
@@ -1983,7 +1985,7 @@ struct ShardedStep {
 };
 }  // namespace
 
-// the backward of hbk_sharded_lookup_bwd_apply, hbk_sharded_lookup_bwd_adam and _ftrl
+// the backward of hbk_sharded_lookup_bwd_apply, hbk_sharded_lookup_bwd_adam, _ftrl and _rowwise_adagrad
 static int sharded_bwd(hbk_sharded_t p, const float* const* grads, const int32_t* grad_strides,
                        const ShardedStep& step, float apply_lr, int64_t* const* unique_rows,
                        float* const* grad_rows, int32_t* const* n_unique, hbk_stream_t stream_) {
@@ -2194,12 +2196,31 @@ extern "C" int hbk_sharded_lookup_bwd_apply(hbk_sharded_t p, const float* const*
 }
 
 namespace {
-// a two-slot optimizer's slot shards, checked and registered with the plan
+// a slot optimizer's slot shards, checked and registered with the plan (one slot: nm.s1 == s1 == NULL)
 int set_slot_pair(hbk_sharded_t p, const hbk::SlotNames& nm, float* const* s0, float* const* s1,
                   hbk::SlotPair hbk_sharded::*pair) {
   using namespace hbk;
   const char* who = nm.who;
   HBK_REQUIRE(p != nullptr, "%s: plan is NULL", who);
+  if (nm.s1 == nullptr) {
+    HBK_REQUIRE(s0 != nullptr, "%s: the %s array is NULL", who, nm.s0);
+    std::vector<uintptr_t> seen;
+    for (int c = 0; c < p->N; ++c) {
+      HBK_REQUIRE(s0[c] != nullptr, "%s: column %d: %s is NULL", who, c, nm.s0);
+      HBK_REQUIRE(((uintptr_t)s0[c] & 3) == 0, "%s: column %d: %s must be 4-byte aligned", who, c, nm.s0);
+      seen.push_back((uintptr_t)s0[c]);
+    }
+    std::sort(seen.begin(), seen.end());
+    HBK_REQUIRE(std::adjacent_find(seen.begin(), seen.end()) == seen.end(), "%s: two columns share an %s buffer",
+                who, nm.s0);
+    for (int c = 0; c < p->N; ++c) {
+      HBK_REQUIRE(!std::binary_search(seen.begin(), seen.end(), (uintptr_t)p->cols[c].shard),
+                  "%s: column %d's shard (table) is also an %s slot", who, c, nm.s0);
+    }
+    (p->*pair).s0.assign(s0, s0 + p->N);
+    (p->*pair).s1.clear();
+    return HBK_OK;
+  }
   HBK_REQUIRE(s0 != nullptr && s1 != nullptr, "%s: the %s / %s arrays are NULL", who, nm.s0, nm.s1);
   for (int c = 0; c < p->N; ++c) {
     HBK_REQUIRE(s0[c] != nullptr, "%s: column %d: %s is NULL", who, c, nm.s0);
@@ -2227,7 +2248,7 @@ int set_slot_pair(hbk_sharded_t p, const hbk::SlotNames& nm, float* const* s0, f
   return HBK_OK;
 }
 
-// the host checks of a sharded two-slot backward before any exchange: the plan, the hyperparameters
+// the host checks of a sharded slot backward (two slots, or one: nm.s1 == NULL) before any exchange: the plan, the hyperparameters
 // (check()), slots registered by `setter`, no column with an Adagrad accumulator
 template <typename Check>
 int two_slot_prologue(hbk_sharded_t p, const hbk::SlotNames& nm, Check check, const char* setter,
@@ -2236,9 +2257,19 @@ int two_slot_prologue(hbk_sharded_t p, const hbk::SlotNames& nm, Check check, co
   HBK_REQUIRE(p != nullptr, "%s: plan is NULL", nm.who);
   const int rc = check();
   if (rc != HBK_OK) return rc;
-  HBK_REQUIRE((int)(p->*pair).s0.size() == p->N, "%s: no %s / %s slots (%s)", nm.who, nm.s0, nm.s1,
-              setter);
+  if (nm.s1 == nullptr) {
+    HBK_REQUIRE((int)(p->*pair).s0.size() == p->N, "%s: no %s slots (%s)", nm.who, nm.s0, setter);
+  } else {
+    HBK_REQUIRE((int)(p->*pair).s0.size() == p->N, "%s: no %s / %s slots (%s)", nm.who, nm.s0, nm.s1,
+                setter);
+  }
   for (int c = 0; c < p->N; ++c) {
+    if (nm.s1 == nullptr) {
+      HBK_REQUIRE(p->cols[c].accum == nullptr,
+                  "%s: column %d: the column's accum must be NULL (%s's slot is %s, from %s)", nm.who, c,
+                  nm.opt, nm.s0, setter);
+      continue;
+    }
     HBK_REQUIRE(p->cols[c].accum == nullptr,
                 "%s: column %d: the column's accum must be NULL (%s's slots are %s and %s, from %s)",
                 nm.who, c, nm.opt, nm.s0, nm.s1, setter);
@@ -2294,6 +2325,30 @@ extern "C" int hbk_sharded_lookup_bwd_ftrl(hbk_sharded_t p, const float* const* 
                            return hbk_group_lookup_bwd_ftrl_clipped(n, cols, clip, p->ftrl.s0.data() + c0,
                                                                     p->ftrl.s1.data() + c0, ftrl, lr, ws,
                                                                     ws_bytes, s);
+                         }};
+  return sharded_bwd(p, grads, grad_strides, step, lr, unique_rows, grad_rows, n_unique, stream_);
+}
+
+extern "C" int hbk_sharded_set_rowwise_adagrad_slots(hbk_sharded_t p, float* const* accum) {
+  return set_slot_pair(p, {"sharded_set_rowwise_adagrad_slots", "row-wise Adagrad", "accum", nullptr}, accum,
+                       nullptr, &hbk_sharded::rowwise);
+}
+
+extern "C" int hbk_sharded_lookup_bwd_rowwise_adagrad(hbk_sharded_t p, const float* const* grads,
+                                                      const int32_t* grad_strides,
+                                                      const hbk_rowwise_adagrad_t* opt, float lr,
+                                                      int64_t* const* unique_rows, float* const* grad_rows,
+                                                      int32_t* const* n_unique, hbk_stream_t stream_) {
+  using namespace hbk;
+  static const SlotNames kNames = {"sharded_lookup_bwd_rowwise_adagrad", "row-wise Adagrad", "accum", nullptr};
+  const int rc = two_slot_prologue(p, kNames, [&] { return rowwise_adagrad_check(opt, lr, kNames.who); },
+                                   "hbk_sharded_set_rowwise_adagrad_slots", &hbk_sharded::rowwise);
+  if (rc != HBK_OK) return rc;
+  const ShardedStep step{HBK_APPLY_SGD, hbk_group_lookup_bwd_rowwise_adagrad_clipped_workspace_bytes,
+                         [&](int32_t c0, int32_t n, const hbk_lookup_grad_column_t* cols, const float* clip,
+                             bool, void* ws, size_t ws_bytes, hbk_stream_t s) {
+                           return hbk_group_lookup_bwd_rowwise_adagrad_clipped(
+                               n, cols, clip, p->rowwise.s0.data() + c0, opt, lr, ws, ws_bytes, s);
                          }};
   return sharded_bwd(p, grads, grad_strides, step, lr, unique_rows, grad_rows, n_unique, stream_);
 }

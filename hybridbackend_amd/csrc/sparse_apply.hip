@@ -24,6 +24,13 @@
 // powers advance after the apply, in stream order (adam_finish_kernel), when the call asks for it.
 // FTRL has no device state besides its slots; its lr_power != -0.5 form (powf) is a separate
 // instantiation, so the default form carries no powf code.
+//
+// Row-wise Adagrad (hbk_group_lookup_bwd_rowwise_adagrad) rides the same walk with ONE slot of another
+// shape: an fp32 [rows, 1] accumulator.  Its rule (RowwiseAdagradRule, kRowwise) is not element-wise:
+// slot_task loads the row's accumulator word with the task's other loads (every lane of the row's group
+// reads the same address: one request), sums g * g over the lane group in the clip prologue's order
+// (chunk_sum, then the group_sum butterfly), and lane 0 of the group stores the word back.  Everything
+// kRowwise adds sits under `if constexpr`, so the other instantiations are the instructions they were.
 #include <string.h>
 
 #include <algorithm>
@@ -91,6 +98,7 @@ struct AdamRule {
   using State = float;
   static constexpr int kSlots = 2;
   static constexpr bool kStep = true;
+  static constexpr bool kRowwise = false;
   float lr_t, beta1, beta2, eps;
 
   __device__ static float& lds_lr_t() {
@@ -132,6 +140,7 @@ struct FtrlRule {
   struct State {};
   static constexpr int kSlots = 2;
   static constexpr bool kStep = true;
+  static constexpr bool kRowwise = false;
   const FtrlParams& a;
 
   __device__ static void setup(const FtrlParams&) {}
@@ -176,6 +185,7 @@ struct SgdRule {
   struct State {};
   static constexpr int kSlots = 0;
   static constexpr bool kStep = true;
+  static constexpr bool kRowwise = false;
   float lr;
 
   __device__ static void setup(const LrParams&) {}
@@ -198,6 +208,7 @@ struct AdagradRule {
   struct State {};
   static constexpr int kSlots = 1;
   static constexpr bool kStep = true;
+  static constexpr bool kRowwise = false;
   float lr;
 
   __device__ static void setup(const LrParams&) {}
@@ -215,10 +226,37 @@ struct EmitRule {
   struct State {};
   static constexpr int kSlots = 0;
   static constexpr bool kStep = false;
+  static constexpr bool kRowwise = false;
 
   __device__ static void setup(const LrParams&) {}
   __device__ static State state() { return State{}; }
   __device__ EmitRule(const LrParams&, State) {}
+};
+
+// Row-wise Adagrad (include/hbk.h, hbk_group_lookup_bwd_rowwise_adagrad): ONE accumulator word per row, in
+// SlotCol::s0 as fp32 [rows, 1] (no pitch: word r belongs to row r).  kRowwise: slot_task reads that word
+// once per row, sums g * g over the row's lane group (the clip prologue's order) and hands the rule the
+// row's sum; the rule returns the new accumulator and the row's one rate.
+struct RowwiseParams {
+  float lr, eps;
+};
+struct RowwiseAdagradRule {
+  using Params = RowwiseParams;
+  struct State {};
+  static constexpr int kSlots = 0;   // (no slot of the table's shape)
+  static constexpr bool kStep = true;
+  static constexpr bool kRowwise = true;
+  float lr, eps;
+
+  __device__ static void setup(const RowwiseParams&) {}
+  __device__ static State state() { return State{}; }
+  __device__ RowwiseAdagradRule(const RowwiseParams& p, State) : lr(p.lr), eps(p.eps) {}
+  // a: the row's accumulator, s: the sum of g * g over the row, dim as a float; *rate: lr / (sqrt(a') + eps)
+  __device__ float row(float a, float s, float fdim, float* rate) const {
+    const float na = a + s / fdim;
+    *rate = lr / (sqrtf(na) + eps);
+    return na;
+  }
 };
 
 // The clip prologue (include/hbk.h, hbk_group_lookup_fwd_clipped): the sums of a row over its lane
@@ -251,6 +289,8 @@ __device__ inline V clip_grad(V x, V g, float c, int lpr_log2) {
 // Rule::kSlots slots are read and written; Rule::kStep false: nothing is stepped.  CLIP: the rows of a
 // column with max_norm > 0 step with clip_grad's g', which is written back over the gradient row in
 // every form (the IndexedSlices of a clipped column are the gradient its rows were stepped with).
+// Rule::kRowwise: c.s0 is one word per row -- every lane of the row's group loads that same word with the
+// task's other loads, the group sums g * g (after the clip: g' * g'), lane 0 of the group stores the word.
 template <typename V, int W, typename Rule, bool CLIP = false>
 __device__ inline void slot_task(const SlotCol& c, int64_t base, int64_t n, const Rule& rule) {
   const int lane = lane_id();
@@ -273,6 +313,11 @@ __device__ inline void slot_task(const SlotCol& c, int64_t base, int64_t n, cons
 #pragma unroll
     for (int k = 0; k < kSlotItems; ++k) w[k] = s0[k] = s1[k] = g[k] = zero_v<V>();
   }
+  float acc[Rule::kRowwise ? kSlotItems : 1], sq[Rule::kRowwise ? kSlotItems : 1];
+  if constexpr (Rule::kRowwise) {
+#pragma unroll
+    for (int k = 0; k < kSlotItems; ++k) acc[k] = 0.0f;
+  }
 #pragma unroll
   for (int k = 0; k < kSlotItems; ++k) {
     if (!on[k]) continue;
@@ -281,6 +326,7 @@ __device__ inline void slot_task(const SlotCol& c, int64_t base, int64_t n, cons
     if constexpr (Rule::kStep || CLIP) w[k] = *reinterpret_cast<const V*>(c.w + off);
     if constexpr (Rule::kSlots >= 1) s0[k] = *reinterpret_cast<const V*>(c.s0 + off);
     if constexpr (Rule::kSlots >= 2) s1[k] = *reinterpret_cast<const V*>(c.s1 + off);
+    if constexpr (Rule::kRowwise) acc[k] = c.s0[r[k]];
     g[k] = __builtin_nontemporal_load(reinterpret_cast<const V*>(c.grows + u * c.dim + sub * W));
   }
   if constexpr (CLIP) {
@@ -288,6 +334,11 @@ __device__ inline void slot_task(const SlotCol& c, int64_t base, int64_t n, cons
 #pragma unroll
       for (int k = 0; k < kSlotItems; ++k) g[k] = clip_grad<V>(w[k], g[k], c.max_norm, lpr);
     }
+  }
+  if constexpr (Rule::kRowwise) {
+    // every lane of the wave takes part (lanes without a row or past dim pass +0.0f)
+#pragma unroll
+    for (int k = 0; k < kSlotItems; ++k) sq[k] = group_sum(chunk_sum(g[k] * g[k]), lpr);
   }
 #pragma unroll
   for (int k = 0; k < kSlotItems; ++k) {
@@ -298,7 +349,13 @@ __device__ inline void slot_task(const SlotCol& c, int64_t base, int64_t n, cons
         *reinterpret_cast<V*>(const_cast<float*>(c.grows) + u * c.dim + sub * W) = g[k];
       }
     }
-    if constexpr (Rule::kStep) {
+    if constexpr (Rule::kRowwise) {
+      float rate;
+      const float na = rule.row(acc[k], sq[k], (float)c.dim, &rate);
+      if (sub == 0) c.s0[r[k]] = na;
+      const int64_t off = r[k] * c.pitch + sub * W;
+      *reinterpret_cast<V*>(c.w + off) = w[k] - rate * g[k];
+    } else if constexpr (Rule::kStep) {
       const int64_t off = r[k] * c.pitch + sub * W;
       const Stepped<V> o = rule(w[k], s0[k], s1[k], g[k]);
       if constexpr (Rule::kSlots >= 1) *reinterpret_cast<V*>(c.s0 + off) = o.s0;
@@ -396,6 +453,14 @@ __global__ __launch_bounds__(kSlotBlock) void sparse_emit_clip_kernel(SlotArgs<L
   slot_apply_body<EmitRule, true>(a);
 }
 
+__global__ __launch_bounds__(kSlotBlock) void sparse_rowwise_adagrad_apply_kernel(SlotArgs<RowwiseParams> a) {
+  slot_apply_body<RowwiseAdagradRule>(a);
+}
+
+__global__ __launch_bounds__(kSlotBlock) void sparse_rowwise_adagrad_clip_kernel(SlotArgs<RowwiseParams> a) {
+  slot_apply_body<RowwiseAdagradRule, true>(a);
+}
+
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // the step-only buffers of column c (unique_rows, grad_rows) behind the emit-form workspace
@@ -416,6 +481,48 @@ std::vector<hbk_lookup_grad_column_t> emit_form(int32_t n_cols, const hbk_lookup
     h.accum = nullptr;
   }
   return e;
+}
+
+// every host check of a one-slot call's columns (nm.s1 == NULL: row-wise Adagrad's accumulators, fp32
+// [rows, 1] in s0), before any device work; the apply's row shapes.  The accumulator is one 4-byte word
+// per row: it does not enter the alignment bits of the row shape (table, grad_rows and the pitch do).
+int check_row_slot_columns(const SlotNames& nm, int32_t n_cols, const hbk_lookup_grad_column_t* cols,
+                           float* const* s0, std::vector<RowShape>* shapes) {
+  const char* who = nm.who;
+  HBK_REQUIRE(n_cols == 0 || cols != nullptr, "%s: cols is NULL", who);
+  HBK_REQUIRE(n_cols == 0 || s0 != nullptr, "%s: the %s array is NULL", who, nm.s0);
+  std::vector<uintptr_t> seen;
+  seen.reserve((size_t)n_cols * 2);
+  shapes->assign((size_t)n_cols, RowShape{});
+  for (int32_t c = 0; c < n_cols; ++c) {
+    const hbk_lookup_grad_column_t& h = cols[c];
+    HBK_REQUIRE(s0[c] != nullptr, "%s: column %d: %s is NULL", who, c, nm.s0);
+    HBK_REQUIRE(((uintptr_t)s0[c] & 3) == 0, "%s: column %d: %s must be 4-byte aligned", who, c, nm.s0);
+    HBK_REQUIRE(s0[c] != h.table, "%s: column %d: %s is the table", who, c, nm.s0);
+    HBK_REQUIRE(h.accum == nullptr, "%s: column %d: accum must be NULL (%s's slot is the %s array)", who, c,
+                nm.opt, nm.s0);
+    HBK_REQUIRE(h.n_ids == 0 || h.table != nullptr, "%s: column %d: table is NULL", who, c);
+    HBK_REQUIRE(h.n_ids < (1ll << 30), "%s: column %d: more than 2^30-1 ids", who, c);
+    HBK_REQUIRE(h.dim >= 1, "%s: column %d: dim must be >= 1", who, c);
+    HBK_REQUIRE(h.table_pitch == 0 || h.table_pitch >= h.dim,
+                "%s: column %d: table_pitch %d is smaller than dim %d", who, c, h.table_pitch, h.dim);
+    HBK_REQUIRE(h.n_ids == 0 || (h.unique_rows != nullptr) == (h.grad_rows != nullptr),
+                "%s: column %d: unique_rows and grad_rows go together", who, c);
+    const int32_t pitch = h.table_pitch > 0 ? h.table_pitch : h.dim;
+    HBK_REQUIRE(h.n_ids <= 0 ||
+                    make_rowshape(h.dim,
+                                  (uintptr_t)h.table | (uintptr_t)h.grad_rows | ((uintptr_t)(uint32_t)pitch * 4),
+                                  &(*shapes)[(size_t)c]),
+                "%s: column %d: dim %d needs more than 64 lanes per row (at most 256 with 16-byte "
+                "aligned table / grad_rows / pitch, 64 otherwise)", who, c, h.dim);
+    if (h.table != nullptr) seen.push_back((uintptr_t)h.table);
+    seen.push_back((uintptr_t)s0[c]);
+  }
+  std::sort(seen.begin(), seen.end());
+  HBK_REQUIRE(std::adjacent_find(seen.begin(), seen.end()) == seen.end(),
+              "%s: two columns name the same table or %s (%s is not additive: a row stepped twice "
+              "in one call would race)", who, nm.s0, nm.opt);
+  return HBK_OK;
 }
 
 // every host check of a two-slot call's columns, before any device work; the apply's row shapes
@@ -525,7 +632,7 @@ int fill_slot_cols(const std::vector<hbk_lookup_grad_column_t>& e, const std::ve
     SlotCol& d = out[k];
     d.w = h.table;
     d.s0 = s0[c];
-    d.s1 = s1[c];
+    d.s1 = s1 != nullptr ? s1[c] : nullptr;   // (a one-slot call has no second array)
     d.urows = h.unique_rows;
     d.grows = h.grad_rows;
     d.nu = h.n_unique;
@@ -547,7 +654,7 @@ int fill_slot_cols(const std::vector<hbk_lookup_grad_column_t>& e, const std::ve
   return k;
 }
 
-// one two-slot call: every host check (n_cols, check() for the hyperparameters, the columns), the
+// one slot call (two slots, or nm.s1 == s1 == NULL: one): every host check (n_cols, check() for the hyperparameters, the columns), the
 // emit-form reduce, then one apply launch per kSlotMaxCols columns -- launch(args, blocks, stream)
 // sets args.p and launches the rule's kernel.  run_empty: go on with n_cols = 0 (what follows the
 // apply still has to run)
@@ -561,7 +668,9 @@ int slot_apply(const SlotNames& nm, Check check, bool run_empty, int32_t n_cols,
   int rc = check();
   if (rc != HBK_OK) return rc;
   std::vector<RowShape> shapes;
-  if ((rc = check_slot_columns(nm, n_cols, cols, s0, s1, &shapes)) != HBK_OK) return rc;
+  rc = nm.s1 != nullptr ? check_slot_columns(nm, n_cols, cols, s0, s1, &shapes)
+                        : check_row_slot_columns(nm, n_cols, cols, s0, &shapes);
+  if (rc != HBK_OK) return rc;
   if (n_cols == 0 && !run_empty) return HBK_OK;
   std::vector<hbk_lookup_grad_column_t> e;
   rc = run_emit_form(nm.who, n_cols, cols, workspace, workspace_bytes, stream_, &e);
@@ -615,6 +724,17 @@ int ftrl_check(const hbk_ftrl_t* ftrl, float lr, const char* who) {
               "%s: l2_shrinkage must be finite and >= 0, got %g", who, (double)ftrl->l2_shrinkage);
   HBK_REQUIRE(ftrl->lr_power <= 0.0f && ftrl->lr_power >= -kMax,
               "%s: lr_power must be finite and <= 0, got %g", who, (double)ftrl->lr_power);
+  return HBK_OK;
+}
+
+// the hyperparameters of a row-wise Adagrad call (host only; shared with the sharded backward)
+int rowwise_adagrad_check(const hbk_rowwise_adagrad_t* opt, float lr, const char* who) {
+  constexpr float kMax = 3.402823466e38f;
+  HBK_REQUIRE(opt != nullptr, "%s: rowwise_adagrad is NULL", who);
+  HBK_REQUIRE(lr != 0.0f && lr >= -kMax && lr <= kMax, "%s: lr must be finite and != 0, got %g", who,
+              (double)lr);
+  HBK_REQUIRE(opt->epsilon >= 0.0f && opt->epsilon <= kMax, "%s: epsilon must be finite and >= 0, got %g",
+              who, (double)opt->epsilon);
   return HBK_OK;
 }
 }  // namespace hbk
@@ -678,6 +798,26 @@ int ftrl_call(int32_t n_cols, const hbk_lookup_grad_column_t* cols, const float*
                              a);
         } else {
           hipLaunchKernelGGL(sparse_ftrl_apply_kernel<false>, dim3(blocks), dim3(kSlotBlock), 0, stream,
+                             a);
+        }
+      },
+      workspace, workspace_bytes, stream_, clip);
+}
+
+int rowwise_adagrad_call(int32_t n_cols, const hbk_lookup_grad_column_t* cols, const float* clip,
+                         float* const* accum, const hbk_rowwise_adagrad_t* opt, float lr, void* workspace,
+                         size_t workspace_bytes, hbk_stream_t stream_) {
+  static const SlotNames kNames = {"group_lookup_bwd_rowwise_adagrad", "row-wise Adagrad", "accum", nullptr};
+  return slot_apply<RowwiseParams>(
+      kNames, [&] { return rowwise_adagrad_check(opt, lr, kNames.who); }, false, n_cols, cols, accum,
+      nullptr,
+      [&](SlotArgs<RowwiseParams>& a, unsigned blocks, hipStream_t stream) {
+        a.p = RowwiseParams{lr, opt->epsilon};
+        if (clip != nullptr) {
+          hipLaunchKernelGGL(sparse_rowwise_adagrad_clip_kernel, dim3(blocks), dim3(kSlotBlock), 0, stream,
+                             a);
+        } else {
+          hipLaunchKernelGGL(sparse_rowwise_adagrad_apply_kernel, dim3(blocks), dim3(kSlotBlock), 0, stream,
                              a);
         }
       },
@@ -878,4 +1018,37 @@ extern "C" int hbk_group_lookup_bwd_ftrl(int32_t n_cols, const hbk_lookup_grad_c
                                          size_t workspace_bytes, hbk_stream_t stream_) {
   return hbk::ftrl_call(n_cols, cols, nullptr, accum, linear, ftrl, lr, workspace, workspace_bytes,
                         stream_);
+}
+
+extern "C" size_t hbk_group_lookup_bwd_rowwise_adagrad_workspace_bytes(int32_t n_cols,
+                                                                       const hbk_lookup_grad_column_t* cols) {
+  return hbk::slot_workspace_bytes(n_cols, cols);
+}
+
+extern "C" int hbk_group_lookup_bwd_rowwise_adagrad(int32_t n_cols, const hbk_lookup_grad_column_t* cols,
+                                                    float* const* accum, const hbk_rowwise_adagrad_t* opt,
+                                                    float lr, void* workspace, size_t workspace_bytes,
+                                                    hbk_stream_t stream_) {
+  return hbk::rowwise_adagrad_call(n_cols, cols, nullptr, accum, opt, lr, workspace, workspace_bytes,
+                                   stream_);
+}
+
+extern "C" size_t hbk_group_lookup_bwd_rowwise_adagrad_clipped_workspace_bytes(
+    int32_t n_cols, const hbk_lookup_grad_column_t* cols, const float* max_norms) {
+  (void)max_norms;
+  return hbk::slot_workspace_bytes(n_cols, cols);
+}
+
+extern "C" int hbk_group_lookup_bwd_rowwise_adagrad_clipped(int32_t n_cols,
+                                                            const hbk_lookup_grad_column_t* cols,
+                                                            const float* max_norms, float* const* accum,
+                                                            const hbk_rowwise_adagrad_t* opt, float lr,
+                                                            void* workspace, size_t workspace_bytes,
+                                                            hbk_stream_t stream_) {
+  using namespace hbk;
+  bool any = false;
+  const int rc = check_max_norms("group_lookup_bwd_rowwise_adagrad_clipped", n_cols, max_norms, &any);
+  if (rc != HBK_OK) return rc;
+  return rowwise_adagrad_call(n_cols, cols, any ? max_norms : nullptr, accum, opt, lr, workspace,
+                              workspace_bytes, stream_);
 }

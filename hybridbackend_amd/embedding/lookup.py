@@ -391,7 +391,7 @@ class GroupLookupGrad:
   """
 
   def __init__(self, lookup, accums=None, interleaved=None, workspace_of=None, deterministic=False,
-               moments=None, adam=None, ftrl_slots=None, ftrl=None):
+               moments=None, adam=None, ftrl_slots=None, ftrl=None, row_accums=None, rowwise_adagrad=None):
     """deterministic: every row's gradient terms are summed in id order (``HBK_GRAD_DETERMINISTIC`` on
     every column): IndexedSlices and stepped tables have the same bits on every run, equal to the
     sequential fp32 sum -- TF's CPU ``UnsortedSegmentSum`` -- and the rows leave ascending.  What the
@@ -421,6 +421,11 @@ class GroupLookupGrad:
     filled with ``initial_accumulator_value``, linear zeros: :meth:`Ftrl.slots_like`), needed for
     ``optimizer='ftrl'``; ftrl: the :class:`Ftrl` hyperparameters (TF's defaults when omitted).
 
+    row_accums: per column the row-wise Adagrad accumulator, ONE word per row (fp32 ``[rows, 1]``, filled
+    with ``initial_accumulator_value``: :meth:`RowwiseAdagrad.slots_like`), needed for
+    ``optimizer='rowwise_adagrad'``; rowwise_adagrad: the :class:`RowwiseAdagrad` hyperparameters (the
+    defaults when omitted).
+
     A lookup with ``max_norms`` is differentiated through its clip: every optimizer steps with the
     clipped gradient g' of each distinct row, taken at the row as it was before the step, and the
     returned gradient rows of a clipped column are g' in every form (with or without a step).  A
@@ -428,16 +433,10 @@ class GroupLookupGrad:
     self._lib = _lib.lib()
     self.lookup = lookup
     n = len(lookup)
-    self.moments, self.adam = _opt.bind_slots(_opt.LazyAdam, moments, adam, lookup.tables,
-                                              'GroupLookupGrad')
-    self.ftrl_slots, self.ftrl = _opt.bind_slots(_opt.Ftrl, ftrl_slots, ftrl, lookup.tables,
-                                                 'GroupLookupGrad')
-    # the pointer arrays of the slot pairs, by optimizer name
-    self._slot_ptrs = {}
-    for opt, pairs in ((self.adam, self.moments), (self.ftrl, self.ftrl_slots)):
-      if pairs is not None:
-        self._slot_ptrs[opt.name] = (_lib.ptr_array([a.data_ptr() for a, _ in pairs]),
-                                     _lib.ptr_array([b.data_ptr() for _, b in pairs]))
+    _opt.bind_all(self, dict(moments=moments, adam=adam, ftrl_slots=ftrl_slots, ftrl=ftrl, row_accums=row_accums,
+                             rowwise_adagrad=rowwise_adagrad), lookup.tables, 'GroupLookupGrad')
+    # the pointer arrays of the slots (one array per slot), by optimizer name
+    self._slot_ptrs = {opt.name: opt.ptr_arrays(slots) for opt, slots in _opt.bound(self)}
     self.accums = list(accums) if accums is not None else None
     self.interleaved = list(interleaved) if interleaved is not None else None
     if self.interleaved is not None and self.accums is None:
@@ -556,7 +555,8 @@ class GroupLookupGrad:
     exactly those without it.  ``optimizer='adam'`` (with ``apply_lr``
     and ``moments``): the Lazy Adam step (:class:`LazyAdam`); ``finish=False`` leaves the beta powers
     for a later call of the same optimizer step to advance.  ``optimizer='ftrl'`` (with ``apply_lr``
-    and ``ftrl_slots``): the FTRL-Proximal step (:class:`Ftrl`)."""
+    and ``ftrl_slots``): the FTRL-Proximal step (:class:`Ftrl`).  ``optimizer='rowwise_adagrad'`` (with
+    ``apply_lr`` and ``row_accums``): the row-wise Adagrad step (:class:`RowwiseAdagrad`)."""
     two_slot = _opt.two_slot_class(optimizer, self, self._NEEDS)
     if not emit and apply_lr == 0.0:
       raise _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT, 'emit=False needs apply_lr != 0')
@@ -693,7 +693,7 @@ class GroupLookupGrad:
       cols[c].accum = None
     return cols
 
-  _NEEDS = 'GroupLookupGrad(lookup, {kw}=[({s0}, {s1}), ...])'
+  _NEEDS = 'GroupLookupGrad(lookup, {slots})'
 
   def _weight_grads(self, n, dev):
     """The weight gradients of the bound step into the bound outputs (self._wg): one foreign call."""
@@ -703,8 +703,7 @@ class GroupLookupGrad:
   def _step(self, n, optimizer, two_slot, apply_lr, finish, ws, dev):
     clip = self.lookup.max_norms_c
     if two_slot is not None and apply_lr != 0.0:
-      s0, s1 = self._slot_ptrs[two_slot.name]
-      getattr(self, two_slot.name).group_step(n, self._slot_cd, s0, s1, apply_lr, ws,
+      getattr(self, two_slot.name).group_step(n, self._slot_cd, self._slot_ptrs[two_slot.name], apply_lr, ws,
                                               _lib.current_stream(dev), finish, max_norms=clip)
       return
     apply = _lib.APPLY_ADAGRAD if optimizer == 'adagrad' else _lib.APPLY_SGD

@@ -1,9 +1,11 @@
-"""The two-slot sparse optimizers: Lazy Adam (``tf.contrib.opt.LazyAdamOptimizer``, TF 1.15) -- the
-hyperparameters and the device-side beta powers -- and FTRL-Proximal (``tf.train.FtrlOptimizer``,
-TF 1.15) -- the hyperparameters only.  Each class also carries what ``GroupLookupGrad``,
+"""The slot optimizers that step after the emit-form reduce: Lazy Adam (``tf.contrib.opt.LazyAdamOptimizer``,
+TF 1.15) -- the hyperparameters and the device-side beta powers --, FTRL-Proximal
+(``tf.train.FtrlOptimizer``, TF 1.15) -- the hyperparameters only -- and row-wise Adagrad (one
+accumulator per row).  Each class also carries what ``GroupLookupGrad``,
 ``ShardedGroupLookup`` and ``DenseFeatures`` need to know of it: its ``optimizer=`` name, the keyword
-of its slot pairs, fresh slots, its TF checkpoint names and its C entry points.  ``TWO_SLOT`` lists
-them; adding one here is all those drivers need."""
+of its slots (pairs of table-shaped tensors, or one ``[rows, 1]`` tensor per table), fresh slots, its
+checkpoint names and its C entry points.  ``TWO_SLOT`` lists them (one or two slots each); adding one
+here is all those drivers need."""
 import math
 import ctypes as C
 
@@ -13,12 +15,36 @@ from hybridbackend_amd import _lib
 
 
 class _TwoSlot:
-  """What the drivers use of a two-slot optimizer.  A subclass sets ``name`` (``optimizer=``, and the
-  drivers' attribute holding the object), ``slot_kw`` (the drivers' keyword and attribute of the slot
-  pairs), ``slot_names``, ``tf_suffixes`` (checkpoint names of the two slots), and implements
+  """What the drivers use of a slot optimizer.  A subclass sets ``name`` (``optimizer=``, and the
+  drivers' attribute holding the object), ``slot_kw`` (the drivers' keyword and attribute of the
+  slots), ``slot_names`` (two names: every table's entry is a pair of tensors; one name: it is the one
+  tensor itself), ``tf_suffixes`` (checkpoint names of the slots), and implements
   ``params(finish)`` (the C parameter struct), ``slots_like(table)``, ``_c(lib)`` (its C entry
   points: group step, workspace query, sharded slot registration, sharded step) and ``_c_clipped(lib)``
-  (the max_norm forms of the group step and its workspace query)."""
+  (the max_norm forms of the group step and its workspace query).  ``slot_shape(table)``: the shape of
+  every slot of ``table`` (the table's own unless overridden)."""
+
+  @staticmethod
+  def slot_shape(table):
+    return tuple(table.shape)
+
+  @classmethod
+  def slot_tensors(cls, entry):
+    """One table's entry of the slot list as a tuple of tensors, in the order of ``slot_names``."""
+    return (entry,) if len(cls.slot_names) == 1 else tuple(entry)
+
+  @classmethod
+  def ptr_arrays(cls, slots):
+    """The C pointer arrays of a slot list: one per slot name, each with one pointer per table."""
+    return tuple(_lib.ptr_array([cls.slot_tensors(e)[k].data_ptr() for e in slots])
+                 for k in range(len(cls.slot_names)))
+
+  @classmethod
+  def needs_text(cls):
+    """``kw=[...]`` as the refusals spell it."""
+    if len(cls.slot_names) == 1:
+      return f'{cls.slot_kw}=[{cls.slot_names[0]}, ...]'
+    return f'{cls.slot_kw}=[({cls.slot_names[0]}, {cls.slot_names[1]}), ...]'
 
   def tf_variables(self):
     """Checkpoint variables besides the slots: ``{name: tensor}``."""
@@ -30,19 +56,19 @@ class _TwoSlot:
       return cls._c_clipped(_lib.lib())[1](n, cols, max_norms)
     return cls._c(_lib.lib())[1](n, cols)
 
-  def group_step(self, n, cols, s0_ptrs, s1_ptrs, lr, ws, stream, finish=True, max_norms=None):
+  def group_step(self, n, cols, slot_ptrs, lr, ws, stream, finish=True, max_norms=None):
     """The step of ``GroupLookupGrad``: the emit-form reduce and the apply on ``n`` descriptors;
-    ``max_norms`` (a ctypes float array, or None): the clipped form."""
+    ``slot_ptrs``: :meth:`ptr_arrays` of the slots; ``max_norms`` (a ctypes float array, or None): the
+    clipped form."""
     lib = _lib.lib()
     head = (n, cols) if max_norms is None else (n, cols, max_norms)
     fn = self._c(lib)[0] if max_norms is None else self._c_clipped(lib)[0]
-    _lib.check(fn(*head, s0_ptrs, s1_ptrs, C.byref(self.params(finish)), C.c_float(lr),
+    _lib.check(fn(*head, *slot_ptrs, C.byref(self.params(finish)), C.c_float(lr),
                   C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()), stream))
 
-  def set_sharded_slots(self, plan, pairs):
+  def set_sharded_slots(self, plan, slots):
     """Every column's slot shards, registered with a sharded plan."""
-    _lib.check(self._c(_lib.lib())[2](plan, _lib.ptr_array([a.data_ptr() for a, _ in pairs]),
-                                      _lib.ptr_array([b.data_ptr() for _, b in pairs])))
+    _lib.check(self._c(_lib.lib())[2](plan, *self.ptr_arrays(slots)))
 
   def sharded_step(self, plan, grads, strides, lr, unique_rows, grad_rows, n_unique, stream,
                    finish=True):
@@ -178,16 +204,73 @@ class Ftrl(_TwoSlot):
     return (lib.hbk_group_lookup_bwd_ftrl_clipped, lib.hbk_group_lookup_bwd_ftrl_clipped_workspace_bytes)
 
 
-# the two-slot optimizers by their optimizer= name; 'sgd' and 'adagrad' are fused into the reduce
-TWO_SLOT = {c.name: c for c in (LazyAdam, Ftrl)}
+class RowwiseAdagrad(_TwoSlot):
+  """Row-wise Adagrad, the step of ``GroupLookupGrad`` / ``ShardedGroupLookup`` / ``DenseFeatures`` with
+  ``optimizer='rowwise_adagrad'``: ONE fp32 accumulator per row.  For every distinct row r of a step, with
+  its deduplicated gradient g (after a ``max_norm`` clip: g'), in fp32::
+
+      s    = sum_k g[k] * g[k]
+      a[r] = a[r] + s / dim
+      w[r] = w[r] - (lr / (sqrt(a[r]) + epsilon)) * g
+
+  (``include/hbk.h``, ``hbk_group_lookup_bwd_rowwise_adagrad``, fixes the rounding and the order of s).
+  Rows that do not occur in the step are not touched.  The slot is ``row_accums``: per table one fp32
+  ``[rows, 1]`` tensor filled with ``initial_accumulator_value`` -- 4 bytes of optimizer state per row
+  instead of Adagrad's ``4 * dim``.  There is no device state: one object may serve any number of calls."""
+  name, slot_kw, slot_names = 'rowwise_adagrad', 'row_accums', ('accum',)
+  tf_suffixes = ('/RowwiseAdagrad',)
+
+  def __init__(self, epsilon=1e-8, initial_accumulator_value=0.0):
+    for name, x in (('epsilon', epsilon), ('initial_accumulator_value', initial_accumulator_value)):
+      if not (math.isfinite(float(x)) and float(x) >= 0.0):
+        raise _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT, f'{name} must be finite and >= 0, got {x}')
+    if float(epsilon) == 0.0 and float(initial_accumulator_value) == 0.0:
+      raise _lib.InvalidArgumentError(
+        _lib.INVALID_ARGUMENT, 'epsilon and initial_accumulator_value must not both be 0 (a row whose gradient '
+        'is all zero would compute 0 / 0)')
+    self.epsilon = float(epsilon)
+    self.initial_accumulator_value = float(initial_accumulator_value)
+    self._params = _lib.RowwiseAdagradParams(C.c_float(self.epsilon))
+
+  def params(self, finish=True):   # pylint: disable=unused-argument
+    """The ``hbk_rowwise_adagrad_t`` of a call (kept alive by this object; ``finish`` is Adam's)."""
+    return self._params
+
+  @classmethod
+  def default(cls, device):   # pylint: disable=unused-argument
+    return cls()
+
+  @staticmethod
+  def slot_shape(table):
+    return (int(table.shape[0]), 1)
+
+  def slots_like(self, table):
+    """A new ``[rows, 1]`` accumulator for ``table``, filled with ``initial_accumulator_value``."""
+    return torch.full((int(table.shape[0]), 1), self.initial_accumulator_value, dtype=torch.float32,
+                      device=table.device)
+
+  @staticmethod
+  def _c(lib):
+    return (lib.hbk_group_lookup_bwd_rowwise_adagrad, lib.hbk_group_lookup_bwd_rowwise_adagrad_workspace_bytes,
+            lib.hbk_sharded_set_rowwise_adagrad_slots, lib.hbk_sharded_lookup_bwd_rowwise_adagrad)
+
+  @staticmethod
+  def _c_clipped(lib):
+    return (lib.hbk_group_lookup_bwd_rowwise_adagrad_clipped,
+            lib.hbk_group_lookup_bwd_rowwise_adagrad_clipped_workspace_bytes)
+
+
+# the slot optimizers (one or two slots per table) by their optimizer= name; 'sgd' and 'adagrad' are fused
+# into the reduce
+TWO_SLOT = {c.name: c for c in (LazyAdam, Ftrl, RowwiseAdagrad)}
 _NAMES = ['sgd', 'adagrad'] + list(TWO_SLOT)
 
 
 def two_slot_class(optimizer, owner=None, needs=''):
-  """The two-slot class ``optimizer`` names, or None for a fused step ('sgd', 'adagrad').  Refuses
-  other names and -- with an ``owner`` -- a two-slot optimizer whose slot pairs the owner does not
-  hold; ``needs``: how to build one that does (formatted with the class's ``name``, ``kw``, ``s0``
-  and ``s1``)."""
+  """The slot-optimizer class ``optimizer`` names, or None for a fused step ('sgd', 'adagrad').  Refuses
+  other names and -- with an ``owner`` -- a slot optimizer whose slots the owner does not hold;
+  ``needs``: how to build one that does (formatted with the class's ``name``, ``kw``, ``s0``, ``s1``
+  and ``slots``, the whole ``kw=[...]`` argument as :meth:`_TwoSlot.needs_text` spells it)."""
   if optimizer in ('sgd', 'adagrad'):
     return None
   cls = TWO_SLOT.get(optimizer)
@@ -198,15 +281,41 @@ def two_slot_class(optimizer, owner=None, needs=''):
   if owner is not None and getattr(owner, cls.slot_kw, None) is None:
     raise _lib.InvalidArgumentError(
       _lib.INVALID_ARGUMENT, f"optimizer='{cls.name}' needs " + needs.format(
-        name=cls.name, kw=cls.slot_kw, s0=cls.slot_names[0], s1=cls.slot_names[1]))
+        name=cls.name, kw=cls.slot_kw, s0=cls.slot_names[0], s1=cls.slot_names[-1], slots=cls.needs_text()))
   return cls
 
 
 def bind_slots(cls, pairs, opt, tables, what):
-  """A driver's ``(slot pairs, optimizer)`` of one two-slot class from its keyword arguments: the
-  pairs checked against ``tables`` (None when not given) and, with pairs, an optimizer with TF's
-  defaults when ``opt`` is None."""
+  """A driver's ``(slots, optimizer)`` of one slot-optimizer class from its keyword arguments: the
+  slots (pairs, or one tensor per table) checked against ``tables`` (None when not given) and, with
+  slots, an optimizer with the class's defaults when ``opt`` is None."""
   if pairs is None:
     return None, opt
-  pairs = _lib.require_slot_pairs(pairs, tables, what, cls.slot_kw, cls.slot_names)
+  pairs = _lib.require_slot_pairs(pairs, tables, what, cls.slot_kw, cls.slot_names, cls.slot_shape)
   return pairs, opt if opt is not None else cls.default(tables[0].device if tables else None)
+
+
+def bind_all(owner, given, tables, what):
+  """``bind_slots`` for every class of ``TWO_SLOT``: ``given`` maps the drivers' keywords (every ``slot_kw``
+  and ``name``; absent = None) to what the caller passed, and the results become ``owner``'s attributes of
+  the same names."""
+  for cls in TWO_SLOT.values():
+    slots, opt = bind_slots(cls, given.get(cls.slot_kw), given.get(cls.name), tables, what)
+    setattr(owner, cls.slot_kw, slots)
+    setattr(owner, cls.name, opt)
+
+
+def bound(owner):
+  """``(optimizer object, slot list)`` of every class whose slots ``owner`` holds."""
+  return [(getattr(owner, cls.name), getattr(owner, cls.slot_kw)) for cls in TWO_SLOT.values()
+          if getattr(owner, cls.slot_kw, None) is not None]
+
+
+def slot_kwargs(owner, idx=None):
+  """The drivers' keyword arguments of every class from ``owner``'s attributes (tables ``idx``, or all)."""
+  kw = {}
+  for cls in TWO_SLOT.values():
+    slots = getattr(owner, cls.slot_kw, None)
+    kw[cls.slot_kw] = slots if slots is None or idx is None else [slots[c] for c in idx]
+    kw[cls.name] = getattr(owner, cls.name, None)
+  return kw

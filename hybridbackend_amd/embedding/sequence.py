@@ -233,18 +233,17 @@ class SequenceLookup:
 class SequenceLookupGrad:
   """Backward of :class:`SequenceLookup`: a :class:`GroupLookupGrad` over the same tables, handed the
   last forward's grids as one-id-per-position columns and the ``[B, T, dim]`` gradients viewed
-  ``[B * T, dim]`` in place.  ``accums`` / ``moments`` / ``adam`` / ``ftrl_slots`` / ``ftrl`` are
-  GroupLookupGrad's.  Truncated ids and zero padding are not in the grid: they reach no gradient row and
-  no optimizer slot; with ``pad_ids`` the pad row collects the gradient of every padding position."""
+  ``[B * T, dim]`` in place.  ``accums`` / ``moments`` / ``adam`` / ``ftrl_slots`` / ``ftrl`` /
+  ``row_accums`` / ``rowwise_adagrad`` are GroupLookupGrad's.  Truncated ids and zero padding are not in
+  the grid: they reach no gradient row and no optimizer slot; with ``pad_ids`` the pad row collects the gradient of every padding position."""
 
-  def __init__(self, lookup, accums=None, moments=None, adam=None, ftrl_slots=None, ftrl=None):
+  def __init__(self, lookup, accums=None, moments=None, adam=None, ftrl_slots=None, ftrl=None, row_accums=None,
+               rowwise_adagrad=None):
     self.lookup = lookup
     self.inner = lookup.plain_lookup()
     # ONE optimizer object behind both drivers (the beta powers advance once per step)
-    self.moments, self.adam = _opt.bind_slots(_opt.LazyAdam, moments, adam, lookup.tables,
-                                              'SequenceLookupGrad')
-    self.ftrl_slots, self.ftrl = _opt.bind_slots(_opt.Ftrl, ftrl_slots, ftrl, lookup.tables,
-                                                 'SequenceLookupGrad')
+    _opt.bind_all(self, dict(moments=moments, adam=adam, ftrl_slots=ftrl_slots, ftrl=ftrl, row_accums=row_accums,
+                             rowwise_adagrad=rowwise_adagrad), lookup.tables, 'SequenceLookupGrad')
     self.accums = list(accums) if accums is not None else None
     self._drivers = {}
 
@@ -254,8 +253,7 @@ class SequenceLookupGrad:
     if d is None:
       other = next(iter(self._drivers.values()), None)
       d = GroupLookupGrad(self.inner, accums=self.accums, workspace_of=other,
-                          deterministic=bool(deterministic), moments=self.moments, adam=self.adam,
-                          ftrl_slots=self.ftrl_slots, ftrl=self.ftrl)
+                          deterministic=bool(deterministic), **_opt.slot_kwargs(self))
       self._drivers[bool(deterministic)] = d
     return d
 

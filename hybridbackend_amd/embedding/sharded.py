@@ -87,7 +87,8 @@ class ShardedGroupLookup:
 
   def __init__(self, shards, coll, buckets=None, combiners='sum', wire_dtype=None,
                world_size=None, accums=None, hot_rows=False, dedup=False, moments=None, adam=None,
-               ftrl_slots=None, ftrl=None, max_norms=None, weight_grads=False):
+               ftrl_slots=None, ftrl=None, max_norms=None, weight_grads=False, row_accums=None,
+               rowwise_adagrad=None):
     from hybridbackend_amd.embedding.lookup import max_norm_list
     self.shards = list(shards)
     # backward() also returns the gradient of the last forward's sp_weights (its own weight_grads
@@ -98,12 +99,11 @@ class ShardedGroupLookup:
     self.max_norms = max_norm_list(max_norms, len(self.shards))
     # Adagrad accumulators of the shards (same shapes), for backward(optimizer='adagrad')
     self.accums = list(accums) if accums is not None else None
-    # the two-slot optimizers' slots of the shards (per column a pair of the shard's shape) and the
-    # optimizers they step with, for backward(optimizer='adam') / backward(optimizer='ftrl')
-    self.moments, self.adam = _opt.bind_slots(_opt.LazyAdam, moments, adam, self.shards,
-                                              'ShardedGroupLookup')
-    self.ftrl_slots, self.ftrl = _opt.bind_slots(_opt.Ftrl, ftrl_slots, ftrl, self.shards,
-                                                 'ShardedGroupLookup')
+    # the slot optimizers' slots of the shards (per column a pair of the shard's shape, or row-wise Adagrad's
+    # one [rows_local, 1] tensor) and the optimizers they step with, for backward(optimizer='adam' / 'ftrl' /
+    # 'rowwise_adagrad')
+    _opt.bind_all(self, dict(moments=moments, adam=adam, ftrl_slots=ftrl_slots, ftrl=ftrl, row_accums=row_accums,
+                             rowwise_adagrad=rowwise_adagrad), self.shards, 'ShardedGroupLookup')
     self.coll = coll
     self.world_size = int(world_size if world_size is not None else coll.world_size)
     n = len(self.shards)
@@ -198,9 +198,8 @@ class ShardedGroupLookup:
     self._plan_created()
     if any(self.max_norms):   # (plan state: set again on every plan this object creates)
       _lib.check(self._lib.hbk_sharded_set_max_norms(self._plan_handle, (C.c_float * n)(*self.max_norms)))
-    for opt, pairs in ((self.adam, self.moments), (self.ftrl, self.ftrl_slots)):
-      if pairs is not None:
-        opt.set_sharded_slots(self._plan_handle, pairs)
+    for opt, slots in _opt.bound(self):
+      opt.set_sharded_slots(self._plan_handle, slots)
 
   def _plan_created(self):
     """Hook: plan state a subclass sets right after creation (ShardedHashGroupLookup: its tables)."""
@@ -518,7 +517,8 @@ class ShardedGroupLookup:
     ``optimizer='adam'`` (with ``apply_lr`` and ``moments``): the Lazy Adam step on the shards
     (hbk_sharded_lookup_bwd_adam); ``finish=False`` leaves the beta powers to a later call.
     ``optimizer='ftrl'`` (with ``apply_lr`` and ``ftrl_slots``): the FTRL-Proximal step on the shards
-    (hbk_sharded_lookup_bwd_ftrl).
+    (hbk_sharded_lookup_bwd_ftrl).  ``optimizer='rowwise_adagrad'`` (with ``apply_lr`` and ``row_accums``):
+    the row-wise Adagrad step on the shards (hbk_sharded_lookup_bwd_rowwise_adagrad).
     ``weight_grads`` (default: the constructor's): True, or per column None / True / a preallocated fp32
     ``[n_ids]`` tensor -- the call returns ``(slices, weight_gradients)``, the second a list with dL/dw of
     every id of the asked columns (those the last forward weighted) and None for the others.  Computed
@@ -533,7 +533,7 @@ class ShardedGroupLookup:
     wg_request = _marshal.weight_grad_request(weight_grads, kept_w, n)
     plan = self._plan()
     two_slot = _opt.two_slot_class(optimizer, self,
-                                   'ShardedGroupLookup(..., {kw}=[({s0}, {s1}), ...])')
+                                   'ShardedGroupLookup(..., {slots})')
     res = []
     shapes = getattr(self, '_last_shapes', None)
     auto = bool(self._auto_hot) and outs is None

@@ -17,11 +17,13 @@ from hybridbackend_amd.embedding.sharded import ShardedGroupLookup
 
 
 def slot_kinds(owner, accum_fill):
-  """The optimizer slots ``owner`` holds (``accums``, ``moments``, ``ftrl_slots`` with ``ftrl``) as (attribute, index
-  in a pair or None, fill value), in the ONE order every call that moves them with a hash table uses -- ``accums``;
-  ``moments`` m, v; ``ftrl_slots`` accum, linear -- and with the value a row that no key holds is set to:
+  """The optimizer slots ``owner`` holds (``accums``, ``moments``, ``ftrl_slots`` with ``ftrl``, ``row_accums``
+  with ``rowwise_adagrad``) as (attribute, index in a pair or None, fill value), in the ONE order every call that
+  moves them with a hash table uses -- ``accums``; ``moments`` m, v; ``ftrl_slots`` accum, linear; ``row_accums``
+  (``[capacity, 1]``: a companion of one word) -- and with the value a row that no key holds is set to:
   ``accum_fill`` for Adagrad's accumulator, 0 for Adam's m / v, FTRL's accum its ``initial_accumulator_value`` and
-  linear 0.  The sharded driver and the feature-column layers share it."""
+  linear 0, row-wise Adagrad's its ``initial_accumulator_value``.  The sharded driver and the feature-column
+  layers share it."""
   kinds = []
   if owner.accums is not None:
     kinds.append(('accums', None, float(accum_fill)))
@@ -29,6 +31,8 @@ def slot_kinds(owner, accum_fill):
     kinds += [('moments', 0, 0.0), ('moments', 1, 0.0)]
   if owner.ftrl_slots is not None:
     kinds += [('ftrl_slots', 0, float(owner.ftrl.initial_accumulator_value)), ('ftrl_slots', 1, 0.0)]
+  if getattr(owner, 'row_accums', None) is not None:
+    kinds.append(('row_accums', None, float(owner.rowwise_adagrad.initial_accumulator_value)))
   return kinds
 
 
@@ -47,7 +51,7 @@ class ShardedHashGroupLookup(ShardedGroupLookup):
     train: True -- ids the owner never saw are inserted (a filtered table: once admitted); False -- a pure find:
       they read as zero rows, and neither ``size()`` nor ``counts`` moves.
     accums / moments, adam / ftrl_slots, ftrl: the optimizer slots of the tables, ``[capacity, dim]`` each, as for
-      :class:`ShardedGroupLookup`.
+      :class:`ShardedGroupLookup`; row_accums, rowwise_adagrad: row-wise Adagrad's, ``[capacity, 1]`` each.
     initial_accumulator_value: what :meth:`maybe_grow` fills the rows of a grown Adagrad accumulator with that no
       key holds (FTRL's comes from ``ftrl``).
 
@@ -60,7 +64,7 @@ class ShardedHashGroupLookup(ShardedGroupLookup):
 
   def __init__(self, tables, coll, combiners='sum', wire_dtype=None, dedup=False, max_norms=None, train=True,
                accums=None, moments=None, adam=None, ftrl_slots=None, ftrl=None, hot_rows=False, world_size=None,
-               initial_accumulator_value=0.1):
+               initial_accumulator_value=0.1, row_accums=None, rowwise_adagrad=None):
     self.tables = list(tables)
     _ht.same_device(self.tables)
     self.train = bool(train)
@@ -68,7 +72,8 @@ class ShardedHashGroupLookup(ShardedGroupLookup):
     self._rows = [t.table for t in self.tables]
     super().__init__(self._rows, coll, buckets=None, combiners=combiners, wire_dtype=wire_dtype,
                      world_size=world_size, accums=accums, hot_rows=hot_rows, dedup=dedup, moments=moments, adam=adam,
-                     ftrl_slots=ftrl_slots, ftrl=ftrl, max_norms=max_norms)
+                     ftrl_slots=ftrl_slots, ftrl=ftrl, max_norms=max_norms, row_accums=row_accums,
+                     rowwise_adagrad=rowwise_adagrad)
 
   def _current(self):
     _ht.check_current(self.tables, self._rows)
@@ -107,7 +112,7 @@ class ShardedHashGroupLookup(ShardedGroupLookup):
       _lib.i64_array([int(o.shape[0]) for o in outs]), _lib.current_stream(self.device)))
     raise _lib.HbkError(_lib.INTERNAL, 'p2p_bind: a plan with hash columns was bound')
 
-  def rebind(self, accums=None, moments=None, ftrl_slots=None):
+  def rebind(self, accums=None, moments=None, ftrl_slots=None, row_accums=None):
     """After a rehash of any table (``hash_rehash``, ``HashTable.maybe_grow``): the plan is closed and the
     owner-side state built again over the tables' current tensors and the given slot tensors (the companions the
     rehash returned; None: the ones bound now, which must still have the tables' shapes).  Until then every call
@@ -120,19 +125,24 @@ class ShardedHashGroupLookup(ShardedGroupLookup):
       accums = list(accums)
       if len(accums) != len(rows) or any(tuple(a.shape) != tuple(r.shape) for a, r in zip(accums, rows)):
         raise _ht._bad('rebind: accums must be one fp32 [capacity, dim] tensor per table')   # pylint: disable=protected-access
-    moments = self.moments if moments is None else moments
-    ftrl_slots = self.ftrl_slots if ftrl_slots is None else ftrl_slots
-    what = 'ShardedHashGroupLookup.rebind'
-    new_moments, adam = _opt.bind_slots(_opt.LazyAdam, moments, self.adam, rows, what)
-    new_ftrl, ftrl = _opt.bind_slots(_opt.Ftrl, ftrl_slots, self.ftrl, rows, what)
+    given = dict(moments=moments, ftrl_slots=ftrl_slots, row_accums=row_accums)
+    for cls in _opt.TWO_SLOT.values():   # (None: the slots bound now; the optimizer objects stay)
+      if given[cls.slot_kw] is None:
+        given[cls.slot_kw] = getattr(self, cls.slot_kw)
+      given[cls.name] = getattr(self, cls.name)
+    # (checked into a scratch holder first: a refusal leaves this object's slots as they were)
+    new = type('_Bound', (), {})()
+    _opt.bind_all(new, given, rows, 'ShardedHashGroupLookup.rebind')
     self.shards, self._rows, self.accums = rows, rows, accums
-    self.moments, self.adam, self.ftrl_slots, self.ftrl = new_moments, adam, new_ftrl, ftrl
+    for cls in _opt.TWO_SLOT.values():
+      setattr(self, cls.slot_kw, getattr(new, cls.slot_kw))
+      setattr(self, cls.name, getattr(new, cls.name))
     self._call_cache = self._keep = self._auto_state = None
     self._setup()
 
   def _slot_kinds(self):
     """The bound optimizer slots as (attribute, index in a pair or None, fill value), in the order every method
-    that moves them uses: ``accums``; ``moments`` m, v; ``ftrl_slots`` accum, linear."""
+    that moves them uses: ``accums``; ``moments`` m, v; ``ftrl_slots`` accum, linear; ``row_accums``."""
     return slot_kinds(self, self.initial_accumulator_value)
 
   def _slot_tensors(self, c):
@@ -140,8 +150,8 @@ class ShardedHashGroupLookup(ShardedGroupLookup):
 
   def export_items(self, since=None):
     """:func:`hash_export` of this rank's tables in one call, the bound optimizer slots travelling as companions
-    in the order Adagrad's ``accums``; Lazy Adam's ``moments`` m, v; FTRL's ``ftrl_slots`` accum, linear (those
-    that are bound).  ``since``: None, or the step of a delta -- every table must then be expiring; with
+    in the order Adagrad's ``accums``; Lazy Adam's ``moments`` m, v; FTRL's ``ftrl_slots`` accum, linear;
+    row-wise Adagrad's ``row_accums`` (those that are bound).  ``since``: None, or the step of a delta -- every table must then be expiring; with
     :meth:`track_removals` on, the delta names the keys that left (``HashExport.removed``).  Returns one
     :class:`HashExport` per table.  Local to the rank: no exchange, and ranks need not agree."""
     self._current()
@@ -215,6 +225,6 @@ class ShardedHashGroupLookup(ShardedGroupLookup):
         else:
           new[name][c][k] = x
     if any(grown):
-      pairs = {name: [tuple(p) for p in new[name]] for name in ('moments', 'ftrl_slots') if name in new}
-      self.rebind(accums=new.get('accums'), moments=pairs.get('moments'), ftrl_slots=pairs.get('ftrl_slots'))
+      paired = {name for name, k, _ in kinds if k is not None}
+      self.rebind(**{name: [tuple(p) for p in xs] if name in paired else xs for name, xs in new.items()})
     return grown

@@ -143,7 +143,7 @@ class _TableLayer:
   W > 1), the optimizer slots, and the checkpoints."""
 
   def _init_tables(self, columns, device, coll, batch_size, init, initial_accumulator_value, optimizer,
-                   adam, ftrl, train=True):
+                   adam, ftrl, train=True, rowwise_adagrad=None):
     self.columns = list(columns)
     self.device = torch.device(device)
     self.coll = coll
@@ -174,10 +174,14 @@ class _TableLayer:
       self.accums = [torch.full_like(w, float(initial_accumulator_value)) for w in self.weights]
     if optimizer is not None:
       _opt.two_slot_class(optimizer)   # (refuses unknown names)
-    # two-slot optimizers: the optimizer named (TF's defaults) or passed, fresh slots for every table
-    # (Lazy Adam: m = v = 0; FTRL: accum = initial_accumulator_value, linear = 0)
-    self.moments = self.adam = self.ftrl_slots = self.ftrl = None
-    for cls, opt in ((_opt.LazyAdam, adam), (_opt.Ftrl, ftrl)):
+    # slot optimizers: the optimizer named (its defaults) or passed, fresh slots for every table
+    # (Lazy Adam: m = v = 0; FTRL: accum = initial_accumulator_value, linear = 0; row-wise Adagrad: one
+    # [rows, 1] accumulator = its initial_accumulator_value)
+    given = dict(adam=adam, ftrl=ftrl, rowwise_adagrad=rowwise_adagrad)
+    for cls in _opt.TWO_SLOT.values():
+      setattr(self, cls.name, None)
+      setattr(self, cls.slot_kw, None)
+      opt = given[cls.name]
       if optimizer == cls.name or opt is not None:
         opt = opt if opt is not None else cls.default(self.device)
         setattr(self, cls.name, opt)
@@ -189,13 +193,8 @@ class _TableLayer:
     self._hash_lookup = self._hash_grad = self._hash_sharded = None
 
   def _two_slot_kw(self, idx):
-    """The drivers' keyword arguments of the two-slot optimizers, tables idx."""
-    kw = {}
-    for cls in _opt.TWO_SLOT.values():
-      pairs = getattr(self, cls.slot_kw)
-      kw[cls.slot_kw] = None if pairs is None else [pairs[c] for c in idx]
-      kw[cls.name] = getattr(self, cls.name)
-    return kw
+    """The drivers' keyword arguments of the slot optimizers, tables idx."""
+    return _opt.slot_kwargs(self, idx)
 
   # ---- hash-keyed columns: what moves with a table ------------------------------------------------------
   def _world(self):
@@ -246,8 +245,8 @@ class _TableLayer:
           slots[c] = tuple(pair)
     if moved and self._hash_sharded is not None:
       pick = lambda xs: None if xs is None else [xs[c] for c in self._hash]   # noqa: E731
-      self._hash_sharded.rebind(accums=pick(self.accums), moments=pick(self.moments),
-                                ftrl_slots=pick(self.ftrl_slots))
+      self._hash_sharded.rebind(accums=pick(self.accums),
+                                **{cls.slot_kw: pick(getattr(self, cls.slot_kw)) for cls in _opt.TWO_SLOT.values()})
     elif moved:
       self._hash_lookup.rebind()
       self._rebuild_hash_grad()
@@ -292,18 +291,18 @@ class _TableLayer:
     variables.py:112-141) and, when the layer keeps them, the Adagrad slots (``.../Adagrad``) or the
     Lazy Adam slots (``.../Adam`` = m, ``.../Adam_1`` = v, sharded as the weights) with the 0-d
     scalars ``beta1_power`` and ``beta2_power``, or the FTRL slots (``.../Ftrl`` = accum,
-    ``.../Ftrl_1`` = linear, sharded as the weights).  Hash-keyed columns are not in it: they do not fit a
-    mapping of preallocated tensors, ``save`` and ``restore`` handle them beside it."""
+    ``.../Ftrl_1`` = linear, sharded as the weights), or the row-wise Adagrad accumulators
+    (``.../RowwiseAdagrad``, ``[rows, 1]``, sharded as the weights).  Hash-keyed columns are not in it:
+    they do not fit a mapping of preallocated tensors, ``save`` and ``restore`` handle them beside it."""
     from hybridbackend_amd.training.saver import ShardedSlice
     world = self.coll.world_size if self.coll is not None else 1
     rank = self.coll.rank if self.coll is not None else 0
     per_table = [('', self.weights), ('/Adagrad', self.accums)]
     extra = {}
     for cls in _opt.TWO_SLOT.values():
-      pairs = getattr(self, cls.slot_kw)
+      pairs = getattr(self, cls.slot_kw, None)
       if pairs is not None:
-        per_table += [(cls.tf_suffixes[0], [a for a, _ in pairs]),
-                      (cls.tf_suffixes[1], [b for _, b in pairs])]
+        per_table += [(suffix, [cls.slot_tensors(e)[k] for e in pairs]) for k, suffix in enumerate(cls.tf_suffixes)]
         extra.update(getattr(self, cls.name).tf_variables())
     out = {}
     for c, col in enumerate(self.columns):
@@ -451,7 +450,9 @@ class DenseFeatures(_TableLayer):
       defaults when omitted), whose beta powers advance once per stepped backward.  ``'ftrl'`` keeps
       FTRL slots -- accum filled with ``ftrl.initial_accumulator_value``, zero linear -- for
       ``backward(optimizer='ftrl')``; ``ftrl`` is the :class:`Ftrl` they step with (TF's defaults
-      when omitted).
+      when omitted).  ``'rowwise_adagrad'`` keeps one ``[rows, 1]`` accumulator per table (``row_accums``)
+      for ``backward(optimizer='rowwise_adagrad')``; ``rowwise_adagrad`` is the :class:`RowwiseAdagrad` they
+      step with (its defaults when omitted).
     train: False makes every hash-keyed column a pure find -- unseen ids read zero rows, ``size()`` and
       ``counts`` do not move, and ``backward`` is refused; bucketed columns ignore it.
 
@@ -466,9 +467,10 @@ class DenseFeatures(_TableLayer):
   """
 
   def __init__(self, columns, device, coll=None, batch_size=0, init=None,
-               initial_accumulator_value=None, optimizer=None, adam=None, ftrl=None, train=True):
+               initial_accumulator_value=None, optimizer=None, adam=None, ftrl=None, train=True,
+               rowwise_adagrad=None):
     self._init_tables(columns, device, coll, batch_size, init, initial_accumulator_value, optimizer,
-                      adam, ftrl, train)
+                      adam, ftrl, train, rowwise_adagrad)
     for c in self._hash:
       col = self.columns[c]
       if col.weight_feature_key is not None and self._world() > 1:
@@ -775,11 +777,12 @@ class SequenceFeatures(_TableLayer):
   ``maybe_evict`` are :class:`DenseFeatures`'."""
 
   def __init__(self, columns, device, coll=None, batch_size=0, init=None,
-               initial_accumulator_value=None, optimizer=None, adam=None, ftrl=None, train=True):
+               initial_accumulator_value=None, optimizer=None, adam=None, ftrl=None, train=True,
+               rowwise_adagrad=None):
     from hybridbackend_amd.embedding.hash_sequence import HashSequenceLookup
     from hybridbackend_amd.embedding.sequence import SequenceLookup, SequenceLookupGrad
     self._init_tables(columns, device, coll, batch_size, init, initial_accumulator_value, optimizer,
-                      adam, ftrl, train)
+                      adam, ftrl, train, rowwise_adagrad)
     for c in self._hash:
       col = self.columns[c]
       if col.pad_id is None and self._world() > 1:

@@ -439,6 +439,39 @@ int hbk_group_lookup_bwd_ftrl(int32_t n_cols, const hbk_lookup_grad_column_t* co
                               float* const* accum, float* const* linear, const hbk_ftrl_t* ftrl,
                               float lr, void* workspace, size_t workspace_bytes, hbk_stream_t stream);
 
+/* Row-wise Adagrad ("exact row-wise Adagrad" of sparse embedding engines): ONE fp32 accumulator per row.
+ * For every distinct row r of the call with its deduplicated gradient g[0..dim) (after the clip: g'), each
+ * a separately rounded fp32 op in this order:
+ *     s    = sum_k g_k * g_k
+ *     a'   = a[r] + s / (float)dim
+ *     m    = lr / (sqrtf(a') + epsilon)
+ *     w_k  = w_k - m * g_k        (every k)
+ *     a[r] = a'
+ * The order of s is the clip's (hbk_group_lookup_fwd_clipped): the row is split over its lanes (chunks of 4
+ * floats when dim % 4 == 0 and table, grad_rows and the pitch are 16-byte aligned, else of 1 float; L = the
+ * power of two >= chunks), a lane sums its chunk in element order (((g0 g0 + g1 g1) + g2 g2) + g3 g3), lanes
+ * without a chunk give +0, and the L partial sums meet in the butterfly p[i] = p[i] + p[i ^ o], o = 1, 2, 4,
+ * .. < L.  accum[c] is a device fp32 [rows, 1], contiguous (word r belongs to row r whatever table_pitch is);
+ * being one 4-byte word per row it does not decide the row shape.  Rows that do not occur, rows outside the
+ * table and -1 touch nothing.  A row with a' == 0 and epsilon == 0 computes 0 / 0: start the accumulator
+ * above 0 or keep epsilon > 0.  The phases (emit-form reduce, then one apply launch per 64 columns that reads
+ * n_unique on the device: no host sync, capturable), step only (unique_rows = grad_rows = NULL) and the
+ * workspace query are hbk_group_lookup_bwd_adam's.  Refused before any device work (HBK_INVALID_ARGUMENT): a
+ * NULL or misaligned accum[c]; accum[c] equal to the table; a table or accumulator named by two columns (the
+ * step is not additive); cols[c].accum != NULL; dim > 256 (> 64 as 4-byte chunks); lr 0 or not finite;
+ * epsilon < 0 or not finite.  The _clipped pair differentiates through max_norm as the other optimizers'
+ * (g' replaces g everywhere, and grad_rows end as g').  Detected by the presence of the symbols; the
+ * structs above and the version are those of 0.2.0. */
+typedef struct {
+  float epsilon;
+} hbk_rowwise_adagrad_t;
+size_t hbk_group_lookup_bwd_rowwise_adagrad_workspace_bytes(int32_t n_cols,
+                                                            const hbk_lookup_grad_column_t* cols);
+int hbk_group_lookup_bwd_rowwise_adagrad(int32_t n_cols, const hbk_lookup_grad_column_t* cols,
+                                         float* const* accum, const hbk_rowwise_adagrad_t* rowwise_adagrad,
+                                         float lr, void* workspace, size_t workspace_bytes,
+                                         hbk_stream_t stream);
+
 /* The gradient of the per-id weights (tf.nn.embedding_lookup_sparse is differentiable in
  * sp_weights.values).  grad_weights[c] is a device fp32 [n_ids of column c], or NULL = not wanted;
  * max_norms is NULL or a HOST float[n_cols] as in the clipped entries (0 = not clipped).  Reads
@@ -539,6 +572,14 @@ int hbk_group_lookup_bwd_ftrl_clipped(int32_t n_cols, const hbk_lookup_grad_colu
                                       const float* max_norms, float* const* accum,
                                       float* const* linear, const hbk_ftrl_t* ftrl, float lr,
                                       void* workspace, size_t workspace_bytes, hbk_stream_t stream);
+size_t hbk_group_lookup_bwd_rowwise_adagrad_clipped_workspace_bytes(int32_t n_cols,
+                                                                    const hbk_lookup_grad_column_t* cols,
+                                                                    const float* max_norms);
+int hbk_group_lookup_bwd_rowwise_adagrad_clipped(int32_t n_cols, const hbk_lookup_grad_column_t* cols,
+                                                 const float* max_norms, float* const* accum,
+                                                 const hbk_rowwise_adagrad_t* rowwise_adagrad, float lr,
+                                                 void* workspace, size_t workspace_bytes,
+                                                 hbk_stream_t stream);
 
 /* Sequence lookups: a ragged id list WITHOUT a combiner -- the padded [batch, max_len, dim] rows an
  * attention layer reads (DIN / DIEN / BST): docs/tutorial/ranking/data.py:195-224
@@ -1771,6 +1812,17 @@ int hbk_sharded_lookup_bwd_ftrl(hbk_sharded_t plan, const float* const* grads,
                                 const int32_t* grad_strides, const hbk_ftrl_t* ftrl, float lr,
                                 int64_t* const* unique_rows, float* const* grad_rows,
                                 int32_t* const* n_unique, hbk_stream_t stream);
+/* Row-wise Adagrad on the shards (hbk_group_lookup_bwd_rowwise_adagrad), as the Lazy Adam pair:
+ * hbk_sharded_set_rowwise_adagrad_slots registers every column's accumulator shard ([rows_local, 1]; the
+ * columns' accum must be NULL), then hbk_sharded_lookup_bwd_rowwise_adagrad runs the owner-side reduce in its
+ * emit form and the apply, launch group by launch group.  Hash plans and max_norms as there; unique_rows and
+ * grad_rows may both be NULL (step only). */
+int hbk_sharded_set_rowwise_adagrad_slots(hbk_sharded_t plan, float* const* accum);
+int hbk_sharded_lookup_bwd_rowwise_adagrad(hbk_sharded_t plan, const float* const* grads,
+                                           const int32_t* grad_strides,
+                                           const hbk_rowwise_adagrad_t* rowwise_adagrad, float lr,
+                                           int64_t* const* unique_rows, float* const* grad_rows,
+                                           int32_t* const* n_unique, hbk_stream_t stream);
 
 #ifdef __cplusplus
 }
