@@ -83,6 +83,12 @@ class Sequence(C.Structure):
               ('lengths', C.c_void_p), ('row_grid', C.c_void_p)]
 
 
+class SequencePack(C.Structure):
+  """hbk_sequence_pack_t"""
+  _fields_ = [('packed', C.c_void_p), ('packed_capacity', C.c_int64), ('pos_splits', C.c_void_p),
+              ('sample_splits', C.c_void_p), ('total', C.c_void_p)]
+
+
 class HashColumn(C.Structure):
   """hbk_hash_column_t"""
   _fields_ = [('keys_cache', C.c_void_p), ('slab_count', C.c_int64), ('slab_size', C.c_int32),
@@ -274,6 +280,8 @@ def _declare(l):
     'hbk_group_lookup_fwd_sequence': (C.c_int, [i32, vp, vp, vp, vp]),
     'hbk_sequence_row_grid_n': (C.c_int, [i32, vp, vp, vp]),
     'hbk_sequence_id_grid_n': (C.c_int, [i32, vp, vp, vp]),
+    'hbk_sequence_pack_workspace_bytes': (sz, [i32, vp]),
+    'hbk_sequence_pack_n': (C.c_int, [i32, vp, vp, vp, vp, sz, vp]),
     'hbk_group_stitch_bwd': (C.c_int, [i32, vp, vp]),
     'hbk_cache_probe': (C.c_int, [vp, i64, i32, vp, i64, vp, vp, vp]),
     'hbk_cache_lookup_workspace_bytes': (sz, [i64]),

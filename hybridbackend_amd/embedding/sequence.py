@@ -350,3 +350,125 @@ def sequence_id_grid(ids, row_splits=None, max_lens=None, pad_ids=None):
     seqs[c].row_grid = bufs[c].data_ptr()
   _lib.check(_lib.lib().hbk_sequence_id_grid_n(n, cols, seqs, _lib.current_stream(dev)))
   return grids, lengths
+
+
+def sequence_pack(ids, row_splits=None, max_lens=None):
+  """The PACKED form of zero-padded sequence columns (``hbk_sequence_pack_n``): per column the first
+  ``min(len, T)`` ids of every sample back to back -- raw: sign-extended from int32, never bucketized, negative
+  ids kept -- and the row splits that make them a ragged column of ``B * T`` segments, one per position,
+  holding one id or none.  Returns ``(packed_ids, pos_splits, lengths, sample_splits)``, each a list with one
+  entry per column: int64 ``[total]``, int32 ``[B * T + 1]``, int32 ``[B]`` and int32 ``[B + 1]`` (the CSR of
+  the packed ids by sample).  There is no pad id: padding is in no list.  What a sharded sequence column
+  without a pad id feeds ``ShardedGroupLookup`` / ``ShardedHashGroupLookup`` with combiner ``'sum'`` (an empty
+  segment is a zero row that reaches no gradient); ids past ``T`` are never read.
+
+  One C call, then ONE device-to-host copy, of the N totals (this call waits for the device there), to narrow
+  every ``packed_ids[c]`` to a view of its ``total`` elements.  The sharded step that follows waits on the host
+  once per forward itself (for the sizes of its id exchange)."""
+  n = len(ids)
+  if max_lens is None:
+    raise _bad('max_lens is required: the padded length of every column')
+  max_lens = per_column(max_lens, n, 'max_lens')
+  for c in range(n):
+    if not 1 <= max_lens[c] < 2 ** 31:
+      raise _bad(f'max_len of column {c} must be in [1, 2^31), got {max_lens[c]}')
+  cols = (_lib.LookupColumn * n)()
+  seqs = (_lib.Sequence * n)()
+  packs = (_lib.SequencePack * n)()
+  batch, _ = _bind_ids(cols, seqs, ids, row_splits, max_lens, [None] * n)
+  if n == 0:
+    return [], [], [], []
+  dev = ids[0].device
+  lengths, _ = _alloc_side(batch, max_lens, dev, False)
+  caps = [min(int(ids[c].numel()), batch[c] * max_lens[c]) for c in range(n)]
+  # (the entry refuses a NULL output whatever the batch: an empty column gets a view of one word)
+  bufs = [torch.empty(max(k, 1), dtype=torch.int64, device=dev) for k in caps]
+  pos = [torch.empty(b * t + 1, dtype=torch.int32, device=dev) for b, t in zip(batch, max_lens)]
+  samp = [torch.empty(b + 1, dtype=torch.int32, device=dev) for b in batch]
+  totals = torch.empty(n, dtype=torch.int32, device=dev)
+  for c in range(n):
+    seqs[c].lengths = lengths[c].data_ptr() if batch[c] else totals.data_ptr()   # (no sample: nothing is written)
+    packs[c].packed = bufs[c].data_ptr()
+    packs[c].packed_capacity = caps[c]
+    packs[c].pos_splits = pos[c].data_ptr()
+    packs[c].sample_splits = samp[c].data_ptr()
+    packs[c].total = totals.data_ptr() + 4 * c
+  lib = _lib.lib()
+  need = int(lib.hbk_sequence_pack_workspace_bytes(n, cols))
+  work = torch.empty(max(need, 4), dtype=torch.uint8, device=dev)
+  _lib.check(lib.hbk_sequence_pack_n(n, cols, seqs, packs, work.data_ptr(), need, _lib.current_stream(dev)))
+  host = totals.cpu().tolist()
+  for c in range(n):
+    if host[c] > caps[c]:
+      raise _bad(f'column {c}: row_splits name {host[c]} ids within max_len, the column holds {caps[c]}: '
+                 'the row splits are no CSR of the ids')
+  packed = [bufs[c][:host[c]] for c in range(n)]
+  return packed, pos, lengths, samp
+
+
+class ShardedSequenceLookup:
+  """Zero-padded sequence lookups on SHARDED tables: a thin wrapper that packs (:func:`sequence_pack`) and hands
+  the packed ids and the position-level row splits to a sharded driver.
+
+  Args:
+    driver: a ``ShardedGroupLookup`` or ``ShardedHashGroupLookup`` built with combiner ``'sum'``: ``dedup``, the
+      fp16 wire, ``max_norms``, ``hot_rows``, every optimizer and ``maybe_grow`` / ``maybe_evict`` stay the
+      driver's own.
+    max_lens: the padded length T of every column (one value for all, or one per column).
+
+  Positions past a sample's length are zero rows that take part in nothing (TF's ``SequenceFeatures``): they are
+  in no id list, so they cross no wire, are looked up on no rank and reach no gradient row or optimizer slot;
+  ids past T are never read, inserted, counted or kept fresh.  One host read per forward (the totals) beside
+  the driver's own.  ``sp_weights``, the p2p form (``p2p_bind``) and ``PipelinedLookup`` are not offered through
+  this wrapper."""
+
+  def __init__(self, driver, max_lens):
+    from hybridbackend_amd.embedding.lookup import _combiner_code
+    self.driver = driver
+    n = len(driver.shards)
+    combs = driver.combiners
+    if isinstance(combs, (str, int)) or combs is None:
+      combs = [combs] * n
+    if any(_combiner_code(k) != _lib.COMBINER_SUM for k in combs):
+      raise _bad("ShardedSequenceLookup: the driver must be built with combiner 'sum' (an empty segment is "
+                 'then a zero row)')
+    self.max_lens = per_column(max_lens, n, 'max_lens')
+    for c, t in enumerate(self.max_lens):
+      if t < 1:
+        raise _bad(f'max_len of column {c} must be >= 1, got {t}')
+    self.dims = list(driver.dims)
+    self.lengths = None
+    self.sample_splits = None
+
+  def __len__(self):
+    return len(self.max_lens)
+
+  def __call__(self, ids, row_splits=None, outs=None):
+    """ids[c]: int32/int64 values, row_splits[c]: int32 ``[B+1]`` or None (one id per sample).  Returns
+    ``(outs, lengths)``: per column fp32 ``[B, T_c, dim_c]`` (the caller's contiguous ``outs[c]`` of that shape,
+    written in place) and int32 ``[B]`` ``min(len, T_c)``.  A collective when the driver's world is."""
+    n = len(self.max_lens)
+    if getattr(self.driver, '_p2p_keep', None) is not None:
+      raise _lib.HbkError(_lib.UNIMPLEMENTED, 'ShardedSequenceLookup: the p2p form takes one id per segment; '
+                          'p2p_unbind first')
+    packed, pos, lengths, samp = sequence_pack(ids, row_splits, self.max_lens)
+    flat = None
+    if outs is not None:
+      if len(outs) != n:
+        raise _bad(f'expected {n} outputs, got {len(outs)}')
+      flat = []
+      for c, o in enumerate(outs):
+        shape = (lengths[c].numel(), self.max_lens[c], self.dims[c])
+        if not o.is_cuda or o.dtype != torch.float32 or tuple(o.shape) != shape or not o.is_contiguous():
+          raise _bad(f'output {c} must be a contiguous fp32 device tensor {list(shape)}')
+        flat.append(o.view(shape[0] * shape[1], shape[2]))
+    rows = self.driver(packed, pos, outs=flat)
+    self.lengths, self.sample_splits = lengths, samp
+    return [o.view(ln.numel(), t, d) for o, ln, t, d in zip(rows, lengths, self.max_lens, self.dims)], lengths
+
+  def backward(self, grads, **kw):
+    """grads[c]: the gradient of the last forward's ``outs[c]``, ``[B, T, dim]`` (or ``[B * T, dim]``).  The
+    driver's ``backward`` with its keywords and its result: it differentiates the last forward and the row
+    splits that forward kept, so padding positions send no gradient row."""
+    flat = [g.contiguous().view(-1, d) for g, d in zip(grads, self.dims)]
+    return self.driver.backward(flat, **kw)

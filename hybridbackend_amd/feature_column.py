@@ -122,7 +122,8 @@ class HashSequenceEmbeddingColumn(_HashColumn):
   """:class:`SequenceEmbeddingColumn` over a :class:`HashTable`: a sample's first ``max_len`` RAW ids looked up
   into ``[batch, max_len, dimension]``.  ``pad_id`` is a raw id, any int64 the table can store (not a sentinel
   of the table); None: the positions past a sample's length are zero rows.  A column on more than one rank
-  needs a ``pad_id``.  The table arguments are :class:`HashEmbeddingColumn`'s."""
+  needs a ``pad_id`` or ``SequenceFeatures(..., sharded_zero_padding=True)``.  The table arguments are
+  :class:`HashEmbeddingColumn`'s."""
 
   def __init__(self, key, capacity, dimension, max_len, pad_id=None, max_norm=None, dedup=False, slab_size=8,
                init_scale=1e-3, seed=0, expiring=False, min_freq=0, sketch_depth=4, sketch_width=None,
@@ -743,7 +744,8 @@ class SequenceEmbeddingColumn:
   ``pad_id`` None: the positions past a sample's length are zero rows that take part in nothing (TF's
   ``SequenceFeatures``); ``pad_id`` set (``0 <= pad_id < num_buckets``): they look that id up
   (``tf.sparse.to_dense(default_value=)``) and its row collects their gradient.  ``max_norm`` and
-  ``dedup`` are EmbeddingColumn's.  A column whose table is sharded needs a ``pad_id``."""
+  ``dedup`` are EmbeddingColumn's.  A column whose table is sharded needs a ``pad_id`` or
+  ``SequenceFeatures(..., sharded_zero_padding=True)``."""
 
   def __init__(self, key, num_buckets, dimension, max_len, pad_id=None, max_norm=None, dedup=False):
     from hybridbackend_amd.embedding.lookup import max_norm_list
@@ -767,37 +769,46 @@ class SequenceFeatures(_TableLayer):
   looked up through ``ShardedGroupLookup`` as ``batch * max_len`` ids of one sample each, over the grid
   ``sequence_row_grid`` builds.  The sharded step bucketizes its ids again, which would carry the ``-1`` of
   a zero-padded position to row ``num_buckets - 1``: a sharded sequence column therefore requires a
-  ``pad_id`` (zero-padded sequences on sharded tables are not provided).
+  ``pad_id`` -- unless the layer is built with ``sharded_zero_padding=True``: a sharded column without a ``pad_id``
+  (bucketed or hash-keyed) then goes through the PACKED form (``sequence_pack``): the step is handed the first
+  ``min(len, max_len)`` ids of every sample and ``batch * max_len`` segments holding one id or none, in the same
+  step as the group's columns with a pad id.  Padding is in no id list: zero rows that cross no wire, reach no
+  gradient row and keep no key fresh (TF's ``SequenceFeatures``), at the price of ONE more host read per forward
+  and group (the packed totals) -- which is why the argument is opt-in.
 
   Hash-keyed columns (:class:`HashSequenceEmbeddingColumn`) mix freely with bucketed ones.  On one rank they go
   through ``HashSequenceLookup`` / ``SequenceLookupGrad``; on W > 1 ranks through ``ShardedHashGroupLookup``
   with combiner ``'sum'`` over the RAW-id grid ``sequence_id_grid`` builds (``batch * max_len`` ids of one sample
   each): ids past ``max_len`` are not in the grid, so they are not inserted, counted or kept fresh on any rank,
-  and a pad id is required there too.  ``train``, ``hash_tables``, ``set_step``, ``maybe_grow`` and
-  ``maybe_evict`` are :class:`DenseFeatures`'."""
+  and a pad id is required there too unless ``sharded_zero_padding`` is set (the packed ids are raw too).
+  ``train``, ``hash_tables``, ``set_step``, ``maybe_grow`` and ``maybe_evict`` are :class:`DenseFeatures`'."""
 
   def __init__(self, columns, device, coll=None, batch_size=0, init=None,
                initial_accumulator_value=None, optimizer=None, adam=None, ftrl=None, train=True,
-               rowwise_adagrad=None):
+               rowwise_adagrad=None, sharded_zero_padding=False):
     from hybridbackend_amd.embedding.hash_sequence import HashSequenceLookup
     from hybridbackend_amd.embedding.sequence import SequenceLookup, SequenceLookupGrad
     self._init_tables(columns, device, coll, batch_size, init, initial_accumulator_value, optimizer,
                       adam, ftrl, train, rowwise_adagrad)
+    self.sharded_zero_padding = bool(sharded_zero_padding)
     for c in self._hash:
       col = self.columns[c]
-      if col.pad_id is None and self._world() > 1:
+      if col.pad_id is None and self._world() > 1 and not self.sharded_zero_padding:
         raise _bad(f'hash sequence column {col.key!r}: its table is sharded over {self._world()} ranks, and a '
                    'sharded sequence column requires a pad_id (the sharded step takes one raw id per position, '
                    'and among raw ids no value means "nothing": every int64 is a key; zero padding is for one '
-                   'rank)')
+                   'rank).  SequenceFeatures(..., sharded_zero_padding=True) looks such a column up zero padded, '
+                   'through the packed form, at the price of one more host read per forward')
     for c in self._shd:
       col = self.columns[c]
-      if col.pad_id is None:
+      if col.pad_id is None and not self.sharded_zero_padding:
         raise _lib.InvalidArgumentError(
           _lib.INVALID_ARGUMENT,
           f'sequence column {col.key!r}: its table is sharded over {coll.world_size} ranks, and a sharded '
           'sequence column requires a pad_id (the sharded step bucketizes the id grid again, which would '
-          'turn the -1 of a zero-padded position into a row; zero padding is for replicated tables)')
+          'turn the -1 of a zero-padded position into a row; zero padding is for replicated tables).  '
+          'SequenceFeatures(..., sharded_zero_padding=True) looks such a column up zero padded, through the '
+          'packed form, at the price of one more host read per forward')
     pick = lambda idx, xs: [xs[c] for c in idx]   # noqa: E731
     attr = lambda idx, name: [getattr(self.columns[c], name) for c in idx]   # noqa: E731
     self._lookup = self._grad = self._sharded = None
@@ -852,30 +863,48 @@ class SequenceFeatures(_TableLayer):
       for k, c in enumerate(self._rep):
         outs[c], lengths[c] = o[k], ln[k]
     if self._shd:
-      cols = pick(self._shd, self.columns)
-      grids, ln = sequence_row_grid(pick(self._shd, ids), pick(self._shd, splits),
-                                    [col.num_buckets for col in cols], [col.max_len for col in cols],
-                                    [col.pad_id for col in cols])
-      o = self._sharded(grids)
-      for k, c in enumerate(self._shd):
-        outs[c] = o[k].view(batch or 0, cols[k].max_len, cols[k].dimension)
-        lengths[c] = ln[k]
+      def row_grid(idx):
+        cols = pick(idx, self.columns)
+        return sequence_row_grid(pick(idx, ids), pick(idx, splits), [col.num_buckets for col in cols],
+                                 [col.max_len for col in cols], [col.pad_id for col in cols])
+      self._sharded_step(self._sharded, self._shd, ids, splits, row_grid, batch or 0, outs, lengths)
     if self._hash_sharded is not None:
       # the RAW-id grid: B * T ids of one sample each, the pad id past a sample's length; ids past T are not in
       # it, so they reach no owner
-      from hybridbackend_amd.embedding.sequence import sequence_id_grid
-      cols = pick(self._hash, self.columns)
-      grids, ln = sequence_id_grid(pick(self._hash, ids), pick(self._hash, splits),
-                                   [col.max_len for col in cols], [col.pad_id for col in cols])
-      o = self._hash_sharded(grids)
-      for k, c in enumerate(self._hash):
-        outs[c] = o[k].view(batch or 0, cols[k].max_len, cols[k].dimension)
-        lengths[c] = ln[k]
+      def id_grid(idx):
+        from hybridbackend_amd.embedding.sequence import sequence_id_grid
+        cols = pick(idx, self.columns)
+        return sequence_id_grid(pick(idx, ids), pick(idx, splits), [col.max_len for col in cols],
+                                [col.pad_id for col in cols])
+      self._sharded_step(self._hash_sharded, self._hash, ids, splits, id_grid, batch or 0, outs, lengths)
     elif self._hash:
       o, ln = self._hash_lookup(pick(self._hash, ids), pick(self._hash, splits))
       for k, c in enumerate(self._hash):
         outs[c], lengths[c] = o[k], ln[k]
     return outs, lengths
+
+  def _sharded_step(self, driver, group, ids, splits, grid_of, batch, outs, lengths):
+    """One step of a sharded driver over the columns ``group``: those with a pad id as ``batch * max_len`` ids of
+    one sample each (``grid_of(columns)``: their grids and lengths), the zero-padded ones
+    (``sharded_zero_padding``) in the packed form -- the first ``min(len, max_len)`` ids of every sample and
+    ``batch * max_len`` segments of one id or none (``sequence_pack``: one call for the group, one host read).
+    The step keeps the row splits, so the backward needs nothing else."""
+    from hybridbackend_amd.embedding.sequence import sequence_pack
+    packed = [c for c in group if self.columns[c].pad_id is None]
+    gridded = [c for c in group if self.columns[c].pad_id is not None]
+    step_ids, step_splits = {}, {}
+    if gridded:
+      grids, ln = grid_of(gridded)
+      for k, c in enumerate(gridded):
+        step_ids[c], step_splits[c], lengths[c] = grids[k], None, ln[k]
+    if packed:
+      p_ids, p_pos, ln, _ = sequence_pack([ids[c] for c in packed], [splits[c] for c in packed],
+                                          [self.columns[c].max_len for c in packed])
+      for k, c in enumerate(packed):
+        step_ids[c], step_splits[c], lengths[c] = p_ids[k], p_pos[k], ln[k]
+    o = driver([step_ids[c] for c in group], [step_splits[c] for c in group] if packed else None)
+    for k, c in enumerate(group):
+      outs[c] = o[k].view(batch, self.columns[c].max_len, self.columns[c].dimension)
 
   def backward(self, grads, apply_lr=0.0, optimizer='sgd', emit=True):
     """grads[c]: the gradient of the last forward's ``outputs[c]``.  Returns per column the

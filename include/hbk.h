@@ -650,6 +650,53 @@ int hbk_sequence_row_grid_n(int32_t n_cols, const hbk_lookup_column_t* cols,
  * Detected by the presence of the symbol; the structs and the version are those of 0.2.0. */
 int hbk_sequence_id_grid_n(int32_t n_cols, const hbk_lookup_column_t* cols,
                            const hbk_sequence_t* seq, hbk_stream_t stream);
+/* The PACKED form of a zero-padded sequence column: what a sharded sequence column WITHOUT a pad id hands the
+ * sharded step.  Neither grid above can say "nothing" to that step (it bucketizes a -1 into row bucket - 1, and
+ * among raw ids every int64 is a key), but the step takes ragged columns, and with combiner sum an empty segment
+ * is a zero row that reaches no gradient.  A zero-padded sequence column is such a column: B * T segments, one
+ * per position, each holding exactly one id where the position holds one and none where it is padding; the ids
+ * are the effective ids packed back to back.  Padding is in no list: it is never sent, looked up or stepped.
+ * Per column, with B = n_segments, T = seq[c].max_len:
+ *     len_b            = row_splits ? row_splits[b + 1] - row_splits[b] : 1      (a negative value counts as 0)
+ *     l_b              = min(len_b, T)
+ *     sample_splits[b] = sum over b' < b of l_b'          sample_splits[B] = total
+ *     lengths[b]       = l_b                                                     int32 [B]   (seq[c].lengths)
+ *     pos_splits[b * T + t] = sample_splits[b] + min(t, l_b)   pos_splits[B * T] = total     int32 [B * T + 1]
+ *     packed[sample_splits[b] + t] = (int64) ids[row_splits[b] + t]   for t < l_b            int64
+ *     total[0]         = sample_splits[B]                                                    int32 [1]
+ * sample_splits (int32 [B + 1]) is the CSR of the packed ids by sample, pos_splits their CSR by position.  Packed
+ * ids are RAW: sign-extended from int32 ids, negative ids kept, nothing bucketized (the sharded step floormods a
+ * bucketed column itself; a hash column wants the raw id).  Never read: an id past a sample's first T.  Never
+ * written: an element of packed at or past total.  An id index row_splits[b] + t outside [0, n_ids) follows
+ * hbk_sequence_id_grid_n's rule: it is not read -- where the grid holds the pad id, the packed element, which has
+ * none to hold, holds 0.  No contents of row_splits make the kernels read or write out of bounds: with row
+ * splits that are no CSR of the ids total may exceed packed_capacity, and the elements at or past
+ * packed_capacity are then not written either (compare total with the capacity).
+ * The id side of cols[c] (ids, ids_dtype, n_ids, row_splits, n_segments) is read as hbk_sequence_id_grid_n reads
+ * it; every other field of the column is ignored.  Of seq[c]: max_len and lengths; has_pad must be 0; row_grid
+ * and pad_id are ignored.  Refused (HBK_INVALID_ARGUMENT) before any launch, the column named: max_len < 1,
+ * B * T >= 2^31, n_ids >= 2^31, n_segments != n_ids with row_splits == NULL, a NULL output (all five are
+ * written, also with B == 0), packed_capacity < min(n_ids, B * T), has_pad != 0 (a pad id belongs to the grid
+ * ops), a workspace smaller than hbk_sequence_pack_workspace_bytes answers (the message states the size).
+ * n_cols == 0, B == 0 and all-empty samples are fine.
+ * Three launches per 64 columns -- the clamped lengths of every tile of 256 samples summed into the workspace;
+ * one workgroup per column scans its tile sums and writes total; every tile scans its own samples, writes lengths
+ * and sample_splits and covers its positions (pos_splits, packed) -- of plain loads and vector stores, 8 bytes
+ * wide to packed, no atomics.  No host read, no device-to-host copy, and no scratch that has to be cleared
+ * (every workspace word is written before it is read): capturable and replayable.  The caller that narrows
+ * packed to total elements reads total himself.
+ * Detected by the presence of the symbols; the structs above and the version are those of 0.2.0. */
+typedef struct {
+  int64_t* packed;           /* device [packed_capacity] */
+  int64_t packed_capacity;   /* >= min(n_ids, B * T) */
+  int32_t* pos_splits;       /* device [B * T + 1] */
+  int32_t* sample_splits;    /* device [B + 1] */
+  int32_t* total;            /* device [1] */
+} hbk_sequence_pack_t;
+size_t hbk_sequence_pack_workspace_bytes(int32_t n_cols, const hbk_lookup_column_t* cols);
+int hbk_sequence_pack_n(int32_t n_cols, const hbk_lookup_column_t* cols, const hbk_sequence_t* seq,
+                        const hbk_sequence_pack_t* pack, void* workspace, size_t workspace_bytes,
+                        hbk_stream_t stream);
 
 /* R10 (sharded form)  d(stitch + combiner): the transpose of the requester-side
  *   `gather(embeddings, shard_index)` + combiner (hbtf/embedding/sharding.py:200; TF emits
