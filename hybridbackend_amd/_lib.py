@@ -166,6 +166,12 @@ class HashMissingColumn(C.Structure):
               ('out_ids', C.c_void_p), ('out_capacity', C.c_int64), ('count', C.c_void_p)]
 
 
+class HashMissingRunsColumn(C.Structure):
+  """hbk_hash_missing_runs_column_t"""
+  _fields_ = [('keys_cache', C.c_void_p), ('slab_count', C.c_int64), ('slab_size', C.c_int32),
+              ('exp', HashExpiry), ('out_ids', C.c_void_p), ('out_capacity', C.c_int64), ('count', C.c_void_p)]
+
+
 HASH_MAX_MOVES = 8
 
 
@@ -299,6 +305,8 @@ def _declare(l):
     'hbk_hash_remove_n': (C.c_int, [i32, vp, vp]),
     'hbk_hash_missing_workspace_bytes': (sz, [i32, vp, vp]),
     'hbk_hash_missing_n': (C.c_int, [i32, vp, vp, vp, sz, vp]),
+    'hbk_hash_missing_runs_workspace_bytes': (sz, [i32, vp, vp]),
+    'hbk_hash_missing_runs_n': (C.c_int, [i32, vp, vp, vp, vp, sz, vp]),
     'hbk_hash_insert_admit_n': (C.c_int, [i32, vp, vp, i32, vp]),
     'hbk_hash_insert_expiring_admit_n': (C.c_int, [i32, vp, vp, vp, i32, vp]),
     'hbk_hash_rehash_n': (C.c_int, [i32, vp, vp]),
@@ -338,6 +346,9 @@ def _declare(l):
     'hbk_sharded_prefetch_on': (C.c_int, [vp, vp, vp, vp]),
     'hbk_sharded_lookup_fwd_begin': (C.c_int, [vp, vp, vp, vp, vp, vp]),
     'hbk_sharded_lookup_fwd_end': (C.c_int, [vp, vp, vp, vp]),
+    'hbk_sharded_lookup_fwd_ids': (C.c_int, [vp, vp, vp, vp, vp, vp]),
+    'hbk_sharded_lookup_fwd_gather': (C.c_int, [vp, vp]),
+    'hbk_sharded_hash_missing': (C.c_int, [vp, vp, vp, vp, vp, vp]),
     'hbk_sharded_prefetch': (C.c_int, [vp, vp, vp, vp]),
     'hbk_sharded_owned_ids': (i64, [vp, i32]),
     'hbk_sharded_last_host_us': (C.c_int, [vp, vp]),

@@ -33,6 +33,10 @@
 // device's L2 whatever CU issues them; a stale EMPTY read only costs a failed swap, whose returned value is the
 // cell's.  The kernel boundary publishes the set: count and write read it (and first[]) with plain loads, as
 // hash_insert.hip's find reads a key array nobody writes.
+//
+// hash_missing_runs.hip (hbk_hash_missing_runs_n) holds a copy of the scratch set -- kMinCells, kNoPosition, cells_of,
+// claim_cell, the clear kernel and the walk of selected() -- for ids that arrive as runs: a change of the set's rules
+// here is a change there.
 #include "hash_pack.h"
 
 namespace hbk {

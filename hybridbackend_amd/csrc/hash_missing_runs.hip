@@ -1,0 +1,488 @@
+// Expiring hash tables (hbk_hash_missing_runs_n): hbk_hash_missing_n over ids that arrive as runs -- on the owner of
+// a sharded hash table a column's ids are W arrays, one per requester, each with its own place for the find's
+// answers (hbk_hash_translate_runs_n).  The id list E of a column is the concatenation of its runs in run order;
+// the call reports the distinct ids of E that the table does not hold, in the order of their first occurrence in
+// E.  include/hbk.h has the contract.  The table is not written.
+//
+// Positions.  Every run is padded up to whole 256-position tiles: run r of a column starts at position
+// 256 * (tiles of the column's earlier runs), and the positions behind its n_keys hold nothing.  No tile straddles
+// a run, positions stay monotone in E-order, and so atomicMin(first[cell], p) and the compaction in position order
+// give first-occurrence order exactly as hash_missing.hip's flat positions do.  Empty runs take no tile.
+//
+// One clear launch per call, then per launch group -- up to 32 columns and HBK_HASH_MAX_RUNS_PER_LAUNCH non-empty
+// runs, a column's runs never split -- five launches, all on the call's stream:
+//   clear  every cell of the call's scratch sets = EMPTY, every first[] = INT32_MAX (plain stores).  The call
+//          clears its own workspace, so it asks nothing of what the workspace held and can be captured and replayed.
+//   find   hbk_hash_translate_runs_n with insert == 0, called as it is: ONE launch for the group.  It writes the
+//          runs' slots.
+//   claim  a workgroup takes up to 1024 positions of ONE run (four tiles; a wave walks four 64-position chunks in
+//          order, as hash_missing.hip's claim does), a lane owns one position of a chunk.  The workgroup finds its
+//          RUN as the runs translate does -- up to four 64-wide ballots over the runs' first claim tiles, the run
+//          tables in the kernarg -- and the run names its column.  It records the run of each of its tiles in the
+//          column's tile_run[] (workspace): count and write, whose lanes meet the position under divergence, read
+//          it from there with a plain load after the kernel boundary.  A position inside the run with slots < 0 and an id that is no sentinel goes into
+//          the column's scratch set: hash_missing.hip's, cell for cell.  A wave without a miss leaves after reading
+//          slots: a batch of resident ids issues no atomic.
+//   count, scan, write
+//          hash_pack.h's stream compaction over the padded positions with the selection "p lies in its run, missed
+//          and first[cell(id)] == p": exactly one position per distinct missed id, the first.  Ids only: no moves.
+//
+// No lane waits for another: the claim's probe reads at most S cells (claim_cell below).  Memory rules: those of
+// hash_missing.hip -- the find reads the key array with plain loads; the claim reads and writes the set with relaxed
+// agent-scope atomics; the kernel boundary publishes the set, first[] and tile_run[] to count and write.
+#include <vector>
+
+#include "hash_pack.h"
+
+namespace hbk {
+namespace {
+
+using namespace pack;
+
+constexpr int kMaxRunsPerLaunch = HBK_HASH_MAX_RUNS_PER_LAUNCH;
+static_assert(kMaxRunsPerLaunch % kWave == 0, "one ballot per 64 runs");
+constexpr int kFindKeysPerGroup = 8;                    // hash_insert.hip's kKeys: a find tile takes (256 / G) * 8 keys
+constexpr int64_t kKeyLimit = 1ll << 30;                // the runs translate of an expiring table takes fewer per column
+constexpr int kClearBlocks = 4096;                      // the clear's grid at the most: it strides
+constexpr int kChunks = 4;                              // 64-position chunks per wave of the claim
+constexpr int kClaimPerBlock = kBlock * kChunks;        // a whole number of 256-position tiles
+
+// The scratch set of a column, as hash_missing.hip keeps it (that file holds the same walk for its flat and sequence
+// positions): the distinct missed ids in open addressing over S = pow2 >= 2 * ids cells (at least 64), home cell =
+// murmur3_i64(id) & (S - 1), linear probing, EMPTY = INT64_MIN, and beside every cell the smallest position that
+// missed with the cell's id.  A cell only ever goes EMPTY -> id and first[] only falls: a lane that loses a swap to
+// ANOTHER id steps to the next cell and a lane that loses to its own id is done.
+constexpr int64_t kMinCells = 64;
+constexpr int32_t kNoPosition = 0x7fffffff;             // first[] of a cell nobody claimed
+
+// the cells of a column that names `ids` ids: at most half of them are ever taken
+inline int64_t cells_of(int64_t ids) {
+  int64_t s = kMinCells;
+  while (s < 2 * ids) s <<= 1;
+  return s;
+}
+
+// the id of a missed position into the set, its position into first[]: at most S = mask + 1 cells are read
+__device__ inline void claim_cell(long long* set, int32_t* first, uint64_t mask, long long id, int32_t p) {
+  uint64_t cell = (uint64_t)murmur3_i64((int64_t)id) & mask;
+  for (uint64_t k = 0; k <= mask; ++k) {
+    long long cur = __hip_atomic_load(set + cell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (cur == kEmptyKey) {
+      long long expected = kEmptyKey;
+      const bool won = __hip_atomic_compare_exchange_strong(set + cell, &expected, id, __ATOMIC_RELAXED,
+                                                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      cur = won ? id : expected;   // (lost: the cell's key now, ours or another's)
+    }
+    if (cur == id) {
+      // (first[] only falls: a position not below the value read changes nothing, and a stale read only costs the
+      // atomic -- the load spares a hot id's later occurrences their turn at one address)
+      if (__hip_atomic_load(first + cell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > p) {
+        __hip_atomic_fetch_min(first + cell, p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      return;
+    }
+    cell = (cell + 1) & mask;
+  }
+}
+
+// after the claim's kernel boundary: the first position that missed with `id`, or kNoPosition when the set does
+// not hold it (the claim's walk; it ends at the id or at an EMPTY cell)
+__device__ inline int32_t first_position(const long long* set, const int32_t* first, uint64_t mask, long long id) {
+  uint64_t cell = (uint64_t)murmur3_i64((int64_t)id) & mask;
+  for (uint64_t k = 0; k <= mask; ++k) {
+    const long long cur = set[cell];
+    if (cur == id) return first[cell];
+    if (cur == kEmptyKey) return kNoPosition;
+    cell = (cell + 1) & mask;
+  }
+  return kNoPosition;
+}
+
+// one non-empty run of the launch
+struct Run {
+  const int64_t* keys;
+  const int64_t* slots;   // the find's answers
+  int64_t n_keys;
+  int32_t col;            // of the launch
+  int32_t first_tile;     // of the launch: the run's first 256-position tile
+};
+
+// one column of the launch: what hash_pack.h's kernels read of a column, and where the column's tiles and runs
+// lie in the launch
+struct ColRec {
+  long long* set;             // workspace [cell_mask + 1]
+  int32_t* first;             // workspace [cell_mask + 1]: the smallest position that missed with the cell's id
+  long long* out_keys;
+  int64_t* count;
+  int64_t* tiles;             // workspace [n_tiles]: the compaction's tile counts
+  int32_t* tile_run;          // workspace [n_tiles]: the run (of the launch) a tile belongs to; written by the claim
+  int64_t out_capacity;
+  int64_t n_tiles;
+  uint64_t cell_mask;         // S - 1
+  int32_t tile_first;         // of the launch: tile_start of this column
+  int32_t pad_;
+};
+
+// The columns of a launch as hash_pack.h's kernels index them: col[ci] is a VIEW of column ci that can see the
+// launch's run table, so that "the id at position p" is answered through the tile's run.
+struct ColTable;
+
+// the ids by position (hash_pack.h's write kernel reads the key of a selected position as keys[p])
+struct RunIds {
+  const ColTable* tab;
+  const int32_t* tile_run;
+  int32_t tile_first;
+  __device__ inline const Run& run_of(int64_t p, int64_t* off) const;
+  __device__ inline long long operator[](int64_t p) const {
+    int64_t off;
+    const Run& r = run_of(p, &off);
+    return (long long)r.keys[off];
+  }
+};
+
+struct ColView {
+  RunIds keys;
+  const long long* set;
+  const int32_t* first;
+  long long* out_keys;
+  int64_t* out_slots;         // NULL: not wanted
+  int64_t* count;
+  int64_t* tiles;
+  int64_t capacity;           // the padded positions: n_tiles * 256
+  int64_t out_capacity;
+  int64_t n_tiles;
+  uint64_t cell_mask;
+  int32_t n_moves;            // 0: ids only
+  const Move* move;           // (never read)
+
+  // position p missed: it lies inside its run, holds an id the table could hold and the find did not see it
+  __device__ inline bool missed(int64_t p, long long* id) const {
+    int64_t off;
+    const Run& r = keys.run_of(p, &off);
+    if (off >= r.n_keys || r.slots[off] >= 0) return false;
+    *id = (long long)r.keys[off];
+    return holds_key(*id, true);
+  }
+  __device__ inline bool selected(int64_t p) const {
+    if (p >= capacity) return false;
+    long long id;
+    if (!missed(p, &id)) return false;
+    return first_position(set, first, cell_mask, id) == (int32_t)p;
+  }
+  __device__ void scanned() const {}
+};
+
+struct ColTable {
+  ColRec rec[kMaxColsPerLaunch];
+  int32_t n_runs;
+  int32_t pad_;
+  int32_t run_claim_start[kMaxRunsPerLaunch];  // the runs' first CLAIM tiles (1024 positions), one per lane of a ballot
+  Run run[kMaxRunsPerLaunch];
+
+  __device__ inline ColView operator[](int ci) const {
+    const ColRec& c = rec[ci];
+    return ColView{RunIds{this, c.tile_run, c.tile_first}, c.set, c.first, c.out_keys, nullptr, c.count, c.tiles,
+                   c.n_tiles * kSlotsPerTile, c.out_capacity, c.n_tiles, c.cell_mask, 0, nullptr};
+  }
+};
+
+// the run of position p of the column, recorded by the claim, and p's place in it.  The 64 positions of a wave
+// lie in one tile: the run is wave-uniform.
+__device__ inline const Run& RunIds::run_of(int64_t p, int64_t* off) const {
+  const int64_t tile = p / kSlotsPerTile;
+  const int ri = __builtin_amdgcn_readfirstlane(tile_run[tile]);
+  const Run& r = tab->run[ri];
+  *off = p - (int64_t)(r.first_tile - tile_first) * kSlotsPerTile;
+  return r;
+}
+
+struct MissRunsArgs {
+  int32_t n_cols;
+  int32_t tile_start[kMaxColsPerLaunch + 1];    // 256 positions per tile: count and write
+  ColTable col;
+};
+static_assert(sizeof(MissRunsArgs) <= 24576, "kernarg budget");
+
+// 16-byte stores: the cells of a call are a multiple of 64 and both arrays start 16-byte aligned
+__global__ __launch_bounds__(kBlock) void hash_missing_runs_clear_kernel(longlong2* set, int4* first, int64_t cells) {
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < (cells >> 1); i += stride) {
+    set[i] = make_longlong2(kEmptyKey, kEmptyKey);
+    if (i < (cells >> 2)) first[i] = make_int4(kNoPosition, kNoPosition, kNoPosition, kNoPosition);
+  }
+}
+
+// last run whose first claim tile is <= b (hash_insert.hip's find_run): up to four 64-wide ballots; every lane calls
+__device__ inline int find_run(const ColTable& t, int b) {
+  const int lane = lane_id();
+  int below = 0;
+#pragma unroll
+  for (int k = 0; k < kMaxRunsPerLaunch / kWave; ++k) {
+    if (k * kWave >= t.n_runs) break;   // (uniform)
+    const int i = k * kWave + lane;
+    const int t0 = i < t.n_runs ? t.run_claim_start[i] : 0x7fffffff;
+    below += (int)__builtin_popcountll(__ballot(t0 <= b));
+  }
+  return __builtin_amdgcn_readfirstlane(below - 1);
+}
+
+// A claim workgroup takes up to 1024 consecutive positions of ONE run -- four 256-position tiles -- and a wave walks
+// its four 64-position chunks in position order, as hash_missing.hip's claim does: the early occurrences of a hot
+// missed id have lowered first[] before the later ones read it.
+__global__ __launch_bounds__(kBlock) void hash_missing_runs_claim_kernel(const MissRunsArgs a) {
+  const int b = (int)blockIdx.x;
+  const int lane = lane_id();
+  const int wave = (int)(threadIdx.x >> 6);
+  const int ri = find_run(a.col, b);
+  const Run& r = a.col.run[ri];
+  const ColRec& c = a.col.rec[r.col];
+  const int64_t n_keys = r.n_keys;
+  const int64_t block_first = (int64_t)(b - a.col.run_claim_start[ri]) * kClaimPerBlock;   // in the run; < n_keys
+  const int64_t run_first = (int64_t)(r.first_tile - c.tile_first) * kSlotsPerTile;        // the run's first position
+  // the run of every 256-position tile this workgroup covers, for count and write: thread j records tile j
+  if (threadIdx.x < kChunks && block_first + (int64_t)threadIdx.x * kSlotsPerTile < n_keys) {
+    c.tile_run[(run_first + block_first) / kSlotsPerTile + threadIdx.x] = ri;
+  }
+#pragma unroll
+  for (int u = 0; u < kChunks; ++u) {
+    const int64_t first = block_first + (int64_t)(u * kWavesPerBlock + wave) * kWave;
+    if (first >= n_keys) break;   // (wave-uniform)
+    const int64_t off = first + lane;
+    long long id = kEmptyKey;
+    bool miss = false;
+    if (off < n_keys && r.slots[off] < 0) {
+      id = (long long)r.keys[off];
+      miss = holds_key(id, true);
+    }
+    if (__ballot(miss) == 0ull) continue;   // (wave-uniform) every id of the chunk is resident: no atomic
+    if (miss) claim_cell(c.set, c.first, c.cell_mask, id, (int32_t)(run_first + off));   // (positions < 2^31: checked)
+  }
+}
+
+// What the call reads of a column before any launch: its ids, its non-empty runs, its padded tiles and the tiles
+// of its find.  Negative: the column is out of range (the call refuses it; the workspace size counts nothing).
+struct Extent {
+  int64_t ids;
+  int64_t tiles;
+  int64_t find_tiles;
+  int32_t runs;
+};
+
+inline bool extent_of(int32_t slab_size, int32_t n_runs, const hbk_hash_run_t* runs, Extent* e) {
+  *e = Extent{0, 0, 0, 0};
+  if (n_runs < 0 || (n_runs > 0 && runs == nullptr)) return false;
+  const int64_t per_find_tile =
+      slab_size >= 1 && slab_size <= kWave ? (int64_t)(kBlock >> pow2_log2(slab_size)) * kFindKeysPerGroup : 1;
+  for (int32_t r = 0; r < n_runs; ++r) {
+    const int64_t n = runs[r].n_keys;
+    if (n < 0 || n >= (1ll << 31)) return false;
+    if (n == 0) continue;
+    e->ids += n;
+    e->tiles += tiles_of(n);
+    e->find_tiles += (n + per_find_tile - 1) / per_find_tile;
+    ++e->runs;
+  }
+  return e->ids < kKeyLimit && e->tiles * kSlotsPerTile < (1ll << 31) && e->runs <= kMaxRunsPerLaunch;
+}
+
+// the workspace: the sets of all columns, first[] of all columns, the tile counts of all columns, then tile_run[]
+struct Layout {
+  int64_t cells;
+  int64_t tiles;
+  size_t bytes() const {
+    return (size_t)cells * (sizeof(long long) + sizeof(int32_t)) + (size_t)tiles * (sizeof(int64_t) + sizeof(int32_t));
+  }
+};
+
+inline Layout layout_of(int32_t n_cols, const int32_t* n_runs, const hbk_hash_run_t* const* runs) {
+  Layout l = {0, 0};
+  if (n_runs == nullptr || runs == nullptr) return l;
+  for (int32_t c = 0; c < n_cols; ++c) {
+    Extent e;
+    if (!extent_of(1, n_runs[c], runs[c], &e) || e.ids == 0) continue;
+    l.cells += cells_of(e.ids);
+    l.tiles += e.tiles;
+  }
+  return l;
+}
+
+// the columns [c0, end) of the launch group that starts at c0: up to 32 columns with ids whose non-empty runs
+// number at most kMaxRunsPerLaunch together (extents: checked, so one column alone always fits)
+inline int32_t group_end(int32_t n_cols, const Extent* extents, int32_t c0) {
+  int32_t k = 0, nr = 0, c = c0;
+  for (; c < n_cols; ++c) {
+    if (extents[c].ids == 0) continue;
+    if (k == kMaxColsPerLaunch || nr + extents[c].runs > kMaxRunsPerLaunch) break;
+    ++k;
+    nr += extents[c].runs;
+  }
+  return c;
+}
+
+}  // namespace
+}  // namespace hbk
+
+extern "C" size_t hbk_hash_missing_runs_workspace_bytes(int32_t n_cols, const int32_t* n_runs,
+                                                        const hbk_hash_run_t* const* runs) {
+  return hbk::layout_of(n_cols, n_runs, runs).bytes();
+}
+
+extern "C" int hbk_hash_missing_runs_n(int32_t n_cols, const hbk_hash_missing_runs_column_t* cols,
+                                       const int32_t* n_runs, const hbk_hash_run_t* const* runs, void* workspace,
+                                       size_t workspace_bytes, hbk_stream_t stream_) {
+  using namespace hbk;
+  const char* who = "hash_missing_runs_n";
+  HBK_REQUIRE(n_cols >= 0, "%s: n_cols must be >= 0, got %d", who, n_cols);
+  HBK_REQUIRE(n_cols == 0 || cols != nullptr, "%s: cols is NULL", who);
+  HBK_REQUIRE(n_cols == 0 || (n_runs != nullptr && runs != nullptr), "%s: n_runs or runs is NULL", who);
+  std::vector<Extent> extents((size_t)n_cols);
+  for (int32_t c = 0; c < n_cols; ++c) {
+    const hbk_hash_missing_runs_column_t& h = cols[c];
+    if (int rc = check_geometry(who, c, "", "keys_cache", h.keys_cache, h.slab_count, h.slab_size)) return rc;
+    HBK_REQUIRE(h.exp.last_seen != nullptr, "%s: column %d: last_seen is NULL (expiring tables only)", who, c);
+    HBK_REQUIRE(h.exp.freq != nullptr, "%s: column %d: freq is NULL (expiring tables only)", who, c);
+    HBK_REQUIRE(h.count != nullptr, "%s: column %d: count is NULL", who, c);
+    HBK_REQUIRE(h.out_capacity >= 0, "%s: column %d: out_capacity must be >= 0, got %lld", who, c,
+                (long long)h.out_capacity);
+    HBK_REQUIRE(h.out_capacity == 0 || h.out_ids != nullptr, "%s: column %d: out_ids is NULL with out_capacity %lld",
+                who, c, (long long)h.out_capacity);
+    // the rules of hbk_hash_translate_runs_n for an expiring table's runs
+    HBK_REQUIRE(n_runs[c] >= 0, "%s: column %d: n_runs must be >= 0, got %d", who, c, n_runs[c]);
+    HBK_REQUIRE(n_runs[c] == 0 || runs[c] != nullptr, "%s: column %d: runs is NULL with n_runs = %d", who, c,
+                n_runs[c]);
+    for (int32_t r = 0; r < n_runs[c]; ++r) {
+      const hbk_hash_run_t& run = runs[c][r];
+      HBK_REQUIRE(run.n_keys >= 0 && run.n_keys < (1ll << 31),
+                  "%s: column %d: run %d: n_keys must be in [0, 2^31), got %lld", who, c, r, (long long)run.n_keys);
+      HBK_REQUIRE(run.n_keys == 0 || (run.keys != nullptr && run.slots != nullptr),
+                  "%s: column %d: run %d: NULL buffer (keys and slots are needed with n_keys > 0)", who, c, r);
+    }
+    Extent& e = extents[(size_t)c];
+    (void)extent_of(h.slab_size, n_runs[c], runs[c], &e);
+    HBK_REQUIRE(e.ids < kKeyLimit, "%s: column %d: the runs sum to %lld keys or more: must stay below 2^30 (the find "
+                "of an expiring table takes no more)", who, c, (long long)e.ids);
+    HBK_REQUIRE(e.tiles * kSlotsPerTile < (1ll << 31),
+                "%s: column %d: n_keys: the runs, each padded to whole tiles of %d, take %lld positions: must stay "
+                "below 2^31", who, c, kSlotsPerTile, (long long)(e.tiles * kSlotsPerTile));
+    HBK_REQUIRE(e.runs <= kMaxRunsPerLaunch, "%s: column %d: n_runs: %d non-empty runs, a launch takes at most %d",
+                who, c, e.runs, kMaxRunsPerLaunch);
+  }
+  // the find's grid of every launch group, before the first launch
+  for (int32_t c0 = 0; c0 < n_cols;) {
+    const int32_t c1 = group_end(n_cols, extents.data(), c0);
+    int64_t find_tiles = 0;
+    for (int32_t c = c0; c < c1; ++c) {
+      find_tiles += extents[(size_t)c].find_tiles;
+      HBK_REQUIRE(find_tiles < (1ll << 31),
+                  "%s: column %d: n_keys: the find of its launch group needs %lld tiles or more, a grid takes fewer "
+                  "than 2^31: name fewer ids per call", who, c, (long long)find_tiles);
+    }
+    c0 = c1;
+  }
+  const Layout layout = layout_of(n_cols, n_runs, runs);
+  const size_t need = layout.bytes();
+  if (need != 0) {
+    HBK_REQUIRE(workspace != nullptr, "%s: workspace is NULL (hbk_hash_missing_runs_workspace_bytes says how large: "
+                "%zu bytes)", who, need);
+    HBK_REQUIRE(((uintptr_t)workspace & 15) == 0, "%s: workspace must be 16-byte aligned", who);
+    HBK_REQUIRE(workspace_bytes >= need, "%s: workspace_bytes %zu is too small: %zu bytes are needed", who,
+                workspace_bytes, need);
+  }
+  hipStream_t stream = as_stream(stream_);
+  long long* sets = static_cast<long long*>(workspace);
+  int32_t* firsts = reinterpret_cast<int32_t*>(sets + layout.cells);      // (cells: a multiple of 64)
+  int64_t* tile_ws = reinterpret_cast<int64_t*>(firsts + layout.cells);
+  int32_t* tile_runs = reinterpret_cast<int32_t*>(tile_ws + layout.tiles);
+  if (layout.cells != 0) {
+    const int64_t blocks = ((layout.cells >> 1) + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(hash_missing_runs_clear_kernel, dim3((unsigned)(blocks < kClearBlocks ? blocks : kClearBlocks)),
+                       dim3(kBlock), 0, stream, reinterpret_cast<longlong2*>(sets), reinterpret_cast<int4*>(firsts),
+                       layout.cells);
+    HBK_HIP_OK(hipGetLastError());
+  }
+  for (int32_t c0 = 0; c0 < n_cols;) {
+    const int32_t c1 = group_end(n_cols, extents.data(), c0);
+    MissRunsArgs args;
+    hbk_hash_column_t find_cols[kMaxColsPerLaunch];
+    hbk_hash_expiry_t find_exp[kMaxColsPerLaunch];
+    int32_t find_n_runs[kMaxColsPerLaunch];
+    const hbk_hash_run_t* find_runs[kMaxColsPerLaunch];
+    int32_t k = 0, nr = 0;
+    int64_t tiles = 0, claim_tiles = 0;
+    args.tile_start[0] = 0;
+    for (int32_t c = c0; c < c1; ++c) {
+      const hbk_hash_missing_runs_column_t& h = cols[c];
+      const Extent& e = extents[(size_t)c];
+      if (e.ids == 0) {   // an empty id list misses nothing
+        HBK_HIP_OK(hipMemsetAsync(h.count, 0, sizeof(int64_t), stream));
+        continue;
+      }
+      // the find's column: the table as a translate sees it, no table rows, no counters
+      hbk_hash_column_t& f = find_cols[k];
+      f.keys_cache = const_cast<int64_t*>(h.keys_cache);
+      f.slab_count = h.slab_count;
+      f.slab_size = h.slab_size;
+      f.keys = nullptr;
+      f.n_keys = 0;
+      f.slots = nullptr;
+      f.counts = nullptr;
+      f.table = nullptr;
+      f.dim = 0;
+      f.table_pitch = 0;
+      f.init_scale = 0.0f;
+      f.seed = 0;
+      hbk_hash_expiry_t& x = find_exp[k];
+      x.last_seen = h.exp.last_seen;
+      x.freq = h.exp.freq;
+      x.step = h.exp.step != nullptr ? h.exp.step : h.exp.last_seen;   // (a find reads no step; its check asks for an address)
+      x.stats = nullptr;
+      find_n_runs[k] = n_runs[c];
+      find_runs[k] = runs[c];
+      const int64_t cells = cells_of(e.ids);
+      ColRec& d = args.col.rec[k];
+      d.set = sets;
+      d.first = firsts;
+      d.out_keys = reinterpret_cast<long long*>(h.out_ids);
+      d.count = h.count;
+      d.tiles = tile_ws;
+      d.tile_run = tile_runs;
+      d.out_capacity = h.out_capacity;
+      d.n_tiles = e.tiles;
+      d.cell_mask = (uint64_t)cells - 1;
+      d.tile_first = (int32_t)tiles;
+      d.pad_ = 0;
+      sets += cells;
+      firsts += cells;
+      tile_ws += e.tiles;
+      tile_runs += e.tiles;
+      for (int32_t r = 0; r < n_runs[c]; ++r) {
+        const hbk_hash_run_t& run = runs[c][r];
+        if (run.n_keys == 0) continue;
+        Run& o = args.col.run[nr];
+        o.keys = run.keys;
+        o.slots = run.slots;
+        o.n_keys = run.n_keys;
+        o.col = k;
+        o.first_tile = (int32_t)tiles;
+        args.col.run_claim_start[nr] = (int32_t)claim_tiles;
+        tiles += tiles_of(run.n_keys);                                   // (< 2^23 per column: 32 of them fit a grid)
+        claim_tiles += (run.n_keys + kClaimPerBlock - 1) / kClaimPerBlock;
+        ++nr;
+      }
+      ++k;
+      args.tile_start[k] = (int32_t)tiles;
+    }
+    c0 = c1;
+    if (k == 0) continue;
+    args.n_cols = k;
+    args.col.n_runs = nr;
+    args.col.pad_ = 0;
+    if (int rc = hbk_hash_translate_runs_n(k, find_cols, find_exp, nullptr, find_n_runs, find_runs, 0, stream_)) {
+      return rc;
+    }
+    hipLaunchKernelGGL(hash_missing_runs_claim_kernel, dim3((unsigned)claim_tiles), dim3(kBlock), 0, stream, args);
+    HBK_HIP_OK(hipGetLastError());
+    if (int rc = launch_pack(args, tiles, stream)) return rc;
+  }
+  return HBK_OK;
+}

@@ -622,8 +622,12 @@ struct hbk_sharded {
   // exchange, no stitch -- one random-row pass instead of two, and the rows cross the link as the
   // gather's own stores.
   // the forward in two halves (hbk_sharded_lookup_fwd_begin / _end): what the second half needs
-  bool fwd_open = false;    // _begin has run, _end has not
+  bool fwd_open = false;    // _begin (or _gather) has run, _end has not
+  bool ids_open = false;    // the forward in three parts: _ids has run, _gather has not
   bool fin_wire = false, fin_hop = false, fin_p2p = false;
+  bool fin_prefetched = false;
+  int32_t* fin_slot_send = nullptr;   // p2p form: the outgoing output slots of the open step
+  hbk::Buffer missing_ws;   // hbk_sharded_hash_missing's workspace
   int fin_use = 0;          // the PartSet of the open step
   std::chrono::steady_clock::time_point fin_t0;
   float fin_us[2] = {0.f, 0.f};
@@ -724,7 +728,7 @@ extern "C" int hbk_sharded_destroy(hbk_sharded_t p) {
   if (p->pre_stream) (void)hipStreamSynchronize(p->pre_stream);
   for (hbk::Buffer* b : {&p->part_ws, &p->ids_buf, &p->rows_buf, &p->wire_ws, &p->bwd_ws,
                          &p->runs_dev, &p->dedup_tmp, &p->slot_send, &p->slot_recv, &p->token_buf,
-                         &p->bind_buf, &p->slots_buf}) {
+                         &p->bind_buf, &p->slots_buf, &p->missing_ws}) {
     b->release();
   }
   for (void* m : p->ipc_opened) (void)hipIpcCloseMemHandle(m);
@@ -1169,6 +1173,16 @@ namespace {
 // Stage C of a plan with hash columns: the ids of the group's hash columns -> slots, one
 // hbk_hash_translate_runs_n per table kind and insert flag present.  ids_at(q, c): where run (q, c) of the group
 // lies (int64 ids); its slots go to the run's place in the layout of the received ids.
+// Where run (q, c) of the group's received ids lies: the own slice in the outgoing buffer when it stayed in place.
+// The rule of the owner gather, the translate and hbk_sharded_hash_missing.
+inline char* received_ids_at(const hbk_sharded* p, const Group& gr, int q, int c) {
+  const int ng = gr.c1 - gr.c0;
+  const int64_t id_bytes = p->id32 ? 4 : 8;
+  return p->zero_copy_self && q == p->rank
+             ? p->send_ids_p + (gr.id_send + gr.lay.req_id_off[(size_t)q * ng + c]) * id_bytes
+             : p->recv_ids_p + (gr.id_recv + gr.lay.own_id_off[(size_t)q * ng + c]) * id_bytes;
+}
+
 template <typename IdsAt>
 int translate_group(hbk_sharded* p, const Group& gr, IdsAt ids_at, int64_t* slots_base, hbk_stream_t stream) {
   const int W = p->W, ng = gr.c1 - gr.c0;
@@ -1258,7 +1272,7 @@ extern "C" int hbk_sharded_set_hash_tables(hbk_sharded_t p, const hbk_sharded_ha
   return HBK_OK;
 }
 
-// The forward in two halves.  _begin: everything up to and including the owner-side gather (partition
+// The forward in two halves, the first of them in two parts.  _begin = _ids + _gather: everything up to and including the owner-side gather (partition
 // or its prefetched result, the step's one host wait, id exchange, gather into the reply buffer --
 // in the p2p form into the requesters' outputs, with the token exchange).  _end: rows exchange +
 // stitch + combiner into `outs`.  hbk_sharded_lookup_fwd = _begin + _end.  Two plans that share
@@ -1266,14 +1280,21 @@ extern "C" int hbk_sharded_set_hash_tables(hbk_sharded_t p, const hbk_sharded_ha
 // of rows(i): plan B gathers while plan A's rows travel, plan A stitches while plan B's travel --
 // the overlap of exchanges with the local gather across STEPS (forward-only use: nothing may change
 // the tables between a step's _begin and its _end).
-extern "C" int hbk_sharded_lookup_fwd_begin(hbk_sharded_t p, const int64_t* const* ids,
-                                            const int64_t* n_ids,
-                                            const int32_t* const* row_splits,
-                                            const int64_t* n_segments, hbk_stream_t stream_) {
-  using namespace hbk;
+//   _ids     everything through stage B: partition or a matching prefetch, the step's one host wait, layouts, run
+//            tables, pack and the id exchanges of all groups.  The received ids then lie in the exchange buffers
+//            (stream-ordered; in the hopped form behind the groups' id-exchange events).
+//   _gather  stage C: translate (hash columns), owner gather and, in the hopped form, the events.
+// Between the two, hbk_sharded_hash_missing asks which of the received ids the hash tables do not hold, and the
+// caller may change the tables in ways that move no tensor, stream-ordered on the step's stream.
+namespace hbk {
+namespace {
+
+int fwd_ids(hbk_sharded_t p, const int64_t* const* ids, const int64_t* n_ids, const int32_t* const* row_splits,
+            const int64_t* n_segments, hbk_stream_t stream_) {
   HBK_REQUIRE(p != nullptr, "sharded_lookup_fwd: plan is NULL");
   HBK_REQUIRE(ids && n_ids, "sharded_lookup_fwd: NULL argument array");
   p->fwd_open = false;
+  p->ids_open = false;
   p->rows_live = false;   // (the exchange buffers are about to be laid out again)
   hipStream_t stream = as_stream(stream_);
   const int N = p->N, W = p->W;
@@ -1295,8 +1316,6 @@ extern "C" int hbk_sharded_lookup_fwd_begin(hbk_sharded_t p, const int64_t* cons
     }
   }
   int rc;
-  // option sharded_trace: host-side time of the step's phases on stderr (us)
-  const bool trace = p->trace;
   auto now = [] { return std::chrono::steady_clock::now(); };
   auto us_since = [](std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
@@ -1445,7 +1464,6 @@ extern "C" int hbk_sharded_lookup_fwd_begin(hbk_sharded_t p, const int64_t* cons
   if ((rc = p->runs_dev.ensure(sizeof(int64_t) * 7 * (size_t)N * W)) != HBK_OK) return rc;
   const bool any_hash = p->any_hash;   // (never with p2p: hbk_sharded_set_hash_tables, hbk_sharded_p2p_bind)
   if (any_hash && (rc = p->slots_buf.ensure((size_t)tot_own_ids * 8 + 16)) != HBK_OK) return rc;
-  int64_t* const slots_base = reinterpret_cast<int64_t*>(p->slots_buf.ptr);
   if (p2p) {
     if ((rc = p->slot_send.ensure((size_t)tot_req_ids * 4 + 16)) != HBK_OK) return rc;
     if ((rc = p->slot_recv.ensure((size_t)tot_own_ids * 4 + 16)) != HBK_OK) return rc;
@@ -1453,10 +1471,7 @@ extern "C" int hbk_sharded_lookup_fwd_begin(hbk_sharded_t p, const int64_t* cons
   }
   char* ids_send_base = p->send_ids_p;
   char* ids_recv_base = p->recv_ids_p;
-  float* rows_send_base = p->send_rows_p;
-  float* rows_recv_base = p->recv_rows_p;
   const bool zc = p->zero_copy_self;
-  const bool half = p->fused_half;   // fp16 rows in the exchange buffers of the forward
   const int me = p->rank;
   // element offsets of the "other side" buffers seen from the owner-side bases of the backward
   const int64_t ids_send_from_recv = (p->send_ids_p - p->recv_ids_p) / (int64_t)id_bytes;
@@ -1602,19 +1617,43 @@ extern "C" int hbk_sharded_lookup_fwd_begin(hbk_sharded_t p, const int64_t* cons
       if (rc != HBK_OK) return rc;
     }
   }
-  // stage C: owner gather of group g as soon as its ids are in (N_g * W virtual columns, straight
-  // into the peer-major reply), then its rows go on the wire
+  // the rest of the first half (translate, owner gather) is fwd_gather
+  p->fin_wire = wire;
+  p->fin_hop = hop;
+  p->fin_p2p = p2p;
+  p->fin_use = use;
+  p->fin_t0 = t_begin;
+  p->fin_us[0] = (float)t_enq1;
+  p->fin_us[1] = (float)(t_sync - t_enq1);
+  p->fin_prefetched = prefetched;
+  p->fin_slot_send = slot_send;
+  p->ids_open = true;
+  return HBK_OK;
+}
+
+// stage C: owner gather of group g as soon as its ids are in (N_g * W virtual columns, straight
+// into the peer-major reply), then its rows go on the wire
+int fwd_gather(hbk_sharded_t p, hbk_stream_t stream_) {
+  p->ids_open = false;
+  hipStream_t stream = as_stream(stream_);
+  const int N = p->N, W = p->W, me = p->rank;
+  const bool wire = p->fin_wire, hop = p->fin_hop, p2p = p->fin_p2p;
+  const bool zc = p->zero_copy_self, half = p->fused_half, any_hash = p->any_hash;
+  const int32_t id_dtype = p->id32 ? HBK_INT32 : HBK_INT64;
+  const std::vector<Group>& groups = p->groups;
+  const int G = (int)groups.size();
+  int64_t* const slots_base = reinterpret_cast<int64_t*>(p->slots_buf.ptr);
+  int32_t* const slot_send = p->fin_slot_send;
+  int32_t* const slot_recv = reinterpret_cast<int32_t*>(p->slot_recv.ptr);
+  float* const rows_send_base = p->send_rows_p;
+  float* const rows_recv_base = p->recv_rows_p;
+  int rc;
   for (int g = 0; g < G; ++g) {
     const Group& gr = groups[g];
     const int ng = gr.c1 - gr.c0;
     if (hop) HBK_HIP_OK(hipStreamWaitEvent(stream, p->ev[1][g], 0));
     if (hop && p2p) HBK_HIP_OK(hipStreamWaitEvent(stream, p->ev[3][0], 0));
-    // where run (q, c) of the group's received ids lies: the own slice in the outgoing buffer when it stayed
-    auto run_ids = [&](int q, int c) {
-      return zc && q == me
-                 ? ids_send_base + (gr.id_send + gr.lay.req_id_off[(size_t)q * ng + c]) * id_bytes
-                 : ids_recv_base + (gr.id_recv + gr.lay.own_id_off[(size_t)q * ng + c]) * id_bytes;
-    };
+    auto run_ids = [&](int q, int c) { return received_ids_at(p, gr, q, c); };
     if (any_hash && (rc = translate_group(p, gr, run_ids, slots_base, stream_)) != HBK_OK) return rc;
     std::vector<hbk_lookup_column_t> v;
     std::vector<float> clip;   // the owner clips: every virtual column carries its column's max_norm
@@ -1685,27 +1724,125 @@ extern "C" int hbk_sharded_lookup_fwd_begin(hbk_sharded_t p, const int64_t* cons
     }
   }
   // the second half (rows exchange, stitch + combiner) is hbk_sharded_lookup_fwd_end
-  p->fin_wire = wire;
-  p->fin_hop = hop;
-  p->fin_p2p = p2p;
-  p->fin_use = use;
-  p->fin_t0 = t_begin;
-  p->fin_us[0] = (float)t_enq1;
-  p->fin_us[1] = (float)(t_sync - t_enq1);
   p->fwd_open = true;
-  if (trace) {
+  if (p->trace) {
+    const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - p->fin_t0).count();
     fprintf(stderr, "hbk_sharded_lookup_fwd_begin host us: enqueue partition+sizes %.1f, sync wait "
                     "%.1f, enqueue through the gather %.1f (G = %d, W = %d%s%s)\n",
-            t_enq1, t_sync - t_enq1, us_since(t_begin) - t_sync, G, W,
-            prefetched ? ", partition prefetched" : "", p2p ? ", p2p" : "");
+            (double)p->fin_us[0], (double)p->fin_us[1], us - p->fin_us[0] - p->fin_us[1], G, W,
+            p->fin_prefetched ? ", partition prefetched" : "", p2p ? ", p2p" : "");
   }
   return HBK_OK;
+}
+
+}  // namespace
+}  // namespace hbk
+
+extern "C" int hbk_sharded_lookup_fwd_begin(hbk_sharded_t p, const int64_t* const* ids,
+                                            const int64_t* n_ids,
+                                            const int32_t* const* row_splits,
+                                            const int64_t* n_segments, hbk_stream_t stream_) {
+  const int rc = hbk::fwd_ids(p, ids, n_ids, row_splits, n_segments, stream_);
+  if (rc != HBK_OK) return rc;
+  return hbk::fwd_gather(p, stream_);
+}
+
+extern "C" int hbk_sharded_lookup_fwd_ids(hbk_sharded_t p, const int64_t* const* ids, const int64_t* n_ids,
+                                          const int32_t* const* row_splits, const int64_t* n_segments,
+                                          hbk_stream_t stream_) {
+  using namespace hbk;
+  HBK_REQUIRE(p != nullptr, "sharded_lookup_fwd_ids: plan is NULL");
+  if (p->p2p_bound) {
+    p->fwd_open = p->ids_open = false;
+    return fail(HBK_UNIMPLEMENTED, "sharded_lookup_fwd_ids: the plan is p2p-bound (hbk_sharded_p2p_bind): the p2p "
+                "form has no forward in three parts");
+  }
+  return fwd_ids(p, ids, n_ids, row_splits, n_segments, stream_);
+}
+
+extern "C" int hbk_sharded_lookup_fwd_gather(hbk_sharded_t p, hbk_stream_t stream_) {
+  using namespace hbk;
+  HBK_REQUIRE(p != nullptr, "sharded_lookup_fwd_gather: plan is NULL");
+  HBK_REQUIRE(p->ids_open, "sharded_lookup_fwd_gather: no step is open (hbk_sharded_lookup_fwd_ids)");
+  return fwd_gather(p, stream_);
+}
+
+// Between _ids and _gather: the distinct received ids of the wanted hash columns that their tables do not hold, in
+// the order of their first occurrence in the column's W runs, peer after peer -- hbk_hash_missing_runs_n over the
+// runs where translate_group will read them.  The find's answers go to the plan's slot buffer, which the translate
+// overwrites.  No host synchronisation.
+extern "C" int hbk_sharded_hash_missing(hbk_sharded_t p, const uint8_t* want, int64_t* const* out_ids,
+                                        const int64_t* out_capacity, int64_t* counts, hbk_stream_t stream_) {
+  using namespace hbk;
+  const char* who = "sharded_hash_missing";
+  HBK_REQUIRE(p != nullptr, "%s: plan is NULL", who);
+  if (p->p2p_bound) {
+    return fail(HBK_UNIMPLEMENTED, "%s: the plan is p2p-bound (hbk_sharded_p2p_bind): the p2p form has no "
+                "owner-side translate", who);
+  }
+  HBK_REQUIRE(p->ids_open, "%s: no step is open: valid only between hbk_sharded_lookup_fwd_ids and "
+              "hbk_sharded_lookup_fwd_gather", who);
+  HBK_REQUIRE(want != nullptr, "%s: want is NULL", who);
+  const int N = p->N, W = p->W;
+  int n_want = 0;
+  for (int c = 0; c < N; ++c) {
+    if (want[c] == 0) continue;
+    HBK_REQUIRE(p->any_hash && p->hash[(size_t)c].keys_cache != nullptr && p->hash[(size_t)c].exp.last_seen != nullptr,
+                "%s: column %d: want: not a hash column with an expiring table (hbk_sharded_set_hash_tables)", who, c);
+    HBK_REQUIRE(out_ids != nullptr && out_capacity != nullptr && counts != nullptr,
+                "%s: NULL argument array (out_ids, out_capacity and counts are needed with a wanted column)", who);
+    ++n_want;
+  }
+  if (n_want == 0) return HBK_OK;
+  hipStream_t stream = as_stream(stream_);
+  int64_t* const slots_base = reinterpret_cast<int64_t*>(p->slots_buf.ptr);
+  std::vector<hbk_hash_missing_runs_column_t> cols;
+  std::vector<hbk_hash_run_t> runs((size_t)n_want * W);
+  std::vector<const hbk_hash_run_t*> run_ptrs;
+  std::vector<int32_t> n_runs((size_t)n_want, W);
+  for (size_t g = 0; g < p->groups.size(); ++g) {
+    const Group& gr = p->groups[g];
+    const int ng = gr.c1 - gr.c0;
+    bool waited = false;
+    for (int c = 0; c < ng; ++c) {
+      const int cc = gr.c0 + c;
+      if (want[cc] == 0) continue;
+      if (p->fin_hop && !waited) {   // the group's ids are in
+        HBK_HIP_OK(hipStreamWaitEvent(stream, p->ev[1][g], 0));
+        waited = true;
+      }
+      const hbk_sharded_hash_t& t = p->hash[(size_t)cc];
+      hbk_hash_missing_runs_column_t h;
+      memset(&h, 0, sizeof(h));
+      h.keys_cache = t.keys_cache;
+      h.slab_count = t.slab_count;
+      h.slab_size = t.slab_size;
+      h.exp = t.exp;
+      h.out_ids = out_ids[cc];
+      h.out_capacity = out_capacity[cc];
+      h.count = counts + cc;
+      hbk_hash_run_t* r = runs.data() + cols.size() * (size_t)W;
+      for (int q = 0; q < W; ++q) {
+        r[q].n_keys = gr.R[(size_t)q * ng + c];
+        r[q].keys = reinterpret_cast<const int64_t*>(received_ids_at(p, gr, q, c));
+        r[q].slots = slots_base + gr.id_recv + gr.lay.own_id_off[(size_t)q * ng + c];
+      }
+      run_ptrs.push_back(r);
+      cols.push_back(h);
+    }
+  }
+  const size_t need = hbk_hash_missing_runs_workspace_bytes(n_want, n_runs.data(), run_ptrs.data());
+  if (int rc = p->missing_ws.ensure(need + 16)) return rc;
+  return hbk_hash_missing_runs_n(n_want, cols.data(), n_runs.data(), run_ptrs.data(), p->missing_ws.ptr,
+                                 p->missing_ws.bytes, stream_);
 }
 
 extern "C" int hbk_sharded_lookup_fwd_end(hbk_sharded_t p, float* const* outs,
                                           const int32_t* out_strides, hbk_stream_t stream_) {
   using namespace hbk;
   HBK_REQUIRE(p != nullptr && outs != nullptr, "sharded_lookup_fwd_end: NULL argument");
+  HBK_REQUIRE(!p->ids_open, "sharded_lookup_fwd_end: the open step has not gathered yet: "
+              "hbk_sharded_lookup_fwd_gather comes before hbk_sharded_lookup_fwd_end");
   HBK_REQUIRE(p->fwd_open, "sharded_lookup_fwd_end: no step is open (hbk_sharded_lookup_fwd_begin)");
   p->fwd_open = false;
   hipStream_t stream = as_stream(stream_);
@@ -2387,9 +2524,9 @@ extern "C" int hbk_sharded_last_host_us(hbk_sharded_t p, float* out3) {
 }
 
 // capacity the caller needs for the backward outputs of column c (rows this rank owns that
-// were requested in the last forward step)
+// were requested in the last forward step; valid from hbk_sharded_lookup_fwd_ids on)
 extern "C" int64_t hbk_sharded_owned_ids(hbk_sharded_t p, int32_t column) {
-  if (p == nullptr || !p->have_step || column < 0 || column >= p->N) return -1;
+  if (p == nullptr || !(p->have_step || p->ids_open || p->fwd_open) || column < 0 || column >= p->N) return -1;
   int64_t n = 0;
   for (int q = 0; q < p->W; ++q) n += p->recv_sizes[(size_t)q * p->N + column];
   return n;

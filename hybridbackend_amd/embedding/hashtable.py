@@ -64,6 +64,7 @@ HashEmbeddingColumn`` / ``HashSequenceEmbeddingColumn``.)
 """
 import ctypes as C
 import math
+import threading
 
 import torch
 
@@ -1043,6 +1044,8 @@ def _describe_sweep(col, t, keep_freq, pairs):
 
 _EVICT_TO_WORKSPACES = {}   # (device, n_tables) -> int32 scratch: the same address at every call, so a captured call replays
 _EVICT_TO_LFU_WORKSPACES = {}   # the same for order='lfu'
+_MAX_SELECT_WORKSPACES = 64     # entries of either: (device, tables, stream) -> scratch, the least recently used leaves
+_SELECT_LOCK = threading.Lock()
 
 # order -> (words of a report, the C entries of the sweep, of the select and of the workspace size, the scratch)
 _EVICT_TO_ORDERS = {
@@ -1123,9 +1126,16 @@ def _evict_to(tables, max_sizes, keep_freq, slots, reports, what, order):
     cols[c].max_size = max_sizes[c]
     cols[c].report = reports[c].data_ptr()
   nbytes = getattr(lib, size_entry)(n)
-  workspace = workspaces.get((dev, n))
-  if workspace is None or workspace.numel() * 4 < nbytes:
-    workspace = workspaces[(dev, n)] = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=dev)
+  # (kept per stream: two streams of one process -- the ranks of an in-process world -- select side by side; at
+  # most _MAX_SELECT_WORKSPACES entries, the oldest leaves: a process that makes streams as it goes does not grow it)
+  slot = (dev, n, torch.cuda.current_stream(dev).cuda_stream)
+  with _SELECT_LOCK:
+    workspace = workspaces.pop(slot, None)
+    if workspace is None or workspace.numel() * 4 < nbytes:
+      workspace = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=dev)
+    workspaces[slot] = workspace                 # (the newest entry: dicts keep insertion order)
+    while len(workspaces) > _MAX_SELECT_WORKSPACES:
+      workspaces.pop(next(iter(workspaces)))
   before = _keys_before(tables) if what == 'evict_to' else None   # (the select writes nothing)
   _lib.check(call(n, cols, workspace.data_ptr(), workspace.numel() * 4, _lib.current_stream(dev)))
   _record_swept(tables, before)
@@ -1555,23 +1565,27 @@ def hash_fault_in(tables, ids_list, stores, slots=None, row_splits=None, max_len
     return restored
   missed, _ = _missing([tables[c] for c in live], [ids_list[c] for c in live],
                        None if seq is None else tuple([x[c] for c in live] for x in seq))
-  sizes = [m.numel() for m in missed]
-  if sum(sizes) == 0:
+  if sum(m.numel() for m in missed) == 0:
     return restored
-  # ascending per table before they leave the device (two stable sorts over all tables' ids at once): `take` orders
-  # its keys on the host, where an ordered list is the cheaper one (profiles/hash_fault_in.txt: 29.4 -> 25.7 ms at
-  # 10 % missed)
+  for c, m in zip(live, missed_to_host(missed)):
+    if m.numel():
+      restored[c] = _restore(tables[c], stores[c], m, slots[c])
+  return restored
+
+
+def missed_to_host(missed):
+  """The missed ids of several tables (device vectors) as CPU vectors, each ascending, in ONE copy: ordered per
+  table before they leave the device (two stable sorts over all tables' ids at once) -- ``take`` orders its keys on
+  the host, where an ordered list is the cheaper one (profiles/hash_fault_in.txt: 29.4 -> 25.7 ms at 10 %
+  missed)."""
+  sizes = [m.numel() for m in missed]
   flat = missed[0] if len(missed) == 1 else torch.cat(missed)
   order = torch.argsort(flat, stable=True)
   if len(missed) > 1:
     owner = torch.repeat_interleave(torch.arange(len(missed), device=flat.device),
                                     torch.tensor(sizes, device=flat.device), output_size=flat.numel())
     order = order[torch.argsort(owner[order], stable=True)]
-  host = torch.split(flat[order].cpu(), sizes)   # the one copy
-  for c, m in zip(live, host):
-    if m.numel():
-      restored[c] = _restore(tables[c], stores[c], m, slots[c])
-  return restored
+  return torch.split(flat[order].cpu(), sizes)   # the one copy
 
 
 def _check_loads(max_load, target_load):

@@ -348,16 +348,7 @@ class ShardedGroupLookup:
     """Enqueue a bound step on the current stream; returns its outputs."""
     self._keep = bound.keep
     self._last_shapes = bound.shapes   # what backward() differentiates
-    st = self._auto_state
-    if st is not None and st[3] and st[1].query():
-      # the last backward's counts have landed: distinct local rows < half the ids asked for ->
-      # the owner gather stages repeated rows in LDS from this step on (and stops when not)
-      st[3] = False
-      counts = st[0].tolist()
-      for c in self._auto_hot:
-        self.hot_rows[c] = st[2][c] > 0 and 2 * counts[c] < st[2][c]
-      _lib.check(self._lib.hbk_sharded_set_hot_rows(
-        self._plan(), (C.c_int32 * len(self.hot_rows))(*[int(h) for h in self.hot_rows])))
+    self._refresh_hot_rows()
     if bound.weights is None:
       self._keep_weights = None
       _lib.check(self._lib.hbk_sharded_lookup_fwd(
@@ -369,6 +360,19 @@ class ShardedGroupLookup:
         self._plan(), a[0], a[1], a[2], a[3], bound.weights[0], a[4], a[5],
         _lib.current_stream(self.device)))
     return bound.outs
+
+  def _refresh_hot_rows(self):
+    """``hot_rows='auto'``, at the start of a step: the last backward's counts, once they have landed."""
+    st = self._auto_state
+    if st is not None and st[3] and st[1].query():
+      # the last backward's counts have landed: distinct local rows < half the ids asked for ->
+      # the owner gather stages repeated rows in LDS from this step on (and stops when not)
+      st[3] = False
+      counts = st[0].tolist()
+      for c in self._auto_hot:
+        self.hot_rows[c] = st[2][c] > 0 and 2 * counts[c] < st[2][c]
+      _lib.check(self._lib.hbk_sharded_set_hot_rows(
+        self._plan(), (C.c_int32 * len(self.hot_rows))(*[int(h) for h in self.hot_rows])))
 
   def prefetch_on_current_stream(self, bound):
     """``prefetch`` without a stream of the plan's own (``hbk_sharded_prefetch_on``): the partition +
@@ -390,6 +394,24 @@ class ShardedGroupLookup:
     a = bound.args
     _lib.check(self._lib.hbk_sharded_lookup_fwd_begin(
       self._plan(), a[0], a[1], a[2], a[3], _lib.current_stream(self.device)))
+
+  def launch_ids(self, bound):
+    """``launch_begin`` in two parts, the first (``hbk_sharded_lookup_fwd_ids``): partition (or its prefetched
+    result), the one host wait and the id exchanges -- the ids this rank owns then lie in the plan's exchange
+    buffers.  ``launch_gather`` and ``launch_end`` finish the step; between this call and ``launch_gather`` the
+    tables may change in ways that move no tensor, on the current stream.  Not on a p2p-bound object."""
+    _refuse_weights(bound, 'launch_ids / launch_gather / launch_end')
+    self._keep_weights = None
+    self._keep = bound.keep
+    self._last_shapes = bound.shapes
+    a = bound.args
+    _lib.check(self._lib.hbk_sharded_lookup_fwd_ids(
+      self._plan(), a[0], a[1], a[2], a[3], _lib.current_stream(self.device)))
+
+  def launch_gather(self, bound):   # pylint: disable=unused-argument
+    """The second part of ``launch_begin`` (``hbk_sharded_lookup_fwd_gather``): the owner side -- the translate of
+    hash columns and the gather of the rows.  ``launch_end`` finishes the step."""
+    _lib.check(self._lib.hbk_sharded_lookup_fwd_gather(self._plan(), _lib.current_stream(self.device)))
 
   def launch_end(self, bound):
     """Second half (``hbk_sharded_lookup_fwd_end``): rows exchange, stitch + combiner; returns the

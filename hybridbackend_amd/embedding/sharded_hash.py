@@ -7,8 +7,14 @@ Every rank holds one :class:`HashTable` per column.  An id belongs to rank ``flo
 numbers of its table (one ``hbk_hash_translate_runs_n`` call per table kind, over the W runs where they lie),
 gathers those rows, and in the backward reduces and steps them -- everything else of the step is
 :class:`ShardedGroupLookup`'s, unchanged.
+
+A bounded table keeps its state in a host tier (``stores``): the forward then runs in three parts, and between the id
+exchange and the owner's translate the keys this rank received and spilled earlier come back from their stores
+(``hbk_sharded_hash_missing``, :meth:`ShardedHashGroupLookup.fault_in_received`).
 """
 import ctypes as C
+
+import torch
 
 from hybridbackend_amd import _lib
 from hybridbackend_amd.embedding import hashtable as _ht
@@ -54,6 +60,14 @@ class ShardedHashGroupLookup(ShardedGroupLookup):
       :class:`ShardedGroupLookup`; row_accums, rowwise_adagrad: row-wise Adagrad's, ``[capacity, 1]`` each.
     initial_accumulator_value: what :meth:`maybe_grow` fills the rows of a grown Adagrad accumulator with that no
       key holds (FTRL's comes from ``ftrl``).
+    stores: None, or per column a :class:`HashSpillStore` or None -- the host tier of this rank's table (an
+      expiring one), of the table's dim and the widths of the bound optimizer slots in the order of ``slot_kinds``.
+      With stores a forward (``__call__`` / ``launch``) is :meth:`launch_ids`, :meth:`fault_in_received`,
+      :meth:`launch_gather`, :meth:`launch_end`: the keys this rank receives come back from their stores with rows,
+      metadata and optimizer slots before the translate could insert fresh rows for them, with ``train=False`` as
+      well (nothing is inserted that a store does not hold).  :meth:`spill_to` bounds the tables into the stores.
+      Such a forward reads the host (the counts of the missed ids), so it is NOT capturable: ``launch`` raises while
+      the current stream is capturing.  ``stores=None`` issues exactly the calls of a driver without a host tier.
 
   ``__call__``, ``bind``, ``launch``, ``backward``, ``prefetch`` and ``close`` are inherited; in the slices
   ``backward`` returns, ``unique_rows`` are slot numbers of this rank's tables (``tables[c].keys[unique_rows]``
@@ -64,7 +78,7 @@ class ShardedHashGroupLookup(ShardedGroupLookup):
 
   def __init__(self, tables, coll, combiners='sum', wire_dtype=None, dedup=False, max_norms=None, train=True,
                accums=None, moments=None, adam=None, ftrl_slots=None, ftrl=None, hot_rows=False, world_size=None,
-               initial_accumulator_value=0.1, row_accums=None, rowwise_adagrad=None):
+               initial_accumulator_value=0.1, row_accums=None, rowwise_adagrad=None, stores=None):
     self.tables = list(tables)
     _ht.same_device(self.tables)
     self.train = bool(train)
@@ -74,6 +88,28 @@ class ShardedHashGroupLookup(ShardedGroupLookup):
                      world_size=world_size, accums=accums, hot_rows=hot_rows, dedup=dedup, moments=moments, adam=adam,
                      ftrl_slots=ftrl_slots, ftrl=ftrl, max_norms=max_norms, row_accums=row_accums,
                      rowwise_adagrad=rowwise_adagrad)
+    self.stores = None if stores is None else list(stores)
+    self.last_restored = [0] * len(self.tables)
+    try:
+      self._check_stores()
+    except _lib.HbkError:
+      self.close()
+      raise
+
+  def _check_stores(self):
+    """Every store fits its table and the bound optimizer slots (in the one order of ``slot_kinds``)."""
+    if self.stores is None:
+      return
+    if len(self.stores) != len(self.tables):
+      raise _ht._bad(f'stores: expected one spill store (or None) per table, {len(self.tables)}, got '   # pylint: disable=protected-access
+                     f'{len(self.stores)}')
+    for c, (t, st) in enumerate(zip(self.tables, self.stores)):
+      if st is None:
+        continue
+      if not t.expiring:
+        raise _ht._bad(f'stores[{c}]: a spill store needs a table built with expiring=True (what leaves a plain '   # pylint: disable=protected-access
+                       'table leaves no TOMBSTONE behind)')
+      _ht._check_store(st, t, self._companions(c))   # pylint: disable=protected-access
 
   def _current(self):
     _ht.check_current(self.tables, self._rows)
@@ -139,6 +175,7 @@ class ShardedHashGroupLookup(ShardedGroupLookup):
       setattr(self, cls.name, getattr(new, cls.name))
     self._call_cache = self._keep = self._auto_state = None
     self._setup()
+    self._check_stores()
 
   def _slot_kinds(self):
     """The bound optimizer slots as (attribute, index in a pair or None, fill value), in the order every method
@@ -179,11 +216,112 @@ class ShardedHashGroupLookup(ShardedGroupLookup):
 
   def remove(self, ids_list):
     """:func:`hash_remove` on this rank's tables: the ids of ``ids_list[c]`` this rank's table c holds leave it,
-    the bound optimizer slots reset as companions with the fill values of :meth:`maybe_grow`.  Local to the rank:
-    ids the rank does not own are simply not found, there is no exchange, and ranks need not agree.  The tensors
-    stay where they are, so the plan stays valid.  Returns the old slots per table."""
+    the bound optimizer slots reset as companions with the fill values of :meth:`maybe_grow`; with ``stores`` they
+    are discarded from the stores too.  Local to the rank: ids the rank does not own are simply not found, there is
+    no exchange, and ranks need not agree.  The tensors stay where they are, so the plan stays valid.  Returns the
+    old slots per table."""
     self._current()
-    return _ht.hash_remove(self.tables, ids_list, [self._companions(c) for c in range(len(self.tables))])
+    companions = [self._companions(c) for c in range(len(self.tables))]
+    if self.stores is None:
+      return _ht.hash_remove(self.tables, ids_list, companions)
+    return _ht.remove_tables(self.tables, ids_list, companions, self.stores)
+
+  # ---- the host tier inside the step ------------------------------------------------------------------------
+  def _tiered(self):
+    """The columns that have a store."""
+    return [c for c, st in enumerate(self.stores or ()) if st is not None]
+
+  def launch(self, bound):
+    """Enqueue a bound step on the current stream; returns its outputs.  With ``stores``: :meth:`launch_ids`,
+    :meth:`fault_in_received`, :meth:`launch_gather`, ``launch_end`` -- not capturable.  No rank leaves a
+    collective half-made: when a table is too full for the keys its store gave back, they return to the store, the
+    step is finished as every other rank finishes it, and only then the error is raised (that refusal alone is
+    deferred: any other error of the fault-in leaves at once)."""
+    if self.stores is None:
+      return super().launch(bound)
+    if torch.cuda.is_current_stream_capturing():
+      raise _lib.HbkError(_lib.INTERNAL, 'launch: a forward with spill stores reads the host (the counts of the '
+                          'missed ids): it cannot be captured into a graph')
+    self._refresh_hot_rows()
+    self.launch_ids(bound)
+    error = None
+    try:
+      self.fault_in_received()
+    except _lib.InvalidArgumentError as e:   # (a table too full: every other error leaves at once)
+      error = e
+    self.launch_gather(bound)
+    outs = self.launch_end(bound)
+    if error is not None:
+      raise error
+    return outs
+
+  def launch_begin(self, bound):
+    """``ShardedGroupLookup.launch_begin``; refused on a driver with stores: the one-call first half translates
+    before anything could come back from a store, and a spilled key would get a fresh row beside its stored one.
+    Use :meth:`launch_ids`, :meth:`fault_in_received`, :meth:`launch_gather`."""
+    if self.stores is not None:
+      raise _lib.HbkError(_lib.UNIMPLEMENTED, 'launch_begin: a driver with spill stores runs its first half as '
+                          'launch_ids, fault_in_received, launch_gather')
+    super().launch_begin(bound)
+
+  def fault_in_received(self):
+    """Between :meth:`launch_ids` and :meth:`launch_gather`: the keys among the ids this rank received that its
+    stores hold come back into the tables -- rows, ``last_seen``, ``freq`` and the bound optimizer slots as they
+    left -- so that the translate finds them.  Columns whose store is empty are not asked; when none is left there
+    is no launch and no host read.  Otherwise ONE ``hbk_sharded_hash_missing`` call, ONE host read of the counts,
+    the missed ids ordered per column on the device and copied to the host in ONE copy (as :func:`hash_fault_in`),
+    then per column ``store.take`` and ``import_items(..., assume_distinct=True)``.  When a table is too full for
+    the taken keys they go back into its store before the error is raised; the columns after it have not been
+    taken from.  Local to the rank: no exchange, and ranks need not agree on whether anything was missed.  Returns
+    the keys restored per column (also ``last_restored``)."""
+    n = len(self.tables)
+    self.last_restored = restored = [0] * n
+    live = [c for c in self._tiered() if len(self.stores[c])]
+    if not live:
+      return restored
+    self._current()
+    plan = self._plan()
+    caps = [0] * n
+    for c in live:
+      caps[c] = max(int(self._lib.hbk_sharded_owned_ids(plan, c)), 0)
+    outs = torch.split(torch.empty(max(sum(caps), 1), dtype=torch.int64, device=self.device)[:sum(caps)], caps)
+    counts = torch.zeros(n, dtype=torch.int64, device=self.device)
+    want = (C.c_uint8 * n)(*[1 if caps[c] else 0 for c in range(n)])
+    _lib.check(self._lib.hbk_sharded_hash_missing(
+      plan, want, _lib.ptr_array([o.data_ptr() if k else None for o, k in zip(outs, caps)]), _lib.i64_array(caps),
+      counts.data_ptr(), _lib.current_stream(self.device)))
+    found = counts.tolist()   # the one host read
+    live = [c for c in live if found[c]]
+    if not live:
+      return restored
+    for c, m in zip(live, _ht.missed_to_host([outs[c][:found[c]] for c in live])):
+      restored[c] = _ht._restore(self.tables[c], self.stores[c], m, self._companions(c))   # pylint: disable=protected-access
+    return restored
+
+  def spill_to(self, max_sizes, keep_freq=0, order='lru'):
+    """:func:`hash_spill` on the columns that have a store: the keys ``evict_to(max_sizes[c])`` would evict leave
+    table c WITH their rows, metadata and the bound optimizer slots (companions with the fill values of
+    :meth:`maybe_grow`) and go into ``stores[c]``.  ``max_sizes``: one bound for all columns or one per column.  It
+    moves no tensor, so the plan stays valid.  Local to the rank: no exchange, and ranks need not agree.  Returns
+    the keys spilled per column."""
+    self._current()
+    n = len(self.tables)
+    if self.stores is None:
+      raise _ht._bad('spill_to: the driver was built without stores')   # pylint: disable=protected-access
+    if isinstance(max_sizes, int):
+      max_sizes = [max_sizes] * n
+    max_sizes = list(max_sizes)
+    if len(max_sizes) != n:
+      raise _ht._bad(f'spill_to: expected {n} max_sizes, got {len(max_sizes)}')   # pylint: disable=protected-access
+    live = self._tiered()
+    spilled = [0] * n
+    exports = _ht.hash_spill([self.tables[c] for c in live], [max_sizes[c] for c in live], keep_freq,
+                             [self._companions(c) for c in live], order=order)
+    for c, exp in zip(live, exports):
+      if len(exp):
+        self.stores[c].put(exp)
+      spilled[c] = len(exp)
+    return spilled
 
   def track_removals(self, on=True):
     """:meth:`HashTable.track_removals` on every table of this rank (all must be expiring): what :meth:`remove`,
@@ -198,26 +336,31 @@ class ShardedHashGroupLookup(ShardedGroupLookup):
     v 0, FTRL's accum its ``initial_accumulator_value`` and linear 0), then :meth:`rebind` with the new tensors
     if any table was rehashed.  Local to the rank: no exchange, and ranks need not agree.  Returns per table
     whether it was rehashed."""
-    return self._maybe(lambda t, comp: t.maybe_grow(max_load, factor, comp))
+    return self._maybe(lambda c, t, comp: t.maybe_grow(max_load, factor, comp))
 
-  def maybe_evict(self, max_load=0.75, target_load=0.5, keep_freq=0, order='lru'):
+  def maybe_evict(self, max_load=0.75, target_load=0.5, keep_freq=0, order='lru', spill=False):
     """:meth:`HashTable.maybe_evict` on every table of this rank -- the capacity stays, the oldest keys leave
     (``order='lfu'``: the least frequently used ones) --
     with the bound optimizer slots as companions and the fill values of :meth:`maybe_grow`, then :meth:`rebind`
-    with the new tensors if any table was rehashed.  Local to the rank: no exchange, and ranks need not agree.
-    Returns per table whether it was rehashed."""
+    with the new tensors if any table was rehashed.  ``spill=True``: a column that has a store spills where it
+    evicted -- what leaves goes into ``stores[c]`` (:meth:`HashTable.spill_to`).  Local to the rank: no exchange,
+    and ranks need not agree.  Returns per table whether it was rehashed."""
     _ht._check_loads(max_load, target_load)   # pylint: disable=protected-access
     _ht._check_order(order)   # pylint: disable=protected-access
-    return self._maybe(lambda t, comp: t.maybe_evict(max_load, target_load, keep_freq, comp, order=order))
+    if spill and self.stores is None:
+      raise _ht._bad('maybe_evict: spill=True needs a driver built with stores')   # pylint: disable=protected-access
+    stores = self.stores if spill else [None] * len(self.tables)
+    return self._maybe(lambda c, t, comp: t.maybe_evict(max_load, target_load, keep_freq, comp, spill=stores[c],
+                                                        order=order))
 
   def _maybe(self, policy):
-    """``policy(table, companions)`` -> None or the new companions, on every table; the rebind that follows."""
+    """``policy(c, table, companions)`` -> None or the new companions, on every table; the rebind that follows."""
     kinds = self._slot_kinds()
     new = {name: [list(x) if k is not None else x for x in getattr(self, name)]
            for name, k, _ in kinds}
     grown = []
     for c, t in enumerate(self.tables):
-      out = policy(t, self._companions(c))
+      out = policy(c, t, self._companions(c))
       grown.append(out is not None)
       for (name, k, _), x in zip(kinds, out or ()):
         if k is None:

@@ -1302,6 +1302,67 @@ int hbk_hash_missing_n(int32_t n_cols, const hbk_hash_missing_column_t* cols,
 size_t hbk_hash_missing_workspace_bytes(int32_t n_cols, const hbk_hash_missing_column_t* cols,
                                         const hbk_hash_sequence_t* seq);
 
+/* Missing ids over runs.  On the owner of a sharded hash table the ids of one column are W separate arrays, one per
+ * requester, each with its own place for the answers -- what hbk_hash_translate_runs_n reads where it lies.
+ * hbk_hash_missing_runs_n is hbk_hash_missing_n for ids in that form: what the owner asks its host tier for before
+ * the translate would insert a fresh row for a spilled id.  Expiring tables only.
+ *
+ * cols[c] describes table c and the outputs; runs[c][0 .. n_runs[c]) are column c's ids and the places for the
+ * find's answers.  Semantics: exactly those of hbk_hash_missing_n called ONCE on E_c, the concatenation of column
+ * c's runs in run order --
+ *   - runs[c][q].slots holds the pure find's answers for that run;
+ *   - out_ids[0 .. min(*count, out_capacity)) holds the distinct ids of E_c that the table does not hold, in the
+ *     order of their FIRST OCCURRENCE in E_c: an id in two runs is reported once, at its earlier run.  *count is
+ *     their number even when it exceeds out_capacity; nothing is written behind out_capacity;
+ *   - INT64_MIN and INT64_MIN + 1 are never reported; a TOMBSTONE slot holds no key, so an evicted id is reported;
+ *   - the table is NOT written: keys, rows, last_seen, freq, counts, stats and the sketch are bit for bit what they
+ *     were;
+ *   - slots, out_ids[0 .. count) and *count are functions of the inputs alone: the same on every run.
+ *
+ * Positions: every run is padded up to whole tiles of 256 positions, so that no tile straddles a run; the positions
+ * behind a run's n_keys hold nothing, and positions stay monotone in the order of E_c.  Launches, on the call's
+ * stream: one clear of the workspace per call, then per launch group -- up to 32 columns and
+ * HBK_HASH_MAX_RUNS_PER_LAUNCH non-empty runs, a column's runs never split (26 columns x 8 runs fit one group) --
+ * the find (hbk_hash_translate_runs_n with insert == 0, called as it is), a claim launch -- a workgroup
+ * takes up to 1024 positions of one run, a wave walking four 64-position chunks in order as hbk_hash_missing_n's
+ * claim does -- and the count, scan and write of the export's stream compaction.  A claim workgroup finds its run as
+ * the runs translate does, with up to four 64-wide ballots over the runs' first claim tiles, and records it for the
+ * count and write of its tiles; the scratch
+ * set, the compare-and-swap, atomicMin(first[cell], p) with the load before it, and the selection are those of
+ * hbk_hash_missing_n.  No lane waits for another: there is no spin loop.  A wave whose positions all hit issues no
+ * atomic.
+ *
+ * Workspace: hbk_hash_missing_runs_workspace_bytes(n_cols, n_runs, runs) bytes, 16-byte aligned: 12 bytes per cell
+ * (S = pow2 >= 2 * ids of the column, at least 64) and 12 bytes per tile.  Only the runs' n_keys are read to size it
+ * (a column whose counts are out of range adds nothing; the call refuses it).  The call clears what it uses on the
+ * stream before it reads it: there is no host read, and a captured call replays on whatever the id buffers then
+ * hold.  Stream-ordered against the translates, sweeps and backwards of its tables, never beside one.
+ *
+ * Refused (HBK_INVALID_ARGUMENT) before any device work, naming the column and the field: what hbk_hash_missing_n
+ * refuses of keys_cache, slab_count, slab_size, last_seen, freq, count, out_capacity and out_ids; what
+ * hbk_hash_translate_runs_n refuses of an expiring table's runs (NULL n_runs or runs with n_cols > 0; n_runs[c] < 0;
+ * NULL runs[c] with n_runs[c] > 0; a run with n_keys outside [0, 2^31), or with n_keys > 0 and NULL keys or slots; a
+ * column whose runs sum to >= 2^30 keys); a column whose padded positions reach 2^31 (below 2^30 keys and at most
+ * HBK_HASH_MAX_RUNS_PER_LAUNCH runs they cannot); a column with more than HBK_HASH_MAX_RUNS_PER_LAUNCH non-empty
+ * runs; a launch group whose find would need a grid of 2^31 tiles; a NULL, misaligned or too small workspace where
+ * one is needed, with the size needed.  n_cols == 0, zero runs and empty runs are fine (*count = 0).  exp.step is
+ * not read and may be NULL; exp.stats is not touched.  Detected by the presence of the symbol; the structs above and
+ * the version are those of 0.2.0. */
+typedef struct {
+  const int64_t* keys_cache;   /* device [slab_count * slab_size], 8-byte aligned: read only */
+  int64_t slab_count;
+  int32_t slab_size;           /* 1..64 */
+  hbk_hash_expiry_t exp;       /* last_seen and freq name an expiring table; nothing of it is written */
+  int64_t* out_ids;            /* device [out_capacity]; written: the distinct missed ids, first occurrence first */
+  int64_t out_capacity;
+  int64_t* count;              /* device int64 [1]; written: the distinct missed ids */
+} hbk_hash_missing_runs_column_t;
+int hbk_hash_missing_runs_n(int32_t n_cols, const hbk_hash_missing_runs_column_t* cols,
+                            const int32_t* n_runs, const hbk_hash_run_t* const* runs,
+                            void* workspace, size_t workspace_bytes, hbk_stream_t stream);
+size_t hbk_hash_missing_runs_workspace_bytes(int32_t n_cols, const int32_t* n_runs,
+                                             const hbk_hash_run_t* const* runs);
+
 /* Rehash: growth and tombstone compaction on the device.  A full table answers -1 for ever, and an expiring
  * table's probes get longer with every tombstone; both are cured by moving every live key into a fresh key
  * array -- of a larger geometry, or of the same one -- with its rows.  hbk_hash_rehash_n does that for N tables
@@ -1773,6 +1834,39 @@ int hbk_sharded_lookup_fwd_begin(hbk_sharded_t plan, const int64_t* const* ids,
                                  const int64_t* n_segments, hbk_stream_t stream);
 int hbk_sharded_lookup_fwd_end(hbk_sharded_t plan, float* const* outs, const int32_t* out_strides,
                                hbk_stream_t stream);
+/* The first half in two parts, so that the owner of a bounded hash table gets its chance between them:
+ * hbk_sharded_lookup_fwd_begin = hbk_sharded_lookup_fwd_ids + hbk_sharded_lookup_fwd_gather, the same launches and
+ * exchanges in the same order and the same host-time report.
+ *   _ids     everything through the id exchanges of all column groups: partition or a matching prefetch, the
+ *            step's one host wait, layouts, run tables, pack, exchanges.  hbk_sharded_owned_ids(plan, c) is valid
+ *            from here on.
+ *   _gather  the owner side: the translate of the hash columns, the owner gather and, where the exchanges run on
+ *            the communicator's stream, the events.
+ * hbk_sharded_hash_missing is valid only between the two.  For every column c with want[c] != 0 -- a hash column
+ * with an expiring table -- it runs hbk_hash_missing_runs_n over the W runs of ids this rank received for the
+ * column, peer after peer, where the translate would read them (the own slice in the outgoing buffer when it stayed
+ * in place): out_ids[c][0 .. min(counts[c], out_capacity[c])) holds the distinct received ids the table does not
+ * hold, first occurrence first, and counts[c] (device int64 [n_cols]; written for wanted columns only) their number.
+ * The find's answers go to the plan's slot buffer, which the translate overwrites; the workspace is the plan's.
+ * Where the exchanges run on the communicator's stream, `stream` first waits for the id exchange of the wanted
+ * columns' groups.  No host synchronisation.  out_ids, out_capacity and counts are read only at wanted columns.
+ *
+ * Between _ids and _gather the caller may change the tables in ways that move no tensor (hbk_hash_store_rows_n
+ * behind an insert: bringing spilled rows back), stream-ordered on the step's stream: the translate then finds
+ * the rows instead of inserting fresh ones.  Nothing here is a collective beyond what _begin is: ranks need not
+ * agree on whether anything was missed.
+ *
+ * Refused, naming the call: _gather or hbk_sharded_hash_missing without an open _ids step; _end before _gather;
+ * want[c] != 0 on a column that is not a hash column with an expiring table (HBK_INVALID_ARGUMENT); _ids and
+ * hbk_sharded_hash_missing on a p2p-bound plan (HBK_UNIMPLEMENTED).  A new _ids, _begin or hbk_sharded_lookup_fwd
+ * drops an open step.  Detected by the presence of the symbols; the version stays that of 0.2.0. */
+int hbk_sharded_lookup_fwd_ids(hbk_sharded_t plan, const int64_t* const* ids, const int64_t* n_ids,
+                               const int32_t* const* row_splits, const int64_t* n_segments,
+                               hbk_stream_t stream);
+int hbk_sharded_lookup_fwd_gather(hbk_sharded_t plan, hbk_stream_t stream);
+int hbk_sharded_hash_missing(hbk_sharded_t plan, const uint8_t* want /* [n_cols] */, int64_t* const* out_ids,
+                             const int64_t* out_capacity, int64_t* counts /* device [n_cols] */,
+                             hbk_stream_t stream);
 /* Optional pipelining hint: partition + size exchange (stages 1-2) of a FUTURE step on the plan's
  * own stream, overlapping what the last forward still has in flight (its exchanges, gather and
  * stitch).  The next hbk_sharded_lookup_fwd with the same id pointers and counts uses it and
