@@ -89,6 +89,12 @@ class SequencePack(C.Structure):
               ('sample_splits', C.c_void_p), ('total', C.c_void_p)]
 
 
+class ExpandColumn(C.Structure):
+  """hbk_expand_column_t"""
+  _fields_ = [('src', C.c_void_p), ('out', C.c_void_p), ('src_stride', C.c_int64), ('out_stride', C.c_int64),
+              ('width', C.c_int32)]
+
+
 class HashColumn(C.Structure):
   """hbk_hash_column_t"""
   _fields_ = [('keys_cache', C.c_void_p), ('slab_count', C.c_int64), ('slab_size', C.c_int32),
@@ -288,6 +294,10 @@ def _declare(l):
     'hbk_sequence_id_grid_n': (C.c_int, [i32, vp, vp, vp]),
     'hbk_sequence_pack_workspace_bytes': (sz, [i32, vp]),
     'hbk_sequence_pack_n': (C.c_int, [i32, vp, vp, vp, vp, sz, vp]),
+    'hbk_expand_rows_n': (C.c_int, [i32, vp, vp, i32, i64, i64, vp]),
+    'hbk_expand_index_workspace_bytes': (sz, [i64, i64]),
+    'hbk_expand_index_build': (C.c_int, [vp, i32, i64, i64, vp, vp, vp, vp, sz, vp]),
+    'hbk_expand_rows_grad_n': (C.c_int, [i32, vp, vp, vp, i64, i64, vp]),
     'hbk_group_stitch_bwd': (C.c_int, [i32, vp, vp]),
     'hbk_cache_probe': (C.c_int, [vp, i64, i32, vp, i64, vp, vp, vp]),
     'hbk_cache_lookup_workspace_bytes': (sz, [i64]),

@@ -943,3 +943,148 @@ class SequenceFeatures(_TableLayer):
     for k, c in enumerate(self._hash):
       res[c] = r[k]
     return res
+
+
+class DeduplicatedFeatures:
+  """Key-deduplicated features: the layer side of the reference's ``hb.data.deduplicate(key_idx_field_names,
+  value_field_names)`` (data/dataframe.py:301-392).  Features that are the same for many samples of a batch (the
+  user side of a click log) arrive once per distinct key -- ``U`` segments for ``B`` samples -- beside a restore
+  index per sample.  The reference restores the IDS to batch length before the lookup; this layer looks the ``U``
+  segments up once and expands the pooled ROWS to the batch on the device (``hb.embedding.expand_rows``), and its
+  backward reduces the batch gradient to ``U`` rows (``expand_rows_grad``: per key the fp32 sum of its samples'
+  rows in ascending sample order, bit-identical from run to run) before the inner layer's backward runs on them.
+  Lookup, reduce plan, optimizer step, sharded step and hash table underneath see ``U`` segments and are untouched.
+
+  Args:
+    plain: a :class:`DenseFeatures` over the per-sample columns, or None.
+    groups: an ordered dict ``{key_idx_feature_name: DenseFeatures | SequenceFeatures}``: per key field the layer
+      over its value columns.  Every inner layer is built as usual -- its own tables, optimizer slots and ``coll``
+      -- and is reachable as ``layer.layers`` (plain first, then the groups in order); checkpoints, ``set_step``,
+      ``maybe_grow`` and ``maybe_evict`` are the inner layers' own.
+    train: False builds no inverse index in the forward (inference needs none); ``backward`` is then refused.
+
+  Forward: ``features[key_idx_name]`` is the int32/int64 ``[B]`` restore index of a group, GLOBAL row numbers into
+  the group's ``U`` segments (a reader that yields the reference's per-row-group local indices adds the offsets
+  itself); the group's columns carry ``U`` segments, the plain columns ``B``.  Returns ``(block, sequences)``:
+  ``block`` is ``[B, sum of widths]`` -- the plain block first, then the :class:`DenseFeatures` groups in order,
+  adjacent, the row pitch padded to 4 floats as in :class:`DenseFeatures` (None without such layers) -- and
+  ``sequences[key_idx_name] = (outputs, lengths)`` of every :class:`SequenceFeatures` group, ``[B, T, dim]`` rows
+  and int32 ``[B]`` lengths per column, expanded by the same launch as rows of ``T * dim`` and of 1 element.  A
+  restore index outside ``[0, U)`` reads zero rows (and a length of 0) and sends no gradient.  The plain block is
+  placed by the identity form of the expand launch (``idx=None``); :class:`DenseFeatures` itself is unchanged.
+
+  ``indexes[key_idx_name]``: the :class:`~hybridbackend_amd.embedding.ExpandIndex` the last forward built
+  (``train``); its ``invalid_count()`` is the only host read."""
+
+  def __init__(self, plain, groups, train=True):
+    from hybridbackend_amd.embedding.expand import ExpandIndex, expand_rows, expand_rows_grad
+    self._index_cls, self._expand, self._expand_grad = ExpandIndex, expand_rows, expand_rows_grad
+    if plain is not None and not isinstance(plain, DenseFeatures):
+      raise _bad('DeduplicatedFeatures: plain must be a DenseFeatures or None')
+    self.plain = plain
+    self.groups = dict(groups)
+    for name, layer in self.groups.items():
+      if not isinstance(layer, (DenseFeatures, SequenceFeatures)):
+        raise _bad(f'DeduplicatedFeatures: group {name!r} must be a DenseFeatures or a SequenceFeatures')
+    if plain is None and not self.groups:
+      raise _bad('DeduplicatedFeatures: no layer at all')
+    self.layers = ([plain] if plain is not None else []) + list(self.groups.values())
+    self.columns = [col for layer in self.layers for col in layer.columns]
+    self.device = self.layers[0].device
+    self.train = bool(train)
+    # the block: plain first, then the DenseFeatures groups in order, adjacent
+    self.offsets, off = {}, plain.width if plain is not None else 0
+    for name, layer in self.groups.items():
+      if isinstance(layer, DenseFeatures):
+        self.offsets[name] = off
+        off += layer.width
+    self.width = off
+    self.indexes = {}
+
+  def __call__(self, features):
+    idxs = {name: features[name] for name in self.groups}
+    batch = None
+    for name, idx in idxs.items():
+      if idx.dim() != 1 or (batch is not None and idx.numel() != batch):
+        raise _bad(f'feature {name}: the restore index must be a vector of one row number per sample'
+                   + ('' if batch is None else f' ({batch} samples)'))
+      batch = idx.numel()
+    block = None
+    plain_block = self.plain(features) if self.plain is not None else None
+    if plain_block is not None:
+      if batch is not None and plain_block.shape[0] != batch:
+        raise _bad(f'the plain columns hold {plain_block.shape[0]} samples, the restore indexes {batch}')
+      batch = plain_block.shape[0]
+    if self.width:
+      pitch = (self.width + 3) // 4 * 4
+      block = torch.empty((batch, pitch), dtype=torch.float32, device=self.device)[:, :self.width]
+    if plain_block is not None:
+      self._expand(None, [plain_block], [block[:, :self.plain.width]])
+    sequences = {}
+    self.indexes = {}
+    for name, layer in self.groups.items():
+      if isinstance(layer, DenseFeatures):
+        rows = layer(features)
+        n_keys, srcs = rows.shape[0], [rows]
+        outs = [block[:, self.offsets[name]:self.offsets[name] + layer.width]]
+      else:
+        o, lengths = layer(features)
+        n_keys, srcs, outs = lengths[0].numel(), list(o) + list(lengths), None
+      if self.train:
+        self.indexes[name] = self._index_cls(idxs[name], n_keys).build()
+      outs = self._expand(idxs[name], srcs, outs, n_keys=n_keys)
+      if not isinstance(layer, DenseFeatures):
+        k = len(layer.columns)
+        sequences[name] = (outs[:k], outs[k:])
+    return block, sequences
+
+  def backward(self, grad, seq_grads=None, **kw):
+    """grad: the gradient of the last forward's block, fp32 ``[B, width]`` (None without one); ``seq_grads``:
+    ``{key_idx_name: [gradient of outputs[c], ...]}`` for the :class:`SequenceFeatures` groups.  Every group's
+    gradient is reduced to its ``U`` rows and handed to the inner layer's ``backward`` with the keywords
+    (``apply_lr``, ``optimizer``, ``emit``; ``weight_grads`` for the :class:`DenseFeatures` layers) unchanged; the
+    plain layer gets its block as the strided view it is.  Returns the inner layers' IndexedSlices as one list in
+    ``layer.columns`` order -- with ``weight_grads=True`` ``(slices, {weight_feature_key: tensor})``, a group's
+    weight gradients being those of its ``U`` segments' ids.  All ranks call the inner layers in the same order."""
+    if not self.train:
+      raise _bad('DeduplicatedFeatures.backward: the layer was built with train=False, its forward builds no index')
+    for name in self.groups:
+      if name not in self.indexes:
+        raise _bad(f'DeduplicatedFeatures.backward: group {name!r} has no index: run the forward first')
+    if self.width:
+      if grad is None or grad.dim() != 2 or grad.shape[1] != self.width or grad.dtype != torch.float32:
+        raise _bad(f'grad must be fp32 [batch, {self.width}]')
+      if grad.stride(1) != 1:
+        grad = grad.contiguous()
+    seq_grads = seq_grads or {}
+    want_w = bool(kw.get('weight_grads', False))
+    seq_kw = {k: v for k, v in kw.items() if k != 'weight_grads'}
+    res, wgrads = [], {}
+
+    def take(r):
+      if want_w:
+        wgrads.update(r[1])
+        r = r[0]
+      res.extend(r)
+    if self.plain is not None:
+      take(self.plain.backward(grad[:, :self.plain.width], **kw))
+    for name, layer in self.groups.items():
+      index = self.indexes[name]
+      if isinstance(layer, DenseFeatures):
+        pitch = (layer.width + 3) // 4 * 4
+        g_keys = torch.empty((index.n_keys, pitch), dtype=torch.float32, device=self.device)[:, :layer.width]
+        off = self.offsets[name]
+        self._expand_grad(index, [grad[:, off:off + layer.width]], [g_keys])
+        take(layer.backward(g_keys, **kw))
+      else:
+        gs = seq_grads.get(name)
+        if gs is None or len(gs) != len(layer.columns):
+          raise _bad(f'seq_grads[{name!r}] must hold {len(layer.columns)} gradients, one per column of the group')
+        res.extend(layer.backward(self._expand_grad(index, [g.contiguous() for g in gs]), **seq_kw))
+    if want_w:
+      return res, wgrads
+    return res
+
+  def close(self):
+    for layer in self.layers:
+      layer.close()

@@ -698,6 +698,63 @@ int hbk_sequence_pack_n(int32_t n_cols, const hbk_lookup_column_t* cols, const h
                         const hbk_sequence_pack_t* pack, void* workspace, size_t workspace_bytes,
                         hbk_stream_t stream);
 
+/* Key-deduplicated features: rows that are the same for many samples of a batch (the user side of a click log;
+ * the reference's hb.data.deduplicate, data/dataframe.py:301-392, restores the IDS to batch length before the
+ * lookup) are looked up ONCE per distinct key and expanded to the batch on the device.  n_keys = U rows are
+ * produced by whatever lookup runs underneath; idx (int32 or int64, [n_samples]) names, per sample, the row it
+ * takes.  A column is rows of `width` 4-byte elements, any width >= 1; strides count elements, 0 = contiguous.
+ *
+ * hbk_expand_rows_n -- the forward.  For every column and every b < n_samples:
+ *     out[b, :] = src[idx[b], :]      if 0 <= idx[b] < n_keys
+ *               = a zero row          otherwise (also: every row when n_keys == 0)
+ * a pure copy of bits (fp32 rows, or int32 rows such as sequence lengths).  idx == NULL is the identity,
+ * out[b, :] = src[b, :] for every b < n_samples (src holds n_samples rows and n_keys is not read): a plain block
+ * placed by the same kind of launch.  An index is compared with [0, n_keys) before any address is formed from it.
+ * One launch per 64 columns; a lane group per output row sized from the width, 16-byte lanes where width, both
+ * strides and both addresses are multiples of 4 elements / 16 bytes, else 4-byte lanes (chosen per column by the
+ * host); wider rows are tiled.  Plain loads and vector stores, no atomics, no workspace, no host read: capturable.
+ *
+ * hbk_expand_index_build -- the inverse of idx, built once per key field and step and shared by its columns:
+ *     order[splits[u] .. splits[u + 1])  = the samples b with idx[b] == u, in ASCENDING b     (u < n_keys)
+ *     invalid[0]                         = the number of samples with idx[b] outside [0, n_keys): in no list
+ * order is int32 [n_samples] (its elements at or past splits[n_keys] hold the samples in no list), splits int32
+ * [n_keys + 1], invalid int32 [1]; splits and invalid are written whatever the sizes.  A key kernel writes the
+ * pairs (idx[b] valid ? idx[b] : n_keys, b), a stable LSD radix sort (rocPRIM) orders them by key, one lower bound
+ * per key writes splits: no atomics, so the order does not depend on the run.  No host read and no allocation;
+ * capture of this call is not promised.  The workspace holds the pairs and the sort's scratch.
+ *
+ * hbk_expand_rows_grad_n -- the transpose.  src is the gradient [n_samples, width] (typically a column block of
+ * the batch gradient), out is [n_keys, width]:
+ *     out[u, :] = src[order[splits[u]], :] + src[order[splits[u] + 1], :] + ...      (fp32, in this order)
+ * one sequential chain per element that STARTS FROM ITS FIRST TERM (not from 0) and adds the following terms one
+ * by one; a key with an empty list gets a zero row; every row of out is written, nothing needs clearing.  One lane
+ * group per (key, width tile), several rows of the list loaded ahead of the adds; no atomics: the same bits on
+ * every run.  An element of order outside [0, n_samples) is skipped, splits are clamped to [0, n_samples].  A key
+ * that owns thousands of samples is one latency-bound chain (long lists are not split).  Capturable.
+ *
+ * Refused (HBK_INVALID_ARGUMENT) before any device work, the column named: a NULL src or out with rows to move,
+ * width < 1, a stride below the width, n_samples or n_keys negative or >= 2^31, an id dtype that is neither int32
+ * nor int64, a workspace smaller than hbk_expand_index_workspace_bytes answers (the message states the size),
+ * more than one column naming the same out.  n_cols == 0, n_samples == 0 and n_keys == 0 are fine.
+ * Bytes moved per column: 4 * width * (n_samples + n_keys) + the index forward; 4 * width * (n_samples + n_keys)
+ * + 4 * n_samples + 4 * n_keys backward.
+ * Detected by the presence of the symbols; the structs above and the version are those of 0.2.0. */
+typedef struct {
+  const void* src;      /* device [rows, src_stride]: n_keys rows (forward), n_samples rows (transpose, identity) */
+  void* out;            /* device [rows, out_stride]: n_samples rows (forward), n_keys rows (transpose) */
+  int64_t src_stride;   /* elements between rows; 0 = width */
+  int64_t out_stride;
+  int32_t width;        /* 4-byte elements per row, >= 1 */
+} hbk_expand_column_t;
+int hbk_expand_rows_n(int32_t n_cols, const hbk_expand_column_t* cols, const void* idx, int32_t idx_dtype,
+                      int64_t n_samples, int64_t n_keys, hbk_stream_t stream);
+size_t hbk_expand_index_workspace_bytes(int64_t n_samples, int64_t n_keys);
+int hbk_expand_index_build(const void* idx, int32_t idx_dtype, int64_t n_samples, int64_t n_keys, int32_t* order,
+                           int32_t* splits, int32_t* invalid, void* workspace, size_t workspace_bytes,
+                           hbk_stream_t stream);
+int hbk_expand_rows_grad_n(int32_t n_cols, const hbk_expand_column_t* cols, const int32_t* order,
+                           const int32_t* splits, int64_t n_samples, int64_t n_keys, hbk_stream_t stream);
+
 /* R10 (sharded form)  d(stitch + combiner): the transpose of the requester-side
  *   `gather(embeddings, shard_index)` + combiner (hbtf/embedding/sharding.py:200; TF emits
  *   SparseSegment*Grad followed by an UnsortedSegmentSum over a permutation):
