@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get('HBK_LIBRARY') or os.path.join(_HERE, 'lib', 'libhbk_c
 # dtype codes of include/hbk.h
 INT8, UINT8, INT32, UINT32, INT64, UINT64, HALF, FLOAT, DOUBLE = range(9)
 APPLY_SGD, APPLY_ADAGRAD = 0, 2
+APPLY_LAZY_ADAM, APPLY_FTRL, APPLY_ROWWISE_ADAGRAD = 3, 4, 5   # hbk_sparse_apply_slices_n
 GRAD_DETERMINISTIC = 1   # hbk_lookup_grad_column_t.flags
 COMBINER_SUM, COMBINER_MEAN, COMBINER_SQRTN = 0, 1, 2
 OK, INVALID_ARGUMENT, UNIMPLEMENTED, INTERNAL = 0, 3, 12, 13
@@ -93,6 +94,20 @@ class ExpandColumn(C.Structure):
   """hbk_expand_column_t"""
   _fields_ = [('src', C.c_void_p), ('out', C.c_void_p), ('src_stride', C.c_int64), ('out_stride', C.c_int64),
               ('width', C.c_int32)]
+
+
+class SlicesColumn(C.Structure):
+  """hbk_slices_column_t"""
+  _fields_ = [('table', C.c_void_p), ('rows', C.c_int64), ('dim', C.c_int32), ('table_pitch', C.c_int32),
+              ('unique_rows', C.c_void_p), ('grad_rows', C.c_void_p), ('n_unique', C.c_void_p),
+              ('capacity', C.c_int64)]
+
+
+class ReplicaColumn(C.Structure):
+  """hbk_replica_column_t"""
+  _fields_ = [('unique_rows', C.c_void_p), ('grad_rows', C.c_void_p), ('n_unique', C.c_void_p),
+              ('capacity', C.c_int64), ('rows', C.c_int64), ('dim', C.c_int32), ('block', C.c_void_p),
+              ('touched', C.c_void_p), ('urows', C.c_void_p)]
 
 
 class HashColumn(C.Structure):
@@ -288,6 +303,9 @@ def _declare(l):
     'hbk_group_lookup_bwd_rowwise_adagrad': (C.c_int, [i32, vp, vp, vp, C.c_float, vp, sz, vp]),
     'hbk_group_lookup_bwd_rowwise_adagrad_clipped_workspace_bytes': (sz, [i32, vp, vp]),
     'hbk_group_lookup_bwd_rowwise_adagrad_clipped': (C.c_int, [i32, vp, vp, vp, vp, C.c_float, vp, sz, vp]),
+    'hbk_sparse_apply_slices_n': (C.c_int, [i32, vp, i32, vp, vp, vp, C.c_float, vp]),
+    'hbk_replica_grads_pack_n': (C.c_int, [i32, vp, vp, i64, vp]),
+    'hbk_replica_grads_rows_n': (C.c_int, [i32, vp, vp]),
     'hbk_group_lookup_bwd_weights': (C.c_int, [i32, vp, vp, vp, vp]),
     'hbk_group_lookup_fwd_sequence': (C.c_int, [i32, vp, vp, vp, vp]),
     'hbk_sequence_row_grid_n': (C.c_int, [i32, vp, vp, vp]),

@@ -1052,3 +1052,175 @@ extern "C" int hbk_group_lookup_bwd_rowwise_adagrad_clipped(int32_t n_cols,
   return rowwise_adagrad_call(n_cols, cols, any ? max_norms : nullptr, accum, opt, lr, workspace,
                               workspace_bytes, stream_);
 }
+
+// ------------------------------------------------------------------------------------------------------------
+// hbk_sparse_apply_slices_n (include/hbk.h): the apply launches above on IndexedSlices the caller holds.  Host
+// code only: the slices become the descriptors phase 2 reads (n_ids = the capacity), the column checks of the
+// slot entries run on them, and the rule's kernel is launched once per kSlotMaxCols columns.  SGD and Adagrad
+// take the clip pass's kernels with every max_norm 0, which makes them plain slice applies with the fused
+// step's arithmetic.
+namespace hbk {
+namespace {
+
+// every host check of an SGD / Adagrad slice call's columns (accum == NULL: SGD); the apply's row shapes
+int check_lr_slices(const char* who, int32_t n_cols, const hbk_lookup_grad_column_t* e, float* const* accum,
+                    std::vector<RowShape>* shapes) {
+  std::vector<uintptr_t> seen;
+  seen.reserve((size_t)n_cols * 2);
+  shapes->assign((size_t)n_cols, RowShape{});
+  for (int32_t c = 0; c < n_cols; ++c) {
+    const hbk_lookup_grad_column_t& h = e[c];
+    float* const a = accum != nullptr ? accum[c] : nullptr;
+    HBK_REQUIRE(accum == nullptr || a != nullptr, "%s: column %d: the accumulator is NULL", who, c);
+    HBK_REQUIRE(a == nullptr || a != h.table, "%s: column %d: the accumulator is the table", who, c);
+    const int32_t pitch = h.table_pitch > 0 ? h.table_pitch : h.dim;
+    HBK_REQUIRE(h.n_ids <= 0 ||
+                    make_rowshape(h.dim,
+                                  (uintptr_t)h.table | (uintptr_t)a | (uintptr_t)h.grad_rows |
+                                      ((uintptr_t)(uint32_t)pitch * 4),
+                                  &(*shapes)[(size_t)c]),
+                "%s: column %d: dim %d needs more than 64 lanes per row (at most 256 with 16-byte "
+                "aligned table / accum / grad_rows / pitch, 64 otherwise)", who, c, h.dim);
+    if (h.table != nullptr) seen.push_back((uintptr_t)h.table);
+    if (a != nullptr) seen.push_back((uintptr_t)a);
+  }
+  std::sort(seen.begin(), seen.end());
+  HBK_REQUIRE(std::adjacent_find(seen.begin(), seen.end()) == seen.end(),
+              "%s: two columns name the same table or accumulator (a row stepped twice in one call would "
+              "race)", who);
+  return HBK_OK;
+}
+
+// the launches of one slice call: launch(args, blocks, stream) sets args.p and launches the rule's kernel
+template <typename P, typename Launch>
+int launch_slices(const std::vector<hbk_lookup_grad_column_t>& e, const std::vector<RowShape>& shapes,
+                  float* const* s0, float* const* s1, hipStream_t stream, Launch launch) {
+  const int32_t n_cols = (int32_t)e.size();
+  for (int32_t c0 = 0; c0 < n_cols; c0 += kSlotMaxCols) {
+    SlotArgs<P> a;
+    memset(&a, 0, sizeof(a));
+    unsigned blocks = 0;
+    a.n_cols = fill_slot_cols(e, shapes, s0, s1, c0, std::min(n_cols, c0 + kSlotMaxCols), a.c, &blocks);
+    if (a.n_cols == 0) continue;
+    launch(a, blocks, stream);
+    HBK_HIP_OK(hipGetLastError());
+  }
+  return HBK_OK;
+}
+
+int sparse_apply_slices(int32_t n_cols, const hbk_slices_column_t* cols, int32_t apply, float* const* slot0,
+                        float* const* slot1, const void* params, float lr, hbk_stream_t stream_) {
+  static const char* kWho = "sparse_apply_slices_n";
+  constexpr float kMax = 3.402823466e38f;
+  HBK_REQUIRE(n_cols >= 0, "%s: n_cols must be >= 0, got %d", kWho, n_cols);
+  HBK_REQUIRE(n_cols == 0 || cols != nullptr, "%s: cols is NULL", kWho);
+  HBK_REQUIRE(apply == HBK_APPLY_SGD || apply == HBK_APPLY_ADAGRAD || apply == HBK_APPLY_LAZY_ADAM ||
+                  apply == HBK_APPLY_FTRL || apply == HBK_APPLY_ROWWISE_ADAGRAD,
+              "%s: apply must be HBK_APPLY_SGD, _ADAGRAD, _LAZY_ADAM, _FTRL or _ROWWISE_ADAGRAD, got %d", kWho,
+              apply);
+  // the slices as the descriptors the apply reads
+  std::vector<hbk_lookup_grad_column_t> e((size_t)n_cols);
+  for (int32_t c = 0; c < n_cols; ++c) {
+    const hbk_slices_column_t& s = cols[c];
+    HBK_REQUIRE(s.capacity >= 0 && s.capacity < (1ll << 30), "%s: column %d: capacity %lld must be in [0, 2^30)",
+                kWho, c, (long long)s.capacity);
+    HBK_REQUIRE(s.rows >= 0, "%s: column %d: rows must be >= 0, got %lld", kWho, c, (long long)s.rows);
+    HBK_REQUIRE(s.dim >= 1, "%s: column %d: dim must be >= 1", kWho, c);
+    HBK_REQUIRE(s.table_pitch == 0 || s.table_pitch >= s.dim,
+                "%s: column %d: table_pitch %d is smaller than dim %d", kWho, c, s.table_pitch, s.dim);
+    if (s.capacity > 0) {
+      HBK_REQUIRE(s.table != nullptr && ((uintptr_t)s.table & 3) == 0,
+                  "%s: column %d: table must be a device fp32 buffer", kWho, c);
+      HBK_REQUIRE(s.unique_rows != nullptr && ((uintptr_t)s.unique_rows & 7) == 0,
+                  "%s: column %d: unique_rows must be a device int64 [capacity]", kWho, c);
+      HBK_REQUIRE(s.grad_rows != nullptr && ((uintptr_t)s.grad_rows & 3) == 0,
+                  "%s: column %d: grad_rows must be a device fp32 [capacity, dim]", kWho, c);
+      HBK_REQUIRE(s.n_unique != nullptr && ((uintptr_t)s.n_unique & 3) == 0,
+                  "%s: column %d: n_unique must be a device int32 [1]", kWho, c);
+    }
+    hbk_lookup_grad_column_t& h = e[(size_t)c];
+    memset(&h, 0, sizeof(h));
+    h.table = s.table;
+    h.rows = s.rows;
+    h.dim = s.dim;
+    h.table_pitch = s.table_pitch;
+    h.n_ids = s.capacity;
+    h.unique_rows = const_cast<int64_t*>(s.unique_rows);
+    h.grad_rows = const_cast<float*>(s.grad_rows);
+    h.n_unique = const_cast<int32_t*>(s.n_unique);
+  }
+  hipStream_t stream = as_stream(stream_);
+  std::vector<RowShape> shapes;
+  int rc = HBK_OK;
+  if (apply == HBK_APPLY_SGD || apply == HBK_APPLY_ADAGRAD) {
+    const bool adagrad = apply == HBK_APPLY_ADAGRAD;
+    HBK_REQUIRE(lr != 0.0f && lr >= -kMax && lr <= kMax, "%s: lr must be finite and != 0, got %g", kWho,
+                (double)lr);
+    HBK_REQUIRE(!adagrad || n_cols == 0 || slot0 != nullptr, "%s: the accumulator array (slot0) is NULL", kWho);
+    if ((rc = check_lr_slices(kWho, n_cols, e.data(), adagrad ? slot0 : nullptr, &shapes)) != HBK_OK) return rc;
+    std::vector<float*> none((size_t)n_cols, nullptr);
+    return launch_slices<LrParams>(e, shapes, adagrad ? slot0 : none.data(), none.data(), stream,
+                                   [&](SlotArgs<LrParams>& a, unsigned blocks, hipStream_t s) {
+                                     a.p = LrParams{lr};
+                                     if (adagrad) {
+                                       hipLaunchKernelGGL(sparse_adagrad_clip_kernel, dim3(blocks),
+                                                          dim3(kSlotBlock), 0, s, a);
+                                     } else {
+                                       hipLaunchKernelGGL(sparse_sgd_clip_kernel, dim3(blocks), dim3(kSlotBlock),
+                                                          0, s, a);
+                                     }
+                                   });
+  }
+  if (apply == HBK_APPLY_LAZY_ADAM) {
+    static const SlotNames kNames = {kWho, "Adam", "m", "v"};
+    const hbk_adam_t* adam = static_cast<const hbk_adam_t*>(params);
+    if ((rc = adam_check(adam, lr, kWho)) != HBK_OK) return rc;
+    if ((rc = check_slot_columns(kNames, n_cols, e.data(), slot0, slot1, &shapes)) != HBK_OK) return rc;
+    rc = launch_slices<AdamParams>(e, shapes, slot0, slot1, stream,
+                                   [&](SlotArgs<AdamParams>& a, unsigned blocks, hipStream_t s) {
+                                     a.p = AdamParams{adam->beta_powers, lr, adam->beta1, adam->beta2,
+                                                      adam->epsilon};
+                                     hipLaunchKernelGGL(sparse_adam_apply_kernel, dim3(blocks), dim3(kSlotBlock),
+                                                        0, s, a);
+                                   });
+    if (rc != HBK_OK || !adam->finish) return rc;
+    hipLaunchKernelGGL(adam_finish_kernel, dim3(1), dim3(kWave), 0, stream, adam->beta_powers, adam->beta1,
+                       adam->beta2);
+    HBK_HIP_OK(hipGetLastError());
+    return HBK_OK;
+  }
+  if (apply == HBK_APPLY_FTRL) {
+    static const SlotNames kNames = {kWho, "FTRL", "accum", "linear"};
+    const hbk_ftrl_t* ftrl = static_cast<const hbk_ftrl_t*>(params);
+    if ((rc = ftrl_check(ftrl, lr, kWho)) != HBK_OK) return rc;
+    if ((rc = check_slot_columns(kNames, n_cols, e.data(), slot0, slot1, &shapes)) != HBK_OK) return rc;
+    return launch_slices<FtrlParams>(
+        e, shapes, slot0, slot1, stream, [&](SlotArgs<FtrlParams>& a, unsigned blocks, hipStream_t s) {
+          a.p = FtrlParams{lr, ftrl->l1, 2.0f * ftrl->l2, 2.0f * ftrl->l2_shrinkage, -ftrl->lr_power};
+          if (ftrl->lr_power != -0.5f) {
+            hipLaunchKernelGGL(sparse_ftrl_apply_kernel<true>, dim3(blocks), dim3(kSlotBlock), 0, s, a);
+          } else {
+            hipLaunchKernelGGL(sparse_ftrl_apply_kernel<false>, dim3(blocks), dim3(kSlotBlock), 0, s, a);
+          }
+        });
+  }
+  static const SlotNames kNames = {kWho, "row-wise Adagrad", "accum", nullptr};
+  const hbk_rowwise_adagrad_t* opt = static_cast<const hbk_rowwise_adagrad_t*>(params);
+  if ((rc = rowwise_adagrad_check(opt, lr, kWho)) != HBK_OK) return rc;
+  if ((rc = check_row_slot_columns(kNames, n_cols, e.data(), slot0, &shapes)) != HBK_OK) return rc;
+  return launch_slices<RowwiseParams>(e, shapes, slot0, nullptr, stream,
+                                      [&](SlotArgs<RowwiseParams>& a, unsigned blocks, hipStream_t s) {
+                                        a.p = RowwiseParams{lr, opt->epsilon};
+                                        hipLaunchKernelGGL(sparse_rowwise_adagrad_apply_kernel, dim3(blocks),
+                                                           dim3(kSlotBlock), 0, s, a);
+                                      });
+}
+
+}  // namespace
+}  // namespace hbk
+
+extern "C" int hbk_sparse_apply_slices_n(int32_t n_cols, const hbk_slices_column_t* cols, int32_t apply,
+                                         float* const* slot0, float* const* slot1, const void* params,
+                                         float lr, hbk_stream_t stream) {
+  return hbk::sparse_apply_slices(n_cols, cols, apply, slot0, slot1, params, lr, stream);
+}

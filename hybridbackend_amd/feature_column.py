@@ -158,7 +158,7 @@ class _TableLayer:
     self.sharded, self.weights, self.hash_tables = [], [], []
     for col in self.columns:
       if _is_hash(col):
-        # never replicated: slot numbers differ per rank, and replicated tables are not stepped at W > 1
+        # never replicated: slot numbers differ per rank, and replicated tables are by default not stepped at W > 1
         table = col.make_table(self.device, world)
         self.hash_tables.append(table)
         self.sharded.append(world > 1)
@@ -196,6 +196,45 @@ class _TableLayer:
   def _two_slot_kw(self, idx):
     """The drivers' keyword arguments of the slot optimizers, tables idx."""
     return _opt.slot_kwargs(self, idx)
+
+  # ---- replicated tables at W > 1: aggregate across ranks, then step (aggregate_replicated) ---------------
+  def _init_replica(self, aggregate_replicated, replicated_scale, what):
+    """The cross-rank step of the replicated group: a ``ReplicatedGradients`` over its tables and a
+    ``SparseApply`` over the tables and the layer's slots.  Built only where it runs (the argument set,
+    replicated columns, W > 1); refuses a replicated column whose dim the apply cannot take."""
+    self.aggregate_replicated = bool(aggregate_replicated)
+    self._replica = self._rep_apply = None
+    if not (self.aggregate_replicated and self._rep and self._world() > 1):
+      return
+    from hybridbackend_amd.distribute.replicated import ReplicatedGradients   # pylint: disable=import-outside-toplevel
+    from hybridbackend_amd.embedding.sparse_apply import SparseApply   # pylint: disable=import-outside-toplevel
+    for c in self._rep:
+      dim = self.columns[c].dimension
+      if dim > 256 or (dim % 4 != 0 and dim > 64):
+        raise _bad(f'{what}(..., aggregate_replicated=True): replicated column {self.columns[c].key!r}: dimension '
+                   f'{dim} is beyond what the aggregated step takes (at most 256 when a multiple of 4, 64 otherwise)')
+    tables = [self.weights[c] for c in self._rep]
+    self._replica = ReplicatedGradients([tuple(t.shape) for t in tables], self.coll, scale=replicated_scale,
+                                        device=self.device)
+    self._rep_apply = SparseApply(tables, [self.accums[c] for c in self._rep] if self.accums is not None else None,
+                                  **self._two_slot_kw(self._rep))
+
+  def _rep_step(self, slices, apply_lr, optimizer, finish):
+    """Stages 2 and 3 of the replicated group's aggregated step, behind the local emit-form reduce that wrote
+    ``slices``: ONE allreduce of the packed dense gradients (every rank issues it here, before the sharded
+    step's backward), then the optimizer step on every row any rank touched."""
+    self._rep_apply(self._replica.aggregate(slices), apply_lr, optimizer, finish)
+
+  def replica_drift(self):
+    """``max(max over ranks - min over ranks)`` over every element of the replicated tables, as a device scalar:
+    two packed allreduces (MAX and MIN).  A collective.  0.0 as long as the replicas agree -- forever under
+    ``aggregate_replicated``, when the transport's allreduce leaves the same bits on every rank."""
+    tables = [self.weights[c] for c in self._rep if self.weights[c].numel()]
+    if not tables or self._world() <= 1:
+      return torch.zeros((), dtype=torch.float32, device=self.device)
+    hi = self.coll.allreduce_n(tables, self.coll.MAX)
+    lo = self.coll.allreduce_n(tables, self.coll.MIN)
+    return torch.stack([(h - l).max() for h, l in zip(hi, lo)]).max()
 
   # ---- hash-keyed columns: what moves with a table ------------------------------------------------------
   def _world(self):
@@ -456,6 +495,13 @@ class DenseFeatures(_TableLayer):
       step with (its defaults when omitted).
     train: False makes every hash-keyed column a pure find -- unseen ids read zero rows, ``size()`` and
       ``counts`` do not move, and ``backward`` is refused; bucketed columns ignore it.
+    aggregate_replicated: True makes a stepping ``backward`` at W > 1 train the REPLICATED tables too: their
+      gradients are aggregated across ranks as one packed dense allreduce (``hb.distribute.ReplicatedGradients``)
+      and applied with the layer's optimizer and slots on every rank (``hb.embedding.SparseApply``), so the
+      replicas stay bit-equal (``replica_drift()``).  False (the default): they are not stepped at W > 1 and the
+      caller aggregates.  At W = 1 it changes nothing.  A replicated column wider than the apply takes (256
+      floats, 64 when not a multiple of 4) is refused at construction.
+    replicated_scale: what multiplies the summed gradients; None: ``1 / W``, the mean of the reference.
 
   Hash-keyed columns (:class:`HashEmbeddingColumn`) mix freely with bucketed ones; column order decides the
   block offsets.  ``hash_tables[c]`` is the column's :class:`HashTable` (None for a bucketed column) and
@@ -469,9 +515,10 @@ class DenseFeatures(_TableLayer):
 
   def __init__(self, columns, device, coll=None, batch_size=0, init=None,
                initial_accumulator_value=None, optimizer=None, adam=None, ftrl=None, train=True,
-               rowwise_adagrad=None):
+               rowwise_adagrad=None, aggregate_replicated=False, replicated_scale=None):
     self._init_tables(columns, device, coll, batch_size, init, initial_accumulator_value, optimizer,
                       adam, ftrl, train, rowwise_adagrad)
+    self._init_replica(aggregate_replicated, replicated_scale, 'DenseFeatures')
     for c in self._hash:
       col = self.columns[c]
       if col.weight_feature_key is not None and self._world() > 1:
@@ -627,8 +674,15 @@ class DenseFeatures(_TableLayer):
     same pass -- for the SHARDED tables.  Small tables are replicated on every rank: at W > 1
     their gradients must first be aggregated across ranks (``hb.distribute.aggregate_gradients``,
     hybridbackend/tensorflow/training/gradient.py:119-177) or the replicas diverge, so for them
-    this method never applies the step at W > 1: it returns their IndexedSlices and the caller
-    applies the aggregated gradient.  ``emit=False`` (with ``apply_lr``): the stepped tables
+    this method by default never applies the step at W > 1: it returns their IndexedSlices and the caller
+    applies the aggregated gradient.  A layer built with ``aggregate_replicated=True`` does both itself: behind
+    the local reduce every rank issues ONE allreduce of the replicated group's packed dense gradients -- at this
+    point of the method, before the sharded step's backward, so all ranks must call ``backward`` in step -- and
+    then steps every row ANY rank touched with ``g = fp32(sum over ranks) * fp32(scale)`` on every rank, also
+    where the sum is zero; rows nobody touched and their slots are not written.  A ``max_norm`` column
+    aggregates the clipped gradients g' of the ranks' local clip passes; the aggregated step is not clipped
+    again.  The return value stays this rank's LOCAL slices (``(None, None, n_unique)`` with ``emit=False``).
+    ``emit=False`` (with ``apply_lr``): the stepped tables
     write no IndexedSlices (step only; their entries are ``(None, None, n_unique)``).
     ``optimizer='adam'`` (layer built with ``optimizer='adam'``): the Lazy Adam step; the beta powers
     advance once per backward that steps any table.  ``optimizer='ftrl'`` (layer built with
@@ -691,6 +745,12 @@ class DenseFeatures(_TableLayer):
                      finish=not ((self._shd or self._hash) and apply_lr != 0.0),
                      weight_grads=want(self._rep))
       r = take(self._rep, r)
+      if self._replica is not None and apply_lr != 0.0:
+        # aggregate_replicated: the emit form above was stage 1; every rank issues the allreduce HERE, before
+        # the sharded step's backward.  The return value stays this rank's LOCAL slices
+        self._rep_step(r, apply_lr, optimizer, not ((self._shd or self._hash) and apply_lr != 0.0))
+        if not emit:
+          r = [(None, None, t[2]) for t in r]
       for k, c in enumerate(self._rep):
         res[c] = r[k]
     if self._shd:
@@ -785,11 +845,13 @@ class SequenceFeatures(_TableLayer):
 
   def __init__(self, columns, device, coll=None, batch_size=0, init=None,
                initial_accumulator_value=None, optimizer=None, adam=None, ftrl=None, train=True,
-               rowwise_adagrad=None, sharded_zero_padding=False):
+               rowwise_adagrad=None, sharded_zero_padding=False, aggregate_replicated=False,
+               replicated_scale=None):
     from hybridbackend_amd.embedding.hash_sequence import HashSequenceLookup
     from hybridbackend_amd.embedding.sequence import SequenceLookup, SequenceLookupGrad
     self._init_tables(columns, device, coll, batch_size, init, initial_accumulator_value, optimizer,
                       adam, ftrl, train, rowwise_adagrad)
+    self._init_replica(aggregate_replicated, replicated_scale, 'SequenceFeatures')
     self.sharded_zero_padding = bool(sharded_zero_padding)
     for c in self._hash:
       col = self.columns[c]
@@ -910,8 +972,10 @@ class SequenceFeatures(_TableLayer):
     """grads[c]: the gradient of the last forward's ``outputs[c]``.  Returns per column the
     ``IndexedSlices`` ``(unique_rows, grad_rows, n_unique)`` of this rank's rows, as
     ``DenseFeatures.backward`` does and with its rule for the step: the sharded tables are stepped in the
-    same pass, replicated tables are stepped only at W = 1 (at W > 1 their gradients must be aggregated
-    across ranks first; their IndexedSlices are returned).  A hash-keyed column is always stepped, and its
+    same pass, replicated tables are by default stepped only at W = 1 (at W > 1 their gradients must be
+    aggregated across ranks first; their IndexedSlices are returned) -- a layer built with
+    ``aggregate_replicated=True`` aggregates and steps them itself, exactly as ``DenseFeatures.backward``
+    describes (one allreduce, issued before the sharded step's backward).  A hash-keyed column is always stepped, and its
     ``unique_rows`` are slot numbers of this rank's table (``layer.hash_tables[c].keys[unique_rows]`` names the
     ids).  Refused after a forward of a layer built with ``train=False``."""
     _opt.two_slot_class(optimizer, self, "SequenceFeatures(..., optimizer='{name}')")
@@ -926,6 +990,11 @@ class SequenceFeatures(_TableLayer):
       r = self._grad([grads[c] for c in self._rep], apply_lr=rep_lr, optimizer=optimizer,
                      emit=emit or rep_lr == 0.0,
                      finish=not ((self._shd or self._hash) and apply_lr != 0.0))
+      if self._replica is not None and apply_lr != 0.0:
+        # aggregate_replicated, as in DenseFeatures.backward: the allreduce is issued here, before the sharded step
+        self._rep_step(r, apply_lr, optimizer, not ((self._shd or self._hash) and apply_lr != 0.0))
+        if not emit:
+          r = [(None, None, t[2]) for t in r]
       for k, c in enumerate(self._rep):
         res[c] = r[k]
     flat = lambda c: grads[c].contiguous().view(   # noqa: E731

@@ -581,6 +581,90 @@ int hbk_group_lookup_bwd_rowwise_adagrad_clipped(int32_t n_cols, const hbk_looku
                                                  void* workspace, size_t workspace_bytes,
                                                  hbk_stream_t stream);
 
+/* The optimizer step on IndexedSlices the CALLER holds: what the second phase of the entries above does,
+ * without the reduce in front of it.  For every u < n_unique[0] (read on the device, clamped to
+ * [0, capacity]; entries at or after it are not read) with r = unique_rows[u] inside [0, rows), row r of the
+ * table and of its slots is stepped with g = grad_rows[u, :]; any other entry (-1 included) touches nothing, so
+ * slices may have holes.  The rows must be DISTINCT: no step but SGD's is additive, and a row named twice
+ * races.  This is documented, not checked.  `apply` names the rule, and formulas, rounding and operation
+ * order are exactly those of the entry it belongs to:
+ *     HBK_APPLY_SGD              table -= lr * g                                   (hbk_group_lookup_bwd_apply)
+ *     HBK_APPLY_ADAGRAD          slot0 = the accumulator                           (hbk_group_lookup_bwd_apply)
+ *     HBK_APPLY_LAZY_ADAM        slot0 = m, slot1 = v, params = hbk_adam_t         (hbk_group_lookup_bwd_adam)
+ *     HBK_APPLY_FTRL             slot0 = accum, slot1 = linear, params = hbk_ftrl_t (hbk_group_lookup_bwd_ftrl)
+ *     HBK_APPLY_ROWWISE_ADAGRAD  slot0 = accum [rows, 1], params = hbk_rowwise_adagrad_t
+ *                                                                       (hbk_group_lookup_bwd_rowwise_adagrad)
+ * slot0 / slot1 are arrays of n_cols device pointers (NULL where the rule has no such slot), params is NULL
+ * for SGD and Adagrad.  Table and table-shaped slots share table_pitch (0 = dim).  hbk_adam_t.finish advances
+ * the beta powers after the step, in stream order, also with n_cols == 0.  The gradient is not clipped.
+ * One launch per 64 columns, no workspace, no host read of device memory: the call can be captured.  Refused
+ * before the first launch (HBK_INVALID_ARGUMENT): an unknown rule; a NULL table, unique_rows, grad_rows,
+ * n_unique or needed slot of a column with capacity > 0; capacity < 0 or >= 2^30; dim < 1, or > 256 (> 64
+ * unless dim % 4 == 0 and table, slots, grad_rows and the pitch are 16-byte aligned); a table or slot named
+ * twice; the hyperparameters and the lr the rule's own entry refuses (lr == 0 for every rule; a non-finite lr
+ * but for Lazy Adam; FTRL: lr <= 0).  Detected by the presence of the symbol; the structs above and the
+ * version are those of 0.2.0. */
+#define HBK_APPLY_LAZY_ADAM 3
+#define HBK_APPLY_FTRL 4
+#define HBK_APPLY_ROWWISE_ADAGRAD 5
+typedef struct {
+  float* table;                /* device [rows, dim], table_pitch floats between rows */
+  int64_t rows;
+  int32_t dim;
+  int32_t table_pitch;         /* 0 = dim */
+  const int64_t* unique_rows;  /* device [capacity] */
+  const float* grad_rows;      /* device [capacity, dim], contiguous */
+  const int32_t* n_unique;     /* device [1] */
+  int64_t capacity;
+} hbk_slices_column_t;
+int hbk_sparse_apply_slices_n(int32_t n_cols, const hbk_slices_column_t* cols, int32_t apply,
+                              float* const* slot0, float* const* slot1, const void* params, float lr,
+                              hbk_stream_t stream);
+
+/* Gradients of REPLICATED tables across ranks, in their dense form (the reference's
+ * TRAINABLE_REPLICATED_SMALL, training/gradient.py:131-141): every rank scatters its IndexedSlices into one
+ * bucket, ONE allreduce sums the buckets, and each table's block of the bucket is then read back as
+ * IndexedSlices with holes -- which hbk_sparse_apply_slices_n takes as they are.
+ *
+ * The bucket is one contiguous fp32 buffer of bucket_floats floats that the caller lays out: per table a
+ * block [rows, dim] (contiguous rows; start every block on a 16-byte boundary to keep 16-byte lanes) and,
+ * behind all blocks, per table `touched`, one fp32 word per row.  cols[c].block and cols[c].touched point into
+ * it; no two of these ranges may overlap.
+ *
+ * hbk_replica_grads_pack_n: clears the whole bucket to +0.0f on the stream (a memset node: capturable), then,
+ * one launch per 64 columns, for every u < n_unique[0] (read on the device, clamped to [0, capacity]) with
+ * r = unique_rows[u] inside [0, rows):
+ *     block[r, :] = grad_rows[u, :]        touched[r] = 1.0f
+ * A bit copy: rows are distinct (not checked), so these are plain stores, no atomics.  Entries at or after
+ * n_unique are not read; an entry outside [0, rows) stores nothing.  A lane group per slice row, sized from the
+ * width: 16-byte lanes when dim % 4 == 0 and grad_rows and block are 16-byte aligned, else 4-byte lanes.
+ * Refused before the memset: a NULL unique_rows, grad_rows or n_unique of a column with capacity > 0; a NULL
+ * block or touched of a column with rows > 0; capacity < 0 or >= 2^30; rows < 0 or >= 2^31; dim < 1 or beyond
+ * the apply's limits (256 as 16-byte lanes, 64 as 4-byte lanes); a NULL bucket; bucket_floats <= 0 or
+ * >= 2^31; a block or touched range that is misaligned, leaves the bucket or overlaps another.
+ *
+ * After the allreduce (SUM, in place; a row is touched when any rank touched it):
+ * hbk_replica_grads_rows_n, one launch per 64 columns:
+ *     urows[r] = touched[r] != 0 ? r : -1     for every r in [0, rows)
+ * (urows int64 [rows]; the word holds the number of ranks that touched row r times the scale the allreduce
+ * applied to the whole bucket: > 0 for a mean or a sum, < 0 under a negative scale).  With a device int32 that holds `rows` as n_unique, (urows, block, rows) is table c's
+ * IndexedSlices with holes: no compaction, no copy.  Reads touched, writes urows; block, unique_rows, grad_rows
+ * and n_unique are not looked at.  Detected by the presence of the symbols. */
+typedef struct {
+  const int64_t* unique_rows;  /* device [capacity] */
+  const float* grad_rows;      /* device [capacity, dim], contiguous */
+  const int32_t* n_unique;     /* device [1] */
+  int64_t capacity;
+  int64_t rows;
+  int32_t dim;
+  float* block;                /* inside the bucket: [rows, dim] */
+  float* touched;              /* inside the bucket, behind the blocks: [rows] */
+  int64_t* urows;              /* device [rows]: written by hbk_replica_grads_rows_n */
+} hbk_replica_column_t;
+int hbk_replica_grads_pack_n(int32_t n_cols, const hbk_replica_column_t* cols, float* bucket,
+                             int64_t bucket_floats, hbk_stream_t stream);
+int hbk_replica_grads_rows_n(int32_t n_cols, const hbk_replica_column_t* cols, hbk_stream_t stream);
+
 /* Sequence lookups: a ragged id list WITHOUT a combiner -- the padded [batch, max_len, dim] rows an
  * attention layer reads (DIN / DIEN / BST): docs/tutorial/ranking/data.py:195-224
  * (transform_categorical_non_pooling: tf.sparse.slice to max_varlength ids, tf.sparse.to_dense(default_value=),
