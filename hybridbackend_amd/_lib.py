@@ -103,6 +103,32 @@ class SlicesColumn(C.Structure):
               ('capacity', C.c_int64)]
 
 
+LOWP_BF16, LOWP_FP16 = 1, 2                      # hbk_lowp_*_column_t.table_dtype
+LOWP_ROUND_NEAREST, LOWP_ROUND_STOCHASTIC = 0, 1  # hbk_lowp_rounding_t.mode
+
+
+class LowpLookupColumn(C.Structure):
+  """hbk_lowp_lookup_column_t"""
+  _fields_ = [('table', C.c_void_p), ('table_dtype', C.c_int32), ('dim', C.c_int32), ('rows', C.c_int64),
+              ('ids', C.c_void_p), ('ids_dtype', C.c_int32), ('combiner', C.c_int32), ('n_ids', C.c_int64),
+              ('row_splits', C.c_void_p), ('n_segments', C.c_int64), ('bucket', C.c_int64),
+              ('divisor', C.c_int32), ('out_stride', C.c_int32), ('out', C.c_void_p),
+              ('id_weights', C.c_void_p), ('chunk_elems', C.c_int32), ('reserved', C.c_int32)]
+
+
+class LowpSlicesColumn(C.Structure):
+  """hbk_lowp_slices_column_t"""
+  _fields_ = [('table', C.c_void_p), ('table_dtype', C.c_int32), ('dim', C.c_int32), ('rows', C.c_int64),
+              ('unique_rows', C.c_void_p), ('grad_rows', C.c_void_p), ('n_unique', C.c_void_p),
+              ('capacity', C.c_int64)]
+
+
+class LowpRounding(C.Structure):
+  """hbk_lowp_rounding_t"""
+  _fields_ = [('mode', C.c_int32), ('seed', C.c_uint32), ('step', C.c_void_p), ('advance', C.c_int32),
+              ('reserved', C.c_int32)]
+
+
 class ReplicaColumn(C.Structure):
   """hbk_replica_column_t"""
   _fields_ = [('unique_rows', C.c_void_p), ('grad_rows', C.c_void_p), ('n_unique', C.c_void_p),
@@ -304,6 +330,8 @@ def _declare(l):
     'hbk_group_lookup_bwd_rowwise_adagrad_clipped_workspace_bytes': (sz, [i32, vp, vp]),
     'hbk_group_lookup_bwd_rowwise_adagrad_clipped': (C.c_int, [i32, vp, vp, vp, vp, C.c_float, vp, sz, vp]),
     'hbk_sparse_apply_slices_n': (C.c_int, [i32, vp, i32, vp, vp, vp, C.c_float, vp]),
+    'hbk_lowp_lookup_fwd': (C.c_int, [i32, vp, vp]),
+    'hbk_lowp_apply_slices_n': (C.c_int, [i32, vp, i32, vp, vp, vp, C.c_float, vp, vp]),
     'hbk_replica_grads_pack_n': (C.c_int, [i32, vp, vp, i64, vp]),
     'hbk_replica_grads_rows_n': (C.c_int, [i32, vp, vp]),
     'hbk_group_lookup_bwd_weights': (C.c_int, [i32, vp, vp, vp, vp]),

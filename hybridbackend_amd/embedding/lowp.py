@@ -1,0 +1,339 @@
+"""Low-precision embedding tables: rows stored as ``torch.bfloat16`` / ``torch.float16``, every sum and every
+optimizer slot fp32 (include/hbk.h, "Low-precision tables").
+
+Three classes with the calling conventions of their fp32 counterparts:
+
+  :class:`LowpGroupLookup`   the forward (``hbk_lowp_lookup_fwd``): gathers 2-byte rows, upcasts them exactly and
+                             combines in fp32 -- bit for bit ``GroupLookup`` over ``table.float()``.
+  :class:`LowpSparseApply`   the optimizer step on IndexedSlices (``hbk_lowp_apply_slices_n``): upcast a row, step
+                             it with the arithmetic of ``SparseApply``, round it back -- to nearest even, or
+                             stochastically (bf16), without which a bf16 table does not train: an SGD step below
+                             half an ulp (2^-8 relative) is rounded away every time.
+  :class:`LowpLookupGrad`    the backward and the step: an unmodified ``GroupLookupGrad`` in its emit form (which
+                             never reads the table), then ``LowpSparseApply`` on the slices it returned.
+"""
+import ctypes as C
+import numbers
+
+import numpy as np
+import torch
+
+from hybridbackend_amd import _lib
+from hybridbackend_amd.embedding import optimizer as _opt
+from hybridbackend_amd.embedding.lookup import GroupLookup, GroupLookupGrad, _combiner_code
+from hybridbackend_amd.embedding.sparse_apply import _APPLY
+
+_DTYPES = {torch.bfloat16: _lib.LOWP_BF16, torch.float16: _lib.LOWP_FP16}
+_ROUNDING = {'nearest': _lib.LOWP_ROUND_NEAREST, 'stochastic': _lib.LOWP_ROUND_STOCHASTIC}
+
+
+def _bad(msg):
+  return _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT, msg)
+
+
+def _require_lowp_tables(tables, what):
+  """``tables`` as a list of bf16 / fp16 ``[rows, dim]`` device tensors (the dtype is looked at first: an fp32
+  table is refused by name wherever it lives)."""
+  tables = list(tables)
+  for c, t in enumerate(tables):
+    if not isinstance(t, torch.Tensor) or t.dtype not in _DTYPES or t.dim() != 2:
+      raise _bad(f'{what}: table {c} must be a torch.bfloat16 or torch.float16 [rows, dim] tensor, got '
+                 f'{getattr(t, "dtype", type(t).__name__)} (fp32 tables go through GroupLookup / SparseApply)')
+    _lib.require_device_tensor(t, 'embedding weights')
+  return tables
+
+
+def check_rounding(rounding, seed, dtypes, what):
+  """The rounding mode's code and the seed as a uint32; 'stochastic' is defined for bf16 tables only."""
+  if rounding not in _ROUNDING:
+    raise _bad(f"{what}: rounding must be 'nearest' or 'stochastic', got {rounding!r}")
+  if isinstance(seed, bool) or not isinstance(seed, numbers.Integral) or not 0 <= int(seed) < 2 ** 32:
+    raise _bad(f'{what}: seed must be an integer in [0, 2^32), got {seed!r}')
+  if rounding == 'stochastic' and any(d != torch.bfloat16 for d in dtypes):
+    raise _bad(f"{what}: rounding='stochastic' is defined for torch.bfloat16 tables only")
+  return _ROUNDING[rounding], int(seed)
+
+
+class LowpGroupLookup(GroupLookup):
+  """A group of N embedding columns over 16-bit tables, looked up with one launch per 64 columns and kind.
+
+  Args:
+    tables: list of ``torch.bfloat16`` / ``torch.float16`` ``[rows, dim]`` device tensors (a call may mix them).
+    buckets, combiners, divisor: as :class:`GroupLookup`.
+    chunk_elems: None (the default lane width: 8 from dim 64 on, else 4), 4 or 8: elements a lane moves where the
+      column allows it (8: ``dim % 8 == 0`` and a 16-byte aligned table).  A pure speed choice: the result does not
+      depend on it.
+
+  The calling convention is :class:`GroupLookup`'s -- ``bind``, ``__call__(ids, row_splits=None, outs=None,
+  sp_weights=None)``, ``launch()``, outputs as column blocks of a wider tensor -- and the result is, bit for bit,
+  ``GroupLookup`` over ``[t.float() for t in tables]`` with the same arguments.  ``max_norms`` and ``hot_rows`` do
+  not exist here: a clip is refused, and the attributes a ``GroupLookupGrad`` reads of its lookup say "none"."""
+
+  def __init__(self, tables, buckets=None, combiners='sum', divisor=1, max_norms=None, chunk_elems=None):   # pylint: disable=super-init-not-called
+    if max_norms is not None and not (isinstance(max_norms, (list, tuple)) and all(x is None for x in max_norms)):
+      raise _bad('LowpGroupLookup: max_norms is not supported for 16-bit tables (the clip reads and the clipped '
+                 'step writes fp32 rows)')
+    if chunk_elems not in (None, 4, 8):
+      raise _bad(f'LowpGroupLookup: chunk_elems must be None, 4 or 8, got {chunk_elems!r}')
+    self.tables = _require_lowp_tables(tables, 'LowpGroupLookup')
+    self._lib = _lib.lib()
+    n = len(self.tables)
+    if buckets is None:
+      buckets = [0] * n
+    if isinstance(combiners, (str, int)) or combiners is None:
+      combiners = [combiners] * n
+    self.buckets = [int(b or 0) for b in buckets]
+    self.combiners = [_combiner_code(c) for c in combiners]
+    self.divisor = int(divisor)
+    # what GroupLookupGrad reads of its lookup: no clip, no hot-row bookkeeping
+    self.max_norms = [0.0] * n
+    self.max_norms_c = None
+    self._auto_hot = []
+    self._auto_state = None
+    self._cols = (_lib.LowpLookupColumn * n)()
+    self._cols_np = np.frombuffer(self._cols, dtype=np.dtype(_lib.LowpLookupColumn)) if n else None
+    self._dims = [int(t.shape[1]) for t in self.tables]
+    for c, t in enumerate(self.tables):
+      col = self._cols[c]
+      col.table = t.data_ptr()
+      col.table_dtype = _DTYPES[t.dtype]
+      col.rows = t.shape[0]
+      col.dim = t.shape[1]
+      col.bucket = self.buckets[c]
+      col.divisor = self.divisor
+      col.combiner = self.combiners[c]
+      col.chunk_elems = chunk_elems or 0
+
+  def launch(self, stream=None):
+    """Enqueue the bound lookup on `stream` (a torch stream; default: current)."""
+    if stream is None:
+      s = _lib.current_stream(self.tables[0].device if self.tables else None)
+    else:
+      s = C.c_void_p(stream.cuda_stream)
+    _lib.check(self._lib.hbk_lowp_lookup_fwd(len(self.tables), self._cols, s))
+
+
+class LowpSparseApply:
+  """The sparse optimizer step of N 16-bit tables from caller-held IndexedSlices, one launch per 64 tables.
+
+  Args:
+    tables: list of ``torch.bfloat16`` / ``torch.float16`` ``[rows, dim]`` device tensors, stepped in place.
+    accums / moments, adam / ftrl_slots, ftrl / row_accums, rowwise_adagrad: the optimizer slots and objects, as
+      :class:`SparseApply` takes them.  Slots are FP32 and have the table's SHAPE (row-wise Adagrad: ``[rows, 1]``).
+    rounding: ``'nearest'`` (ties to even; bf16: the bits of torch's ``float32 -> bfloat16`` cast) or
+      ``'stochastic'`` (bf16 only): ``(u + 16 bits of noise) >> 16`` on the fp32 pattern, unbiased, with noise that
+      is a pure function of ``(seed, step counter, column, row, element)`` (include/hbk.h).
+    seed: the noise's seed, an integer in [0, 2^32).
+
+  A stepped row is ``round(rule(upcast(row), slots, g))`` with the formulas, rounding and operation order of
+  :class:`SparseApply`; with ``'nearest'`` table and slots equal ``SparseApply`` on ``table.float()``, cast, bit for
+  bit.  The object owns the device step counter (``step_counter``, one int32 word read as uint32): a call with
+  ``finish=True`` advances it once, behind the apply in stream order, so replays of a captured graph draw fresh
+  noise; ``'nearest'`` never touches it.  No workspace and no host read: a call can be captured in a graph, and
+  ``launch()`` repeats it."""
+
+  _NEEDS = 'LowpSparseApply(tables, {slots})'
+
+  def __init__(self, tables, accums=None, moments=None, adam=None, ftrl_slots=None, ftrl=None, row_accums=None,
+               rowwise_adagrad=None, rounding='nearest', seed=0):
+    self.tables = _require_lowp_tables(tables, 'LowpSparseApply')
+    mode, seed = check_rounding(rounding, seed, [t.dtype for t in self.tables], 'LowpSparseApply')
+    self.rounding, self.seed = rounding, seed
+    self._lib = _lib.lib()
+    n = len(self.tables)
+    _opt.bind_all(self, dict(moments=moments, adam=adam, ftrl_slots=ftrl_slots, ftrl=ftrl, row_accums=row_accums,
+                             rowwise_adagrad=rowwise_adagrad), self.tables, 'LowpSparseApply')
+    self._slot_ptrs = {opt.name: opt.ptr_arrays(slots) for opt, slots in _opt.bound(self)}
+    self.accums = list(accums) if accums is not None else None
+    self._accum_ptrs = None
+    if self.accums is not None:
+      if len(self.accums) != n:
+        raise _bad(f'LowpSparseApply: {len(self.accums)} accumulators for {n} tables')
+      for c, (a, t) in enumerate(zip(self.accums, self.tables)):
+        _lib.require_device_tensor(a, 'accumulator')
+        if a.dtype != torch.float32 or a.shape != t.shape:
+          raise _bad(f'accumulator {c} must be fp32 {tuple(t.shape)}')
+      self._accum_ptrs = _lib.ptr_array([a.data_ptr() for a in self.accums])
+    self._cols = (_lib.LowpSlicesColumn * n)()
+    for c, t in enumerate(self.tables):
+      col = self._cols[c]
+      col.table = t.data_ptr()
+      col.table_dtype = _DTYPES[t.dtype]
+      col.rows = t.shape[0]
+      col.dim = t.shape[1]
+    dev = self.tables[0].device if n else torch.device('cuda', torch.cuda.current_device())
+    self.step_counter = torch.zeros(1, dtype=torch.int32, device=dev)
+    # the hbk_lowp_rounding_t of a call with / without the advance (kept alive by this object)
+    self._rounding_c = {f: _lib.LowpRounding(mode, seed, self.step_counter.data_ptr(), 1 if f else 0, 0)
+                        for f in (False, True)}
+    self._slices_key = None
+    self._bound = None
+
+  def __len__(self):
+    return len(self.tables)
+
+  def _check(self, lr, optimizer):
+    two_slot = _opt.two_slot_class(optimizer, self, self._NEEDS)
+    if lr == 0.0:
+      raise _bad('LowpSparseApply: lr must be != 0')
+    if optimizer == 'adagrad' and self.accums is None:
+      raise _bad("optimizer='adagrad' needs LowpSparseApply(tables, accums=...)")
+    return two_slot
+
+  def bind(self, slices):
+    """Point the descriptors at ``slices`` (checked) without stepping."""
+    n = len(self.tables)
+    slices = list(slices)
+    if len(slices) != n:
+      raise _bad(f'LowpSparseApply: {len(slices)} slices for {n} tables')
+    key = tuple(id(x) for s in slices for x in s)
+    if key == self._slices_key and all(
+        x.data_ptr() == q for s, qs in zip(slices, self._slices_ptrs) for x, q in zip(s, qs)):
+      return
+    keep = []
+    for c, (s, t) in enumerate(zip(slices, self.tables)):
+      if len(s) != 3:
+        raise _bad(f'slices[{c}] must be (unique_rows, grad_rows, n_unique)')
+      urows, grows, nu = s
+      for x, what in ((urows, 'unique_rows'), (grows, 'grad_rows'), (nu, 'n_unique')):
+        if not isinstance(x, torch.Tensor):
+          raise _bad(f'slices[{c}].{what} must be a device tensor')
+        _lib.require_device_tensor(x, f'slices[{c}].{what}')
+      if urows.dtype != torch.int64 or urows.dim() != 1:
+        raise _bad(f'slices[{c}].unique_rows must be an int64 vector')
+      cap, dim = int(urows.shape[0]), int(t.shape[1])
+      if grows.dtype != torch.float32 or tuple(grows.shape) != (cap, dim):
+        raise _bad(f'slices[{c}].grad_rows must be fp32 [{cap}, {dim}]')
+      if nu.dtype != torch.int32 or nu.numel() != 1:
+        raise _bad(f'slices[{c}].n_unique must be an int32 device tensor of one element')
+      col = self._cols[c]
+      col.unique_rows = urows.data_ptr()
+      col.grad_rows = grows.data_ptr()
+      col.n_unique = nu.data_ptr()
+      col.capacity = cap
+      keep.append((urows, grows, nu))
+    self._keep = keep
+    self._slices_key = key
+    self._slices_ptrs = [tuple(x.data_ptr() for x in s) for s in keep]
+
+  def __call__(self, slices, lr, optimizer='sgd', finish=True):
+    """slices[c] = ``(unique_rows int64 [capacity], grad_rows fp32 [capacity, dim], n_unique int32 [1])`` on the
+    device, as :class:`SparseApply` takes them: the first ``n_unique`` entries are read (on the device, clamped to
+    the capacity), an entry outside ``[0, rows)`` -- ``-1`` -- touches nothing, rows must be DISTINCT.
+    ``finish=True`` advances Adam's beta powers and the rounding's step counter behind the step."""
+    two_slot = self._check(lr, optimizer)
+    self.bind(slices)
+    self._bound = (float(lr), optimizer, bool(finish))
+    self._step(two_slot, float(lr), optimizer, finish)
+
+  def _step(self, two_slot, lr, optimizer, finish):
+    n = len(self.tables)
+    dev = self.tables[0].device if n else None
+    s0 = s1 = params = None
+    if two_slot is not None:
+      ptrs = self._slot_ptrs[two_slot.name]
+      s0 = ptrs[0]
+      s1 = ptrs[1] if len(ptrs) > 1 else None
+      params = C.byref(getattr(self, two_slot.name).params(finish))
+    elif optimizer == 'adagrad':
+      s0 = self._accum_ptrs
+    _lib.check(self._lib.hbk_lowp_apply_slices_n(n, self._cols, _APPLY[optimizer], s0, s1, params, C.c_float(lr),
+                                                 C.byref(self._rounding_c[bool(finish)]), _lib.current_stream(dev)))
+
+  def launch(self, lr=None, optimizer=None, finish=None):
+    """The step again on the bound slices (refilled in place): one foreign call.  ``lr``, ``optimizer`` and
+    ``finish`` default to the last call's."""
+    if self._slices_key is None or (self._bound is None and (lr is None or optimizer is None or finish is None)):
+      raise _lib.HbkError(_lib.INTERNAL, 'launch() needs a call that bound the slices first')
+    lr = self._bound[0] if lr is None else float(lr)
+    optimizer = self._bound[1] if optimizer is None else optimizer
+    finish = self._bound[2] if finish is None else bool(finish)
+    self._step(self._check(lr, optimizer), lr, optimizer, finish)
+
+
+class LowpLookupGrad:
+  """Backward and optimizer step of a :class:`LowpGroupLookup`, with :class:`GroupLookupGrad`'s calling convention.
+
+  Internally an UNMODIFIED ``GroupLookupGrad`` over the lookup, always called with ``apply_lr=0.0, emit=True`` --
+  the reduce's emit form never reads the table, so every plan, ``deterministic=True`` and weighted columns work
+  unchanged on a table of any element type -- and then a :class:`LowpSparseApply` on the slices it returned.  The
+  split costs a launch and a round trip of ``grad_rows`` through memory that the fused fp32 step does not pay.
+
+  Never give a bare ``GroupLookupGrad`` a lookup over 16-bit tables and a non-zero ``apply_lr``: its fused step
+  (and the slot optimizers' apply) reads and writes ``table`` as fp32 rows of ``4 * dim`` bytes -- on a 16-bit
+  table that corrupts two rows per step and runs past the end of the allocation.  This class is the way to step
+  one, and it cannot reach the fused step: the inner object holds no slots and is only ever asked to emit.
+
+  Args:
+    lookup: the :class:`LowpGroupLookup`.
+    accums / moments, adam / ftrl_slots, ftrl / row_accums, rowwise_adagrad: FP32 slots of the table's shape.
+    deterministic: as :class:`GroupLookupGrad`.
+    rounding, seed: as :class:`LowpSparseApply`."""
+
+  def __init__(self, lookup, accums=None, moments=None, adam=None, ftrl_slots=None, ftrl=None, row_accums=None,
+               rowwise_adagrad=None, deterministic=False, rounding='nearest', seed=0):
+    if not isinstance(lookup, LowpGroupLookup):
+      raise _bad('LowpLookupGrad needs a LowpGroupLookup (fp32 tables go through GroupLookupGrad)')
+    self.lookup = lookup
+    self._apply = LowpSparseApply(lookup.tables, accums=accums, moments=moments, adam=adam, ftrl_slots=ftrl_slots,
+                                  ftrl=ftrl, row_accums=row_accums, rowwise_adagrad=rowwise_adagrad,
+                                  rounding=rounding, seed=seed)
+    # no slots, no accumulators: this object can only emit
+    self._reduce = GroupLookupGrad(lookup, deterministic=deterministic)
+    self._last_emit = True
+
+  @property
+  def step_counter(self):
+    return self._apply.step_counter
+
+  @property
+  def accums(self):
+    return self._apply.accums
+
+  def __getattr__(self, name):
+    # the slot lists and optimizer objects (moments / adam / ...) live with the apply
+    if name in ('_apply', '_reduce'):
+      raise AttributeError(name)
+    for cls in _opt.TWO_SLOT.values():
+      if name in (cls.name, cls.slot_kw):
+        return getattr(self._apply, name)
+    raise AttributeError(name)
+
+  @staticmethod
+  def _refuse_weight_grads(weight_grads):
+    if weight_grads is not False and weight_grads is not None:
+      raise _bad('LowpLookupGrad: weight_grads is not supported for 16-bit tables (hbk_group_lookup_bwd_weights '
+                 'reads fp32 rows)')
+
+  def __call__(self, ids, grads, row_splits=None, apply_lr=0.0, optimizer='sgd', emit=True, grad_block=None,
+               sp_weights=None, finish=True, weight_grads=False):
+    """As :meth:`GroupLookupGrad.__call__`; returns per column ``(unique_rows, grad_rows, n_unique)``, equal to the
+    fp32 object's.  ``emit=False`` (with ``apply_lr``) is accepted: the slices are written all the same (the step
+    reads them) and the returned triples are ``(None, None, n_unique)``.  ``weight_grads`` is refused."""
+    self._refuse_weight_grads(weight_grads)
+    if not emit and apply_lr == 0.0:
+      raise _bad('emit=False needs apply_lr != 0')
+    if apply_lr != 0.0:
+      self._apply._check(apply_lr, optimizer)   # (before the reduce: a refused call writes nothing)
+    else:
+      _opt.two_slot_class(optimizer)
+    r = self._reduce(ids, grads, row_splits, apply_lr=0.0, optimizer='sgd', emit=True, grad_block=grad_block,
+                     sp_weights=sp_weights)
+    if apply_lr != 0.0:
+      self._apply(r, apply_lr, optimizer, finish)
+    else:
+      self._apply.bind(r)   # (a later launch() may step)
+    self._last_emit = bool(emit)
+    return r if emit else [(None, None, t[2]) for t in r]
+
+  def launch(self, apply_lr=0.0, optimizer='sgd', finish=True):
+    """The backward of the LAST call again on the same tensors, then the step when ``apply_lr`` != 0: two foreign
+    calls.  Same emit mode as that call; returns the same result views."""
+    if not self._last_emit and apply_lr == 0.0:
+      raise _bad('emit=False needs apply_lr != 0')
+    if apply_lr != 0.0:
+      self._apply._check(apply_lr, optimizer)
+    r = self._reduce.launch(0.0)
+    if apply_lr != 0.0:
+      self._apply.launch(apply_lr, optimizer, finish)
+    return r if self._last_emit else [(None, None, t[2]) for t in r]

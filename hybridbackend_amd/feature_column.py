@@ -144,7 +144,7 @@ class _TableLayer:
   W > 1), the optimizer slots, and the checkpoints."""
 
   def _init_tables(self, columns, device, coll, batch_size, init, initial_accumulator_value, optimizer,
-                   adam, ftrl, train=True, rowwise_adagrad=None):
+                   adam, ftrl, train=True, rowwise_adagrad=None, table_dtype=None):
     self.columns = list(columns)
     self.device = torch.device(device)
     self.coll = coll
@@ -169,10 +169,16 @@ class _TableLayer:
       is_sharded = is_sharded and world > 1
       self.sharded.append(is_sharded)
       self.weights.append(init(col, rows if is_sharded else col.num_buckets, self.device))
+    # 16-bit tables (DenseFeatures(table_dtype=)): init's result rounded to nearest; every slot below stays
+    # fp32 and is built from an fp32 stand-in of the table's shape (zero strides: it owns one word)
+    like = self.weights
+    if table_dtype is not None:
+      self.weights = [w.to(table_dtype) for w in self.weights]
+      like = [torch.empty((), dtype=torch.float32, device=self.device).expand(w.shape) for w in self.weights]
     # Adagrad accumulators (tf.train.AdagradOptimizer: initial_accumulator_value = 0.1)
     self.accums = None
     if initial_accumulator_value is not None:
-      self.accums = [torch.full_like(w, float(initial_accumulator_value)) for w in self.weights]
+      self.accums = [torch.full_like(w, float(initial_accumulator_value)) for w in like]
     if optimizer is not None:
       _opt.two_slot_class(optimizer)   # (refuses unknown names)
     # slot optimizers: the optimizer named (its defaults) or passed, fresh slots for every table
@@ -186,7 +192,7 @@ class _TableLayer:
       if optimizer == cls.name or opt is not None:
         opt = opt if opt is not None else cls.default(self.device)
         setattr(self, cls.name, opt)
-        setattr(self, cls.slot_kw, [opt.slots_like(w) for w in self.weights])
+        setattr(self, cls.slot_kw, [opt.slots_like(w) for w in like])
     self._hash = [c for c in range(len(self.columns)) if self.hash_tables[c] is not None]
     self._rep = [c for c in range(len(self.columns)) if not self.sharded[c] and c not in self._hash]
     self._shd = [c for c in range(len(self.columns)) if self.sharded[c] and c not in self._hash]
@@ -502,6 +508,15 @@ class DenseFeatures(_TableLayer):
       caller aggregates.  At W = 1 it changes nothing.  A replicated column wider than the apply takes (256
       floats, 64 when not a multiple of 4) is refused at construction.
     replicated_scale: what multiplies the summed gradients; None: ``1 / W``, the mean of the reference.
+    table_dtype: None (fp32 tables: nothing below applies), ``torch.bfloat16`` or ``torch.float16``: the tables are
+      stored in 16 bits -- ``init``'s result rounded to nearest -- with fp32 sums in the forward
+      (``hb.embedding.LowpGroupLookup``) and fp32 accumulators and slots in the step
+      (``hb.embedding.LowpLookupGrad``: the reduce's emit form, then an apply of its own).  ``weights[c]`` are the
+      16-bit tensors, and ``variables()`` / ``save`` / ``restore`` carry them as they are.  One rank only (``coll``
+      None or of one rank); a hash-keyed column, a column with ``max_norm`` and a column wider than 64 whose block
+      does not start on a multiple of 4 floats are refused by name; ``backward(weight_grads=True)`` is refused.
+    table_rounding: ``'nearest'``, or ``'stochastic'`` (bf16 only) -- what lets a bf16 table train on steps
+      smaller than half an ulp; table_seed: the seed of its noise.
 
   Hash-keyed columns (:class:`HashEmbeddingColumn`) mix freely with bucketed ones; column order decides the
   block offsets.  ``hash_tables[c]`` is the column's :class:`HashTable` (None for a bucketed column) and
@@ -515,9 +530,13 @@ class DenseFeatures(_TableLayer):
 
   def __init__(self, columns, device, coll=None, batch_size=0, init=None,
                initial_accumulator_value=None, optimizer=None, adam=None, ftrl=None, train=True,
-               rowwise_adagrad=None, aggregate_replicated=False, replicated_scale=None):
+               rowwise_adagrad=None, aggregate_replicated=False, replicated_scale=None, table_dtype=None,
+               table_rounding='nearest', table_seed=0):
+    self.table_dtype = table_dtype
+    if table_dtype is not None:
+      self._check_lowp(columns, coll, table_dtype, table_rounding, table_seed)
     self._init_tables(columns, device, coll, batch_size, init, initial_accumulator_value, optimizer,
-                      adam, ftrl, train, rowwise_adagrad)
+                      adam, ftrl, train, rowwise_adagrad, table_dtype)
     self._init_replica(aggregate_replicated, replicated_scale, 'DenseFeatures')
     for c in self._hash:
       col = self.columns[c]
@@ -539,7 +558,16 @@ class DenseFeatures(_TableLayer):
     pick = lambda idx, xs: [xs[c] for c in idx]   # noqa: E731
     two_slot_kw = self._two_slot_kw
     self._lookup = self._grad = self._sharded = None
-    if self._rep:
+    if self._rep and table_dtype is not None:
+      # 16-bit tables: the same two roles, so that __call__ and backward do not fork
+      from hybridbackend_amd.embedding.lowp import LowpGroupLookup, LowpLookupGrad   # pylint: disable=import-outside-toplevel
+      self._lookup = LowpGroupLookup(pick(self._rep, self.weights),
+                                     [self.columns[c].num_buckets for c in self._rep],
+                                     [self.columns[c].combiner for c in self._rep])
+      self._grad = LowpLookupGrad(
+        self._lookup, pick(self._rep, self.accums) if self.accums is not None else None,
+        rounding=table_rounding, seed=table_seed, **two_slot_kw(self._rep))
+    elif self._rep:
       self._lookup = GroupLookup(pick(self._rep, self.weights),
                                  [self.columns[c].num_buckets for c in self._rep],
                                  [self.columns[c].combiner for c in self._rep],
@@ -572,6 +600,30 @@ class DenseFeatures(_TableLayer):
     self._hash_grad = GroupLookupGrad(
       self._hash_lookup.lookup, [self.accums[c] for c in self._hash] if self.accums is not None else None,
       **self._two_slot_kw(self._hash))
+
+  @staticmethod
+  def _check_lowp(columns, coll, table_dtype, table_rounding, table_seed):
+    """Everything ``table_dtype`` refuses, before any table is allocated."""
+    from hybridbackend_amd.embedding.lowp import check_rounding   # pylint: disable=import-outside-toplevel
+    if table_dtype not in (torch.bfloat16, torch.float16):
+      raise _bad(f'DenseFeatures(table_dtype=): None, torch.bfloat16 or torch.float16, got {table_dtype!r}')
+    check_rounding(table_rounding, table_seed, [table_dtype], 'DenseFeatures(table_dtype=)')
+    if coll is not None and coll.world_size > 1:
+      raise _bad(f'DenseFeatures(table_dtype={table_dtype}): 16-bit tables are kept on one rank only, the layer '
+                 f'spans {coll.world_size} (sharded and replicated-at-W>1 tables stay fp32)')
+    off = 0
+    for col in columns:
+      if _is_hash(col):
+        raise _bad(f'DenseFeatures(table_dtype={table_dtype}): column {col.key!r} is hash-keyed; hash tables '
+                   'stay fp32')
+      if col.max_norm is not None:
+        raise _bad(f'DenseFeatures(table_dtype={table_dtype}): column {col.key!r} has max_norm; the clip reads '
+                   'and the clipped step writes fp32 rows')
+      if col.dimension > 64 and off % 4 != 0:
+        raise _bad(f'DenseFeatures(table_dtype={table_dtype}): column {col.key!r} ({col.dimension} wide at float '
+                   f'{off} of the block) cannot be addressed in place: a row of more than 64 elements must start '
+                   'on a 16-byte boundary of the output row; reorder the columns')
+      off += col.dimension
 
   def _weights(self, features):
     """Per column its fp32 per-id weights (weight_feature_key) or None; None when no column has any."""

@@ -621,6 +621,128 @@ int hbk_sparse_apply_slices_n(int32_t n_cols, const hbk_slices_column_t* cols, i
                               float* const* slot0, float* const* slot1, const void* params, float lr,
                               hbk_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Low-precision tables: rows stored as bf16 or fp16 (2 bytes per element), every sum and every optimizer
+ * slot fp32.  Two entries, both detected by the presence of the symbol (the structs above and the version
+ * are those of 0.2.0): a forward of its own and the optimizer step on IndexedSlices the caller holds.  The
+ * backward between them is hbk_group_lookup_bwd_apply in its emit form (apply_lr = 0), which never reads the
+ * table (hbk_lookup_grad_column_t.table: "only touched when apply_lr != 0") and so serves a table of any
+ * element type.  NEVER hand a 16-bit table to an entry that steps (apply_lr != 0, the slot entries,
+ * hbk_sparse_apply_slices_n): they read and write `table` as fp32.
+ *
+ * Element types (hbk_lowp_*_column_t.table_dtype; a call may mix them):
+ *     HBK_LOWP_BF16   1 sign, 8 exponent, 7 fraction bits: the upper half of the fp32 pattern
+ *     HBK_LOWP_FP16   IEEE binary16
+ *   upcast(x) is exact for both: bf16 bits << 16 as an fp32 pattern; (float)(_Float16)x, subnormals included.
+ *
+ * FORWARD  hbk_lowp_lookup_fwd: per column, with e_j = upcast(table[row(j), :]) and row(j) as in
+ *   hbk_group_lookup_fwd (bucket: floormod; divisor; rows outside [0, rows) are zero rows),
+ *     row_splits == NULL:                 out[s] = e_s                                  (the combiner is ignored)
+ *       with id_weights:   sum   out[s] = w_s e_s
+ *                          mean  out[s] = (w_s e_s) / w_s
+ *                          sqrtn out[s] = (w_s e_s) / sqrtf(w_s * w_s)
+ *                          an invalid row or a zero divisor gives a zero row
+ *     row_splits != NULL:  acc = +0; for j in id order: acc = acc + e_j              (n = all ids of the segment)
+ *                          sum   out[s] = acc;  mean acc / (float)n;  sqrtn acc / sqrtf((float)n);  n == 0: zeros
+ *       with id_weights:   acc = acc + e_j * w_j, W = W + w_j (sqrtn: Q = Q + w_j * w_j), ids of VALID rows only
+ *                          sum   out[s] = acc;  mean acc / W;  sqrtn acc / sqrtf(Q);  a zero divisor: zeros
+ *   every product and sum a separately rounded fp32 operation.  This is hbk_group_lookup_fwd on the table upcast
+ *   to fp32, bit for bit; per-element sums are independent, so the lane layout cannot change a bit.
+ *   Rows move as chunks of 4 elements (8 bytes) per lane -- or 8 elements (16 bytes) where dim % 8 == 0 and the
+ *   table is 16-byte aligned: by default (chunk_elems = 0) from dim 64 on, with chunk_elems = 8 wherever possible,
+ *   with chunk_elems = 4 never -- when dim % 4 == 0, the table is 8-byte aligned and `out` and its stride are
+ *   16-byte aligned: dim <= 256.  Otherwise one element per lane: dim <= 64.
+ *   One launch per 64 columns and kind (one id per segment / ragged), plain loads and stores, no atomics, no
+ *   workspace, no host read: the call can be captured.  There is no max_norm, no segmented table, no output
+ *   permutation and no fp16 output here.  Refused before the first launch (HBK_INVALID_ARGUMENT, the column
+ *   named): an unknown table_dtype, ids_dtype or combiner; chunk_elems not 0, 4 or 8; dim < 1 or beyond the
+ *   bounds above; a table at an odd address or an `out` not 4-byte aligned; a NULL table (rows > 0), ids
+ *   (n_ids > 0) or out of a column with segments; negative sizes, >= 2^31 ids or segments; bucket < 0;
+ *   divisor < 1; out_stride != 0 and < dim; n_segments != n_ids without row_splits.  n_cols == 0 answers OK. */
+#define HBK_LOWP_BF16 1
+#define HBK_LOWP_FP16 2
+typedef struct {
+  const void* table;         /* device [rows, dim] of 2-byte elements, contiguous rows */
+  int32_t table_dtype;       /* HBK_LOWP_BF16 | HBK_LOWP_FP16 */
+  int32_t dim;
+  int64_t rows;
+  const void* ids;           /* device [n_ids] */
+  int32_t ids_dtype;         /* HBK_INT32 | HBK_INT64 */
+  int32_t combiner;          /* HBK_COMBINER_* */
+  int64_t n_ids;
+  const int32_t* row_splits; /* device [n_segments + 1] or NULL */
+  int64_t n_segments;        /* == n_ids when row_splits == NULL */
+  int64_t bucket;            /* 0 = ids are row numbers already */
+  int32_t divisor;           /* >= 1 */
+  int32_t out_stride;        /* floats between rows of `out`; 0 = dim */
+  float* out;                /* device fp32 [n_segments, dim] */
+  const float* id_weights;   /* device fp32 [n_ids] or NULL */
+  int32_t chunk_elems;       /* 0 = the default (8 from dim 64 on, else 4); 4 or 8: elements per lane where the column allows it */
+  int32_t reserved;          /* 0 */
+} hbk_lowp_lookup_column_t;
+int hbk_lowp_lookup_fwd(int32_t n_cols, const hbk_lowp_lookup_column_t* cols, hbk_stream_t stream);
+
+/* APPLY  hbk_lowp_apply_slices_n: the contract of hbk_sparse_apply_slices_n (distinct rows; an entry outside
+ *   [0, rows), -1 included, touches nothing; n_unique read on the device and clamped to [0, capacity]; the five
+ *   rules; one launch per 64 columns, no workspace, no host read; hbk_adam_t.finish advances the beta powers
+ *   behind the step, also with n_cols == 0) on tables of 2-byte elements with contiguous rows.  For a stepped
+ *   row r:
+ *       w32          = upcast(table[r, :])
+ *       (w32', s')   = rule(w32, slots[r], g)      formulas, rounding and operation order of the fp32 entry
+ *       slots[r]     = s'                          fp32, stored as the fp32 entry stores them
+ *       table[r, :]  = round(w32')
+ *   so that with rounding 0 the table equals the fp32 entry's result on upcast(table), cast, bit for bit.
+ *   A row is split over lanes as in the fp32 entry: 4 elements per lane when dim % 4 == 0, the table is 8-byte
+ *   and the slots and grad_rows are 16-byte aligned (dim <= 256), else one element per lane (dim <= 64).  Row-wise
+ *   Adagrad's sum of g * g follows that layout (each lane's chunk in element order, then the butterfly), as there.
+ *
+ *   round, HBK_LOWP_ROUND_NEAREST (0): round to nearest, ties to even.  bf16, on the fp32 pattern u of w32':
+ *       a NaN stays a NaN (0x7FC0 today; the payload is not specified); otherwise
+ *       out = (u + 0x7FFF + ((u >> 16) & 1)) >> 16      (infinities stay; a carry out of the largest finite value
+ *                                                        gives infinity)
+ *     fp16: the (_Float16) conversion.
+ *   round, HBK_LOWP_ROUND_STOCHASTIC (1): bf16 only (refused with an fp16 column).
+ *       exponent field of u all ones: as NEAREST; otherwise  out = (u + (noise_k & 0xFFFF)) >> 16
+ *     (no wrap-around is possible there).  It rounds in magnitude, is unbiased for both signs, and an exactly
+ *     representable value never moves.  A carry into the exponent, infinity at the very top included, is
+ *     correct behaviour.  noise_k is a pure function of the call's seed, the step counter, the column's index c in
+ *     the call, the row r (int64) and the element index k in the row, all arithmetic modulo 2^32:
+ *       fmix32(h): h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16   (murmur3's finalizer)
+ *       base    = fmix32(seed ^ fmix32(step + 0x9E3779B9 * (c + 1)))
+ *       rowh    = fmix32(fmix32(base ^ lo32(r)) ^ hi32(r))
+ *       noise_k = fmix32(rowh + 0x9E3779B9 * (k + 1))
+ *     step = rounding->step[0], a device uint32 the call reads ON THE DEVICE; with rounding->advance != 0 a
+ *     one-thread launch behind the apply adds 1 to it in stream order (also with n_cols == 0), so replays of a
+ *     captured graph draw fresh noise and a run is reproducible.  NEAREST never reads or writes the counter.
+ *   rounding == NULL means NEAREST.
+ *   Refused before the first launch (HBK_INVALID_ARGUMENT): what hbk_sparse_apply_slices_n refuses (an unknown
+ *   rule; a NULL table, unique_rows, grad_rows, n_unique or needed slot of a column with capacity > 0;
+ *   capacity < 0 or >= 2^30; dim < 1 or beyond the bounds above; a table or slot named twice; lr == 0 and the
+ *   hyperparameters the rule's own entry refuses), an unknown table_dtype or rounding mode, a table at an odd
+ *   address, STOCHASTIC with an fp16 column, STOCHASTIC with a NULL or misaligned step counter. */
+#define HBK_LOWP_ROUND_NEAREST 0
+#define HBK_LOWP_ROUND_STOCHASTIC 1
+typedef struct {
+  void* table;                 /* device [rows, dim] of 2-byte elements, contiguous rows */
+  int32_t table_dtype;         /* HBK_LOWP_BF16 | HBK_LOWP_FP16 */
+  int32_t dim;
+  int64_t rows;
+  const int64_t* unique_rows;  /* device [capacity] */
+  const float* grad_rows;      /* device fp32 [capacity, dim], contiguous */
+  const int32_t* n_unique;     /* device [1] */
+  int64_t capacity;
+} hbk_lowp_slices_column_t;
+typedef struct {
+  int32_t mode;                /* HBK_LOWP_ROUND_* */
+  uint32_t seed;
+  uint32_t* step;              /* device uint32 [1]; STOCHASTIC only */
+  int32_t advance;             /* != 0: step[0] += 1 behind the apply (STOCHASTIC only) */
+  int32_t reserved;            /* 0 */
+} hbk_lowp_rounding_t;
+int hbk_lowp_apply_slices_n(int32_t n_cols, const hbk_lowp_slices_column_t* cols, int32_t apply,
+                            float* const* slot0, float* const* slot1, const void* params, float lr,
+                            const hbk_lowp_rounding_t* rounding, hbk_stream_t stream);
+
 /* Gradients of REPLICATED tables across ranks, in their dense form (the reference's
  * TRAINABLE_REPLICATED_SMALL, training/gradient.py:131-141): every rank scatters its IndexedSlices into one
  * bucket, ONE allreduce sums the buckets, and each table's block of the bucket is then read back as
