@@ -129,6 +129,22 @@ class LowpRounding(C.Structure):
               ('reserved', C.c_int32)]
 
 
+LOWP_WIRE_TABLE, LOWP_WIRE_FLOAT = 0, 1   # hbk_sharded_set_table_dtypes' wire
+
+
+class LowpGatherColumn(C.Structure):
+  """hbk_lowp_gather_column_t"""
+  _fields_ = [('table', C.c_void_p), ('dim', C.c_int32), ('ids_dtype', C.c_int32), ('rows', C.c_int64),
+              ('ids', C.c_void_p), ('n_ids', C.c_int64), ('bucket', C.c_int64), ('divisor', C.c_int32),
+              ('out_stride', C.c_int32), ('out', C.c_void_p)]
+
+
+class LowpLookupRunsColumn(C.Structure):
+  """hbk_lowp_lookup_runs_column_t"""
+  _fields_ = [('col', LowpLookupColumn), ('run_start', C.c_void_p), ('run_base', C.c_void_p),
+              ('n_runs', C.c_int32), ('reserved', C.c_int32)]
+
+
 class ReplicaColumn(C.Structure):
   """hbk_replica_column_t"""
   _fields_ = [('unique_rows', C.c_void_p), ('grad_rows', C.c_void_p), ('n_unique', C.c_void_p),
@@ -332,6 +348,9 @@ def _declare(l):
     'hbk_sparse_apply_slices_n': (C.c_int, [i32, vp, i32, vp, vp, vp, C.c_float, vp]),
     'hbk_lowp_lookup_fwd': (C.c_int, [i32, vp, vp]),
     'hbk_lowp_apply_slices_n': (C.c_int, [i32, vp, i32, vp, vp, vp, C.c_float, vp, vp]),
+    'hbk_lowp_gather_rows_n': (C.c_int, [i32, vp, vp]),
+    'hbk_lowp_lookup_fwd_runs': (C.c_int, [i32, vp, vp]),
+    'hbk_sharded_set_table_dtypes': (C.c_int, [vp, vp, i32]),
     'hbk_replica_grads_pack_n': (C.c_int, [i32, vp, vp, i64, vp]),
     'hbk_replica_grads_rows_n': (C.c_int, [i32, vp, vp]),
     'hbk_group_lookup_bwd_weights': (C.c_int, [i32, vp, vp, vp, vp]),

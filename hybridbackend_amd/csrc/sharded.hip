@@ -553,6 +553,10 @@ struct hbk_sharded {
   hbk::SlotPair ftrl;   // FTRL's accum / linear shards (hbk_sharded_set_ftrl_slots)
   hbk::SlotPair rowwise;   // row-wise Adagrad's [rows_local, 1] accumulators (hbk_sharded_set_rowwise_adagrad_slots)
   std::vector<float> max_norms;   // [N] the columns' max_norm (hbk_sharded_set_max_norms; 0: not clipped)
+  std::vector<int32_t> lowp;      // [N] HBK_LOWP_BF16 / _FP16: the shards hold 2-byte rows (hbk_sharded_set_table_dtypes),
+                                  // or empty: fp32 shards
+  bool lowp_wire16 = false;       // ... and the forward's rows cross the wire in those 16 bits (HBK_LOWP_WIRE_TABLE):
+                                  // the gather writes and the stitch reads 2-byte elements at the fused fp16 wire's offsets
   std::vector<hbk_sharded_hash_t> hash;   // [N] the hash columns' tables (hbk_sharded_set_hash_tables; keys_cache
                                           // NULL: an ordinary column), or empty
   bool any_hash = false;
@@ -759,6 +763,16 @@ extern "C" int hbk_sharded_destroy(hbk_sharded_t p) {
 
 namespace hbk {
 namespace {
+
+// 16-bit shards (hbk_sharded_set_table_dtypes): an entry that reads or writes `shard` as fp32 rows -- every fused
+// step -- or that has no 16-bit form is refused by name, before any launch or exchange
+int lowp_refuse(const hbk_sharded* p, const char* who, const char* why) {
+  if (p == nullptr || p->lowp.empty()) return HBK_OK;
+  return fail(HBK_UNIMPLEMENTED, "%s: the plan's shards are 16-bit tables (hbk_sharded_set_table_dtypes): %s", who, why);
+}
+const char* const kLowpSteps =
+    "a fused step reads and writes fp32 rows and would write past a 2-byte shard; take the emit form (apply_lr = 0) "
+    "and step the shards with hbk_lowp_apply_slices_n";
 
 inline Seg make_seg(const void* src, void* dst, int64_t bytes, int narrow = 0) {
   Seg s;
@@ -1021,6 +1035,7 @@ extern "C" int hbk_sharded_p2p_bind(hbk_sharded_t p, float* const* outs, const i
   const int N = p->N, W = p->W, me = p->rank;
   p->p2p_bound = false;
   p->ps[0].pending = p->ps[1].pending = false;   // (a prefetch packed for another group count)
+  if (int rc = lowp_refuse(p, "sharded_p2p_bind", "the p2p form's owner gather stores fp32 rows")) return rc;
   // (the same on every rank that set hash tables; before the option, so that the refusal names its reason)
   if (p->any_hash) {
     return fail(HBK_UNIMPLEMENTED, "sharded_p2p_bind: the plan has a hash column (hbk_sharded_set_hash_tables): "
@@ -1247,6 +1262,7 @@ extern "C" int hbk_sharded_set_hash_tables(hbk_sharded_t p, const hbk_sharded_ha
   for (int c = 0; tables != nullptr && c < p->N; ++c) {
     const hbk_sharded_hash_t& t = tables[c];
     if (t.keys_cache == nullptr) continue;
+    if (int rc = lowp_refuse(p, who, "a hash column's rows are fp32")) return rc;
     any = true;
     const hbk_sharded_column_t& col = p->cols[c];
     HBK_REQUIRE(col.bucket == 0, "%s: column %d: a hash column takes raw ids: its bucket must be 0, got %lld", who,
@@ -1639,6 +1655,7 @@ int fwd_gather(hbk_sharded_t p, hbk_stream_t stream_) {
   const int N = p->N, W = p->W, me = p->rank;
   const bool wire = p->fin_wire, hop = p->fin_hop, p2p = p->fin_p2p;
   const bool zc = p->zero_copy_self, half = p->fused_half, any_hash = p->any_hash;
+  const bool lowp = !p->lowp.empty(), wire16 = p->lowp_wire16;
   const int32_t id_dtype = p->id32 ? HBK_INT32 : HBK_INT64;
   const std::vector<Group>& groups = p->groups;
   const int G = (int)groups.size();
@@ -1657,12 +1674,14 @@ int fwd_gather(hbk_sharded_t p, hbk_stream_t stream_) {
     if (any_hash && (rc = translate_group(p, gr, run_ids, slots_base, stream_)) != HBK_OK) return rc;
     std::vector<hbk_lookup_column_t> v;
     std::vector<float> clip;   // the owner clips: every virtual column carries its column's max_norm
+    std::vector<int32_t> lowp_dtype;   // 16-bit shards: every virtual column's element type
     v.reserve((size_t)ng * W);
     for (int q = 0; q < W; ++q) {
       for (int c = 0; c < ng; ++c) {
         const int64_t n = gr.R[(size_t)q * ng + c];
         if (n == 0) continue;
         clip.push_back(p->max_norms[(size_t)(gr.c0 + c)]);
+        if (lowp) lowp_dtype.push_back(p->lowp[(size_t)(gr.c0 + c)]);
         const hbk_sharded_column_t& col = p->cols[gr.c0 + c];
         hbk_lookup_column_t h;
         memset(&h, 0, sizeof(h));
@@ -1697,17 +1716,59 @@ int fwd_gather(hbk_sharded_t p, hbk_stream_t stream_) {
             h.out_slots = slot_send + gr.id_send + gr.lay.req_id_off[(size_t)q * ng + c];
           }
           h.hot_rows = 0;
-        } else if (half) {   // the same element offsets inside the same buffers, two bytes each
+        } else if (half || wire16) {   // the same element offsets inside the same buffers, two bytes each
           h.out = reinterpret_cast<float*>(reinterpret_cast<uint16_t*>(out_base) + out_at);
-          h.half_io = HBK_LOOKUP_OUT_HALF;
+          h.half_io = half ? HBK_LOOKUP_OUT_HALF : 0;
         } else {
           h.out = out_base + out_at;
         }
         v.push_back(h);
       }
     }
-    // (no column clipped: hbk_group_lookup_fwd_clipped is hbk_group_lookup_fwd)
-    rc = hbk_group_lookup_fwd_clipped((int32_t)v.size(), v.data(), clip.data(), stream_);
+    if (lowp) {
+      // 16-bit shards (never p2p, hashed or clipped: hbk_sharded_set_table_dtypes): the virtual columns just
+      // built, handed to the low-precision gathers -- rows as bits onto a 16-bit wire (the fused fp16 wire's
+      // addresses), or upcast into the fp32 reply
+      if (wire16) {
+        std::vector<hbk_lowp_gather_column_t> lv(v.size());
+        for (size_t i = 0; i < v.size(); ++i) {
+          const hbk_lookup_column_t& h = v[i];
+          hbk_lowp_gather_column_t& d = lv[i];
+          memset(&d, 0, sizeof(d));
+          d.table = h.table;
+          d.dim = h.dim;
+          d.ids_dtype = h.ids_dtype;
+          d.rows = h.rows;
+          d.ids = h.ids;
+          d.n_ids = h.n_ids;
+          d.divisor = h.divisor;
+          d.out = h.out;   // (a 2-byte address: set with the column above)
+        }
+        rc = hbk_lowp_gather_rows_n((int32_t)lv.size(), lv.data(), stream_);
+      } else {
+        std::vector<hbk_lowp_lookup_column_t> lv(v.size());
+        for (size_t i = 0; i < v.size(); ++i) {
+          const hbk_lookup_column_t& h = v[i];
+          hbk_lowp_lookup_column_t& d = lv[i];
+          memset(&d, 0, sizeof(d));
+          d.table = h.table;
+          d.table_dtype = lowp_dtype[i];
+          d.dim = h.dim;
+          d.rows = h.rows;
+          d.ids = h.ids;
+          d.ids_dtype = h.ids_dtype;
+          d.combiner = HBK_COMBINER_SUM;
+          d.n_ids = h.n_ids;
+          d.n_segments = h.n_segments;
+          d.divisor = h.divisor;
+          d.out = h.out;
+        }
+        rc = hbk_lowp_lookup_fwd((int32_t)lv.size(), lv.data(), stream_);
+      }
+    } else {
+      // (no column clipped: hbk_group_lookup_fwd_clipped is hbk_group_lookup_fwd)
+      rc = hbk_group_lookup_fwd_clipped((int32_t)v.size(), v.data(), clip.data(), stream_);
+    }
     if (rc != HBK_OK) return rc;
     if (!wire) continue;
     if (hop) HBK_HIP_OK(hipEventRecord(p->ev[2][g], stream));
@@ -1849,6 +1910,7 @@ extern "C" int hbk_sharded_lookup_fwd_end(hbk_sharded_t p, float* const* outs,
   const int N = p->N, W = p->W;
   const bool wire = p->fin_wire, hop = p->fin_hop, p2p = p->fin_p2p;
   const bool half = p->fused_half, zc = p->zero_copy_self;
+  const bool wire16 = p->lowp_wire16;   // 16-bit shards on their own wire: 2-byte rows, as the fused fp16 wire moves them
   const std::vector<Group>& groups = p->groups;
   const int G = (int)groups.size();
   hbk_sharded::PartSet& set = p->ps[p->fin_use];
@@ -1869,7 +1931,7 @@ extern "C" int hbk_sharded_lookup_fwd_end(hbk_sharded_t p, float* const* outs,
   // the rows of group g go on the wire (its gather has recorded ev[2][g])
   for (int g = 0; g < G && wire && !p2p; ++g) {
     const Group& gr = groups[g];
-    if (half) {
+    if (half || wire16) {
       rc = exchange(p, HBK_HALF, HBK_HALF, reinterpret_cast<uint16_t*>(rows_send_base) + gr.row_send,
                     gr.lay.rows_send_peer.data(),
                     reinterpret_cast<uint16_t*>(rows_recv_base) + gr.row_recv,
@@ -1903,9 +1965,9 @@ extern "C" int hbk_sharded_lookup_fwd_end(hbk_sharded_t p, float* const* outs,
       const int cc = gr.c0 + c;
       hbk_lookup_column_t& h = v[c];
       memset(&h, 0, sizeof(h));
-      h.table = half ? reinterpret_cast<const float*>(reinterpret_cast<const uint16_t*>(rows_recv_base) +
-                                                      gr.row_recv)
-                     : rows_recv_base + gr.row_recv;
+      h.table = half || wire16 ? reinterpret_cast<const float*>(reinterpret_cast<const uint16_t*>(rows_recv_base) +
+                                                                gr.row_recv)
+                               : rows_recv_base + gr.row_recv;
       h.half_io = half ? HBK_LOOKUP_TABLE_HALF : 0;
       h.rows = p->n_sent[cc];   // rows that came back (the distinct ids of a deduplicated column)
       h.dim = p->cols[cc].dim;
@@ -1923,7 +1985,35 @@ extern "C" int hbk_sharded_lookup_fwd_end(hbk_sharded_t p, float* const* outs,
       h.n_runs = W;
       h.id_weights = p->id_weights[cc];   // the weights are applied here, on the requester
     }
-    rc = hbk_group_lookup_fwd(ng, v.data(), stream_);
+    if (wire16) {
+      // the received rows are the shards' own 16 bits: the same columns over the same runs, upcast by the stitch
+      std::vector<hbk_lowp_lookup_runs_column_t> lv((size_t)ng);
+      for (int c = 0; c < ng; ++c) {
+        const hbk_lookup_column_t& h = v[c];
+        hbk_lowp_lookup_runs_column_t& d = lv[(size_t)c];
+        memset(&d, 0, sizeof(d));
+        d.col.table = h.table;
+        d.col.table_dtype = p->lowp[(size_t)(gr.c0 + c)];
+        d.col.dim = h.dim;
+        d.col.rows = h.rows;
+        d.col.ids = h.ids;
+        d.col.ids_dtype = h.ids_dtype;
+        d.col.combiner = h.combiner;
+        d.col.n_ids = h.n_ids;
+        d.col.row_splits = h.row_splits;
+        d.col.n_segments = h.n_segments;
+        d.col.divisor = 1;
+        d.col.out_stride = h.out_stride;
+        d.col.out = h.out;
+        d.col.id_weights = h.id_weights;
+        d.run_start = h.run_start;
+        d.run_base = h.run_base;
+        d.n_runs = h.n_runs;
+      }
+      rc = hbk_lowp_lookup_fwd_runs(ng, lv.data(), stream_);
+    } else {
+      rc = hbk_group_lookup_fwd(ng, v.data(), stream_);
+    }
     if (rc != HBK_OK) return rc;
   }
   p->have_step = true;
@@ -2044,6 +2134,10 @@ extern "C" int hbk_sharded_lookup_bwd_weights(hbk_sharded_t p, const float* cons
                                               hbk_stream_t stream_) {
   using namespace hbk;
   HBK_REQUIRE(p != nullptr, "sharded_lookup_bwd_weights: plan is NULL");
+  if (int rc = lowp_refuse(p, "sharded_lookup_bwd_weights", "the received rows are 16-bit and the weight gradient "
+                           "reads fp32 (or fp16 wire) rows")) {
+    return rc;
+  }
   // (the same on every rank: the bind is collective)
   if (p->p2p_bound) {
     return fail(HBK_UNIMPLEMENTED, "sharded_lookup_bwd_weights: the p2p form (hbk_sharded_p2p_bind) has no "
@@ -2129,6 +2223,10 @@ static int sharded_bwd(hbk_sharded_t p, const float* const* grads, const int32_t
   using namespace hbk;
   const bool two_slot = step.workspace_bytes != nullptr;
   HBK_REQUIRE(p != nullptr, "sharded_lookup_bwd: plan is NULL");
+  const bool lowp = !p->lowp.empty();
+  if (two_slot || apply_lr != 0.0f) {
+    if (int rc = lowp_refuse(p, "sharded_lookup_bwd", kLowpSteps)) return rc;
+  }
   HBK_REQUIRE(p->have_step, "sharded_lookup_bwd: no forward step to differentiate");
   HBK_REQUIRE(grads && n_unique, "sharded_lookup_bwd: NULL argument array");
   HBK_REQUIRE((unique_rows != nullptr) == (grad_rows != nullptr),
@@ -2275,8 +2373,9 @@ static int sharded_bwd(hbk_sharded_t p, const float* const* grads, const int32_t
     for (int q = 0; q < W; ++q) n_own += R[(size_t)q * N + c];
     hbk_lookup_grad_column_t& h = v[c];
     memset(&h, 0, sizeof(h));
-    h.table = const_cast<float*>(p->cols[c].shard);
-    h.accum = two_slot ? nullptr : p->cols[c].accum;
+    // (16-bit shards: the emit form never reads the table, and is not handed it)
+    h.table = lowp ? nullptr : const_cast<float*>(p->cols[c].shard);
+    h.accum = two_slot || lowp ? nullptr : p->cols[c].accum;
     h.rows = p->cols[c].rows_local;
     h.dim = p->cols[c].dim;
     h.ids_dtype = p->id32 ? HBK_INT32 : HBK_INT64;
@@ -2339,6 +2438,7 @@ int set_slot_pair(hbk_sharded_t p, const hbk::SlotNames& nm, float* const* s0, f
   using namespace hbk;
   const char* who = nm.who;
   HBK_REQUIRE(p != nullptr, "%s: plan is NULL", who);
+  if (int rc = lowp_refuse(p, who, kLowpSteps)) return rc;
   if (nm.s1 == nullptr) {
     HBK_REQUIRE(s0 != nullptr, "%s: the %s array is NULL", who, nm.s0);
     std::vector<uintptr_t> seen;
@@ -2392,6 +2492,7 @@ int two_slot_prologue(hbk_sharded_t p, const hbk::SlotNames& nm, Check check, co
                       hbk::SlotPair hbk_sharded::*pair) {
   using namespace hbk;
   HBK_REQUIRE(p != nullptr, "%s: plan is NULL", nm.who);
+  if (int rc = lowp_refuse(p, nm.who, kLowpSteps)) return rc;
   const int rc = check();
   if (rc != HBK_OK) return rc;
   if (nm.s1 == nullptr) {
@@ -2500,7 +2601,64 @@ extern "C" int hbk_sharded_set_max_norms(hbk_sharded_t p, const float* max_norms
                 "sharded_set_max_norms: column %d: max_norm must be 0 (no clip) or finite and > 0, got %g", c,
                 (double)max_norms[c]);
   }
+  for (int c = 0; max_norms != nullptr && c < p->N; ++c) {
+    if (max_norms[c] == 0.0f) continue;
+    if (int rc = lowp_refuse(p, "sharded_set_max_norms", "the clip reads and the clipped step writes fp32 rows")) {
+      return rc;
+    }
+  }
   for (int c = 0; c < p->N; ++c) p->max_norms[(size_t)c] = max_norms != nullptr ? max_norms[c] : 0.0f;
+  return HBK_OK;
+}
+
+// 16-bit shards (include/hbk.h): plan state like the max_norms.  NULL: an fp32 plan again.
+extern "C" int hbk_sharded_set_table_dtypes(hbk_sharded_t p, const int32_t* dtypes, int32_t wire) {
+  using namespace hbk;
+  const char* who = "sharded_set_table_dtypes";
+  HBK_REQUIRE(p != nullptr, "%s: plan is NULL", who);
+  if (dtypes == nullptr) {
+    p->lowp.clear();
+    p->lowp_wire16 = false;
+    p->have_step = false;   // (a step of the other element type is not differentiated)
+    p->rows_live = false;
+    p->fwd_open = p->ids_open = false;
+    return HBK_OK;
+  }
+  HBK_REQUIRE(wire == HBK_LOWP_WIRE_TABLE || wire == HBK_LOWP_WIRE_FLOAT,
+              "%s: wire must be HBK_LOWP_WIRE_TABLE or HBK_LOWP_WIRE_FLOAT, got %d", who, wire);
+  for (int c = 0; c < p->N; ++c) {
+    HBK_REQUIRE(dtypes[c] == HBK_LOWP_BF16 || dtypes[c] == HBK_LOWP_FP16,
+                "%s: column %d: dtype must be HBK_LOWP_BF16 or HBK_LOWP_FP16, got %d (all or nothing: a plan has "
+                "16-bit shards in every column or in none)", who, c, dtypes[c]);
+    HBK_REQUIRE(((uintptr_t)p->cols[c].shard & 1) == 0, "%s: column %d: shard must be 2-byte aligned", who, c);
+  }
+  if (p->wire_dtype == HBK_HALF) {
+    return fail(HBK_UNIMPLEMENTED, "%s: the plan was created with wire_dtype == HBK_HALF: a 16-bit plan sends its rows "
+                "in the table's own bits (HBK_LOWP_WIRE_TABLE) or as fp32, and its gradients as fp32", who);
+  }
+  for (int c = 0; c < p->N; ++c) {
+    if (p->max_norms[(size_t)c] != 0.0f) {
+      return fail(HBK_UNIMPLEMENTED, "%s: column %d has a max_norm (hbk_sharded_set_max_norms): the clip reads and "
+                  "the clipped step writes fp32 rows", who, c);
+    }
+  }
+  if (p->any_hash) {
+    return fail(HBK_UNIMPLEMENTED, "%s: the plan has a hash column (hbk_sharded_set_hash_tables): its rows are fp32",
+                who);
+  }
+  if (p->p2p_bound) {
+    return fail(HBK_UNIMPLEMENTED, "%s: the plan is p2p-bound (hbk_sharded_p2p_bind): the p2p form's owner gather "
+                "stores fp32 rows", who);
+  }
+  // slots registered while the plan was an fp32 plan are dropped: no slot entry can run on a 16-bit plan
+  p->adam = SlotPair();
+  p->ftrl = SlotPair();
+  p->rowwise = SlotPair();
+  p->lowp.assign(dtypes, dtypes + p->N);
+  p->lowp_wire16 = wire == HBK_LOWP_WIRE_TABLE;
+  p->have_step = false;
+  p->rows_live = false;
+  p->fwd_open = p->ids_open = false;
   return HBK_OK;
 }
 

@@ -1,7 +1,7 @@
 """Low-precision embedding tables: rows stored as ``torch.bfloat16`` / ``torch.float16``, every sum and every
 optimizer slot fp32 (include/hbk.h, "Low-precision tables").
 
-Three classes with the calling conventions of their fp32 counterparts:
+Four classes with the calling conventions of their fp32 counterparts:
 
   :class:`LowpGroupLookup`   the forward (``hbk_lowp_lookup_fwd``): gathers 2-byte rows, upcasts them exactly and
                              combines in fp32 -- bit for bit ``GroupLookup`` over ``table.float()``.
@@ -11,6 +11,8 @@ Three classes with the calling conventions of their fp32 counterparts:
                              half an ulp (2^-8 relative) is rounded away every time.
   :class:`LowpLookupGrad`    the backward and the step: an unmodified ``GroupLookupGrad`` in its emit form (which
                              never reads the table), then ``LowpSparseApply`` on the slices it returned.
+  :class:`LowpShardedGroupLookup`  the sharded step over 16-bit shards: rows cross the wire in the table's own 16
+                             bits (or upcast by the owner), the plan's emit backward, ``LowpSparseApply`` on the shards.
 """
 import ctypes as C
 import numbers
@@ -21,6 +23,7 @@ import torch
 from hybridbackend_amd import _lib
 from hybridbackend_amd.embedding import optimizer as _opt
 from hybridbackend_amd.embedding.lookup import GroupLookup, GroupLookupGrad, _combiner_code
+from hybridbackend_amd.embedding.sharded import ShardedGroupLookup
 from hybridbackend_amd.embedding.sparse_apply import _APPLY
 
 _DTYPES = {torch.bfloat16: _lib.LOWP_BF16, torch.float16: _lib.LOWP_FP16}
@@ -337,3 +340,172 @@ class LowpLookupGrad:
     if apply_lr != 0.0:
       self._apply.launch(apply_lr, optimizer, finish)
     return r if self._last_emit else [(None, None, t[2]) for t in r]
+
+
+_WIRES = {'table': _lib.LOWP_WIRE_TABLE, 'float': _lib.LOWP_WIRE_FLOAT}
+
+
+def rank_seed(seed, rank):
+  """The seed rank ``rank`` steps its shards with: ``(seed + 0x9E3779B9 * rank) mod 2^32`` (include/hbk.h)."""
+  return (int(seed) + 0x9E3779B9 * int(rank)) % (1 << 32)
+
+
+class LowpShardedGroupLookup(ShardedGroupLookup):
+  """N row-sharded 16-bit embedding tables looked up together: :class:`ShardedGroupLookup` over bf16 / fp16 shards.
+
+  Args:
+    shards16: this rank's local rows per column, ``torch.bfloat16`` / ``torch.float16`` ``[rows_local, dim]`` (a
+      plan has 16-bit shards in every column; the two types may be mixed).
+    coll, buckets, combiners, dedup: as :class:`ShardedGroupLookup`.
+    wire: what crosses the link in the forward.  ``'table'`` (the default): the rows in the table's own 16 bits --
+      the owner gather copies bits (``hbk_lowp_gather_rows_n``), the exchange moves 2-byte elements and the
+      requester's stitch upcasts them (``hbk_lowp_lookup_fwd_runs``): half the wire bytes of fp32 and, unlike the
+      fp16 wire, nothing is rounded.  ``'float'``: the owner upcasts (``hbk_lowp_lookup_fwd``) and everything behind
+      it is the fp32 step -- the twin ``'table'`` is compared and timed against.  Both give, bit for bit,
+      ``ShardedGroupLookup`` over ``[s.float() for s in shards16]`` on the fp32 wire.
+    accums / moments, adam / ftrl_slots, ftrl / row_accums, rowwise_adagrad: FP32 slots of the shards' shapes
+      (row-wise Adagrad: ``[rows_local, 1]``) and the optimizer objects, as :class:`LowpSparseApply` takes them.
+    rounding, seed: as :class:`LowpSparseApply`.  The stochastic noise is keyed by the LOCAL row, so two ranks with
+      one seed would round local row r alike: rank k steps with ``rank_seed = (seed + 0x9E3779B9 * k) mod 2^32``.
+
+  ``__call__``, ``bind``, ``launch`` (weighted steps included), ``prefetch`` and the split forward are the base
+  class's.  ``backward(grads, apply_lr=, optimizer=, emit=, finish=)`` is the plan's emit backward -- which never
+  reads the shards and returns LOCAL row numbers, the gradient exchange in fp32 -- followed by a
+  :class:`LowpSparseApply` on the shards; with ``emit=False`` the slices go into buffers this object owns.  All five
+  optimizers.  The plan's own stepping entries read and write fp32 rows and are refused on a 16-bit plan at the ABI;
+  this class never calls them.
+
+  Refused by name: fp32 shards, ``max_norms``, ``weight_grads``, ``wire_dtype``, ``hot_rows`` and ``p2p_bind``."""
+
+  def __init__(self, shards16, coll, buckets=None, combiners='sum', wire='table', dedup=False, accums=None,   # pylint: disable=super-init-not-called
+               moments=None, adam=None, ftrl_slots=None, ftrl=None, row_accums=None, rowwise_adagrad=None,
+               rounding='nearest', seed=0, max_norms=None, weight_grads=False, wire_dtype=None, hot_rows=False):
+    what = 'LowpShardedGroupLookup'
+    self.shards = _require_lowp_tables(shards16, what)
+    if max_norms is not None and not (isinstance(max_norms, (list, tuple)) and all(x is None for x in max_norms)):
+      raise _bad(f'{what}: max_norms is not supported for 16-bit shards (the clip reads and the clipped step writes '
+                 'fp32 rows)')
+    if weight_grads is not False and weight_grads is not None:
+      raise _bad(f'{what}: weight_grads is not supported for 16-bit shards (the received rows are 16-bit)')
+    if wire_dtype is not None:
+      raise _bad(f"{what}: wire_dtype is not supported: a 16-bit plan names its wire with wire='table' | 'float' "
+                 '(the fp16 wire rounds what it sends)')
+    if hot_rows is not False and hot_rows is not None and hot_rows != [False] * len(self.shards):
+      raise _bad(f'{what}: hot_rows is not supported for 16-bit shards (the low-precision gathers stage nothing)')
+    if wire not in _WIRES:
+      raise _bad(f"{what}: wire must be 'table' or 'float', got {wire!r}")
+    check_rounding(rounding, seed, [t.dtype for t in self.shards], what)
+    n = len(self.shards)
+    self.wire = wire
+    self.coll = coll
+    self.world_size = int(coll.world_size)
+    self.rank = int(getattr(coll, 'rank', 0))
+    self.seed = int(seed)
+    self.rank_seed = rank_seed(seed, self.rank)
+    # a rank that owns no row of a table has an empty shard and empty slots, which have no address: the apply is
+    # handed one-row stand-ins for them (never stepped: such a column's slices are empty), so that every column
+    # keeps its index -- the stochastic noise is keyed by it
+    empty = [c for c, t in enumerate(self.shards) if t.shape[0] == 0]
+
+    def filled(tensors, pair=False):
+      if tensors is None or not empty:
+        return tensors
+      tensors = list(tensors)
+      for c in empty:
+        one = lambda t: torch.zeros((1,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)   # noqa: E731
+        tensors[c] = tuple(one(t) for t in tensors[c]) if pair else one(tensors[c])
+      return tensors
+    self._apply = LowpSparseApply(filled(self.shards), accums=filled(accums), moments=filled(moments, True), adam=adam,
+                                  ftrl_slots=filled(ftrl_slots, True), ftrl=ftrl, row_accums=filled(row_accums),
+                                  rowwise_adagrad=rowwise_adagrad, rounding=rounding, seed=self.rank_seed)
+    # what the base class reads: no clip, no slots of the plan's own (they live with the apply), no hints
+    self.weight_grads = False
+    self.max_norms = [0.0] * n
+    self.accums = None
+    for cls in _opt.TWO_SLOT.values():
+      setattr(self, cls.slot_kw, None)
+      setattr(self, cls.name, None)
+    self.buckets = [int(b or 0) for b in (buckets or [0] * n)]
+    self.combiners = combiners
+    self.wire_dtype = None
+    self.device = self.shards[0].device if n else None
+    self.dims = [int(t.shape[1]) for t in self.shards]
+    self._auto_hot = []
+    self._auto_state = None
+    self.hot_rows = [False] * n
+    self.dedup = [bool(dedup)] * n if isinstance(dedup, (bool, int)) else [bool(d) for d in dedup]
+    self._own = None   # emit=False: per column (unique_rows, grad_rows, n_unique) this object owns
+    self._setup()
+
+  def _setup(self):
+    self._lib = _lib.lib()
+
+  def _plan_created(self):
+    n = len(self.shards)
+    _lib.check(self._lib.hbk_sharded_set_table_dtypes(
+      self._plan_handle, (C.c_int32 * n)(*[_DTYPES[t.dtype] for t in self.shards]), _WIRES[self.wire]))
+
+  @property
+  def step_counter(self):
+    return self._apply.step_counter
+
+  def p2p_bind(self, outs):   # pylint: disable=unused-argument
+    raise _lib.HbkError(_lib.UNIMPLEMENTED, 'LowpShardedGroupLookup: p2p_bind is not supported for 16-bit shards '
+                        "(the p2p form's owner gather stores fp32 rows)")
+
+  def _phase(self, *args, **kwargs):   # pylint: disable=unused-argument
+    raise _lib.HbkError(_lib.UNIMPLEMENTED, 'LowpShardedGroupLookup has no separate phase methods: the step runs '
+                        'inside the plan (__call__ / launch / backward)')
+
+  partition = owner_gather = stitch = stitch_bwd = owner_bwd = _phase
+
+  def _own_slices(self, plan):
+    """Driver-owned IndexedSlices buffers with room for the rows this rank owns of the last forward."""
+    n = len(self.shards)
+    if self._own is None:
+      self._own = [None] * n
+    for c in range(n):
+      k = int(self._lib.hbk_sharded_owned_ids(plan, c))
+      if k < 0:
+        raise _lib.HbkError(_lib.INTERNAL, 'backward() needs a forward step first')
+      cur = self._own[c]
+      if cur is None or cur[0].numel() < k:
+        cap = max(k, 1) if cur is None else max(k, 2 * cur[0].numel())
+        self._own[c] = (torch.empty(cap, dtype=torch.int64, device=self.device),
+                        torch.empty((cap, self.dims[c]), dtype=torch.float32, device=self.device),
+                        torch.zeros(1, dtype=torch.int32, device=self.device))
+    return self._own
+
+  def backward(self, grads, apply_lr=0.0, outs=None, optimizer='sgd', emit=True, finish=True, weight_grads=None):
+    """Backward of the LAST forward step and, with ``apply_lr``, the optimizer step on the 16-bit shards.  Returns
+    per column the IndexedSlices of the LOCAL shard ``(unique_rows, grad_rows, n_unique)``, equal to the fp32
+    driver's; ``emit=False`` (with ``apply_lr``): the slices go into buffers this object owns and the triples are
+    ``(None, None, n_unique)``.  ``optimizer``: 'sgd', 'adagrad', 'adam', 'ftrl' or 'rowwise_adagrad' (the slots
+    given to the constructor); ``finish=True`` advances Adam's beta powers and the rounding's step counter once,
+    behind the step.  ``weight_grads`` is refused."""
+    if weight_grads is not False and weight_grads is not None:
+      raise _bad('LowpShardedGroupLookup: weight_grads is not supported for 16-bit shards (the received rows are '
+                 '16-bit)')
+    if not emit and apply_lr == 0.0:
+      raise _bad('emit=False needs apply_lr != 0')
+    if apply_lr != 0.0:
+      self._apply._check(apply_lr, optimizer)   # (before the exchange: a refused call moves nothing)
+    else:
+      _opt.two_slot_class(optimizer)
+    if not emit and outs is None:
+      outs = self._own_slices(self._plan())
+    r = ShardedGroupLookup.backward(self, grads, apply_lr=0.0, outs=outs, optimizer='sgd', emit=True, weight_grads=False)
+    if apply_lr != 0.0:
+      self._apply(self._apply_views(r), apply_lr, optimizer, finish)
+    return r if emit else [(None, None, t[2]) for t in r]
+
+  def _apply_views(self, slices):
+    """The slices as :class:`LowpSparseApply` takes them: ``grad_rows`` ``[capacity, dim]`` (caller-owned outputs
+    may be larger than the rows they hold)."""
+    out = []
+    for c, (u, g, nu) in enumerate(slices):
+      cap = int(u.shape[0])
+      if g.dim() != 2 or tuple(g.shape) != (cap, self.dims[c]):
+        g = g.reshape(-1)[:cap * self.dims[c]].view(cap, self.dims[c])
+      out.append((u, g, nu))
+    return out

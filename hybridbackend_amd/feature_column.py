@@ -144,7 +144,7 @@ class _TableLayer:
   W > 1), the optimizer slots, and the checkpoints."""
 
   def _init_tables(self, columns, device, coll, batch_size, init, initial_accumulator_value, optimizer,
-                   adam, ftrl, train=True, rowwise_adagrad=None, table_dtype=None):
+                   adam, ftrl, train=True, rowwise_adagrad=None, table_dtype=None, lowp_sharded=False):
     self.columns = list(columns)
     self.device = torch.device(device)
     self.coll = coll
@@ -171,10 +171,13 @@ class _TableLayer:
       self.weights.append(init(col, rows if is_sharded else col.num_buckets, self.device))
     # 16-bit tables (DenseFeatures(table_dtype=)): init's result rounded to nearest; every slot below stays
     # fp32 and is built from an fp32 stand-in of the table's shape (zero strides: it owns one word)
+    # DenseFeatures(lowp_sharded=True) at W > 1: the SHARDED tables only; the replicated ones stay fp32
     like = self.weights
     if table_dtype is not None:
-      self.weights = [w.to(table_dtype) for w in self.weights]
-      like = [torch.empty((), dtype=torch.float32, device=self.device).expand(w.shape) for w in self.weights]
+      low = [world <= 1 or (bool(lowp_sharded) and s and h is None) for s, h in zip(self.sharded, self.hash_tables)]
+      self.weights = [w.to(table_dtype) if l else w for w, l in zip(self.weights, low)]
+      like = [torch.empty((), dtype=torch.float32, device=self.device).expand(w.shape) if l else w
+              for w, l in zip(self.weights, low)]
     # Adagrad accumulators (tf.train.AdagradOptimizer: initial_accumulator_value = 0.1)
     self.accums = None
     if initial_accumulator_value is not None:
@@ -513,8 +516,16 @@ class DenseFeatures(_TableLayer):
       (``hb.embedding.LowpGroupLookup``) and fp32 accumulators and slots in the step
       (``hb.embedding.LowpLookupGrad``: the reduce's emit form, then an apply of its own).  ``weights[c]`` are the
       16-bit tensors, and ``variables()`` / ``save`` / ``restore`` carry them as they are.  One rank only (``coll``
-      None or of one rank); a hash-keyed column, a column with ``max_norm`` and a column wider than 64 whose block
-      does not start on a multiple of 4 floats are refused by name; ``backward(weight_grads=True)`` is refused.
+      None or of one rank) unless ``lowp_sharded``; a hash-keyed column, a column with ``max_norm`` and a column
+      wider than 64 whose block does not start on a multiple of 4 floats are refused by name;
+      ``backward(weight_grads=True)`` is refused.
+    lowp_sharded: True lets a layer with ``table_dtype`` span W > 1 ranks: its SHARDED tables are 16-bit shards
+      looked up and stepped by ``hb.embedding.LowpShardedGroupLookup`` -- the rows cross the wire in the table's own
+      16 bits, the slots are fp32, ``table_rounding`` / ``table_seed`` as above (rank k rounds with
+      ``(table_seed + 0x9E3779B9 * k) mod 2^32``) -- and ``variables()`` / ``save`` / ``restore`` carry the 16-bit
+      shards, resharding across world sizes as the fp32 ones do.  The REPLICATED tables stay fp32 (they hold at
+      most ``max(batch, W)`` rows: capacity is not their problem) with every path they have today,
+      ``aggregate_replicated`` included.  The refusals above stand.  At W = 1 the argument changes nothing.
     table_rounding: ``'nearest'``, or ``'stochastic'`` (bf16 only) -- what lets a bf16 table train on steps
       smaller than half an ulp; table_seed: the seed of its noise.
 
@@ -531,12 +542,13 @@ class DenseFeatures(_TableLayer):
   def __init__(self, columns, device, coll=None, batch_size=0, init=None,
                initial_accumulator_value=None, optimizer=None, adam=None, ftrl=None, train=True,
                rowwise_adagrad=None, aggregate_replicated=False, replicated_scale=None, table_dtype=None,
-               table_rounding='nearest', table_seed=0):
+               table_rounding='nearest', table_seed=0, lowp_sharded=False):
     self.table_dtype = table_dtype
+    self.lowp_sharded = bool(lowp_sharded)
     if table_dtype is not None:
-      self._check_lowp(columns, coll, table_dtype, table_rounding, table_seed)
+      self._check_lowp(columns, coll, table_dtype, table_rounding, table_seed, lowp_sharded)
     self._init_tables(columns, device, coll, batch_size, init, initial_accumulator_value, optimizer,
-                      adam, ftrl, train, rowwise_adagrad, table_dtype)
+                      adam, ftrl, train, rowwise_adagrad, table_dtype, lowp_sharded)
     self._init_replica(aggregate_replicated, replicated_scale, 'DenseFeatures')
     for c in self._hash:
       col = self.columns[c]
@@ -558,7 +570,7 @@ class DenseFeatures(_TableLayer):
     pick = lambda idx, xs: [xs[c] for c in idx]   # noqa: E731
     two_slot_kw = self._two_slot_kw
     self._lookup = self._grad = self._sharded = None
-    if self._rep and table_dtype is not None:
+    if self._rep and table_dtype is not None and self._world() <= 1:
       # 16-bit tables: the same two roles, so that __call__ and backward do not fork
       from hybridbackend_amd.embedding.lowp import LowpGroupLookup, LowpLookupGrad   # pylint: disable=import-outside-toplevel
       self._lookup = LowpGroupLookup(pick(self._rep, self.weights),
@@ -576,7 +588,17 @@ class DenseFeatures(_TableLayer):
       self._grad = GroupLookupGrad(
         self._lookup, pick(self._rep, self.accums) if self.accums is not None else None,
         **two_slot_kw(self._rep))
-    if self._shd:
+    if self._shd and table_dtype is not None:
+      # lowp_sharded (else refused above): 16-bit shards on their own wire, fp32 slots, the step in the driver
+      from hybridbackend_amd.embedding.lowp import LowpShardedGroupLookup   # pylint: disable=import-outside-toplevel
+      self._sharded = LowpShardedGroupLookup(pick(self._shd, self.weights), coll,
+                                             buckets=[self.columns[c].num_buckets for c in self._shd],
+                                             combiners=[self.columns[c].combiner for c in self._shd],
+                                             dedup=[self.columns[c].dedup for c in self._shd],
+                                             accums=(pick(self._shd, self.accums)
+                                                     if self.accums is not None else None),
+                                             rounding=table_rounding, seed=table_seed, **two_slot_kw(self._shd))
+    elif self._shd:
       self._sharded = ShardedGroupLookup(pick(self._shd, self.weights), coll,
                                          buckets=[self.columns[c].num_buckets for c in self._shd],
                                          combiners=[self.columns[c].combiner for c in self._shd],
@@ -602,13 +624,13 @@ class DenseFeatures(_TableLayer):
       **self._two_slot_kw(self._hash))
 
   @staticmethod
-  def _check_lowp(columns, coll, table_dtype, table_rounding, table_seed):
+  def _check_lowp(columns, coll, table_dtype, table_rounding, table_seed, lowp_sharded=False):
     """Everything ``table_dtype`` refuses, before any table is allocated."""
     from hybridbackend_amd.embedding.lowp import check_rounding   # pylint: disable=import-outside-toplevel
     if table_dtype not in (torch.bfloat16, torch.float16):
       raise _bad(f'DenseFeatures(table_dtype=): None, torch.bfloat16 or torch.float16, got {table_dtype!r}')
     check_rounding(table_rounding, table_seed, [table_dtype], 'DenseFeatures(table_dtype=)')
-    if coll is not None and coll.world_size > 1:
+    if coll is not None and coll.world_size > 1 and not lowp_sharded:
       raise _bad(f'DenseFeatures(table_dtype={table_dtype}): 16-bit tables are kept on one rank only, the layer '
                  f'spans {coll.world_size} (sharded and replicated-at-W>1 tables stay fp32)')
     off = 0

@@ -743,6 +743,58 @@ int hbk_lowp_apply_slices_n(int32_t n_cols, const hbk_lowp_slices_column_t* cols
                             float* const* slot0, float* const* slot1, const void* params, float lr,
                             const hbk_lowp_rounding_t* rounding, hbk_stream_t stream);
 
+/* The two sides of a 16-bit wire (the sharded step over 16-bit shards, hbk_sharded_set_table_dtypes): rows travel
+ * in the table's own 2 bytes per element and are upcast by the requester, so nothing is rounded on the way -- the
+ * result stays hbk_group_lookup_fwd over the upcast table, bit for bit, at half the wire bytes.  Both detected by
+ * the presence of the symbol; the structs above and the version stay those of 0.2.0.
+ *
+ * OWNER GATHER  hbk_lowp_gather_rows_n: per column, one id per segment, no weights, no combiner:
+ *       out[s, :] = table[row(ids[s]), :]   copied as 16-bit patterns
+ *   with row() the id map of hbk_lowp_lookup_fwd (bucket: floormod; divisor; rows).  A row outside [0, rows) gives
+ *   0x0000 elements: +0 in bf16 and in fp16, what the upcast forward writes for it.  Nothing is converted, so the
+ *   entry does not ask whether the bits are bf16 or fp16 (NaN payloads, infinities, subnormals and -0 arrive as
+ *   they are).  out_stride counts ELEMENTS between rows of `out` (0 = dim).
+ *   A lane moves 8 elements (16 bytes) when dim % 8 == 0 and table, out and the stride in bytes are 16-byte
+ *   aligned, 4 elements (8 bytes) when dim % 4 == 0 and they are 8-byte aligned: dim <= 256; otherwise one element:
+ *   dim <= 64.  Ids are read once per wave and handed to a row's lanes by shuffle; a lane issues its 4 independent
+ *   row loads before it stores.  One launch per 64 columns and lane width (a call with more columns splits), plain
+ *   loads, non-temporal stores, no atomics, no workspace, no host read: capturable.
+ *   Refused before the first launch (HBK_INVALID_ARGUMENT, the column named): dim < 1 or beyond the bounds above;
+ *   an unknown ids_dtype; negative sizes or >= 2^31 ids; bucket < 0; divisor < 1; out_stride != 0 and < dim; a
+ *   table or out at an odd address; a NULL table (rows > 0), ids or out of a column with ids.  n_cols == 0: OK. */
+typedef struct {
+  const void* table;         /* device [rows, dim] of 2-byte elements, contiguous rows */
+  int32_t dim;
+  int32_t ids_dtype;         /* HBK_INT32 | HBK_INT64 */
+  int64_t rows;
+  const void* ids;           /* device [n_ids] */
+  int64_t n_ids;
+  int64_t bucket;            /* 0 = ids are row numbers already */
+  int32_t divisor;           /* >= 1 */
+  int32_t out_stride;        /* ELEMENTS between rows of `out`; 0 = dim */
+  void* out;                 /* device [n_ids, dim] of 2-byte elements */
+} hbk_lowp_gather_column_t;
+int hbk_lowp_gather_rows_n(int32_t n_cols, const hbk_lowp_gather_column_t* cols, hbk_stream_t stream);
+
+/* REQUESTER STITCH  hbk_lowp_lookup_fwd_runs: hbk_lowp_lookup_fwd -- ragged segments, the three combiners,
+ *   id_weights, the zero-row rules, out_stride, fp32 output, fp32 sums in id order from +0 -- over a SEGMENTED
+ *   table as in hbk_lookup_column_t: logical rows [run_start[k], run_start[k + 1]) (the last run ends at
+ *   col.rows) live at col.table + run_base[k] ELEMENTS; run_start[0] = 0; device int64 arrays [n_runs], n_runs >= 1;
+ *   a base may be negative.  table_dtype is per column: one call may mix bf16 and fp16 columns.  The result is
+ *   hbk_group_lookup_fwd over the same runs of the upcast fp32 buffer, bit for bit.
+ *   Lane widths as hbk_lowp_lookup_fwd, with one difference: a lane moves 4 elements by default at every dim
+ *   (the run bases must then be multiples of 4 elements, which hbk_sharded_layout's padding gives) and 8 only
+ *   with col.chunk_elems = 8 (the caller then promises bases that are multiples of 8 elements).
+ *   Refused as hbk_lowp_lookup_fwd refuses, plus n_runs < 1 or a NULL run array. */
+typedef struct {
+  hbk_lowp_lookup_column_t col;
+  const int64_t* run_start;  /* device [n_runs] */
+  const int64_t* run_base;   /* device [n_runs], elements */
+  int32_t n_runs;            /* >= 1 */
+  int32_t reserved;          /* 0 */
+} hbk_lowp_lookup_runs_column_t;
+int hbk_lowp_lookup_fwd_runs(int32_t n_cols, const hbk_lowp_lookup_runs_column_t* cols, hbk_stream_t stream);
+
 /* Gradients of REPLICATED tables across ranks, in their dense form (the reference's
  * TRAINABLE_REPLICATED_SMALL, training/gradient.py:131-141): every rank scatters its IndexedSlices into one
  * bucket, ONE allreduce sums the buckets, and each table's block of the bucket is then read back as
@@ -2027,6 +2079,39 @@ int hbk_sharded_set_hot_rows(hbk_sharded_t plan, const int32_t* hot_rows);
  * p2p-bound plan (hbk_sharded_p2p_bind) refuses a forward with a clipped column: HBK_UNIMPLEMENTED
  * before any exchange.  Values are refused as in the clipped entries. */
 int hbk_sharded_set_max_norms(hbk_sharded_t plan, const float* max_norms);
+/* 16-bit shards (plan state like the max_norms; a new symbol, the structs and the version stay those of 0.2.0).
+ * dtypes: host int32 [n_cols], every entry HBK_LOWP_BF16 or HBK_LOWP_FP16 -- cols[c].shard then points at
+ * [rows_local, dim] rows of 2-byte elements -- or NULL: the plan is an fp32 plan again, as created.  All or nothing:
+ * a plan has 16-bit shards in every column or in none.  `wire` names what crosses the link in the forward:
+ *   HBK_LOWP_WIRE_TABLE  the rows in the table's own 16 bits: the owner gather is hbk_lowp_gather_rows_n into the
+ *                        send buffer (the element offsets of the fp32 layout, two bytes each, as the fused fp16
+ *                        wire addresses it), the row exchange moves 2-byte elements, the stitch is
+ *                        hbk_lowp_lookup_fwd_runs over the received rows; the own slice stays in place.  Half the
+ *                        wire bytes of fp32 and, unlike the fp16 wire, nothing is rounded.
+ *   HBK_LOWP_WIRE_FLOAT  the owner gather is hbk_lowp_lookup_fwd (one id per segment, sum, divisor = W, fp32 out)
+ *                        and everything behind it the fp32 path: the twin the 16-bit wire is compared against.
+ * Both give hbk_sharded_lookup_fwd over fp32 shards holding the upcast values, bit for bit.  Requester-side dedup,
+ * column groups, inline and hopped exchanges, weighted forwards and the prefetch work unchanged; hot_rows hints
+ * are ignored; the gradient exchange stays fp32.
+ *
+ * THE BACKWARD.  hbk_sharded_lookup_bwd[_apply] with apply_lr == 0 (the emit form, which never reads the shard)
+ * works unchanged and returns LOCAL row numbers; the caller steps its shards with hbk_lowp_apply_slices_n.  Every
+ * entry that steps reads and writes `shard` as fp32 rows of 4 * dim bytes and would run past a 2-byte shard, so on
+ * a 16-bit plan each of them is refused by name before any launch or exchange: hbk_sharded_lookup_bwd[_apply] with
+ * apply_lr != 0, hbk_sharded_lookup_bwd_adam, _ftrl and _rowwise_adagrad, and hbk_sharded_set_adam_slots,
+ * _ftrl_slots and _rowwise_adagrad_slots (HBK_UNIMPLEMENTED).  Also refused on a 16-bit plan:
+ * hbk_sharded_lookup_bwd_weights (the received rows are 16-bit), hbk_sharded_p2p_bind, a non-zero max_norm
+ * (hbk_sharded_set_max_norms) and a hash column (hbk_sharded_set_hash_tables), each HBK_UNIMPLEMENTED; and this
+ * setter itself on a plan created with wire_dtype == HBK_HALF, on a plan with a non-zero max_norm, a hash column
+ * or a p2p bind (HBK_UNIMPLEMENTED), with an unknown dtype or wire (HBK_INVALID_ARGUMENT).
+ *
+ * Stochastic rounding over shards: hbk_lowp_apply_slices_n keys its noise by (seed, step, column, row, element),
+ * and the row is the LOCAL row, so two ranks with one seed would round local row r alike.  A caller that steps the
+ * shards of rank k seeds that rank with  rank_seed = (seed + 0x9E3779B9 * k) mod 2^32  (what
+ * hb.embedding.LowpShardedGroupLookup does). */
+#define HBK_LOWP_WIRE_TABLE 0
+#define HBK_LOWP_WIRE_FLOAT 1
+int hbk_sharded_set_table_dtypes(hbk_sharded_t plan, const int32_t* dtypes /* [n_cols] or NULL */, int32_t wire);
 /* Sharded hash tables: columns of the plan whose shard is a hash-keyed table (hbk_hash_column_t above) keyed by
  * the RAW id.  owner = floormod(id, W) as for every column (the partition uses floormod: negative ids have an
  * owner); what changes is the owner's side: instead of row = id // W in a dense shard, the owner TRANSLATES the
