@@ -270,6 +270,8 @@ struct SlotNames {
   const char* s0;    // "m"
   const char* s1;    // "v"; NULL: the optimizer has one slot
 };
+// The three hyperparameter checks are defined in sparse_apply.hip, where every slot and slice entry (fp32 and 16-bit)
+// uses them, and declared here for sharded.hip alone, which checks before its exchanges.
 // host checks of a Lazy Adam call's hyperparameters (sparse_apply.hip): HBK_OK or HBK_INVALID_ARGUMENT
 int adam_check(const hbk_adam_t* adam, float lr, const char* who);
 // host checks of an FTRL call's hyperparameters (sparse_apply.hip): HBK_OK or HBK_INVALID_ARGUMENT

@@ -9,11 +9,6 @@
 //                            elements each (W = 4: one 8-byte load, W = 8: one 16-byte load, W = 1: unaligned or
 //                            dim % 4 != 0); ids are read once per wave, non-temporally, and handed to the row's
 //                            lanes by shuffle; outputs are streamed with non-temporal 16-byte stores.
-//   hbk_lowp_apply_slices_n  the optimizer step on IndexedSlices: sparse_apply.hip's walk (wave tasks of
-//                            kLowpItems rows per lane group, n_unique scanned on the device, grid-stride) with
-//                            another load and store of w -- upcast a row, step it with the SAME rule functors
-//                            (sparse_rules.h), round it back (nearest even, or stochastic for bf16).
-//
 //   hbk_lowp_gather_rows_n   the owner gather of the sharded step onto a 16-bit wire: the gather's tiles without the
 //                            upcast -- rows copied as bit patterns (8, 4 or 1 elements per lane), four row loads per
 //                            lane in flight before the first store.
@@ -21,7 +16,9 @@
 //                            instantiated over a column that carries a segmented table's run_start / run_base; the
 //                            plain instantiations keep their code (the row offset is an overload on the column type).
 //
-// The backward between the two is the fp32 reduce in its emit form, which never reads the table.
+// The element helpers (the upcast, the roundings) live in lowp_elems.h.  The backward is the fp32 reduce in its emit
+// form, which never reads the table; the optimizer step on its slices, hbk_lowp_apply_slices_n, is sparse_apply.hip's
+// walk over 16-bit rows and lives there.
 #include <string.h>
 
 #include <algorithm>
@@ -30,47 +27,10 @@
 
 #include "common.h"
 #include "lookup_common.h"
-#include "sparse_rules.h"
+#include "lowp_elems.h"
 
 namespace hbk {
 namespace {
-
-// ---------------------------------------------------------------------------------------------------------
-// element types
-
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ inline float up_bf16(uint32_t h) { return __uint_as_float(h << 16); }
-__device__ inline float up_fp16(uint32_t h) {
-  const uint16_t b = (uint16_t)h;
-  _Float16 x;
-  __builtin_memcpy(&x, &b, 2);
-  return (float)x;
-}
-__device__ inline float upcast(uint32_t h, bool bf16) { return bf16 ? up_bf16(h) : up_fp16(h); }
-
-// W elements of a row starting at element `off` (W = 4: 8-byte aligned, W = 8: 16-byte aligned), upcast
-template <int W>
-__device__ inline void load_elems(const uint16_t* table, uint64_t off, bool bf16, float (&v)[W]) {
-  if constexpr (W == 1) {
-    v[0] = upcast(table[off], bf16);
-  } else if constexpr (W == 4) {
-    const u32x2 p = *reinterpret_cast<const u32x2*>(table + off);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      v[2 * i] = upcast(p[i] & 0xffffu, bf16);
-      v[2 * i + 1] = upcast(p[i] >> 16, bf16);
-    }
-  } else {
-    const u32x4 p = *reinterpret_cast<const u32x4*>(table + off);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      v[2 * i] = upcast(p[i] & 0xffffu, bf16);
-      v[2 * i + 1] = upcast(p[i] >> 16, bf16);
-    }
-  }
-}
 
 // W fp32 outputs at float offset `off` (W >= 4: 16-byte aligned), streamed
 template <int W>
@@ -658,417 +618,6 @@ int lowp_gather_rows_n(int32_t n_cols, const hbk_lowp_gather_column_t* cols, hbk
   return HBK_OK;
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// apply
-
-constexpr int kLowpMaxCols = 64;   // columns per apply launch
-constexpr int kLowpBlock = 256;
-constexpr int kLowpWaves = kLowpBlock / kWave;
-constexpr int kLowpItems = 4;      // rows per lane group in flight
-constexpr int kLowpBlocksPerCU = 8;
-static_assert(kLowpMaxCols <= kWave, "one lane per column in the task scan");
-
-struct LowpCol {
-  uint16_t* w;
-  float* s0;
-  float* s1;
-  const int64_t* urows;
-  const float* grows;   // [cap, dim] contiguous
-  const int32_t* nu;
-  int64_t rows;
-  int32_t cap;
-  int32_t dim;
-  int32_t index;        // the column's index in the CALL (the noise is keyed by it)
-  uint8_t lpr_log2;
-  uint8_t vec4;
-  uint8_t bf16;
-};
-
-struct LowpRound {
-  const uint32_t* step;   // NULL: round to nearest even
-  uint32_t seed;
-};
-
-template <typename P>
-struct LowpArgs {
-  LowpCol c[kLowpMaxCols];
-  P p;
-  LowpRound round;
-  int32_t n_cols;
-};
-
-// murmur3's finalizer, and the noise of include/hbk.h
-__device__ inline uint32_t fmix32(uint32_t h) {
-  h ^= h >> 16;
-  h *= 0x85EBCA6Bu;
-  h ^= h >> 13;
-  h *= 0xC2B2AE35u;
-  h ^= h >> 16;
-  return h;
-}
-__device__ inline uint32_t noise_base(uint32_t seed, uint32_t step, int32_t c) {
-  return fmix32(seed ^ fmix32(step + 0x9E3779B9u * ((uint32_t)c + 1u)));
-}
-__device__ inline uint32_t noise_row(uint32_t base, int64_t r) {
-  return fmix32(fmix32(base ^ (uint32_t)(uint64_t)r) ^ (uint32_t)((uint64_t)r >> 32));
-}
-__device__ inline uint32_t noise_elem(uint32_t rowh, int k) {
-  return fmix32(rowh + 0x9E3779B9u * ((uint32_t)k + 1u));
-}
-
-// fp32 -> bf16, round to nearest even (a NaN stays a NaN: 0x7FC0)
-__device__ inline uint32_t bf16_nearest(float x) {
-  const uint32_t u = __float_as_uint(x);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0u;
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-// fp32 -> bf16, stochastic: nearest when the exponent field is all ones, else add 16 bits of noise and cut
-__device__ inline uint32_t bf16_stochastic(float x, uint32_t noise) {
-  const uint32_t u = __float_as_uint(x);
-  if ((u & 0x7f800000u) == 0x7f800000u) return bf16_nearest(x);
-  return (u + (noise & 0xffffu)) >> 16;
-}
-__device__ inline uint32_t fp16_nearest(float x) {
-  const _Float16 h = (_Float16)x;
-  uint16_t b;
-  __builtin_memcpy(&b, &h, 2);
-  return b;
-}
-
-// element k0 + i of row r rounded to the table's type
-__device__ inline uint32_t round_elem(float x, bool bf16, bool stochastic, uint32_t rowh, int k) {
-  if (!bf16) return fp16_nearest(x);
-  return stochastic ? bf16_stochastic(x, noise_elem(rowh, k)) : bf16_nearest(x);
-}
-
-// a lane chunk of a row of the table: load + upcast, round + store.  V = f32x4: 4 elements (8 bytes), V = float: one
-__device__ inline f32x4 load_w(const uint16_t* p, bool bf16, f32x4) {
-  float v[4];
-  load_elems<4>(p, 0, bf16, v);
-  return f32x4{v[0], v[1], v[2], v[3]};
-}
-__device__ inline float load_w(const uint16_t* p, bool bf16, float) { return upcast(*p, bf16); }
-__device__ inline void store_w(uint16_t* p, f32x4 v, bool bf16, bool stochastic, uint32_t rowh, int k0) {
-  u32x2 o;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    o[i] = round_elem(v[2 * i], bf16, stochastic, rowh, k0 + 2 * i) |
-           (round_elem(v[2 * i + 1], bf16, stochastic, rowh, k0 + 2 * i + 1) << 16);
-  }
-  *reinterpret_cast<u32x2*>(p) = o;
-}
-__device__ inline void store_w(uint16_t* p, float v, bool bf16, bool stochastic, uint32_t rowh, int k0) {
-  *p = (uint16_t)round_elem(v, bf16, stochastic, rowh, k0);
-}
-
-// one task: rows base + k * groups + grp (k < kLowpItems) of column c; W elements per lane chunk -- slot_task of
-// sparse_apply.hip with the table's load and store replaced (no clip, no pitch, no emit rule).  A lane issues
-// the w / slot / slot / g loads of all its rows before any arithmetic.
-template <typename V, int W, typename Rule>
-__device__ inline void lowp_task(const LowpCol& c, int64_t base, int64_t n, const Rule& rule, const LowpRound& round,
-                                 uint32_t step) {
-  const int lane = lane_id();
-  const int lpr = c.lpr_log2;
-  const int grp = lane >> lpr;
-  const int sub = lane & ((1 << lpr) - 1);
-  const int groups = kWave >> lpr;
-  const bool lane_on = sub * W < c.dim;
-  const bool bf16 = c.bf16 != 0;
-  const bool stochastic = round.step != nullptr;
-  int64_t r[kLowpItems];
-  bool on[kLowpItems];
-#pragma unroll
-  for (int k = 0; k < kLowpItems; ++k) {
-    const int64_t u = base + (int64_t)k * groups + grp;
-    on[k] = lane_on && u < n;
-    r[k] = on[k] ? __builtin_nontemporal_load(c.urows + u) : 0;
-    on[k] = on[k] && (uint64_t)r[k] < (uint64_t)c.rows;   // (holes: -1, or anything outside the table)
-  }
-  V w[kLowpItems], s0[kLowpItems], s1[kLowpItems], g[kLowpItems];
-#pragma unroll
-  for (int k = 0; k < kLowpItems; ++k) w[k] = s0[k] = s1[k] = g[k] = zero_v<V>();
-  float acc[Rule::kRowwise ? kLowpItems : 1], sq[Rule::kRowwise ? kLowpItems : 1];
-  if constexpr (Rule::kRowwise) {
-#pragma unroll
-    for (int k = 0; k < kLowpItems; ++k) acc[k] = 0.0f;
-  }
-#pragma unroll
-  for (int k = 0; k < kLowpItems; ++k) {
-    if (!on[k]) continue;
-    const int64_t u = base + (int64_t)k * groups + grp;
-    const int64_t off = r[k] * c.dim + sub * W;
-    w[k] = load_w(c.w + off, bf16, V());
-    if constexpr (Rule::kSlots >= 1) s0[k] = *reinterpret_cast<const V*>(c.s0 + off);
-    if constexpr (Rule::kSlots >= 2) s1[k] = *reinterpret_cast<const V*>(c.s1 + off);
-    if constexpr (Rule::kRowwise) acc[k] = c.s0[r[k]];
-    g[k] = __builtin_nontemporal_load(reinterpret_cast<const V*>(c.grows + u * c.dim + sub * W));
-  }
-  if constexpr (Rule::kRowwise) {
-    // every lane of the wave takes part (lanes without a row or past dim pass +0.0f)
-#pragma unroll
-    for (int k = 0; k < kLowpItems; ++k) sq[k] = group_sum(chunk_sum(g[k] * g[k]), lpr);
-  }
-  const uint32_t nbase = stochastic ? noise_base(round.seed, step, c.index) : 0u;
-#pragma unroll
-  for (int k = 0; k < kLowpItems; ++k) {
-    if (!on[k]) continue;
-    const int64_t off = r[k] * c.dim + sub * W;
-    const uint32_t rowh = stochastic ? noise_row(nbase, r[k]) : 0u;
-    if constexpr (Rule::kRowwise) {
-      float rate;
-      const float na = rule.row(acc[k], sq[k], (float)c.dim, &rate);
-      if (sub == 0) c.s0[r[k]] = na;
-      store_w(c.w + off, w[k] - rate * g[k], bf16, stochastic, rowh, sub * W);
-    } else {
-      const Stepped<V> o = rule(w[k], s0[k], s1[k], g[k]);
-      if constexpr (Rule::kSlots >= 1) *reinterpret_cast<V*>(c.s0 + off) = o.s0;
-      if constexpr (Rule::kSlots >= 2) *reinterpret_cast<V*>(c.s1 + off) = o.s1;
-      store_w(c.w + off, o.w, bf16, stochastic, rowh, sub * W);
-    }
-  }
-}
-
-// the body of every apply kernel (slot_apply_body of sparse_apply.hip): wave 0 reads the columns' n_unique
-// (clamped to the capacity) and scans their task counts into LDS, lane 0 runs the rule's setup; after the
-// barrier every wave walks the tasks grid-stride
-template <typename Rule>
-__device__ inline void lowp_apply_body(const LowpArgs<typename Rule::Params>& a) {
-  __shared__ int64_t s_end[kLowpMaxCols];   // inclusive prefix of the columns' task counts
-  __shared__ int64_t s_n[kLowpMaxCols];     // their n_unique (clamped to the capacity)
-  if (threadIdx.x < kWave) {
-    const int lane = (int)threadIdx.x;
-    int64_t tasks = 0;
-    if (lane < a.n_cols) {
-      const LowpCol& c = a.c[lane];
-      const int64_t n = min(max(__builtin_nontemporal_load(c.nu), 0), c.cap);
-      const int64_t rpt = (int64_t)(kWave >> c.lpr_log2) * kLowpItems;
-      tasks = (n + rpt - 1) / rpt;
-      s_n[lane] = n;
-    }
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-      const int64_t t = __shfl_up(tasks, d, kWave);
-      if (lane >= d) tasks += t;
-    }
-    if (lane < a.n_cols) s_end[lane] = tasks;
-    if (lane == 0) Rule::setup(a.p);
-  }
-  __syncthreads();
-  const typename Rule::State st = Rule::state();
-  const uint32_t step = a.round.step != nullptr ? *a.round.step : 0u;   // (read before the advance launch writes it)
-  const int64_t total = s_end[a.n_cols - 1];
-  int ci = 0;
-  for (int64_t t = (int64_t)blockIdx.x * kLowpWaves + threadIdx.x / kWave; t < total;
-       t += (int64_t)gridDim.x * kLowpWaves) {
-    while (s_end[ci] <= t) ++ci;   // (t only grows: the column only moves forward)
-    const LowpCol& col = a.c[ci];
-    const int64_t t0 = ci == 0 ? 0 : s_end[ci - 1];
-    const int64_t base = (t - t0) * ((int64_t)(kWave >> col.lpr_log2) * kLowpItems);
-    if (col.vec4) {
-      lowp_task<f32x4, 4, Rule>(col, base, s_n[ci], Rule(a.p, st), a.round, step);
-    } else {
-      lowp_task<float, 1, Rule>(col, base, s_n[ci], Rule(a.p, st), a.round, step);
-    }
-  }
-}
-
-template <typename Rule>
-__global__ __launch_bounds__(kLowpBlock) void lowp_apply_kernel(LowpArgs<typename Rule::Params> a) {
-  lowp_apply_body<Rule>(a);
-}
-
-// TF's _finish (adam_finish_kernel of sparse_apply.hip): beta1^t, beta2^t -> beta1^(t+1), beta2^(t+1)
-__global__ void lowp_adam_finish_kernel(float* powers, float beta1, float beta2) {
-  if (threadIdx.x == 0) {
-    powers[0] = powers[0] * beta1;
-    powers[1] = powers[1] * beta2;
-  }
-}
-
-// the step counter of the stochastic rounding, behind the apply in stream order
-__global__ void lowp_advance_kernel(uint32_t* step) {
-  if (threadIdx.x == 0) step[0] = step[0] + 1u;
-}
-
-// the launches of one call: launch(args, blocks, stream) sets args.p and launches the rule's kernel
-template <typename P, typename Launch>
-int launch_lowp(int32_t n_cols, const hbk_lowp_slices_column_t* cols, const std::vector<RowShape>& shapes,
-                float* const* s0, float* const* s1, const LowpRound& round, hipStream_t stream, Launch launch) {
-  for (int32_t c0 = 0; c0 < n_cols; c0 += kLowpMaxCols) {
-    LowpArgs<P> a;
-    memset(&a, 0, sizeof(a));
-    a.round = round;
-    int64_t tasks = 0;
-    int k = 0;
-    for (int32_t c = c0; c < std::min(n_cols, c0 + kLowpMaxCols); ++c) {
-      const hbk_lowp_slices_column_t& h = cols[c];
-      if (h.capacity <= 0 || h.rows <= 0) continue;
-      LowpCol& d = a.c[k];
-      d.w = static_cast<uint16_t*>(h.table);
-      d.s0 = s0 != nullptr ? s0[c] : nullptr;
-      d.s1 = s1 != nullptr ? s1[c] : nullptr;
-      d.urows = h.unique_rows;
-      d.grows = h.grad_rows;
-      d.nu = h.n_unique;
-      d.rows = h.rows;
-      d.cap = (int32_t)h.capacity;
-      d.dim = h.dim;
-      d.index = c;
-      d.lpr_log2 = shapes[(size_t)c].lpr_log2;
-      d.vec4 = shapes[(size_t)c].vec4;
-      d.bf16 = h.table_dtype == HBK_LOWP_BF16;
-      const int64_t rpt = (int64_t)(kWave >> d.lpr_log2) * kLowpItems;
-      tasks += (std::min<int64_t>(h.capacity, h.rows) + rpt - 1) / rpt;
-      ++k;
-    }
-    if (k == 0) continue;
-    a.n_cols = k;
-    const int64_t want = (tasks + kLowpWaves - 1) / kLowpWaves;
-    const unsigned blocks =
-        (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)device_cus() * kLowpBlocksPerCU));
-    launch(a, blocks, stream);
-    HBK_HIP_OK(hipGetLastError());
-  }
-  return HBK_OK;
-}
-
-int lowp_apply_slices(int32_t n_cols, const hbk_lowp_slices_column_t* cols, int32_t apply, float* const* slot0,
-                      float* const* slot1, const void* params, float lr, const hbk_lowp_rounding_t* rounding,
-                      hbk_stream_t stream_) {
-  static const char* kWho = "lowp_apply_slices_n";
-  constexpr float kMax = 3.402823466e38f;
-  HBK_REQUIRE(n_cols >= 0, "%s: n_cols must be >= 0, got %d", kWho, n_cols);
-  HBK_REQUIRE(n_cols == 0 || cols != nullptr, "%s: cols is NULL", kWho);
-  HBK_REQUIRE(apply == HBK_APPLY_SGD || apply == HBK_APPLY_ADAGRAD || apply == HBK_APPLY_LAZY_ADAM ||
-                  apply == HBK_APPLY_FTRL || apply == HBK_APPLY_ROWWISE_ADAGRAD,
-              "%s: apply must be HBK_APPLY_SGD, _ADAGRAD, _LAZY_ADAM, _FTRL or _ROWWISE_ADAGRAD, got %d", kWho,
-              apply);
-  const int32_t mode = rounding != nullptr ? rounding->mode : HBK_LOWP_ROUND_NEAREST;
-  HBK_REQUIRE(mode == HBK_LOWP_ROUND_NEAREST || mode == HBK_LOWP_ROUND_STOCHASTIC,
-              "%s: rounding mode must be HBK_LOWP_ROUND_NEAREST or HBK_LOWP_ROUND_STOCHASTIC, got %d", kWho, mode);
-  const bool stochastic = mode == HBK_LOWP_ROUND_STOCHASTIC;
-  HBK_REQUIRE(!stochastic || (rounding->step != nullptr && ((uintptr_t)rounding->step & 3) == 0),
-              "%s: stochastic rounding needs a device uint32 [1] step counter", kWho);
-  // the rule's slots: how many table-shaped ones (they enter the row shape's alignment), and the row-wise one
-  const int n_slots = apply == HBK_APPLY_ADAGRAD ? 1 : (apply == HBK_APPLY_LAZY_ADAM || apply == HBK_APPLY_FTRL) ? 2 : 0;
-  const bool rowwise = apply == HBK_APPLY_ROWWISE_ADAGRAD;
-  const char* n0 = apply == HBK_APPLY_LAZY_ADAM ? "m" : apply == HBK_APPLY_FTRL ? "accum" : "the accumulator";
-  const char* n1 = apply == HBK_APPLY_LAZY_ADAM ? "v" : "linear";
-  // the hyperparameters and the lr, as the rule's own entry refuses them
-  int rc = HBK_OK;
-  if (apply == HBK_APPLY_LAZY_ADAM) {
-    if ((rc = adam_check(static_cast<const hbk_adam_t*>(params), lr, kWho)) != HBK_OK) return rc;
-  } else if (apply == HBK_APPLY_FTRL) {
-    if ((rc = ftrl_check(static_cast<const hbk_ftrl_t*>(params), lr, kWho)) != HBK_OK) return rc;
-  } else if (rowwise) {
-    if ((rc = rowwise_adagrad_check(static_cast<const hbk_rowwise_adagrad_t*>(params), lr, kWho)) != HBK_OK) return rc;
-  } else {
-    HBK_REQUIRE(lr != 0.0f && lr >= -kMax && lr <= kMax, "%s: lr must be finite and != 0, got %g", kWho, (double)lr);
-  }
-  HBK_REQUIRE(n_cols == 0 || (n_slots < 1 && !rowwise) || slot0 != nullptr, "%s: the %s array (slot0) is NULL", kWho, n0);
-  HBK_REQUIRE(n_cols == 0 || n_slots < 2 || slot1 != nullptr, "%s: the %s array (slot1) is NULL", kWho, n1);
-  std::vector<RowShape> shapes((size_t)n_cols, RowShape{});
-  std::vector<uintptr_t> seen;
-  seen.reserve((size_t)n_cols * 3);
-  for (int32_t c = 0; c < n_cols; ++c) {
-    const hbk_lowp_slices_column_t& s = cols[c];
-    HBK_REQUIRE(dtype_ok(s.table_dtype), "%s: column %d: table_dtype must be HBK_LOWP_BF16 or HBK_LOWP_FP16, got %d",
-                kWho, c, s.table_dtype);
-    HBK_REQUIRE(!stochastic || s.table_dtype == HBK_LOWP_BF16,
-                "%s: column %d: stochastic rounding is defined for bf16 tables only", kWho, c);
-    HBK_REQUIRE(s.capacity >= 0 && s.capacity < (1ll << 30), "%s: column %d: capacity %lld must be in [0, 2^30)",
-                kWho, c, (long long)s.capacity);
-    HBK_REQUIRE(s.rows >= 0, "%s: column %d: rows must be >= 0, got %lld", kWho, c, (long long)s.rows);
-    HBK_REQUIRE(s.dim >= 1, "%s: column %d: dim must be >= 1", kWho, c);
-    HBK_REQUIRE(((uintptr_t)s.table & 1) == 0, "%s: column %d: table must be 2-byte aligned", kWho, c);
-    float* const a0 = (n_slots >= 1 || rowwise) ? slot0[c] : nullptr;
-    float* const a1 = n_slots >= 2 ? slot1[c] : nullptr;
-    HBK_REQUIRE(!(n_slots >= 1 || rowwise) || (a0 != nullptr && ((uintptr_t)a0 & 3) == 0),
-                "%s: column %d: %s must be a device fp32 buffer", kWho, c, n0);
-    HBK_REQUIRE(n_slots < 2 || (a1 != nullptr && ((uintptr_t)a1 & 3) == 0),
-                "%s: column %d: %s must be a device fp32 buffer", kWho, c, n1);
-    if (s.capacity > 0) {
-      HBK_REQUIRE(s.table != nullptr, "%s: column %d: table is NULL", kWho, c);
-      HBK_REQUIRE(s.unique_rows != nullptr && ((uintptr_t)s.unique_rows & 7) == 0,
-                  "%s: column %d: unique_rows must be a device int64 [capacity]", kWho, c);
-      HBK_REQUIRE(s.grad_rows != nullptr && ((uintptr_t)s.grad_rows & 3) == 0,
-                  "%s: column %d: grad_rows must be a device fp32 [capacity, dim]", kWho, c);
-      HBK_REQUIRE(s.n_unique != nullptr && ((uintptr_t)s.n_unique & 3) == 0,
-                  "%s: column %d: n_unique must be a device int32 [1]", kWho, c);
-      // the row shape of the fp32 entry: the table's bytes count twice (an 8-byte chunk where fp32 has 16), the
-      // row-wise word does not enter
-      const uintptr_t bits = ((uintptr_t)s.table * 2) | (uintptr_t)s.grad_rows |
-                             (n_slots >= 1 ? (uintptr_t)a0 : 0) | (uintptr_t)a1;
-      HBK_REQUIRE(make_rowshape(s.dim, bits, &shapes[(size_t)c]),
-                  "%s: column %d: dim %d: at most 256 when dim %% 4 == 0, the table is 8-byte and the slots and "
-                  "grad_rows are 16-byte aligned, 64 otherwise", kWho, c, s.dim);
-    }
-    if (s.table != nullptr) seen.push_back((uintptr_t)s.table);
-    if (a0 != nullptr) seen.push_back((uintptr_t)a0);
-    if (a1 != nullptr) seen.push_back((uintptr_t)a1);
-  }
-  std::sort(seen.begin(), seen.end());
-  HBK_REQUIRE(std::adjacent_find(seen.begin(), seen.end()) == seen.end(),
-              "%s: two columns name the same table or slot (a row stepped twice in one call would race)", kWho);
-
-  hipStream_t stream = as_stream(stream_);
-  const LowpRound round = {stochastic ? rounding->step : nullptr, stochastic ? rounding->seed : 0u};
-  if (apply == HBK_APPLY_SGD) {
-    rc = launch_lowp<LrParams>(n_cols, cols, shapes, nullptr, nullptr, round, stream,
-                               [&](LowpArgs<LrParams>& a, unsigned blocks, hipStream_t s) {
-                                 a.p = LrParams{lr};
-                                 hipLaunchKernelGGL(lowp_apply_kernel<SgdRule>, dim3(blocks), dim3(kLowpBlock), 0, s, a);
-                               });
-  } else if (apply == HBK_APPLY_ADAGRAD) {
-    rc = launch_lowp<LrParams>(n_cols, cols, shapes, slot0, nullptr, round, stream,
-                               [&](LowpArgs<LrParams>& a, unsigned blocks, hipStream_t s) {
-                                 a.p = LrParams{lr};
-                                 hipLaunchKernelGGL(lowp_apply_kernel<AdagradRule>, dim3(blocks), dim3(kLowpBlock), 0,
-                                                    s, a);
-                               });
-  } else if (apply == HBK_APPLY_LAZY_ADAM) {
-    const hbk_adam_t* adam = static_cast<const hbk_adam_t*>(params);
-    rc = launch_lowp<AdamParams>(n_cols, cols, shapes, slot0, slot1, round, stream,
-                                 [&](LowpArgs<AdamParams>& a, unsigned blocks, hipStream_t s) {
-                                   a.p = AdamParams{adam->beta_powers, lr, adam->beta1, adam->beta2, adam->epsilon};
-                                   hipLaunchKernelGGL(lowp_apply_kernel<AdamRule>, dim3(blocks), dim3(kLowpBlock), 0,
-                                                      s, a);
-                                 });
-    if (rc == HBK_OK && adam->finish) {
-      hipLaunchKernelGGL(lowp_adam_finish_kernel, dim3(1), dim3(kWave), 0, stream, adam->beta_powers, adam->beta1,
-                         adam->beta2);
-      HBK_HIP_OK(hipGetLastError());
-    }
-  } else if (apply == HBK_APPLY_FTRL) {
-    const hbk_ftrl_t* ftrl = static_cast<const hbk_ftrl_t*>(params);
-    rc = launch_lowp<FtrlParams>(
-        n_cols, cols, shapes, slot0, slot1, round, stream,
-        [&](LowpArgs<FtrlParams>& a, unsigned blocks, hipStream_t s) {
-          a.p = FtrlParams{lr, ftrl->l1, 2.0f * ftrl->l2, 2.0f * ftrl->l2_shrinkage, -ftrl->lr_power};
-          // lr_power = -0.5 (TF's default) takes the sqrtf instantiation, any other the powf one
-          if (ftrl->lr_power != -0.5f) {
-            hipLaunchKernelGGL(lowp_apply_kernel<FtrlRule<true>>, dim3(blocks), dim3(kLowpBlock), 0, s, a);
-          } else {
-            hipLaunchKernelGGL(lowp_apply_kernel<FtrlRule<false>>, dim3(blocks), dim3(kLowpBlock), 0, s, a);
-          }
-        });
-  } else {
-    const hbk_rowwise_adagrad_t* opt = static_cast<const hbk_rowwise_adagrad_t*>(params);
-    rc = launch_lowp<RowwiseParams>(n_cols, cols, shapes, slot0, nullptr, round, stream,
-                                    [&](LowpArgs<RowwiseParams>& a, unsigned blocks, hipStream_t s) {
-                                      a.p = RowwiseParams{lr, opt->epsilon};
-                                      hipLaunchKernelGGL(lowp_apply_kernel<RowwiseAdagradRule>, dim3(blocks),
-                                                         dim3(kLowpBlock), 0, s, a);
-                                    });
-  }
-  if (rc != HBK_OK) return rc;
-  if (stochastic && rounding->advance != 0) {
-    hipLaunchKernelGGL(lowp_advance_kernel, dim3(1), dim3(kWave), 0, stream, rounding->step);
-    HBK_HIP_OK(hipGetLastError());
-  }
-  return HBK_OK;
-}
-
 }  // namespace
 }  // namespace hbk
 
@@ -1083,10 +632,4 @@ extern "C" int hbk_lowp_lookup_fwd_runs(int32_t n_cols, const hbk_lowp_lookup_ru
 
 extern "C" int hbk_lowp_gather_rows_n(int32_t n_cols, const hbk_lowp_gather_column_t* cols, hbk_stream_t stream) {
   return hbk::lowp_gather_rows_n(n_cols, cols, stream);
-}
-
-extern "C" int hbk_lowp_apply_slices_n(int32_t n_cols, const hbk_lowp_slices_column_t* cols, int32_t apply,
-                                       float* const* slot0, float* const* slot1, const void* params, float lr,
-                                       const hbk_lowp_rounding_t* rounding, hbk_stream_t stream) {
-  return hbk::lowp_apply_slices(n_cols, cols, apply, slot0, slot1, params, lr, rounding, stream);
 }

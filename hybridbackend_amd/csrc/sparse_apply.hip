@@ -31,6 +31,15 @@
 // reads the same address: one request), sums g * g over the lane group in the clip prologue's order
 // (chunk_sum, then the group_sum butterfly), and lane 0 of the group stores the word back.  Everything
 // kRowwise adds sits under `if constexpr`, so the other instantiations are the instructions they were.
+//
+// The walk is also parameterised by a table policy: how a lane chunk of a table row is read and written.
+// Fp32Rows is the plain load and store of every kernel above (SlotCol, SlotArgs; their instructions did not
+// change when the policy came).  LowpRows (LowpCol, LowpArgs; hbk_lowp_apply_slices_n, lowp_apply_kernel<Rule>)
+// reads bf16 / fp16 rows upcast exactly and rounds the stepped row back -- to nearest even, or for bf16
+// stochastically with noise keyed by (seed, step, column, row, element); the element helpers are lowp_elems.h's,
+// which the 16-bit forward (lowp_tables.hip) shares.  It has no clip, no pitch and no emit rule.  The two slice
+// entries share the rule dispatch (dispatch_rule), the launch packer (launch_slices over fill_slot_cols) and the
+// checks both word alike; each keeps the refusals of its own.
 #include <string.h>
 
 #include <algorithm>
@@ -38,6 +47,7 @@
 
 #include "common.h"
 #include "lookup_common.h"
+#include "lowp_elems.h"
 #include "sparse_rules.h"
 
 namespace hbk {
@@ -75,7 +85,90 @@ struct SlotArgs {
   int32_t n_cols;
 };
 
-// The rules (sparse_rules.h, shared with lowp_tables.hip): AdamRule, FtrlRule<>, SgdRule, AdagradRule,
+// one column of a 16-bit apply (hbk_lowp_apply_slices_n): rows of bf16 / fp16 elements, dim apart; fp32 slots
+struct LowpCol {
+  uint16_t* w;
+  float* s0;
+  float* s1;
+  const int64_t* urows;
+  const float* grows;   // [cap, dim] contiguous
+  const int32_t* nu;
+  int64_t rows;
+  int32_t cap;
+  int32_t dim;
+  int32_t index;        // the column's index in the CALL (the noise is keyed by it)
+  uint8_t lpr_log2;
+  uint8_t vec4;
+  uint8_t bf16;
+};
+
+struct LowpRound {
+  const uint32_t* step;   // NULL: round to nearest even
+  uint32_t seed;
+};
+
+template <typename P>
+struct LowpArgs {
+  LowpCol c[kSlotMaxCols];
+  P p;
+  LowpRound round;
+  int32_t n_cols;
+};
+
+// The table policies: how the walk reads and writes a lane chunk of a table row.  A policy names its column and
+// its kernel arguments, is built once per thread from the arguments (after the barrier), and builds a Task once
+// per task.  load(c, off, V()) reads the chunk at element `off` of c.w as fp32; task.row(r) is row r's word of
+// rounding noise and task.store(x, p, that word, k0) writes x at p as elements k0 .. of the row.  Fp32Rows holds
+// nothing and compiles to the plain loads and stores -- to the very instructions of the kernels before the
+// policies, which is why store takes the value first (an assignment evaluates its right side first) and row takes
+// the row by reference (an argument passed by value is marked as defined, and that alone reorders the FTRL kernels).
+struct Fp32Rows {
+  using Col = SlotCol;
+  template <typename P>
+  using Args = SlotArgs<P>;
+  template <typename P>
+  __device__ explicit Fp32Rows(const SlotArgs<P>&) {}
+  __device__ static int32_t pitch(const SlotCol& c) { return c.pitch; }
+  template <typename V>
+  __device__ static V load(const SlotCol& c, int64_t off, V) { return *reinterpret_cast<const V*>(c.w + off); }
+  struct Task {
+    __device__ Task(const Fp32Rows&, const SlotCol&) {}
+    template <typename V>
+    __device__ void store(V x, float* p, uint32_t, int) const { *reinterpret_cast<V*>(p) = x; }
+    __device__ uint32_t row(const int64_t&) const { return 0u; }
+  };
+};
+
+// 16-bit rows: upcast on the load; on the store round to nearest even or, for bf16, stochastically with the noise
+// of include/hbk.h, keyed by (seed, step, the column's index, the row, the element).  The step word is read once
+// per thread, behind the barrier and so before the advance launch -- behind the apply in stream order -- writes it.
+struct LowpRows {
+  using Col = LowpCol;
+  template <typename P>
+  using Args = LowpArgs<P>;
+  bool stochastic;
+  uint32_t seed, step;
+  template <typename P>
+  __device__ explicit LowpRows(const LowpArgs<P>& a)
+      : stochastic(a.round.step != nullptr), seed(a.round.seed), step(stochastic ? *a.round.step : 0u) {}
+  __device__ static int32_t pitch(const LowpCol& c) { return c.dim; }
+  template <typename V>
+  __device__ static V load(const LowpCol& c, int64_t off, V) { return load_w(c.w + off, c.bf16 != 0, V()); }
+  struct Task {
+    bool bf16, stochastic;
+    uint32_t nbase;
+    __device__ Task(const LowpRows& t, const LowpCol& c)
+        : bf16(c.bf16 != 0), stochastic(t.stochastic),
+          nbase(stochastic ? noise_base(t.seed, t.step, c.index) : 0u) {}
+    template <typename V>
+    __device__ void store(V x, uint16_t* p, uint32_t rowh, int k0) const {
+      store_w(p, x, bf16, stochastic, rowh, k0);
+    }
+    __device__ uint32_t row(const int64_t& r) const { return stochastic ? noise_row(nbase, r) : 0u; }
+  };
+};
+
+// The rules (sparse_rules.h): AdamRule, FtrlRule<>, SgdRule, AdagradRule,
 // RowwiseAdagradRule, their Params, Stepped<> and the sums chunk_sum / group_sum.  A rule is the arithmetic
 // of one optimizer: Rule::setup(p) runs on wave 0 lane 0 of every workgroup before the barrier,
 // Rule::state() on every thread after it; every task builds its Rule(p, state), and rule(w, s0, s1, g)
@@ -128,8 +221,10 @@ __device__ inline V clip_grad(V x, V g, float c, int lpr_log2) {
 // every form (the IndexedSlices of a clipped column are the gradient its rows were stepped with).
 // Rule::kRowwise: c.s0 is one word per row -- every lane of the row's group loads that same word with the
 // task's other loads, the group sums g * g (after the clip: g' * g'), lane 0 of the group stores the word.
-template <typename V, int W, typename Rule, bool CLIP = false>
-__device__ inline void slot_task(const SlotCol& c, int64_t base, int64_t n, const Rule& rule) {
+// Table: the rows' policy (the 16-bit one has no clip, no emit rule and no pitch of its own).
+template <typename V, int W, typename Rule, bool CLIP, typename Table>
+__device__ inline void slot_task(const Table& table, const typename Table::Col& c, int64_t base, int64_t n,
+                                 const Rule& rule) {
   const int lane = lane_id();
   const int lpr = c.lpr_log2;
   const int grp = lane >> lpr;
@@ -159,8 +254,8 @@ __device__ inline void slot_task(const SlotCol& c, int64_t base, int64_t n, cons
   for (int k = 0; k < kSlotItems; ++k) {
     if (!on[k]) continue;
     const int64_t u = base + (int64_t)k * groups + grp;
-    const int64_t off = r[k] * c.pitch + sub * W;
-    if constexpr (Rule::kStep || CLIP) w[k] = *reinterpret_cast<const V*>(c.w + off);
+    const int64_t off = r[k] * Table::pitch(c) + sub * W;
+    if constexpr (Rule::kStep || CLIP) w[k] = Table::load(c, off, V());
     if constexpr (Rule::kSlots >= 1) s0[k] = *reinterpret_cast<const V*>(c.s0 + off);
     if constexpr (Rule::kSlots >= 2) s1[k] = *reinterpret_cast<const V*>(c.s1 + off);
     if constexpr (Rule::kRowwise) acc[k] = c.s0[r[k]];
@@ -177,6 +272,7 @@ __device__ inline void slot_task(const SlotCol& c, int64_t base, int64_t n, cons
 #pragma unroll
     for (int k = 0; k < kSlotItems; ++k) sq[k] = group_sum(chunk_sum(g[k] * g[k]), lpr);
   }
+  const typename Table::Task rows(table, c);
 #pragma unroll
   for (int k = 0; k < kSlotItems; ++k) {
     if (!on[k]) continue;
@@ -186,29 +282,30 @@ __device__ inline void slot_task(const SlotCol& c, int64_t base, int64_t n, cons
         *reinterpret_cast<V*>(const_cast<float*>(c.grows) + u * c.dim + sub * W) = g[k];
       }
     }
+    const uint32_t rowh = rows.row(r[k]);
     if constexpr (Rule::kRowwise) {
       float rate;
       const float na = rule.row(acc[k], sq[k], (float)c.dim, &rate);
       if (sub == 0) c.s0[r[k]] = na;
-      const int64_t off = r[k] * c.pitch + sub * W;
-      *reinterpret_cast<V*>(c.w + off) = w[k] - rate * g[k];
+      const int64_t off = r[k] * Table::pitch(c) + sub * W;
+      rows.store(w[k] - rate * g[k], c.w + off, rowh, sub * W);
     } else if constexpr (Rule::kStep) {
-      const int64_t off = r[k] * c.pitch + sub * W;
+      const int64_t off = r[k] * Table::pitch(c) + sub * W;
       const Stepped<V> o = rule(w[k], s0[k], s1[k], g[k]);
       if constexpr (Rule::kSlots >= 1) *reinterpret_cast<V*>(c.s0 + off) = o.s0;
       if constexpr (Rule::kSlots >= 2) *reinterpret_cast<V*>(c.s1 + off) = o.s1;
-      *reinterpret_cast<V*>(c.w + off) = o.w;
+      rows.store(o.w, c.w + off, rowh, sub * W);
     }
   }
 }
 
 // wave 0 of a workgroup: the columns' n_unique (clamped to the capacity) into s_n and the inclusive
 // prefix of their task counts into s_end
-__device__ inline void scan_tasks(const SlotCol* cols, int n_cols, int lane, int64_t* s_end,
-                                  int64_t* s_n) {
+template <typename Col>
+__device__ inline void scan_tasks(const Col* cols, int n_cols, int lane, int64_t* s_end, int64_t* s_n) {
   int64_t tasks = 0;
   if (lane < n_cols) {
-    const SlotCol& c = cols[lane];
+    const Col& c = cols[lane];
     const int64_t n = min(max(__builtin_nontemporal_load(c.nu), 0), c.cap);
     const int64_t rpt = (int64_t)(kWave >> c.lpr_log2) * kSlotItems;
     tasks = (n + rpt - 1) / rpt;
@@ -223,15 +320,15 @@ __device__ inline void scan_tasks(const SlotCol* cols, int n_cols, int lane, int
 }
 
 // every wave: the tasks of the scan, grid-stride; task(col, first row, n_unique) runs one
-template <typename Task>
-__device__ inline void walk_tasks(const SlotCol* cols, int n_cols, const int64_t* s_end,
-                                  const int64_t* s_n, Task task) {
+template <typename Col, typename Task>
+__device__ inline void walk_tasks(const Col* cols, int n_cols, const int64_t* s_end, const int64_t* s_n,
+                                  Task task) {
   const int64_t total = s_end[n_cols - 1];
   int c = 0;
   for (int64_t t = (int64_t)blockIdx.x * kSlotWaves + threadIdx.x / kWave; t < total;
        t += (int64_t)gridDim.x * kSlotWaves) {
     while (s_end[c] <= t) ++c;   // (t only grows: the column only moves forward)
-    const SlotCol& col = cols[c];
+    const Col& col = cols[c];
     const int64_t t0 = c == 0 ? 0 : s_end[c - 1];
     const int64_t base = (t - t0) * ((int64_t)(kWave >> col.lpr_log2) * kSlotItems);
     task(col, base, s_n[c]);
@@ -239,8 +336,8 @@ __device__ inline void walk_tasks(const SlotCol* cols, int n_cols, const int64_t
 }
 
 // the body of every apply kernel: the scan, the rule's setup, the barrier, the walk
-template <typename Rule, bool CLIP = false>
-__device__ inline void slot_apply_body(const SlotArgs<typename Rule::Params>& a) {
+template <typename Rule, bool CLIP = false, typename Table = Fp32Rows>
+__device__ inline void slot_apply_body(const typename Table::template Args<typename Rule::Params>& a) {
   __shared__ int64_t s_end[kSlotMaxCols];   // inclusive prefix of the columns' task counts
   __shared__ int64_t s_n[kSlotMaxCols];     // their n_unique (clamped to the capacity)
   if (threadIdx.x < kWave) {
@@ -250,11 +347,12 @@ __device__ inline void slot_apply_body(const SlotArgs<typename Rule::Params>& a)
   }
   __syncthreads();
   const typename Rule::State st = Rule::state();
-  walk_tasks(a.c, a.n_cols, s_end, s_n, [&](const SlotCol& col, int64_t base, int64_t n) {
+  const Table table(a);
+  walk_tasks(a.c, a.n_cols, s_end, s_n, [&](const typename Table::Col& col, int64_t base, int64_t n) {
     if (col.vec4) {
-      slot_task<f32x4, 4, Rule, CLIP>(col, base, n, Rule(a.p, st));
+      slot_task<f32x4, 4, Rule, CLIP>(table, col, base, n, Rule(a.p, st));
     } else {
-      slot_task<float, 1, Rule, CLIP>(col, base, n, Rule(a.p, st));
+      slot_task<float, 1, Rule, CLIP>(table, col, base, n, Rule(a.p, st));
     }
   });
 }
@@ -296,6 +394,17 @@ __global__ __launch_bounds__(kSlotBlock) void sparse_rowwise_adagrad_apply_kerne
 
 __global__ __launch_bounds__(kSlotBlock) void sparse_rowwise_adagrad_clip_kernel(SlotArgs<RowwiseParams> a) {
   slot_apply_body<RowwiseAdagradRule, true>(a);
+}
+
+// the walk over 16-bit rows (hbk_lowp_apply_slices_n), every rule
+template <typename Rule>
+__global__ __launch_bounds__(kSlotBlock) void lowp_apply_kernel(LowpArgs<typename Rule::Params> a) {
+  slot_apply_body<Rule, false, LowpRows>(a);
+}
+
+// the step counter of the stochastic rounding, behind the apply in stream order
+__global__ void lowp_advance_kernel(uint32_t* step) {
+  if (threadIdx.x == 0) step[0] = step[0] + 1u;
 }
 
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -456,33 +565,46 @@ int run_emit_form(const char* who, int32_t n_cols, const hbk_lookup_grad_column_
                                     workspace_bytes - (size_t)(base - (char*)workspace), stream_);
 }
 
+// what a descriptor takes from the host column of its table kind: the capacity, and the table's own fields
+inline int64_t capacity_of(const hbk_lookup_grad_column_t& h) { return h.n_ids; }
+inline int64_t capacity_of(const hbk_lowp_slices_column_t& h) { return h.capacity; }
+inline void set_table(SlotCol& d, const hbk_lookup_grad_column_t& h, int32_t c, const float* max_norms) {
+  d.w = h.table;
+  d.pitch = h.table_pitch > 0 ? h.table_pitch : h.dim;
+  d.max_norm = max_norms != nullptr ? max_norms[c] : 0.0f;
+}
+inline void set_table(LowpCol& d, const hbk_lowp_slices_column_t& h, int32_t c, const float*) {
+  d.w = static_cast<uint16_t*>(h.table);
+  d.index = c;
+  d.bf16 = h.table_dtype == HBK_LOWP_BF16;
+}
+
 // phase 2's descriptors of columns c0 .. c1 (those with rows to step) into out; the number of them
-// and the grid the launch needs
-int fill_slot_cols(const std::vector<hbk_lookup_grad_column_t>& e, const std::vector<RowShape>& shapes,
-                   float* const* s0, float* const* s1, int32_t c0, int32_t c1, SlotCol* out,
-                   unsigned* blocks, const float* max_norms = nullptr) {
+// and the grid the launch needs.  s0 / s1: NULL where the rule has no such slot.
+template <typename Col, typename HostCol>
+int fill_slot_cols(const HostCol* e, const std::vector<RowShape>& shapes, float* const* s0, float* const* s1,
+                   int32_t c0, int32_t c1, Col* out, unsigned* blocks, const float* max_norms = nullptr) {
   int64_t tasks = 0;
   int k = 0;
   for (int32_t c = c0; c < c1; ++c) {
-    const hbk_lookup_grad_column_t& h = e[(size_t)c];
-    if (h.n_ids <= 0 || h.rows <= 0) continue;
-    SlotCol& d = out[k];
-    d.w = h.table;
-    d.s0 = s0[c];
-    d.s1 = s1 != nullptr ? s1[c] : nullptr;   // (a one-slot call has no second array)
+    const HostCol& h = e[c];
+    const int64_t cap = capacity_of(h);
+    if (cap <= 0 || h.rows <= 0) continue;
+    Col& d = out[k];
+    set_table(d, h, c, max_norms);
+    d.s0 = s0 != nullptr ? s0[c] : nullptr;
+    d.s1 = s1 != nullptr ? s1[c] : nullptr;
     d.urows = h.unique_rows;
     d.grows = h.grad_rows;
     d.nu = h.n_unique;
     d.rows = h.rows;
-    d.cap = (int32_t)h.n_ids;
+    d.cap = (int32_t)cap;
     d.dim = h.dim;
-    d.pitch = h.table_pitch > 0 ? h.table_pitch : h.dim;
     const RowShape& shape = shapes[(size_t)c];   // (validated before the reduce)
     d.lpr_log2 = shape.lpr_log2;
     d.vec4 = shape.vec4;
-    d.max_norm = max_norms != nullptr ? max_norms[c] : 0.0f;
     const int64_t rpt = (int64_t)(kWave >> shape.lpr_log2) * kSlotItems;
-    tasks += (std::min<int64_t>(h.n_ids, h.rows) + rpt - 1) / rpt;
+    tasks += (std::min<int64_t>(cap, h.rows) + rpt - 1) / rpt;
     ++k;
   }
   const int64_t want = (tasks + kSlotWaves - 1) / kSlotWaves;
@@ -517,7 +639,7 @@ int slot_apply(const SlotNames& nm, Check check, bool run_empty, int32_t n_cols,
     SlotArgs<P> a;
     memset(&a, 0, sizeof(a));
     unsigned blocks = 0;
-    a.n_cols = fill_slot_cols(e, shapes, s0, s1, c0, std::min(n_cols, c0 + kSlotMaxCols), a.c, &blocks,
+    a.n_cols = fill_slot_cols(e.data(), shapes, s0, s1, c0, std::min(n_cols, c0 + kSlotMaxCols), a.c, &blocks,
                               max_norms);
     if (a.n_cols == 0) continue;
     launch(a, blocks, stream);
@@ -777,7 +899,7 @@ extern "C" int hbk_group_lookup_bwd_apply_clipped(int32_t n_cols, const hbk_look
     SlotArgs<LrParams> a;
     memset(&a, 0, sizeof(a));
     unsigned blocks = 0;
-    a.n_cols = fill_slot_cols(e, shapes, s0.data(), s1.data(), c0, std::min(nc, c0 + kSlotMaxCols), a.c,
+    a.n_cols = fill_slot_cols(e.data(), shapes, s0.data(), s1.data(), c0, std::min(nc, c0 + kSlotMaxCols), a.c,
                               &blocks, s.c.data());
     if (a.n_cols == 0) continue;
     a.p = LrParams{apply_lr};
@@ -928,52 +1050,122 @@ int check_lr_slices(const char* who, int32_t n_cols, const hbk_lookup_grad_colum
   return HBK_OK;
 }
 
-// the launches of one slice call: launch(args, blocks, stream) sets args.p and launches the rule's kernel
-template <typename P, typename Launch>
-int launch_slices(const std::vector<hbk_lookup_grad_column_t>& e, const std::vector<RowShape>& shapes,
-                  float* const* s0, float* const* s1, hipStream_t stream, Launch launch) {
-  const int32_t n_cols = (int32_t)e.size();
+// what both slice entries refuse first, in the same words
+int check_slices_call(const char* who, int32_t n_cols, const void* cols, int32_t apply) {
+  HBK_REQUIRE(n_cols >= 0, "%s: n_cols must be >= 0, got %d", who, n_cols);
+  HBK_REQUIRE(n_cols == 0 || cols != nullptr, "%s: cols is NULL", who);
+  HBK_REQUIRE(apply == HBK_APPLY_SGD || apply == HBK_APPLY_ADAGRAD || apply == HBK_APPLY_LAZY_ADAM ||
+                  apply == HBK_APPLY_FTRL || apply == HBK_APPLY_ROWWISE_ADAGRAD,
+              "%s: apply must be HBK_APPLY_SGD, _ADAGRAD, _LAZY_ADAM, _FTRL or _ROWWISE_ADAGRAD, got %d", who,
+              apply);
+  return HBK_OK;
+}
+
+// the sizes of slice column c, and its slices when it has any (S: hbk_slices_column_t or hbk_lowp_slices_column_t)
+template <typename S>
+int check_slice_sizes(const char* who, int32_t c, const S& s) {
+  HBK_REQUIRE(s.capacity >= 0 && s.capacity < (1ll << 30), "%s: column %d: capacity %lld must be in [0, 2^30)",
+              who, c, (long long)s.capacity);
+  HBK_REQUIRE(s.rows >= 0, "%s: column %d: rows must be >= 0, got %lld", who, c, (long long)s.rows);
+  HBK_REQUIRE(s.dim >= 1, "%s: column %d: dim must be >= 1", who, c);
+  return HBK_OK;
+}
+template <typename S>
+int check_slice_buffers(const char* who, int32_t c, const S& s) {
+  HBK_REQUIRE(s.unique_rows != nullptr && ((uintptr_t)s.unique_rows & 7) == 0,
+              "%s: column %d: unique_rows must be a device int64 [capacity]", who, c);
+  HBK_REQUIRE(s.grad_rows != nullptr && ((uintptr_t)s.grad_rows & 3) == 0,
+              "%s: column %d: grad_rows must be a device fp32 [capacity, dim]", who, c);
+  HBK_REQUIRE(s.n_unique != nullptr && ((uintptr_t)s.n_unique & 3) == 0,
+              "%s: column %d: n_unique must be a device int32 [1]", who, c);
+  return HBK_OK;
+}
+
+// a rule as the argument of dispatch_rule's callback
+template <typename R>
+struct RuleOf {
+  using Rule = R;
+};
+
+// The one rule dispatch of the slice entries: the apply code's hyperparameter check (the lr's own for SGD and
+// Adagrad), then run(RuleOf<Rule>(), the names the rule's refusals use, the rule's Params) -- where the caller
+// checks its columns and launches the kernel of its table policy -- and Adam's finish launch behind it.
+template <typename Run>
+int dispatch_rule(const char* who, int32_t apply, const void* params, float lr, hipStream_t stream, Run run) {
+  int rc = HBK_OK;
+  if (apply == HBK_APPLY_LAZY_ADAM) {
+    const hbk_adam_t* adam = static_cast<const hbk_adam_t*>(params);
+    if ((rc = adam_check(adam, lr, who)) != HBK_OK) return rc;
+    rc = run(RuleOf<AdamRule>(), SlotNames{who, "Adam", "m", "v"},
+             AdamParams{adam->beta_powers, lr, adam->beta1, adam->beta2, adam->epsilon});
+    if (rc != HBK_OK || !adam->finish) return rc;
+    hipLaunchKernelGGL(adam_finish_kernel, dim3(1), dim3(kWave), 0, stream, adam->beta_powers, adam->beta1,
+                       adam->beta2);
+    HBK_HIP_OK(hipGetLastError());
+    return HBK_OK;
+  }
+  if (apply == HBK_APPLY_FTRL) {
+    const hbk_ftrl_t* ftrl = static_cast<const hbk_ftrl_t*>(params);
+    if ((rc = ftrl_check(ftrl, lr, who)) != HBK_OK) return rc;
+    const SlotNames nm = {who, "FTRL", "accum", "linear"};
+    const FtrlParams p = {lr, ftrl->l1, 2.0f * ftrl->l2, 2.0f * ftrl->l2_shrinkage, -ftrl->lr_power};
+    // lr_power = -0.5 (TF's default) takes the sqrtf instantiation, any other the powf one
+    return ftrl->lr_power != -0.5f ? run(RuleOf<FtrlRule<true>>(), nm, p) : run(RuleOf<FtrlRule<false>>(), nm, p);
+  }
+  if (apply == HBK_APPLY_ROWWISE_ADAGRAD) {
+    const hbk_rowwise_adagrad_t* opt = static_cast<const hbk_rowwise_adagrad_t*>(params);
+    if ((rc = rowwise_adagrad_check(opt, lr, who)) != HBK_OK) return rc;
+    return run(RuleOf<RowwiseAdagradRule>(), SlotNames{who, "row-wise Adagrad", "accum", nullptr},
+               RowwiseParams{lr, opt->epsilon});
+  }
+  HBK_REQUIRE(lr != 0.0f && lr >= -3.402823466e38f && lr <= 3.402823466e38f,
+              "%s: lr must be finite and != 0, got %g", who, (double)lr);
+  const SlotNames nm = {who, apply == HBK_APPLY_ADAGRAD ? "Adagrad" : "SGD", "the accumulator", nullptr};
+  return apply == HBK_APPLY_ADAGRAD ? run(RuleOf<AdagradRule>(), nm, LrParams{lr})
+                                    : run(RuleOf<SgdRule>(), nm, LrParams{lr});
+}
+
+// the launches of one slice call over either kind of table: launch(args, blocks) sets what args holds besides
+// the columns and launches the rule's kernel
+template <typename Table, typename P, typename HostCol, typename Launch>
+int launch_slices(int32_t n_cols, const HostCol* cols, const std::vector<RowShape>& shapes, float* const* s0,
+                  float* const* s1, Launch launch) {
   for (int32_t c0 = 0; c0 < n_cols; c0 += kSlotMaxCols) {
-    SlotArgs<P> a;
+    typename Table::template Args<P> a;
     memset(&a, 0, sizeof(a));
     unsigned blocks = 0;
-    a.n_cols = fill_slot_cols(e, shapes, s0, s1, c0, std::min(n_cols, c0 + kSlotMaxCols), a.c, &blocks);
+    a.n_cols = fill_slot_cols(cols, shapes, s0, s1, c0, std::min(n_cols, c0 + kSlotMaxCols), a.c, &blocks);
     if (a.n_cols == 0) continue;
-    launch(a, blocks, stream);
+    launch(a, blocks);
     HBK_HIP_OK(hipGetLastError());
   }
   return HBK_OK;
 }
 
+// the fp32 slice kernel of a rule: SGD and Adagrad take the clip pass's kernels (every max_norm is 0)
+inline auto fp32_slices_kernel(RuleOf<SgdRule>) { return sparse_sgd_clip_kernel; }
+inline auto fp32_slices_kernel(RuleOf<AdagradRule>) { return sparse_adagrad_clip_kernel; }
+inline auto fp32_slices_kernel(RuleOf<AdamRule>) { return sparse_adam_apply_kernel; }
+template <bool kPow>
+inline auto fp32_slices_kernel(RuleOf<FtrlRule<kPow>>) { return sparse_ftrl_apply_kernel<kPow>; }
+inline auto fp32_slices_kernel(RuleOf<RowwiseAdagradRule>) { return sparse_rowwise_adagrad_apply_kernel; }
+
 int sparse_apply_slices(int32_t n_cols, const hbk_slices_column_t* cols, int32_t apply, float* const* slot0,
                         float* const* slot1, const void* params, float lr, hbk_stream_t stream_) {
   static const char* kWho = "sparse_apply_slices_n";
-  constexpr float kMax = 3.402823466e38f;
-  HBK_REQUIRE(n_cols >= 0, "%s: n_cols must be >= 0, got %d", kWho, n_cols);
-  HBK_REQUIRE(n_cols == 0 || cols != nullptr, "%s: cols is NULL", kWho);
-  HBK_REQUIRE(apply == HBK_APPLY_SGD || apply == HBK_APPLY_ADAGRAD || apply == HBK_APPLY_LAZY_ADAM ||
-                  apply == HBK_APPLY_FTRL || apply == HBK_APPLY_ROWWISE_ADAGRAD,
-              "%s: apply must be HBK_APPLY_SGD, _ADAGRAD, _LAZY_ADAM, _FTRL or _ROWWISE_ADAGRAD, got %d", kWho,
-              apply);
+  int rc = check_slices_call(kWho, n_cols, cols, apply);
+  if (rc != HBK_OK) return rc;
   // the slices as the descriptors the apply reads
   std::vector<hbk_lookup_grad_column_t> e((size_t)n_cols);
   for (int32_t c = 0; c < n_cols; ++c) {
     const hbk_slices_column_t& s = cols[c];
-    HBK_REQUIRE(s.capacity >= 0 && s.capacity < (1ll << 30), "%s: column %d: capacity %lld must be in [0, 2^30)",
-                kWho, c, (long long)s.capacity);
-    HBK_REQUIRE(s.rows >= 0, "%s: column %d: rows must be >= 0, got %lld", kWho, c, (long long)s.rows);
-    HBK_REQUIRE(s.dim >= 1, "%s: column %d: dim must be >= 1", kWho, c);
+    if ((rc = check_slice_sizes(kWho, c, s)) != HBK_OK) return rc;
     HBK_REQUIRE(s.table_pitch == 0 || s.table_pitch >= s.dim,
                 "%s: column %d: table_pitch %d is smaller than dim %d", kWho, c, s.table_pitch, s.dim);
     if (s.capacity > 0) {
       HBK_REQUIRE(s.table != nullptr && ((uintptr_t)s.table & 3) == 0,
                   "%s: column %d: table must be a device fp32 buffer", kWho, c);
-      HBK_REQUIRE(s.unique_rows != nullptr && ((uintptr_t)s.unique_rows & 7) == 0,
-                  "%s: column %d: unique_rows must be a device int64 [capacity]", kWho, c);
-      HBK_REQUIRE(s.grad_rows != nullptr && ((uintptr_t)s.grad_rows & 3) == 0,
-                  "%s: column %d: grad_rows must be a device fp32 [capacity, dim]", kWho, c);
-      HBK_REQUIRE(s.n_unique != nullptr && ((uintptr_t)s.n_unique & 3) == 0,
-                  "%s: column %d: n_unique must be a device int32 [1]", kWho, c);
+      if ((rc = check_slice_buffers(kWho, c, s)) != HBK_OK) return rc;
     }
     hbk_lookup_grad_column_t& h = e[(size_t)c];
     memset(&h, 0, sizeof(h));
@@ -987,70 +1179,118 @@ int sparse_apply_slices(int32_t n_cols, const hbk_slices_column_t* cols, int32_t
     h.n_unique = const_cast<int32_t*>(s.n_unique);
   }
   hipStream_t stream = as_stream(stream_);
-  std::vector<RowShape> shapes;
+  return dispatch_rule(kWho, apply, params, lr, stream, [&](auto rule, const SlotNames& nm, const auto& p) {
+    using Rule = typename decltype(rule)::Rule;
+    using P = typename Rule::Params;
+    // the column checks of the rule's slot entry (SGD and Adagrad: their own)
+    float* const* const s0 = Rule::kSlots >= 1 || Rule::kRowwise ? slot0 : nullptr;
+    float* const* const s1 = Rule::kSlots >= 2 ? slot1 : nullptr;
+    std::vector<RowShape> shapes;
+    int rc = HBK_OK;
+    if constexpr (Rule::kRowwise) {
+      rc = check_row_slot_columns(nm, n_cols, e.data(), s0, &shapes);
+    } else if constexpr (Rule::kSlots == 2) {
+      rc = check_slot_columns(nm, n_cols, e.data(), s0, s1, &shapes);
+    } else {
+      HBK_REQUIRE(Rule::kSlots == 0 || n_cols == 0 || s0 != nullptr, "%s: the accumulator array (slot0) is NULL",
+                  kWho);
+      rc = check_lr_slices(kWho, n_cols, e.data(), s0, &shapes);
+    }
+    if (rc != HBK_OK) return rc;
+    return launch_slices<Fp32Rows, P>(n_cols, e.data(), shapes, s0, s1, [&](SlotArgs<P>& a, unsigned blocks) {
+      a.p = p;
+      hipLaunchKernelGGL(fp32_slices_kernel(rule), dim3(blocks), dim3(kSlotBlock), 0, stream, a);
+    });
+  });
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// hbk_lowp_apply_slices_n (include/hbk.h): the same step on tables of bf16 / fp16 rows -- the same dispatch, the
+// same launches, lowp_apply_kernel<Rule> in the place of the fp32 kernels.
+
+// every host check of a 16-bit slice call's slots and columns (n_slots table-shaped slots, or the row-wise
+// accumulator in slot0; n0 / n1: their names); the apply's row shapes
+int check_lowp_columns(const char* who, int32_t n_cols, const hbk_lowp_slices_column_t* cols, int n_slots,
+                       bool rowwise, const char* n0, const char* n1, float* const* slot0, float* const* slot1,
+                       bool stochastic, std::vector<RowShape>* shapes) {
+  HBK_REQUIRE(n_cols == 0 || (n_slots < 1 && !rowwise) || slot0 != nullptr, "%s: the %s array (slot0) is NULL", who,
+              n0);
+  HBK_REQUIRE(n_cols == 0 || n_slots < 2 || slot1 != nullptr, "%s: the %s array (slot1) is NULL", who, n1);
+  shapes->assign((size_t)n_cols, RowShape{});
+  std::vector<uintptr_t> seen;
+  seen.reserve((size_t)n_cols * 3);
   int rc = HBK_OK;
-  if (apply == HBK_APPLY_SGD || apply == HBK_APPLY_ADAGRAD) {
-    const bool adagrad = apply == HBK_APPLY_ADAGRAD;
-    HBK_REQUIRE(lr != 0.0f && lr >= -kMax && lr <= kMax, "%s: lr must be finite and != 0, got %g", kWho,
-                (double)lr);
-    HBK_REQUIRE(!adagrad || n_cols == 0 || slot0 != nullptr, "%s: the accumulator array (slot0) is NULL", kWho);
-    if ((rc = check_lr_slices(kWho, n_cols, e.data(), adagrad ? slot0 : nullptr, &shapes)) != HBK_OK) return rc;
-    std::vector<float*> none((size_t)n_cols, nullptr);
-    return launch_slices<LrParams>(e, shapes, adagrad ? slot0 : none.data(), none.data(), stream,
-                                   [&](SlotArgs<LrParams>& a, unsigned blocks, hipStream_t s) {
-                                     a.p = LrParams{lr};
-                                     if (adagrad) {
-                                       hipLaunchKernelGGL(sparse_adagrad_clip_kernel, dim3(blocks),
-                                                          dim3(kSlotBlock), 0, s, a);
-                                     } else {
-                                       hipLaunchKernelGGL(sparse_sgd_clip_kernel, dim3(blocks), dim3(kSlotBlock),
-                                                          0, s, a);
-                                     }
-                                   });
+  for (int32_t c = 0; c < n_cols; ++c) {
+    const hbk_lowp_slices_column_t& s = cols[c];
+    HBK_REQUIRE(s.table_dtype == HBK_LOWP_BF16 || s.table_dtype == HBK_LOWP_FP16,
+                "%s: column %d: table_dtype must be HBK_LOWP_BF16 or HBK_LOWP_FP16, got %d", who, c, s.table_dtype);
+    HBK_REQUIRE(!stochastic || s.table_dtype == HBK_LOWP_BF16,
+                "%s: column %d: stochastic rounding is defined for bf16 tables only", who, c);
+    if ((rc = check_slice_sizes(who, c, s)) != HBK_OK) return rc;
+    HBK_REQUIRE(((uintptr_t)s.table & 1) == 0, "%s: column %d: table must be 2-byte aligned", who, c);
+    float* const a0 = (n_slots >= 1 || rowwise) ? slot0[c] : nullptr;
+    float* const a1 = n_slots >= 2 ? slot1[c] : nullptr;
+    HBK_REQUIRE(!(n_slots >= 1 || rowwise) || (a0 != nullptr && ((uintptr_t)a0 & 3) == 0),
+                "%s: column %d: %s must be a device fp32 buffer", who, c, n0);
+    HBK_REQUIRE(n_slots < 2 || (a1 != nullptr && ((uintptr_t)a1 & 3) == 0),
+                "%s: column %d: %s must be a device fp32 buffer", who, c, n1);
+    if (s.capacity > 0) {
+      HBK_REQUIRE(s.table != nullptr, "%s: column %d: table is NULL", who, c);
+      if ((rc = check_slice_buffers(who, c, s)) != HBK_OK) return rc;
+      // the row shape of the fp32 entry: the table's bytes count twice (an 8-byte chunk where fp32 has 16), the
+      // row-wise word does not enter
+      const uintptr_t bits = ((uintptr_t)s.table * 2) | (uintptr_t)s.grad_rows |
+                             (n_slots >= 1 ? (uintptr_t)a0 : 0) | (uintptr_t)a1;
+      HBK_REQUIRE(make_rowshape(s.dim, bits, &(*shapes)[(size_t)c]),
+                  "%s: column %d: dim %d: at most 256 when dim %% 4 == 0, the table is 8-byte and the slots and "
+                  "grad_rows are 16-byte aligned, 64 otherwise", who, c, s.dim);
+    }
+    if (s.table != nullptr) seen.push_back((uintptr_t)s.table);
+    if (a0 != nullptr) seen.push_back((uintptr_t)a0);
+    if (a1 != nullptr) seen.push_back((uintptr_t)a1);
   }
-  if (apply == HBK_APPLY_LAZY_ADAM) {
-    static const SlotNames kNames = {kWho, "Adam", "m", "v"};
-    const hbk_adam_t* adam = static_cast<const hbk_adam_t*>(params);
-    if ((rc = adam_check(adam, lr, kWho)) != HBK_OK) return rc;
-    if ((rc = check_slot_columns(kNames, n_cols, e.data(), slot0, slot1, &shapes)) != HBK_OK) return rc;
-    rc = launch_slices<AdamParams>(e, shapes, slot0, slot1, stream,
-                                   [&](SlotArgs<AdamParams>& a, unsigned blocks, hipStream_t s) {
-                                     a.p = AdamParams{adam->beta_powers, lr, adam->beta1, adam->beta2,
-                                                      adam->epsilon};
-                                     hipLaunchKernelGGL(sparse_adam_apply_kernel, dim3(blocks), dim3(kSlotBlock),
-                                                        0, s, a);
-                                   });
-    if (rc != HBK_OK || !adam->finish) return rc;
-    hipLaunchKernelGGL(adam_finish_kernel, dim3(1), dim3(kWave), 0, stream, adam->beta_powers, adam->beta1,
-                       adam->beta2);
+  std::sort(seen.begin(), seen.end());
+  HBK_REQUIRE(std::adjacent_find(seen.begin(), seen.end()) == seen.end(),
+              "%s: two columns name the same table or slot (a row stepped twice in one call would race)", who);
+  return HBK_OK;
+}
+
+int lowp_apply_slices(int32_t n_cols, const hbk_lowp_slices_column_t* cols, int32_t apply, float* const* slot0,
+                      float* const* slot1, const void* params, float lr, const hbk_lowp_rounding_t* rounding,
+                      hbk_stream_t stream_) {
+  static const char* kWho = "lowp_apply_slices_n";
+  int rc = check_slices_call(kWho, n_cols, cols, apply);
+  if (rc != HBK_OK) return rc;
+  const int32_t mode = rounding != nullptr ? rounding->mode : HBK_LOWP_ROUND_NEAREST;
+  HBK_REQUIRE(mode == HBK_LOWP_ROUND_NEAREST || mode == HBK_LOWP_ROUND_STOCHASTIC,
+              "%s: rounding mode must be HBK_LOWP_ROUND_NEAREST or HBK_LOWP_ROUND_STOCHASTIC, got %d", kWho, mode);
+  const bool stochastic = mode == HBK_LOWP_ROUND_STOCHASTIC;
+  HBK_REQUIRE(!stochastic || (rounding->step != nullptr && ((uintptr_t)rounding->step & 3) == 0),
+              "%s: stochastic rounding needs a device uint32 [1] step counter", kWho);
+  const LowpRound round = {stochastic ? rounding->step : nullptr, stochastic ? rounding->seed : 0u};
+  hipStream_t stream = as_stream(stream_);
+  rc = dispatch_rule(kWho, apply, params, lr, stream, [&](auto rule, const SlotNames& nm, const auto& p) {
+    using Rule = typename decltype(rule)::Rule;
+    using P = typename Rule::Params;
+    float* const* const s0 = Rule::kSlots >= 1 || Rule::kRowwise ? slot0 : nullptr;
+    float* const* const s1 = Rule::kSlots >= 2 ? slot1 : nullptr;
+    std::vector<RowShape> shapes;
+    const int rc = check_lowp_columns(kWho, n_cols, cols, Rule::kSlots, Rule::kRowwise,
+                                      Rule::kSlots == 2 ? nm.s0 : "the accumulator", nm.s1, s0, s1, stochastic,
+                                      &shapes);
+    if (rc != HBK_OK) return rc;
+    return launch_slices<LowpRows, P>(n_cols, cols, shapes, s0, s1, [&](LowpArgs<P>& a, unsigned blocks) {
+      a.p = p;
+      a.round = round;
+      hipLaunchKernelGGL(lowp_apply_kernel<Rule>, dim3(blocks), dim3(kSlotBlock), 0, stream, a);
+    });
+  });
+  if (rc != HBK_OK) return rc;
+  if (stochastic && rounding->advance != 0) {
+    hipLaunchKernelGGL(lowp_advance_kernel, dim3(1), dim3(kWave), 0, stream, rounding->step);
     HBK_HIP_OK(hipGetLastError());
-    return HBK_OK;
   }
-  if (apply == HBK_APPLY_FTRL) {
-    static const SlotNames kNames = {kWho, "FTRL", "accum", "linear"};
-    const hbk_ftrl_t* ftrl = static_cast<const hbk_ftrl_t*>(params);
-    if ((rc = ftrl_check(ftrl, lr, kWho)) != HBK_OK) return rc;
-    if ((rc = check_slot_columns(kNames, n_cols, e.data(), slot0, slot1, &shapes)) != HBK_OK) return rc;
-    return launch_slices<FtrlParams>(
-        e, shapes, slot0, slot1, stream, [&](SlotArgs<FtrlParams>& a, unsigned blocks, hipStream_t s) {
-          a.p = FtrlParams{lr, ftrl->l1, 2.0f * ftrl->l2, 2.0f * ftrl->l2_shrinkage, -ftrl->lr_power};
-          if (ftrl->lr_power != -0.5f) {
-            hipLaunchKernelGGL(sparse_ftrl_apply_kernel<true>, dim3(blocks), dim3(kSlotBlock), 0, s, a);
-          } else {
-            hipLaunchKernelGGL(sparse_ftrl_apply_kernel<false>, dim3(blocks), dim3(kSlotBlock), 0, s, a);
-          }
-        });
-  }
-  static const SlotNames kNames = {kWho, "row-wise Adagrad", "accum", nullptr};
-  const hbk_rowwise_adagrad_t* opt = static_cast<const hbk_rowwise_adagrad_t*>(params);
-  if ((rc = rowwise_adagrad_check(opt, lr, kWho)) != HBK_OK) return rc;
-  if ((rc = check_row_slot_columns(kNames, n_cols, e.data(), slot0, &shapes)) != HBK_OK) return rc;
-  return launch_slices<RowwiseParams>(e, shapes, slot0, nullptr, stream,
-                                      [&](SlotArgs<RowwiseParams>& a, unsigned blocks, hipStream_t s) {
-                                        a.p = RowwiseParams{lr, opt->epsilon};
-                                        hipLaunchKernelGGL(sparse_rowwise_adagrad_apply_kernel, dim3(blocks),
-                                                           dim3(kSlotBlock), 0, s, a);
-                                      });
+  return HBK_OK;
 }
 
 }  // namespace
@@ -1060,4 +1300,10 @@ extern "C" int hbk_sparse_apply_slices_n(int32_t n_cols, const hbk_slices_column
                                          float* const* slot0, float* const* slot1, const void* params,
                                          float lr, hbk_stream_t stream) {
   return hbk::sparse_apply_slices(n_cols, cols, apply, slot0, slot1, params, lr, stream);
+}
+
+extern "C" int hbk_lowp_apply_slices_n(int32_t n_cols, const hbk_lowp_slices_column_t* cols, int32_t apply,
+                                       float* const* slot0, float* const* slot1, const void* params, float lr,
+                                       const hbk_lowp_rounding_t* rounding, hbk_stream_t stream) {
+  return hbk::lowp_apply_slices(n_cols, cols, apply, slot0, slot1, params, lr, rounding, stream);
 }

@@ -1,8 +1,8 @@
 // The arithmetic of the sparse optimizer steps: one rule functor per optimizer and the small helpers they
-// use.  Included by sparse_apply.hip (fp32 tables: the apply launches of the slot entries, the clip pass and
-// hbk_sparse_apply_slices_n) and by lowp_tables.hip (bf16 / fp16 tables: hbk_lowp_apply_slices_n), so that
-// both step a row with the SAME formulas, rounding and operation order; only the code that touches memory
-// (slot_task there, lowp_task here) differs between them.
+// use.  Included by sparse_apply.hip, whose one row walk (slot_task) steps fp32 tables (the apply launches of
+// the slot entries, the clip pass, hbk_sparse_apply_slices_n) and bf16 / fp16 tables (hbk_lowp_apply_slices_n)
+// with these formulas, in this rounding and operation order; only how a table row is read and written (the
+// walk's table policy) differs between the two.
 #ifndef HBK_CSRC_SPARSE_RULES_H_
 #define HBK_CSRC_SPARSE_RULES_H_
 

@@ -24,7 +24,7 @@ from hybridbackend_amd import _lib
 from hybridbackend_amd.embedding import optimizer as _opt
 from hybridbackend_amd.embedding.lookup import GroupLookup, GroupLookupGrad, _combiner_code
 from hybridbackend_amd.embedding.sharded import ShardedGroupLookup
-from hybridbackend_amd.embedding.sparse_apply import _APPLY
+from hybridbackend_amd.embedding.sparse_apply import SparseApply
 
 _DTYPES = {torch.bfloat16: _lib.LOWP_BF16, torch.float16: _lib.LOWP_FP16}
 _ROUNDING = {'nearest': _lib.LOWP_ROUND_NEAREST, 'stochastic': _lib.LOWP_ROUND_STOCHASTIC}
@@ -116,7 +116,7 @@ class LowpGroupLookup(GroupLookup):
     _lib.check(self._lib.hbk_lowp_lookup_fwd(len(self.tables), self._cols, s))
 
 
-class LowpSparseApply:
+class LowpSparseApply(SparseApply):
   """The sparse optimizer step of N 16-bit tables from caller-held IndexedSlices, one launch per 64 tables.
 
   Args:
@@ -132,126 +132,52 @@ class LowpSparseApply:
   :class:`SparseApply`; with ``'nearest'`` table and slots equal ``SparseApply`` on ``table.float()``, cast, bit for
   bit.  The object owns the device step counter (``step_counter``, one int32 word read as uint32): a call with
   ``finish=True`` advances it once, behind the apply in stream order, so replays of a captured graph draw fresh
-  noise; ``'nearest'`` never touches it.  No workspace and no host read: a call can be captured in a graph, and
-  ``launch()`` repeats it."""
+  noise; ``'nearest'`` never touches it.  ``__call__``, ``bind`` and ``launch`` are :class:`SparseApply`'s: the
+  slices are those it takes, ``finish=True`` also advances the step counter, and ``launch()`` steps again on the
+  bound slices (after a bare ``bind`` it needs ``lr``, ``optimizer`` and ``finish``)."""
 
+  _NAME = 'LowpSparseApply'
   _NEEDS = 'LowpSparseApply(tables, {slots})'
+  _COLUMN = _lib.LowpSlicesColumn
 
   def __init__(self, tables, accums=None, moments=None, adam=None, ftrl_slots=None, ftrl=None, row_accums=None,
                rowwise_adagrad=None, rounding='nearest', seed=0):
-    self.tables = _require_lowp_tables(tables, 'LowpSparseApply')
-    mode, seed = check_rounding(rounding, seed, [t.dtype for t in self.tables], 'LowpSparseApply')
-    self.rounding, self.seed = rounding, seed
-    self._lib = _lib.lib()
-    n = len(self.tables)
-    _opt.bind_all(self, dict(moments=moments, adam=adam, ftrl_slots=ftrl_slots, ftrl=ftrl, row_accums=row_accums,
-                             rowwise_adagrad=rowwise_adagrad), self.tables, 'LowpSparseApply')
-    self._slot_ptrs = {opt.name: opt.ptr_arrays(slots) for opt, slots in _opt.bound(self)}
-    self.accums = list(accums) if accums is not None else None
-    self._accum_ptrs = None
-    if self.accums is not None:
-      if len(self.accums) != n:
-        raise _bad(f'LowpSparseApply: {len(self.accums)} accumulators for {n} tables')
-      for c, (a, t) in enumerate(zip(self.accums, self.tables)):
-        _lib.require_device_tensor(a, 'accumulator')
-        if a.dtype != torch.float32 or a.shape != t.shape:
-          raise _bad(f'accumulator {c} must be fp32 {tuple(t.shape)}')
-      self._accum_ptrs = _lib.ptr_array([a.data_ptr() for a in self.accums])
-    self._cols = (_lib.LowpSlicesColumn * n)()
-    for c, t in enumerate(self.tables):
-      col = self._cols[c]
-      col.table = t.data_ptr()
-      col.table_dtype = _DTYPES[t.dtype]
-      col.rows = t.shape[0]
-      col.dim = t.shape[1]
-    dev = self.tables[0].device if n else torch.device('cuda', torch.cuda.current_device())
+    self.rounding, self.seed = rounding, seed   # (checked with the tables, before anything is bound)
+    super().__init__(tables, accums=accums, moments=moments, adam=adam, ftrl_slots=ftrl_slots, ftrl=ftrl,
+                     row_accums=row_accums, rowwise_adagrad=rowwise_adagrad)
+    dev = self.tables[0].device if self.tables else torch.device('cuda', torch.cuda.current_device())
     self.step_counter = torch.zeros(1, dtype=torch.int32, device=dev)
     # the hbk_lowp_rounding_t of a call with / without the advance (kept alive by this object)
-    self._rounding_c = {f: _lib.LowpRounding(mode, seed, self.step_counter.data_ptr(), 1 if f else 0, 0)
+    self._rounding_c = {f: _lib.LowpRounding(self._mode, self.seed, self.step_counter.data_ptr(), 1 if f else 0, 0)
                         for f in (False, True)}
     self._slices_key = None
-    self._bound = None
 
-  def __len__(self):
-    return len(self.tables)
+  def _require_tables(self, tables):
+    tables = _require_lowp_tables(tables, 'LowpSparseApply')
+    self._mode, self.seed = check_rounding(self.rounding, self.seed, [t.dtype for t in tables], 'LowpSparseApply')
+    return tables
 
-  def _check(self, lr, optimizer):
-    two_slot = _opt.two_slot_class(optimizer, self, self._NEEDS)
-    if lr == 0.0:
-      raise _bad('LowpSparseApply: lr must be != 0')
-    if optimizer == 'adagrad' and self.accums is None:
-      raise _bad("optimizer='adagrad' needs LowpSparseApply(tables, accums=...)")
-    return two_slot
+  def _fill_table(self, col, table):
+    col.table_dtype = _DTYPES[table.dtype]
+
+  def _foreign_call(self, apply, s0, s1, params, lr, finish, stream):
+    return self._lib.hbk_lowp_apply_slices_n(len(self.tables), self._cols, apply, s0, s1, params, lr,
+                                             C.byref(self._rounding_c[finish]), stream)
+
+  def _launchable(self, explicit):
+    return self._slices_key is not None and (self._bound is not None or explicit)
 
   def bind(self, slices):
-    """Point the descriptors at ``slices`` (checked) without stepping."""
-    n = len(self.tables)
+    """Point the descriptors at ``slices`` (checked) without stepping; the same tensors at the same addresses as
+    the last time are not looked at again."""
     slices = list(slices)
-    if len(slices) != n:
-      raise _bad(f'LowpSparseApply: {len(slices)} slices for {n} tables')
-    key = tuple(id(x) for s in slices for x in s)
-    if key == self._slices_key and all(
+    key = tuple(id(x) for s in slices for x in s) if len(slices) == len(self.tables) else None
+    if key is not None and key == self._slices_key and all(
         x.data_ptr() == q for s, qs in zip(slices, self._slices_ptrs) for x, q in zip(s, qs)):
       return
-    keep = []
-    for c, (s, t) in enumerate(zip(slices, self.tables)):
-      if len(s) != 3:
-        raise _bad(f'slices[{c}] must be (unique_rows, grad_rows, n_unique)')
-      urows, grows, nu = s
-      for x, what in ((urows, 'unique_rows'), (grows, 'grad_rows'), (nu, 'n_unique')):
-        if not isinstance(x, torch.Tensor):
-          raise _bad(f'slices[{c}].{what} must be a device tensor')
-        _lib.require_device_tensor(x, f'slices[{c}].{what}')
-      if urows.dtype != torch.int64 or urows.dim() != 1:
-        raise _bad(f'slices[{c}].unique_rows must be an int64 vector')
-      cap, dim = int(urows.shape[0]), int(t.shape[1])
-      if grows.dtype != torch.float32 or tuple(grows.shape) != (cap, dim):
-        raise _bad(f'slices[{c}].grad_rows must be fp32 [{cap}, {dim}]')
-      if nu.dtype != torch.int32 or nu.numel() != 1:
-        raise _bad(f'slices[{c}].n_unique must be an int32 device tensor of one element')
-      col = self._cols[c]
-      col.unique_rows = urows.data_ptr()
-      col.grad_rows = grows.data_ptr()
-      col.n_unique = nu.data_ptr()
-      col.capacity = cap
-      keep.append((urows, grows, nu))
-    self._keep = keep
+    super().bind(slices)
     self._slices_key = key
-    self._slices_ptrs = [tuple(x.data_ptr() for x in s) for s in keep]
-
-  def __call__(self, slices, lr, optimizer='sgd', finish=True):
-    """slices[c] = ``(unique_rows int64 [capacity], grad_rows fp32 [capacity, dim], n_unique int32 [1])`` on the
-    device, as :class:`SparseApply` takes them: the first ``n_unique`` entries are read (on the device, clamped to
-    the capacity), an entry outside ``[0, rows)`` -- ``-1`` -- touches nothing, rows must be DISTINCT.
-    ``finish=True`` advances Adam's beta powers and the rounding's step counter behind the step."""
-    two_slot = self._check(lr, optimizer)
-    self.bind(slices)
-    self._bound = (float(lr), optimizer, bool(finish))
-    self._step(two_slot, float(lr), optimizer, finish)
-
-  def _step(self, two_slot, lr, optimizer, finish):
-    n = len(self.tables)
-    dev = self.tables[0].device if n else None
-    s0 = s1 = params = None
-    if two_slot is not None:
-      ptrs = self._slot_ptrs[two_slot.name]
-      s0 = ptrs[0]
-      s1 = ptrs[1] if len(ptrs) > 1 else None
-      params = C.byref(getattr(self, two_slot.name).params(finish))
-    elif optimizer == 'adagrad':
-      s0 = self._accum_ptrs
-    _lib.check(self._lib.hbk_lowp_apply_slices_n(n, self._cols, _APPLY[optimizer], s0, s1, params, C.c_float(lr),
-                                                 C.byref(self._rounding_c[bool(finish)]), _lib.current_stream(dev)))
-
-  def launch(self, lr=None, optimizer=None, finish=None):
-    """The step again on the bound slices (refilled in place): one foreign call.  ``lr``, ``optimizer`` and
-    ``finish`` default to the last call's."""
-    if self._slices_key is None or (self._bound is None and (lr is None or optimizer is None or finish is None)):
-      raise _lib.HbkError(_lib.INTERNAL, 'launch() needs a call that bound the slices first')
-    lr = self._bound[0] if lr is None else float(lr)
-    optimizer = self._bound[1] if optimizer is None else optimizer
-    finish = self._bound[2] if finish is None else bool(finish)
-    self._step(self._check(lr, optimizer), lr, optimizer, finish)
+    self._slices_ptrs = [tuple(x.data_ptr() for x in s) for s in self._keep]
 
 
 class LowpLookupGrad:

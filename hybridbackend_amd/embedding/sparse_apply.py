@@ -28,37 +28,56 @@ class SparseApply:
 
   No workspace and no host read: a call can be captured in a graph, and ``launch()`` repeats it."""
 
+  # what a subclass over another kind of table (embedding/lowp.py) replaces: the name its refusals use, the
+  # descriptor, and _require_tables / _fill_table / _foreign_call / _launchable below
+  _NAME = 'SparseApply'
   _NEEDS = 'SparseApply(tables, {slots})'
+  _COLUMN = _lib.SlicesColumn
 
   def __init__(self, tables, accums=None, moments=None, adam=None, ftrl_slots=None, ftrl=None, row_accums=None,
                rowwise_adagrad=None):
+    self.tables = self._require_tables(tables)
     self._lib = _lib.lib()
-    self.tables = list(tables)
     n = len(self.tables)
-    for t in self.tables:
-      _lib.require_device_tensor(t, 'embedding weights')
-      if t.dtype != torch.float32 or t.dim() != 2:
-        raise _bad('embedding weights must be fp32 [rows, dim]')
     _opt.bind_all(self, dict(moments=moments, adam=adam, ftrl_slots=ftrl_slots, ftrl=ftrl, row_accums=row_accums,
-                             rowwise_adagrad=rowwise_adagrad), self.tables, 'SparseApply')
+                             rowwise_adagrad=rowwise_adagrad), self.tables, self._NAME)
     self._slot_ptrs = {opt.name: opt.ptr_arrays(slots) for opt, slots in _opt.bound(self)}
     self.accums = list(accums) if accums is not None else None
     self._accum_ptrs = None
     if self.accums is not None:
       if len(self.accums) != n:
-        raise _bad(f'SparseApply: {len(self.accums)} accumulators for {n} tables')
+        raise _bad(f'{self._NAME}: {len(self.accums)} accumulators for {n} tables')
       for c, (a, t) in enumerate(zip(self.accums, self.tables)):
         _lib.require_device_tensor(a, 'accumulator')
         if a.dtype != torch.float32 or a.shape != t.shape:
           raise _bad(f'accumulator {c} must be fp32 {tuple(t.shape)}')
       self._accum_ptrs = _lib.ptr_array([a.data_ptr() for a in self.accums])
-    self._cols = (_lib.SlicesColumn * n)()
+    self._cols = (self._COLUMN * n)()
     for c, t in enumerate(self.tables):
       col = self._cols[c]
       col.table = t.data_ptr()
       col.rows = t.shape[0]
       col.dim = t.shape[1]
+      self._fill_table(col, t)
     self._bound = None
+
+  def _require_tables(self, tables):
+    tables = list(tables)
+    for t in tables:
+      _lib.require_device_tensor(t, 'embedding weights')
+      if t.dtype != torch.float32 or t.dim() != 2:
+        raise _bad('embedding weights must be fp32 [rows, dim]')
+    return tables
+
+  def _fill_table(self, col, table):
+    """What the descriptor holds of its table besides the address and the shape."""
+
+  def _foreign_call(self, apply, s0, s1, params, lr, finish, stream):   # pylint: disable=unused-argument
+    return self._lib.hbk_sparse_apply_slices_n(len(self.tables), self._cols, apply, s0, s1, params, lr, stream)
+
+  def _launchable(self, explicit):   # pylint: disable=unused-argument
+    """Whether ``launch()`` has what it repeats (explicit: the caller gave lr, optimizer and finish)."""
+    return self._bound is not None
 
   def __len__(self):
     return len(self.tables)
@@ -66,9 +85,9 @@ class SparseApply:
   def _check(self, lr, optimizer):
     two_slot = _opt.two_slot_class(optimizer, self, self._NEEDS)
     if lr == 0.0:
-      raise _bad('SparseApply: lr must be != 0')
+      raise _bad(f'{self._NAME}: lr must be != 0')
     if optimizer == 'adagrad' and self.accums is None:
-      raise _bad("optimizer='adagrad' needs SparseApply(tables, accums=...)")
+      raise _bad(f"optimizer='adagrad' needs {self._NAME}(tables, accums=...)")
     return two_slot
 
   def __call__(self, slices, lr, optimizer='sgd', finish=True):
@@ -77,10 +96,16 @@ class SparseApply:
     ``[0, rows)`` -- ``-1`` -- touches nothing.  Rows must be DISTINCT (not checked: no step but SGD's is
     additive).  ``optimizer`` and ``finish`` as in :class:`GroupLookupGrad`; the gradient is not clipped."""
     two_slot = self._check(lr, optimizer)
+    self.bind(slices)
+    self._bound = (float(lr), optimizer, bool(finish))
+    self._step(two_slot, float(lr), optimizer, finish)
+
+  def bind(self, slices):
+    """Point the descriptors at ``slices`` (checked) without stepping."""
     n = len(self.tables)
     slices = list(slices)
     if len(slices) != n:
-      raise _bad(f'SparseApply: {len(slices)} slices for {n} tables')
+      raise _bad(f'{self._NAME}: {len(slices)} slices for {n} tables')
     keep = []
     for c, (s, t) in enumerate(zip(slices, self.tables)):
       if len(s) != 3:
@@ -104,8 +129,6 @@ class SparseApply:
       col.capacity = cap
       keep.append((urows, grows, nu))
     self._keep = keep
-    self._bound = (float(lr), optimizer, bool(finish))
-    self._step(two_slot, float(lr), optimizer, finish)
 
   def _step(self, two_slot, lr, optimizer, finish):
     n = len(self.tables)
@@ -118,13 +141,13 @@ class SparseApply:
       params = C.byref(getattr(self, two_slot.name).params(finish))
     elif optimizer == 'adagrad':
       s0 = self._accum_ptrs
-    _lib.check(self._lib.hbk_sparse_apply_slices_n(n, self._cols, _APPLY[optimizer], s0, s1, params,
-                                                   C.c_float(lr), _lib.current_stream(dev)))
+    _lib.check(self._foreign_call(_APPLY[optimizer], s0, s1, params, C.c_float(lr), bool(finish),
+                                  _lib.current_stream(dev)))
 
   def launch(self, lr=None, optimizer=None, finish=None):
     """The last call again on the same tensors (refilled in place): one foreign call.  ``lr``, ``optimizer``
     and ``finish`` default to that call's."""
-    if self._bound is None:
+    if not self._launchable(None not in (lr, optimizer, finish)):
       raise _lib.HbkError(_lib.INTERNAL, 'launch() needs a call that bound the slices first')
     lr = self._bound[0] if lr is None else float(lr)
     optimizer = self._bound[1] if optimizer is None else optimizer
