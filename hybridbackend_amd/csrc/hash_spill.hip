@@ -1,7 +1,9 @@
-// Spilling (hbk_hash_spill_n): export exactly the keys an eviction removes, then remove them.  include/hbk.h has
-// the semantics.  The selection was made by hbk_hash_evict_to_select_n and is READ FROM DEVICE MEMORY by every
-// launch: selection = {live_before, need, cut, n_selected}, and a slot is selected iff it holds a key, is not
-// protected by keep_freq, need > 0 and last_seen <= cut (signed).  No host read anywhere.
+// Spilling (hbk_hash_spill_n, hbk_hash_spill_lfu_n): export exactly the keys an eviction removes, then remove them.
+// include/hbk.h has the semantics.  The selection was made by the order's select entry (hash_evict_to.hip) and is
+// READ FROM DEVICE MEMORY by every launch: selection = that order's report (hash_order.h) -- {live_before, need, cut,
+// n_selected} for LRU, {live_before, need, cut_freq, cut_last_seen, n_selected, ...} for LFU -- and a slot is
+// selected iff it holds a key, is not protected by keep_freq, need > 0 and its key is at or below the cut: last_seen
+// <= cut (signed), or the pair (freq, last_seen) against (cut_freq, cut_last_seen).  No host read anywhere.
 //
 // Four launches per 32 tables on the call's stream:
 //   1-3. count, scan, write   hash_pack.h's stream compaction (the export's kernels, instantiated with this
@@ -13,6 +15,7 @@
 //                             (integer atomics: order-independent sums).  A table whose *count exceeds its
 //                             out_capacity is left untouched: nothing leaves that was not exported in full.
 // The kernel boundary between 3 and 4 orders the copies before the resets.
+#include "hash_order.h"
 #include "hash_pack.h"
 
 namespace hbk {
@@ -20,12 +23,14 @@ namespace {
 
 using namespace pack;
 
-// the selection as both halves read it (selection: {live_before, need, cut, n_selected})
+// the selection as both halves read it (selection: the order's report, hash_order.h)
+template <class Order>
 __device__ inline bool spilled(const int32_t* selection, int32_t keep_freq, long long key, int32_t seen,
                                int32_t freq) {
-  return holds_key(key, true) && (keep_freq == 0 || freq < keep_freq) && selection[1] > 0 && seen <= selection[2];
+  return holds_key(key, true) && (keep_freq == 0 || freq < keep_freq) && Order::selected(selection, freq, seen);
 }
 
+template <class Order>
 struct SpillCol {
   long long* keys;
   const int32_t* last_seen;
@@ -45,19 +50,20 @@ struct SpillCol {
 
   __device__ bool selected(int64_t slot) const {
     if (slot >= capacity) return false;
-    return spilled(selection, keep_freq, keys[slot], last_seen[slot], freq[slot]);
+    return spilled<Order>(selection, keep_freq, keys[slot], last_seen[slot], freq[slot]);
   }
   __device__ void scanned() const {
     if (n_evicted != nullptr) *n_evicted = 0;
   }
 };
 
+template <class Order>
 struct SpillArgs {
   int32_t n_cols;
   int32_t tile_start[kMaxColsPerLaunch + 1];
-  SpillCol col[kMaxColsPerLaunch];
+  SpillCol<Order> col[kMaxColsPerLaunch];
 };
-static_assert(sizeof(SpillArgs) <= 24576, "kernarg budget");
+static_assert(sizeof(SpillArgs<LruOrder>) <= 24576 && sizeof(SpillArgs<LfuOrder>) <= 24576, "kernarg budget");
 
 struct SweepCol {
   long long* keys;
@@ -81,6 +87,7 @@ struct SweepArgs {
 };
 static_assert(sizeof(SweepArgs) <= 24576, "kernarg budget");
 
+template <class Order>
 __global__ __launch_bounds__(kBlock) void hash_spill_sweep_kernel(const SweepArgs a) {
   const int b = (int)blockIdx.x;
   const int lane = lane_id();
@@ -96,7 +103,7 @@ __global__ __launch_bounds__(kBlock) void hash_spill_sweep_kernel(const SweepArg
   if (first >= capacity) return;   // (wave-uniform)
   const int32_t n = sweep_wave(c.keys, c.last_seen, c.freq, capacity, first, lane, c.n_fills, c.fill,
                                [&](long long key, int32_t seen, int32_t freq) {
-                                 return spilled(selection, keep_freq, key, seen, freq);
+                                 return spilled<Order>(selection, keep_freq, key, seen, freq);
                                });
   if (lane == 0 && n != 0) {
     if (c.stats != nullptr) atomicAdd(c.stats, n);
@@ -145,24 +152,26 @@ extern "C" int hbk_hash_spill_workspace_bytes(int32_t n_cols, const hbk_hash_spi
   return HBK_OK;
 }
 
-extern "C" int hbk_hash_spill_n(int32_t n_cols, const hbk_hash_spill_column_t* cols, void* workspace,
-                                hbk_stream_t stream) {
-  using namespace hbk;
-  const char* who = "hash_spill_n";
+namespace hbk {
+namespace {
+
+// both entries, after check_spill: the compaction and the sweep with the order's selection
+template <class Order>
+int spill(const char* who, int32_t n_cols, const hbk_hash_spill_column_t* cols, void* workspace, hbk_stream_t stream) {
   if (int rc = check_spill(who, n_cols, cols, true)) return rc;
   if (n_cols == 0) return HBK_OK;
   HBK_REQUIRE(workspace != nullptr, "%s: workspace is NULL (hbk_hash_spill_workspace_bytes says how large)", who);
   HBK_REQUIRE(((uintptr_t)workspace & 7) == 0, "%s: workspace must be 8-byte aligned", who);
   int64_t* ws = static_cast<int64_t*>(workspace);
   for (int32_t c0 = 0; c0 < n_cols; c0 += kMaxColsPerLaunch) {
-    SpillArgs args;
+    SpillArgs<Order> args;
     SweepArgs sweep;
     const int32_t k = n_cols - c0 < kMaxColsPerLaunch ? n_cols - c0 : kMaxColsPerLaunch;
     int64_t tiles = 0;
     args.tile_start[0] = sweep.tile_start[0] = 0;
     for (int32_t i = 0; i < k; ++i) {
       const hbk_hash_spill_column_t& h = cols[c0 + i];
-      SpillCol& d = args.col[i];
+      SpillCol<Order>& d = args.col[i];
       d.keys = reinterpret_cast<long long*>(h.keys_cache);
       d.last_seen = h.exp.last_seen;
       d.freq = h.exp.freq;
@@ -197,8 +206,22 @@ extern "C" int hbk_hash_spill_n(int32_t n_cols, const hbk_hash_spill_column_t* c
     }
     args.n_cols = sweep.n_cols = k;
     if (int rc = launch_pack(args, tiles, as_stream(stream))) return rc;
-    hipLaunchKernelGGL(hash_spill_sweep_kernel, dim3((unsigned)tiles), dim3(kBlock), 0, as_stream(stream), sweep);
+    hipLaunchKernelGGL(hash_spill_sweep_kernel<Order>, dim3((unsigned)tiles), dim3(kBlock), 0, as_stream(stream),
+                       sweep);
     HBK_HIP_OK(hipGetLastError());
   }
   return HBK_OK;
+}
+
+}  // namespace
+}  // namespace hbk
+
+extern "C" int hbk_hash_spill_n(int32_t n_cols, const hbk_hash_spill_column_t* cols, void* workspace,
+                                hbk_stream_t stream) {
+  return hbk::spill<hbk::LruOrder>("hash_spill_n", n_cols, cols, workspace, stream);
+}
+
+extern "C" int hbk_hash_spill_lfu_n(int32_t n_cols, const hbk_hash_spill_column_t* cols, void* workspace,
+                                    hbk_stream_t stream) {
+  return hbk::spill<hbk::LfuOrder>("hash_spill_lfu_n", n_cols, cols, workspace, stream);
 }
