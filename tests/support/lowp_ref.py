@@ -196,13 +196,15 @@ def forward_rows(bits, dtype, ids, splits=None, weights=None, combiner='sum', bu
 
 # ---- the apply ----------------------------------------------------------------------------------------------------
 def apply_step(bits, dtype, slots, rows, g, optimizer, lr, hyper=None, rounding='nearest', seed=0, step=0, col=0,
-               vec4=None):
+               vec4=None, noise_rows=None):
   """One optimizer step of hbk_lowp_apply_slices_n restated: a stepped row is round(rule(upcast(row), slots, g)).
 
   bits uint16 [R, dim]; slots: the fp32 slot arrays of the rule (sgd: none; adagrad: accum; adam: m, v; ftrl: accum,
   linear; rowwise_adagrad: accum [R, 1]); rows int64 [n] (entries outside [0, R) touch nothing), g fp32 [n, dim].
   hyper: adam {'powers': (b1^t, b2^t)[, 'beta1', 'beta2', 'epsilon']}, ftrl {'l1', 'l2', 'l2_shrinkage', 'lr_power'},
-  rowwise_adagrad {'epsilon'}.  vec4: the row-wise sum's lane layout (default: dim % 4 == 0).  The rules are the
+  rowwise_adagrad {'epsilon'}.  vec4: the row-wise sum's lane layout (default: dim % 4 == 0).  noise_rows int64 [n]: the
+  row numbers the stochastic noise is keyed by when `bits` is a compact copy of a few rows of a table too large for
+  the host and `rows` number that copy (default: `rows`).  The rules are the
   project's restatements (tests/support/reference.py, rowwise_adagrad_ref.py).  Returns (new bits, new slots); the
   arguments are left alone."""
   from tests.support import reference, rowwise_adagrad_ref
@@ -212,7 +214,8 @@ def apply_step(bits, dtype, slots, rows, g, optimizer, lr, hyper=None, rounding=
   rows = np.asarray(rows, np.int64)
   g = np.asarray(g, F32)
   keep = (rows >= 0) & (rows < bits.shape[0])
-  rows, g = rows[keep], g[keep]
+  noise_rows = rows if noise_rows is None else np.asarray(noise_rows, np.int64)
+  rows, g, noise_rows = rows[keep], g[keep], noise_rows[keep]
   assert np.unique(rows).size == rows.size, 'a row twice: the step is not additive'
   dim = bits.shape[1]
   w = upcast(bits, dtype).copy()
@@ -235,7 +238,7 @@ def apply_step(bits, dtype, slots, rows, g, optimizer, lr, hyper=None, rounding=
   u = bits32(w[rows])
   if rounding == 'stochastic':
     assert dtype == BF16
-    bits[rows] = bf16_stochastic(u, noise(seed, step, col, rows, dim))
+    bits[rows] = bf16_stochastic(u, noise(seed, step, col, noise_rows, dim))
   else:
     bits[rows] = round_nearest(u, dtype)
   return bits, slots

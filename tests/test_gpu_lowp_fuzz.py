@@ -17,8 +17,8 @@ FTRL is drawn with lr_power = -0.5 only: the powf form is bounded in ulps of fp3
 result that is a few fp32 ulps off cannot be held bit for bit behind a 16-bit rounding -- near a tie it rounds the
 other way.  Its arithmetic is the fp32 entry's functor, which the fp32 fuzz holds to that bound.
 
-Known and left out: noise_row's use of the upper 32 bits of the row number is not exercised on the device -- it would
-need a table of more than 2^32 rows; tests/test_lowp_ref.py covers the formula.
+noise_row's use of the upper 32 bits of the row number needs a table of more than 2^32 rows: that is
+tests/test_gpu_wide_offsets.py (test_lowp_step on geometry R, test_lowp_apply_stochastic_on_rows_past_2_32).
 
 The committed runs are deterministic; HBK_FUZZ_RANDOM=1 HBK_FUZZ_SCALE=10 hunts with fresh draws."""
 import os
