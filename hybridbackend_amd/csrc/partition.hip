@@ -905,7 +905,9 @@ int partition_impl(const char* what, int32_t n_cols, int32_t dtype, int32_t P,
     args.sizes_t = sizes_t;
     args.n_total_cols = n_cols;
     args.uniform_tiles = 0;
-    args.fixed_max = options().partition_fixed_max;
+    // (one ballot per shard keeps shard p's counter in lane p: never past the 64 lanes, whatever the
+    // option says -- beyond them the counts of shards >= 64 were dropped without a word)
+    args.fixed_max = options().partition_fixed_max < kWave ? options().partition_fixed_max : kWave;
     args.sub_tiles = sub;
     int32_t k = 0;
     int64_t tiles = 0;

@@ -93,7 +93,7 @@ int hbk_tables_free(void* slab);
  * bwd_trace (the launch groups of every backward call on stderr), bwd_lds_pad (a probe), sharded_p2p,
  * sharded_p2p_test_refuse (test hook: the rank whose hbk_sharded_p2p_bind behaves as if a peer's memory could not be mapped),
  * unique_buckets_log2,
- * unique_onepass, partition_sub_tiles, partition_fixed_max, partition_onepass, sharded_groups,
+ * unique_onepass, partition_sub_tiles (held to 8), partition_fixed_max (held to 64, the lanes of a wave), partition_onepass, sharded_groups,
  * sharded_id64, sharded_copy_self, sharded_trace, sharded_inline, sharded_wire_fused, sharded_pack_early (the sharded_* ones are taken by
  * hbk_sharded_create), sync_wait_ms, sync_onepass_off, sync_test_withhold.
  * *_onepass (default 1): small calls of partition / unique / the backward group their ids in ONE
