@@ -1,7 +1,10 @@
 // The hash tables' contract, once: what probe.hip, hash_insert.hip, hash_evict.hip, hash_rehash.hip and
 // hash_export.hip must agree on to read each other's tables -- the sentinels, the placement hash, which slots
 // hold a key, the host checks of a table's geometry -- and the pieces their sweeps share: the wave compaction,
-// the eviction sweep's body and fills, and the per-slot row moves.  Plain constants, structs and inline functions; internal to libhbk_core.so.
+// the eviction sweep's body and fills (hash_evict.hip, hash_evict_to.hip, hash_spill.hip; the fills also
+// hash_remove.hip's), and the per-slot row moves.  Last, the pure find as a pre-pass of hash_remove.hip,
+// hash_missing.hip and hash_missing_runs.hip: its tile size, its grid check and its columns.  (The miss lists'
+// scratch set is hash_miss_set.h's.)  Plain constants, structs and inline functions; internal to libhbk_core.so.
 #ifndef HBK_CSRC_HASH_COMMON_H_
 #define HBK_CSRC_HASH_COMMON_H_
 
@@ -75,6 +78,26 @@ struct Fill {
   int32_t pad_;
 };
 
+// The companion rows of the n slots a wave has just freed (a sweep's evicted slots, hash_remove.hip's winners),
+// filled by all lanes: groups of pow2(dim) lanes, 64 / pow2(dim) rows per pass.  row_of(r), r < 64, is the slot of
+// the r-th of them; it may shuffle, so every lane calls it, also for an r it will not fill.
+template <class RowOf>
+__device__ inline void fill_rows(int n_fills, const Fill* fills, int n, int lane, RowOf row_of) {
+  for (int f = 0; f < n_fills; ++f) {
+    const Fill& fl = fills[f];
+    const int rows_log2 = 6 - fl.lanes_log2;                 // rows per pass
+    const int j0 = lane & ((1 << fl.lanes_log2) - 1);
+    for (int r0 = 0; r0 < n; r0 += 1 << rows_log2) {
+      const int r = r0 + (lane >> fl.lanes_log2);
+      const int64_t slot = row_of(r & (kWave - 1));
+      if (r < n) {
+        float* row = fl.base + slot * fl.pitch;
+        for (int j = j0; j < fl.dim; j += 1 << fl.lanes_log2) row[j] = fl.value;
+      }
+    }
+  }
+}
+
 // The sweeps' body (hash_evict.hip, hash_evict_to.hip): a wave decides the 64 consecutive slots from `first`
 // (wave-uniform, < capacity) with coalesced loads, 16 bytes per slot -- doomed(key, last_seen, freq) is the
 // sweep's predicate -- ballots the evicted ones, writes key = TOMBSTONE, last_seen = freq = 0, gathers their lane
@@ -101,19 +124,7 @@ __device__ inline int sweep_wave(long long* keys, int32_t* last_seen, int32_t* f
   }
   if (n_fills == 0) return n;
   const int evicted_lane = compact_lanes(mask, evict, lane);   // lane r < n: the lane of the r-th evicted slot
-  for (int f = 0; f < n_fills; ++f) {
-    const Fill& fl = fills[f];
-    const int rows_log2 = 6 - fl.lanes_log2;                 // rows per pass
-    const int j0 = lane & ((1 << fl.lanes_log2) - 1);
-    for (int r0 = 0; r0 < n; r0 += 1 << rows_log2) {
-      const int r = r0 + (lane >> fl.lanes_log2);
-      const int src = __shfl(evicted_lane, r & (kWave - 1), kWave);   // (every lane takes the shuffle)
-      if (r < n) {
-        float* row = fl.base + (first + src) * fl.pitch;
-        for (int j = j0; j < fl.dim; j += 1 << fl.lanes_log2) row[j] = fl.value;
-      }
-    }
-  }
+  fill_rows(n_fills, fills, n, lane, [&](int r) { return first + __shfl(evicted_lane, r, kWave); });
   return n;
 }
 
@@ -224,6 +235,82 @@ inline int check_geometry(const char* who, int32_t c, const char* prefix, const 
   HBK_REQUIRE(keys != nullptr, "%s: column %d: %s%s is NULL", who, c, prefix, keys_name);
   HBK_REQUIRE(((uintptr_t)keys & 7) == 0, "%s: column %d: %s%s must be 8-byte aligned", who, c, prefix, keys_name);
   return HBK_OK;
+}
+
+// The pure find as a pre-pass (hash_remove.hip, hash_missing.hip, hash_missing_runs.hip): the translate entries of
+// hash_insert.hip with insert == 0, called as they are on columns built here.
+constexpr int kFindKeysPerGroup = 8;                    // keys per lane group of a translate tile, first reads all in
+                                                        // flight (probe.hip): a tile takes (256 / G) * 8 keys
+constexpr int64_t kFindKeys = (1ll << 30) - 1;          // the find entry takes fewer than 2^30 keys per column
+constexpr int kFindParts = 3;                           // n_keys < 2^31: at most three such parts
+
+// the find's tiles of n keys at this slab size (checked), taken in parts of kFindKeys
+inline int64_t find_tiles_of(int64_t n, int32_t slab_size) {
+  const int64_t per_tile = (int64_t)(256 >> pow2_log2(slab_size)) * kFindKeysPerGroup;
+  int64_t tiles = 0;
+  for (int64_t at = 0; at < n; at += kFindKeys) {
+    const int64_t part = n - at < kFindKeys ? n - at : kFindKeys;
+    tiles += (part + per_tile - 1) / per_tile;
+  }
+  return tiles;
+}
+
+// The find's grid of every launch group -- `group` consecutive columns with keys -- before the first launch: the
+// find entry would notice a grid of 2^31 tiles only at that group's turn.  keys_of(c, &slab_size) is the number of
+// keys of column c.
+template <class KeysOf>
+inline int check_find_grids(const char* who, int32_t n_cols, int32_t group, KeysOf keys_of) {
+  int32_t k = 0;
+  int64_t find_tiles = 0;
+  for (int32_t c = 0; c < n_cols; ++c) {
+    int32_t slab_size;
+    const int64_t n = keys_of(c, &slab_size);
+    if (n == 0) continue;
+    find_tiles += find_tiles_of(n, slab_size);
+    HBK_REQUIRE(find_tiles < (1ll << 31),
+                "%s: column %d: n_keys: the find of its launch group (%d columns) needs %lld tiles or more, a grid "
+                "takes fewer than 2^31: name fewer ids per call", who, c, group, (long long)find_tiles);
+    if (++k == group) {
+      k = 0;
+      find_tiles = 0;
+    }
+  }
+  return HBK_OK;
+}
+
+// The find's column of a table and, with n > 0, n of its ids: the table as a translate sees it, no table rows, no
+// counters.  Col: any entry's column struct with keys_cache, slab_count, slab_size and exp.
+template <class Col>
+inline void describe_find(const Col& h, const int64_t* keys, int64_t* slots, int64_t n, hbk_hash_column_t* f,
+                          hbk_hash_expiry_t* x) {
+  f->keys_cache = const_cast<int64_t*>(h.keys_cache);   // (a find writes no key)
+  f->slab_count = h.slab_count;
+  f->slab_size = h.slab_size;
+  f->keys = keys;
+  f->n_keys = n;
+  f->slots = slots;
+  f->counts = nullptr;
+  f->table = nullptr;
+  f->dim = 0;
+  f->table_pitch = 0;
+  f->init_scale = 0.0f;
+  f->seed = 0;
+  x->last_seen = h.exp.last_seen;
+  x->freq = h.exp.freq;
+  x->step = h.exp.step != nullptr ? h.exp.step : h.exp.last_seen;   // (a find reads no step; its check asks for an address)
+  x->stats = nullptr;
+}
+
+// ... of a flat column (keys, n_keys < 2^31 and slots are h's): 2^30 keys or more go in parts, consecutive ranges of
+// the same keys and slots (the entry's own limit).  Returns the parts written, at most kFindParts.
+template <class Col>
+inline int32_t describe_find_parts(const Col& h, hbk_hash_column_t* f, hbk_hash_expiry_t* x) {
+  int32_t parts = 0;
+  for (int64_t at = 0; at < h.n_keys; at += kFindKeys, ++parts) {
+    describe_find(h, h.keys + at, h.slots + at, h.n_keys - at < kFindKeys ? h.n_keys - at : kFindKeys, f + parts,
+                  x + parts);
+  }
+  return parts;
 }
 
 }  // namespace hbk

@@ -89,7 +89,7 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kWavesPerBlock = kBlock / kWave;
 constexpr int kMaxColsPerLaunch = 64;   // one ballot finds the column; HashArgs travels by value
-constexpr int kKeys = 8;                // keys per lane group, first reads all in flight (probe.hip)
+constexpr int kKeys = kFindKeysPerGroup;   // keys per lane group, first reads all in flight (probe.hip)
 
 struct HashCol {
   long long* cache;

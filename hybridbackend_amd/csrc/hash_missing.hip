@@ -10,48 +10,24 @@
 //          or hbk_hash_translate_sequence_n with insert == 0.  It writes slots.
 //   claim  tiled over the POSITIONS, 1024 per tile, a lane owns one.  A position that holds an id (flat: always;
 //          sequence: recomputed by position as the sequence translate does, b = p / T by FastDiv and two row_splits
-//          reads) with slots[p] < 0 and an id that is no sentinel puts the id into the column's scratch set: open
-//          addressing over S = pow2 >= 2 * positions cells (at least 64), home cell = murmur3_i64(id) & (S - 1),
-//          linear probing; an EMPTY cell is claimed with a 64-bit agent-scope compare-and-swap.  At the id's cell the
-//          lane does atomicMin(first[cell], p).  A lane that finds its id already there does only the atomicMin,
-//          and not even that when the first[cell] it reads is already below p (first[] only falls; on a Zipf(1.2)
-//          batch the claim and compaction took 285 us with every occurrence's atomic and 185 us with the load:
-//          profiles/hash_fault_in.txt).  A wave without a miss leaves after reading slots: a batch of resident ids
-//          issues no atomic.
+//          reads) with slots[p] < 0 and an id that is no sentinel puts the id into the column's scratch set and
+//          its position into first[] of the id's cell (hash_miss_set.h: claim_cell).  A wave without a miss leaves
+//          after reading slots: a batch of resident ids issues no atomic.
 //   count, scan, write
 //          hash_pack.h's stream compaction over the positions with the selection "p missed and first[cell(id)] ==
 //          p": exactly one position per distinct missed id, the first, so the output is in first-occurrence order
 //          and a function of the inputs alone.  Ids only: no moves.
 //
-// No lane waits for another.  The claim's probe reads at most S cells, the bound written out in the loop: a cell
-// only ever goes EMPTY -> id, the distinct ids are at most S / 2, so a lane that loses a swap to ANOTHER id steps to
-// the next cell and a lane that loses to its own id is done.  No spin, no retry of a cell.
-//
-// Memory rules.  The find reads the key array with plain loads: nothing writes it beside it (the call is
-// stream-ordered against the translates, sweeps and backwards of its tables, never beside one).  The claim reads
-// the set with relaxed agent-scope atomic loads and writes it with the swap and the atomicMin, all served by the
-// device's L2 whatever CU issues them; a stale EMPTY read only costs a failed swap, whose returned value is the
-// cell's.  The kernel boundary publishes the set: count and write read it (and first[]) with plain loads, as
-// hash_insert.hip's find reads a key array nobody writes.
-//
-// hash_missing_runs.hip (hbk_hash_missing_runs_n) holds a copy of the scratch set -- kMinCells, kNoPosition, cells_of,
-// claim_cell, the clear kernel and the walk of selected() -- for ids that arrive as runs: a change of the set's rules
-// here is a change there.
-#include "hash_pack.h"
+// The scratch set -- its invariants, why no lane waits for another, its memory rules and the workspace -- is
+// hash_miss_set.h's, shared with hash_missing_runs.hip (ids that arrive as runs).  The find reads the key array with
+// plain loads: nothing writes it beside it (the call is stream-ordered against the translates, sweeps and backwards
+// of its tables, never beside one).
+#include "hash_miss_set.h"
 
 namespace hbk {
 namespace {
 
-using namespace pack;
-
-constexpr int kChunks = 4;                              // 64-position chunks per wave of the claim
-constexpr int kClaimPerBlock = kBlock * kChunks;
-constexpr int64_t kFindKeys = (1ll << 30) - 1;          // the find entry takes fewer than 2^30 keys per column
-constexpr int kFindParts = 3;                           // n_keys < 2^31: at most three such parts
-constexpr int kFindKeysPerGroup = 8;                    // hash_insert.hip's kKeys: a find tile takes (256 / G) * 8 keys
-constexpr int64_t kMinCells = 64;
-constexpr int32_t kNoPosition = 0x7fffffff;             // first[] of a cell nobody claimed
-constexpr int kClearBlocks = 4096;                      // the clear's grid at the most: it strides
+using namespace miss_set;
 
 // The id list by position.  Flat: position p holds ids[p].  Sequence: hash_insert.hip's seq_key, restated -- the
 // sample's t-th id when t < min(len_b, T), else the pad id, else nothing.
@@ -116,14 +92,7 @@ struct MissCol {
     if (p >= capacity) return false;
     long long id;
     if (!missed(p, &id)) return false;
-    uint64_t cell = (uint64_t)murmur3_i64((int64_t)id) & cell_mask;
-    for (uint64_t k = 0; k <= cell_mask; ++k) {   // (the claim's walk; it ends at the id: every missed id is in the set)
-      const long long cur = set[cell];
-      if (cur == id) return first[cell] == (int32_t)p;
-      if (cur == kEmptyKey) return false;
-      cell = (cell + 1) & cell_mask;
-    }
-    return false;
+    return first_position(set, first, cell_mask, id) == (int32_t)p;
   }
   __device__ void scanned() const {}
 };
@@ -135,39 +104,6 @@ struct MissArgs {
   MissCol col[kMaxColsPerLaunch];
 };
 static_assert(sizeof(MissArgs) <= 24576, "kernarg budget");
-
-// 16-byte stores: the cells of a call are a multiple of 64 and both arrays start 16-byte aligned
-__global__ __launch_bounds__(kBlock) void hash_missing_clear_kernel(longlong2* set, int4* first, int64_t cells) {
-  const int64_t stride = (int64_t)gridDim.x * kBlock;
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < (cells >> 1); i += stride) {
-    set[i] = make_longlong2(kEmptyKey, kEmptyKey);
-    if (i < (cells >> 2)) first[i] = make_int4(kNoPosition, kNoPosition, kNoPosition, kNoPosition);
-  }
-}
-
-// the id of a missed position into the column's set, its position into first[]: at most S cells are read
-__device__ inline void claim_cell(const MissCol& c, long long id, int32_t p) {
-  const uint64_t mask = c.cell_mask;
-  uint64_t cell = (uint64_t)murmur3_i64((int64_t)id) & mask;
-  for (uint64_t k = 0; k <= mask; ++k) {
-    long long cur = __hip_atomic_load(c.set + cell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == kEmptyKey) {
-      long long expected = kEmptyKey;
-      const bool won = __hip_atomic_compare_exchange_strong(c.set + cell, &expected, id, __ATOMIC_RELAXED,
-                                                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      cur = won ? id : expected;   // (lost: the cell's key now, ours or another's)
-    }
-    if (cur == id) {
-      // (first[] only falls: a position not below the value read changes nothing, and a stale read only costs the
-      // atomic -- the load spares a hot id's later occurrences their turn at one address)
-      if (__hip_atomic_load(c.first + cell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > p) {
-        __hip_atomic_fetch_min(c.first + cell, p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      return;
-    }
-    cell = (cell + 1) & mask;
-  }
-}
 
 __global__ __launch_bounds__(kBlock) void hash_missing_claim_kernel(const MissArgs a) {
   const int b = (int)blockIdx.x;
@@ -185,14 +121,8 @@ __global__ __launch_bounds__(kBlock) void hash_missing_claim_kernel(const MissAr
     long long id = kEmptyKey;
     const bool miss = p < positions && c.missed(p, &id);
     if (__ballot(miss) == 0ull) continue;   // (wave-uniform) every id of the chunk is resident: no atomic
-    if (miss) claim_cell(c, id, (int32_t)p);   // (positions < 2^31 was checked)
+    if (miss) claim_cell(c.set, c.first, c.cell_mask, id, (int32_t)p);   // (positions < 2^31 was checked)
   }
-}
-
-inline int64_t cells_of(int64_t positions) {
-  int64_t s = kMinCells;
-  while (s < 2 * positions) s <<= 1;
-  return s;
 }
 
 // the positions of a column whose counts are in range, else -1
@@ -202,13 +132,6 @@ inline int64_t positions_of(const hbk_hash_missing_column_t& h, const hbk_hash_s
   const int64_t positions = q->n_segments * (int64_t)q->max_len;
   return positions < (1ll << 31) ? positions : -1;
 }
-
-// the workspace: the sets of all columns, first[] of all columns, then the tile counts of all columns
-struct Layout {
-  int64_t cells;
-  int64_t tiles;
-  size_t bytes() const { return (size_t)cells * (sizeof(long long) + sizeof(int32_t)) + (size_t)tiles * sizeof(int64_t); }
-};
 
 inline Layout layout_of(int32_t n_cols, const hbk_hash_missing_column_t* cols, const hbk_hash_sequence_t* seq) {
   Layout l = {0, 0};
@@ -240,13 +163,7 @@ extern "C" int hbk_hash_missing_n(int32_t n_cols, const hbk_hash_missing_column_
   for (int32_t c = 0; c < n_cols; ++c) {
     const hbk_hash_missing_column_t& h = cols[c];
     if (int rc = check_geometry(who, c, "", "keys_cache", h.keys_cache, h.slab_count, h.slab_size)) return rc;
-    HBK_REQUIRE(h.exp.last_seen != nullptr, "%s: column %d: last_seen is NULL (expiring tables only)", who, c);
-    HBK_REQUIRE(h.exp.freq != nullptr, "%s: column %d: freq is NULL (expiring tables only)", who, c);
-    HBK_REQUIRE(h.count != nullptr, "%s: column %d: count is NULL", who, c);
-    HBK_REQUIRE(h.out_capacity >= 0, "%s: column %d: out_capacity must be >= 0, got %lld", who, c,
-                (long long)h.out_capacity);
-    HBK_REQUIRE(h.out_capacity == 0 || h.out_ids != nullptr, "%s: column %d: out_ids is NULL with out_capacity %lld",
-                who, c, (long long)h.out_capacity);
+    if (int rc = check_column(who, c, h.exp, h.count, h.out_capacity, h.out_ids)) return rc;
     HBK_REQUIRE(h.n_keys >= 0 && h.n_keys < (1ll << 31), "%s: column %d: n_keys must be in [0, 2^31), got %lld", who,
                 c, (long long)h.n_keys);
     HBK_REQUIRE(h.n_keys == 0 || h.keys != nullptr, "%s: column %d: keys is NULL with n_keys = %lld", who, c,
@@ -275,47 +192,19 @@ extern "C" int hbk_hash_missing_n(int32_t n_cols, const hbk_hash_missing_column_
                   "%s: column %d: pad_id INT64_MIN + 1 (TOMBSTONE) is never stored in an expiring table", who, c);
     }
   }
-  // the find's grid of every launch group, before the first launch (hash_remove.hip: the find entry would notice a
-  // grid of 2^31 tiles only at that group's turn)
-  {
-    int32_t k = 0;
-    int64_t find_tiles = 0;
-    for (int32_t c = 0; c < n_cols; ++c) {
-      const int64_t positions = positions_of(cols[c], seq != nullptr ? seq + c : nullptr);
-      if (positions == 0) continue;
-      const int64_t per_tile = (int64_t)(kBlock >> pow2_log2(cols[c].slab_size)) * kFindKeysPerGroup;
-      for (int64_t at = 0; at < positions; at += kFindKeys) {
-        const int64_t part = positions - at < kFindKeys ? positions - at : kFindKeys;
-        find_tiles += (part + per_tile - 1) / per_tile;
-      }
-      HBK_REQUIRE(find_tiles < (1ll << 31),
-                  "%s: column %d: n_keys: the find of its launch group (32 columns) needs %lld tiles or more, a grid "
-                  "takes fewer than 2^31: name fewer ids per call", who, c, (long long)find_tiles);
-      if (++k == kMaxColsPerLaunch) {
-        k = 0;
-        find_tiles = 0;
-      }
-    }
+  // the find's grid of every launch group, before the first launch
+  if (int rc = check_find_grids(who, n_cols, kMaxColsPerLaunch, [&](int32_t c, int32_t* slab_size) {
+        *slab_size = cols[c].slab_size;
+        return positions_of(cols[c], seq != nullptr ? seq + c : nullptr);
+      })) {
+    return rc;
   }
   const Layout layout = layout_of(n_cols, cols, seq);
-  const size_t need = layout.bytes();
-  if (need != 0) {
-    HBK_REQUIRE(workspace != nullptr, "%s: workspace is NULL (hbk_hash_missing_workspace_bytes says how large: %zu "
-                "bytes)", who, need);
-    HBK_REQUIRE(((uintptr_t)workspace & 15) == 0, "%s: workspace must be 16-byte aligned", who);
-    HBK_REQUIRE(workspace_bytes >= need, "%s: workspace_bytes %zu is too small: %zu bytes are needed", who,
-                workspace_bytes, need);
-  }
   hipStream_t stream = as_stream(stream_);
-  long long* sets = static_cast<long long*>(workspace);
-  int32_t* firsts = reinterpret_cast<int32_t*>(sets + layout.cells);      // (cells: a multiple of 64)
-  int64_t* tile_ws = reinterpret_cast<int64_t*>(firsts + layout.cells);
-  if (layout.cells != 0) {
-    const int64_t blocks = ((layout.cells >> 1) + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(hash_missing_clear_kernel, dim3((unsigned)(blocks < kClearBlocks ? blocks : kClearBlocks)),
-                       dim3(kBlock), 0, stream, reinterpret_cast<longlong2*>(sets), reinterpret_cast<int4*>(firsts),
-                       layout.cells);
-    HBK_HIP_OK(hipGetLastError());
+  Workspace ws;
+  if (int rc = open_workspace(who, "hbk_hash_missing_workspace_bytes", workspace, workspace_bytes, layout.bytes(),
+                              layout, stream, &ws)) {
+    return rc;
   }
   int32_t c0 = 0;
   while (c0 < n_cols) {
@@ -335,29 +224,13 @@ extern "C" int hbk_hash_missing_n(int32_t n_cols, const hbk_hash_missing_column_
         HBK_HIP_OK(hipMemsetAsync(h.count, 0, sizeof(int64_t), stream));
         continue;
       }
-      // the find's columns: the table as a translate sees it, no table rows, no counters; a flat column of 2^30
-      // keys or more goes in parts (the entry's own limit)
-      for (int64_t at = 0; at < (q != nullptr ? 1 : positions); at += kFindKeys) {
-        hbk_hash_column_t& f = find_cols[n_find];
-        f.keys_cache = const_cast<int64_t*>(h.keys_cache);
-        f.slab_count = h.slab_count;
-        f.slab_size = h.slab_size;
-        f.keys = q != nullptr ? h.keys : h.keys + at;
-        f.n_keys = q != nullptr ? h.n_keys : (positions - at < kFindKeys ? positions - at : kFindKeys);
-        f.slots = q != nullptr ? h.slots : h.slots + at;
-        f.counts = nullptr;
-        f.table = nullptr;
-        f.dim = 0;
-        f.table_pitch = 0;
-        f.init_scale = 0.0f;
-        f.seed = 0;
-        hbk_hash_expiry_t& x = find_exp[n_find++];
-        x.last_seen = h.exp.last_seen;
-        x.freq = h.exp.freq;
-        x.step = h.exp.step != nullptr ? h.exp.step : h.exp.last_seen;   // (a find reads no step; its check asks for an address)
-        x.stats = nullptr;
+      // the find's columns: a sequence column as it is (with every id, also behind T), a flat one in parts
+      if (q != nullptr) {
+        describe_find(h, h.keys, h.slots, h.n_keys, find_cols + k, find_exp + k);
+        find_seq[k] = *q;
+      } else {
+        n_find += describe_find_parts(h, find_cols + n_find, find_exp + n_find);
       }
-      if (q != nullptr) find_seq[k] = *q;
       MissCol& d = args.col[k];
       d.keys.ids = h.keys;
       d.keys.row_splits = q != nullptr ? q->row_splits : nullptr;
@@ -369,12 +242,12 @@ extern "C" int hbk_hash_missing_n(int32_t n_cols, const hbk_hash_missing_column_
       d.keys.has_pad = q != nullptr && q->has_pad != 0 ? 1 : 0;
       d.slots = h.slots;
       const int64_t cells = cells_of(positions);
-      d.set = sets;
-      d.first = firsts;
+      d.set = ws.set;
+      d.first = ws.first;
       d.out_keys = reinterpret_cast<long long*>(h.out_ids);
       d.out_slots = nullptr;
       d.count = h.count;
-      d.tiles = tile_ws;
+      d.tiles = ws.tiles;
       d.capacity = positions;
       d.out_capacity = h.out_capacity;
       d.n_tiles = tiles_of(positions);
@@ -382,10 +255,8 @@ extern "C" int hbk_hash_missing_n(int32_t n_cols, const hbk_hash_missing_column_
       d.n_moves = 0;
       d.pad_ = 0;
       d.move[0] = Move{nullptr, nullptr, 0, 0, 0, 0, 0};
-      sets += cells;
-      firsts += cells;
-      tile_ws += d.n_tiles;
-      tiles += d.n_tiles;                                              // (< 2^23 per column: 32 of them fit a grid)
+      ws.take(cells, d.n_tiles);
+      tiles += d.n_tiles;                                             // (< 2^23 per column: 32 of them fit a grid)
       claim_tiles += (positions + kClaimPerBlock - 1) / kClaimPerBlock;
       ++k;
       args.tile_start[k] = (int32_t)tiles;

@@ -20,83 +20,29 @@
 //          RUN as the runs translate does -- up to four 64-wide ballots over the runs' first claim tiles, the run
 //          tables in the kernarg -- and the run names its column.  It records the run of each of its tiles in the
 //          column's tile_run[] (workspace): count and write, whose lanes meet the position under divergence, read
-//          it from there with a plain load after the kernel boundary.  A position inside the run with slots < 0 and an id that is no sentinel goes into
-//          the column's scratch set: hash_missing.hip's, cell for cell.  A wave without a miss leaves after reading
-//          slots: a batch of resident ids issues no atomic.
+//          it from there with a plain load after the kernel boundary.  A position inside the run with slots < 0 and
+//          an id that is no sentinel goes into the column's scratch set (hash_miss_set.h: claim_cell, the set
+//          hash_missing.hip fills).  A wave without a miss leaves after reading slots: a batch of resident ids
+//          issues no atomic.
 //   count, scan, write
 //          hash_pack.h's stream compaction over the padded positions with the selection "p lies in its run, missed
 //          and first[cell(id)] == p": exactly one position per distinct missed id, the first.  Ids only: no moves.
 //
-// No lane waits for another: the claim's probe reads at most S cells (claim_cell below).  Memory rules: those of
-// hash_missing.hip -- the find reads the key array with plain loads; the claim reads and writes the set with relaxed
-// agent-scope atomics; the kernel boundary publishes the set, first[] and tile_run[] to count and write.
+// The scratch set, why no lane waits for another and the memory rules: hash_miss_set.h.  The find reads the key
+// array with plain loads, as hash_missing.hip's; the kernel boundary that publishes the set and first[] to count and
+// write publishes tile_run[] too.
 #include <vector>
 
-#include "hash_pack.h"
+#include "hash_miss_set.h"
 
 namespace hbk {
 namespace {
 
-using namespace pack;
+using namespace miss_set;
 
 constexpr int kMaxRunsPerLaunch = HBK_HASH_MAX_RUNS_PER_LAUNCH;
 static_assert(kMaxRunsPerLaunch % kWave == 0, "one ballot per 64 runs");
-constexpr int kFindKeysPerGroup = 8;                    // hash_insert.hip's kKeys: a find tile takes (256 / G) * 8 keys
 constexpr int64_t kKeyLimit = 1ll << 30;                // the runs translate of an expiring table takes fewer per column
-constexpr int kClearBlocks = 4096;                      // the clear's grid at the most: it strides
-constexpr int kChunks = 4;                              // 64-position chunks per wave of the claim
-constexpr int kClaimPerBlock = kBlock * kChunks;        // a whole number of 256-position tiles
-
-// The scratch set of a column, as hash_missing.hip keeps it (that file holds the same walk for its flat and sequence
-// positions): the distinct missed ids in open addressing over S = pow2 >= 2 * ids cells (at least 64), home cell =
-// murmur3_i64(id) & (S - 1), linear probing, EMPTY = INT64_MIN, and beside every cell the smallest position that
-// missed with the cell's id.  A cell only ever goes EMPTY -> id and first[] only falls: a lane that loses a swap to
-// ANOTHER id steps to the next cell and a lane that loses to its own id is done.
-constexpr int64_t kMinCells = 64;
-constexpr int32_t kNoPosition = 0x7fffffff;             // first[] of a cell nobody claimed
-
-// the cells of a column that names `ids` ids: at most half of them are ever taken
-inline int64_t cells_of(int64_t ids) {
-  int64_t s = kMinCells;
-  while (s < 2 * ids) s <<= 1;
-  return s;
-}
-
-// the id of a missed position into the set, its position into first[]: at most S = mask + 1 cells are read
-__device__ inline void claim_cell(long long* set, int32_t* first, uint64_t mask, long long id, int32_t p) {
-  uint64_t cell = (uint64_t)murmur3_i64((int64_t)id) & mask;
-  for (uint64_t k = 0; k <= mask; ++k) {
-    long long cur = __hip_atomic_load(set + cell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == kEmptyKey) {
-      long long expected = kEmptyKey;
-      const bool won = __hip_atomic_compare_exchange_strong(set + cell, &expected, id, __ATOMIC_RELAXED,
-                                                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      cur = won ? id : expected;   // (lost: the cell's key now, ours or another's)
-    }
-    if (cur == id) {
-      // (first[] only falls: a position not below the value read changes nothing, and a stale read only costs the
-      // atomic -- the load spares a hot id's later occurrences their turn at one address)
-      if (__hip_atomic_load(first + cell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > p) {
-        __hip_atomic_fetch_min(first + cell, p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      return;
-    }
-    cell = (cell + 1) & mask;
-  }
-}
-
-// after the claim's kernel boundary: the first position that missed with `id`, or kNoPosition when the set does
-// not hold it (the claim's walk; it ends at the id or at an EMPTY cell)
-__device__ inline int32_t first_position(const long long* set, const int32_t* first, uint64_t mask, long long id) {
-  uint64_t cell = (uint64_t)murmur3_i64((int64_t)id) & mask;
-  for (uint64_t k = 0; k <= mask; ++k) {
-    const long long cur = set[cell];
-    if (cur == id) return first[cell];
-    if (cur == kEmptyKey) return kNoPosition;
-    cell = (cell + 1) & mask;
-  }
-  return kNoPosition;
-}
 
 // one non-empty run of the launch
 struct Run {
@@ -203,15 +149,6 @@ struct MissRunsArgs {
 };
 static_assert(sizeof(MissRunsArgs) <= 24576, "kernarg budget");
 
-// 16-byte stores: the cells of a call are a multiple of 64 and both arrays start 16-byte aligned
-__global__ __launch_bounds__(kBlock) void hash_missing_runs_clear_kernel(longlong2* set, int4* first, int64_t cells) {
-  const int64_t stride = (int64_t)gridDim.x * kBlock;
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < (cells >> 1); i += stride) {
-    set[i] = make_longlong2(kEmptyKey, kEmptyKey);
-    if (i < (cells >> 2)) first[i] = make_int4(kNoPosition, kNoPosition, kNoPosition, kNoPosition);
-  }
-}
-
 // last run whose first claim tile is <= b (hash_insert.hip's find_run): up to four 64-wide ballots; every lane calls
 __device__ inline int find_run(const ColTable& t, int b) {
   const int lane = lane_id();
@@ -268,31 +205,24 @@ struct Extent {
   int32_t runs;
 };
 
+// (slab_size: checked, or 1 where the find's tiles are not read)
 inline bool extent_of(int32_t slab_size, int32_t n_runs, const hbk_hash_run_t* runs, Extent* e) {
   *e = Extent{0, 0, 0, 0};
   if (n_runs < 0 || (n_runs > 0 && runs == nullptr)) return false;
-  const int64_t per_find_tile =
-      slab_size >= 1 && slab_size <= kWave ? (int64_t)(kBlock >> pow2_log2(slab_size)) * kFindKeysPerGroup : 1;
   for (int32_t r = 0; r < n_runs; ++r) {
     const int64_t n = runs[r].n_keys;
     if (n < 0 || n >= (1ll << 31)) return false;
     if (n == 0) continue;
     e->ids += n;
     e->tiles += tiles_of(n);
-    e->find_tiles += (n + per_find_tile - 1) / per_find_tile;
+    e->find_tiles += find_tiles_of(n, slab_size);   // (a run is one part: the ids of a column stay below kKeyLimit)
     ++e->runs;
   }
   return e->ids < kKeyLimit && e->tiles * kSlotsPerTile < (1ll << 31) && e->runs <= kMaxRunsPerLaunch;
 }
 
-// the workspace: the sets of all columns, first[] of all columns, the tile counts of all columns, then tile_run[]
-struct Layout {
-  int64_t cells;
-  int64_t tiles;
-  size_t bytes() const {
-    return (size_t)cells * (sizeof(long long) + sizeof(int32_t)) + (size_t)tiles * (sizeof(int64_t) + sizeof(int32_t));
-  }
-};
+// the workspace: hash_miss_set.h's, then tile_run[] of all columns
+constexpr size_t kTileRunBytes = sizeof(int32_t);
 
 inline Layout layout_of(int32_t n_cols, const int32_t* n_runs, const hbk_hash_run_t* const* runs) {
   Layout l = {0, 0};
@@ -324,7 +254,7 @@ inline int32_t group_end(int32_t n_cols, const Extent* extents, int32_t c0) {
 
 extern "C" size_t hbk_hash_missing_runs_workspace_bytes(int32_t n_cols, const int32_t* n_runs,
                                                         const hbk_hash_run_t* const* runs) {
-  return hbk::layout_of(n_cols, n_runs, runs).bytes();
+  return hbk::layout_of(n_cols, n_runs, runs).bytes(hbk::kTileRunBytes);
 }
 
 extern "C" int hbk_hash_missing_runs_n(int32_t n_cols, const hbk_hash_missing_runs_column_t* cols,
@@ -339,13 +269,7 @@ extern "C" int hbk_hash_missing_runs_n(int32_t n_cols, const hbk_hash_missing_ru
   for (int32_t c = 0; c < n_cols; ++c) {
     const hbk_hash_missing_runs_column_t& h = cols[c];
     if (int rc = check_geometry(who, c, "", "keys_cache", h.keys_cache, h.slab_count, h.slab_size)) return rc;
-    HBK_REQUIRE(h.exp.last_seen != nullptr, "%s: column %d: last_seen is NULL (expiring tables only)", who, c);
-    HBK_REQUIRE(h.exp.freq != nullptr, "%s: column %d: freq is NULL (expiring tables only)", who, c);
-    HBK_REQUIRE(h.count != nullptr, "%s: column %d: count is NULL", who, c);
-    HBK_REQUIRE(h.out_capacity >= 0, "%s: column %d: out_capacity must be >= 0, got %lld", who, c,
-                (long long)h.out_capacity);
-    HBK_REQUIRE(h.out_capacity == 0 || h.out_ids != nullptr, "%s: column %d: out_ids is NULL with out_capacity %lld",
-                who, c, (long long)h.out_capacity);
+    if (int rc = check_column(who, c, h.exp, h.count, h.out_capacity, h.out_ids)) return rc;
     // the rules of hbk_hash_translate_runs_n for an expiring table's runs
     HBK_REQUIRE(n_runs[c] >= 0, "%s: column %d: n_runs must be >= 0, got %d", who, c, n_runs[c]);
     HBK_REQUIRE(n_runs[c] == 0 || runs[c] != nullptr, "%s: column %d: runs is NULL with n_runs = %d", who, c,
@@ -380,26 +304,13 @@ extern "C" int hbk_hash_missing_runs_n(int32_t n_cols, const hbk_hash_missing_ru
     c0 = c1;
   }
   const Layout layout = layout_of(n_cols, n_runs, runs);
-  const size_t need = layout.bytes();
-  if (need != 0) {
-    HBK_REQUIRE(workspace != nullptr, "%s: workspace is NULL (hbk_hash_missing_runs_workspace_bytes says how large: "
-                "%zu bytes)", who, need);
-    HBK_REQUIRE(((uintptr_t)workspace & 15) == 0, "%s: workspace must be 16-byte aligned", who);
-    HBK_REQUIRE(workspace_bytes >= need, "%s: workspace_bytes %zu is too small: %zu bytes are needed", who,
-                workspace_bytes, need);
-  }
   hipStream_t stream = as_stream(stream_);
-  long long* sets = static_cast<long long*>(workspace);
-  int32_t* firsts = reinterpret_cast<int32_t*>(sets + layout.cells);      // (cells: a multiple of 64)
-  int64_t* tile_ws = reinterpret_cast<int64_t*>(firsts + layout.cells);
-  int32_t* tile_runs = reinterpret_cast<int32_t*>(tile_ws + layout.tiles);
-  if (layout.cells != 0) {
-    const int64_t blocks = ((layout.cells >> 1) + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(hash_missing_runs_clear_kernel, dim3((unsigned)(blocks < kClearBlocks ? blocks : kClearBlocks)),
-                       dim3(kBlock), 0, stream, reinterpret_cast<longlong2*>(sets), reinterpret_cast<int4*>(firsts),
-                       layout.cells);
-    HBK_HIP_OK(hipGetLastError());
+  Workspace ws;
+  if (int rc = open_workspace(who, "hbk_hash_missing_runs_workspace_bytes", workspace, workspace_bytes,
+                              layout.bytes(kTileRunBytes), layout, stream, &ws)) {
+    return rc;
   }
+  int32_t* tile_runs = reinterpret_cast<int32_t*>(ws.tiles + layout.tiles);
   for (int32_t c0 = 0; c0 < n_cols;) {
     const int32_t c1 = group_end(n_cols, extents.data(), c0);
     MissRunsArgs args;
@@ -417,43 +328,23 @@ extern "C" int hbk_hash_missing_runs_n(int32_t n_cols, const hbk_hash_missing_ru
         HBK_HIP_OK(hipMemsetAsync(h.count, 0, sizeof(int64_t), stream));
         continue;
       }
-      // the find's column: the table as a translate sees it, no table rows, no counters
-      hbk_hash_column_t& f = find_cols[k];
-      f.keys_cache = const_cast<int64_t*>(h.keys_cache);
-      f.slab_count = h.slab_count;
-      f.slab_size = h.slab_size;
-      f.keys = nullptr;
-      f.n_keys = 0;
-      f.slots = nullptr;
-      f.counts = nullptr;
-      f.table = nullptr;
-      f.dim = 0;
-      f.table_pitch = 0;
-      f.init_scale = 0.0f;
-      f.seed = 0;
-      hbk_hash_expiry_t& x = find_exp[k];
-      x.last_seen = h.exp.last_seen;
-      x.freq = h.exp.freq;
-      x.step = h.exp.step != nullptr ? h.exp.step : h.exp.last_seen;   // (a find reads no step; its check asks for an address)
-      x.stats = nullptr;
+      describe_find(h, nullptr, nullptr, 0, find_cols + k, find_exp + k);   // (the ids: the runs)
       find_n_runs[k] = n_runs[c];
       find_runs[k] = runs[c];
       const int64_t cells = cells_of(e.ids);
       ColRec& d = args.col.rec[k];
-      d.set = sets;
-      d.first = firsts;
+      d.set = ws.set;
+      d.first = ws.first;
       d.out_keys = reinterpret_cast<long long*>(h.out_ids);
       d.count = h.count;
-      d.tiles = tile_ws;
+      d.tiles = ws.tiles;
       d.tile_run = tile_runs;
       d.out_capacity = h.out_capacity;
       d.n_tiles = e.tiles;
       d.cell_mask = (uint64_t)cells - 1;
       d.tile_first = (int32_t)tiles;
       d.pad_ = 0;
-      sets += cells;
-      firsts += cells;
-      tile_ws += e.tiles;
+      ws.take(cells, e.tiles);
       tile_runs += e.tiles;
       for (int32_t r = 0; r < n_runs[c]; ++r) {
         const hbk_hash_run_t& run = runs[c][r];

@@ -10,9 +10,9 @@
 //          keys[s]: id -> TOMBSTONE with a 64-bit agent-scope compare-and-swap.  Of the occurrences of one id
 //          exactly one finds the id still there: the winner.  It stores the metadata zeros; the wave ballots its
 //          winners, gathers their lane numbers into the low lanes with one permute (compact_lanes) and fills their
-//          companion rows with groups of pow2(dim) lanes, 64 / pow2(dim) rows per pass, as sweep_wave does -- the
-//          row's slot number arrives by a shuffle from the winner's lane, where the sweep has first + lane.  One
-//          atomic per wave and counter.
+//          companion rows with groups of pow2(dim) lanes, 64 / pow2(dim) rows per pass: hash_common.h's fill_rows,
+//          the loop of sweep_wave -- the row's slot number arrives by a shuffle from the winner's lane, where the
+//          sweep has first + lane.  One atomic per wave and counter.
 //
 // Why two kernels.  In one fused kernel a duplicate that walks after the winner's swap would find a TOMBSTONE and
 // answer -1: slots would depend on which wave runs first.  The kernel boundary puts every read of the key array
@@ -41,9 +41,6 @@ constexpr int kWavesPerBlock = kBlock / kWave;
 constexpr int kChunks = 4;                              // 64-occurrence chunks per wave
 constexpr int kKeysPerBlock = kBlock * kChunks;
 constexpr int kMaxColsPerLaunch = 32;                   // RemoveArgs travels by value
-constexpr int64_t kFindKeys = (1ll << 30) - 1;          // the find entry takes fewer than 2^30 keys per column
-constexpr int kFindParts = 3;                           // n_keys < 2^31: at most three such parts
-constexpr int kFindKeysPerGroup = 8;                    // hash_insert.hip's kKeys: a find tile takes (256 / G) * 8 keys
 
 struct RemoveCol {
   long long* keys;        // the table's key array
@@ -107,19 +104,7 @@ __global__ __launch_bounds__(kBlock) void hash_remove_erase_kernel(const RemoveA
     if (c.n_fills == 0) continue;
     const int won_lane = compact_lanes(mask, won, lane);     // lane r < n: the lane of the r-th winner
     const int32_t won_slot = __shfl(slot, won_lane, kWave);  // lane r < n: its slot
-    for (int f = 0; f < c.n_fills; ++f) {
-      const Fill& fl = fills[f];
-      const int rows_log2 = 6 - fl.lanes_log2;                 // rows per pass
-      const int j0 = lane & ((1 << fl.lanes_log2) - 1);
-      for (int r0 = 0; r0 < n; r0 += 1 << rows_log2) {
-        const int r = r0 + (lane >> fl.lanes_log2);
-        const int32_t s = __shfl(won_slot, r & (kWave - 1), kWave);   // (every lane takes the shuffle)
-        if (r < n) {
-          float* row = fl.base + (int64_t)s * fl.pitch;
-          for (int j = j0; j < fl.dim; j += 1 << fl.lanes_log2) row[j] = fl.value;
-        }
-      }
-    }
+    fill_rows(c.n_fills, fills, n, lane, [&](int r) { return (int64_t)__shfl(won_slot, r, kWave); });
   }
   if (lane == 0 && n_won != 0) {
     if (c.stats != nullptr) atomicAdd(c.stats, n_won);
@@ -154,25 +139,11 @@ extern "C" int hbk_hash_remove_n(int32_t n_cols, const hbk_hash_remove_column_t*
   // the grids of every launch group, before the first launch: the find entry would refuse a grid of 2^31 tiles
   // only when its group's turn came, behind the erase of the groups before it (the erase's own grid is smaller:
   // 1024 occurrences per tile)
-  {
-    int32_t k = 0;
-    int64_t find_tiles = 0;
-    for (int32_t c = 0; c < n_cols; ++c) {
-      const hbk_hash_remove_column_t& h = cols[c];
-      if (h.n_keys == 0) continue;
-      const int64_t per_tile = (int64_t)(kBlock >> pow2_log2(h.slab_size)) * kFindKeysPerGroup;
-      for (int64_t at = 0; at < h.n_keys; at += kFindKeys) {
-        const int64_t part = h.n_keys - at < kFindKeys ? h.n_keys - at : kFindKeys;
-        find_tiles += (part + per_tile - 1) / per_tile;
-      }
-      HBK_REQUIRE(find_tiles < (1ll << 31),
-                  "%s: column %d: n_keys: the find of its launch group (32 columns) needs %lld tiles or more, a grid "
-                  "takes fewer than 2^31: name fewer ids per call", who, c, (long long)find_tiles);
-      if (++k == kMaxColsPerLaunch) {
-        k = 0;
-        find_tiles = 0;
-      }
-    }
+  if (int rc = check_find_grids(who, n_cols, kMaxColsPerLaunch, [&](int32_t c, int32_t* slab_size) {
+        *slab_size = cols[c].slab_size;
+        return cols[c].n_keys;
+      })) {
+    return rc;
   }
   int32_t c0 = 0;
   while (c0 < n_cols) {
@@ -185,28 +156,7 @@ extern "C" int hbk_hash_remove_n(int32_t n_cols, const hbk_hash_remove_column_t*
     while (c0 < n_cols && k < kMaxColsPerLaunch) {
       const hbk_hash_remove_column_t& h = cols[c0++];
       if (h.n_keys == 0) continue;
-      // the find's columns: the table as a translate sees it, no table rows, no counters; a column of 2^30 keys
-      // or more goes in parts (the entry's own limit)
-      for (int64_t at = 0; at < h.n_keys; at += kFindKeys) {
-        hbk_hash_column_t& f = find_cols[n_find];
-        f.keys_cache = h.keys_cache;
-        f.slab_count = h.slab_count;
-        f.slab_size = h.slab_size;
-        f.keys = h.keys + at;
-        f.n_keys = h.n_keys - at < kFindKeys ? h.n_keys - at : kFindKeys;
-        f.slots = h.slots + at;
-        f.counts = nullptr;
-        f.table = nullptr;
-        f.dim = 0;
-        f.table_pitch = 0;
-        f.init_scale = 0.0f;
-        f.seed = 0;
-        hbk_hash_expiry_t& x = find_exp[n_find++];
-        x.last_seen = h.exp.last_seen;
-        x.freq = h.exp.freq;
-        x.step = h.exp.step != nullptr ? h.exp.step : h.exp.last_seen;   // (a find reads no step; its check asks for an address)
-        x.stats = nullptr;
-      }
+      n_find += describe_find_parts(h, find_cols + n_find, find_exp + n_find);
       RemoveCol& d = args.col[k];
       d.keys = reinterpret_cast<long long*>(h.keys_cache);
       d.ids = h.keys;

@@ -188,6 +188,38 @@ def test_run_lengths_with_empty_runs_first_in_the_middle_and_last(half, odd, n):
     check([half, odd], [[draw(rng, m) for m in lengths], [draw(rng, m) for m in lengths]])
 
 
+# ---- one id list, cut into runs: the flat call's answer, bit for bit -------------------------------------------------
+WIDE = distinct_keys(np.random.RandomState(61), 1200)
+
+
+@pytest.fixture(scope='module')
+def wide():
+  """2048 slots in slabs of 8: every second id of the wide pool is resident."""
+  return table_with(WIDE[::2], capacity=2048, slab=8, dim=4)
+
+
+@pytest.mark.parametrize('n', [1, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025])
+def test_one_list_cut_into_runs_answers_as_the_flat_call(wide, n):
+  """Both entries claim into one scratch set (csrc/hash_miss_set.h): over the same ids E -- about half of them
+  resident, one missed id at both ends, so in the first and in the last run -- hbk_hash_missing_n on E and
+  hbk_hash_missing_runs_n on E cut into runs report the same count and the same ids in the same order.  The lengths
+  are the edges of a wave (64), of a compaction tile (256) and of a claim tile (1024)."""
+  rng = np.random.RandomState(400 + n)
+  ids = draw(rng, n, WIDE)
+  ids[0] = ids[-1] = WIDE[1]
+  flat_slots, flat_out, flat_count = flat_on_device([wide], [ids], [n])[0]
+  assert 0 < flat_count <= n and (n == 1 or bool((flat_slots >= 0).any()))
+  assert flat_out[0] == WIDE[1] and (flat_out[:flat_count] == WIDE[1]).sum() == 1
+  cuts = ([ids], [ids[:1], ids[1:]], [ids[:n - 1], ids[n - 1:]], [ids[:n // 2], ids[:0], ids[n // 2:]])
+  for runs in cuts:
+    call = RunsCall([wide], [runs])
+    call.launch()
+    slots, out, count = call.results()[0]
+    assert count == flat_count, [r.size for r in runs]
+    assert out.tobytes() == flat_out.tobytes(), [r.size for r in runs]
+    assert slots.tobytes() == flat_slots.tobytes(), [r.size for r in runs]
+
+
 # ---- order across runs ---------------------------------------------------------------------------------------------
 def test_an_id_in_two_runs_is_reported_once_at_its_earlier_run(half):
   rng = np.random.RandomState(21)
