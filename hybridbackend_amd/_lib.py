@@ -113,7 +113,7 @@ class LowpLookupColumn(C.Structure):
               ('ids', C.c_void_p), ('ids_dtype', C.c_int32), ('combiner', C.c_int32), ('n_ids', C.c_int64),
               ('row_splits', C.c_void_p), ('n_segments', C.c_int64), ('bucket', C.c_int64),
               ('divisor', C.c_int32), ('out_stride', C.c_int32), ('out', C.c_void_p),
-              ('id_weights', C.c_void_p), ('chunk_elems', C.c_int32), ('reserved', C.c_int32)]
+              ('id_weights', C.c_void_p), ('chunk_elems', C.c_int32), ('wide_rows', C.c_int32)]
 
 
 class LowpSlicesColumn(C.Structure):
@@ -384,6 +384,7 @@ def _declare(l):
     'hbk_hash_missing_runs_n': (C.c_int, [i32, vp, vp, vp, vp, sz, vp]),
     'hbk_hash_insert_admit_n': (C.c_int, [i32, vp, vp, i32, vp]),
     'hbk_hash_insert_expiring_admit_n': (C.c_int, [i32, vp, vp, vp, i32, vp]),
+    'hbk_hash_insert_lowp_n': (C.c_int, [i32, vp, vp, vp, vp, i32, vp]),
     'hbk_hash_rehash_n': (C.c_int, [i32, vp, vp]),
     'hbk_hash_translate_runs_n': (C.c_int, [i32, vp, vp, vp, vp, vp, i32, vp]),
     'hbk_hash_translate_sequence_n': (C.c_int, [i32, vp, vp, vp, vp, i32, vp]),

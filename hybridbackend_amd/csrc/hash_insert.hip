@@ -79,9 +79,18 @@
 // its slot is written -1 and it counts nowhere, while an id INT64_MIN in the data is -1 counted as failed, as
 // everywhere.  The walk is the body above, every lane of the wave in every ballot and shuffle as before.
 // Everything new is behind `if constexpr (kSeq)`.
+//
+// 16-bit tables (hbk_hash_insert_lowp_n): the same kernels with LOWP = true, for the launches that insert.  The walk,
+// the claims, the metadata and the counters are the body above; the one difference is init_row, the two kernels' one
+// row initialisation: the winning group rounds the fp32 start values to the column's 16 bits (lowp_elems.h, the
+// rounding of the apply) and stores whole 4-byte words of two elements.  HashCol has no spare field, so the element
+// code rides in the bits of group_log2 above kElemShift, which only the LOWP instantiations mask: the others are
+// the kernels they were, instruction for instruction.  A launch that writes no row -- a find, the counting phase of a
+// filtered table -- is the fp32 kernel as it is.
 #include <math.h>
 
 #include "hash_common.h"
+#include "lowp_elems.h"
 
 namespace hbk {
 namespace {
@@ -96,16 +105,17 @@ struct HashCol {
   const int64_t* keys;
   int64_t* slots;
   int32_t* counts;      // {n_inserted, n_failed} or NULL
-  float* table;         // NULL: no row is written
+  float* table;         // NULL: no row is written (16-bit kernels: 2-byte elements behind it)
   int64_t n_keys;
   FastDiv slab_div;     // .d = slab_count
-  int64_t pitch;        // floats between rows
+  int64_t pitch;        // elements between rows
   uint64_t seed;
   float init_scale;
   int32_t slab_size;
   int32_t dim;
-  int32_t group_log2;
+  int32_t group_log2;   // 16-bit kernels: bits 0-7; the element code (HBK_LOWP_*) from kElemShift up
 };
+static_assert(sizeof(HashCol) == 104, "HashCol has no spare field: SeqArgs<ExpiringAdmitArgs> exactly fits 64 columns");
 
 struct HashArgs {
   int32_t n_cols;
@@ -231,6 +241,41 @@ __host__ __device__ inline float init_value(int64_t key, uint64_t seed, int j, f
   return unit * scale;
 }
 
+// The 16-bit kernels (LOWP; hbk_hash_insert_lowp_n) carry the column's element code in the spare bits of
+// HashCol.group_log2; the fp32 kernels read the field whole, as they always did.
+constexpr int kElemShift = 8;
+template <bool LOWP>
+__device__ inline int lane_group_log2(const HashCol& c) {
+  if constexpr (LOWP) return c.group_log2 & ((1 << kElemShift) - 1);
+  return c.group_log2;
+}
+
+// The new row of `key` at `slot`, written by the lane group that won the slot (sub = the lane's place in it).
+// fp32: one element per lane and pass.  LOWP: the fp32 value rounded to nearest even by lowp_elems.h, whole 4-byte
+// words -- word w = elements 2w (low half) and 2w + 1 (high half); dim and the pitch are even and the table 4-byte
+// aligned (checked), so no lane writes a partial dword and nothing outside [row, row + dim) is written.
+template <bool LOWP>
+__device__ inline void init_row(const HashCol& c, long long key, int64_t slot, int sub, int gsize) {
+  if constexpr (LOWP) {
+    const bool bf16 = (c.group_log2 >> kElemShift) == HBK_LOWP_BF16;
+    uint32_t* row = reinterpret_cast<uint32_t*>(reinterpret_cast<uint16_t*>(c.table) + slot * c.pitch);
+    for (int w = sub; w < (c.dim >> 1); w += gsize) {
+      uint32_t word = 0u;
+      if (c.init_scale != 0.0f) {
+        const float lo = init_value(key, c.seed, 2 * w, c.init_scale);
+        const float hi = init_value(key, c.seed, 2 * w + 1, c.init_scale);
+        word = bf16 ? bf16_nearest(lo) | (bf16_nearest(hi) << 16) : fp16_nearest(lo) | (fp16_nearest(hi) << 16);
+      }
+      row[w] = word;
+    }
+  } else {
+    float* row = c.table + slot * c.pitch;
+    for (int j = sub; j < c.dim; j += gsize) {
+      row[j] = c.init_scale == 0.0f ? 0.0f : init_value(key, c.seed, j, c.init_scale);
+    }
+  }
+}
+
 constexpr int32_t kFreqCeiling = 1 << 30;   // of freq and of the sketch's counters
 constexpr int64_t kPending = -2;            // slots[i] between the two phases of an admitting call: not resolved yet
 
@@ -290,9 +335,10 @@ __device__ inline long long read_slot(const long long* p) {
 // an admitting call -- 1 = the find walk, the sketch adds of its misses, kPending into their slots; 2 = the
 // find-or-insert of the pending occurrences whose estimate reaches min_freq, -1 for the others.  Everything the
 // phases add is behind `if constexpr`: the PHASE 0 instantiations are the kernels they were.
-template <bool INSERT, int PHASE = 0, class Args = HashArgs>
+template <bool INSERT, int PHASE = 0, class Args = HashArgs, bool LOWP = false>
 __global__ __launch_bounds__(kBlock) void hash_insert_kernel(const Args args) {
   static_assert(PHASE == 0 || INSERT == (PHASE == 2), "phase 1 finds, phase 2 inserts");
+  static_assert(INSERT || !LOWP, "only an inserting launch writes rows: a find of a 16-bit table is the fp32 find");
   constexpr bool kSeq = IsSeq<Args>::value;
   const HashArgs& a = hash_args(args);
   const int b = (int)blockIdx.x;
@@ -301,7 +347,7 @@ __global__ __launch_bounds__(kBlock) void hash_insert_kernel(const Args args) {
   const HashCol& c = a.col[ci];
   const int lane = lane_id();
   const int wave = (int)(threadIdx.x >> 6);
-  const int group_log2 = c.group_log2;
+  const int group_log2 = lane_group_log2<LOWP>(c);
   const int gsize = 1 << group_log2;
   const int sub = lane & (gsize - 1);
   const int grp = lane >> group_log2;
@@ -421,12 +467,7 @@ __global__ __launch_bounds__(kBlock) void hash_insert_kernel(const Args args) {
       rk = 0;
       if (active && in_slab) rk = read_slot<INSERT>(cache + slab[u] * slab_size + sub);
     }
-    if (INSERT && won && c.table != nullptr) {
-      float* row = c.table + result * c.pitch;
-      for (int j = sub; j < c.dim; j += gsize) {
-        row[j] = c.init_scale == 0.0f ? 0.0f : init_value(key[u], c.seed, j, c.init_scale);
-      }
-    }
+    if (INSERT && won && c.table != nullptr) init_row<LOWP>(c, key[u], result, sub, gsize);
     if constexpr (PHASE == 1) {
       // not found and not the sentinel (which stays -1, counted as failed): counted, decided in phase 2
       if (result < 0 && key[u] != kEmptyKey) {
@@ -495,9 +536,10 @@ __device__ inline const ExpiringArgs& expiring_args(const ExpiringAdmitArgs& x) 
 // The sibling of hash_insert_kernel for expiring tables: same lane mapping and first reads, the placement
 // rule with tombstones of the header comment.  PHASE as in hash_insert_kernel (Args = ExpiringAdmitArgs for 1 and
 // 2); the metadata of an occurrence is written by the phase that resolved it to a slot.
-template <bool INSERT, int PHASE = 0, class Args = ExpiringArgs>
+template <bool INSERT, int PHASE = 0, class Args = ExpiringArgs, bool LOWP = false>
 __global__ __launch_bounds__(kBlock) void hash_insert_expiring_kernel(const Args args) {
   static_assert(PHASE == 0 || INSERT == (PHASE == 2), "phase 1 finds, phase 2 inserts");
+  static_assert(INSERT || !LOWP, "only an inserting launch writes rows: a find of a 16-bit table is the fp32 find");
   constexpr bool kMetadata = INSERT || PHASE == 1;
   constexpr bool kSeq = IsSeq<Args>::value;
   const ExpiringArgs& x = expiring_args(args);
@@ -509,7 +551,7 @@ __global__ __launch_bounds__(kBlock) void hash_insert_expiring_kernel(const Args
   const ExpiryCol& e = x.e[ci];
   const int lane = lane_id();
   const int wave = (int)(threadIdx.x >> 6);
-  const int group_log2 = c.group_log2;
+  const int group_log2 = lane_group_log2<LOWP>(c);
   const int gsize = 1 << group_log2;
   const int sub = lane & (gsize - 1);
   const int grp = lane >> group_log2;
@@ -645,12 +687,7 @@ __global__ __launch_bounds__(kBlock) void hash_insert_expiring_kernel(const Args
       rk = 0;
       if (active && in_slab) rk = read_slot<INSERT>(cache + slab * slab_size + sub);
     }
-    if (INSERT && won && c.table != nullptr) {
-      float* row = c.table + result * c.pitch;
-      for (int j = sub; j < c.dim; j += gsize) {
-        row[j] = c.init_scale == 0.0f ? 0.0f : init_value(key[u], c.seed, j, c.init_scale);
-      }
-    }
+    if (INSERT && won && c.table != nullptr) init_row<LOWP>(c, key[u], result, sub, gsize);
     if constexpr (PHASE == 1) {
       // not found and not a sentinel (which stays -1, counted as failed): counted, decided in phase 2
       if (result < 0 && key[u] != kEmptyKey) {
@@ -746,8 +783,9 @@ int check_column(const char* who, int32_t c, const hbk_hash_column_t& h) {
   return HBK_OK;
 }
 
-// the kernel's view of one column; returns its tiles
-int64_t describe_column(const hbk_hash_column_t& h, int32_t insert, HashCol* out) {
+// the kernel's view of one column; returns its tiles.  elem: 0, or the element code of a 16-bit table for a LOWP
+// kernel (which alone looks at it)
+int64_t describe_column(const hbk_hash_column_t& h, int32_t insert, HashCol* out, int32_t elem = 0) {
   HashCol& d = *out;
   d.cache = reinterpret_cast<long long*>(h.keys_cache);
   d.keys = h.keys;
@@ -762,8 +800,9 @@ int64_t describe_column(const hbk_hash_column_t& h, int32_t insert, HashCol* out
   d.init_scale = h.init_scale;
   d.slab_size = h.slab_size;
   d.dim = h.dim;
-  d.group_log2 = pow2_log2(h.slab_size);
-  const int64_t keys_per_block = (int64_t)(kBlock >> d.group_log2) * kKeys;
+  const int32_t group_log2 = pow2_log2(h.slab_size);
+  d.group_log2 = group_log2 | (elem << kElemShift);
+  const int64_t keys_per_block = (int64_t)(kBlock >> group_log2) * kKeys;
   return (h.n_keys + keys_per_block - 1) / keys_per_block;
 }
 
@@ -1138,6 +1177,112 @@ extern "C" int hbk_hash_translate_runs_n(int32_t n_cols, const hbk_hash_column_t
                                insert != 0 ? hash_insert_kernel<true, 0, RunsArgs<HashArgs>>
                                            : hash_insert_kernel<false, 0, RunsArgs<HashArgs>>,
                                stream);
+}
+
+// ---- 16-bit tables --------------------------------------------------------------------------------------
+namespace hbk {
+namespace {
+
+// One pass over all columns with `kernel`, 64 columns with keys per launch: the loop of the four entries above, for
+// any kind of arguments.  dtypes: the element codes for a LOWP kernel, or NULL for a kernel that writes no row (the
+// counting phase of a filtered table).
+template <class Base>
+int launch_columns(const char* who, int32_t n_cols, const hbk_hash_column_t* cols, const hbk_hash_expiry_t* exp,
+                   const hbk_hash_admission_t* adm, const int32_t* dtypes, int32_t insert,
+                   void (*kernel)(const Base), hipStream_t stream) {
+  int32_t c0 = 0;
+  while (c0 < n_cols) {
+    Base args;
+    HashArgs& h = hash_part(args);
+    int32_t k = 0;
+    int64_t tiles = 0;
+    h.tile_start[0] = 0;
+    while (c0 < n_cols && k < kMaxColsPerLaunch) {
+      const int32_t c = c0++;
+      if (cols[c].n_keys == 0) continue;
+      tiles += describe_column(cols[c], insert, &h.col[k], dtypes != nullptr ? dtypes[c] : 0);
+      HBK_REQUIRE(tiles < (1ll << 31), "%s: grid too large", who);
+      if (ExpiryCol* e = expiry_part(args)) describe_expiry(exp[c], e + k);
+      if (AdmitCol* f = admit_part(args)) describe_admission(adm[c], f + k);
+      ++k;
+      h.tile_start[k] = (int32_t)tiles;
+    }
+    if (k == 0) continue;
+    h.n_cols = k;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)tiles), dim3(kBlock), 0, stream, args);
+    HBK_HIP_OK(hipGetLastError());
+  }
+  return HBK_OK;
+}
+
+}  // namespace
+}  // namespace hbk
+
+extern "C" int hbk_hash_insert_lowp_n(int32_t n_cols, const hbk_hash_column_t* cols, const hbk_hash_expiry_t* exp,
+                                      const hbk_hash_admission_t* adm, const int32_t* table_dtypes, int32_t insert,
+                                      hbk_stream_t stream_) {
+  using namespace hbk;
+  const char* who = "hash_insert_lowp_n";
+  HBK_REQUIRE(n_cols >= 0, "%s: n_cols must be >= 0, got %d", who, n_cols);
+  if (n_cols == 0) return HBK_OK;
+  HBK_REQUIRE(cols != nullptr, "%s: cols is NULL", who);
+  HBK_REQUIRE(table_dtypes != nullptr, "%s: table_dtypes is NULL", who);
+  for (int32_t c = 0; c < n_cols; ++c) {
+    const hbk_hash_column_t& h = cols[c];
+    if (int rc = check_column(who, c, h)) return rc;
+    if (exp != nullptr) {
+      HBK_REQUIRE(h.n_keys < (1ll << 30), "%s: column %d: n_keys must be below 2^30 (freq must not wrap), got %lld",
+                  who, c, (long long)h.n_keys);
+      HBK_REQUIRE(h.n_keys == 0 || (exp[c].last_seen != nullptr && exp[c].freq != nullptr && exp[c].step != nullptr),
+                  "%s: column %d: NULL expiry buffer (last_seen, freq and step are needed with n_keys > 0)", who, c);
+    }
+    if (adm != nullptr) {
+      if (int rc = check_admission(who, c, h, adm[c])) return rc;
+    }
+    const int32_t code = table_dtypes[c];
+    HBK_REQUIRE(code == HBK_LOWP_BF16 || code == HBK_LOWP_FP16,
+                "%s: column %d: table_dtypes must be HBK_LOWP_BF16 (%d) or HBK_LOWP_FP16 (%d), got %d", who, c,
+                HBK_LOWP_BF16, HBK_LOWP_FP16, code);
+    if (h.table != nullptr) {
+      HBK_REQUIRE((h.dim & 1) == 0, "%s: column %d: dim must be even on a 16-bit table (rows are written as 4-byte "
+                  "words), got %d", who, c, h.dim);
+      HBK_REQUIRE((h.table_pitch & 1) == 0, "%s: column %d: table_pitch must be even on a 16-bit table, got %d", who, c,
+                  h.table_pitch);
+      HBK_REQUIRE(((uintptr_t)h.table & 3) == 0, "%s: column %d: table must be 4-byte aligned", who, c);
+    }
+    HBK_REQUIRE(code != HBK_LOWP_FP16 || h.init_scale <= 65504.0f,
+                "%s: column %d: init_scale %g is above 65504, the largest fp16: a start value would round to infinity",
+                who, c, (double)h.init_scale);
+  }
+  if (insert == 0) {
+    // a find writes no row and touches no sketch: the find of the fp32 entry, as it is
+    return exp != nullptr ? hbk_hash_insert_expiring_n(n_cols, cols, exp, 0, stream_)
+                          : hbk_hash_insert_n(n_cols, cols, 0, stream_);
+  }
+  hipStream_t stream = as_stream(stream_);
+  if (adm != nullptr) {   // count (no row is written: the fp32 kernel), then admit
+    if (exp != nullptr) {
+      if (int rc = launch_columns<ExpiringAdmitArgs>(
+              who, n_cols, cols, exp, adm, nullptr, insert, hash_insert_expiring_kernel<false, 1, ExpiringAdmitArgs>,
+              stream)) {
+        return rc;
+      }
+      return launch_columns<ExpiringAdmitArgs>(who, n_cols, cols, exp, adm, table_dtypes, insert,
+                                               hash_insert_expiring_kernel<true, 2, ExpiringAdmitArgs, true>, stream);
+    }
+    if (int rc = launch_columns<AdmitArgs>(who, n_cols, cols, nullptr, adm, nullptr, insert,
+                                           hash_insert_kernel<false, 1, AdmitArgs>, stream)) {
+      return rc;
+    }
+    return launch_columns<AdmitArgs>(who, n_cols, cols, nullptr, adm, table_dtypes, insert,
+                                     hash_insert_kernel<true, 2, AdmitArgs, true>, stream);
+  }
+  if (exp != nullptr) {
+    return launch_columns<ExpiringArgs>(who, n_cols, cols, exp, nullptr, table_dtypes, insert,
+                                        hash_insert_expiring_kernel<true, 0, ExpiringArgs, true>, stream);
+  }
+  return launch_columns<HashArgs>(who, n_cols, cols, nullptr, nullptr, table_dtypes, insert,
+                                  hash_insert_kernel<true, 0, HashArgs, true>, stream);
 }
 
 // ---- keys that arrive as ragged sequences ---------------------------------------------------------------

@@ -345,7 +345,9 @@ int lowp_lookup_fwd(const char* kWho, int32_t n_cols, const HostCol* cols_, hbk_
   struct Classified {
     int w;      // 0: nothing to do (no segments)
     int chunks, lpr_log2;
+    int blocks;   // 1, or (wide_rows) the column blocks of kWideBlock elements a wide row is served in
   };
+  constexpr int kWideBlock = 64;   // one element per lane: a lane group holds at most a wave
   std::vector<Classified> cls((size_t)std::max(n_cols, 1));
   for (int32_t c = 0; c < n_cols; ++c) {
     const hbk_lowp_lookup_column_t& h = cols(c);
@@ -363,6 +365,8 @@ int lowp_lookup_fwd(const char* kWho, int32_t n_cols, const HostCol* cols_, hbk_
                 "%s: column %d: unknown combiner %d", kWho, c, h.combiner);
     HBK_REQUIRE(h.chunk_elems == 0 || h.chunk_elems == 4 || h.chunk_elems == 8,
                 "%s: column %d: chunk_elems must be 0, 4 or 8, got %d", kWho, c, h.chunk_elems);
+    HBK_REQUIRE(h.wide_rows == 0 || h.wide_rows == 1, "%s: column %d: wide_rows must be 0 or 1, got %d", kWho, c,
+                h.wide_rows);
     HBK_REQUIRE(h.row_splits != nullptr || h.n_segments == h.n_ids,
                 "%s: column %d: n_segments (%lld) must equal n_ids (%lld) when row_splits is NULL", kWho, c,
                 (long long)h.n_segments, (long long)h.n_ids);
@@ -387,12 +391,16 @@ int lowp_lookup_fwd(const char* kWho, int32_t n_cols, const HostCol* cols_, hbk_
     // hbk_sharded_layout --, so 8 elements per lane are taken there when the caller asks: chunk_elems = 8)
     const bool want8 = h.chunk_elems == 8 || (!kRuns && h.chunk_elems == 0 && h.dim >= 64);
     if (vec && want8 && h.dim % 8 == 0 && (uintptr_t)h.table % 16 == 0) w = 8;
-    HBK_REQUIRE(h.dim <= (vec ? 256 : 64),
+    // wide_rows: a row of one element per lane wider than a wave goes in column blocks of kWideBlock elements, each a
+    // column of its own to the kernel (per-element sums are independent: no bit depends on the split)
+    const bool wide = h.wide_rows != 0 && !vec && h.dim > kWideBlock;
+    HBK_REQUIRE(h.dim <= (vec || wide ? 256 : 64),
                 "%s: column %d: dim %d: at most 256 when dim %% 4 == 0, the table is 8-byte aligned and out and its "
                 "stride are 16-byte aligned, 64 otherwise", kWho, c, h.dim);
     cls[(size_t)c].w = w;
     cls[(size_t)c].chunks = h.dim / w;
     cls[(size_t)c].lpr_log2 = ceil_log2_u32((uint32_t)(h.dim / w));
+    cls[(size_t)c].blocks = wide ? (h.dim + kWideBlock - 1) / kWideBlock : 1;
   }
   hipStream_t stream = as_stream(stream_);
   static const int kWidths[3] = {4, 8, 1};
@@ -405,31 +413,42 @@ int lowp_lookup_fwd(const char* kWho, int32_t n_cols, const HostCol* cols_, hbk_
         int64_t tiles = 0;
         args.tile_start[0] = 0;
         while (c0 < n_cols && k < kFwdMaxCols) {
-          const int32_t ci = c0++;
+          const int32_t ci = c0;
           const hbk_lowp_lookup_column_t& h = cols(ci);
-          if (cls[(size_t)ci].w != w || (h.row_splits != nullptr) != (csr != 0)) continue;
-          auto& d = args.col[k];
-          set_runs(d, cols_[ci]);
-          d.table = static_cast<const uint16_t*>(h.table);
-          d.ids = h.ids;
-          d.splits = h.row_splits;
-          d.weights = h.id_weights;
-          d.out = h.out;
-          d.n_seg = h.n_segments;
-          d.map = make_idmap(h.bucket, h.divisor, h.rows);
-          d.dim = h.dim;
-          d.chunks = cls[(size_t)ci].chunks;
-          d.out_stride = h.out_stride > 0 ? h.out_stride : h.dim;
-          d.lpr_log2 = (uint8_t)cls[(size_t)ci].lpr_log2;
-          d.ids64 = h.ids_dtype == HBK_INT64;
-          d.combiner = (uint8_t)h.combiner;
-          d.bf16 = h.table_dtype == HBK_LOWP_BF16;
-          const int64_t rpi = kWave >> d.lpr_log2;
-          const int64_t per_block = kFwdWaves * rpi * (csr ? kFwdSegIters : kFwdU);
-          tiles += (h.n_segments + per_block - 1) / per_block;
-          HBK_REQUIRE(tiles < (1ll << 31), "%s: grid too large", kWho);
-          ++k;
-          args.tile_start[k] = (int32_t)tiles;
+          if (cls[(size_t)ci].w != w || (h.row_splits != nullptr) != (csr != 0)) {
+            ++c0;
+            continue;
+          }
+          const int blocks = cls[(size_t)ci].blocks;   // (at most 4: they fit an empty launch)
+          if (k + blocks > kFwdMaxCols) break;          // the next launch takes the column whole
+          ++c0;
+          for (int b = 0; b < blocks; ++b) {
+            // block b: elements [b * kWideBlock, ...) of every row and of every output row; d.dim stays the pitch
+            const int first = b * kWideBlock;
+            const int chunks = blocks == 1 ? cls[(size_t)ci].chunks : std::min(kWideBlock, h.dim - first);
+            auto& d = args.col[k];
+            set_runs(d, cols_[ci]);
+            d.table = static_cast<const uint16_t*>(h.table) + first;
+            d.ids = h.ids;
+            d.splits = h.row_splits;
+            d.weights = h.id_weights;
+            d.out = h.out + first;
+            d.n_seg = h.n_segments;
+            d.map = make_idmap(h.bucket, h.divisor, h.rows);
+            d.dim = h.dim;
+            d.chunks = chunks;
+            d.out_stride = h.out_stride > 0 ? h.out_stride : h.dim;
+            d.lpr_log2 = (uint8_t)(blocks == 1 ? cls[(size_t)ci].lpr_log2 : (int)ceil_log2_u32((uint32_t)chunks));
+            d.ids64 = h.ids_dtype == HBK_INT64;
+            d.combiner = (uint8_t)h.combiner;
+            d.bf16 = h.table_dtype == HBK_LOWP_BF16;
+            const int64_t rpi = kWave >> d.lpr_log2;
+            const int64_t per_block = kFwdWaves * rpi * (csr ? kFwdSegIters : kFwdU);
+            tiles += (h.n_segments + per_block - 1) / per_block;
+            HBK_REQUIRE(tiles < (1ll << 31), "%s: grid too large", kWho);
+            ++k;
+            args.tile_start[k] = (int32_t)tiles;
+          }
         }
         if (k == 0) continue;
         args.n_cols = k;

@@ -35,6 +35,7 @@ from hybridbackend_amd.embedding.hashtable import _missing
 from hybridbackend_amd.embedding.hashtable import hash_fault_in
 from hybridbackend_amd.embedding.hashtable import check_bound
 from hybridbackend_amd.embedding.hashtable import check_current
+from hybridbackend_amd.embedding.hashtable import require_fp32_tables
 from hybridbackend_amd.embedding.hashtable import check_ids
 from hybridbackend_amd.embedding.hashtable import evict_tables
 from hybridbackend_amd.embedding.hashtable import grow_tables
@@ -47,6 +48,10 @@ from hybridbackend_amd.embedding.sequence import per_column
 
 def _bad(msg):
   return _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT, msg)
+
+
+_FP32_ONLY = ('hbk_hash_translate_sequence_n writes new rows, and the sequence gather reads them, as fp32 rows of '
+              '4 * dim bytes: hash-keyed sequence lookups take fp32 tables (HashGroupLookup serves 16-bit ones)')
 
 
 def check_hash_sequence_args(tables, max_lens, pad_ids):
@@ -157,6 +162,7 @@ def hash_translate_sequence(tables, ids, row_splits=None, max_lens=None, pad_ids
   on the effective id list (per sample its first ``min(len, T)`` ids, then the pad ids) would change them."""
   tables, ids = list(tables), list(ids)
   same_device(tables)
+  require_fp32_tables(tables, 'hash_translate_sequence', _FP32_ONLY)
   max_lens, pad_ids = check_hash_sequence_args(tables, max_lens, pad_ids)
   plan = _SeqPlan(tables)
   grids, lengths, _ = _bind(plan, tables, ids, row_splits, max_lens, pad_ids, insert, outs)
@@ -208,6 +214,7 @@ class HashSequenceLookup:
   def __init__(self, tables, max_lens, pad_ids=None, max_norms=None, train=True):
     self.hash_tables = list(tables)
     same_device(self.hash_tables)
+    require_fp32_tables(self.hash_tables, 'HashSequenceLookup', _FP32_ONLY)
     self.max_lens, self.pad_ids = check_hash_sequence_args(self.hash_tables, max_lens, pad_ids)
     self.max_norms = max_norm_list(max_norms, len(self.hash_tables))
     self.train = bool(train)

@@ -58,7 +58,12 @@ with rows, ``last_seen``, ``freq`` and the optimizer slots into a :class:`HashEx
 :meth:`HashTable.import_items` upserts one into a table of any geometry or, with ``world`` / ``rank``, onto any
 number of ranks.  ``items()`` / ``load()`` / ``load_owned()`` / ``variables()`` are what they were.
 
-Not provided: growth from inside a translate launch (a full table answers -1 until ``maybe_grow`` ran), a
+16-bit rows (``HashTable(..., dtype=torch.bfloat16 / torch.float16)``; ``hbk_hash_insert_lowp_n``): the inserting
+launch rounds a new row to the table's 16 bits, every move carries rows as 4-byte words whatever they hold, and
+:class:`HashGroupLookup` puts a ``LowpGroupLookup`` behind the translate; ``LowpLookupGrad`` is the step.
+
+Not provided: 16-bit tables behind sequence lookups, sharded tables and the feature columns; growth from inside a
+translate launch (a full table answers -1 until ``maybe_grow`` ran), a
 compaction that keeps the tensors' addresses, the TF shim op.  (As feature columns: ``feature_column.
 HashEmbeddingColumn`` / ``HashSequenceEmbeddingColumn``.)
 """
@@ -73,6 +78,7 @@ from hybridbackend_amd.embedding.cache import EMPTY_KEY
 from hybridbackend_amd.embedding.lookup import GroupLookup
 
 TOMBSTONE_KEY = EMPTY_KEY + 1   # expiring tables only: a slot the eviction sweep took back
+LOWP_DTYPES = {torch.bfloat16: _lib.LOWP_BF16, torch.float16: _lib.LOWP_FP16}   # HashTable(dtype=): 16-bit rows
 
 
 def _bad(msg):
@@ -128,6 +134,13 @@ class HashTable:
     sketch_depth / sketch_width / sketch_seed: the count-min sketch, ``depth`` rows (1..8) of ``width`` int32
       counters (None: ``capacity``); an id's cell in row r is ``sketch_cells``'s.  Collisions only add: an id
       may be admitted early, never late.
+    dtype: ``torch.float32`` -- nothing changes -- or ``torch.bfloat16`` / ``torch.float16``: ``table`` holds
+      16-bit rows (``dim`` even; fp16: ``init_scale <= 65504``), a new row is the fp32 start value rounded to
+      nearest even by the inserting launch (``hbk_hash_insert_lowp_n``), and every row-carrying call -- ``items``,
+      ``load``, ``export_items`` / ``import_items``, the spill store, ``variables`` -- carries rows of this dtype
+      bit for bit and refuses another.  The metadata and the companions (optimizer slots) stay what they were,
+      fp32.  Look up through :class:`HashGroupLookup`, step with ``LowpLookupGrad``; sequence lookups, sharded
+      tables and the feature-column layers take fp32 tables only.
 
   Attributes of a filtered table: ``sketch`` int32 ``[depth, width]``, ``filter_counts`` int32 ``[1]`` = id
   occurrences the filter answered -1.  The sketch is never decremented, so an id evicted from an expiring table
@@ -138,13 +151,13 @@ class HashTable:
   fade), ``step`` int32 ``[1]`` on the device (:meth:`set_step`), ``stats`` int32 ``[2]`` = keys evicted / keys
   stored into a reused slot.
 
-  Attributes: ``keys`` int64 ``[slab_count * slab_size]`` (EMPTY = INT64_MIN), ``table`` fp32
+  Attributes: ``keys`` int64 ``[slab_count * slab_size]`` (EMPTY = INT64_MIN), ``table`` ``dtype``
   ``[capacity, dim]``, ``counts`` int32 ``[2]`` = keys inserted (since the last rehash or compact: the keys it
   moved count as inserted) / id occurrences answered -1 by inserting calls (table full, or a sentinel id) so far.
   """
 
   def __init__(self, capacity, dim, device, slab_size=8, init_scale=1e-3, seed=0, expiring=False, min_freq=0,
-               sketch_depth=4, sketch_width=None, sketch_seed=0):
+               sketch_depth=4, sketch_width=None, sketch_seed=0, dtype=torch.float32):
     slab_size, capacity, dim = int(slab_size), int(capacity), int(dim)
     _check_geometry(capacity, slab_size)
     if dim < 1:
@@ -152,6 +165,14 @@ class HashTable:
     init_scale = float(init_scale)
     if not math.isfinite(init_scale) or init_scale < 0 or not math.isfinite(C.c_float(init_scale).value):
       raise _bad(f'init_scale must be finite and >= 0, got {init_scale!r}')
+    if dtype != torch.float32 and dtype not in LOWP_DTYPES:
+      raise _bad(f'dtype must be torch.float32, torch.bfloat16 or torch.float16, got {dtype!r}')
+    if dtype in LOWP_DTYPES and dim % 2:
+      raise _bad(f'dim must be even on a {dtype} table (a 16-bit row is written and moved as 4-byte words), got {dim}')
+    if dtype == torch.float16 and init_scale > 65504.0:
+      raise _bad(f'init_scale {init_scale!r} is above 65504, the largest torch.float16: a start value would round to '
+                 'infinity')
+    self.dtype = dtype
     self.slab_size = slab_size
     self.slab_count = capacity // slab_size
     self.capacity = self.slab_count * slab_size
@@ -160,7 +181,7 @@ class HashTable:
     self.seed = int(seed)
     self.device = torch.device(device)
     self.keys = torch.full((self.capacity,), EMPTY_KEY, dtype=torch.int64, device=self.device)
-    self.table = torch.zeros((self.capacity, dim), dtype=torch.float32, device=self.device)
+    self.table = torch.zeros((self.capacity, dim), dtype=dtype, device=self.device)
     self.counts = torch.zeros(2, dtype=torch.int32, device=self.device)
     self.expiring = bool(expiring)
     self._removals = None   # track_removals(): the keys that left, as device tensors
@@ -223,6 +244,13 @@ class HashTable:
     live = self.keys != EMPTY_KEY
     return live & (self.keys != TOMBSTONE_KEY) if self.expiring else live
 
+  def _check_rows_dtype(self, rows):
+    """The dtype check of :meth:`load` and :meth:`load_owned`, made before anything else is looked at: rows of
+    another dtype are refused, never cast."""
+    if isinstance(rows, torch.Tensor) and rows.dtype != self.dtype:
+      raise _bad(f'load: rows must be {_dtype_name(self.dtype)}, the table\'s own dtype (nothing is cast: a round '
+                 f'trip is bit-exact), got {rows.dtype}')
+
   def lookup_or_insert(self, ids):
     """Row number of every id, int64 ``[n]``; ids never seen are inserted and their rows initialised; -1
     where the table is full, for id == INT64_MIN and, on an expiring table, for id == INT64_MIN + 1 (these count
@@ -277,10 +305,10 @@ class HashTable:
     the keys go through the expiring insert, so a loaded key counts as seen now: ``last_seen`` = the current step
     and ``freq`` + 1, for keys the table already held as well (a key loaded with ``last_seen`` 0 would leave with
     the next sweep); ``items()`` does not carry the metadata of the table it came from."""
+    self._check_rows_dtype(rows)
     check_ids([keys], [self])
-    if rows.dtype != torch.float32 or tuple(rows.shape) != (keys.numel(), self.dim) or \
-        rows.device != self.table.device:
-      raise _bad(f'rows must be fp32 [{keys.numel()}, {self.dim}] on {self.table.device}')
+    if tuple(rows.shape) != (keys.numel(), self.dim) or rows.device != self.table.device:
+      raise _bad(f'rows must be {_dtype_name(self.dtype)} [{keys.numel()}, {self.dim}] on {self.table.device}')
     slots = _translate([self], [keys], True, None, init=False, plan=_Plan([self], admit=False))[0]
     ok = slots >= 0
     if not bool(ok.all().item()):
@@ -292,6 +320,7 @@ class HashTable:
     """:meth:`load` of the keys rank ``rank`` of ``world`` owns (:func:`hash_owner`) and their rows: handed the
     concatenated ``items()`` of W ranks on each of W' ranks, the tables are resharded.  Returns the slots of the
     keys loaded."""
+    self._check_rows_dtype(rows)   # (as load: before the ids are looked at; load sees the filtered rows)
     check_ids([keys], [self])
     mine = hash_owner(keys, world) == int(rank)
     return self.load(keys[mine], rows[mine])
@@ -626,8 +655,9 @@ class HashTable:
     n = exp.keys.numel()
     if exp.keys.dtype != torch.int64 or exp.keys.dim() != 1:
       raise _bad('import_items: exp.keys must be an int64 vector')
-    if exp.rows.dtype != torch.float32 or tuple(exp.rows.shape) != (n, self.dim):
-      raise _bad(f'import_items: exp.rows must be fp32 [{n}, {self.dim}], got {tuple(exp.rows.shape)}')
+    if exp.rows.dtype != self.dtype or tuple(exp.rows.shape) != (n, self.dim):
+      raise _bad(f'import_items: exp.rows must be {_dtype_name(self.dtype)} [{n}, {self.dim}], the table\'s own '
+                 f'dtype (nothing is cast), got {exp.rows.dtype} {tuple(exp.rows.shape)}')
     for k, (x, y) in enumerate(zip(exp.slots, dst_slots)):
       if x.dtype != torch.float32 or x.dim() != 2 or tuple(x.shape) != (n, y.shape[1]):
         raise _bad(f'import_items: exp.slots[{k}] must be fp32 [{n}, {y.shape[1]}], got {tuple(x.shape)}')
@@ -707,20 +737,35 @@ def _plain_companions(table, slots):
   return [t for t, _ in _companions(table, [(x, 0.0) for x in slots])]
 
 
+def _dtype_name(dtype):
+  return 'fp32' if dtype == torch.float32 else str(dtype)
+
+
+def _words(x, elements):
+  """``elements`` elements of ``x`` in 4-byte words: rows travel as words, bit for bit, whatever they hold (a 16-bit
+  row of even dim is dim / 2 words; its pitch is even too)."""
+  nbytes = elements * x.element_size()
+  if nbytes % 4:
+    raise _bad(f'a row of {elements} {x.dtype} elements is no whole number of 4-byte words')
+  return nbytes // 4
+
+
 def _describe_move(mv, per_slot, packed, to_packed):
-  """One hbk_hash_move_t between a per-slot array of a table and a packed array of an export."""
+  """One hbk_hash_move_t between a per-slot array of a table and a packed array of an export: a vector of 4-byte
+  elements, or a matrix of any element size described in 4-byte words."""
   src, dst = (per_slot, packed) if to_packed else (packed, per_slot)
   mv.src, mv.dst = src.data_ptr(), dst.data_ptr()
-  mv.words = 1 if per_slot.dim() == 1 else per_slot.shape[1]
-  mv.src_pitch = 1 if src.dim() == 1 else src.stride(0)
-  mv.dst_pitch = 1 if dst.dim() == 1 else dst.stride(0)
+  mv.words = 1 if per_slot.dim() == 1 else _words(per_slot, per_slot.shape[1])
+  mv.src_pitch = 1 if src.dim() == 1 else _words(src, src.stride(0))
+  mv.dst_pitch = 1 if dst.dim() == 1 else _words(dst, dst.stride(0))
 
 
 class HashExport:
   """What :meth:`HashTable.export_items` returns and :meth:`HashTable.import_items` takes: the keys of a table
   (all of them, or a delta) with everything that belongs to them, independent of the table's geometry.
 
-  Attributes: ``keys`` int64 ``[n]``; ``rows`` fp32 ``[n, dim]``; ``last_seen`` / ``freq`` int32 ``[n]`` (None
+  Attributes: ``keys`` int64 ``[n]``; ``rows`` ``[n, dim]`` in the table's dtype; ``last_seen`` / ``freq`` int32 ``[n]``
+  (None
   for a table that is not expiring); ``slots``: a list of fp32 ``[n, d]`` tensors, one per companion; ``src_slots``
   int64 ``[n]``: the slot every key had in the table it came from (ascending: the order of the export); ``since``:
   the ``since`` of the export, 0 for a full one; ``removed``: int64 ``[m]`` ascending, the keys that left the
@@ -771,12 +816,13 @@ class HashExport:
                d.get(base + 'removed'))
 
   @classmethod
-  def empty(cls, n, dim, expiring=False, slot_dims=(), device='cpu', n_removed=None):
+  def empty(cls, n, dim, expiring=False, slot_dims=(), device='cpu', n_removed=None, dtype=torch.float32):
     """An export of ``n`` zero keys: the tensors a ``Saver.restore`` of a saved export is read into.  ``n_removed``:
-    None, or the length of ``removed``."""
+    None, or the length of ``removed``.  ``dtype``: of ``rows``, the table's."""
     n = int(n)
     meta = [torch.zeros(n, dtype=torch.int32, device=device) for _ in range(2)] if expiring else [None, None]
-    return cls(torch.zeros(n, dtype=torch.int64, device=device), torch.zeros((n, int(dim)), device=device),
+    return cls(torch.zeros(n, dtype=torch.int64, device=device),
+               torch.zeros((n, int(dim)), dtype=dtype, device=device),
                meta[0], meta[1], [torch.zeros((n, int(d)), device=device) for d in slot_dims],
                torch.zeros(n, dtype=torch.int64, device=device), 0,
                None if n_removed is None else torch.zeros(int(n_removed), dtype=torch.int64, device=device))
@@ -847,7 +893,7 @@ def hash_export(tables, sinces=None, slots=None):
     rows = max(cap, 1)   # (never an empty allocation: a move needs an address)
     out = {'keys': torch.empty(rows, dtype=torch.int64, device=dev),
            'src_slots': torch.empty(rows, dtype=torch.int64, device=dev),
-           'rows': torch.empty((rows, t.dim), dtype=torch.float32, device=dev)}
+           'rows': torch.empty((rows, t.dim), dtype=t.dtype, device=dev)}
     moves = [(t.table, out['rows'])]
     if t.expiring:
       for name in ('last_seen', 'freq'):
@@ -949,7 +995,7 @@ def hash_rehash(tables, capacities=None, slab_sizes=None, slots=None):
     slab_count, slab_size = geometry[c]
     capacity, dev = slab_count * slab_size, t.keys.device
     new = {'keys': torch.full((capacity,), EMPTY_KEY, dtype=torch.int64, device=dev),
-           'table': torch.zeros((capacity, t.dim), dtype=torch.float32, device=dev)}
+           'table': torch.zeros((capacity, t.dim), dtype=t.dtype, device=dev)}
     moves = [(t.table, new['table'])]
     if t.expiring:
       for name in ('last_seen', 'freq'):
@@ -1186,7 +1232,7 @@ def hash_spill(tables, max_sizes, keep_freq=0, slots=None, order='lru'):
     rows = max(cap, 1)   # (never an empty allocation: a move needs an address)
     out = {'keys': torch.empty(rows, dtype=torch.int64, device=dev),
            'src_slots': torch.empty(rows, dtype=torch.int64, device=dev),
-           'rows': torch.empty((rows, t.dim), dtype=torch.float32, device=dev),
+           'rows': torch.empty((rows, t.dim), dtype=t.dtype, device=dev),
            'last_seen': torch.empty(rows, dtype=torch.int32, device=dev),
            'freq': torch.empty(rows, dtype=torch.int32, device=dev),
            'slots': [torch.empty((rows, x.shape[1]), dtype=torch.float32, device=dev) for x, _ in checked[c]]}
@@ -1291,6 +1337,9 @@ def _check_store(store, table, slots):
   if store.dim != table.dim or store.slot_dims != widths:
     raise _bad(f'the store holds rows of dim {store.dim} with companions of widths {list(store.slot_dims)}, the '
                f'table has dim {table.dim} and companions of widths {list(widths)}')
+  if store.dtype != table.dtype:
+    raise _bad(f'the store holds {_dtype_name(store.dtype)} rows, the table {_dtype_name(table.dtype)} rows: build '
+               'HashSpillStore(..., dtype=table.dtype) (nothing is cast)')
 
 
 class HashSpillStore:
@@ -1303,12 +1352,17 @@ class HashSpillStore:
     slot_dims: the widths of the companion tensors, in the order of the ``slots`` of ``spill_to`` / ``fault_in``.
     pin_memory: keep the arrays in page-locked memory when a GPU is present (copies from and to the device run
       at the link's speed).
+    dtype: of the table's rows (``HashTable(dtype=)``): the store keeps them as they are, bit for bit, and takes
+      no other.
 
   Everything is vectorised torch (sort, ``searchsorted``, masks): no per-key Python loop; the results are a
   function of the calls alone."""
 
-  def __init__(self, dim, slot_dims=(), pin_memory=True):
+  def __init__(self, dim, slot_dims=(), pin_memory=True, dtype=torch.float32):
     self.dim = int(dim)
+    if dtype != torch.float32 and dtype not in LOWP_DTYPES:
+      raise _bad(f'dtype must be torch.float32, torch.bfloat16 or torch.float16, got {dtype!r}')
+    self.dtype = dtype
     self.slot_dims = tuple(int(d) for d in slot_dims)
     if self.dim < 1 or any(d < 1 for d in self.slot_dims):
       raise _bad(f'dim and slot_dims must be >= 1, got {dim} and {list(slot_dims)}')
@@ -1317,7 +1371,7 @@ class HashSpillStore:
 
   def clear(self):
     """Forget everything."""
-    self._data = self._arrays(HashExport.empty(0, self.dim, True, self.slot_dims))
+    self._data = self._arrays(HashExport.empty(0, self.dim, True, self.slot_dims, dtype=self.dtype))
 
   @staticmethod
   def _arrays(exp):
@@ -1342,8 +1396,9 @@ class HashSpillStore:
     n = exp.keys.numel()
     if exp.keys.dtype != torch.int64 or exp.keys.dim() != 1:
       raise _bad('put: exp.keys must be an int64 vector')
-    if exp.rows.dtype != torch.float32 or tuple(exp.rows.shape) != (n, self.dim):
-      raise _bad(f'put: exp.rows must be fp32 [{n}, {self.dim}], got {tuple(exp.rows.shape)}')
+    if exp.rows.dtype != self.dtype or tuple(exp.rows.shape) != (n, self.dim):
+      raise _bad(f'put: exp.rows must be {_dtype_name(self.dtype)} [{n}, {self.dim}], the store\'s own dtype (nothing '
+                 f'is cast), got {exp.rows.dtype} {tuple(exp.rows.shape)}')
     if exp.last_seen is None or exp.freq is None:
       raise _bad('put: the export carries no last_seen / freq: a store keeps the keys of an expiring table')
     for name in ('last_seen', 'freq'):
@@ -1434,7 +1489,7 @@ class HashSpillStore:
     exp = HashExport.from_variables(name, d)
     if exp.rows.dim() != 2 or any(x.dim() != 2 for x in exp.slots):
       raise _bad('from_variables: rows and companions must be matrices')
-    store = cls(exp.rows.shape[1], [x.shape[1] for x in exp.slots], pin_memory)
+    store = cls(exp.rows.shape[1], [x.shape[1] for x in exp.slots], pin_memory, dtype=exp.rows.dtype)
     store.put(exp)
     return store
 
@@ -1614,15 +1669,18 @@ class _Plan:
   expiring ones' (with their expiry records) for ``hbk_hash_insert_expiring_n``, and the filtered tables of
   either kind (with their admission records) for ``hbk_hash_insert_admit_n`` /
   ``hbk_hash_insert_expiring_admit_n``.  ``cols[c]`` is table c's.  ``admit=False``: no table is taken as
-  filtered (:meth:`HashTable.load`)."""
+  filtered (:meth:`HashTable.load`).  The 16-bit tables of each kind form groups of their own, after the fp32
+  ones, and go through ``hbk_hash_insert_lowp_n``: ``dtypes[g]`` is group g's element codes, None for an fp32
+  group, whose calls are what they were."""
 
   def __init__(self, tables, admit=True):
     groups = {}
     for c, t in enumerate(tables):
-      groups.setdefault((t.expiring, bool(admit and t.min_freq)), []).append(c)
+      groups.setdefault((t.dtype in LOWP_DTYPES, t.expiring, bool(admit and t.min_freq)), []).append(c)
     self.cols = [None] * len(tables)
     self.groups = []   # (expiring, filtered, columns, expiry records, admission records)
-    for (expiring, filtered), members in sorted(groups.items()):
+    self.dtypes = []   # per group: None, or the int32 element codes of its 16-bit tables
+    for (lowp, expiring, filtered), members in sorted(groups.items()):
       cols = (_lib.HashColumn * len(members))()
       expiry = (_lib.HashExpiry * len(members))() if expiring else None
       adm = (_lib.HashAdmission * len(members))() if filtered else None
@@ -1633,15 +1691,19 @@ class _Plan:
         if filtered:
           tables[c]._describe_admission(adm[k])
       self.groups.append((expiring, filtered, cols, expiry, adm))
+      codes = [LOWP_DTYPES[tables[c].dtype] for c in members] if lowp else None
+      self.dtypes.append((C.c_int32 * len(members))(*codes) if lowp else None)
 
   def launch(self, insert, stream):
     insert = 1 if insert else 0
     lib = _lib.lib()
     if not self.groups:
       _lib.check(lib.hbk_hash_insert_n(0, None, insert, stream))
-    for expiring, filtered, cols, expiry, adm in self.groups:
+    for (expiring, filtered, cols, expiry, adm), dtypes in zip(self.groups, self.dtypes):
       n = len(cols)
-      if expiring and filtered:
+      if dtypes is not None:
+        _lib.check(lib.hbk_hash_insert_lowp_n(n, cols, expiry, adm, dtypes, insert, stream))
+      elif expiring and filtered:
         _lib.check(lib.hbk_hash_insert_expiring_admit_n(n, cols, expiry, adm, insert, stream))
       elif expiring:
         _lib.check(lib.hbk_hash_insert_expiring_n(n, cols, expiry, insert, stream))
@@ -1722,6 +1784,13 @@ def same_device(tables):
                  f'{tables[0].keys.device}')
 
 
+def require_fp32_tables(tables, what, why):
+  """Refuses, by name, a 16-bit :class:`HashTable` where only fp32 rows are served."""
+  for c, t in enumerate(tables):
+    if isinstance(t, HashTable) and t.dtype != torch.float32:
+      raise _bad(f'{what}: table {c} is a {t.dtype} HashTable; {why}')
+
+
 def check_current(tables, rows):
   """Refuses when ``rows``, the ``table`` tensors an object was built over, are no longer the tables' own."""
   if any(t.table is not r for t, r in zip(tables, rows)):
@@ -1771,6 +1840,19 @@ class HashGroupLookup:
 
   After a call ``self.slots`` holds the row numbers per column and ``self.lookup`` the GroupLookup:
   ``GroupLookupGrad(hgl.lookup, ...)(hgl.slots, grads, row_splits, ...)`` is the backward / optimizer step.
+
+  16-bit tables (``HashTable(..., dtype=torch.bfloat16 / torch.float16)``): all tables of one object are fp32 or all
+  are 16-bit -- a mix is refused; ``hash_translate`` takes all kinds in one call, the lookups are two groups.  Over
+  16-bit tables ``self.lookup`` is a :class:`hybridbackend_amd.embedding.LowpGroupLookup` with buckets 0 (a ``-1``
+  slot reads a zero row; ``max_norms`` is refused), and the step is ``LowpLookupGrad`` where it was
+  ``GroupLookupGrad``::
+
+      step = LowpLookupGrad(hgl.lookup, row_accums=accums, rounding='stochastic', seed=7)
+      step(hgl.slots, grads, row_splits, apply_lr=lr, optimizer='rowwise_adagrad')
+
+  rebuilt after a rehash exactly as a ``GroupLookupGrad`` is.  The optimizer slots stay fp32.  Never hand
+  ``hgl.lookup`` over 16-bit tables to a bare ``GroupLookupGrad`` with a non-zero ``apply_lr`` (see
+  ``LowpLookupGrad``).
   """
 
   def __init__(self, tables, combiners='sum', max_norms=None, train=True):
@@ -1786,8 +1868,19 @@ class HashGroupLookup:
     is dropped -- :meth:`launch` refuses until the next call, as on a fresh object.  Slot numbers and tensor
     addresses changed: a ``GroupLookupGrad`` built on the old ``hgl.lookup`` must be rebuilt with the new slot
     tensors (the companions the rehash returned), and a captured graph must be captured again."""
-    self.lookup = GroupLookup([t.table for t in self.tables], buckets=None, combiners=self._combiners,
-                              max_norms=self._max_norms)
+    lowp = [t.dtype in LOWP_DTYPES for t in self.tables]
+    if any(lowp) and not all(lowp):
+      mixed = ', '.join(f'table {c}: {_dtype_name(t.dtype)}' for c, t in enumerate(self.tables))
+      raise _bad(f'HashGroupLookup: fp32 and 16-bit tables cannot share one lookup ({mixed}): translate them together '
+                 'with hash_translate, then look them up in two groups -- or build one HashGroupLookup per kind')
+    if any(lowp):
+      # (a clip is refused there, by name: it reads and the clipped step writes fp32 rows)
+      from hybridbackend_amd.embedding.lowp import LowpGroupLookup   # pylint: disable=import-outside-toplevel
+      self.lookup = LowpGroupLookup([t.table for t in self.tables], buckets=None, combiners=self._combiners,
+                                    max_norms=self._max_norms, wide_rows=True)
+    else:
+      self.lookup = GroupLookup([t.table for t in self.tables], buckets=None, combiners=self._combiners,
+                                max_norms=self._max_norms)
     self._plan = _Plan(self.tables)
     self._rows = [t.table for t in self.tables]
     self.slots = None

@@ -66,13 +66,17 @@ class LowpGroupLookup(GroupLookup):
     chunk_elems: None (the default lane width: 8 from dim 64 on, else 4), 4 or 8: elements a lane moves where the
       column allows it (8: ``dim % 8 == 0`` and a 16-byte aligned table).  A pure speed choice: the result does not
       depend on it.
+    wide_rows: False -- a table whose rows cannot move 4 elements per lane (``dim % 4 != 0``, or an unaligned table or
+      output) is served up to dim 64, as ever.  True -- up to dim 256: the launch takes such a row in column blocks of
+      64 elements.  The forward only: the 16-bit apply keeps its bound.
 
   The calling convention is :class:`GroupLookup`'s -- ``bind``, ``__call__(ids, row_splits=None, outs=None,
   sp_weights=None)``, ``launch()``, outputs as column blocks of a wider tensor -- and the result is, bit for bit,
   ``GroupLookup`` over ``[t.float() for t in tables]`` with the same arguments.  ``max_norms`` and ``hot_rows`` do
   not exist here: a clip is refused, and the attributes a ``GroupLookupGrad`` reads of its lookup say "none"."""
 
-  def __init__(self, tables, buckets=None, combiners='sum', divisor=1, max_norms=None, chunk_elems=None):   # pylint: disable=super-init-not-called
+  def __init__(self, tables, buckets=None, combiners='sum', divisor=1, max_norms=None,   # pylint: disable=super-init-not-called
+               chunk_elems=None, wide_rows=False):
     if max_norms is not None and not (isinstance(max_norms, (list, tuple)) and all(x is None for x in max_norms)):
       raise _bad('LowpGroupLookup: max_norms is not supported for 16-bit tables (the clip reads and the clipped '
                  'step writes fp32 rows)')
@@ -106,6 +110,7 @@ class LowpGroupLookup(GroupLookup):
       col.divisor = self.divisor
       col.combiner = self.combiners[c]
       col.chunk_elems = chunk_elems or 0
+      col.wide_rows = 1 if wide_rows else 0
 
   def launch(self, stream=None):
     """Enqueue the bound lookup on `stream` (a torch stream; default: current)."""

@@ -81,6 +81,9 @@ class ShardedHashGroupLookup(ShardedGroupLookup):
                initial_accumulator_value=0.1, row_accums=None, rowwise_adagrad=None, stores=None):
     self.tables = list(tables)
     _ht.same_device(self.tables)
+    _ht.require_fp32_tables(self.tables, 'ShardedHashGroupLookup',
+                            'the owner-side translate, gather and step read and write fp32 rows of 4 * dim bytes: '
+                            'sharded hash tables are fp32 (HashGroupLookup serves 16-bit ones)')
     self.train = bool(train)
     self.initial_accumulator_value = float(initial_accumulator_value)
     self._rows = [t.table for t in self.tables]

@@ -651,12 +651,14 @@ int hbk_sparse_apply_slices_n(int32_t n_cols, const hbk_slices_column_t* cols, i
  *   Rows move as chunks of 4 elements (8 bytes) per lane -- or 8 elements (16 bytes) where dim % 8 == 0 and the
  *   table is 16-byte aligned: by default (chunk_elems = 0) from dim 64 on, with chunk_elems = 8 wherever possible,
  *   with chunk_elems = 4 never -- when dim % 4 == 0, the table is 8-byte aligned and `out` and its stride are
- *   16-byte aligned: dim <= 256.  Otherwise one element per lane: dim <= 64.
+ *   16-byte aligned: dim <= 256.  Otherwise one element per lane: dim <= 64 -- or, with wide_rows = 1 (the field
+ *   that was reserved; 0 changes nothing), dim <= 256 here too: such a row is served as column blocks of 64 elements,
+ *   each a column of its own to the kernel, 64 columns and blocks per launch; no bit depends on the split.
  *   One launch per 64 columns and kind (one id per segment / ragged), plain loads and stores, no atomics, no
  *   workspace, no host read: the call can be captured.  There is no max_norm, no segmented table, no output
  *   permutation and no fp16 output here.  Refused before the first launch (HBK_INVALID_ARGUMENT, the column
- *   named): an unknown table_dtype, ids_dtype or combiner; chunk_elems not 0, 4 or 8; dim < 1 or beyond the
- *   bounds above; a table at an odd address or an `out` not 4-byte aligned; a NULL table (rows > 0), ids
+ *   named): an unknown table_dtype, ids_dtype or combiner; chunk_elems not 0, 4 or 8; wide_rows not 0 or 1; dim < 1
+ *   or beyond the bounds above; a table at an odd address or an `out` not 4-byte aligned; a NULL table (rows > 0), ids
  *   (n_ids > 0) or out of a column with segments; negative sizes, >= 2^31 ids or segments; bucket < 0;
  *   divisor < 1; out_stride != 0 and < dim; n_segments != n_ids without row_splits.  n_cols == 0 answers OK. */
 #define HBK_LOWP_BF16 1
@@ -678,7 +680,7 @@ typedef struct {
   float* out;                /* device fp32 [n_segments, dim] */
   const float* id_weights;   /* device fp32 [n_ids] or NULL */
   int32_t chunk_elems;       /* 0 = the default (8 from dim 64 on, else 4); 4 or 8: elements per lane where the column allows it */
-  int32_t reserved;          /* 0 */
+  int32_t wide_rows;         /* 0; 1: one-element-per-lane rows up to dim 256, in blocks of 64 (the reserved word) */
 } hbk_lowp_lookup_column_t;
 int hbk_lowp_lookup_fwd(int32_t n_cols, const hbk_lowp_lookup_column_t* cols, hbk_stream_t stream);
 
@@ -1449,6 +1451,36 @@ int hbk_hash_insert_admit_n(int32_t n_cols, const hbk_hash_column_t* cols, const
 int hbk_hash_insert_expiring_admit_n(int32_t n_cols, const hbk_hash_column_t* cols,
                                      const hbk_hash_expiry_t* exp, const hbk_hash_admission_t* adm,
                                      int32_t insert, hbk_stream_t stream);
+
+/* Hash-keyed 16-bit tables: the translate entries over tables whose rows are bf16 / fp16 ("Low-precision
+ * tables" above).  exp / adm select the table kind for ALL columns of the call, as for hbk_hash_translate_runs_n
+ * below: (NULL, NULL) = hbk_hash_insert_n, (exp, NULL) = hbk_hash_insert_expiring_n,
+ * (NULL, adm) = hbk_hash_insert_admit_n, (exp, adm) = hbk_hash_insert_expiring_admit_n -- and the call IS that
+ * entry: placement, tombstone reuse,
+ * last_seen / freq, the sketch's two phases, the counters and insert == 0 are unchanged, the same kernels walk the
+ * slabs.  The one difference is the row the inserting call writes.  cols[c].table points at 2-byte elements of
+ * table_dtypes[c] (host int32 [n_cols], HBK_LOWP_BF16 or HBK_LOWP_FP16); dim and table_pitch count ELEMENTS;
+ *     row[j] = round_to_nearest_even(v_j),   v_j = the fp32 value of "Row initialisation" above
+ * with the rounding of the low-precision apply (bf16: the bits of a float32 -> bfloat16 cast; fp16: the hardware
+ * conversion); init_scale == 0 stores 0x0000.  A row depends on (key, seed, j, dtype) alone, never on the slot;
+ * there is no stochastic initialisation.  The winning lane group writes whole 4-byte words -- word w holds element
+ * 2w in its low and 2w + 1 in its high half -- so nothing outside [row, row + dim) is written and the padding up to
+ * table_pitch keeps what it held.  Every other per-slot array (rows moved by hbk_hash_rehash_n, hbk_hash_export_n,
+ * hbk_hash_store_rows_n, hbk_hash_spill_n) travels as 4-byte words already: a 16-bit row of even dim is dim / 2 of
+ * them.  The optimizer slots of such a table stay fp32.
+ *
+ * Refused (HBK_INVALID_ARGUMENT) before any device work, with the entry, the column and the field named: everything
+ * the matching fp32 entry refuses; NULL table_dtypes with n_cols > 0; a code other than HBK_LOWP_BF16 /
+ * HBK_LOWP_FP16; with a table: an odd dim, an odd non-zero table_pitch, a table that is not 4-byte aligned;
+ * HBK_LOWP_FP16 with init_scale > 65504 (a start value would round to infinity).  n_cols == 0 returns HBK_OK without
+ * touching a device.  No workspace, no host synchronisation: capturable.  Not served here: keys that arrive as runs
+ * or sequences (hbk_hash_translate_runs_n / hbk_hash_translate_sequence_n write fp32 rows).  Detected by the presence
+ * of the symbol; the structs and the version are those of 0.2.0. */
+int hbk_hash_insert_lowp_n(int32_t n_cols, const hbk_hash_column_t* cols,
+                           const hbk_hash_expiry_t* exp    /* NULL: plain tables */,
+                           const hbk_hash_admission_t* adm /* NULL: no filter */,
+                           const int32_t* table_dtypes     /* [n_cols]: HBK_LOWP_BF16 / HBK_LOWP_FP16 */,
+                           int32_t insert, hbk_stream_t stream);
 
 /* Keys that arrive as runs.  On the owner of a sharded hash table (hbk_sharded_set_hash_tables below) the ids of
  * one column are W separate arrays, one per requester, each with its own place for the answers.  Handing them
