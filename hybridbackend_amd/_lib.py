@@ -8,7 +8,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# (HBK_LIBRARY: another build of the same library -- the probe builds of tools/scratch/*.sh; the
+# (HBK_LIBRARY: another build of the same library -- the stamps library of tools/Makefile; the
 # default is the in-tree one, and either way a missing file is an ImportError, never a fallback)
 LIB_PATH = os.environ.get('HBK_LIBRARY') or os.path.join(_HERE, 'lib', 'libhbk_core.so')
 

@@ -76,10 +76,6 @@
 
 #include "lookup_common.h"
 
-#ifndef HBK_BWD_WAVES
-#define HBK_BWD_WAVES 4
-#endif
-
 namespace hbk {
 // det_prims.hip: the stable radix sort and the scan of the deterministic backward (rocPRIM)
 size_t det_sort_temp_bytes(size_t n, int end_bit);
@@ -94,73 +90,30 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kWavesPerBlock = kBlock / kWave;
 constexpr int kMaxCols = 64;
-#ifndef HBK_BWD_TILE
-#define HBK_BWD_TILE 2048
-#endif
-constexpr int kTile = HBK_BWD_TILE;  // ids per 256-thread block in hist / scatter (config 2
+constexpr int kReduceWaves = 4;      // workgroups per CU the hashed reduce and merge kernels are compiled for
+constexpr int kTile = 2048;          // ids per 256-thread block in hist / scatter (config 2
                                      // backward: 4096 149 us, 2048 139, 1024 145, 512 158)
 constexpr int kPerThread = kTile / kBlock;
 constexpr int kBatch = kPerThread < 8 ? kPerThread : 8;   // loads in flight per thread
 constexpr int kMaxBuckets = 16384;   // 64 KB of LDS counters in hist / scatter
-// The reduce stage works in TEAMS: kTeam threads own one bucket.  kTeam = 256 (shipped): a team
-// is the workgroup.  kTeam = 64 (-DHBK_BWD_TEAM=64): a team is ONE WAVE, a workgroup holds four
-// independent teams with their own LDS tables and there is no workgroup barrier anywhere in the
-// reduce kernel (lanes of a wave execute LDS instructions in lockstep: a fence that keeps the
-// compiler from reordering them is all the synchronisation a team needs), so a CU runs 16
-// independent chains of dependent memory round trips instead of 4.  Measured on the config-2
-// backward (profiles/r02_bwd_reduce_trace.txt): a wave-team job lives 17 us instead of 21 and the
-// reduce kernel takes the same ~95 us either way (jobs x life / resident teams + one life of
-// tail), while four times as many buckets cost the grouping kernels 19 us (scatter 26 -> 39, scan
-// 6 -> 12): 164 vs 142 us in total.
-#ifndef HBK_BWD_TEAM
-#define HBK_BWD_TEAM 256
-#endif
-constexpr int kTeam = HBK_BWD_TEAM;
-constexpr int kTeams = kBlock / kTeam;  // teams per workgroup
-constexpr int kCP = 2 * kTeam;        // pairs per chunk in the reduce kernel
-#ifndef HBK_BWD_RS_CAP
-#define HBK_BWD_RS_CAP 2048
-#endif
-constexpr int kRsCap = HBK_BWD_RS_CAP;   // pairs per chunk of the row-sorted reduce (4c, lookup_bwd_rowsort.h)
-#ifndef HBK_BWD_SLOTX
-#define HBK_BWD_SLOTX 2
-#endif
-constexpr int kSlots = HBK_BWD_SLOTX * kCP;   // LDS hash-table slots
-constexpr int kRoom = kSlots - kTeam - 8;   // rows enter the table while it holds fewer (a
-                                           // team's concurrent inserts overshoot by < kTeam)
-static_assert(kTeam == 64 || kTeam == kBlock, "a team is one wave or the whole workgroup");
-
-// all threads of a team have finished their LDS accesses before anyone goes on
-__device__ inline void team_sync() {
-  if (kTeam == kBlock) {
-    __syncthreads();
-  } else {
-    // one wave: the hardware runs its LDS instructions in order; keep the compiler from moving
-    // LDS accesses across this point and wait for the ones issued
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  }
-}
-#ifndef HBK_BWD_PRE
-#define HBK_BWD_PRE 3
-#endif
+// A reduce job (one bucket) belongs to the whole workgroup.  One-wave teams (four jobs per workgroup, no
+// barrier) were tried: config-2 backward 164 vs 142 us in total (profiles/r02_bwd_reduce_trace.txt).
+constexpr int kCP = 2 * kBlock;       // pairs per chunk in the reduce kernel
+constexpr int kRsCap = 2048;          // pairs per chunk of the row-sorted reduce (4c, lookup_bwd_rowsort.h)
+constexpr int kSlots = 2 * kCP;       // LDS hash-table slots
+constexpr int kRoom = kSlots - kBlock - 8;  // rows enter the table while it holds fewer (a
+                                            // workgroup's concurrent inserts overshoot by < kBlock)
 // gradient rows a lane keeps in flight: 2 x kPre without the optimizer step, kPre with it.  Four
 // (8 / 4 rows) made the kernels spill 64-188 bytes per lane of loop-invariant state: 63 MB of
 // scratch writes per config-2 launch (TCC_EA0_WRREQ_64B 2.85 M where the rows account for 1.86 M),
 // 117 us instead of 110.
-constexpr int kPre = HBK_BWD_PRE;
-#ifndef HBK_BWD_WIDE_W
-#define HBK_BWD_WIDE_W 5   // width of the WIDE walk (rows of >= 16 lanes, with the optimizer step).  2 x kPre = 6 spills
-                          // 28 VGPRs in the SGD instantiation, 5 spills 12: config 4 + SGD 423-428 -> 412-416 us, the
-                          // config-5 mix + SGD 3.39-3.60 -> 3.22-3.46 ms in-box (Adagrad the same)
-#endif
+constexpr int kPre = 3;
+constexpr int kWideW = 5;  // width of the WIDE walk (rows of >= 16 lanes, with the optimizer step).  2 x kPre = 6 spills
+                           // 28 VGPRs in the SGD instantiation, 5 spills 12: config 4 + SGD 423-428 -> 412-416 us, the
+                           // config-5 mix + SGD 3.39-3.60 -> 3.22-3.46 ms in-box (Adagrad the same)
 constexpr int kLdsRowPairs = kCP / 8; // multi-pair slots are summed in LDS rows when they hold at
                                       // most this many pairs together
-#ifndef HBK_BWD_HOT
-#define HBK_BWD_HOT 4
-#endif
-constexpr int kHotTries = HBK_BWD_HOT; // ballot rounds that look for a hot row inside a wave
+constexpr int kHotTries = 4;           // ballot rounds that look for a hot row inside a wave
 constexpr int kHotMin = 8;             // lanes sharing a row that make the wave reduce it first
 constexpr unsigned long long kEmptyKey = ~0ull;
 constexpr int64_t kDonePair = -1;      // a pair struck out of the pair buffer (rows are >= 0)
@@ -189,14 +142,10 @@ __device__ unsigned long long g_bwd_sub[kTraceBlocks * 4];   // sub-stamps insid
       g_bwd_trace[blockIdx.x * kTraceSlots + (i)] = __builtin_amdgcn_s_memrealtime();          \
     }                                                                                      \
   } while (0)
-#define HBK_STAMP_ARG
-#define HBK_STAMP_PASS
 #else
 #define HBK_SUBSTAMP(i)
 #define HBK_STAMP_BEGIN()
 #define HBK_STAMP(i)
-#define HBK_STAMP_ARG
-#define HBK_STAMP_PASS
 #endif
 
 struct GCol {
@@ -1199,10 +1148,10 @@ struct ReduceLds {
   uint16_t order[kCP];       // their pair indices grouped by slot
   uint16_t pslot[kCP];       // slot of every pair; kNoSlot: struck out earlier / left for a later pass
   uint16_t emitted[kSlots];  // slots of the rows this pass has emitted (jobs of several chunks)
-  int32_t wave_tot[kTeam / kWave];
+  int32_t wave_tot[kBlock / kWave];
   int32_t n_active, n_new, n_single, base_u, occupied, occupied_before, n_left, lds_rows,
       n_emitted, emit0, n_multi;
-  float red[kTeam * 4];      // partial sums handed between lane groups, one 16-byte chunk per thread
+  float red[kBlock * 4];      // partial sums handed between lane groups, one 16-byte chunk per thread
   float carry[2][kWave * 4]; // sum of the slot that runs on into the next round of the sorted walk
 };
 
@@ -1237,47 +1186,16 @@ struct ReduceJob {
 // dim 8), asked for by two different buckets a few microseconds apart, and a ragged column reads
 // every segment gradient ~8 times: with plain loads (and whole columns per XCD, xcd_contiguous)
 // config 2 100.5 -> 91.7 us, SGD step only 150 -> 131.5, ragged dim 16 / 64 + SGD 774 -> 704 /
-// 1367 -> 1269, over 10 M rows 1037 -> 901 (tools/scratch/bwd_cache_variants.sh, two visits each).
-// Write-through stores of the output rows (so that they do not push gradient lines out of L2)
-// change nothing (HBK_BWD_OUT_WT).  -DHBK_BWD_GRAD_NT=1 brings the hint back (probe builds).
-#ifndef HBK_BWD_GRAD_NT
-#define HBK_BWD_GRAD_NT 0
-#endif
-#if HBK_BWD_GRAD_NT
-#define HBK_GRAD_LOAD(P) __builtin_nontemporal_load(P)
-#else
-#define HBK_GRAD_LOAD(P) (*(P))
-#endif
-
-// the pairs of a bucket are read once (probe builds: -DHBK_BWD_PAIRS_NT=1 non-temporal loads)
-#ifndef HBK_BWD_PAIRS_NT
-#define HBK_BWD_PAIRS_NT 0
-#endif
-#if HBK_BWD_PAIRS_NT
-#define HBK_PAIR_LOAD(P) __builtin_nontemporal_load(P)
-#else
-#define HBK_PAIR_LOAD(P) (*(P))
-#endif
-
-// table / accumulator rows of the optimizer step (probe builds: -DHBK_BWD_STEP_NT=0 plain loads)
-#ifndef HBK_BWD_STEP_NT
-#define HBK_BWD_STEP_NT 1
-#endif
-#if HBK_BWD_STEP_NT
-#define HBK_STEP_LOAD(P) __builtin_nontemporal_load(P)
-#else
-#define HBK_STEP_LOAD(P) (*(P))
-#endif
+// 1367 -> 1269, over 10 M rows 1037 -> 901 (two visits each: profiles/HISTORY.md "Gradient loads: plain",
+// two more passes in profiles/r03_bwd_cache_variants.txt).  Write-through stores of the output rows (so
+// that they do not push gradient lines out of L2) changed nothing.  The pairs of a bucket are read once,
+// with plain loads too; the table / accumulator rows of the optimizer step with non-temporal ones.
 
 template <typename V>
 __device__ inline V load_grad(const GCol& c, const ReduceJob& job, int32_t seg, int sub) {
   constexpr int VE = sizeof(V) / 4;
   const int64_t off = job.seg_is_offset ? (int64_t)(uint32_t)seg : (int64_t)seg * job.stride;
-#ifdef HBK_BWD_ABLATE_LOADS   // probe builds: what the kernel costs without its gradient traffic
-  V g = zero_v<V>() + (float)(off & 7);
-#else
-  V g = HBK_GRAD_LOAD(reinterpret_cast<const V*>(job.grad + off + (int64_t)sub * VE));
-#endif
+  V g = *reinterpret_cast<const V*>(job.grad + off + (int64_t)sub * VE);
   if (job.scale && c.combiner != HBK_COMBINER_SUM && c.splits != nullptr) {
     const int32_t n = c.splits[seg + 1] - c.splits[seg];
     g = c.combiner == HBK_COMBINER_MEAN ? g / (float)n : g / sqrtf((float)n);
@@ -1292,11 +1210,7 @@ __device__ inline V load_grad_lds(const GCol& c, const ReduceJob& job, int32_t s
                                   bool scaled, int32_t n) {
   constexpr int VE = sizeof(V) / 4;
   const int64_t off = job.seg_is_offset ? (int64_t)(uint32_t)seg : (int64_t)seg * job.stride;
-#ifdef HBK_BWD_ABLATE_LOADS
-  V g = zero_v<V>() + (float)(off & 7);
-#else
-  V g = HBK_GRAD_LOAD(reinterpret_cast<const V*>(job.grad + off + (int64_t)sub * VE));
-#endif
+  V g = *reinterpret_cast<const V*>(job.grad + off + (int64_t)sub * VE);
   if (scaled) g = c.combiner == HBK_COMBINER_MEAN ? g / (float)n : g / sqrtf((float)n);
   return g;
 }
@@ -1309,7 +1223,7 @@ __device__ inline V load_grad_raw(const GCol& c, const ReduceJob& job, int32_t s
                                   int32_t* n) {
   constexpr int VE = sizeof(V) / 4;
   const int64_t off = job.seg_is_offset ? (int64_t)(uint32_t)seg : (int64_t)seg * job.stride;
-  const V g = HBK_GRAD_LOAD(reinterpret_cast<const V*>(job.grad + off + (int64_t)sub * VE));
+  const V g = *reinterpret_cast<const V*>(job.grad + off + (int64_t)sub * VE);
   *n = 0;
   if (job.scale && c.combiner != HBK_COMBINER_SUM && c.splits != nullptr) {
     *n = c.splits[seg + 1] - c.splits[seg];
@@ -1335,18 +1249,6 @@ __device__ inline f32x4 rsqrt_v<f32x4>(f32x4 a) {
   return f32x4{1.0f / sqrtf(a.x), 1.0f / sqrtf(a.y), 1.0f / sqrtf(a.z), 1.0f / sqrtf(a.w)};
 }
 
-// A row chunk stored write-through (sc0 sc1): the line does not stay in the XCD's L2 (probe builds,
-// -DHBK_BWD_OUT_WT=1: do the output rows push the gradient lines out of L2?)
-#ifndef HBK_BWD_OUT_WT
-#define HBK_BWD_OUT_WT 0
-#endif
-__device__ inline void store_wt(f32x4* p, f32x4 v) {
-  asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" : : "v"(p), "v"(v) : "memory");
-}
-__device__ inline void store_wt(float* p, float v) {
-  asm volatile("global_store_dword %0, %1, off sc0 sc1" : : "v"(p), "v"(v) : "memory");
-}
-
 // out row u += (or =) v.  A new row is 0 + v, not v: a row whose ONE pair is stored straight from the
 // registers it arrived in would otherwise keep a term of -0.0 (a zero gradient under a negative weight)
 // where the scatter-add into zeros -- and every plan that sums into a zeroed accumulator -- gives +0.0
@@ -1356,21 +1258,8 @@ __device__ inline void emit_row(const GCol& c, const ReduceJob& job, int32_t u, 
   constexpr int VE = sizeof(V) / 4;
   V* o = reinterpret_cast<V*>(job.out_vals + (int64_t)u * c.dim + (int64_t)sub * VE);
   if (is_new) v = v + 0.0f;
-#ifdef HBK_BWD_ABLATE_STORES   // probe builds: what the kernel costs without its output traffic
-  if (u == 0x7fffffff) *o = v;
-  (void)is_new;
-#else
   // rows are owned by this workgroup; bypass L1 when re-reading what an earlier chunk wrote
-#if HBK_BWD_OUT_WT
-  if (is_new) {
-    store_wt(o, v);
-  } else {
-    *o = __builtin_nontemporal_load(o) + v;
-  }
-#else
   *o = is_new ? v : __builtin_nontemporal_load(o) + v;
-#endif
-#endif
 }
 
 // The sparse optimizer step of one row chunk (this workgroup owns the row), from values already
@@ -1399,9 +1288,9 @@ __device__ inline void emit_step_row(const GCol& c, const ReduceJob& job, float 
   if (STEP && lr != 0.0f) {
     constexpr bool adagrad = STEP == 2;
     const int64_t toff = row * c.tpitch + (int64_t)sub * VE;
-    const V tv = HBK_STEP_LOAD(reinterpret_cast<const V*>(c.table + toff));
+    const V tv = __builtin_nontemporal_load(reinterpret_cast<const V*>(c.table + toff));
     V av = zero_v<V>();
-    if (adagrad) av = HBK_STEP_LOAD(reinterpret_cast<const V*>(c.accum + toff));
+    if (adagrad) av = __builtin_nontemporal_load(reinterpret_cast<const V*>(c.accum + toff));
     step_row<V>(c, adagrad, lr, toff, v, tv, av);
   }
 }
@@ -1418,7 +1307,7 @@ __device__ inline int table_slot(ReduceLds& L, unsigned long long row, bool* ent
     if (k == row) return h;
     if (k == kEmptyKey) {
       // racy read of the fill level (the waves add their new rows after every pair of the chunk
-      // loop): concurrent inserts overshoot kRoom by < kTeam rows, the table keeps >= 8 empty
+      // loop): concurrent inserts overshoot kRoom by < kBlock rows, the table keeps >= 8 empty
       // slots, so every probe sequence ends
       if (*(volatile int32_t*)&L.occupied >= kRoom) return -1;
       const unsigned long long prev = atomicCAS(&L.keys[h], kEmptyKey, row);
@@ -1450,12 +1339,13 @@ __device__ inline int table_find(const ReduceLds& L, unsigned long long row) {
 template <typename V, int STEP, bool WIDE = false>
 __device__ inline void bucket_reduce(const GCol& c, const ReduceJob& job, ReduceLds& L) {
   constexpr int VE = sizeof(V) / 4;
-  const int tid = (int)threadIdx.x & (kTeam - 1);   // inside the team
+  const int tid = (int)threadIdx.x & (kBlock - 1);   // (the mask changes nothing; kept because the kernels' code changes
+                                                     // without it: see profiles/bwd_switches_retired.txt)
   const int lane = tid & (kWave - 1), wave = tid >> 6;
   const int lpr_log2 = c.lpr_log2;
   const int sub = lane & ((1 << lpr_log2) - 1);
   const bool live = sub < c.chunks;
-  const int groups = kTeam >> lpr_log2 > 0 ? kTeam >> lpr_log2 : 1;
+  const int groups = kBlock >> lpr_log2 > 0 ? kBlock >> lpr_log2 : 1;
   const int my_group = tid >> lpr_log2;
 
   const int32_t n_pairs = job.n_pairs;
@@ -1463,8 +1353,8 @@ __device__ inline void bucket_reduce(const GCol& c, const ReduceJob& job, Reduce
   int64_t* prow = job.prow;
   const int32_t* pseg = job.pseg;
 
-  team_sync();   // a workgroup may run several jobs: the previous one is done with the table
-  for (int i = tid; i < kSlots; i += kTeam) {
+  __syncthreads();   // a workgroup may run several jobs: the previous one is done with the table
+  for (int i = tid; i < kSlots; i += kBlock) {
     L.keys[i] = kEmptyKey;
     L.slot_out[i] = -1;
     L.cnt[i] = 0;
@@ -1474,7 +1364,7 @@ __device__ inline void bucket_reduce(const GCol& c, const ReduceJob& job, Reduce
     L.occupied_before = 0;
     L.n_left = 0;
   }
-  team_sync();
+  __syncthreads();
   HBK_STAMP(2);
 
   // The optimizer step is taken once per row.  A job of one chunk (almost all: buckets aim at 7/8
@@ -1505,21 +1395,21 @@ __device__ inline void bucket_reduce(const GCol& c, const ReduceJob& job, Reduce
       // serialise, so a hot row is first reduced inside the wave: up to kHotTries times the first
       // pending lane's row is matched with a ballot; a group of >= kHotMin lanes lets its leader
       // probe once and take all tickets, the other lanes get slot and ticket by broadcast.
-      int hs_[kCP / kTeam], tk_[kCP / kTeam], rk_[kCP / kTeam];
-      unsigned long long row_[kCP / kTeam];
+      int hs_[kCP / kBlock], tk_[kCP / kBlock], rk_[kCP / kBlock];
+      unsigned long long row_[kCP / kBlock];
       HBK_SUBSTAMP(0);
       // all pairs of the chunk are requested before the first is worked on (inside the loop below
       // the second pair's loads waited behind the LDS work of the first: two memory round trips)
-      int64_t r_in[kCP / kTeam];
-      int32_t seg_in[kCP / kTeam];
+      int64_t r_in[kCP / kBlock];
+      int32_t seg_in[kCP / kBlock];
 #pragma unroll
-      for (int k = 0; k < kCP / kTeam; ++k) {
-        const int e = k * kTeam + tid;
+      for (int k = 0; k < kCP / kBlock; ++k) {
+        const int e = k * kBlock + tid;
         r_in[k] = kDonePair;
         seg_in[k] = cb + e;
         if (e < n_chunk) {
-          r_in[k] = HBK_PAIR_LOAD(prow + cb + e);
-          if (pseg != nullptr) seg_in[k] = HBK_PAIR_LOAD(pseg + cb + e);
+          r_in[k] = *(prow + cb + e);
+          if (pseg != nullptr) seg_in[k] = *(pseg + cb + e);
         }
       }
 #ifdef HBK_BWD_STAMPS
@@ -1530,17 +1420,17 @@ __device__ inline void bucket_reduce(const GCol& c, const ReduceJob& job, Reduce
       // for the whole chunk beside the insert work, and kept in LDS.  (Divided inside the gradient
       // loads -- load, wait for the length, divide, next load -- the rows of a round travelled one
       // memory round trip at a time.)
-      int32_t n_in[kCP / kTeam];
+      int32_t n_in[kCP / kBlock];
       if (scaled) {   // uniform
 #pragma unroll
-        for (int k = 0; k < kCP / kTeam; ++k) {
+        for (int k = 0; k < kCP / kBlock; ++k) {
           n_in[k] = 1;
-          if (k * kTeam + tid < n_chunk) n_in[k] = c.splits[seg_in[k] + 1] - c.splits[seg_in[k]];
+          if (k * kBlock + tid < n_chunk) n_in[k] = c.splits[seg_in[k] + 1] - c.splits[seg_in[k]];
         }
       }
 #pragma unroll
-      for (int k = 0; k < kCP / kTeam; ++k) {
-        const int e = k * kTeam + tid;
+      for (int k = 0; k < kCP / kBlock; ++k) {
+        const int e = k * kBlock + tid;
         bool valid = e < n_chunk;
         unsigned long long row = 0;
         if (valid) {
@@ -1563,9 +1453,7 @@ __device__ inline void bucket_reduce(const GCol& c, const ReduceJob& job, Reduce
           // wave-uniform.  Uniform ids: the first lane's row is shared with nobody and the search
           // ends after one round (it would cost 5 % of the backward otherwise); skewed ids: the
           // first lane most likely holds a repeated row and the search goes on
-#ifndef HBK_BWD_HOT_NOEARLY
           if (n_same == 1 && t == 0) break;
-#endif
           if (n_same < kHotMin) continue;
           int hs = -1, base = 0;
           if (lane == leader) {
@@ -1598,29 +1486,29 @@ __device__ inline void bucket_reduce(const GCol& c, const ReduceJob& job, Reduce
       }
       if (scaled) {
 #pragma unroll
-        for (int k = 0; k < kCP / kTeam; ++k) {
-          if (k * kTeam + tid < n_chunk) L.nseg[k * kTeam + tid] = n_in[k];
+        for (int k = 0; k < kCP / kBlock; ++k) {
+          if (k * kBlock + tid < n_chunk) L.nseg[k * kBlock + tid] = n_in[k];
         }
       }
       HBK_SUBSTAMP(2);
-      team_sync();
+      __syncthreads();
       HBK_SUBSTAMP(3);
       if (L.n_left > 0) {   // uniform: nobody changes it before the next pass
         // A pair that found no room may belong to a row another lane entered in the same instant
         // (it read the slot before that lane's CAS and the fill level after it): the next pass
         // would enter the row a second time and emit it twice.  The table is still now: look again.
 #pragma unroll
-        for (int k = 0; k < kCP / kTeam; ++k) {
+        for (int k = 0; k < kCP / kBlock; ++k) {
           if (hs_[k] == -2) {
             const int h = table_find(L, row_[k]);
             if (h >= 0) {
               tk_[k] = atomicAdd(&L.cnt[h], 1);
-              L.pslot[k * kTeam + tid] = (uint16_t)h;
+              L.pslot[k * kBlock + tid] = (uint16_t)h;
             }
             hs_[k] = h >= 0 ? h : -1;
           }
         }
-        team_sync();
+        __syncthreads();
       }
       HBK_STAMP(3);
 
@@ -1629,7 +1517,7 @@ __device__ inline void bucket_reduce(const GCol& c, const ReduceJob& job, Reduce
       // as soon as the count is known -- the rows the table has gained in this chunk -- and its
       // round trip runs beside the scan of (b) and the gradient loads of (c).
       int32_t claimed = 0;
-      if (tid == kTeam - 1) {
+      if (tid == kBlock - 1) {
         const int32_t n_new = L.occupied - L.occupied_before;
         L.occupied_before = L.occupied;
         if (STEP && job.no_emit) {
@@ -1643,9 +1531,9 @@ __device__ inline void bucket_reduce(const GCol& c, const ReduceJob& job, Reduce
       // (b) one packed exclusive scan over the PAIRS that hold ticket 0 (one per slot of the
       // chunk): new rows | slots with several pairs << 10 | their pairs << 20
       {
-        int32_t pk[kCP / kTeam], sum = 0;
+        int32_t pk[kCP / kBlock], sum = 0;
 #pragma unroll
-        for (int k = 0; k < kCP / kTeam; ++k) {
+        for (int k = 0; k < kCP / kBlock; ++k) {
           pk[k] = 0;
           if (hs_[k] >= 0 && tk_[k] == 0) {
             const int32_t n = L.cnt[hs_[k]];
@@ -1664,10 +1552,10 @@ __device__ inline void bucket_reduce(const GCol& c, const ReduceJob& job, Reduce
           if (lane >= o) incl += y;
         }
         if (lane == kWave - 1) L.wave_tot[wave] = incl;
-        team_sync();
+        __syncthreads();
         int32_t run = incl - sum;
         for (int w = 0; w < wave; ++w) run += L.wave_tot[w];
-        if (tid == kTeam - 1) {
+        if (tid == kBlock - 1) {
           const int32_t tot = run + sum;
           L.n_new = tot & 1023;
           L.n_active = (tot >> 10) & 1023;
@@ -1676,12 +1564,12 @@ __device__ inline void bucket_reduce(const GCol& c, const ReduceJob& job, Reduce
           // rows by ds_add_f32; many, or a slot with many pairs (skewed ids: same-address LDS
           // atomics serialise): they are sorted by slot and walked / summed by the whole
           // workgroup, see (d)
-          L.lds_rows = ((tot >> 10) & 1023) * c.dim <= kTeam * 4 && (tot >> 20) <= kLdsRowPairs;
+          L.lds_rows = ((tot >> 10) & 1023) * c.dim <= kBlock * 4 && (tot >> 20) <= kLdsRowPairs;
         }
-        team_sync();
+        __syncthreads();
         const bool lds_rows_b = L.lds_rows != 0;
 #pragma unroll
-        for (int k = 0; k < kCP / kTeam; ++k) {
+        for (int k = 0; k < kCP / kBlock; ++k) {
           rk_[k] = -1;
           if (!lds_rows_b) {
             // skewed ids: most pairs belong to multi-pair slots and go through (d); (c) then walks
@@ -1693,7 +1581,7 @@ __device__ inline void bucket_reduce(const GCol& c, const ReduceJob& job, Reduce
               const int first = __builtin_ctzll(single);
               if (lane == first) base = atomicAdd(&L.n_single, (int)__builtin_popcountll(single));
               base = __builtin_amdgcn_readlane(base, first);
-              if (pk[k] == 1) L.order[base + rank_below(single)] = (uint16_t)(k * kTeam + tid);
+              if (pk[k] == 1) L.order[base + rank_below(single)] = (uint16_t)(k * kBlock + tid);
             }
           }
           if (pk[k] != 0) {
@@ -1714,7 +1602,7 @@ __device__ inline void bucket_reduce(const GCol& c, const ReduceJob& job, Reduce
           run += pk[k];
         }
       }
-      team_sync();
+      __syncthreads();
       HBK_STAMP(4);
 
       // (c) one round of gradient loads, kPre rows in flight per lane.  A NEW row with ONE pair in
@@ -1752,22 +1640,22 @@ __device__ inline void bucket_reduce(const GCol& c, const ReduceJob& job, Reduce
                 // the table (and accumulator) row of the step travels with the gradient
                 const int64_t toff = (int64_t)L.keys[sidx] * c.tpitch + (int64_t)sub * VE;
                 tv[STEP ? k : 0] =
-                    HBK_STEP_LOAD(reinterpret_cast<const V*>(c.table + toff));
+                    __builtin_nontemporal_load(reinterpret_cast<const V*>(c.table + toff));
                 if (STEP == 2) {
                   av[STEP == 2 ? k : 0] =
-                      HBK_STEP_LOAD(reinterpret_cast<const V*>(c.accum + toff));
+                      __builtin_nontemporal_load(reinterpret_cast<const V*>(c.accum + toff));
                 }
               }
             }
           }
         }
         if (e0 == 0) {
-          if (tid == kTeam - 1) {
+          if (tid == kBlock - 1) {
             L.base_u = job.out_base + claimed;
             L.emit0 = L.n_emitted;
             L.n_emitted += L.n_new;
           }
-          team_sync();
+          __syncthreads();
           base_u = L.base_u;
         }
 #pragma unroll
@@ -1793,9 +1681,9 @@ __device__ inline void bucket_reduce(const GCol& c, const ReduceJob& job, Reduce
       }
       // the new rows' slots get their absolute output position (later chunks, (d), the optimizer
       // step read it), and the row numbers go out
-      team_sync();
+      __syncthreads();
 #pragma unroll
-      for (int k = 0; k < kCP / kTeam; ++k) {
+      for (int k = 0; k < kCP / kBlock; ++k) {
         if (rk_[k] >= 0) {
           const int32_t u = base_u + rk_[k];
           L.slot_out[hs_[k]] = u;
@@ -1804,7 +1692,7 @@ __device__ inline void bucket_reduce(const GCol& c, const ReduceJob& job, Reduce
         }
       }
       if (lds_rows && n_active > 0) {
-        team_sync();
+        __syncthreads();
         for (int m = my_group; m < n_active; m += groups) {
           if (!live) continue;
           const int sidx = L.active[m];
@@ -1818,8 +1706,8 @@ __device__ inline void bucket_reduce(const GCol& c, const ReduceJob& job, Reduce
         // (d) counting sort of the pairs of multi-pair slots (off[] ends up as the end of every
         // slot's run); tickets of a hot slot are taken once per wave and split by ballot rank
 #pragma unroll
-        for (int k = 0; k < kCP / kTeam; ++k) {
-          const int e = k * kTeam + tid;
+        for (int k = 0; k < kCP / kBlock; ++k) {
+          const int e = k * kBlock + tid;
           const int h = hs_[k];
           const bool valid = h >= 0 && L.cnt[h] != (kNewBit | 1);
           int pos = -1;
@@ -1841,7 +1729,7 @@ __device__ inline void bucket_reduce(const GCol& c, const ReduceJob& job, Reduce
             L.order[pos] = (uint16_t)e;
           }
         }
-        team_sync();
+        __syncthreads();
 
         // The sorted pairs are walked FLAT: per round a lane group takes kW consecutive positions
         // of the sorted order, all their gradient rows in flight at once, and sums runs of one slot
@@ -1883,7 +1771,7 @@ __device__ inline void bucket_reduce(const GCol& c, const ReduceJob& job, Reduce
               }
               *reinterpret_cast<V*>(&L.red[(size_t)tid * VE]) = head;
             }
-            team_sync();
+            __syncthreads();
             const int round_end = r0 + per_round;
             V acc = zero_v<V>();
             int cur = -1;
@@ -1940,10 +1828,10 @@ __device__ inline void bucket_reduce(const GCol& c, const ReduceJob& job, Reduce
                   tv[b] = zero_v<V>();
                   if (w < kW && (fin >> w & 1u)) {
                     const int64_t toff = (int64_t)L.keys[sl[w]] * c.tpitch + (int64_t)sub * VE;
-                    tv[b] = HBK_STEP_LOAD(reinterpret_cast<const V*>(c.table + toff));
+                    tv[b] = __builtin_nontemporal_load(reinterpret_cast<const V*>(c.table + toff));
                     if (STEP == 2) {
                       av[STEP == 2 ? b : 0] =
-                          HBK_STEP_LOAD(reinterpret_cast<const V*>(c.accum + toff));
+                          __builtin_nontemporal_load(reinterpret_cast<const V*>(c.accum + toff));
                     }
                   }
                 }
@@ -1970,22 +1858,22 @@ __device__ inline void bucket_reduce(const GCol& c, const ReduceJob& job, Reduce
                 }
               }
             }
-            team_sync();
+            __syncthreads();
           }
         };
         // Width of the walk with the optimizer step: as many positions as the step's table /
         // accumulator rows leave registers for (kPre with SGD, 2 with Adagrad) -- or, for WIDE rows
         // (dim >= 64: <= 16 lane groups, i.e. 10-28 rounds of two barriers and two memory round
-        // trips per chunk at the narrow width), HBK_BWD_WIDE_W positions with the step's rows requested
+        // trips per chunk at the narrow width), kWideW positions with the step's rows requested
         // two positions at a time (a round finishes ~1 row per lane group).  Narrow rows lose with
         // that form (ragged dim 16: 937 vs 782 us: more dependent table round trips per round).
         if constexpr (STEP != 0 && WIDE) {
-          walk(std::integral_constant<int, HBK_BWD_WIDE_W>());
+          walk(std::integral_constant<int, kWideW>());
         } else {
           walk(std::integral_constant<int, STEP == 2 ? 2 : STEP ? kPre : 2 * kPre>());
         }
       }
-      team_sync();
+      __syncthreads();
 
       // chunk done: the tickets go back to zero; once a pass has left pairs behind, the pairs it
       // did handle are struck out of the pair buffer so that the next pass skips them
@@ -1993,13 +1881,13 @@ __device__ inline void bucket_reduce(const GCol& c, const ReduceJob& job, Reduce
       if (left && first_left < 0) first_left = cb;
       striking = striking || left;
 #pragma unroll
-      for (int k = 0; k < kCP / kTeam; ++k) {
+      for (int k = 0; k < kCP / kBlock; ++k) {
         if (hs_[k] >= 0) {
           L.cnt[hs_[k]] = 0;
-          if (striking) prow[cb + k * kTeam + tid] = kDonePair;
+          if (striking) prow[cb + k * kBlock + tid] = kDonePair;
         }
       }
-      team_sync();
+      __syncthreads();
       HBK_STAMP(6);
     }
     // the pass is over (job of several chunks): one optimizer step per row the pass emitted.  All
@@ -2022,9 +1910,9 @@ __device__ inline void bucket_reduce(const GCol& c, const ReduceJob& job, Reduce
             toff[k] = (int64_t)L.keys[s] * c.tpitch + (int64_t)sub * VE;
             g[k] = __builtin_nontemporal_load(reinterpret_cast<const V*>(
                 job.out_vals + (int64_t)L.slot_out[s] * c.dim + (int64_t)sub * VE));
-            tv[k] = HBK_STEP_LOAD(reinterpret_cast<const V*>(c.table + toff[k]));
+            tv[k] = __builtin_nontemporal_load(reinterpret_cast<const V*>(c.table + toff[k]));
             if (adagrad) {
-              av[k] = HBK_STEP_LOAD(reinterpret_cast<const V*>(c.accum + toff[k]));
+              av[k] = __builtin_nontemporal_load(reinterpret_cast<const V*>(c.accum + toff[k]));
             }
           }
         }
@@ -2036,8 +1924,8 @@ __device__ inline void bucket_reduce(const GCol& c, const ReduceJob& job, Reduce
     }
     if (first_left < 0) break;     // uniform
     // another pass for the rows that found no room, with an emptied table
-    team_sync();
-    for (int i = tid; i < kSlots; i += kTeam) {
+    __syncthreads();
+    for (int i = tid; i < kSlots; i += kBlock) {
       L.keys[i] = kEmptyKey;
       L.slot_out[i] = -1;
     }
@@ -2048,7 +1936,7 @@ __device__ inline void bucket_reduce(const GCol& c, const ReduceJob& job, Reduce
       L.n_emitted = 0;
     }
     first_cb = first_left;
-    team_sync();
+    __syncthreads();
   }
 }
 
@@ -2074,22 +1962,11 @@ __device__ inline void bucket_reduce(const GCol& c, const ReduceJob& job, Reduce
 // of a split bucket, the merge of their partial entries) read their pairs once per stage.
 // workgroups per CU the dense kernels are compiled for: 5 (96 VGPRs) for the lean instantiation,
 // 4 (128 VGPRs) for the one with the sorted walk (it spills at 96)
-#ifndef HBK_BWD_DENSE_WAVES
-#define HBK_BWD_DENSE_WAVES(SORT) ((SORT) ? 4 : 5)
-#endif
-#ifndef HBK_BWD_DENSE_WALK
-#define HBK_BWD_DENSE_WALK(STEP) ((STEP) == 2 ? 2 : (STEP) ? 3 : 4)
-#endif
-// probe switches (tools/scratch/bwd_dense_variants.sh builds the library with them turned off)
-#ifndef HBK_DENSE_FOLD
-#define HBK_DENSE_FOLD 0          // few dup pairs ride with the single rows' loads
-#endif
-#ifndef HBK_DENSE_EARLY_CLAIM
-#define HBK_DENSE_EARLY_CLAIM 0   // output range claimed before the scan (rows = pairs - repeats)
-#endif
-#ifndef HBK_DENSE_SORT
-#define HBK_DENSE_SORT 1          // many dup pairs: sorted flat walk instead of LDS float atomics
-#endif
+constexpr int dense_waves(bool sort) { return sort ? 4 : 5; }
+constexpr int dense_walk_width(int step) { return step == 2 ? 2 : step ? 3 : 4; }   // positions per lane group in dense_walk
+// Many dup pairs take a sorted flat walk instead of LDS float atomics.  Tried and dropped for what they cost
+// the common path (profiles/r03_bwd_variants.txt): "fold", few dup pairs riding with the single rows' loads,
+// and "early claim", the output range claimed before the scan (rows = pairs - repeats).
 constexpr int kDenseSpan = 16384;                 // rows of a bucket's range (bits per bitmap)
 constexpr int kDenseWords = kDenseSpan / 32;
 constexpr int kDenseWPT = kDenseWords / kBlock;   // bitmap words per thread in the scan
@@ -2176,7 +2053,7 @@ __device__ inline void dense_walk(const WalkArgs w_, DenseLds& L) {
   const int my_group = tid >> lpr_log2;
   const bool emit = !(STEP && job.no_emit);
   {
-  constexpr int kW = HBK_BWD_DENSE_WALK(STEP);   // (register budget: 96 VGPRs = 5 workgroups per CU)
+  constexpr int kW = dense_walk_width(STEP);   // (register budget: 96 VGPRs = 5 workgroups per CU)
   const int per_round = groups * kW;
   int cpar = 0;
   for (int r0 = 0; r0 < n_dl; r0 += per_round, cpar ^= 1) {
@@ -2280,10 +2157,10 @@ __device__ inline void dense_walk(const WalkArgs w_, DenseLds& L) {
           if (STEP && lr != 0.0f) {
             const int64_t toff = (int64_t)(base + off) * c.tpitch + (int64_t)sub * VE;
             tv[STEP ? w : 0] =
-                HBK_STEP_LOAD(reinterpret_cast<const V*>(c.table + toff));
+                __builtin_nontemporal_load(reinterpret_cast<const V*>(c.table + toff));
             if (STEP == 2) {
               av[STEP == 2 ? w : 0] =
-                  HBK_STEP_LOAD(reinterpret_cast<const V*>(c.accum + toff));
+                  __builtin_nontemporal_load(reinterpret_cast<const V*>(c.accum + toff));
             }
           }
         }
@@ -2319,8 +2196,8 @@ __device__ inline void load_first_pairs(const ReduceJob& job, FirstPairs& f) {
     f.row[k] = -1;
     f.seg[k] = e;
     if (e < job.n_pairs) {
-      f.row[k] = HBK_PAIR_LOAD(job.prow + e);
-      if (job.pseg != nullptr) f.seg[k] = HBK_PAIR_LOAD(job.pseg + e);
+      f.row[k] = job.prow[e];
+      if (job.pseg != nullptr) f.seg[k] = job.pseg[e];
     }
   }
 }
@@ -2366,8 +2243,8 @@ __device__ inline void dense_reduce(const GCol& c, const ReduceJob& job, DenseLd
       r_in[k] = -1;
       seg_in[k] = e;
       if (e < n_pairs) {
-        r_in[k] = HBK_PAIR_LOAD(prow + e);
-        if (pseg != nullptr) seg_in[k] = HBK_PAIR_LOAD(pseg + e);
+        r_in[k] = prow[e];
+        if (pseg != nullptr) seg_in[k] = pseg[e];
       }
     }
   };
@@ -2400,8 +2277,8 @@ __device__ inline void dense_reduce(const GCol& c, const ReduceJob& job, DenseLd
 
   // A: rows -> bitmaps.  A bit that is already set is not set again: the pairs of a hot row
   // would serialise on its word (64 same-address LDS atomics per instruction).
-  // The pairs that find their bit set are counted: rows of the bucket = pairs - those, known
-  // right behind the barrier, a scan earlier than the ranks.
+  // The pairs that find their bit set are counted: rows of the bucket = pairs - those
+  // (no reader since the early claim went: see profiles/bwd_switches_retired.txt)
   int n_again = 0;   // (wave-uniform)
   for (int32_t cb = 0; cb < n_pairs; cb += kCP) {
     if (cb > 0) load_pairs(cb);
@@ -2425,18 +2302,10 @@ __device__ inline void dense_reduce(const GCol& c, const ReduceJob& job, DenseLd
   HBK_STAMP(3);
 
   // One global atomic per workgroup claims the output range of the bucket's rows; a returning
-  // device-scope atomic takes microseconds under load: it is issued as soon as the count is known
-  // and its round trip runs beside the scan of B and the gradient loads of C.  Step only: just
-  // the count is wanted, nobody waits for it.
+  // device-scope atomic takes microseconds under load: it is issued at the end of the scan of B
+  // and its round trip runs beside the gradient loads of C.  Step only: just the count is wanted,
+  // nobody waits for it.
   int32_t claimed = 0;
-  if (HBK_DENSE_EARLY_CLAIM && tid == kBlock - 1) {
-    const int32_t n_rows = n_pairs - L.n_again;
-    if (!emit) {
-      __hip_atomic_fetch_add(job.out_counter, n_rows, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-      claimed = atomicAdd(job.out_counter, n_rows);
-    }
-  }
 
   // B: rows before every word, present and dup counts packed in one scan (both <= kDenseSpan < 2^16)
   {
@@ -2469,13 +2338,11 @@ __device__ inline void dense_reduce(const GCol& c, const ReduceJob& job, DenseLd
     }
     if (tid == kBlock - 1) {
       L.n_dup = (int32_t)(run >> 16);
-      if (!HBK_DENSE_EARLY_CLAIM) {
-        const int32_t n_rows = (int32_t)(run & 0xffffu);
-        if (!emit) {
-          __hip_atomic_fetch_add(job.out_counter, n_rows, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-          claimed = atomicAdd(job.out_counter, n_rows);
-        }
+      const int32_t n_rows = (int32_t)(run & 0xffffu);
+      if (!emit) {
+        __hip_atomic_fetch_add(job.out_counter, n_rows, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      } else {
+        claimed = atomicAdd(job.out_counter, n_rows);
       }
     }
   }
@@ -2551,7 +2418,7 @@ __device__ inline void dense_reduce(const GCol& c, const ReduceJob& job, DenseLd
       // tickets taken above) and walked in D; the tickets leave the registers before C needs them
       const int n_dl = L.n_dlist[par];
       const int nd = d1 - d0;
-      const bool sorted = SORT && HBK_DENSE_SORT && n_dl > kSortMin;   // uniform
+      const bool sorted = SORT && n_dl > kSortMin;   // uniform
       if (__builtin_expect(sorted, 0)) {
         {
           int32_t cn[PT], sum = 0;
@@ -2591,17 +2458,13 @@ __device__ inline void dense_reduce(const GCol& c, const ReduceJob& job, DenseLd
         for (int i = tid; i < nd; i += kBlock) L.dcnt[i] = 0;   // (next read: behind a barrier)
       }
 
-      // C: the pairs that are alone on their row (first round only).  When the chunk's dup pairs
-      // are few (not sorted), their gradient rows travel in the same round and go into the rows'
-      // LDS sums (ds_add_f32) when they arrive.
+      // C: the pairs that are alone on their row (first round only).
       if (round == 0) {
-        const bool fold = HBK_DENSE_FOLD && !sorted && n_dl > 0;   // uniform
-        used_red = used_red || fold;
         HBK_SUBSTAMP(0);
         for (int e0 = 0; e0 < n_chunk; e0 += kDepth * groups) {
           V g[kDepth], tv[STEP ? kDepth : 1], av[STEP == 2 ? kDepth : 1];
           int32_t n_[kDepth];
-          uint32_t mask = 0, dmask = 0;
+          uint32_t mask = 0;
 #pragma unroll
           for (int k = 0; k < kDepth; ++k) {
             const int i = e0 + k * groups + my_group;
@@ -2615,15 +2478,12 @@ __device__ inline void dense_reduce(const GCol& c, const ReduceJob& job, DenseLd
                 if (STEP && lr != 0.0f) {
                   const int64_t toff = (int64_t)(base + L.off[i]) * c.tpitch + (int64_t)sub * VE;
                   tv[STEP ? k : 0] =
-                      HBK_STEP_LOAD(reinterpret_cast<const V*>(c.table + toff));
+                      __builtin_nontemporal_load(reinterpret_cast<const V*>(c.table + toff));
                   if (STEP == 2) {
                     av[STEP == 2 ? k : 0] =
-                        HBK_STEP_LOAD(reinterpret_cast<const V*>(c.accum + toff));
+                        __builtin_nontemporal_load(reinterpret_cast<const V*>(c.accum + toff));
                   }
                 }
-              } else if (fold && (code & (kDupBit - 1)) < d1) {   // (round 0: d0 = 0)
-                dmask |= 1u << k;
-                g[k] = load_grad_raw<V>(c, job, L.seg[i], sub, &n_[k]);
               }
             }
           }
@@ -2641,15 +2501,9 @@ __device__ inline void dense_reduce(const GCol& c, const ReduceJob& job, DenseLd
 #endif
 #pragma unroll
           for (int k = 0; k < kDepth; ++k) {
-            if (((mask | dmask) >> k & 1u) == 0) continue;
+            if ((mask >> k & 1u) == 0) continue;
             const int i = e0 + k * groups + my_group;
             if (dscaled) g[k] = scale_grad<V>(c, g[k], n_[k]);
-            if (dmask >> k & 1u) {
-              float* r = &L.red[(size_t)(L.code[i] & (kDupBit - 1)) * c.dim + (size_t)sub * VE];
-#pragma unroll
-              for (int q = 0; q < VE; ++q) atomicAdd(r + q, reinterpret_cast<const float*>(&g[k])[q]);
-              continue;
-            }
             if (emit) emit_row<V>(c, job, base_u + L.code[i], true, sub, g[k]);
             if (STEP && lr != 0.0f) {
               const int64_t toff = (int64_t)(base + L.off[i]) * c.tpitch + (int64_t)sub * VE;
@@ -2690,10 +2544,10 @@ __device__ inline void dense_reduce(const GCol& c, const ReduceJob& job, DenseLd
         wa.one_chunk = one_chunk;
         wa.no_emit = job.no_emit;
         dense_walk<V, STEP>(wa, L);
-      } else if (round > 0 || !HBK_DENSE_FOLD) {
-        // Few, and not the first round (wide rows: only 2048 / dim sums fit LDS at a time; the
-        // first round's pairs went with C): summed into the rows' LDS sums by ds_add_f32; what a
-        // lane group holds for one row in consecutive registers is added up first.
+      } else {
+        // Few: summed into the rows' LDS sums by ds_add_f32 (wide rows: only 2048 / dim sums fit LDS
+        // at a time, hence the rounds); what a lane group holds for one row in consecutive registers
+        // is added up first.
         used_red = used_red || n_dl > 0;
         for (int i0 = 0; i0 < n_dl; i0 += kDepth * groups) {
           V g[kDepth];
@@ -2824,15 +2678,15 @@ __device__ inline bool decode_job(const GArgs& a, int my_b0, int vb, const int4&
 // the job slots of one kind are one range [slot0, slot0 + grid) and no workgroup starts for
 // nothing.
 template <typename V, int STEP, bool WIDE>
-__global__ __launch_bounds__(kBlock, HBK_BWD_WAVES) void bwd_reduce_kernel(const GArgs a,
+__global__ __launch_bounds__(kBlock, kReduceWaves) void bwd_reduce_kernel(const GArgs a,
                                                                           const int4* desc,
                                                                           int slot0, int total,
                                                                           const int32_t* poison) {
-  __shared__ ReduceLds lds[kTeams];
+  __shared__ ReduceLds lds[1];   // (an array for `team` below)
   if (poisoned(poison)) return;   // the grouping launch gave up: no descriptors, no pairs
   HBK_STAMP_BEGIN()
   const int lane = (int)threadIdx.x & (kWave - 1);
-  const int team = (int)threadIdx.x / kTeam;
+  const int team = (int)threadIdx.x / kBlock;   // (always 0; kept because the kernels' code changes without it: see profiles/bwd_switches_retired.txt)
   constexpr int kKind = 2 * (WIDE ? 3 : 2) + (sizeof(V) == 4 ? 1 : 0);   // (the host's ColInfo.kind)
   int jb = (int)blockIdx.x;
   if ((a.xcd_w >> kKind) & 1) {
@@ -2842,8 +2696,8 @@ __global__ __launch_bounds__(kBlock, HBK_BWD_WAVES) void bwd_reduce_kernel(const
   } else {
     jb = xcd_contiguous(jb, (int)gridDim.x, (a.xcd >> kKind) & 1);
   }
-  const int vb = slot0 + jb * kTeams + team;   // the team's job slot
-  if (vb >= total) return;                          // team-uniform; no workgroup barrier follows
+  const int vb = slot0 + jb + team;
+  if (vb >= total) return;
   // two independent loads (the job, the columns' first slots): one round trip
   const int4 d = desc[vb];
   const int my_b0 = lane < a.n_cols ? a.bucket0[lane] : 0x7fffffff;
@@ -2861,7 +2715,7 @@ __global__ __launch_bounds__(kBlock, HBK_BWD_WAVES) void bwd_reduce_kernel(const
 // SLOWER on the config-2 backward and 10 % slower on ragged columns: the registers that carry the
 // next job's pairs cost more than the round trips they hide.)
 template <typename V, int STEP, bool SORT>
-__global__ __launch_bounds__(kBlock, HBK_BWD_DENSE_WAVES(SORT)) void bwd_dense_kernel(
+__global__ __launch_bounds__(kBlock, dense_waves(SORT)) void bwd_dense_kernel(
     const GArgs a, const int4* desc, int slot0, int total, const int32_t* poison) {
   __shared__ DenseLds lds;
   if (poisoned(poison)) return;   // the grouping launch gave up: no descriptors, no pairs
@@ -2951,16 +2805,16 @@ __device__ inline void merge_job(const GArgs& a, const GCol& c, int bucket, Redu
 }
 
 template <typename V, int STEP, bool WIDE>
-__global__ __launch_bounds__(kBlock, HBK_BWD_WAVES) void bwd_merge_kernel(const GArgs a, int block0,
+__global__ __launch_bounds__(kBlock, kReduceWaves) void bwd_merge_kernel(const GArgs a, int block0,
                                                                          const int32_t* poison) {
-  __shared__ ReduceLds lds[kTeams];
+  __shared__ ReduceLds lds[1];   // (an array for `team` below)
   if (poisoned(poison)) return;
   const int block = block0 + (int)blockIdx.x;
   HBK_FIND_COL_AT(a, merge0, block)
-  const int team = (int)threadIdx.x / kTeam;
+  const int team = (int)threadIdx.x / kBlock;   // (always 0; kept because the kernels' code changes without it: see profiles/bwd_switches_retired.txt)
   const int n_extra = *c.n_extra;
   const int blocks = c.e_max < kMergeBlocks ? c.e_max : kMergeBlocks;
-  for (int e = (block - c.merge0) * kTeams + team; e < n_extra; e += blocks * kTeams) {
+  for (int e = block - c.merge0 + team; e < n_extra; e += blocks) {
     if (c.work[2 * e + 1] != 1) continue;
     ReduceJob job;
     merge_job(a, c, c.work[2 * e], &job);
@@ -2970,7 +2824,7 @@ __global__ __launch_bounds__(kBlock, HBK_BWD_WAVES) void bwd_merge_kernel(const 
 }
 
 template <typename V, int STEP>
-__global__ __launch_bounds__(kBlock, HBK_BWD_DENSE_WAVES(true)) void bwd_dense_merge_kernel(const GArgs a,
+__global__ __launch_bounds__(kBlock, dense_waves(true)) void bwd_dense_merge_kernel(const GArgs a,
                                                                                      int block0,
                                                                                      const int32_t* poison) {
   __shared__ DenseLds lds;
@@ -3351,7 +3205,7 @@ ColPlan plan_of(int64_t n_ids, int32_t dim, int64_t rows, bool ragged, bool det 
     // reduce kind with an in-order form (lookup_bwd_rowsort.h) -- and no bucket is split over
     // workgroups (partial sums joined by a merge are not the sequential sum)
     const bool want = det || dense_opt == 3 || (dense_opt == 1 && ratio > 0 && rows <= ratio * n_ids);
-    if (kTeam == kBlock && want && rows >= 1 && rows < (1ll << 32)) {
+    if (want && rows >= 1 && rows < (1ll << 32)) {
       int64_t rs_target = (int64_t)kRsCap * 7 / 8;
       // wide rows: a lane group is 16-64 lanes, a workgroup holds 4-16 of them, and a job of 1792
       // pairs is a serial walk of 100-450 positions per lane group; option bwd_rowsort_pos (> 0)
@@ -3393,7 +3247,7 @@ ColPlan plan_of(int64_t n_ids, int32_t dim, int64_t rows, bool ragged, bool det 
   }
   const bool forced_dense = options().bwd_dense == 2;
   const bool eligible = forced_dense || (dim <= 32 && !ragged && n_ids <= rows / 8);
-  if (kTeam == kBlock && options().bwd_dense != 0 && eligible && rows >= 1 && rows < (1ll << 32)) {
+  if (options().bwd_dense != 0 && eligible && rows >= 1 && rows < (1ll << 32)) {
     const int64_t P = nb < rows ? nb : rows;
     uint64_t M = ((uint64_t)P << 32) / (uint64_t)rows;
     if (M > 0xffffffffull) M = 0xffffffffull;
@@ -3430,10 +3284,6 @@ constexpr int kKinds = 2 * kBucketKinds;
 static_assert(kKinds == sizeof(GArgs::xcd_start) / sizeof(GArgs::xcd_start[0]), "one xcd_start row per kind");
 inline int kind_of(int bucket_kind, bool vec4) { return 2 * bucket_kind + (vec4 ? 0 : 1); }
 inline int bucket_kind_of(int kind) { return kind >> 1; }
-// job slots per workgroup of a kind's reduce launch
-inline int64_t slots_per_block(int kind) {
-  return bucket_kind_of(kind) == kHashed || bucket_kind_of(kind) == kHashedWide ? kTeams : 1;
-}
 
 // Where a column's buffers lie: offsets from the start of the column's slice of the call's buffer
 // region (kNoBuf: the column has no such buffer), the bytes of that slice, of the column's job
@@ -4177,13 +4027,12 @@ void place_xcds(Group& g) {
     if (!g.have_kind[kind] || options().bwd_xcd == 0) continue;
     bool even = options().bwd_xcd == 2;
     if (!even) {
-      const int64_t per = slots_per_block(kind);
-      const int64_t n = (g.slot_hi[kind] - g.slot_lo[kind] + per - 1) / per;   // the launch's blocks
+      const int64_t n = g.slot_hi[kind] - g.slot_lo[kind];   // the launch's blocks: one per job slot
       const int64_t q = n / 8, r = n % 8;
       double work[8] = {0}, total = 0;
       int64_t slot = 0;      // walked once: ranges and columns both ascend
       int x = 0;
-      int64_t x_end = (r > 0 ? q + 1 : q) * per;
+      int64_t x_end = r > 0 ? q + 1 : q;
       for (const KindCol& kc : g.kind_cols[kind]) {
         for (int part = 0; part < 2; ++part) {
           int64_t len = part == 0 ? kc.n_buckets : kc.e_max;
@@ -4191,7 +4040,7 @@ void place_xcds(Group& g) {
           while (len > 0) {
             while (x < 7 && slot >= x_end) {
               ++x;
-              x_end += (x < r ? q + 1 : q) * per;
+              x_end += x < r ? q + 1 : q;
             }
             const int64_t take = x < 7 && x_end - slot < len ? x_end - slot : len;
             work[x] += w * (double)take;
@@ -4213,7 +4062,7 @@ void place_xcds(Group& g) {
   // launch -- the config-5 shape loses 5 % with them, so its loss above is not the imbalance
   // alone.)
   args.xcd_w = 0;
-  if ((options().bwd_xcd == 4 || options().bwd_xcd == 1 || options().bwd_xcd == 3) && kTeams == 1) {
+  if (options().bwd_xcd == 4 || options().bwd_xcd == 1 || options().bwd_xcd == 3) {
     for (int kind = 0; kind < kKinds; ++kind) {
       if (!g.have_kind[kind]) continue;
       if (options().bwd_xcd != 4 && !((args.xcd >> kind) & 1)) continue;
@@ -4345,8 +4194,7 @@ int launch_reduce_merge(const Group& g, bool det, int32_t apply, float apply_lr,
   for (int kind = 0; kind < kKinds; ++kind) {
     if (!g.have_kind[kind]) continue;
     const int64_t n_slots = g.slot_hi[kind] - g.slot_lo[kind];
-    const int64_t per = slots_per_block(kind);
-    const int64_t grid = g.xcd_grid[kind] > 0 ? g.xcd_grid[kind] : (n_slots + per - 1) / per;
+    const int64_t grid = g.xcd_grid[kind] > 0 ? g.xcd_grid[kind] : n_slots;
     if (det && bucket_kind_of(kind) != kRowSorted) {
       status = fail(HBK_INTERNAL, "group_lookup_bwd: a deterministic column without row-sorted buckets");
       break;

@@ -55,31 +55,19 @@ __device__ inline V rs_load_grad(const ReduceJob& job, int32_t seg, int sub, boo
   const uint64_t off = !F16 && job.seg_is_offset ? (uint64_t)(uint32_t)seg
                                          : (uint64_t)(uint32_t)seg * (uint32_t)job.stride;
   V g = zero_v<V>();
-  if (live) g = HBK_GRAD_LOAD(reinterpret_cast<const V*>(job.grad + off + (uint64_t)sub * VE));
+  if (live) g = *reinterpret_cast<const V*>(job.grad + off + (uint64_t)sub * VE);
   return g;
 }
 
 // Output rows of a one-chunk job are written once and not read again by this kernel: non-temporal,
 // so that they do not push the gradient lines out of L2 -- a ragged column reads every segment's
-// gradient row ~8 times, from different jobs (probe builds: -DHBK_RS_OUT_NT=0 plain stores).
-#ifndef HBK_RS_OUT_NT
-#define HBK_RS_OUT_NT 1
-#endif
+// gradient row ~8 times, from different jobs (plain stores, and the cache policy bits spelled out one by
+// one: profiles/r05_rowsort_counters.txt, profiles/r05_rowsort_limits.txt 3).
 template <typename V, bool F16 = false>
 __device__ inline void rs_store_row(const GCol& c, const ReduceJob& job, int32_t u, int sub, V v) {
   constexpr int VE = sizeof(V) / 4;
   V* o = reinterpret_cast<V*>(job.out_vals + (int64_t)u * (F16 ? 16 : c.dim) + (int64_t)sub * VE);
-#if defined(HBK_RS_OUT_ASM)   // probe builds: the cache policy bits of the row store, spelled out
-  if constexpr (sizeof(V) == 16) {
-    asm volatile("global_store_dwordx4 %0, %1, off " HBK_RS_OUT_ASM : : "v"(o), "v"(v) : "memory");
-  } else {
-    asm volatile("global_store_dword %0, %1, off " HBK_RS_OUT_ASM : : "v"(o), "v"(v) : "memory");
-  }
-#elif HBK_RS_OUT_NT
   __builtin_nontemporal_store(v, o);
-#else
-  *o = v;
-#endif
 }
 
 // Whole-line stores for 64-byte rows (round 5, tools/store_probe.hip): a non-temporal store of HALF a
@@ -94,13 +82,8 @@ __device__ inline void rs_store_row(const GCol& c, const ReduceJob& job, int32_t
 // (Only in the instantiation without an optimizer step.  Tried in the SGD / Adagrad ones as well, with a
 // per-batch guard "some lane group finishes two rows at neighbouring positions": config 2 + SGD 171 -> 166 us on
 // one box and 150 -> 152.6 on another, ragged 10 M rows + SGD -5 %, ragged over 100 k rows + SGD + 3 %, dim 4 / 64
-// + 1-2 % -- the extra registers spill in kernels that are already at 128: not shipped.)
-#ifndef HBK_RS_PAIR_STORES
-#define HBK_RS_PAIR_STORES 1
-#endif
-#ifndef HBK_RS_PAIR_DIST
-#define HBK_RS_PAIR_DIST 1   // positions between two rows of one lane group that still leave as one line; 2 and 3: probe builds (round 6, see below)
-#endif
+// + 1-2 % -- the extra registers spill in kernels that are already at 128: not shipped.  Without the
+// whole-line stores: 15.21 M -> 12.75 M write requests with them, profiles/r05_rowsort_counters.txt.)
 template <int CTRL>
 __device__ inline int rs_dpp_i(int v) {
   return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true);
@@ -131,23 +114,11 @@ constexpr int kDppRowShr4 = 0x114;   // lane i reads lane i - 4
 
 // (the row NUMBERS stay plain stores: 8-byte pieces per lane that the L2 combines into whole
 // sectors; non-temporal they went out one by one -- ragged 1M-row case 650-667 -> 830-920 us)
-#ifndef HBK_RS_ROWNUM_NT
-#define HBK_RS_ROWNUM_NT 0
-#endif
-#ifndef HBK_RS_ROWS_FROM_ROFF
-#define HBK_RS_ROWS_FROM_ROFF 1
-#endif
-#ifndef HBK_RS_W0
-#define HBK_RS_W0 11   // (8: ragged dim 16 675 us, 12: 616 us; 16 spills.  Round 5: 12 spilled 2 VGPRs into the
-                       // walk -- 11 does not: ragged 561-563 -> 523-539 us in-box, 10: 547-551; with the step
-                       // W1 = 5 / W2 = 3 also stop their spills but measure the same as 6 / 4: kept)
-#endif
-#ifndef HBK_RS_W1
-#define HBK_RS_W1 6
-#endif
-#ifndef HBK_RS_W2
-#define HBK_RS_W2 4
-#endif
+// Gradient rows a lane of the walk keeps in flight, by optimizer step (none / SGD / Adagrad).  Without a step
+// 8: ragged dim 16 675 us, 12: 616 us; 16 spills.  Round 5: 12 spilled 2 VGPRs into the walk -- 11 does not:
+// ragged 561-563 -> 523-539 us in-box, 10: 547-551; with the step 5 / 3 also stop their spills but measure
+// the same as 6 / 4: kept.
+constexpr int rs_walk_width(int step) { return step == 2 ? 4 : step == 1 ? 6 : 11; }
 
 // the finished rows of one batch of a lane group (bit w of `mine`: position w ends a run of mine, its
 // sum is in g[w], its rank among the job's rows uu[w]); half0: parity of the job's first output row
@@ -167,18 +138,13 @@ __device__ inline void rs_store_pairs(const GCol& c, const ReduceJob& job, int32
     if (w + 1 < W) {
       // the NEXT row this lane group finishes in the batch sits at the next set bit of `mine`; rows
       // finish in rank order, so it is row R + 1 -- the other half of R's line when R is the even one.
-      // Round 5 paired only rows finishing at ADJACENT positions (the second row a single pair):
-      // 45 % of the even rows of the ragged case; up to HBK_RS_PAIR_DIST positions apart covers runs of
-      // up to that many pairs.
-      const uint32_t ahead = ((mine & ~done) >> (w + 1)) & ((1u << HBK_RS_PAIR_DIST) - 1u);
-      const int d = ahead != 0u ? __builtin_ctz(ahead) + 1 : 0;
-      pair = partner_on && ((mine >> w) & 1u) != 0u && d != 0 && ((R + half0) & 1) == 0 &&
+      // Only rows finishing at ADJACENT positions are paired (the second row a single pair): 45 % of the
+      // even rows of the ragged case.  Round 6 tried rows up to 2 and 3 positions apart (runs of up to that
+      // many pairs) and did not ship them.
+      const bool ahead = (((mine & ~done) >> (w + 1)) & 1u) != 0u;
+      pair = partner_on && ((mine >> w) & 1u) != 0u && ahead && ((R + half0) & 1) == 0 &&
              ((done >> w) & 1u) == 0u;
-      f32x4 nxt = g[w + 1];
-#pragma unroll
-      for (int k = 2; k <= HBK_RS_PAIR_DIST; ++k) {
-        if (w + k < W && d == k) nxt = g[w + k];
-      }
+      const f32x4 nxt = g[w + 1];
       // turn e: the octet stores the pair of its lane group e
       // (every DPP move outside any lane-dependent condition: a source lane that is masked off reads as 0)
       const int p_i = pair ? 1 : 0;
@@ -200,7 +166,7 @@ __device__ inline void rs_store_pairs(const GCol& c, const ReduceJob& job, int32
           rs_store_row<f32x4, F16>(c, job, odd_group ? R : r_odd + 1, sub, odd_group ? g[w] : second);
         }
       }
-      if (pair) done |= (1u << w) | (1u << (w + d));
+      if (pair) done |= 3u << w;
     }
     if (((mine & ~done) >> w) & 1u) rs_store_row<f32x4, F16>(c, job, R, sub, g[w]);
   }
@@ -330,7 +296,7 @@ __device__ __attribute__((noinline)) void rs_long_runs(RsLds& L, const RsLongArg
         const int32_t seg = L.sseg[q < end ? q : end - 1];
         const uint64_t off = a.seg_is_offset ? (uint64_t)(uint32_t)seg : (uint64_t)(uint32_t)seg * (uint32_t)a.stride;
         g[b] = zero_v<V>();
-        if (a.live && q < end) g[b] = HBK_GRAD_LOAD(reinterpret_cast<const V*>(a.grad + off + (uint64_t)sub * VE));
+        if (a.live && q < end) g[b] = *reinterpret_cast<const V*>(a.grad + off + (uint64_t)sub * VE);
       }
     };
     V g[WB], gn[WB];
@@ -361,19 +327,15 @@ __device__ __attribute__((noinline)) void rs_long_runs(RsLds& L, const RsLongArg
     if (wave == 0 && grp == 0 && a.live) {
       const V acc = carry[sub];
       if (a.one_chunk && (a.emit || !stepping)) {   // (written once, not read again by this kernel: rs_store_row)
-#if HBK_RS_OUT_NT
         __builtin_nontemporal_store(acc, o);
-#else
-        *o = acc;
-#endif
       } else if (!a.one_chunk) {
         *o = acc;   // (the step of a row of several chunks is taken once, behind the last chunk)
       }
       if (a.one_chunk && stepping) {
         const int64_t toff = (int64_t)(a.base + L.roff[u]) * a.tpitch + (int64_t)sub * VE;
-        const V tv = HBK_STEP_LOAD(reinterpret_cast<const V*>(a.table + toff));
+        const V tv = __builtin_nontemporal_load(reinterpret_cast<const V*>(a.table + toff));
         V av = zero_v<V>();
-        if (adagrad) av = HBK_STEP_LOAD(reinterpret_cast<const V*>(a.accum + toff));
+        if (adagrad) av = __builtin_nontemporal_load(reinterpret_cast<const V*>(a.accum + toff));
         // (step_row, lookup_bwd.hip)
         if (adagrad) {
           const V acc2 = av + acc * acc;
@@ -394,7 +356,7 @@ __device__ inline void rowsort_reduce(const GCol& c, const ReduceJob& job, RsLds
   constexpr bool adagrad = STEP == 2;
   // gradient rows a lane keeps in flight (with the step, the table / accumulator rows of the rows
   // that finish in a batch travel together: register budget of 128)
-  constexpr int W = STEP == 2 ? HBK_RS_W2 : STEP == 1 ? HBK_RS_W1 : HBK_RS_W0;
+  constexpr int W = rs_walk_width(STEP);
   const int tid = (int)threadIdx.x;
   const int lane = tid & (kWave - 1), wave = tid >> 6;
   // (F16: the caller has looked -- rows of 16 floats in four 16-byte chunks, packed pairs, gradient rows by number)
@@ -404,7 +366,7 @@ __device__ inline void rowsort_reduce(const GCol& c, const ReduceJob& job, RsLds
   const int groups = kBlock >> lpr_log2;
   const int my_group = tid >> lpr_log2;
   // rows of 64 bytes (dim 16, four 16-byte chunks) leave as whole 128-byte lines where they can
-  const bool pair_rows = HBK_RS_PAIR_STORES != 0 && sizeof(V) == 16 && (F16 || (lpr_log2 == 2 && c.chunks == 4 &&
+  const bool pair_rows = sizeof(V) == 16 && (F16 || (lpr_log2 == 2 && c.chunks == 4 &&
                          c.dim == 16)) && ((uintptr_t)job.out_vals & 63u) == 0u;
   const int half0 = (int)(((uintptr_t)job.out_vals >> 6) & 1u);
   const int32_t n_pairs = job.n_pairs;
@@ -445,7 +407,7 @@ __device__ inline void rowsort_reduce(const GCol& c, const ReduceJob& job, RsLds
 #pragma unroll
       for (int k = 0; k < PT; ++k) {
         const int32_t e = cb + k * kBlock + tid;
-        r_[k] = HBK_PAIR_LOAD(prow + (e < ce ? e : ce - 1));
+        r_[k] = prow[e < ce ? e : ce - 1];
       }
     }
     if (packed) {
@@ -461,7 +423,7 @@ __device__ inline void rowsort_reduce(const GCol& c, const ReduceJob& job, RsLds
 #pragma unroll
       for (int k = 0; k < PT; ++k) {
         const int32_t e = cb + k * kBlock + tid;
-        seg_[k] = HBK_PAIR_LOAD(pseg + (e < ce ? e : ce - 1));
+        seg_[k] = pseg[e < ce ? e : ce - 1];
       }
     } else {
 #pragma unroll
@@ -542,12 +504,7 @@ __device__ inline void rowsort_reduce(const GCol& c, const ReduceJob& job, RsLds
     }
   }
   __syncthreads();
-#ifdef HBK_RS_PROBE_ARRIVAL
-  const int32_t n_rows_scan = scan_bitmap(L.present, L.pre);
-  const int32_t n_rows_job = one_chunk ? n_pairs : n_rows_scan;
-#else
   const int32_t n_rows_job = scan_bitmap(L.present, L.pre);
-#endif
   // One global atomic per job claims the output range; a returning device-scope atomic takes
   // microseconds under load: its round trip runs beside C-E.  Step only: just the count is wanted.
   int32_t claimed = 0;
@@ -643,9 +600,7 @@ __device__ inline void rowsort_reduce(const GCol& c, const ReduceJob& job, RsLds
       if (valid) {
         const int w = (int)(off_[k] >> 5);
         u = pr[w] + (uint32_t)__builtin_popcount(bm[w] & ((1u << (off_[k] & 31u)) - 1u));
-        if (HBK_RS_ROWS_FROM_ROFF || stepping || !one_chunk) {
-          L.roff[u] = (uint16_t)off_[k];   // (every pair of the row: same value)
-        }
+        L.roff[u] = (uint16_t)off_[k];   // (every pair of the row: same value)
       }
       int32_t tk = 0;
       bool done = !valid;
@@ -714,16 +669,9 @@ __device__ inline void rowsort_reduce(const GCol& c, const ReduceJob& job, RsLds
 #pragma unroll
     for (int k = 0; k < PT; ++k) {
       if (u_[k] != ~0u) {
-#ifdef HBK_RS_PROBE_ARRIVAL   // probe builds (results wrong): every pair its own row, walked in ARRIVAL order --
-                              // what the walk costs when the jobs of a column read the gradient block in step
-        const int pos = k * kBlock + tid;
-        L.sseg[pos] = seg_[k];
-        L.su[pos] = (uint16_t)pos;
-#else
         const int pos = (int)(L.cnt[u_[k]] & kRsMask) + tk_[k];
         L.sseg[pos] = seg_[k];
         L.su[pos] = (uint16_t)u_[k];
-#endif
       }
     }
     if (cb == 0 && emit && tid == kBlock - 1) L.base_u = job.out_base + claimed;
@@ -900,9 +848,9 @@ __device__ inline void rowsort_reduce(const GCol& c, const ReduceJob& job, RsLds
             if (STEP == 2) av[STEP == 2 ? w : 0] = zero_v<V>();
             if ((mine >> w & 1u) && live) {
               const int64_t toff = (int64_t)(base + L.roff[uu[w]]) * c.tpitch + (int64_t)sub * VE;
-              tv[STEP ? w : 0] = HBK_STEP_LOAD(reinterpret_cast<const V*>(c.table + toff));
+              tv[STEP ? w : 0] = __builtin_nontemporal_load(reinterpret_cast<const V*>(c.table + toff));
               if (STEP == 2) {
-                av[STEP == 2 ? w : 0] = HBK_STEP_LOAD(reinterpret_cast<const V*>(c.accum + toff));
+                av[STEP == 2 ? w : 0] = __builtin_nontemporal_load(reinterpret_cast<const V*>(c.accum + toff));
               }
             }
           }
@@ -923,7 +871,7 @@ __device__ inline void rowsort_reduce(const GCol& c, const ReduceJob& job, RsLds
             }
           }
         }
-        if constexpr (HBK_RS_PAIR_STORES && sizeof(V) == 16 && STEP == 0) {
+        if constexpr (sizeof(V) == 16 && STEP == 0) {
           // (the paired stores are cooperative: a lane group with nothing to emit lends its lanes)
           if (pair_rows && one_chunk && !stepping) {
             rs_store_pairs<W, F16>(c, job, base_u, half0, uu, g, mine, lane, sub);
@@ -975,9 +923,9 @@ __device__ inline void rowsort_reduce(const GCol& c, const ReduceJob& job, RsLds
         if (one_chunk && stepping) {
           if (emit) rs_store_row<V, F16>(c, job, base_u + (int32_t)u, sub, acc);
           const int64_t toff = (int64_t)(base + L.roff[u]) * c.tpitch + (int64_t)sub * VE;
-          const V tv = HBK_STEP_LOAD(reinterpret_cast<const V*>(c.table + toff));
+          const V tv = __builtin_nontemporal_load(reinterpret_cast<const V*>(c.table + toff));
           V av = zero_v<V>();
-          if (adagrad) av = HBK_STEP_LOAD(reinterpret_cast<const V*>(c.accum + toff));
+          if (adagrad) av = __builtin_nontemporal_load(reinterpret_cast<const V*>(c.accum + toff));
           step_row<V>(c, adagrad, lr, toff, acc, tv, av);
         } else if (one_chunk) {
           rs_store_row<V, F16>(c, job, base_u + (int32_t)u, sub, acc);
@@ -1026,11 +974,7 @@ __device__ inline void rowsort_reduce(const GCol& c, const ReduceJob& job, RsLds
   // the row numbers, sorted.  One chunk: the chunk's row index IS the output rank, and roff[] holds
   // every row's offset: consecutive lanes write consecutive entries (whole lines per store
   // instruction).  Several chunks: straight from the job's bitmap.
-#ifdef HBK_RS_NO_ROWNUM   // probe builds: what the row-number stores cost (results are then wrong)
-  if (false) {
-#else
-  if (emit && one_chunk && HBK_RS_ROWS_FROM_ROFF) {
-#endif
+  if (emit && one_chunk) {
     for (int u = tid; u < n_rows_job; u += kBlock) {
       job.out_rows[base_u + u] = (int64_t)base + (int64_t)L.roff[u];
     }
@@ -1040,11 +984,7 @@ __device__ inline void rowsort_reduce(const GCol& c, const ReduceJob& job, RsLds
       int64_t* o = job.out_rows + base_u + (int32_t)L.pre[w];
       const int64_t r0 = (int64_t)base + 32 * (int64_t)w;
       while (m != 0u) {
-#if HBK_RS_ROWNUM_NT
-        __builtin_nontemporal_store(r0 + __builtin_ctz(m), o++);   // (written once, like the rows)
-#else
         *o++ = r0 + __builtin_ctz(m);
-#endif
         m &= m - 1u;
       }
     }
@@ -1069,8 +1009,8 @@ __device__ inline void rowsort_reduce(const GCol& c, const ReduceJob& job, RsLds
           toff[k] = row * c.tpitch + (int64_t)sub * VE;
           g[k] = __builtin_nontemporal_load(reinterpret_cast<const V*>(
               job.out_vals + (int64_t)(base_u + i) * c.dim + (int64_t)sub * VE));
-          tv[k] = HBK_STEP_LOAD(reinterpret_cast<const V*>(c.table + toff[k]));
-          if (adagrad) av[k] = HBK_STEP_LOAD(reinterpret_cast<const V*>(c.accum + toff[k]));
+          tv[k] = __builtin_nontemporal_load(reinterpret_cast<const V*>(c.table + toff[k]));
+          if (adagrad) av[k] = __builtin_nontemporal_load(reinterpret_cast<const V*>(c.accum + toff[k]));
         }
       }
 #pragma unroll
@@ -1081,13 +1021,9 @@ __device__ inline void rowsort_reduce(const GCol& c, const ReduceJob& job, RsLds
   }
 }
 
-#ifndef HBK_RS_LB2
-#define HBK_RS_LB2 4   // workgroups per CU the Adagrad instantiation is compiled for
-#endif
 template <typename V, int STEP, bool DET = false>
-__global__ __launch_bounds__(kBlock, STEP == 2 ? HBK_RS_LB2 : 4) void bwd_rowsort_kernel(const GArgs a, const int4* desc,
-                                                               int slot0, int total,
-                                                               const int32_t* poison) {
+__global__ __launch_bounds__(kBlock, 4) void bwd_rowsort_kernel(const GArgs a, const int4* desc, int slot0,
+                                                                int total, const int32_t* poison) {
   __shared__ RsLds lds;
   if (poisoned(poison)) return;   // the grouping launch gave up: no descriptors, no pairs
   HBK_STAMP_BEGIN()
