@@ -388,6 +388,8 @@ def _declare(l):
     'hbk_hash_rehash_n': (C.c_int, [i32, vp, vp]),
     'hbk_hash_translate_runs_n': (C.c_int, [i32, vp, vp, vp, vp, vp, i32, vp]),
     'hbk_hash_translate_sequence_n': (C.c_int, [i32, vp, vp, vp, vp, i32, vp]),
+    'hbk_hash_translate_runs_lowp_n': (C.c_int, [i32, vp, vp, vp, vp, vp, vp, i32, vp]),
+    'hbk_hash_translate_sequence_lowp_n': (C.c_int, [i32, vp, vp, vp, vp, vp, i32, vp]),
     'hbk_hash_export_workspace_bytes': (C.c_int, [i32, vp, vp]),
     'hbk_hash_export_n': (C.c_int, [i32, vp, vp, vp]),
     'hbk_hash_store_rows_n': (C.c_int, [i32, vp, vp]),
@@ -417,6 +419,7 @@ def _declare(l):
     'hbk_sharded_set_hot_rows': (C.c_int, [vp, vp]),
     'hbk_sharded_set_max_norms': (C.c_int, [vp, vp]),
     'hbk_sharded_set_hash_tables': (C.c_int, [vp, vp]),
+    'hbk_sharded_set_lowp_hash_tables': (C.c_int, [vp, vp, vp, i32]),
     'hbk_sharded_lookup_fwd': (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
     'hbk_sharded_lookup_fwd_weighted': (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     'hbk_sharded_prefetch_on': (C.c_int, [vp, vp, vp, vp]),

@@ -86,7 +86,8 @@
 // rounding of the apply) and stores whole 4-byte words of two elements.  HashCol has no spare field, so the element
 // code rides in the bits of group_log2 above kElemShift, which only the LOWP instantiations mask: the others are
 // the kernels they were, instruction for instruction.  A launch that writes no row -- a find, the counting phase of a
-// filtered table -- is the fp32 kernel as it is.
+// filtered table -- is the fp32 kernel as it is.  hbk_hash_translate_runs_lowp_n and hbk_hash_translate_sequence_lowp_n
+// are the same step for the other two sources of work: LOWP = true over RunsArgs / SeqArgs, inserting launches only.
 #include <math.h>
 
 #include "hash_common.h"
@@ -783,6 +784,24 @@ int check_column(const char* who, int32_t c, const hbk_hash_column_t& h) {
   return HBK_OK;
 }
 
+// what the 16-bit entries add to check_column for one column: its element code and the layout of whole 4-byte words
+int check_lowp_column(const char* who, int32_t c, const hbk_hash_column_t& h, int32_t code) {
+  HBK_REQUIRE(code == HBK_LOWP_BF16 || code == HBK_LOWP_FP16,
+              "%s: column %d: table_dtypes must be HBK_LOWP_BF16 (%d) or HBK_LOWP_FP16 (%d), got %d", who, c,
+              HBK_LOWP_BF16, HBK_LOWP_FP16, code);
+  if (h.table != nullptr) {
+    HBK_REQUIRE((h.dim & 1) == 0, "%s: column %d: dim must be even on a 16-bit table (rows are written as 4-byte "
+                "words), got %d", who, c, h.dim);
+    HBK_REQUIRE((h.table_pitch & 1) == 0, "%s: column %d: table_pitch must be even on a 16-bit table, got %d", who, c,
+                h.table_pitch);
+    HBK_REQUIRE(((uintptr_t)h.table & 3) == 0, "%s: column %d: table must be 4-byte aligned", who, c);
+  }
+  HBK_REQUIRE(code != HBK_LOWP_FP16 || h.init_scale <= 65504.0f,
+              "%s: column %d: init_scale %g is above 65504, the largest fp16: a start value would round to infinity",
+              who, c, (double)h.init_scale);
+  return HBK_OK;
+}
+
 // the kernel's view of one column; returns its tiles.  elem: 0, or the element code of a 16-bit table for a LOWP
 // kernel (which alone looks at it)
 int64_t describe_column(const hbk_hash_column_t& h, int32_t insert, HashCol* out, int32_t elem = 0) {
@@ -1043,17 +1062,19 @@ inline AdmitCol* admit_part(ExpiringArgs&) { return nullptr; }
 inline AdmitCol* admit_part(ExpiringAdmitArgs& a) { return a.f; }
 
 // One pass over all runs of all columns with `kernel`: a launch takes up to kMaxRunsPerLaunch non-empty runs of
-// up to kMaxColsPerLaunch columns (a column whose runs straddle two launches is described in both).
+// up to kMaxColsPerLaunch columns (a column whose runs straddle two launches is described in both).  dtypes: the
+// element codes for a LOWP kernel, or NULL for every other kernel (launch_columns below).
 template <class Base>
 int launch_runs(const char* who, int32_t n_cols, const hbk_hash_column_t* cols, const hbk_hash_expiry_t* exp,
-                const hbk_hash_admission_t* adm, const int32_t* n_runs, const hbk_hash_run_t* const* runs,
-                int32_t insert, void (*kernel)(const RunsArgs<Base>), hipStream_t stream) {
+                const hbk_hash_admission_t* adm, const int32_t* dtypes, const int32_t* n_runs,
+                const hbk_hash_run_t* const* runs, int32_t insert, void (*kernel)(const RunsArgs<Base>),
+                hipStream_t stream) {
   int32_t c = 0, r = 0;   // the next run to place
   while (c < n_cols) {
     RunsArgs<Base> args;
     HashArgs& h = hash_part(static_cast<Base&>(args));
     int32_t k = 0, nr = 0, described = -1;
-    int64_t tiles = 0;
+    int64_t tiles = 0, keys_per_block = 0;   // keys_per_block: of the column described last
     h.tile_start[0] = 0;
     args.run_tile_start[0] = 0;
     while (c < n_cols && nr < kMaxRunsPerLaunch) {
@@ -1073,13 +1094,13 @@ int launch_runs(const char* who, int32_t n_cols, const hbk_hash_column_t* cols, 
         col.keys = nullptr;
         col.slots = nullptr;
         col.n_keys = 0;
-        (void)describe_column(col, insert, &h.col[k]);
+        (void)describe_column(col, insert, &h.col[k], dtypes != nullptr ? dtypes[c] : 0);
         if (ExpiryCol* e = expiry_part(static_cast<Base&>(args))) describe_expiry(exp[c], e + k);
         if (AdmitCol* f = admit_part(static_cast<Base&>(args))) describe_admission(adm[c], f + k);
+        keys_per_block = (int64_t)(kBlock >> pow2_log2(col.slab_size)) * kKeys;   // (describe_column's tiling)
         described = c;
         ++k;
       }
-      const int64_t keys_per_block = (int64_t)(kBlock >> h.col[k - 1].group_log2) * kKeys;
       tiles += (run.n_keys + keys_per_block - 1) / keys_per_block;
       HBK_REQUIRE(tiles < (1ll << 31), "%s: grid too large", who);
       args.run[nr].keys = run.keys;
@@ -1106,14 +1127,20 @@ int launch_runs(const char* who, int32_t n_cols, const hbk_hash_column_t* cols, 
 // The four translate entries over keys that arrive as runs: one launch (two for filtered tables: every counting
 // launch of the call before any admitting one) while the non-empty runs stay within
 // HBK_HASH_MAX_RUNS_PER_LAUNCH and the columns within 64.
-extern "C" int hbk_hash_translate_runs_n(int32_t n_cols, const hbk_hash_column_t* cols,
-                                         const hbk_hash_expiry_t* exp, const hbk_hash_admission_t* adm,
-                                         const int32_t* n_runs, const hbk_hash_run_t* const* runs,
-                                         int32_t insert, hbk_stream_t stream_) {
-  using namespace hbk;
-  const char* who = "hash_translate_runs_n";
+//
+// translate_runs is both entries: `lowp` is the 16-bit one (hbk_hash_translate_runs_lowp_n), whose checks come after
+// the fp32 entry's for every column and whose INSERTING launches are the LOWP instantiations with the element codes;
+// a find and the counting phase of a filtered table write no row and are the fp32 launches as they are.
+namespace hbk {
+namespace {
+
+int translate_runs(const char* who, bool lowp, int32_t n_cols, const hbk_hash_column_t* cols,
+                   const hbk_hash_expiry_t* exp, const hbk_hash_admission_t* adm, const int32_t* table_dtypes,
+                   const int32_t* n_runs, const hbk_hash_run_t* const* runs, int32_t insert, hbk_stream_t stream_) {
   HBK_REQUIRE(n_cols >= 0, "%s: n_cols must be >= 0, got %d", who, n_cols);
+  if (lowp && n_cols == 0) return HBK_OK;
   HBK_REQUIRE(n_cols == 0 || cols != nullptr, "%s: cols is NULL", who);
+  HBK_REQUIRE(!lowp || table_dtypes != nullptr, "%s: table_dtypes is NULL", who);
   HBK_REQUIRE(n_cols == 0 || (n_runs != nullptr && runs != nullptr), "%s: n_runs or runs is NULL", who);
   const int64_t key_limit = exp != nullptr || adm != nullptr ? (1ll << 30) : (1ll << 31);
   for (int32_t c = 0; c < n_cols; ++c) {
@@ -1146,37 +1173,73 @@ extern "C" int hbk_hash_translate_runs_n(int32_t n_cols, const hbk_hash_column_t
     HBK_REQUIRE(exp == nullptr || total == 0 ||
                     (exp[c].last_seen != nullptr && exp[c].freq != nullptr && exp[c].step != nullptr),
                 "%s: column %d: NULL expiry buffer (last_seen, freq and step are needed with keys)", who, c);
+    if (lowp) {
+      if (int rc = check_lowp_column(who, c, whole, table_dtypes[c])) return rc;
+    }
   }
   hipStream_t stream = as_stream(stream_);
+  const int32_t* const no_dtypes = nullptr;
   if (adm != nullptr && insert != 0) {   // count, then admit
     if (exp != nullptr) {
       if (int rc = launch_runs<ExpiringAdmitArgs>(
-              who, n_cols, cols, exp, adm, n_runs, runs, insert,
+              who, n_cols, cols, exp, adm, no_dtypes, n_runs, runs, insert,
               hash_insert_expiring_kernel<false, 1, RunsArgs<ExpiringAdmitArgs>>, stream)) {
         return rc;
       }
-      return launch_runs<ExpiringAdmitArgs>(who, n_cols, cols, exp, adm, n_runs, runs, insert,
-                                            hash_insert_expiring_kernel<true, 2, RunsArgs<ExpiringAdmitArgs>>,
-                                            stream);
+      return launch_runs<ExpiringAdmitArgs>(
+          who, n_cols, cols, exp, adm, table_dtypes, n_runs, runs, insert,
+          lowp ? hash_insert_expiring_kernel<true, 2, RunsArgs<ExpiringAdmitArgs>, true>
+               : hash_insert_expiring_kernel<true, 2, RunsArgs<ExpiringAdmitArgs>>,
+          stream);
     }
-    if (int rc = launch_runs<AdmitArgs>(who, n_cols, cols, exp, adm, n_runs, runs, insert,
+    if (int rc = launch_runs<AdmitArgs>(who, n_cols, cols, exp, adm, no_dtypes, n_runs, runs, insert,
                                         hash_insert_kernel<false, 1, RunsArgs<AdmitArgs>>, stream)) {
       return rc;
     }
-    return launch_runs<AdmitArgs>(who, n_cols, cols, exp, adm, n_runs, runs, insert,
-                                  hash_insert_kernel<true, 2, RunsArgs<AdmitArgs>>, stream);
+    return launch_runs<AdmitArgs>(who, n_cols, cols, exp, adm, table_dtypes, n_runs, runs, insert,
+                                  lowp ? hash_insert_kernel<true, 2, RunsArgs<AdmitArgs>, true>
+                                       : hash_insert_kernel<true, 2, RunsArgs<AdmitArgs>>,
+                                  stream);
   }
   // no filter, or a find (which never touches the sketch)
+  if (insert == 0) {
+    if (exp != nullptr) {
+      return launch_runs<ExpiringArgs>(who, n_cols, cols, exp, nullptr, no_dtypes, n_runs, runs, insert,
+                                       hash_insert_expiring_kernel<false, 0, RunsArgs<ExpiringArgs>>, stream);
+    }
+    return launch_runs<HashArgs>(who, n_cols, cols, nullptr, nullptr, no_dtypes, n_runs, runs, insert,
+                                 hash_insert_kernel<false, 0, RunsArgs<HashArgs>>, stream);
+  }
   if (exp != nullptr) {
-    return launch_runs<ExpiringArgs>(who, n_cols, cols, exp, nullptr, n_runs, runs, insert,
-                                     insert != 0 ? hash_insert_expiring_kernel<true, 0, RunsArgs<ExpiringArgs>>
-                                                 : hash_insert_expiring_kernel<false, 0, RunsArgs<ExpiringArgs>>,
+    return launch_runs<ExpiringArgs>(who, n_cols, cols, exp, nullptr, table_dtypes, n_runs, runs, insert,
+                                     lowp ? hash_insert_expiring_kernel<true, 0, RunsArgs<ExpiringArgs>, true>
+                                          : hash_insert_expiring_kernel<true, 0, RunsArgs<ExpiringArgs>>,
                                      stream);
   }
-  return launch_runs<HashArgs>(who, n_cols, cols, nullptr, nullptr, n_runs, runs, insert,
-                               insert != 0 ? hash_insert_kernel<true, 0, RunsArgs<HashArgs>>
-                                           : hash_insert_kernel<false, 0, RunsArgs<HashArgs>>,
+  return launch_runs<HashArgs>(who, n_cols, cols, nullptr, nullptr, table_dtypes, n_runs, runs, insert,
+                               lowp ? hash_insert_kernel<true, 0, RunsArgs<HashArgs>, true>
+                                    : hash_insert_kernel<true, 0, RunsArgs<HashArgs>>,
                                stream);
+}
+
+}  // namespace
+}  // namespace hbk
+
+extern "C" int hbk_hash_translate_runs_n(int32_t n_cols, const hbk_hash_column_t* cols,
+                                         const hbk_hash_expiry_t* exp, const hbk_hash_admission_t* adm,
+                                         const int32_t* n_runs, const hbk_hash_run_t* const* runs,
+                                         int32_t insert, hbk_stream_t stream) {
+  return hbk::translate_runs("hash_translate_runs_n", false, n_cols, cols, exp, adm, nullptr, n_runs, runs, insert,
+                             stream);
+}
+
+extern "C" int hbk_hash_translate_runs_lowp_n(int32_t n_cols, const hbk_hash_column_t* cols,
+                                              const hbk_hash_expiry_t* exp, const hbk_hash_admission_t* adm,
+                                              const int32_t* table_dtypes, const int32_t* n_runs,
+                                              const hbk_hash_run_t* const* runs, int32_t insert,
+                                              hbk_stream_t stream) {
+  return hbk::translate_runs("hash_translate_runs_lowp_n", true, n_cols, cols, exp, adm, table_dtypes, n_runs, runs,
+                             insert, stream);
 }
 
 // ---- 16-bit tables --------------------------------------------------------------------------------------
@@ -1239,20 +1302,7 @@ extern "C" int hbk_hash_insert_lowp_n(int32_t n_cols, const hbk_hash_column_t* c
     if (adm != nullptr) {
       if (int rc = check_admission(who, c, h, adm[c])) return rc;
     }
-    const int32_t code = table_dtypes[c];
-    HBK_REQUIRE(code == HBK_LOWP_BF16 || code == HBK_LOWP_FP16,
-                "%s: column %d: table_dtypes must be HBK_LOWP_BF16 (%d) or HBK_LOWP_FP16 (%d), got %d", who, c,
-                HBK_LOWP_BF16, HBK_LOWP_FP16, code);
-    if (h.table != nullptr) {
-      HBK_REQUIRE((h.dim & 1) == 0, "%s: column %d: dim must be even on a 16-bit table (rows are written as 4-byte "
-                  "words), got %d", who, c, h.dim);
-      HBK_REQUIRE((h.table_pitch & 1) == 0, "%s: column %d: table_pitch must be even on a 16-bit table, got %d", who, c,
-                  h.table_pitch);
-      HBK_REQUIRE(((uintptr_t)h.table & 3) == 0, "%s: column %d: table must be 4-byte aligned", who, c);
-    }
-    HBK_REQUIRE(code != HBK_LOWP_FP16 || h.init_scale <= 65504.0f,
-                "%s: column %d: init_scale %g is above 65504, the largest fp16: a start value would round to infinity",
-                who, c, (double)h.init_scale);
+    if (int rc = check_lowp_column(who, c, h, table_dtypes[c])) return rc;
   }
   if (insert == 0) {
     // a find writes no row and touches no sketch: the find of the fp32 entry, as it is
@@ -1293,11 +1343,11 @@ static_assert(sizeof(SeqArgs<HashArgs>) <= 24576, "kernarg budget");
 static_assert(sizeof(SeqArgs<ExpiringAdmitArgs>) <= 24576, "kernarg budget");   // (64 columns fit: no smaller chunk)
 
 // One pass over the positions of all columns with `kernel`: up to kMaxColsPerLaunch columns with positions per
-// launch.
+// launch.  dtypes as for launch_runs.
 template <class Base>
 int launch_sequences(const char* who, int32_t n_cols, const hbk_hash_column_t* cols, const hbk_hash_expiry_t* exp,
-                     const hbk_hash_admission_t* adm, const hbk_hash_sequence_t* seq, int32_t insert,
-                     void (*kernel)(const SeqArgs<Base>), hipStream_t stream) {
+                     const hbk_hash_admission_t* adm, const int32_t* dtypes, const hbk_hash_sequence_t* seq,
+                     int32_t insert, void (*kernel)(const SeqArgs<Base>), hipStream_t stream) {
   int32_t c0 = 0;
   while (c0 < n_cols) {
     SeqArgs<Base> args;
@@ -1312,7 +1362,7 @@ int launch_sequences(const char* who, int32_t n_cols, const hbk_hash_column_t* c
       if (positions == 0) continue;
       hbk_hash_column_t col = cols[c];   // (the kernel's n_keys: the positions; its keys: the flat ids)
       col.n_keys = positions;
-      tiles += describe_column(col, insert, &h.col[k]);
+      tiles += describe_column(col, insert, &h.col[k], dtypes != nullptr ? dtypes[c] : 0);
       HBK_REQUIRE(tiles < (1ll << 31), "%s: grid too large", who);
       if (ExpiryCol* e = expiry_part(static_cast<Base&>(args))) describe_expiry(exp[c], e + k);
       if (AdmitCol* f = admit_part(static_cast<Base&>(args))) describe_admission(adm[c], f + k);
@@ -1341,14 +1391,18 @@ int launch_sequences(const char* who, int32_t n_cols, const hbk_hash_column_t* c
 
 // The four translate entries over the first T ids of every sample, answers into a [B * T] slot grid: one launch
 // (two for filtered tables: every counting launch of the call before any admitting one) per 64 columns.
-extern "C" int hbk_hash_translate_sequence_n(int32_t n_cols, const hbk_hash_column_t* cols,
-                                             const hbk_hash_expiry_t* exp, const hbk_hash_admission_t* adm,
-                                             const hbk_hash_sequence_t* seq, int32_t insert,
-                                             hbk_stream_t stream_) {
-  using namespace hbk;
-  const char* who = "hash_translate_sequence_n";
+//
+// translate_sequence is both entries, as translate_runs above: `lowp` is hbk_hash_translate_sequence_lowp_n.
+namespace hbk {
+namespace {
+
+int translate_sequence(const char* who, bool lowp, int32_t n_cols, const hbk_hash_column_t* cols,
+                       const hbk_hash_expiry_t* exp, const hbk_hash_admission_t* adm, const int32_t* table_dtypes,
+                       const hbk_hash_sequence_t* seq, int32_t insert, hbk_stream_t stream_) {
   HBK_REQUIRE(n_cols >= 0, "%s: n_cols must be >= 0, got %d", who, n_cols);
+  if (lowp && n_cols == 0) return HBK_OK;
   HBK_REQUIRE(n_cols == 0 || cols != nullptr, "%s: cols is NULL", who);
+  HBK_REQUIRE(!lowp || table_dtypes != nullptr, "%s: table_dtypes is NULL", who);
   HBK_REQUIRE(n_cols == 0 || seq != nullptr, "%s: seq is NULL", who);
   const int64_t limit = exp != nullptr || adm != nullptr ? (1ll << 30) : (1ll << 31);
   for (int32_t c = 0; c < n_cols; ++c) {
@@ -1388,35 +1442,70 @@ extern "C" int hbk_hash_translate_sequence_n(int32_t n_cols, const hbk_hash_colu
     HBK_REQUIRE(exp == nullptr || positions == 0 ||
                     (exp[c].last_seen != nullptr && exp[c].freq != nullptr && exp[c].step != nullptr),
                 "%s: column %d: NULL expiry buffer (last_seen, freq and step are needed with B * T > 0)", who, c);
+    if (lowp) {
+      if (int rc = check_lowp_column(who, c, whole, table_dtypes[c])) return rc;
+    }
   }
   hipStream_t stream = as_stream(stream_);
+  const int32_t* const no_dtypes = nullptr;
   if (adm != nullptr && insert != 0) {   // count, then admit
     if (exp != nullptr) {
       if (int rc = launch_sequences<ExpiringAdmitArgs>(
-              who, n_cols, cols, exp, adm, seq, insert,
+              who, n_cols, cols, exp, adm, no_dtypes, seq, insert,
               hash_insert_expiring_kernel<false, 1, SeqArgs<ExpiringAdmitArgs>>, stream)) {
         return rc;
       }
-      return launch_sequences<ExpiringAdmitArgs>(who, n_cols, cols, exp, adm, seq, insert,
-                                                 hash_insert_expiring_kernel<true, 2, SeqArgs<ExpiringAdmitArgs>>,
-                                                 stream);
+      return launch_sequences<ExpiringAdmitArgs>(
+          who, n_cols, cols, exp, adm, table_dtypes, seq, insert,
+          lowp ? hash_insert_expiring_kernel<true, 2, SeqArgs<ExpiringAdmitArgs>, true>
+               : hash_insert_expiring_kernel<true, 2, SeqArgs<ExpiringAdmitArgs>>,
+          stream);
     }
-    if (int rc = launch_sequences<AdmitArgs>(who, n_cols, cols, exp, adm, seq, insert,
+    if (int rc = launch_sequences<AdmitArgs>(who, n_cols, cols, exp, adm, no_dtypes, seq, insert,
                                              hash_insert_kernel<false, 1, SeqArgs<AdmitArgs>>, stream)) {
       return rc;
     }
-    return launch_sequences<AdmitArgs>(who, n_cols, cols, exp, adm, seq, insert,
-                                       hash_insert_kernel<true, 2, SeqArgs<AdmitArgs>>, stream);
+    return launch_sequences<AdmitArgs>(who, n_cols, cols, exp, adm, table_dtypes, seq, insert,
+                                       lowp ? hash_insert_kernel<true, 2, SeqArgs<AdmitArgs>, true>
+                                            : hash_insert_kernel<true, 2, SeqArgs<AdmitArgs>>,
+                                       stream);
   }
   // no filter, or a find (which never touches the sketch)
+  if (insert == 0) {
+    if (exp != nullptr) {
+      return launch_sequences<ExpiringArgs>(who, n_cols, cols, exp, nullptr, no_dtypes, seq, insert,
+                                            hash_insert_expiring_kernel<false, 0, SeqArgs<ExpiringArgs>>, stream);
+    }
+    return launch_sequences<HashArgs>(who, n_cols, cols, nullptr, nullptr, no_dtypes, seq, insert,
+                                      hash_insert_kernel<false, 0, SeqArgs<HashArgs>>, stream);
+  }
   if (exp != nullptr) {
-    return launch_sequences<ExpiringArgs>(who, n_cols, cols, exp, nullptr, seq, insert,
-                                          insert != 0 ? hash_insert_expiring_kernel<true, 0, SeqArgs<ExpiringArgs>>
-                                                      : hash_insert_expiring_kernel<false, 0, SeqArgs<ExpiringArgs>>,
+    return launch_sequences<ExpiringArgs>(who, n_cols, cols, exp, nullptr, table_dtypes, seq, insert,
+                                          lowp ? hash_insert_expiring_kernel<true, 0, SeqArgs<ExpiringArgs>, true>
+                                               : hash_insert_expiring_kernel<true, 0, SeqArgs<ExpiringArgs>>,
                                           stream);
   }
-  return launch_sequences<HashArgs>(who, n_cols, cols, nullptr, nullptr, seq, insert,
-                                    insert != 0 ? hash_insert_kernel<true, 0, SeqArgs<HashArgs>>
-                                                : hash_insert_kernel<false, 0, SeqArgs<HashArgs>>,
+  return launch_sequences<HashArgs>(who, n_cols, cols, nullptr, nullptr, table_dtypes, seq, insert,
+                                    lowp ? hash_insert_kernel<true, 0, SeqArgs<HashArgs>, true>
+                                         : hash_insert_kernel<true, 0, SeqArgs<HashArgs>>,
                                     stream);
+}
+
+}  // namespace
+}  // namespace hbk
+
+extern "C" int hbk_hash_translate_sequence_n(int32_t n_cols, const hbk_hash_column_t* cols,
+                                             const hbk_hash_expiry_t* exp, const hbk_hash_admission_t* adm,
+                                             const hbk_hash_sequence_t* seq, int32_t insert,
+                                             hbk_stream_t stream) {
+  return hbk::translate_sequence("hash_translate_sequence_n", false, n_cols, cols, exp, adm, nullptr, seq, insert,
+                                 stream);
+}
+
+extern "C" int hbk_hash_translate_sequence_lowp_n(int32_t n_cols, const hbk_hash_column_t* cols,
+                                                  const hbk_hash_expiry_t* exp, const hbk_hash_admission_t* adm,
+                                                  const int32_t* table_dtypes, const hbk_hash_sequence_t* seq,
+                                                  int32_t insert, hbk_stream_t stream) {
+  return hbk::translate_sequence("hash_translate_sequence_lowp_n", true, n_cols, cols, exp, adm, table_dtypes, seq,
+                                 insert, stream);
 }

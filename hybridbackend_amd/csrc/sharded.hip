@@ -1243,9 +1243,19 @@ int translate_group(hbk_sharded* p, const Group& gr, IdsAt ids_at, int64_t* slot
       }
       run_ptrs[k] = runs.data() + k * W;
     }
-    const int rc = hbk_hash_translate_runs_n((int32_t)members.size(), cols.data(), expiring ? exp.data() : nullptr,
-                                             filtered ? adm.data() : nullptr, n_runs.data(), run_ptrs.data(),
-                                             insert ? 1 : 0, stream);
+    int rc;
+    if (!p->lowp.empty()) {
+      // 16-bit hash columns (hbk_sharded_set_lowp_hash_tables): the same kinds, the element codes beside them
+      std::vector<int32_t> elems(members.size());
+      for (size_t k = 0; k < members.size(); ++k) elems[k] = p->lowp[(size_t)(gr.c0 + members[k])];
+      rc = hbk_hash_translate_runs_lowp_n((int32_t)members.size(), cols.data(), expiring ? exp.data() : nullptr,
+                                          filtered ? adm.data() : nullptr, elems.data(), n_runs.data(),
+                                          run_ptrs.data(), insert ? 1 : 0, stream);
+    } else {
+      rc = hbk_hash_translate_runs_n((int32_t)members.size(), cols.data(), expiring ? exp.data() : nullptr,
+                                     filtered ? adm.data() : nullptr, n_runs.data(), run_ptrs.data(),
+                                     insert ? 1 : 0, stream);
+    }
     if (rc != HBK_OK) return rc;
   }
   return HBK_OK;
@@ -1254,15 +1264,20 @@ int translate_group(hbk_sharded* p, const Group& gr, IdsAt ids_at, int64_t* slot
 }  // namespace hbk
 
 // The hash columns of a plan (include/hbk.h): plan state like the max_norms, set by every rank for itself.
-extern "C" int hbk_sharded_set_hash_tables(hbk_sharded_t p, const hbk_sharded_hash_t* tables) {
-  using namespace hbk;
-  const char* who = "sharded_set_hash_tables";
-  HBK_REQUIRE(p != nullptr, "%s: plan is NULL", who);
+namespace hbk {
+namespace {
+
+// The checks both setters of hash columns make of `tables`; *any: a column has a table.  fp32_rows: the setter of fp32
+// hash columns, which a 16-bit plan refuses at the first table it meets.
+int check_hash_tables(const hbk_sharded* p, const char* who, const hbk_sharded_hash_t* tables, bool fp32_rows,
+                      bool* any_out) {
   bool any = false;
   for (int c = 0; tables != nullptr && c < p->N; ++c) {
     const hbk_sharded_hash_t& t = tables[c];
     if (t.keys_cache == nullptr) continue;
-    if (int rc = lowp_refuse(p, who, "a hash column's rows are fp32")) return rc;
+    if (fp32_rows) {
+      if (int rc = lowp_refuse(p, who, "a hash column's rows are fp32")) return rc;
+    }
     any = true;
     const hbk_sharded_column_t& col = p->cols[c];
     HBK_REQUIRE(col.bucket == 0, "%s: column %d: a hash column takes raw ids: its bucket must be 0, got %lld", who,
@@ -1281,10 +1296,93 @@ extern "C" int hbk_sharded_set_hash_tables(hbk_sharded_t p, const hbk_sharded_ha
     return fail(HBK_UNIMPLEMENTED, "%s: the plan is p2p-bound (hbk_sharded_p2p_bind): the p2p form has no "
                 "owner-side translate", who);
   }
+  *any_out = any;
+  return HBK_OK;
+}
+
+}  // namespace
+}  // namespace hbk
+
+extern "C" int hbk_sharded_set_hash_tables(hbk_sharded_t p, const hbk_sharded_hash_t* tables) {
+  using namespace hbk;
+  const char* who = "sharded_set_hash_tables";
+  HBK_REQUIRE(p != nullptr, "%s: plan is NULL", who);
+  bool any = false;
+  if (int rc = check_hash_tables(p, who, tables, true, &any)) return rc;
   p->hash.clear();
   if (any) p->hash.assign(tables, tables + p->N);
   p->any_hash = any;
   p->have_step = false;   // (a step translated under other tables is not differentiated)
+  return HBK_OK;
+}
+
+// 16-bit shards AND hash columns in one piece of plan state (include/hbk.h): the two setters above refuse each other,
+// this one registers both or neither.  Every check comes before the first change of the plan.
+extern "C" int hbk_sharded_set_lowp_hash_tables(hbk_sharded_t p, const hbk_sharded_hash_t* tables,
+                                                const int32_t* dtypes, int32_t wire) {
+  using namespace hbk;
+  const char* who = "sharded_set_lowp_hash_tables";
+  HBK_REQUIRE(p != nullptr, "%s: plan is NULL", who);
+  if (tables == nullptr || dtypes == nullptr) {
+    // the fp32 plan without hash columns that it was created as
+    p->hash.clear();
+    p->any_hash = false;
+    p->lowp.clear();
+    p->lowp_wire16 = false;
+    p->have_step = false;
+    p->rows_live = false;
+    p->fwd_open = p->ids_open = false;
+    return HBK_OK;
+  }
+  HBK_REQUIRE(wire == HBK_LOWP_WIRE_TABLE || wire == HBK_LOWP_WIRE_FLOAT,
+              "%s: wire must be HBK_LOWP_WIRE_TABLE or HBK_LOWP_WIRE_FLOAT, got %d", who, wire);
+  for (int c = 0; c < p->N; ++c) {
+    HBK_REQUIRE(dtypes[c] == HBK_LOWP_BF16 || dtypes[c] == HBK_LOWP_FP16,
+                "%s: column %d: dtype must be HBK_LOWP_BF16 or HBK_LOWP_FP16, got %d (all or nothing: a plan has "
+                "16-bit shards in every column or in none)", who, c, dtypes[c]);
+    HBK_REQUIRE(((uintptr_t)p->cols[c].shard & 1) == 0, "%s: column %d: shard must be 2-byte aligned", who, c);
+  }
+  if (p->wire_dtype == HBK_HALF) {
+    return fail(HBK_UNIMPLEMENTED, "%s: the plan was created with wire_dtype == HBK_HALF: a 16-bit plan sends its rows "
+                "in the table's own bits (HBK_LOWP_WIRE_TABLE) or as fp32, and its gradients as fp32", who);
+  }
+  for (int c = 0; c < p->N; ++c) {
+    if (p->max_norms[(size_t)c] != 0.0f) {
+      return fail(HBK_UNIMPLEMENTED, "%s: column %d has a max_norm (hbk_sharded_set_max_norms): the clip reads and "
+                  "the clipped step writes fp32 rows", who, c);
+    }
+  }
+  if (p->p2p_bound) {
+    return fail(HBK_UNIMPLEMENTED, "%s: the plan is p2p-bound (hbk_sharded_p2p_bind): the p2p form's owner gather "
+                "stores fp32 rows and has no owner-side translate", who);
+  }
+  bool any = false;
+  if (int rc = check_hash_tables(p, who, tables, false, &any)) return rc;
+  for (int c = 0; c < p->N; ++c) {
+    if (tables[c].keys_cache == nullptr) continue;
+    const hbk_sharded_column_t& col = p->cols[c];
+    // what hbk_hash_translate_runs_lowp_n and the 16-bit gathers (without wide_rows) would refuse inside the step
+    HBK_REQUIRE((col.dim & 1) == 0, "%s: column %d: dim must be even on a 16-bit hash column (new rows are written as "
+                "4-byte words), got %d", who, c, col.dim);
+    HBK_REQUIRE(col.dim <= 64 || col.dim % 4 == 0, "%s: column %d: dim %d: a 16-bit hash column wider than 64 needs "
+                "dim %% 4 == 0 (the bound of the 16-bit gathers)", who, c, col.dim);
+    HBK_REQUIRE(((uintptr_t)col.shard & 3) == 0, "%s: column %d: the shard of a 16-bit hash column must be 4-byte "
+                "aligned", who, c);
+    HBK_REQUIRE(dtypes[c] != HBK_LOWP_FP16 || tables[c].init_scale <= 65504.0f,
+                "%s: column %d: init_scale %g is above 65504, the largest fp16", who, c, (double)tables[c].init_scale);
+  }
+  // slots registered while the plan was an fp32 plan are dropped: no slot entry can run on a 16-bit plan
+  p->adam = SlotPair();
+  p->ftrl = SlotPair();
+  p->rowwise = SlotPair();
+  p->lowp.assign(dtypes, dtypes + p->N);
+  p->lowp_wire16 = wire == HBK_LOWP_WIRE_TABLE;
+  p->hash.clear();
+  if (any) p->hash.assign(tables, tables + p->N);
+  p->any_hash = any;
+  p->have_step = false;
+  p->rows_live = false;
+  p->fwd_open = p->ids_open = false;
   return HBK_OK;
 }
 
@@ -1726,9 +1824,10 @@ int fwd_gather(hbk_sharded_t p, hbk_stream_t stream_) {
       }
     }
     if (lowp) {
-      // 16-bit shards (never p2p, hashed or clipped: hbk_sharded_set_table_dtypes): the virtual columns just
-      // built, handed to the low-precision gathers -- rows as bits onto a 16-bit wire (the fused fp16 wire's
-      // addresses), or upcast into the fp32 reply
+      // 16-bit shards (never p2p or clipped: hbk_sharded_set_table_dtypes; hashed through
+      // hbk_sharded_set_lowp_hash_tables, whose columns carry ids = the translated slots, int64, divisor 1 from
+      // above): the virtual columns just built, handed to the low-precision gathers -- rows as bits onto a 16-bit
+      // wire (the fused fp16 wire's addresses), or upcast into the fp32 reply; a -1 slot is a zero row on both
       if (wire16) {
         std::vector<hbk_lowp_gather_column_t> lv(v.size());
         for (size_t i = 0; i < v.size(); ++i) {
@@ -2617,6 +2716,12 @@ extern "C" int hbk_sharded_set_table_dtypes(hbk_sharded_t p, const int32_t* dtyp
   const char* who = "sharded_set_table_dtypes";
   HBK_REQUIRE(p != nullptr, "%s: plan is NULL", who);
   if (dtypes == nullptr) {
+    if (!p->lowp.empty() && p->any_hash) {
+      // 16-bit hash columns (hbk_sharded_set_lowp_hash_tables) do not outlive the 16-bit plan: an fp32 translate
+      // would write 4-byte rows into their 2-byte shards
+      p->hash.clear();
+      p->any_hash = false;
+    }
     p->lowp.clear();
     p->lowp_wire16 = false;
     p->have_step = false;   // (a step of the other element type is not differentiated)

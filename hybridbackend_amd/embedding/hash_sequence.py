@@ -14,6 +14,11 @@ The gather over the slot grid and the whole backward already exist: :class:`Hash
 launch in front of the plain :class:`GroupLookup` (buckets 0) over the grid viewed as one id per position, and
 ``SequenceLookupGrad(hsl, ...)`` is its backward and optimizer step.
 
+16-bit tables (``HashTable(..., dtype=torch.bfloat16 / torch.float16)``): a list that is 16-bit THROUGHOUT goes through
+``hbk_hash_translate_sequence_lowp_n`` -- the same translate, whose inserting launch rounds the start row to the
+table's 16 bits -- and :class:`HashSequenceLookup` gathers with a ``LowpGroupLookup`` (fp32 outputs, the rows upcast
+exactly); :class:`LowpSequenceLookupGrad` is the step.  A list that mixes fp32 and 16-bit tables is refused by name.
+
 Tiered tables: :meth:`HashSequenceLookup.fault_in` brings back, before the call of a step, the spilled keys among
 the ids the call will read -- the first ``T`` ids of every sample and the pad id, never an id past ``T``
 (:func:`hash_missing_sequence`, ``hbk_hash_missing_n``).
@@ -29,6 +34,7 @@ import torch
 
 from hybridbackend_amd import _lib
 from hybridbackend_amd.embedding.cache import EMPTY_KEY
+from hybridbackend_amd.embedding.hashtable import LOWP_DTYPES
 from hybridbackend_amd.embedding.hashtable import TOMBSTONE_KEY
 from hybridbackend_amd.embedding.hashtable import _Plan
 from hybridbackend_amd.embedding.hashtable import _missing
@@ -43,6 +49,7 @@ from hybridbackend_amd.embedding.hashtable import remove_tables
 from hybridbackend_amd.embedding.hashtable import same_device
 from hybridbackend_amd.embedding.lookup import GroupLookup
 from hybridbackend_amd.embedding.lookup import max_norm_list
+from hybridbackend_amd.embedding.sequence import SequenceLookupGrad
 from hybridbackend_amd.embedding.sequence import per_column
 
 
@@ -50,8 +57,19 @@ def _bad(msg):
   return _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT, msg)
 
 
-_FP32_ONLY = ('hbk_hash_translate_sequence_n writes new rows, and the sequence gather reads them, as fp32 rows of '
-              '4 * dim bytes: hash-keyed sequence lookups take fp32 tables (HashGroupLookup serves 16-bit ones)')
+_ONE_DTYPE = ('one translate call writes new rows, and one gather reads them, as fp32 rows or as 16-bit rows: a '
+              'hash-keyed sequence lookup takes tables that are fp32 throughout or 16-bit throughout (two objects serve '
+              'a mix)')
+
+
+def _all_lowp(tables, what):
+  """True when every table has 16-bit rows, False when every table is fp32; a mix is refused, naming the first 16-bit
+  table."""
+  lowp = [t.dtype in LOWP_DTYPES for t in tables]
+  if lowp and all(lowp):
+    return True
+  require_fp32_tables(tables, what, _ONE_DTYPE)
+  return False
 
 
 def check_hash_sequence_args(tables, max_lens, pad_ids):
@@ -77,7 +95,8 @@ def check_hash_sequence_args(tables, max_lens, pad_ids):
 
 class _SeqPlan(_Plan):
   """:class:`_Plan` with one ``hbk_hash_sequence_t`` per column, grouped with the columns: ``seqs[c]`` is column
-  c's record.  One ``hbk_hash_translate_sequence_n`` call per table kind."""
+  c's record.  One ``hbk_hash_translate_sequence_n`` call per table kind; the groups of 16-bit tables (``dtypes[g]``
+  their element codes) go through ``hbk_hash_translate_sequence_lowp_n``."""
 
   def __init__(self, tables):
     super().__init__(tables)
@@ -95,8 +114,12 @@ class _SeqPlan(_Plan):
     f = _lib.lib().hbk_hash_translate_sequence_n
     if not self.groups:
       _lib.check(f(0, None, None, None, None, insert, stream))
-    for (_, _, cols, expiry, adm), seqs in zip(self.groups, self._seq_groups):
-      _lib.check(f(len(cols), cols, expiry, adm, seqs, insert, stream))
+    for (_, _, cols, expiry, adm), dtypes, seqs in zip(self.groups, self.dtypes, self._seq_groups):
+      if dtypes is not None:
+        _lib.check(_lib.lib().hbk_hash_translate_sequence_lowp_n(len(cols), cols, expiry, adm, dtypes, seqs, insert,
+                                                                 stream))
+      else:
+        _lib.check(f(len(cols), cols, expiry, adm, seqs, insert, stream))
 
 
 def _bind(plan, tables, ids, row_splits, max_lens, pad_ids, insert, outs, lengths=None):
@@ -150,7 +173,9 @@ def _bind(plan, tables, ids, row_splits, max_lens, pad_ids, insert, outs, length
 
 def hash_translate_sequence(tables, ids, row_splits=None, max_lens=None, pad_ids=None, insert=True, outs=None):
   """The first ``T_c`` ids of every sample -> row numbers, for N columns (``hbk_hash_translate_sequence_n``; plain,
-  expiring and filtered tables may be mixed: one entry call per kind, the filtered ones in two launches).
+  expiring and filtered tables may be mixed: one entry call per kind, the filtered ones in two launches).  The
+  tables are fp32 throughout or 16-bit throughout (``hbk_hash_translate_sequence_lowp_n``: a new row is the fp32
+  start row rounded to nearest even).
 
   ids[c]: int64 raw ids, row_splits[c]: int32 ``[B + 1]`` or None (one id per sample).  ``pad_ids``: None --
   positions past a sample's length are ``-1`` in the grid and touch nothing -- or the RAW id such positions look
@@ -162,7 +187,7 @@ def hash_translate_sequence(tables, ids, row_splits=None, max_lens=None, pad_ids
   on the effective id list (per sample its first ``min(len, T)`` ids, then the pad ids) would change them."""
   tables, ids = list(tables), list(ids)
   same_device(tables)
-  require_fp32_tables(tables, 'hash_translate_sequence', _FP32_ONLY)
+  _all_lowp(tables, 'hash_translate_sequence')
   max_lens, pad_ids = check_hash_sequence_args(tables, max_lens, pad_ids)
   plan = _SeqPlan(tables)
   grids, lengths, _ = _bind(plan, tables, ids, row_splits, max_lens, pad_ids, insert, outs)
@@ -209,14 +234,23 @@ class HashSequenceLookup:
   tensors), ``dims`` and :meth:`plain_lookup` what ``SequenceLookupGrad(hsl, accums=..., ...)`` reads of a
   lookup: the backward and optimizer step, every reduce plan, ``deterministic=True``, the clip, SGD, Adagrad,
   Lazy Adam and FTRL unchanged.  ``hash_tables`` are the :class:`HashTable` objects.
+
+  16-bit tables (all of them: a mix with fp32 tables is refused by name): the translate is
+  ``hbk_hash_translate_sequence_lowp_n``, :meth:`plain_lookup` a ``LowpGroupLookup`` with buckets 0 and
+  ``wide_rows=True`` -- outputs stay fp32, bit for bit those of the fp32 object over the upcast tables -- and the
+  step is :class:`LowpSequenceLookupGrad`.  ``max_norms`` is refused there by name; ``launch()``, captured graphs,
+  ``maybe_grow``, ``maybe_evict``, ``remove`` and ``fault_in`` are what they are on fp32 tables.
   """
 
   def __init__(self, tables, max_lens, pad_ids=None, max_norms=None, train=True):
     self.hash_tables = list(tables)
     same_device(self.hash_tables)
-    require_fp32_tables(self.hash_tables, 'HashSequenceLookup', _FP32_ONLY)
+    self.lowp = _all_lowp(self.hash_tables, 'HashSequenceLookup')
     self.max_lens, self.pad_ids = check_hash_sequence_args(self.hash_tables, max_lens, pad_ids)
     self.max_norms = max_norm_list(max_norms, len(self.hash_tables))
+    if self.lowp and any(self.max_norms):
+      raise _bad('HashSequenceLookup: max_norms is not supported for 16-bit tables (the clip reads and the clipped '
+                 'step writes fp32 rows)')
     self.train = bool(train)
     self.dims = [t.dim for t in self.hash_tables]
     self.rebind()
@@ -227,8 +261,12 @@ class HashSequenceLookup:
     call.  Slot numbers and tensor addresses changed: a ``SequenceLookupGrad`` built on this lookup before must
     be rebuilt (with the companions the rehash returned), and a captured graph captured again."""
     self.tables = [t.table for t in self.hash_tables]
-    self._plain = GroupLookup(self.tables, buckets=None, combiners='sum',
-                              max_norms=[m or None for m in self.max_norms])
+    if self.lowp:
+      from hybridbackend_amd.embedding.lowp import LowpGroupLookup   # pylint: disable=import-outside-toplevel
+      self._plain = LowpGroupLookup(self.tables, buckets=None, combiners='sum', wide_rows=True)
+    else:
+      self._plain = GroupLookup(self.tables, buckets=None, combiners='sum',
+                                max_norms=[m or None for m in self.max_norms])
     self._plan = _SeqPlan(self.hash_tables)
     self.grids = None
     self.lengths = None
@@ -323,3 +361,46 @@ class HashSequenceLookup:
     graphs): two foreign calls (three with filtered tables of both kinds), no allocation."""
     check_bound(self, self.hash_tables, self.tables)
     self._launch(stream)
+
+
+class LowpSequenceLookupGrad:
+  """Backward and optimizer step of a :class:`HashSequenceLookup` over 16-bit tables, the named form of
+  ``LowpLookupGrad(hsl.plain_lookup(), ...)`` over ``hsl.grids`` with the ``[B, T, dim]`` gradients viewed
+  ``[B * T, dim]`` -- what :class:`SequenceLookupGrad` is to the fp32 object.  The slots (``accums`` / ``moments`` /
+  ``adam`` / ``ftrl_slots`` / ``ftrl`` / ``row_accums`` / ``rowwise_adagrad``) are fp32 and have the tables' shapes;
+  ``deterministic``, ``rounding`` and ``seed`` are ``LowpLookupGrad``'s.  Truncated ids and zero padding are not in
+  the grid: they reach no gradient row and no slot; with ``pad_ids`` the pad row collects the gradient of every
+  padding position.  Rebuilt after a rehash, with the companions the rehash returned, as a ``SequenceLookupGrad``
+  is."""
+
+  def __init__(self, lookup, accums=None, moments=None, adam=None, ftrl_slots=None, ftrl=None, row_accums=None,
+               rowwise_adagrad=None, deterministic=False, rounding='nearest', seed=0):
+    if not isinstance(lookup, HashSequenceLookup) or not lookup.lowp:
+      raise _bad('LowpSequenceLookupGrad needs a HashSequenceLookup over 16-bit tables (fp32 tables go through '
+                 'SequenceLookupGrad)')
+    from hybridbackend_amd.embedding.lowp import LowpLookupGrad   # pylint: disable=import-outside-toplevel
+    self.lookup = lookup
+    self.inner = LowpLookupGrad(lookup.plain_lookup(), accums=accums, moments=moments, adam=adam,
+                                ftrl_slots=ftrl_slots, ftrl=ftrl, row_accums=row_accums,
+                                rowwise_adagrad=rowwise_adagrad, deterministic=deterministic, rounding=rounding,
+                                seed=seed)
+
+  @property
+  def step_counter(self):
+    return self.inner.step_counter
+
+  _rows_view = SequenceLookupGrad._rows_view   # pylint: disable=protected-access
+
+  def __call__(self, grads, apply_lr=0.0, optimizer='sgd', emit=True, finish=True, grids=None):
+    """grads[c]: the gradient of the last forward's ``outs[c]``.  Returns what ``LowpLookupGrad`` returns: per column
+    ``(unique_rows, grad_rows, n_unique)`` (capacity ``B * T``; slot numbers).  ``grids``: explicit slot grids for a
+    backward without a forward."""
+    check_current(self.lookup.hash_tables, self.inner.lookup.tables)
+    grids = self.lookup.grids if grids is None else list(grids)
+    if grids is None:
+      raise _bad('LowpSequenceLookupGrad: the lookup kept no grids: call it first, or pass grids=')
+    n = len(self.lookup)
+    if len(grads) != n or len(grids) != n:
+      raise _bad(f'expected {n} gradients and grids, got {len(grads)} and {len(grids)}')
+    rows = [self._rows_view(c, grads[c], int(grids[c].numel())) for c in range(n)]
+    return self.inner(grids, rows, None, apply_lr=apply_lr, optimizer=optimizer, emit=emit, finish=finish)

@@ -18,6 +18,7 @@ import torch
 
 from hybridbackend_amd import _lib
 from hybridbackend_amd.embedding import hashtable as _ht
+from hybridbackend_amd.embedding import lowp as _lowp
 from hybridbackend_amd.embedding import optimizer as _opt
 from hybridbackend_amd.embedding.sharded import ShardedGroupLookup
 
@@ -91,6 +92,10 @@ class ShardedHashGroupLookup(ShardedGroupLookup):
                      world_size=world_size, accums=accums, hot_rows=hot_rows, dedup=dedup, moments=moments, adam=adam,
                      ftrl_slots=ftrl_slots, ftrl=ftrl, max_norms=max_norms, row_accums=row_accums,
                      rowwise_adagrad=rowwise_adagrad)
+    self._init_stores(stores)
+
+  def _init_stores(self, stores):
+    """The last part of construction, shared with the subclasses: the host tier and its checks."""
     self.stores = None if stores is None else list(stores)
     self.last_restored = [0] * len(self.tables)
     try:
@@ -121,8 +126,8 @@ class ShardedHashGroupLookup(ShardedGroupLookup):
     self._current()
     return super()._plan()
 
-  def _plan_created(self):
-    """The tables' descriptors, right after the plan's creation; a refusal leaves no plan behind."""
+  def _hash_descriptors(self):
+    """The ``hbk_sharded_hash_t`` of every table, as the plan's setters take them."""
     n = len(self.tables)
     arr = (_lib.ShardedHash * n)()
     for c, t in enumerate(self.tables):
@@ -137,8 +142,15 @@ class ShardedHashGroupLookup(ShardedGroupLookup):
       if t.min_freq:
         t._describe_admission(h.adm)     # pylint: disable=protected-access
       h.insert = 1 if self.train else 0
+    return arr
+
+  def _set_hash_tables(self, arr):
+    return self._lib.hbk_sharded_set_hash_tables(self._plan_handle, arr)
+
+  def _plan_created(self):
+    """The tables' descriptors, right after the plan's creation; a refusal leaves no plan behind."""
     try:
-      _lib.check(self._lib.hbk_sharded_set_hash_tables(self._plan_handle, arr))
+      _lib.check(self._set_hash_tables(self._hash_descriptors()))
     except _lib.HbkError:
       self.close()
       raise
@@ -374,3 +386,135 @@ class ShardedHashGroupLookup(ShardedGroupLookup):
       paired = {name for name, k, _ in kinds if k is not None}
       self.rebind(**{name: [tuple(p) for p in xs] if name in paired else xs for name, xs in new.items()})
     return grown
+
+
+class LowpShardedHashGroupLookup(ShardedHashGroupLookup):
+  """N hash-keyed columns over 16-bit tables (``HashTable(..., dtype=torch.bfloat16 / torch.float16)``), each sharded
+  over the ranks by ``floormod(id, W)``: :class:`ShardedHashGroupLookup`'s forward and lifecycle over
+  ``hbk_sharded_set_lowp_hash_tables``, ``LowpShardedGroupLookup``'s backward and step.
+
+  Args:
+    tables16: this rank's :class:`HashTable` per column, every one of them 16-bit (bf16 and fp16 may be mixed; plain,
+      expiring and filtered ones too).
+    coll, combiners, dedup, train, stores, initial_accumulator_value: :class:`ShardedHashGroupLookup`'s.  Stores come
+      from ``HashSpillStore(dtype=)`` of the table's dtype.
+    wire: ``'table'`` (the default) -- the owner's rows cross the link in the table's own 16 bits, half the bytes of
+      fp32 and nothing rounded -- or ``'float'``: the owner upcasts.  Both give, bit for bit,
+      :class:`ShardedHashGroupLookup` over fp32 tables holding the upcast rows of the same keys.
+    accums / moments, adam / ftrl_slots, ftrl / row_accums, rowwise_adagrad: FP32 slots of the tables' shapes
+      (``[capacity, dim]``; row-wise Adagrad ``[capacity, 1]``) and the optimizer objects.  They are the companions
+      every lifecycle method moves with the keys.
+    rounding, seed: as ``LowpSparseApply``; rank k steps with ``rank_seed(seed, k)``, the noise keyed by the SLOT.
+
+  The owner's translate is ``hbk_hash_translate_runs_lowp_n``: a new row is the fp32 start row rounded to nearest
+  even.  ``backward(grads, apply_lr=, optimizer=, emit=, finish=)`` is the plan's emit backward -- slot numbers,
+  nothing sent for a ``-1`` -- followed by ``LowpSparseApply`` on ``tables[c].table``; with ``emit=False`` the slices
+  go into buffers this object owns.  ``rebind``, ``maybe_grow``, ``maybe_evict``, ``remove``, ``export_items`` /
+  ``import_items``, ``track_removals``, ``spill_to`` and ``fault_in_received`` are the base class's: rows travel in
+  the table's dtype, nothing is cast.  The rounding's step counter survives a :meth:`rebind`.
+
+  Refused by name: fp32 tables and a mix of fp32 and 16-bit tables, ``max_norms``, ``weight_grads``, ``wire_dtype``,
+  ``hot_rows``, ``p2p_bind``; ``sp_weights`` by the library (a weighted column needs a bucket); a ``dim`` the plan
+  refuses (odd, or wider than 64 with ``dim % 4 != 0``); ``PipelinedLookup`` over objects of this class."""
+
+  def __init__(self, tables16, coll, combiners='sum', wire='table', dedup=False, train=True, accums=None,   # pylint: disable=super-init-not-called
+               moments=None, adam=None, ftrl_slots=None, ftrl=None, row_accums=None, rowwise_adagrad=None,
+               rounding='nearest', seed=0, stores=None, initial_accumulator_value=0.1, max_norms=None,
+               weight_grads=False, wire_dtype=None, hot_rows=False):
+    what = 'LowpShardedHashGroupLookup'
+    self.tables = list(tables16)
+    _ht.same_device(self.tables)
+    if any(t.dtype not in _ht.LOWP_DTYPES for t in self.tables):
+      named = ', '.join(f'table {c}: {_ht._dtype_name(t.dtype)}' for c, t in enumerate(self.tables))   # pylint: disable=protected-access
+      raise _ht._bad(f'{what}: every table must be a 16-bit HashTable (dtype=torch.bfloat16 / torch.float16), got '   # pylint: disable=protected-access
+                     f'{named}: fp32 tables go through ShardedHashGroupLookup, a mix through two drivers')
+    # (the four arguments below exist to be refused by name: only their defaults pass)
+    if max_norms is not None:
+      raise _ht._bad(f'{what}: max_norms is not supported for 16-bit tables (the clip reads and the clipped step '   # pylint: disable=protected-access
+                     'writes fp32 rows)')
+    if weight_grads is not False and weight_grads is not None:
+      raise _ht._bad(f'{what}: weight_grads is not supported for 16-bit tables (the received rows are 16-bit)')   # pylint: disable=protected-access
+    if wire_dtype is not None:
+      raise _ht._bad(f"{what}: wire_dtype is not supported: a 16-bit plan names its wire with wire='table' | "   # pylint: disable=protected-access
+                     "'float' (the fp16 wire rounds what it sends)")
+    if hot_rows is not False and hot_rows is not None:
+      raise _ht._bad(f'{what}: hot_rows is not supported for 16-bit tables (the low-precision gathers stage '   # pylint: disable=protected-access
+                     'nothing)')
+    if wire not in _lowp._WIRES:   # pylint: disable=protected-access
+      raise _ht._bad(f"{what}: wire must be 'table' or 'float', got {wire!r}")   # pylint: disable=protected-access
+    _lowp.check_rounding(rounding, seed, [t.dtype for t in self.tables], what)
+    for c, t in enumerate(self.tables):
+      if t.dim > 64 and t.dim % 4:
+        raise _ht._bad(f'{what}: table {c}: dim {t.dim}: a sharded 16-bit hash table wider than 64 needs '   # pylint: disable=protected-access
+                       'dim % 4 == 0 (the bound of the 16-bit gathers of the plan)')
+    self.wire, self.rounding = wire, rounding
+    self.seed = int(seed)
+    self.rank_seed = _lowp.rank_seed(seed, int(getattr(coll, 'rank', 0)))
+    self.train = bool(train)
+    self.initial_accumulator_value = float(initial_accumulator_value)
+    self._rows = [t.table for t in self.tables]
+    self._apply = None
+    self._own = None   # emit=False: per column (unique_rows, grad_rows, n_unique) this object owns
+    ShardedGroupLookup.__init__(self, self._rows, coll, buckets=None, combiners=combiners, accums=accums, dedup=dedup,
+                                moments=moments, adam=adam, ftrl_slots=ftrl_slots, ftrl=ftrl, row_accums=row_accums,
+                                rowwise_adagrad=rowwise_adagrad)
+    self._init_stores(stores)
+
+  def _setup(self):
+    """The step of the tables as they are now: a ``LowpSparseApply`` over the current row and slot tensors (built
+    again by every :meth:`rebind`; the rounding's step counter carries over)."""
+    self._lib = _lib.lib()
+    old = self._apply
+    self._apply = _lowp.LowpSparseApply(self.shards, accums=self.accums, rounding=self.rounding, seed=self.rank_seed,
+                                        **_opt.slot_kwargs(self))
+    if old is not None:
+      self._apply.step_counter.copy_(old.step_counter)
+    self._own = None
+
+  def _create_plan(self):
+    # the slots live with the apply: a 16-bit plan takes none (its stepping entries are refused)
+    held = {cls.slot_kw: getattr(self, cls.slot_kw) for cls in _opt.TWO_SLOT.values()}
+    for kw in held:
+      setattr(self, kw, None)
+    try:
+      super()._create_plan()
+    finally:
+      for kw, slots in held.items():
+        setattr(self, kw, slots)
+
+  def _set_hash_tables(self, arr):
+    n = len(self.tables)
+    return self._lib.hbk_sharded_set_lowp_hash_tables(
+      self._plan_handle, arr, (C.c_int32 * n)(*[_ht.LOWP_DTYPES[t.dtype] for t in self.tables]),
+      _lowp._WIRES[self.wire])   # pylint: disable=protected-access
+
+  @property
+  def step_counter(self):
+    return self._apply.step_counter
+
+  def p2p_bind(self, outs):   # pylint: disable=unused-argument
+    raise _lib.HbkError(_lib.UNIMPLEMENTED, 'LowpShardedHashGroupLookup: p2p_bind is not supported (the p2p form '
+                        'has no owner-side translate and its owner gather stores fp32 rows)')
+
+  def _phase(self, *args, **kwargs):   # pylint: disable=unused-argument
+    raise _lib.HbkError(_lib.UNIMPLEMENTED, 'LowpShardedHashGroupLookup has no separate phase methods: the step runs '
+                        'inside the plan (__call__ / launch / backward)')
+
+  partition = owner_gather = stitch = stitch_bwd = owner_bwd = _phase
+
+  _own_slices = _lowp.LowpShardedGroupLookup._own_slices     # pylint: disable=protected-access
+  _apply_views = _lowp.LowpShardedGroupLookup._apply_views   # pylint: disable=protected-access
+
+  def backward(self, grads, apply_lr=0.0, outs=None, optimizer='sgd', emit=True, finish=True, weight_grads=None):
+    """Backward of the LAST forward step and, with ``apply_lr``, the optimizer step on the 16-bit tables.  Returns
+    per column the IndexedSlices of this rank's table ``(unique_rows, grad_rows, n_unique)`` -- ``unique_rows`` are
+    slot numbers -- equal to the fp32 driver's; ``emit=False`` (with ``apply_lr``): the slices go into buffers this
+    object owns and the triples are ``(None, None, n_unique)``.  ``optimizer``: 'sgd', 'adagrad', 'adam', 'ftrl' or
+    'rowwise_adagrad' (the slots given to the constructor); ``finish=True`` advances Adam's beta powers and the
+    rounding's step counter once, behind the step.  ``weight_grads`` is refused."""
+    if weight_grads is not False and weight_grads is not None:
+      raise _ht._bad('LowpShardedHashGroupLookup: weight_grads is not supported for 16-bit tables (the received rows '   # pylint: disable=protected-access
+                     'are 16-bit)')
+    self._current()
+    return _lowp.LowpShardedGroupLookup.backward(self, grads, apply_lr=apply_lr, outs=outs, optimizer=optimizer,
+                                                 emit=emit, finish=finish)

@@ -74,12 +74,17 @@ class _HashColumn:
   column is made (a table on the ``meta`` device allocates nothing and refuses what every table refuses)."""
 
   def _init_table_args(self, key, capacity, dimension, max_norm, dedup, slab_size, init_scale, seed, expiring,
-                       min_freq, sketch_depth, sketch_width, sketch_seed):
+                       min_freq, sketch_depth, sketch_width, sketch_seed, dtype=torch.float32):
     from hybridbackend_amd.embedding.lookup import max_norm_list
     self.key, self.capacity, self.dimension = key, int(capacity), int(dimension)
     self.table_args = dict(slab_size=int(slab_size), init_scale=float(init_scale), seed=int(seed),
                            expiring=bool(expiring), min_freq=int(min_freq), sketch_depth=sketch_depth,
                            sketch_width=sketch_width, sketch_seed=sketch_seed)
+    if dtype != torch.float32:
+      # (the default adds no argument: an fp32 column builds the table it always built; HashTable refuses an
+      # unknown dtype, an odd dim and an fp16 init_scale above 65504 when the probe below is made)
+      self.table_args['dtype'] = dtype
+    self.dtype = dtype
     self.expiring = bool(expiring)
     self._probe = HashTable(self.capacity, self.dimension, 'meta', **self.table_args)
     self.max_norm = None if max_norm is None else max_norm_list([max_norm], 1)[0]
@@ -105,14 +110,17 @@ class HashEmbeddingColumn(_HashColumn):
   ``sketch_*`` arguments are the table's, with its refusals.  ``combiner``, ``max_norm``, ``dedup`` and
   ``weight_feature_key`` are :class:`EmbeddingColumn`'s; per-id weights work on one rank only (the sharded step
   refuses weights on a column without a bucket, so a weighted hash column is refused when a layer is built over
-  more than one rank)."""
+  more than one rank).  ``dtype``: ``torch.float32`` (the default: nothing changes), ``torch.bfloat16`` or
+  ``torch.float16`` -- the column's table is ``HashTable(dtype=)`` with 2-byte rows (``dimension`` even, fp16 takes
+  ``init_scale <= 65504``; refused here, when the column is made) and fp32 optimizer slots.  All hash columns of one
+  layer share one dtype; on a 16-bit column ``max_norm`` and ``weight_feature_key`` are refused by the layer."""
 
   def __init__(self, key, capacity, dimension, combiner='mean', max_norm=None, dedup=False,
                weight_feature_key=None, slab_size=8, init_scale=1e-3, seed=0, expiring=False, min_freq=0,
-               sketch_depth=4, sketch_width=None, sketch_seed=0):
+               sketch_depth=4, sketch_width=None, sketch_seed=0, dtype=torch.float32):
     from hybridbackend_amd.embedding.lookup import _combiner_code
     self._init_table_args(key, capacity, dimension, max_norm, dedup, slab_size, init_scale, seed, expiring,
-                          min_freq, sketch_depth, sketch_width, sketch_seed)
+                          min_freq, sketch_depth, sketch_width, sketch_seed, dtype)
     _combiner_code(combiner)   # (refuses unknown names)
     self.combiner = combiner
     self.weight_feature_key = weight_feature_key
@@ -123,14 +131,14 @@ class HashSequenceEmbeddingColumn(_HashColumn):
   into ``[batch, max_len, dimension]``.  ``pad_id`` is a raw id, any int64 the table can store (not a sentinel
   of the table); None: the positions past a sample's length are zero rows.  A column on more than one rank
   needs a ``pad_id`` or ``SequenceFeatures(..., sharded_zero_padding=True)``.  The table arguments are
-  :class:`HashEmbeddingColumn`'s."""
+  :class:`HashEmbeddingColumn`'s, ``dtype`` included."""
 
   def __init__(self, key, capacity, dimension, max_len, pad_id=None, max_norm=None, dedup=False, slab_size=8,
                init_scale=1e-3, seed=0, expiring=False, min_freq=0, sketch_depth=4, sketch_width=None,
-               sketch_seed=0):
+               sketch_seed=0, dtype=torch.float32):
     from hybridbackend_amd.embedding.hash_sequence import check_hash_sequence_args
     self._init_table_args(key, capacity, dimension, max_norm, dedup, slab_size, init_scale, seed, expiring,
-                          min_freq, sketch_depth, sketch_width, sketch_seed)
+                          min_freq, sketch_depth, sketch_width, sketch_seed, dtype)
     (self.max_len,), (self.pad_id,) = check_hash_sequence_args([self._probe], max_len, pad_id)
 
 
@@ -144,8 +152,10 @@ class _TableLayer:
   W > 1), the optimizer slots, and the checkpoints."""
 
   def _init_tables(self, columns, device, coll, batch_size, init, initial_accumulator_value, optimizer,
-                   adam, ftrl, train=True, rowwise_adagrad=None, table_dtype=None, lowp_sharded=False):
+                   adam, ftrl, train=True, rowwise_adagrad=None, table_dtype=None, lowp_sharded=False,
+                   table_rounding='nearest', table_seed=0, what='DenseFeatures'):
     self.columns = list(columns)
+    self._check_hash_dtype(what, table_rounding, table_seed)
     self.device = torch.device(device)
     self.coll = coll
     self.train = bool(train)
@@ -178,6 +188,10 @@ class _TableLayer:
       self.weights = [w.to(table_dtype) if l else w for w, l in zip(self.weights, low)]
       like = [torch.empty((), dtype=torch.float32, device=self.device).expand(w.shape) if l else w
               for w, l in zip(self.weights, low)]
+    elif self.hash_dtype != torch.float32:
+      # 16-bit hash columns (HashEmbeddingColumn(dtype=)): their tables are built 16-bit, their slots stay fp32
+      like = [torch.empty((), dtype=torch.float32, device=self.device).expand(w.shape) if h is not None else w
+              for w, h in zip(self.weights, self.hash_tables)]
     # Adagrad accumulators (tf.train.AdagradOptimizer: initial_accumulator_value = 0.1)
     self.accums = None
     if initial_accumulator_value is not None:
@@ -256,9 +270,43 @@ class _TableLayer:
     # (the driver's own fill value: read only with accums, which the layer keeps only with a value of its own)
     kw = {} if self.accums is None else dict(accums=pick(self.accums),
                                              initial_accumulator_value=self._initial_accumulator_value)
+    if self.hash_dtype != torch.float32:
+      # 16-bit hash columns: the same forward and lifecycle, the step in the driver (fp32 slots, the layer's rounding)
+      from hybridbackend_amd.embedding.sharded_hash import LowpShardedHashGroupLookup   # pylint: disable=import-outside-toplevel
+      return LowpShardedHashGroupLookup(pick(self.hash_tables), self.coll, combiners=combiners, dedup=attr('dedup'),
+                                        train=self.train, rounding=self._hash_rounding, seed=self._hash_seed, **kw,
+                                        **self._two_slot_kw(self._hash))
     return ShardedHashGroupLookup(pick(self.hash_tables), self.coll, combiners=combiners, dedup=attr('dedup'),
                                   max_norms=attr('max_norm'), train=self.train, **kw,
                                   **self._two_slot_kw(self._hash))
+
+  def _check_hash_dtype(self, what, rounding, seed):
+    """The one dtype of the layer's hash columns (``hash_dtype``; fp32 without any) and everything a layer with
+    16-bit hash columns refuses, before any table is allocated."""
+    from hybridbackend_amd.embedding.lowp import check_rounding   # pylint: disable=import-outside-toplevel
+    cols = [col for col in self.columns if _is_hash(col)]
+    dtypes = {col.dtype for col in cols}
+    if len(dtypes) > 1:
+      named = ', '.join(f'{col.key!r}: {col.dtype}' for col in cols)
+      raise _bad(f'{what}: the hash columns of one layer share one dtype, as one HashGroupLookup holds fp32 or '
+                 f'16-bit tables ({named}): build two layers')
+    self.hash_dtype = dtypes.pop() if dtypes else torch.float32
+    self._hash_rounding, self._hash_seed = rounding, seed
+    if self.hash_dtype == torch.float32:
+      return
+    check_rounding(rounding, seed, [self.hash_dtype], f'{what}(table_rounding=, table_seed=)')
+    for col in cols:
+      if col.max_norm is not None:
+        raise _bad(f'{what}: hash column {col.key!r} is a {col.dtype} column with max_norm; the clip reads and the '
+                   'clipped step writes fp32 rows')
+      if getattr(col, 'weight_feature_key', None) is not None:
+        raise _bad(f'{what}: hash column {col.key!r} is a {col.dtype} column with weight_feature_key '
+                   f'{col.weight_feature_key!r}; per-id weights and their gradients read fp32 rows')
+
+  def _refuse_weight_grads(self, what, weight_grads):
+    if weight_grads and self._hash and self.hash_dtype != torch.float32:
+      raise _bad(f'{what}.backward(weight_grads=True): the layer has {self.hash_dtype} hash columns; weight '
+                 'gradients are not supported over 16-bit tables (hbk_group_lookup_bwd_weights reads fp32 rows)')
 
   def _hash_slot_kinds(self):
     """The layer's optimizer slots in the drivers' one order with their fill values (``sharded_hash.slot_kinds``):
@@ -456,6 +504,9 @@ class _TableLayer:
       for base in bases:
         d = {n: torch.from_numpy(np.array(load_full(prefix, n), copy=True))
              for n in names if n.startswith(base + '/items/')}
+        rows = base + '/items/rows'
+        if self.hash_tables[c].dtype == torch.bfloat16 and rows in d and d[rows].dtype == torch.int16:
+          d[rows] = d[rows].view(torch.bfloat16)   # (the saver keeps bfloat16 as its bit patterns)
         parts.append(HashExport.from_variables(base, d))
       exp = HashExport.cat(parts)
       slots = self._hash_companions(c)
@@ -537,6 +588,15 @@ class DenseFeatures(_TableLayer):
   the bucketed columns' -- and ``weight_feature_key`` on a hash column is then refused.  See ``set_step``,
   ``maybe_grow`` and ``maybe_evict``.  Spilling to a host tier, ``track_removals`` and delta exports are not
   driven by the layer: compose them on ``hash_tables``.
+
+  16-bit hash columns (``HashEmbeddingColumn(dtype=torch.bfloat16 / torch.float16)``; all hash columns of a layer
+  share one dtype, a mix is refused by name: two layers): the tables are ``HashTable(dtype=)``, the slots fp32, and
+  ``table_rounding`` / ``table_seed`` -- without ``table_dtype``, which stays the bucketed tables' argument and still
+  refuses a hash column -- are the rounding of the hash group's step.  On one rank the group goes through
+  ``HashGroupLookup`` + ``LowpLookupGrad``, on W > 1 ranks through ``LowpShardedHashGroupLookup`` (``wire='table'``).
+  ``set_step``, ``maybe_grow``, ``maybe_evict``, ``train=False``, ``save`` / ``restore`` (W ranks onto W') carry the
+  16-bit rows through the same ``export_items`` / ``import_items`` path: nothing is cast.  Refused by name on such a
+  layer: ``max_norm`` and ``weight_feature_key`` on a 16-bit hash column, ``backward(weight_grads=True)``.
   """
 
   def __init__(self, columns, device, coll=None, batch_size=0, init=None,
@@ -548,7 +608,8 @@ class DenseFeatures(_TableLayer):
     if table_dtype is not None:
       self._check_lowp(columns, coll, table_dtype, table_rounding, table_seed, lowp_sharded)
     self._init_tables(columns, device, coll, batch_size, init, initial_accumulator_value, optimizer,
-                      adam, ftrl, train, rowwise_adagrad, table_dtype, lowp_sharded)
+                      adam, ftrl, train, rowwise_adagrad, table_dtype, lowp_sharded, table_rounding, table_seed,
+                      'DenseFeatures')
     self._init_replica(aggregate_replicated, replicated_scale, 'DenseFeatures')
     for c in self._hash:
       col = self.columns[c]
@@ -619,9 +680,14 @@ class DenseFeatures(_TableLayer):
         self._rebuild_hash_grad()
 
   def _rebuild_hash_grad(self):
-    self._hash_grad = GroupLookupGrad(
-      self._hash_lookup.lookup, [self.accums[c] for c in self._hash] if self.accums is not None else None,
-      **self._two_slot_kw(self._hash))
+    accums = [self.accums[c] for c in self._hash] if self.accums is not None else None
+    if self.hash_dtype != torch.float32:
+      # 16-bit hash columns: HashGroupLookup put a LowpGroupLookup behind the translate; this is its step
+      from hybridbackend_amd.embedding.lowp import LowpLookupGrad   # pylint: disable=import-outside-toplevel
+      self._hash_grad = LowpLookupGrad(self._hash_lookup.lookup, accums, rounding=self._hash_rounding,
+                                       seed=self._hash_seed, **self._two_slot_kw(self._hash))
+      return
+    self._hash_grad = GroupLookupGrad(self._hash_lookup.lookup, accums, **self._two_slot_kw(self._hash))
 
   @staticmethod
   def _check_lowp(columns, coll, table_dtype, table_rounding, table_seed, lowp_sharded=False):
@@ -769,6 +835,7 @@ class DenseFeatures(_TableLayer):
     ids.  Refused after a forward of a layer built with ``train=False``."""
     _opt.two_slot_class(optimizer, self, "DenseFeatures(..., optimizer='{name}')")
     self._refuse_backward_of_a_find('DenseFeatures')
+    self._refuse_weight_grads('DenseFeatures', weight_grads)
     ids, splits, ws = self._last
     if grad.dim() != 2 or grad.shape[1] != self.width or grad.dtype != torch.float32:
       raise _lib.InvalidArgumentError(
@@ -915,16 +982,22 @@ class SequenceFeatures(_TableLayer):
   with combiner ``'sum'`` over the RAW-id grid ``sequence_id_grid`` builds (``batch * max_len`` ids of one sample
   each): ids past ``max_len`` are not in the grid, so they are not inserted, counted or kept fresh on any rank,
   and a pad id is required there too unless ``sharded_zero_padding`` is set (the packed ids are raw too).
-  ``train``, ``hash_tables``, ``set_step``, ``maybe_grow`` and ``maybe_evict`` are :class:`DenseFeatures`'."""
+  ``train``, ``hash_tables``, ``set_step``, ``maybe_grow`` and ``maybe_evict`` are :class:`DenseFeatures`'.
+
+  16-bit hash columns (``HashSequenceEmbeddingColumn(dtype=)``, one dtype per layer): on one rank
+  ``HashSequenceLookup`` + ``LowpSequenceLookupGrad``, on W > 1 ranks ``LowpShardedHashGroupLookup`` over the id grid
+  or, with ``sharded_zero_padding``, the packed form; ``table_rounding`` / ``table_seed`` are the rounding of their
+  step, and ``max_norm`` on such a column is refused by name."""
 
   def __init__(self, columns, device, coll=None, batch_size=0, init=None,
                initial_accumulator_value=None, optimizer=None, adam=None, ftrl=None, train=True,
                rowwise_adagrad=None, sharded_zero_padding=False, aggregate_replicated=False,
-               replicated_scale=None):
+               replicated_scale=None, table_rounding='nearest', table_seed=0):
     from hybridbackend_amd.embedding.hash_sequence import HashSequenceLookup
     from hybridbackend_amd.embedding.sequence import SequenceLookup, SequenceLookupGrad
     self._init_tables(columns, device, coll, batch_size, init, initial_accumulator_value, optimizer,
-                      adam, ftrl, train, rowwise_adagrad)
+                      adam, ftrl, train, rowwise_adagrad, table_rounding=table_rounding, table_seed=table_seed,
+                      what='SequenceFeatures')
     self._init_replica(aggregate_replicated, replicated_scale, 'SequenceFeatures')
     self.sharded_zero_padding = bool(sharded_zero_padding)
     for c in self._hash:
@@ -973,9 +1046,13 @@ class SequenceFeatures(_TableLayer):
 
   def _rebuild_hash_grad(self):
     from hybridbackend_amd.embedding.sequence import SequenceLookupGrad
-    self._hash_grad = SequenceLookupGrad(
-      self._hash_lookup, [self.accums[c] for c in self._hash] if self.accums is not None else None,
-      **self._two_slot_kw(self._hash))
+    accums = [self.accums[c] for c in self._hash] if self.accums is not None else None
+    if self.hash_dtype != torch.float32:
+      from hybridbackend_amd.embedding.hash_sequence import LowpSequenceLookupGrad   # pylint: disable=import-outside-toplevel
+      self._hash_grad = LowpSequenceLookupGrad(self._hash_lookup, accums, rounding=self._hash_rounding,
+                                               seed=self._hash_seed, **self._two_slot_kw(self._hash))
+      return
+    self._hash_grad = SequenceLookupGrad(self._hash_lookup, accums, **self._two_slot_kw(self._hash))
 
   def __call__(self, features):
     """features[key] = ``(values, row_splits)`` (int32/int64 ids, int32 ``[batch + 1]``), or an id vector

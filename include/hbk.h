@@ -1473,9 +1473,10 @@ int hbk_hash_insert_expiring_admit_n(int32_t n_cols, const hbk_hash_column_t* co
  * the matching fp32 entry refuses; NULL table_dtypes with n_cols > 0; a code other than HBK_LOWP_BF16 /
  * HBK_LOWP_FP16; with a table: an odd dim, an odd non-zero table_pitch, a table that is not 4-byte aligned;
  * HBK_LOWP_FP16 with init_scale > 65504 (a start value would round to infinity).  n_cols == 0 returns HBK_OK without
- * touching a device.  No workspace, no host synchronisation: capturable.  Not served here: keys that arrive as runs
- * or sequences (hbk_hash_translate_runs_n / hbk_hash_translate_sequence_n write fp32 rows).  Detected by the presence
- * of the symbol; the structs and the version are those of 0.2.0. */
+ * touching a device.  No workspace, no host synchronisation: capturable.  Keys that arrive as runs or sequences go
+ * through hbk_hash_translate_runs_lowp_n / hbk_hash_translate_sequence_lowp_n below (hbk_hash_translate_runs_n and
+ * hbk_hash_translate_sequence_n write fp32 rows).  Detected by the presence of the symbol; the structs and the version
+ * are those of 0.2.0. */
 int hbk_hash_insert_lowp_n(int32_t n_cols, const hbk_hash_column_t* cols,
                            const hbk_hash_expiry_t* exp    /* NULL: plain tables */,
                            const hbk_hash_admission_t* adm /* NULL: no filter */,
@@ -1520,6 +1521,30 @@ int hbk_hash_translate_runs_n(int32_t n_cols, const hbk_hash_column_t* cols,
                               const hbk_hash_admission_t* adm,   /* NULL, or [n_cols] */
                               const int32_t* n_runs, const hbk_hash_run_t* const* runs,
                               int32_t insert, hbk_stream_t stream);
+
+/* Runs over 16-bit tables: hbk_hash_translate_runs_n for tables whose rows are bf16 / fp16, what the owner of a
+ * sharded 16-bit hash table calls.  The call IS hbk_hash_translate_runs_n with the same cols, exp, adm, n_runs and runs
+ * -- placement, tombstone reuse, last_seen / freq, the two phases of a filtered table, the counters, how a tile finds
+ * its run, the chunking beyond HBK_HASH_MAX_RUNS_PER_LAUNCH runs or 64 columns -- except for the row the inserting
+ * launch writes, which is hbk_hash_insert_lowp_n's: cols[c].table points at 2-byte elements of table_dtypes[c] (host
+ * int32 [n_cols], HBK_LOWP_BF16 or HBK_LOWP_FP16), dim and table_pitch count ELEMENTS, row[j] is the fp32 start value
+ * rounded to nearest even, stored as whole 4-byte words, a function of (key, seed, j, dtype) alone; the padding up to
+ * table_pitch keeps what it held.  Only the inserting launches are other kernels (the LOWP instantiations over the
+ * runs); insert == 0 and the counting phase of a filtered table write no row and are the launches of
+ * hbk_hash_translate_runs_n as they are.
+ *
+ * Refused (HBK_INVALID_ARGUMENT) before any device work, with the entry, the column and the field named: everything
+ * hbk_hash_translate_runs_n refuses; NULL table_dtypes with n_cols > 0; a code other than HBK_LOWP_BF16 /
+ * HBK_LOWP_FP16; with a table: an odd dim, an odd non-zero table_pitch, a table that is not 4-byte aligned;
+ * HBK_LOWP_FP16 with init_scale > 65504.  n_cols == 0 returns HBK_OK without touching a device.  No workspace, no host
+ * synchronisation: capturable.  Detected by the presence of the symbol; the structs and the version are those of
+ * 0.2.0. */
+int hbk_hash_translate_runs_lowp_n(int32_t n_cols, const hbk_hash_column_t* cols,
+                                   const hbk_hash_expiry_t* exp,      /* NULL, or [n_cols] */
+                                   const hbk_hash_admission_t* adm,   /* NULL, or [n_cols] */
+                                   const int32_t* table_dtypes        /* [n_cols]: HBK_LOWP_BF16 / HBK_LOWP_FP16 */,
+                                   const int32_t* n_runs, const hbk_hash_run_t* const* runs,
+                                   int32_t insert, hbk_stream_t stream);
 
 /* Hash-keyed sequence lookups: the first T ids of every sample translated into a slot grid.  The behaviour
  * histories of DIN / DIEN / BST (item and shop ids: an open vocabulary) are the columns that most need a raw-id
@@ -1585,6 +1610,29 @@ int hbk_hash_translate_sequence_n(int32_t n_cols, const hbk_hash_column_t* cols,
                                   const hbk_hash_admission_t* adm,   /* NULL, or [n_cols] */
                                   const hbk_hash_sequence_t* seq,    /* [n_cols] */
                                   int32_t insert, hbk_stream_t stream);
+
+/* Sequences over 16-bit tables: hbk_hash_translate_sequence_n for tables whose rows are bf16 / fp16.  The call IS
+ * hbk_hash_translate_sequence_n with the same cols, exp, adm and seq -- the effective id list, the slot grid, lengths,
+ * the "nothing" state of a padding position without a pad id, the rule that ids at positions >= T are never read,
+ * placement, metadata, the sketch's two phases, the counters -- except for the row the inserting launch writes, which
+ * is hbk_hash_insert_lowp_n's (see hbk_hash_translate_runs_lowp_n above: table_dtypes[c], nearest even, whole 4-byte
+ * words, a function of (key, seed, j, dtype) alone).  Only the inserting launches are other kernels; insert == 0 and
+ * the counting phase of a filtered table are the launches of hbk_hash_translate_sequence_n as they are.  The recipe
+ * above holds with the 16-bit gathers in the place of hbk_group_lookup_fwd: hbk_lowp_lookup_fwd over ids = the slot
+ * grid, bucket = 0; a -1 reads a zero row.
+ *
+ * Refused (HBK_INVALID_ARGUMENT) before any device work, with the entry, the column and the field named: everything
+ * hbk_hash_translate_sequence_n refuses; NULL table_dtypes with n_cols > 0; a code other than HBK_LOWP_BF16 /
+ * HBK_LOWP_FP16; with a table: an odd dim, an odd non-zero table_pitch, a table that is not 4-byte aligned;
+ * HBK_LOWP_FP16 with init_scale > 65504.  n_cols == 0 returns HBK_OK without touching a device.  No workspace, no host
+ * synchronisation: capturable.  Detected by the presence of the symbol; the structs and the version are those of
+ * 0.2.0. */
+int hbk_hash_translate_sequence_lowp_n(int32_t n_cols, const hbk_hash_column_t* cols,
+                                       const hbk_hash_expiry_t* exp,      /* NULL, or [n_cols] */
+                                       const hbk_hash_admission_t* adm,   /* NULL, or [n_cols] */
+                                       const int32_t* table_dtypes        /* [n_cols]: HBK_LOWP_BF16 / HBK_LOWP_FP16 */,
+                                       const hbk_hash_sequence_t* seq,    /* [n_cols] */
+                                       int32_t insert, hbk_stream_t stream);
 
 /* Missing ids: the distinct ids of N id lists that their tables do not hold -- what a fault-in asks the host tier
  * for (HashTable.fault_in composed it from a find, a boolean index and a sort per table, with two host
@@ -2177,6 +2225,34 @@ typedef struct {
   int32_t insert;               /* 0: pure find (inference) */
 } hbk_sharded_hash_t;
 int hbk_sharded_set_hash_tables(hbk_sharded_t plan, const hbk_sharded_hash_t* tables /* [n_cols] or NULL */);
+/* 16-bit sharded hash tables: hash columns whose tables hold bf16 / fp16 rows.  The two setters above refuse each
+ * other -- hbk_sharded_set_hash_tables on a 16-bit plan, hbk_sharded_set_table_dtypes on a plan with a hash column,
+ * both as before -- so this ONE setter registers both pieces of state or neither.  Plan state, set right after
+ * creation by every rank for itself.
+ *   dtypes, wire  as hbk_sharded_set_table_dtypes: all or nothing, every entry HBK_LOWP_BF16 / HBK_LOWP_FP16;
+ *                 HBK_LOWP_WIRE_TABLE or HBK_LOWP_WIRE_FLOAT.  The plan becomes a 16-bit plan: everything a 16-bit
+ *                 plan refuses stays refused (the stepping entries, the slot setters, hbk_sharded_lookup_bwd_weights,
+ *                 hbk_sharded_p2p_bind, a non-zero max_norm; HBK_UNIMPLEMENTED).
+ *   tables        as hbk_sharded_set_hash_tables; tables[c].keys_cache == NULL: column c is an ordinary 16-bit
+ *                 bucketed column.
+ *   tables == NULL or dtypes == NULL: the plan is the fp32 plan without hash columns that it was created as.
+ *   (hbk_sharded_set_table_dtypes(plan, NULL, .) on such a plan drops its hash columns with the 16-bit state.)
+ * Stage C of the forward: the hash columns of a group are translated by hbk_hash_translate_runs_lowp_n, one call per
+ * table kind and insert flag as before, the columns' element codes beside them -- a new row is the fp32 start row
+ * rounded to nearest even -- and the virtual columns go to the gathers of the 16-bit plan: hbk_lowp_gather_rows_n
+ * onto the 16-bit wire, hbk_lowp_lookup_fwd for HBK_LOWP_WIRE_FLOAT, a hash column with ids = the translated slots,
+ * HBK_INT64, divisor = 1.  A -1 slot is a zero row on both wires.  The emit backward (slot numbers; nothing is sent
+ * for -1), the split forward _ids / _gather / _end and hbk_sharded_hash_missing (whose find writes no row) are
+ * unchanged; the caller steps the tables with hbk_lowp_apply_slices_n over [capacity, dim] fp32 slots.
+ *
+ * Refused before the plan changes.  HBK_UNIMPLEMENTED: a plan created with wire_dtype == HBK_HALF, a plan with a
+ * non-zero max_norm, a p2p-bound plan.  HBK_INVALID_ARGUMENT: an unknown dtype or wire, a shard that is not 2-byte
+ * aligned; everything hbk_sharded_set_hash_tables refuses of a hash column; and of a hash column also an odd dim (new
+ * rows are whole 4-byte words), dim > 64 with dim % 4 != 0 (the bound of the 16-bit gathers without wide_rows), a
+ * shard that is not 4-byte aligned, HBK_LOWP_FP16 with init_scale > 65504.  Detected by the presence of the symbol;
+ * the structs and the version are those of 0.2.0. */
+int hbk_sharded_set_lowp_hash_tables(hbk_sharded_t plan, const hbk_sharded_hash_t* tables /* [n_cols] or NULL */,
+                                     const int32_t* dtypes /* [n_cols] or NULL */, int32_t wire);
 int hbk_sharded_destroy(hbk_sharded_t plan);
 /* out_strides / grad_strides: NULL, or per column the row stride in floats of outs[c] /
  * grads[c] (0 = dim): the columns' blocks of one concatenated [segments, sum of dims] tensor. */
