@@ -116,6 +116,19 @@ class LowpLookupColumn(C.Structure):
               ('id_weights', C.c_void_p), ('chunk_elems', C.c_int32), ('wide_rows', C.c_int32)]
 
 
+OUT16_TABLE_FP32 = 0   # hbk_out16_lookup_column_t.table_dtype beside LOWP_BF16 / LOWP_FP16
+
+
+class Out16LookupColumn(C.Structure):
+  """hbk_out16_lookup_column_t"""
+  _fields_ = [('table', C.c_void_p), ('table_dtype', C.c_int32), ('dim', C.c_int32), ('rows', C.c_int64),
+              ('ids', C.c_void_p), ('ids_dtype', C.c_int32), ('combiner', C.c_int32), ('n_ids', C.c_int64),
+              ('row_splits', C.c_void_p), ('n_segments', C.c_int64), ('bucket', C.c_int64),
+              ('divisor', C.c_int32), ('out_stride', C.c_int32), ('out', C.c_void_p),
+              ('id_weights', C.c_void_p), ('out_dtype', C.c_int32), ('chunk_elems', C.c_int32),
+              ('reserved', C.c_int32)]
+
+
 class LowpSlicesColumn(C.Structure):
   """hbk_lowp_slices_column_t"""
   _fields_ = [('table', C.c_void_p), ('table_dtype', C.c_int32), ('dim', C.c_int32), ('rows', C.c_int64),
@@ -347,6 +360,7 @@ def _declare(l):
     'hbk_group_lookup_bwd_rowwise_adagrad_clipped': (C.c_int, [i32, vp, vp, vp, vp, C.c_float, vp, sz, vp]),
     'hbk_sparse_apply_slices_n': (C.c_int, [i32, vp, i32, vp, vp, vp, C.c_float, vp]),
     'hbk_lowp_lookup_fwd': (C.c_int, [i32, vp, vp]),
+    'hbk_group_lookup_fwd_out16': (C.c_int, [i32, vp, vp]),
     'hbk_lowp_apply_slices_n': (C.c_int, [i32, vp, i32, vp, vp, vp, C.c_float, vp, vp]),
     'hbk_lowp_gather_rows_n': (C.c_int, [i32, vp, vp]),
     'hbk_lowp_lookup_fwd_runs': (C.c_int, [i32, vp, vp]),

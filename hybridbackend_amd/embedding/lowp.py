@@ -23,6 +23,7 @@ import torch
 from hybridbackend_amd import _lib
 from hybridbackend_amd.embedding import optimizer as _opt
 from hybridbackend_amd.embedding.lookup import GroupLookup, GroupLookupGrad, _combiner_code
+from hybridbackend_amd.embedding.out16 import Out16GroupLookup
 from hybridbackend_amd.embedding.sharded import ShardedGroupLookup
 from hybridbackend_amd.embedding.sparse_apply import SparseApply
 
@@ -206,7 +207,9 @@ class LowpLookupGrad:
 
   def __init__(self, lookup, accums=None, moments=None, adam=None, ftrl_slots=None, ftrl=None, row_accums=None,
                rowwise_adagrad=None, deterministic=False, rounding='nearest', seed=0):
-    if not isinstance(lookup, LowpGroupLookup):
+    # (an Out16GroupLookup over 16-bit tables is the same lookup with 16-bit outputs; fp32 tables among its tables
+    # are refused by the apply below, by name)
+    if not isinstance(lookup, (LowpGroupLookup, Out16GroupLookup)):
       raise _bad('LowpLookupGrad needs a LowpGroupLookup (fp32 tables go through GroupLookupGrad)')
     self.lookup = lookup
     self._apply = LowpSparseApply(lookup.tables, accums=accums, moments=moments, adam=adam, ftrl_slots=ftrl_slots,

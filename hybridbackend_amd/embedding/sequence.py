@@ -25,6 +25,8 @@ from hybridbackend_amd.embedding import optimizer as _opt
 from hybridbackend_amd.embedding.lookup import GroupLookup
 from hybridbackend_amd.embedding.lookup import GroupLookupGrad
 from hybridbackend_amd.embedding.lookup import max_norm_list
+from hybridbackend_amd.embedding.out16 import Out16GroupLookup
+from hybridbackend_amd.embedding.out16 import check_out_dtype
 
 
 def _bad(msg):
@@ -141,10 +143,19 @@ class SequenceLookup:
       (``hbk_group_lookup_fwd_sequence``); False -- ``hbk_sequence_row_grid_n`` followed by the plain
       gather over the grid (the same bits; outputs with a sample stride of their own still take the fused
       entry).  The default is the form that measured faster (profiles/sequence_lookup.txt).
+    out_dtype: None (fp32 outputs), ``torch.bfloat16`` or ``torch.float16``: the ``[B, T, dim]`` outputs have that
+      dtype -- bit for bit the fp32 outputs cast with torch.  Always the two-launch form: the grid launch, then
+      :class:`Out16GroupLookup` over the grid (a ``-1`` is a zero row).  Outputs must be contiguous; ``max_norms``
+      is refused; ``SequenceLookupGrad`` is unchanged and takes an fp32 gradient.
   """
 
   def __init__(self, tables, buckets=None, max_lens=None, pad_ids=None, divisor=1, max_norms=None,
-               fused=True):
+               fused=True, out_dtype=None):
+    self.out_dtype = None if out_dtype is None else check_out_dtype(out_dtype, 'SequenceLookup')
+    if out_dtype is not None and max_norms is not None and not (
+        isinstance(max_norms, (list, tuple)) and all(x is None for x in max_norms)):
+      raise _bad('SequenceLookup: max_norms is not supported with out_dtype (the clip is part of the fp32-output '
+                 'forward)')
     self._lib = _lib.lib()
     self.tables = list(tables)
     n = len(self.tables)
@@ -169,6 +180,7 @@ class SequenceLookup:
       col.bucket = self.buckets[c]
       col.divisor = self.divisor
     self._plain = None       # the two-launch form's gather over the grid
+    self._plain16 = None     # out_dtype: the same gather with 16-bit outputs
     self.grids = None        # the last forward's grids (None after an inference call)
     self.lengths = None
 
@@ -196,11 +208,16 @@ class SequenceLookup:
     if len(outs) != n:
       raise _bad(f'expected {n} outputs, got {len(outs)}')
     contiguous = True
+    out_dtype = self.out_dtype or torch.float32
     for c in range(n):
       shape = (batch[c], self.max_lens[c], self.dims[c])
       if outs[c] is None:
-        outs[c] = torch.empty(shape, dtype=torch.float32, device=dev)
+        outs[c] = torch.empty(shape, dtype=out_dtype, device=dev)
       o = outs[c]
+      if self.out_dtype is not None:
+        if not o.is_cuda or o.dtype != out_dtype or tuple(o.shape) != shape or not o.is_contiguous():
+          raise _bad(f'output {c} must be a contiguous {out_dtype} (out_dtype) device tensor {list(shape)}')
+        continue
       if not o.is_cuda or o.dtype != torch.float32 or tuple(o.shape) != shape:
         raise _bad(f'output {c} must be an fp32 device tensor {list(shape)}')
       stride = 0
@@ -213,7 +230,7 @@ class SequenceLookup:
         contiguous = False
       self._cols[c].out = o.data_ptr()
       self._cols[c].out_stride = stride
-    fused = self.fused or not contiguous
+    fused = (self.fused or not contiguous) and self.out_dtype is None
     lengths, gs = _alloc_side(batch, self.max_lens, dev, grids or not fused)
     for c in range(n):
       self._seqs[c].lengths = lengths[c].data_ptr()
@@ -223,7 +240,11 @@ class SequenceLookup:
       _lib.check(self._lib.hbk_group_lookup_fwd_sequence(n, self._cols, self._seqs, self.max_norms_c, stream))
     else:
       _lib.check(self._lib.hbk_sequence_row_grid_n(n, self._cols, self._seqs, stream))
-      self.plain_lookup()(gs, None, [o.view(g.numel(), d) for o, g, d in zip(outs, gs, self.dims)])
+      if self.out_dtype is not None and self._plain16 is None:
+        self._plain16 = Out16GroupLookup(self.tables, buckets=None, combiners='sum', divisor=self.divisor,
+                                         out_dtype=self.out_dtype)
+      plain = self._plain16 if self.out_dtype is not None else self.plain_lookup()
+      plain(gs, None, [o.view(g.numel(), d) for o, g, d in zip(outs, gs, self.dims)])
     self._keep = (list(ids), row_splits, outs)
     self.grids = gs if grids else None
     self.lengths = lengths

@@ -579,6 +579,14 @@ class DenseFeatures(_TableLayer):
       ``aggregate_replicated`` included.  The refusals above stand.  At W = 1 the argument changes nothing.
     table_rounding: ``'nearest'``, or ``'stochastic'`` (bf16 only) -- what lets a bf16 table train on steps
       smaller than half an ulp; table_seed: the seed of its noise.
+    output_dtype: None (the fp32 block: nothing below applies), ``torch.bfloat16`` or ``torch.float16``: the layer's
+      block is a tensor of that dtype, its row pitch padded to 8 elements, written in place by
+      ``hb.embedding.Out16GroupLookup`` -- bit for bit the fp32 block cast with torch, without the cast pass.  With
+      fp32 tables or with ``table_dtype``; weighted columns included.  ``backward`` takes the gradient in
+      ``output_dtype`` or fp32 and upcasts it with one copy into its padded fp32 block; everything behind that is
+      unchanged.  Refused by name at construction: more than one rank, a hash-keyed column, a column with
+      ``max_norm``, and a column that would have to be staged through a tensor of its own (wider than 64 and not a
+      multiple of 4 elements wide at a multiple of 4 elements of the row).
 
   Hash-keyed columns (:class:`HashEmbeddingColumn`) mix freely with bucketed ones; column order decides the
   block offsets.  ``hash_tables[c]`` is the column's :class:`HashTable` (None for a bucketed column) and
@@ -602,9 +610,12 @@ class DenseFeatures(_TableLayer):
   def __init__(self, columns, device, coll=None, batch_size=0, init=None,
                initial_accumulator_value=None, optimizer=None, adam=None, ftrl=None, train=True,
                rowwise_adagrad=None, aggregate_replicated=False, replicated_scale=None, table_dtype=None,
-               table_rounding='nearest', table_seed=0, lowp_sharded=False):
+               table_rounding='nearest', table_seed=0, lowp_sharded=False, output_dtype=None):
     self.table_dtype = table_dtype
     self.lowp_sharded = bool(lowp_sharded)
+    self.output_dtype = output_dtype
+    if output_dtype is not None:
+      self._check_out16(columns, coll, output_dtype)
     if table_dtype is not None:
       self._check_lowp(columns, coll, table_dtype, table_rounding, table_seed, lowp_sharded)
     self._init_tables(columns, device, coll, batch_size, init, initial_accumulator_value, optimizer,
@@ -631,7 +642,21 @@ class DenseFeatures(_TableLayer):
     pick = lambda idx, xs: [xs[c] for c in idx]   # noqa: E731
     two_slot_kw = self._two_slot_kw
     self._lookup = self._grad = self._sharded = None
-    if self._rep and table_dtype is not None and self._world() <= 1:
+    if self._rep and output_dtype is not None:
+      # 16-bit outputs (one rank, bucketed columns: checked above): the block is written in place by the 16-bit-output
+      # forward; the backward is the one the tables' type has today, over an fp32 gradient block
+      from hybridbackend_amd.embedding.out16 import Out16GroupLookup   # pylint: disable=import-outside-toplevel
+      self._lookup = Out16GroupLookup(pick(self._rep, self.weights),
+                                      [self.columns[c].num_buckets for c in self._rep],
+                                      [self.columns[c].combiner for c in self._rep], out_dtype=output_dtype)
+      accums = pick(self._rep, self.accums) if self.accums is not None else None
+      if table_dtype is not None:
+        from hybridbackend_amd.embedding.lowp import LowpLookupGrad   # pylint: disable=import-outside-toplevel
+        self._grad = LowpLookupGrad(self._lookup, accums, rounding=table_rounding, seed=table_seed,
+                                    **two_slot_kw(self._rep))
+      else:
+        self._grad = GroupLookupGrad(self._lookup, accums, **two_slot_kw(self._rep))
+    elif self._rep and table_dtype is not None and self._world() <= 1:
       # 16-bit tables: the same two roles, so that __call__ and backward do not fork
       from hybridbackend_amd.embedding.lowp import LowpGroupLookup, LowpLookupGrad   # pylint: disable=import-outside-toplevel
       self._lookup = LowpGroupLookup(pick(self._rep, self.weights),
@@ -713,6 +738,27 @@ class DenseFeatures(_TableLayer):
                    'on a 16-byte boundary of the output row; reorder the columns')
       off += col.dimension
 
+  @staticmethod
+  def _check_out16(columns, coll, output_dtype):
+    """Everything ``output_dtype`` refuses, before any table is allocated."""
+    what = f'DenseFeatures(output_dtype={output_dtype})'
+    if output_dtype not in (torch.bfloat16, torch.float16):
+      raise _bad(f'DenseFeatures(output_dtype=): None, torch.bfloat16 or torch.float16, got {output_dtype!r}')
+    if coll is not None and coll.world_size > 1:
+      raise _bad(f'{what}: 16-bit outputs are written on one rank only, the layer spans {coll.world_size} (the '
+                 'sharded step stores fp32 rows)')
+    off = 0
+    for col in columns:
+      if _is_hash(col):
+        raise _bad(f'{what}: column {col.key!r} is hash-keyed; hash-keyed lookups store fp32 rows')
+      if col.max_norm is not None:
+        raise _bad(f'{what}: column {col.key!r} has max_norm; the clip is part of the fp32-output forward')
+      if col.dimension > 64 and (off % 4 != 0 or col.dimension % 4 != 0):
+        raise _bad(f'{what}: column {col.key!r} ({col.dimension} wide at element {off} of the block) would have to '
+                   'be staged through a tensor of its own: a row of more than 64 elements must be a multiple of 4 '
+                   'elements wide and start on a multiple of 4 elements of the output row; reorder the columns')
+      off += col.dimension
+
   def _weights(self, features):
     """Per column its fp32 per-id weights (weight_feature_key) or None; None when no column has any."""
     ws = [features[col.weight_feature_key] if col.weight_feature_key is not None else None
@@ -742,7 +788,11 @@ class DenseFeatures(_TableLayer):
     # rows start on 16-byte boundaries (row stride padded to 4 floats) so that columns whose
     # offset is a multiple of 4 floats keep 16-byte accesses
     pitch = (self.width + 3) // 4 * 4
-    out = torch.empty((batch or 0, pitch), dtype=torch.float32, device=self.device)[:, :self.width]
+    out_dtype = torch.float32
+    if self.output_dtype is not None:
+      # 16-bit outputs: the same 16 bytes are 8 elements
+      pitch, out_dtype = (self.width + 7) // 8 * 8, self.output_dtype
+    out = torch.empty((batch or 0, pitch), dtype=out_dtype, device=self.device)[:, :self.width]
     pick = lambda idx, xs: [xs[c] for c in idx]   # noqa: E731
     pick_w = lambda idx: None if ws is None else pick(idx, ws)   # noqa: E731
     views = None
@@ -837,10 +887,12 @@ class DenseFeatures(_TableLayer):
     self._refuse_backward_of_a_find('DenseFeatures')
     self._refuse_weight_grads('DenseFeatures', weight_grads)
     ids, splits, ws = self._last
-    if grad.dim() != 2 or grad.shape[1] != self.width or grad.dtype != torch.float32:
+    # (a layer with output_dtype also takes the gradient in that dtype: upcast by the copy into the padded block)
+    if grad.dim() != 2 or grad.shape[1] != self.width or \
+        (grad.dtype != torch.float32 and (self.output_dtype is None or grad.dtype != self.output_dtype)):
       raise _lib.InvalidArgumentError(
         _lib.INVALID_ARGUMENT, f'grad must be fp32 [batch, {self.width}]')
-    if grad.stride(1) != 1 or grad.stride(0) % 4 != 0:
+    if grad.dtype != torch.float32 or grad.stride(1) != 1 or grad.stride(0) % 4 != 0:
       # same pitch as the forward's block: rows on 16-byte boundaries (one extra copy)
       pitch = (self.width + 3) // 4 * 4
       padded = torch.empty((grad.shape[0], pitch), dtype=torch.float32,

@@ -684,6 +684,69 @@ typedef struct {
 } hbk_lowp_lookup_column_t;
 int hbk_lowp_lookup_fwd(int32_t n_cols, const hbk_lowp_lookup_column_t* cols, hbk_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * 16-bit outputs: the group lookup's forward over fp32, bf16 or fp16 tables that WRITES bf16 or fp16 rows -- what the
+ * dense tower behind the lookup reads -- instead of fp32 rows followed by a cast pass.  One entry, detected by the
+ * presence of the symbol (the structs above and the version are those of 0.2.0).  A call may mix table types and
+ * output types across columns.
+ *
+ * hbk_group_lookup_fwd_out16: per column out[s] = round(f[s]), where f[s] is the fp32 row that hbk_group_lookup_fwd
+ *   computes for an fp32 table and that hbk_lowp_lookup_fwd computes for a 16-bit table: with e_j = table[row(j), :]
+ *   (a 16-bit table: e_j = upcast(table[row(j), :]), exact) and row(j) as in hbk_group_lookup_fwd (bucket: floormod;
+ *   divisor; rows outside [0, rows) are zero rows),
+ *     row_splits == NULL:                 f[s] = e_s                                    (the combiner is ignored)
+ *       with id_weights:   sum   f[s] = w_s e_s
+ *                          mean  f[s] = (w_s e_s) / w_s
+ *                          sqrtn f[s] = (w_s e_s) / sqrtf(w_s * w_s)
+ *                          an invalid row or a zero divisor gives a zero row
+ *     row_splits != NULL:  acc = +0; for j in id order: acc = acc + e_j              (n = all ids of the segment)
+ *                          sum   f[s] = acc;  mean acc / (float)n;  sqrtn acc / sqrtf((float)n);  n == 0: zeros
+ *       with id_weights:   acc = acc + e_j * w_j, W = W + w_j (sqrtn: Q = Q + w_j * w_j), ids of VALID rows only
+ *                          sum   f[s] = acc;  mean acc / W;  sqrtn acc / sqrtf(Q);  a zero divisor: zeros
+ *   every product and sum a separately rounded fp32 operation.  round is applied ONCE per element and goes to nearest,
+ *   ties to even: bf16 on the fp32 pattern u, (u + 0x7FFF + ((u >> 16) & 1)) >> 16 (a NaN gives 0x7FC0); fp16 the
+ *   IEEE conversion, subnormals included, overflow to +-inf.  These are the bits of torch's float32 -> bfloat16 /
+ *   float16 cast, so the result equals the fp32-output entry followed by that cast, bit for bit; per-element sums are
+ *   independent, so the lane layout cannot change a bit.
+ *   A row is owned by pow2(dim / W) adjacent lanes, W consecutive elements each, and the STORE side decides W:
+ *     W = 8  dim % 8 == 0, `out` and its stride 16-byte aligned, table 16-byte aligned: one 16-byte store per lane, fed
+ *            by two 16-byte loads of an fp32 table or one of a 16-bit table;
+ *     W = 4  dim % 4 == 0, `out` and its stride 8-byte aligned, table 16-byte (fp32) or 8-byte (16-bit) aligned: one
+ *            8-byte store per lane.  Both serve dim <= 256;
+ *     W = 1  otherwise, dim <= 64: 2-byte stores that touch no neighbouring byte (columns are blocks of a wider
+ *            tensor; what lies between blocks survives).  Output memory is never read.
+ *   chunk_elems = 0 takes 8 from dim 64 on where the column allows it, else 4; chunk_elems = 8 takes 8 wherever
+ *   possible, chunk_elems = 4 never; no bit depends on it.  One launch per 64 columns, kind (one id per segment /
+ *   ragged) and lane width; no LDS, no atomics, no workspace, no host read: the call can be captured.  There is no
+ *   max_norm, no segmented table, no output permutation and no hot rows here.  Refused before the first launch
+ *   (HBK_INVALID_ARGUMENT, the column named): an unknown table_dtype, out_dtype, ids_dtype or combiner; chunk_elems not
+ *   0, 4 or 8; a non-zero reserved word; dim < 1 or beyond the bounds above; `out` at an odd address, a table not
+ *   aligned to its element; a NULL table (rows > 0), ids (n_ids > 0) or out of a column with segments; negative sizes,
+ *   >= 2^31 ids or segments; bucket < 0; divisor < 1; out_stride != 0 and < dim; n_segments != n_ids without
+ *   row_splits.  n_cols == 0 answers OK without touching a device. */
+#define HBK_OUT16_TABLE_FP32 0
+typedef struct {
+  const void* table;         /* device [rows, dim], contiguous rows, of fp32 or 2-byte elements */
+  int32_t table_dtype;       /* HBK_OUT16_TABLE_FP32 | HBK_LOWP_BF16 | HBK_LOWP_FP16 */
+  int32_t dim;
+  int64_t rows;
+  const void* ids;           /* device [n_ids] */
+  int32_t ids_dtype;         /* HBK_INT32 | HBK_INT64 */
+  int32_t combiner;          /* HBK_COMBINER_* */
+  int64_t n_ids;
+  const int32_t* row_splits; /* device [n_segments + 1] or NULL */
+  int64_t n_segments;        /* == n_ids when row_splits == NULL */
+  int64_t bucket;            /* 0 = ids are row numbers already */
+  int32_t divisor;           /* >= 1 */
+  int32_t out_stride;        /* ELEMENTS between rows of `out`; 0 = dim */
+  void* out;                 /* device [n_segments, dim] of out_dtype elements */
+  const float* id_weights;   /* device fp32 [n_ids] or NULL */
+  int32_t out_dtype;         /* HBK_LOWP_BF16 | HBK_LOWP_FP16 */
+  int32_t chunk_elems;       /* 0 = the default (8 from dim 64 on, else 4); 4 or 8: elements per lane where the column allows it */
+  int32_t reserved;          /* must be 0 */
+} hbk_out16_lookup_column_t;
+int hbk_group_lookup_fwd_out16(int32_t n_cols, const hbk_out16_lookup_column_t* cols, hbk_stream_t stream);
+
 /* APPLY  hbk_lowp_apply_slices_n: the contract of hbk_sparse_apply_slices_n (distinct rows; an entry outside
  *   [0, rows), -1 included, touches nothing; n_unique read on the device and clamped to [0, capacity]; the five
  *   rules; one launch per 64 columns, no workspace, no host read; hbk_adam_t.finish advances the beta powers
