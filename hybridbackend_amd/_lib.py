@@ -158,6 +158,12 @@ class LowpLookupRunsColumn(C.Structure):
               ('n_runs', C.c_int32), ('reserved', C.c_int32)]
 
 
+class Out16RunsColumn(C.Structure):
+  """hbk_out16_runs_column_t"""
+  _fields_ = [('col', Out16LookupColumn), ('run_start', C.c_void_p), ('run_base', C.c_void_p),
+              ('n_runs', C.c_int32), ('reserved', C.c_int32)]
+
+
 class ReplicaColumn(C.Structure):
   """hbk_replica_column_t"""
   _fields_ = [('unique_rows', C.c_void_p), ('grad_rows', C.c_void_p), ('n_unique', C.c_void_p),
@@ -364,6 +370,7 @@ def _declare(l):
     'hbk_lowp_apply_slices_n': (C.c_int, [i32, vp, i32, vp, vp, vp, C.c_float, vp, vp]),
     'hbk_lowp_gather_rows_n': (C.c_int, [i32, vp, vp]),
     'hbk_lowp_lookup_fwd_runs': (C.c_int, [i32, vp, vp]),
+    'hbk_lookup_fwd_runs_out16': (C.c_int, [i32, vp, vp]),
     'hbk_sharded_set_table_dtypes': (C.c_int, [vp, vp, i32]),
     'hbk_replica_grads_pack_n': (C.c_int, [i32, vp, vp, i64, vp]),
     'hbk_replica_grads_rows_n': (C.c_int, [i32, vp, vp]),
@@ -439,6 +446,9 @@ def _declare(l):
     'hbk_sharded_prefetch_on': (C.c_int, [vp, vp, vp, vp]),
     'hbk_sharded_lookup_fwd_begin': (C.c_int, [vp, vp, vp, vp, vp, vp]),
     'hbk_sharded_lookup_fwd_end': (C.c_int, [vp, vp, vp, vp]),
+    'hbk_sharded_lookup_fwd_end_out16': (C.c_int, [vp, vp, vp, i32, vp]),
+    'hbk_sharded_lookup_fwd_out16': (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, vp]),
+    'hbk_sharded_lookup_fwd_weighted_out16': (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
     'hbk_sharded_lookup_fwd_ids': (C.c_int, [vp, vp, vp, vp, vp, vp]),
     'hbk_sharded_lookup_fwd_gather': (C.c_int, [vp, vp]),
     'hbk_sharded_hash_missing': (C.c_int, [vp, vp, vp, vp, vp, vp]),

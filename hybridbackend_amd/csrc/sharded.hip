@@ -1997,9 +1997,13 @@ extern "C" int hbk_sharded_hash_missing(hbk_sharded_t p, const uint8_t* want, in
                                  p->missing_ws.bytes, stream_);
 }
 
-extern "C" int hbk_sharded_lookup_fwd_end(hbk_sharded_t p, float* const* outs,
-                                          const int32_t* out_strides, hbk_stream_t stream_) {
-  using namespace hbk;
+namespace hbk {
+namespace {
+// The second half of the forward.  out_dtype 0: fp32 outputs (hbk_sharded_lookup_fwd_end); HBK_LOWP_BF16 /
+// HBK_LOWP_FP16: the same step with the 16-bit stitch behind it (hbk_sharded_lookup_fwd_end_out16).  Everything up
+// to stage D is one code for both.
+int fwd_end(hbk_sharded_t p, void* const* outs, const int32_t* out_strides, int32_t out_dtype,
+            hbk_stream_t stream_) {
   HBK_REQUIRE(p != nullptr && outs != nullptr, "sharded_lookup_fwd_end: NULL argument");
   HBK_REQUIRE(!p->ids_open, "sharded_lookup_fwd_end: the open step has not gathered yet: "
               "hbk_sharded_lookup_fwd_gather comes before hbk_sharded_lookup_fwd_end");
@@ -2077,14 +2081,41 @@ extern "C" int hbk_sharded_lookup_fwd_end(hbk_sharded_t p, float* const* outs,
       h.n_segments = p->n_seg[cc];
       h.divisor = 1;
       h.combiner = p->cols[cc].combiner;
-      h.out = outs[cc];
+      h.out = static_cast<float*>(outs[cc]);   // (16-bit outputs: the 16-bit stitch below takes it as it is)
       h.out_stride = out_strides ? out_strides[cc] : 0;
       h.run_start = d_start + (size_t)cc * W;
       h.run_base = d_base + (size_t)cc * W;
       h.n_runs = W;
       h.id_weights = p->id_weights[cc];   // the weights are applied here, on the requester
     }
-    if (wire16) {
+    if (out_dtype != 0) {
+      // 16-bit outputs: the same columns over the same runs through the stitch that rounds once
+      std::vector<hbk_out16_runs_column_t> ov((size_t)ng);
+      for (int c = 0; c < ng; ++c) {
+        const hbk_lookup_column_t& h = v[c];
+        hbk_out16_runs_column_t& d = ov[(size_t)c];
+        memset(&d, 0, sizeof(d));
+        d.col.table = h.table;
+        d.col.table_dtype = wire16 ? p->lowp[(size_t)(gr.c0 + c)] : half ? HBK_LOWP_FP16 : HBK_OUT16_TABLE_FP32;
+        d.col.dim = h.dim;
+        d.col.rows = h.rows;
+        d.col.ids = h.ids;
+        d.col.ids_dtype = h.ids_dtype;
+        d.col.combiner = h.combiner;
+        d.col.n_ids = h.n_ids;
+        d.col.row_splits = h.row_splits;
+        d.col.n_segments = h.n_segments;
+        d.col.divisor = 1;
+        d.col.out_stride = h.out_stride;
+        d.col.out = outs[gr.c0 + c];
+        d.col.id_weights = h.id_weights;
+        d.col.out_dtype = out_dtype;
+        d.run_start = h.run_start;
+        d.run_base = h.run_base;
+        d.n_runs = h.n_runs;
+      }
+      rc = hbk_lookup_fwd_runs_out16(ng, ov.data(), stream_);
+    } else if (wire16) {
       // the received rows are the shards' own 16 bits: the same columns over the same runs, upcast by the stitch
       std::vector<hbk_lowp_lookup_runs_column_t> lv((size_t)ng);
       for (int c = 0; c < ng; ++c) {
@@ -2125,6 +2156,43 @@ extern "C" int hbk_sharded_lookup_fwd_end(hbk_sharded_t p, float* const* outs,
   return HBK_OK;
 }
 
+// refused before any launch or exchange, the same on every rank
+int out16_check(hbk_sharded_t p, const char* who, int32_t out_dtype) {
+  HBK_REQUIRE(p != nullptr, "%s: NULL argument", who);
+  HBK_REQUIRE(out_dtype == HBK_LOWP_BF16 || out_dtype == HBK_LOWP_FP16,
+              "%s: out_dtype must be HBK_LOWP_BF16 or HBK_LOWP_FP16, got %d", who, out_dtype);
+  if (p->p2p_bound) {
+    return fail(HBK_UNIMPLEMENTED, "%s: the p2p form (hbk_sharded_p2p_bind) has no stitch to round in: its owner "
+                "gather writes fp32 rows into the requester's output", who);
+  }
+  return HBK_OK;
+}
+}  // namespace
+}  // namespace hbk
+
+extern "C" int hbk_sharded_lookup_fwd_end(hbk_sharded_t p, float* const* outs,
+                                          const int32_t* out_strides, hbk_stream_t stream_) {
+  return hbk::fwd_end(p, reinterpret_cast<void* const*>(outs), out_strides, 0, stream_);
+}
+
+extern "C" int hbk_sharded_lookup_fwd_end_out16(hbk_sharded_t p, void* const* outs, const int32_t* out_strides,
+                                                int32_t out_dtype, hbk_stream_t stream_) {
+  if (int rc = hbk::out16_check(p, "sharded_lookup_fwd_end_out16", out_dtype)) return rc;
+  return hbk::fwd_end(p, outs, out_strides, out_dtype, stream_);
+}
+
+extern "C" int hbk_sharded_lookup_fwd_out16(hbk_sharded_t p, const int64_t* const* ids, const int64_t* n_ids,
+                                            const int32_t* const* row_splits, const int64_t* n_segments,
+                                            void* const* outs, const int32_t* out_strides, int32_t out_dtype,
+                                            hbk_stream_t stream_) {
+  using namespace hbk;
+  if (int rc = out16_check(p, "sharded_lookup_fwd_out16", out_dtype)) return rc;
+  HBK_REQUIRE(outs != nullptr, "sharded_lookup_fwd_out16: NULL argument array");
+  const int rc = hbk_sharded_lookup_fwd_begin(p, ids, n_ids, row_splits, n_segments, stream_);
+  if (rc != HBK_OK) return rc;
+  return fwd_end(p, outs, out_strides, out_dtype, stream_);
+}
+
 extern "C" int hbk_sharded_lookup_fwd(hbk_sharded_t p, const int64_t* const* ids,
                                       const int64_t* n_ids,
                                       const int32_t* const* row_splits,
@@ -2139,13 +2207,12 @@ extern "C" int hbk_sharded_lookup_fwd(hbk_sharded_t p, const int64_t* const* ids
 
 // Weights never cross the wire: the owners gather unweighted rows, the requester's stitch (an
 // hbk_group_lookup_fwd over the received rows) multiplies, and the backward's stitch keeps them.
-extern "C" int hbk_sharded_lookup_fwd_weighted(hbk_sharded_t p, const int64_t* const* ids,
-                                               const int64_t* n_ids,
-                                               const int32_t* const* row_splits,
-                                               const int64_t* n_segments,
-                                               const float* const* id_weights, float* const* outs,
-                                               const int32_t* out_strides, hbk_stream_t stream_) {
-  using namespace hbk;
+namespace hbk {
+namespace {
+// the weighted forward up to its _end: the checks, _begin, and the weights left for the stitch
+int fwd_weighted_begin(hbk_sharded_t p, const int64_t* const* ids, const int64_t* n_ids,
+                       const int32_t* const* row_splits, const int64_t* n_segments,
+                       const float* const* id_weights, const void* outs, hbk_stream_t stream_) {
   HBK_REQUIRE(p != nullptr && outs != nullptr, "sharded_lookup_fwd: NULL argument");
   bool weighted = false;
   for (int c = 0; id_weights != nullptr && c < p->N; ++c) weighted = weighted || id_weights[c] != nullptr;
@@ -2165,7 +2232,29 @@ extern "C" int hbk_sharded_lookup_fwd_weighted(hbk_sharded_t p, const int64_t* c
   int rc = hbk_sharded_lookup_fwd_begin(p, ids, n_ids, row_splits, n_segments, stream_);
   if (rc != HBK_OK) return rc;
   for (int c = 0; weighted && c < p->N; ++c) p->id_weights[c] = id_weights[c];
+  return HBK_OK;
+}
+}  // namespace
+}  // namespace hbk
+
+extern "C" int hbk_sharded_lookup_fwd_weighted(hbk_sharded_t p, const int64_t* const* ids,
+                                               const int64_t* n_ids,
+                                               const int32_t* const* row_splits,
+                                               const int64_t* n_segments,
+                                               const float* const* id_weights, float* const* outs,
+                                               const int32_t* out_strides, hbk_stream_t stream_) {
+  if (int rc = hbk::fwd_weighted_begin(p, ids, n_ids, row_splits, n_segments, id_weights, outs, stream_)) return rc;
   return hbk_sharded_lookup_fwd_end(p, outs, out_strides, stream_);
+}
+
+extern "C" int hbk_sharded_lookup_fwd_weighted_out16(hbk_sharded_t p, const int64_t* const* ids,
+                                                     const int64_t* n_ids, const int32_t* const* row_splits,
+                                                     const int64_t* n_segments, const float* const* id_weights,
+                                                     void* const* outs, const int32_t* out_strides,
+                                                     int32_t out_dtype, hbk_stream_t stream_) {
+  if (int rc = hbk::out16_check(p, "sharded_lookup_fwd_weighted_out16", out_dtype)) return rc;
+  if (int rc = hbk::fwd_weighted_begin(p, ids, n_ids, row_splits, n_segments, id_weights, outs, stream_)) return rc;
+  return hbk::fwd_end(p, outs, out_strides, out_dtype, stream_);
 }
 
 // Partition (stages 1-2) of a FUTURE step on the plan's own stream, so that it overlaps whatever

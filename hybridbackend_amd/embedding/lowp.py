@@ -301,6 +301,7 @@ class LowpShardedGroupLookup(ShardedGroupLookup):
       (row-wise Adagrad: ``[rows_local, 1]``) and the optimizer objects, as :class:`LowpSparseApply` takes them.
     rounding, seed: as :class:`LowpSparseApply`.  The stochastic noise is keyed by the LOCAL row, so two ranks with
       one seed would round local row r alike: rank k steps with ``rank_seed = (seed + 0x9E3779B9 * k) mod 2^32``.
+    out_dtype: as :class:`ShardedGroupLookup`: 16-bit outputs written by the stitch, on either wire.
 
   ``__call__``, ``bind``, ``launch`` (weighted steps included), ``prefetch`` and the split forward are the base
   class's.  ``backward(grads, apply_lr=, optimizer=, emit=, finish=)`` is the plan's emit backward -- which never
@@ -313,8 +314,10 @@ class LowpShardedGroupLookup(ShardedGroupLookup):
 
   def __init__(self, shards16, coll, buckets=None, combiners='sum', wire='table', dedup=False, accums=None,   # pylint: disable=super-init-not-called
                moments=None, adam=None, ftrl_slots=None, ftrl=None, row_accums=None, rowwise_adagrad=None,
-               rounding='nearest', seed=0, max_norms=None, weight_grads=False, wire_dtype=None, hot_rows=False):
+               rounding='nearest', seed=0, max_norms=None, weight_grads=False, wire_dtype=None, hot_rows=False,
+               out_dtype=None):
     what = 'LowpShardedGroupLookup'
+    self._set_out_dtype(out_dtype)
     self.shards = _require_lowp_tables(shards16, what)
     if max_norms is not None and not (isinstance(max_norms, (list, tuple)) and all(x is None for x in max_norms)):
       raise _bad(f'{what}: max_norms is not supported for 16-bit shards (the clip reads and the clipped step writes '

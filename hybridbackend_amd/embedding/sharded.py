@@ -83,13 +83,22 @@ class ShardedGroupLookup:
     max_norms: TF's ``max_norm``, as for ``GroupLookup``: the owner clips every row it gathers (in
       fp32, before the fp16 wire) and steps its shard rows with the gradient through the clip; the
       p2p form (``p2p_bind``) refuses a clipped forward.
+    out_dtype: None (fp32 outputs), or ``torch.bfloat16`` / ``torch.float16``: the requester's stitch writes rows of
+      that type itself (``hbk_sharded_lookup_fwd_out16``), rounded once per element to nearest even -- the fp32
+      outputs followed by ``.to(out_dtype)``, bit for bit, without the fp32 block and the cast pass.  ``bind``,
+      ``__call__``, ``launch`` and ``launch_end`` then allocate and expect outputs of that type (column blocks of a
+      wider 16-bit tensor included); ``backward`` takes fp32 gradients as before.  Not with ``p2p_bind`` (its owner
+      gather writes fp32 rows into the requester's output: there is no stitch to round in).
   """
+
+  out_dtype = None   # (subclasses with constructors of their own set it through _set_out_dtype)
 
   def __init__(self, shards, coll, buckets=None, combiners='sum', wire_dtype=None,
                world_size=None, accums=None, hot_rows=False, dedup=False, moments=None, adam=None,
                ftrl_slots=None, ftrl=None, max_norms=None, weight_grads=False, row_accums=None,
-               rowwise_adagrad=None):
+               rowwise_adagrad=None, out_dtype=None):
     from hybridbackend_amd.embedding.lookup import max_norm_list
+    self._set_out_dtype(out_dtype)
     self.shards = list(shards)
     # backward() also returns the gradient of the last forward's sp_weights (its own weight_grads
     # argument overrides this default)
@@ -120,6 +129,19 @@ class ShardedGroupLookup:
     self.hot_rows = [False if h == 'auto' else bool(h) for h in hot_rows]
     self.dedup = [bool(dedup)] * n if isinstance(dedup, (bool, int)) else [bool(d) for d in dedup]
     self._setup()
+
+  def _set_out_dtype(self, out_dtype):
+    if out_dtype is not None and out_dtype not in (torch.bfloat16, torch.float16):
+      raise _lib.InvalidArgumentError(
+        _lib.INVALID_ARGUMENT, f'{type(self).__name__}: out_dtype must be None, torch.bfloat16 or torch.float16, '
+        f'got {out_dtype!r}')
+    self.out_dtype = out_dtype
+
+  def _out_torch_dtype(self):
+    return torch.float32 if self.out_dtype is None else self.out_dtype
+
+  def _out_code(self):
+    return _lib.LOWP_BF16 if self.out_dtype == torch.bfloat16 else _lib.LOWP_FP16
 
   def _setup(self):
     """Device-side state of the compute phases (the HIP path; there is no other)."""
@@ -222,6 +244,9 @@ class ShardedGroupLookup:
     peer's memory cannot be mapped, in which case the object keeps the exchange form.  Not with
     ``dedup`` or the fp16 wire."""
     n = len(self.shards)
+    if self.out_dtype is not None:
+      raise _lib.HbkError(_lib.UNIMPLEMENTED, f'p2p_bind: not with out_dtype={self.out_dtype}: the owner gather of '
+                          'the p2p form writes fp32 rows into the requester\'s output, there is no stitch to round in')
     if len(outs) != n:
       raise _lib.InvalidArgumentError(_lib.INVALID_ARGUMENT, f'p2p_bind: {len(outs)} outputs for {n} columns')
     for c, o in enumerate(outs):
@@ -280,14 +305,17 @@ class ShardedGroupLookup:
           raise _lib.InvalidArgumentError(
             _lib.INVALID_ARGUMENT, 'row_splits must be an int32 vector [segments+1]')
       n_seg.append(ids[c].numel() if s is None else s.numel() - 1)
+    odt = self._out_torch_dtype()
     if outs is None:
-      outs = [torch.empty((n_seg[c], self.dims[c]), dtype=torch.float32, device=self.device)
+      outs = [torch.empty((n_seg[c], self.dims[c]), dtype=odt, device=self.device)
               for c in range(n)]
     for c in range(n):
       _lib.require_device_tensor(outs[c], 'output', row_strided=True)
-      if outs[c].dtype != torch.float32 or tuple(outs[c].shape) != (n_seg[c], self.dims[c]):
+      if outs[c].dtype != odt or tuple(outs[c].shape) != (n_seg[c], self.dims[c]):
         raise _lib.InvalidArgumentError(
-          _lib.INVALID_ARGUMENT, f'output {c} must be fp32 [{n_seg[c]}, {self.dims[c]}]')
+          _lib.INVALID_ARGUMENT, f'output {c} must be {"fp32" if self.out_dtype is None else odt} '
+          f'[{n_seg[c]}, {self.dims[c]}]' + ('' if self.out_dtype is None else ' (out_dtype)') +
+          f', got {outs[c].dtype} {tuple(outs[c].shape)}')
     bound = _BoundStep()
     bound.shapes = [(n_seg[c], self.dims[c]) for c in range(n)]
     bound.keep = (list(ids), list(row_splits), list(outs))   # (own lists: the caller may refill his)
@@ -329,10 +357,11 @@ class ShardedGroupLookup:
         sp_ptrs.append(sp.data_ptr())
         n_seg.append(sh[0] - 1)
     dims = self.dims
+    odt = self._out_torch_dtype()
     o_ptrs = []
     for c in range(n):
       o = outs[c]
-      if (o.dtype is not torch.float32 or not o.is_cuda or not o.is_contiguous() or
+      if (o.dtype is not odt or not o.is_cuda or not o.is_contiguous() or
           tuple(o.shape) != (n_seg[c], dims[c])):
         return None
       o_ptrs.append(o.data_ptr())
@@ -349,16 +378,25 @@ class ShardedGroupLookup:
     self._keep = bound.keep
     self._last_shapes = bound.shapes   # what backward() differentiates
     self._refresh_hot_rows()
+    a = bound.args
     if bound.weights is None:
       self._keep_weights = None
-      _lib.check(self._lib.hbk_sharded_lookup_fwd(
-        self._plan(), *bound.args, _lib.current_stream(self.device)))
+      if self.out_dtype is None:
+        _lib.check(self._lib.hbk_sharded_lookup_fwd(
+          self._plan(), *a, _lib.current_stream(self.device)))
+      else:
+        _lib.check(self._lib.hbk_sharded_lookup_fwd_out16(
+          self._plan(), *a, self._out_code(), _lib.current_stream(self.device)))
     else:
       self._keep_weights = bound.weights[1]   # (the backward reads them: alive until the next step)
-      a = bound.args
-      _lib.check(self._lib.hbk_sharded_lookup_fwd_weighted(
-        self._plan(), a[0], a[1], a[2], a[3], bound.weights[0], a[4], a[5],
-        _lib.current_stream(self.device)))
+      if self.out_dtype is None:
+        _lib.check(self._lib.hbk_sharded_lookup_fwd_weighted(
+          self._plan(), a[0], a[1], a[2], a[3], bound.weights[0], a[4], a[5],
+          _lib.current_stream(self.device)))
+      else:
+        _lib.check(self._lib.hbk_sharded_lookup_fwd_weighted_out16(
+          self._plan(), a[0], a[1], a[2], a[3], bound.weights[0], a[4], a[5], self._out_code(),
+          _lib.current_stream(self.device)))
     return bound.outs
 
   def _refresh_hot_rows(self):
@@ -417,8 +455,12 @@ class ShardedGroupLookup:
     """Second half (``hbk_sharded_lookup_fwd_end``): rows exchange, stitch + combiner; returns the
     step's outputs."""
     a = bound.args
-    _lib.check(self._lib.hbk_sharded_lookup_fwd_end(
-      self._plan(), a[4], a[5], _lib.current_stream(self.device)))
+    if self.out_dtype is None:
+      _lib.check(self._lib.hbk_sharded_lookup_fwd_end(
+        self._plan(), a[4], a[5], _lib.current_stream(self.device)))
+    else:
+      _lib.check(self._lib.hbk_sharded_lookup_fwd_end_out16(
+        self._plan(), a[4], a[5], self._out_code(), _lib.current_stream(self.device)))
     return bound.outs
 
   def prefetch(self, bound, ids_ready=None):

@@ -79,7 +79,7 @@ class ShardedHashGroupLookup(ShardedGroupLookup):
 
   def __init__(self, tables, coll, combiners='sum', wire_dtype=None, dedup=False, max_norms=None, train=True,
                accums=None, moments=None, adam=None, ftrl_slots=None, ftrl=None, hot_rows=False, world_size=None,
-               initial_accumulator_value=0.1, row_accums=None, rowwise_adagrad=None, stores=None):
+               initial_accumulator_value=0.1, row_accums=None, rowwise_adagrad=None, stores=None, out_dtype=None):
     self.tables = list(tables)
     _ht.same_device(self.tables)
     _ht.require_fp32_tables(self.tables, 'ShardedHashGroupLookup',
@@ -91,7 +91,7 @@ class ShardedHashGroupLookup(ShardedGroupLookup):
     super().__init__(self._rows, coll, buckets=None, combiners=combiners, wire_dtype=wire_dtype,
                      world_size=world_size, accums=accums, hot_rows=hot_rows, dedup=dedup, moments=moments, adam=adam,
                      ftrl_slots=ftrl_slots, ftrl=ftrl, max_norms=max_norms, row_accums=row_accums,
-                     rowwise_adagrad=rowwise_adagrad)
+                     rowwise_adagrad=rowwise_adagrad, out_dtype=out_dtype)
     self._init_stores(stores)
 
   def _init_stores(self, stores):
@@ -405,6 +405,7 @@ class LowpShardedHashGroupLookup(ShardedHashGroupLookup):
       (``[capacity, dim]``; row-wise Adagrad ``[capacity, 1]``) and the optimizer objects.  They are the companions
       every lifecycle method moves with the keys.
     rounding, seed: as ``LowpSparseApply``; rank k steps with ``rank_seed(seed, k)``, the noise keyed by the SLOT.
+    out_dtype: as :class:`ShardedGroupLookup`: 16-bit outputs written by the requester's stitch.
 
   The owner's translate is ``hbk_hash_translate_runs_lowp_n``: a new row is the fp32 start row rounded to nearest
   even.  ``backward(grads, apply_lr=, optimizer=, emit=, finish=)`` is the plan's emit backward -- slot numbers,
@@ -420,7 +421,7 @@ class LowpShardedHashGroupLookup(ShardedHashGroupLookup):
   def __init__(self, tables16, coll, combiners='sum', wire='table', dedup=False, train=True, accums=None,   # pylint: disable=super-init-not-called
                moments=None, adam=None, ftrl_slots=None, ftrl=None, row_accums=None, rowwise_adagrad=None,
                rounding='nearest', seed=0, stores=None, initial_accumulator_value=0.1, max_norms=None,
-               weight_grads=False, wire_dtype=None, hot_rows=False):
+               weight_grads=False, wire_dtype=None, hot_rows=False, out_dtype=None):
     what = 'LowpShardedHashGroupLookup'
     self.tables = list(tables16)
     _ht.same_device(self.tables)
@@ -457,7 +458,7 @@ class LowpShardedHashGroupLookup(ShardedHashGroupLookup):
     self._own = None   # emit=False: per column (unique_rows, grad_rows, n_unique) this object owns
     ShardedGroupLookup.__init__(self, self._rows, coll, buckets=None, combiners=combiners, accums=accums, dedup=dedup,
                                 moments=moments, adam=adam, ftrl_slots=ftrl_slots, ftrl=ftrl, row_accums=row_accums,
-                                rowwise_adagrad=rowwise_adagrad)
+                                rowwise_adagrad=rowwise_adagrad, out_dtype=out_dtype)
     self._init_stores(stores)
 
   def _setup(self):

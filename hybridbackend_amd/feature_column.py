@@ -584,9 +584,14 @@ class DenseFeatures(_TableLayer):
       ``hb.embedding.Out16GroupLookup`` -- bit for bit the fp32 block cast with torch, without the cast pass.  With
       fp32 tables or with ``table_dtype``; weighted columns included.  ``backward`` takes the gradient in
       ``output_dtype`` or fp32 and upcasts it with one copy into its padded fp32 block; everything behind that is
-      unchanged.  Refused by name at construction: more than one rank, a hash-keyed column, a column with
-      ``max_norm``, and a column that would have to be staged through a tensor of its own (wider than 64 and not a
-      multiple of 4 elements wide at a multiple of 4 elements of the row).
+      unchanged.  One rank only unless ``out16_sharded``.  Refused by name at construction: more than one rank
+      without ``out16_sharded``, a hash-keyed column, a column with ``max_norm``, and a column that would have to be
+      staged through a tensor of its own (wider than 64 and not a multiple of 4 elements wide at a multiple of 4
+      elements of the row).
+    out16_sharded: True lets a layer with ``output_dtype`` span W > 1 ranks, as ``lowp_sharded`` does for
+      ``table_dtype``: the sharded group's columns are written into the same padded block by the sharded 16-bit forward
+      (``ShardedGroupLookup(out_dtype=)``; with ``lowp_sharded`` over 16-bit shards), the replicated group's by
+      ``Out16GroupLookup`` as on one rank.  The refusals above stand.  At W = 1 the argument changes nothing.
 
   Hash-keyed columns (:class:`HashEmbeddingColumn`) mix freely with bucketed ones; column order decides the
   block offsets.  ``hash_tables[c]`` is the column's :class:`HashTable` (None for a bucketed column) and
@@ -610,12 +615,12 @@ class DenseFeatures(_TableLayer):
   def __init__(self, columns, device, coll=None, batch_size=0, init=None,
                initial_accumulator_value=None, optimizer=None, adam=None, ftrl=None, train=True,
                rowwise_adagrad=None, aggregate_replicated=False, replicated_scale=None, table_dtype=None,
-               table_rounding='nearest', table_seed=0, lowp_sharded=False, output_dtype=None):
+               table_rounding='nearest', table_seed=0, lowp_sharded=False, output_dtype=None, out16_sharded=False):
     self.table_dtype = table_dtype
     self.lowp_sharded = bool(lowp_sharded)
     self.output_dtype = output_dtype
     if output_dtype is not None:
-      self._check_out16(columns, coll, output_dtype)
+      self._check_out16(columns, coll, output_dtype, out16_sharded)
     if table_dtype is not None:
       self._check_lowp(columns, coll, table_dtype, table_rounding, table_seed, lowp_sharded)
     self._init_tables(columns, device, coll, batch_size, init, initial_accumulator_value, optimizer,
@@ -643,14 +648,14 @@ class DenseFeatures(_TableLayer):
     two_slot_kw = self._two_slot_kw
     self._lookup = self._grad = self._sharded = None
     if self._rep and output_dtype is not None:
-      # 16-bit outputs (one rank, bucketed columns: checked above): the block is written in place by the 16-bit-output
+      # 16-bit outputs (bucketed columns: checked above): the block is written in place by the 16-bit-output
       # forward; the backward is the one the tables' type has today, over an fp32 gradient block
       from hybridbackend_amd.embedding.out16 import Out16GroupLookup   # pylint: disable=import-outside-toplevel
       self._lookup = Out16GroupLookup(pick(self._rep, self.weights),
                                       [self.columns[c].num_buckets for c in self._rep],
                                       [self.columns[c].combiner for c in self._rep], out_dtype=output_dtype)
       accums = pick(self._rep, self.accums) if self.accums is not None else None
-      if table_dtype is not None:
+      if table_dtype is not None and self._world() <= 1:   # (at W > 1 the replicated tables stay fp32)
         from hybridbackend_amd.embedding.lowp import LowpLookupGrad   # pylint: disable=import-outside-toplevel
         self._grad = LowpLookupGrad(self._lookup, accums, rounding=table_rounding, seed=table_seed,
                                     **two_slot_kw(self._rep))
@@ -683,7 +688,8 @@ class DenseFeatures(_TableLayer):
                                              dedup=[self.columns[c].dedup for c in self._shd],
                                              accums=(pick(self._shd, self.accums)
                                                      if self.accums is not None else None),
-                                             rounding=table_rounding, seed=table_seed, **two_slot_kw(self._shd))
+                                             rounding=table_rounding, seed=table_seed, out_dtype=output_dtype,
+                                             **two_slot_kw(self._shd))
     elif self._shd:
       self._sharded = ShardedGroupLookup(pick(self._shd, self.weights), coll,
                                          buckets=[self.columns[c].num_buckets for c in self._shd],
@@ -693,7 +699,7 @@ class DenseFeatures(_TableLayer):
                                          max_norms=[self.columns[c].max_norm for c in self._shd],
                                          accums=(pick(self._shd, self.accums)
                                                  if self.accums is not None else None),
-                                         **two_slot_kw(self._shd))
+                                         out_dtype=output_dtype, **two_slot_kw(self._shd))
     if self._hash:
       combiners = [self.columns[c].combiner for c in self._hash]
       if self._world() > 1:
@@ -739,18 +745,19 @@ class DenseFeatures(_TableLayer):
       off += col.dimension
 
   @staticmethod
-  def _check_out16(columns, coll, output_dtype):
+  def _check_out16(columns, coll, output_dtype, out16_sharded=False):
     """Everything ``output_dtype`` refuses, before any table is allocated."""
     what = f'DenseFeatures(output_dtype={output_dtype})'
     if output_dtype not in (torch.bfloat16, torch.float16):
       raise _bad(f'DenseFeatures(output_dtype=): None, torch.bfloat16 or torch.float16, got {output_dtype!r}')
-    if coll is not None and coll.world_size > 1:
-      raise _bad(f'{what}: 16-bit outputs are written on one rank only, the layer spans {coll.world_size} (the '
-                 'sharded step stores fp32 rows)')
+    if coll is not None and coll.world_size > 1 and not out16_sharded:
+      raise _bad(f'{what}: 16-bit outputs are written on one rank only, the layer spans {coll.world_size}; '
+                 'out16_sharded=True lets the sharded step write them (ShardedGroupLookup(out_dtype=))')
     off = 0
     for col in columns:
       if _is_hash(col):
-        raise _bad(f'{what}: column {col.key!r} is hash-keyed; hash-keyed lookups store fp32 rows')
+        raise _bad(f'{what}: column {col.key!r} is hash-keyed; the layer writes 16-bit outputs for bucketed columns '
+                   'only (ShardedHashGroupLookup(out_dtype=) serves hash columns on their own)')
       if col.max_norm is not None:
         raise _bad(f'{what}: column {col.key!r} has max_norm; the clip is part of the fp32-output forward')
       if col.dimension > 64 and (off % 4 != 0 or col.dimension % 4 != 0):

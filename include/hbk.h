@@ -747,6 +747,43 @@ typedef struct {
 } hbk_out16_lookup_column_t;
 int hbk_group_lookup_fwd_out16(int32_t n_cols, const hbk_out16_lookup_column_t* cols, hbk_stream_t stream);
 
+/* THE 16-BIT STITCH  hbk_lookup_fwd_runs_out16: the entry above over a SEGMENTED table, as the requester of the sharded
+ *   step sees its received rows: logical rows [run_start[k], run_start[k + 1]) (the last run ends at col.rows) live at
+ *   col.table + run_base[k] ELEMENTS; run_start[0] = 0, run_start non-decreasing (an empty run is stepped over); device
+ *   int64 arrays [n_runs], n_runs >= 1; a base may be negative.  A new symbol, detected by its presence.
+ *   col.table_dtype names the rows of the buffer: HBK_OUT16_TABLE_FP32, HBK_LOWP_BF16 / HBK_LOWP_FP16 (a 16-bit table's
+ *   own bits), and HBK_LOWP_FP16 also for the fp16 rows of the fused wire (what HBK_LOOKUP_TABLE_HALF marks in
+ *   hbk_lookup_column_t: the same exact upcast).  One call may mix them.  Ids are row numbers, int32 or int64:
+ *   col.bucket must be 0 and col.divisor 1; a row outside [0, col.rows) is a zero row.
+ *   out[s] = round(f[s]) with f[s] the fp32 row that hbk_group_lookup_fwd (fp32 and fused-wire rows) or
+ *   hbk_lowp_lookup_fwd_runs (16-bit rows) computes over the same runs: the sums, the three combiners, id_weights, the
+ *   zero-divisor and invalid-row rules and the rounding are those written out above, expression for expression.  Output
+ *   memory is never read.
+ *   The STORE side picks the lane width and the LOAD side follows the run alignment:
+ *     W = 8  dim % 8 == 0, `out` and its stride 16-byte aligned: one 16-byte store per lane, fed by TWO loads of 4
+ *            elements (2 x 16 bytes of fp32 rows, 2 x 8 bytes of 16-bit rows);
+ *     W = 4  dim % 4 == 0, `out` and its stride 8-byte aligned: one 8-byte store, one load.  Both serve dim <= 256 and
+ *            need the buffer 16-byte (fp32) or 8-byte (16-bit) aligned and every run base a multiple of 4 ELEMENTS --
+ *            not of 8: what hbk_sharded_layout's padding gives.  The bases are device data, so this is the caller's
+ *            promise (the entry reads nothing on the host); there is no width whose bases must be multiples of 8;
+ *     W = 1  otherwise, dim <= 64, any base: 2-byte stores that touch no neighbouring byte.
+ *   chunk_elems as above: 0 takes 8 from dim 64 on where the column allows it, else 4; 8 takes 8 wherever possible, 4
+ *   never; no bit depends on it.  The lane that holds an id resolves it once to its row's element offset and hands that
+ *   to the row's lanes by shuffle; with n_runs <= 64 the run table is held in registers (lane k: run k) and searched
+ *   without touching memory, with more runs the holding lane walks the arrays.  One launch per 64 columns, kind and
+ *   lane width; non-temporal stores; no LDS, no atomics, no workspace, no host read: the call can be captured.
+ *   Refused before the first launch (HBK_INVALID_ARGUMENT, the column named): what hbk_group_lookup_fwd_out16 refuses,
+ *   plus n_runs < 1 or a NULL run array, bucket != 0 or divisor != 1, and a non-zero reserved word of either struct.
+ *   n_cols == 0 answers OK without touching a device. */
+typedef struct {
+  hbk_out16_lookup_column_t col;
+  const int64_t* run_start;  /* device [n_runs] */
+  const int64_t* run_base;   /* device [n_runs], elements */
+  int32_t n_runs;            /* >= 1 */
+  int32_t reserved;          /* 0 */
+} hbk_out16_runs_column_t;
+int hbk_lookup_fwd_runs_out16(int32_t n_cols, const hbk_out16_runs_column_t* cols, hbk_stream_t stream);
+
 /* APPLY  hbk_lowp_apply_slices_n: the contract of hbk_sparse_apply_slices_n (distinct rows; an entry outside
  *   [0, rows), -1 included, touches nothing; n_unique read on the device and clamped to [0, capacity]; the five
  *   rules; one launch per 64 columns, no workspace, no host read; hbk_adam_t.finish advances the beta powers
@@ -2353,6 +2390,25 @@ int hbk_sharded_lookup_fwd_begin(hbk_sharded_t plan, const int64_t* const* ids,
                                  const int64_t* n_segments, hbk_stream_t stream);
 int hbk_sharded_lookup_fwd_end(hbk_sharded_t plan, float* const* outs, const int32_t* out_strides,
                                hbk_stream_t stream);
+/* 16-bit outputs of the sharded forward (new symbols, detected by their presence): _end_out16 is _end whose stitch
+ * is hbk_lookup_fwd_runs_out16 -- outs[c] holds [n_segments, dim] rows of out_dtype (HBK_LOWP_BF16 | HBK_LOWP_FP16)
+ * elements, out_strides count ELEMENTS, and outs[c] = round(what _end writes), once per element, to nearest even: the
+ * fp32 forward followed by torch's cast, bit for bit.  Everything before the stitch -- partition, size wait, id
+ * exchange, owner gather, row exchange, dedup compose, hop events -- is _end's and _begin's own, on every wire (fp32,
+ * the fused fp16 wire, 16-bit shards with HBK_LOWP_WIRE_TABLE or _FLOAT), with dedup, column groups, inline and
+ * hopped exchanges and prefetch.  hbk_sharded_lookup_fwd_out16 / _weighted_out16 = _begin (the weighted one with its
+ * own checks) + _end_out16.  The backward is unchanged: it reads the step's index and the gradient, never the outputs.
+ * Refused before any launch or exchange: an unknown out_dtype (HBK_INVALID_ARGUMENT); a p2p-bound plan
+ * (HBK_UNIMPLEMENTED: its owner gather writes fp32 rows into the requester's output, there is no stitch to round in). */
+int hbk_sharded_lookup_fwd_end_out16(hbk_sharded_t plan, void* const* outs, const int32_t* out_strides,
+                                     int32_t out_dtype, hbk_stream_t stream);
+int hbk_sharded_lookup_fwd_out16(hbk_sharded_t plan, const int64_t* const* ids, const int64_t* n_ids,
+                                 const int32_t* const* row_splits, const int64_t* n_segments, void* const* outs,
+                                 const int32_t* out_strides, int32_t out_dtype, hbk_stream_t stream);
+int hbk_sharded_lookup_fwd_weighted_out16(hbk_sharded_t plan, const int64_t* const* ids, const int64_t* n_ids,
+                                          const int32_t* const* row_splits, const int64_t* n_segments,
+                                          const float* const* id_weights, void* const* outs,
+                                          const int32_t* out_strides, int32_t out_dtype, hbk_stream_t stream);
 /* The first half in two parts, so that the owner of a bounded hash table gets its chance between them:
  * hbk_sharded_lookup_fwd_begin = hbk_sharded_lookup_fwd_ids + hbk_sharded_lookup_fwd_gather, the same launches and
  * exchanges in the same order and the same host-time report.
