@@ -164,6 +164,31 @@ class Out16RunsColumn(C.Structure):
               ('n_runs', C.c_int32), ('reserved', C.c_int32)]
 
 
+QUANT8_OUT_FP32 = 0   # hbk_quant8_lookup_column_t.out_dtype / hbk_quant8_rows_column_t.src_dtype beside LOWP_*
+
+
+class Quant8RowsColumn(C.Structure):
+  """hbk_quant8_rows_column_t"""
+  _fields_ = [('table', C.c_void_p), ('rows_f', C.c_void_p), ('rows', C.c_int64), ('dim', C.c_int32),
+              ('pitch', C.c_int32), ('src_dtype', C.c_int32), ('reserved', C.c_int32)]
+
+
+class Quant8LookupColumn(C.Structure):
+  """hbk_quant8_lookup_column_t"""
+  _fields_ = [('table', C.c_void_p), ('pitch', C.c_int32), ('dim', C.c_int32), ('rows', C.c_int64),
+              ('ids', C.c_void_p), ('ids_dtype', C.c_int32), ('combiner', C.c_int32), ('n_ids', C.c_int64),
+              ('row_splits', C.c_void_p), ('n_segments', C.c_int64), ('bucket', C.c_int64),
+              ('divisor', C.c_int32), ('out_stride', C.c_int32), ('out', C.c_void_p),
+              ('id_weights', C.c_void_p), ('out_dtype', C.c_int32), ('chunk_elems', C.c_int32)]
+
+
+class Quant8SlicesColumn(C.Structure):
+  """hbk_quant8_slices_column_t"""
+  _fields_ = [('table', C.c_void_p), ('pitch', C.c_int32), ('dim', C.c_int32), ('rows', C.c_int64),
+              ('unique_rows', C.c_void_p), ('grad_rows', C.c_void_p), ('n_unique', C.c_void_p),
+              ('capacity', C.c_int64)]
+
+
 class ReplicaColumn(C.Structure):
   """hbk_replica_column_t"""
   _fields_ = [('unique_rows', C.c_void_p), ('grad_rows', C.c_void_p), ('n_unique', C.c_void_p),
@@ -371,6 +396,10 @@ def _declare(l):
     'hbk_lowp_gather_rows_n': (C.c_int, [i32, vp, vp]),
     'hbk_lowp_lookup_fwd_runs': (C.c_int, [i32, vp, vp]),
     'hbk_lookup_fwd_runs_out16': (C.c_int, [i32, vp, vp]),
+    'hbk_quant8_rows_n': (C.c_int, [i32, vp, vp, vp]),
+    'hbk_dequant8_rows_n': (C.c_int, [i32, vp, vp]),
+    'hbk_quant8_lookup_fwd': (C.c_int, [i32, vp, vp]),
+    'hbk_quant8_apply_slices_n': (C.c_int, [i32, vp, i32, vp, vp, vp, C.c_float, vp, vp]),
     'hbk_sharded_set_table_dtypes': (C.c_int, [vp, vp, i32]),
     'hbk_replica_grads_pack_n': (C.c_int, [i32, vp, vp, i64, vp]),
     'hbk_replica_grads_rows_n': (C.c_int, [i32, vp, vp]),

@@ -183,7 +183,12 @@ class _TableLayer:
     # fp32 and is built from an fp32 stand-in of the table's shape (zero strides: it owns one word)
     # DenseFeatures(lowp_sharded=True) at W > 1: the SHARDED tables only; the replicated ones stay fp32
     like = self.weights
-    if table_dtype is not None:
+    if table_dtype == 'int8':
+      # 8-bit tables (one rank only, checked before): init's result quantised to nearest, row by row
+      from hybridbackend_amd.embedding.quant8 import quantize_rows8   # pylint: disable=import-outside-toplevel
+      like = [torch.empty((), dtype=torch.float32, device=self.device).expand(w.shape) for w in self.weights]
+      self.weights = quantize_rows8(self.weights)
+    elif table_dtype is not None:
       low = [world <= 1 or (bool(lowp_sharded) and s and h is None) for s, h in zip(self.sharded, self.hash_tables)]
       self.weights = [w.to(table_dtype) if l else w for w, l in zip(self.weights, low)]
       like = [torch.empty((), dtype=torch.float32, device=self.device).expand(w.shape) if l else w
@@ -562,6 +567,12 @@ class DenseFeatures(_TableLayer):
       caller aggregates.  At W = 1 it changes nothing.  A replicated column wider than the apply takes (256
       floats, 64 when not a multiple of 4) is refused at construction.
     replicated_scale: what multiplies the summed gradients; None: ``1 / W``, the mean of the reference.
+    table_dtype: ``'int8'``: the tables are 8-bit rows with one fp32 scale each (``torch.uint8`` ``[rows, pitch]``,
+      include/hbk.h "8-bit tables"): ``init``'s result quantised to nearest, fp32 slots, the forward
+      ``hb.embedding.Quant8GroupLookup`` (fp32 outputs, or ``output_dtype``), the step ``hb.embedding.Quant8LookupGrad``
+      with ``table_rounding`` (``'stochastic'`` allowed) and ``table_seed``; ``variables()`` / ``save`` / ``restore``
+      carry the 8-bit tensors.  One rank only (``lowp_sharded`` does not apply); the other refusals are the 16-bit
+      layer's.  Otherwise:
     table_dtype: None (fp32 tables: nothing below applies), ``torch.bfloat16`` or ``torch.float16``: the tables are
       stored in 16 bits -- ``init``'s result rounded to nearest -- with fp32 sums in the forward
       (``hb.embedding.LowpGroupLookup``) and fp32 accumulators and slots in the step
@@ -647,7 +658,7 @@ class DenseFeatures(_TableLayer):
     pick = lambda idx, xs: [xs[c] for c in idx]   # noqa: E731
     two_slot_kw = self._two_slot_kw
     self._lookup = self._grad = self._sharded = None
-    if self._rep and output_dtype is not None:
+    if self._rep and output_dtype is not None and table_dtype != 'int8':
       # 16-bit outputs (bucketed columns: checked above): the block is written in place by the 16-bit-output
       # forward; the backward is the one the tables' type has today, over an fp32 gradient block
       from hybridbackend_amd.embedding.out16 import Out16GroupLookup   # pylint: disable=import-outside-toplevel
@@ -661,6 +672,8 @@ class DenseFeatures(_TableLayer):
                                     **two_slot_kw(self._rep))
       else:
         self._grad = GroupLookupGrad(self._lookup, accums, **two_slot_kw(self._rep))
+    elif self._rep and table_dtype == 'int8':
+      pass   # (below: the 8-bit lookup writes either kind of output itself)
     elif self._rep and table_dtype is not None and self._world() <= 1:
       # 16-bit tables: the same two roles, so that __call__ and backward do not fork
       from hybridbackend_amd.embedding.lowp import LowpGroupLookup, LowpLookupGrad   # pylint: disable=import-outside-toplevel
@@ -679,6 +692,16 @@ class DenseFeatures(_TableLayer):
       self._grad = GroupLookupGrad(
         self._lookup, pick(self._rep, self.accums) if self.accums is not None else None,
         **two_slot_kw(self._rep))
+    if self._rep and table_dtype == 'int8':
+      # 8-bit tables: the same two roles; fp32 or 16-bit outputs from the one forward
+      from hybridbackend_amd.embedding.quant8 import Quant8GroupLookup, Quant8LookupGrad   # pylint: disable=import-outside-toplevel
+      self._lookup = Quant8GroupLookup(pick(self._rep, self.weights), [self.columns[c].dimension for c in self._rep],
+                                       [self.columns[c].num_buckets for c in self._rep],
+                                       [self.columns[c].combiner for c in self._rep],
+                                       out_dtype=output_dtype or torch.float32)
+      self._grad = Quant8LookupGrad(
+        self._lookup, pick(self._rep, self.accums) if self.accums is not None else None,
+        rounding=table_rounding, seed=table_seed, **two_slot_kw(self._rep))
     if self._shd and table_dtype is not None:
       # lowp_sharded (else refused above): 16-bit shards on their own wire, fp32 slots, the step in the driver
       from hybridbackend_amd.embedding.lowp import LowpShardedGroupLookup   # pylint: disable=import-outside-toplevel
@@ -724,12 +747,14 @@ class DenseFeatures(_TableLayer):
   def _check_lowp(columns, coll, table_dtype, table_rounding, table_seed, lowp_sharded=False):
     """Everything ``table_dtype`` refuses, before any table is allocated."""
     from hybridbackend_amd.embedding.lowp import check_rounding   # pylint: disable=import-outside-toplevel
-    if table_dtype not in (torch.bfloat16, torch.float16):
-      raise _bad(f'DenseFeatures(table_dtype=): None, torch.bfloat16 or torch.float16, got {table_dtype!r}')
-    check_rounding(table_rounding, table_seed, [table_dtype], 'DenseFeatures(table_dtype=)')
-    if coll is not None and coll.world_size > 1 and not lowp_sharded:
-      raise _bad(f'DenseFeatures(table_dtype={table_dtype}): 16-bit tables are kept on one rank only, the layer '
-                 f'spans {coll.world_size} (sharded and replicated-at-W>1 tables stay fp32)')
+    int8 = isinstance(table_dtype, str) and table_dtype == 'int8'
+    if not int8 and table_dtype not in (torch.bfloat16, torch.float16):
+      raise _bad(f"DenseFeatures(table_dtype=): None, torch.bfloat16, torch.float16 or 'int8', got {table_dtype!r}")
+    # (stochastic rounding is defined for bf16 and for 8-bit tables)
+    check_rounding(table_rounding, table_seed, [] if int8 else [table_dtype], 'DenseFeatures(table_dtype=)')
+    if coll is not None and coll.world_size > 1 and (int8 or not lowp_sharded):
+      raise _bad(f'DenseFeatures(table_dtype={table_dtype}): {"8" if int8 else "16"}-bit tables are kept on one rank '
+                 f'only, the layer spans {coll.world_size} (sharded and replicated-at-W>1 tables stay fp32)')
     off = 0
     for col in columns:
       if _is_hash(col):
@@ -742,6 +767,9 @@ class DenseFeatures(_TableLayer):
         raise _bad(f'DenseFeatures(table_dtype={table_dtype}): column {col.key!r} ({col.dimension} wide at float '
                    f'{off} of the block) cannot be addressed in place: a row of more than 64 elements must start '
                    'on a 16-byte boundary of the output row; reorder the columns')
+      if int8 and (col.dimension > 256 or (col.dimension % 4 != 0 and col.dimension > 64)):
+        raise _bad(f"DenseFeatures(table_dtype='int8'): column {col.key!r}: dimension {col.dimension} is beyond what "
+                   'the 8-bit step takes (at most 256 when a multiple of 4, 64 otherwise)')
       off += col.dimension
 
   @staticmethod

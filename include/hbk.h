@@ -897,6 +897,126 @@ typedef struct {
 } hbk_lowp_lookup_runs_column_t;
 int hbk_lowp_lookup_fwd_runs(int32_t n_cols, const hbk_lowp_lookup_runs_column_t* cols, hbk_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * 8-bit tables: rows of int8 codes with one fp32 scale per row (row-wise symmetric int8), fp32 sums, fp32
+ * optimizer slots.  Four entries, all detected by the presence of the symbol (the structs above and the version
+ * are those of 0.2.0): a quantiser, a dequantiser, a forward and the optimizer step on IndexedSlices the caller
+ * holds.  The backward between them is hbk_group_lookup_bwd_apply in its emit form (apply_lr = 0), which never
+ * reads the table.  NEVER hand an 8-bit table to an entry that steps or gathers fp32 or 16-bit rows.
+ *
+ * LAYOUT  a table is a uint8 buffer [rows, pitch], 4-byte aligned.  With dim4 = round_up(dim, 4):
+ *     bytes 0 .. dim-1 of a row    the codes
+ *     bytes dim4 .. dim4+3         the row's fp32 scale (little endian, as the device stores a float)
+ *   pitch is a multiple of 4 and >= dim4 + 4 (the default: dim4 + 4).  The bytes between dim and dim4 and the
+ *   bytes past the scale are written as 0 by the quantiser and are never read by any entry; the step leaves them.
+ *
+ * DECODE  a code c means q = c - 128 (offset binary: the unsigned byte-to-float conversions unpack it), and the
+ *   element is x = (float)q * scale: one fp32 multiply.
+ *
+ * QUANTISE  a row v[0 .. dim) -> codes and scale; every step one correctly rounded fp32 operation, no contraction:
+ *     amax = max_k |v_k|
+ *     amax < 0x1p-100f:  the row is a zero row: scale = 0, every code 128
+ *     otherwise          scale = amax / 127.0f,  t_k = v_k / scale
+ *       HBK_LOWP_ROUND_NEAREST     q_k = rintf(t_k)                               (ties to even)
+ *       HBK_LOWP_ROUND_STOCHASTIC  q_k = floorf(t_k + (float)u_k * 0x1p-16f),     u_k = noise_k & 0xFFFF
+ *     q_k is clamped to [-127, 127]; the code is q_k + 128 (0 is never written).
+ *   noise_k is the noise of hbk_lowp_apply_slices_n above: a function of (seed, step counter, the column's index in
+ *   the call, the row, the element index k).  u_k * 2^-16 is exact and lies in [0, 1), so the stochastic form rounds
+ *   t down with probability 1 - frac(t) and up with frac(t): unbiased, and an exactly representable t never moves.
+ *   Non-finite inputs promise no particular codes or scale; nothing is ever written outside the row.
+ *
+ * hbk_quant8_rows_n / hbk_dequant8_rows_n: one launch for up to 64 tables (a call with more splits).  Quantise reads
+ *   src = fp32, bf16 or fp16 [rows, dim] (contiguous; 16-bit elements are upcast exactly first) and writes the whole
+ *   row of the table, padding bytes included; dequantise writes fp32 [rows, dim].  A row is owned by
+ *   pow2(dim4 / 4) adjacent lanes of 4 elements each (dim <= 256); amax is a butterfly maximum over the row's lanes.
+ *   rounding as hbk_lowp_rounding_t above (NULL = NEAREST; STOCHASTIC reads step[0] on the device and, with advance,
+ *   a one-thread launch adds 1 behind it).  Refused before the first launch (HBK_INVALID_ARGUMENT, the column named):
+ *   dim < 1 or > 256; pitch not a multiple of 4 or < dim4 + 4; a table not 4-byte aligned; src not aligned to its
+ *   element; an unknown src_dtype or rounding mode; a NULL table or src with rows > 0; rows < 0 or >= 2^31;
+ *   STOCHASTIC with a NULL or misaligned step counter.
+ *
+ * FORWARD  hbk_quant8_lookup_fwd: hbk_lowp_lookup_fwd (ragged columns, id_weights, the three combiners, bucket and
+ *   divisor, the zero-divisor and invalid-row rules, in-order fp32 sums from +0: the expressions written out there)
+ *   with e_j = decode(table[row(j), :]), writing fp32 rows (out_dtype HBK_QUANT8_OUT_FP32) or bf16 / fp16 rows
+ *   (HBK_LOWP_BF16 / HBK_LOWP_FP16) rounded once per element to nearest even as hbk_group_lookup_fwd_out16 rounds.
+ *   The result is hbk_group_lookup_fwd over the dequantised table, bit for bit (16-bit outputs: followed by the
+ *   cast).  Output memory is never read.  A row's scale is loaded once per row and lane.
+ *   A row is owned by pow2(dim4 / 4) adjacent lanes of 4 codes each -- ONE 4-byte load per lane whatever the row's
+ *   alignment, the scale word read by the row's lanes from the same line, ONE 16-byte (fp32) or 8-byte (16-bit)
+ *   store per lane -- when dim % 4 == 0 and `out` and its stride are 16-byte (fp32) / 8-byte (16-bit) aligned:
+ *   dim <= 256.  Otherwise one code per lane, dim <= 64, with element-sized stores that touch no neighbouring byte.
+ *   chunk_elems: 0 (the default) or 4; wider lanes are not built, and no bit could depend on the width.
+ *   One launch per 64 columns, kind (one id per segment / ragged), lane width and output size; no LDS, no atomics,
+ *   no workspace, no host read: the call can be captured.  Refused before the first launch (HBK_INVALID_ARGUMENT,
+ *   the column named): what hbk_lowp_lookup_fwd refuses, with: dim beyond the bounds above; pitch not a multiple of
+ *   4 or < dim4 + 4; a table not 4-byte aligned; an unknown out_dtype; `out` not aligned to its element;
+ *   chunk_elems not 0 or 4.  n_cols == 0 answers OK.
+ *
+ * STEP  hbk_quant8_apply_slices_n: the contract of hbk_lowp_apply_slices_n (distinct rows; an entry outside
+ *   [0, rows), -1 included, touches nothing; n_unique read on the device and clamped to [0, capacity]; the five rules
+ *   with the arithmetic of sparse_rules.h; one launch per 64 columns, no workspace, no host read; hbk_adam_t.finish
+ *   advances the beta powers behind the step, also with n_cols == 0).  For a stepped row r:
+ *       w32          = decode(table[r, :])
+ *       (w32', s')   = rule(w32, slots[r], g)      formulas, rounding and operation order of the fp32 entry
+ *       slots[r]     = s'                          fp32 [rows, dim] contiguous (row-wise Adagrad: [rows, 1])
+ *       table[r, :]  = quantise(w32')              codes and scale; amax by a butterfly maximum over the row's
+ *                                                  lanes in which every lane of the wave takes part
+ *   so that with NEAREST table and slots equal hbk_sparse_apply_slices_n on the dequantised table, quantised, bit for
+ *   bit.  A row is split over lanes as there: 4 elements per lane when dim % 4 == 0 and the slots and grad_rows are
+ *   16-byte aligned (dim <= 256), else one element per lane (dim <= 64); row-wise Adagrad's sum follows that layout.
+ *   STOCHASTIC works for every rule; the counter and the advance are those of hbk_lowp_apply_slices_n.
+ *   Refused before the first launch: what hbk_lowp_apply_slices_n refuses, with the pitch and alignment rules of the
+ *   layout in the place of the 16-bit ones. */
+#define HBK_QUANT8_OUT_FP32 0
+#define HBK_QUANT8_SRC_FP32 0    /* hbk_quant8_rows_column_t.src_dtype beside HBK_LOWP_BF16 / HBK_LOWP_FP16 */
+typedef struct {
+  void* table;               /* device uint8 [rows, pitch] */
+  void* rows_f;              /* quantise: the source [rows, dim] of src_dtype; dequantise: the fp32 [rows, dim] result */
+  int64_t rows;
+  int32_t dim;
+  int32_t pitch;             /* bytes between rows of the table; 0 = dim4 + 4 */
+  int32_t src_dtype;         /* quantise: HBK_QUANT8_SRC_FP32 | HBK_LOWP_BF16 | HBK_LOWP_FP16; dequantise: 0 */
+  int32_t reserved;          /* 0 */
+} hbk_quant8_rows_column_t;
+int hbk_quant8_rows_n(int32_t n_cols, const hbk_quant8_rows_column_t* cols, const hbk_lowp_rounding_t* rounding,
+                      hbk_stream_t stream);
+int hbk_dequant8_rows_n(int32_t n_cols, const hbk_quant8_rows_column_t* cols, hbk_stream_t stream);
+
+typedef struct {
+  const void* table;         /* device uint8 [rows, pitch] */
+  int32_t pitch;             /* bytes between rows; 0 = dim4 + 4 */
+  int32_t dim;
+  int64_t rows;
+  const void* ids;           /* device [n_ids] */
+  int32_t ids_dtype;         /* HBK_INT32 | HBK_INT64 */
+  int32_t combiner;          /* HBK_COMBINER_* */
+  int64_t n_ids;
+  const int32_t* row_splits; /* device [n_segments + 1] or NULL */
+  int64_t n_segments;        /* == n_ids when row_splits == NULL */
+  int64_t bucket;            /* 0 = ids are row numbers already */
+  int32_t divisor;           /* >= 1 */
+  int32_t out_stride;        /* ELEMENTS between rows of `out`; 0 = dim */
+  void* out;                 /* device [n_segments, dim] of out_dtype elements */
+  const float* id_weights;   /* device fp32 [n_ids] or NULL */
+  int32_t out_dtype;         /* HBK_QUANT8_OUT_FP32 | HBK_LOWP_BF16 | HBK_LOWP_FP16 */
+  int32_t chunk_elems;       /* 0 = the default, or 4: codes per lane where the column allows it */
+} hbk_quant8_lookup_column_t;
+int hbk_quant8_lookup_fwd(int32_t n_cols, const hbk_quant8_lookup_column_t* cols, hbk_stream_t stream);
+
+typedef struct {
+  void* table;                 /* device uint8 [rows, pitch] */
+  int32_t pitch;               /* bytes between rows; 0 = dim4 + 4 */
+  int32_t dim;
+  int64_t rows;
+  const int64_t* unique_rows;  /* device [capacity] */
+  const float* grad_rows;      /* device fp32 [capacity, dim], contiguous */
+  const int32_t* n_unique;     /* device [1] */
+  int64_t capacity;
+} hbk_quant8_slices_column_t;
+int hbk_quant8_apply_slices_n(int32_t n_cols, const hbk_quant8_slices_column_t* cols, int32_t apply,
+                              float* const* slot0, float* const* slot1, const void* params, float lr,
+                              const hbk_lowp_rounding_t* rounding, hbk_stream_t stream);
+
 /* Gradients of REPLICATED tables across ranks, in their dense form (the reference's
  * TRAINABLE_REPLICATED_SMALL, training/gradient.py:131-141): every rank scatters its IndexedSlices into one
  * bucket, ONE allreduce sums the buckets, and each table's block of the bucket is then read back as
