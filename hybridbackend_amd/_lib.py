@@ -400,6 +400,8 @@ def _declare(l):
     'hbk_dequant8_rows_n': (C.c_int, [i32, vp, vp]),
     'hbk_quant8_lookup_fwd': (C.c_int, [i32, vp, vp]),
     'hbk_quant8_apply_slices_n': (C.c_int, [i32, vp, i32, vp, vp, vp, C.c_float, vp, vp]),
+    'hbk_quant8_lookup_fwd_wide': (C.c_int, [i32, vp, i32, vp]),
+    'hbk_quant8_lookup_lane_codes': (C.c_int32, [vp, i32]),
     'hbk_sharded_set_table_dtypes': (C.c_int, [vp, vp, i32]),
     'hbk_replica_grads_pack_n': (C.c_int, [i32, vp, vp, i64, vp]),
     'hbk_replica_grads_rows_n': (C.c_int, [i32, vp, vp]),

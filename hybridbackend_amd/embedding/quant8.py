@@ -41,9 +41,34 @@ class Quant8Rows:
     return (int(dim) + 3) // 4 * 4
 
   @staticmethod
-  def pitch_for(dim):
-    """The default pitch of a ``dim``-wide row in bytes: the codes rounded up to 4, then the scale."""
-    return Quant8Rows.dim4(dim) + 4
+  def pitch_for(dim, align=4):
+    """The smallest pitch of a ``dim``-wide row in bytes that is a multiple of ``align`` (4, 8 or 16): the codes
+    rounded up to 4, then the scale, then padding.  ``align=4`` is the default pitch; 8 / 16 is what lets a lane of 8 /
+    16 codes read its codes in one load (``Quant8GroupLookup(lane_codes=)``)."""
+    if align not in (4, 8, 16):
+      raise _bad(f'Quant8Rows.pitch_for: align must be 4, 8 or 16, got {align!r}')
+    return (Quant8Rows.dim4(dim) + 4 + align - 1) // align * align
+
+
+# 'auto': (ragged, 16-bit outputs, first dim, last dim) -> lane_codes.  Only what two runs of
+# tools/bench_quant8_tables.py both showed faster than 4 codes per lane with the ranges apart
+# (profiles/quant8_tables.txt; dims 16, 64 and 128 with one id per segment, 16 and 64 ragged); every other column keeps
+# the narrow forward.
+AUTO_LANE_CODES = (
+  (False, True, 16, 128, 8),    # one id per segment, 16-bit outputs: 6 % faster at dim 16, 17 % at 64, 18 - 19 % at 128
+  (False, False, 16, 16, 8),    # one id per segment, fp32 outputs: 3.5 % at dim 16; 11 - 16 % SLOWER at 64 and 128
+  (True, True, 64, 64, 16),     # ragged, 16-bit outputs, dim 64: 27 % (8 codes: 9 %); dim 16: every width loses
+  (True, False, 64, 64, 8),     # ragged, fp32 outputs, dim 64: 10 %
+)
+
+
+def auto_lane_codes(dim, out_dtype, ragged):
+  """The width ``lane_codes='auto'`` gives a column: 8, 16, or 0 for the narrow forward."""
+  o16 = out_dtype != torch.float32
+  for r, o, lo, hi, w in AUTO_LANE_CODES:
+    if r == bool(ragged) and o == o16 and lo <= dim <= hi and dim % w == 0:
+      return w
+  return 0
 
 
 def _require_tables8(tables8, dims, what):
@@ -140,8 +165,13 @@ class Quant8GroupLookup(GroupLookup):
     dims: the tables' dims.
     buckets, combiners, divisor: as :class:`GroupLookup`.
     out_dtype: ``torch.float32``, ``torch.bfloat16`` or ``torch.float16``: the element type of every output.
-    chunk_elems: None (the default lane width) or 4: codes a lane moves where the column allows it -- the one width
-      the build offers.  A pure speed choice: the result does not depend on it.
+    chunk_elems: None (the default lane width) or 4: codes a lane moves where the column allows it, in
+      ``hbk_quant8_lookup_fwd``.  A pure speed choice: the result does not depend on it.
+    lane_codes: None (``hbk_quant8_lookup_fwd``, unchanged), 8 or 16 (``hbk_quant8_lookup_fwd_wide``: lanes of that
+      many codes wherever a column allows it -- ``dim % lane_codes == 0`` and the output block and its stride on a
+      16-byte boundary -- and the narrow forward, in the same call, where not), or ``'auto'``: per column and bound
+      kind, the width :data:`AUTO_LANE_CODES` names.  A pure speed choice too.  ``lane_codes_used`` lists the width
+      every bound column gets.
 
   The calling convention is :class:`GroupLookup`'s -- ``bind``, ``__call__(ids, row_splits=None, outs=None,
   sp_weights=None)``, ``launch()``, ``bind_block``, outputs as column blocks of a wider tensor -- and the result is,
@@ -150,8 +180,14 @@ class Quant8GroupLookup(GroupLookup):
   ``GroupLookupGrad`` reads of its lookup say "none"."""
 
   def __init__(self, tables8, dims, buckets=None, combiners='sum', divisor=1, out_dtype=torch.float32,   # pylint: disable=super-init-not-called
-               chunk_elems=None, max_norms=None, hot_rows=False):
+               chunk_elems=None, max_norms=None, hot_rows=False, lane_codes=None):
     what = 'Quant8GroupLookup'
+    if lane_codes not in (None, 8, 16, 'auto'):
+      raise _bad(f"{what}: lane_codes must be None, 8, 16 or 'auto', got {lane_codes!r}")
+    if lane_codes is not None and chunk_elems is not None:
+      raise _bad(f'{what}: lane_codes={lane_codes!r} cannot be given together with chunk_elems={chunk_elems!r} '
+                 '(chunk_elems is the narrow forward\'s width)')
+    self.lane_codes = lane_codes
     if max_norms is not None and not (isinstance(max_norms, (list, tuple)) and all(x is None for x in max_norms)):
       raise _bad(f'{what}: max_norms is not supported for 8-bit tables (the clip reads and the clipped step writes '
                  'fp32 rows)')
@@ -191,6 +227,7 @@ class Quant8GroupLookup(GroupLookup):
       col.combiner = self.combiners[c]
       col.out_dtype = _OUT_DTYPES[out_dtype]
       col.chunk_elems = chunk_elems or 0
+    self._plan_calls()
 
   @property
   def dims(self):
@@ -246,7 +283,28 @@ class Quant8GroupLookup(GroupLookup):
       col.out = o.data_ptr()
       col.out_stride = 0 if o.is_contiguous() else int(o.stride(0))
     self._keep = (list(ids), row_splits, outs)
+    self._plan_calls()
     return outs
+
+  def _plan_calls(self):
+    """The calls of a launch: [(lane_codes or 0, n, column array)].  One call over the bound array, except under
+    ``'auto'`` when the rule gives the columns different widths: then one call, over a copy of its columns, per
+    width."""
+    n = len(self.tables)
+    if self.lane_codes == 'auto':
+      self._want = [auto_lane_codes(self._dims[c], self.out_dtype, bool(self._cols[c].row_splits)) for c in range(n)]
+    else:
+      self._want = [self.lane_codes or 0] * n
+    self._calls = []
+    for w in sorted(set(self._want)):
+      idx = [c for c in range(n) if self._want[c] == w]
+      cols = self._cols if len(idx) == n else (_lib.Quant8LookupColumn * len(idx))(*[self._cols[c] for c in idx])
+      self._calls.append((w, len(idx), cols))
+
+  @property
+  def lane_codes_used(self):
+    """The codes per lane of every bound column (``hbk_quant8_lookup_lane_codes``): 16, 8, 4 or 1."""
+    return [int(self._lib.hbk_quant8_lookup_lane_codes(C.byref(self._cols[c]), w)) for c, w in enumerate(self._want)]
 
   def bind_block(self, ids, row_splits, block, offsets, sp_weights=None):
     """bind() with every column's output a column block of ONE ``[segments, pitch]`` tensor of ``out_dtype``
@@ -267,7 +325,11 @@ class Quant8GroupLookup(GroupLookup):
       s = _lib.current_stream(self.tables[0].device if self.tables else None)
     else:
       s = C.c_void_p(stream.cuda_stream)
-    _lib.check(self._lib.hbk_quant8_lookup_fwd(len(self.tables), self._cols, s))
+    for w, n, cols in self._calls:
+      if w:
+        _lib.check(self._lib.hbk_quant8_lookup_fwd_wide(n, cols, w, s))
+      else:
+        _lib.check(self._lib.hbk_quant8_lookup_fwd(n, cols, s))
 
 
 class Quant8SparseApply(SparseApply):

@@ -572,7 +572,8 @@ class DenseFeatures(_TableLayer):
       ``hb.embedding.Quant8GroupLookup`` (fp32 outputs, or ``output_dtype``), the step ``hb.embedding.Quant8LookupGrad``
       with ``table_rounding`` (``'stochastic'`` allowed) and ``table_seed``; ``variables()`` / ``save`` / ``restore``
       carry the 8-bit tensors.  One rank only (``lowp_sharded`` does not apply); the other refusals are the 16-bit
-      layer's.  Otherwise:
+      layer's.  ``table_lane_codes`` (None, 8, 16 or ``'auto'``) is that forward's ``lane_codes``: a speed choice, the
+      result does not depend on it, and None changes nothing.  Otherwise:
     table_dtype: None (fp32 tables: nothing below applies), ``torch.bfloat16`` or ``torch.float16``: the tables are
       stored in 16 bits -- ``init``'s result rounded to nearest -- with fp32 sums in the forward
       (``hb.embedding.LowpGroupLookup``) and fp32 accumulators and slots in the step
@@ -626,8 +627,13 @@ class DenseFeatures(_TableLayer):
   def __init__(self, columns, device, coll=None, batch_size=0, init=None,
                initial_accumulator_value=None, optimizer=None, adam=None, ftrl=None, train=True,
                rowwise_adagrad=None, aggregate_replicated=False, replicated_scale=None, table_dtype=None,
-               table_rounding='nearest', table_seed=0, lowp_sharded=False, output_dtype=None, out16_sharded=False):
+               table_rounding='nearest', table_seed=0, lowp_sharded=False, output_dtype=None, out16_sharded=False,
+               table_lane_codes=None):
     self.table_dtype = table_dtype
+    if table_lane_codes is not None and table_dtype != 'int8':
+      raise _bad("DenseFeatures(table_lane_codes=) applies to table_dtype='int8' only")
+    if table_lane_codes not in (None, 8, 16, 'auto'):
+      raise _bad(f"DenseFeatures(table_lane_codes=): None, 8, 16 or 'auto', got {table_lane_codes!r}")
     self.lowp_sharded = bool(lowp_sharded)
     self.output_dtype = output_dtype
     if output_dtype is not None:
@@ -698,7 +704,7 @@ class DenseFeatures(_TableLayer):
       self._lookup = Quant8GroupLookup(pick(self._rep, self.weights), [self.columns[c].dimension for c in self._rep],
                                        [self.columns[c].num_buckets for c in self._rep],
                                        [self.columns[c].combiner for c in self._rep],
-                                       out_dtype=output_dtype or torch.float32)
+                                       out_dtype=output_dtype or torch.float32, lane_codes=table_lane_codes)
       self._grad = Quant8LookupGrad(
         self._lookup, pick(self._rep, self.accums) if self.accums is not None else None,
         rounding=table_rounding, seed=table_seed, **two_slot_kw(self._rep))

@@ -945,12 +945,32 @@ int hbk_lowp_lookup_fwd_runs(int32_t n_cols, const hbk_lowp_lookup_runs_column_t
  *   alignment, the scale word read by the row's lanes from the same line, ONE 16-byte (fp32) or 8-byte (16-bit)
  *   store per lane -- when dim % 4 == 0 and `out` and its stride are 16-byte (fp32) / 8-byte (16-bit) aligned:
  *   dim <= 256.  Otherwise one code per lane, dim <= 64, with element-sized stores that touch no neighbouring byte.
- *   chunk_elems: 0 (the default) or 4; wider lanes are not built, and no bit could depend on the width.
+ *   chunk_elems: 0 (the default) or 4; lanes of 8 or 16 codes are hbk_quant8_lookup_fwd_wide below, and no bit depends
+ *   on the width.
  *   One launch per 64 columns, kind (one id per segment / ragged), lane width and output size; no LDS, no atomics,
  *   no workspace, no host read: the call can be captured.  Refused before the first launch (HBK_INVALID_ARGUMENT,
  *   the column named): what hbk_lowp_lookup_fwd refuses, with: dim beyond the bounds above; pitch not a multiple of
  *   4 or < dim4 + 4; a table not 4-byte aligned; an unknown out_dtype; `out` not aligned to its element;
  *   chunk_elems not 0 or 4.  n_cols == 0 answers OK.
+ *
+ * FORWARD, WIDE LANES  hbk_quant8_lookup_fwd_wide(n_cols, cols, lane_codes, stream): hbk_quant8_lookup_fwd with a row
+ *   owned by pow2(dim / L) adjacent lanes of L = lane_codes = 8 or 16 consecutive codes (one width per call).  The
+ *   semantics are exactly those above -- the same id map and decode, in-order fp32 sums from +0, the weighted forms,
+ *   the zero-divisor and invalid-row rules, 16-bit outputs rounded once to nearest even -- and no bit depends on L.
+ *   A column takes the width when dim % L == 0, dim <= 256 and `out` and its stride in bytes are multiples of 16.
+ *   Its codes are read as L / 4 loads of 4 bytes at consecutive words, which needs nothing beyond the layout (the
+ *   default pitch, a view that starts at any row), or as ONE L-byte load when the table's base and pitch are
+ *   multiples of L (the host chooses per column); the scale word is one 4-byte load per row and lane; a lane's sums
+ *   leave as L / 4 (fp32) or L / 8 (16-bit) non-temporal 16-byte stores.  A ragged lane group prefetches
+ *   max(lanes of the row, 64 / L) ids per chunk whatever the row's lane count.  A column that cannot take the width
+ *   is run, in the same call and behind the wide launches, by hbk_quant8_lookup_fwd at 4 codes or 1 as it would
+ *   choose.  Output memory is never read; no LDS, no atomics, no workspace, no host read: the call can be captured.
+ *   Refused before the first launch (HBK_INVALID_ARGUMENT, the column named): everything hbk_quant8_lookup_fwd
+ *   refuses; lane_codes not 8 or 16; chunk_elems != 0.  n_cols == 0 answers OK.
+ * hbk_quant8_lookup_lane_codes(col, lane_codes): host only, no launch: the codes per lane `col` gets from
+ *   hbk_quant8_lookup_fwd_wide(.., lane_codes = 8 | 16, ..) -- 16, 8, 4 or 1 -- or, with lane_codes 0 or 4, from
+ *   hbk_quant8_lookup_fwd (4 or 1); reads dim, out, out_stride and out_dtype.  0: col is NULL or lane_codes is none of
+ *   these.
  *
  * STEP  hbk_quant8_apply_slices_n: the contract of hbk_lowp_apply_slices_n (distinct rows; an entry outside
  *   [0, rows), -1 included, touches nothing; n_unique read on the device and clamped to [0, capacity]; the five rules
@@ -1002,6 +1022,9 @@ typedef struct {
   int32_t chunk_elems;       /* 0 = the default, or 4: codes per lane where the column allows it */
 } hbk_quant8_lookup_column_t;
 int hbk_quant8_lookup_fwd(int32_t n_cols, const hbk_quant8_lookup_column_t* cols, hbk_stream_t stream);
+int hbk_quant8_lookup_fwd_wide(int32_t n_cols, const hbk_quant8_lookup_column_t* cols, int32_t lane_codes,
+                               hbk_stream_t stream);
+int32_t hbk_quant8_lookup_lane_codes(const hbk_quant8_lookup_column_t* col, int32_t lane_codes);
 
 typedef struct {
   void* table;                 /* device uint8 [rows, pitch] */

@@ -7,10 +7,13 @@ Forward, 26 columns x 1M rows, batch 65536, into fp32 and into bf16 outputs (`_o
   d64     dim 64, one id per sample
   d128    dim 128, one id per sample
   ragged  dim 16, Poisson(8) ids per sample clipped to [0, 32], mean
+  ragged64  the same at dim 64
 
   fp32    hb.embedding.GroupLookup / Out16GroupLookup over fp32 tables
   bf16    LowpGroupLookup / Out16GroupLookup over bf16 tables (their default lane widths)
-  int8    Quant8GroupLookup (4 codes per lane: the one width built)
+  int8    Quant8GroupLookup, 4 codes per lane (hbk_quant8_lookup_fwd: the baseline of the wide lanes)
+  int8_L8 / int8_L16      lane_codes 8 / 16 over the same tables (default pitch dim + 4: L / 4 loads of 4 bytes)
+  int8p / int8p_L8 / int8p_L16   4, 8 and 16 codes per lane over tables whose pitch is rounded up to 16 (one load)
 
 Step, on c2's shape and the same ids and gradients, for SGD, Adagrad and row-wise Adagrad: the emit-form reduce
 and the split apply, `bf16_rn` / `bf16_sr` (LowpLookupGrad) against `int8_rn` / `int8_sr` (Quant8LookupGrad).
@@ -20,7 +23,7 @@ max.  Beside every forward line: bytes per looked-up row by the README's model (
 beside every step line: bytes per row of table plus optimizer state.  Appends its lines to `--out` (default
 profiles/quant8_tables.txt) and prints one JSON line.
 
-  python tools/bench_quant8_tables.py [--steps 20 --warmup 5 --rounds 7 --cases c2,d64,d128,ragged,step]
+  python tools/bench_quant8_tables.py [--steps 20 --warmup 5 --rounds 7 --cases c2,d64,d128,ragged,ragged64,step]
 """
 import argparse
 import json
@@ -40,7 +43,7 @@ def main():
   p.add_argument('--steps', type=int, default=20)
   p.add_argument('--warmup', type=int, default=5)
   p.add_argument('--rounds', type=int, default=7)
-  p.add_argument('--cases', default='c2,d64,d128,ragged,step')
+  p.add_argument('--cases', default='c2,d64,d128,ragged,ragged64,step')
   p.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'quant8_tables.txt'))
   args = p.parse_args()
   import hybridbackend_amd as hb   # pylint: disable=import-outside-toplevel
@@ -87,7 +90,7 @@ def main():
       med = float(np.median(t[k]))
       out[f'{case}_{k}'] = {'us': round(med, 2), 'min_max_us': [round(min(t[k]), 2), round(max(t[k]), 2)],
                             'row_bytes': row_bytes[k]}
-      lines.append(f'{case:14s} {k:9s} {med:9.2f} us  (min {min(t[k]):.2f}, max {max(t[k]):.2f})   '
+      lines.append(f'{case:14s} {k:10s} {med:9.2f} us  (min {min(t[k]):.2f}, max {max(t[k]):.2f})   '
                    f'{row_bytes[k]:4d} {what}')
     return out
 
@@ -104,6 +107,7 @@ def main():
     t32 = [torch.empty(rows, dim, device=dev).uniform_(-1e-3, 1e-3, generator=gen) for _ in range(cols)]
     t16 = [t.to(torch.bfloat16) for t in t32]
     t8 = E.quantize_rows8(t32)
+    t8p = E.quantize_rows8(t32, pitch=E.Quant8Rows.pitch_for(dim, 16))
     ids, splits = ids_of(is_ragged)
     combiner = 'mean' if is_ragged else 'sum'
     buckets, dims = [rows] * cols, [dim] * cols
@@ -116,13 +120,21 @@ def main():
       else:
         looks = {'fp32': E.Out16GroupLookup(t32, buckets, combiner, out_dtype=odt),
                  'bf16': E.Out16GroupLookup(t16, buckets, combiner, out_dtype=odt)}
-      looks['int8'] = E.Quant8GroupLookup(t8, dims, buckets, combiner, out_dtype=odt)
+      for k, t in (('int8', t8), ('int8p', t8p)):
+        for lane_codes in (None, 8, 16):
+          if lane_codes is None or dim % lane_codes == 0:
+            looks[k + (f'_L{lane_codes}' if lane_codes else '')] = E.Quant8GroupLookup(
+              t, dims, buckets, combiner, out_dtype=odt, lane_codes=lane_codes)
       forms = {}
       for k, look in looks.items():
         look(ids, splits, outs)
+        if k.startswith('int8'):   # the form runs the path it names
+          assert look.lane_codes_used == [int(k.split('_L')[1]) if '_L' in k else 4] * cols, (k, look.lane_codes_used)
         forms[k] = graphed(look.launch)
-      table_bytes = {'fp32': 4 * dim, 'bf16': 2 * dim, 'int8': E.Quant8Rows.pitch_for(dim)}
-      out.update(take_turns(f'{name}_{tag}', forms, {k: 8 + table_bytes[k] + obytes * dim for k in forms},
+      table_bytes = {'fp32': 4 * dim, 'bf16': 2 * dim, 'int8': E.Quant8Rows.pitch_for(dim),
+                     'int8p': E.Quant8Rows.pitch_for(dim, 16)}
+      out.update(take_turns(f'{name}_{tag}', forms,
+                            {k: 8 + table_bytes[k.split('_')[0]] + obytes * dim for k in forms},
                             'B per looked-up row (id + table row + output row)'))
     return out
 
@@ -159,7 +171,7 @@ def main():
     return out
 
   result = {}
-  fwd = {'c2': (16, False), 'd64': (64, False), 'd128': (128, False), 'ragged': (16, True)}
+  fwd = {'c2': (16, False), 'd64': (64, False), 'd128': (128, False), 'ragged': (16, True), 'ragged64': (64, True)}
   for name in args.cases.split(','):
     result.update(step_case('step', 16) if name == 'step' else forward_case(name, *fwd[name]))
     torch.cuda.empty_cache()
