@@ -437,6 +437,7 @@ def _declare(l):
     'hbk_hash_insert_admit_n': (C.c_int, [i32, vp, vp, i32, vp]),
     'hbk_hash_insert_expiring_admit_n': (C.c_int, [i32, vp, vp, vp, i32, vp]),
     'hbk_hash_insert_lowp_n': (C.c_int, [i32, vp, vp, vp, vp, i32, vp]),
+    'hbk_hash_insert_quant8_n': (C.c_int, [i32, vp, vp, vp, vp, i32, vp]),
     'hbk_hash_rehash_n': (C.c_int, [i32, vp, vp]),
     'hbk_hash_translate_runs_n': (C.c_int, [i32, vp, vp, vp, vp, vp, i32, vp]),
     'hbk_hash_translate_sequence_n': (C.c_int, [i32, vp, vp, vp, vp, i32, vp]),

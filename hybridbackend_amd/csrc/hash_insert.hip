@@ -88,7 +88,33 @@
 // the kernels they were, instruction for instruction.  A launch that writes no row -- a find, the counting phase of a
 // filtered table -- is the fp32 kernel as it is.  hbk_hash_translate_runs_lowp_n and hbk_hash_translate_sequence_lowp_n
 // are the same step for the other two sources of work: LOWP = true over RunsArgs / SeqArgs, inserting launches only.
+//
+// 8-bit tables (hbk_hash_insert_quant8_n): the same kernels with Q8 = true, a second flag beside LOWP, for the
+// launches that insert over the columns of the entry itself (no runs, no sequences).  HashCol.table is the uint8
+// [capacity, pitch] table and HashCol.pitch its pitch in BYTES; the element code kElemQuant8 rides above kElemShift as
+// the 16-bit codes do, so only the Q8 instantiations mask group_log2 and the others are the kernels they were.  The new
+// row is QUANTISE of include/hbk.h over v_j = init_value(key, seed, j, init_scale), in two phases:
+//   amax   (quant8_row_amax) is HOISTED out of the `won` branch: EVERY lane of the wave takes the butterfly
+//          (__shfl_xor over 1 .. gsize/2, gsize wave-uniform), as in sketch_estimate; the lanes of a group that did
+//          not win compute nothing and pass +0, the neutral value of a maximum of magnitudes.  The call sits where
+//          init_row sits, behind the walk's `if (!__any(active)) break`, where the wave has converged again -- in
+//          both kernels.  gsize == 1 runs no shuffle.
+//   codes  (init_row_quant8), the winning group alone: the row as pitch / 4 whole 4-byte words, lane `sub` taking
+//          words sub, sub + gsize, ..: word w < dim4 / 4 holds the codes 4w .. 4w+3 (bytes past dim stay 0), word
+//          dim4 / 4 the scale, every later word 0, so a reused slot keeps nothing of its previous owner.  One loop,
+//          every word stored once, nothing outside [row, row + pitch), no partial dword.  With gsize > pitch / 4 the
+//          lanes past the last word idle.
+// v_j is RECOMPUTED for the code pass (a murmur mix and a multiply) and not kept: at dim 256 and slab_size 8 a lane owns
+// 32 elements, and an array of them would be 32 registers or scratch; the instantiations use 0 bytes of scratch
+// (profiles/hash_quant8.txt has the register counts).  init_value, the quotient and rintf are single correctly rounded
+// fp32 operations (no contraction in this build), so the row equals hbk_quant8_rows_n on the fp32 table's row bit for
+// bit.  Order of writes: as for fp32 and 16-bit rows, the key is visible (the CAS) before the row is written, and that
+// is sound because no translate kernel ever reads a row: rows are read by launches stream-ordered behind this one,
+// and the kernel boundary publishes the codes, the scale word and the padding words together.  A find and the counting
+// phase of a filtered table write no row and are the fp32 launches as they are.
 #include <math.h>
+
+#include <vector>
 
 #include "hash_common.h"
 #include "lowp_elems.h"
@@ -245,9 +271,10 @@ __host__ __device__ inline float init_value(int64_t key, uint64_t seed, int j, f
 // The 16-bit kernels (LOWP; hbk_hash_insert_lowp_n) carry the column's element code in the spare bits of
 // HashCol.group_log2; the fp32 kernels read the field whole, as they always did.
 constexpr int kElemShift = 8;
-template <bool LOWP>
+constexpr int kElemQuant8 = 3;   // the 8-bit kernels' (Q8) code, beside HBK_LOWP_BF16 (1) and HBK_LOWP_FP16 (2)
+template <bool LOWP, bool Q8 = false>
 __device__ inline int lane_group_log2(const HashCol& c) {
-  if constexpr (LOWP) return c.group_log2 & ((1 << kElemShift) - 1);
+  if constexpr (LOWP || Q8) return c.group_log2 & ((1 << kElemShift) - 1);
   return c.group_log2;
 }
 
@@ -274,6 +301,54 @@ __device__ inline void init_row(const HashCol& c, long long key, int64_t slot, i
     for (int j = sub; j < c.dim; j += gsize) {
       row[j] = c.init_scale == 0.0f ? 0.0f : init_value(key, c.seed, j, c.init_scale);
     }
+  }
+}
+
+// ---- 8-bit rows (Q8; the header comment) ----
+constexpr float kQuantTiny = 0x1p-100f;   // a row whose amax is below this is a zero row (include/hbk.h, QUANTISE)
+
+// max_j |v_j| of the new row of `key`, for EVERY lane of the wave: a lane of a group that writes no row (mine ==
+// false) computes nothing and brings +0 to the butterfly.  A lane's elements are those of its words in init_row_quant8.
+__device__ inline float quant8_row_amax(const HashCol& c, long long key, bool mine, int sub, int gsize) {
+  float m = 0.0f;
+  if (mine && c.init_scale != 0.0f) {
+    for (int j0 = 4 * sub; j0 < c.dim; j0 += 4 * gsize) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (j0 + k < c.dim) m = fmaxf(m, fabsf(init_value(key, c.seed, j0 + k, c.init_scale)));
+      }
+    }
+  }
+  for (int off = 1; off < gsize; off <<= 1) m = fmaxf(m, __shfl_xor(m, off, kWave));
+  return m;
+}
+
+// The new row of `key` at `slot`, all pitch / 4 words of it, by the lane group that won the slot: codes, scale, zeros.
+__device__ inline void init_row_quant8(const HashCol& c, long long key, int64_t slot, float amax, int sub, int gsize) {
+  uint32_t* const row = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(c.table) + slot * c.pitch);
+  const int code_words = (c.dim + 3) >> 2;
+  const int row_words = (int)(c.pitch >> 2);
+  const bool zero = amax < kQuantTiny;
+  const float scale = zero ? 0.0f : amax / 127.0f;
+  for (int w = sub; w < row_words; w += gsize) {
+    uint32_t word = 0u;
+    if (w < code_words) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int j = 4 * w + k;
+        if (j >= c.dim) break;   // (the bytes between dim and dim4 stay 0)
+        uint32_t code = 128u;
+        if (!zero) {
+          const float t = init_value(key, c.seed, j, c.init_scale) / scale;
+          const float q = fminf(fmaxf(rintf(t), -127.0f), 127.0f);
+          code = (uint32_t)((int)q + 128);
+        }
+        word |= code << (8 * k);
+      }
+    } else if (w == code_words) {
+      word = __float_as_uint(scale);
+    }
+    row[w] = word;
   }
 }
 
@@ -336,10 +411,11 @@ __device__ inline long long read_slot(const long long* p) {
 // an admitting call -- 1 = the find walk, the sketch adds of its misses, kPending into their slots; 2 = the
 // find-or-insert of the pending occurrences whose estimate reaches min_freq, -1 for the others.  Everything the
 // phases add is behind `if constexpr`: the PHASE 0 instantiations are the kernels they were.
-template <bool INSERT, int PHASE = 0, class Args = HashArgs, bool LOWP = false>
+template <bool INSERT, int PHASE = 0, class Args = HashArgs, bool LOWP = false, bool Q8 = false>
 __global__ __launch_bounds__(kBlock) void hash_insert_kernel(const Args args) {
   static_assert(PHASE == 0 || INSERT == (PHASE == 2), "phase 1 finds, phase 2 inserts");
   static_assert(INSERT || !LOWP, "only an inserting launch writes rows: a find of a 16-bit table is the fp32 find");
+  static_assert((INSERT || !Q8) && !(LOWP && Q8), "an 8-bit row is written by an inserting launch, and is no 16-bit row");
   constexpr bool kSeq = IsSeq<Args>::value;
   const HashArgs& a = hash_args(args);
   const int b = (int)blockIdx.x;
@@ -348,7 +424,7 @@ __global__ __launch_bounds__(kBlock) void hash_insert_kernel(const Args args) {
   const HashCol& c = a.col[ci];
   const int lane = lane_id();
   const int wave = (int)(threadIdx.x >> 6);
-  const int group_log2 = lane_group_log2<LOWP>(c);
+  const int group_log2 = lane_group_log2<LOWP, Q8>(c);
   const int gsize = 1 << group_log2;
   const int sub = lane & (gsize - 1);
   const int grp = lane >> group_log2;
@@ -468,7 +544,14 @@ __global__ __launch_bounds__(kBlock) void hash_insert_kernel(const Args args) {
       rk = 0;
       if (active && in_slab) rk = read_slot<INSERT>(cache + slab[u] * slab_size + sub);
     }
-    if (INSERT && won && c.table != nullptr) init_row<LOWP>(c, key[u], result, sub, gsize);
+    if constexpr (Q8) {
+      // (every lane of the wave takes the butterfly of the amax; the wave converged at the walk's break)
+      const bool mine = won && c.table != nullptr;
+      const float amax = quant8_row_amax(c, key[u], mine, sub, gsize);
+      if (mine) init_row_quant8(c, key[u], result, amax, sub, gsize);
+    } else {
+      if (INSERT && won && c.table != nullptr) init_row<LOWP>(c, key[u], result, sub, gsize);
+    }
     if constexpr (PHASE == 1) {
       // not found and not the sentinel (which stays -1, counted as failed): counted, decided in phase 2
       if (result < 0 && key[u] != kEmptyKey) {
@@ -537,10 +620,11 @@ __device__ inline const ExpiringArgs& expiring_args(const ExpiringAdmitArgs& x) 
 // The sibling of hash_insert_kernel for expiring tables: same lane mapping and first reads, the placement
 // rule with tombstones of the header comment.  PHASE as in hash_insert_kernel (Args = ExpiringAdmitArgs for 1 and
 // 2); the metadata of an occurrence is written by the phase that resolved it to a slot.
-template <bool INSERT, int PHASE = 0, class Args = ExpiringArgs, bool LOWP = false>
+template <bool INSERT, int PHASE = 0, class Args = ExpiringArgs, bool LOWP = false, bool Q8 = false>
 __global__ __launch_bounds__(kBlock) void hash_insert_expiring_kernel(const Args args) {
   static_assert(PHASE == 0 || INSERT == (PHASE == 2), "phase 1 finds, phase 2 inserts");
   static_assert(INSERT || !LOWP, "only an inserting launch writes rows: a find of a 16-bit table is the fp32 find");
+  static_assert((INSERT || !Q8) && !(LOWP && Q8), "an 8-bit row is written by an inserting launch, and is no 16-bit row");
   constexpr bool kMetadata = INSERT || PHASE == 1;
   constexpr bool kSeq = IsSeq<Args>::value;
   const ExpiringArgs& x = expiring_args(args);
@@ -552,7 +636,7 @@ __global__ __launch_bounds__(kBlock) void hash_insert_expiring_kernel(const Args
   const ExpiryCol& e = x.e[ci];
   const int lane = lane_id();
   const int wave = (int)(threadIdx.x >> 6);
-  const int group_log2 = lane_group_log2<LOWP>(c);
+  const int group_log2 = lane_group_log2<LOWP, Q8>(c);
   const int gsize = 1 << group_log2;
   const int sub = lane & (gsize - 1);
   const int grp = lane >> group_log2;
@@ -688,7 +772,14 @@ __global__ __launch_bounds__(kBlock) void hash_insert_expiring_kernel(const Args
       rk = 0;
       if (active && in_slab) rk = read_slot<INSERT>(cache + slab * slab_size + sub);
     }
-    if (INSERT && won && c.table != nullptr) init_row<LOWP>(c, key[u], result, sub, gsize);
+    if constexpr (Q8) {
+      // (every lane of the wave takes the butterfly of the amax; the wave converged at the walk's break)
+      const bool mine = won && c.table != nullptr;
+      const float amax = quant8_row_amax(c, key[u], mine, sub, gsize);
+      if (mine) init_row_quant8(c, key[u], result, amax, sub, gsize);
+    } else {
+      if (INSERT && won && c.table != nullptr) init_row<LOWP>(c, key[u], result, sub, gsize);
+    }
     if constexpr (PHASE == 1) {
       // not found and not a sentinel (which stays -1, counted as failed): counted, decided in phase 2
       if (result < 0 && key[u] != kEmptyKey) {
@@ -1333,6 +1424,91 @@ extern "C" int hbk_hash_insert_lowp_n(int32_t n_cols, const hbk_hash_column_t* c
   }
   return launch_columns<HashArgs>(who, n_cols, cols, nullptr, nullptr, table_dtypes, insert,
                                   hash_insert_kernel<true, 0, HashArgs, true>, stream);
+}
+
+// ---- 8-bit tables ---------------------------------------------------------------------------------------
+namespace hbk {
+namespace {
+
+// what the 8-bit entry adds to check_column for one column: the layout of include/hbk.h ("8-bit tables") within the
+// bounds of the forward and the step; *pitch: the pitch in bytes (0 = the default)
+int check_quant8_column(const char* who, int32_t c, const hbk_hash_column_t& h, int32_t pitch_in, int32_t* pitch) {
+  *pitch = pitch_in;
+  if (h.table == nullptr) return HBK_OK;   // (no row is written: the shape of a row is not looked at)
+  // (dim >= 1: check_column)
+  HBK_REQUIRE(h.dim <= 256 && (h.dim <= 64 || h.dim % 4 == 0),
+              "%s: column %d: dim %d is beyond what the 8-bit forward and step take (at most 256 when a multiple of 4, "
+              "64 otherwise)", who, c, h.dim);
+  const int32_t dim4 = (h.dim + 3) & ~3;
+  if (pitch_in == 0) *pitch = dim4 + 4;
+  HBK_REQUIRE(*pitch % 4 == 0 && *pitch >= dim4 + 4,
+              "%s: column %d: pitch %d must be a multiple of 4 and >= round_up(dim, 4) + 4 = %d", who, c, *pitch,
+              dim4 + 4);
+  HBK_REQUIRE(((uintptr_t)h.table & 3) == 0, "%s: column %d: table must be 4-byte aligned", who, c);
+  return HBK_OK;
+}
+
+}  // namespace
+}  // namespace hbk
+
+extern "C" int hbk_hash_insert_quant8_n(int32_t n_cols, const hbk_hash_column_t* cols, const hbk_hash_expiry_t* exp,
+                                        const hbk_hash_admission_t* adm, const int32_t* pitches, int32_t insert,
+                                        hbk_stream_t stream_) {
+  using namespace hbk;
+  const char* who = "hash_insert_quant8_n";
+  HBK_REQUIRE(n_cols >= 0, "%s: n_cols must be >= 0, got %d", who, n_cols);
+  if (n_cols == 0) return HBK_OK;
+  HBK_REQUIRE(cols != nullptr, "%s: cols is NULL", who);
+  HBK_REQUIRE(pitches != nullptr, "%s: pitches is NULL", who);
+  // the columns as the kernels see them: table_pitch = the row pitch in bytes (the caller's table_pitch is not read)
+  std::vector<hbk_hash_column_t> local(cols, cols + n_cols);
+  for (int32_t c = 0; c < n_cols; ++c) {
+    hbk_hash_column_t& h = local[c];
+    h.table_pitch = 0;
+    if (int rc = check_column(who, c, h)) return rc;
+    if (exp != nullptr) {
+      HBK_REQUIRE(h.n_keys < (1ll << 30), "%s: column %d: n_keys must be below 2^30 (freq must not wrap), got %lld",
+                  who, c, (long long)h.n_keys);
+      HBK_REQUIRE(h.n_keys == 0 || (exp[c].last_seen != nullptr && exp[c].freq != nullptr && exp[c].step != nullptr),
+                  "%s: column %d: NULL expiry buffer (last_seen, freq and step are needed with n_keys > 0)", who, c);
+    }
+    if (adm != nullptr) {
+      if (int rc = check_admission(who, c, h, adm[c])) return rc;
+    }
+    if (int rc = check_quant8_column(who, c, h, pitches[c], &h.table_pitch)) return rc;
+  }
+  if (insert == 0) {
+    // a find writes no row and touches no sketch: the find of the fp32 entry, as it is
+    return exp != nullptr ? hbk_hash_insert_expiring_n(n_cols, cols, exp, 0, stream_)
+                          : hbk_hash_insert_n(n_cols, cols, 0, stream_);
+  }
+  hipStream_t stream = as_stream(stream_);
+  const std::vector<int32_t> elems((size_t)n_cols, kElemQuant8);
+  const hbk_hash_column_t* q = local.data();
+  if (adm != nullptr) {   // count (no row is written: the fp32 kernel), then admit
+    if (exp != nullptr) {
+      if (int rc = launch_columns<ExpiringAdmitArgs>(
+              who, n_cols, q, exp, adm, nullptr, insert, hash_insert_expiring_kernel<false, 1, ExpiringAdmitArgs>,
+              stream)) {
+        return rc;
+      }
+      return launch_columns<ExpiringAdmitArgs>(who, n_cols, q, exp, adm, elems.data(), insert,
+                                               hash_insert_expiring_kernel<true, 2, ExpiringAdmitArgs, false, true>,
+                                               stream);
+    }
+    if (int rc = launch_columns<AdmitArgs>(who, n_cols, q, nullptr, adm, nullptr, insert,
+                                           hash_insert_kernel<false, 1, AdmitArgs>, stream)) {
+      return rc;
+    }
+    return launch_columns<AdmitArgs>(who, n_cols, q, nullptr, adm, elems.data(), insert,
+                                     hash_insert_kernel<true, 2, AdmitArgs, false, true>, stream);
+  }
+  if (exp != nullptr) {
+    return launch_columns<ExpiringArgs>(who, n_cols, q, exp, nullptr, elems.data(), insert,
+                                        hash_insert_expiring_kernel<true, 0, ExpiringArgs, false, true>, stream);
+  }
+  return launch_columns<HashArgs>(who, n_cols, q, nullptr, nullptr, elems.data(), insert,
+                                  hash_insert_kernel<true, 0, HashArgs, false, true>, stream);
 }
 
 // ---- keys that arrive as ragged sequences ---------------------------------------------------------------

@@ -62,6 +62,10 @@ number of ranks.  ``items()`` / ``load()`` / ``load_owned()`` / ``variables()`` 
 launch rounds a new row to the table's 16 bits, every move carries rows as 4-byte words whatever they hold, and
 :class:`HashGroupLookup` puts a ``LowpGroupLookup`` behind the translate; ``LowpLookupGrad`` is the step.
 
+8-bit rows (``HashTable(..., dtype='int8')``; ``hbk_hash_insert_quant8_n``): the inserting launch quantises a new row
+to int8 codes and a row scale, the moves carry the uint8 rows as ``pitch / 4`` words, and :class:`HashGroupLookup` puts
+a ``Quant8GroupLookup`` behind the translate; ``Quant8LookupGrad`` is the step.  No sequence, sharded or layer form.
+
 Not provided: 16-bit tables behind sequence lookups, sharded tables and the feature columns; growth from inside a
 translate launch (a full table answers -1 until ``maybe_grow`` ran), a
 compaction that keeps the tensors' addresses, the TF shim op.  (As feature columns: ``feature_column.
@@ -79,6 +83,38 @@ from hybridbackend_amd.embedding.lookup import GroupLookup
 
 TOMBSTONE_KEY = EMPTY_KEY + 1   # expiring tables only: a slot the eviction sweep took back
 LOWP_DTYPES = {torch.bfloat16: _lib.LOWP_BF16, torch.float16: _lib.LOWP_FP16}   # HashTable(dtype=): 16-bit rows
+QUANT8 = 'int8'   # HashTable(dtype=): 8-bit rows, torch.uint8 [capacity, pitch] (include/hbk.h, "8-bit tables")
+
+
+def _is_quant8(dtype):
+  return isinstance(dtype, str) and dtype == QUANT8
+
+
+def _quant8_pitch(dim, pitch, what):
+  """The checked row pitch in bytes of an 8-bit row of ``dim`` codes (None: the default), within the bounds of the
+  8-bit forward and step."""
+  from hybridbackend_amd.embedding.quant8 import MAX_DIM, Quant8Rows   # pylint: disable=import-outside-toplevel
+  if dim > MAX_DIM or (dim > 64 and dim % 4):
+    raise _bad(f"{what}: dim {dim} is beyond what the 8-bit forward and step take (at most {MAX_DIM} when a multiple "
+               'of 4, 64 otherwise)')
+  least = Quant8Rows.pitch_for(dim)
+  pitch = least if pitch is None else int(pitch)
+  if pitch % 4 or pitch < least:
+    raise _bad(f'{what}: pitch {pitch} must be a multiple of 4 and >= {least} for dim {dim}')
+  return pitch
+
+
+def _row_layout(dtype, dim, pitch, what):
+  """``(tensor dtype, columns, pitch)`` of the row tensor of a table, an export or a store of ``dtype``: ``[n, dim]`` of
+  the dtype, or uint8 ``[n, pitch]`` for ``'int8'``.  An unknown dtype, and a pitch without ``'int8'``, are refused."""
+  if _is_quant8(dtype):
+    pitch = _quant8_pitch(dim, pitch, what)
+    return torch.uint8, pitch, pitch
+  if dtype != torch.float32 and dtype not in LOWP_DTYPES:
+    raise _bad(f"{what}: dtype must be torch.float32, torch.bfloat16, torch.float16 or 'int8', got {dtype!r}")
+  if pitch is not None:
+    raise _bad(f"{what}: pitch is the row pitch of an 8-bit table (dtype='int8'), got pitch={pitch!r} with {dtype}")
+  return dtype, dim, None
 
 
 def _bad(msg):
@@ -141,6 +177,17 @@ class HashTable:
       bit for bit and refuses another.  The metadata and the companions (optimizer slots) stay what they were,
       fp32.  Look up through :class:`HashGroupLookup`, step with ``LowpLookupGrad``; sequence lookups, sharded
       tables and the feature-column layers take fp32 tables only.
+      ``'int8'``: 8-bit rows (include/hbk.h, "8-bit tables"): ``table`` is ``torch.uint8`` ``[capacity, pitch]``,
+      ``dim`` stays the logical width (at most 256 when a multiple of 4, else at most 64) and ``self.pitch`` is the
+      bytes between rows.  A new row is the fp32 start value quantised to nearest by the inserting launch
+      (``hbk_hash_insert_quant8_n``): bit for bit ``quantize_rows8`` of the row an fp32 table would have started
+      with.  Every row-carrying call carries the uint8 rows at the table's own pitch, bit for bit, and refuses rows of
+      another dtype or pitch.  A slot that holds no key has UNSPECIFIED bytes and is never decoded by a lookup:
+      ``torch.zeros`` is not a zero row (code 0 does not exist), and neither a fresh table nor a rehash makes it one.
+      Look up through :class:`HashGroupLookup`, step with ``Quant8LookupGrad``; sequence, sharded and layer forms
+      refuse such a table by name.
+    pitch: with ``dtype='int8'``, the row pitch in bytes: None -- ``Quant8Rows.pitch_for(dim)`` -- or a multiple of 4
+      that is at least that (``Quant8Rows.pitch_for(dim, align=16)`` lets wide lanes load 16 codes at once).
 
   Attributes of a filtered table: ``sketch`` int32 ``[depth, width]``, ``filter_counts`` int32 ``[1]`` = id
   occurrences the filter answered -1.  The sketch is never decremented, so an id evicted from an expiring table
@@ -157,7 +204,7 @@ class HashTable:
   """
 
   def __init__(self, capacity, dim, device, slab_size=8, init_scale=1e-3, seed=0, expiring=False, min_freq=0,
-               sketch_depth=4, sketch_width=None, sketch_seed=0, dtype=torch.float32):
+               sketch_depth=4, sketch_width=None, sketch_seed=0, dtype=torch.float32, pitch=None):
     slab_size, capacity, dim = int(slab_size), int(capacity), int(dim)
     _check_geometry(capacity, slab_size)
     if dim < 1:
@@ -165,8 +212,8 @@ class HashTable:
     init_scale = float(init_scale)
     if not math.isfinite(init_scale) or init_scale < 0 or not math.isfinite(C.c_float(init_scale).value):
       raise _bad(f'init_scale must be finite and >= 0, got {init_scale!r}')
-    if dtype != torch.float32 and dtype not in LOWP_DTYPES:
-      raise _bad(f'dtype must be torch.float32, torch.bfloat16 or torch.float16, got {dtype!r}')
+    # what `table` is made of: [capacity, dim] of the dtype, or uint8 [capacity, pitch]
+    self.row_dtype, self.row_width, self.pitch = _row_layout(dtype, dim, pitch, 'HashTable')
     if dtype in LOWP_DTYPES and dim % 2:
       raise _bad(f'dim must be even on a {dtype} table (a 16-bit row is written and moved as 4-byte words), got {dim}')
     if dtype == torch.float16 and init_scale > 65504.0:
@@ -181,7 +228,7 @@ class HashTable:
     self.seed = int(seed)
     self.device = torch.device(device)
     self.keys = torch.full((self.capacity,), EMPTY_KEY, dtype=torch.int64, device=self.device)
-    self.table = torch.zeros((self.capacity, dim), dtype=dtype, device=self.device)
+    self.table = torch.zeros((self.capacity, self.row_width), dtype=self.row_dtype, device=self.device)
     self.counts = torch.zeros(2, dtype=torch.int32, device=self.device)
     self.expiring = bool(expiring)
     self._removals = None   # track_removals(): the keys that left, as device tensors
@@ -247,8 +294,8 @@ class HashTable:
   def _check_rows_dtype(self, rows):
     """The dtype check of :meth:`load` and :meth:`load_owned`, made before anything else is looked at: rows of
     another dtype are refused, never cast."""
-    if isinstance(rows, torch.Tensor) and rows.dtype != self.dtype:
-      raise _bad(f'load: rows must be {_dtype_name(self.dtype)}, the table\'s own dtype (nothing is cast: a round '
+    if isinstance(rows, torch.Tensor) and rows.dtype != self.row_dtype:
+      raise _bad(f'load: rows must be {_rows_name(self)}, the table\'s own dtype (nothing is cast: a round '
                  f'trip is bit-exact), got {rows.dtype}')
 
   def lookup_or_insert(self, ids):
@@ -307,8 +354,9 @@ class HashTable:
     the next sweep); ``items()`` does not carry the metadata of the table it came from."""
     self._check_rows_dtype(rows)
     check_ids([keys], [self])
-    if tuple(rows.shape) != (keys.numel(), self.dim) or rows.device != self.table.device:
-      raise _bad(f'rows must be {_dtype_name(self.dtype)} [{keys.numel()}, {self.dim}] on {self.table.device}')
+    if tuple(rows.shape) != (keys.numel(), self.row_width) or rows.device != self.table.device:
+      raise _bad(f'load: rows must be {_rows_name(self)} [{keys.numel()}, {self.row_width}] on {self.table.device} '
+                 f'(nothing is re-pitched), got {tuple(rows.shape)}')
     slots = _translate([self], [keys], True, None, init=False, plan=_Plan([self], admit=False))[0]
     ok = slots >= 0
     if not bool(ok.all().item()):
@@ -655,8 +703,8 @@ class HashTable:
     n = exp.keys.numel()
     if exp.keys.dtype != torch.int64 or exp.keys.dim() != 1:
       raise _bad('import_items: exp.keys must be an int64 vector')
-    if exp.rows.dtype != self.dtype or tuple(exp.rows.shape) != (n, self.dim):
-      raise _bad(f'import_items: exp.rows must be {_dtype_name(self.dtype)} [{n}, {self.dim}], the table\'s own '
+    if exp.rows.dtype != self.row_dtype or tuple(exp.rows.shape) != (n, self.row_width):
+      raise _bad(f'import_items: exp.rows must be {_rows_name(self)} [{n}, {self.row_width}], the table\'s own '
                  f'dtype (nothing is cast), got {exp.rows.dtype} {tuple(exp.rows.shape)}')
     for k, (x, y) in enumerate(zip(exp.slots, dst_slots)):
       if x.dtype != torch.float32 or x.dim() != 2 or tuple(x.shape) != (n, y.shape[1]):
@@ -741,6 +789,11 @@ def _dtype_name(dtype):
   return 'fp32' if dtype == torch.float32 else str(dtype)
 
 
+def _rows_name(t):
+  """What the rows of a table or a store are, for a refusal."""
+  return f'uint8 (int8 codes and scale at pitch {t.pitch})' if _is_quant8(t.dtype) else _dtype_name(t.dtype)
+
+
 def _words(x, elements):
   """``elements`` elements of ``x`` in 4-byte words: rows travel as words, bit for bit, whatever they hold (a 16-bit
   row of even dim is dim / 2 words; its pitch is even too)."""
@@ -816,13 +869,15 @@ class HashExport:
                d.get(base + 'removed'))
 
   @classmethod
-  def empty(cls, n, dim, expiring=False, slot_dims=(), device='cpu', n_removed=None, dtype=torch.float32):
+  def empty(cls, n, dim, expiring=False, slot_dims=(), device='cpu', n_removed=None, dtype=torch.float32, pitch=None):
     """An export of ``n`` zero keys: the tensors a ``Saver.restore`` of a saved export is read into.  ``n_removed``:
-    None, or the length of ``removed``.  ``dtype``: of ``rows``, the table's."""
+    None, or the length of ``removed``.  ``dtype``: of ``rows``, the table's; with ``'int8'`` the rows are uint8
+    ``[n, pitch]`` (``pitch``: the table's, None for the default of ``dim``)."""
     n = int(n)
+    row_dtype, width, _ = _row_layout(dtype, int(dim), pitch, 'HashExport.empty')
     meta = [torch.zeros(n, dtype=torch.int32, device=device) for _ in range(2)] if expiring else [None, None]
     return cls(torch.zeros(n, dtype=torch.int64, device=device),
-               torch.zeros((n, int(dim)), dtype=dtype, device=device),
+               torch.zeros((n, width), dtype=row_dtype, device=device),
                meta[0], meta[1], [torch.zeros((n, int(d)), device=device) for d in slot_dims],
                torch.zeros(n, dtype=torch.int64, device=device), 0,
                None if n_removed is None else torch.zeros(int(n_removed), dtype=torch.int64, device=device))
@@ -893,7 +948,7 @@ def hash_export(tables, sinces=None, slots=None):
     rows = max(cap, 1)   # (never an empty allocation: a move needs an address)
     out = {'keys': torch.empty(rows, dtype=torch.int64, device=dev),
            'src_slots': torch.empty(rows, dtype=torch.int64, device=dev),
-           'rows': torch.empty((rows, t.dim), dtype=t.dtype, device=dev)}
+           'rows': torch.empty((rows, t.row_width), dtype=t.row_dtype, device=dev)}
     moves = [(t.table, out['rows'])]
     if t.expiring:
       for name in ('last_seen', 'freq'):
@@ -995,7 +1050,7 @@ def hash_rehash(tables, capacities=None, slab_sizes=None, slots=None):
     slab_count, slab_size = geometry[c]
     capacity, dev = slab_count * slab_size, t.keys.device
     new = {'keys': torch.full((capacity,), EMPTY_KEY, dtype=torch.int64, device=dev),
-           'table': torch.zeros((capacity, t.dim), dtype=t.dtype, device=dev)}
+           'table': torch.zeros((capacity, t.row_width), dtype=t.row_dtype, device=dev)}
     moves = [(t.table, new['table'])]
     if t.expiring:
       for name in ('last_seen', 'freq'):
@@ -1232,7 +1287,7 @@ def hash_spill(tables, max_sizes, keep_freq=0, slots=None, order='lru'):
     rows = max(cap, 1)   # (never an empty allocation: a move needs an address)
     out = {'keys': torch.empty(rows, dtype=torch.int64, device=dev),
            'src_slots': torch.empty(rows, dtype=torch.int64, device=dev),
-           'rows': torch.empty((rows, t.dim), dtype=t.dtype, device=dev),
+           'rows': torch.empty((rows, t.row_width), dtype=t.row_dtype, device=dev),
            'last_seen': torch.empty(rows, dtype=torch.int32, device=dev),
            'freq': torch.empty(rows, dtype=torch.int32, device=dev),
            'slots': [torch.empty((rows, x.shape[1]), dtype=torch.float32, device=dev) for x, _ in checked[c]]}
@@ -1340,6 +1395,9 @@ def _check_store(store, table, slots):
   if store.dtype != table.dtype:
     raise _bad(f'the store holds {_dtype_name(store.dtype)} rows, the table {_dtype_name(table.dtype)} rows: build '
                'HashSpillStore(..., dtype=table.dtype) (nothing is cast)')
+  if store.pitch != table.pitch:
+    raise _bad(f'the store holds 8-bit rows at pitch {store.pitch}, the table at pitch {table.pitch}: build '
+               'HashSpillStore(..., dtype=\'int8\', pitch=table.pitch) (nothing is re-pitched)')
 
 
 class HashSpillStore:
@@ -1353,25 +1411,26 @@ class HashSpillStore:
     pin_memory: keep the arrays in page-locked memory when a GPU is present (copies from and to the device run
       at the link's speed).
     dtype: of the table's rows (``HashTable(dtype=)``): the store keeps them as they are, bit for bit, and takes
-      no other.
+      no other.  ``'int8'``: the uint8 ``[n, pitch]`` rows of an 8-bit table.
+    pitch: with ``dtype='int8'``, the table's row pitch in bytes (None: the default of ``dim``); rows of another pitch
+      are refused, never re-pitched.
 
   Everything is vectorised torch (sort, ``searchsorted``, masks): no per-key Python loop; the results are a
   function of the calls alone."""
 
-  def __init__(self, dim, slot_dims=(), pin_memory=True, dtype=torch.float32):
+  def __init__(self, dim, slot_dims=(), pin_memory=True, dtype=torch.float32, pitch=None):
     self.dim = int(dim)
-    if dtype != torch.float32 and dtype not in LOWP_DTYPES:
-      raise _bad(f'dtype must be torch.float32, torch.bfloat16 or torch.float16, got {dtype!r}')
-    self.dtype = dtype
     self.slot_dims = tuple(int(d) for d in slot_dims)
     if self.dim < 1 or any(d < 1 for d in self.slot_dims):
       raise _bad(f'dim and slot_dims must be >= 1, got {dim} and {list(slot_dims)}')
+    self.row_dtype, self.row_width, self.pitch = _row_layout(dtype, self.dim, pitch, 'HashSpillStore')
+    self.dtype = dtype
     self._pin = bool(pin_memory) and torch.cuda.is_available()
     self.clear()
 
   def clear(self):
     """Forget everything."""
-    self._data = self._arrays(HashExport.empty(0, self.dim, True, self.slot_dims, dtype=self.dtype))
+    self._data = self._arrays(HashExport.empty(0, self.dim, True, self.slot_dims, dtype=self.dtype, pitch=self.pitch))
 
   @staticmethod
   def _arrays(exp):
@@ -1396,8 +1455,8 @@ class HashSpillStore:
     n = exp.keys.numel()
     if exp.keys.dtype != torch.int64 or exp.keys.dim() != 1:
       raise _bad('put: exp.keys must be an int64 vector')
-    if exp.rows.dtype != self.dtype or tuple(exp.rows.shape) != (n, self.dim):
-      raise _bad(f'put: exp.rows must be {_dtype_name(self.dtype)} [{n}, {self.dim}], the store\'s own dtype (nothing '
+    if exp.rows.dtype != self.row_dtype or tuple(exp.rows.shape) != (n, self.row_width):
+      raise _bad(f'put: exp.rows must be {_rows_name(self)} [{n}, {self.row_width}], the store\'s own dtype (nothing '
                  f'is cast), got {exp.rows.dtype} {tuple(exp.rows.shape)}')
     if exp.last_seen is None or exp.freq is None:
       raise _bad('put: the export carries no last_seen / freq: a store keeps the keys of an expiring table')
@@ -1483,12 +1542,18 @@ class HashSpillStore:
     return self._export(self._data).variables(name)
 
   @classmethod
-  def from_variables(cls, name, d, pin_memory=True):
+  def from_variables(cls, name, d, pin_memory=True, dim=None):
     """The store a :meth:`variables` dict describes (:meth:`HashExport.from_variables`): dim and slot widths are
-    read from the tensors."""
+    read from the tensors.  ``dim``: needed for the uint8 rows of an 8-bit table, whose width is the pitch."""
     exp = HashExport.from_variables(name, d)
     if exp.rows.dim() != 2 or any(x.dim() != 2 for x in exp.slots):
       raise _bad('from_variables: rows and companions must be matrices')
+    if exp.rows.dtype == torch.uint8:
+      if dim is None:
+        raise _bad('from_variables: the rows are uint8 (an 8-bit table\'s): dim= is needed, their width is the pitch')
+      store = cls(dim, [x.shape[1] for x in exp.slots], pin_memory, dtype=QUANT8, pitch=exp.rows.shape[1])
+      store.put(exp)
+      return store
     store = cls(exp.rows.shape[1], [x.shape[1] for x in exp.slots], pin_memory, dtype=exp.rows.dtype)
     store.put(exp)
     return store
@@ -1671,16 +1736,20 @@ class _Plan:
   ``hbk_hash_insert_expiring_admit_n``.  ``cols[c]`` is table c's.  ``admit=False``: no table is taken as
   filtered (:meth:`HashTable.load`).  The 16-bit tables of each kind form groups of their own, after the fp32
   ones, and go through ``hbk_hash_insert_lowp_n``: ``dtypes[g]`` is group g's element codes, None for an fp32
-  group, whose calls are what they were."""
+  group, whose calls are what they were.  The 8-bit tables (``dtype='int8'``) form groups after those and go through
+  ``hbk_hash_insert_quant8_n``: ``pitches[g]`` is group g's row pitches in bytes, None for every other group."""
 
   def __init__(self, tables, admit=True):
     groups = {}
     for c, t in enumerate(tables):
-      groups.setdefault((t.dtype in LOWP_DTYPES, t.expiring, bool(admit and t.min_freq)), []).append(c)
+      kind = 2 if _is_quant8(t.dtype) else int(t.dtype in LOWP_DTYPES)
+      groups.setdefault((kind, t.expiring, bool(admit and t.min_freq)), []).append(c)
     self.cols = [None] * len(tables)
     self.groups = []   # (expiring, filtered, columns, expiry records, admission records)
     self.dtypes = []   # per group: None, or the int32 element codes of its 16-bit tables
-    for (lowp, expiring, filtered), members in sorted(groups.items()):
+    self.pitches = []  # per group: None, or the int32 row pitches of its 8-bit tables
+    for (kind, expiring, filtered), members in sorted(groups.items()):
+      lowp = kind == 1
       cols = (_lib.HashColumn * len(members))()
       expiry = (_lib.HashExpiry * len(members))() if expiring else None
       adm = (_lib.HashAdmission * len(members))() if filtered else None
@@ -1693,15 +1762,18 @@ class _Plan:
       self.groups.append((expiring, filtered, cols, expiry, adm))
       codes = [LOWP_DTYPES[tables[c].dtype] for c in members] if lowp else None
       self.dtypes.append((C.c_int32 * len(members))(*codes) if lowp else None)
+      self.pitches.append((C.c_int32 * len(members))(*[tables[c].pitch for c in members]) if kind == 2 else None)
 
   def launch(self, insert, stream):
     insert = 1 if insert else 0
     lib = _lib.lib()
     if not self.groups:
       _lib.check(lib.hbk_hash_insert_n(0, None, insert, stream))
-    for (expiring, filtered, cols, expiry, adm), dtypes in zip(self.groups, self.dtypes):
+    for (expiring, filtered, cols, expiry, adm), dtypes, pitches in zip(self.groups, self.dtypes, self.pitches):
       n = len(cols)
-      if dtypes is not None:
+      if pitches is not None:
+        _lib.check(lib.hbk_hash_insert_quant8_n(n, cols, expiry, adm, pitches, insert, stream))
+      elif dtypes is not None:
         _lib.check(lib.hbk_hash_insert_lowp_n(n, cols, expiry, adm, dtypes, insert, stream))
       elif expiring and filtered:
         _lib.check(lib.hbk_hash_insert_expiring_admit_n(n, cols, expiry, adm, insert, stream))
@@ -1787,6 +1859,9 @@ def same_device(tables):
 def require_fp32_tables(tables, what, why):
   """Refuses, by name, a 16-bit :class:`HashTable` where only fp32 rows are served."""
   for c, t in enumerate(tables):
+    if isinstance(t, HashTable) and _is_quant8(t.dtype):
+      raise _bad(f"{what}: table {c} is an 'int8' HashTable; 8-bit hash-keyed tables are served by HashGroupLookup "
+                 'alone: they have no sequence, sharded or feature-column form')
     if isinstance(t, HashTable) and t.dtype != torch.float32:
       raise _bad(f'{what}: table {c} is a {t.dtype} HashTable; {why}')
 
@@ -1853,13 +1928,25 @@ class HashGroupLookup:
   rebuilt after a rehash exactly as a ``GroupLookupGrad`` is.  The optimizer slots stay fp32.  Never hand
   ``hgl.lookup`` over 16-bit tables to a bare ``GroupLookupGrad`` with a non-zero ``apply_lr`` (see
   ``LowpLookupGrad``).
+
+  8-bit tables (``HashTable(..., dtype='int8')``): all tables of one object are 8-bit, a mix with another kind is
+  refused as above.  ``self.lookup`` is a :class:`hybridbackend_amd.embedding.Quant8GroupLookup` with buckets 0 over
+  the tables' dims and pitches, ``lane_codes`` and ``out_dtype`` are handed to it (they are refused over other tables),
+  a ``-1`` slot reads a zero row, ``max_norms`` is refused by name, and the step is ``Quant8LookupGrad``::
+
+      step = Quant8LookupGrad(hgl.lookup, row_accums=accums, rounding='nearest')
+      step(hgl.slots, grads, row_splits, apply_lr=lr, optimizer='rowwise_adagrad')
+
+  rebuilt after a rehash as above.  Never hand ``hgl.lookup`` over 8-bit tables to a bare ``GroupLookupGrad`` with a
+  non-zero ``apply_lr``.
   """
 
-  def __init__(self, tables, combiners='sum', max_norms=None, train=True):
+  def __init__(self, tables, combiners='sum', max_norms=None, train=True, lane_codes=None, out_dtype=None):
     self.tables = list(tables)
     same_device(self.tables)
     self.train = bool(train)
     self._combiners, self._max_norms = combiners, max_norms
+    self._lane_codes, self._out_dtype = lane_codes, out_dtype
     self.rebind()
 
   def rebind(self):
@@ -1869,11 +1956,23 @@ class HashGroupLookup:
     addresses changed: a ``GroupLookupGrad`` built on the old ``hgl.lookup`` must be rebuilt with the new slot
     tensors (the companions the rehash returned), and a captured graph must be captured again."""
     lowp = [t.dtype in LOWP_DTYPES for t in self.tables]
-    if any(lowp) and not all(lowp):
+    quant8 = [_is_quant8(t.dtype) for t in self.tables]
+    if (any(lowp) and not all(lowp)) or (any(quant8) and not all(quant8)):
       mixed = ', '.join(f'table {c}: {_dtype_name(t.dtype)}' for c, t in enumerate(self.tables))
-      raise _bad(f'HashGroupLookup: fp32 and 16-bit tables cannot share one lookup ({mixed}): translate them together '
-                 'with hash_translate, then look them up in two groups -- or build one HashGroupLookup per kind')
-    if any(lowp):
+      raise _bad(f'HashGroupLookup: fp32, 16-bit and 8-bit tables cannot share one lookup ({mixed}): translate them '
+                 'together with hash_translate, then look them up in one group per kind -- or build one '
+                 'HashGroupLookup per kind')
+    if not any(quant8) and (self._lane_codes is not None or self._out_dtype is not None):
+      raise _bad("HashGroupLookup: lane_codes and out_dtype belong to 8-bit tables (HashTable(dtype='int8')), got "
+                 f'lane_codes={self._lane_codes!r} and out_dtype={self._out_dtype!r} over other tables')
+    if any(quant8):
+      # (max_norms is refused there, by name)
+      from hybridbackend_amd.embedding.quant8 import Quant8GroupLookup   # pylint: disable=import-outside-toplevel
+      self.lookup = Quant8GroupLookup([t.table for t in self.tables], [t.dim for t in self.tables], buckets=None,
+                                      combiners=self._combiners, max_norms=self._max_norms,
+                                      lane_codes=self._lane_codes,
+                                      out_dtype=torch.float32 if self._out_dtype is None else self._out_dtype)
+    elif any(lowp):
       # (a clip is refused there, by name: it reads and the clipped step writes fp32 rows)
       from hybridbackend_amd.embedding.lowp import LowpGroupLookup   # pylint: disable=import-outside-toplevel
       self.lookup = LowpGroupLookup([t.table for t in self.tables], buckets=None, combiners=self._combiners,

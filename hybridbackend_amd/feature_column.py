@@ -80,6 +80,10 @@ class _HashColumn:
     self.table_args = dict(slab_size=int(slab_size), init_scale=float(init_scale), seed=int(seed),
                            expiring=bool(expiring), min_freq=int(min_freq), sketch_depth=sketch_depth,
                            sketch_width=sketch_width, sketch_seed=sketch_seed)
+    if isinstance(dtype, str) and dtype == 'int8':
+      raise _lib.InvalidArgumentError(
+        _lib.INVALID_ARGUMENT, f"{type(self).__name__}: column {key!r}: dtype='int8' is not served by the feature-column "
+        "layers; an 8-bit hash-keyed table is a HashTable(dtype='int8') behind a HashGroupLookup")
     if dtype != torch.float32:
       # (the default adds no argument: an fp32 column builds the table it always built; HashTable refuses an
       # unknown dtype, an odd dim and an fp16 init_scale above 65504 when the probe below is made)

@@ -1040,6 +1040,23 @@ int hbk_quant8_apply_slices_n(int32_t n_cols, const hbk_quant8_slices_column_t* 
                               float* const* slot0, float* const* slot1, const void* params, float lr,
                               const hbk_lowp_rounding_t* rounding, hbk_stream_t stream);
 
+/* HASH-KEYED 8-bit tables  hbk_hash_insert_quant8_n: hbk_hash_insert_lowp_n with the row pitches where that entry has
+ *   the element codes -- the find-or-insert of the four table kinds (exp and adm NULL or not, as there) over columns
+ *   whose `table` is a uint8 [slab_count * slab_size, pitch] table of the LAYOUT above.  pitches[c]: the bytes
+ *   between rows of column c, 0 = dim4 + 4; cols[c].table_pitch is not read.  The lane group that inserts a key
+ *   writes its whole row: QUANTISE with HBK_LOWP_ROUND_NEAREST over v_j = the fp32 start value of (key, seed, j,
+ *   init_scale) (hbk_hash_insert_n), the bytes dim .. dim4-1 zero, the scale at dim4 and every word behind it up to
+ *   the pitch zero -- bit for bit hbk_quant8_rows_n over the row hbk_hash_insert_n would have written; init_scale 0,
+ *   or any row whose amax is below 2^-100, is a zero row.  A row no key holds has unspecified bytes (all-zero bytes
+ *   are NOT a row: code 0 does not exist) and is never decoded: a slot of -1 reads as the forward's invalid row.
+ *   insert == 0, and the counting phase of a filtered table, write no row and are the launches of the fp32 entries.
+ *   A new symbol: the structs and hbk_version() are those of 0.2.0.  Refused before the first launch
+ *   (HBK_INVALID_ARGUMENT, the column named): everything the matching fp32 entry refuses (dim < 1 with a table among
+ *   it); with a table, dim > 256, or dim > 64 with dim % 4 != 0 (the bounds of the forward and the step); a pitch
+ *   that is no multiple of 4 or < dim4 + 4; a table not 4-byte aligned; pitches NULL with n_cols > 0.  n_cols == 0
+ *   answers OK.  The runs and sequence translates have no 8-bit form.  (Declared behind hbk_hash_insert_lowp_n, where
+ *   the records it takes are known.) */
+
 /* Gradients of REPLICATED tables across ranks, in their dense form (the reference's
  * TRAINABLE_REPLICATED_SMALL, training/gradient.py:131-141): every rank scatters its IndexedSlices into one
  * bucket, ONE allreduce sums the buckets, and each table's block of the bucket is then read back as
@@ -1725,6 +1742,12 @@ int hbk_hash_insert_lowp_n(int32_t n_cols, const hbk_hash_column_t* cols,
                            const hbk_hash_admission_t* adm /* NULL: no filter */,
                            const int32_t* table_dtypes     /* [n_cols]: HBK_LOWP_BF16 / HBK_LOWP_FP16 */,
                            int32_t insert, hbk_stream_t stream);
+/* the same over 8-bit tables ("8-bit tables" above, HASH-KEYED) */
+int hbk_hash_insert_quant8_n(int32_t n_cols, const hbk_hash_column_t* cols,
+                             const hbk_hash_expiry_t* exp    /* NULL: plain tables */,
+                             const hbk_hash_admission_t* adm /* NULL: no filter */,
+                             const int32_t* pitches          /* [n_cols]: bytes between rows; 0 = dim4 + 4 */,
+                             int32_t insert, hbk_stream_t stream);
 
 /* Keys that arrive as runs.  On the owner of a sharded hash table (hbk_sharded_set_hash_tables below) the ids of
  * one column are W separate arrays, one per requester, each with its own place for the answers.  Handing them
