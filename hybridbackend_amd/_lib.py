@@ -182,6 +182,17 @@ class Quant8LookupColumn(C.Structure):
               ('id_weights', C.c_void_p), ('out_dtype', C.c_int32), ('chunk_elems', C.c_int32)]
 
 
+ROWS_INT8 = 3   # hbk_sequence_lowbit_column_t.row_format beside LOWP_BF16 / LOWP_FP16
+
+
+class SequenceLowbitColumn(C.Structure):
+  """hbk_sequence_lowbit_column_t"""
+  _fields_ = [('table', C.c_void_p), ('pitch', C.c_int32), ('dim', C.c_int32), ('rows', C.c_int64),
+              ('ids', C.c_void_p), ('ids_dtype', C.c_int32), ('row_format', C.c_int32), ('n_ids', C.c_int64),
+              ('row_splits', C.c_void_p), ('n_segments', C.c_int64), ('bucket', C.c_int64),
+              ('divisor', C.c_int32), ('out_dtype', C.c_int32), ('out', C.c_void_p), ('out_stride', C.c_int64)]
+
+
 class Quant8SlicesColumn(C.Structure):
   """hbk_quant8_slices_column_t"""
   _fields_ = [('table', C.c_void_p), ('pitch', C.c_int32), ('dim', C.c_int32), ('rows', C.c_int64),
@@ -409,6 +420,8 @@ def _declare(l):
     'hbk_group_lookup_fwd_sequence': (C.c_int, [i32, vp, vp, vp, vp]),
     'hbk_sequence_row_grid_n': (C.c_int, [i32, vp, vp, vp]),
     'hbk_sequence_id_grid_n': (C.c_int, [i32, vp, vp, vp]),
+    'hbk_sequence_lookup_fwd_lowbit': (C.c_int, [i32, vp, vp, vp]),
+    'hbk_sequence_lowbit_lane_elems': (C.c_int32, [vp]),
     'hbk_sequence_pack_workspace_bytes': (sz, [i32, vp]),
     'hbk_sequence_pack_n': (C.c_int, [i32, vp, vp, vp, vp, sz, vp]),
     'hbk_expand_rows_n': (C.c_int, [i32, vp, vp, i32, i64, i64, vp]),

@@ -1084,17 +1084,31 @@ class SequenceFeatures(_TableLayer):
   16-bit hash columns (``HashSequenceEmbeddingColumn(dtype=)``, one dtype per layer): on one rank
   ``HashSequenceLookup`` + ``LowpSequenceLookupGrad``, on W > 1 ranks ``LowpShardedHashGroupLookup`` over the id grid
   or, with ``sharded_zero_padding``, the packed form; ``table_rounding`` / ``table_seed`` are the rounding of their
-  step, and ``max_norm`` on such a column is refused by name."""
+  step, and ``max_norm`` on such a column is refused by name.
+
+  ``table_dtype`` (``torch.bfloat16``, ``torch.float16`` or ``'int8'``; one rank, bucketed columns): the tables are
+  ``init``'s result rounded / quantised to nearest, the slots stay fp32, the forward is ``LowbitSequenceLookup`` -- one
+  fused launch, fp32 outputs or ``output_dtype`` (``torch.bfloat16`` / ``torch.float16``) -- and the step
+  ``LowbitSequenceLookupGrad`` with ``table_rounding`` / ``table_seed``; ``variables`` / ``save`` / ``restore`` carry
+  the low-bit tensors as :class:`DenseFeatures` does.  Refused by name before any allocation: W > 1, a hash-keyed
+  column, ``max_norm``, a dimension beyond 256 (64 when not a multiple of 4), and ``output_dtype`` without
+  ``table_dtype`` (over fp32 tables that is ``SequenceLookup(out_dtype=)``)."""
 
   def __init__(self, columns, device, coll=None, batch_size=0, init=None,
                initial_accumulator_value=None, optimizer=None, adam=None, ftrl=None, train=True,
                rowwise_adagrad=None, sharded_zero_padding=False, aggregate_replicated=False,
-               replicated_scale=None, table_rounding='nearest', table_seed=0):
+               replicated_scale=None, table_rounding='nearest', table_seed=0, table_dtype=None, output_dtype=None):
     from hybridbackend_amd.embedding.hash_sequence import HashSequenceLookup
     from hybridbackend_amd.embedding.sequence import SequenceLookup, SequenceLookupGrad
+    self.table_dtype, self.output_dtype = table_dtype, output_dtype
+    if table_dtype is not None:
+      self._check_lowbit(columns, coll, table_dtype, output_dtype, table_rounding, table_seed)
+    elif output_dtype is not None:
+      raise _bad(f'SequenceFeatures(output_dtype={output_dtype}) needs table_dtype: the fused 16-bit-output forward '
+                 'reads low-bit tables; over fp32 tables it is SequenceLookup(out_dtype=)')
     self._init_tables(columns, device, coll, batch_size, init, initial_accumulator_value, optimizer,
-                      adam, ftrl, train, rowwise_adagrad, table_rounding=table_rounding, table_seed=table_seed,
-                      what='SequenceFeatures')
+                      adam, ftrl, train, rowwise_adagrad, table_dtype=table_dtype, table_rounding=table_rounding,
+                      table_seed=table_seed, what='SequenceFeatures')
     self._init_replica(aggregate_replicated, replicated_scale, 'SequenceFeatures')
     self.sharded_zero_padding = bool(sharded_zero_padding)
     for c in self._hash:
@@ -1118,7 +1132,17 @@ class SequenceFeatures(_TableLayer):
     pick = lambda idx, xs: [xs[c] for c in idx]   # noqa: E731
     attr = lambda idx, name: [getattr(self.columns[c], name) for c in idx]   # noqa: E731
     self._lookup = self._grad = self._sharded = None
-    if self._rep:
+    if self._rep and table_dtype is not None:
+      # low-bit tables (one rank, bucketed columns: checked above): the fused low-bit forward and the step behind it
+      from hybridbackend_amd.embedding.sequence_lowbit import LowbitSequenceLookup, LowbitSequenceLookupGrad   # pylint: disable=import-outside-toplevel
+      self._lookup = LowbitSequenceLookup(pick(self._rep, self.weights),
+                                          attr(self._rep, 'dimension') if table_dtype == 'int8' else None,
+                                          attr(self._rep, 'num_buckets'), max_lens=attr(self._rep, 'max_len'),
+                                          pad_ids=attr(self._rep, 'pad_id'), out_dtype=output_dtype or torch.float32)
+      self._grad = LowbitSequenceLookupGrad(
+        self._lookup, pick(self._rep, self.accums) if self.accums is not None else None,
+        rounding=table_rounding, seed=table_seed, **self._two_slot_kw(self._rep))
+    elif self._rep:
       self._lookup = SequenceLookup(pick(self._rep, self.weights), attr(self._rep, 'num_buckets'),
                                     max_lens=attr(self._rep, 'max_len'), pad_ids=attr(self._rep, 'pad_id'),
                                     max_norms=attr(self._rep, 'max_norm'))
@@ -1140,6 +1164,32 @@ class SequenceFeatures(_TableLayer):
                                              pad_ids=attr(self._hash, 'pad_id'),
                                              max_norms=attr(self._hash, 'max_norm'), train=self.train)
       self._rebuild_hash_grad()
+
+  @staticmethod
+  def _check_lowbit(columns, coll, table_dtype, output_dtype, table_rounding, table_seed):
+    """Everything ``table_dtype`` refuses, before any table is allocated (``DenseFeatures._check_lowp``'s rules for
+    the columns of this layer)."""
+    from hybridbackend_amd.embedding.lowp import check_rounding   # pylint: disable=import-outside-toplevel
+    int8 = isinstance(table_dtype, str) and table_dtype == 'int8'
+    if not int8 and table_dtype not in (torch.bfloat16, torch.float16):
+      raise _bad("SequenceFeatures(table_dtype=): None, torch.bfloat16, torch.float16 or 'int8', got "
+                 f'{table_dtype!r}')
+    if output_dtype not in (None, torch.bfloat16, torch.float16):
+      raise _bad(f'SequenceFeatures(output_dtype=): None, torch.bfloat16 or torch.float16, got {output_dtype!r}')
+    what = f'SequenceFeatures(table_dtype={table_dtype})'
+    check_rounding(table_rounding, table_seed, [] if int8 else [table_dtype], 'SequenceFeatures(table_dtype=)')
+    if coll is not None and coll.world_size > 1:
+      raise _bad(f'{what}: low-bit sequence tables are kept on one rank only, the layer spans {coll.world_size} '
+                 '(the sharded sequence form reads fp32 tables)')
+    for col in columns:
+      if _is_hash(col):
+        raise _bad(f'{what}: column {col.key!r} is hash-keyed; a hash sequence column names its own dtype '
+                   '(HashSequenceEmbeddingColumn(dtype=))')
+      if col.max_norm is not None:
+        raise _bad(f'{what}: column {col.key!r} has max_norm; the clip reads and the clipped step writes fp32 rows')
+      if col.dimension > 256 or (col.dimension % 4 != 0 and col.dimension > 64):
+        raise _bad(f'{what}: column {col.key!r}: dimension {col.dimension} is beyond what the low-bit sequence '
+                   'forward and the step take (at most 256 when a multiple of 4, 64 otherwise)')
 
   def _rebuild_hash_grad(self):
     from hybridbackend_amd.embedding.sequence import SequenceLookupGrad

@@ -1170,6 +1170,61 @@ int hbk_sequence_row_grid_n(int32_t n_cols, const hbk_lookup_column_t* cols,
  * Detected by the presence of the symbol; the structs and the version are those of 0.2.0. */
 int hbk_sequence_id_grid_n(int32_t n_cols, const hbk_lookup_column_t* cols,
                            const hbk_sequence_t* seq, hbk_stream_t stream);
+/* Sequence lookups over LOW-BIT tables, fused: hbk_group_lookup_fwd_sequence -- the same positions, pad rule, bucket
+ * and divisor, grid words, lengths, truncation and out-of-range row splits, by the same code -- over 16-bit tables
+ * ("Low-precision tables") or 8-bit tables ("8-bit tables": LAYOUT and DECODE), into fp32, bf16 or fp16 outputs:
+ *     out[b, t, :] = (out_dtype) upcast_or_decode(table[g(p) / divisor, :])       (+0 where nothing is looked up)
+ * A lookup sums nothing: a 16-bit element is upcast exactly, an 8-bit one is ((float)code - 128) * scale, and a
+ * 16-bit output is that value rounded ONCE to nearest even -- bit for bit torch's cast of the dequantised row.
+ * seq is hbk_sequence_t as above (lengths and row_grid may be NULL); there is no max_norm here.
+ *   row_format  HBK_LOWP_BF16 | HBK_LOWP_FP16: table is [rows, dim] 16-bit elements, `pitch` BYTES between rows
+ *                 (0 = 2 * dim; even and >= 2 * dim), 2-byte aligned;
+ *               HBK_ROWS_INT8: table is the uint8 [rows, pitch] of "8-bit tables" (0 = dim4 + 4), 4-byte aligned.
+ *   out_dtype   HBK_QUANT8_OUT_FP32 | HBK_LOWP_BF16 | HBK_LOWP_FP16; out is [B, T, dim] of it, a sample's T rows
+ *               contiguous; out_stride counts ELEMENTS between samples (0 = T * dim, else >= T * dim).
+ * GEOMETRY  a lane owns the W elements of ONE output store, a row pow2(ceil(dim / W)) adjacent lanes:
+ *     W = 8   16-bit outputs, dim % 8 == 0, out and its sample stride on 16 bytes: one 16-byte store.  A 16-bit row
+ *             chunk is one 16-byte load (table and pitch on 16) or two 8-byte loads (on 8); 8 codes are one 8-byte
+ *             load (table and pitch on 8) or two 4-byte loads.
+ *     W = 4   fp32 outputs, dim % 4 == 0, out and its stride on 16 bytes: one 16-byte store; or 16-bit outputs that
+ *             cannot take W = 8, dim % 4 == 0, out and its stride on 8 bytes: one 8-byte store.  A 16-bit chunk is one
+ *             8-byte load (table and pitch on 8), 4 codes one 4-byte load.
+ *     W = 1   everything else: element-sized loads and stores that touch no neighbouring byte; dim <= 64.
+ *   dim <= 256 at W >= 4.  An 8-bit row's scale word is read by every lane of the row.  A wave takes 4 * (64 / lanes
+ *   per row) consecutive positions; ids and row splits travel by shuffle (no LDS); every row load of a lane is issued
+ *   before its first store and a row stays packed (its 16-bit words, or its codes and scale) until it is stored; grid
+ *   words and outputs are stored non-temporally.  One launch per 64 columns and kind (table width, W, output size).
+ *   No workspace, no atomics, no host read: capturable.
+ * hbk_sequence_lowbit_lane_elems(col): host only, no launch: the W a bound column gets -- 8, 4 or 1 -- from dim,
+ *   table, pitch, row_format, out, out_stride and out_dtype; 0 for a NULL column or an unknown format / out_dtype.
+ * Refused (HBK_INVALID_ARGUMENT, the column named) before any device work: an unknown row_format or out_dtype; an
+ *   8-bit pitch that is no multiple of 4 or < round_up(dim, 4) + 4, a 16-bit pitch that is odd or < 2 * dim; a table
+ *   off 4 bytes (8-bit) or 2 bytes (16-bit); out off its element; dim outside [1, 256], or > 64 at W = 1; max_len
+ *   < 1; B * T >= 2^31; an out_stride below T * dim; negative sizes, ids that are not int32 / int64, bucket < 0,
+ *   divisor < 1, n_segments != n_ids without row_splits, a NULL buffer of a column with samples.  A column with no
+ *   samples launches nothing; n_cols == 0 answers OK.  New symbols: the structs above and the version are those of
+ *   0.2.0. */
+#define HBK_ROWS_INT8 3          /* hbk_sequence_lowbit_column_t.row_format beside HBK_LOWP_BF16 / HBK_LOWP_FP16 */
+typedef struct {
+  const void* table;         /* device: 16-bit [rows, dim] or uint8 [rows, pitch] */
+  int32_t pitch;             /* BYTES between rows; 0 = 2 * dim (16-bit) / dim4 + 4 (8-bit) */
+  int32_t dim;
+  int64_t rows;
+  const void* ids;           /* device [n_ids] */
+  int32_t ids_dtype;         /* HBK_INT32 | HBK_INT64 */
+  int32_t row_format;        /* HBK_LOWP_BF16 | HBK_LOWP_FP16 | HBK_ROWS_INT8 */
+  int64_t n_ids;
+  const int32_t* row_splits; /* device [n_segments + 1] or NULL (one id per sample) */
+  int64_t n_segments;        /* B; == n_ids when row_splits == NULL */
+  int64_t bucket;            /* 0 = ids are row numbers already */
+  int32_t divisor;           /* >= 1 */
+  int32_t out_dtype;         /* HBK_QUANT8_OUT_FP32 | HBK_LOWP_BF16 | HBK_LOWP_FP16 */
+  void* out;                 /* device [B, T, dim] of out_dtype elements */
+  int64_t out_stride;        /* ELEMENTS between samples; 0 = T * dim */
+} hbk_sequence_lowbit_column_t;
+int hbk_sequence_lookup_fwd_lowbit(int32_t n_cols, const hbk_sequence_lowbit_column_t* cols,
+                                   const hbk_sequence_t* seq, hbk_stream_t stream);
+int32_t hbk_sequence_lowbit_lane_elems(const hbk_sequence_lowbit_column_t* col);
 /* The PACKED form of a zero-padded sequence column: what a sharded sequence column WITHOUT a pad id hands the
  * sharded step.  Neither grid above can say "nothing" to that step (it bucketizes a -1 into row bucket - 1, and
  * among raw ids every int64 is a key), but the step takes ragged columns, and with combiner sum an empty segment
